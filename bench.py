@@ -6,10 +6,15 @@ One "step" = one pass of the hot path over one batch: the full 50-step DDIM deno
 batch of 4 synthetic 512x512 masked-text crops (latents 4x64x64, glyph context [4,577,1024]) with
 random-init SD2-inpainting-shaped weights, bf16 MFMA compute, inputs resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N>1: launched by torch.distributed.run, one rank per GPU; images are independent so the batch is
 replicated per rank (weak scaling, no data-path collective); RCCL is used only for the barrier and
 the max-over-ranks of the elapsed time.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K passes and prints the line.  --dump-outputs DIR writes what
+the last timed pass returned (rank 0's final latents) as DIR/latents.npy, float32.  --full adds the legs
+beyond the headline figure: the hipEvent-bracketed roofline pass, the CPU baseline and the secondary
+configs (--no-profile / --no-cpu-baseline / --no-secondary leave one of them out).
 """
 import argparse
 import ctypes
@@ -201,13 +206,23 @@ def main():
     ap.add_argument("--latent", type=int, default=64, help="latent side (64 = 512 px)")
     ap.add_argument("--denoise-steps", type=int, default=50)
     ap.add_argument("--micro-batches", type=int, default=1, help="independent chains of the batch run concurrently on separate streams")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the one-rep timings of the other BASELINE configs (cfg3, cfg5, train step, B=1 DDPM-150)")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--profile-csv", default="", help="write one row per kernel launch of the profiled pass")
+    ap.add_argument("--full", action="store_true", help="after the headline: the profiled roofline pass, the CPU baseline and the secondary configs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed pass's final latents (rank 0) as DIR/latents.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the timings of the other BASELINE configs (cfg3, cfg5, train step, B=1 DDPM-150)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the profiled roofline pass")
+    ap.add_argument("--profile-csv", default="", help="with --full: write one row per kernel launch of the profiled pass")
     ap.add_argument("--mode", choices=("denoise", "train"), default="denoise",
                     help="denoise = BASELINE configs[1] (the headline metric); train = configs[3] DDP training step (scripts/bench_train.py)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:                         # a plain run does only what the headline figure needs
+        args.no_profile = args.no_cpu_baseline = args.no_secondary = True
+    if args.profile_csv and args.no_profile:
+        ap.error("--profile-csv needs the profiled pass: add --full (without --no-profile)")
+    if args.mode == "train" and (args.full or args.dump_outputs):
+        ap.error("--full and --dump-outputs apply to the denoise benchmark")
     # ---- launcher contract: `--gpus N` is the number of ranks.  Under torchrun WORLD_SIZE must agree; a bare
     # `python bench.py --gpus N` (N > 1) starts the N ranks itself as a CHILD torchrun - before this process has touched
     # the GPU (never exec from a process that initialised HIP) - and forwards the child's output and exit code.
@@ -300,6 +315,10 @@ def main():
             dist.destroy_process_group()
         raise SystemExit(1)
     ms_per_step = 1e3 * elapsed / args.steps
+    if rank == 0 and args.dump_outputs:             # `out` = what the last timed pass returned: denoise()'s final latents, [B, 4, h, w] fp32
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), out.detach().float().cpu().numpy())
 
     # executed work: the upsampler convs run phase-decomposed (4/9 of the reference formulation's multiply-adds)
     loop_flops = T * unet_flops(unet.config, B, hw, hw, 577, True, phase_upsample=True) + context_kv_flops(unet.config, B, 577)

@@ -1,4 +1,4 @@
-"""Summarise a bench.py --profile-csv dump: per (kernel class, shape) totals, TF/s, share of the pass."""
+"""Summarise a bench.py --full --profile-csv dump: per (kernel class, shape) totals, TF/s, share of the pass."""
 import collections
 import csv
 import sys

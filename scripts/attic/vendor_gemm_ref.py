@@ -1,7 +1,7 @@
 """Reference point for the GEMM plans: every distinct conv/linear GEMM shape of a profiled UNet pass, timed (a) through
 this library's automatic plan (implicit-GEMM gather included) and (b) as a plain [M,K]x[K,N] bf16 torch.matmul (the
 vendor BLAS: hipBLASLt / rocBLAS) on a pre-materialised matrix of the same size -- i.e. the vendor number has no im2col,
-bias, residual or type conversion in it.  Input: the CSV written by `bench.py --profile-csv`.  Development tool."""
+bias, residual or type conversion in it.  Input: the CSV written by `bench.py --full --profile-csv`.  Development tool."""
 import csv
 import math
 import re

@@ -4,7 +4,7 @@
 mkdir -p gpurun_out
 : > gpurun_out/bench5.txt
 for i in 1 2 3 4 5; do
-  extra="--no-secondary --no-cpu-baseline"; [ $i = 1 ] && extra=""
+  extra="--full --no-secondary --no-cpu-baseline"; [ $i = 1 ] && extra="--full"
   python3 bench.py --gpus 1 --steps 20 --warmup 5 $extra > gpurun_out/bench5_$i.json 2> gpurun_out/bench5_$i.err; rc=$?
   python3 - <<PY >> gpurun_out/bench5.txt
 import json

@@ -1,5 +1,5 @@
 """Times every distinct conv/linear GEMM shape of a profiled UNet pass under forced (tile, split-K) plans and
-prints the best next to the automatic plan's choice.  Input: the CSV written by bench.py --profile-csv."""
+prints the best next to the automatic plan's choice.  Input: the CSV written by bench.py --full --profile-csv."""
 import csv
 import math
 import re
