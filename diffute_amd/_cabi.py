@@ -67,6 +67,12 @@ class SkinnyDesc(ctypes.Structure):
                 ("res", c_void_p), ("ldres", c_int), ("out", c_void_p), ("ldo", c_int), ("colstats", c_void_p), ("force_S", c_int), ("timing", c_void_p), ("dbg", c_int)]
 
 
+class DpmCoefs(ctypes.Structure):
+    """dmx_dpm_coefs (include/diffute_hip.h): the host-side scalars of one DPM-Solver++ step, passed by value."""
+    _fields_ = [("alpha_s0", c_float), ("sigma_s0", c_float), ("c_x", c_float), ("c_m0", c_float), ("c_d1", c_float), ("c_d2", c_float),
+                ("inv_r0", c_float), ("inv_r1", c_float), ("r0_over_r01", c_float), ("inv_r01", c_float)]
+
+
 class ViTConfig(ctypes.Structure):
     _fields_ = [("image_size", c_int), ("patch_size", c_int), ("num_channels", c_int), ("hidden_size", c_int), ("num_layers", c_int),
                 ("num_heads", c_int), ("intermediate_size", c_int), ("qkv_bias", c_int), ("layer_norm_eps", c_float)]
@@ -159,6 +165,7 @@ _PROTOS = {
     "dmx_nchw_f32_to_nhwc_bf16": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "dmx_sched_step_ddim": (c_int, [_P, _P, _P, _P, c_size_t, c_float, c_float, c_float, c_float, c_float, c_int, _P]),
     "dmx_sched_step_ddpm": (c_int, [_P, _P, _P, _P, c_size_t, c_float, c_float, c_float, c_float, c_float, c_int, _P]),
+    "dmx_sched_step_dpmpp": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t, c_int, DpmCoefs, c_int, _P]),
     "dmx_sched_add_noise": (c_int, [_P, _P, _P, _P, _P, c_int, c_size_t, _P]),
     "dmx_sched_get_velocity": (c_int, [_P, _P, _P, _P, _P, c_int, c_size_t, _P]),
     "dmx_gaussian_sample": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, _P]),

@@ -376,6 +376,15 @@ extern "C" int dmx_sched_step_ddpm(const float* sample, const float* model_outpu
   return dmx_sched_ddpm_launch(sample, model_output, noise, prev_sample, n, sqrt_beta_prod_t, sqrt_alpha_prod_t, coef_x0, coef_xt,
                                sigma, v_prediction, (hipStream_t)stream);
 }
+static bool dmx_overlap(const float* a, const float* b, size_t n) { return a && b && a < b + n && b < a + n; }
+extern "C" int dmx_sched_step_dpmpp(const float* sample, const float* model_output, const float* m1, const float* m2, float* x0_out,
+                                    float* prev_sample, size_t n, int order, dmx_dpm_coefs coefs, int v_prediction, dmx_stream_t stream) {
+  DMX_REQUIRE(sample && model_output && x0_out && prev_sample, "sched_step_dpmpp: null argument");
+  DMX_REQUIRE(order >= 1 && order <= 3, "sched_step_dpmpp: order %d (1, 2 or 3)", order);
+  DMX_REQUIRE((order < 2 || m1) && (order < 3 || m2), "sched_step_dpmpp: order %d needs the previous %d data prediction(s)", order, order - 1);
+  DMX_REQUIRE(!dmx_overlap(x0_out, m1, n) && !dmx_overlap(x0_out, m2, n) && !dmx_overlap(x0_out, prev_sample, n), "sched_step_dpmpp: x0_out overlaps m1, m2 or prev_sample");
+  return dmx_sched_dpmpp_launch(sample, model_output, m1, m2, x0_out, prev_sample, n, order, coefs, v_prediction, (hipStream_t)stream);
+}
 extern "C" int dmx_sched_add_noise(const float* x0, const float* noise, const float* sa, const float* sb, float* out, int B, size_t per, dmx_stream_t stream) {
   DMX_REQUIRE(x0 && noise && sa && sb && out, "sched_add_noise: null argument");
   return dmx_add_noise_launch(x0, noise, sa, sb, out, B, per, 0, (hipStream_t)stream);

@@ -406,6 +406,9 @@ int dmx_sched_ddim_launch(const float* x, const float* eps, const float* noise, 
                           float sqrt_bt, float sqrt_at, float sqrt_ap, float dir_coef, float std, int vpred, hipStream_t stream);
 int dmx_sched_ddpm_launch(const float* x, const float* eps, const float* noise, float* out, size_t n,
                           float sqrt_bt, float sqrt_at, float c0, float c1, float sigma, int vpred, hipStream_t stream);
+struct dmx_dpm_coefs;                                  // include/diffute_hip.h
+int dmx_sched_dpmpp_launch(const float* x, const float* eps, const float* m1, const float* m2, float* x0_out, float* out, size_t n,
+                           int order, const dmx_dpm_coefs& c, int vpred, hipStream_t stream);
 int dmx_add_noise_launch(const float* x0, const float* noise, const float* sa, const float* sb, float* out,
                          int B, size_t per, int velocity, hipStream_t stream);
 int dmx_gaussian_sample_launch(const float* moments, const float* noise, float* out, int B, int C, int HW, float scale, hipStream_t stream);

@@ -2,8 +2,10 @@
 // Compiled with -ffp-contract=off and written with explicit _rn ops in the op order of
 // diffusers' DDIMScheduler.step / DDPMScheduler.step so results are bit-identical to the
 // fp32 CPU evaluation of the same formulas (scalar coefficients are computed on the host).
+// DPMSolverMultistepScheduler.step likewise (diffute_amd/schedulers.py step_plan: one coefficient struct per step).
 #include "common.h"
 #include "kernels.h"
+#include "../../include/diffute_hip.h"
 
 // DDIM: x0 = (x - sqrt(1-abar_t)*eps)/sqrt(abar_t); prev = sqrt(abar_p)*x0 + dir*eps (+ std*noise)
 __global__ __launch_bounds__(256) void dmx_sched_ddim_kernel(const float* x, const float* eps, const float* noise, float* out, size_t n,
@@ -91,4 +93,70 @@ int dmx_gaussian_sample_launch(const float* moments, const float* noise, float* 
   int blocks = (int)((n + 255) / 256); if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(dmx_gaussian_sample_kernel, dim3(blocks), dim3(256), 0, stream, moments, noise, out, B, C, HW, scale);
   return dmx_check_launch("dmx_gaussian_sample_kernel");
+}
+
+// DPM-Solver++ multistep (Lu et al. 2022, Alg. 2; DPMSolverMultistepScheduler.step of diffusers >=0.15), orders 1-3.  Per element:
+//   m0 = (x - sigma_s0*eps)/alpha_s0  (eps)  |  alpha_s0*x - sigma_s0*v  (v_prediction)      -> x0_out (the caller's history)
+//   order 1: prev = c_x*x - c_m0*m0
+//   order 2: D1 = inv_r0*(m0 - m1);                                              prev = c_x*x - c_m0*m0 + c_d1*D1
+//   order 3: D1_0 = inv_r0*(m0 - m1), D1_1 = inv_r1*(m1 - m2), D1 = D1_0 + w*(D1_0 - D1_1), D2 = inv_r01*(D1_0 - D1_1);
+//            prev = c_x*x - c_m0*m0 + c_d1*D1 - c_d2*D2
+// c_d1 carries the sign of its term (midpoint: -(0.5*c_m0); fsub(a, b*c) == fadd(a, (-b)*c) exactly in round-to-nearest).
+// prev may alias x: every element is read before it is written, by the same thread.
+__device__ __forceinline__ float dpm_elem(float x, float e, float m1, float m2, float& m0, int order, const dmx_dpm_coefs& c, int vpred) {
+  m0 = !vpred ? __fdiv_rn(__fsub_rn(x, __fmul_rn(c.sigma_s0, e)), c.alpha_s0)
+              : __fsub_rn(__fmul_rn(c.alpha_s0, x), __fmul_rn(c.sigma_s0, e));
+  float prev = __fsub_rn(__fmul_rn(c.c_x, x), __fmul_rn(c.c_m0, m0));
+  if (order == 2) {
+    const float d1 = __fmul_rn(c.inv_r0, __fsub_rn(m0, m1));
+    prev = __fadd_rn(prev, __fmul_rn(c.c_d1, d1));
+  } else if (order == 3) {
+    const float d10 = __fmul_rn(c.inv_r0, __fsub_rn(m0, m1));
+    const float d11 = __fmul_rn(c.inv_r1, __fsub_rn(m1, m2));
+    const float dd = __fsub_rn(d10, d11);
+    const float d1 = __fadd_rn(d10, __fmul_rn(c.r0_over_r01, dd));
+    const float d2 = __fmul_rn(c.inv_r01, dd);
+    prev = __fsub_rn(__fadd_rn(prev, __fmul_rn(c.c_d1, d1)), __fmul_rn(c.c_d2, d2));
+  }
+  return prev;
+}
+
+// VEC: every pointer is 16-byte aligned; float4 over the first n/4*4 elements, the n % 4 tail by the first threads of block 0
+template <bool VEC>
+__global__ __launch_bounds__(256) void dmx_sched_dpmpp_kernel(const float* x, const float* eps, const float* m1, const float* m2, float* x0_out,
+                                                              float* out, size_t n, int order, dmx_dpm_coefs c, int vpred) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  size_t done = 0;
+  if (VEC) {
+    const size_t n4 = n / 4;
+    for (size_t i = tid; i < n4; i += stride) {
+      const float4 xv = reinterpret_cast<const float4*>(x)[i], ev = reinterpret_cast<const float4*>(eps)[i];
+      const float4 a = order >= 2 ? reinterpret_cast<const float4*>(m1)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 b = order >= 3 ? reinterpret_cast<const float4*>(m2)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 m0, p;
+      p.x = dpm_elem(xv.x, ev.x, a.x, b.x, m0.x, order, c, vpred);
+      p.y = dpm_elem(xv.y, ev.y, a.y, b.y, m0.y, order, c, vpred);
+      p.z = dpm_elem(xv.z, ev.z, a.z, b.z, m0.z, order, c, vpred);
+      p.w = dpm_elem(xv.w, ev.w, a.w, b.w, m0.w, order, c, vpred);
+      reinterpret_cast<float4*>(x0_out)[i] = m0;
+      reinterpret_cast<float4*>(out)[i] = p;
+    }
+    done = n4 * 4;
+  }
+  for (size_t i = done + tid; i < n; i += stride) {
+    float m0;
+    const float p = dpm_elem(x[i], eps[i], order >= 2 ? m1[i] : 0.f, order >= 3 ? m2[i] : 0.f, m0, order, c, vpred);
+    x0_out[i] = m0;
+    out[i] = p;
+  }
+}
+int dmx_sched_dpmpp_launch(const float* x, const float* eps, const float* m1, const float* m2, float* x0_out, float* out, size_t n,
+                           int order, const dmx_dpm_coefs& c, int vpred, hipStream_t stream) {
+  auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  const bool vec = a16(x) && a16(eps) && a16(x0_out) && a16(out) && (order < 2 || a16(m1)) && (order < 3 || a16(m2));
+  const size_t work = vec ? (n + 3) / 4 : n;
+  int blocks = (int)((work + 255) / 256); if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
+  if (vec) hipLaunchKernelGGL(dmx_sched_dpmpp_kernel<true>, dim3(blocks), dim3(256), 0, stream, x, eps, m1, m2, x0_out, out, n, order, c, vpred);
+  else hipLaunchKernelGGL(dmx_sched_dpmpp_kernel<false>, dim3(blocks), dim3(256), 0, stream, x, eps, m1, m2, x0_out, out, n, order, c, vpred);
+  return dmx_check_launch("dmx_sched_dpmpp_kernel");
 }

@@ -1,14 +1,15 @@
 """The reference's denoise loop (app.ipynb:796-816) driven through the C-ABI.
 
 `denoise()` is the hot path BASELINE.json names: per step one `dmx_unet_forward` (which fuses
-torch.cat([latents, mask, masked_image_latents], 1)) and one scheduler-step kernel.  The glyph
+torch.cat([latents, mask, masked_image_latents], 1)) and one scheduler-step kernel (DDPM, DDIM or
+DPM-Solver++; the latter keeps its multistep history in fixed per-chain buffers).  The glyph
 context K/V are projected once per image, timesteps live on the device, nothing synchronises
 with the host inside the loop.
 """
 import torch
 
 from . import _cabi
-from .schedulers import DDIMScheduler, DDPMScheduler
+from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
 
 
 _SIDE = {}
@@ -32,7 +33,7 @@ def mask_to_latent(mask, vae_scale_factor=8):
 class _Run:
     """One micro-batch of the denoise loop: its own stream, UNet execution slot and fixed-address buffers."""
 
-    def __init__(self, unet, scheduler, latents, mask, mlat, ctx, slot, stream, use_graph, temb_table=None):
+    def __init__(self, unet, scheduler, latents, mask, mlat, ctx, slot, stream, use_graph, temb_table=None, n_hist=0):
         self.unet, self.sched, self.slot, self.stream, self.use_graph = unet, scheduler, slot, stream, use_graph
         self.temb_table = temb_table
         with torch.cuda.stream(stream):
@@ -40,6 +41,8 @@ class _Run:
             self.m = mask.to(torch.float32).contiguous()
             self.ml = mlat.to(torch.float32).contiguous()
             self.eps = torch.empty_like(self.x)
+            # DPM-Solver++: the data predictions of the last solver_order steps; step i writes hist[i % n], reads hist[(i-1) % n], hist[(i-2) % n]
+            self.hist = [torch.empty_like(self.x) for _ in range(n_hist)]
             self.t_cur = torch.empty(1, dtype=torch.int64, device=self.x.device)   # fixed address: the captured graph reads it
             self.step_idx = torch.zeros(1, dtype=torch.int32, device=self.x.device)   # likewise: the row of temb_table this step fetches
             unet.set_context(ctx, slot=slot)
@@ -57,7 +60,14 @@ class _Run:
                 self.t_cur.copy_(ts_dev[0][i:i + 1], non_blocking=True)
                 self.unet.forward_parts([x, self.m, self.ml], self.t_cur, out=eps, graph=self.use_graph, slot=self.slot)
             # the update is elementwise, so prev_sample overwrites the sample in place (stable pointers for the graph)
-            if is_ddim:
+            if self.hist:
+                order, c = coefs
+                k = len(self.hist)
+                m1 = self.hist[(i - 1) % k] if order >= 2 else None
+                m2 = self.hist[(i - 2) % k] if order >= 3 else None
+                _cabi.check(lib.dmx_sched_step_dpmpp(_cabi.ptr(x), _cabi.ptr(eps), _cabi.ptr(m1), _cabi.ptr(m2), _cabi.ptr(self.hist[i % k]),
+                                                     _cabi.ptr(x), x.numel(), order, c, vpred, st), "sched_step_dpmpp")
+            elif is_ddim:
                 sbt, sat, sap, dirc, std = coefs
                 _cabi.check(lib.dmx_sched_step_ddim(_cabi.ptr(x), _cabi.ptr(eps), _cabi.ptr(noise), _cabi.ptr(x), x.numel(),
                                                     sbt, sat, sap, dirc, std, vpred, st), "sched_step_ddim")
@@ -78,6 +88,8 @@ def denoise(unet, scheduler, latents, mask, masked_image_latents, encoder_hidden
     with its own captured graph: one chain's kernels fill the CUs the other chain's small / draining kernels
     leave idle.  Results are identical to micro_batches=1 up to per-kernel tile-plan rounding."""
     _cabi.require_cuda(latents, mask, masked_image_latents, encoder_hidden_states)
+    if isinstance(scheduler, DPMSolverMultistepScheduler) and (variance_noise is not None or eta != 0):
+        raise ValueError("DPMSolverMultistepScheduler is deterministic: no variance_noise, eta = 0")
     _cabi.poll_device_error()            # what a kernel of an EARLIER pass raised (no sync; include/diffute_hip.h dmx_device_error)
     unet._ensure_packed()
     scheduler.set_timesteps(int(num_inference_steps))
@@ -110,13 +122,18 @@ def denoise(unet, scheduler, latents, mask, masked_image_latents, encoder_hidden
 def _denoise_enqueue(unet, scheduler, bounds, streams, main, n, latents, mask, masked_image_latents, encoder_hidden_states,
                      ts_host, ts_dev, temb_table, is_ddim, vpred, eta, variance_noise, callback, use_graph):
     runs = []
+    dpm = scheduler._plan if isinstance(scheduler, DPMSolverMultistepScheduler) else None
+    n_hist = scheduler.config.solver_order if dpm is not None else 0
     for j, (lo, hi) in enumerate(bounds):
         streams[j].wait_stream(main)
         runs.append(_Run(unet, scheduler, latents[lo:hi], mask[lo:hi], masked_image_latents[lo:hi],
-                         encoder_hidden_states[lo:hi].contiguous(), j, streams[j], use_graph, temb_table))
+                         encoder_hidden_states[lo:hi].contiguous(), j, streams[j], use_graph, temb_table, n_hist))
     for i, t in enumerate(ts_host):
-        coefs = scheduler.step_coefficients(t, eta) if is_ddim else scheduler.step_coefficients(t)
-        need_noise = (eta > 0) if is_ddim else (t > 0)
+        if dpm is not None:
+            coefs, need_noise = dpm[i], False
+        else:
+            coefs = scheduler.step_coefficients(t, eta) if is_ddim else scheduler.step_coefficients(t)
+            need_noise = (eta > 0) if is_ddim else (t > 0)
         for j, (lo, hi) in enumerate(bounds):
             nz = None
             if need_noise:

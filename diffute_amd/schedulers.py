@@ -36,21 +36,11 @@ class _Config(SimpleNamespace):
 
 class _SchedulerBase:
     order = 1
+    _config_defaults = SD2_SCHEDULER_CONFIG      # the class's own defaults; their keys (+ "thresholding") are what from_pretrained / from_config keep
 
     def __init__(self, **config):
-        cfg = dict(SD2_SCHEDULER_CONFIG); cfg.update(config)
-        # options of the diffusers schedulers whose arithmetic is NOT implemented by the step kernels: refuse them instead of
-        # silently computing something else (DDPMScheduler's own default is clip_sample=True; SD2's scheduler config sets False)
-        if cfg.get("clip_sample"):
-            raise NotImplementedError("clip_sample=True is not implemented (the SD2-inpainting scheduler config uses clip_sample=false)")
-        if cfg.get("thresholding"):
-            raise NotImplementedError("thresholding=True is not implemented")
-        if cfg.get("variance_type", "fixed_small") != "fixed_small":
-            raise NotImplementedError(f"variance_type={cfg['variance_type']!r} is not implemented (only 'fixed_small')")
-        if cfg.get("timestep_spacing", "leading") != "leading":
-            raise NotImplementedError(f"timestep_spacing={cfg['timestep_spacing']!r} is not implemented (only 'leading')")
-        if cfg["prediction_type"] not in ("epsilon", "v_prediction"):
-            raise NotImplementedError(f"prediction_type={cfg['prediction_type']!r} is not implemented")
+        cfg = dict(self._config_defaults); cfg.update(config)
+        self._check_config(cfg)
         self.config = _Config(**cfg)
         N = cfg["num_train_timesteps"]
         self.num_train_timesteps = N                      # read directly at train_diffute_v1.py:892
@@ -68,12 +58,40 @@ class _SchedulerBase:
         self.timesteps = torch.from_numpy(np.arange(0, N)[::-1].copy().astype(np.int64))
         self._dev_tables = {}
 
+    @staticmethod
+    def _check_config(cfg):
+        # options of the diffusers schedulers whose arithmetic is NOT implemented by the step kernels: refuse them instead of
+        # silently computing something else (DDPMScheduler's own default is clip_sample=True; SD2's scheduler config sets False)
+        if cfg.get("clip_sample"):
+            raise NotImplementedError("clip_sample=True is not implemented (the SD2-inpainting scheduler config uses clip_sample=false)")
+        if cfg.get("thresholding"):
+            raise NotImplementedError("thresholding=True is not implemented")
+        if cfg.get("variance_type", "fixed_small") != "fixed_small":
+            raise NotImplementedError(f"variance_type={cfg['variance_type']!r} is not implemented (only 'fixed_small')")
+        if cfg.get("timestep_spacing", "leading") != "leading":
+            raise NotImplementedError(f"timestep_spacing={cfg['timestep_spacing']!r} is not implemented (only 'leading')")
+        if cfg["prediction_type"] not in ("epsilon", "v_prediction"):
+            raise NotImplementedError(f"prediction_type={cfg['prediction_type']!r} is not implemented")
+
+    @classmethod
+    def _known_keys(cls):
+        return set(cls._config_defaults) | {"thresholding"}
+
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, subfolder=None, **kw):
         d = pretrained_model_name_or_path if subfolder is None else os.path.join(pretrained_model_name_or_path, subfolder)
         with open(os.path.join(d, "scheduler_config.json")) as f:
             cfg = json.load(f)
-        known = set(SD2_SCHEDULER_CONFIG) | {"thresholding"}
+        known = cls._known_keys()
+        return cls(**{k: v for k, v in cfg.items() if k in known})
+
+    @classmethod
+    def from_config(cls, config, **overrides):
+        """`SchedulerB.from_config(scheduler_a.config)`, the diffusers idiom for swapping schedulers: `config` is a `.config`
+        object or a dict; the keys this class knows are kept (overrides win), the rest are dropped."""
+        cfg = dict(config) if isinstance(config, dict) else dict(vars(config))
+        cfg.update(overrides)
+        known = cls._known_keys()
         return cls(**{k: v for k, v in cfg.items() if k in known})
 
     def save_pretrained(self, save_directory):
@@ -240,5 +258,165 @@ class DDIMScheduler(_SchedulerBase):
         _cabi.check(_cabi.lib().dmx_sched_step_ddim(_cabi.ptr(x), _cabi.ptr(eps), _cabi.ptr(noise), _cabi.ptr(out), x.numel(),
                                                     sbt, sat, sap, dirc, std, int(self.config.prediction_type == "v_prediction"),
                                                     _cabi.current_stream()), "sched_step_ddim")
+        out = out.to(sample.dtype)
+        return SchedulerOutput(prev_sample=out) if return_dict else (out,)
+
+
+DPM_SOLVER_CONFIG = dict(
+    num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", prediction_type="epsilon",
+    solver_order=2, algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True,
+    timestep_spacing="linspace", steps_offset=1, clip_sample=False, thresholding=False, use_karras_sigmas=False)
+
+
+class DPMSolverMultistepScheduler(_SchedulerBase):
+    """DPM-Solver++ multistep (Lu et al. 2022, arXiv 2211.01095, Alg. 2), orders 1-3, in the tensor form of diffusers >=0.15's
+    DPMSolverMultistepScheduler: the deterministic ~20-step replacement of DDIM-50 / DDPM-150 for eps / v models.  Betas and
+    prediction_type as SD2_SCHEDULER_CONFIG; the grid defaults to "linspace" (diffusers' default for this class).
+
+    The scalars of every step (order plus the parenthesised 0-d fp32 expressions of diffusers' update) are computed on the host
+    once per set_timesteps (step_plan()); the elementwise update - data prediction m0, the multistep combination with the
+    previous m0's - is one kernel (dmx_sched_step_dpmpp).  step() keeps the m0 history itself, as diffusers does, so the
+    reference-shaped loop works unchanged; denoise() keeps its own fixed buffers instead.
+
+    Refused (NotImplementedError): thresholding, algorithm_type other than "dpmsolver++", Karras / Lu sigmas, "trailing" spacing,
+    clip_sample, euler_at_final=True and any final_sigmas_type but "sigma_min" (the last step lands on timestep 0 - diffusers'
+    "zero" would land on sigma = 0).  The solver is deterministic: no noise, no eta."""
+    _config_defaults = DPM_SOLVER_CONFIG
+
+    def __init__(self, **config):
+        super().__init__(**config)
+        ac = self.alphas_cumprod
+        self.alpha_t = torch.sqrt(ac)
+        self.sigma_t = torch.sqrt(1 - ac)
+        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
+        self._ts = np.zeros(0, dtype=np.int64)
+        self._plan = []
+        self._history = []
+        self._step_index = None
+
+    @staticmethod
+    def _check_config(cfg):
+        if cfg.get("clip_sample"):
+            raise NotImplementedError("clip_sample=True is not implemented")
+        if cfg.get("thresholding"):
+            raise NotImplementedError("thresholding=True is not implemented")
+        if cfg["algorithm_type"] != "dpmsolver++":
+            raise NotImplementedError(f"algorithm_type={cfg['algorithm_type']!r} is not implemented (only 'dpmsolver++')")
+        if cfg.get("use_karras_sigmas") or cfg.get("use_lu_lambdas"):
+            raise NotImplementedError("use_karras_sigmas / use_lu_lambdas are not implemented")
+        if cfg["timestep_spacing"] not in ("linspace", "leading"):
+            raise NotImplementedError(f"timestep_spacing={cfg['timestep_spacing']!r} is not implemented (only 'linspace', 'leading')")
+        if cfg.get("euler_at_final"):
+            raise NotImplementedError("euler_at_final=True is not implemented")
+        if cfg.get("final_sigmas_type", "sigma_min") != "sigma_min":
+            raise NotImplementedError(f"final_sigmas_type={cfg['final_sigmas_type']!r} is not implemented (the last step lands on timestep 0)")
+        if cfg["solver_type"] not in ("midpoint", "heun"):
+            raise NotImplementedError(f"solver_type={cfg['solver_type']!r} is not implemented (only 'midpoint', 'heun')")
+        if cfg["prediction_type"] not in ("epsilon", "v_prediction"):
+            raise NotImplementedError(f"prediction_type={cfg['prediction_type']!r} is not implemented")
+        if cfg["solver_order"] not in (1, 2, 3):
+            raise ValueError(f"solver_order={cfg['solver_order']!r}: 1, 2 or 3")
+
+    @classmethod
+    def _known_keys(cls):
+        return set(cls._config_defaults) | {"euler_at_final", "final_sigmas_type", "use_lu_lambdas"}
+
+    def _grid(self, num_inference_steps):
+        N = self.config.num_train_timesteps
+        if num_inference_steps > N:
+            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than {N}")
+        n = num_inference_steps
+        if self.config.timestep_spacing == "linspace":
+            ts = np.linspace(0, N - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+        else:                                                              # "leading"
+            ts = (np.arange(0, n + 1) * (N // (n + 1))).round()[::-1][:-1].copy().astype(np.int64) + np.int64(self.config.steps_offset)
+        _, first = np.unique(ts, return_index=True)                        # dense grids round to repeated timesteps: keep the first of each
+        return ts[np.sort(first)]
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        """The grid (deduplicated, so num_inference_steps may come out smaller than asked), the step plan, an empty history."""
+        ts = self._grid(int(num_inference_steps))
+        self.num_inference_steps = len(ts)
+        self.timesteps = torch.from_numpy(ts)
+        if device is not None:
+            self.timesteps = self.timesteps.to(device)
+        self._ts = ts
+        self._plan = [(o, _cabi.DpmCoefs(**c)) for o, c in self._make_plan(ts)]
+        self._history = []
+        self._step_index = None
+
+    def _orders(self, n):
+        k = self.config.solver_order
+        low = self.config.lower_order_final and n < 15
+        out = []
+        for i in range(n):
+            if k == 1 or i == 0 or (low and i == n - 1):
+                out.append(1)
+            elif k == 2 or i == 1 or (low and i == n - 2):
+                out.append(2)
+            else:
+                out.append(3)
+        return out
+
+    def _make_plan(self, ts):
+        """Per step: (order, {dmx_dpm_coefs field: python float holding the fp32 value}), with diffusers' 0-d fp32 expressions."""
+        lam, al, sg = self.lambda_t, self.alpha_t, self.sigma_t
+        heun = self.config.solver_type == "heun"
+        plan = []
+        for i, o in enumerate(self._orders(len(ts))):
+            s0 = int(ts[i]); t = int(ts[i + 1]) if i + 1 < len(ts) else 0
+            alpha_t, sigma_t, lambda_t = al[t], sg[t], lam[t]
+            alpha_s0, sigma_s0, lambda_s0 = al[s0], sg[s0], lam[s0]
+            h = lambda_t - lambda_s0
+            c = dict(alpha_s0=alpha_s0, sigma_s0=sigma_s0, c_x=sigma_t / sigma_s0, c_m0=alpha_t * (torch.exp(-h) - 1.0),
+                     c_d1=0.0, c_d2=0.0, inv_r0=0.0, inv_r1=0.0, r0_over_r01=0.0, inv_r01=0.0)
+            if o >= 2:
+                h_0 = lambda_s0 - lam[int(ts[i - 1])]
+                r0 = h_0 / h
+                c["inv_r0"] = 1.0 / r0
+                if o == 2 and not heun:      # midpoint: "- 0.5 * (alpha_t * (exp(-h) - 1.0)) * D1", the sign carried by the coefficient
+                    c["c_d1"] = -(0.5 * (alpha_t * (torch.exp(-h) - 1.0)))
+                else:
+                    c["c_d1"] = alpha_t * ((torch.exp(-h) - 1.0) / h + 1.0)
+            if o == 3:
+                h_1 = lam[int(ts[i - 1])] - lam[int(ts[i - 2])]
+                r1 = h_1 / h
+                c["inv_r1"] = 1.0 / r1
+                c["r0_over_r01"] = r0 / (r0 + r1)
+                c["inv_r01"] = 1.0 / (r0 + r1)
+                c["c_d2"] = alpha_t * ((torch.exp(-h) - 1.0 + h) / h ** 2 - 0.5)
+            plan.append((o, {k: float(v) for k, v in c.items()}))
+        return plan
+
+    def step_plan(self):
+        """[(order, {coefficient: float})] of every step of the current grid - what step() and denoise() hand to the kernel."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        return [(o, {k: getattr(c, k) for k, _ in c._fields_}) for o, c in self._plan]
+
+    def step(self, model_output, timestep, sample, return_dict=True):
+        """One solver step; the steps of the grid are taken in order (set_timesteps starts over)."""
+        _cabi.require_cuda(model_output, sample)
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        t = self._t_int(timestep)
+        i = self._step_index
+        if i is None:
+            hits = np.flatnonzero(self._ts == t)
+            i = int(hits[0]) if len(hits) else len(self._ts)
+        if i >= len(self._ts) or int(self._ts[i]) != t:
+            raise ValueError(f"step(): timestep {t} is not the next step of the grid (a multistep solver takes its steps in order; "
+                             "call set_timesteps to start over)")
+        order, coefs = self._plan[i]
+        x = sample.to(torch.float32).contiguous(); e = model_output.to(torch.float32).contiguous()
+        m1 = self._history[-1] if order >= 2 else None
+        m2 = self._history[-2] if order >= 3 else None
+        x0 = torch.empty_like(x); out = torch.empty_like(x)
+        _cabi.check(_cabi.lib().dmx_sched_step_dpmpp(_cabi.ptr(x), _cabi.ptr(e), _cabi.ptr(m1), _cabi.ptr(m2), _cabi.ptr(x0), _cabi.ptr(out),
+                                                     x.numel(), order, coefs, int(self.config.prediction_type == "v_prediction"),
+                                                     _cabi.current_stream()), "sched_step_dpmpp")
+        k = self.config.solver_order
+        self._history = (self._history + [x0])[1 - k:] if k > 1 else []
+        self._step_index = i + 1
         out = out.to(sample.dtype)
         return SchedulerOutput(prev_sample=out) if return_dict else (out,)

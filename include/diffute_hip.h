@@ -393,6 +393,21 @@ int dmx_sched_step_ddim(const float* sample, const float* model_output, const fl
 int dmx_sched_step_ddpm(const float* sample, const float* model_output, const float* noise, float* prev_sample, size_t n,
                         float sqrt_beta_prod_t, float sqrt_alpha_prod_t, float coef_x0, float coef_xt,
                         float sigma, int v_prediction, dmx_stream_t stream);
+/* DPMSolverMultistepScheduler.step(...).prev_sample (DPM-Solver++, orders 1-3): the per-step scalars, computed on the
+ * host (diffute_amd/schedulers.py step_plan).  alpha_s0 / sigma_s0 convert the model output to the data prediction m0;
+ * c_x = sigma_t/sigma_s0, c_m0 = alpha_t*(exp(-h)-1); order >= 2: inv_r0 = 1/r0 and c_d1, the SIGNED coefficient of D1
+ * (midpoint -(0.5*c_m0), heun / order 3 alpha_t*((exp(-h)-1)/h+1)); order 3: inv_r1 = 1/r1, r0_over_r01 = r0/(r0+r1),
+ * inv_r01 = 1/(r0+r1), c_d2 = alpha_t*((exp(-h)-1+h)/h^2-0.5) (subtracted).  Fields an order does not read are ignored. */
+typedef struct dmx_dpm_coefs {
+  float alpha_s0, sigma_s0;
+  float c_x, c_m0, c_d1, c_d2;
+  float inv_r0, inv_r1, r0_over_r01, inv_r01;
+} dmx_dpm_coefs;
+/* m1 / m2: the data predictions of the previous two steps (NULL when `order` does not read them: m1 for order >= 2, m2 for
+ * order 3); x0_out receives this step's m0 (the next step's m1) and must not overlap m1, m2 or prev_sample; prev_sample may
+ * be `sample` (in-place update).  Bit-identical to the fp32 CPU evaluation of diffusers' expressions in their op order. */
+int dmx_sched_step_dpmpp(const float* sample, const float* model_output, const float* m1, const float* m2, float* x0_out,
+                         float* prev_sample, size_t n, int order, dmx_dpm_coefs coefs, int v_prediction, dmx_stream_t stream);
 /* scheduler.add_noise / get_velocity (train_diffute_v1.py:897,907): per-sample coefficients */
 int dmx_sched_add_noise(const float* x0, const float* noise, const float* sqrt_alpha_prod, const float* sqrt_one_minus,
                         float* out, int B, size_t per_sample, dmx_stream_t stream);
