@@ -231,6 +231,8 @@ _PROTOS = {
     "dmx_unet_adamw_step": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, c_int, c_float, _P, _P, c_size_t, _P, c_float, _P]),
     "dmx_unet_adamw_step_scaled": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, c_int, c_float, _P, _P, c_size_t, _P, c_float, c_float, _P]),
     "dmx_unet_refresh_derived": (c_int, [_P, _P]),
+    "dmx_ema_step_multi": (c_int, [_P, c_int, c_float, _P]),
+    "dmx_copy_multi": (c_int, [_P, c_int, _P]),
     "dmx_unet_temb_table_floats": (c_size_t, [_P, c_int]),
     "dmx_unet_temb_table_workspace_bytes": (c_size_t, [_P, c_int]),
     "dmx_unet_temb_table": (c_int, [_P, _P, c_int, _P, _P, c_size_t, _P]),

@@ -11,6 +11,7 @@ import ctypes
 import json
 import math
 import os
+import weakref
 from collections import OrderedDict
 from types import SimpleNamespace
 
@@ -44,6 +45,14 @@ _UNET_MUST_BE_NONE = ("addition_embed_type", "class_embed_type", "cross_attentio
                       "num_class_embeds", "projection_class_embeddings_input_dim", "time_cond_proj_dim", "time_embedding_act_fn",
                       "time_embedding_dim", "timestep_post_act")
 _VAE_ONLY_SUPPORTED = dict(act_fn="silu")
+
+
+# config.json keys `EMAModel.save_pretrained` adds next to the model config (diffusers' `register_to_config(**ema.state_dict())`);
+# `load_config(..., return_unused_kwargs=True)` hands them back as the unused kwargs, `from_pretrained` / `from_config` skip them
+_EMA_CONFIG_KEYS = ("decay", "inv_gamma", "min_decay", "optimization_step", "power", "update_after_step", "use_ema_warmup")
+
+# every live HIP model: diffute_amd.EMAModel finds the model (and the parameter names) behind a bare `model.parameters()` list
+_LIVE_MODELS = weakref.WeakSet()
 
 
 def _check_supported(kind, cfg, only, must_be_none=()):
@@ -155,6 +164,7 @@ class _HipModel(nn.Module):
             self._slots = {}
 
     def _setup(self, handle, seed, device):
+        _LIVE_MODELS.add(self)
         self._h = handle
         self._elem = "bf16"
         self._dtype = torch.float32
@@ -278,12 +288,27 @@ class _HipModel(nn.Module):
                   os.path.join(save_directory, "diffusion_pytorch_model.safetensors"))
 
     @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path, subfolder=None, revision=None, **kw):
+    def load_config(cls, pretrained_model_name_or_path, subfolder=None, return_unused_kwargs=False):
+        """config.json of a diffusers model directory -> the model config (keys starting with "_" dropped); with
+        return_unused_kwargs also the keys that are not model config - what EMAModel.save_pretrained adds (decay,
+        optimization_step, ...; EMAModel.from_pretrained reads them back this way)"""
         d = pretrained_model_name_or_path if subfolder is None else os.path.join(pretrained_model_name_or_path, subfolder)
         with open(os.path.join(d, "config.json")) as f:
-            cfg = json.load(f)
-        cfg = {k: v for k, v in cfg.items() if not k.startswith("_")}
-        model = cls(**cfg)
+            raw = json.load(f)
+        cfg = {k: v for k, v in raw.items() if not k.startswith("_") and k not in _EMA_CONFIG_KEYS}
+        unused = {k: v for k, v in raw.items() if k in _EMA_CONFIG_KEYS}
+        return (cfg, unused) if return_unused_kwargs else cfg
+
+    @classmethod
+    def from_config(cls, config):
+        """a freshly initialised model from a config (`model.config`, or a dict as load_config returns it)"""
+        cfg = config.to_dict() if hasattr(config, "to_dict") else dict(config)
+        return cls(**{k: v for k, v in cfg.items() if not k.startswith("_") and k not in _EMA_CONFIG_KEYS})
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, subfolder=None, revision=None, **kw):
+        d = pretrained_model_name_or_path if subfolder is None else os.path.join(pretrained_model_name_or_path, subfolder)
+        model = cls(**cls.load_config(d))
         st = os.path.join(d, "diffusion_pytorch_model.safetensors")
         if os.path.exists(st):
             from safetensors.torch import load_file

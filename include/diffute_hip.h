@@ -566,6 +566,33 @@ int dmx_unet_adamw_step_scaled(dmx_unet* u, const void* table_dev, int nchunks, 
                                float* scalars, void* workspace, size_t workspace_bytes, void* ema, float ema_decay, float grad_inv_scale,
                                dmx_stream_t stream);
 int dmx_unet_refresh_derived(dmx_unet* u, dmx_stream_t stream);
+
+/* Multi-tensor EMA update / cast-copy (diffusers EMAModel as the reference drives it: `ema_unet.step(unet.parameters())`,
+ * train_diffute_v1.py:934-935; copy_to / store / restore; diffute_amd.EMAModel).  One launch per call whatever the number of
+ * tensors: `table` is a DEVICE array of `nchunks` entries, each a contiguous run of `count` elements; the host splits large
+ * tensors into several entries so the grid fills the GPU.  dst and src runs must not overlap each other or any other entry's dst.
+ * Entries whose two pointers are both 16-byte aligned use 4-element vector accesses (16 bytes for fp32), others a scalar path.
+ *   dmx_ema_step_multi  mode DMX_MULTI_EMA:  dst -= one_minus_decay * (dst - src), i.e. diffusers' `s.sub_(omd * (s - p))` with
+ *                       torch's type promotion: d = s - p and m = omd * d are each rounded to T (the dtype of dst when src has
+ *                       the same dtype, else fp32), then s - m is rounded to dst's dtype; every op is one fp32 _rn op,
+ *                       16-bit roundings are RNE.  one_minus_decay is the fp32 rounding of the host's double `1 - decay` (what
+ *                       torch does with a Python scalar), so the result is bit-identical to torch's.
+ *                       mode DMX_MULTI_COPY: dst = cast(src) (`s.copy_(p)`, parameters with requires_grad=False).
+ *   dmx_copy_multi      every entry: dst = cast(src) (the mode field is ignored).
+ * dtypes: DMX_DT_F32, DMX_DT_BF16, DMX_DT_F16 for either side, in both builds of the library. */
+#define DMX_DT_F32 0
+#define DMX_DT_BF16 1
+#define DMX_DT_F16 2
+#define DMX_MULTI_EMA 0
+#define DMX_MULTI_COPY 1
+typedef struct dmx_multi_chunk {
+  void* dst;                   /* first element of the run (shadow / destination) */
+  const void* src;             /* first element of the run (parameter / source) */
+  unsigned int count;          /* elements */
+  unsigned char dst_dtype, src_dtype, mode, reserved;
+} dmx_multi_chunk;             /* 24 bytes */
+int dmx_ema_step_multi(const void* table, int nchunks, float one_minus_decay, dmx_stream_t stream);
+int dmx_copy_multi(const void* table, int nchunks, dmx_stream_t stream);
 size_t dmx_mse_loss_workspace_bytes(void);
 int dmx_mse_loss(const float* pred, const float* target, size_t n, float* loss, float* dpred, float grad_scale,
                  void* workspace, size_t workspace_bytes, dmx_stream_t stream);
