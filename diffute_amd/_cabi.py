@@ -78,6 +78,12 @@ class ViTConfig(ctypes.Structure):
                 ("num_heads", c_int), ("intermediate_size", c_int), ("qkv_bias", c_int), ("layer_norm_eps", c_float)]
 
 
+class TrOCRDecConfig(ctypes.Structure):
+    _fields_ = [("vocab_size", c_int), ("d_model", c_int), ("num_layers", c_int), ("num_heads", c_int), ("ffn_dim", c_int),
+                ("max_position_embeddings", c_int), ("cross_hidden_size", c_int), ("activation", c_int), ("scale_embedding", c_int),
+                ("layernorm_embedding", c_int), ("tie_word_embeddings", c_int)]
+
+
 class UNetConfig(ctypes.Structure):
     _fields_ = [("in_channels", c_int), ("out_channels", c_int), ("block_out_channels", c_int * 4),
                 ("layers_per_block", c_int), ("heads", c_int * 4), ("cross_attention_dim", c_int),
@@ -183,6 +189,26 @@ _PROTOS = {
     "dmx_vit_master_import": (c_int, [_P, _P, c_char_p, _P, _P]),
     "dmx_vit_workspace_bytes_f32": (c_size_t, [_P, c_int]),
     "dmx_vit_forward_f32": (c_int, [_P, _P, _P, _P, c_int, _P, c_size_t, _P]),
+    "dmx_trocr_dec_create": (_P, [POINTER(TrOCRDecConfig)]),
+    "dmx_trocr_dec_destroy": (None, [_P]),
+    "dmx_trocr_dec_param_count": (c_int, [_P]),
+    "dmx_trocr_dec_param_info": (c_int, [_P, c_int, POINTER(c_char_p), POINTER(c_int * 4)]),
+    "dmx_trocr_dec_arena_bytes": (c_size_t, [_P]),
+    "dmx_trocr_dec_bind_arena": (c_int, [_P, _P, c_size_t]),
+    "dmx_trocr_dec_load_param": (c_int, [_P, c_char_p, _P, _P]),
+    "dmx_trocr_dec_finalize": (c_int, [_P, _P]),
+    "dmx_trocr_dec_cache_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
+    "dmx_trocr_dec_workspace_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
+    "dmx_trocr_dec_cross_kv": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "dmx_trocr_dec_reset": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "dmx_trocr_dec_set_tokens": (c_int, [_P, _P, _P, c_int, _P]),
+    "dmx_trocr_dec_step": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, c_size_t, _P]),
+    "dmx_trocr_dec_launches_per_step": (c_int, [_P]),
+    "dmx_trocr_dec_linear_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dmx_trocr_dec_linear": (c_int, [c_int, c_int, _P, c_int, c_int, _P, c_int, _P, c_float, _P, c_int, _P, _P, _P, _P,
+                                     _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "dmx_trocr_dec_attn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dmx_trocr_dec_attn": (c_int, [_P, c_int, c_int, _P, c_int64, c_int, c_int, _P, _P, c_size_t, _P]),
     "dmx_unet_create": (_P, [POINTER(UNetConfig)]),
     "dmx_unet_destroy": (None, [_P]),
     "dmx_unet_param_count": (c_int, [_P]),

@@ -1,0 +1,801 @@
+// OCR read-back: the text decoder of TrOCR (reference: `full_trocr_model = VisionEncoderDecoderModel.from_pretrained(
+// 'microsoft/trocr-large-printed')`, app.ipynb:548; `full_trocr_model_te.generate(pixel_values)`, :845).  Module structure =
+// transformers' TrOCRForCausalLM (BART-style post-LN decoder):
+//   x = LN_emb(embed_tokens[tok] * scale + embed_positions[pos + 2])
+//   L x { x = LN(x + o(self_attn(qkv(x))));  x = LN(x + o(cross_attn(q(x), K/V(enc))));  x = LN(x + fc2(act(fc1(x)))) }
+//   logits = x output_projection^T  (tied to embed_tokens unless the checkpoint says otherwise)
+// Greedy decode is batch-small (M = number of crops <= 64) and weight-streaming: every kernel of a step reads its weights once.
+//   dec_linear  - y[M][N] = x[M][K] W[N][K]^T on v_mfma_f32_16x16x32 with the M rows padded to 16 in registers (zero lanes), 64
+//                 output features per block, K split over blockIdx.y.  The split partials are combined by the LAST block of each
+//                 feature tile to arrive (integer counter, fixed summation order s = 0..splits-1: deterministic, no float atomics),
+//                 which also applies the epilogue: bias [+ act] | q-scale + K/V-cache write | + residual and, through a second
+//                 counter over the tiles, the row LayerNorm | logits + per-block (max, lowest index) and the greedy pick.
+//   dec_attn    - one query row per (b, head), d = 64, split over 64-key chunks; the last chunk block combines in chunk order.
+//   dec_embed   - token + position (+ scale) + layernorm_embedding, token and position read from device memory.
+// Per step: 1 + 8 per layer + 1 launches; the counters reset themselves, so one captured graph replays every step.
+#include <math.h>
+#include <memory>
+#include <string>
+#include <vector>
+#include "exec.h"
+#include "../../include/diffute_hip.h"
+
+namespace {
+enum { EPI_STORE = 0, EPI_QKV = 1, EPI_LN = 2, EPI_PICK = 3 };
+enum { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2 };
+// state words at the start of the cache (DMX_TROCR_STATE_* in the header)
+enum { ST_POS = 0, ST_DONE = 1, ST_STOP = 2, ST_TOK = 16, ST_FIN = 16 + 64, ST_INTS = 256 };
+
+struct DecLin {
+  const bf16* x; int ldx;            // [M][K]
+  const bf16* w; int ldw;            // [N][K]
+  const float* bias;                 // [N] or null
+  int M, N, K, kchunk, splits;
+  float* part;                       // [splits][M][N] fp32 (splits > 1)
+  int* cnt;                          // [gridDim.x + 1] self-resetting counters (zero on entry)
+  int epi, act;
+  float oscale;                      // EPI_STORE: y = act(acc + bias) * oscale
+  float* yf; int ldyf;               // fp32 out (EPI_STORE / EPI_QKV: q / EPI_LN: hidden / EPI_PICK: logits, optional)
+  bf16* yb; int ldyb;                // bf16 out (EPI_STORE / EPI_LN)
+  // EPI_QKV: columns [0, D) are q (-> yf, times oscale), [D, 3D) k|v -> kv + m * kv_bstride + pos * 2D
+  bf16* kv; long long kv_bstride; const int* state; int D;
+  // EPI_LN: pre = acc + bias + res; then LN over the row (gamma, beta, eps) -> yf, yb
+  const float* res; float* pre; const float* gamma; const float* beta; float eps;
+  // EPI_PICK: per-block partials [M][gridDim.x], then the greedy pick into state / ids
+  float* pv; int* pi; long long* ids; int max_len, eos, pad;
+};
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
+  return v;
+}
+// greedy order: larger value first, equal values -> lower index (torch.argmax); NaN never wins
+__device__ __forceinline__ bool pick_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+__device__ __forceinline__ void pick_merge(float& bv, int& bi, float v, int i) { if (pick_better(v, i, bv, bi)) { bv = v; bi = i; } }
+
+// Cross-block hand-offs: the data another block of the same launch reads are stored WRITE-THROUGH (sc1 buffer stores) and read
+// with sc1 loads, so publishing needs no agent-scope release / acquire fence (buffer_wbl2 walks the whole L2, buffer_inv drops it:
+// microseconds per block - the recipe of gemm.hip's stream-K fix-up)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wt_rsrc(const void* base, size_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ void wt_store(__amdgpu_buffer_rsrc_t rs, size_t idx, float v) {
+  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, (int)(idx * 4), 0, 16);
+}
+__device__ __forceinline__ void wt_store_i(__amdgpu_buffer_rsrc_t rs, size_t idx, int v) {
+  __builtin_amdgcn_raw_buffer_store_b32((unsigned)v, rs, (int)(idx * 4), 0, 16);
+}
+__device__ __forceinline__ float wt_load(__amdgpu_buffer_rsrc_t rs, size_t idx) {
+  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(idx * 4), 0, 16));
+}
+__device__ __forceinline__ int wt_load_i(__amdgpu_buffer_rsrc_t rs, size_t idx) {
+  return (int)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(idx * 4), 0, 16);
+}
+// four consecutive floats (idx % 4 == 0)
+__device__ __forceinline__ void wt_store4(__amdgpu_buffer_rsrc_t rs, size_t idx, f32x4 v) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, (int)(idx * 4), 0, 16);
+}
+__device__ __forceinline__ f32x4 wt_load4(__amdgpu_buffer_rsrc_t rs, size_t idx) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(idx * 4), 0, 16));
+}
+
+// the block that increments `c` last (of `total` arrivals) returns true; every arrival's write-through stores have drained
+// before its increment.  The last one resets the counter for the next launch.
+__device__ __forceinline__ bool last_arrival(int* c, int total) {
+  __shared__ int s_last;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int old = __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = (old == total - 1);
+    if (s_last) __hip_atomic_store(c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  return s_last != 0;
+}
+
+// one row of the LayerNorm tail: v = this lane's nper = N / 64 consecutive values (columns lane * nper + e, nper % 4 == 0), held
+// in one vector register tuple; gamma / beta come in the same layout, loaded once per tail; the row leaves with 16-byte stores
+__device__ __forceinline__ void ln_row(f32x16 v, int nper, int N, int m, f32x16 g, f32x16 b, float eps, float* yf, bf16* yb) {
+  const int c0 = (threadIdx.x & 63) * nper;
+  float s = 0.f;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) if (e < nper) s += v[e];
+  const float mean = wave_sum(s) / (float)N;
+  float sq = 0.f;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) if (e < nper) { const float d = v[e] - mean; sq += d * d; }
+  const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)N + eps);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (4 * q >= nper) break;
+    float y[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) y[e] = (v[4 * q + e] - mean) * rstd * g[4 * q + e] + b[4 * q + e];
+    *(f32x4*)(yf + (size_t)m * N + c0 + 4 * q) = (f32x4){y[0], y[1], y[2], y[3]};
+    *(u32x2*)(yb + (size_t)m * N + c0 + 4 * q) = (u32x2){pack_bf2(y[0], y[1]), pack_bf2(y[2], y[3])};
+  }
+}
+__device__ __forceinline__ f32x16 ln_load(__amdgpu_buffer_rsrc_t rs, size_t row0, int nper) {
+  const int c0 = (threadIdx.x & 63) * nper;
+  f32x16 v;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4 u = wt_load4(rs, row0 + c0 + min(q, nper / 4 - 1) * 4);
+    v[4 * q] = u[0]; v[4 * q + 1] = u[1]; v[4 * q + 2] = u[2]; v[4 * q + 3] = u[3];
+  }
+  return v;
+}
+__device__ __forceinline__ f32x16 ln_vec(const float* p, int nper) {
+  const int c0 = (threadIdx.x & 63) * nper;
+  f32x16 v;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4 u = *(const f32x4*)(p + c0 + min(q, nper / 4 - 1) * 4);
+    v[4 * q] = u[0]; v[4 * q + 1] = u[1]; v[4 * q + 2] = u[2]; v[4 * q + 3] = u[3];
+  }
+  return v;
+}
+// row LayerNorm of pre[M][N] (N % 256 == 0, N <= 1024) by one block: wave w takes rows w, w + 4, ..., four rows at a time with
+// all of their loads in flight together (the tail is a chain of round trips, not of bandwidth)
+__device__ void rows_layernorm(const float* pre, int M, int N, const float* gamma, const float* beta, float eps, float* yf, bf16* yb) {
+  const int wv = threadIdx.x >> 6, nper = N >> 6;
+  const __amdgpu_buffer_rsrc_t rs = wt_rsrc(pre, (size_t)M * N * 4);
+  const f32x16 g = ln_vec(gamma, nper), b = ln_vec(beta, nper);
+  for (int m0 = wv; m0 < M; m0 += 16) {
+    const f32x16 v0 = ln_load(rs, (size_t)m0 * N, nper);
+    const f32x16 v1 = ln_load(rs, (size_t)min(m0 + 4, M - 1) * N, nper);
+    const f32x16 v2 = ln_load(rs, (size_t)min(m0 + 8, M - 1) * N, nper);
+    const f32x16 v3 = ln_load(rs, (size_t)min(m0 + 12, M - 1) * N, nper);
+    ln_row(v0, nper, N, m0, g, b, eps, yf, yb);
+    if (m0 + 4 < M) ln_row(v1, nper, N, m0 + 4, g, b, eps, yf, yb);
+    if (m0 + 8 < M) ln_row(v2, nper, N, m0 + 8, g, b, eps, yf, yb);
+    if (m0 + 12 < M) ln_row(v3, nper, N, m0 + 12, g, b, eps, yf, yb);
+  }
+}
+
+template <int MT>
+__global__ __launch_bounds__(256) void dmx_dec_linear_kernel(DecLin a) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int g = lane >> 4, r = lane & 15;
+  const int nb = blockIdx.x, s = blockIdx.y;
+  const int n0 = nb * 64 + wv * 16;
+  const int k_beg = s * a.kchunk, k_end = min(a.K, k_beg + a.kchunk);
+  // lane (g, r): weight row n0 + r and activation rows t*16 + r, k = kb + 32 g + 8 j + e for MFMA j - the same k set in A and B,
+  // so each lane reads one contiguous 64-byte run per operand and 128-k step
+  const bool wok = n0 + r < a.N;
+  const bf16* wp = a.w + (size_t)(wok ? n0 + r : 0) * a.ldw + g * 32;
+  const bf16* xp[MT];
+  bool xok[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    xok[t] = t * 16 + r < a.M;
+    xp[t] = a.x + (size_t)(xok[t] ? t * 16 + r : 0) * a.ldx + g * 32;
+  }
+  f32x4 acc[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+  for (int k = k_beg; k < k_end; k += 128) {
+    u32x4 wa[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) wa[j] = wok ? *(const u32x4*)(wp + k + j * 8) : zero;
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      u32x4 xb[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) xb[j] = xok[t] ? *(const u32x4*)(xp[t] + k + j * 8) : zero;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[t] = DMX_MFMA_16x16x32(__builtin_bit_cast(bf16x8, wa[j]), __builtin_bit_cast(bf16x8, xb[j]), acc[t]);
+    }
+  }
+  // acc[t][i]: feature n0 + 4 g + i, row t * 16 + r
+  if (a.splits > 1) {
+    const size_t plane = (size_t)a.M * a.N;
+    const __amdgpu_buffer_rsrc_t rs = wt_rsrc(a.part, plane * a.splits * 4);
+    // split planes hold 16-byte runs: the four features n0 + 4g .. + 3 of a lane are consecutive (split plans have N % 64 == 0)
+    const int n4 = n0 + 4 * g;
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      const int m = t * 16 + r;
+      if (m < a.M && n4 < a.N) wt_store4(rs, s * plane + (size_t)m * a.N + n4, acc[t]);
+    }
+    if (!last_arrival(a.cnt + nb, a.splits)) return;
+    // fixed order s = 0, 1, ...; the loads of SB splits of every row tile are issued before their adds (round trips, not
+    // bandwidth, bound this)
+    constexpr int SB = MT == 1 ? 16 : 8;
+    f32x4 sum[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) sum[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int s0 = 0; s0 < a.splits; s0 += SB) {
+      f32x4 u[MT][SB];
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {
+        const int m = min(t * 16 + r, a.M - 1);
+#pragma unroll
+        for (int e = 0; e < SB; ++e) u[t][e] = wt_load4(rs, min(s0 + e, a.splits - 1) * plane + (size_t)m * a.N + min(n4, a.N - 4));
+      }
+#pragma unroll
+      for (int t = 0; t < MT; ++t)
+#pragma unroll
+        for (int e = 0; e < SB; ++e) if (s0 + e < a.splits) sum[t] += u[t][e];
+    }
+#pragma unroll
+    for (int t = 0; t < MT; ++t) acc[t] = sum[t];
+  }
+  if (a.epi == EPI_PICK) {
+    __shared__ float sv[4][64];
+    __shared__ int si[4][64];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      const int m = t * 16 + r;
+      float bv = -INFINITY; int bi = 0x7fffffff;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int n = n0 + 4 * g + i;
+        if (m < a.M && n < a.N) {
+          if (a.yf) a.yf[(size_t)m * a.ldyf + n] = acc[t][i];
+          pick_merge(bv, bi, acc[t][i], n);
+        }
+      }
+#pragma unroll
+      for (int d = 16; d <= 32; d <<= 1) {
+        const float ov = __shfl_xor(bv, d); const int oi = __shfl_xor(bi, d);
+        pick_merge(bv, bi, ov, oi);
+      }
+      if (g == 0) { sv[wv][t * 16 + r] = bv; si[wv][t * 16 + r] = bi; }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < a.M) {
+      const int m = threadIdx.x;
+      float bv = sv[0][m]; int bi = si[0][m];
+      for (int w = 1; w < 4; ++w) pick_merge(bv, bi, sv[w][m], si[w][m]);
+      wt_store(wt_rsrc(a.pv, (size_t)a.M * gridDim.x * 4), (size_t)m * gridDim.x + nb, bv);
+      wt_store_i(wt_rsrc(a.pi, (size_t)a.M * gridDim.x * 4), (size_t)m * gridDim.x + nb, bi);
+    }
+    if (!last_arrival(a.cnt + gridDim.x, gridDim.x)) return;
+    int* st = const_cast<int*>(a.state);
+    const int pos = st[ST_POS];
+    const __amdgpu_buffer_rsrc_t rv = wt_rsrc(a.pv, (size_t)a.M * gridDim.x * 4), ri = wt_rsrc(a.pi, (size_t)a.M * gridDim.x * 4);
+    const int nbk = gridDim.x;
+    __shared__ int s_best[64];
+    // two rows per wave at a time, every load of both in flight together; the order of the merges does not matter (the
+    // greedy order is total)
+    for (int m0 = wv; m0 < a.M; m0 += 8) {
+      const int m1 = min(m0 + 4, a.M - 1);
+      float bv0 = -INFINITY, bv1 = -INFINITY; int bi0 = 0x7fffffff, bi1 = 0x7fffffff;
+      for (int c0 = 0; c0 < nbk; c0 += 16 * 64) {
+        float pv0[16], pv1[16]; int pi0[16], pi1[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int c = min(c0 + e * 64 + lane, nbk - 1);
+          pv0[e] = wt_load(rv, (size_t)m0 * nbk + c); pi0[e] = wt_load_i(ri, (size_t)m0 * nbk + c);
+          pv1[e] = wt_load(rv, (size_t)m1 * nbk + c); pi1[e] = wt_load_i(ri, (size_t)m1 * nbk + c);
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { pick_merge(bv0, bi0, pv0[e], pi0[e]); pick_merge(bv1, bi1, pv1[e], pi1[e]); }
+      }
+#pragma unroll
+      for (int d = 1; d <= 32; d <<= 1) {
+        const float ov0 = __shfl_xor(bv0, d); const int oi0 = __shfl_xor(bi0, d);
+        const float ov1 = __shfl_xor(bv1, d); const int oi1 = __shfl_xor(bi1, d);
+        pick_merge(bv0, bi0, ov0, oi0); pick_merge(bv1, bi1, ov1, oi1);
+      }
+      if (lane == 0) { s_best[m0] = bi0; if (m0 + 4 < a.M) s_best[m0 + 4] = bi1; }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < a.M) {
+      const int m = threadIdx.x;
+      int bi = s_best[m];
+      if (bi < 0 || bi >= a.N) bi = 0;                           // (all logits NaN: keep the id in range)
+      const int fin = st[ST_FIN + m];
+      const int tok = fin ? a.pad : bi;                          // a finished row emits pad_token_id
+      if (pos + 1 < a.max_len) a.ids[(size_t)m * a.max_len + pos + 1] = tok;
+      st[ST_TOK + m] = tok;
+      if (a.eos >= 0 && tok == a.eos) st[ST_FIN + m] = 1;
+    }
+    __syncthreads();
+    __threadfence_block();
+    if (threadIdx.x == 0) {
+      int all = 1;
+      for (int m = 0; m < a.M; ++m) all &= (st[ST_FIN + m] != 0);
+      if (all && st[ST_DONE] == 0) { st[ST_DONE] = 1; st[ST_STOP] = pos + 2; }
+      st[ST_POS] = pos + 1;
+    }
+    return;
+  }
+  const int pos = a.epi == EPI_QKV ? a.state[ST_POS] : 0;
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    const int m = t * 16 + r;
+    if (m >= a.M) continue;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int n = n0 + 4 * g + i;
+      if (n >= a.N) continue;
+      float v = acc[t][i] + (a.bias ? a.bias[n] : 0.f);
+      if (a.epi == EPI_STORE) {
+        if (a.act == ACT_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+        else if (a.act == ACT_RELU) v = fmaxf(v, 0.f);
+        v *= a.oscale;
+        if (a.yf) a.yf[(size_t)m * a.ldyf + n] = v;
+        if (a.yb) a.yb[(size_t)m * a.ldyb + n] = (bf16)v;
+      } else if (a.epi == EPI_QKV) {
+        if (n < a.D) a.yf[(size_t)m * a.ldyf + n] = v * a.oscale;
+        else if (pos < a.max_len) a.kv[(size_t)m * a.kv_bstride + (size_t)pos * 2 * a.D + (n - a.D)] = (bf16)v;
+      } else {                                                   // EPI_LN
+        wt_store(wt_rsrc(a.pre, (size_t)a.M * a.N * 4), (size_t)m * a.N + n, v + a.res[(size_t)m * a.N + n]);
+      }
+    }
+  }
+  if (a.epi == EPI_LN && last_arrival(a.cnt + gridDim.x, gridDim.x))
+    rows_layernorm(a.pre, a.M, a.N, a.gamma, a.beta, a.eps, a.yf, a.yb);
+}
+
+struct DecAttn {
+  const float* q; int ldq;           // [M][ldq], already scaled by head_dim^-0.5
+  const bf16* kv; long long bstride; int rstride;   // key j of batch b, head h: kv + b*bstride + j*rstride + h*64; value: + D
+  const int* state; int L;           // self-attention: L = min(state[ST_POS] + 1, L); cross-attention (state null): L
+  int M, H, D, nch;
+  float* part; int* cnt;             // [M][H][nch][66]; [M*H]
+  bf16* o; int ldo;
+};
+
+__global__ __launch_bounds__(64) void dmx_dec_attn_kernel(DecAttn a) {
+  const int lane = threadIdx.x, c = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const int L = a.state ? min(a.state[ST_POS] + 1, a.L) : a.L;
+  const bf16* kb = a.kv + (size_t)b * a.bstride + h * 64;
+  const int j0 = c * 64, nvalid = max(0, min(64, L - j0));
+  float s = -INFINITY;
+  if (lane < nvalid) {
+    const float* q = a.q + (size_t)b * a.ldq + h * 64;
+    const bf16* kr = kb + (size_t)(j0 + lane) * a.rstride;
+    float dot = 0.f;
+#pragma unroll
+    for (int d = 0; d < 64; d += 8) {
+      float kf[8]; unpack_bf8(*(const u32x4*)(kr + d), kf);
+      const f32x4 q0 = *(const f32x4*)(q + d), q1 = *(const f32x4*)(q + d + 4);
+      dot += q0[0] * kf[0] + q0[1] * kf[1] + q0[2] * kf[2] + q0[3] * kf[3] + q1[0] * kf[4] + q1[1] * kf[5] + q1[2] * kf[6] + q1[3] * kf[7];
+    }
+    s = dot;
+  }
+  const float mx = wave_max(s);
+  const float p = lane < nvalid ? expf(s - mx) : 0.f;
+  const float l = wave_sum(p);
+  // o[d] = sum_j p_j v_j[d]: lane (kg = lane / 8, dg = lane % 8) takes keys kg, kg + 8, ... and dims 8 dg ... 8 dg + 7 with 16-byte
+  // loads (all eight issued before the first FMA), then the eight key groups are summed across lanes
+  const int kg = lane >> 3, dg = lane & 7;
+  float o8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  u32x4 vv[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int jj = u * 8 + kg;
+    vv[u] = jj < nvalid ? *(const u32x4*)(kb + a.D + (size_t)(j0 + jj) * a.rstride + dg * 8) : (u32x4){0u, 0u, 0u, 0u};
+  }
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const float pj = __shfl(p, u * 8 + kg);
+    float vf[8]; unpack_bf8(vv[u], vf);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o8[e] += pj * vf[e];
+  }
+#pragma unroll
+  for (int d = 8; d <= 32; d <<= 1)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o8[e] += __shfl_xor(o8[e], d);
+  const int bh = b * a.H + h;
+  const size_t rec = (size_t)a.M * a.H * a.nch * 66;
+  const __amdgpu_buffer_rsrc_t rs = wt_rsrc(a.part, rec * 4);
+  const size_t P = ((size_t)bh * a.nch + c) * 66;
+  if (lane == 0) { wt_store(rs, P, nvalid ? mx : -INFINITY); wt_store(rs, P + 1, l); }
+  if (kg == 0) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) wt_store(rs, P + 2 + dg * 8 + e, o8[e]);
+  }
+  if (!last_arrival(a.cnt + bh, a.nch)) return;
+  // chunk order 0, 1, ...; the (m, l, o) of 16 chunks are loaded together
+  const size_t Pb = (size_t)bh * a.nch * 66;
+  float M = -INFINITY;
+  for (int c0 = 0; c0 < a.nch; c0 += 16) {
+    float mc[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) mc[e] = wt_load(rs, Pb + (size_t)min(c0 + e, a.nch - 1) * 66);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) M = fmaxf(M, mc[e]);
+  }
+  float acc = 0.f, den = 0.f;
+  for (int c0 = 0; c0 < a.nch; c0 += 16) {
+    float mc[16], lc[16], oc[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const size_t q = Pb + (size_t)min(c0 + e, a.nch - 1) * 66;
+      mc[e] = wt_load(rs, q); lc[e] = wt_load(rs, q + 1); oc[e] = wt_load(rs, q + 2 + lane);
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      if (c0 + e >= a.nch) break;
+      const float w = mc[e] == -INFINITY ? 0.f : expf(mc[e] - M);
+      den += w * lc[e];
+      acc += w * oc[e];
+    }
+  }
+  a.o[(size_t)b * a.ldo + h * 64 + lane] = (bf16)(acc / den);
+}
+
+// x = LN(embed[tok] * scale + pos_table[pos + 2]) (LN skipped without gamma): one wave per row
+__global__ __launch_bounds__(64) void dmx_dec_embed_kernel(const int* state, const bf16* emb, int V, const float* posw, int npos, float scale,
+                                                           const float* gamma, const float* beta, int D, float* yf, bf16* yb) {
+  const int lane = threadIdx.x, m = blockIdx.x, nper = D >> 6;
+  int tok = state[ST_TOK + m]; tok = min(max(tok, 0), V - 1);
+  const int prow = min(state[ST_POS] + 2, npos - 1);
+  float v[16];
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {                                // (clamped, unconditional loads: all in flight together)
+    const int n = min(j, nper - 1) * 64 + lane;
+    v[j] = (float)emb[(size_t)tok * D + n] * scale + posw[(size_t)prow * D + n];
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) if (j < nper) s += v[j];
+  if (gamma) {
+    const float mean = wave_sum(s) / (float)D;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) if (j < nper) { const float d = v[j] - mean; q += d * d; }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + 1e-5f);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) if (j < nper) { const int n = j * 64 + lane; v[j] = (v[j] - mean) * rstd * gamma[n] + beta[n]; }
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) if (j < nper) {
+    const int n = j * 64 + lane;
+    yf[(size_t)m * D + n] = v[j];
+    yb[(size_t)m * D + n] = (bf16)v[j];
+  }
+}
+
+// zero the counters / state, every row starts from `start`
+__global__ __launch_bounds__(256) void dmx_dec_reset_kernel(int* words, size_t nwords, int B, int start, long long* ids, int max_len) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += (size_t)gridDim.x * blockDim.x)
+    words[i] = (i >= ST_TOK && i < (size_t)ST_TOK + B) ? start : 0;
+  if (blockIdx.x == 0 && (int)threadIdx.x < B && ids) ids[(size_t)threadIdx.x * max_len] = start;
+}
+__global__ __launch_bounds__(256) void dmx_f32_to_bf16_kernel(const float* in, bf16* out, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = (bf16)in[i];
+}
+__global__ __launch_bounds__(256) void dmx_i64_to_i32_kernel(const long long* in, int* out, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (int)in[i];
+}
+
+int dec_linear_launch(const DecLin& a, hipStream_t stream) {
+  const int nblk = cdiv(a.N, 64);
+  DMX_REQUIRE(a.M >= 1 && a.M <= 64 && a.K % 128 == 0 && a.kchunk % 128 == 0 && a.ldw % 8 == 0 && a.ldx % 8 == 0,
+              "dec_linear: M=%d K=%d kchunk=%d", a.M, a.K, a.kchunk);
+  DMX_REQUIRE(a.splits == cdiv(a.K, a.kchunk), "dec_linear: splits %d != K / kchunk", a.splits);
+  DMX_REQUIRE(a.epi != EPI_PICK || a.splits == 1, "dec_linear: the pick epilogue runs unsplit");
+  DMX_REQUIRE(a.splits == 1 || a.N % 4 == 0, "dec_linear: a split plan needs N %% 4 == 0 (16-byte partial runs)");
+  DMX_REQUIRE(a.epi != EPI_LN || (a.N % 256 == 0 && a.N <= 1024), "dec_linear: LayerNorm epilogue needs N %% 256 == 0, N <= 1024");
+  const dim3 grid(nblk, a.splits);
+  switch ((a.M + 15) / 16) {
+    case 1: hipLaunchKernelGGL(dmx_dec_linear_kernel<1>, grid, dim3(256), 0, stream, a); break;
+    case 2: hipLaunchKernelGGL(dmx_dec_linear_kernel<2>, grid, dim3(256), 0, stream, a); break;
+    case 3: hipLaunchKernelGGL(dmx_dec_linear_kernel<3>, grid, dim3(256), 0, stream, a); break;
+    default: hipLaunchKernelGGL(dmx_dec_linear_kernel<4>, grid, dim3(256), 0, stream, a); break;
+  }
+  return dmx_check_launch("dmx_dec_linear_kernel");
+}
+}  // namespace
+
+namespace {
+struct DecLayer { size_t wqkv, bqkv, wo, bo, l1g, l1b, wcq, bcq, wco, bco, l2g, l2b, w1, b1, w2, b2, l3g, l3b; };
+constexpr int kLaunchesPerLayer = 8;
+
+// split-K plan of one weight-streaming linear: enough blocks to cover the CUs several times over, partials bounded at large M
+int plan_kchunk(int N, int K, int M, int epi) {
+  if (epi == EPI_PICK) return K;
+  const int nblk = cdiv(N, 64);
+  int sp = std::min(K / 128, std::max(1, 1024 / nblk));
+  sp = std::max(1, std::min(sp, std::max(2, 256 / M)));
+  return (int)align_up((size_t)cdiv(K, sp), 128);
+}
+size_t lin_part_floats(int N, int K, int M, int epi) {
+  const int kc = plan_kchunk(N, K, M, epi), sp = cdiv(K, kc);
+  return sp > 1 ? (size_t)sp * M * N : 0;
+}
+}  // namespace
+
+struct dmx_trocr_dec {
+  dmx_trocr_dec_config cfg;
+  ParamTable pt;
+  char* arena = nullptr;
+  bool finalized = false;
+  size_t emb, posw, leg = 0, leb = 0, wckv, bckv, lm;
+  int npos = 0, kdim = 0, cnt_slice = 0;
+  std::vector<DecLayer> layers;
+  template <typename T> T* at(size_t off) const { return (T*)(arena + off); }
+};
+
+namespace {
+struct DecLayout {                   // byte offsets in the cache / workspace
+  size_t words, kv, ckv, cache_total;
+  size_t xf, xb, qf, ab, hb, pre, part, apart, pv, pi, encb, gemm_ws, step_total, ws_total;
+  int nch_self, nch_cross, lm_blocks;
+};
+DecLayout dec_layout(const dmx_trocr_dec* d, int B, int S, int max_len) {
+  const dmx_trocr_dec_config& c = d->cfg;
+  const int D = c.d_model, F = c.ffn_dim, L = c.num_layers, H = D / 64, V = c.vocab_size;
+  DecLayout y{};
+  const int nslices = kLaunchesPerLayer * L + 1;
+  y.words = 0;
+  y.kv = align_up(((size_t)ST_INTS + (size_t)nslices * d->cnt_slice) * 4, 256);
+  y.ckv = y.kv + align_up((size_t)L * B * max_len * 2 * D * 2, 256);
+  y.cache_total = y.ckv + align_up((size_t)B * S * L * 2 * D * 2, 256);
+  y.nch_self = cdiv(max_len, 64); y.nch_cross = cdiv(S, 64); y.lm_blocks = cdiv(V, 64);
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t r = o; o += align_up(bytes, 256); return r; };
+  y.xf = take((size_t)B * D * 4); y.xb = take((size_t)B * D * 2); y.qf = take((size_t)B * D * 4); y.ab = take((size_t)B * D * 2);
+  y.hb = take((size_t)B * F * 2); y.pre = take((size_t)B * D * 4);
+  size_t pf = 0;
+  pf = std::max(pf, lin_part_floats(3 * D, D, B, EPI_QKV));
+  pf = std::max(pf, lin_part_floats(D, D, B, EPI_LN));
+  pf = std::max(pf, lin_part_floats(D, D, B, EPI_STORE));
+  pf = std::max(pf, lin_part_floats(F, D, B, EPI_STORE));
+  pf = std::max(pf, lin_part_floats(D, F, B, EPI_LN));
+  y.part = take(pf * 4 + 4);
+  y.apart = take((size_t)B * H * std::max(y.nch_self, y.nch_cross) * 66 * 4);
+  y.pv = take((size_t)B * y.lm_blocks * 4); y.pi = take((size_t)B * y.lm_blocks * 4);
+  y.step_total = o;
+  // cross K/V (dmx_trocr_dec_cross_kv, before the steps): the bf16 encoder states and the GEMM's own workspace, from offset 0
+  o = 0;
+  y.encb = take((size_t)B * S * d->kdim * 2);
+  y.gemm_ws = o;
+  Exec ex; ex.dry = true; ex.ws.reset(nullptr, 0, true);
+  ex.gemm_raw(nullptr, d->kdim, B * S, nullptr, d->kdim, 2 * L * D, d->kdim, nullptr, nullptr, 2 * L * D, 0);
+  y.ws_total = std::max(y.step_total, y.gemm_ws + ex.ws.peak() + 4096);
+  return y;
+}
+
+int dec_attn_launch(const DecAttn& a0, int M, hipStream_t stream) {
+  DecAttn a = a0; a.M = M;
+  hipLaunchKernelGGL(dmx_dec_attn_kernel, dim3(a.nch, a.H, M), dim3(64), 0, stream, a);
+  return dmx_check_launch("dmx_dec_attn_kernel");
+}
+
+DecLin lin_base(const bf16* x, int M, int K, const bf16* w, int N, const float* bias, int epi, int* cnt, float* part) {
+  DecLin a{};
+  a.x = x; a.ldx = K; a.w = w; a.ldw = K; a.bias = bias; a.M = M; a.N = N; a.K = K; a.epi = epi; a.cnt = cnt; a.part = part;
+  a.kchunk = plan_kchunk(N, K, M, epi); a.splits = cdiv(K, a.kchunk); a.oscale = 1.f; a.eps = 1e-5f; a.eos = -1;
+  return a;
+}
+
+int dec_step(dmx_trocr_dec* d, char* cache, int B, int S, int max_len, int eos, int pad, long long* ids, float* logits, int ldl,
+             char* ws, size_t ws_bytes, hipStream_t st) {
+  const dmx_trocr_dec_config& c = d->cfg;
+  const int D = c.d_model, F = c.ffn_dim, L = c.num_layers, H = D / 64, V = c.vocab_size;
+  const DecLayout y = dec_layout(d, B, S, max_len);
+  DMX_REQUIRE(ws_bytes >= y.ws_total, "trocr_dec_step: workspace %zu < %zu bytes", ws_bytes, y.ws_total);
+  int* state = (int*)(cache + y.words);
+  int* cnt = state + ST_INTS;
+  int slice = 0;
+  auto next_cnt = [&]() { return cnt + (size_t)(slice++) * d->cnt_slice; };
+  float* xf = (float*)(ws + y.xf); bf16* xb = (bf16*)(ws + y.xb); float* qf = (float*)(ws + y.qf); bf16* ab = (bf16*)(ws + y.ab);
+  bf16* hb = (bf16*)(ws + y.hb); float* pre = (float*)(ws + y.pre); float* part = (float*)(ws + y.part); float* apart = (float*)(ws + y.apart);
+  bf16* kv = (bf16*)(cache + y.kv); const bf16* ckv = (const bf16*)(cache + y.ckv);
+  const float qscale = 0.125f;                                   // head_dim ** -0.5, head_dim = 64
+  const float escale = c.scale_embedding ? sqrtf((float)D) : 1.0f;
+  hipLaunchKernelGGL(dmx_dec_embed_kernel, dim3(B), dim3(64), 0, st, state, d->at<bf16>(d->emb), V, d->at<float>(d->posw), d->npos, escale,
+                     c.layernorm_embedding ? d->at<float>(d->leg) : nullptr, c.layernorm_embedding ? d->at<float>(d->leb) : nullptr, D, xf, xb);
+  int rc = dmx_check_launch("dmx_dec_embed_kernel");
+  const int act = c.activation == 1 ? ACT_RELU : ACT_GELU;
+  for (int l = 0; l < L && !rc; ++l) {
+    const DecLayer& W = d->layers[l];
+    bf16* kvl = kv + (size_t)l * B * max_len * 2 * D;
+    DecLin a = lin_base(xb, B, D, d->at<bf16>(W.wqkv), 3 * D, d->at<float>(W.bqkv), EPI_QKV, next_cnt(), part);
+    a.oscale = qscale; a.yf = qf; a.ldyf = D; a.kv = kvl; a.kv_bstride = (long long)max_len * 2 * D; a.state = state; a.D = D; a.max_len = max_len;
+    if ((rc = dec_linear_launch(a, st))) break;
+    DecAttn t{};
+    t.q = qf; t.ldq = D; t.kv = kvl; t.bstride = (long long)max_len * 2 * D; t.rstride = 2 * D; t.state = state; t.L = max_len; t.H = H; t.D = D;
+    t.nch = y.nch_self; t.part = apart; t.cnt = next_cnt(); t.o = ab; t.ldo = D;
+    if ((rc = dec_attn_launch(t, B, st))) break;
+    a = lin_base(ab, B, D, d->at<bf16>(W.wo), D, d->at<float>(W.bo), EPI_LN, next_cnt(), part);
+    a.res = xf; a.pre = pre; a.gamma = d->at<float>(W.l1g); a.beta = d->at<float>(W.l1b); a.yf = xf; a.yb = xb;
+    if ((rc = dec_linear_launch(a, st))) break;
+    a = lin_base(xb, B, D, d->at<bf16>(W.wcq), D, d->at<float>(W.bcq), EPI_STORE, next_cnt(), part);
+    a.oscale = qscale; a.yf = qf; a.ldyf = D;
+    if ((rc = dec_linear_launch(a, st))) break;
+    t.kv = ckv + (size_t)l * 2 * D; t.bstride = (long long)S * L * 2 * D; t.rstride = L * 2 * D; t.state = nullptr; t.L = S;
+    t.nch = y.nch_cross; t.cnt = next_cnt();
+    if ((rc = dec_attn_launch(t, B, st))) break;
+    a = lin_base(ab, B, D, d->at<bf16>(W.wco), D, d->at<float>(W.bco), EPI_LN, next_cnt(), part);
+    a.res = xf; a.pre = pre; a.gamma = d->at<float>(W.l2g); a.beta = d->at<float>(W.l2b); a.yf = xf; a.yb = xb;
+    if ((rc = dec_linear_launch(a, st))) break;
+    a = lin_base(xb, B, D, d->at<bf16>(W.w1), F, d->at<float>(W.b1), EPI_STORE, next_cnt(), part);
+    a.act = act; a.yb = hb; a.ldyb = F;
+    if ((rc = dec_linear_launch(a, st))) break;
+    a = lin_base(hb, B, F, d->at<bf16>(W.w2), D, d->at<float>(W.b2), EPI_LN, next_cnt(), part);
+    a.res = xf; a.pre = pre; a.gamma = d->at<float>(W.l3g); a.beta = d->at<float>(W.l3b); a.yf = xf; a.yb = xb;
+    if ((rc = dec_linear_launch(a, st))) break;
+  }
+  if (rc) return rc;
+  DecLin a = lin_base(xb, B, D, d->at<bf16>(d->lm), V, nullptr, EPI_PICK, next_cnt(), part);
+  a.yf = logits; a.ldyf = ldl; a.pv = (float*)(ws + y.pv); a.pi = (int*)(ws + y.pi); a.ids = ids; a.max_len = max_len;
+  a.eos = eos; a.pad = pad; a.state = state;
+  return dec_linear_launch(a, st);
+}
+}  // namespace
+
+extern "C" dmx_trocr_dec* dmx_trocr_dec_create(const dmx_trocr_dec_config* cfg) {
+  if (!cfg) { dmx_set_error("trocr_dec_create: null config"); return nullptr; }
+  const int D = cfg->d_model, F = cfg->ffn_dim, L = cfg->num_layers, V = cfg->vocab_size;
+  const int kdim = cfg->cross_hidden_size > 0 ? cfg->cross_hidden_size : D;
+  if (D % 256 != 0 || D > 1024 || cfg->num_heads != D / 64) { dmx_set_error("trocr_dec_create: d_model=%d heads=%d: head dim must be 64, d_model a multiple of 256 and <= 1024", D, cfg->num_heads); return nullptr; }
+  if (F % 128 != 0 || kdim % 64 != 0 || L <= 0 || V <= 0 || cfg->max_position_embeddings <= 0) { dmx_set_error("trocr_dec_create: bad ffn_dim / cross size / layers / vocab"); return nullptr; }
+  if (cfg->activation != 0 && cfg->activation != 1) { dmx_set_error("trocr_dec_create: activation %d (0 gelu, 1 relu)", cfg->activation); return nullptr; }
+  auto d = std::make_unique<dmx_trocr_dec>();
+  d->cfg = *cfg; d->kdim = kdim; d->npos = cfg->max_position_embeddings + 2;
+  d->cnt_slice = (int)align_up((size_t)std::max(cdiv(std::max(V, std::max(3 * D, F)), 64) + 1, 64 * (D / 64)), 64);
+  ParamTable& pt = d->pt;
+  const std::string p0 = "model.decoder.";
+  d->emb = pt.linear(p0 + "embed_tokens.weight", V, D);
+  { PackRule r; r.kind = PackRule::COPY_F32; r.dst = pt.reserve((size_t)d->npos * D * 4); r.rows = d->npos * D; pt.add(p0 + "embed_positions.weight", {d->npos, D}, r); d->posw = r.dst; }
+  if (cfg->layernorm_embedding) { d->leg = pt.f32(p0 + "layernorm_embedding.weight", D); d->leb = pt.f32(p0 + "layernorm_embedding.bias", D); }
+  d->wckv = pt.reserve((size_t)L * 2 * D * kdim * 2);
+  d->bckv = pt.reserve((size_t)L * 2 * D * 4);
+  d->layers.resize(L);
+  for (int i = 0; i < L; ++i) {
+    DecLayer& W = d->layers[i];
+    const std::string p = p0 + "layers." + std::to_string(i) + ".";
+    W.wqkv = pt.reserve((size_t)3 * D * D * 2); W.bqkv = pt.reserve((size_t)3 * D * 4);
+    // transformers' state-dict order: k, v, q; packed q | k | v
+    pt.linear_at(p + "self_attn.k_proj.weight", D, D, W.wqkv + (size_t)D * D * 2, D); pt.f32_at(p + "self_attn.k_proj.bias", D, W.bqkv + (size_t)D * 4);
+    pt.linear_at(p + "self_attn.v_proj.weight", D, D, W.wqkv + (size_t)2 * D * D * 2, D); pt.f32_at(p + "self_attn.v_proj.bias", D, W.bqkv + (size_t)2 * D * 4);
+    pt.linear_at(p + "self_attn.q_proj.weight", D, D, W.wqkv, D); pt.f32_at(p + "self_attn.q_proj.bias", D, W.bqkv);
+    W.wo = pt.linear(p + "self_attn.out_proj.weight", D, D); W.bo = pt.f32(p + "self_attn.out_proj.bias", D);
+    W.l1g = pt.f32(p + "self_attn_layer_norm.weight", D); W.l1b = pt.f32(p + "self_attn_layer_norm.bias", D);
+    // cross k / v of every layer: rows [l][k | v] of one [L * 2D][kdim] matrix (one GEMM per image, dmx_trocr_dec_cross_kv)
+    const size_t kr = (size_t)i * 2 * D;
+    pt.linear_at(p + "encoder_attn.k_proj.weight", D, kdim, d->wckv + kr * kdim * 2, kdim); pt.f32_at(p + "encoder_attn.k_proj.bias", D, d->bckv + kr * 4);
+    pt.linear_at(p + "encoder_attn.v_proj.weight", D, kdim, d->wckv + (kr + D) * kdim * 2, kdim); pt.f32_at(p + "encoder_attn.v_proj.bias", D, d->bckv + (kr + D) * 4);
+    W.wcq = pt.linear(p + "encoder_attn.q_proj.weight", D, D); W.bcq = pt.f32(p + "encoder_attn.q_proj.bias", D);
+    W.wco = pt.linear(p + "encoder_attn.out_proj.weight", D, D); W.bco = pt.f32(p + "encoder_attn.out_proj.bias", D);
+    W.l2g = pt.f32(p + "encoder_attn_layer_norm.weight", D); W.l2b = pt.f32(p + "encoder_attn_layer_norm.bias", D);
+    W.w1 = pt.linear(p + "fc1.weight", F, D); W.b1 = pt.f32(p + "fc1.bias", F);
+    W.w2 = pt.linear(p + "fc2.weight", D, F); W.b2 = pt.f32(p + "fc2.bias", D);
+    W.l3g = pt.f32(p + "final_layer_norm.weight", D); W.l3b = pt.f32(p + "final_layer_norm.bias", D);
+  }
+  d->lm = cfg->tie_word_embeddings ? d->emb : pt.linear("output_projection.weight", V, D);
+  return d.release();
+}
+extern "C" void dmx_trocr_dec_destroy(dmx_trocr_dec* d) { delete d; }
+extern "C" int dmx_trocr_dec_param_count(const dmx_trocr_dec* d) { return d ? (int)d->pt.entries().size() : 0; }
+extern "C" int dmx_trocr_dec_param_info(const dmx_trocr_dec* d, int index, const char** name, int shape[4]) {
+  DMX_REQUIRE(d && index >= 0 && index < (int)d->pt.entries().size(), "trocr_dec_param_info: bad index %d", index);
+  const ParamEntry& e = d->pt.entries()[index];
+  if (name) *name = e.name.c_str();
+  if (shape) for (int k = 0; k < 4; ++k) shape[k] = e.shape[k];
+  return DMX_OK;
+}
+extern "C" size_t dmx_trocr_dec_arena_bytes(const dmx_trocr_dec* d) { return d ? d->pt.total() : 0; }
+extern "C" int dmx_trocr_dec_bind_arena(dmx_trocr_dec* d, void* arena, size_t bytes) {
+  DMX_REQUIRE(d && arena && bytes >= d->pt.total(), "trocr_dec_bind_arena: need %zu bytes", d ? d->pt.total() : (size_t)0);
+  d->arena = (char*)arena; d->finalized = false;
+  DMX_HIP(hipMemset(arena, 0, d->pt.total()));
+  return DMX_OK;
+}
+extern "C" int dmx_trocr_dec_load_param(dmx_trocr_dec* d, const char* name, const float* src, dmx_stream_t stream) {
+  DMX_REQUIRE(d != nullptr, "trocr_dec_load_param: null handle");
+  d->finalized = false;
+  return d->pt.load(d->arena, name, src, (hipStream_t)stream);
+}
+extern "C" int dmx_trocr_dec_finalize(dmx_trocr_dec* d, dmx_stream_t stream) {
+  DMX_REQUIRE(d && d->arena, "trocr_dec_finalize: arena not bound");
+  DMX_HIP(hipStreamSynchronize((hipStream_t)stream));
+  d->finalized = true;
+  return DMX_OK;
+}
+extern "C" size_t dmx_trocr_dec_cache_bytes(const dmx_trocr_dec* d, int B, int S, int max_len) {
+  return d ? dec_layout(d, B, S, max_len).cache_total : 0;
+}
+extern "C" size_t dmx_trocr_dec_workspace_bytes(const dmx_trocr_dec* d, int B, int S, int max_len) {
+  return d ? dec_layout(d, B, S, max_len).ws_total : 0;
+}
+extern "C" int dmx_trocr_dec_launches_per_step(const dmx_trocr_dec* d) { return d ? 2 + kLaunchesPerLayer * d->cfg.num_layers : 0; }
+
+extern "C" int dmx_trocr_dec_cross_kv(dmx_trocr_dec* d, const float* enc, int B, int S, int max_len, void* cache, void* ws, size_t ws_bytes,
+                                      dmx_stream_t stream) {
+  DMX_REQUIRE(d && d->finalized, "trocr_dec_cross_kv: weights not finalized (bind_arena, load_param*, finalize)");
+  DMX_REQUIRE(enc && cache && ws && B >= 1 && B <= 64 && S >= 1 && max_len >= 1 && max_len <= d->cfg.max_position_embeddings,
+              "trocr_dec_cross_kv: bad argument (B=%d S=%d max_len=%d)", B, S, max_len);
+  const DecLayout y = dec_layout(d, B, S, max_len);
+  DMX_REQUIRE(ws_bytes >= y.ws_total, "trocr_dec_cross_kv: workspace %zu < %zu bytes", ws_bytes, y.ws_total);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)B * S * d->kdim;
+  bf16* eb = (bf16*)((char*)ws + y.encb);
+  hipLaunchKernelGGL(dmx_f32_to_bf16_kernel, dim3((unsigned)std::min<size_t>(8192, (n + 255) / 256)), dim3(256), 0, st, enc, eb, n);
+  int rc = dmx_check_launch("dmx_f32_to_bf16_kernel");
+  if (rc) return rc;
+  Exec ex; ex.stream = st; ex.ws.reset((char*)ws + y.gemm_ws, ws_bytes - y.gemm_ws, false);
+  const int N = 2 * d->cfg.num_layers * d->cfg.d_model;
+  ex.gemm_raw(eb, d->kdim, B * S, d->at<bf16>(d->wckv), d->kdim, N, d->kdim, d->at<float>(d->bckv), (char*)cache + y.ckv, N, 0);
+  return ex.rc;
+}
+extern "C" int dmx_trocr_dec_reset(dmx_trocr_dec* d, void* cache, int B, int S, int max_len, int start_token, long long* ids, dmx_stream_t stream) {
+  DMX_REQUIRE(d && cache && B >= 1 && B <= 64, "trocr_dec_reset: bad argument");
+  const DecLayout y = dec_layout(d, B, S, max_len);
+  const size_t nwords = (y.kv - y.words) / 4;
+  hipLaunchKernelGGL(dmx_dec_reset_kernel, dim3((unsigned)std::min<size_t>(1024, (nwords + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (int*)((char*)cache + y.words), nwords, B, start_token, ids, max_len);
+  return dmx_check_launch("dmx_dec_reset_kernel");
+}
+extern "C" int dmx_trocr_dec_set_tokens(dmx_trocr_dec* d, void* cache, const long long* tokens, int B, dmx_stream_t stream) {
+  DMX_REQUIRE(d && cache && tokens && B >= 1 && B <= 64, "trocr_dec_set_tokens: bad argument");
+  hipLaunchKernelGGL(dmx_i64_to_i32_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, tokens, (int*)cache + ST_TOK, B);
+  return dmx_check_launch("dmx_i64_to_i32_kernel");
+}
+extern "C" int dmx_trocr_dec_step(dmx_trocr_dec* d, void* cache, int B, int S, int max_len, int eos_token_id, int pad_token_id,
+                                  long long* ids, float* logits, int ld_logits, void* ws, size_t ws_bytes, dmx_stream_t stream) {
+  DMX_REQUIRE(d && d->finalized, "trocr_dec_step: weights not finalized (bind_arena, load_param*, finalize)");
+  DMX_REQUIRE(cache && ids && ws && B >= 1 && B <= 64 && S >= 1 && max_len >= 1 && max_len <= d->cfg.max_position_embeddings,
+              "trocr_dec_step: bad argument (B=%d S=%d max_len=%d)", B, S, max_len);
+  DMX_REQUIRE(!logits || ld_logits >= d->cfg.vocab_size, "trocr_dec_step: ld_logits %d < vocab %d", ld_logits, d->cfg.vocab_size);
+  return dec_step(d, (char*)cache, B, S, max_len, eos_token_id, pad_token_id, ids, logits, ld_logits, (char*)ws, ws_bytes, (hipStream_t)stream);
+}
+
+// ---- op entry points (tests / benchmarks): one weight-streaming linear with a chosen epilogue, one decode attention
+extern "C" size_t dmx_trocr_dec_linear_workspace_bytes(int M, int N, int K) {
+  const size_t nblk = (size_t)cdiv(N, 64);
+  return align_up((nblk + 1) * 4, 256) + align_up((size_t)(K / 128) * M * N * 4, 256) + align_up((size_t)M * N * 4, 256) + 2 * align_up((size_t)M * nblk * 4, 256);
+}
+extern "C" int dmx_trocr_dec_linear(int epi, int act, const void* x, int M, int K, const void* w, int N, const float* bias, float oscale,
+                                    float* yf, int ldyf, void* yb, const float* res, const float* gamma, const float* beta,
+                                    void* kv, int max_len, int* state, long long* ids, int eos, int pad, int kchunk,
+                                    void* ws, size_t ws_bytes, dmx_stream_t stream) {
+  DMX_REQUIRE(x && w && ws && epi >= 0 && epi <= 3 && M >= 1 && M <= 64 && N >= 1 && K >= 128, "trocr_dec_linear: bad argument");
+  DMX_REQUIRE(ws_bytes >= dmx_trocr_dec_linear_workspace_bytes(M, N, K), "trocr_dec_linear: workspace too small");
+  DMX_REQUIRE(epi != EPI_QKV || (N % 3 == 0 && yf && kv && state), "trocr_dec_linear: q|k|v epilogue needs N = 3D, yf, kv, state");
+  DMX_REQUIRE(epi != EPI_LN || (res && gamma && beta && yf && yb), "trocr_dec_linear: LayerNorm epilogue needs res, gamma, beta, yf, yb");
+  DMX_REQUIRE(epi != EPI_PICK || (state && ids && max_len >= 1), "trocr_dec_linear: pick epilogue needs state, ids");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t nblk = (size_t)cdiv(N, 64);
+  char* p = (char*)ws;
+  int* cnt = (int*)p; p += align_up((nblk + 1) * 4, 256);
+  float* part = (float*)p; p += align_up((size_t)(K / 128) * M * N * 4, 256);
+  float* pre = (float*)p; p += align_up((size_t)M * N * 4, 256);
+  float* pv = (float*)p; p += align_up((size_t)M * nblk * 4, 256);
+  int* pi = (int*)p;
+  hipLaunchKernelGGL(dmx_dec_reset_kernel, dim3(1), dim3(256), 0, st, cnt, nblk + 1, 0, 0, (long long*)nullptr, 1);
+  int rc = dmx_check_launch("dmx_dec_reset_kernel");
+  if (rc) return rc;
+  DecLin a = lin_base((const bf16*)x, M, K, (const bf16*)w, N, bias, epi, cnt, part);
+  if (kchunk > 0) { a.kchunk = kchunk; a.splits = cdiv(K, kchunk); }
+  a.act = act; a.oscale = oscale; a.yf = yf; a.ldyf = ldyf; a.yb = (bf16*)yb; a.ldyb = N;
+  if (epi == EPI_QKV) { a.D = N / 3; a.ldyf = a.D; a.kv = (bf16*)kv; a.kv_bstride = (long long)max_len * 2 * a.D; a.state = state; a.max_len = max_len; }
+  if (epi == EPI_LN) { a.res = res; a.pre = pre; a.gamma = gamma; a.beta = beta; a.ldyb = N; }
+  if (epi == EPI_PICK) { a.pv = pv; a.pi = pi; a.ids = ids; a.max_len = max_len; a.eos = eos; a.pad = pad; a.state = state; }
+  return dec_linear_launch(a, st);
+}
+extern "C" size_t dmx_trocr_dec_attn_workspace_bytes(int M, int H, int L) {
+  return align_up((size_t)M * H * 4, 256) + (size_t)M * H * cdiv(L, 64) * 66 * 4;
+}
+extern "C" int dmx_trocr_dec_attn(const float* q, int M, int H, const void* kv, long long bstride, int rstride, int L, void* out,
+                                  void* ws, size_t ws_bytes, dmx_stream_t stream) {
+  DMX_REQUIRE(q && kv && out && ws && M >= 1 && H >= 1 && L >= 1 && rstride >= 2 * H * 64, "trocr_dec_attn: bad argument");
+  DMX_REQUIRE(ws_bytes >= dmx_trocr_dec_attn_workspace_bytes(M, H, L), "trocr_dec_attn: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  int* cnt = (int*)ws;
+  hipLaunchKernelGGL(dmx_dec_reset_kernel, dim3(1), dim3(256), 0, st, cnt, (size_t)M * H, 0, 0, (long long*)nullptr, 1);
+  int rc = dmx_check_launch("dmx_dec_reset_kernel");
+  if (rc) return rc;
+  DecAttn t{};
+  t.q = q; t.ldq = H * 64; t.kv = (const bf16*)kv; t.bstride = bstride; t.rstride = rstride; t.state = nullptr; t.L = L; t.H = H; t.D = H * 64;
+  t.nch = cdiv(L, 64); t.part = (float*)((char*)ws + align_up((size_t)M * H * 4, 256)); t.cnt = cnt; t.o = (bf16*)out; t.ldo = H * 64;
+  return dec_attn_launch(t, M, st);
+}

@@ -1,0 +1,330 @@
+"""OCR read-back: TrOCR's text decoder and the encoder-decoder wrapper the reference loads as `full_trocr_model`.
+
+app.ipynb:547-548 builds two models from `trocr-large-printed`: `.encoder` (the glyph encoder, `TrOCREncoder`) and the full
+`VisionEncoderDecoderModel`, whose `generate(pixel_values)` reads an edited box back as token ids (app.ipynb:842-847; the
+tokenizer's `batch_decode` stays with the caller).  `from diffute_amd import VisionEncoderDecoderModel` serves both.
+Greedy generation follows transformers' `generate(num_beams=1, do_sample=False)`; every FLOP runs in the gfx950 library.
+"""
+import ctypes
+import json
+import os
+
+import torch
+from torch import nn
+
+from . import _cabi
+from .models import TROCR_LARGE_VIT_CONFIG, TrOCREncoder, _Config, _HipModel
+
+# transformers' TrOCRConfig defaults = the trocr-large decoder
+TROCR_LARGE_DECODER_CONFIG = dict(
+    vocab_size=50265, d_model=1024, decoder_layers=12, decoder_attention_heads=16, decoder_ffn_dim=4096, activation_function="gelu",
+    max_position_embeddings=512, scale_embedding=False, use_learned_position_embeddings=True, layernorm_embedding=True,
+    tie_word_embeddings=True, cross_attention_hidden_size=None, decoder_start_token_id=2, eos_token_id=2, pad_token_id=1, bos_token_id=0)
+
+# generation settings whose non-default values select search / processing this library does not implement
+_GEN_UNSUPPORTED = dict(num_beams=1, do_sample=False, num_beam_groups=1, no_repeat_ngram_size=0, length_penalty=1.0, min_length=0,
+                        min_new_tokens=None, forced_bos_token_id=None, forced_eos_token_id=None, repetition_penalty=1.0,
+                        early_stopping=False, penalty_alpha=None, num_return_sequences=1, temperature=1.0, top_k=50, top_p=1.0,
+                        bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, encoder_no_repeat_ngram_size=0)
+
+# settings that only beam search reads: inert when greedy search runs (num_beams == 1)
+_BEAM_ONLY = ("early_stopping", "length_penalty", "num_beam_groups")
+
+POLL_EVERY = 4          # generate() reads the device's all-finished flag (copied asynchronously) every POLL_EVERY steps
+
+
+class CausalLMOutput:
+    def __init__(self, logits):
+        self.logits = logits
+
+
+class TrOCRForCausalLM(_HipModel):
+    """TrOCR's text decoder (transformers `TrOCRForCausalLM`; the `.decoder` of app.ipynb:548's `full_trocr_model`).  Parameters
+    carry transformers' state-dict keys; `output_projection.weight` exists only when the config unties it from `embed_tokens`.
+    Forward-only."""
+    _kind = "trocr_dec"
+
+    def __init__(self, seed=555, device="cpu", **config):
+        super().__init__()
+        cfg = dict(TROCR_LARGE_DECODER_CONFIG)
+        cfg.update({k: v for k, v in config.items() if k in TROCR_LARGE_DECODER_CONFIG})
+        if not cfg["use_learned_position_embeddings"]:
+            raise NotImplementedError("TrOCRForCausalLM: sinusoidal position embeddings are not implemented (use_learned_position_embeddings=False)")
+        if cfg["activation_function"] not in ("gelu", "relu"):
+            raise NotImplementedError(f"TrOCRForCausalLM: activation_function={cfg['activation_function']!r} is not implemented (gelu, relu)")
+        if cfg["max_position_embeddings"] > 512:
+            raise NotImplementedError("TrOCRForCausalLM: more than 512 positions are not implemented")
+        self.config = _Config(**cfg)
+        c = _cabi.TrOCRDecConfig()
+        c.vocab_size = cfg["vocab_size"]; c.d_model = cfg["d_model"]; c.num_layers = cfg["decoder_layers"]
+        c.num_heads = cfg["decoder_attention_heads"]; c.ffn_dim = cfg["decoder_ffn_dim"]; c.max_position_embeddings = cfg["max_position_embeddings"]
+        c.cross_hidden_size = int(cfg["cross_attention_hidden_size"] or 0)
+        c.activation = 1 if cfg["activation_function"] == "relu" else 0
+        c.scale_embedding = int(bool(cfg["scale_embedding"])); c.layernorm_embedding = int(bool(cfg["layernorm_embedding"]))
+        c.tie_word_embeddings = int(bool(cfg["tie_word_embeddings"]))
+        self._cstruct = c
+        h = self._create_handle("bf16")
+        self._setup(h, seed, device)
+        self.requires_grad_(False)
+        self._runs = {}
+
+    def _finalize(self, st):
+        _cabi.check(self._lib.dmx_trocr_dec_finalize(self._h, st), "trocr_dec_finalize")
+        self._runs = {}
+
+    def _switch_build(self, elem):
+        if elem != "bf16":
+            raise NotImplementedError("TrOCRForCausalLM: the decoder runs on the bf16 build")
+
+    @property
+    def launches_per_step(self):
+        return int(self._lib.dmx_trocr_dec_launches_per_step(self._h))
+
+    # ---- buffers of one (B, S, max_len): cache (state words, self / cross K/V), workspace, output ids, optional logits row
+    def _run(self, B, S, max_len):
+        key = (B, S, max_len)
+        r = self._runs.get(key)
+        if r is None:
+            lib, dev = self._lib, self.device
+            r = dict(cache=torch.empty(lib.dmx_trocr_dec_cache_bytes(self._h, B, S, max_len), dtype=torch.uint8, device=dev),
+                     ws=torch.empty(lib.dmx_trocr_dec_workspace_bytes(self._h, B, S, max_len), dtype=torch.uint8, device=dev),
+                     ids=torch.zeros(B, max_len, dtype=torch.int64, device=dev),
+                     logits=torch.empty(B, self.config.vocab_size, dtype=torch.float32, device=dev), graphs={})
+            self._runs[key] = r
+        return r
+
+    def _begin(self, r, enc, max_len, start):
+        lib = self._lib
+        B, S = enc.shape[0], enc.shape[1]
+        st = _cabi.current_stream()
+        _cabi.check(lib.dmx_trocr_dec_cross_kv(self._h, _cabi.ptr(enc), B, S, max_len, _cabi.ptr(r["cache"]), _cabi.ptr(r["ws"]),
+                                               r["ws"].numel(), st), "trocr_dec_cross_kv")
+        _cabi.check(lib.dmx_trocr_dec_reset(self._h, _cabi.ptr(r["cache"]), B, S, max_len, int(start), _cabi.ptr(r["ids"]), st), "trocr_dec_reset")
+
+    def _step(self, r, B, S, max_len, eos, pad, logits, ld):
+        _cabi.check(self._lib.dmx_trocr_dec_step(self._h, _cabi.ptr(r["cache"]), B, S, max_len, int(eos), int(pad), _cabi.ptr(r["ids"]),
+                                                 None if logits is None else ctypes.c_void_p(logits), ld, _cabi.ptr(r["ws"]),
+                                                 r["ws"].numel(), _cabi.current_stream()), "trocr_dec_step")
+
+    def _check_inputs(self, enc):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("diffute_amd: the OCR decoder is forward-only")
+        _cabi.require_cuda(enc)
+        kdim = self.config.cross_attention_hidden_size or self.config.d_model
+        if enc.ndim != 3 or enc.shape[2] != kdim:
+            raise ValueError(f"encoder_hidden_states must be [B, S, {kdim}], got {tuple(enc.shape)}")
+        if not 1 <= enc.shape[0] <= 64:
+            raise ValueError(f"TrOCRForCausalLM: 1 <= batch <= 64 rows, got {enc.shape[0]}")
+        self._ensure_packed()
+        return enc.to(torch.float32).contiguous()
+
+    @torch.no_grad()
+    def forward(self, input_ids, encoder_hidden_states, return_dict=True, **unused):
+        """teacher-forced logits [B, T, V] (fp32) of input_ids [B, T]: the decode step run T times over the KV cache"""
+        enc = self._check_inputs(encoder_hidden_states)
+        ids = input_ids.to(device=enc.device, dtype=torch.int64).contiguous()
+        B, T = ids.shape
+        if ids.shape[0] != enc.shape[0] or not 1 <= T <= self.config.max_position_embeddings:
+            raise ValueError(f"input_ids must be [B, T] with B = {enc.shape[0]} and 1 <= T <= {self.config.max_position_embeddings}")
+        V = self.config.vocab_size
+        r = self._run(B, enc.shape[1], T)
+        out = torch.empty(B, T, V, dtype=torch.float32, device=enc.device)
+        self._begin(r, enc, T, 0)
+        lib, st = self._lib, _cabi.current_stream()
+        for t in range(T):
+            col = ids[:, t].contiguous()
+            _cabi.check(lib.dmx_trocr_dec_set_tokens(self._h, _cabi.ptr(r["cache"]), _cabi.ptr(col), B, st), "trocr_dec_set_tokens")
+            self._step(r, B, enc.shape[1], T, -1, 0, out.data_ptr() + t * V * 4, T * V)
+        return CausalLMOutput(out) if return_dict else (out,)
+
+    @torch.no_grad()
+    def greedy(self, encoder_hidden_states, max_length, decoder_start_token_id, eos_token_id, pad_token_id, use_graph=True, keep_logits=False):
+        """greedy ids [B, L] (L <= max_length, counting the start token), as transformers' greedy search; with keep_logits also the
+        fp32 logits [B, L - 1, V] of every step"""
+        enc = self._check_inputs(encoder_hidden_states)
+        B, S = enc.shape[0], enc.shape[1]
+        if not 1 <= max_length <= self.config.max_position_embeddings:
+            raise ValueError(f"max_length={max_length}: the decoder has {self.config.max_position_embeddings} positions")
+        eos = -1 if eos_token_id is None else int(eos_token_id)
+        pad = eos if pad_token_id is None else int(pad_token_id)
+        if pad < 0:
+            pad = 0
+        r = self._run(B, S, max_length)
+        self._begin(r, enc, max_length, decoder_start_token_id)
+        n_steps = max_length - 1
+        if n_steps == 0:
+            return r["ids"][:, :1].clone(), None
+        V = self.config.vocab_size
+        lg = r["logits"] if keep_logits else None
+        lg_ptr = None if lg is None else lg.data_ptr()
+        main = torch.cuda.current_stream()
+        if use_graph:
+            gkey = (eos, pad, keep_logits)
+            g = r["graphs"].get(gkey)
+            if g is None:
+                # one linear chain of kernels, captured on a side stream; the tokens, the position and the counters live in device
+                # memory, so the same graph replays every step
+                side = torch.cuda.Stream(device=enc.device)
+                side.wait_stream(main)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                    self._step(r, B, S, max_length, eos, pad, lg_ptr, V)
+                main.wait_stream(side)
+                r["graphs"][gkey] = g
+        state = r["cache"][:16].view(torch.int32)
+        # every POLL_EVERY steps the all-finished flag is copied to pinned memory behind an event; before more steps are enqueued
+        # the host waits for the copy of POLL_EVERY steps back, so at most 2 * POLL_EVERY steps are in flight and a batch that
+        # has finished stops within that many steps instead of running to max_length
+        polls, steps, kept = [], 0, []
+        while steps < n_steps:
+            if use_graph:
+                r["graphs"][gkey].replay()
+            else:
+                self._step(r, B, S, max_length, eos, pad, lg_ptr, V)
+            steps += 1
+            if keep_logits:
+                kept.append(lg.clone())
+            if steps % POLL_EVERY == 0 and steps < n_steps:
+                f = torch.empty(2, dtype=torch.int32, pin_memory=True)
+                f.copy_(state[1:3], non_blocking=True)
+                ev = torch.cuda.Event(); ev.record()
+                polls.append((ev, f))
+                if len(polls) > 1:
+                    ev0, f0 = polls.pop(0)
+                    ev0.synchronize()
+                    if int(f0[0]):
+                        break
+        flag = torch.empty(2, dtype=torch.int32)
+        flag.copy_(state[1:3])                   # (one synchronisation at the end: the stop length)
+        L = int(flag[1]) if int(flag[0]) else steps + 1
+        ids = r["ids"][:, :L].clone()
+        return ids, (torch.stack(kept[:L - 1], 1) if keep_logits else None)
+
+
+def _check_generation(settings, explicit_beams):
+    for k, want in _GEN_UNSUPPORTED.items():
+        v = settings.get(k)
+        if v is None or v == want:
+            continue
+        if k == "num_beams" and explicit_beams:
+            continue
+        if k in ("temperature", "top_k", "top_p") and not settings.get("do_sample"):
+            continue                              # sampling knobs are inert under greedy search
+        if k in _BEAM_ONLY and (explicit_beams or int(settings.get("num_beams") or 1) == 1):
+            continue                              # beam-search knobs are inert under greedy search
+        hint = "; pass num_beams=1 to run greedy search anyway" if k in ("num_beams", *_BEAM_ONLY) else \
+            " (greedy search only: remove it from the call / generation_config)"
+        raise NotImplementedError(f"VisionEncoderDecoderModel.generate: {k}={v!r} is not implemented{hint}")
+
+
+class VisionEncoderDecoderModel(nn.Module):
+    """`full_trocr_model` of app.ipynb:548: `.encoder` is the glyph encoder (`TrOCREncoder`, app.ipynb:547), `.decoder` the text
+    decoder (`TrOCRForCausalLM`); `generate(pixel_values)` (app.ipynb:845) is transformers' greedy search.  Not implemented (refused
+    where a config asks for it): beam search, sampling, logits processors (no_repeat_ngram_size, repetition_penalty, min_length,
+    forced tokens, ...), an encoder wider than the decoder's cross-attention (`enc_to_dec_proj`)."""
+
+    def __init__(self, encoder=None, decoder=None, generation_config=None):
+        super().__init__()
+        self.encoder = encoder if encoder is not None else TrOCREncoder()
+        self.decoder = decoder if decoder is not None else TrOCRForCausalLM()
+        kdim = self.decoder.config.cross_attention_hidden_size or self.decoder.config.d_model
+        if self.encoder.config.hidden_size != kdim:
+            raise NotImplementedError(f"VisionEncoderDecoderModel: encoder width {self.encoder.config.hidden_size} != cross-attention width {kdim} "
+                                      "(enc_to_dec_proj) is not implemented")
+        dc = self.decoder.config
+        gen = dict(decoder_start_token_id=dc.decoder_start_token_id, eos_token_id=dc.eos_token_id, pad_token_id=dc.pad_token_id,
+                   max_length=20, max_new_tokens=None)
+        gen.update(generation_config or {})
+        self.generation_config = _Config(**gen)
+
+    def to(self, *args, **kwargs):
+        self.encoder.to(*args, **kwargs)
+        self.decoder.to(*args, **kwargs)
+        return self
+
+    def cuda(self, device=None):
+        return self.to(torch.device("cuda" if device is None else device))
+
+    def eval(self):
+        return self
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path, subfolder=None, revision=None, **kw):
+        """transformers' VisionEncoderDecoder directory: config.json (`encoder` / `decoder` entries), generation_config.json if
+        present, model.safetensors or pytorch_model.bin with `encoder.*` / `decoder.*` keys"""
+        d = pretrained_model_name_or_path if subfolder is None else os.path.join(pretrained_model_name_or_path, subfolder)
+        with open(os.path.join(d, "config.json")) as f:
+            cfg = json.load(f)
+        ecfg, dcfg = cfg.get("encoder"), cfg.get("decoder")
+        if ecfg is None or dcfg is None:
+            raise ValueError(f"{d}: config.json has no encoder / decoder entries (not a VisionEncoderDecoder checkpoint)")
+        if ecfg.get("hidden_act", "gelu") != "gelu":
+            raise NotImplementedError(f"VisionEncoderDecoderModel: encoder hidden_act={ecfg['hidden_act']!r}")
+        encoder = TrOCREncoder(**{k: ecfg[k] for k in TROCR_LARGE_VIT_CONFIG if k in ecfg})
+        decoder = TrOCRForCausalLM(**{k: dcfg[k] for k in TROCR_LARGE_DECODER_CONFIG if k in dcfg})
+        gen = {k: cfg[k] for k in ("decoder_start_token_id", "eos_token_id", "pad_token_id", "max_length") if cfg.get(k) is not None}
+        gp = os.path.join(d, "generation_config.json")
+        if os.path.exists(gp):
+            with open(gp) as f:
+                g = json.load(f)
+            gen.update({k: v for k, v in g.items() if not k.startswith("_") and k != "transformers_version"})
+        for k in _GEN_UNSUPPORTED:                   # settings the config.json itself carries (transformers' legacy generation keys)
+            if k not in gen and cfg.get(k) is not None:
+                gen[k] = cfg[k]
+        model = cls(encoder, decoder, gen)
+        st = os.path.join(d, "model.safetensors")
+        if os.path.exists(st):
+            from safetensors.torch import load_file
+            sd = load_file(st)
+        else:
+            sd = torch.load(os.path.join(d, "pytorch_model.bin"), map_location="cpu")
+        if any(k.startswith("enc_to_dec_proj.") for k in sd):
+            raise NotImplementedError("VisionEncoderDecoderModel: enc_to_dec_proj is not implemented")
+        enc_sd = TrOCREncoder._convert_legacy_keys({k: v for k, v in sd.items() if k.startswith("encoder.")})
+        dec_sd = {k[len("decoder."):]: v for k, v in sd.items() if k.startswith("decoder.")}
+        if decoder.config.tie_word_embeddings:
+            dec_sd.pop("output_projection.weight", None)
+        encoder.load_state_dict(enc_sd)
+        decoder.load_state_dict(dec_sd)
+        return model
+
+    def _settings(self, kw):
+        g = self.generation_config.to_dict()
+        g.update({k: v for k, v in kw.items() if v is not None})
+        return g
+
+    @torch.no_grad()
+    def generate(self, pixel_values=None, *, encoder_hidden_states=None, max_new_tokens=None, max_length=None, num_beams=None,
+                 use_graph=True, **kwargs):
+        """greedy ids [B, L] (int64, on the device), L counting the decoder start token - transformers' `generate` with
+        num_beams=1, do_sample=False.  Rows that emitted eos_token_id continue with pad_token_id; generation stops when every
+        row has finished or at max_length (default 20) / 1 + max_new_tokens."""
+        unknown = set(kwargs) - set(_GEN_UNSUPPORTED) - {"decoder_start_token_id", "eos_token_id", "pad_token_id"}
+        if unknown:
+            raise TypeError(f"generate() got unexpected keyword arguments {sorted(unknown)}")
+        g = self._settings(dict(kwargs, num_beams=num_beams))
+        _check_generation(g, explicit_beams=num_beams == 1)
+        if (pixel_values is None) == (encoder_hidden_states is None):
+            raise ValueError("generate: pass exactly one of pixel_values / encoder_hidden_states")
+        if max_new_tokens is not None:
+            L = 1 + int(max_new_tokens)
+        elif max_length is not None:
+            L = int(max_length)
+        elif g.get("max_new_tokens") is not None:
+            L = 1 + int(g["max_new_tokens"])
+        else:
+            L = int(g.get("max_length") or 20)
+        if L > self.decoder.config.max_position_embeddings:
+            raise ValueError(f"generate: max_length {L} exceeds the decoder's {self.decoder.config.max_position_embeddings} positions")
+        if L < 1:
+            raise ValueError("generate: max_length must be >= 1")
+        eos = g.get("eos_token_id")
+        if isinstance(eos, (list, tuple)):
+            if len(eos) != 1:
+                raise NotImplementedError("generate: several eos_token_id values are not implemented")
+            eos = eos[0]
+        if encoder_hidden_states is None:
+            encoder_hidden_states = self.encoder(pixel_values).last_hidden_state
+        ids, _ = self.decoder.greedy(encoder_hidden_states, L, g["decoder_start_token_id"], eos, g.get("pad_token_id"),
+                                     use_graph=use_graph)
+        return ids

@@ -630,6 +630,70 @@ size_t dmx_vit_workspace_bytes_f32(dmx_vit* v, int B);
 int dmx_vit_forward_f32(dmx_vit* v, const void* masters, const float* pixel_values, float* last_hidden_state, int B,
                         void* workspace, size_t workspace_bytes, dmx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * OCR read-back (app.ipynb:548/845): the text decoder of TrOCR - transformers' TrOCRForCausalLM, the `.decoder` of
+ * `full_trocr_model = VisionEncoderDecoderModel.from_pretrained(...)` (app.ipynb:548) that `full_trocr_model_te.generate(
+ * pixel_values)` (app.ipynb:845) runs greedily.  Same handle protocol as the ViT: create, enumerate the parameters (transformers
+ * state-dict keys), bind an arena, load fp32 tensors, finalize.  The caller owns the arena, the cache and the workspace.
+ * Generation: dmx_trocr_dec_cross_kv (once per image batch), dmx_trocr_dec_reset, then dmx_trocr_dec_step per token.  A step
+ * reads the input token and the position from the cache's state words and advances them on the device, so one captured graph
+ * of dmx_trocr_dec_step replays every step.
+ * ---------------------------------------------------------------------------------- */
+typedef struct dmx_trocr_dec dmx_trocr_dec;
+typedef struct dmx_trocr_dec_config {           /* app.ipynb:548 (trocr-large: TrOCRConfig defaults) */
+  int vocab_size, d_model, num_layers, num_heads; /* 50265, 1024, 12, 16 (head dim 64; d_model a multiple of 256, <= 1024) */
+  int ffn_dim, max_position_embeddings;          /* 4096, 512 (learned positions: table of max + 2 rows) */
+  int cross_hidden_size;                         /* k/v input width of the cross-attention (0: d_model) */
+  int activation;                                /* 0 exact-erf gelu, 1 relu */
+  int scale_embedding, layernorm_embedding, tie_word_embeddings;
+} dmx_trocr_dec_config;
+/* state words (int32) at the start of the cache: position of the current input token, all-rows-finished flag, the sequence
+ * length at which every row had finished, the next input token of each row (B <= 64), the finished flag of each row */
+#define DMX_TROCR_STATE_POS 0
+#define DMX_TROCR_STATE_DONE 1
+#define DMX_TROCR_STATE_STOP_LEN 2
+#define DMX_TROCR_STATE_TOKENS 16
+#define DMX_TROCR_STATE_FINISHED 80
+dmx_trocr_dec* dmx_trocr_dec_create(const dmx_trocr_dec_config* cfg);                       /* app.ipynb:548 */
+void dmx_trocr_dec_destroy(dmx_trocr_dec* d);                                               /* app.ipynb:548 */
+int dmx_trocr_dec_param_count(const dmx_trocr_dec* d);                                      /* app.ipynb:548 */
+int dmx_trocr_dec_param_info(const dmx_trocr_dec* d, int index, const char** name, int shape[4]);   /* app.ipynb:548 */
+size_t dmx_trocr_dec_arena_bytes(const dmx_trocr_dec* d);                                   /* app.ipynb:548 */
+int dmx_trocr_dec_bind_arena(dmx_trocr_dec* d, void* arena, size_t bytes);                  /* app.ipynb:548 */
+int dmx_trocr_dec_load_param(dmx_trocr_dec* d, const char* name, const float* src_f32, dmx_stream_t stream);   /* app.ipynb:548 */
+int dmx_trocr_dec_finalize(dmx_trocr_dec* d, dmx_stream_t stream);                          /* app.ipynb:548 */
+/* cache: state words + self-attention K/V [layers][B][max_len][2 d_model] + cross K/V [B][S][layers][2 d_model] (bf16);
+ * workspace: the activations of one step, or of the cross K/V GEMM (app.ipynb:845) */
+size_t dmx_trocr_dec_cache_bytes(const dmx_trocr_dec* d, int B, int S, int max_len);        /* app.ipynb:845 */
+size_t dmx_trocr_dec_workspace_bytes(const dmx_trocr_dec* d, int B, int S, int max_len);    /* app.ipynb:845 */
+/* the k_proj | v_proj of every layer over the encoder states [B][S][cross_hidden_size] fp32: one GEMM (app.ipynb:845) */
+int dmx_trocr_dec_cross_kv(dmx_trocr_dec* d, const float* encoder_hidden_states, int B, int S, int max_len, void* cache,
+                           void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+/* position 0, no row finished, every row's input = start_token, ids[b][0] = start_token (ids: [B][max_len] int64) (app.ipynb:845) */
+int dmx_trocr_dec_reset(dmx_trocr_dec* d, void* cache, int B, int S, int max_len, int start_token, long long* ids, dmx_stream_t stream);
+/* teacher forcing: the next step's input tokens from tokens[B] (int64) (app.ipynb:845 restated as a forward) */
+int dmx_trocr_dec_set_tokens(dmx_trocr_dec* d, void* cache, const long long* tokens, int B, dmx_stream_t stream);
+/* one greedy step (app.ipynb:845): logits of the input tokens at the current position, argmax (lowest index on ties), a finished
+ * row emits pad_token_id, a row that emits eos_token_id (< 0: none) finishes; the token goes to ids[b][pos + 1] and becomes the
+ * next input; the position advances.  logits (nullable): fp32 [B][ld_logits] */
+int dmx_trocr_dec_step(dmx_trocr_dec* d, void* cache, int B, int S, int max_len, int eos_token_id, int pad_token_id,
+                       long long* ids, float* logits, int ld_logits, void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+int dmx_trocr_dec_launches_per_step(const dmx_trocr_dec* d);                                /* app.ipynb:845 */
+/* op entry points of the decoder kernels (tests, benchmarks; app.ipynb:845): y = x W^T on M <= 64 rows with one epilogue
+ * (0: y = act(xW^T + bias) * oscale -> yf fp32 and / or yb; 1: q|k|v - q * oscale -> yf, k|v -> kv row state[0];
+ * 2: LayerNorm(xW^T + bias + res) -> yf, yb; 3: logits -> yf (nullable) + the greedy pick into state / ids);
+ * kchunk > 0 forces the K split.  x, w, yb, kv: 16-bit elements. */
+size_t dmx_trocr_dec_linear_workspace_bytes(int M, int N, int K);
+int dmx_trocr_dec_linear(int epi, int act, const void* x, int M, int K, const void* w, int N, const float* bias, float oscale,
+                         float* yf, int ld_yf, void* yb, const float* res, const float* gamma, const float* beta,
+                         void* kv, int max_len, int* state, long long* ids, int eos, int pad, int kchunk,
+                         void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+/* decode attention, one query row per (b, head), d = 64: q [M][H*64] fp32 (pre-scaled), key j of row b at kv + b*bstride + j*rstride
+ * + h*64, its value d_model = H*64 elements further; out [M][H*64] (app.ipynb:845) */
+size_t dmx_trocr_dec_attn_workspace_bytes(int M, int H, int L);
+int dmx_trocr_dec_attn(const float* q, int M, int H, const void* kv, long long bstride, int rstride, int L, void* out,
+                       void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+
 typedef struct dmx_vae_config {
   int in_channels, out_channels, latent_channels;
   int block_out_channels[4];
