@@ -42,6 +42,23 @@ def _ld(x):
     return x.stride(-2)
 
 
+def _out(t, shape, dtype, dev, zero=False):
+    """a caller-provided output tensor (checked), or a fresh one"""
+    if t is None:
+        return (torch.zeros if zero else torch.empty)(*shape, dtype=dtype, device=dev)
+    assert tuple(t.shape) == tuple(shape) and t.dtype == dtype, f"output tensor must be {tuple(shape)} {dtype}, got {tuple(t.shape)} {t.dtype}"
+    assert t.dim() < 2 or t.stride(-1) == 1, "channel dim must be contiguous"
+    return t
+
+
+def _grad_pair(into, C, dev):
+    """(dgamma, dbeta) fp32 [C]: the caller's `into` pair or fresh tensors"""
+    if into is None:
+        return torch.empty(C, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)
+    dg, db = into
+    return _out(dg, (C,), torch.float32, dev), _out(db, (C,), torch.float32, dev)
+
+
 def nchw_to_nhwc_bf16(x):
     """fp32 NCHW -> bf16 NHWC through dmx_nchw_f32_to_nhwc_bf16."""
     x = x.to(torch.float32).contiguous()
@@ -96,22 +113,61 @@ def pack_linear_weight_t(w):
     return out
 
 
-def conv_dgrad(dy, wt, Cin, *, ksize=3, stride=1, ups=False, res=None):
-    """dX [B,IH,IW,Cin] bf16 of a pad-(k//2) conv from dy [B,OH,OW,Cout] and the transposed pack of its filter.
+def conv_dgrad(dy, wt, Cin, *, ksize=3, stride=1, ups=False, res=None, pad=None, dx=None):
+    """dX [B,IH,IW,Cin] bf16 of a conv from dy [B,OH,OW,Cout] and the transposed pack of its filter.  `pad` is the FORWARD
+    conv's padding (default k//2; 0 for the VAE's stride-2 conv behind its (0,1,0,1) pad): the data-gradient conv pads k-1-pad.
     stride 2: dY is zero-inserted onto the input grid first; ups: the gradient on the upsampled grid is sum-pooled.
-    `res` (bf16, input-shaped) is added: the gradient arriving over a residual / second consumer."""
+    `res` (bf16, input-shaped) is added: the gradient arriving over a residual / second consumer.  `dx`: write there
+    (its row stride is taken from the tensor)."""
     B, OH, OW, Cout = dy.shape
     g = dy
     if stride == 2:
-        g = torch.empty(B, 2 * OH, 2 * OW, Cout, dtype=h16(), device=dy.device)
-        check(lib().dmx_zero_insert2(ptr(dy), _ld(dy), ptr(g), B, OH, OW, Cout, current_stream()), "zero_insert2")
-    du = conv_gemm(g, wt, Cin, ksize=ksize, stride=1, pad=ksize // 2, res=None if ups else res, out_f32=ups)
+        g = zero_insert2(dy)
+    gpad = ksize - 1 - (ksize // 2 if pad is None else pad)
+    du = conv_gemm(g, wt, Cin, ksize=ksize, stride=1, pad=gpad, res=None if ups else res, out_f32=ups, out=None if ups else dx)
     if not ups:
         return du
     H, W = du.shape[1] // 2, du.shape[2] // 2
-    dx = res.clone() if res is not None else torch.empty(B, H, W, Cin, dtype=h16(), device=dy.device)
-    check(lib().dmx_sumpool2(ptr(du), _ld(du), 1, ptr(dx), _ld(dx), B, H, W, Cin, int(res is not None), current_stream()), "sumpool2")
+    dx = _out(dx, (B, H, W, Cin), h16(), dy.device)
+    if res is not None:
+        dx.copy_(res)
+    return sumpool2(du, dx=dx, accumulate=res is not None)
+
+
+def zero_insert2(dy, out=None):
+    """z[b][2y][2x] = dy[b][y][x], 0 elsewhere: [B,OH,OW,C] -> contiguous [B,2OH,2OW,C] (exact)"""
+    B, OH, OW, C = dy.shape
+    z = _out(out, (B, 2 * OH, 2 * OW, C), h16(), dy.device)
+    assert z.is_contiguous(), "zero_insert2 writes a contiguous tensor"
+    check(lib().dmx_zero_insert2(ptr(dy), _ld(dy), ptr(z), B, OH, OW, C, current_stream()), "zero_insert2")
+    return z
+
+
+def sumpool2(du, dx=None, accumulate=False):
+    """dx[b][y][x] (+)= the 2x2 block sum of du [B,2H,2W,C] (bf16 or fp32; fp32 sum, one rounding)"""
+    B, H2, W2, C = du.shape
+    dx = _out(dx, (B, H2 // 2, W2 // 2, C), h16(), du.device)
+    check(lib().dmx_sumpool2(ptr(du), _ld(du), int(du.dtype == torch.float32), ptr(dx), _ld(dx), B, H2 // 2, W2 // 2, C, int(accumulate),
+                             current_stream()), "sumpool2")
     return dx
+
+
+def mse_loss(pred, target, grad_scale=1.0, dpred=True, loss=None):
+    """-> (loss fp32 [1], dpred): loss = mean((pred - target)^2), dpred = 2 (pred - target) / n * grad_scale (fp32, pred-shaped).
+    dpred: True = a fresh tensor, a tensor = write there, None / False = loss only (nothing else is written)."""
+    assert pred.dtype == torch.float32 and target.dtype == torch.float32 and pred.is_contiguous() and target.is_contiguous()
+    n = pred.numel()
+    loss = _out(loss, (1,), torch.float32, pred.device)
+    if dpred is True:
+        dpred = torch.empty_like(pred)
+    elif dpred is False:
+        dpred = None
+    if dpred is not None:
+        assert dpred.is_contiguous() and dpred.numel() == n and dpred.dtype == torch.float32
+    wsb = lib().dmx_mse_loss_workspace_bytes()
+    ws = torch.empty(wsb, dtype=torch.uint8, device=pred.device)
+    check(lib().dmx_mse_loss(ptr(pred), ptr(target), n, ptr(loss), ptr(dpred), float(grad_scale), ptr(ws), wsb, current_stream()), "mse_loss")
+    return loss, dpred
 
 
 def pack_geglu_bias(b):
@@ -141,7 +197,7 @@ def conv_ups2x(x, wp, N, bias=None, force_tn=0, force_splitk=0):
 
 def conv_gemm(x0, w, N, *, x1=None, ksize=3, stride=1, pad=1, ups=False, bias=None, rowbias=None,
               res=None, sc0=None, sc1=None, out_f32=False, geglu=False, direct=None, force_tn=0, force_splitk=0, timing=None, group_m=0, dbg=0, act=0,
-              rowstats=False, ln=None, gn_stats=False):
+              rowstats=False, ln=None, gn_stats=False, out=None):
     """Fused conv / linear.  x0 (and x1) NHWC bf16; w packed bf16 [N][K].  Returns NHWC (bf16 or fp32).
     gn_stats=True: also returns the [B][N][2] int64 fixed-point (sum * 2^20, sumsq * 2^32) GroupNorm statistics of the output
     (or None when the plan this problem runs on cannot emit them: split-K / tiles straddling samples).
@@ -177,8 +233,8 @@ def conv_gemm(x0, w, N, *, x1=None, ksize=3, stride=1, pad=1, ups=False, bias=No
     if res is not None:
         d.res = res.data_ptr(); d.ldres = _ld(res)
     Nout = N // 2 if geglu else N
-    out = torch.empty(B, OH, OW, Nout, dtype=torch.float32 if out_f32 else h16(), device=x0.device)
-    d.out = out.data_ptr(); d.ldo = Nout; d.out_f32 = int(out_f32); d.geglu = int(geglu)
+    out = _out(out, (B, OH, OW, Nout), torch.float32 if out_f32 else h16(), x0.device)
+    d.out = out.data_ptr(); d.ldo = _ld(out); d.out_f32 = int(out_f32); d.geglu = int(geglu)
     d.force_tn = force_tn; d.force_splitk = force_splitk; d.group_m = group_m; d.dbg = dbg; d.act = act
     if timing is not None:
         d.timing = timing.data_ptr()
@@ -223,13 +279,15 @@ def _gather_desc(x0, x1, ksize, stride, pad, ups, direct):
     return d
 
 
-def conv_wgrad(x0, dy, *, x1=None, ksize=3, stride=1, pad=1, ups=False, direct=None, into=None):
-    """dW[N][K] fp32 (packed tap-major k) = sum over output pixels of dy[m][n] * gathered x[m][k]; `into` accumulates."""
+def conv_wgrad(x0, dy, *, x1=None, ksize=3, stride=1, pad=1, ups=False, direct=None, into=None, out=None):
+    """dW[N][K] fp32 (packed tap-major k) = sum over output pixels of dy[m][n] * gathered x[m][k]; `into` accumulates, `out` is overwritten."""
     d = _gather_desc(x0, x1, ksize, stride, pad, ups, direct)
     N = dy.shape[-1]
     d.N = N
     assert dy.numel() == d.M * N, "dy must be [B, OH, OW, N]"
-    out = into if into is not None else torch.empty(N, d.K, dtype=torch.float32, device=x0.device)
+    assert into is None or out is None
+    out = _out(into if into is not None else out, (N, d.K), torch.float32, x0.device)
+    assert out.is_contiguous()
     acc = int(into is not None)
     wsb = lib().dmx_conv_wgrad_workspace_bytes(ctypes.byref(d), acc)
     ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=x0.device)
@@ -237,15 +295,19 @@ def conv_wgrad(x0, dy, *, x1=None, ksize=3, stride=1, pad=1, ups=False, direct=N
     return out
 
 
-def colsum(dy, groups=1, into=None):
-    """column sums of dy viewed as [groups][rows/groups][N] -> [groups][N] fp32 (bias / row-bias gradients)."""
+def colsum(dy, groups=1, into=None, out=None, accumulate=None):
+    """column sums of dy viewed as [groups][rows/groups][N] -> [groups][N] fp32 (bias / row-bias gradients).
+    `into` adds onto an existing gradient (accumulate defaults to True with it); `out` is overwritten."""
     N = dy.shape[-1]
     rows = dy.numel() // N
     rpg = rows // groups
-    out = into if into is not None else torch.empty(groups, N, dtype=torch.float32, device=dy.device)
+    assert into is None or out is None
+    acc = int(into is not None) if accumulate is None else int(accumulate)
+    assert into is not None or not acc, "accumulate needs into= (an existing gradient)"
+    out = _out(into if into is not None else out, (groups, N), torch.float32, dy.device)
     wsb = lib().dmx_colsum_workspace_bytes(groups, rpg, N)
     ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dy.device)
-    check(lib().dmx_colsum(ptr(dy), _ld(dy), groups, rpg, N, ptr(out), N, int(into is not None), ptr(ws), wsb, current_stream()), "colsum")
+    check(lib().dmx_colsum(ptr(dy), _ld(dy), groups, rpg, N, ptr(out), out.stride(0), acc, ptr(ws), wsb, current_stream()), "colsum")
     return out
 
 
@@ -432,62 +494,68 @@ def groupnorm_from_stats(x0, st0, gamma, beta, groups, eps, silu, x1=None, st1=N
     return y
 
 
-def groupnorm_train(x0, gamma, beta, groups, eps, silu, x1=None):
+def groupnorm_train(x0, gamma, beta, groups, eps, silu, x1=None, out=None, stats=None):
     """forward GroupNorm that also returns the saved (mean, rstd) [B][groups][2]"""
     B, H, W, C0 = x0.shape
     C = C0 + (x1.shape[-1] if x1 is not None else 0)
-    y = torch.empty(B, H, W, C, dtype=h16(), device=x0.device)
-    stats = torch.empty(B, groups, 2, dtype=torch.float32, device=x0.device)
+    y = _out(out, (B, H, W, C), h16(), x0.device)
+    stats = _out(stats, (B, groups, 2), torch.float32, x0.device)
+    assert stats.is_contiguous()
     wsb = lib().dmx_groupnorm_workspace_bytes(B, H * W, groups)
     ws = torch.empty(wsb, dtype=torch.uint8, device=x0.device)
     check(lib().dmx_groupnorm_train(ptr(x0), _ld(x0), ptr(x1), _ld(x1) if x1 is not None else 0, C0, C, groups, B, H * W,
-                                    ptr(gamma), ptr(beta), float(eps), int(silu), ptr(y), C, ptr(stats), ptr(ws), wsb, current_stream()),
+                                    ptr(gamma), ptr(beta), float(eps), int(silu), ptr(y), _ld(y), ptr(stats), ptr(ws), wsb, current_stream()),
           "groupnorm_train")
     return y, stats
 
 
-def groupnorm_bwd(x0, dy, gamma, beta, groups, silu, stats, x1=None, res0=None, res1=None):
-    """-> (dx0, dx1 or None, dgamma, dbeta)"""
+def groupnorm_bwd(x0, dy, gamma, beta, groups, silu, stats, x1=None, res0=None, res1=None, dx0=None, dx1=None, into=None, accumulate=False):
+    """-> (dx0, dx1 or None, dgamma, dbeta).  dx0 / dx1: write there (strides from the tensors); into=(dgamma, dbeta) fp32 [C],
+    `accumulate` adds onto them."""
     B, H, W, C0 = x0.shape
     C = C0 + (x1.shape[-1] if x1 is not None else 0)
-    dx0 = torch.empty_like(x0)
-    dx1 = torch.empty_like(x1) if x1 is not None else None
-    dg = torch.empty(C, dtype=torch.float32, device=x0.device); db = torch.empty_like(dg)
+    dx0 = _out(dx0, tuple(x0.shape), h16(), x0.device)
+    dx1 = _out(dx1, tuple(x1.shape), h16(), x0.device) if x1 is not None else None
+    assert into is not None or not accumulate, "accumulate needs into=(dgamma, dbeta)"
+    dg, db = _grad_pair(into, C, x0.device)
     wsb = lib().dmx_groupnorm_bwd_workspace_bytes(B, H * W, C)
     ws = torch.empty(wsb, dtype=torch.uint8, device=x0.device)
     check(lib().dmx_groupnorm_bwd(ptr(x0), _ld(x0), ptr(x1), _ld(x1) if x1 is not None else 0, C0, C, groups, B, H * W,
                                   ptr(gamma), ptr(beta), int(silu), ptr(stats), ptr(dy), _ld(dy),
                                   ptr(dx0), _ld(dx0), ptr(dx1), _ld(dx1) if dx1 is not None else 0,
                                   ptr(res0), _ld(res0) if res0 is not None else 0, ptr(res1), _ld(res1) if res1 is not None else 0,
-                                  ptr(dg), ptr(db), 0, ptr(ws), wsb, current_stream()), "groupnorm_bwd")
+                                  ptr(dg), ptr(db), int(accumulate), ptr(ws), wsb, current_stream()), "groupnorm_bwd")
     return dx0, dx1, dg, db
 
 
-def layernorm_bwd(x, dy, gamma, eps=1e-5, res=None):
+def layernorm_bwd(x, dy, gamma, eps=1e-5, res=None, dx=None, into=None, accumulate=False):
+    """-> (dx, dgamma, dbeta); x / dy / res / dx are [..., rows, C] views whose row strides are taken from the tensors"""
     C = x.shape[-1]
     rows = x.numel() // C
-    dx = torch.empty_like(x)
-    dg = torch.empty(C, dtype=torch.float32, device=x.device); db = torch.empty_like(dg)
+    dx = _out(dx, tuple(x.shape), h16(), x.device)
+    assert into is not None or not accumulate, "accumulate needs into=(dgamma, dbeta)"
+    dg, db = _grad_pair(into, C, x.device)
     wsb = lib().dmx_layernorm_bwd_workspace_bytes(rows, C)
     ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=x.device)
-    check(lib().dmx_layernorm_bwd(ptr(x), C, ptr(dy), C, ptr(gamma), ptr(dx), C, ptr(res), C if res is not None else 0,
-                                  ptr(dg), ptr(db), 0, rows, C, float(eps), ptr(ws), wsb, current_stream()), "layernorm_bwd")
+    check(lib().dmx_layernorm_bwd(ptr(x), _ld(x), ptr(dy), _ld(dy), ptr(gamma), ptr(dx), _ld(dx), ptr(res), _ld(res) if res is not None else 0,
+                                  ptr(dg), ptr(db), int(accumulate), rows, C, float(eps), ptr(ws), wsb, current_stream()), "layernorm_bwd")
     return dx, dg, db
 
 
-def geglu_fwd(h):
+def geglu_fwd(h, out=None):
     C2 = h.shape[-1] // 2
     rows = h.numel() // (2 * C2)
-    y = torch.empty(*h.shape[:-1], C2, dtype=h16(), device=h.device)
-    check(lib().dmx_geglu_fwd(ptr(h), 2 * C2, ptr(y), C2, rows, C2, current_stream()), "geglu_fwd")
+    y = _out(out, (*h.shape[:-1], C2), h16(), h.device)
+    check(lib().dmx_geglu_fwd(ptr(h), _ld(h), ptr(y), _ld(y), rows, C2, current_stream()), "geglu_fwd")
     return y
 
 
-def geglu_bwd(h, dy):
+def geglu_bwd(h, dy, dx=None):
+    """gradient of geglu_fwd with respect to h = [a | g]"""
     C2 = h.shape[-1] // 2
     rows = h.numel() // (2 * C2)
-    dh = torch.empty_like(h)
-    check(lib().dmx_geglu_bwd(ptr(h), 2 * C2, ptr(dy), C2, ptr(dh), 2 * C2, rows, C2, current_stream()), "geglu_bwd")
+    dh = _out(dx, tuple(h.shape), h16(), h.device)
+    check(lib().dmx_geglu_bwd(ptr(h), _ld(h), ptr(dy), _ld(dy), ptr(dh), _ld(dh), rows, C2, current_stream()), "geglu_bwd")
     return dh
 
 
@@ -539,17 +607,23 @@ def attention_wide(q, k, v, B, Sq, Skv, D, scale, kv_rows=None):
     return o
 
 
-def attention_train(q, k, v, B, H, Sq, Skv, scale, kv_rows=None):
-    """forward with row-major V that also returns lse [B,H,Sq] (log2 domain)"""
-    o = torch.empty(B * Sq, H * 64, dtype=h16(), device=q.device)
-    lse = torch.empty(B, H, Sq, dtype=torch.float32, device=q.device)
+def attention_train(q, k, v, B, H, Sq, Skv, scale, kv_rows=None, out=None, lse=None):
+    """forward with row-major V that also returns lse [B,H,Sq] (log2 domain); q / k / v / out may be column slices of fused buffers"""
+    o = _out(out, (B * Sq, H * 64), h16(), q.device)
+    lse = _out(lse, (B, H, Sq), torch.float32, q.device)
+    assert lse.is_contiguous()
     check(lib().dmx_attention_fwd_train(ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), kv_rows or Skv,
-                                        ptr(o), H * 64, ptr(lse), B, H, Sq, Skv, float(scale), current_stream()), "attention_fwd_train")
+                                        ptr(o), o.stride(0), ptr(lse), B, H, Sq, Skv, float(scale), current_stream()), "attention_fwd_train")
     return o, lse
 
 
-def attention_bwd(q, k, v, o, do, lse, B, H, Sq, Skv, scale, kv_rows=None):
-    dq = torch.empty_like(q); dk = torch.zeros_like(k); dv = torch.zeros_like(v)
+def attention_bwd(q, k, v, o, do, lse, B, H, Sq, Skv, scale, kv_rows=None, dq=None, dk=None, dv=None):
+    """-> (dq, dk, dv).  Every operand may be a column slice of a fused buffer (strides from the tensors; o and do share one).
+    Rows [Skv, kv_rows) of dk / dv are not written: fresh ones are zero, a caller's keep what they held."""
+    assert o.stride(0) == do.stride(0), "o and do share one row stride"
+    dq = _out(dq, tuple(q.shape), h16(), q.device)
+    dk = _out(dk, tuple(k.shape), h16(), q.device, zero=True)
+    dv = _out(dv, tuple(v.shape), h16(), q.device, zero=True)
     wsb = lib().dmx_attention_bwd_workspace_bytes(B, H, Sq)
     ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
     check(lib().dmx_attention_bwd(ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), kv_rows or Skv,

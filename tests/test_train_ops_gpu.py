@@ -1,7 +1,13 @@
 """GPU parity of the training (backward) kernels against torch autograd on the CPU oracle ops.
 
 Inputs are rounded to bf16 first, so the only differences are fp32 accumulation order (and, where a kernel rounds an
-intermediate to bf16, that rounding): tolerances are stated per test."""
+intermediate to bf16, that rounding): tolerances are stated per test.
+
+This file holds the contiguous-operand, whole-tensor cases.  test_train_layout_gpu.py runs the same kernels the way the training
+graph calls them, against fp64: strided and fused operands (q | k | v, dq | dk | dv, the padded context projection, channel
+slices), outputs in poisoned buffers with guard bands, per-slice bounds next to the whole-tensor ones of this file, ragged
+tiles and spiked keys, accumulate=1, dmx_mse_loss / dmx_zero_insert2 / dmx_sumpool2, and the fp16 build's backward with the
+upstream gradient scaled by 2^10 and 2^16; test_train_refs_host.py derives those bounds on the CPU."""
 import math
 
 import pytest
