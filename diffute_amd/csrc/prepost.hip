@@ -175,3 +175,83 @@ extern "C" int dmx_postprocess_paste(const float* image_vae, int S, const unsign
   hipLaunchKernelGGL(dmx_postprocess_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, p);
   return dmx_check_launch("dmx_postprocess_kernel");
 }
+
+// ---- TrOCRProcessor's image half (reference: `processor(images=ttf_imgs, return_tensors="pt").pixel_values`, app.ipynb:773,
+// train_diffute_v1.py:868): Pillow's 8-bit two-pass resample (Resample.c as published) + the processor's rescale / normalise, for a
+// ragged batch in ONE launch.  Everything that involves floating point is done on the host and shipped as tables: per (in, out, filter) the
+// bounds [out][2] = (first source index, tap count) followed by the 2^22 fixed-point coefficients [out][ksize]; the uint8 -> fp32
+// normalisation as norm[3][256].  The kernel is integer MACs and table look-ups only, so its result does not depend on build flags.
+//   horizontal pass first: h = clip8((2^21 + sum pixel * k) >> 22) stored as a BYTE, the vertical pass runs on those bytes; a pass whose
+//   input and output size are equal is skipped (table offset < 0).
+// One thread per destination pixel, all three channels; the thread recomputes the horizontally-resampled bytes its vertical taps need.
+namespace {
+struct GlyphArgs {
+  const dmx_glyph_image* desc; const int* tab; const float* norm;
+  int S_h, S_w; float* out; unsigned char* out_u8;
+};
+__device__ __forceinline__ int clip8(int v) { v >>= 22; return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+__global__ __launch_bounds__(128) void dmx_glyph_resize_normalize_kernel(const GlyphArgs p) {
+  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y, b = blockIdx.z;
+  if (ox >= p.S_w) return;
+  const dmx_glyph_image d = p.desc[b];
+  const unsigned char* src = (const unsigned char*)d.src;
+  // the tables come from device memory the entry cannot inspect: every bound is clamped to the image, so a bad table reads wrong pixels, never outside
+  int xmin = ox, xn = 1, ymin = oy, yn = 1;
+  const int *kh = nullptr, *kv = nullptr;
+  if (d.h_off >= 0) {
+    const int* t = p.tab + d.h_off;
+    xmin = min(max(t[2 * ox], 0), d.W - 1); xn = min(min(t[2 * ox + 1], d.h_taps), min(d.W - xmin, DMX_GLYPH_MAX_TAPS));
+    kh = t + 2 * p.S_w + (size_t)ox * d.h_taps;
+  } else xmin = min(xmin, d.W - 1);
+  if (d.v_off >= 0) {
+    const int* t = p.tab + d.v_off;
+    ymin = min(max(t[2 * oy], 0), d.H - 1); yn = min(min(t[2 * oy + 1], d.v_taps), min(d.H - ymin, DMX_GLYPH_MAX_TAPS));
+    kv = t + 2 * p.S_h + (size_t)oy * d.v_taps;
+  } else ymin = min(ymin, d.H - 1);
+  int acc[3] = {1 << 21, 1 << 21, 1 << 21}, h[3] = {0, 0, 0};
+  for (int j = 0; j < yn; ++j) {
+    const unsigned char* row = src + (long long)(ymin + j) * d.stride_y + (long long)xmin * d.stride_x;
+    if (kh) {
+      int s[3] = {1 << 21, 1 << 21, 1 << 21};
+      for (int i = 0; i < xn; ++i) {
+        const int k = kh[i];
+        const unsigned char* px = row + (long long)i * d.stride_x;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s[c] += (int)px[c * d.stride_c] * k;
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) h[c] = clip8(s[c]);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) h[c] = row[c * d.stride_c];
+    }
+    if (kv) {
+      const int k = kv[j];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[c] += h[c] * k;
+    }
+  }
+  const size_t plane = (size_t)p.S_h * p.S_w, o = (size_t)b * 3 * plane + (size_t)oy * p.S_w + ox;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int v = kv ? clip8(acc[c]) : h[c];
+    p.out[o + c * plane] = p.norm[c * 256 + v];
+    if (p.out_u8) p.out_u8[o + c * plane] = (unsigned char)v;
+  }
+}
+}  // namespace
+
+extern "C" int dmx_glyph_max_taps(void) { return DMX_GLYPH_MAX_TAPS; }
+
+extern "C" int dmx_glyph_resize_normalize(const dmx_glyph_image* images, int B, const int* tables, const float* norm, int max_taps, int S_h, int S_w,
+                                          float* out_pixel_values, unsigned char* out_resized, dmx_stream_t stream) {
+  DMX_REQUIRE(images && tables && norm && out_pixel_values, "glyph_resize_normalize: null argument");
+  DMX_REQUIRE(B > 0 && B <= 65535 && S_h > 0 && S_h <= 65535 && S_w > 0, "glyph_resize_normalize: bad sizes (B %d, output %dx%d)", B, S_h, S_w);
+  DMX_REQUIRE(max_taps >= 0 && max_taps <= DMX_GLYPH_MAX_TAPS,
+              "glyph_resize_normalize: %d taps per output pixel exceed the cap of %d (downscale ratio at most 31 for bilinear, 15 for bicubic)",
+              max_taps, DMX_GLYPH_MAX_TAPS);
+  GlyphArgs p{images, tables, norm, S_h, S_w, out_pixel_values, out_resized};
+  hipLaunchKernelGGL(dmx_glyph_resize_normalize_kernel, dim3(cdiv(S_w, 128), S_h, B), dim3(128), 0, (hipStream_t)stream, p);
+  return dmx_check_launch("dmx_glyph_resize_normalize_kernel");
+}

@@ -541,6 +541,32 @@ int dmx_preprocess_crop(const unsigned char* image_hwc, const unsigned char* mas
 int dmx_postprocess_paste(const float* image_vae, int S, const unsigned char* original_hwc, unsigned char* out_hwc, int H, int W,
                           int x_s, int y_s, int crop_scale, int x1, int y1, int x2, int y2, dmx_stream_t stream);
 
+/* The image half of TrOCRProcessor (`processor(images=ttf_imgs, return_tensors="pt").pixel_values`, app.ipynb:773,
+ * train_diffute_v1.py:868; a ViT image processor: PIL resize, rescale, normalise): ONE launch turns a ragged batch of uint8
+ * 3-channel images into out_pixel_values fp32 [B][3][S_h][S_w], bit for bit what Pillow's 8-bit Image.resize (Resample.c as
+ * published: horizontal pass, result stored as bytes, then the vertical pass; a pass whose sizes are equal is skipped)
+ * followed by the processor's float arithmetic gives.  All floating point is done by the CALLER and passed as device tables:
+ *   images  B descriptors.  src = device address of pixel (0,0) channel 0; strides in bytes, so HWC, CHW and strided views
+ *           are read in place.  h_off / v_off = offset (in ints) of that pass's table inside `tables`, < 0 = pass skipped;
+ *           h_taps / v_taps = its coefficient row length (Pillow's ksize).
+ *   tables  per pass: bounds int[out][2] = (first source index, tap count), then coefficients int[out][taps] in 2^22
+ *           fixed point.  Each output byte is clip8((2^21 + sum pixel * k) >> 22).
+ *   norm    float[3][256]: the value written for channel c and resized byte v.
+ *   max_taps the largest h_taps / v_taps of the batch; more than DMX_GLYPH_MAX_TAPS is refused (DMX_ERR_ARG): a thread does
+ *           h_taps * v_taps MACs per channel, which caps the downscale ratio at 31 (bilinear) / 15 (bicubic).
+ *   out_resized (optional, may be NULL) uint8 [B][3][S_h][S_w]: the resized bytes before normalisation.
+ * Table bounds are clamped to the image inside the kernel; the descriptors' addresses and strides are trusted. */
+#define DMX_GLYPH_MAX_TAPS 64
+typedef struct dmx_glyph_image {
+  unsigned long long src;
+  long long stride_y, stride_x, stride_c;
+  int H, W;
+  int h_off, h_taps, v_off, v_taps;
+} dmx_glyph_image;
+int dmx_glyph_max_taps(void);
+int dmx_glyph_resize_normalize(const dmx_glyph_image* images, int B, const int* tables, const float* norm, int max_taps, int S_h, int S_w,
+                               float* out_pixel_values, unsigned char* out_resized, dmx_stream_t stream);
+
 /* Fused AdamW + global-norm clipping over packed fp32 arenas (torch.optim.AdamW + clip_grad_norm_,
  * train_diffute_v1.py:721-727,927-930).  masters / exp_avg / exp_avg_sq / grads: dmx_unet_grad_bytes each.  The step also
  * rewrites the weights arena (bf16 weights, fp32 vectors) in place; afterwards call dmx_unet_refresh_derived (folded
