@@ -95,25 +95,30 @@ extern "C" int dmx_colsum(const void* dy, int lddy, int groups, int rows_per_gro
   return dmx_colsum_launch((const bf16*)dy, lddy, groups, rows_per_group, N, out, ldo, accumulate, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// the fields the three GroupNorm entry points share (the callers add partial / stats_out / st0, st1)
+static GroupNormArgs gn_args(const void* x0, int ldx0, const void* x1, int ldx1, int c0, int C, int groups, int B, int HW,
+                             const float* gamma, const float* beta, float eps, int silu, void* y, int ldy) {
+  GroupNormArgs a{};
+  a.x0 = (const bf16*)x0; a.ldx0 = ldx0; a.x1 = (const bf16*)x1; a.ldx1 = ldx1; a.c0 = x1 ? c0 : C;
+  a.C = C; a.groups = groups; a.B = B; a.HW = HW; a.gamma = gamma; a.beta = beta; a.eps = eps; a.silu = silu;
+  a.y = (bf16*)y; a.ldy = ldy;
+  return a;
+}
 extern "C" int dmx_groupnorm(const void* x0, int ldx0, const void* x1, int ldx1, int c0, int C, int groups,
                              int B, int HW, const float* gamma, const float* beta, float eps, int silu,
                              void* y, int ldy, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(x0 && y && gamma && beta, "groupnorm: null argument");
   DMX_REQUIRE(workspace && workspace_bytes >= dmx_gn_workspace_bytes(B, HW, groups), "groupnorm: workspace too small");
-  GroupNormArgs a{};
-  a.x0 = (const bf16*)x0; a.ldx0 = ldx0; a.x1 = (const bf16*)x1; a.ldx1 = ldx1; a.c0 = x1 ? c0 : C;
-  a.C = C; a.groups = groups; a.B = B; a.HW = HW; a.gamma = gamma; a.beta = beta; a.eps = eps; a.silu = silu;
-  a.y = (bf16*)y; a.ldy = ldy; a.partial = (float*)workspace;
+  GroupNormArgs a = gn_args(x0, ldx0, x1, ldx1, c0, C, groups, B, HW, gamma, beta, eps, silu, y, ldy);
+  a.partial = (float*)workspace;
   return dmx_groupnorm_launch(a, (hipStream_t)stream);
 }
 extern "C" int dmx_groupnorm_from_stats(const void* x0, int ldx0, const void* x1, int ldx1, int c0, int C, int groups,
                                         int B, int HW, const float* gamma, const float* beta, float eps, int silu,
                                         const long long* st0, const long long* st1, void* y, int ldy, dmx_stream_t stream) {
   DMX_REQUIRE(x0 && y && gamma && beta && st0 && (!x1 || st1), "groupnorm_from_stats: null argument");
-  GroupNormArgs a{};
-  a.x0 = (const bf16*)x0; a.ldx0 = ldx0; a.x1 = (const bf16*)x1; a.ldx1 = ldx1; a.c0 = x1 ? c0 : C;
-  a.C = C; a.groups = groups; a.B = B; a.HW = HW; a.gamma = gamma; a.beta = beta; a.eps = eps; a.silu = silu;
-  a.y = (bf16*)y; a.ldy = ldy; a.st0 = st0; a.st1 = x1 ? st1 : st0;
+  GroupNormArgs a = gn_args(x0, ldx0, x1, ldx1, c0, C, groups, B, HW, gamma, beta, eps, silu, y, ldy);
+  a.st0 = st0; a.st1 = x1 ? st1 : st0;
   return dmx_groupnorm_sums_launch(a, (hipStream_t)stream);
 }
 static HaloConvArgs halo_args(const dmx_halo_conv_desc* d) {
@@ -182,10 +187,8 @@ extern "C" int dmx_groupnorm_train(const void* x0, int ldx0, const void* x1, int
                                    void* y, int ldy, float* stats, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(x0 && y && gamma && beta && stats, "groupnorm_train: null argument");
   DMX_REQUIRE(workspace && workspace_bytes >= dmx_gn_workspace_bytes(B, HW, groups), "groupnorm_train: workspace too small");
-  GroupNormArgs a{};
-  a.x0 = (const bf16*)x0; a.ldx0 = ldx0; a.x1 = (const bf16*)x1; a.ldx1 = ldx1; a.c0 = x1 ? c0 : C;
-  a.C = C; a.groups = groups; a.B = B; a.HW = HW; a.gamma = gamma; a.beta = beta; a.eps = eps; a.silu = silu;
-  a.y = (bf16*)y; a.ldy = ldy; a.partial = (float*)workspace; a.stats_out = stats;
+  GroupNormArgs a = gn_args(x0, ldx0, x1, ldx1, c0, C, groups, B, HW, gamma, beta, eps, silu, y, ldy);
+  a.partial = (float*)workspace; a.stats_out = stats;
   return dmx_groupnorm_launch(a, (hipStream_t)stream);
 }
 extern "C" size_t dmx_groupnorm_bwd_workspace_bytes(int B, int HW, int C) { return dmx_gn_bwd_workspace_bytes(B, HW, C); }
@@ -226,13 +229,18 @@ extern "C" int dmx_layernorm(const void* x, int ldx, void* y, int ldy, const flo
   DMX_REQUIRE(x && y && gamma && beta, "layernorm: null argument");
   return dmx_layernorm_launch((const bf16*)x, ldx, (bf16*)y, ldy, gamma, beta, rows, C, eps, (hipStream_t)stream);
 }
+// the fields the d=64 attention entry points share (the callers add the V operand - row-major v or transposed vt - and lse / balanced-schedule scratch)
+static AttnArgs attn_args(const void* q, int ldq, const void* k, int ldk, int kv_rows, void* o, int ldo, int B, int H, int Sq, int Skv, float scale) {
+  AttnArgs a{};
+  a.q = (const bf16*)q; a.ldq = ldq; a.k = (const bf16*)k; a.ldk = ldk; a.kv_rows = kv_rows; a.o = (bf16*)o; a.ldo = ldo;
+  a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.scale = scale;
+  return a;
+}
 extern "C" int dmx_attention_fwd(const void* q, int ldq, const void* k, int ldk, int kv_rows, const void* vt, int ldvt, int skv_stride,
                                  void* o, int ldo, int B, int H, int Sq, int Skv, float scale, dmx_stream_t stream) {
   DMX_REQUIRE(q && k && vt && o, "attention: null argument");
-  AttnArgs a{};
-  a.q = (const bf16*)q; a.ldq = ldq; a.k = (const bf16*)k; a.ldk = ldk; a.kv_rows = kv_rows;
-  a.vt = (const bf16*)vt; a.ldvt = ldvt; a.skv_stride = skv_stride; a.o = (bf16*)o; a.ldo = ldo;
-  a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.scale = scale;
+  AttnArgs a = attn_args(q, ldq, k, ldk, kv_rows, o, ldo, B, H, Sq, Skv, scale);
+  a.vt = (const bf16*)vt; a.ldvt = ldvt; a.skv_stride = skv_stride;
   return dmx_attention_launch(a, (hipStream_t)stream);
 }
 extern "C" int dmx_attention_wide(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int kv_rows,
@@ -246,10 +254,8 @@ extern "C" int dmx_attention_wide(const void* q, int ldq, const void* k, int ldk
 extern "C" int dmx_attention_fwd_v(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int kv_rows,
                                    void* o, int ldo, int B, int H, int Sq, int Skv, float scale, dmx_stream_t stream) {
   DMX_REQUIRE(q && k && v && o, "attention: null argument");
-  AttnArgs a{};
-  a.q = (const bf16*)q; a.ldq = ldq; a.k = (const bf16*)k; a.ldk = ldk; a.kv_rows = kv_rows;
-  a.v = (const bf16*)v; a.ldv = ldv; a.o = (bf16*)o; a.ldo = ldo;
-  a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.scale = scale;
+  AttnArgs a = attn_args(q, ldq, k, ldk, kv_rows, o, ldo, B, H, Sq, Skv, scale);
+  a.v = (const bf16*)v; a.ldv = ldv;
   return dmx_attention_launch(a, (hipStream_t)stream);
 }
 // K5 with the balanced schedule (attention_sk.hip): workspace = dmx_attention_fwd_v_balanced_workspace_bytes (0: the plan keeps the plain grid for this
@@ -265,10 +271,8 @@ extern "C" int dmx_attention_fwd_v_balanced(const void* q, int ldq, const void* 
                                             void* o, int ldo, int B, int H, int Sq, int Skv, float scale,
                                             void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(q && k && v && o && workspace, "attention (balanced): null argument");
-  AttnArgs a{};
-  a.q = (const bf16*)q; a.ldq = ldq; a.k = (const bf16*)k; a.ldk = ldk; a.kv_rows = kv_rows;
-  a.v = (const bf16*)v; a.ldv = ldv; a.o = (bf16*)o; a.ldo = ldo;
-  a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.scale = scale;
+  AttnArgs a = attn_args(q, ldq, k, ldk, kv_rows, o, ldo, B, H, Sq, Skv, scale);
+  a.v = (const bf16*)v; a.ldv = ldv;
   const int ns = dmx_attention_balanced_slots(a);
   DMX_REQUIRE(ns > 0, "attention (balanced): the plan keeps the plain grid for B=%d H=%d Sq=%d Skv=%d (dmx_attention_fwd_v)", B, H, Sq, Skv);
   const size_t fb = attn_bal_flag_bytes(ns), need = fb + dmx_attention_balanced_part_bytes(a);
@@ -280,10 +284,8 @@ extern "C" int dmx_attention_fwd_v_balanced(const void* q, int ldq, const void* 
 extern "C" int dmx_attention_fwd_train(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int kv_rows,
                                        void* o, int ldo, float* lse, int B, int H, int Sq, int Skv, float scale, dmx_stream_t stream) {
   DMX_REQUIRE(q && k && v && o && lse, "attention_fwd_train: null argument");
-  AttnArgs a{};
-  a.q = (const bf16*)q; a.ldq = ldq; a.k = (const bf16*)k; a.ldk = ldk; a.kv_rows = kv_rows;
-  a.v = (const bf16*)v; a.ldv = ldv; a.o = (bf16*)o; a.ldo = ldo; a.lse = lse;
-  a.B = B; a.H = H; a.Sq = Sq; a.Skv = Skv; a.scale = scale;
+  AttnArgs a = attn_args(q, ldq, k, ldk, kv_rows, o, ldo, B, H, Sq, Skv, scale);
+  a.v = (const bf16*)v; a.ldv = ldv; a.lse = lse;
   return dmx_attention_launch(a, (hipStream_t)stream);
 }
 extern "C" size_t dmx_attention_bwd_workspace_bytes(int B, int H, int Sq) { return dmx_attn_bwd_ws_bytes(B, H, Sq); }

@@ -1,5 +1,6 @@
-// Host-side executor infrastructure shared by the UNet and VAE graphs:
+// Host-side executor infrastructure shared by the model graphs (UNet, VAE, ViT, TrOCR decoder):
 //   ParamTable  - diffusers state-dict key -> packed location in the caller's weights arena
+//   ModelBase   - what every model handle shares: the table, the bound arena and the bind -> load -> finalize lifecycle
 //   Workspace   - first-fit sub-allocator over the caller's activation workspace; a dry run
 //                 of the same alloc/free sequence gives the exact peak (workspace_bytes query)
 //   Exec        - op wrappers that launch (or, in a dry run, only account for) the kernels
@@ -73,9 +74,33 @@ class Workspace {
   size_t used_ = 0, peak_ = 0; bool failed_ = false;
 };
 
+// Base of the model handles (dmx_unet, dmx_vae, dmx_vit, dmx_trocr_dec).  The lifecycle entry points of the C ABI are one-line
+// forwards to the model_* functions below (DMX_MODEL_ABI); `who` is the model's prefix in error strings ("unet", "vae", ...).
+struct ModelBase {
+  ParamTable pt;
+  char* arena = nullptr;
+  bool finalized = false;
+  virtual ~ModelBase() {}
+  virtual void rebound() {}                                        // the arena was rebound: forget whatever has its addresses baked in
+  virtual int derive(hipStream_t) { return DMX_OK; }               // finalize: whatever the model computes from the raw weights (asynchronous)
+  template <typename T> T* at(size_t off) const { return (T*)(arena + off); }
+};
+int model_param_count(const ModelBase* m);
+int model_param_info(const ModelBase* m, const char* who, int index, const char** name, int shape[4]);
+size_t model_arena_bytes(const ModelBase* m);
+int model_bind_arena(ModelBase* m, const char* who, void* arena, size_t bytes);     // also zeroes the arena (K padding, absent biases)
+int model_load_param(ModelBase* m, const char* who, const char* name, const float* src, hipStream_t stream);
+int model_finalize(ModelBase* m, const char* who, hipStream_t stream);              // derive(), then a stream sync
 // optim.hip: one parameter (torch layout, fp32) into an fp32 master arena laid out like the packed weights arena
-// (weights-arena byte o <-> master byte 2*o); shared by the UNet / autoencoder / ViT handles
-int dmx_master_import(const ParamTable& pt, void* masters, const char* name, const float* src, hipStream_t stream, const char* who);
+// (weights-arena byte o <-> master byte 2*o)
+int model_master_import(const ModelBase* m, const char* who, void* masters, const char* name, const float* src, hipStream_t stream);
+#define DMX_MODEL_ABI(T, who)                                                                                                        \
+  extern "C" void dmx_##who##_destroy(T* m) { delete m; }                                                                            \
+  extern "C" int dmx_##who##_param_count(const T* m) { return model_param_count(m); }                                                \
+  extern "C" int dmx_##who##_param_info(const T* m, int i, const char** name, int shape[4]) { return model_param_info(m, #who, i, name, shape); } \
+  extern "C" size_t dmx_##who##_arena_bytes(const T* m) { return model_arena_bytes(m); }                                             \
+  extern "C" int dmx_##who##_bind_arena(T* m, void* arena, size_t bytes) { return model_bind_arena(m, #who, arena, bytes); }         \
+  extern "C" int dmx_##who##_load_param(T* m, const char* name, const float* src, dmx_stream_t s) { return model_load_param(m, #who, name, src, (hipStream_t)s); }
 
 struct Tn {                 // NHWC bf16 activation [B*H*W][C] with row stride ld
   bf16* p = nullptr; int B = 0, H = 0, W = 0, C = 0, ld = 0;
@@ -95,6 +120,12 @@ struct TapSink {
   float* buf = nullptr; size_t cap = 0, used = 0;     // floats
   int n = 0; int shape[16][4];                         // (B, C, H, W) of tap i, written back to back in `buf`
 };
+// the tap count and shapes, back to the caller of a *_forward_taps / *_forward_f32 entry point (n_taps may be null: nothing is written)
+inline void write_taps(const TapSink& sink, int* tap_shapes, int* n_taps) {
+  if (!n_taps) return;
+  *n_taps = sink.n;
+  for (int i = 0; i < sink.n; ++i) for (int k = 0; k < 4; ++k) tap_shapes[4 * i + k] = sink.shape[i][k];
+}
 
 struct ConvOpts {
   int ksize = 3, stride = 1, pad = 1, ups = 0;
@@ -120,6 +151,15 @@ class Exec {
   // fp32 VALIDATION mode (ref_f32.hip): activations are floats (Tn::p points to float data), weights come from the fp32
   // master arena (callers pass float pointers typed as bf16*), every op runs the plain fp32 kernel.  Tests only.
   bool f32 = false;
+  const char* masters = nullptr;   // f32 mode: the caller's fp32 master arena, where weights-arena byte o lives at byte 2*o (null in dry walks)
+  struct Weights {                 // where the parameters of this walk come from: at<T>(offset in the weights arena)
+    const char* base; size_t mul;
+    template <typename T> const T* at(size_t off) const { return (const T*)(base + off * mul); }
+  };
+  Weights weights(const char* arena) const { return f32 ? Weights{masters, 2} : Weights{arena, 1}; }
+  // a dry walk (workspace queries, prefetch plans) / a real walk on `stream` over the caller's workspace
+  static Exec dry_run(bool f32 = false) { Exec e; e.dry = true; e.f32 = f32; e.ws.reset(nullptr, 0, true); return e; }
+  static Exec on(hipStream_t stream, void* ws, size_t bytes, bool f32 = false) { Exec e; e.stream = stream; e.f32 = f32; e.ws.reset(ws, bytes, false); return e; }
   TapSink* taps = nullptr;
   size_t esz() const { return f32 ? 4 : 2; }
   // column offset inside an activation row, in the active element type
@@ -212,6 +252,6 @@ struct ResW {
 // as extra K columns of conv2 and its bias is folded into conv2's by resnet_finalize.
 void resnet_build(ParamTable& pt, ResW& r, const std::string& p, int cin, int cout);
 int resnet_finalize(const ResW& r, char* arena, hipStream_t stream);
-// wmul: 1 = `arena` is the packed bf16 weights arena; 2 = fp32 validation mode, `arena` is the fp32 master arena (byte offsets double)
+// `arena` is the packed bf16 weights arena; in fp32 validation mode the parameters come from ex.masters instead (Exec::weights)
 Tn resnet_run(Exec& ex, const char* arena, const ResW& r, const Tn& x0, const Tn* x1, int groups, float eps,
-              const float* tproj, int tproj_total, int wmul = 1);
+              const float* tproj, int tproj_total);

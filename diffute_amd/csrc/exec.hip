@@ -684,6 +684,35 @@ void Exec::tap(const Tn& t) {
   taps->used += n;
 }
 
+// --------------------------------------------------------------------------- model handle lifecycle (ModelBase)
+int model_param_count(const ModelBase* m) { return m ? (int)m->pt.entries().size() : 0; }
+int model_param_info(const ModelBase* m, const char* who, int index, const char** name, int shape[4]) {
+  DMX_REQUIRE(m && index >= 0 && index < (int)m->pt.entries().size(), "%s_param_info: bad index %d", who, index);
+  const ParamEntry& e = m->pt.entries()[index];
+  if (name) *name = e.name.c_str();
+  if (shape) for (int k = 0; k < 4; ++k) shape[k] = e.shape[k];
+  return DMX_OK;
+}
+size_t model_arena_bytes(const ModelBase* m) { return m ? m->pt.total() : 0; }
+int model_bind_arena(ModelBase* m, const char* who, void* arena, size_t bytes) {
+  DMX_REQUIRE(m && arena && bytes >= m->pt.total(), "%s_bind_arena: need %zu bytes", who, m ? m->pt.total() : (size_t)0);
+  m->arena = (char*)arena; m->finalized = false; m->rebound();
+  DMX_HIP(hipMemset(arena, 0, m->pt.total()));
+  return DMX_OK;
+}
+int model_load_param(ModelBase* m, const char* who, const char* name, const float* src, hipStream_t stream) {
+  DMX_REQUIRE(m != nullptr, "%s_load_param: null handle", who);
+  m->finalized = false;
+  return m->pt.load(m->arena, name, src, stream);
+}
+int model_finalize(ModelBase* m, const char* who, hipStream_t stream) {
+  DMX_REQUIRE(m && m->arena, "%s_finalize: arena not bound", who);
+  const int rc = m->derive(stream);
+  DMX_HIP(hipStreamSynchronize(stream));
+  m->finalized = (rc == 0);
+  return rc;
+}
+
 // --------------------------------------------------------------------------- ResnetBlock2D
 void resnet_build(ParamTable& pt, ResW& r, const std::string& p, int cin, int cout) {
   r.cin = cin; r.cout = cout; r.shortcut = (cin != cout);
@@ -717,9 +746,10 @@ int resnet_finalize(const ResW& r, char* arena, hipStream_t stream) {
 }
 
 Tn resnet_run(Exec& ex, const char* arena, const ResW& r, const Tn& x0, const Tn* x1, int groups, float eps,
-              const float* tproj, int tproj_total, int wmul) {
-  auto F = [&](size_t off) { return (const float*)(arena + off * (size_t)wmul); };
-  auto H = [&](size_t off) { return (const bf16*)(arena + off * (size_t)wmul); };
+              const float* tproj, int tproj_total) {
+  const Exec::Weights wt = ex.weights(arena);
+  auto F = [&](size_t off) { return wt.at<float>(off); };
+  auto H = [&](size_t off) { return wt.at<bf16>(off); };
   // [GroupNorm -> SiLU -> conv3x3] twice; each pair is ONE launch where the halo conv takes it (Exec::conv_gn)
   ConvOpts o1; o1.bias = F(r.b1); o1.stats = 1;        // norm2 reads conv1's output
   o1.defer = 1;                                        // ... FIRST (and only): a split-K conv1 leaves its reduce pass to norm2

@@ -143,9 +143,10 @@ extern "C" int dmx_unet_optim_table(const dmx_unet* u, void* table_dev, size_t b
 }
 
 // master[name] <- src (fp32, torch layout)
-int dmx_master_import(const ParamTable& pt, void* masters, const char* name, const float* src, hipStream_t stream, const char* who) {
-  const ParamEntry* e = pt.find(name);
-  DMX_REQUIRE(e != nullptr, "%s: unknown parameter %s", who, name);
+int model_master_import(const ModelBase* m, const char* who, void* masters, const char* name, const float* src, hipStream_t stream) {
+  DMX_REQUIRE(m && masters && name && src, "%s_master_import: null argument", who);
+  const ParamEntry* e = m->pt.find(name);
+  DMX_REQUIRE(e != nullptr, "%s_master_import: unknown parameter %s", who, name);
   const PackRule& r = e->rule;
   float* g = (float*)((char*)masters + 2 * r.dst);
   int kind = 0, rows = r.rows, cols = r.cols;
@@ -162,14 +163,11 @@ int dmx_master_import(const ParamTable& pt, void* masters, const char* name, con
   return dmx_check_launch("dmx_master_pack_kernel");
 }
 extern "C" int dmx_unet_master_import(const dmx_unet* u, void* masters, const char* name, const float* src, dmx_stream_t stream) {
-  DMX_REQUIRE(u && masters && name && src, "unet_master_import: null argument");
-  return dmx_master_import(u->pt, masters, name, src, (hipStream_t)stream, "unet_master_import");
+  return model_master_import(u, "unet", masters, name, src, (hipStream_t)stream);
 }
-// the autoencoder's fp32 master copy (same layout rule: weights-arena byte o <-> master byte 2*o); used by the fp32
-// validation path dmx_vae_encode_f32 / dmx_vae_decode_f32
+// the autoencoder's fp32 master copy (same layout rule); used by the fp32 validation path dmx_vae_encode_f32 / dmx_vae_decode_f32
 extern "C" int dmx_vae_master_import(const dmx_vae* v, void* masters, const char* name, const float* src, dmx_stream_t stream) {
-  DMX_REQUIRE(v && masters && name && src, "vae_master_import: null argument");
-  return dmx_master_import(v->pt, masters, name, src, (hipStream_t)stream, "vae_master_import");
+  return model_master_import(v, "vae", masters, name, src, (hipStream_t)stream);
 }
 
 // scalars: device float[2] = (gradient norm before clipping, clip coefficient); workspace: nchunks floats.

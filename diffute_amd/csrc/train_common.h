@@ -159,3 +159,26 @@ struct TrainOps {
     return dx0;
   }
 };
+
+// ------------------------------------------------------------------ transposed weights (data-gradient operands)
+// W^T of a GEMM weight, at the weight's own offset in the `wt` arena (*_train_prepare of both training graphs)
+inline int transpose_linear(const ModelBase* m, char* wt, size_t off, int N, int K, hipStream_t s) {
+  return dmx_transpose_bf16_launch((const bf16*)(m->arena + off), K, (bf16*)(wt + off), N, N, K, s);
+}
+// conv [N][ld: tap*Cin + ci] -> [Cin][flip(tap)*N + n]
+inline int transpose_conv(const ModelBase* m, char* wt, size_t off, int N, int Cin, int ld, int ldt, hipStream_t s) {
+  for (int tap = 0; tap < 9; ++tap) {
+    const int rc = dmx_transpose_bf16_launch((const bf16*)(m->arena + off) + (size_t)tap * Cin, ld,
+                                             (bf16*)(wt + off) + (size_t)(8 - tap) * N, ldt, N, Cin, s);
+    if (rc) return rc;
+  }
+  return DMX_OK;
+}
+inline int transpose_resnet(const ModelBase* m, char* wt, const ResW& r, hipStream_t s) {
+  int rc = transpose_conv(m, wt, r.w1, r.cout, r.cin, 9 * r.cin, 9 * r.cout, s);
+  const int k2 = 9 * r.cout + (r.shortcut ? r.cin : 0);
+  if (!rc) rc = transpose_conv(m, wt, r.w2, r.cout, r.cout, k2, 9 * r.cout, s);
+  if (!rc && r.shortcut)      // Wsc^T [cin][cout] behind the 9*cout*cout elements of the main filter
+    rc = dmx_transpose_bf16_launch((const bf16*)(m->arena + r.w2) + 9 * r.cout, k2, (bf16*)(wt + r.w2) + (size_t)9 * r.cout * r.cout, r.cout, r.cout, r.cin, s);
+  return rc;
+}

@@ -512,15 +512,11 @@ size_t lin_part_floats(int N, int K, int M, int epi) {
 }
 }  // namespace
 
-struct dmx_trocr_dec {
+struct dmx_trocr_dec : ModelBase {
   dmx_trocr_dec_config cfg;
-  ParamTable pt;
-  char* arena = nullptr;
-  bool finalized = false;
   size_t emb, posw, leg = 0, leb = 0, wckv, bckv, lm;
   int npos = 0, kdim = 0, cnt_slice = 0;
   std::vector<DecLayer> layers;
-  template <typename T> T* at(size_t off) const { return (T*)(arena + off); }
 };
 
 namespace {
@@ -557,7 +553,7 @@ DecLayout dec_layout(const dmx_trocr_dec* d, int B, int S, int max_len) {
   o = 0;
   y.encb = take((size_t)B * S * d->kdim * 2);
   y.gemm_ws = o;
-  Exec ex; ex.dry = true; ex.ws.reset(nullptr, 0, true);
+  Exec ex = Exec::dry_run();
   ex.gemm_raw(nullptr, d->kdim, B * S, nullptr, d->kdim, 2 * L * D, d->kdim, nullptr, nullptr, 2 * L * D, 0);
   y.ws_total = std::max(y.step_total, y.gemm_ws + ex.ws.peak() + 4096);
   return y;
@@ -674,33 +670,8 @@ extern "C" dmx_trocr_dec* dmx_trocr_dec_create(const dmx_trocr_dec_config* cfg) 
   d->lm = cfg->tie_word_embeddings ? d->emb : pt.linear("output_projection.weight", V, D);
   return d.release();
 }
-extern "C" void dmx_trocr_dec_destroy(dmx_trocr_dec* d) { delete d; }
-extern "C" int dmx_trocr_dec_param_count(const dmx_trocr_dec* d) { return d ? (int)d->pt.entries().size() : 0; }
-extern "C" int dmx_trocr_dec_param_info(const dmx_trocr_dec* d, int index, const char** name, int shape[4]) {
-  DMX_REQUIRE(d && index >= 0 && index < (int)d->pt.entries().size(), "trocr_dec_param_info: bad index %d", index);
-  const ParamEntry& e = d->pt.entries()[index];
-  if (name) *name = e.name.c_str();
-  if (shape) for (int k = 0; k < 4; ++k) shape[k] = e.shape[k];
-  return DMX_OK;
-}
-extern "C" size_t dmx_trocr_dec_arena_bytes(const dmx_trocr_dec* d) { return d ? d->pt.total() : 0; }
-extern "C" int dmx_trocr_dec_bind_arena(dmx_trocr_dec* d, void* arena, size_t bytes) {
-  DMX_REQUIRE(d && arena && bytes >= d->pt.total(), "trocr_dec_bind_arena: need %zu bytes", d ? d->pt.total() : (size_t)0);
-  d->arena = (char*)arena; d->finalized = false;
-  DMX_HIP(hipMemset(arena, 0, d->pt.total()));
-  return DMX_OK;
-}
-extern "C" int dmx_trocr_dec_load_param(dmx_trocr_dec* d, const char* name, const float* src, dmx_stream_t stream) {
-  DMX_REQUIRE(d != nullptr, "trocr_dec_load_param: null handle");
-  d->finalized = false;
-  return d->pt.load(d->arena, name, src, (hipStream_t)stream);
-}
-extern "C" int dmx_trocr_dec_finalize(dmx_trocr_dec* d, dmx_stream_t stream) {
-  DMX_REQUIRE(d && d->arena, "trocr_dec_finalize: arena not bound");
-  DMX_HIP(hipStreamSynchronize((hipStream_t)stream));
-  d->finalized = true;
-  return DMX_OK;
-}
+DMX_MODEL_ABI(dmx_trocr_dec, trocr_dec)
+extern "C" int dmx_trocr_dec_finalize(dmx_trocr_dec* d, dmx_stream_t stream) { return model_finalize(d, "trocr_dec", (hipStream_t)stream); }
 extern "C" size_t dmx_trocr_dec_cache_bytes(const dmx_trocr_dec* d, int B, int S, int max_len) {
   return d ? dec_layout(d, B, S, max_len).cache_total : 0;
 }
@@ -722,7 +693,7 @@ extern "C" int dmx_trocr_dec_cross_kv(dmx_trocr_dec* d, const float* enc, int B,
   hipLaunchKernelGGL(dmx_f32_to_bf16_kernel, dim3((unsigned)std::min<size_t>(8192, (n + 255) / 256)), dim3(256), 0, st, enc, eb, n);
   int rc = dmx_check_launch("dmx_f32_to_bf16_kernel");
   if (rc) return rc;
-  Exec ex; ex.stream = st; ex.ws.reset((char*)ws + y.gemm_ws, ws_bytes - y.gemm_ws, false);
+  Exec ex = Exec::on(st, (char*)ws + y.gemm_ws, ws_bytes - y.gemm_ws);
   const int N = 2 * d->cfg.num_layers * d->cfg.d_model;
   ex.gemm_raw(eb, d->kdim, B * S, d->at<bf16>(d->wckv), d->kdim, N, d->kdim, d->at<float>(d->bckv), (char*)cache + y.ckv, N, 0);
   return ex.rc;

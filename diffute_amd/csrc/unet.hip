@@ -146,35 +146,12 @@ extern "C" dmx_unet* dmx_unet_create(const dmx_unet_config* cfg) {
   return u.release();
 }
 
-extern "C" void dmx_unet_destroy(dmx_unet* u) { delete u; }
-extern "C" int dmx_unet_param_count(const dmx_unet* u) { return u ? (int)u->pt.entries().size() : 0; }
-extern "C" int dmx_unet_param_info(const dmx_unet* u, int index, const char** name, int shape[4]) {
-  DMX_REQUIRE(u && index >= 0 && index < (int)u->pt.entries().size(), "unet_param_info: bad index %d", index);
-  const ParamEntry& e = u->pt.entries()[index];
-  if (name) *name = e.name.c_str();
-  if (shape) for (int k = 0; k < 4; ++k) shape[k] = e.shape[k];
-  return DMX_OK;
-}
-extern "C" size_t dmx_unet_arena_bytes(const dmx_unet* u) { return u ? u->pt.total() : 0; }
-extern "C" int dmx_unet_bind_arena(dmx_unet* u, void* arena, size_t bytes) {
-  DMX_REQUIRE(u && arena && bytes >= u->pt.total(), "unet_bind_arena: need %zu bytes", u ? u->pt.total() : (size_t)0);
-  u->arena = (char*)arena; u->finalized = false; u->drop_graphs();
-  DMX_HIP(hipMemset(arena, 0, u->pt.total()));      // zero the K padding of conv_in
-  return DMX_OK;
-}
-extern "C" int dmx_unet_load_param(dmx_unet* u, const char* name, const float* src, dmx_stream_t stream) {
-  DMX_REQUIRE(u != nullptr, "unet_load_param: null handle");
-  u->finalized = false;
-  return u->pt.load(u->arena, name, src, (hipStream_t)stream);
-}
+DMX_MODEL_ABI(dmx_unet, unet)
 
 // Recompute everything derived from the raw weights in the arena (folded shortcut biases, LayerNorm-folded GEMM
 // weights and their c1 / c2 vectors) after the raw weights changed in place (fused optimizer); asynchronous.
 static int refresh_derived(dmx_unet* u, hipStream_t s) {
-  auto fuse = [&](const ResW& r) -> int { return resnet_finalize(r, u->arena, s); };
-  int rc = 0;
-  for (int i = 0; i < 4 && !rc; ++i) { for (auto& r : u->down_res[i]) if (!rc) rc = fuse(r); for (auto& r : u->up_res[i]) if (!rc) rc = fuse(r); }
-  if (!rc) rc = fuse(u->mid_res[0]); if (!rc) rc = fuse(u->mid_res[1]);
+  int rc = for_each_resnet(u, [&](const ResW& r) { return resnet_finalize(r, u->arena, s); });
   for (int i = 0; i < 3 && !rc; ++i)
     rc = dmx_ups_phase_weights_launch(u->at<bf16>(u->up_us[i].w), 9 * u->up_us[i].c, u->at<bf16>(u->up_us[i].wp), u->up_us[i].c, u->up_us[i].c, s);
   // fold norm1/2/3 of every BasicTransformerBlock into the GEMM that consumes it (W' = W*gamma, c1, c2)
@@ -195,18 +172,18 @@ extern "C" int dmx_unet_refresh_derived(dmx_unet* u, dmx_stream_t stream) {
   return refresh_derived(u, (hipStream_t)stream);
 }
 
+int dmx_unet::derive(hipStream_t s) {
+  drop_graphs();
+  int rc = refresh_derived(this, s);
+  const bf16* zp = nullptr;
+  if (!rc) rc = dmx_zero_page(&zp);                  // allocate the padding page now, never inside a stream capture
+  return rc;
+}
 extern "C" int dmx_unet_finalize(dmx_unet* u, const float* h_freq, dmx_stream_t stream) {
   DMX_REQUIRE(u && u->arena, "unet_finalize: arena not bound");
   DMX_REQUIRE(h_freq != nullptr, "unet_finalize: null frequency table");
-  hipStream_t s = (hipStream_t)stream;
-  DMX_HIP(hipMemcpyAsync(u->arena + u->freq, h_freq, (size_t)(u->cfg.block_out_channels[0] / 2) * 4, hipMemcpyHostToDevice, s));
-  int rc = refresh_derived(u, s);
-  DMX_HIP(hipStreamSynchronize(s));
-  const bf16* zp = nullptr;
-  if (!rc) rc = dmx_zero_page(&zp);                  // allocate the padding page now, never inside a stream capture
-  u->finalized = (rc == 0);
-  u->drop_graphs();
-  return rc;
+  DMX_HIP(hipMemcpyAsync(u->arena + u->freq, h_freq, (size_t)(u->cfg.block_out_channels[0] / 2) * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
+  return model_finalize(u, "unet", (hipStream_t)stream);
 }
 
 // ----------------------------------------------------------------------------- context
@@ -230,7 +207,7 @@ extern "C" int dmx_unet_set_context(dmx_unet* u, const void* ctx, int ctx_is_bf1
                                     void* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(u && u->finalized, "unet_set_context: weights not finalized");
   DMX_REQUIRE(ctx && cache && cache_bytes >= dmx_unet_context_bytes(u, B, ctx_len), "unet_set_context: context cache too small");
-  Exec ex; ex.stream = (hipStream_t)stream; ex.ws.reset(workspace, workspace_bytes, false);
+  Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes);
   const int D = u->cfg.cross_attention_dim, sp = ctx_pad(ctx_len);
   bf16* cp = (bf16*)ex.raw((size_t)B * sp * D * 2);
   if (ex.rc) return ex.rc;
@@ -250,11 +227,11 @@ namespace {
 
 struct Fwd {
   dmx_unet* u; Exec& ex; int B; const float* tproj; int tp_ld; const void* cache; int ctx_len;
-  const char* wbase; int wmul;      // weights: the packed bf16 arena (x1) or, in fp32 validation mode, the fp32 master arena (byte offsets x2)
-  template <typename T> const T* W(size_t off) const { return (const T*)(wbase + off * (size_t)wmul); }
+  Exec::Weights wt;                 // the packed bf16 arena or, in fp32 validation mode, the fp32 master arena
+  template <typename T> const T* W(size_t off) const { return wt.at<T>(off); }
 
   Tn resnet(const ResW& r, const Tn& x0, const Tn* x1) {
-    return resnet_run(ex, wbase, r, x0, x1, u->cfg.norm_num_groups, 1e-5f, tproj, tp_ld, wmul);
+    return resnet_run(ex, u->arena, r, x0, x1, u->cfg.norm_num_groups, 1e-5f, tproj, tp_ld);
   }
 
   // fp32 validation mode: the same block with explicit LayerNorms on the RAW weights (the folded copies are derived data of
@@ -376,34 +353,36 @@ __global__ __launch_bounds__(256) void dmx_temb_row_kernel(const float* table, c
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) out[i] = src[i];
 }
 
-// the time-embedding MLP + the stacked time_emb_proj of every resnet for `rows` timesteps (product path: fp32 math, bf16 weights;
-// each row is computed exactly as the per-step path computes its single row)
-static int temb_rows(dmx_unet* u, Exec& ex, const long long* timesteps, int rows, float* tproj) {
+}  // namespace
+
+int temb_rows(const dmx_unet* u, Exec& ex, const long long* timesteps, int t_count, int rows, const TembBufs& b, float* tproj) {
   const int c0 = u->cfg.block_out_channels[0], temb = u->temb_dim;
-  float* sinus = (float*)ex.raw((size_t)rows * c0 * 4);
-  float* e1 = (float*)ex.raw((size_t)rows * temb * 4);
-  float* emb = (float*)ex.raw((size_t)rows * temb * 4);
-  if (!ex.dry && !ex.rc) {
-    ex.rc = dmx_timestep_embedding_launch(timesteps, rows, u->at<float>(u->freq), rows, c0, sinus, ex.stream);
-    if (!ex.rc) ex.rc = dmx_linear_small_launch(sinus, c0, u->at<bf16>(u->te_w1), c0, u->at<float>(u->te_b1), e1, temb, rows, temb, c0, 0, ex.stream);
-    if (!ex.rc) ex.rc = dmx_linear_small_launch(e1, temb, u->at<bf16>(u->te_w2), temb, u->at<float>(u->te_b2), emb, temb, rows, temb, temb, 1, ex.stream);
-    if (!ex.rc) ex.rc = dmx_linear_small_launch(emb, temb, u->at<bf16>(u->tp_w), temb, u->at<float>(u->tp_b), tproj, u->tproj_total, rows, u->tproj_total, temb, 1, ex.stream);
-  }
-  ex.drop(sinus); ex.drop(e1); ex.drop(emb);
+  if (ex.dry || ex.rc) return ex.rc;
+  ex.rc = dmx_timestep_embedding_launch(timesteps, t_count, u->at<float>(u->freq), rows, c0, b.sinus, ex.stream);
+  if (!ex.rc) ex.rc = dmx_linear_small_launch(b.sinus, c0, u->at<bf16>(u->te_w1), c0, u->at<float>(u->te_b1), b.e1, temb, rows, temb, c0, 0, ex.stream);
+  if (!ex.rc) ex.rc = dmx_linear_small_launch(b.e1, temb, u->at<bf16>(u->te_w2), temb, u->at<float>(u->te_b2), b.emb, temb, rows, temb, temb, 1, ex.stream);
+  if (!ex.rc) ex.rc = dmx_linear_small_launch(b.emb, temb, u->at<bf16>(u->tp_w), temb, u->at<float>(u->tp_b), tproj, u->tproj_total, rows, u->tproj_total, temb, 1, ex.stream);
+  return ex.rc;
+}
+// the projections of all T timesteps of a denoise loop in one batched pass (each row is computed exactly as the per-step path computes its single row)
+static int temb_table_run(dmx_unet* u, Exec& ex, const long long* timesteps, int T, float* table) {
+  const TembBufs b(u, ex, T);
+  temb_rows(u, ex, timesteps, T, T, b, table);
+  b.drop(ex);
   return ex.rc;
 }
 extern "C" size_t dmx_unet_temb_table_floats(dmx_unet* u, int T) { return u ? (size_t)T * u->tproj_total : 0; }
 extern "C" size_t dmx_unet_temb_table_workspace_bytes(dmx_unet* u, int T) {
   if (!u) return 0;
-  Exec ex; ex.dry = true; ex.ws.reset(nullptr, 0, true);
-  temb_rows(u, ex, nullptr, T, nullptr);
+  Exec ex = Exec::dry_run();
+  temb_table_run(u, ex, nullptr, T, nullptr);
   return ex.ws.peak() + 4096;
 }
 extern "C" int dmx_unet_temb_table(dmx_unet* u, const int64_t* timesteps, int T, float* table, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(u && u->finalized, "unet_temb_table: weights not finalized");
   DMX_REQUIRE(timesteps && table && workspace && T > 0, "unet_temb_table: null argument");
-  Exec ex; ex.stream = (hipStream_t)stream; ex.ws.reset(workspace, workspace_bytes, false);
-  return temb_rows(u, ex, (const long long*)timesteps, T, table);
+  Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes);
+  return temb_table_run(u, ex, (const long long*)timesteps, T, table);
 }
 extern "C" int dmx_unet_use_temb_table(dmx_unet* u, const float* table, const int* step_index) {
   DMX_REQUIRE(u != nullptr, "unet_use_temb_table: null handle");
@@ -412,32 +391,38 @@ extern "C" int dmx_unet_use_temb_table(dmx_unet* u, const float* table, const in
   return DMX_OK;
 }
 
-int unet_run(dmx_unet* u, Exec& ex, const float* f0, int c0, const float* f1, int c1, const float* f2, int c2,
-             const long long* timesteps, int t_count, const void* cache, int ctx_len, float* out, int B, int H, int W) {
+int unet_check_call(const dmx_unet* u, const UNetCall& c, const void* workspace, const char* who) {
+  DMX_REQUIRE(u && u->finalized, "%s: weights not finalized (bind_arena, load_param*, finalize)", who);
+  DMX_REQUIRE(c.f0 && c.out && c.timesteps && c.ctx && workspace, "%s: null argument", who);
+  DMX_REQUIRE(c.c0 + c.c1 + c.c2 == u->cfg.in_channels, "%s: c0+c1+c2=%d != in_channels=%d", who, c.c0 + c.c1 + c.c2, u->cfg.in_channels);
+  DMX_REQUIRE(c.B > 0 && c.H > 0 && c.W > 0 && c.H % 8 == 0 && c.W % 8 == 0, "%s: H=%d W=%d must be positive multiples of 8", who, c.H, c.W);
+  return DMX_OK;
+}
+
+namespace {
+
+int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c) {
+  const int B = c.B, H = c.H, W = c.W, t_count = c.t_count;
   const dmx_unet_config& cfg = u->cfg;
   const int* boc = cfg.block_out_channels; const int L = cfg.layers_per_block; const int temb = u->temb_dim;
   // ---- time embedding (fp32, bf16 weights).  A scalar timestep (the denoise loop) is embedded once and every image reads
   // row 0 of the projections (row stride 0); per-sample timesteps (training) get one row each.
   const int Bt = (t_count == 1) ? 1 : B;
   const int tp_ld = (t_count == 1) ? 0 : u->tproj_total;
-  float* sinus = (float*)ex.raw((size_t)B * boc[0] * 4);              // sized for B rows either way (workspace query)
-  float* e1 = (float*)ex.raw((size_t)B * temb * 4);
-  float* emb = (float*)ex.raw((size_t)B * temb * 4);
+  const TembBufs te(u, ex, B);                                        // sized for B rows either way (workspace query)
+  float* const sinus = te.sinus; float* const e1 = te.e1; float* const emb = te.emb;
   float* tproj = (float*)ex.raw((size_t)B * u->tproj_total * 4);
-  const char* wbase = ex.f32 ? (const char*)u->masters_f32 : u->arena;
-  const int wmul = ex.f32 ? 2 : 1;
-  Fwd f{u, ex, B, tproj, tp_ld, cache, ctx_len, wbase, wmul};
+  Fwd f{u, ex, B, tproj, tp_ld, c.ctx, c.ctx_len, ex.weights(u->arena)};
   Tn h;
   if (ex.f32) {
     // fp32 validation mode: same layers on the fp32 masters through the generic fp32 GEMM (SiLU as its own tiny pass)
     auto small = [&](float* x, int K, size_t w, size_t b, int N, float* y) {
-      Tn xi; xi.p = (bf16*)x; xi.B = Bt; xi.H = xi.W = 1; xi.C = K; xi.ld = K;
       if (ex.dry || ex.rc) return;
       GemmF32Args a{}; a.x0 = a.x1 = x; a.ldx0 = a.ldx1 = K; a.cx0 = a.Cin = K; a.direct = 1; a.ksize = 1; a.stride = 1; a.Ktaps = a.K = K;
       a.w = f.W<float>(w); a.ldw = K; a.M = Bt; a.N = N; a.bias = f.W<float>(b); a.rows_per_group = 1; a.out = y; a.ldo = N;
       ex.rc = dmx_gemm_f32_launch(a, ex.stream);
     };
-    if (!ex.dry && !ex.rc) ex.rc = dmx_timestep_embedding_launch(timesteps, t_count, (const float*)(u->arena + u->freq), Bt, boc[0], sinus, ex.stream);
+    if (!ex.dry && !ex.rc) ex.rc = dmx_timestep_embedding_launch(c.timesteps, t_count, (const float*)(u->arena + u->freq), Bt, boc[0], sinus, ex.stream);
     small(sinus, boc[0], u->te_w1, u->te_b1, temb, e1);
     if (!ex.dry && !ex.rc) ex.rc = dmx_silu_f32_launch(e1, (size_t)Bt * temb, ex.stream);
     small(e1, temb, u->te_w2, u->te_b2, temb, emb);
@@ -446,27 +431,23 @@ int unet_run(dmx_unet* u, Exec& ex, const float* f0, int c0, const float* f1, in
     // stacked bf16 weight rows) they are not one contiguous vector there - gather them into one
     float* tpb = (float*)ex.raw((size_t)u->tproj_total * 4);
     if (!ex.dry && !ex.rc) {
-      auto put = [&](const ResW& r) {
-        if (r.temb_off >= 0 && !ex.rc &&
+      for_each_resnet(u, [&](const ResW& r) {
+        if (r.temb_off >= 0 &&
             hipMemcpyAsync(tpb + r.temb_off, f.W<float>(u->tp_b + (size_t)r.temb_off * 4), (size_t)r.cout * 4, hipMemcpyDeviceToDevice, ex.stream) != hipSuccess) {
           dmx_set_error("unet_forward_f32: bias gather failed"); ex.rc = DMX_ERR_HIP;
         }
-      };
-      for (int i = 0; i < 4; ++i) { for (auto& r : u->down_res[i]) put(r); for (auto& r : u->up_res[i]) put(r); }
-      put(u->mid_res[0]); put(u->mid_res[1]);
+        return ex.rc;
+      });
     }
-    {
-      Tn xi; (void)xi;
-      if (!ex.dry && !ex.rc) {
-        GemmF32Args a{}; a.x0 = a.x1 = emb; a.ldx0 = a.ldx1 = temb; a.cx0 = a.Cin = temb; a.direct = 1; a.ksize = 1; a.stride = 1; a.Ktaps = a.K = temb;
-        a.w = f.W<float>(u->tp_w); a.ldw = temb; a.M = Bt; a.N = u->tproj_total; a.bias = tpb; a.rows_per_group = 1; a.out = tproj; a.ldo = u->tproj_total;
-        ex.rc = dmx_gemm_f32_launch(a, ex.stream);
-      }
+    if (!ex.dry && !ex.rc) {
+      GemmF32Args a{}; a.x0 = a.x1 = emb; a.ldx0 = a.ldx1 = temb; a.cx0 = a.Cin = temb; a.direct = 1; a.ksize = 1; a.stride = 1; a.Ktaps = a.K = temb;
+      a.w = f.W<float>(u->tp_w); a.ldw = temb; a.M = Bt; a.N = u->tproj_total; a.bias = tpb; a.rows_per_group = 1; a.out = tproj; a.ldo = u->tproj_total;
+      ex.rc = dmx_gemm_f32_launch(a, ex.stream);
     }
     ex.drop(tpb);
-    ex.drop(sinus); ex.drop(e1); ex.drop(emb);
+    te.drop(ex);
     Tn x9 = ex.make(B, H, W, cfg.in_channels);
-    if (!ex.dry && !ex.rc) ex.rc = dmx_concat_nchw_to_nhwc_f32_launch(f0, c0, f1, c1, f2, c2, (float*)x9.p, B, H * W, ex.stream);
+    if (!ex.dry && !ex.rc) ex.rc = dmx_concat_nchw_to_nhwc_f32_launch(c.f0, c.c0, c.f1, c.c1, c.f2, c.c2, (float*)x9.p, B, H * W, ex.stream);
     ConvOpts oi; oi.bias = f.W<float>(u->ci_b); oi.ldw = u->ci_kpad;
     h = ex.conv(x9, nullptr, f.W<bf16>(u->ci_w), boc[0], oi);
     ex.drop(x9);
@@ -477,17 +458,14 @@ int unet_run(dmx_unet* u, Exec& ex, const float* f0, int c0, const float* f1, in
         hipLaunchKernelGGL(dmx_temb_row_kernel, dim3(cdiv(u->tproj_total, 1024)), dim3(256), 0, ex.stream, u->temb_table, u->temb_step, tproj, u->tproj_total);
         ex.rc = dmx_check_launch("dmx_temb_row_kernel");
       } else {
-        ex.rc = dmx_timestep_embedding_launch(timesteps, t_count, u->at<float>(u->freq), Bt, boc[0], sinus, ex.stream);
-        if (!ex.rc) ex.rc = dmx_linear_small_launch(sinus, boc[0], u->at<bf16>(u->te_w1), boc[0], u->at<float>(u->te_b1), e1, temb, Bt, temb, boc[0], 0, ex.stream);
-        if (!ex.rc) ex.rc = dmx_linear_small_launch(e1, temb, u->at<bf16>(u->te_w2), temb, u->at<float>(u->te_b2), emb, temb, Bt, temb, temb, 1, ex.stream);
-        if (!ex.rc) ex.rc = dmx_linear_small_launch(emb, temb, u->at<bf16>(u->tp_w), temb, u->at<float>(u->tp_b), tproj, u->tproj_total, Bt, u->tproj_total, temb, 1, ex.stream);
+        temb_rows(u, ex, c.timesteps, t_count, Bt, te, tproj);
       }
     }
-    ex.drop(sinus); ex.drop(e1); ex.drop(emb);
+    te.drop(ex);
     // ---- conv_in: cat + layout + im2col, then GEMM
     Tn col = ex.make(B, H, W, u->ci_kpad);
     if (!ex.dry && !ex.rc) {
-      Im2colArgs a{}; a.f0 = f0; a.c0 = c0; a.f1 = f1; a.c1 = c1; a.f2 = f2; a.c2 = c2; a.C = cfg.in_channels;
+      Im2colArgs a{}; a.f0 = c.f0; a.c0 = c.c0; a.f1 = c.f1; a.c1 = c.c1; a.f2 = c.f2; a.c2 = c.c2; a.C = cfg.in_channels;
       a.B = B; a.IH = a.OH = H; a.IW = a.OW = W; a.ksize = 3; a.stride = 1; a.pad = 1; a.out = col.p; a.Kpad = u->ci_kpad;
       ex.rc = dmx_im2col_small_launch(a, ex.stream);
     }
@@ -551,36 +529,51 @@ int unet_run(dmx_unet* u, Exec& ex, const float* f0, int c0, const float* f1, in
   ConvOpts oo; oo.bias = f.W<float>(u->co_b); oo.out_f32 = 1;
   ex.conv(t, nullptr, f.W<bf16>(u->co_w), cfg.out_channels, oo, eps_nhwc);
   ex.drop(t);
-  if (!ex.dry && !ex.rc) ex.rc = dmx_nhwc_to_nchw_f32_launch(eps_nhwc, cfg.out_channels, out, B, cfg.out_channels, H * W, ex.stream);
+  if (!ex.dry && !ex.rc) ex.rc = dmx_nhwc_to_nchw_f32_launch(eps_nhwc, cfg.out_channels, c.out, B, cfg.out_channels, H * W, ex.stream);
   ex.drop(eps_nhwc); ex.drop(tproj);
   return ex.rc;
 }
 
 // the product walk with the weight prefetch plan (Exec::note / peek): a dry walk of the same graph lists the weight ranges in launch
 // order, the real walk hands every launch the ranges of the launches that follow it
-int unet_run_planned(dmx_unet* u, Exec& ex, const float* f0, int c0, const float* f1, int c1, const float* f2, int c2,
-                     const long long* timesteps, int t_count, const void* cache, int ctx_len, float* out, int B, int H, int W) {
+int unet_run_planned(dmx_unet* u, Exec& ex, const UNetCall& c) {
   Exec::PfPlan plan;
   {
-    Exec dr; dr.dry = true; dr.ws.reset(nullptr, 0, true); dr.plan = &plan; dr.plan_rec = true;
-    unet_run(u, dr, nullptr, c0, nullptr, c1, nullptr, c2, nullptr, t_count, cache, ctx_len, nullptr, B, H, W);
+    Exec dr = Exec::dry_run(); dr.plan = &plan; dr.plan_rec = true;
+    UNetCall d = c; d.f0 = d.f1 = d.f2 = nullptr; d.timesteps = nullptr; d.out = nullptr;
+    unet_run(u, dr, d);
   }
   ex.plan = &plan; ex.plan_rec = false; ex.plan_bad = false; ex.plan_i = 0;
-  int rc = unet_run(u, ex, f0, c0, f1, c1, f2, c2, timesteps, t_count, cache, ctx_len, out, B, H, W);
+  int rc = unet_run(u, ex, c);
   if (!rc && (ex.plan_bad || ex.plan_i != (int)plan.w.size())) { dmx_set_error("unet: the prefetch plan of the dry walk (%d launches) does not match the real walk (%d)", (int)plan.w.size(), ex.plan_i); rc = DMX_ERR_ARG; }
   ex.plan = nullptr;
   return rc;
+}
+
+// the call record of a workspace query: shapes only
+UNetCall dry_call(int t_count, int ctx_len, int B, int H, int W) {
+  UNetCall c; c.t_count = t_count; c.ctx_len = ctx_len; c.B = B; c.H = H; c.W = W;
+  return c;
+}
+// the call record of the C ABI's argument list (the one place that list is spelled out)
+#define UNET_CALL_PARAMS const float* f0, int c0, const float* f1, int c1, const float* f2, int c2, const int64_t* timesteps, int t_count, \
+                         const void* ctx, int ctx_len, float* out, int B, int H, int W
+#define UNET_CALL_RECORD UNetCall{f0, f1, f2, c0, c1, c2, (const long long*)timesteps, t_count, ctx, ctx_len, out, B, H, W}
+
+int forward_eager(dmx_unet* u, const UNetCall& c, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  Exec ex = Exec::on(stream, workspace, workspace_bytes);
+  return unet_run_planned(u, ex, c);
 }
 
 }  // namespace
 
 extern "C" size_t dmx_unet_workspace_bytes(dmx_unet* u, int B, int H, int W, int ctx_len) {
   if (!u) return 0;
-  Exec ex; ex.dry = true; ex.ws.reset(nullptr, 0, true);
-  unet_run(u, ex, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 1, nullptr, ctx_len, nullptr, B, H, W);
+  Exec ex = Exec::dry_run();
+  unet_run(u, ex, dry_call(1, ctx_len, B, H, W));
   size_t need = ex.ws.peak();
   // set_context needs the padded context + split-K scratch
-  Exec e2; e2.dry = true; e2.ws.reset(nullptr, 0, true);
+  Exec e2 = Exec::dry_run();
   const int D = u->cfg.cross_attention_dim, sp = ctx_pad(ctx_len);
   void* cp = e2.raw((size_t)B * sp * D * 2);
   for (const XfW* x : u->xf_all)
@@ -589,81 +582,69 @@ extern "C" size_t dmx_unet_workspace_bytes(dmx_unet* u, int B, int H, int W, int
   return need + 4096;
 }
 
-extern "C" int dmx_unet_forward(dmx_unet* u, const float* f0, int c0, const float* f1, int c1, const float* f2, int c2,
-                                const int64_t* timesteps, int t_count, const void* cache, int ctx_len,
-                                float* out, int B, int H, int W, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
-  DMX_REQUIRE(u && u->finalized, "unet_forward: weights not finalized (bind_arena, load_param*, finalize)");
-  DMX_REQUIRE(f0 && out && timesteps && cache && workspace, "unet_forward: null argument");
-  DMX_REQUIRE(c0 + c1 + c2 == u->cfg.in_channels, "unet_forward: c0+c1+c2=%d != in_channels=%d", c0 + c1 + c2, u->cfg.in_channels);
-  DMX_REQUIRE(B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "unet_forward: H=%d W=%d must be positive multiples of 8", H, W);
-  Exec ex; ex.stream = (hipStream_t)stream; ex.ws.reset(workspace, workspace_bytes, false);
-  return unet_run_planned(u, ex, f0, c0, f1, c1, f2, c2, (const long long*)timesteps, t_count, cache, ctx_len, out, B, H, W);
+extern "C" int dmx_unet_forward(dmx_unet* u, UNET_CALL_PARAMS, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
+  const UNetCall c = UNET_CALL_RECORD;
+  if (const int rc = unet_check_call(u, c, workspace, "unet_forward")) return rc;
+  return forward_eager(u, c, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // dmx_unet_forward + debug taps: the block outputs conv_in, down0..3, mid, up0..3 (the oracle's tap points) are copied out as
 // NCHW fp32, back to back, into `taps`; shapes (B, C, H, W) land in tap_shapes[i*4..], the count in *n_taps.
-extern "C" int dmx_unet_forward_taps(dmx_unet* u, const float* f0, int c0, const float* f1, int c1, const float* f2, int c2,
-                                     const int64_t* timesteps, int t_count, const void* cache, int ctx_len, float* out, int B, int H, int W,
-                                     void* workspace, size_t workspace_bytes, float* taps, size_t tap_floats, int* tap_shapes, int* n_taps, dmx_stream_t stream) {
-  DMX_REQUIRE(u && u->finalized, "unet_forward_taps: weights not finalized");
-  DMX_REQUIRE(f0 && out && timesteps && cache && workspace && taps && tap_shapes && n_taps, "unet_forward_taps: null argument");
-  DMX_REQUIRE(c0 + c1 + c2 == u->cfg.in_channels && B > 0 && H % 8 == 0 && W % 8 == 0, "unet_forward_taps: bad shapes");
+extern "C" int dmx_unet_forward_taps(dmx_unet* u, UNET_CALL_PARAMS, void* workspace, size_t workspace_bytes,
+                                     float* taps, size_t tap_floats, int* tap_shapes, int* n_taps, dmx_stream_t stream) {
+  const UNetCall c = UNET_CALL_RECORD;
+  if (const int rc = unet_check_call(u, c, workspace, "unet_forward_taps")) return rc;
+  DMX_REQUIRE(taps && tap_shapes && n_taps, "unet_forward_taps: null argument");
   TapSink sink; sink.buf = taps; sink.cap = tap_floats;
-  Exec ex; ex.stream = (hipStream_t)stream; ex.ws.reset(workspace, workspace_bytes, false); ex.taps = &sink;
-  const int rc = unet_run(u, ex, f0, c0, f1, c1, f2, c2, (const long long*)timesteps, t_count, cache, ctx_len, out, B, H, W);
-  *n_taps = sink.n;
-  for (int i = 0; i < sink.n; ++i) for (int k = 0; k < 4; ++k) tap_shapes[4 * i + k] = sink.shape[i][k];
+  Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes); ex.taps = &sink;
+  const int rc = unet_run(u, ex, c);
+  write_taps(sink, tap_shapes, n_taps);
   return rc;
 }
 
 // fp32 VALIDATION forward (tests): the same graph walker on fp32 activations, the fp32 master copy of the parameters
 // (`masters`: dmx_unet_grad_bytes(u) bytes filled by dmx_unet_master_import for every parameter) and the plain fp32 kernels of
-// ref_f32.hip.  `context` is the raw glyph context [B][ctx_len][cross_attention_dim] fp32 (its K / V are projected in the call).
+// ref_f32.hip.  `ctx` is the raw glyph context [B][ctx_len][cross_attention_dim] fp32 (its K / V are projected in the call).
 // taps / tap_shapes / n_taps may be NULL.  Never used by the product path.
 extern "C" size_t dmx_unet_workspace_bytes_f32(dmx_unet* u, int B, int H, int W, int ctx_len) {
   if (!u) return 0;
-  Exec ex; ex.dry = true; ex.f32 = true; ex.ws.reset(nullptr, 0, true);
-  unet_run(u, ex, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, B, nullptr, ctx_len, nullptr, B, H, W);
+  Exec ex = Exec::dry_run(true);
+  unet_run(u, ex, dry_call(B, ctx_len, B, H, W));
   return ex.ws.peak() + 4096;
 }
 extern "C" int dmx_unet_forward_f32(dmx_unet* u, const void* masters, const float* f0, int c0, const float* f1, int c1, const float* f2, int c2,
-                                    const int64_t* timesteps, int t_count, const float* context, int ctx_len, float* out, int B, int H, int W,
+                                    const int64_t* timesteps, int t_count, const float* ctx, int ctx_len, float* out, int B, int H, int W,
                                     void* workspace, size_t workspace_bytes, float* taps, size_t tap_floats, int* tap_shapes, int* n_taps, dmx_stream_t stream) {
-  DMX_REQUIRE(u && u->finalized && masters, "unet_forward_f32: weights not finalized / no master arena");
-  DMX_REQUIRE(f0 && out && timesteps && context && workspace, "unet_forward_f32: null argument");
-  DMX_REQUIRE(c0 + c1 + c2 == u->cfg.in_channels && B > 0 && H % 8 == 0 && W % 8 == 0, "unet_forward_f32: bad shapes");
+  const UNetCall c = UNET_CALL_RECORD;
+  if (const int rc = unet_check_call(u, c, workspace, "unet_forward_f32")) return rc;
+  DMX_REQUIRE(masters != nullptr, "unet_forward_f32: no master arena");
   TapSink sink; sink.buf = taps; sink.cap = tap_floats;
-  Exec ex; ex.stream = (hipStream_t)stream; ex.ws.reset(workspace, workspace_bytes, false); ex.f32 = true;
+  Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes, true); ex.masters = (const char*)masters;
   if (taps) ex.taps = &sink;
-  u->masters_f32 = masters;
-  const int rc = unet_run(u, ex, f0, c0, f1, c1, f2, c2, (const long long*)timesteps, t_count, context, ctx_len, out, B, H, W);
-  u->masters_f32 = nullptr;
-  if (n_taps) { *n_taps = sink.n; for (int i = 0; i < sink.n; ++i) for (int k = 0; k < 4; ++k) tap_shapes[4 * i + k] = sink.shape[i][k]; }
+  const int rc = unet_run(u, ex, c);
+  write_taps(sink, tap_shapes, n_taps);
   return rc;
 }
 
 // Same contract as dmx_unet_forward, but the launch sequence (~600 kernels) is captured into a hipGraph the second
-// time an identical argument tuple is seen and replayed afterwards (one hipGraphLaunch per UNet step).  Needs a
+// time an identical call is seen and replayed afterwards (one hipGraphLaunch per UNet step).  Needs a
 // non-default stream (the legacy NULL stream cannot be captured); falls back to eager launches otherwise or while
 // the profiler is recording.
 bool dmx_profile_active();
-extern "C" int dmx_unet_forward_graph(dmx_unet* u, const float* f0, int c0, const float* f1, int c1, const float* f2, int c2,
-                                      const int64_t* timesteps, int t_count, const void* cache, int ctx_len,
-                                      float* out, int B, int H, int W, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
-  DMX_REQUIRE(u && u->finalized, "unet_forward_graph: weights not finalized");
-  if (stream == nullptr || dmx_profile_active())
-    return dmx_unet_forward(u, f0, c0, f1, c1, f2, c2, timesteps, t_count, cache, ctx_len, out, B, H, W, workspace, workspace_bytes, stream);
-  dmx_unet::GraphKey key(f0, f1, f2, timesteps, cache, out, workspace, c0, c1, c2, t_count, ctx_len, B, H, W, u->temb_table, u->temb_step, dmx_plan_epoch());
-  dmx_unet::GraphEntry& e = u->graphs[key];
+extern "C" int dmx_unet_forward_graph(dmx_unet* u, UNET_CALL_PARAMS, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
+  const UNetCall c = UNET_CALL_RECORD;
+  if (const int rc = unet_check_call(u, c, workspace, "unet_forward_graph")) return rc;
   hipStream_t s = (hipStream_t)stream;
+  if (s == nullptr || dmx_profile_active()) return forward_eager(u, c, workspace, workspace_bytes, s);
+  const dmx_unet::GraphKey key = u->graph_key(c, workspace);
+  dmx_unet::GraphEntry& e = u->graphs[key];
   if (e.exec) { DMX_HIP(hipGraphLaunch(e.exec, s)); return dmx_poll_device_error(); }      // (what an earlier replay raised: common.h)
   if (e.seen++ == 0)        // first sight: eager (also runs every one-time hipFuncSetAttribute outside a capture)
-    return dmx_unet_forward(u, f0, c0, f1, c1, f2, c2, timesteps, t_count, cache, ctx_len, out, B, H, W, workspace, workspace_bytes, stream);
+    return forward_eager(u, c, workspace, workspace_bytes, s);
   if (u->graphs.size() > 64) { u->graphs.erase(key); u->drop_graphs(); }
-  DMX_REQUIRE(f0 && out && timesteps && cache && workspace, "unet_forward_graph: null argument");
   DMX_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  Exec ex; ex.stream = s; ex.ws.reset(workspace, workspace_bytes, false);
-  const int rc = unet_run_planned(u, ex, f0, c0, f1, c1, f2, c2, (const long long*)timesteps, t_count, cache, ctx_len, out, B, H, W);
+  Exec ex = Exec::on(s, workspace, workspace_bytes);
+  const int rc = unet_run_planned(u, ex, c);
   hipGraph_t g = nullptr;
   const hipError_t ce = hipStreamEndCapture(s, &g);
   if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }

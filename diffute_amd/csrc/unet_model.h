@@ -17,11 +17,18 @@ struct XfW {
 };
 struct ConvW { size_t w, b; int c; size_t wp = 0; /* upsamplers: derived [4][c][4c] phase weights */ };
 
-struct dmx_unet {
+// One forward call of the UNet as the C ABI describes it: the three channel groups of the input (NCHW fp32; cat order), the timesteps,
+// the cross-attention context (product path: the K / V cache of dmx_unet_set_context; fp32 validation and training: the raw context) and
+// the output (NCHW fp32)
+struct UNetCall {
+  const float *f0 = nullptr, *f1 = nullptr, *f2 = nullptr; int c0 = 0, c1 = 0, c2 = 0;
+  const long long* timesteps = nullptr; int t_count = 1;
+  const void* ctx = nullptr; int ctx_len = 0;
+  float* out = nullptr; int B = 0, H = 0, W = 0;
+};
+
+struct dmx_unet : ModelBase {
   dmx_unet_config cfg;
-  ParamTable pt;
-  char* arena = nullptr;
-  const void* masters_f32 = nullptr;   // fp32 validation forward only (dmx_unet_forward_f32): the caller's fp32 master arena for the duration of the call
   int temb_dim = 0, tproj_total = 0;
   size_t te_w1, te_b1, te_w2, te_b2, tp_w, tp_b, freq;
   size_t ci_w, ci_b; int ci_kpad = 0;
@@ -31,21 +38,59 @@ struct dmx_unet {
   ResW mid_res[2]; XfW mid_xf;
   std::vector<XfW*> xf_all;          // cross-attention layers in graph order (context cache slots)
   std::vector<TrJob> tr_cache;       // the transpose job table dmx_unet_train_prepare uploaded last (kernels.h TrBatch)
-  bool finalized = false;
   std::shared_ptr<void> train_state;   // live training pass (unet_train.hip)
-  // hipGraph cache: one captured UNet step per distinct argument tuple (pointers are baked into the nodes)
-  typedef std::tuple<const void*, const void*, const void*, const void*, const void*, const void*, const void*,
-                     int, int, int, int, int, int, int, int, const void*, const void*, int> GraphKey;       // (last: dmx_plan_epoch() - every dmx_set_* switch changes the plans baked into the graph)
   // optional source of the time-embedding projections (dmx_unet_use_temb_table): row *temb_step of a table computed for all
   // timesteps of a denoise loop in one batched pass, instead of four small launches per step
   const float* temb_table = nullptr; const int* temb_step = nullptr;
+  // hipGraph cache: one captured UNet step per distinct call (pointers are baked into the nodes).  The key is everything the captured
+  // launches depend on: the call record, the workspace, the time-embedding table and dmx_plan_epoch() (every dmx_set_* switch changes
+  // the plans baked into the graph)
+  struct GraphKey {
+    const void *f0, *f1, *f2, *timesteps, *ctx, *out, *workspace; int c0, c1, c2, t_count, ctx_len, B, H, W;
+    const void *temb_table, *temb_step; int plan_epoch;
+    auto tie() const { return std::tie(f0, f1, f2, timesteps, ctx, out, workspace, c0, c1, c2, t_count, ctx_len, B, H, W, temb_table, temb_step, plan_epoch); }
+    bool operator<(const GraphKey& o) const { return tie() < o.tie(); }
+  };
+  GraphKey graph_key(const UNetCall& c, const void* workspace) const {
+    return GraphKey{c.f0, c.f1, c.f2, c.timesteps, c.ctx, c.out, workspace, c.c0, c.c1, c.c2, c.t_count, c.ctx_len, c.B, c.H, c.W,
+                    temb_table, temb_step, dmx_plan_epoch()};
+  }
   struct GraphEntry { hipGraphExec_t exec = nullptr; int seen = 0; };
   std::map<GraphKey, GraphEntry> graphs;
   void drop_graphs() { for (auto& kv : graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec); graphs.clear(); }
-  ~dmx_unet() { drop_graphs(); }
-
-  template <typename T> T* at(size_t off) const { return (T*)(arena + off); }
+  ~dmx_unet() override { drop_graphs(); }
+  void rebound() override { drop_graphs(); }
+  int derive(hipStream_t s) override;     // unet.hip: folded biases / LayerNorm-folded weights / phase weights, the zero page; drops the graphs
 };
 
+// every ResnetBlock2D of the UNet, level by level (down_res[i], up_res[i]), then the two of the mid block; stops at the first non-zero
+// return of fn(ResW&) and returns it.  (NOT the order the parameter table registers time_emb_proj in - down, mid, up: dmx_unet_create
+// spells that one out.)
+template <typename F> int for_each_resnet(dmx_unet* u, F&& fn) {
+  for (int i = 0; i < 4; ++i) {
+    for (auto& r : u->down_res[i]) if (const int rc = fn(r)) return rc;
+    for (auto& r : u->up_res[i]) if (const int rc = fn(r)) return rc;
+  }
+  for (auto& r : u->mid_res) if (const int rc = fn(r)) return rc;
+  return 0;
+}
+
+// the common argument checks of the forward entry points (`who` names the entry point in the error string)
+int unet_check_call(const dmx_unet* u, const UNetCall& c, const void* workspace, const char* who);
+
+// The time-embedding MLP and the stacked time_emb_proj of every resnet (product path: fp32 math, bf16 weights), four launches:
+// sinusoid of `t_count` timesteps broadcast to `rows` rows, linear_1, linear_2, time_emb_proj -> tproj[rows][tproj_total].  The per-step
+// path, the batched table of a denoise loop and the training forward (which keeps the intermediates for its backward) all run this
+// one, so a row is the same bits wherever it was computed.  The caller owns the buffers (their place in the allocation order is part
+// of the workspace contract).
+struct TembBufs {
+  float *sinus = nullptr, *e1 = nullptr, *emb = nullptr;
+  TembBufs() {}
+  TembBufs(const dmx_unet* u, Exec& ex, int rows)
+      : sinus((float*)ex.raw((size_t)rows * u->cfg.block_out_channels[0] * 4)), e1((float*)ex.raw((size_t)rows * u->temb_dim * 4)),
+        emb((float*)ex.raw((size_t)rows * u->temb_dim * 4)) {}
+  void drop(Exec& ex) const { ex.drop(sinus); ex.drop(e1); ex.drop(emb); }
+};
+int temb_rows(const dmx_unet* u, Exec& ex, const long long* timesteps, int t_count, int rows, const TembBufs& b, float* tproj);
 
 static inline int dmx_ctx_pad(int ctx_len) { return (int)align_up((size_t)ctx_len, 64); }

@@ -121,7 +121,7 @@ struct TrainState {
   std::vector<ResSave> down_res[4], up_res[4]; std::vector<XfSave> down_xf[4], up_xf[4];
   ResSave mid_res[2]; XfSave mid_xf;
   ConvSave down_ds[4], up_us[4];
-  float *sinus = nullptr, *e1 = nullptr, *emb = nullptr;
+  TembBufs te;                                          // the stages of the time-embedding MLP (kept: the backward needs every one)
   Tn col, h0, hlast, tout; float* st_out = nullptr;
   std::vector<Tn> skips;                                // in push order (forward)
 };
@@ -142,79 +142,71 @@ struct TrainSession {
     ++ev_next;
   }
 
-  int forward(const float* f0, int c0, const float* f1, int c1, const float* f2, int c2, const long long* timesteps, int t_count,
-              const void* ctx, int ctx_is_bf16, float* pred, int B_, int H_, int W_) {
-    B = B_; H = H_; W = W_;
+  int forward(const UNetCall& c, int ctx_is_bf16) {
+    B = c.B; H = c.H; W = c.W;
     const int ctx_len = T.ctx_len;
-  const dmx_unet_config& cfg = u->cfg;
-  const int* boc = cfg.block_out_channels; const int L = cfg.layers_per_block; const int temb = u->temb_dim;
-  const int D = cfg.cross_attention_dim, sp = dmx_ctx_pad(ctx_len);
-  auto live = [&]() { return !ex.dry && !ex.rc; };
-  // ---- time embedding (kept: the backward needs every stage)
-  st.sinus = (float*)ex.raw((size_t)B * boc[0] * 4);
-  st.e1 = (float*)ex.raw((size_t)B * temb * 4);
-  st.emb = (float*)ex.raw((size_t)B * temb * 4);
-  T.tproj = (float*)ex.raw((size_t)B * u->tproj_total * 4);
-  T.dtproj = (float*)ex.raw((size_t)B * u->tproj_total * 4);
-  if (live()) {
-    ex.rc = dmx_timestep_embedding_launch(timesteps, t_count, u->at<float>(u->freq), B, boc[0], st.sinus, ex.stream);
-    if (!ex.rc) ex.rc = dmx_linear_small_launch(st.sinus, boc[0], u->at<bf16>(u->te_w1), boc[0], u->at<float>(u->te_b1), st.e1, temb, B, temb, boc[0], 0, ex.stream);
-    if (!ex.rc) ex.rc = dmx_linear_small_launch(st.e1, temb, u->at<bf16>(u->te_w2), temb, u->at<float>(u->te_b2), st.emb, temb, B, temb, temb, 1, ex.stream);
-    if (!ex.rc) ex.rc = dmx_linear_small_launch(st.emb, temb, u->at<bf16>(u->tp_w), temb, u->at<float>(u->tp_b), T.tproj, u->tproj_total, B, u->tproj_total, temb, 1, ex.stream);
-  }
-  // ---- context rows, padded to a multiple of 64 per image (zero rows)
-  T.ctxp = ex.make(1, 1, B * sp, D);
-  if (live()) ex.rc = dmx_cast_pad_rows_launch(ctx, ctx_is_bf16, T.ctxp.p, B, ctx_len, sp, D, ex.stream);
-  // ---- conv_in
-  st.col = ex.make(B, H, W, u->ci_kpad);
-  if (live()) {
-    Im2colArgs a{}; a.f0 = f0; a.c0 = c0; a.f1 = f1; a.c1 = c1; a.f2 = f2; a.c2 = c2; a.C = cfg.in_channels;
-    a.B = B; a.IH = a.OH = H; a.IW = a.OW = W; a.ksize = 3; a.stride = 1; a.pad = 1; a.out = st.col.p; a.Kpad = u->ci_kpad;
-    ex.rc = dmx_im2col_small_launch(a, ex.stream);
-  }
-  Tn h = ex.linear(st.col, u->at<bf16>(u->ci_w), boc[0], u->at<float>(u->ci_b), nullptr, false);
-  st.h0 = h;
-  st.skips.push_back(h);
-  for (int i = 0; i < 4; ++i) {
-    st.down_res[i].resize(L); if (cfg.down_has_attn[i]) st.down_xf[i].resize(L);
-    for (int j = 0; j < L; ++j) {
-      Tn y = T.res_fwd(u->down_res[i][j], h, nullptr, st.down_res[i][j]);
-      if (cfg.down_has_attn[i]) y = T.xf_fwd(u->down_xf[i][j], y, st.down_xf[i][j]);
-      h = y; st.skips.push_back(h);
+    const dmx_unet_config& cfg = u->cfg;
+    const int* boc = cfg.block_out_channels; const int L = cfg.layers_per_block;
+    const int D = cfg.cross_attention_dim, sp = dmx_ctx_pad(ctx_len);
+    auto live = [&]() { return !ex.dry && !ex.rc; };
+    // ---- time embedding (kept: the backward needs every stage)
+    st.te = TembBufs(u, ex, B);
+    T.tproj = (float*)ex.raw((size_t)B * u->tproj_total * 4);
+    T.dtproj = (float*)ex.raw((size_t)B * u->tproj_total * 4);
+    temb_rows(u, ex, c.timesteps, c.t_count, B, st.te, T.tproj);
+    // ---- context rows, padded to a multiple of 64 per image (zero rows)
+    T.ctxp = ex.make(1, 1, B * sp, D);
+    if (live()) ex.rc = dmx_cast_pad_rows_launch(c.ctx, ctx_is_bf16, T.ctxp.p, B, ctx_len, sp, D, ex.stream);
+    // ---- conv_in
+    st.col = ex.make(B, H, W, u->ci_kpad);
+    if (live()) {
+      Im2colArgs a{}; a.f0 = c.f0; a.c0 = c.c0; a.f1 = c.f1; a.c1 = c.c1; a.f2 = c.f2; a.c2 = c.c2; a.C = cfg.in_channels;
+      a.B = B; a.IH = a.OH = H; a.IW = a.OW = W; a.ksize = 3; a.stride = 1; a.pad = 1; a.out = st.col.p; a.Kpad = u->ci_kpad;
+      ex.rc = dmx_im2col_small_launch(a, ex.stream);
     }
-    if (i < 3) {
-      ConvOpts o; o.stride = 2; o.pad = 1; o.bias = u->at<float>(u->down_ds[i].b);
-      st.down_ds[i].x = h;
-      h = ex.conv(h, nullptr, u->at<bf16>(u->down_ds[i].w), boc[i], o);
-      st.skips.push_back(h);
+    Tn h = ex.linear(st.col, u->at<bf16>(u->ci_w), boc[0], u->at<float>(u->ci_b), nullptr, false);
+    st.h0 = h;
+    st.skips.push_back(h);
+    for (int i = 0; i < 4; ++i) {
+      st.down_res[i].resize(L); if (cfg.down_has_attn[i]) st.down_xf[i].resize(L);
+      for (int j = 0; j < L; ++j) {
+        Tn y = T.res_fwd(u->down_res[i][j], h, nullptr, st.down_res[i][j]);
+        if (cfg.down_has_attn[i]) y = T.xf_fwd(u->down_xf[i][j], y, st.down_xf[i][j]);
+        h = y; st.skips.push_back(h);
+      }
+      if (i < 3) {
+        ConvOpts o; o.stride = 2; o.pad = 1; o.bias = u->at<float>(u->down_ds[i].b);
+        st.down_ds[i].x = h;
+        h = ex.conv(h, nullptr, u->at<bf16>(u->down_ds[i].w), boc[i], o);
+        st.skips.push_back(h);
+      }
     }
-  }
-  { Tn y = T.res_fwd(u->mid_res[0], h, nullptr, st.mid_res[0]);
-    Tn z = T.xf_fwd(u->mid_xf, y, st.mid_xf);
-    h = T.res_fwd(u->mid_res[1], z, nullptr, st.mid_res[1]); }
-  std::vector<Tn> stack = st.skips;
-  for (int i = 0; i < 4; ++i) {
-    st.up_res[i].resize(L + 1); if (cfg.up_has_attn[i]) st.up_xf[i].resize(L + 1);
-    for (int j = 0; j < L + 1; ++j) {
-      Tn s = stack.back(); stack.pop_back();
-      Tn y = T.res_fwd(u->up_res[i][j], h, &s, st.up_res[i][j]);
-      if (cfg.up_has_attn[i]) y = T.xf_fwd(u->up_xf[i][j], y, st.up_xf[i][j]);
-      h = y;
+    { Tn y = T.res_fwd(u->mid_res[0], h, nullptr, st.mid_res[0]);
+      Tn z = T.xf_fwd(u->mid_xf, y, st.mid_xf);
+      h = T.res_fwd(u->mid_res[1], z, nullptr, st.mid_res[1]); }
+    std::vector<Tn> stack = st.skips;
+    for (int i = 0; i < 4; ++i) {
+      st.up_res[i].resize(L + 1); if (cfg.up_has_attn[i]) st.up_xf[i].resize(L + 1);
+      for (int j = 0; j < L + 1; ++j) {
+        Tn s = stack.back(); stack.pop_back();
+        Tn y = T.res_fwd(u->up_res[i][j], h, &s, st.up_res[i][j]);
+        if (cfg.up_has_attn[i]) y = T.xf_fwd(u->up_xf[i][j], y, st.up_xf[i][j]);
+        h = y;
+      }
+      if (i < 3) {
+        ConvOpts o; o.ups = 1; o.bias = u->at<float>(u->up_us[i].b);
+        st.up_us[i].x = h;
+        h = ex.conv(h, nullptr, u->at<bf16>(u->up_us[i].w), boc[3 - i], o);
+      }
     }
-    if (i < 3) {
-      ConvOpts o; o.ups = 1; o.bias = u->at<float>(u->up_us[i].b);
-      st.up_us[i].x = h;
-      h = ex.conv(h, nullptr, u->at<bf16>(u->up_us[i].w), boc[3 - i], o);
-    }
-  }
-  st.hlast = h;
-  st.tout = T.gn(h, nullptr, u->cno_g, u->cno_b, 1e-5f, true, &st.st_out);
-  const int OC = cfg.out_channels;
-  float* eps_nhwc = (float*)ex.raw((size_t)B * H * W * OC * 4);
-  { ConvOpts oo; oo.bias = u->at<float>(u->co_b); oo.out_f32 = 1;
-    ex.conv(st.tout, nullptr, u->at<bf16>(u->co_w), OC, oo, eps_nhwc); }
-  if (live()) ex.rc = dmx_nhwc_to_nchw_f32_launch(eps_nhwc, OC, pred, B, OC, H * W, ex.stream);
-  ex.drop(eps_nhwc);
+    st.hlast = h;
+    st.tout = T.gn(h, nullptr, u->cno_g, u->cno_b, 1e-5f, true, &st.st_out);
+    const int OC = cfg.out_channels;
+    float* eps_nhwc = (float*)ex.raw((size_t)B * H * W * OC * 4);
+    { ConvOpts oo; oo.bias = u->at<float>(u->co_b); oo.out_f32 = 1;
+      ex.conv(st.tout, nullptr, u->at<bf16>(u->co_w), OC, oo, eps_nhwc); }
+    if (live()) ex.rc = dmx_nhwc_to_nchw_f32_launch(eps_nhwc, OC, c.out, B, OC, H * W, ex.stream);
+    ex.drop(eps_nhwc);
     forward_done = (ex.rc == 0);
     return ex.rc;
   }
@@ -228,145 +220,119 @@ struct TrainSession {
     char* wt = T.wt;
     auto live = [&]() { return !ex.dry && !ex.rc; };
     ev_next = 0;
-  // conv_out: OC (=4) output channels -> pad dY to 8 columns for the wgrad kernel; the data gradient goes through an
-  // im2col of dY (K = 9*OC padded to 64) and a [C0][64] transposed filter
-  Tn dy8 = ex.make(B, H, W, 8);
-  float* dw8 = (float*)ex.raw((size_t)8 * 9 * boc[0] * 4);
-  if (live()) {
-    ex.rc = (int)hipMemsetAsync(dy8.p, 0, (size_t)dy8.rows() * 8 * 2, ex.stream) ? DMX_ERR_HIP : 0;
-    if (!ex.rc) ex.rc = dmx_nchw_f32_to_nhwc_bf16_launch(dpred, dy8.p, 8, B, OC, H * W, ex.stream);
-  }
-  T.wgrad(dy8, st.tout, nullptr, 3, 1, 0, dw8, 9 * boc[0]);
-  if (live()) ex.rc = (int)hipMemcpyAsync(T.G(u->co_w), dw8, (size_t)OC * 9 * boc[0] * 4, hipMemcpyDeviceToDevice, ex.stream) ? DMX_ERR_HIP : 0;
-  { float* db8 = (float*)ex.raw(8 * 4);
-    T.colsum(dy8, 1, db8, 8);
-    if (live()) ex.rc = (int)hipMemcpyAsync(T.G(u->co_b), db8, (size_t)OC * 4, hipMemcpyDeviceToDevice, ex.stream) ? DMX_ERR_HIP : 0;
-    ex.drop(db8); }
-  ex.drop(dw8); ex.drop(dy8);
-  Tn dcol = ex.make(B, H, W, 64);
-  if (live()) {
-    Im2colArgs a{}; a.f0 = dpred; a.c0 = OC; a.C = OC; a.B = B; a.IH = a.OH = H; a.IW = a.OW = W; a.ksize = 3; a.stride = 1; a.pad = 1;
-    a.out = dcol.p; a.Kpad = 64;
-    ex.rc = dmx_im2col_small_launch(a, ex.stream);
-  }
-  Tn dtout = ex.linear(dcol, (const bf16*)(wt + co_wt_off(u)), boc[0], nullptr, nullptr, false);   // [C0][64], behind the mirrored arena
-  ex.drop(dcol);
-  Tn dh = T.gn_bwd(st.hlast, nullptr, u->cno_g, u->cno_b, true, st.st_out, dtout, nullptr, nullptr, nullptr);
-  ex.drop(dtout);
+    // conv_out: OC (=4) output channels -> pad dY to 8 columns for the wgrad kernel; the data gradient goes through an
+    // im2col of dY (K = 9*OC padded to 64) and a [C0][64] transposed filter
+    Tn dy8 = ex.make(B, H, W, 8);
+    float* dw8 = (float*)ex.raw((size_t)8 * 9 * boc[0] * 4);
+    if (live()) {
+      ex.rc = (int)hipMemsetAsync(dy8.p, 0, (size_t)dy8.rows() * 8 * 2, ex.stream) ? DMX_ERR_HIP : 0;
+      if (!ex.rc) ex.rc = dmx_nchw_f32_to_nhwc_bf16_launch(dpred, dy8.p, 8, B, OC, H * W, ex.stream);
+    }
+    T.wgrad(dy8, st.tout, nullptr, 3, 1, 0, dw8, 9 * boc[0]);
+    if (live()) ex.rc = (int)hipMemcpyAsync(T.G(u->co_w), dw8, (size_t)OC * 9 * boc[0] * 4, hipMemcpyDeviceToDevice, ex.stream) ? DMX_ERR_HIP : 0;
+    { float* db8 = (float*)ex.raw(8 * 4);
+      T.colsum(dy8, 1, db8, 8);
+      if (live()) ex.rc = (int)hipMemcpyAsync(T.G(u->co_b), db8, (size_t)OC * 4, hipMemcpyDeviceToDevice, ex.stream) ? DMX_ERR_HIP : 0;
+      ex.drop(db8); }
+    ex.drop(dw8); ex.drop(dy8);
+    Tn dcol = ex.make(B, H, W, 64);
+    if (live()) {
+      Im2colArgs a{}; a.f0 = dpred; a.c0 = OC; a.C = OC; a.B = B; a.IH = a.OH = H; a.IW = a.OW = W; a.ksize = 3; a.stride = 1; a.pad = 1;
+      a.out = dcol.p; a.Kpad = 64;
+      ex.rc = dmx_im2col_small_launch(a, ex.stream);
+    }
+    Tn dtout = ex.linear(dcol, (const bf16*)(wt + co_wt_off(u)), boc[0], nullptr, nullptr, false);   // [C0][64], behind the mirrored arena
+    ex.drop(dcol);
+    Tn dh = T.gn_bwd(st.hlast, nullptr, u->cno_g, u->cno_b, true, st.st_out, dtout, nullptr, nullptr, nullptr);
+    ex.drop(dtout);
 
-  mark();                                                     // bucket: conv_out, conv_norm_out
-  if (live()) ex.rc = (int)hipMemsetAsync(T.dtproj, 0, (size_t)B * u->tproj_total * 4, ex.stream) ? DMX_ERR_HIP : 0;
-  std::map<const bf16*, Tn> sgrad;                            // gradients the up path sends to the skip tensors
-  // ---- up blocks, reversed
-  size_t sp_idx = 0;                                          // skips consumed by the up path so far (forward order: from the back)
-  std::vector<std::pair<int, int>> up_order;                  // (i, j) in forward order
-  for (int i = 0; i < 4; ++i) for (int j = 0; j < L + 1; ++j) up_order.push_back({i, j});
-  (void)sp_idx;
-  for (int i = 3; i >= 0; --i) {
-    if (i < 3) {
-      // upsample conv: y = conv(up2(x)) + b
-      const ConvW& cw = u->up_us[i];
-      T.wgrad(dh, st.up_us[i].x, nullptr, 3, 1, 1, T.G(cw.w), 9 * cw.c);
-      T.colsum(dh, 1, T.G(cw.b), cw.c);
-      float* du = (float*)ex.raw((size_t)dh.rows() * cw.c * 4);
-      { ConvOpts o; o.out_f32 = 1; ex.conv(dh, nullptr, T.WT(cw.w), cw.c, o, du); }
-      Tn dx = ex.make(B, st.up_us[i].x.H, st.up_us[i].x.W, cw.c);
-      if (live()) ex.rc = dmx_sumpool2_launch(du, cw.c, 1, dx.p, dx.ld, B, dx.H, dx.W, cw.c, 0, ex.stream);
-      ex.drop(du); ex.drop(dh); dh = dx;
-    }
-    for (int j = L; j >= 0; --j) {
-      if (cfg.up_has_attn[i]) { Tn d = T.xf_bwd(u->up_xf[i][j], st.up_xf[i][j], dh); ex.drop(dh); dh = d; }
-      Tn dx1;
-      Tn dx0 = T.res_bwd(u->up_res[i][j], st.up_res[i][j], dh, nullptr, &dx1);
-      ex.drop(dh); dh = dx0;
-      sgrad[st.up_res[i][j].x1.p] = dx1;
-    }
-    mark();                                                   // bucket: up_blocks[i]
-  }
-  auto take = [&](const Tn& x) -> Tn* { auto it = sgrad.find(x.p); return it == sgrad.end() ? nullptr : &it->second; };
-  auto done = [&](const Tn& x) { auto it = sgrad.find(x.p); if (it != sgrad.end()) { ex.drop(it->second); sgrad.erase(it); } };
-  // ---- mid block
-  { Tn d = T.res_bwd(u->mid_res[1], st.mid_res[1], dh, nullptr, nullptr); ex.drop(dh);
-    Tn e = T.xf_bwd(u->mid_xf, st.mid_xf, d); ex.drop(d);
-    Tn* g0 = take(st.mid_res[0].x0);
-    dh = T.res_bwd(u->mid_res[0], st.mid_res[0], e, g0, nullptr); ex.drop(e);
-    done(st.mid_res[0].x0); }
-  mark();                                                     // bucket: mid_block
-  // ---- down blocks, reversed.  dh is now the TOTAL gradient of the last down-path tensor.
-  for (int i = 3; i >= 0; --i) {
-    if (i < 3) {
-      // stride-2 conv: its output (a skip) already has its total gradient in dh; input = level i's last tensor (a skip too)
-      const ConvW& cw = u->down_ds[i];
-      const Tn& x = st.down_ds[i].x;
-      T.wgrad(dh, x, nullptr, 3, 2, 0, T.G(cw.w), 9 * cw.c);
-      T.colsum(dh, 1, T.G(cw.b), cw.c);
-      Tn z = ex.make(B, x.H, x.W, cw.c);
-      if (live()) ex.rc = dmx_zero_insert2_launch(dh.p, dh.ld, z.p, B, dh.H, dh.W, cw.c, ex.stream);
-      ConvOpts o; o.res = take(x);
-      Tn dx = ex.conv(z, nullptr, T.WT(cw.w), cw.c, o);
-      ex.drop(z); ex.drop(dh); done(x); dh = dx;
-    }
-    for (int j = L - 1; j >= 0; --j) {
-      if (cfg.down_has_attn[i]) { Tn d = T.xf_bwd(u->down_xf[i][j], st.down_xf[i][j], dh); ex.drop(dh); dh = d; }
-      ResSave& rs = st.down_res[i][j];
-      Tn* g0 = take(rs.x0);
-      Tn dx0 = T.res_bwd(u->down_res[i][j], rs, dh, g0, nullptr);
-      ex.drop(dh); done(rs.x0); dh = dx0;
-    }
-    mark();                                                   // bucket: down_blocks[i]
-  }
-  // ---- conv_in (im2col GEMM): dW = dh0^T col, db; no data gradient (the latents are inputs)
-  T.wgrad(dh, st.col, nullptr, 1, 1, 0, T.G(u->ci_w), u->ci_kpad);
-  T.colsum(dh, 1, T.G(u->ci_b), boc[0]);
-  ex.drop(dh);
-  // ---- time embedding: tproj = Wp silu(emb) + bp ; emb = W2 silu(e1) + b2 ; e1 = W1 sinus + b1
-  float* demb = (float*)ex.raw((size_t)B * temb * 4);
-  float* de1 = (float*)ex.raw((size_t)B * temb * 4);
-  float* dbtp = (float*)ex.raw((size_t)u->tproj_total * 4);
-  if (live()) {
-    ex.rc = dmx_linear_small_bwd_launch(st.emb, temb, T.dtproj, u->tproj_total, u->at<bf16>(u->tp_w), temb, T.G(u->tp_w), temb, dbtp, 1,
-                                        demb, temb, B, u->tproj_total, temb, 1, 0, ex.stream);
-    // the per-resnet bias entries live at arena offset tp_b + 4*temb_off, i.e. gradient offset 2*tp_b + 8*temb_off
-    auto put = [&](const ResW& r) {
-      if (!ex.rc && hipMemcpyAsync(T.G(u->tp_b + (size_t)r.temb_off * 4), dbtp + r.temb_off, (size_t)r.cout * 4, hipMemcpyDeviceToDevice, ex.stream) != hipSuccess) {
-        dmx_set_error("hipMemcpyAsync failed (time_emb_proj bias gradient)"); ex.rc = DMX_ERR_HIP;
+    mark();                                                     // bucket: conv_out, conv_norm_out
+    if (live()) ex.rc = (int)hipMemsetAsync(T.dtproj, 0, (size_t)B * u->tproj_total * 4, ex.stream) ? DMX_ERR_HIP : 0;
+    std::map<const bf16*, Tn> sgrad;                            // gradients the up path sends to the skip tensors
+    // ---- up blocks, reversed
+    for (int i = 3; i >= 0; --i) {
+      if (i < 3) {
+        // upsample conv: y = conv(up2(x)) + b
+        const ConvW& cw = u->up_us[i];
+        T.wgrad(dh, st.up_us[i].x, nullptr, 3, 1, 1, T.G(cw.w), 9 * cw.c);
+        T.colsum(dh, 1, T.G(cw.b), cw.c);
+        float* du = (float*)ex.raw((size_t)dh.rows() * cw.c * 4);
+        { ConvOpts o; o.out_f32 = 1; ex.conv(dh, nullptr, T.WT(cw.w), cw.c, o, du); }
+        Tn dx = ex.make(B, st.up_us[i].x.H, st.up_us[i].x.W, cw.c);
+        if (live()) ex.rc = dmx_sumpool2_launch(du, cw.c, 1, dx.p, dx.ld, B, dx.H, dx.W, cw.c, 0, ex.stream);
+        ex.drop(du); ex.drop(dh); dh = dx;
       }
-    };
-    for (int i = 0; i < 4; ++i) { for (auto& r : u->down_res[i]) put(r); for (auto& r : u->up_res[i]) put(r); }
-    put(u->mid_res[0]); put(u->mid_res[1]);
-    if (!ex.rc) ex.rc = dmx_linear_small_bwd_launch(st.e1, temb, demb, temb, u->at<bf16>(u->te_w2), temb, T.G(u->te_w2), temb, T.G(u->te_b2), 1,
-                                                    de1, temb, B, temb, temb, 1, 0, ex.stream);
-    if (!ex.rc) ex.rc = dmx_linear_small_bwd_launch(st.sinus, boc[0], de1, temb, u->at<bf16>(u->te_w1), boc[0], T.G(u->te_w1), boc[0], T.G(u->te_b1), 1,
-                                                    nullptr, 0, B, temb, boc[0], 0, 0, ex.stream);
-  }
-  ex.drop(dbtp);
-  ex.drop(demb); ex.drop(de1);
+      for (int j = L; j >= 0; --j) {
+        if (cfg.up_has_attn[i]) { Tn d = T.xf_bwd(u->up_xf[i][j], st.up_xf[i][j], dh); ex.drop(dh); dh = d; }
+        Tn dx1;
+        Tn dx0 = T.res_bwd(u->up_res[i][j], st.up_res[i][j], dh, nullptr, &dx1);
+        ex.drop(dh); dh = dx0;
+        sgrad[st.up_res[i][j].x1.p] = dx1;
+      }
+      mark();                                                   // bucket: up_blocks[i]
+    }
+    auto take = [&](const Tn& x) -> Tn* { auto it = sgrad.find(x.p); return it == sgrad.end() ? nullptr : &it->second; };
+    auto done = [&](const Tn& x) { auto it = sgrad.find(x.p); if (it != sgrad.end()) { ex.drop(it->second); sgrad.erase(it); } };
+    // ---- mid block
+    { Tn d = T.res_bwd(u->mid_res[1], st.mid_res[1], dh, nullptr, nullptr); ex.drop(dh);
+      Tn e = T.xf_bwd(u->mid_xf, st.mid_xf, d); ex.drop(d);
+      Tn* g0 = take(st.mid_res[0].x0);
+      dh = T.res_bwd(u->mid_res[0], st.mid_res[0], e, g0, nullptr); ex.drop(e);
+      done(st.mid_res[0].x0); }
+    mark();                                                     // bucket: mid_block
+    // ---- down blocks, reversed.  dh is now the TOTAL gradient of the last down-path tensor.
+    for (int i = 3; i >= 0; --i) {
+      if (i < 3) {
+        // stride-2 conv: its output (a skip) already has its total gradient in dh; input = level i's last tensor (a skip too)
+        const ConvW& cw = u->down_ds[i];
+        const Tn& x = st.down_ds[i].x;
+        T.wgrad(dh, x, nullptr, 3, 2, 0, T.G(cw.w), 9 * cw.c);
+        T.colsum(dh, 1, T.G(cw.b), cw.c);
+        Tn z = ex.make(B, x.H, x.W, cw.c);
+        if (live()) ex.rc = dmx_zero_insert2_launch(dh.p, dh.ld, z.p, B, dh.H, dh.W, cw.c, ex.stream);
+        ConvOpts o; o.res = take(x);
+        Tn dx = ex.conv(z, nullptr, T.WT(cw.w), cw.c, o);
+        ex.drop(z); ex.drop(dh); done(x); dh = dx;
+      }
+      for (int j = L - 1; j >= 0; --j) {
+        if (cfg.down_has_attn[i]) { Tn d = T.xf_bwd(u->down_xf[i][j], st.down_xf[i][j], dh); ex.drop(dh); dh = d; }
+        ResSave& rs = st.down_res[i][j];
+        Tn* g0 = take(rs.x0);
+        Tn dx0 = T.res_bwd(u->down_res[i][j], rs, dh, g0, nullptr);
+        ex.drop(dh); done(rs.x0); dh = dx0;
+      }
+      mark();                                                   // bucket: down_blocks[i]
+    }
+    // ---- conv_in (im2col GEMM): dW = dh0^T col, db; no data gradient (the latents are inputs)
+    T.wgrad(dh, st.col, nullptr, 1, 1, 0, T.G(u->ci_w), u->ci_kpad);
+    T.colsum(dh, 1, T.G(u->ci_b), boc[0]);
+    ex.drop(dh);
+    // ---- time embedding: tproj = Wp silu(emb) + bp ; emb = W2 silu(e1) + b2 ; e1 = W1 sinus + b1
+    float* demb = (float*)ex.raw((size_t)B * temb * 4);
+    float* de1 = (float*)ex.raw((size_t)B * temb * 4);
+    float* dbtp = (float*)ex.raw((size_t)u->tproj_total * 4);
+    if (live()) {
+      ex.rc = dmx_linear_small_bwd_launch(st.te.emb, temb, T.dtproj, u->tproj_total, u->at<bf16>(u->tp_w), temb, T.G(u->tp_w), temb, dbtp, 1,
+                                          demb, temb, B, u->tproj_total, temb, 1, 0, ex.stream);
+      // the per-resnet bias entries live at arena offset tp_b + 4*temb_off, i.e. gradient offset 2*tp_b + 8*temb_off
+      if (!ex.rc) for_each_resnet(u, [&](const ResW& r) {
+        if (hipMemcpyAsync(T.G(u->tp_b + (size_t)r.temb_off * 4), dbtp + r.temb_off, (size_t)r.cout * 4, hipMemcpyDeviceToDevice, ex.stream) != hipSuccess) {
+          dmx_set_error("hipMemcpyAsync failed (time_emb_proj bias gradient)"); ex.rc = DMX_ERR_HIP;
+        }
+        return ex.rc;
+      });
+      if (!ex.rc) ex.rc = dmx_linear_small_bwd_launch(st.te.e1, temb, demb, temb, u->at<bf16>(u->te_w2), temb, T.G(u->te_w2), temb, T.G(u->te_b2), 1,
+                                                      de1, temb, B, temb, temb, 1, 0, ex.stream);
+      if (!ex.rc) ex.rc = dmx_linear_small_bwd_launch(st.te.sinus, boc[0], de1, temb, u->at<bf16>(u->te_w1), boc[0], T.G(u->te_w1), boc[0], T.G(u->te_b1), 1,
+                                                      nullptr, 0, B, temb, boc[0], 0, 0, ex.stream);
+    }
+    ex.drop(dbtp);
+    ex.drop(demb); ex.drop(de1);
     mark();
     return ex.rc;
   }
 };
 
-// ------------------------------------------------------------------ transposed weights (data-gradient operands)
-int transpose_linear(const dmx_unet* u, char* wt, size_t off, int N, int K, hipStream_t s) {
-  return dmx_transpose_bf16_launch((const bf16*)(u->arena + off), K, (bf16*)(wt + off), N, N, K, s);
-}
-// conv [N][ld: tap*Cin + ci] -> [Cin][flip(tap)*N + n]
-int transpose_conv(const dmx_unet* u, char* wt, size_t off, int N, int Cin, int ld, int ldt, hipStream_t s) {
-  for (int tap = 0; tap < 9; ++tap) {
-    const int rc = dmx_transpose_bf16_launch((const bf16*)(u->arena + off) + (size_t)tap * Cin, ld,
-                                             (bf16*)(wt + off) + (size_t)(8 - tap) * N, ldt, N, Cin, s);
-    if (rc) return rc;
-  }
-  return DMX_OK;
-}
-int transpose_resnet(const dmx_unet* u, char* wt, const ResW& r, hipStream_t s) {
-  int rc = transpose_conv(u, wt, r.w1, r.cout, r.cin, 9 * r.cin, 9 * r.cout, s);
-  const int k2 = 9 * r.cout + (r.shortcut ? r.cin : 0);
-  if (!rc) rc = transpose_conv(u, wt, r.w2, r.cout, r.cout, k2, 9 * r.cout, s);
-  if (!rc && r.shortcut)      // Wsc^T [cin][cout] behind the 9*cout*cout elements of the main filter
-    rc = dmx_transpose_bf16_launch((const bf16*)(u->arena + r.w2) + 9 * r.cout, k2, (bf16*)(wt + r.w2) + (size_t)9 * r.cout * r.cout, r.cout, r.cout, r.cin, s);
-  return rc;
-}
 int transpose_xf(const dmx_unet* u, char* wt, const XfW& x, hipStream_t s) {
   const int C = x.C;
   int rc = transpose_linear(u, wt, x.wpi, C, C, s);
@@ -410,8 +376,9 @@ __global__ __launch_bounds__(256) void dmx_grad_unpack_kernel(const float* g, fl
 extern "C" size_t dmx_unet_train_workspace_bytes(dmx_unet* u, int B, int H, int W, int ctx_len) {
   if (!u) return 0;
   TrainSession ts(u, nullptr, B, ctx_len);
-  ts.ex.dry = true; ts.ex.ws.reset(nullptr, 0, true);
-  ts.forward(nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 1, nullptr, 0, nullptr, B, H, W);
+  ts.ex = Exec::dry_run();
+  UNetCall c; c.B = B; c.H = H; c.W = W;
+  ts.forward(c, 0);
   ts.backward(nullptr, nullptr);
   return ts.ex.ws.peak() + 4096;
 }
@@ -460,15 +427,14 @@ extern "C" int dmx_unet_train_forward(dmx_unet* u, const void* wt_arena,
                                       const float* f0, int c0, const float* f1, int c1, const float* f2, int c2,
                                       const int64_t* timesteps, int t_count, const void* ctx, int ctx_is_bf16, int ctx_len,
                                       float* pred, int B, int H, int W, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
-  DMX_REQUIRE(u && u->finalized, "unet_train_forward: weights not finalized");
-  DMX_REQUIRE(wt_arena && f0 && timesteps && ctx && pred && workspace, "unet_train_forward: null argument");
-  DMX_REQUIRE(c0 + c1 + c2 == u->cfg.in_channels, "unet_train_forward: c0+c1+c2=%d != in_channels=%d", c0 + c1 + c2, u->cfg.in_channels);
-  DMX_REQUIRE(B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "unet_train_forward: H=%d W=%d must be positive multiples of 8", H, W);
+  const UNetCall c{f0, f1, f2, c0, c1, c2, (const long long*)timesteps, t_count, ctx, ctx_len, pred, B, H, W};
+  if (const int rc = unet_check_call(u, c, workspace, "unet_train_forward")) return rc;
+  DMX_REQUIRE(wt_arena != nullptr, "unet_train_forward: null argument");
   DMX_REQUIRE(t_count == 1 || t_count == B, "unet_train_forward: t_count=%d must be 1 or B", t_count);
   auto ts = std::make_shared<TrainSession>(u, (char*)wt_arena, B, ctx_len);
-  ts->ex.stream = (hipStream_t)stream; ts->ex.ws.reset(workspace, workspace_bytes, false);
+  ts->ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes);
   u->train_state = ts;
-  const int rc = ts->forward(f0, c0, f1, c1, f2, c2, (const long long*)timesteps, t_count, ctx, ctx_is_bf16, pred, B, H, W);
+  const int rc = ts->forward(c, ctx_is_bf16);
   if (rc) u->train_state.reset();
   return rc;
 }
@@ -485,7 +451,6 @@ extern "C" int dmx_unet_train_bucket_range(const dmx_unet* u, int i, size_t* beg
     for (const ParamEntry& e : u->pt.entries()) if (e.name.rfind(prefix, 0) == 0 && e.rule.dst < lo) lo = e.rule.dst;
     return lo;
   };
-  const size_t total = u->pt.total();
   const size_t e_down[4] = {first("down_blocks.0."), first("down_blocks.1."), first("down_blocks.2."), first("down_blocks.3.")};
   const size_t e_mid = first("mid_block."), e_up[4] = {first("up_blocks.0."), first("up_blocks.1."), first("up_blocks.2."), first("up_blocks.3.")};
   const size_t e_out = first("conv_norm_out."), e_tp = u->tp_w;
@@ -496,7 +461,6 @@ extern "C" int dmx_unet_train_bucket_range(const dmx_unet* u, int i, size_t* beg
   else if (i >= 6 && i <= 9) { const int lvl = 9 - i; lo = e_down[lvl]; hi = lvl == 3 ? e_mid : e_down[lvl + 1]; }
   else { lo = 0; hi = e_down[0]; }            // bucket 10: time_embedding + conv_in ... and the time_emb_proj block below
   *begin = 2 * lo; *end = 2 * hi;
-  (void)total;
   return DMX_OK;
 }
 // the batched time_emb_proj matrix sits behind conv_out in the arena; its gradient completes with bucket 10

@@ -40,21 +40,22 @@ void attn_build(ParamTable& pt, AttnW& a, const std::string& p, int C) {
 // (attention_wide.hip: nothing of size S x S is materialised) -> to_out + residual
 Tn attn_run(Exec& ex, const dmx_vae* v, const AttnW& w, const Tn& x, int G) {
   const int C = w.C, S = x.H * x.W;
-  Tn n = ex.groupnorm(x, nullptr, v->W<float>(w.gg), v->W<float>(w.gb), G, 1e-6f, false);
-  const float* bqkv = v->W<float>(w.bq);
+  const Exec::Weights wt = ex.weights(v->arena);
+  Tn n = ex.groupnorm(x, nullptr, wt.at<float>(w.gg), wt.at<float>(w.gb), G, 1e-6f, false);
+  const float* bqkv = wt.at<float>(w.bq);
   float* btmp = nullptr;
   if (ex.f32) {                                        // the three bias vectors are not adjacent in the fp32 master arena
     btmp = (float*)ex.raw((size_t)3 * C * 4);
     if (!ex.dry && !ex.rc) {
       const size_t offs[3] = {w.bq, w.bk, w.bv};
       for (int i = 0; i < 3 && !ex.rc; ++i)
-        if (hipMemcpyAsync(btmp + (size_t)i * C, v->W<float>(offs[i]), (size_t)C * 4, hipMemcpyDeviceToDevice, ex.stream) != hipSuccess) {
+        if (hipMemcpyAsync(btmp + (size_t)i * C, wt.at<float>(offs[i]), (size_t)C * 4, hipMemcpyDeviceToDevice, ex.stream) != hipSuccess) {
           dmx_set_error("hipMemcpyAsync failed (attention biases)"); ex.rc = DMX_ERR_HIP;
         }
     }
     bqkv = btmp;
   }
-  Tn qkv = ex.linear(n, v->W<bf16>(w.wq), 3 * C, bqkv, nullptr, false);
+  Tn qkv = ex.linear(n, wt.at<bf16>(w.wq), 3 * C, bqkv, nullptr, false);
   ex.drop(n);
   if (btmp) ex.drop(btmp);
   Tn a = ex.make(x.B, x.H, x.W, C);
@@ -72,19 +73,20 @@ Tn attn_run(Exec& ex, const dmx_vae* v, const AttnW& w, const Tn& x, int G) {
     ex.rc = dmx_attention_wide_launch(aa, ex.stream);
   }
   ex.drop(qkv);
-  Tn y = ex.linear(a, v->W<bf16>(w.wo), C, v->W<float>(w.bo), &x, false, nullptr, nullptr, true);
+  Tn y = ex.linear(a, wt.at<bf16>(w.wo), C, wt.at<float>(w.bo), &x, false, nullptr, nullptr, true);
   ex.drop(a);
   return y;
 }
 
 int vae_encode_run(dmx_vae* v, Exec& ex, const float* x, float* moments, int B, int H, int W) {
   const dmx_vae_config& c = v->cfg; const int G = c.norm_num_groups; const int L = c.layers_per_block;
+  const Exec::Weights wt = ex.weights(v->arena);
   Tn h;
   if (ex.f32) {                                        // NCHW -> NHWC, then the generic conv on the K-padded filter matrix
     Tn xn = ex.make(B, H, W, c.in_channels);
     if (!ex.dry && !ex.rc) ex.rc = dmx_concat_nchw_to_nhwc_f32_launch(x, c.in_channels, nullptr, 0, nullptr, 0, (float*)xn.p, B, H * W, ex.stream);
-    ConvOpts oi; oi.bias = v->W<float>(v->e_in.b); oi.ldw = v->e_in.kpad;
-    h = ex.conv(xn, nullptr, v->W<bf16>(v->e_in.w), c.block_out_channels[0], oi);
+    ConvOpts oi; oi.bias = wt.at<float>(v->e_in.b); oi.ldw = v->e_in.kpad;
+    h = ex.conv(xn, nullptr, wt.at<bf16>(v->e_in.w), c.block_out_channels[0], oi);
     ex.drop(xn);
   } else {
     Tn col = ex.make(B, H, W, v->e_in.kpad);
@@ -93,34 +95,34 @@ int vae_encode_run(dmx_vae* v, Exec& ex, const float* x, float* moments, int B, 
       a.ksize = 3; a.stride = 1; a.pad = 1; a.out = col.p; a.Kpad = v->e_in.kpad;
       ex.rc = dmx_im2col_small_launch(a, ex.stream);
     }
-    h = ex.linear(col, v->W<bf16>(v->e_in.w), c.block_out_channels[0], v->W<float>(v->e_in.b), nullptr, false, nullptr, nullptr, true);
+    h = ex.linear(col, wt.at<bf16>(v->e_in.w), c.block_out_channels[0], wt.at<float>(v->e_in.b), nullptr, false, nullptr, nullptr, true);
     ex.drop(col);
   }
   ex.ensure_stats(h);                                  // (statistics records for the first resnet's fused GroupNorm -> conv launch)
   for (int i = 0; i < 4; ++i) {
     for (int j = 0; j < L; ++j) {
-      Tn y = resnet_run(ex, v->wbase(), v->e_res[i][j], h, nullptr, G, 1e-6f, nullptr, 0, v->wmul());
+      Tn y = resnet_run(ex, v->arena, v->e_res[i][j], h, nullptr, G, 1e-6f, nullptr, 0);
       ex.drop(h); h = y;
     }
     if (i < 3) {                       // F.pad(h,(0,1,0,1)) + conv s2 p0: the gather's range check is the pad
-      ConvOpts o; o.stride = 2; o.pad = 0; o.bias = v->W<float>(v->e_ds[i].b); o.stats = 1;
-      Tn y = ex.conv(h, nullptr, v->W<bf16>(v->e_ds[i].w), c.block_out_channels[i], o);
+      ConvOpts o; o.stride = 2; o.pad = 0; o.bias = wt.at<float>(v->e_ds[i].b); o.stats = 1;
+      Tn y = ex.conv(h, nullptr, wt.at<bf16>(v->e_ds[i].w), c.block_out_channels[i], o);
       ex.ensure_stats(y);
       ex.drop(h); h = y;
     }
   }
-  { Tn y = resnet_run(ex, v->wbase(), v->e_mid[0], h, nullptr, G, 1e-6f, nullptr, 0, v->wmul()); ex.drop(h);
+  { Tn y = resnet_run(ex, v->arena, v->e_mid[0], h, nullptr, G, 1e-6f, nullptr, 0); ex.drop(h);
     Tn z = attn_run(ex, v, v->e_attn, y, G); ex.drop(y);
     ex.ensure_stats(z);
-    h = resnet_run(ex, v->wbase(), v->e_mid[1], z, nullptr, G, 1e-6f, nullptr, 0, v->wmul()); ex.drop(z); }
-  Tn t = ex.groupnorm(h, nullptr, v->W<float>(v->e_ng), v->W<float>(v->e_nb), G, 1e-6f, true);
+    h = resnet_run(ex, v->arena, v->e_mid[1], z, nullptr, G, 1e-6f, nullptr, 0); ex.drop(z); }
+  Tn t = ex.groupnorm(h, nullptr, wt.at<float>(v->e_ng), wt.at<float>(v->e_nb), G, 1e-6f, true);
   ex.drop(h);
-  ConvOpts oo; oo.bias = v->W<float>(v->e_out.b);
-  Tn m8 = ex.conv(t, nullptr, v->W<bf16>(v->e_out.w), 2 * c.latent_channels, oo);   // [M][8] bf16
+  ConvOpts oo; oo.bias = wt.at<float>(v->e_out.b);
+  Tn m8 = ex.conv(t, nullptr, wt.at<bf16>(v->e_out.w), 2 * c.latent_channels, oo);   // [M][8] bf16
   ex.drop(t);
   if (ex.f32) {
-    ConvOpts oq; oq.ksize = 1; oq.pad = 0; oq.bias = v->W<float>(v->quant.b); oq.ldw = v->quant.kpad;
-    Tn mo = ex.conv(m8, nullptr, v->W<bf16>(v->quant.w), 2 * c.latent_channels, oq);
+    ConvOpts oq; oq.ksize = 1; oq.pad = 0; oq.bias = wt.at<float>(v->quant.b); oq.ldw = v->quant.kpad;
+    Tn mo = ex.conv(m8, nullptr, wt.at<bf16>(v->quant.w), 2 * c.latent_channels, oq);
     if (!ex.dry && !ex.rc) ex.rc = dmx_nhwc_to_nchw_f32_launch((const float*)mo.p, mo.ld, moments, B, mo.C, m8.H * m8.W, ex.stream);
     ex.drop(m8); ex.drop(mo);
     return ex.rc;
@@ -134,7 +136,7 @@ int vae_encode_run(dmx_vae* v, Exec& ex, const float* x, float* moments, int B, 
   }
   const int Mo = B * m8.H * m8.W, C2 = 2 * c.latent_channels;
   float* mo = (float*)ex.raw((size_t)Mo * C2 * 4);
-  ex.gemm_raw(qc.p, qc.ld, Mo, v->W<bf16>(v->quant.w), v->quant.kpad, C2, v->quant.kpad, v->W<float>(v->quant.b), mo, C2, 1);
+  ex.gemm_raw(qc.p, qc.ld, Mo, wt.at<bf16>(v->quant.w), v->quant.kpad, C2, v->quant.kpad, wt.at<float>(v->quant.b), mo, C2, 1);
   if (!ex.dry && !ex.rc) ex.rc = dmx_nhwc_to_nchw_f32_launch(mo, C2, moments, B, C2, m8.H * m8.W, ex.stream);
   ex.drop(qc); ex.drop(m8); ex.drop(mo);
   return ex.rc;
@@ -143,15 +145,16 @@ int vae_encode_run(dmx_vae* v, Exec& ex, const float* x, float* moments, int B, 
 int vae_decode_run(dmx_vae* v, Exec& ex, const float* z, float* image, int B, int h0, int w0) {
   const dmx_vae_config& c = v->cfg; const int G = c.norm_num_groups; const int L = c.layers_per_block;
   const int lc = c.latent_channels;
+  const Exec::Weights wt = ex.weights(v->arena);
   Tn h;
   if (ex.f32) {
     Tn zn = ex.make(B, h0, w0, lc);
     if (!ex.dry && !ex.rc) ex.rc = dmx_concat_nchw_to_nhwc_f32_launch(z, lc, nullptr, 0, nullptr, 0, (float*)zn.p, B, h0 * w0, ex.stream);
-    ConvOpts op; op.ksize = 1; op.pad = 0; op.bias = v->W<float>(v->pquant.b); op.ldw = v->pquant.kpad;
-    Tn z2 = ex.conv(zn, nullptr, v->W<bf16>(v->pquant.w), lc, op);
+    ConvOpts op; op.ksize = 1; op.pad = 0; op.bias = wt.at<float>(v->pquant.b); op.ldw = v->pquant.kpad;
+    Tn z2 = ex.conv(zn, nullptr, wt.at<bf16>(v->pquant.w), lc, op);
     ex.drop(zn);
-    ConvOpts oi; oi.bias = v->W<float>(v->d_in.b); oi.ldw = v->d_in.kpad;
-    h = ex.conv(z2, nullptr, v->W<bf16>(v->d_in.w), c.block_out_channels[3], oi);
+    ConvOpts oi; oi.bias = wt.at<float>(v->d_in.b); oi.ldw = v->d_in.kpad;
+    h = ex.conv(z2, nullptr, wt.at<bf16>(v->d_in.w), c.block_out_channels[3], oi);
     ex.drop(z2);
   } else {
   // post_quant_conv 1x1 on the NCHW fp32 latents
@@ -162,7 +165,7 @@ int vae_decode_run(dmx_vae* v, Exec& ex, const float* z, float* image, int B, in
     ex.rc = dmx_im2col_small_launch(a, ex.stream);
   }
   Tn z2 = ex.make(B, h0, w0, lc);
-  ex.gemm_raw(pc.p, pc.ld, B * h0 * w0, v->W<bf16>(v->pquant.w), v->pquant.kpad, lc, v->pquant.kpad, v->W<float>(v->pquant.b), z2.p, lc, 0);
+  ex.gemm_raw(pc.p, pc.ld, B * h0 * w0, wt.at<bf16>(v->pquant.w), v->pquant.kpad, lc, v->pquant.kpad, wt.at<float>(v->pquant.b), z2.p, lc, 0);
   ex.drop(pc);
   Tn col = ex.make(B, h0, w0, v->d_in.kpad);
   if (!ex.dry && !ex.rc) {
@@ -171,34 +174,34 @@ int vae_decode_run(dmx_vae* v, Exec& ex, const float* z, float* image, int B, in
     ex.rc = dmx_im2col_small_launch(a, ex.stream);
   }
   ex.drop(z2);
-  h = ex.linear(col, v->W<bf16>(v->d_in.w), c.block_out_channels[3], v->W<float>(v->d_in.b), nullptr, false, nullptr, nullptr, true);
+  h = ex.linear(col, wt.at<bf16>(v->d_in.w), c.block_out_channels[3], wt.at<float>(v->d_in.b), nullptr, false, nullptr, nullptr, true);
   ex.drop(col);
   }
   ex.ensure_stats(h);
-  { Tn y = resnet_run(ex, v->wbase(), v->d_mid[0], h, nullptr, G, 1e-6f, nullptr, 0, v->wmul()); ex.drop(h);
+  { Tn y = resnet_run(ex, v->arena, v->d_mid[0], h, nullptr, G, 1e-6f, nullptr, 0); ex.drop(h);
     Tn zz = attn_run(ex, v, v->d_attn, y, G); ex.drop(y);
     ex.ensure_stats(zz);
-    h = resnet_run(ex, v->wbase(), v->d_mid[1], zz, nullptr, G, 1e-6f, nullptr, 0, v->wmul()); ex.drop(zz); }
+    h = resnet_run(ex, v->arena, v->d_mid[1], zz, nullptr, G, 1e-6f, nullptr, 0); ex.drop(zz); }
   for (int i = 0; i < 4; ++i) {
     for (int j = 0; j < L + 1; ++j) {
-      Tn y = resnet_run(ex, v->wbase(), v->d_res[i][j], h, nullptr, G, 1e-6f, nullptr, 0, v->wmul());
+      Tn y = resnet_run(ex, v->arena, v->d_res[i][j], h, nullptr, G, 1e-6f, nullptr, 0);
       ex.drop(h); h = y;
     }
     if (i < 3) {
       // nearest x2 + conv3x3 as four 2x2 phase convolutions on the source grid (GemmArgs.ups2)
       const bool direct = ex.f32;                                          // (the phase weights are derived data of the bf16 path)
-      ConvOpts o; o.ups = 1; o.ups2 = direct ? 0 : 1; o.bias = v->W<float>(v->d_us[i].b); o.stats = 1;
-      Tn y = ex.conv(h, nullptr, v->W<bf16>(direct ? v->d_us[i].w : v->d_us[i].wp), c.block_out_channels[3 - i], o);
+      ConvOpts o; o.ups = 1; o.ups2 = direct ? 0 : 1; o.bias = wt.at<float>(v->d_us[i].b); o.stats = 1;
+      Tn y = ex.conv(h, nullptr, wt.at<bf16>(direct ? v->d_us[i].w : v->d_us[i].wp), c.block_out_channels[3 - i], o);
       ex.ensure_stats(y);
       ex.drop(h); h = y;
     }
   }
-  Tn t = ex.groupnorm(h, nullptr, v->W<float>(v->d_ng), v->W<float>(v->d_nb), G, 1e-6f, true);
+  Tn t = ex.groupnorm(h, nullptr, wt.at<float>(v->d_ng), wt.at<float>(v->d_nb), G, 1e-6f, true);
   ex.drop(h);
   const int Mo = B * t.H * t.W;
   float* im = (float*)ex.raw((size_t)Mo * c.out_channels * 4);
-  ConvOpts oo; oo.bias = v->W<float>(v->d_out.b); oo.out_f32 = 1;
-  ex.conv(t, nullptr, v->W<bf16>(v->d_out.w), c.out_channels, oo, im);
+  ConvOpts oo; oo.bias = wt.at<float>(v->d_out.b); oo.out_f32 = 1;
+  ex.conv(t, nullptr, wt.at<bf16>(v->d_out.w), c.out_channels, oo, im);
   if (!ex.dry && !ex.rc) ex.rc = dmx_nhwc_to_nchw_f32_launch(im, c.out_channels, image, B, c.out_channels, t.H * t.W, ex.stream);
   ex.drop(t); ex.drop(im);
   return ex.rc;
@@ -257,45 +260,17 @@ extern "C" dmx_vae* dmx_vae_create(const dmx_vae_config* cfg) {
   return v.release();
 }
 
-extern "C" void dmx_vae_destroy(dmx_vae* v) { delete v; }
-extern "C" int dmx_vae_param_count(const dmx_vae* v) { return v ? (int)v->pt.entries().size() : 0; }
-extern "C" int dmx_vae_param_info(const dmx_vae* v, int index, const char** name, int shape[4]) {
-  DMX_REQUIRE(v && index >= 0 && index < (int)v->pt.entries().size(), "vae_param_info: bad index %d", index);
-  const ParamEntry& e = v->pt.entries()[index];
-  if (name) *name = e.name.c_str();
-  if (shape) for (int k = 0; k < 4; ++k) shape[k] = e.shape[k];
-  return DMX_OK;
-}
-extern "C" size_t dmx_vae_arena_bytes(const dmx_vae* v) { return v ? v->pt.total() : 0; }
-extern "C" int dmx_vae_bind_arena(dmx_vae* v, void* arena, size_t bytes) {
-  DMX_REQUIRE(v && arena && bytes >= v->pt.total(), "vae_bind_arena: need %zu bytes", v ? v->pt.total() : (size_t)0);
-  v->arena = (char*)arena; v->finalized = false;
-  DMX_HIP(hipMemset(arena, 0, v->pt.total()));
-  return DMX_OK;
-}
-extern "C" int dmx_vae_load_param(dmx_vae* v, const char* name, const float* src, dmx_stream_t stream) {
-  DMX_REQUIRE(v != nullptr, "vae_load_param: null handle");
-  v->finalized = false;
-  return v->pt.load(v->arena, name, src, (hipStream_t)stream);
-}
-extern "C" int dmx_vae_finalize(dmx_vae* v, dmx_stream_t stream) {
-  DMX_REQUIRE(v && v->arena, "vae_finalize: arena not bound");
-  hipStream_t s = (hipStream_t)stream;
-  int rc = 0;
-  for (int i = 0; i < 4 && !rc; ++i) {
-    for (auto& r : v->e_res[i]) if (!rc) rc = resnet_finalize(r, v->arena, s);
-    for (auto& r : v->d_res[i]) if (!rc) rc = resnet_finalize(r, v->arena, s);
-  }
-  for (int k = 0; k < 2 && !rc; ++k) { rc = resnet_finalize(v->e_mid[k], v->arena, s); if (!rc) rc = resnet_finalize(v->d_mid[k], v->arena, s); }
+DMX_MODEL_ABI(dmx_vae, vae)
+int dmx_vae::derive(hipStream_t s) {
+  int rc = for_each_resnet(this, [&](const ResW& r) { return resnet_finalize(r, arena, s); });
   for (int i = 0; i < 3 && !rc; ++i)
-    rc = dmx_ups_phase_weights_launch(v->at<bf16>(v->d_us[i].w), v->d_us[i].kpad, v->at<bf16>(v->d_us[i].wp), v->d_us[i].cout, v->d_us[i].cin, s);
-  DMX_HIP(hipStreamSynchronize(s));
-  v->finalized = (rc == 0);
+    rc = dmx_ups_phase_weights_launch(at<bf16>(d_us[i].w), d_us[i].kpad, at<bf16>(d_us[i].wp), d_us[i].cout, d_us[i].cin, s);
   return rc;
 }
+extern "C" int dmx_vae_finalize(dmx_vae* v, dmx_stream_t stream) { return model_finalize(v, "vae", (hipStream_t)stream); }
 extern "C" size_t dmx_vae_workspace_bytes(dmx_vae* v, int B, int H, int W, int decode) {
   if (!v) return 0;
-  Exec ex; ex.dry = true; ex.ws.reset(nullptr, 0, true);
+  Exec ex = Exec::dry_run();
   if (decode) vae_decode_run(v, ex, nullptr, nullptr, B, H, W); else vae_encode_run(v, ex, nullptr, nullptr, B, H, W);
   return ex.ws.peak() + 4096;
 }
@@ -304,44 +279,36 @@ extern "C" int dmx_vae_encode(dmx_vae* v, const float* x, float* moments, int B,
   DMX_REQUIRE(v && v->finalized, "vae_encode: weights not finalized");
   DMX_REQUIRE(x && moments && workspace, "vae_encode: null argument");
   DMX_REQUIRE(B > 0 && H % 8 == 0 && W % 8 == 0 && H > 0 && W > 0, "vae_encode: H=%d W=%d must be positive multiples of 8", H, W);
-  Exec ex; ex.stream = (hipStream_t)stream; ex.ws.reset(workspace, workspace_bytes, false);
+  Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes);
   return vae_encode_run(v, ex, x, moments, B, H, W);
 }
 // ---- fp32 VALIDATION instantiation (tests only): the same walkers on fp32 activations, the caller's fp32 master copy of the
 // parameters and the plain fp32 kernels of ref_f32.hip
 extern "C" size_t dmx_vae_workspace_bytes_f32(dmx_vae* v, int B, int H, int W, int decode) {
   if (!v) return 0;
-  Exec ex; ex.dry = true; ex.f32 = true; ex.ws.reset(nullptr, 0, true);
-  v->masters_f32 = (const char*)4096;                  // dry run: pointers are never dereferenced
+  Exec ex = Exec::dry_run(true);
   if (decode) vae_decode_run(v, ex, nullptr, nullptr, B, H, W); else vae_encode_run(v, ex, nullptr, nullptr, B, H, W);
-  v->masters_f32 = nullptr;
   return ex.ws.peak() + 4096;
 }
 extern "C" int dmx_vae_encode_f32(dmx_vae* v, const void* masters, const float* x, float* moments, int B, int H, int W,
                                   void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(v && masters && x && moments && workspace, "vae_encode_f32: null argument");
   DMX_REQUIRE(B > 0 && H % 8 == 0 && W % 8 == 0 && H > 0 && W > 0, "vae_encode_f32: H=%d W=%d must be positive multiples of 8", H, W);
-  Exec ex; ex.stream = (hipStream_t)stream; ex.f32 = true; ex.ws.reset(workspace, workspace_bytes, false);
-  v->masters_f32 = (const char*)masters;
-  const int rc = vae_encode_run(v, ex, x, moments, B, H, W);
-  v->masters_f32 = nullptr;
-  return rc;
+  Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes, true); ex.masters = (const char*)masters;
+  return vae_encode_run(v, ex, x, moments, B, H, W);
 }
 extern "C" int dmx_vae_decode_f32(dmx_vae* v, const void* masters, const float* z, float* image, int B, int h, int w,
                                   void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(v && masters && z && image && workspace, "vae_decode_f32: null argument");
   DMX_REQUIRE(B > 0 && h > 0 && w > 0, "vae_decode_f32: empty problem");
-  Exec ex; ex.stream = (hipStream_t)stream; ex.f32 = true; ex.ws.reset(workspace, workspace_bytes, false);
-  v->masters_f32 = (const char*)masters;
-  const int rc = vae_decode_run(v, ex, z, image, B, h, w);
-  v->masters_f32 = nullptr;
-  return rc;
+  Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes, true); ex.masters = (const char*)masters;
+  return vae_decode_run(v, ex, z, image, B, h, w);
 }
 extern "C" int dmx_vae_decode(dmx_vae* v, const float* z, float* image, int B, int h, int w,
                               void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(v && v->finalized, "vae_decode: weights not finalized");
   DMX_REQUIRE(z && image && workspace, "vae_decode: null argument");
   DMX_REQUIRE(B > 0 && h > 0 && w > 0, "vae_decode: empty problem");
-  Exec ex; ex.stream = (hipStream_t)stream; ex.ws.reset(workspace, workspace_bytes, false);
+  Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes);
   return vae_decode_run(v, ex, z, image, B, h, w);
 }

@@ -283,29 +283,11 @@ struct VaeTrain {
   }
 };
 
-int t_linear(const dmx_vae* v, char* wt, size_t off, int N, int K, hipStream_t s) {
-  return dmx_transpose_bf16_launch((const bf16*)(v->arena + off), K, (bf16*)(wt + off), N, N, K, s);
-}
-int t_conv(const dmx_vae* v, char* wt, size_t off, int N, int Cin, int ld, int ldt, hipStream_t s) {
-  for (int tap = 0; tap < 9; ++tap) {
-    const int rc = dmx_transpose_bf16_launch((const bf16*)(v->arena + off) + (size_t)tap * Cin, ld, (bf16*)(wt + off) + (size_t)(8 - tap) * N, ldt, N, Cin, s);
-    if (rc) return rc;
-  }
-  return DMX_OK;
-}
-int t_resnet(const dmx_vae* v, char* wt, const ResW& r, hipStream_t s) {
-  int rc = t_conv(v, wt, r.w1, r.cout, r.cin, 9 * r.cin, 9 * r.cout, s);
-  const int k2 = 9 * r.cout + (r.shortcut ? r.cin : 0);
-  if (!rc) rc = t_conv(v, wt, r.w2, r.cout, r.cout, k2, 9 * r.cout, s);
-  if (!rc && r.shortcut)
-    rc = dmx_transpose_bf16_launch((const bf16*)(v->arena + r.w2) + 9 * r.cout, k2, (bf16*)(wt + r.w2) + (size_t)9 * r.cout * r.cout, r.cout, r.cout, r.cin, s);
-  return rc;
-}
 int t_attn(const dmx_vae* v, char* wt, const AttnW& a, hipStream_t s) {
-  int rc = t_linear(v, wt, a.wq, a.C, a.C, s);
-  if (!rc) rc = t_linear(v, wt, a.wk, a.C, a.C, s);
-  if (!rc) rc = t_linear(v, wt, a.wv, a.C, a.C, s);
-  if (!rc) rc = t_linear(v, wt, a.wo, a.C, a.C, s);
+  int rc = transpose_linear(v, wt, a.wq, a.C, a.C, s);
+  if (!rc) rc = transpose_linear(v, wt, a.wk, a.C, a.C, s);
+  if (!rc) rc = transpose_linear(v, wt, a.wv, a.C, a.C, s);
+  if (!rc) rc = transpose_linear(v, wt, a.wo, a.C, a.C, s);
   return rc;
 }
 }  // namespace
@@ -317,16 +299,16 @@ extern "C" int dmx_vae_train_prepare(dmx_vae* v, void* wt_arena, size_t wt_bytes
   DMX_REQUIRE(v && v->finalized, "vae_train_prepare: weights not finalized");
   DMX_REQUIRE(wt_arena && wt_bytes >= wt_total(v), "vae_train_prepare: need %zu bytes", wt_total(v));
   hipStream_t s = (hipStream_t)stream; char* wt = (char*)wt_arena;
-  const int* boc = v->cfg.block_out_channels; const int lc = v->cfg.latent_channels, OC = v->cfg.out_channels;
+  const int lc = v->cfg.latent_channels, OC = v->cfg.out_channels;
   DMX_REQUIRE(9 * 2 * lc <= 128 && 9 * OC <= 64, "vae_train_prepare: latent/out channel counts too large for the padded conv_out data gradients");
   int rc = 0;
   for (int i = 0; i < 4 && !rc; ++i) {
-    for (auto& r : v->e_res[i]) if (!rc) rc = t_resnet(v, wt, r, s);
-    for (auto& r : v->d_res[i]) if (!rc) rc = t_resnet(v, wt, r, s);
-    if (i < 3 && !rc) rc = t_conv(v, wt, v->e_ds[i].w, v->e_ds[i].cout, v->e_ds[i].cin, 9 * v->e_ds[i].cin, 9 * v->e_ds[i].cout, s);
-    if (i < 3 && !rc) rc = t_conv(v, wt, v->d_us[i].w, v->d_us[i].cout, v->d_us[i].cin, 9 * v->d_us[i].cin, 9 * v->d_us[i].cout, s);
+    for (auto& r : v->e_res[i]) if (!rc) rc = transpose_resnet(v, wt, r, s);
+    for (auto& r : v->d_res[i]) if (!rc) rc = transpose_resnet(v, wt, r, s);
+    if (i < 3 && !rc) rc = transpose_conv(v, wt, v->e_ds[i].w, v->e_ds[i].cout, v->e_ds[i].cin, 9 * v->e_ds[i].cin, 9 * v->e_ds[i].cout, s);
+    if (i < 3 && !rc) rc = transpose_conv(v, wt, v->d_us[i].w, v->d_us[i].cout, v->d_us[i].cin, 9 * v->d_us[i].cin, 9 * v->d_us[i].cout, s);
   }
-  for (int k = 0; k < 2 && !rc; ++k) { rc = t_resnet(v, wt, v->e_mid[k], s); if (!rc) rc = t_resnet(v, wt, v->d_mid[k], s); }
+  for (int k = 0; k < 2 && !rc; ++k) { rc = transpose_resnet(v, wt, v->e_mid[k], s); if (!rc) rc = transpose_resnet(v, wt, v->d_mid[k], s); }
   if (!rc) rc = t_attn(v, wt, v->e_attn, s);
   if (!rc) rc = t_attn(v, wt, v->d_attn, s);
   // decoder conv_in [C][kpad: tap*lc + c] -> [lc][flip(tap)*C + n] (plain conv data gradient with N = lc)
@@ -347,14 +329,13 @@ extern "C" int dmx_vae_train_prepare(dmx_vae* v, void* wt_arena, size_t wt_bytes
     for (int tap = 0; tap < 9 && !rc; ++tap)
       rc = dmx_transpose_bf16_launch((const bf16*)(v->arena + v->d_out.w) + (size_t)tap * C, 9 * C, (bf16*)(wt + wt_extra_dout(v)) + (size_t)(8 - tap) * OC, 64, OC, C, s);
   }
-  (void)boc;
   return rc;
 }
 
 extern "C" size_t dmx_vae_train_workspace_bytes(dmx_vae* v, int B, int H, int W) {
   if (!v) return 0;
   VaeTrain ts(v, nullptr, B);
-  ts.ex.dry = true; ts.ex.ws.reset(nullptr, 0, true);
+  ts.ex = Exec::dry_run();
   ts.forward(nullptr, nullptr, B, H, W);
   ts.backward(nullptr, nullptr);
   return ts.ex.ws.peak() + 4096;
@@ -367,7 +348,7 @@ extern "C" int dmx_vae_train_forward(dmx_vae* v, const void* wt_arena, const flo
   DMX_REQUIRE(wt_arena && x && recon && workspace, "vae_train_forward: null argument");
   DMX_REQUIRE(B > 0 && H > 0 && W > 0 && H % 64 == 0 && W % 64 == 0, "vae_train_forward: H=%d W=%d must be positive multiples of 64", H, W);
   auto ts = std::make_shared<VaeTrain>(v, (char*)wt_arena, B);
-  ts->ex.stream = (hipStream_t)stream; ts->ex.ws.reset(workspace, workspace_bytes, false);
+  ts->ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes);
   v->train_state = ts;
   const int rc = ts->forward(x, recon, B, H, W);
   if (rc) v->train_state.reset();

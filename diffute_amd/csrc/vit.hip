@@ -48,17 +48,11 @@ __global__ __launch_bounds__(256) void dmx_bf16_to_f32_kernel(const bf16* in, fl
 }
 }  // namespace
 
-struct dmx_vit {
+struct dmx_vit : ModelBase {
   dmx_vit_config cfg;
-  ParamTable pt;
-  char* arena = nullptr;
-  bool finalized = false;
   size_t cls, pos, pw, pb, lng, lnb; int kpad = 0, np = 0;
   std::vector<VitLayer> layers;
-  template <typename T> T* at(size_t off) const { return (T*)(arena + off); }
-  // fp32 VALIDATION mode (dmx_vit_forward_f32, tests only): parameters from the caller's fp32 master arena (byte offsets double)
-  const char* masters_f32 = nullptr;
-  template <typename T> const T* W(size_t off) const { return masters_f32 ? (const T*)(masters_f32 + 2 * off) : (const T*)(arena + off); }
+  int derive(hipStream_t) override { const bf16* zp = nullptr; return dmx_zero_page(&zp); }   // the padding page: never allocated inside a stream capture
 };
 
 extern "C" dmx_vit* dmx_vit_create(const dmx_vit_config* cfg) {
@@ -103,47 +97,21 @@ extern "C" dmx_vit* dmx_vit_create(const dmx_vit_config* cfg) {
   v->lng = pt.f32("layernorm.weight", D); v->lnb = pt.f32("layernorm.bias", D);
   return v.release();
 }
-extern "C" void dmx_vit_destroy(dmx_vit* v) { delete v; }
-extern "C" int dmx_vit_param_count(const dmx_vit* v) { return v ? (int)v->pt.entries().size() : 0; }
-extern "C" int dmx_vit_param_info(const dmx_vit* v, int index, const char** name, int shape[4]) {
-  DMX_REQUIRE(v && index >= 0 && index < (int)v->pt.entries().size(), "vit_param_info: bad index %d", index);
-  const ParamEntry& e = v->pt.entries()[index];
-  if (name) *name = e.name.c_str();
-  if (shape) for (int k = 0; k < 4; ++k) shape[k] = e.shape[k];
-  return DMX_OK;
-}
-extern "C" size_t dmx_vit_arena_bytes(const dmx_vit* v) { return v ? v->pt.total() : 0; }
-extern "C" int dmx_vit_bind_arena(dmx_vit* v, void* arena, size_t bytes) {
-  DMX_REQUIRE(v && arena && bytes >= v->pt.total(), "vit_bind_arena: need %zu bytes", v ? v->pt.total() : (size_t)0);
-  v->arena = (char*)arena; v->finalized = false;
-  DMX_HIP(hipMemset(arena, 0, v->pt.total()));      // K padding of the patch filter, absent q/k/v biases
-  return DMX_OK;
-}
-extern "C" int dmx_vit_load_param(dmx_vit* v, const char* name, const float* src, dmx_stream_t stream) {
-  DMX_REQUIRE(v != nullptr, "vit_load_param: null handle");
-  v->finalized = false;
-  return v->pt.load(v->arena, name, src, (hipStream_t)stream);
-}
-extern "C" int dmx_vit_finalize(dmx_vit* v, dmx_stream_t stream) {
-  DMX_REQUIRE(v && v->arena, "vit_finalize: arena not bound");
-  DMX_HIP(hipStreamSynchronize((hipStream_t)stream));
-  const bf16* zp = nullptr;
-  int rc = dmx_zero_page(&zp);
-  v->finalized = (rc == 0);
-  return rc;
-}
+DMX_MODEL_ABI(dmx_vit, vit)
+extern "C" int dmx_vit_finalize(dmx_vit* v, dmx_stream_t stream) { return model_finalize(v, "vit", (hipStream_t)stream); }
 
 namespace {
 int vit_run(dmx_vit* v, Exec& ex, const float* pixels, float* out, int B) {
   const dmx_vit_config& c = v->cfg;
   const int D = c.hidden_size, H = c.num_heads, S = v->np + 1, g = c.image_size / c.patch_size;
+  const Exec::Weights wt = ex.weights(v->arena);
   // ---- patch embedding
   Tn emb;
   if (ex.f32) {                                        // NCHW -> NHWC, then the generic strided conv on the K-padded filter matrix
     Tn xn = ex.make(B, c.image_size, c.image_size, c.num_channels);
     if (!ex.dry && !ex.rc) ex.rc = dmx_concat_nchw_to_nhwc_f32_launch(pixels, c.num_channels, nullptr, 0, nullptr, 0, (float*)xn.p, B, c.image_size * c.image_size, ex.stream);
-    ConvOpts op; op.ksize = c.patch_size; op.stride = c.patch_size; op.pad = 0; op.bias = v->W<float>(v->pb); op.ldw = v->kpad;
-    emb = ex.conv(xn, nullptr, v->W<bf16>(v->pw), D, op);
+    ConvOpts op; op.ksize = c.patch_size; op.stride = c.patch_size; op.pad = 0; op.bias = wt.at<float>(v->pb); op.ldw = v->kpad;
+    emb = ex.conv(xn, nullptr, wt.at<bf16>(v->pw), D, op);
     ex.drop(xn);
   } else {
     Tn col = ex.make(B, g, g, v->kpad);
@@ -152,50 +120,50 @@ int vit_run(dmx_vit* v, Exec& ex, const float* pixels, float* out, int B) {
       a.B = B; a.IH = a.IW = c.image_size; a.OH = a.OW = g; a.ksize = c.patch_size; a.stride = c.patch_size; a.pad = 0; a.out = col.p; a.Kpad = v->kpad;
       ex.rc = dmx_im2col_small_launch(a, ex.stream);
     }
-    emb = ex.linear(col, v->W<bf16>(v->pw), D, v->W<float>(v->pb), nullptr, false);
+    emb = ex.linear(col, wt.at<bf16>(v->pw), D, wt.at<float>(v->pb), nullptr, false);
     ex.drop(col);
   }
   Tn x = ex.make(1, 1, B * S, D);
   if (ex.f32) {
     if (!ex.dry && !ex.rc) {
-      hipLaunchKernelGGL(dmx_vit_assemble_f32_kernel, dim3(4096), dim3(256), 0, ex.stream, (const float*)emb.p, v->W<float>(v->cls), v->W<float>(v->pos), (float*)x.p, B, v->np, D);
+      hipLaunchKernelGGL(dmx_vit_assemble_f32_kernel, dim3(4096), dim3(256), 0, ex.stream, (const float*)emb.p, wt.at<float>(v->cls), wt.at<float>(v->pos), (float*)x.p, B, v->np, D);
       ex.rc = dmx_check_launch("dmx_vit_assemble_f32_kernel");
     }
   } else if (!ex.dry && !ex.rc) {
     const size_t total = (size_t)B * S * (D / 8);
     int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(dmx_vit_assemble_kernel, dim3(blocks), dim3(256), 0, ex.stream, emb.p, v->W<float>(v->cls), v->W<float>(v->pos), x.p, B, v->np, D);
+    hipLaunchKernelGGL(dmx_vit_assemble_kernel, dim3(blocks), dim3(256), 0, ex.stream, emb.p, wt.at<float>(v->cls), wt.at<float>(v->pos), x.p, B, v->np, D);
     ex.rc = dmx_check_launch("dmx_vit_assemble_kernel");
   }
   ex.drop(emb);
   for (const VitLayer& L : v->layers) {
-    Tn n1 = ex.layernorm(x, v->W<float>(L.l1g), v->W<float>(L.l1b), c.layer_norm_eps);
-    const float* bqkv = v->W<float>(L.bqkv);
+    Tn n1 = ex.layernorm(x, wt.at<float>(L.l1g), wt.at<float>(L.l1b), c.layer_norm_eps);
+    const float* bqkv = wt.at<float>(L.bqkv);
     float* btmp = nullptr;
     if (ex.f32) {                                      // the q / k / v bias vectors are not adjacent in the fp32 master arena
       btmp = (float*)ex.raw((size_t)3 * D * 4);
       if (!ex.dry && !ex.rc)
         for (int i = 0; i < 3 && !ex.rc; ++i)
-          if (hipMemcpyAsync(btmp + (size_t)i * D, v->W<float>(L.bqkv + (size_t)i * D * 4), (size_t)D * 4, hipMemcpyDeviceToDevice, ex.stream) != hipSuccess) {
+          if (hipMemcpyAsync(btmp + (size_t)i * D, wt.at<float>(L.bqkv + (size_t)i * D * 4), (size_t)D * 4, hipMemcpyDeviceToDevice, ex.stream) != hipSuccess) {
             dmx_set_error("hipMemcpyAsync failed (ViT q/k/v biases)"); ex.rc = DMX_ERR_HIP;
           }
       bqkv = btmp;
     }
-    Tn qkv = ex.linear(n1, v->W<bf16>(L.wqkv), 3 * D, bqkv, nullptr, false);
+    Tn qkv = ex.linear(n1, wt.at<bf16>(L.wqkv), 3 * D, bqkv, nullptr, false);
     ex.drop(n1);
     if (btmp) ex.drop(btmp);
     Tn a = ex.make(1, 1, B * S, D);
     ex.attention(qkv.p, 3 * D, ex.col(qkv, D), 3 * D, ex.col(qkv, 2 * D), 3 * D, S, a.p, D, B, H, S, S, 0.125f);
     ex.drop(qkv);
-    Tn x2 = ex.linear(a, v->W<bf16>(L.wo), D, v->W<float>(L.bo), &x, false);
+    Tn x2 = ex.linear(a, wt.at<bf16>(L.wo), D, wt.at<float>(L.bo), &x, false);
     ex.drop(a); ex.drop(x);
-    Tn n2 = ex.layernorm(x2, v->W<float>(L.l2g), v->W<float>(L.l2b), c.layer_norm_eps);
-    Tn h = ex.linear_gelu(n2, v->W<bf16>(L.w1), c.intermediate_size, v->W<float>(L.b1));
+    Tn n2 = ex.layernorm(x2, wt.at<float>(L.l2g), wt.at<float>(L.l2b), c.layer_norm_eps);
+    Tn h = ex.linear_gelu(n2, wt.at<bf16>(L.w1), c.intermediate_size, wt.at<float>(L.b1));
     ex.drop(n2);
-    x = ex.linear(h, v->W<bf16>(L.w2), D, v->W<float>(L.b2), &x2, false);
+    x = ex.linear(h, wt.at<bf16>(L.w2), D, wt.at<float>(L.b2), &x2, false);
     ex.drop(h); ex.drop(x2);
   }
-  Tn y = ex.layernorm(x, v->W<float>(v->lng), v->W<float>(v->lnb), c.layer_norm_eps);
+  Tn y = ex.layernorm(x, wt.at<float>(v->lng), wt.at<float>(v->lnb), c.layer_norm_eps);
   ex.drop(x);
   if (ex.f32) {
     if (!ex.dry && !ex.rc && hipMemcpyAsync(out, y.p, (size_t)B * S * D * 4, hipMemcpyDeviceToDevice, ex.stream) != hipSuccess) {
@@ -214,7 +182,7 @@ int vit_run(dmx_vit* v, Exec& ex, const float* pixels, float* out, int B) {
 
 extern "C" size_t dmx_vit_workspace_bytes(dmx_vit* v, int B) {
   if (!v) return 0;
-  Exec ex; ex.dry = true; ex.ws.reset(nullptr, 0, true);
+  Exec ex = Exec::dry_run();
   vit_run(v, ex, nullptr, nullptr, B);
   return ex.ws.peak() + 4096;
 }
@@ -222,25 +190,19 @@ extern "C" size_t dmx_vit_workspace_bytes(dmx_vit* v, int B) {
 // parameters (dmx_vit_master_bytes, filled by dmx_vit_master_import) and the plain fp32 kernels of ref_f32.hip
 extern "C" size_t dmx_vit_master_bytes(const dmx_vit* v) { return v ? 2 * v->pt.total() : 0; }
 extern "C" int dmx_vit_master_import(const dmx_vit* v, void* masters, const char* name, const float* src, dmx_stream_t stream) {
-  DMX_REQUIRE(v && masters && name && src, "vit_master_import: null argument");
-  return dmx_master_import(v->pt, masters, name, src, (hipStream_t)stream, "vit_master_import");
+  return model_master_import(v, "vit", masters, name, src, (hipStream_t)stream);
 }
 extern "C" size_t dmx_vit_workspace_bytes_f32(dmx_vit* v, int B) {
   if (!v) return 0;
-  Exec ex; ex.dry = true; ex.f32 = true; ex.ws.reset(nullptr, 0, true);
-  v->masters_f32 = (const char*)4096;
+  Exec ex = Exec::dry_run(true);
   vit_run(v, ex, nullptr, nullptr, B);
-  v->masters_f32 = nullptr;
   return ex.ws.peak() + 4096;
 }
 extern "C" int dmx_vit_forward_f32(dmx_vit* v, const void* masters, const float* pixel_values, float* last_hidden_state, int B,
                                    void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(v && masters && pixel_values && last_hidden_state && workspace && B > 0, "vit_forward_f32: null argument");
-  Exec ex; ex.stream = (hipStream_t)stream; ex.f32 = true; ex.ws.reset(workspace, workspace_bytes, false);
-  v->masters_f32 = (const char*)masters;
-  const int rc = vit_run(v, ex, pixel_values, last_hidden_state, B);
-  v->masters_f32 = nullptr;
-  return rc;
+  Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes, true); ex.masters = (const char*)masters;
+  return vit_run(v, ex, pixel_values, last_hidden_state, B);
 }
 // last_hidden_state [B][num_patches + 1][hidden] fp32 from pixel_values [B][C][image][image] fp32 (NCHW, already
 // resized / normalised by the processor)
@@ -248,6 +210,6 @@ extern "C" int dmx_vit_forward(dmx_vit* v, const float* pixel_values, float* las
                                void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(v && v->finalized, "vit_forward: weights not finalized (bind_arena, load_param*, finalize)");
   DMX_REQUIRE(pixel_values && last_hidden_state && workspace && B > 0, "vit_forward: null argument");
-  Exec ex; ex.stream = (hipStream_t)stream; ex.ws.reset(workspace, workspace_bytes, false);
+  Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes);
   return vit_run(v, ex, pixel_values, last_hidden_state, B);
 }
