@@ -175,28 +175,12 @@ _PROTOS = {
     "dmx_sched_add_noise": (c_int, [_P, _P, _P, _P, _P, c_int, c_size_t, _P]),
     "dmx_sched_get_velocity": (c_int, [_P, _P, _P, _P, _P, c_int, c_size_t, _P]),
     "dmx_gaussian_sample": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, _P]),
-    "dmx_vit_create": (_P, [POINTER(ViTConfig)]),
-    "dmx_vit_destroy": (None, [_P]),
-    "dmx_vit_param_count": (c_int, [_P]),
-    "dmx_vit_param_info": (c_int, [_P, c_int, POINTER(c_char_p), POINTER(c_int * 4)]),
-    "dmx_vit_arena_bytes": (c_size_t, [_P]),
-    "dmx_vit_bind_arena": (c_int, [_P, _P, c_size_t]),
-    "dmx_vit_load_param": (c_int, [_P, c_char_p, _P, _P]),
-    "dmx_vit_finalize": (c_int, [_P, _P]),
     "dmx_vit_workspace_bytes": (c_size_t, [_P, c_int]),
     "dmx_vit_forward": (c_int, [_P, _P, _P, c_int, _P, c_size_t, _P]),
     "dmx_vit_master_bytes": (c_size_t, [_P]),
     "dmx_vit_master_import": (c_int, [_P, _P, c_char_p, _P, _P]),
     "dmx_vit_workspace_bytes_f32": (c_size_t, [_P, c_int]),
     "dmx_vit_forward_f32": (c_int, [_P, _P, _P, _P, c_int, _P, c_size_t, _P]),
-    "dmx_trocr_dec_create": (_P, [POINTER(TrOCRDecConfig)]),
-    "dmx_trocr_dec_destroy": (None, [_P]),
-    "dmx_trocr_dec_param_count": (c_int, [_P]),
-    "dmx_trocr_dec_param_info": (c_int, [_P, c_int, POINTER(c_char_p), POINTER(c_int * 4)]),
-    "dmx_trocr_dec_arena_bytes": (c_size_t, [_P]),
-    "dmx_trocr_dec_bind_arena": (c_int, [_P, _P, c_size_t]),
-    "dmx_trocr_dec_load_param": (c_int, [_P, c_char_p, _P, _P]),
-    "dmx_trocr_dec_finalize": (c_int, [_P, _P]),
     "dmx_trocr_dec_cache_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
     "dmx_trocr_dec_workspace_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
     "dmx_trocr_dec_cross_kv": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
@@ -209,14 +193,6 @@ _PROTOS = {
                                      _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     "dmx_trocr_dec_attn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dmx_trocr_dec_attn": (c_int, [_P, c_int, c_int, _P, c_int64, c_int, c_int, _P, _P, c_size_t, _P]),
-    "dmx_unet_create": (_P, [POINTER(UNetConfig)]),
-    "dmx_unet_destroy": (None, [_P]),
-    "dmx_unet_param_count": (c_int, [_P]),
-    "dmx_unet_param_info": (c_int, [_P, c_int, POINTER(c_char_p), POINTER(c_int * 4)]),
-    "dmx_unet_arena_bytes": (c_size_t, [_P]),
-    "dmx_unet_bind_arena": (c_int, [_P, _P, c_size_t]),
-    "dmx_unet_load_param": (c_int, [_P, c_char_p, _P, _P]),
-    "dmx_unet_finalize": (c_int, [_P, _P, _P]),
     "dmx_unet_context_bytes": (c_size_t, [_P, c_int, c_int]),
     "dmx_unet_workspace_bytes": (c_size_t, [_P, c_int, c_int, c_int, c_int]),
     "dmx_unet_set_context": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_size_t, _P, c_size_t, _P]),
@@ -278,18 +254,22 @@ _PROTOS = {
     "dmx_profile_end": (c_int, [POINTER(ctypes.c_double), c_int]),
     "dmx_profile_dump_path": (c_int, [c_char_p]),
     "dmx_profile_symbols": (c_size_t, [c_char_p, c_size_t]),
-    "dmx_vae_create": (_P, [POINTER(VAEConfig)]),
-    "dmx_vae_destroy": (None, [_P]),
-    "dmx_vae_param_count": (c_int, [_P]),
-    "dmx_vae_param_info": (c_int, [_P, c_int, POINTER(c_char_p), POINTER(c_int * 4)]),
-    "dmx_vae_arena_bytes": (c_size_t, [_P]),
-    "dmx_vae_bind_arena": (c_int, [_P, _P, c_size_t]),
-    "dmx_vae_load_param": (c_int, [_P, c_char_p, _P, _P]),
-    "dmx_vae_finalize": (c_int, [_P, _P]),
     "dmx_vae_workspace_bytes": (c_size_t, [_P, c_int, c_int, c_int, c_int]),
     "dmx_vae_encode": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     "dmx_vae_decode": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
 }
+# the model lifecycle every handle shares (DMX_MODEL_ABI in include/diffute_hip.h); the UNet's finalize also takes the frequency table
+for _kind, _cfg in (("unet", UNetConfig), ("vae", VAEConfig), ("vit", ViTConfig), ("trocr_dec", TrOCRDecConfig)):
+    _PROTOS.update({
+        f"dmx_{_kind}_create": (_P, [POINTER(_cfg)]),
+        f"dmx_{_kind}_destroy": (None, [_P]),
+        f"dmx_{_kind}_param_count": (c_int, [_P]),
+        f"dmx_{_kind}_param_info": (c_int, [_P, c_int, POINTER(c_char_p), POINTER(c_int * 4)]),
+        f"dmx_{_kind}_arena_bytes": (c_size_t, [_P]),
+        f"dmx_{_kind}_bind_arena": (c_int, [_P, _P, c_size_t]),
+        f"dmx_{_kind}_load_param": (c_int, [_P, c_char_p, _P, _P]),
+        f"dmx_{_kind}_finalize": (c_int, [_P, _P, _P] if _kind == "unet" else [_P, _P]),
+    })
 
 
 def lib_path():

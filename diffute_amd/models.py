@@ -123,9 +123,26 @@ def _attach(root: nn.Module, key: str, param: nn.Parameter):
     mod.register_parameter(parts[-1], param)
 
 
+def load_weights_file(directory, safetensors_name, bin_name):
+    """the state dict of a model directory: `safetensors_name` if present, else the torch pickle `bin_name`"""
+    st = os.path.join(directory, safetensors_name)
+    if os.path.exists(st):
+        from safetensors.torch import load_file
+        return load_file(st)
+    return torch.load(os.path.join(directory, bin_name), map_location="cpu")
+
+
+def _three_parts(parts):
+    """the (tensor, channels) pairs of up to three input parts, padded with (None, 0)"""
+    return [(p, p.shape[1]) for p in parts] + [(None, 0)] * (3 - len(parts))
+
+
 class _HipModel(nn.Module):
-    """Shared plumbing: parameter tree from the C library's table, packed-weights arena, workspace."""
-    _kind = None         # "unet" | "vae"
+    """Shared plumbing: parameter tree from the C library's table, packed-weights arena, workspace, and the weights epoch
+    every cache derived from the arena is stamped with."""
+    _kind = None            # "unet" | "vae" | "vit" | "trocr_dec"
+    _master_bytes = None    # name of the query for the size of the packed fp32 master / gradient arena
+    _tb_extra = {}          # further entries of the training buffers
 
     def _create_handle(self, elem):
         l = _cabi.lib(elem)
@@ -149,19 +166,15 @@ class _HipModel(nn.Module):
         workspaces, context caches and captured graphs belong to the old handle and are dropped"""
         if elem == self._elem:
             return
-        if getattr(self, "_fused", None) is not None or getattr(self, "_tb", None) is not None:
+        if self._fused is not None or self._tb is not None:
             raise NotImplementedError(f"{type(self).__name__}: changing the compute type after training state exists is not supported")
         torch.cuda.synchronize() if torch.cuda.is_initialized() else None
         new_h = self._create_handle(elem)                 # (first the new handle: a missing build / failed create leaves the model as it was)
         old_h, old_elem = self._h, self._elem
         self._h, self._elem = new_h, elem
         getattr(_cabi.lib(old_elem), f"dmx_{self._kind}_destroy")(old_h)
-        self._arena = None; self._packed_sig = None; self._ws = None
-        for attr in ("_masters32", "_train"):
-            if hasattr(self, attr):
-                setattr(self, attr, None)
-        if hasattr(self, "_slots"):
-            self._slots = {}
+        self._arena = None; self._packed_sig = None; self._ws = None; self._masters32 = None
+        self._slots = {}
 
     def _setup(self, handle, seed, device):
         _LIVE_MODELS.add(self)
@@ -171,6 +184,13 @@ class _HipModel(nn.Module):
         self._arena = None
         self._packed_sig = None
         self._ws = None
+        self._epoch = 0                 # counts the changes of the arena's contents (_weights_changed): the stamp of every derived cache
+        self._slots = {}                # UNet execution slots
+        self._fused = None              # the FusedAdamW that owns the weights
+        self._tb = None                 # training buffers (_train_buffers)
+        self._sync = None               # gradient exchange (set_gradient_sync)
+        self._excl_before_sync = None
+        self._masters32 = None          # (epoch, fp32 master arena) of the validation path
         lib = self._lib
         n = getattr(lib, f"dmx_{self._kind}_param_count")(self._h)
         self._keys = []
@@ -241,7 +261,14 @@ class _HipModel(nn.Module):
         optimizer steps are detected without it."""
         self._packed_sig = None
 
-    def _ensure_packed(self):
+    def _weights_changed(self):
+        """the arena's contents changed: context K/V, transposed training weights, fp32 validation masters and decoder runs
+        built at an earlier epoch are rebuilt on their next use"""
+        self._epoch += 1
+
+    def _ensure_packed(self, reimport_masters=True):
+        """re-pack the arena when the Parameters changed; reimport_masters=False when a fused optimizer's masters are what
+        the Parameters were just written from"""
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("diffute_amd: model parameters must be on the GPU (call .cuda()); there is no CPU path")
@@ -256,26 +283,84 @@ class _HipModel(nn.Module):
         torch.cuda.synchronize(dev)
         _cabi.check(getattr(lib, f"dmx_{k}_bind_arena")(self._h, _cabi.ptr(self._arena), nbytes), "bind_arena")
         st = _cabi.current_stream()
-        sd = dict(self.named_parameters())
-        for key in self._keys:
-            src = sd[key].detach().to(torch.float32).contiguous()
+        for key, p in zip(self._keys, self._param_list()):
+            src = p.detach().to(torch.float32).contiguous()
             _cabi.check(getattr(lib, f"dmx_{k}_load_param")(self._h, key.encode(), _cabi.ptr(src), st), f"load_param({key})")
         self._finalize(st)
         self._packed_sig = sig
-        fused = getattr(self, "_fused", None)
-        if fused is not None:                        # the Parameters changed under a fused optimizer (load_state_dict, an in-place
-            fused.reimport_masters()                 # write under no_grad, mark_parameters_changed()): they are the new master copy
+        self._weights_changed()
+        if self._fused is not None and reimport_masters:    # the Parameters changed under a fused optimizer (load_state_dict, an in-place
+            self._fused.reimport_masters()                   # write under no_grad, mark_parameters_changed()): they are the new master copy
+
+    def _finalize(self, st):
+        _cabi.check(getattr(self._lib, f"dmx_{self._kind}_finalize")(self._h, st), f"{self._kind}_finalize")
+
+    def _grown(self, holder, key, nbytes):
+        """the grow-only uint8 buffer holder[key] on the model's device, at least nbytes large (the old one is released before
+        a larger one is allocated)"""
+        buf = holder[key]
+        if buf is None or buf.numel() < nbytes or buf.device != self.device:
+            buf = holder[key] = None
+            buf = holder[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        return buf
 
     def _workspace(self, nbytes):
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != self.device:
-            self._ws = None
-            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._grown(self.__dict__, "_ws", nbytes)
+
+    def _param_list(self):
+        sd = dict(self.named_parameters())
+        return [sd[k] for k in self._keys]
+
+    # ---- the per-parameter walk between torch layouts and a packed fp32 arena (masters, gradients, EMA shadows)
+    def _import_arena(self, tensors, arena=None, keys=None):
+        """tensors (of the parameters `keys`, default all) -> their places in the packed fp32 `arena` (default a new zeroed one)"""
+        lib = self._lib
+        if arena is None:
+            arena = torch.zeros(getattr(lib, self._master_bytes)(self._h) // 4, dtype=torch.float32, device=tensors[0].device)
+        imp = getattr(lib, f"dmx_{self._kind}_master_import")
+        st = _cabi.current_stream()
+        for k, t in zip(keys or self._keys, tensors):
+            src = t.detach().to(torch.float32).contiguous()
+            _cabi.check(imp(self._h, _cabi.ptr(arena), k.encode(), _cabi.ptr(src), st), f"master_import({k})")
+        return arena
+
+    def _export_arena(self, arena, tensors, keys=None):
+        """packed fp32 `arena` -> tensors (of the parameters `keys`, default all): in place where a tensor is fp32 and
+        contiguous, through a temporary otherwise"""
+        exp = getattr(self._lib, f"dmx_{self._kind}_grad_export")
+        st = _cabi.current_stream()
+        for k, t in zip(keys or self._keys, tensors):
+            dst = t if (t.dtype == torch.float32 and t.is_contiguous()) else torch.empty(t.shape, dtype=torch.float32, device=t.device)
+            _cabi.check(exp(self._h, _cabi.ptr(arena), k.encode(), _cabi.ptr(dst), st), f"grad_export({k})")
+            if dst is not t:
+                t.copy_(dst)
+        return tensors
+
+    def _masters_fp32(self):
+        """fp32 master arena of the validation path: the current weights (a fused optimizer's included), imported once per epoch"""
+        self._ensure_packed()
+        if self._fused is not None:
+            self._fused.sync_to_model()
+        if self._masters32 is None or self._masters32[0] != self._epoch:
+            self._masters32 = (self._epoch, self._import_arena(self._param_list()))
+        return self._masters32[1]
+
+    def _train_buffers(self):
+        """transposed-weights arena (data-gradient operands, refreshed when the weights change) and the fp32 gradient arena"""
+        lib, k = self._lib, self._kind
+        tb = self._tb
+        if tb is None or tb["wt"].device != self.device:
+            tb = self._tb = dict(wt=torch.empty(getattr(lib, f"dmx_{k}_train_wt_bytes")(self._h), dtype=torch.uint8, device=self.device),
+                                 grads=torch.zeros(getattr(lib, self._master_bytes)(self._h) // 4, dtype=torch.float32, device=self.device),      # (zeros: slots no backward writes - derived weights - are summed / exchanged with the rest)
+                                 wt_sig=None, ws=None, **self._tb_extra)
+        if tb["wt_sig"] != self._epoch:
+            _cabi.check(getattr(lib, f"dmx_{k}_train_prepare")(self._h, _cabi.ptr(tb["wt"]), tb["wt"].numel(), _cabi.current_stream()), f"{k}_train_prepare")
+            tb["wt_sig"] = self._epoch
+        return tb
 
     def state_dict(self, *args, **kwargs):
-        f = getattr(self, "_fused", None)
-        if f is not None:
-            f.sync_to_model()
+        if self._fused is not None:
+            self._fused.sync_to_model()
         return super().state_dict(*args, **kwargs)
 
     # ---- (de)serialisation in the diffusers directory layout (train_diffute_v1.py:664-690)
@@ -309,12 +394,7 @@ class _HipModel(nn.Module):
     def from_pretrained(cls, pretrained_model_name_or_path, subfolder=None, revision=None, **kw):
         d = pretrained_model_name_or_path if subfolder is None else os.path.join(pretrained_model_name_or_path, subfolder)
         model = cls(**cls.load_config(d))
-        st = os.path.join(d, "diffusion_pytorch_model.safetensors")
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st)
-        else:
-            sd = torch.load(os.path.join(d, "diffusion_pytorch_model.bin"), map_location="cpu")
+        sd = load_weights_file(d, "diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.bin")
         model.load_state_dict(cls._convert_legacy_keys(sd))
         return model
 
@@ -332,6 +412,8 @@ class _HipModel(nn.Module):
 class UNet2DConditionModel(_HipModel):
     """SD2-inpainting UNet (reference: train_diffute_v1.py:633-635, app.ipynb:551-553)."""
     _kind = "unet"
+    _master_bytes = "dmx_unet_grad_bytes"
+    _tb_extra = dict(events=None, plan=None)     # bucket events and exchange plan of the gradient sync
 
     def __init__(self, seed=1234, device="cpu", **config):
         super().__init__()
@@ -357,7 +439,6 @@ class UNet2DConditionModel(_HipModel):
             c.down_has_attn[i] = int(cfg["down_block_types"][i].startswith("CrossAttn"))
             c.up_has_attn[i] = int(cfg["up_block_types"][i].startswith("CrossAttn"))
         self._cstruct = c
-        self._slots = {}
         self._setup(self._create_handle("bf16"), seed, device)
 
     def _finalize(self, st):
@@ -367,8 +448,6 @@ class UNet2DConditionModel(_HipModel):
         freq = torch.exp(exponent / (half - self.config.freq_shift)).contiguous()
         self._freq_host = freq
         _cabi.check(self._lib.dmx_unet_finalize(self._h, ctypes.c_void_p(freq.data_ptr()), st), "unet_finalize")
-        for sl in self._slots.values():
-            sl["ctx_key"] = None
 
     # ---- execution slots: independent (workspace, context cache) pairs so that several micro-batches can be in
     # flight on different streams at once (pipeline.denoise(..., micro_batches=n)); slot 0 serves the plain API.
@@ -377,12 +456,6 @@ class UNet2DConditionModel(_HipModel):
         if sl is None:
             sl = self._slots[i] = dict(ws=None, ctx_cache=None, ctx_key=None, ctx_shape=None, ws_need=None)
         return sl
-
-    def _slot_workspace(self, sl, nbytes):
-        if sl["ws"] is None or sl["ws"].numel() < nbytes or sl["ws"].device != self.device:
-            sl["ws"] = None
-            sl["ws"] = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
-        return sl["ws"]
 
     # ---- glyph-context K/V cache (constant across denoise steps, app.ipynb:776,814)
     def set_context(self, encoder_hidden_states, slot=0):
@@ -400,13 +473,13 @@ class UNet2DConditionModel(_HipModel):
         nb = lib.dmx_unet_context_bytes(self._h, B, S)
         if sl["ctx_cache"] is None or sl["ctx_cache"].numel() < nb or sl["ctx_cache"].device != ctx.device:
             sl["ctx_cache"] = torch.empty(nb, dtype=torch.uint8, device=ctx.device)
-        ws = self._slot_workspace(sl, lib.dmx_unet_workspace_bytes(self._h, B, 8, 8, S))
+        ws = self._grown(sl, "ws", lib.dmx_unet_workspace_bytes(self._h, B, 8, 8, S))
         _cabi.check(lib.dmx_unet_set_context(self._h, _cabi.ptr(ctx), int(ctx.dtype == self.compute_dtype), B, S,
                                              _cabi.ptr(sl["ctx_cache"]), sl["ctx_cache"].numel(),
                                              _cabi.ptr(ws), ws.numel(), _cabi.current_stream()), "unet_set_context")
-        # identity + version of the tensor object the K/V were projected from.  The strong reference keeps the allocator from
-        # handing the same address to a different tensor (a key on data_ptr would then silently reuse stale K/V).
-        sl["ctx_key"] = (encoder_hidden_states, encoder_hidden_states._version)
+        # identity + version of the tensor object the K/V were projected from, and the weights epoch they were projected at.  The strong
+        # reference keeps the allocator from handing the same address to a different tensor (a key on data_ptr would then silently reuse stale K/V).
+        sl["ctx_key"] = (encoder_hidden_states, encoder_hidden_states._version, self._epoch)
         sl["ctx_shape"] = (B, S)
 
     def temb_table(self, timesteps_dev):
@@ -432,15 +505,15 @@ class UNet2DConditionModel(_HipModel):
         sl = self._slot(slot)
         x0 = parts[0]
         B, _, H, W = x0.shape
-        if sl["ctx_key"] is None or sl["ctx_shape"][0] != B:
+        if sl["ctx_key"] is None or sl["ctx_key"][2] != self._epoch or sl["ctx_shape"][0] != B:
             raise RuntimeError("UNet2DConditionModel: set_context() must be called with a batch-matching context first")
-        ps = [(p, p.shape[1]) for p in parts] + [(None, 0)] * (3 - len(parts))
+        ps = _three_parts(parts)
         if out is None:
             out = torch.empty(B, self.config.out_channels, H, W, dtype=torch.float32, device=x0.device)
         key = (B, H, W, sl["ctx_shape"][1], int(lib.dmx_plan_epoch()))      # (every plan switch changes the walk, hence the workspace it needs)
         if sl["ws_need"] is None or sl["ws_need"][0] != key:
             sl["ws_need"] = (key, lib.dmx_unet_workspace_bytes(self._h, B, H, W, sl["ctx_shape"][1]))
-        ws = self._slot_workspace(sl, sl["ws_need"][1])
+        ws = self._grown(sl, "ws", sl["ws_need"][1])
         fwd = lib.dmx_unet_forward_graph if graph else lib.dmx_unet_forward
         if temb is not None:
             _cabi.check(lib.dmx_unet_use_temb_table(self._h, _cabi.ptr(temb[0]), _cabi.ptr(temb[1])), "unet_use_temb_table")
@@ -482,7 +555,7 @@ class UNet2DConditionModel(_HipModel):
         B, _, H, W = x.shape
         t = torch.as_tensor(timestep).reshape(-1).to(device=x.device, dtype=torch.int64)
         out = torch.empty(B, self.config.out_channels, H, W, dtype=torch.float32, device=x.device)
-        ws = self._slot_workspace(sl, lib.dmx_unet_workspace_bytes(self._h, B, H, W, sl["ctx_shape"][1]))
+        ws = self._grown(sl, "ws", lib.dmx_unet_workspace_bytes(self._h, B, H, W, sl["ctx_shape"][1]))
         buf, shapes, n = self._tap_buffers(B, H, W)
         _cabi.check(lib.dmx_unet_forward_taps(self._h, _cabi.ptr(x), x.shape[1], None, 0, None, 0, _cabi.ptr(t), t.numel(),
                                               _cabi.ptr(sl["ctx_cache"]), sl["ctx_shape"][1], _cabi.ptr(out), B, H, W, _cabi.ptr(ws), ws.numel(),
@@ -495,48 +568,26 @@ class UNet2DConditionModel(_HipModel):
         north_star's "within 1e-3 rel fp32" check against the fp32 reference path.  parts: one NCHW tensor or the list
         [latents, mask, masked_latents]; returns eps (and the block taps when taps=True).  Slow; never on the product path."""
         lib = self._lib
-        self._ensure_packed()
+        m = self._masters_fp32()
         if torch.is_tensor(parts):
             parts = [parts]
         parts = [p.to(torch.float32).contiguous() for p in parts]
         B, _, H, W = parts[0].shape
         dev = parts[0].device
-        m = getattr(self, "_masters32", None)
-        if m is None or m[0] != self._packed_sig:
-            arena = torch.zeros(lib.dmx_unet_grad_bytes(self._h) // 4, dtype=torch.float32, device=dev)
-            st = _cabi.current_stream()
-            for k, p in zip(self._keys, self._param_list()):
-                src = p.detach().to(torch.float32).contiguous()
-                _cabi.check(lib.dmx_unet_master_import(self._h, _cabi.ptr(arena), k.encode(), _cabi.ptr(src), st), f"master_import({k})")
-            m = self._masters32 = (self._packed_sig, arena)
         ctx = encoder_hidden_states.to(torch.float32).contiguous()
         S = ctx.shape[1]
         t = torch.as_tensor(timestep).reshape(-1).to(device=dev, dtype=torch.int64)
         out = torch.empty(B, self.config.out_channels, H, W, dtype=torch.float32, device=dev)
         ws = torch.empty(lib.dmx_unet_workspace_bytes_f32(self._h, B, H, W, S), dtype=torch.uint8, device=dev)
-        ps = [(p, p.shape[1]) for p in parts] + [(None, 0)] * (3 - len(parts))
+        ps = _three_parts(parts)
         buf, shapes, n = self._tap_buffers(B, H, W) if taps else (None, None, None)
-        _cabi.check(lib.dmx_unet_forward_f32(self._h, _cabi.ptr(m[1]), _cabi.ptr(ps[0][0]), ps[0][1], _cabi.ptr(ps[1][0]), ps[1][1],
+        _cabi.check(lib.dmx_unet_forward_f32(self._h, _cabi.ptr(m), _cabi.ptr(ps[0][0]), ps[0][1], _cabi.ptr(ps[1][0]), ps[1][1],
                                              _cabi.ptr(ps[2][0]), ps[2][1], _cabi.ptr(t), t.numel(), _cabi.ptr(ctx), S, _cabi.ptr(out), B, H, W,
                                              _cabi.ptr(ws), ws.numel(), _cabi.ptr(buf) if taps else None, buf.numel() if taps else 0,
                                              shapes if taps else None, ctypes.byref(n) if taps else None, _cabi.current_stream()), "unet_forward_f32")
         return (out, self._split_taps(buf, shapes, n)) if taps else out
 
     # ---- training (train_diffute_v1.py:913-925): forward that keeps activations + hand-written HIP backward
-    def _train_buffers(self):
-        """transposed-weights arena (data-gradient operands, refreshed when the weights change) and the fp32 gradient arena"""
-        lib = self._lib
-        tb = getattr(self, "_tb", None)
-        if tb is None or tb["wt"].device != self.device:
-            tb = self._tb = dict(wt=torch.empty(lib.dmx_unet_train_wt_bytes(self._h), dtype=torch.uint8, device=self.device),
-                                 grads=torch.zeros(lib.dmx_unet_grad_bytes(self._h) // 4, dtype=torch.float32, device=self.device),      # (zeros: slots no backward writes - derived weights - are summed / exchanged with the rest)
-                                 wt_sig=None, ws=None, events=None, plan=None)
-        sig = (self._packed_sig, getattr(self, "_arena_version", 0))
-        if tb["wt_sig"] != sig:
-            _cabi.check(lib.dmx_unet_train_prepare(self._h, _cabi.ptr(tb["wt"]), tb["wt"].numel(), _cabi.current_stream()), "unet_train_prepare")
-            tb["wt_sig"] = sig
-        return tb
-
     def set_gradient_sync(self, dist=None, group=None, mode="rs_ag", accumulate_steps=1):
         """Average gradients over the ranks of `dist` (torch.distributed; RCCL on GPUs) INSIDE the backward: each of the
         11 gradient buckets is exchanged on a side stream as soon as the backward has finished it - as an
@@ -556,9 +607,9 @@ class UNet2DConditionModel(_HipModel):
         # the exchange runs collective kernels on a side stream while the library's launches run: those hold CUs, so plans whose blocks need
         # co-resident peers (the in-kernel K split of dmx_conv3x3_gn, e.g. in the VAE encodes of the training step) are off for this process
         shared = self._sync is not None and self._sync["world"] > 1
-        if shared and getattr(self, "_excl_before_sync", None) is None:
+        if shared and self._excl_before_sync is None:
             self._excl_before_sync = (_cabi.set_exclusive_device(False),)
-        elif not shared and getattr(self, "_excl_before_sync", None) is not None:
+        elif not shared and self._excl_before_sync is not None:
             _cabi.set_exclusive_device(self._excl_before_sync[0])      # what the caller had before the exchange was switched on
             self._excl_before_sync = None
 
@@ -570,7 +621,7 @@ class UNet2DConditionModel(_HipModel):
 
         @contextlib.contextmanager
         def ctx():
-            sync = getattr(self, "_sync", None)
+            sync = self._sync
             if sync is not None:
                 sync["acc"].skip_ctx += 1
             try:
@@ -583,7 +634,7 @@ class UNet2DConditionModel(_HipModel):
     def exposed_exchange_ms(self):
         """how long the last backward's main stream sat waiting for the gradient exchange after its own kernels were done
         (the NON-overlapped part of D1); None before the first synchronised backward"""
-        sync = getattr(self, "_sync", None)
+        sync = self._sync
         if not sync or not sync.get("exposed"):
             return None
         a, b = sync["exposed"]
@@ -615,10 +666,7 @@ class UNet2DConditionModel(_HipModel):
         tb = self._train_buffers()
         B, _, H, W = sample.shape
         S = ctx.shape[1]
-        need = lib.dmx_unet_train_workspace_bytes(self._h, B, H, W, S)
-        if tb["ws"] is None or tb["ws"].numel() < need:
-            tb["ws"] = None
-            tb["ws"] = torch.empty(int(need), dtype=torch.uint8, device=sample.device)
+        self._grown(tb, "ws", lib.dmx_unet_train_workspace_bytes(self._h, B, H, W, S))
         pred = torch.empty(B, self.config.out_channels, H, W, dtype=torch.float32, device=sample.device)
         _cabi.check(lib.dmx_unet_train_forward(self._h, _cabi.ptr(tb["wt"]), _cabi.ptr(sample), sample.shape[1], None, 0, None, 0,
                                                _cabi.ptr(timestep), timestep.numel(), _cabi.ptr(ctx), int(ctx.dtype == self.compute_dtype), S,
@@ -631,13 +679,13 @@ class UNet2DConditionModel(_HipModel):
         """-> list of parameter gradients (torch layouts, fp32) in self._keys order"""
         lib = self._lib
         tb = self._tb
-        sync = getattr(self, "_sync", None)
+        sync = self._sync
         if sync is not None:
             dpred = dpred / sync["world"]                      # SUM over ranks below -> mean gradient
         dpred = dpred.to(torch.float32).contiguous()
         ev_arr, n_ev = None, 0
         acc = sync["acc"] if sync is not None else None
-        fused = getattr(self, "_fused", None)
+        fused = self._fused
         # gradient-accumulation window with the exchange on: local sum in acc.acc, one exchange at the boundary (dist.GradientAccumulator)
         windowed = acc is not None and (not acc.boundary() or acc.acc_n > 0)
         if windowed and acc.acc_n == 0 and fused is not None and fused._pending > 0:
@@ -688,30 +736,25 @@ class UNet2DConditionModel(_HipModel):
         if sync is not None and not exchange:              # torch optimizer, non-boundary micro-step: `.grad` stays as it is; the boundary delivers the window's sum
             torch.cuda.current_stream(dpred.device).wait_stream(tb["fwd_stream"])
             return [None] * len(self._keys)
-        out = []
         with torch.cuda.stream(tb["fwd_stream"]):
-            st = _cabi.current_stream()
-            for k, p in zip(self._keys, self._param_list()):
-                g = torch.empty(p.shape, dtype=torch.float32, device=dpred.device)
-                _cabi.check(lib.dmx_unet_grad_export(self._h, _cabi.ptr(tb["grads"]), k.encode(), _cabi.ptr(g), st), "grad_export")
-                out.append(g if p.dtype == torch.float32 else g.to(p.dtype))
+            out = self._export_arena(tb["grads"], [torch.empty(p.shape, dtype=p.dtype, device=dpred.device) for p in self._param_list()])
         torch.cuda.current_stream(dpred.device).wait_stream(tb["fwd_stream"])
         return out
 
-    def _param_list(self):
-        sd = dict(self.named_parameters())
-        return [sd[k] for k in self._keys]
+    def _timesteps(self, timestep, B, device):
+        """timestep (int / 0-d / [B] tensor) -> int64 tensor [1] or [B] on `device`"""
+        if not torch.is_tensor(timestep):
+            timestep = torch.tensor([int(timestep)], dtype=torch.int64)
+        t = timestep.reshape(-1).to(device=device, dtype=torch.int64)
+        if t.numel() not in (1, B):
+            raise ValueError(f"timestep must have 1 or {B} elements, got {t.numel()}")
+        return t
 
     def forward(self, sample, timestep, encoder_hidden_states, return_dict=True, **unused):
         """unet(sample[B,9,h,w], timestep (int / 0-d / [B] tensor), encoder_hidden_states[B,S,1024])."""
         _cabi.require_cuda(sample, encoder_hidden_states)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            B = sample.shape[0]
-            if not torch.is_tensor(timestep):
-                timestep = torch.tensor([int(timestep)], dtype=torch.int64)
-            t = timestep.reshape(-1).to(device=sample.device, dtype=torch.int64)
-            if t.numel() not in (1, B):
-                raise ValueError(f"timestep must have 1 or {B} elements, got {t.numel()}")
+            t = self._timesteps(timestep, sample.shape[0], sample.device)
             # (the fp16 build trains too - `--mixed_precision fp16`, train_diffute_v1.py:267,583,790: activation gradients are stored in
             # fp16 there, so run the backward under a loss scale: diffute_amd.GradScaler / torch.amp.GradScaler, training.train_step(scaler=))
             ctx = encoder_hidden_states if encoder_hidden_states.dtype in (torch.float32, self.compute_dtype) else encoder_hidden_states.float()
@@ -721,14 +764,9 @@ class UNet2DConditionModel(_HipModel):
             return UNet2DConditionOutput(sample=out) if return_dict else (out,)
         self._ensure_packed()
         ck = self._slot(0)["ctx_key"]
-        if ck is None or ck[0] is not encoder_hidden_states or ck[1] != encoder_hidden_states._version:
+        if ck is None or ck[0] is not encoder_hidden_states or ck[1] != encoder_hidden_states._version or ck[2] != self._epoch:
             self.set_context(encoder_hidden_states)
-        B = sample.shape[0]
-        if not torch.is_tensor(timestep):
-            timestep = torch.tensor([int(timestep)], dtype=torch.int64)
-        t = timestep.reshape(-1).to(device=sample.device, dtype=torch.int64)
-        if t.numel() not in (1, B):
-            raise ValueError(f"timestep must have 1 or {B} elements, got {t.numel()}")
+        t = self._timesteps(timestep, sample.shape[0], sample.device)
         x = sample.to(torch.float32).contiguous()
         out = self.forward_parts([x], t)
         if self._dtype != torch.float32 and sample.dtype != torch.float32:
@@ -792,6 +830,7 @@ class _MSEFn(torch.autograd.Function):
 class AutoencoderKL(_HipModel):
     """SD VAE (reference: train_diffute_v1.py:632, app.ipynb:550, train_vae.py:516)."""
     _kind = "vae"
+    _master_bytes = "dmx_vae_grad_bytes"
 
     def __init__(self, seed=4321, device="cpu", **config):
         super().__init__()
@@ -816,9 +855,6 @@ class AutoencoderKL(_HipModel):
         self._cstruct = c
         h = self._create_handle("bf16")
         self._setup(h, seed, device)
-
-    def _finalize(self, st):
-        _cabi.check(self._lib.dmx_vae_finalize(self._h, st), "vae_finalize")
 
     @staticmethod
     def _convert_legacy_keys(sd):
@@ -869,19 +905,6 @@ class AutoencoderKL(_HipModel):
         return DecoderOutput(sample=img) if return_dict else (img,)
 
     # ---- fp32 VALIDATION path (tests only): the same graphs on fp32 activations, fp32 master weights, plain fp32 kernels
-    def _masters_fp32(self):
-        lib = self._lib
-        self._ensure_packed()
-        m = getattr(self, "_masters32", None)
-        if m is None or m[0] != self._packed_sig:
-            arena = torch.zeros(lib.dmx_vae_grad_bytes(self._h) // 4, dtype=torch.float32, device=self.device)
-            st = _cabi.current_stream()
-            for k, p in zip(self._keys, self._param_list()):
-                src = p.detach().to(torch.float32).contiguous()
-                _cabi.check(lib.dmx_vae_master_import(self._h, _cabi.ptr(arena), k.encode(), _cabi.ptr(src), st), f"vae_master_import({k})")
-            m = self._masters32 = (self._packed_sig, arena)
-        return m[1]
-
     @torch.no_grad()
     def encode_fp32(self, x):
         """VALIDATION ONLY: `encode(x).latent_dist.parameters` (the moments) through the fp32 instantiation of the graph -
@@ -912,31 +935,12 @@ class AutoencoderKL(_HipModel):
         return img
 
     # ---- training (train_vae.py:716-736): recon = decode(encode(x).mode()) with a HIP backward
-    def _train_buffers(self):
-        lib = self._lib
-        tb = getattr(self, "_tb", None)
-        if tb is None or tb["wt"].device != self.device:
-            tb = self._tb = dict(wt=torch.empty(lib.dmx_vae_train_wt_bytes(self._h), dtype=torch.uint8, device=self.device),
-                                 grads=torch.zeros(lib.dmx_vae_grad_bytes(self._h) // 4, dtype=torch.float32, device=self.device),
-                                 wt_sig=None, ws=None)
-        if tb["wt_sig"] != self._packed_sig:
-            _cabi.check(lib.dmx_vae_train_prepare(self._h, _cabi.ptr(tb["wt"]), tb["wt"].numel(), _cabi.current_stream()), "vae_train_prepare")
-            tb["wt_sig"] = self._packed_sig
-        return tb
-
-    def _param_list(self):
-        sd = dict(self.named_parameters())
-        return [sd[k] for k in self._keys]
-
     def _train_forward(self, x):
         lib = self._lib
         self._ensure_packed()
         tb = self._train_buffers()
         B, _, H, W = x.shape
-        need = lib.dmx_vae_train_workspace_bytes(self._h, B, H, W)
-        if tb["ws"] is None or tb["ws"].numel() < need:
-            tb["ws"] = None
-            tb["ws"] = torch.empty(int(need), dtype=torch.uint8, device=x.device)
+        self._grown(tb, "ws", lib.dmx_vae_train_workspace_bytes(self._h, B, H, W))
         recon = torch.empty(B, self.config.out_channels, H, W, dtype=torch.float32, device=x.device)
         _cabi.check(lib.dmx_vae_train_forward(self._h, _cabi.ptr(tb["wt"]), _cabi.ptr(x), _cabi.ptr(recon), B, H, W,
                                               _cabi.ptr(tb["ws"]), tb["ws"].numel(), _cabi.current_stream()), "vae_train_forward")
@@ -947,14 +951,9 @@ class AutoencoderKL(_HipModel):
         lib = self._lib
         tb = self._tb
         drecon = drecon.to(torch.float32).contiguous()
-        out = []
         with torch.cuda.stream(tb["fwd_stream"]):
-            st = _cabi.current_stream()
-            _cabi.check(lib.dmx_vae_train_backward(self._h, _cabi.ptr(tb["grads"]), _cabi.ptr(drecon), st), "vae_train_backward")
-            for k, p in zip(self._keys, self._param_list()):
-                g = torch.empty(p.shape, dtype=torch.float32, device=drecon.device)
-                _cabi.check(lib.dmx_vae_grad_export(self._h, _cabi.ptr(tb["grads"]), k.encode(), _cabi.ptr(g), st), "vae_grad_export")
-                out.append(g if p.dtype == torch.float32 else g.to(p.dtype))
+            _cabi.check(lib.dmx_vae_train_backward(self._h, _cabi.ptr(tb["grads"]), _cabi.ptr(drecon), _cabi.current_stream()), "vae_train_backward")
+            out = self._export_arena(tb["grads"], [torch.empty(p.shape, dtype=p.dtype, device=drecon.device) for p in self._param_list()])
         torch.cuda.current_stream(drecon.device).wait_stream(tb["fwd_stream"])
         return out
 
@@ -988,6 +987,7 @@ class TrOCREncoder(_HipModel):
     'microsoft/trocr-large-printed').encoder`, train_diffute_v1.py:630-631, app.ipynb:546-548;
     `trocr_model(pixel_values).last_hidden_state`, :868-871 / :773-776).  Forward-only (frozen in the reference, :638)."""
     _kind = "vit"
+    _master_bytes = "dmx_vit_master_bytes"
 
     def __init__(self, seed=777, device="cpu", **config):
         super().__init__()
@@ -1003,9 +1003,6 @@ class TrOCREncoder(_HipModel):
         h = self._create_handle("bf16")
         self._setup(h, seed, device)
         self.requires_grad_(False)
-
-    def _finalize(self, st):
-        _cabi.check(self._lib.dmx_vit_finalize(self._h, st), "vit_finalize")
 
     @staticmethod
     def _convert_legacy_keys(sd):
@@ -1024,13 +1021,7 @@ class TrOCREncoder(_HipModel):
         cfg = cfg.get("encoder", cfg)
         keep = {k: cfg[k] for k in TROCR_LARGE_VIT_CONFIG if k in cfg}
         model = cls(**keep)
-        st = os.path.join(d, "model.safetensors")
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st)
-        else:
-            sd = torch.load(os.path.join(d, "pytorch_model.bin"), map_location="cpu")
-        model.load_state_dict(cls._convert_legacy_keys(sd))
+        model.load_state_dict(cls._convert_legacy_keys(load_weights_file(d, "model.safetensors", "pytorch_model.bin")))
         return model
 
     def forward(self, pixel_values, return_dict=True, **unused):
@@ -1056,21 +1047,12 @@ class TrOCREncoder(_HipModel):
         """VALIDATION ONLY: `last_hidden_state` through the fp32 instantiation of the graph (fp32 activations, fp32 master
         weights, plain fp32 kernels) - compared with transformers' ViTModel at north_star's 1e-3.  Slow."""
         lib = self._lib
-        self._ensure_packed()
+        m = self._masters_fp32()
         x = pixel_values.to(torch.float32).contiguous()
         B = x.shape[0]
-        m = getattr(self, "_masters32", None)
-        if m is None or m[0] != self._packed_sig:
-            arena = torch.zeros(lib.dmx_vit_master_bytes(self._h) // 4, dtype=torch.float32, device=x.device)
-            st = _cabi.current_stream()
-            sd = dict(self.named_parameters())
-            for k in self._keys:
-                src = sd[k].detach().to(torch.float32).contiguous()
-                _cabi.check(lib.dmx_vit_master_import(self._h, _cabi.ptr(arena), k.encode(), _cabi.ptr(src), st), f"vit_master_import({k})")
-            m = self._masters32 = (self._packed_sig, arena)
         n = (self.config.image_size // self.config.patch_size) ** 2 + 1
         out = torch.empty(B, n, self.config.hidden_size, dtype=torch.float32, device=x.device)
         ws = torch.empty(lib.dmx_vit_workspace_bytes_f32(self._h, B), dtype=torch.uint8, device=x.device)
-        _cabi.check(lib.dmx_vit_forward_f32(self._h, _cabi.ptr(m[1]), _cabi.ptr(x), _cabi.ptr(out), B, _cabi.ptr(ws), ws.numel(),
+        _cabi.check(lib.dmx_vit_forward_f32(self._h, _cabi.ptr(m), _cabi.ptr(x), _cabi.ptr(out), B, _cabi.ptr(ws), ws.numel(),
                                             _cabi.current_stream()), "vit_forward_f32")
         return out

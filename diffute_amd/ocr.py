@@ -13,7 +13,7 @@ import torch
 from torch import nn
 
 from . import _cabi
-from .models import TROCR_LARGE_VIT_CONFIG, TrOCREncoder, _Config, _HipModel
+from .models import TROCR_LARGE_VIT_CONFIG, TrOCREncoder, _Config, _HipModel, load_weights_file
 
 # transformers' TrOCRConfig defaults = the trocr-large decoder
 TROCR_LARGE_DECODER_CONFIG = dict(
@@ -66,11 +66,7 @@ class TrOCRForCausalLM(_HipModel):
         h = self._create_handle("bf16")
         self._setup(h, seed, device)
         self.requires_grad_(False)
-        self._runs = {}
-
-    def _finalize(self, st):
-        _cabi.check(self._lib.dmx_trocr_dec_finalize(self._h, st), "trocr_dec_finalize")
-        self._runs = {}
+        self._runs, self._runs_epoch = {}, self._epoch
 
     def _switch_build(self, elem):
         if elem != "bf16":
@@ -83,6 +79,8 @@ class TrOCRForCausalLM(_HipModel):
     # ---- buffers of one (B, S, max_len): cache (state words, self / cross K/V), workspace, output ids, optional logits row
     def _run(self, B, S, max_len):
         key = (B, S, max_len)
+        if self._runs_epoch != self._epoch:      # runs (and their captured graphs) of earlier weights
+            self._runs, self._runs_epoch = {}, self._epoch
         r = self._runs.get(key)
         if r is None:
             lib, dev = self._lib, self.device
@@ -272,12 +270,7 @@ class VisionEncoderDecoderModel(nn.Module):
             if k not in gen and cfg.get(k) is not None:
                 gen[k] = cfg[k]
         model = cls(encoder, decoder, gen)
-        st = os.path.join(d, "model.safetensors")
-        if os.path.exists(st):
-            from safetensors.torch import load_file
-            sd = load_file(st)
-        else:
-            sd = torch.load(os.path.join(d, "pytorch_model.bin"), map_location="cpu")
+        sd = load_weights_file(d, "model.safetensors", "pytorch_model.bin")
         if any(k.startswith("enc_to_dec_proj.") for k in sd):
             raise NotImplementedError("VisionEncoderDecoderModel: enc_to_dec_proj is not implemented")
         enc_sd = TrOCREncoder._convert_legacy_keys({k: v for k, v in sd.items() if k.startswith("encoder.")})

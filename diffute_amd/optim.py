@@ -35,11 +35,9 @@ class FusedAdamW(torch.optim.Optimizer):
         self.t = 0
         lib = unet._lib                        # the build the model computes in writes its 16-bit weights (bf16 / fp16)
         dev = unet.device
-        n = lib.dmx_unet_grad_bytes(unet._h) // 4
-        self.masters = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
-        self._import_masters()
+        self.masters = unet._import_arena(unet._param_list())
+        self.exp_avg = torch.zeros_like(self.masters)
+        self.exp_avg_sq = torch.zeros_like(self.masters)
         self.ema = self.masters.clone() if ema_decay is not None else None      # shadow parameters start as a copy of the model
         st = _cabi.current_stream()
         self.nchunks = lib.dmx_unet_optim_chunks(unet._h)
@@ -70,19 +68,11 @@ class FusedAdamW(torch.optim.Optimizer):
     def weight_decay(self):
         return float(self.param_groups[0]["weight_decay"])
 
-    def _import_masters(self):
-        u = self.unet
-        lib = u._lib
-        st = _cabi.current_stream()
-        for k, p in zip(u._keys, u._param_list()):
-            src = p.detach().to(torch.float32).contiguous()
-            _cabi.check(lib.dmx_unet_master_import(u._h, _cabi.ptr(self.masters), k.encode(), _cabi.ptr(src), st), f"master_import({k})")
-
     def reimport_masters(self):
         """the torch Parameters were changed from outside (load_state_dict, broadcast_parameters): they replace the master
         copy; the Adam moments are kept (what torch.optim.AdamW does when parameters are overwritten in place).  Called by
         UNet2DConditionModel._ensure_packed, which has just re-packed the weights arena from the same Parameters."""
-        self._import_masters()
+        self.unet._import_arena(self.unet._param_list(), self.masters)
         self.dirty = False
 
     @property
@@ -113,9 +103,8 @@ class FusedAdamW(torch.optim.Optimizer):
     def zero_grad(self, set_to_none=True):
         """drops the accumulated gradient: the next backward starts from zero"""
         self._pending = 0
-        sync = getattr(self.unet, "_sync", None)
-        if sync is not None:
-            sync["acc"].exchanged()                 # ... and so does an open no_sync() / accumulate_steps window
+        if self.unet._sync is not None:
+            self.unet._sync["acc"].exchanged()                # ... and so does an open no_sync() / accumulate_steps window
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=None):
@@ -148,9 +137,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 self._pending = 0
                 return
         _cabi.check(lib.dmx_unet_refresh_derived(u._h, st), "refresh_derived")
-        u._arena_version = getattr(u, "_arena_version", 0) + 1      # transposed weights are refreshed by the next training forward
-        for sl in u._slots.values():
-            sl["ctx_key"] = None                                     # cached context K/V were projected with the old weights
+        u._weights_changed()                                         # transposed weights, context K/V and fp32 masters follow at their next use
         self.dirty = True
         self._pending = 0
 
@@ -178,13 +165,9 @@ class FusedAdamW(torch.optim.Optimizer):
         # the loaded masters become the weights: Parameters first, then the packed arena + derived copies from them
         self.dirty = True
         self.sync_to_model()
-        self.unet._packed_sig = None
-        fused, self.unet._fused = self.unet._fused, None        # re-pack without re-importing the masters we just loaded
-        try:
-            self.unet._ensure_packed()
-        finally:
-            self.unet._fused = fused
-        self.unet._arena_version = getattr(self.unet, "_arena_version", 0) + 1   # transposed weights follow at the next training forward
+        self.unet.mark_parameters_changed()
+        self.unet._ensure_packed(reimport_masters=False)        # (the Parameters were just written from the loaded masters)
+        self.unet._weights_changed()
         self._pending = 0
 
     def ema_state_dict(self):
@@ -192,28 +175,14 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.ema is None:
             raise RuntimeError("FusedAdamW was built without ema_decay")
         u = self.unet
-        lib = u._lib
-        st = _cabi.current_stream()
-        out = {}
-        for k, p in zip(u._keys, u._param_list()):
-            dst = torch.empty(p.shape, dtype=torch.float32, device=p.device)
-            _cabi.check(lib.dmx_unet_grad_export(u._h, _cabi.ptr(self.ema), k.encode(), _cabi.ptr(dst), st), "ema_export")
-            out[k] = dst
-        return out
+        return dict(zip(u._keys, u._export_arena(self.ema, [torch.empty(p.shape, dtype=torch.float32, device=p.device) for p in u._param_list()])))
 
     def sync_to_model(self):
         """master arena -> the torch Parameters (fp32, torch layouts)"""
         if not self.dirty:
             return
-        u = self.unet
-        lib = u._lib
-        st = _cabi.current_stream()
         with torch.no_grad():
-            for k, p in zip(u._keys, u._param_list()):
-                dst = p.data if (p.dtype == torch.float32 and p.is_contiguous()) else torch.empty(p.shape, dtype=torch.float32, device=p.device)
-                _cabi.check(lib.dmx_unet_grad_export(u._h, _cabi.ptr(self.masters), k.encode(), _cabi.ptr(dst), st), "master_export")
-                if dst is not p.data:
-                    p.data.copy_(dst)
+            self.unet._export_arena(self.masters, [p.data for p in self.unet._param_list()])
         self.dirty = False
 
 

@@ -149,15 +149,8 @@ class EMAModel:
         if not self._stale:
             return
         a = self._arena
-        u = a["unet"]
-        lib = u._lib
         with torch.cuda.device(a["buf"].device):
-            st = _cabi.current_stream()
-            for s, k in zip(self._shadow, a["keys"]):
-                dst = s if (s.dtype == torch.float32 and s.is_contiguous()) else torch.empty(s.shape, dtype=torch.float32, device=s.device)
-                _cabi.check(lib.dmx_unet_grad_export(u._h, _cabi.ptr(a["buf"]), k.encode(), _cabi.ptr(dst), st), "ema_export")
-                if dst is not s:
-                    s.copy_(dst)
+            a["unet"]._export_arena(a["buf"], self._shadow, a["keys"])
         self._stale = False
 
     def _drop_arena(self):
@@ -204,7 +197,7 @@ class EMAModel:
             return
         dev = _check_kernel_operands(shadows, parameters, "step")
         owner, _ = _owner_of(parameters, full=False)
-        f = getattr(owner, "_fused", None) if owner is not None else None
+        f = owner._fused if owner is not None else None
         if f is not None:
             f.sync_to_model()                     # (FusedAdamW with shadows the arena path does not take - not fp32, a partial list)
         key = ("step",) + tuple((s.data_ptr(), s.dtype, p.data_ptr(), p.numel(), p.dtype, p.requires_grad) for s, p in zip(shadows, parameters))
@@ -222,13 +215,13 @@ class EMAModel:
         a = self._arena
         if a is not None:
             u = a["unet"]
-            f = getattr(u, "_fused", None)
+            f = u._fused
             if f is None or len(parameters) != len(a["ids"]) or any(id(p) != i for p, i in zip(parameters, a["ids"])):
                 self._drop_arena()
                 a = None
         if a is None:
             u, names = _owner_of(parameters)
-            f = getattr(u, "_fused", None) if u is not None else None
+            f = u._fused if u is not None else None
             if f is None:
                 return False
             if len(self._shadow) != len(parameters) or not all(s.dtype == torch.float32 and s.is_cuda and s.device == f.masters.device
@@ -249,13 +242,8 @@ class EMAModel:
         return True
 
     def _import_arena(self, u, names, parameters):
-        lib = u._lib
-        buf = torch.zeros(lib.dmx_unet_grad_bytes(u._h) // 4, dtype=torch.float32, device=self._shadow[0].device)
-        with torch.cuda.device(buf.device):
-            st = _cabi.current_stream()
-            for s, k in zip(self._shadow, names):
-                src = s.contiguous()
-                _cabi.check(lib.dmx_unet_master_import(u._h, _cabi.ptr(buf), k.encode(), _cabi.ptr(src), st), "ema_import")
+        with torch.cuda.device(self._shadow[0].device):
+            buf = u._import_arena(self._shadow, keys=names)
         self._arena = dict(unet=u, keys=names, ids=[id(p) for p in parameters], buf=buf)
         self._stale = False
 
@@ -298,7 +286,7 @@ class EMAModel:
     def _write_params(self, srcs, parameters, what):
         """param.data <- src for every pair; a diffute_amd model then re-packs its weights (and FusedAdamW re-imports its masters)"""
         owner, _ = _owner_of(parameters, full=False)
-        f = getattr(owner, "_fused", None) if owner is not None else None
+        f = owner._fused if owner is not None else None
         if f is not None and len(parameters) < len(owner._keys):
             f.sync_to_model()                     # the Parameters not written here must be current before the re-pack below
         cuda = [(s, p) for s, p in zip(srcs, parameters) if p.is_cuda and s.device == p.device]
@@ -320,7 +308,7 @@ class EMAModel:
             if f is not None:
                 f.dirty = False                   # the Parameters are the current weights now; the masters follow below
             owner.mark_parameters_changed()
-            owner._arena_version = getattr(owner, "_arena_version", 0) + 1     # transposed training weights follow too
+            owner._weights_changed()
             if owner.device.type == "cuda":
                 owner._ensure_packed()
 
@@ -334,7 +322,7 @@ class EMAModel:
         """save the current parameters (restore() brings them back after evaluating with copy_to())"""
         parameters = list(parameters)
         owner, _ = _owner_of(parameters, full=False)
-        f = getattr(owner, "_fused", None) if owner is not None else None
+        f = owner._fused if owner is not None else None
         if f is not None:
             f.sync_to_model()                     # a FusedAdamW-trained model's current weights are its masters
         self.collected_params = [param.detach().clone() for param in parameters]

@@ -1100,6 +1100,29 @@ def test_tiny_unet_fp32_validation_path(cuda, tiny_unet):
         assert rel_l2(tb[k], taps[k]) < 2e-2, k
 
 
+def test_fp32_validation_path_follows_a_fused_step(cuda):
+    """FusedAdamW.step() rewrites the arena in place and leaves the Parameters alone: the fp32 masters of the validation path
+    follow the weights epoch, so forward_fp32 after a step runs the stepped weights - within the fp32 path's 1e-3 of
+    forward_fp32 of a fresh model loaded from the stepped model's state_dict(), and not the pre-step output."""
+    import diffute_amd as D
+    from diffute_amd.models import mse_loss
+    from diffute_amd.synthetic import synth_inputs
+    lat, mask, mlat, ctx = synth_inputs(2, 16, 16, 77, 128, device=cuda)
+    x = torch.cat([lat, mask, mlat], 1); t = torch.tensor([500, 40], device=cuda)
+    unet = D.UNet2DConditionModel(**TINY_UNET).cuda()
+    opt = D.FusedAdamW(unet, lr=1e-3)
+    before = unet.forward_fp32(x, t, ctx)
+    mse_loss(unet(x, t, ctx).sample, torch.zeros_like(lat)).backward()
+    opt.step()
+    after = unet.forward_fp32(x, t, ctx)                            # (before state_dict() below syncs the Parameters)
+    fresh = D.UNet2DConditionModel(**TINY_UNET, seed=99).cuda()
+    fresh.load_state_dict(unet.state_dict())
+    want = fresh.forward_fp32(x, t, ctx)
+    print(f"fp32 path after a fused step: rel-L2 vs reloaded model {rel_l2(after, want):.1e}, vs pre-step output {rel_l2(after, before):.1e}")
+    assert_close(after, want.cpu(), 1e-3, "forward_fp32 after FusedAdamW.step vs a model loaded from the stepped state_dict")
+    assert not torch.equal(after, before), "forward_fp32 after FusedAdamW.step still runs the pre-step masters"
+
+
 def test_cfg1_fp32_validation_path(cuda):
     """BASELINE config 1 (full SD2-inpaint UNet, B=1, 256 px, 10 DDIM steps) on the fp32 validation path: first-step eps and
     the final latents within 1e-3 rel-L2 of the fp32 oracle's (tests/golden/cfg1_full.npz eps0_fp32 / final_fp32)."""
