@@ -90,6 +90,11 @@ class UNetConfig(ctypes.Structure):
                 ("norm_num_groups", c_int), ("down_has_attn", c_int * 4), ("up_has_attn", c_int * 4)]
 
 
+class TestTrJob(ctypes.Structure):
+    """dmx_test_tr_job (include/diffute_hip.h): one transpose of dmx_test_transpose_batch"""
+    _fields_ = [("in_", c_void_p), ("ldin", c_int), ("out", c_void_p), ("ldout", c_int), ("R", c_int), ("C", c_int)]
+
+
 class VAEConfig(ctypes.Structure):
     _fields_ = [("in_channels", c_int), ("out_channels", c_int), ("latent_channels", c_int),
                 ("block_out_channels", c_int * 4), ("layers_per_block", c_int), ("norm_num_groups", c_int)]
@@ -103,6 +108,19 @@ _PROTOS = {
     "dmx_test_raise_device_error": (c_int, [c_int, c_void_p]),
     "dmx_test_occupy_cus": (c_int, [c_int, c_int64, c_void_p]),
     "dmx_element_type": (c_char_p, []),
+    # test support: the small training kernels without an operator-level entry (tests/test_train_small_gpu.py)
+    "dmx_test_transpose_bf16": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P]),
+    "dmx_test_transpose_batch": (c_int, [_P, c_int, _P, c_size_t, _P]),
+    "dmx_test_add_bf16": (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P]),
+    "dmx_test_softmax_rows": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_float, _P]),
+    "dmx_test_softmax_bwd_rows": (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_float, _P]),
+    "dmx_test_pointwise_small_fwd": (c_int, [_P, c_int, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "dmx_test_pointwise_small_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dmx_test_pointwise_small_bwd": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "dmx_test_linear_small_bwd": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "dmx_test_slice_cast": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P]),
+    "dmx_test_mode_bwd": (c_int, [_P, c_int, _P, c_int, c_int, _P]),
+    "dmx_test_bf16_to_f32_rows": (c_int, [_P, c_int, _P, c_int, c_int, _P]),
     "dmx_conv_gemm_workspace_bytes": (c_size_t, [POINTER(GemmDesc)]),
     "dmx_conv_gemm": (c_int, [POINTER(GemmDesc), _P, c_size_t, _P]),
     "dmx_conv_gemm_rowstats_tiles": (c_int, [POINTER(GemmDesc)]),

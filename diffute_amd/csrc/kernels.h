@@ -395,6 +395,11 @@ int dmx_softmax_bwd_rows_launch(const bf16* P, int ldp, const float* dP, int ldd
 int dmx_linear_small_bwd_launch(const float* x, int ldx, const float* dy, int lddy, const bf16* w, int ldw,
                                 float* dw, int lddw, float* db, int db_stride, float* dx, int lddx,
                                 int B, int N, int K, int silu_in, int accumulate, hipStream_t stream);
+// vae_train.hip: the casts around the posterior mode (z = 16-bit of the mean half of the fp32 moments; dmom = (fp32 dz | 0); fp32 rows of a
+// strided 16-bit tensor)
+int dmx_slice_cast_launch(const float* in, int ldin, bf16* out, int ldo, int M, int C, hipStream_t stream);
+int dmx_mode_bwd_launch(const bf16* dz, int lddz, float* dmom, int M, int C, hipStream_t stream);
+int dmx_bf16_to_f32_rows_launch(const bf16* in, int ldin, float* out, int M, int C, hipStream_t stream);
 
 // ------------------------------------------------------------------ temb.hip
 int dmx_timestep_embedding_launch(const long long* t, int t_count, const float* freq, int B, int dim, float* out, hipStream_t stream);

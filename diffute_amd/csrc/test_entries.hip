@@ -1,0 +1,82 @@
+// Test support (include/diffute_hip.h "test support"): extern "C" entries that reach the small training kernels which have no
+// operator-level entry of their own - train_small.hip's transposes, add, pointwise 1x1 and small-linear backward, norm.hip's row
+// softmax and vae_train.hip's casts.  Each entry checks its arguments and forwards to the *_launch function the training graphs
+// call (tests/test_train_small_gpu.py); none does arithmetic of its own.
+#include "kernels.h"
+#include "../../include/diffute_hip.h"
+
+#define ST(s) ((hipStream_t)(s))
+
+extern "C" int dmx_test_transpose_bf16(const void* in, int ldin, void* out, int ldout, int R, int C, dmx_stream_t stream) {
+  DMX_REQUIRE(in && out && R > 0 && C > 0 && ldin >= C && ldout >= R, "test_transpose_bf16: bad argument");
+  return dmx_transpose_bf16_launch((const bf16*)in, ldin, (bf16*)out, ldout, R, C, ST(stream));
+}
+
+// The jobs are recorded through a TrBatch exactly as *_train_prepare records them (kernels.h) and run as one launch.  `table` is the
+// caller's device buffer for the job table; the host-side copy of what was uploaded last stays alive between calls, so a repeated
+// batch takes the "table unchanged" path.  njobs = 0, or another table pointer, forgets that copy.
+extern "C" int dmx_test_transpose_batch(const dmx_test_tr_job* h_jobs, int njobs, void* table, size_t table_bytes, dmx_stream_t stream) {
+  static std::vector<TrJob> cache;
+  static void* cache_table = nullptr;
+  if (njobs == 0) { cache.clear(); cache_table = nullptr; return DMX_OK; }
+  DMX_REQUIRE(h_jobs && njobs > 0 && table, "test_transpose_batch: null argument");
+  DMX_REQUIRE((size_t)njobs * sizeof(TrJob) <= table_bytes && table_bytes <= DMX_TR_TABLE_BYTES, "test_transpose_batch: %d jobs, table of %zu bytes", njobs, table_bytes);
+  for (int i = 0; i < njobs; ++i)
+    DMX_REQUIRE(h_jobs[i].in && h_jobs[i].out && h_jobs[i].R > 0 && h_jobs[i].C > 0 && h_jobs[i].ldin >= h_jobs[i].C && h_jobs[i].ldout >= h_jobs[i].R,
+                "test_transpose_batch: bad job %d", i);
+  if (table != cache_table) { cache.clear(); cache_table = table; }
+  TrBatch batch;
+  for (int i = 0; i < njobs; ++i) {
+    const int rc = dmx_transpose_bf16_launch((const bf16*)h_jobs[i].in, h_jobs[i].ldin, (bf16*)h_jobs[i].out, h_jobs[i].ldout, h_jobs[i].R, h_jobs[i].C, ST(stream));
+    if (rc) return rc;
+  }
+  return batch.run(table, table_bytes, cache, ST(stream));
+}
+
+extern "C" int dmx_test_add_bf16(const void* a, int lda, const void* b, int ldb, void* out, int ldo, int rows, int C, dmx_stream_t stream) {
+  DMX_REQUIRE(a && b && out && rows > 0 && C > 0 && lda >= C && ldb >= C && ldo >= C, "test_add_bf16: bad argument");
+  return dmx_add_bf16_launch((const bf16*)a, lda, (const bf16*)b, ldb, (bf16*)out, ldo, rows, C, ST(stream));
+}
+
+extern "C" int dmx_test_softmax_rows(const float* s, int lds, void* p, int ldp, int rows, int n, float scale, dmx_stream_t stream) {
+  DMX_REQUIRE(s && p && rows > 0 && n > 0 && lds >= n && ldp >= n, "test_softmax_rows: bad argument");
+  return dmx_softmax_rows_launch(s, lds, (bf16*)p, ldp, rows, n, scale, ST(stream));
+}
+extern "C" int dmx_test_softmax_bwd_rows(const void* p, int ldp, const float* dp, int lddp, void* ds, int ldds, int rows, int n, float scale, dmx_stream_t stream) {
+  DMX_REQUIRE(p && dp && ds && rows > 0 && n > 0 && ldp >= n && lddp >= n && ldds >= n, "test_softmax_bwd_rows: bad argument");
+  return dmx_softmax_bwd_rows_launch((const bf16*)p, ldp, dp, lddp, (bf16*)ds, ldds, rows, n, scale, ST(stream));
+}
+
+extern "C" int dmx_test_pointwise_small_fwd(const void* x, int ldx, const void* w, int ldw, const float* bias, void* y, int ldy, int M, int Cin, int Cout,
+                                            int out_f32, dmx_stream_t stream) {
+  DMX_REQUIRE(x && w && y && M > 0 && ldx >= Cin && ldw >= Cin && ldy >= Cout, "test_pointwise_small_fwd: bad argument");
+  return dmx_pointwise_small_fwd_launch((const bf16*)x, ldx, (const bf16*)w, ldw, bias, y, ldy, M, Cin, Cout, out_f32, ST(stream));
+}
+extern "C" size_t dmx_test_pointwise_small_bwd_workspace_bytes(int M, int Cin, int Cout) { return dmx_pointwise_small_bwd_ws_bytes(M, Cin, Cout); }
+extern "C" int dmx_test_pointwise_small_bwd(const void* x, int ldx, const float* dy, int lddy, const void* w, int ldw, void* dx, int lddx,
+                                            float* dw, int lddw, float* db, int M, int Cin, int Cout, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
+  DMX_REQUIRE(x && dy && w && dw && db && M > 0 && ldx >= Cin && lddy >= Cout && ldw >= Cin && lddw >= Cin && (!dx || lddx >= Cin), "test_pointwise_small_bwd: bad argument");
+  return dmx_pointwise_small_bwd_launch((const bf16*)x, ldx, dy, lddy, (const bf16*)w, ldw, (bf16*)dx, lddx, dw, lddw, db, M, Cin, Cout, workspace, workspace_bytes, ST(stream));
+}
+
+extern "C" int dmx_test_linear_small_bwd(const float* x, int ldx, const float* dy, int lddy, const void* w, int ldw, float* dw, int lddw, float* db, int db_stride,
+                                         float* dx, int lddx, int B, int N, int K, int silu_in, int accumulate, dmx_stream_t stream) {
+  DMX_REQUIRE(dy && B > 0 && N > 0 && K > 0 && lddy >= N && (dw || dx), "test_linear_small_bwd: bad argument");
+  DMX_REQUIRE(!dw || (x && ldx >= K && lddw >= K && (!db || db_stride >= 1)), "test_linear_small_bwd: dw wants x, lddw >= K, db_stride >= 1");
+  DMX_REQUIRE(!dx || (w && ldw >= K && lddx >= K && (!silu_in || (x && ldx >= K))), "test_linear_small_bwd: dx wants w, lddx >= K (and x with silu_in)");
+  DMX_REQUIRE(dw || !db, "test_linear_small_bwd: db is written by the dw kernel");
+  return dmx_linear_small_bwd_launch(x, ldx, dy, lddy, (const bf16*)w, ldw, dw, lddw, db, db_stride, dx, lddx, B, N, K, silu_in, accumulate, ST(stream));
+}
+
+extern "C" int dmx_test_slice_cast(const float* in, int ldin, void* out, int ldo, int M, int C, dmx_stream_t stream) {
+  DMX_REQUIRE(in && out && M > 0 && C > 0 && ldin >= C && ldo >= C, "test_slice_cast: bad argument");
+  return dmx_slice_cast_launch(in, ldin, (bf16*)out, ldo, M, C, ST(stream));
+}
+extern "C" int dmx_test_mode_bwd(const void* dz, int lddz, float* dmom, int M, int C, dmx_stream_t stream) {
+  DMX_REQUIRE(dz && dmom && M > 0 && C > 0 && lddz >= C, "test_mode_bwd: bad argument");
+  return dmx_mode_bwd_launch((const bf16*)dz, lddz, dmom, M, C, ST(stream));
+}
+extern "C" int dmx_test_bf16_to_f32_rows(const void* in, int ldin, float* out, int M, int C, dmx_stream_t stream) {
+  DMX_REQUIRE(in && out && M > 0 && C > 0 && ldin >= C, "test_bf16_to_f32_rows: bad argument");
+  return dmx_bf16_to_f32_rows_launch((const bf16*)in, ldin, out, M, C, ST(stream));
+}

@@ -42,6 +42,22 @@ __global__ __launch_bounds__(256) void dmx_bf16_to_f32_rows_kernel(const bf16* i
   out[i] = bf_bits2f(((const unsigned short*)in)[(size_t)m * ldin + c]);
 }
 
+}  // namespace
+// the launch functions of the three casts (kernels.h; the dmx_test_* entries of test_entries.hip run the same ones)
+int dmx_slice_cast_launch(const float* in, int ldin, bf16* out, int ldo, int M, int C, hipStream_t stream) {
+  hipLaunchKernelGGL(dmx_slice_cast_kernel, dim3(cdiv(M * C, 256)), dim3(256), 0, stream, in, ldin, out, ldo, M, C);
+  return dmx_check_launch("dmx_slice_cast_kernel");
+}
+int dmx_mode_bwd_launch(const bf16* dz, int lddz, float* dmom, int M, int C, hipStream_t stream) {
+  hipLaunchKernelGGL(dmx_mode_bwd_kernel, dim3(cdiv(M * 2 * C, 256)), dim3(256), 0, stream, dz, lddz, dmom, M, C);
+  return dmx_check_launch("dmx_mode_bwd_kernel");
+}
+int dmx_bf16_to_f32_rows_launch(const bf16* in, int ldin, float* out, int M, int C, hipStream_t stream) {
+  hipLaunchKernelGGL(dmx_bf16_to_f32_rows_kernel, dim3(cdiv(M * C, 256)), dim3(256), 0, stream, in, ldin, out, M, C);
+  return dmx_check_launch("dmx_bf16_to_f32_rows_kernel");
+}
+namespace {
+
 size_t wt_extra_eout(const dmx_vae* v) { return align_up(v->pt.total(), 256); }                       // [C_last][128]
 size_t wt_extra_dout(const dmx_vae* v) { return wt_extra_eout(v) + align_up((size_t)v->cfg.block_out_channels[3] * 128 * 2, 256); }   // [C_0][64]
 size_t wt_total(const dmx_vae* v) { return wt_extra_dout(v) + (size_t)v->cfg.block_out_channels[0] * 64 * 2; }
@@ -154,7 +170,7 @@ struct VaeTrain {
     float* mom = (float*)ex.raw((size_t)Ml * 2 * lc * 4);
     if (live()) ex.rc = dmx_pointwise_small_fwd_launch(m8.p, m8.ld, T.W(v->quant.w), v->quant.kpad, T.F(v->quant.b), mom, 2 * lc, Ml, 2 * lc, 2 * lc, 1, ex.stream);
     z = ex.make(B, lh, lw, lc);                      // posterior mode = mean, rounded as the decoder's input is
-    if (live()) { hipLaunchKernelGGL(dmx_slice_cast_kernel, dim3(cdiv(Ml * lc, 256)), dim3(256), 0, ex.stream, mom, 2 * lc, z.p, lc, Ml, lc); ex.rc = dmx_check_launch("dmx_slice_cast_kernel"); }
+    if (live()) ex.rc = dmx_slice_cast_launch(mom, 2 * lc, z.p, lc, Ml, lc, ex.stream);
     ex.drop(mom);
     z2 = ex.make(B, lh, lw, lc);
     if (live()) ex.rc = dmx_pointwise_small_fwd_launch(z.p, z.ld, T.W(v->pquant.w), v->pquant.kpad, T.F(v->pquant.b), z2.p, lc, Ml, lc, lc, 0, ex.stream);
@@ -240,7 +256,7 @@ struct VaeTrain {
     const int Ml = z.rows();
     // ---- post_quant_conv, mode(), quant_conv
     float* dz2f = (float*)ex.raw((size_t)Ml * lc * 4);
-    if (live()) { hipLaunchKernelGGL(dmx_bf16_to_f32_rows_kernel, dim3(cdiv(Ml * lc, 256)), dim3(256), 0, ex.stream, dz2.p, dz2.ld, dz2f, Ml, lc); ex.rc = dmx_check_launch("dmx_bf16_to_f32_rows_kernel"); }
+    if (live()) ex.rc = dmx_bf16_to_f32_rows_launch(dz2.p, dz2.ld, dz2f, Ml, lc, ex.stream);
     ex.drop(dz2);
     Tn dz = ex.make(z.B, z.H, z.W, lc);
     { const size_t wsb = dmx_pointwise_small_bwd_ws_bytes(Ml, 2 * lc, 2 * lc);
@@ -248,7 +264,7 @@ struct VaeTrain {
       if (live()) ex.rc = dmx_pointwise_small_bwd_launch(z.p, z.ld, dz2f, lc, T.W(v->pquant.w), v->pquant.kpad, dz.p, dz.ld,
                                                          T.G(v->pquant.w), v->pquant.kpad, T.G(v->pquant.b), Ml, lc, lc, ws, wsb, ex.stream);
       float* dmom = (float*)ex.raw((size_t)Ml * 2 * lc * 4);
-      if (live()) { hipLaunchKernelGGL(dmx_mode_bwd_kernel, dim3(cdiv(Ml * 2 * lc, 256)), dim3(256), 0, ex.stream, dz.p, dz.ld, dmom, Ml, lc); ex.rc = dmx_check_launch("dmx_mode_bwd_kernel"); }
+      if (live()) ex.rc = dmx_mode_bwd_launch(dz.p, dz.ld, dmom, Ml, lc, ex.stream);
       Tn dm8 = ex.make(m8.B, m8.H, m8.W, 2 * lc);
       if (live()) ex.rc = dmx_pointwise_small_bwd_launch(m8.p, m8.ld, dmom, 2 * lc, T.W(v->quant.w), v->quant.kpad, dm8.p, dm8.ld,
                                                          T.G(v->quant.w), v->quant.kpad, T.G(v->quant.b), Ml, 2 * lc, 2 * lc, ws, wsb, ex.stream);

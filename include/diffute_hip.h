@@ -58,6 +58,41 @@ int dmx_test_occupy_cus(int blocks, long long ticks, dmx_stream_t stream);
 const char* dmx_element_type(void);
 
 /* ------------------------------------------------------------------------------------
+ * Test support: the small kernels of the training graphs that have no operator-level entry (the W^T transposes, the
+ * gradient add, the row softmax and its backward of the VAE's single-head attention, the 1x1 convolutions between <= 8
+ * channels, the backward of the fp32 time-embedding linears, the casts around the posterior mode).  Each entry checks its
+ * arguments and forwards to the launch function the training graphs call; tests/test_train_small_gpu.py compares them with
+ * fp64.  "16" below is the build's 16-bit element; row strides (ld*) are in elements.
+ * ---------------------------------------------------------------------------------- */
+/* out[c][r] = in[r][c], 16-bit, R x C -> C x R */
+int dmx_test_transpose_bf16(const void* in, int ldin, void* out, int ldout, int R, int C, dmx_stream_t stream);
+/* the same for a list of jobs in ONE launch, as *_train_prepare runs its transposes.  `table`: device buffer of table_bytes
+ * (>= 40 * njobs, <= 81920) that receives the job table; the entry remembers the table it uploaded last and skips the upload
+ * when the next call's jobs are identical.  njobs = 0 (or another `table`) forgets it. */
+typedef struct dmx_test_tr_job { const void* in; int ldin; void* out; int ldout; int R, C; } dmx_test_tr_job;
+int dmx_test_transpose_batch(const dmx_test_tr_job* h_jobs, int njobs, void* table, size_t table_bytes, dmx_stream_t stream);
+/* out = a + b (16-bit, one fp32 add per element); C and the strides multiples of 8 */
+int dmx_test_add_bf16(const void* a, int lda, const void* b, int ldb, void* out, int ldo, int rows, int C, dmx_stream_t stream);
+/* p (16) = softmax(scale * s) along each row of the fp32 scores; ds (16) = scale * p o (dp - rowsum(dp o p)) */
+int dmx_test_softmax_rows(const float* s, int lds, void* p, int ldp, int rows, int n, float scale, dmx_stream_t stream);
+int dmx_test_softmax_bwd_rows(const void* p, int ldp, const float* dp, int lddp, void* ds, int ldds, int rows, int n, float scale, dmx_stream_t stream);
+/* y[m][o] = bias[o] + sum_i w[o][i] x[m][i], Cin, Cout <= 8; x, w 16-bit, bias fp32 or NULL, y fp32 (out_f32) or 16-bit.
+ * Backward: dx (16, or NULL) = dy w, dw[o][i] = sum_m dy[m][o] x[m][i], db[o] = sum_m dy[m][o]; dy, dw, db fp32 */
+int dmx_test_pointwise_small_fwd(const void* x, int ldx, const void* w, int ldw, const float* bias, void* y, int ldy, int M, int Cin, int Cout,
+                                 int out_f32, dmx_stream_t stream);
+size_t dmx_test_pointwise_small_bwd_workspace_bytes(int M, int Cin, int Cout);
+int dmx_test_pointwise_small_bwd(const void* x, int ldx, const float* dy, int lddy, const void* w, int ldw, void* dx, int lddx,
+                                 float* dw, int lddw, float* db, int M, int Cin, int Cout, void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+/* backward of y = w act(x) + b, act = SiLU when silu_in (dmx_linear_small): x [B][K], dy [B][N], dw [N][K], dx [B][K] fp32, w [N][K] 16-bit;
+ * dw (+)= dy^T act(x), db[n * db_stride] (+)= sum_b dy[b][n] (with dw only), dx = act'(x) o (dy w).  dw or dx may be NULL. */
+int dmx_test_linear_small_bwd(const float* x, int ldx, const float* dy, int lddy, const void* w, int ldw, float* dw, int lddw, float* db, int db_stride,
+                              float* dx, int lddx, int B, int N, int K, int silu_in, int accumulate, dmx_stream_t stream);
+/* out (16) [M][C] = in (fp32) [M][0:C]; dmom (fp32, dense [M][2C]) = (dz (16) | 0); out (fp32, dense [M][C]) = in (16) */
+int dmx_test_slice_cast(const float* in, int ldin, void* out, int ldo, int M, int C, dmx_stream_t stream);
+int dmx_test_mode_bwd(const void* dz, int lddz, float* dmom, int M, int C, dmx_stream_t stream);
+int dmx_test_bf16_to_f32_rows(const void* in, int ldin, float* out, int M, int C, dmx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Operator level.  Used by the parity tests and by the executors.
  * ---------------------------------------------------------------------------------- */
 

@@ -9,7 +9,7 @@ Every case (train_refs.py holds the case tables, the fp64 references and the bou
     deviation of torch float32 from fp64, never below 2^-20.  The recorded figures are train_floors.py's,
   * that every output element was written and nothing outside the logical output was (util.poisoned / assert_guard_intact),
   * where stated, bit-equality of two runs / of accumulate=1 with "previous + fresh".
-Each check prints `key:quantity whole <error>/<bound> slice <error>/<bound>` (pytest -rA shows them)."""
+Each check prints one line `key:quantity whole <error>/<bound> slice <error>/<bound>` (pytest -rA shows them)."""
 import pytest
 import torch
 
@@ -53,21 +53,21 @@ def assert_close_f64(hip, ref, tol, name=""):
 
 
 def check(key, qty, got):
-    """whole-tensor and per-slice parity of every quantity in `got` ({name: tensor in the reference's layout}); all figures are
-    printed, every miss is reported"""
+    """whole-tensor and per-slice parity of every quantity in `got` ({name: tensor in the reference's layout}); one line per
+    quantity with both figures, every miss is reported"""
     bounds = R.bounds(key, qty)
     misses = []
     for name, t in got.items():
         q = qty[name]; wt, st = bounds[name]
         t = host(t).reshape(q.ref.shape)
-        for fn, args, label in ((assert_close if q.kind == "16" else assert_close_f64, (t, q.whole_ref, wt, f"{key}:{name}"), "whole"),
-                                (assert_close_slices, (t, q.ref, st, q.dims, f"{key}:{name}"), "slice")):
+        fig = []
+        for fn, args in ((assert_close if q.kind == "16" else assert_close_f64, (t, q.whole_ref, wt, f"{key}:{name}")),
+                         (assert_close_slices, (t, q.ref, st, q.dims, f"{key}:{name}"))):
             try:
-                e = fn(*args)
-                print(f"{key}:{name} {label} {e:.3e}/{wt if label == 'whole' else st:.2e}")
+                fig.append(f"{fn(*args):.3e}")
             except AssertionError as ex:
-                print(f"MISS {ex}")
-                misses.append(str(ex))
+                fig.append("MISS"); misses.append(str(ex))
+        print(f"{key}:{name} whole {fig[0]}/{wt:.2e} slice {fig[1]}/{st:.2e}")
     assert not misses, "\n".join(misses)
 
 

@@ -26,7 +26,9 @@ def test_restatement_inside_bounds(key, thunk):
         wt, st = bounds[name]
         print(f"{key}:{name} restatement whole {w:.3e} (bound {wt:.2e}) slice {s:.3e} (bound {st:.2e})")
         assert torch.isfinite(q.model).all() and torch.isfinite(q.ref).all()
-        if q.kind == "16":
+        if q.kind == "x":
+            assert torch.equal(q.model, q.ref) and (wt, st) == (0.0, 0.0)        # compared bit for bit on the GPU: no tolerance
+        elif q.kind == "16":
             # the recorded floor is the measured one (the restatement is fp64 arithmetic + roundings: reproducible)
             assert abs(w - rw) <= 0.02 * rw + 1e-12 and abs(s - rs) <= 0.02 * rs + 1e-12, f"{key}:{name}: recorded ({rw:.3e}, {rs:.3e}), measured ({w:.3e}, {s:.3e})"
             assert w <= wt and s <= st / 3 * 1.02 or s <= q.base / 3, f"{key}:{name}: restatement outside its bound"
@@ -104,6 +106,50 @@ def test_injected_kernel_faults_are_caught():
     buf.view(torch.int16)[3, 8 + 192] = 0
     with pytest.raises(AssertionError, match="outside the output"):
         assert_guard_intact(buf, g)
+
+
+def test_injected_small_kernel_faults_are_caught():
+    """one fault per family of the small training kernels (test_train_small_gpu.py), of the kind its cases exist for.  Each is
+    confined to one column / one sample / one tile: the per-slice bound, the guard check or the bit comparison names it.  The
+    whole-tensor figure is printed next to the training-step bounds that were these kernels' only check before (whole-gradient
+    rel-L2 5e-2, worst parameter 1.5e-1): the figure of the one affected tensor is of that order, and a training step sees it
+    only after it has been mixed into every gradient upstream."""
+    for elem in ("bf16", "fp16"):
+        # the softmax loops stop after one pass of 256 threads: column 256 of an n = 257 row never enters the sum and is not stored
+        for fn, case, name in ((R.softmax_eval, ("gauss", 5, 257), "p"), (R.softmax_bwd_eval, (5, 257), "ds")):
+            key = ("softmax/gauss_5x257/" if name == "p" else "softmax_bwd/5x257/") + elem
+            _, good = fn(case, elem)
+            _, bad = fn(case, elem, fault="first_256")
+            wt, st = R.bounds(key, good)[name]
+            print(f"{key}: first-256 fault whole {rel_l2(bad[name].model, good[name].whole_ref):.3e}")
+            assert_close_slices(good[name].model, good[name].ref, st, good[name].dims, "unperturbed")
+            with pytest.raises(AssertionError, match=r"dim 1 is index 256"):
+                assert_close_slices(bad[name].model, good[name].ref, st, [1], "column 256 dropped")
+    # the dx kernel of linear_small_bwd tiles the batch in eights: the second tile (sample 9 of B = 9) missing
+    case = next(c for c in R.LSB_CASES if c[0] == 9 and c[5] == "both" and c[1] > 1)
+    key = f"lsb/{R.lsb_name(case)}/bf16"
+    _, good = R.lsb_eval(case, "bf16")
+    _, bad = R.lsb_eval(case, "bf16", fault="ninth_sample")
+    wt, st = R.bounds(key, good)["dx"]
+    print(f"{key}: ninth-sample fault whole {R.rel_l2_f64(bad['dx'].model, good['dx'].ref):.3e}")
+    assert_close_slices(good["dx"].model, good["dx"].ref, st, good["dx"].dims, "unperturbed")
+    with pytest.raises(AssertionError, match=r"dim 0 is index 8"):
+        assert_close_slices(bad["dx"].model, good["dx"].ref, st, [0], "ninth sample missing")
+    # batched transpose: the last ragged 64-tile of a job left unwritten.  Into a poisoned buffer the guard check says so; over
+    # the previous step's W^T (the product's situation: the weights moved by a few 1e-3 relative since) the whole
+    # tensor stays inside every tolerance this suite uses and only the bit comparison sees the stale tile
+    i = 2; Rr, C = R.TRB_JOBS[i][:2]                     # 65 x 63 -> out 63 x 65: the tile of output columns 64 .. 64
+    inputs, qty = R.transpose_batch_eval("bf16")
+    want = qty[f"out{i}"].ref.to(torch.bfloat16)
+    buf, out = poisoned((C, Rr), torch.bfloat16, "cpu")
+    out[:, :64] = want[:, :64]
+    with pytest.raises(AssertionError, match="never written"):
+        assert_guard_intact(buf, out)
+    stale = (want.double() * (1.0 + 3e-3 * seeded((C, Rr), 5).double())).to(torch.bfloat16)
+    out2 = want.clone(); out2[:, 64:] = stale[:, 64:]
+    assert not torch.equal(out2.view(torch.int16), want.view(torch.int16))
+    assert_close(out2, want.float(), 1e-3, "whole tensor over a stale tile")     # TOL_D does not notice
+    assert torch.equal(want.view(torch.int16), inputs["xs"][i].t().to(torch.bfloat16).contiguous().view(torch.int16))
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])

@@ -14,7 +14,8 @@ with  ref        the fp64 result,
                  oracle, else `ref`).
 Bounds (tol_of): kind "16": whole = base; slice = base, or 3 x the restatement's worst slice where that exceeds base / 3 (the
 restatement has the rounding points, not the MFMA accumulation order or the 1-ulp exp).  kind "32": 8 x the float32 torch
-deviation from fp64, never below 2^-20.  FLOORS records the measured restatement figures the bounds are computed from;
+deviation from fp64, never below 2^-20; kind "x" (the kernels that only move or cast: transposes, add, casts): the single torch
+operation, compared bit for bit - no tolerance.  FLOORS records the measured restatement figures the bounds are computed from;
 test_train_refs_host.py re-measures them."""
 import math
 from collections import namedtuple
@@ -49,6 +50,11 @@ def q32(ref, f32, dims):
     return Q(ref, f32.double(), "32", None, dims, ref)
 
 
+def qx(want):
+    """a bit-exact quantity: `want` holds the expected values (exactly representable in the output type)"""
+    return Q(want, want, "x", None, [0], want)
+
+
 def rel_l2_f64(a, b):
     """util.rel_l2 casts both sides to float32, which would measure an fp32 output against the ROUNDED fp64 reference: fp32
     quantities take their whole-tensor figure in double"""
@@ -66,6 +72,8 @@ def measure(q):
 def tol_of(q, floor):
     """(whole-tensor bound, per-slice bound) from the recorded floor (whole, slice)"""
     fw, fs = floor
+    if q.kind == "x":
+        return 0.0, 0.0
     if q.kind == "32":
         return max(8 * fw, 2.0 ** -20), max(8 * fs, 2.0 ** -20)
     return q.base, (q.base if fs <= q.base / 3 else 3 * fs)
@@ -271,6 +279,210 @@ def mse_eval(n):
     return dict(pred=p, target=t), {"loss": q32(loss, F.mse_loss(p.float(), t.float()).reshape(1), [0])}
 
 
+# ---------------------------------------------------------------------------------------------- the small training kernels
+# (test_train_small_gpu.py, through the dmx_test_* entries).  Bit-exact ones first: transposes, add, the casts of the posterior mode.
+TRANSPOSE_CASES = [(1, 1), (31, 33), (32, 32), (33, 31), (64, 4), (577, 130), (1280, 320)]      # the single kernel tiles 32 x 32
+
+
+def transpose_eval(case, elem):
+    x = inp(case, 1, elem)
+    return dict(x=x), {"out": qx(x.t().contiguous())}
+
+
+# one batch of the batched kernel (64 x 64 tiles; 16-byte accesses on a side whose stride is a multiple of 8 and whose base is
+# 16-byte aligned, element accesses otherwise):  R, C, ldin, ldout, input base offset, output base offset (elements past a
+# 16-byte boundary).  A one-tile job first and last: both ends of the bisection over the jobs' first tiles.
+TRB_JOBS = [
+    (64, 64, 72, 72, 0, 0),          # one tile, vector loads and stores
+    (63, 65, 72, 64, 0, 0),          # aligned strides, ragged both ways: vector body, element edges
+    (65, 63, 67, 69, 0, 0),          # odd ldin and ldout
+    (1, 200, 200, 8, 0, 0),          # one row: every vector store would be 7 elements too wide
+    (4, 320, 321, 8, 0, 0),          # odd ldin, vector-eligible output of 4 columns
+    (129, 7, 8, 133, 0, 1),          # 7 columns: vector-eligible input never has 8 to load; odd ldout, output base off by one
+    (320, 1280, 1288, 328, 3, 0),    # a real weight shape; input base off by three
+    (64, 64, 72, 72, 8, 8),
+    (63, 65, 72, 72, 1, 3),          # aligned strides, both bases off
+    (40, 24, 24, 40, 0, 0),          # one tile, last
+]
+
+
+def transpose_batch_eval(elem, jobs=None, seed=0):
+    jobs = TRB_JOBS if jobs is None else jobs
+    xs = [inp((j[0], j[1]), 10 + seed + i, elem) for i, j in enumerate(jobs)]
+    return dict(xs=xs), {f"out{i}": qx(x.t().contiguous()) for i, x in enumerate(xs)}
+
+
+ADD_CASES = [(1, 8), (3, 320), (4099, 1280), (16411, 1280)]      # the last: 2.6 M vectors > 8192 blocks x 256, the grid-stride loop turns
+
+
+def add_eval(case, elem):
+    a, b = inp(case, 1, elem), inp(case, 2, elem)
+    return dict(a=a, b=b), {"out": qx((a.float() + b.float()).to(ELEMS[elem]).double())}
+
+
+CAST_CASES = [(M, C) for M in (1, 257, 4096) for C in (4, 8)]
+
+
+def cast_eval(kind, case, elem):
+    M, C = case
+    if kind == "slice_cast":                       # z (16-bit) = the mean half of the fp32 moments [M][2C]
+        mom = seeded((M, 2 * C), 1).double()
+        return dict(x=mom), {"out": qx(mom[:, :C].float().to(ELEMS[elem]).double())}
+    dz = inp((M, C), 1, elem)
+    if kind == "mode_bwd":                         # dmom (fp32 [M][2C]) = (dz | 0)
+        return dict(x=dz), {"out": qx(torch.cat([dz.float(), torch.zeros(M, C)], 1).double())}
+    return dict(x=dz), {"out": qx(dz.float().double())}          # bf16_to_f32_rows
+
+
+CAST_KINDS = ("slice_cast", "mode_bwd", "bf16_to_f32_rows")
+
+# ---- row softmax (the VAE's single-head d = 512 attention: fp32 scores -> 16-bit P) and its backward
+SM_SCALE = float(torch.tensor(1.0 / math.sqrt(512.0), dtype=torch.float32))
+SM_N = (1, 63, 64, 255, 256, 257, 1000, 4096)            # one block of 256 threads per row: n < / = / > one pass of the loops
+SM_ROWS = (1, 5)
+SM_PATTERNS = ("gauss", "equal", "spike")
+SM_CASES = [(p, r, n) for p in SM_PATTERNS for r in SM_ROWS for n in SM_N]
+SMB_CASES = [(r, n) for r in SM_ROWS for n in SM_N]
+# the gradient-scaling case: scores 4 x as wide, so each row has a few P of 0.1 .. 0.9 and the dS that carry the row stay fp16
+# normals at GS_BASE x 1 (with P ~ 1 / n every dS of that factor, ~1e-6, would be a subnormal and its rounding would set the bound
+# of the larger factors too)
+SMB_GS_CASE = (5, 257, 4.0)
+
+
+def _scores(pattern, rows, n):
+    s = seeded((rows, n), 1) * math.sqrt(512.0)           # scaled scores ~ N(0, 1)
+    if pattern == "equal":
+        s = torch.full((rows, n), 3.25)
+    if pattern == "spike":                                # one score 1e4 above the rest (test_attention_reference_max_stress)
+        for r in range(rows):
+            s[r, (n - 1 - 97 * r) % n] = float(s[r].max()) + 1e4
+    return s.float().double()
+
+
+def softmax_eval(case, elem, fault=None):
+    pattern, rows, n = case
+    s = _scores(pattern, rows, n)
+    P = torch.softmax(s * SM_SCALE, -1)
+    model = rnd(P, elem)
+    if fault == "first_256":                              # the loops stop after their first pass: columns >= 256 never enter
+        model = torch.zeros_like(P); model[:, :256] = rnd(torch.softmax(s[:, :256] * SM_SCALE, -1), elem)
+    return dict(s=s), {"p": q16(P, model, TOL_D, [0, 1], True, elem)}
+
+
+def softmax_bwd_eval(case, elem, gscale=1.0, fault=None):
+    rows, n = case[:2]
+    sharp = case[2] if len(case) > 2 else 1.0
+    P = rnd(torch.softmax(_scores("gauss", rows, n) * SM_SCALE * sharp, -1), elem)       # the kernel's input: P as stored
+    dP = (seeded((rows, n), 2) * gscale).float().double()
+    dS = SM_SCALE * P * (dP - (P * dP).sum(-1, keepdim=True))
+    if gscale != 1.0:                                     # the 16-bit output must stay finite at the largest GradScaler factor
+        assert float(dS.abs().max()) / gscale * GS_BASE * GS_FACTORS[-1] < 65504.0
+    model = rnd(dS, elem)
+    if fault == "first_256":
+        model = torch.zeros_like(dS)
+        model[:, :256] = rnd(SM_SCALE * P[:, :256] * (dP[:, :256] - (P[:, :256] * dP[:, :256]).sum(-1, keepdim=True)), elem)
+    return dict(p=P, dp=dP), {"ds": q16(dS, model, TOL_D, [0, 1], True, elem)}
+
+
+# ---- 1x1 convolutions between <= 8 channels (quant_conv / post_quant_conv): one thread per row, 256 rows per block, the
+# per-block partials of dW / db folded by a second kernel
+PW_CH = [(4, 4), (8, 8), (8, 4), (3, 8), (1, 1)]
+PW_M = (1, 255, 256, 257, 4099)
+PW_CASES = [(ci, co, M) for ci, co in PW_CH for M in PW_M]
+PW_GS_CASE = (8, 4, 257)
+PW_LDW = 64                                               # the padded K of the real weights (1x1 conv: Cin rounded up to 64)
+
+
+def pw_eval(case, elem, gscale=1.0):
+    Cin, Cout, M = case
+    x = inp((M, Cin), 1, elem); w = inp((Cout, Cin), 2, elem, 1.0 / math.sqrt(Cin))
+    bias = (0.1 * seeded((Cout,), 3)).double()
+    dy = (seeded((M, Cout), 4) * gscale).float().double()
+    ynb = x @ w.t(); y = ynb + bias
+    ynb32 = x.float() @ w.float().t(); y32 = bias.float() + ynb32
+    dx = dy @ w
+    if gscale != 1.0:
+        assert float(dx.abs().max()) / gscale * GS_BASE * GS_FACTORS[-1] < 65504.0
+    row_ch = [0, 1]
+    qty = {"y16": q16(y, rnd(y, elem), TOL_D, row_ch, True, elem), "y32": q32(y, y32, row_ch),
+           "y16_nobias": q16(ynb, rnd(ynb, elem), TOL_D, row_ch, True, elem), "y32_nobias": q32(ynb, ynb32, row_ch),
+           "dx": q16(dx, rnd(dx, elem), TOL_D, row_ch, True, elem),
+           "dw": q32(dy.t() @ x, dy.float().t() @ x.float(), [0, 1]), "db": q32(dy.sum(0), dy.float().sum(0), [0])}
+    return dict(x=x, w=w, bias=bias, dy=dy), qty
+
+
+# ---- backward of the fp32 time-embedding linears y = W act(x) + b (M = batch): the dx kernel owns 8 columns k and up to 8
+# samples per block and splits N over 128 lanes; the dw kernel one row n and 256 columns k per block.
+#   B, N, K, silu_in, db_stride, which outputs
+LSB_CASES = [
+    (1, 1, 1, 0, 1, "both"), (1, 128, 8, 1, 1, "both"), (1, 127, 1283, 1, 1, "dx"),
+    (3, 127, 7, 0, 3, "both"), (3, 129, 9, 1, 1, "both"), (3, 1000, 1, 1, 1, "both"),
+    (8, 128, 320, 0, 1, "both"), (8, 1000, 1283, 1, 3, "both"), (8, 1, 1283, 0, 1, "both"),
+    (9, 127, 7, 1, 1, "both"), (9, 129, 9, 0, 3, "both"), (9, 1000, 320, 1, 1, "both"), (9, 1, 1, 0, 1, "both"),
+    (9, 128, 1283, 1, 1, "dx"), (9, 127, 9, 1, 3, "dw"), (9, 129, 7, 0, 1, "dx"),
+    (17, 127, 1283, 1, 3, "both"), (17, 129, 7, 0, 1, "both"), (17, 1000, 9, 1, 1, "both"), (17, 128, 8, 0, 1, "both"),
+    (17, 1, 320, 1, 1, "both"), (17, 1000, 1283, 0, 1, "dw"),
+]
+# SiLU on the input goes through the kernel's fast exponential: __expf(x) = v_exp_f32(fl(log2(e)) * x) - that much is the
+# compiler's own header (__clang_hip_math.h: `__expf` = `__builtin_amdgcn_exp2f(__log2_e * x)`).  The accuracy of v_exp_f32 is
+# taken as 1 ulp, i.e. a relative error <= 2^-23.  That figure is recalled from AMD's public CDNA3 instruction-set reference guide
+# (V_EXP_F32, "1 ULP accuracy"); no ISA document was at hand to check it against when this was written, so it is an assumption
+# of this bound, not a verified citation.  The argument carries the rounding of the constant (<= 2^-24 relative) and of the product
+# (<= 2^-24): |d arg| <= |arg| 2^-23, which the exponential turns into a relative error of ln(2) |arg| 2^-23 = |x| 2^-23.  So
+# exp(-x) is modelled with a relative error of at most (1 + |x|) 2^-23.
+EXP_REL = lambda x: (1.0 + x.abs()) * 2.0 ** -23
+
+
+def _silu_worst(x):
+    """(worst |error| of SiLU(x), worst |error| of SiLU'(x)) over both signs of the exponential's error, in fp64"""
+    e = torch.exp(-x); eta = EXP_REL(x)
+    def f(ee):
+        sg = 1.0 / (1.0 + ee)
+        return x * sg, sg * (1.0 + x * (1.0 - sg))
+    a0, d0 = f(e); ap, dp = f(e * (1 + eta)); am, dm = f(e * (1 - eta))
+    return torch.maximum((ap - a0).abs(), (am - a0).abs()), torch.maximum((dp - d0).abs(), (dm - d0).abs())
+
+
+def _away(v32, ref, mag):
+    """the float32 value pushed by `mag` in the direction that takes it further from the reference"""
+    v = v32.double()
+    sgn = torch.where(v >= ref, 1.0, -1.0).double()
+    return v + sgn * mag
+
+
+def lsb_eval(case, elem, fault=None):
+    B, N, K, silu, dbs, which = case
+    x = seeded((B, K), 1).float().double(); dy = seeded((B, N), 2).float().double()
+    w = inp((N, K), 3, elem, 1.0 / math.sqrt(K))
+    sig = torch.sigmoid(x)
+    act = x * sig if silu else x
+    dact = sig * (1 + x * (1 - sig)) if silu else torch.ones_like(x)
+    dw, db, g = dy.t() @ act, dy.sum(0), dy @ w
+    dx = dact * g
+    x32, dy32 = x.float(), dy.float()
+    sig32 = 1.0 / (1.0 + torch.exp(-x32))
+    act32 = x32 * sig32 if silu else x32
+    dact32 = sig32 * (1.0 + x32 * (1.0 - sig32)) if silu else torch.ones_like(x32)
+    dw32, g32 = dy32.t() @ act32, dy32 @ w.float()
+    dx32 = dact32 * g32
+    if silu:             # the float32 restatement with the exponential's documented error, signed against the reference
+        ea, ed = _silu_worst(x)
+        dw32 = _away(dw32, dw, dy.abs().t() @ ea)
+        dx32 = _away(dx32, dx, g32.double().abs() * ed)
+    if fault == "ninth_sample":                           # the second batch tile of the dx kernel never runs
+        dx32 = dx32.clone(); dx32[8:] = 0
+    qty = {}
+    if which != "dx":
+        qty["dw"] = q32(dw, dw32, [0, 1]); qty["db"] = q32(db, dy32.sum(0), [0])
+    if which != "dw":
+        qty["dx"] = q32(dx, dx32, [0, 1])
+    return dict(x=x, dy=dy, w=w), qty
+
+
+def lsb_name(c):
+    return f"b{c[0]}_n{c[1]}_k{c[2]}_silu{c[3]}_dbs{c[4]}_{c[5]}"
+
+
 # ---------------------------------------------------------------------------------------------- the table
 def all_cases():
     """(key, thunk) for every (family, case, element[, gradient-scaling]) the GPU tests run"""
@@ -290,6 +502,19 @@ def all_cases():
     out.append((f"conv/{CONV_GS_CASE[0]}/fp16/gs", lambda: conv_eval(CONV_GS_CASE, "fp16", GS_BASE)))
     out.append((f"colsum/{COLSUM_GS_CASE[0]}/fp16/gs", lambda: colsum_eval(COLSUM_GS_CASE, "fp16", GS_BASE)))
     for n in MSE_SIZES: out.append((f"mse/{n}", lambda n=n: mse_eval(n)))
+    # the small training kernels (test_train_small_gpu.py)
+    for elem in ("bf16", "fp16"):
+        for c in TRANSPOSE_CASES: out.append((f"transpose/{c[0]}x{c[1]}/{elem}", lambda c=c, e=elem: transpose_eval(c, e)))
+        out.append((f"transpose_batch/{elem}", lambda e=elem: transpose_batch_eval(e)))
+        for c in ADD_CASES: out.append((f"add/{c[0]}x{c[1]}/{elem}", lambda c=c, e=elem: add_eval(c, e)))
+        for k in CAST_KINDS:
+            for c in CAST_CASES: out.append((f"{k}/{c[0]}x{c[1]}/{elem}", lambda k=k, c=c, e=elem: cast_eval(k, c, e)))
+        for c in SM_CASES: out.append((f"softmax/{c[0]}_{c[1]}x{c[2]}/{elem}", lambda c=c, e=elem: softmax_eval(c, e)))
+        for c in SMB_CASES: out.append((f"softmax_bwd/{c[0]}x{c[1]}/{elem}", lambda c=c, e=elem: softmax_bwd_eval(c, e)))
+        for c in PW_CASES: out.append((f"pw/{c[0]}to{c[1]}_m{c[2]}/{elem}", lambda c=c, e=elem: pw_eval(c, e)))
+        for c in LSB_CASES: out.append((f"lsb/{lsb_name(c)}/{elem}", lambda c=c, e=elem: lsb_eval(c, e)))
+    out.append((f"softmax_bwd/{SMB_GS_CASE[0]}x{SMB_GS_CASE[1]}/fp16/gs", lambda: softmax_bwd_eval(SMB_GS_CASE, "fp16", GS_BASE)))
+    out.append((f"pw/{PW_GS_CASE[0]}to{PW_GS_CASE[1]}_m{PW_GS_CASE[2]}/fp16/gs", lambda: pw_eval(PW_GS_CASE, "fp16", GS_BASE)))
     return out
 
 

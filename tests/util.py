@@ -82,13 +82,14 @@ def poisoned(shape, dtype, dev, pad_rows=2, pad_cols=8):
 
 
 def assert_guard_intact(buf, view, sentinel=None, name=""):
-    """every element of `buf` outside `view` (any view into it) still holds the sentinel - nothing was written out of
-    range - and no element inside it does: every output element was written."""
+    """every element of `buf` outside `view` (any view into it, or a list of views) still holds the sentinel - nothing was
+    written out of range - and no element inside it does: every output element was written."""
     it, bits = SENTINEL_BITS[buf.dtype]
     bits = bits if sentinel is None else sentinel
     inside = torch.zeros(buf.numel(), dtype=torch.bool)
-    off = (view.data_ptr() - buf.data_ptr()) // buf.element_size()
-    torch.as_strided(inside, view.shape, view.stride(), off).fill_(True)
+    for v in (view if isinstance(view, (list, tuple)) else [view]):
+        off = (v.data_ptr() - buf.data_ptr()) // buf.element_size()
+        torch.as_strided(inside, v.shape, v.stride(), off).fill_(True)
     raw = buf.detach().cpu().contiguous().view(it).flatten()
     hit = (raw != bits) & ~inside
     if hit.any():
