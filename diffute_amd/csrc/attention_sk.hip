@@ -1,9 +1,11 @@
 // Balanced schedule of the head-dim-64 attention forward (attention.hip dmx_attn_d64_kernel<true, 1, 4>): stream-K over (query block, key tile) items.
 //
-// Why: the 64x64-level self-attention of the headline pass (B = 4, 5 heads, 4096 x 4096) is 640 blocks of 128 query rows on 768 block slots (three
-// 4-wave blocks per CU): half the SIMDs run three waves, half two, and the launch ends with the three-wave SIMDs (112.9 us against 121.0 us for
-// 768 blocks and 92.7 us for 512: EXPERIMENTS.md round 5).  Here the grid IS the 768 slots; slot k takes the global (query block, 64-key tile)
-// iterations [T k / 768, T (k + 1) / 768) - 53 or 54 of a query block's 64 tiles - so every SIMD carries the same 2.5 waves' worth of work.
+// Why: the plain grid of the 64x64-level self-attention (5 heads, 4096 x 4096: 160 blocks of 128 query rows per image) fills the 768 block slots
+// (three 4-wave blocks per CU) unevenly - at batch 1 - 3 most CUs hold one or two blocks or none; at batch 4, 640 blocks, half the SIMDs run three
+// waves, half two, and the launch ends with the three-wave SIMDs (112.9 us against 121.0 us for 768 blocks and 92.7 us for 512: EXPERIMENTS.md round 5).
+// Here the grid IS the 768 slots; slot k takes the global (query block, 64-key tile) iterations [T k / 768, T (k + 1) / 768), so every SIMD carries the
+// same work.  The plan (dmx_attention_balanced_slots) takes this schedule at batch 1 - 3 only: at the headline batch 4 (640 query blocks > 2 x CUs) it
+// measured a wash and the plain grid stays.
 //
 // A slot's range touches at most two query blocks (in general: a head part, whole blocks, a tail part).  The part that does NOT reach its query block's
 // last key tile is a HELPER part: it runs FIRST and publishes (O, m, l) of its keys - fp32, write-through, then a flag.  The parts that reach the last
@@ -18,10 +20,7 @@
 // bit-repeatable run to run (fixed split points, fixed fold order).
 #include "common.h"
 #include "kernels.h"
-
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
+#include "attention_d64.h"
 
 #define SK_PART_QUADS 9                     // per wave: 8 quads of O (32 floats per lane) + (m, l, -, -)
 #define SK_PART_BYTES (4 * SK_PART_QUADS * 64 * 16)      // per slot: 4 waves x 9 quads x 64 lanes x 16 B = 36 KB
@@ -280,11 +279,6 @@ __global__ __launch_bounds__(256, 3) void dmx_attn_d64_sk_kernel(const AttnArgs 
 static int g_attn_balanced = 1;            // dmx_set_attn_balanced: 0 never, 1 where the plan says it pays, 2 wherever the kernel takes the problem (tests)
 extern "C" int dmx_set_attn_balanced(int mode) { const int old = g_attn_balanced; g_attn_balanced = mode; dmx_plan_switch(DMX_SW_ATTN_BALANCED, mode); return old; }
 
-static int sk_n_cus() {
-  static int n = 0;
-  if (!n) { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) n = pr.multiProcessorCount; if (n <= 0) n = 256; }
-  return n;
-}
 // slots of the balanced schedule for this problem, 0 = the plain grid.  Measured (EXPERIMENTS.md round 6, profiles/r06_attn_balanced_probe.txt): a slot pays ~7 us
 // for its second prologue, the publish and the fold, and the slots lose the lock step that keeps a head's K / V tiles in L2.  That is a win where the plain
 // grid leaves CUs idle or with half the work of their neighbours (at most two blocks per CU: 4096 x 4096 at batch 1, 59.6 -> 40.7 us, batch 2, 82 -> 64 us), a wash at the headline shape
@@ -292,13 +286,13 @@ static int sk_n_cus() {
 int dmx_attention_balanced_slots(const AttnArgs& a) {
   if (!g_attn_balanced || !a.v || a.lse || a.Sq % 128 || a.B <= 0) return 0;
   const long long nqb = (long long)a.B * a.H * (a.Sq / 128), nt = (a.Skv + 63) / 64, T = nqb * nt;
-  const int ns = 3 * sk_n_cus();
+  const int ns = 3 * n_cus();                          // of the current device (conv_halo.hip)
   if (T < ns) return 0;
   if (g_attn_balanced >= 2) return ns;
   // (with other streams sharing the CUs - dmx_set_exclusive_device(0): micro-batches, a collective next to the step - the slots of a launch are not all
   // resident and the 8 slots at an XCD boundary would wait for blocks dispatched after them: correct (bounded, others retire), but not a plan to choose)
   if (!dmx_exclusive_device()) return 0;
-  if (nqb > 2 * sk_n_cus() || T / ns < 12) return 0;
+  if (nqb > 2 * n_cus() || T / ns < 12) return 0;
   return ns;
 }
 size_t dmx_attention_balanced_part_bytes(const AttnArgs& a) {

@@ -365,7 +365,8 @@ int dmx_attention_fwd_v(const void* q, int ldq, const void* k, int ldk, const vo
                         void* o, int ldo, int B, int H, int Sq, int Skv, float scale, dmx_stream_t stream);
 /* The same op on the BALANCED schedule (stream-K over (128-query block, 64-key tile) items on 3 x CUs block slots; a split row's (O, m, l) halves are
  * folded in a fixed order: bit-repeatable, equal to dmx_attention_fwd_v within the fp32 rounding of the fold).  The executors take it where the plain
- * grid fills the slots unevenly (the 4096 x 4096 self-attention of the 64x64 level at batch 4).  workspace_bytes = 0: the plan keeps the plain grid. */
+ * grid leaves at most two blocks per CU (the 4096 x 4096 self-attention of the 64x64 level at batch 1 - 3; at the headline batch 4 the plain grid
+ * stays).  workspace_bytes = 0: the plan keeps the plain grid. */
 size_t dmx_attention_fwd_v_balanced_workspace_bytes(int B, int H, int Sq, int Skv);
 int dmx_attention_fwd_v_balanced(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, int kv_rows,
                                  void* o, int ldo, int B, int H, int Sq, int Skv, float scale,
