@@ -184,13 +184,13 @@ def pack_ups_phase_weights(w3, N, Cin):
     return wp
 
 
-def conv_ups2x(x, wp, N, bias=None, force_tn=0, force_splitk=0):
+def conv_ups2x(x, wp, N, bias=None, force_tn=0, force_splitk=0, out=None):
     """conv3x3(nearest_x2(x)) through four 2x2 phase convolutions on the source grid.  x NHWC bf16 -> NHWC bf16 [B,2H,2W,N]."""
     B, H, W, Cin = x.shape
-    out = torch.empty(B, 2 * H, 2 * W, N, dtype=h16(), device=x.device)
+    out = _out(out, (B, 2 * H, 2 * W, N), h16(), x.device)
     wsb = lib().dmx_conv_ups2x_workspace_bytes(B, H, W, Cin, N, force_tn, force_splitk)
     ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=x.device)
-    check(lib().dmx_conv_ups2x(ptr(x), _ld(x), B, H, W, Cin, ptr(wp), N, ptr(bias) if bias is not None else None, ptr(out), N,
+    check(lib().dmx_conv_ups2x(ptr(x), _ld(x), B, H, W, Cin, ptr(wp), N, ptr(bias) if bias is not None else None, ptr(out), _ld(out),
                                force_tn, force_splitk, ptr(ws), wsb, current_stream()), "conv_ups2x")
     return out
 
@@ -311,13 +311,17 @@ def colsum(dy, groups=1, into=None, out=None, accumulate=None):
     return out
 
 
-def linear(x, w, bias=None, res=None, geglu=False, out_f32=False, act=0, force_tn=0, rowstats=False, ln=None, timing=None, dbg=0):
-    """x [..., K] bf16 (2-D view [rows][K]) @ w[N][K]^T."""
+def linear(x, w, bias=None, res=None, geglu=False, out_f32=False, act=0, force_tn=0, rowstats=False, ln=None, timing=None, dbg=0, out=None):
+    """x [..., K] bf16 (2-D view [rows][K]) @ w[N][K]^T.  `out`: write there ([rows][N] view, row stride from the tensor)."""
     K = x.shape[-1]
     x4 = x.reshape(1, 1, -1, K)
     r4 = None if res is None else res.reshape(1, 1, -1, res.shape[-1])
+    o4 = None
+    if out is not None:
+        assert out.dim() == 2 and out.stride(-1) == 1, "linear: out is a [rows][N] view"
+        o4 = out.as_strided((1, 1, out.shape[0], out.shape[1]), (0, 0, out.stride(0), 1))
     y = conv_gemm(x4, w, w.shape[0], ksize=1, pad=0, bias=bias, res=r4, geglu=geglu, out_f32=out_f32, act=act, force_tn=force_tn,
-                  rowstats=rowstats, ln=ln, timing=timing, dbg=dbg)
+                  rowstats=rowstats, ln=ln, timing=timing, dbg=dbg, out=o4)
     if rowstats:
         y, st = y
         return y.reshape(*x.shape[:-1], y.shape[-1]), st
@@ -325,19 +329,19 @@ def linear(x, w, bias=None, res=None, geglu=False, out_f32=False, act=0, force_t
 
 
 def xf_chain(mode, x, res, w0, b0, c1, c2, w1=None, wf1=None, wf2=None, bf2=None, wpo=None, bpo=None, xres=None, eps=1e-5, dbg=0, timing=None,
-             out_stats_rows=0, gn=None):
+             out_stats_rows=0, gn=None, h_out=None, y_out=None):
     """The row-local chains of a transformer block at the C = 320 levels, one launch each (include/diffute_hip.h dmx_xf_chain).
     x / res / xres [M][C]; returns (h_out, y).  out_stats_rows (mode 1): also return the statistics records of y, samples of that many
     rows.  gn = (st, gamma, beta, groups, rows_per_sample, eps) (mode 2): x is raw, GroupNorm from its records in the operand load."""
     M, C = x.shape
     d = _cabi.XfChainDesc()
-    h = torch.empty(M, C, dtype=h16(), device=x.device)
-    y = torch.empty(M, 3 * C if mode == 2 else C, dtype=h16(), device=x.device)
+    h = _out(h_out, (M, C), h16(), x.device)
+    y = _out(y_out, (M, 3 * C if mode == 2 else C), h16(), x.device)
     d.M, d.C, d.eps, d.dbg = M, C, float(eps), int(dbg)
     if timing is not None:
         d.timing = timing.data_ptr()
     d.x, d.ldx, d.res, d.ldres = ptr(x), _ld(x), ptr(res), (_ld(res) if res is not None else 0)
-    d.w0, d.b0, d.h_out, d.ldh, d.y, d.ldy = ptr(w0), ptr(b0), ptr(h), C, ptr(y), y.shape[1]
+    d.w0, d.b0, d.h_out, d.ldh, d.y, d.ldy = ptr(w0), ptr(b0), ptr(h), _ld(h), ptr(y), _ld(y)
     d.c1, d.c2 = ptr(c1), ptr(c2)
     keep = [x, res, w0, b0, c1, c2, w1, wf1, wf2, bf2, wpo, bpo, xres]
     if mode != 1:
@@ -357,14 +361,14 @@ def xf_chain(mode, x, res, w0, b0, c1, c2, w1=None, wf1=None, wf2=None, bf2=None
     return (h, y, cst) if out_stats_rows else (h, y)
 
 
-def groupnorm(x0, gamma, beta, groups, eps, silu, x1=None):
+def groupnorm(x0, gamma, beta, groups, eps, silu, x1=None, out=None):
     B, H, W, C0 = x0.shape
     C = C0 + (x1.shape[-1] if x1 is not None else 0)
-    y = torch.empty(B, H, W, C, dtype=h16(), device=x0.device)
+    y = _out(out, (B, H, W, C), h16(), x0.device)
     wsb = lib().dmx_groupnorm_workspace_bytes(B, H * W, groups)
     ws = torch.empty(wsb, dtype=torch.uint8, device=x0.device)
     check(lib().dmx_groupnorm(ptr(x0), _ld(x0), ptr(x1), _ld(x1) if x1 is not None else 0, C0, C, groups, B, H * W,
-                              ptr(gamma), ptr(beta), float(eps), int(silu), ptr(y), C, ptr(ws), wsb, current_stream()), "groupnorm")
+                              ptr(gamma), ptr(beta), float(eps), int(silu), ptr(y), _ld(y), ptr(ws), wsb, current_stream()), "groupnorm")
     return y
 
 
@@ -383,7 +387,7 @@ def colstats(x):
 
 
 def conv3x3_gn(x0, w, N, *, x1=None, gn=None, st0=None, st1=None, sc0=None, sc1=None, bias=None, rowbias=None, res=None,
-               out_stats=False, force_split=0, force_bn=0, force_waves=0, timing=None, dbg=0):
+               out_stats=False, force_split=0, force_bn=0, force_waves=0, timing=None, dbg=0, out=None):
     """conv3x3 (stride 1, pad 1) over a halo tile staged in LDS, with GroupNorm(+SiLU) applied to the staged tile in place
     (dmx_conv3x3_gn).  gn = (gamma, beta, groups, eps, silu) with st0 / st1 the statistics records of x0 / x1, or None for a plain
     conv.  Returns out, or (out, records of out) with out_stats."""
@@ -410,8 +414,8 @@ def conv3x3_gn(x0, w, N, *, x1=None, gn=None, st0=None, st1=None, sc0=None, sc1=
         d.rowbias = rowbias.data_ptr(); d.ldrb = rowbias.stride(0)
     if res is not None:
         d.res = res.data_ptr(); d.ldres = _ld(res)
-    out = torch.empty(B, H, W, N, dtype=h16(), device=x0.device)
-    d.out = out.data_ptr(); d.ldo = N
+    out = _out(out, (B, H, W, N), h16(), x0.device)
+    d.out = out.data_ptr(); d.ldo = _ld(out)
     cst = None
     if out_stats:
         cst = torch.zeros(B, N, 4, dtype=torch.int64, device=x0.device)
@@ -440,7 +444,7 @@ def skinny_pack(w, segs):
     return wp
 
 
-def skinny_conv(segs, wp, N, *, gn=None, bias=None, rowbias=None, res=None, out_stats=False, force_S=0, timing=None, dbg=0):
+def skinny_conv(segs, wp, N, *, gn=None, bias=None, rowbias=None, res=None, out_stats=False, force_S=0, timing=None, dbg=0, out=None):
     """Weight-streaming conv / linear for M = B H W <= 256 rows (dmx_skinny_conv).  segs: list of dicts x=[B,H,W,C] tensor, taps=9|1, and for
     GroupNorm'ed sources st= statistics records, gamma=, beta= (this tensor's channels), gn_c0=; gn = (groups, Ctot, eps, silu) of the norm
     over the concatenation of those sources.  Returns out [B,H,W,N] (and the statistics records of out with out_stats)."""
@@ -466,8 +470,8 @@ def skinny_conv(segs, wp, N, *, gn=None, bias=None, rowbias=None, res=None, out_
         d.rowbias = rowbias.data_ptr(); d.ldrb = rowbias.stride(0)
     if res is not None:
         d.res = res.data_ptr(); d.ldres = _ld(res)
-    out = torch.empty(B, H, W, N, dtype=h16(), device=x0.device)
-    d.out = out.data_ptr(); d.ldo = N
+    out = _out(out, (B, H, W, N), h16(), x0.device)
+    d.out = out.data_ptr(); d.ldo = _ld(out)
     cst = None
     if out_stats:
         cst = torch.zeros(B, N, 4, dtype=torch.int64, device=x0.device)
@@ -483,13 +487,13 @@ def skinny_conv(segs, wp, N, *, gn=None, bias=None, rowbias=None, res=None, out_
     return (out, cst) if out_stats else out
 
 
-def groupnorm_from_stats(x0, st0, gamma, beta, groups, eps, silu, x1=None, st1=None):
+def groupnorm_from_stats(x0, st0, gamma, beta, groups, eps, silu, x1=None, st1=None, out=None):
     """GroupNorm (+SiLU) whose statistics were emitted by the GEMM(s) that produced x0 / x1 (conv_gemm(..., gn_stats=True))"""
     B, H, W, C0 = x0.shape
     C = C0 + (x1.shape[-1] if x1 is not None else 0)
-    y = torch.empty(B, H, W, C, dtype=h16(), device=x0.device)
+    y = _out(out, (B, H, W, C), h16(), x0.device)
     check(lib().dmx_groupnorm_from_stats(ptr(x0), _ld(x0), ptr(x1), _ld(x1) if x1 is not None else 0, C0, C, groups, B, H * W,
-                                         ptr(gamma), ptr(beta), float(eps), int(silu), ptr(st0), ptr(st1), ptr(y), C, current_stream()),
+                                         ptr(gamma), ptr(beta), float(eps), int(silu), ptr(st0), ptr(st1), ptr(y), _ld(y), current_stream()),
           "groupnorm_from_stats")
     return y
 
@@ -559,51 +563,55 @@ def geglu_bwd(h, dy, dx=None):
     return dh
 
 
-def layernorm(x, gamma, beta, eps=1e-5):
+def layernorm(x, gamma, beta, eps=1e-5, out=None):
+    """x / out are [..., rows, C] views whose row strides are taken from the tensors (leading dims must collapse onto that stride)"""
     C = x.shape[-1]
     rows = x.numel() // C
-    y = torch.empty_like(x)
-    check(lib().dmx_layernorm(ptr(x), C, ptr(y), C, ptr(gamma), ptr(beta), rows, C, float(eps), current_stream()), "layernorm")
+    y = _out(out, tuple(x.shape), h16(), x.device)
+    for t in (x, y):
+        assert t.stride(-1) == 1 and all(t.stride(i) == t.stride(i + 1) * t.shape[i + 1] for i in range(t.dim() - 2)), \
+            "layernorm: the leading dimensions must collapse into rows of one stride"
+    check(lib().dmx_layernorm(ptr(x), _ld(x) if x.dim() > 1 else C, ptr(y), _ld(y) if y.dim() > 1 else C, ptr(gamma), ptr(beta), rows, C, float(eps), current_stream()), "layernorm")
     return y
 
 
-def attention(q, k, vt, B, H, Sq, Skv, scale, kv_rows=None, skv_stride=None):
+def attention(q, k, vt, B, H, Sq, Skv, scale, kv_rows=None, skv_stride=None, out=None):
     """q [B*Sq, >=H*64], k [B*kv_rows, >=H*64], vt [H*64, >= B*skv_stride] (2-D, row-major views)."""
-    o = torch.empty(B * Sq, H * 64, dtype=h16(), device=q.device)
+    o = _out(out, (B * Sq, H * 64), h16(), q.device)
     kv_rows = Skv if kv_rows is None else kv_rows
     skv_stride = Skv if skv_stride is None else skv_stride
     check(lib().dmx_attention_fwd(ptr(q), q.stride(0), ptr(k), k.stride(0), kv_rows, ptr(vt), vt.stride(0), skv_stride,
-                                  ptr(o), H * 64, B, H, Sq, Skv, float(scale), current_stream()), "attention_fwd")
+                                  ptr(o), o.stride(0), B, H, Sq, Skv, float(scale), current_stream()), "attention_fwd")
     return o
 
 
-def attention_v(q, k, v, B, H, Sq, Skv, scale, kv_rows=None):
+def attention_v(q, k, v, B, H, Sq, Skv, scale, kv_rows=None, out=None):
     """q [B*Sq, >=H*64], k / v [B*kv_rows, >=H*64] row-major 2-D views (V read through LDS transpose reads)."""
-    o = torch.empty(B * Sq, H * 64, dtype=h16(), device=q.device)
+    o = _out(out, (B * Sq, H * 64), h16(), q.device)
     kv_rows = Skv if kv_rows is None else kv_rows
     check(lib().dmx_attention_fwd_v(ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), kv_rows,
-                                    ptr(o), H * 64, B, H, Sq, Skv, float(scale), current_stream()), "attention_fwd_v")
+                                    ptr(o), o.stride(0), B, H, Sq, Skv, float(scale), current_stream()), "attention_fwd_v")
     return o
 
 
-def attention_v_balanced(q, k, v, B, H, Sq, Skv, scale, kv_rows=None):
+def attention_v_balanced(q, k, v, B, H, Sq, Skv, scale, kv_rows=None, out=None):
     """attention_v on the balanced schedule (attention_sk.hip); None when the plan keeps the plain grid for this problem (dmx_set_attn_balanced)"""
     wsb = lib().dmx_attention_fwd_v_balanced_workspace_bytes(B, H, Sq, Skv)
     if not wsb:
         return None
-    o = torch.empty(B * Sq, H * 64, dtype=h16(), device=q.device)
+    o = _out(out, (B * Sq, H * 64), h16(), q.device)
     ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
     kv_rows = Skv if kv_rows is None else kv_rows
     check(lib().dmx_attention_fwd_v_balanced(ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), kv_rows,
-                                             ptr(o), H * 64, B, H, Sq, Skv, float(scale), ptr(ws), wsb, current_stream()), "attention_fwd_v_balanced")
+                                             ptr(o), o.stride(0), B, H, Sq, Skv, float(scale), ptr(ws), wsb, current_stream()), "attention_fwd_v_balanced")
     return o
 
 
-def attention_wide(q, k, v, B, Sq, Skv, D, scale, kv_rows=None):
+def attention_wide(q, k, v, B, Sq, Skv, D, scale, kv_rows=None, out=None):
     """single head of width D (128 / 256 / 512): q [B*Sq, >=D], k / v [B*kv_rows, >=D] row-major 2-D views -> [B*Sq, D]"""
-    o = torch.empty(B * Sq, D, dtype=h16(), device=q.device)
+    o = _out(out, (B * Sq, D), h16(), q.device)
     check(lib().dmx_attention_wide(ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), Skv if kv_rows is None else kv_rows,
-                                   ptr(o), D, B, Sq, Skv, D, float(scale), current_stream()), "attention_wide")
+                                   ptr(o), o.stride(0), B, Sq, Skv, D, float(scale), current_stream()), "attention_wide")
     return o
 
 
@@ -657,10 +665,10 @@ def timestep_embedding(t, freq, B, dim):
     return out
 
 
-def linear_small(x, w, bias=None, silu_in=False):
+def linear_small(x, w, bias=None, silu_in=False, out=None):
     B, K = x.shape
     N = w.shape[0]
-    y = torch.empty(B, N, dtype=torch.float32, device=x.device)
-    check(lib().dmx_linear_small(ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(y), N, B, N, K, int(silu_in),
+    y = _out(out, (B, N), torch.float32, x.device)
+    check(lib().dmx_linear_small(ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(y), y.stride(0), B, N, K, int(silu_in),
                                  current_stream()), "linear_small")
     return y

@@ -52,10 +52,11 @@ def assert_close_f64(hip, ref, tol, name=""):
     return e
 
 
-def check(key, qty, got):
+def check(key, qty, got, bounds=None):
     """whole-tensor and per-slice parity of every quantity in `got` ({name: tensor in the reference's layout}); one line per
-    quantity with both figures, every miss is reported"""
-    bounds = R.bounds(key, qty)
+    quantity with both figures, every miss is reported.  `bounds`: {name: (whole, slice)}, train_refs.bounds by default
+    (test_fwd_layout_gpu.py passes fwd_refs.bounds)"""
+    bounds = R.bounds(key, qty) if bounds is None else bounds
     misses = []
     for name, t in got.items():
         q = qty[name]; wt, st = bounds[name]
