@@ -95,6 +95,17 @@ class TestTrJob(ctypes.Structure):
     _fields_ = [("in_", c_void_p), ("ldin", c_int), ("out", c_void_p), ("ldout", c_int), ("R", c_int), ("C", c_int)]
 
 
+class EditItem(ctypes.Structure):
+    """dmx_edit_item (include/diffute_hip.h): one text box of dmx_preprocess_crop_batch / dmx_postprocess_paste_batch.  The caller sets the
+    first seven fields, dmx_edit_items_prepare fills the rest."""
+    _fields_ = [("x1", c_int), ("y1", c_int), ("x2", c_int), ("y2", c_int), ("x_s", c_int), ("y_s", c_int), ("crop_scale", c_int),
+                ("cw", c_int), ("ch", c_int), ("pre_area2", c_int), ("post_area2", c_int), ("reserved", c_int),
+                ("pre_sx", ctypes.c_double), ("pre_sy", ctypes.c_double), ("post_sx", ctypes.c_double), ("post_sy", ctypes.c_double)]
+
+
+EDIT_MAX_ITEMS = 64      # DMX_EDIT_MAX_ITEMS
+
+
 class VAEConfig(ctypes.Structure):
     _fields_ = [("in_channels", c_int), ("out_channels", c_int), ("latent_channels", c_int),
                 ("block_out_channels", c_int * 4), ("layers_per_block", c_int), ("norm_num_groups", c_int)]
@@ -260,6 +271,9 @@ _PROTOS = {
     "dmx_mask_rasterize": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "dmx_preprocess_crop": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "dmx_postprocess_paste": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "dmx_edit_items_prepare": (c_int, [_P, c_int, c_int, c_int, c_int]),
+    "dmx_preprocess_crop_batch": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+    "dmx_postprocess_paste_batch": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, _P, _P, c_int, _P]),
     "dmx_glyph_max_taps": (c_int, []),
     "dmx_glyph_resize_normalize": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "dmx_gemm_plan_override": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),

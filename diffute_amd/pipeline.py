@@ -6,9 +6,10 @@ DPM-Solver++; the latter keeps its multistep history in fixed per-chain buffers)
 context K/V are projected once per image, timesteps live on the device, nothing synchronises
 with the host inside the loop.
 """
+import numpy as np
 import torch
 
-from . import _cabi
+from . import _cabi, prepost
 from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
 
 
@@ -170,3 +171,53 @@ def edit_latents(unet, vae, scheduler, image, masked_image, mask, encoder_hidden
                                    generator=torch.manual_seed(0), dtype=torch.float32).to(masked_image.device)  # :798
     lat = denoise(unet, scheduler, init_latents, m, mlat, encoder_hidden_states, num_inference_steps, variance_noise=variance_noise)
     return vae.decode(lat / sf).sample                                                    # app.ipynb:818-819
+
+
+@torch.no_grad()
+def edit_boxes(unet, vae, scheduler, instance_image, locations, encoder_hidden_states, num_inference_steps, *, origins=None,
+               crop_scales=None, rng=None, batch_size=4, generator=None, enc_noise=None, variance_noise=None,
+               return_intermediate=False, size=512):
+    """text_editing() (app.ipynb:674-846) for several boxes of ONE image as one batch: instance_image uint8 CUDA [h][w][3], locations
+    N boxes (x1, y1, x2, y2), encoder_hidden_states [N,L,D] the glyph context of each box.  One preprocess_batch launch, the boxes
+    through edit_latents in chunks of `batch_size` (the last chunk may be smaller), one postprocess_batch launch; returns the uint8
+    [h][w][3] result, with return_intermediate=True also image_vae [N,3,S,S] and the preprocess dict.
+
+    origins / crop_scales: N crop origins (x_s, y_s) / crop sides; what is not given comes from the reference's ladder and origin rule
+    (prepost.plan_edits), random origins drawn from `rng` (default numpy's global state) in box order.  Every box starts from the
+    reference's seed-0 [1,4,h,w] draw (app.ipynb:796-801), not from row b of a [N,...] draw: a box edited in a batch starts where a
+    single call starts it.  enc_noise [N,4,h,w] / variance_noise [steps,N,4,h,w] inject the device-RNG draws as in edit_latents.
+
+    Difference from N sequential text_editing() calls: every crop is taken from the ORIGINAL image, so box k's context does not contain
+    the edits of boxes < k.  The pastes are identical (a later box wins where boxes overlap)."""
+    locations = list(locations)
+    N = len(locations)
+    if int(batch_size) < 1:
+        raise ValueError("batch_size must be at least 1")
+    if not isinstance(instance_image, torch.Tensor) or instance_image.dim() != 3:
+        raise TypeError("instance_image: expected a contiguous uint8 CUDA tensor [h][w][3]")
+    h, w = int(instance_image.shape[0]), int(instance_image.shape[1])
+    if crop_scales is None:
+        crop_scales = [prepost.crop_scale_for(loc, h, w) for loc in locations]
+    crop_scales = list(crop_scales)
+    if origins is None:
+        if len(crop_scales) != N:
+            raise ValueError(f"{N} boxes, {len(crop_scales)} crop scales: the lengths must agree")
+        origins = [prepost.crop_origin(loc, cs, w, rng if rng is not None else np.random) for loc, cs in zip(locations, crop_scales)]
+    if encoder_hidden_states.shape[0] != N:
+        raise ValueError(f"{N} boxes but {encoder_hidden_states.shape[0]} glyph contexts")
+    pre = prepost.preprocess_batch(instance_image, locations, origins, crop_scales, size=size)
+    f = 2 ** (len(vae.config.block_out_channels) - 1)
+    S = int(size)
+    # app.ipynb:796-801: ONE seed-0 draw of a single sample, shared by every box
+    init = torch.randn((1, vae.config.latent_channels, S // f, S // f), generator=torch.manual_seed(0), dtype=torch.float32).to(instance_image.device)
+    outs = []
+    for lo in range(0, N, int(batch_size)):
+        hi = min(N, lo + int(batch_size))
+        outs.append(edit_latents(unet, vae, scheduler, pre["image"][lo:hi], pre["masked_image"][lo:hi], pre["mask"][lo:hi],
+                                 encoder_hidden_states[lo:hi], num_inference_steps,
+                                 init_latents=init.expand(hi - lo, -1, -1, -1).contiguous(), generator=generator,
+                                 enc_noise=None if enc_noise is None else enc_noise[lo:hi],
+                                 variance_noise=None if variance_noise is None else variance_noise[:, lo:hi]))
+    image_vae = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+    out = prepost.postprocess_batch(image_vae, instance_image, locations, origins, crop_scales)
+    return (out, image_vae, pre) if return_intermediate else out

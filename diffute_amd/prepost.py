@@ -2,6 +2,8 @@
 functions (app.ipynb:370-383 mask, :674-720 crop ladder / origin, :722-745 resize + normalise, :776-779 latent mask,
 :825-846 paste-back) over the HIP kernels in csrc/prepost.hip.  The uint8 image is uploaded once; the three network inputs
 come out of one kernel and the result is pasted back by another - no PIL / cv2 / albumentations and no second PCIe hop."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -81,3 +83,90 @@ def postprocess(image_vae, instance_image, location, x_s, y_s, crop_scale):
     _cabi.check(_cabi.lib().dmx_postprocess_paste(_cabi.ptr(v), int(v.shape[-1]), _cabi.ptr(img), _cabi.ptr(out), h, w, int(x_s), int(y_s),
                                                  int(crop_scale), x1, y1, x2, y2, _cabi.current_stream()), "postprocess_paste")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ several boxes of one image per launch
+def plan_edits(locations, h, w, rng=np.random):
+    """crop_scale_for + crop_origin for every box of one h x w image: [(x_s, y_s, crop_scale), ...].  Boxes that need a random origin draw
+    from `rng` in box order, so a seeded rng gives what one text_editing() call per box would draw."""
+    plans = []
+    for loc in locations:
+        crop_scale = crop_scale_for(loc, h, w)
+        x_s, y_s = crop_origin(loc, crop_scale, w, rng)
+        plans.append((x_s, y_s, crop_scale))
+    return plans
+
+
+def _check_items(locations, origins, crop_scales):
+    """the list half of the batched functions' arguments, checked before anything touches a tensor"""
+    locations, origins, crop_scales = list(locations), list(origins), list(crop_scales)
+    B = len(locations)
+    if B == 0:
+        raise ValueError("no boxes: the batched pre/post-processing needs at least one")
+    if B > _cabi.EDIT_MAX_ITEMS:
+        raise ValueError(f"{B} boxes in one launch, at most {_cabi.EDIT_MAX_ITEMS}")
+    if len(origins) != B or len(crop_scales) != B:
+        raise ValueError(f"{B} boxes, {len(origins)} origins, {len(crop_scales)} crop scales: the lengths must agree")
+    return locations, origins, crop_scales
+
+
+def _upload_items(locations, origins, crop_scales, h, w, S, dev):
+    """the dmx_edit_item table of one launch: filled and validated in pinned memory, then ONE asynchronous copy on the current stream.
+    Returns (host table, its pinned storage, device table): the entry reads the host table, the kernel the device one."""
+    B = len(locations)
+    nbytes = B * ctypes.sizeof(_cabi.EditItem)
+    stage = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+    host = (_cabi.EditItem * B).from_buffer(stage.numpy())
+    for it, loc, (x_s, y_s), crop_scale in zip(host, locations, origins, crop_scales):
+        it.x1, it.y1, it.x2, it.y2 = (int(v) for v in loc[:4])
+        it.x_s, it.y_s, it.crop_scale = int(x_s), int(y_s), int(crop_scale)
+    _cabi.check(_cabi.lib().dmx_edit_items_prepare(host, B, h, w, S), "edit_items_prepare")
+    table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        table.copy_(stage, non_blocking=True)
+    return host, stage, table
+
+
+def preprocess_batch(instance_image, locations, origins, crop_scales, size=512):
+    """B boxes of one image in one launch.  instance_image: uint8 CUDA tensor [h][w][3]; locations: B boxes (x1, y1, x2, y2); origins: B
+    crop origins (x_s, y_s); crop_scales: B crop sides (plan_edits gives the last two).  Returns dict(image, masked_image: fp32
+    [B,3,S,S] in [-1,1]; mask: uint8 [B,1,S,S]; mask_latent: fp32 [B,1,S/8,S/8]); row b equals preprocess() of box b, whose mask holds
+    that box alone.  No [h][w] mask is built."""
+    locations, origins, crop_scales = _check_items(locations, origins, crop_scales)
+    img = _u8(instance_image, "instance_image")
+    h, w, c = img.shape
+    if c != 3:
+        raise ValueError("instance_image must be HWC with 3 channels")
+    dev, B, S = img.device, len(locations), int(size)
+    host, stage, table = _upload_items(locations, origins, crop_scales, h, w, S, dev)
+    with torch.cuda.device(dev):
+        image = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+        masked = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+        mask = torch.empty(B, 1, S, S, dtype=torch.uint8, device=dev)
+        mask_lat = torch.empty(B, 1, S // 8, S // 8, dtype=torch.float32, device=dev)
+        _cabi.check(_cabi.lib().dmx_preprocess_crop_batch(_cabi.ptr(img), h, w, host, _cabi.ptr(table), B, S, _cabi.ptr(image), _cabi.ptr(masked),
+                                                         _cabi.ptr(mask), _cabi.ptr(mask_lat), _cabi.current_stream()), "preprocess_crop_batch")
+    return dict(image=image, masked_image=masked, mask=mask, mask_latent=mask_lat)
+
+
+def postprocess_batch(image_vae, instance_image, locations, origins, crop_scales, return_mask=False):
+    """image_vae: fp32 CUDA [B,3,S,S] decoder outputs in [-1,1], one per box; returns the uint8 [h][w][3] image that B chained
+    postprocess() calls in box order leave (a later box wins where boxes overlap), in one launch.  return_mask=True also returns the
+    union of the boxes as uint8 [h][w] in {0, 1} (the app shows mask * 255)."""
+    locations, origins, crop_scales = _check_items(locations, origins, crop_scales)
+    img = _u8(instance_image, "instance_image")
+    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
+        raise TypeError("image_vae: expected a CUDA tensor")
+    h, w, _ = img.shape
+    B = len(locations)
+    if image_vae.dim() != 4 or tuple(image_vae.shape[:2]) != (B, 3) or image_vae.shape[2] != image_vae.shape[3]:
+        raise ValueError(f"image_vae must be [{B},3,S,S]: one square 3-channel image per box")
+    v = image_vae.to(torch.float32).contiguous()
+    dev, S = img.device, int(v.shape[-1])
+    host, stage, table = _upload_items(locations, origins, crop_scales, h, w, S, dev)
+    with torch.cuda.device(dev):
+        out = torch.empty_like(img)
+        union = torch.empty(h, w, dtype=torch.uint8, device=dev) if return_mask else None
+        _cabi.check(_cabi.lib().dmx_postprocess_paste_batch(_cabi.ptr(v), S, _cabi.ptr(img), _cabi.ptr(out), _cabi.ptr(union), h, w, host,
+                                                           _cabi.ptr(table), B, _cabi.current_stream()), "postprocess_paste_batch")
+    return (out, union) if return_mask else out

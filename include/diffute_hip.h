@@ -577,6 +577,39 @@ int dmx_preprocess_crop(const unsigned char* image_hwc, const unsigned char* mas
 int dmx_postprocess_paste(const float* image_vae, int S, const unsigned char* original_hwc, unsigned char* out_hwc, int H, int W,
                           int x_s, int y_s, int crop_scale, int x1, int y1, int x2, int y2, dmx_stream_t stream);
 
+/* Several text boxes of ONE image in one launch each way (1 <= B <= DMX_EDIT_MAX_ITEMS, H <= 65535).  The geometry of the
+ * boxes travels as a table of dmx_edit_item, not as kernel arguments.  The caller fills box, origin and crop_scale of every
+ * item, lets edit_items_prepare validate them and fill the derived fields (the host arithmetic of the single-box entries:
+ * extent clipped at the border, scales as doubles, the exact-2x flags), and copies the table to the device in stream order
+ * (one asynchronous copy from pinned memory) before the launch.  Both entries take the host table and its device copy: the
+ * host table is checked again, item by item, exactly like the arguments of the single-box entries - a bad item is reported
+ * by index through the last-error string and nothing is launched -, the kernels read the device copy (trusted to hold the same
+ * bytes; they clamp every origin / extent to the image, so a stale table reads wrong pixels, never outside).
+ *   preprocess_crop_batch:  row b of out_image / out_masked_image fp32 [B][3][S][S], out_mask uint8 [B][1][S][S] and
+ *                     out_mask_latent fp32 [B][1][S/8][S/8] (may be NULL) is what preprocess_crop writes for item b with the
+ *                     mask mask_rasterize draws for item b's box alone (both corners included).  The mask is a predicate
+ *                     inside the kernel: no [H][W] buffer, no rasterise launch.
+ *   postprocess_paste_batch: image_vae fp32 [B][3][S][S]; out_hwc is what B chained postprocess_paste calls in index order
+ *                     leave (where boxes overlap the later item wins; a pixel no item covers is copied).  union_mask
+ *                     (may be NULL) uint8 [H][W]: 1 where the inclusive box of any item covers the pixel. */
+#define DMX_EDIT_MAX_ITEMS 64
+typedef struct dmx_edit_item {
+  int x1, y1, x2, y2;               /* text box */
+  int x_s, y_s, crop_scale;         /* crop origin and side */
+  int cw, ch;                       /* derived: crop extent clipped at the image border */
+  int pre_area2, post_area2;        /* derived: the crop is exactly 2S x 2S / exactly S/2 x S/2 */
+  int reserved;
+  double pre_sx, pre_sy;            /* derived: cw / S, ch / S */
+  double post_sx, post_sy;          /* derived: S / cw, S / ch */
+} dmx_edit_item;
+int dmx_edit_items_prepare(dmx_edit_item* items, int B, int H, int W, int S);
+int dmx_preprocess_crop_batch(const unsigned char* image_hwc, int H, int W, const dmx_edit_item* items_host, const dmx_edit_item* items_device,
+                              int B, int S, float* out_image, float* out_masked_image, unsigned char* out_mask, float* out_mask_latent,
+                              dmx_stream_t stream);
+int dmx_postprocess_paste_batch(const float* image_vae, int S, const unsigned char* original_hwc, unsigned char* out_hwc,
+                                unsigned char* union_mask, int H, int W, const dmx_edit_item* items_host,
+                                const dmx_edit_item* items_device, int B, dmx_stream_t stream);
+
 /* The image half of TrOCRProcessor (`processor(images=ttf_imgs, return_tensors="pt").pixel_values`, app.ipynb:773,
  * train_diffute_v1.py:868; a ViT image processor: PIL resize, rescale, normalise): ONE launch turns a ragged batch of uint8
  * 3-channel images into out_pixel_values fp32 [B][3][S_h][S_w], bit for bit what Pillow's 8-bit Image.resize (Resample.c as
