@@ -220,6 +220,17 @@ _PROTOS = {
     "dmx_trocr_dec_linear_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dmx_trocr_dec_linear": (c_int, [c_int, c_int, _P, c_int, c_int, _P, c_int, _P, c_float, _P, c_int, _P, _P, _P, _P,
                                      _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "dmx_trocr_dec_beam_cache_bytes": (c_size_t, [_P, c_int, c_int, c_int, c_int]),
+    "dmx_trocr_dec_beam_workspace_bytes": (c_size_t, [_P, c_int, c_int, c_int, c_int]),
+    "dmx_trocr_dec_beam_state_offset": (c_size_t, [_P, c_int, c_int, c_int, c_int]),
+    "dmx_trocr_dec_beam_state_bytes": (c_size_t, [c_int]),
+    "dmx_trocr_dec_beam_launches_per_step": (c_int, [_P]),
+    "dmx_trocr_dec_beam_begin": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "dmx_trocr_dec_beam_step": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P, _P, c_size_t, _P]),
+    "dmx_trocr_dec_beam_finalize": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "dmx_trocr_dec_beam_select_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dmx_trocr_dec_beam_select": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "dmx_trocr_dec_beam_attn": (c_int, [_P, c_int, c_int, _P, c_int64, c_int, c_int, _P, c_int, c_int, _P, _P, c_size_t, _P]),
     "dmx_trocr_dec_attn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dmx_trocr_dec_attn": (c_int, [_P, c_int, c_int, _P, c_int64, c_int, c_int, _P, _P, c_size_t, _P]),
     "dmx_unet_context_bytes": (c_size_t, [_P, c_int, c_int]),
@@ -291,6 +302,9 @@ _PROTOS = {
     "dmx_vae_decode": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
 }
 # the model lifecycle every handle shares (DMX_MODEL_ABI in include/diffute_hip.h); the UNet's finalize also takes the frequency table
+# words of the decoder's beam state block (include/diffute_hip.h DMX_TROCR_BEAM_*)
+BEAM_RUN_SCORE, BEAM_FIN_SCORE, BEAM_FIN_FLAG, BEAM_FIN_LEN, BEAM_IMPROVABLE, BEAM_PARENT, BEAM_STEPS, BEAM_WORDS = 0, 64, 128, 192, 256, 320, 580, 640
+
 for _kind, _cfg in (("unet", UNetConfig), ("vae", VAEConfig), ("vit", ViTConfig), ("trocr_dec", TrOCRDecConfig)):
     _PROTOS.update({
         f"dmx_{_kind}_create": (_P, [POINTER(_cfg)]),

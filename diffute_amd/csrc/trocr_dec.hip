@@ -13,6 +13,9 @@
 //   dec_attn    - one query row per (b, head), d = 64, split over 64-key chunks; the last chunk block combines in chunk order.
 //   dec_embed   - token + position (+ scale) + layernorm_embedding, token and position read from device memory.
 // Per step: 1 + 8 per layer + 1 launches; the counters reset themselves, so one captured graph replays every step.
+// Beam search (rows = items x beams) runs the same step with an LM head that writes fp32 logits + log-sum-exp partials, one
+//   beam_select launch (top 2 x beams candidates per item, running / finished bookkeeping, loop condition) and an ancestry table through which
+//   the self-attention reads the never-reordered K/V cache: 1 + 8 per layer + 2 launches.
 #include <math.h>
 #include <memory>
 #include <string>
@@ -21,10 +24,15 @@
 #include "../../include/diffute_hip.h"
 
 namespace {
-enum { EPI_STORE = 0, EPI_QKV = 1, EPI_LN = 2, EPI_PICK = 3 };
+enum { EPI_STORE = 0, EPI_QKV = 1, EPI_LN = 2, EPI_PICK = 3, EPI_BEAM = 4 };
 enum { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2 };
 // state words at the start of the cache (DMX_TROCR_STATE_* in the header)
 enum { ST_POS = 0, ST_DONE = 1, ST_STOP = 2, ST_TOK = 16, ST_FIN = 16 + 64, ST_INTS = 256 };
+// beam state block (DMX_TROCR_BEAM_* in the header): int32 / fp32 words, then the token history int32 [max_len][64], the
+// finished ids int32 [64][max_len] and the two ancestry tables uint8 [2][64][max_len]
+enum { BS_RUN = 0, BS_FSC = 64, BS_FFLAG = 128, BS_FLEN = 192, BS_IMPR = 256, BS_PARENT = 320, BS_FULL = 384, BS_HIT = 448,
+       BS_CNT = 512, BS_STEPS = 580, BS_WORDS = 640 };
+constexpr int kBeamMaxK = 32, kBeamLds = 8192, kBeamEntries = kBeamLds / 2;
 
 struct DecLin {
   const bf16* x; int ldx;            // [M][K]
@@ -43,6 +51,8 @@ struct DecLin {
   const float* res; float* pre; const float* gamma; const float* beta; float eps;
   // EPI_PICK: per-block partials [M][gridDim.x], then the greedy pick into state / ids
   float* pv; int* pi; long long* ids; int max_len, eos, pad;
+  // EPI_BEAM: logits -> yf; per-block (max, sum exp(x - max)) -> pv, psum [M][gridDim.x]
+  float* psum;
 };
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -311,6 +321,47 @@ __global__ __launch_bounds__(256) void dmx_dec_linear_kernel(DecLin a) {
     }
     return;
   }
+  if (a.epi == EPI_BEAM) {
+    // fp32 logits, and per (row, 64-feature block) the block maximum and sum exp(x - max): the row's log-sum-exp follows from
+    // the partials in block order (beam_row_lse), without a second pass over the weights
+    __shared__ float bm_s[4][64], bs_s[4][64];
+    float bmx[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      const int m = t * 16 + r;
+      float mx = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int n = n0 + 4 * g + i;
+        if (m < a.M && n < a.N) { a.yf[(size_t)m * a.ldyf + n] = acc[t][i]; mx = fmaxf(mx, acc[t][i]); }
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 16)); mx = fmaxf(mx, __shfl_xor(mx, 32));
+      if (g == 0) bm_s[wv][t * 16 + r] = mx;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      const int m = t * 16 + r;
+      bmx[t] = fmaxf(fmaxf(bm_s[0][m], bm_s[1][m]), fmaxf(bm_s[2][m], bm_s[3][m]));
+      float sm = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int n = n0 + 4 * g + i;
+        if (m < a.M && n < a.N && bmx[t] != -INFINITY) sm += expf(acc[t][i] - bmx[t]);
+      }
+      sm += __shfl_xor(sm, 16); sm += __shfl_xor(sm, 32);
+      if (g == 0) bs_s[wv][m] = sm;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < a.M) {
+      const int m = threadIdx.x;
+      const float mx = fmaxf(fmaxf(bm_s[0][m], bm_s[1][m]), fmaxf(bm_s[2][m], bm_s[3][m]));
+      const float sm = ((bs_s[0][m] + bs_s[1][m]) + bs_s[2][m]) + bs_s[3][m];
+      wt_store(wt_rsrc(a.pv, (size_t)a.M * gridDim.x * 4), (size_t)m * gridDim.x + nb, mx);
+      wt_store(wt_rsrc(a.psum, (size_t)a.M * gridDim.x * 4), (size_t)m * gridDim.x + nb, sm);
+    }
+    return;
+  }
   const int pos = a.epi == EPI_QKV ? a.state[ST_POS] : 0;
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
@@ -346,13 +397,24 @@ struct DecAttn {
   int M, H, D, nch;
   float* part; int* cnt;             // [M][H][nch][66]; [M*H]
   bf16* o; int ldo;
+  // beam search: key j < pos of row b lies in physical row src[b * src_ld + j] of the table half (pos & 1) (pos = state[ST_POS];
+  // without state pos = L - 1 and the table is the first half), key pos in row b itself; rpi > 0: row b reads the K/V of item
+  // b / rpi (cross-attention)
+  const unsigned char* src; int src_ld, rpi;
 };
 
 __global__ __launch_bounds__(64) void dmx_dec_attn_kernel(DecAttn a) {
   const int lane = threadIdx.x, c = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int L = a.state ? min(a.state[ST_POS] + 1, a.L) : a.L;
-  const bf16* kb = a.kv + (size_t)b * a.bstride + h * 64;
   const int j0 = c * 64, nvalid = max(0, min(64, L - j0));
+  // physical row of this lane's key
+  int prow = a.rpi > 0 ? b / a.rpi : b;
+  if (a.src && lane < nvalid) {
+    const int pos = a.state ? a.state[ST_POS] : a.L - 1;
+    const size_t half = a.state ? (size_t)(pos & 1) * 64 * a.src_ld : 0;
+    if (j0 + lane < pos) prow = a.src[half + (size_t)b * a.src_ld + j0 + lane];
+  }
+  const bf16* kb = a.kv + (size_t)prow * a.bstride + h * 64;
   float s = -INFINITY;
   if (lane < nvalid) {
     const float* q = a.q + (size_t)b * a.ldq + h * 64;
@@ -377,7 +439,9 @@ __global__ __launch_bounds__(64) void dmx_dec_attn_kernel(DecAttn a) {
 #pragma unroll
   for (int u = 0; u < 8; ++u) {
     const int jj = u * 8 + kg;
-    vv[u] = jj < nvalid ? *(const u32x4*)(kb + a.D + (size_t)(j0 + jj) * a.rstride + dg * 8) : (u32x4){0u, 0u, 0u, 0u};
+    const int pr = __shfl(prow, jj);
+    vv[u] = jj < nvalid ? *(const u32x4*)(a.kv + (size_t)pr * a.bstride + h * 64 + a.D + (size_t)(j0 + jj) * a.rstride + dg * 8)
+                        : (u32x4){0u, 0u, 0u, 0u};
   }
 #pragma unroll
   for (int u = 0; u < 8; ++u) {
@@ -475,12 +539,241 @@ __global__ __launch_bounds__(256) void dmx_i64_to_i32_kernel(const long long* in
   if (i < n) out[i] = (int)in[i];
 }
 
+// ---- beam search: selection + bookkeeping of one step in one launch (transformers' GenerationMixin._beam_search, do_sample=False,
+// no logits processors, one eos id, decoder prompt length 1)
+struct BeamSel {
+  const float* logits; int ldl;      // [M][V] fp32, M = B * nb rows (row = item * nb + beam)
+  const float* pmax; const float* psum; int nblk;   // per (row, 64-feature block): max, sum exp(x - max)
+  int B, nb, V, K, chunk, C, max_len, eos, early;   // K = 2 nb; early: 0 False, 1 True, 2 "never"
+  float lp;                          // length_penalty
+  int* state; int* bs;               // the state words; the beam state block
+  float* cv; int* ci;                // chunk candidates [M][C][K]: accumulated score, token
+  float* logp;                       // nullable [M][V]: the log-probs the selection used
+};
+__device__ __forceinline__ int* beam_hist(int* bs) { return bs + BS_WORDS; }
+__device__ __forceinline__ int* beam_fin_ids(int* bs, int max_len) { return bs + BS_WORDS + (size_t)max_len * 64; }
+__device__ __forceinline__ unsigned char* beam_src(int* bs, int max_len) { return (unsigned char*)(bs + BS_WORDS + (size_t)max_len * 128); }
+
+// the K best of s_val[0, n) in the order rule (larger first, equal values -> lower index, NaN never wins), best first, into
+// ov / oi (LDS); the index of entry i is s_idx[i], or i.  Winners leave s_val as NaN; a slot nothing could fill holds (NaN, INT_MAX)
+__device__ void block_topk(float* s_val, const int* s_idx, int n, int K, float* ov, int* oi) {
+  __shared__ float r_v[4];
+  __shared__ int r_i[4], r_p[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int it = 0; it < K; ++it) {
+    float bv = -INFINITY; int bi = 0x7fffffff, bp = -1;
+    for (int i = threadIdx.x; i < n; i += 256) {
+      const float v = s_val[i]; const int id = s_idx ? s_idx[i] : i;
+      if (pick_better(v, id, bv, bi)) { bv = v; bi = id; bp = i; }
+    }
+#pragma unroll
+    for (int d = 1; d <= 32; d <<= 1) {
+      const float xv = __shfl_xor(bv, d); const int xi = __shfl_xor(bi, d), xp = __shfl_xor(bp, d);
+      if (pick_better(xv, xi, bv, bi)) { bv = xv; bi = xi; bp = xp; }
+    }
+    if (lane == 0) { r_v[wv] = bv; r_i[wv] = bi; r_p[wv] = bp; }
+    __syncthreads();
+    bv = r_v[0]; bi = r_i[0]; bp = r_p[0];
+    for (int w = 1; w < 4; ++w) if (pick_better(r_v[w], r_i[w], bv, bi)) { bv = r_v[w]; bi = r_i[w]; bp = r_p[w]; }
+    if (threadIdx.x == 0) { ov[it] = bp >= 0 ? bv : NAN; oi[it] = bp >= 0 ? bi : 0x7fffffff; }
+    if (bp >= 0 && (bp & 255) == (int)threadIdx.x) s_val[bp] = NAN;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void dmx_dec_beam_select_kernel(BeamSel a) {
+  __shared__ float s_buf[kBeamLds];
+  __shared__ float s_tv[kBeamMaxK], s_cand[kBeamMaxK], s_pen[kBeamMaxK], s_mv[kBeamMaxK + 16], s_nsc[16], s_red[4];
+  __shared__ int s_ti[kBeamMaxK], s_par[kBeamMaxK], s_tok[kBeamMaxK], s_hit[kBeamMaxK], s_mf[kBeamMaxK + 16];
+  __shared__ int s_newpar[16], s_fsrc[16], s_nfl[16], s_nln[16], s_oln[16];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int c = blockIdx.x, m = blockIdx.y, nb = a.nb, b = m / nb, V = a.V, K = a.K;
+  int* st = a.state; int* bs = a.bs;
+  if (st[ST_DONE]) {                                             // the search has ended: later replays change nothing
+    if (c == 0 && m == 0 && tid == 0) bs[BS_STEPS] += 1;
+    return;
+  }
+  const int pos = st[ST_POS], cur = pos + 1;                     // cur: tokens so far
+  // the row's log-sum-exp from the LM head's block partials, in block order
+  const float* pm = a.pmax + (size_t)m * a.nblk; const float* ps = a.psum + (size_t)m * a.nblk;
+  float mx = -INFINITY;
+  for (int i = tid; i < a.nblk; i += 256) mx = fmaxf(mx, pm[i]);
+  mx = wave_max(mx);
+  if (lane == 0) s_red[wv] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+  __syncthreads();
+  float sm = 0.f;
+  for (int i = tid; i < a.nblk; i += 256) { const float v = pm[i]; sm += v == -INFINITY ? 0.f : ps[i] * expf(v - mx); }
+  sm = wave_sum(sm);
+  if (lane == 0) s_red[wv] = sm;
+  __syncthreads();
+  const float lse = mx + logf(((s_red[0] + s_red[1]) + s_red[2]) + s_red[3]);
+  // this chunk's accumulated scores: running score + (logit - lse), one fp32 add
+  const float rs = ((const float*)bs)[BS_RUN + m];
+  const int n0 = c * a.chunk, n = max(0, min(a.chunk, V - n0));
+  for (int i = tid; i < n; i += 256) {
+    const float lpv = a.logits[(size_t)m * a.ldl + n0 + i] - lse;
+    if (a.logp) a.logp[(size_t)m * V + n0 + i] = lpv;
+    s_buf[i] = lpv + rs;
+  }
+  __syncthreads();
+  block_topk(s_buf, nullptr, n, K, s_tv, s_ti);
+  const size_t ncand = (size_t)a.B * nb * a.C * K;
+  const __amdgpu_buffer_rsrc_t rcv = wt_rsrc(a.cv, ncand * 4), rci = wt_rsrc(a.ci, ncand * 4);
+  if (tid < K) {
+    const size_t q = ((size_t)m * a.C + c) * K + tid;
+    wt_store(rcv, q, s_tv[tid]);
+    wt_store_i(rci, q, s_ti[tid] == 0x7fffffff ? 0x7fffffff : n0 + s_ti[tid]);
+  }
+  if (!last_arrival(bs + BS_CNT + b, nb * a.C)) return;
+
+  // ---- the item's last block: merge nb x C sorted lists, then the step's bookkeeping
+  const int ne = nb * a.C * K;
+  float* e_v = s_buf; int* e_i = (int*)(s_buf + kBeamEntries);
+  for (int i = tid; i < ne; i += 256) {
+    const size_t q = (size_t)b * ne + i;
+    const float v = wt_load(rcv, q); const int id = wt_load_i(rci, q);
+    const bool ok = id != 0x7fffffff;
+    e_v[i] = ok ? v : NAN; e_i[i] = ok ? (i / (a.C * K)) * V + id : 0x7fffffff;
+  }
+  __syncthreads();
+  block_topk(e_v, e_i, ne, K, s_tv, s_ti);
+  float* rsv = (float*)bs + BS_RUN + b * nb; float* fsc = (float*)bs + BS_FSC + b * nb;
+  int* ffl = bs + BS_FFLAG + b * nb; int* fln = bs + BS_FLEN + b * nb;
+  int* hist = beam_hist(bs); int* fin = beam_fin_ids(bs, a.max_len);
+  const unsigned char* told = beam_src(bs, a.max_len) + (size_t)(pos & 1) * 64 * a.max_len;
+  unsigned char* tnew = beam_src(bs, a.max_len) + (size_t)((pos + 1) & 1) * 64 * a.max_len;
+  if (tid == 0) {
+    int allhit = 1;
+    for (int i = 0; i < K; ++i) {
+      float v = s_tv[i]; int fl = s_ti[i];
+      if (fl == 0x7fffffff || fl < 0) { v = -INFINITY; fl = 0; }   // (only with NaN logits: keep the ids in range)
+      const int tk = fl % V;
+      const int hit = (tk == a.eos) || (cur + 1 >= a.max_len);
+      s_cand[i] = v; s_par[i] = fl / V; s_tok[i] = tk; s_hit[i] = hit; allhit &= hit;
+      s_pen[i] = hit ? v + -1.0e9f : v;
+    }
+    // the next running beams: top nb of the penalised candidates
+    unsigned taken = 0;
+    for (int r = 0; r < nb; ++r) {
+      float bv = -INFINITY; int bi = 0x7fffffff;
+      for (int i = 0; i < K; ++i) if (!((taken >> i) & 1)) pick_merge(bv, bi, s_pen[i], i);
+      if (bi == 0x7fffffff) for (int i = K - 1; i >= 0; --i) if (!((taken >> i) & 1)) bi = i;
+      taken |= 1u << bi;
+      const int row = b * nb + r, prow = b * nb + s_par[bi];
+      rsv[r] = s_pen[bi]; bs[BS_PARENT + row] = prow; s_newpar[r] = prow; st[ST_TOK + row] = s_tok[bi];
+      if (cur < a.max_len) hist[(size_t)cur * 64 + row] = s_tok[bi];
+    }
+    // the finished set: [nb finished | K candidates] -> top nb
+    const float div = (float)pow((double)cur, (double)a.lp);
+    int full = 1;
+    for (int j = 0; j < nb; ++j) { full &= (ffl[j] != 0); s_mv[j] = fsc[j]; s_mf[j] = ffl[j]; s_oln[j] = fln[j]; }
+    const int impr = bs[BS_IMPR + b];
+    for (int i = 0; i < K; ++i) {
+      float sc = s_cand[i] / div;
+      if (full && a.early == 1) sc += -1.0e9f;
+      if (!impr) sc += -1.0e9f;
+      const int fini = s_hit[i] && i < nb;
+      if (!fini) sc += -1.0e9f;
+      s_mv[nb + i] = sc; s_mf[nb + i] = fini;
+    }
+    unsigned long long tk2 = 0;
+    for (int j = 0; j < nb; ++j) {
+      float bv = -INFINITY; int bi = 0x7fffffff;
+      for (int i = 0; i < nb + K; ++i) if (!((tk2 >> i) & 1)) pick_merge(bv, bi, s_mv[i], i);
+      if (bi == 0x7fffffff) for (int i = nb + K - 1; i >= 0; --i) if (!((tk2 >> i) & 1)) bi = i;
+      tk2 |= 1ull << bi;
+      s_fsrc[j] = bi; s_nsc[j] = s_mv[bi]; s_nfl[j] = s_mf[bi]; s_nln[j] = bi < nb ? s_oln[bi] : cur;
+    }
+    float mn = INFINITY; int full2 = 1;
+    for (int j = 0; j < nb; ++j) { fsc[j] = s_nsc[j]; ffl[j] = s_nfl[j]; mn = fminf(mn, s_nsc[j]); full2 &= (s_nfl[j] != 0); }
+    // can the running beams still improve on the finished ones?
+    const int hl = (a.early == 2 && a.lp > 0.f) ? a.max_len - 1 : cur;
+    const float best = rsv[0] / (float)pow((double)hl, (double)a.lp);
+    int any = 0;
+    for (int j = 0; j < nb; ++j) any |= best > (s_nfl[j] ? mn : -1.0e9f);
+    const __amdgpu_buffer_rsrc_t rb = wt_rsrc(bs, (size_t)BS_WORDS * 4);
+    wt_store_i(rb, BS_IMPR + b, impr && any); wt_store_i(rb, BS_FULL + b, full2); wt_store_i(rb, BS_HIT + b, allhit);
+  }
+  __syncthreads();
+  // ancestry of the new rows: the parent's row of every earlier position, then the parent itself (the other half of the table)
+  for (int i = tid; i < nb * cur; i += 256) {
+    const int r = i / cur, j = i % cur, p = s_newpar[r];
+    tnew[(size_t)(b * nb + r) * a.max_len + j] = j < pos ? told[(size_t)p * a.max_len + j] : (unsigned char)p;
+  }
+  // finished ids, in place: an old slot only moves down, so the slots are filled from the last one up
+  for (int j = nb - 1; j >= 0; --j) {
+    const int mi = s_fsrc[j];
+    int* dst = fin + (size_t)(b * nb + j) * a.max_len;
+    if (mi < nb) {
+      if (mi != j) {
+        const int* src = fin + (size_t)(b * nb + mi) * a.max_len;
+        for (int i = tid; i <= min(s_oln[mi], a.max_len - 1); i += 256) dst[i] = src[i];
+      }
+    } else {
+      const int p = b * nb + s_par[mi - nb];
+      for (int i = tid; i <= pos; i += 256) dst[i] = hist[(size_t)i * 64 + (i < pos ? told[(size_t)p * a.max_len + i] : p)];
+      if (tid == 0 && cur < a.max_len) dst[cur] = s_tok[mi - nb];
+    }
+    __syncthreads();
+  }
+  if (tid < nb) fln[tid] = s_nln[tid];
+  if (!last_arrival(bs + BS_CNT + 64, a.B)) return;
+  if (tid == 0) {                                               // the whole batch's loop condition
+    const __amdgpu_buffer_rsrc_t rb = wt_rsrc(bs, (size_t)BS_WORDS * 4);
+    int any_impr = 0, all_full = 1, all_hit = 1;
+    for (int i = 0; i < a.B; ++i) {
+      any_impr |= wt_load_i(rb, BS_IMPR + i); all_full &= wt_load_i(rb, BS_FULL + i); all_hit &= wt_load_i(rb, BS_HIT + i);
+    }
+    const int go = any_impr && !(all_full && a.early == 1) && !all_hit;
+    if (!go) { st[ST_DONE] = 1; st[ST_STOP] = cur + 1; }
+    st[ST_POS] = pos + 1;
+    bs[BS_STEPS] += 1;
+  }
+}
+
+// per (row, 64-feature block) maximum and sum exp(x - max) of supplied logits (the op entry; the decoder's LM head writes them itself)
+__global__ __launch_bounds__(64) void dmx_dec_beam_partials_kernel(const float* logits, int ldl, int V, int nblk, float* pmax, float* psum) {
+  const int lane = threadIdx.x, blk = blockIdx.x, m = blockIdx.y, n = blk * 64 + lane;
+  const float x = n < V ? logits[(size_t)m * ldl + n] : -INFINITY;
+  const float mx = wave_max(x);
+  const float e = (n < V && mx != -INFINITY) ? expf(x - mx) : 0.f;
+  const float sm = wave_sum(e);
+  if (lane == 0) { pmax[(size_t)m * nblk + blk] = mx; psum[(size_t)m * nblk + blk] = sm; }
+}
+
+// cache words zeroed with every row's input = start; beam state: running scores [0, -1e9, ...], finished scores -1e9, every
+// item improvable, position 0 of the history and of every finished slot = start
+__global__ __launch_bounds__(256) void dmx_dec_beam_reset_kernel(int* words, size_t nwords, int M, int nb, int start, int* bs, size_t bwords, int max_len) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x, i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (size_t i = i0; i < nwords; i += stride) words[i] = (i >= ST_TOK && i < (size_t)ST_TOK + M) ? start : 0;
+  const size_t fin0 = (size_t)BS_WORDS + (size_t)max_len * 64, fin1 = fin0 + (size_t)max_len * 64;
+  for (size_t i = i0; i < bwords; i += stride) {
+    int v = 0;
+    if (i < (size_t)BS_RUN + 64) v = (int)__float_as_uint((i - BS_RUN) % nb == 0 ? 0.f : -1.0e9f);
+    else if (i < (size_t)BS_FSC + 64) v = (int)__float_as_uint(-1.0e9f);
+    else if (i >= BS_IMPR && i < (size_t)BS_IMPR + 64) v = 1;
+    else if (i >= BS_WORDS && i < (size_t)BS_WORDS + 64) v = start;
+    else if (i >= fin0 && i < fin1 && (i - fin0) % max_len == 0) v = start;
+    bs[i] = v;
+  }
+}
+// the first nret finished slots of every item: ids (pad beyond the hypothesis), score, generated length
+__global__ __launch_bounds__(64) void dmx_dec_beam_gather_kernel(int* bs, int nb, int nret, int max_len, int pad, long long* seq, float* scores, int* lens) {
+  const int o = blockIdx.x, b = o / nret, slot = b * nb + o % nret;
+  const int len = min(bs[BS_FLEN + slot], max_len - 1);
+  const int* fin = beam_fin_ids(bs, max_len) + (size_t)slot * max_len;
+  for (int i = threadIdx.x; i < max_len; i += 64) seq[(size_t)o * max_len + i] = i <= len ? fin[i] : pad;
+  if (threadIdx.x == 0) { scores[o] = ((const float*)bs)[BS_FSC + slot]; lens[o] = len; }
+}
+
 int dec_linear_launch(const DecLin& a, hipStream_t stream) {
   const int nblk = cdiv(a.N, 64);
   DMX_REQUIRE(a.M >= 1 && a.M <= 64 && a.K % 128 == 0 && a.kchunk % 128 == 0 && a.ldw % 8 == 0 && a.ldx % 8 == 0,
               "dec_linear: M=%d K=%d kchunk=%d", a.M, a.K, a.kchunk);
   DMX_REQUIRE(a.splits == cdiv(a.K, a.kchunk), "dec_linear: splits %d != K / kchunk", a.splits);
-  DMX_REQUIRE(a.epi != EPI_PICK || a.splits == 1, "dec_linear: the pick epilogue runs unsplit");
+  DMX_REQUIRE((a.epi != EPI_PICK && a.epi != EPI_BEAM) || a.splits == 1, "dec_linear: the pick / beam epilogues run unsplit");
   DMX_REQUIRE(a.splits == 1 || a.N % 4 == 0, "dec_linear: a split plan needs N %% 4 == 0 (16-byte partial runs)");
   DMX_REQUIRE(a.epi != EPI_LN || (a.N % 256 == 0 && a.N <= 1024), "dec_linear: LayerNorm epilogue needs N %% 256 == 0, N <= 1024");
   const dim3 grid(nblk, a.splits);
@@ -500,7 +793,7 @@ constexpr int kLaunchesPerLayer = 8;
 
 // split-K plan of one weight-streaming linear: enough blocks to cover the CUs several times over, partials bounded at large M
 int plan_kchunk(int N, int K, int M, int epi) {
-  if (epi == EPI_PICK) return K;
+  if (epi == EPI_PICK || epi == EPI_BEAM) return K;
   const int nblk = cdiv(N, 64);
   int sp = std::min(K / 128, std::max(1, 1024 / nblk));
   sp = std::max(1, std::min(sp, std::max(2, 256 / M)));
@@ -572,12 +865,49 @@ DecLin lin_base(const bf16* x, int M, int K, const bf16* w, int N, const float* 
   return a;
 }
 
+const unsigned char* beam_src_host(const int* bs, int max_len) { return (const unsigned char*)(bs + BS_WORDS + (size_t)max_len * 128); }
+// beam search (null: greedy): the B rows of the step are nb beams of B / nb items
+struct BeamStep { int nb, early; float lp; float* logp; };
+struct BeamLayout { DecLayout y; size_t bstate, cache_total, logits, cv, ci, ws_total; int K, chunk, C; };
+size_t beam_state_bytes(int max_len) { return ((size_t)BS_WORDS + (size_t)max_len * 160) * 4; }
+// selection plan: 2048-value chunks, grown until the nb x C x K candidates of an item fit the merge's LDS
+int beam_chunk(int V, int nb) {
+  for (int ch = 2048; ch <= kBeamLds; ch += 2048) if ((size_t)nb * cdiv(V, ch) * 2 * nb <= (size_t)kBeamEntries) return ch;
+  return 0;
+}
+BeamLayout beam_layout(const dmx_trocr_dec* d, int B, int nb, int S, int max_len) {
+  const dmx_trocr_dec_config& c = d->cfg;
+  const int M = B * nb;
+  BeamLayout z{};
+  z.y = dec_layout(d, M, S, max_len);                            // M rows everywhere but the cross K/V, which is per item
+  z.bstate = z.y.ckv + align_up((size_t)B * S * c.num_layers * 2 * c.d_model * 2, 256);
+  z.cache_total = z.bstate + align_up(beam_state_bytes(max_len), 256);
+  z.K = 2 * nb; z.chunk = beam_chunk(c.vocab_size, nb); z.C = z.chunk ? cdiv(c.vocab_size, z.chunk) : 0;
+  size_t o = align_up(z.y.ws_total, 256);
+  auto take = [&](size_t bytes) { const size_t r = o; o += align_up(bytes, 256); return r; };
+  z.logits = take((size_t)M * c.vocab_size * 4);
+  z.cv = take((size_t)M * z.C * z.K * 4); z.ci = take((size_t)M * z.C * z.K * 4);
+  z.ws_total = o;
+  return z;
+}
+int beam_select_launch(const BeamSel& a, hipStream_t st) {
+  DMX_REQUIRE(a.nb >= 2 && a.nb <= 16 && a.B >= 1 && a.B * a.nb <= 64 && a.K == 2 * a.nb && a.V >= a.K, "beam_select: B=%d beams=%d V=%d", a.B, a.nb, a.V);
+  DMX_REQUIRE(a.chunk > 0 && a.chunk <= kBeamLds && a.C == cdiv(a.V, a.chunk) && (size_t)a.nb * a.C * a.K <= (size_t)kBeamEntries,
+              "beam_select: vocabulary %d too large for %d beams", a.V, a.nb);
+  DMX_REQUIRE(a.max_len >= 2, "beam_select: max_len %d", a.max_len);
+  hipLaunchKernelGGL(dmx_dec_beam_select_kernel, dim3(a.C, a.B * a.nb), dim3(256), 0, st, a);
+  return dmx_check_launch("dmx_dec_beam_select_kernel");
+}
+
 int dec_step(dmx_trocr_dec* d, char* cache, int B, int S, int max_len, int eos, int pad, long long* ids, float* logits, int ldl,
-             char* ws, size_t ws_bytes, hipStream_t st) {
+             char* ws, size_t ws_bytes, hipStream_t st, const BeamStep* bm = nullptr) {
   const dmx_trocr_dec_config& c = d->cfg;
   const int D = c.d_model, F = c.ffn_dim, L = c.num_layers, H = D / 64, V = c.vocab_size;
-  const DecLayout y = dec_layout(d, B, S, max_len);
-  DMX_REQUIRE(ws_bytes >= y.ws_total, "trocr_dec_step: workspace %zu < %zu bytes", ws_bytes, y.ws_total);
+  BeamLayout z{};
+  if (bm) z = beam_layout(d, B / bm->nb, bm->nb, S, max_len);
+  const DecLayout y = bm ? z.y : dec_layout(d, B, S, max_len);
+  DMX_REQUIRE(ws_bytes >= (bm ? z.ws_total : y.ws_total), "trocr_dec_step: workspace %zu < %zu bytes", ws_bytes, bm ? z.ws_total : y.ws_total);
+  int* bstate = bm ? (int*)(cache + z.bstate) : nullptr;
   int* state = (int*)(cache + y.words);
   int* cnt = state + ST_INTS;
   int slice = 0;
@@ -600,6 +930,7 @@ int dec_step(dmx_trocr_dec* d, char* cache, int B, int S, int max_len, int eos, 
     DecAttn t{};
     t.q = qf; t.ldq = D; t.kv = kvl; t.bstride = (long long)max_len * 2 * D; t.rstride = 2 * D; t.state = state; t.L = max_len; t.H = H; t.D = D;
     t.nch = y.nch_self; t.part = apart; t.cnt = next_cnt(); t.o = ab; t.ldo = D;
+    if (bm) { t.src = beam_src_host(bstate, max_len); t.src_ld = max_len; }
     if ((rc = dec_attn_launch(t, B, st))) break;
     a = lin_base(ab, B, D, d->at<bf16>(W.wo), D, d->at<float>(W.bo), EPI_LN, next_cnt(), part);
     a.res = xf; a.pre = pre; a.gamma = d->at<float>(W.l1g); a.beta = d->at<float>(W.l1b); a.yf = xf; a.yb = xb;
@@ -608,7 +939,7 @@ int dec_step(dmx_trocr_dec* d, char* cache, int B, int S, int max_len, int eos, 
     a.oscale = qscale; a.yf = qf; a.ldyf = D;
     if ((rc = dec_linear_launch(a, st))) break;
     t.kv = ckv + (size_t)l * 2 * D; t.bstride = (long long)S * L * 2 * D; t.rstride = L * 2 * D; t.state = nullptr; t.L = S;
-    t.nch = y.nch_cross; t.cnt = next_cnt();
+    t.nch = y.nch_cross; t.cnt = next_cnt(); t.src = nullptr; t.rpi = bm ? bm->nb : 0;
     if ((rc = dec_attn_launch(t, B, st))) break;
     a = lin_base(ab, B, D, d->at<bf16>(W.wco), D, d->at<float>(W.bco), EPI_LN, next_cnt(), part);
     a.res = xf; a.pre = pre; a.gamma = d->at<float>(W.l2g); a.beta = d->at<float>(W.l2b); a.yf = xf; a.yb = xb;
@@ -621,6 +952,17 @@ int dec_step(dmx_trocr_dec* d, char* cache, int B, int S, int max_len, int eos, 
     if ((rc = dec_linear_launch(a, st))) break;
   }
   if (rc) return rc;
+  if (bm) {
+    // LM head: fp32 logits + block partials of the log-sum-exp, then selection and bookkeeping in one launch
+    DecLin a = lin_base(xb, B, D, d->at<bf16>(d->lm), V, nullptr, EPI_BEAM, next_cnt(), part);
+    a.yf = (float*)(ws + z.logits); a.ldyf = V; a.pv = (float*)(ws + y.pv); a.psum = (float*)(ws + y.pi);
+    if ((rc = dec_linear_launch(a, st))) return rc;
+    BeamSel q{};
+    q.logits = a.yf; q.ldl = V; q.pmax = a.pv; q.psum = a.psum; q.nblk = y.lm_blocks; q.B = B / bm->nb; q.nb = bm->nb; q.V = V; q.K = z.K;
+    q.chunk = z.chunk; q.C = z.C; q.max_len = max_len; q.eos = eos; q.early = bm->early; q.lp = bm->lp; q.state = state; q.bs = bstate;
+    q.cv = (float*)(ws + z.cv); q.ci = (int*)(ws + z.ci); q.logp = bm->logp;
+    return beam_select_launch(q, st);
+  }
   DecLin a = lin_base(xb, B, D, d->at<bf16>(d->lm), V, nullptr, EPI_PICK, next_cnt(), part);
   a.yf = logits; a.ldyf = ldl; a.pv = (float*)(ws + y.pv); a.pi = (int*)(ws + y.pi); a.ids = ids; a.max_len = max_len;
   a.eos = eos; a.pad = pad; a.state = state;
@@ -718,6 +1060,115 @@ extern "C" int dmx_trocr_dec_step(dmx_trocr_dec* d, void* cache, int B, int S, i
               "trocr_dec_step: bad argument (B=%d S=%d max_len=%d)", B, S, max_len);
   DMX_REQUIRE(!logits || ld_logits >= d->cfg.vocab_size, "trocr_dec_step: ld_logits %d < vocab %d", ld_logits, d->cfg.vocab_size);
   return dec_step(d, (char*)cache, B, S, max_len, eos_token_id, pad_token_id, ids, logits, ld_logits, (char*)ws, ws_bytes, (hipStream_t)stream);
+}
+
+// ---- beam search: cache = state words | self K/V of B * nb rows | cross K/V of B items | beam state block
+static int beam_args_ok(const dmx_trocr_dec* d, int B, int nb, int S, int max_len) {
+  return d && B >= 1 && nb >= 2 && nb <= 16 && B * nb <= 64 && S >= 1 && max_len >= 2 && max_len <= d->cfg.max_position_embeddings &&
+         d->cfg.vocab_size >= 2 * nb && beam_chunk(d->cfg.vocab_size, nb) > 0;
+}
+extern "C" size_t dmx_trocr_dec_beam_cache_bytes(const dmx_trocr_dec* d, int B, int nb, int S, int max_len) {
+  return beam_args_ok(d, B, nb, S, max_len) ? beam_layout(d, B, nb, S, max_len).cache_total : 0;
+}
+extern "C" size_t dmx_trocr_dec_beam_workspace_bytes(const dmx_trocr_dec* d, int B, int nb, int S, int max_len) {
+  return beam_args_ok(d, B, nb, S, max_len) ? beam_layout(d, B, nb, S, max_len).ws_total : 0;
+}
+extern "C" size_t dmx_trocr_dec_beam_state_offset(const dmx_trocr_dec* d, int B, int nb, int S, int max_len) {
+  return beam_args_ok(d, B, nb, S, max_len) ? beam_layout(d, B, nb, S, max_len).bstate : 0;
+}
+extern "C" size_t dmx_trocr_dec_beam_state_bytes(int max_len) { return max_len >= 1 ? beam_state_bytes(max_len) : 0; }
+extern "C" int dmx_trocr_dec_beam_launches_per_step(const dmx_trocr_dec* d) { return d ? 3 + kLaunchesPerLayer * d->cfg.num_layers : 0; }
+extern "C" int dmx_trocr_dec_beam_begin(dmx_trocr_dec* d, const float* enc, int B, int nb, int S, int max_len, int start_token, void* cache,
+                                        void* ws, size_t ws_bytes, dmx_stream_t stream) {
+  DMX_REQUIRE(d && d->finalized, "trocr_dec_beam_begin: weights not finalized (bind_arena, load_param*, finalize)");
+  DMX_REQUIRE(enc && cache && ws && beam_args_ok(d, B, nb, S, max_len), "trocr_dec_beam_begin: bad argument (B=%d beams=%d S=%d max_len=%d)", B, nb, S, max_len);
+  const BeamLayout z = beam_layout(d, B, nb, S, max_len);
+  DMX_REQUIRE(ws_bytes >= z.ws_total, "trocr_dec_beam_begin: workspace %zu < %zu bytes", ws_bytes, z.ws_total);
+  hipStream_t st = (hipStream_t)stream;
+  // cross K/V once per item: the GEMM runs at B * S rows
+  const size_t n = (size_t)B * S * d->kdim;
+  bf16* eb = (bf16*)((char*)ws + z.y.encb);
+  hipLaunchKernelGGL(dmx_f32_to_bf16_kernel, dim3((unsigned)std::min<size_t>(8192, (n + 255) / 256)), dim3(256), 0, st, enc, eb, n);
+  int rc = dmx_check_launch("dmx_f32_to_bf16_kernel");
+  if (rc) return rc;
+  Exec ex = Exec::on(st, (char*)ws + z.y.gemm_ws, ws_bytes - z.y.gemm_ws);
+  const int N = 2 * d->cfg.num_layers * d->cfg.d_model;
+  ex.gemm_raw(eb, d->kdim, B * S, d->at<bf16>(d->wckv), d->kdim, N, d->kdim, d->at<float>(d->bckv), (char*)cache + z.y.ckv, N, 0);
+  if (ex.rc) return ex.rc;
+  const size_t nwords = (z.y.kv - z.y.words) / 4, bwords = beam_state_bytes(max_len) / 4;
+  hipLaunchKernelGGL(dmx_dec_beam_reset_kernel, dim3((unsigned)std::min<size_t>(1024, (std::max(nwords, bwords) + 255) / 256)), dim3(256), 0, st,
+                     (int*)((char*)cache + z.y.words), nwords, B * nb, nb, start_token, (int*)((char*)cache + z.bstate), bwords, max_len);
+  return dmx_check_launch("dmx_dec_beam_reset_kernel");
+}
+extern "C" int dmx_trocr_dec_beam_step(dmx_trocr_dec* d, void* cache, int B, int nb, int S, int max_len, int eos_token_id, float length_penalty,
+                                       int early_stopping, float* logp, void* ws, size_t ws_bytes, dmx_stream_t stream) {
+  DMX_REQUIRE(d && d->finalized, "trocr_dec_beam_step: weights not finalized (bind_arena, load_param*, finalize)");
+  DMX_REQUIRE(cache && ws && beam_args_ok(d, B, nb, S, max_len) && early_stopping >= 0 && early_stopping <= 2,
+              "trocr_dec_beam_step: bad argument (B=%d beams=%d S=%d max_len=%d early_stopping=%d)", B, nb, S, max_len, early_stopping);
+  BeamStep bm{nb, early_stopping, length_penalty, logp};
+  return dec_step(d, (char*)cache, B * nb, S, max_len, eos_token_id, 0, nullptr, nullptr, 0, (char*)ws, ws_bytes, (hipStream_t)stream, &bm);
+}
+extern "C" int dmx_trocr_dec_beam_finalize(dmx_trocr_dec* d, void* cache, int B, int nb, int S, int max_len, int num_return, int pad_token_id,
+                                           long long* sequences, float* scores, int* lengths, dmx_stream_t stream) {
+  DMX_REQUIRE(cache && sequences && scores && lengths && beam_args_ok(d, B, nb, S, max_len) && num_return >= 1 && num_return <= nb,
+              "trocr_dec_beam_finalize: bad argument");
+  const BeamLayout z = beam_layout(d, B, nb, S, max_len);
+  hipLaunchKernelGGL(dmx_dec_beam_gather_kernel, dim3(B * num_return), dim3(64), 0, (hipStream_t)stream, (int*)((char*)cache + z.bstate), nb,
+                     num_return, max_len, pad_token_id, sequences, scores, lengths);
+  return dmx_check_launch("dmx_dec_beam_gather_kernel");
+}
+// op entry (tests): one selection step on supplied fp32 logits [B * nb][V], through the launch function the step calls.  state:
+// the 256 state words; beam_state: dmx_trocr_dec_beam_state_bytes(max_len) bytes (set up by reset != 0: position 0)
+extern "C" size_t dmx_trocr_dec_beam_select_workspace_bytes(int B, int nb, int V) {
+  if (B < 1 || nb < 2 || nb > 16 || B * nb > 64 || V < 2 * nb || !beam_chunk(V, nb)) return 0;
+  const size_t M = (size_t)B * nb, C = cdiv(V, beam_chunk(V, nb));
+  return 2 * align_up(M * cdiv(V, 64) * 4, 256) + 2 * align_up(M * C * 2 * nb * 4, 256);
+}
+extern "C" int dmx_trocr_dec_beam_select(const float* logits, int B, int nb, int V, int max_len, int eos_token_id, float length_penalty,
+                                         int early_stopping, int reset, int start_token, int* state, void* beam_state, float* logp,
+                                         void* ws, size_t ws_bytes, dmx_stream_t stream) {
+  const size_t need = dmx_trocr_dec_beam_select_workspace_bytes(B, nb, V);
+  DMX_REQUIRE(logits && state && beam_state && ws && need && ws_bytes >= need && max_len >= 2 && early_stopping >= 0 && early_stopping <= 2,
+              "trocr_dec_beam_select: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int M = B * nb, nblk = cdiv(V, 64);
+  BeamSel q{};
+  q.chunk = beam_chunk(V, nb); q.C = cdiv(V, q.chunk); q.K = 2 * nb;
+  char* p = (char*)ws;
+  float* pmax = (float*)p; p += align_up((size_t)M * nblk * 4, 256);
+  float* psum = (float*)p; p += align_up((size_t)M * nblk * 4, 256);
+  q.cv = (float*)p; p += align_up((size_t)M * q.C * q.K * 4, 256);
+  q.ci = (int*)p;
+  int rc;
+  if (reset) {
+    const size_t bwords = beam_state_bytes(max_len) / 4;
+    hipLaunchKernelGGL(dmx_dec_beam_reset_kernel, dim3((unsigned)std::min<size_t>(1024, (bwords + 255) / 256)), dim3(256), 0, st, state, (size_t)ST_INTS,
+                       M, nb, start_token, (int*)beam_state, bwords, max_len);
+    if ((rc = dmx_check_launch("dmx_dec_beam_reset_kernel"))) return rc;
+  }
+  hipLaunchKernelGGL(dmx_dec_beam_partials_kernel, dim3(nblk, M), dim3(64), 0, st, logits, V, V, nblk, pmax, psum);
+  if ((rc = dmx_check_launch("dmx_dec_beam_partials_kernel"))) return rc;
+  q.logits = logits; q.ldl = V; q.pmax = pmax; q.psum = psum; q.nblk = nblk; q.B = B; q.nb = nb; q.V = V; q.max_len = max_len;
+  q.eos = eos_token_id; q.early = early_stopping; q.lp = length_penalty; q.state = state; q.bs = (int*)beam_state; q.logp = logp;
+  return beam_select_launch(q, st);
+}
+// decode attention with the beam indirections: table (nullable) uint8 [M][ld_table] - key j < L - 1 of row b from physical row
+// table[b][j], key L - 1 from row b -, rows_per_item > 0: row b reads the K/V of item b / rows_per_item
+extern "C" int dmx_trocr_dec_beam_attn(const float* q, int M, int H, const void* kv, long long bstride, int rstride, int L, const void* table,
+                                       int ld_table, int rows_per_item, void* out, void* ws, size_t ws_bytes, dmx_stream_t stream) {
+  DMX_REQUIRE(q && kv && out && ws && M >= 1 && M <= 64 && H >= 1 && L >= 1 && rstride >= 2 * H * 64 && rows_per_item >= 0, "trocr_dec_beam_attn: bad argument");
+  DMX_REQUIRE(!table || ld_table >= L - 1, "trocr_dec_beam_attn: ld_table %d < L - 1", ld_table);
+  DMX_REQUIRE(ws_bytes >= dmx_trocr_dec_attn_workspace_bytes(M, H, L), "trocr_dec_beam_attn: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  int* cnt = (int*)ws;
+  hipLaunchKernelGGL(dmx_dec_reset_kernel, dim3(1), dim3(256), 0, st, cnt, (size_t)M * H, 0, 0, (long long*)nullptr, 1);
+  int rc = dmx_check_launch("dmx_dec_reset_kernel");
+  if (rc) return rc;
+  DecAttn t{};
+  t.q = q; t.ldq = H * 64; t.kv = (const bf16*)kv; t.bstride = bstride; t.rstride = rstride; t.state = nullptr; t.L = L; t.H = H; t.D = H * 64;
+  t.nch = cdiv(L, 64); t.part = (float*)((char*)ws + align_up((size_t)M * H * 4, 256)); t.cnt = cnt; t.o = (bf16*)out; t.ldo = H * 64;
+  t.src = (const unsigned char*)table; t.src_ld = ld_table; t.rpi = rows_per_item;
+  return dec_attn_launch(t, M, st);
 }
 
 // ---- op entry points (tests / benchmarks): one weight-streaming linear with a chosen epilogue, one decode attention

@@ -30,6 +30,9 @@ _GEN_UNSUPPORTED = dict(num_beams=1, do_sample=False, num_beam_groups=1, no_repe
 # settings that only beam search reads: inert when greedy search runs (num_beams == 1)
 _BEAM_ONLY = ("early_stopping", "length_penalty", "num_beam_groups")
 
+# the settings beam_search() implements itself (every other non-default entry of _GEN_UNSUPPORTED stays refused there too)
+_BEAM_SEARCH_OWN = ("num_beams", "length_penalty", "early_stopping", "num_return_sequences")
+
 POLL_EVERY = 4          # generate() reads the device's all-finished flag (copied asynchronously) every POLL_EVERY steps
 
 
@@ -198,6 +201,131 @@ class TrOCRForCausalLM(_HipModel):
         ids = r["ids"][:, :L].clone()
         return ids, (torch.stack(kept[:L - 1], 1) if keep_logits else None)
 
+    # ---- beam search: rows = items x beams; the cache adds a beam state block (include/diffute_hip.h DMX_TROCR_BEAM_*)
+    @property
+    def beam_launches_per_step(self):
+        return int(self._lib.dmx_trocr_dec_beam_launches_per_step(self._h))
+
+    def _check_beam_args(self, enc, max_length, num_beams, length_penalty, early_stopping, num_return_sequences):
+        kdim = self.config.cross_attention_hidden_size or self.config.d_model
+        if enc.ndim != 3 or enc.shape[2] != kdim:
+            raise ValueError(f"encoder_hidden_states must be [B, S, {kdim}], got {tuple(enc.shape)}")
+        if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 2 <= num_beams <= 16:
+            raise ValueError(f"beam_search: num_beams must be an integer in 2 ... 16, got {num_beams!r}")
+        if not 1 <= enc.shape[0] or enc.shape[0] * num_beams > 64:
+            raise ValueError(f"beam_search: batch * num_beams = {enc.shape[0]} * {num_beams} exceeds the decoder's 64 rows")
+        if not 1 <= int(num_return_sequences) <= num_beams:
+            raise ValueError(f"beam_search: num_return_sequences={num_return_sequences} must be in 1 ... num_beams")
+        if self.config.vocab_size < 2 * num_beams:
+            raise ValueError(f"beam_search: vocab_size {self.config.vocab_size} < 2 * num_beams")
+        if not (early_stopping is True or early_stopping is False or early_stopping == "never"):
+            raise ValueError(f"beam_search: early_stopping must be False, True or 'never', got {early_stopping!r}")
+        if not 1 <= max_length <= self.config.max_position_embeddings:
+            raise ValueError(f"max_length={max_length}: the decoder has {self.config.max_position_embeddings} positions")
+        float(length_penalty)
+
+    def _beam_run(self, B, nb, S, max_len):
+        key = ("beam", B, nb, S, max_len)
+        if self._runs_epoch != self._epoch:
+            self._runs, self._runs_epoch = {}, self._epoch
+        r = self._runs.get(key)
+        if r is None:
+            lib, dev, h = self._lib, self.device, self._h
+            nbytes = lib.dmx_trocr_dec_beam_cache_bytes(h, B, nb, S, max_len)
+            if not nbytes:
+                raise NotImplementedError(f"beam_search: vocab_size {self.config.vocab_size} is too large for {nb} beams")
+            off = lib.dmx_trocr_dec_beam_state_offset(h, B, nb, S, max_len)
+            cache = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            bstate = cache[off:off + lib.dmx_trocr_dec_beam_state_bytes(max_len)]
+            W = _cabi.BEAM_WORDS
+            r = dict(cache=cache, ws=torch.empty(lib.dmx_trocr_dec_beam_workspace_bytes(h, B, nb, S, max_len), dtype=torch.uint8, device=dev),
+                     words=bstate[:W * 4].view(torch.int32), fwords=bstate[:W * 4].view(torch.float32),
+                     hist=bstate[W * 4:(W + 64 * max_len) * 4].view(torch.int32).view(max_len, 64),
+                     table=bstate[(W + 128 * max_len) * 4:(W + 160 * max_len) * 4].view(2, 64, max_len),
+                     logp=torch.empty(B * nb, self.config.vocab_size, dtype=torch.float32, device=dev), graphs={})
+            self._runs[key] = r
+        return r
+
+    def _beam_step(self, r, B, nb, S, max_len, eos, lp, es, logp):
+        _cabi.check(self._lib.dmx_trocr_dec_beam_step(self._h, _cabi.ptr(r["cache"]), B, nb, S, max_len, int(eos), float(lp), int(es),
+                                                      None if logp is None else _cabi.ptr(logp), _cabi.ptr(r["ws"]), r["ws"].numel(),
+                                                      _cabi.current_stream()), "trocr_dec_beam_step")
+
+    @torch.no_grad()
+    def beam_search(self, encoder_hidden_states, max_length, decoder_start_token_id, eos_token_id, pad_token_id, *, num_beams,
+                    length_penalty=1.0, early_stopping=False, num_return_sequences=1, use_graph=True, keep_trace=False):
+        """transformers' beam search (do_sample=False, no logits processors, one eos id or none): (sequences int64
+        [B * num_return_sequences, L], sequences_scores fp32 [B * num_return_sequences], trace).  With keep_trace the trace
+        lists, per executed step, the fp32 log-probs [B * num_beams, V] the selection used, the input tokens, the running
+        scores before the step, the chosen (parent, token) of every row and every row's running sequence after it."""
+        self._check_beam_args(encoder_hidden_states, max_length, num_beams, length_penalty, early_stopping, num_return_sequences)
+        enc = self._check_inputs(encoder_hidden_states)
+        B, S, nb, nret = enc.shape[0], enc.shape[1], num_beams, int(num_return_sequences)
+        eos = -1 if eos_token_id is None else int(eos_token_id)
+        pad = eos if pad_token_id is None else int(pad_token_id)
+        if pad < 0:
+            pad = 0
+        if max_length == 1:
+            return (torch.full((B * nret, 1), int(decoder_start_token_id), dtype=torch.int64, device=enc.device),
+                    torch.full((B * nret,), -1.0e9, dtype=torch.float32, device=enc.device), [] if keep_trace else None)
+        es = 2 if early_stopping == "never" else int(bool(early_stopping))
+        lib, M = self._lib, B * nb
+        r = self._beam_run(B, nb, S, max_length)
+        _cabi.check(lib.dmx_trocr_dec_beam_begin(self._h, _cabi.ptr(enc), B, nb, S, max_length, int(decoder_start_token_id), _cabi.ptr(r["cache"]),
+                                                 _cabi.ptr(r["ws"]), r["ws"].numel(), _cabi.current_stream()), "trocr_dec_beam_begin")
+        logp = r["logp"] if keep_trace else None
+        main = torch.cuda.current_stream()
+        gkey = (eos, float(length_penalty), es, keep_trace)
+        if use_graph and gkey not in r["graphs"]:
+            # one linear chain of kernels; tokens, position, scores, the ancestry table and the counters live in device memory
+            side = torch.cuda.Stream(device=enc.device)
+            side.wait_stream(main)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                self._beam_step(r, B, nb, S, max_length, eos, length_penalty, es, logp)
+            main.wait_stream(side)
+            r["graphs"][gkey] = g
+        state = r["cache"][:16].view(torch.int32)
+        words, fwords = r["words"], r["fwords"]
+        RUN, PAR = _cabi.BEAM_RUN_SCORE, _cabi.BEAM_PARENT
+        n_steps, steps, polls, trace = max_length - 1, 0, [], []
+        while steps < n_steps:
+            if keep_trace:
+                before = dict(input_tokens=r["cache"][64:64 + 4 * M].view(torch.int32).clone(), running_scores=fwords[RUN:RUN + M].clone())
+            if use_graph:
+                r["graphs"][gkey].replay()
+            else:
+                self._beam_step(r, B, nb, S, max_length, eos, length_penalty, es, logp)
+            steps += 1
+            if keep_trace:
+                rows = torch.arange(M, device=enc.device)
+                tab = r["table"][steps & 1, :M, :steps].long()                       # physical row of positions 0 .. steps - 1
+                seq = torch.cat([r["hist"][torch.arange(steps, device=enc.device)[None, :], tab].long(), r["hist"][steps, :M].long()[:, None]], 1)
+                trace.append(dict(before, logp=logp.clone(), parent=words[PAR:PAR + M].clone() - (rows // nb * nb).int(),
+                                  token=r["cache"][64:64 + 4 * M].view(torch.int32).clone(), sequences=seq))
+            if steps % POLL_EVERY == 0 and steps < n_steps:
+                f = torch.empty(2, dtype=torch.int32, pin_memory=True)
+                f.copy_(state[1:3], non_blocking=True)
+                ev = torch.cuda.Event(); ev.record()
+                polls.append((ev, f))
+                if len(polls) > 1:
+                    ev0, f0 = polls.pop(0)
+                    ev0.synchronize()
+                    if int(f0[0]):
+                        break
+        seqs = torch.empty(B * nret, max_length, dtype=torch.int64, device=enc.device)
+        scores = torch.empty(B * nret, dtype=torch.float32, device=enc.device)
+        lens = torch.empty(B * nret, dtype=torch.int32, device=enc.device)
+        _cabi.check(lib.dmx_trocr_dec_beam_finalize(self._h, _cabi.ptr(r["cache"]), B, nb, S, max_length, nret, pad, _cabi.ptr(seqs), _cabi.ptr(scores),
+                                                    _cabi.ptr(lens), _cabi.current_stream()), "trocr_dec_beam_finalize")
+        flag = torch.empty(2, dtype=torch.int32)
+        flag.copy_(state[1:3])                   # (one synchronisation at the end)
+        L = 1 + int(lens.max())
+        if keep_trace:
+            ran = int(flag[1]) - 1 if int(flag[0]) else steps    # steps the device executed before the loop condition ended it
+            trace = trace[:ran]
+        return seqs[:, :L].contiguous(), scores, (trace if keep_trace else None)
+
 
 def _check_generation(settings, explicit_beams):
     for k, want in _GEN_UNSUPPORTED.items():
@@ -210,16 +338,18 @@ def _check_generation(settings, explicit_beams):
             continue                              # sampling knobs are inert under greedy search
         if k in _BEAM_ONLY and (explicit_beams or int(settings.get("num_beams") or 1) == 1):
             continue                              # beam-search knobs are inert under greedy search
-        hint = "; pass num_beams=1 to run greedy search anyway" if k in ("num_beams", *_BEAM_ONLY) else \
+        hint = "; pass num_beams=1 to run greedy search anyway, or call beam_search()" if k in ("num_beams", *_BEAM_ONLY) else \
             " (greedy search only: remove it from the call / generation_config)"
         raise NotImplementedError(f"VisionEncoderDecoderModel.generate: {k}={v!r} is not implemented{hint}")
 
 
 class VisionEncoderDecoderModel(nn.Module):
     """`full_trocr_model` of app.ipynb:548: `.encoder` is the glyph encoder (`TrOCREncoder`, app.ipynb:547), `.decoder` the text
-    decoder (`TrOCRForCausalLM`); `generate(pixel_values)` (app.ipynb:845) is transformers' greedy search.  Not implemented (refused
-    where a config asks for it): beam search, sampling, logits processors (no_repeat_ngram_size, repetition_penalty, min_length,
-    forced tokens, ...), an encoder wider than the decoder's cross-attention (`enc_to_dec_proj`)."""
+    decoder (`TrOCRForCausalLM`); `generate(pixel_values)` (app.ipynb:845) is transformers' greedy search and refuses settings that ask
+    for anything else; `beam_search(pixel_values)` is transformers' beam search with the checkpoint's own num_beams / length_penalty /
+    early_stopping.  Not implemented (refused where a config asks for it): sampling, group / constrained beam search, logits
+    processors (no_repeat_ngram_size, repetition_penalty, min_length, forced tokens, ...), several eos ids, an encoder wider than the
+    decoder's cross-attention (`enc_to_dec_proj`)."""
 
     def __init__(self, encoder=None, decoder=None, generation_config=None):
         super().__init__()
@@ -321,3 +451,58 @@ class VisionEncoderDecoderModel(nn.Module):
         ids, _ = self.decoder.greedy(encoder_hidden_states, L, g["decoder_start_token_id"], eos, g.get("pad_token_id"),
                                      use_graph=use_graph)
         return ids
+
+    @torch.no_grad()
+    def beam_search(self, pixel_values=None, *, encoder_hidden_states=None, max_new_tokens=None, max_length=None, num_beams=None,
+                    length_penalty=None, early_stopping=None, num_return_sequences=None, return_scores=False, use_graph=True, **kwargs):
+        """beam-search ids [B * num_return_sequences, L] (int64, on the device) - transformers' `generate` with num_beams > 1,
+        do_sample=False.  Settings not passed come from generation_config (what from_pretrained read; else length_penalty 1.0,
+        early_stopping False, num_return_sequences 1, max_length 20).  With return_scores also `sequences_scores`."""
+        unknown = set(kwargs) - set(_GEN_UNSUPPORTED) - {"decoder_start_token_id", "eos_token_id", "pad_token_id"}
+        if unknown:
+            raise TypeError(f"beam_search() got unexpected keyword arguments {sorted(unknown)}")
+        g = self._settings(dict(kwargs, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping,
+                                num_return_sequences=num_return_sequences))
+        for k, want in _GEN_UNSUPPORTED.items():
+            v = g.get(k)
+            if k in _BEAM_SEARCH_OWN or v is None or v == want:
+                continue
+            if k in ("temperature", "top_k", "top_p") and not g.get("do_sample"):
+                continue
+            raise NotImplementedError(f"VisionEncoderDecoderModel.beam_search: {k}={v!r} is not implemented (remove it from the call / generation_config)")
+        nb = g.get("num_beams")
+        if isinstance(nb, bool) or not isinstance(nb, int) or not 2 <= nb <= 16:
+            raise ValueError(f"beam_search: num_beams must resolve to 2 ... 16, got {nb!r} (generate() runs greedy search)")
+        if (pixel_values is None) == (encoder_hidden_states is None):
+            raise ValueError("beam_search: pass exactly one of pixel_values / encoder_hidden_states")
+        if max_new_tokens is not None:
+            L = 1 + int(max_new_tokens)
+        elif max_length is not None:
+            L = int(max_length)
+        elif g.get("max_new_tokens") is not None:
+            L = 1 + int(g["max_new_tokens"])
+        else:
+            L = int(g.get("max_length") or 20)
+        if L > self.decoder.config.max_position_embeddings:
+            raise ValueError(f"beam_search: max_length {L} exceeds the decoder's {self.decoder.config.max_position_embeddings} positions")
+        if L < 1:
+            raise ValueError("beam_search: max_length must be >= 1")
+        eos = g.get("eos_token_id")
+        if isinstance(eos, (list, tuple)):
+            if len(eos) != 1:
+                raise NotImplementedError("beam_search: several eos_token_id values are not implemented")
+            eos = eos[0]
+        lp = g.get("length_penalty"); es = g.get("early_stopping"); nret = g.get("num_return_sequences")
+        lp, es, nret = (1.0 if lp is None else float(lp)), (False if es is None else es), (1 if nret is None else int(nret))
+        probe = encoder_hidden_states if encoder_hidden_states is not None else None
+        if probe is not None:                        # every argument check before anything touches the device
+            self.decoder._check_beam_args(probe, L, nb, lp, es, nret)
+        else:
+            if pixel_values.ndim != 4:
+                raise ValueError(f"pixel_values must be [B, C, H, W], got {tuple(pixel_values.shape)}")
+            kdim = self.decoder.config.cross_attention_hidden_size or self.decoder.config.d_model
+            self.decoder._check_beam_args(torch.empty(pixel_values.shape[0], 1, kdim, device="meta"), L, nb, lp, es, nret)
+            encoder_hidden_states = self.encoder(pixel_values).last_hidden_state
+        ids, scores, _ = self.decoder.beam_search(encoder_hidden_states, L, g["decoder_start_token_id"], eos, g.get("pad_token_id"), num_beams=nb,
+                                                  length_penalty=lp, early_stopping=es, num_return_sequences=nret, use_graph=use_graph)
+        return (ids, scores) if return_scores else ids

@@ -789,6 +789,49 @@ size_t dmx_trocr_dec_attn_workspace_bytes(int M, int H, int L);
 int dmx_trocr_dec_attn(const float* q, int M, int H, const void* kv, long long bstride, int rstride, int L, void* out,
                        void* workspace, size_t workspace_bytes, dmx_stream_t stream);
 
+/* Beam search over the same decoder (transformers' GenerationMixin._beam_search with do_sample=False, no logits processors, one
+ * eos id; app.ipynb:845 with a checkpoint's own num_beams / length_penalty / early_stopping).  Rows = B items x num_beams (<= 64,
+ * 2 <= num_beams <= 16).  cache: state words | self K/V of every row | cross K/V of every ITEM | beam state block.  The self
+ * K/V is never reordered: row r writes the K/V of its input token at the current position, and an ancestry table uint8
+ * [2][64][max_len] (two halves, used by the parity of the position) names the physical row that holds position j of each beam.
+ * A step = the greedy step's launches with an LM head that writes fp32 logits and log-sum-exp partials, plus ONE selection
+ * launch (top 2 num_beams per item, running / finished bookkeeping, the loop condition into DMX_TROCR_STATE_DONE / _STOP_LEN).
+ * Beam state block, int32 / fp32 words from dmx_trocr_dec_beam_state_offset: */
+#define DMX_TROCR_BEAM_RUN_SCORE 0     /* fp32 [64] running score of each row */
+#define DMX_TROCR_BEAM_FIN_SCORE 64    /* fp32 [64] finished slots: score, */
+#define DMX_TROCR_BEAM_FIN_FLAG 128    /* finished flag, */
+#define DMX_TROCR_BEAM_FIN_LEN 192     /* generated length */
+#define DMX_TROCR_BEAM_IMPROVABLE 256  /* per item: the running beams can still improve on the finished ones */
+#define DMX_TROCR_BEAM_PARENT 320      /* per row: the row it continued in the last step */
+#define DMX_TROCR_BEAM_STEPS 580       /* selection launches since the reset */
+#define DMX_TROCR_BEAM_WORDS 640       /* then: token history int32 [max_len][64], finished ids int32 [64][max_len], the table */
+size_t dmx_trocr_dec_beam_cache_bytes(const dmx_trocr_dec* d, int B, int num_beams, int S, int max_len);       /* app.ipynb:845 */
+size_t dmx_trocr_dec_beam_workspace_bytes(const dmx_trocr_dec* d, int B, int num_beams, int S, int max_len);   /* app.ipynb:845 */
+size_t dmx_trocr_dec_beam_state_offset(const dmx_trocr_dec* d, int B, int num_beams, int S, int max_len);      /* app.ipynb:845 */
+size_t dmx_trocr_dec_beam_state_bytes(int max_len);
+int dmx_trocr_dec_beam_launches_per_step(const dmx_trocr_dec* d);                              /* app.ipynb:845 */
+/* cross K/V of the B items (one GEMM at B * S rows) and the reset: position 0, running scores [0, -1e9, ...] (app.ipynb:845) */
+int dmx_trocr_dec_beam_begin(dmx_trocr_dec* d, const float* encoder_hidden_states, int B, int num_beams, int S, int max_len, int start_token,
+                             void* cache, void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+/* one beam step (app.ipynb:845); eos_token_id < 0: none; early_stopping 0 False, 1 True, 2 "never"; logp (nullable): fp32
+ * [B * num_beams][vocab], the log-probs the selection used.  After DMX_TROCR_STATE_DONE is set a step changes nothing */
+int dmx_trocr_dec_beam_step(dmx_trocr_dec* d, void* cache, int B, int num_beams, int S, int max_len, int eos_token_id, float length_penalty,
+                            int early_stopping, float* logp, void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+/* the first num_return finished slots of every item: sequences int64 [B * num_return][max_len] (pad beyond the hypothesis),
+ * scores fp32 and generated lengths int32 [B * num_return] (app.ipynb:845) */
+int dmx_trocr_dec_beam_finalize(dmx_trocr_dec* d, void* cache, int B, int num_beams, int S, int max_len, int num_return, int pad_token_id,
+                                long long* sequences, float* scores, int* lengths, dmx_stream_t stream);
+/* op entry points (tests): one selection step on supplied fp32 logits [B * num_beams][V] through the step's launch function
+ * (state: 256 state words, beam_state: dmx_trocr_dec_beam_state_bytes(max_len) bytes, both set up when reset != 0); the
+ * decode attention with the ancestry table (nullable, uint8 [M][ld_table]: key j < L - 1 of row b from row table[b][j], key
+ * L - 1 from row b) and rows_per_item > 0 rows sharing one item's K/V */
+size_t dmx_trocr_dec_beam_select_workspace_bytes(int B, int num_beams, int V);
+int dmx_trocr_dec_beam_select(const float* logits, int B, int num_beams, int V, int max_len, int eos_token_id, float length_penalty,
+                              int early_stopping, int reset, int start_token, int* state, void* beam_state, float* logp,
+                              void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+int dmx_trocr_dec_beam_attn(const float* q, int M, int H, const void* kv, long long bstride, int rstride, int L, const void* table,
+                            int ld_table, int rows_per_item, void* out, void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+
 typedef struct dmx_vae_config {
   int in_channels, out_channels, latent_channels;
   int block_out_channels[4];
