@@ -233,6 +233,12 @@ _PROTOS = {
     "dmx_trocr_dec_beam_attn": (c_int, [_P, c_int, c_int, _P, c_int64, c_int, c_int, _P, c_int, c_int, _P, _P, c_size_t, _P]),
     "dmx_trocr_dec_attn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dmx_trocr_dec_attn": (c_int, [_P, c_int, c_int, _P, c_int64, c_int, c_int, _P, _P, c_size_t, _P]),
+    "dmx_trocr_dec_prefill_workspace_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
+    "dmx_trocr_dec_score": (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, c_size_t, _P]),
+    "dmx_trocr_dec_prefill_embed": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, c_float, _P, _P, c_int, _P, _P, _P]),
+    "dmx_trocr_dec_prefill_attn": (c_int, [_P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_float, _P]),
+    "dmx_trocr_dec_prefill_lm_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dmx_trocr_dec_prefill_lm_loss": (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "dmx_unet_context_bytes": (c_size_t, [_P, c_int, c_int]),
     "dmx_unet_workspace_bytes": (c_size_t, [_P, c_int, c_int, c_int, c_int]),
     "dmx_unet_set_context": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_size_t, _P, c_size_t, _P]),

@@ -20,8 +20,7 @@
 #include <memory>
 #include <string>
 #include <vector>
-#include "exec.h"
-#include "../../include/diffute_hip.h"
+#include "trocr_dec.h"
 
 namespace {
 enum { EPI_STORE = 0, EPI_QKV = 1, EPI_LN = 2, EPI_PICK = 3, EPI_BEAM = 4 };
@@ -788,7 +787,6 @@ int dec_linear_launch(const DecLin& a, hipStream_t stream) {
 }  // namespace
 
 namespace {
-struct DecLayer { size_t wqkv, bqkv, wo, bo, l1g, l1b, wcq, bcq, wco, bco, l2g, l2b, w1, b1, w2, b2, l3g, l3b; };
 constexpr int kLaunchesPerLayer = 8;
 
 // split-K plan of one weight-streaming linear: enough blocks to cover the CUs several times over, partials bounded at large M
@@ -804,13 +802,6 @@ size_t lin_part_floats(int N, int K, int M, int epi) {
   return sp > 1 ? (size_t)sp * M * N : 0;
 }
 }  // namespace
-
-struct dmx_trocr_dec : ModelBase {
-  dmx_trocr_dec_config cfg;
-  size_t emb, posw, leg = 0, leb = 0, wckv, bckv, lm;
-  int npos = 0, kdim = 0, cnt_slice = 0;
-  std::vector<DecLayer> layers;
-};
 
 namespace {
 struct DecLayout {                   // byte offsets in the cache / workspace

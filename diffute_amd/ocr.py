@@ -41,6 +41,36 @@ class CausalLMOutput:
         self.logits = logits
 
 
+class ScoreOutput:
+    """what `score()` returns: per-token log-probs of the labels under teacher forcing, their sums and the batch loss"""
+
+    def __init__(self, token_logprobs, sequence_logprobs, num_tokens, predictions, loss, logits=None):
+        self.token_logprobs, self.sequence_logprobs, self.num_tokens = token_logprobs, sequence_logprobs, num_tokens
+        self.predictions, self.loss, self.logits = predictions, loss, logits
+
+
+class BaseModelOutput:
+    def __init__(self, last_hidden_state=None):
+        self.last_hidden_state = last_hidden_state
+
+    def __getitem__(self, i):
+        return (self.last_hidden_state,)[i]
+
+
+class Seq2SeqLMOutput:
+    def __init__(self, loss=None, logits=None, encoder_last_hidden_state=None):
+        self.loss, self.logits, self.encoder_last_hidden_state = loss, logits, encoder_last_hidden_state
+
+    def to_tuple(self):
+        return tuple(v for v in (self.loss, self.logits, self.encoder_last_hidden_state) if v is not None)
+
+    def __getitem__(self, i):
+        return self.to_tuple()[i]
+
+
+MAX_SCORE_ROWS = 4096   # B * T rows of one score() call (include/diffute_hip.h dmx_trocr_dec_score)
+
+
 class TrOCRForCausalLM(_HipModel):
     """TrOCR's text decoder (transformers `TrOCRForCausalLM`; the `.decoder` of app.ipynb:548's `full_trocr_model`).  Parameters
     carry transformers' state-dict keys; `output_projection.weight` exists only when the config unties it from `embed_tokens`.
@@ -137,6 +167,82 @@ class TrOCRForCausalLM(_HipModel):
             _cabi.check(lib.dmx_trocr_dec_set_tokens(self._h, _cabi.ptr(r["cache"]), _cabi.ptr(col), B, st), "trocr_dec_set_tokens")
             self._step(r, B, enc.shape[1], T, -1, 0, out.data_ptr() + t * V * 4, T * V)
         return CausalLMOutput(out) if return_dict else (out,)
+
+    def _check_score_args(self, enc_shape, labels, decoder_input_ids, ignore_index):
+        """every shape / dtype / range check of score(), on the host side: nothing is launched before it passes"""
+        kdim = self.config.cross_attention_hidden_size or self.config.d_model
+        if len(enc_shape) != 3 or enc_shape[2] != kdim:
+            raise ValueError(f"encoder_hidden_states must be [B, S, {kdim}], got {tuple(enc_shape)}")
+        B = enc_shape[0]
+        if not 1 <= B <= 64:
+            raise ValueError(f"TrOCRForCausalLM: 1 <= batch <= 64 rows, got {B}")
+        if enc_shape[1] < 1:
+            raise ValueError("encoder_hidden_states has no rows")
+        if labels is None and decoder_input_ids is None:
+            raise ValueError("score: pass labels or decoder_input_ids")
+        V, P = self.config.vocab_size, self.config.max_position_embeddings
+        shape = None
+        for name, t in (("labels", labels), ("decoder_input_ids", decoder_input_ids)):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.int64:
+                raise ValueError(f"score: {name} must be an int64 tensor, got {getattr(t, 'dtype', type(t))}")
+            if t.ndim != 2 or t.shape[0] != B:
+                raise ValueError(f"score: {name} must be [B, T] with B = {B}, got {tuple(t.shape)}")
+            if shape is not None and tuple(t.shape) != shape:
+                raise ValueError(f"score: labels {shape} and decoder_input_ids {tuple(t.shape)} differ in shape")
+            shape = tuple(t.shape)
+        T = shape[1]
+        if not 1 <= T <= P:
+            raise ValueError(f"score: 1 <= T <= {P} positions, got T = {T}")
+        if B * T > MAX_SCORE_ROWS:
+            raise ValueError(f"score: B * T = {B} * {T} exceeds {MAX_SCORE_ROWS} rows")
+        if not -2 ** 31 <= int(ignore_index) < 2 ** 31:
+            raise ValueError(f"score: ignore_index {ignore_index} is not a 32-bit integer")
+        if labels is not None:
+            bad = ((labels < 0) | (labels >= V)) & (labels != int(ignore_index))
+            if bool(bad.any()):
+                raise ValueError(f"score: labels must lie in [0, {V}) or equal ignore_index = {ignore_index}")
+        if decoder_input_ids is not None and bool(((decoder_input_ids < 0) | (decoder_input_ids >= V)).any()):
+            raise ValueError(f"score: decoder_input_ids must lie in [0, {V})")
+        return B, T
+
+    @torch.no_grad()
+    def score(self, labels, encoder_hidden_states, *, decoder_start_token_id=None, pad_token_id=None, ignore_index=-100,
+              decoder_input_ids=None, return_logits=False):
+        """Teacher-forced pass over known target ids in ONE prefill (transformers' `model(encoder_outputs=..., labels=...)`): the
+        decoder inputs are the labels shifted right (start token first, ignore_index -> pad), or decoder_input_ids as they are.
+        Returns a ScoreOutput: token_logprobs [B, T] fp32 (0 where the label is ignore_index), sequence_logprobs [B], num_tokens
+        [B], predictions [B, T] int64 (the teacher-forced arg-max), loss = -sum(token_logprobs) / sum(num_tokens) (torch's
+        CrossEntropyLoss over the flattened batch; NaN when every label is ignored) and logits [B, T, V] fp32 only with
+        return_logits.  With labels=None (decoder_input_ids given) only predictions and logits are computed."""
+        B, T = self._check_score_args(tuple(encoder_hidden_states.shape), labels, decoder_input_ids, ignore_index)
+        start = self.config.decoder_start_token_id if decoder_start_token_id is None else decoder_start_token_id
+        pad = self.config.pad_token_id if pad_token_id is None else pad_token_id
+        if decoder_input_ids is None and (start is None or pad is None):
+            raise ValueError("score: decoder_start_token_id and pad_token_id are needed to shift the labels")
+        enc = self._check_inputs(encoder_hidden_states)
+        dev, S, V = enc.device, enc.shape[1], self.config.vocab_size
+        lab = None if labels is None else labels.to(dev).contiguous()
+        dids = None if decoder_input_ids is None else decoder_input_ids.to(dev).contiguous()
+        key = ("score", B, S, T)
+        if self._runs_epoch != self._epoch:
+            self._runs, self._runs_epoch = {}, self._epoch
+        r = self._runs.get(key)
+        if r is None:
+            r = dict(ws=torch.empty(self._lib.dmx_trocr_dec_prefill_workspace_bytes(self._h, B, S, T), dtype=torch.uint8, device=dev))
+            self._runs[key] = r
+        logp = None if lab is None else torch.empty(B, T, dtype=torch.float32, device=dev)
+        amax = torch.empty(B, T, dtype=torch.int32, device=dev)
+        logits = torch.empty(B, T, V, dtype=torch.float32, device=dev) if return_logits else None
+        _cabi.check(self._lib.dmx_trocr_dec_score(self._h, _cabi.ptr(enc), B, S, _cabi.ptr(lab), _cabi.ptr(dids), T, int(start or 0), int(pad or 0),
+                                                  int(ignore_index), _cabi.ptr(logp), _cabi.ptr(amax), _cabi.ptr(logits), V, _cabi.ptr(r["ws"]),
+                                                  r["ws"].numel(), _cabi.current_stream()), "trocr_dec_score")
+        if lab is None:
+            return ScoreOutput(None, None, None, amax.long(), None, logits)
+        n = (lab != int(ignore_index)).sum(1)
+        seq = logp.sum(1)
+        return ScoreOutput(logp, seq, n, amax.long(), -logp.sum() / n.sum(), logits)
 
     @torch.no_grad()
     def greedy(self, encoder_hidden_states, max_length, decoder_start_token_id, eos_token_id, pad_token_id, use_graph=True, keep_logits=False):
@@ -415,6 +521,52 @@ class VisionEncoderDecoderModel(nn.Module):
         g = self.generation_config.to_dict()
         g.update({k: v for k, v in kw.items() if v is not None})
         return g
+
+    def _score_inputs(self, who, pixel_values, encoder_hidden_states, labels, decoder_input_ids, ignore_index):
+        """the argument checks of forward() / score(), all before the encoder runs"""
+        if (pixel_values is None) == (encoder_hidden_states is None):
+            raise ValueError(f"{who}: pass exactly one of pixel_values / encoder_hidden_states")
+        if labels is None and decoder_input_ids is None:
+            raise ValueError(f"{who}: pass labels or decoder_input_ids")
+        kdim = self.decoder.config.cross_attention_hidden_size or self.decoder.config.d_model
+        if encoder_hidden_states is not None:
+            shape = tuple(encoder_hidden_states.shape)
+        else:
+            if pixel_values.ndim != 4:
+                raise ValueError(f"pixel_values must be [B, C, H, W], got {tuple(pixel_values.shape)}")
+            shape = (pixel_values.shape[0], 1, kdim)
+        self.decoder._check_score_args(shape, labels, decoder_input_ids, ignore_index)
+
+    @torch.no_grad()
+    def score(self, pixel_values=None, *, encoder_hidden_states=None, labels=None, decoder_input_ids=None, decoder_start_token_id=None,
+              pad_token_id=None, ignore_index=-100, return_logits=False):
+        """how well the boxes read as `labels` [B, T] (ids; -100 = ignored): `TrOCRForCausalLM.score` on the encoder's states, or on
+        encoder_hidden_states computed earlier.  No logits unless asked: what a best-of-N loop calls."""
+        self._score_inputs("score", pixel_values, encoder_hidden_states, labels, decoder_input_ids, ignore_index)
+        g = self.generation_config
+        start = g.decoder_start_token_id if decoder_start_token_id is None else decoder_start_token_id
+        pad = g.pad_token_id if pad_token_id is None else pad_token_id
+        if encoder_hidden_states is None:
+            encoder_hidden_states = self.encoder(pixel_values).last_hidden_state
+        return self.decoder.score(labels, encoder_hidden_states, decoder_start_token_id=start, pad_token_id=pad, ignore_index=ignore_index,
+                                  decoder_input_ids=decoder_input_ids, return_logits=return_logits)
+
+    @torch.no_grad()
+    def forward(self, pixel_values=None, labels=None, decoder_input_ids=None, encoder_outputs=None, return_dict=True):
+        """transformers' `VisionEncoderDecoderModel.forward`: Seq2SeqLMOutput(loss, logits, encoder_last_hidden_state).  `labels`
+        [B, T] (-100 = ignored) give the loss and the logits of the labels shifted right; `decoder_input_ids` alone give logits with
+        loss None; encoder_outputs (a BaseModelOutput or a tuple) stands in for pixel_values.  Forward-only."""
+        enc = None
+        if encoder_outputs is not None:
+            enc = encoder_outputs.last_hidden_state if hasattr(encoder_outputs, "last_hidden_state") else encoder_outputs[0]
+        self._score_inputs("forward", pixel_values, enc, labels, decoder_input_ids, -100)
+        if enc is None:
+            enc = self.encoder(pixel_values).last_hidden_state
+        g = self.generation_config
+        out = self.decoder.score(labels, enc, decoder_start_token_id=g.decoder_start_token_id, pad_token_id=g.pad_token_id,
+                                 decoder_input_ids=decoder_input_ids, return_logits=True)
+        res = Seq2SeqLMOutput(out.loss, out.logits, enc)
+        return res if return_dict else res.to_tuple()
 
     @torch.no_grad()
     def generate(self, pixel_values=None, *, encoder_hidden_states=None, max_new_tokens=None, max_length=None, num_beams=None,

@@ -832,6 +832,37 @@ int dmx_trocr_dec_beam_select(const float* logits, int B, int num_beams, int V, 
 int dmx_trocr_dec_beam_attn(const float* q, int M, int H, const void* kv, long long bstride, int rstride, int L, const void* table,
                             int ld_table, int rows_per_item, void* out, void* workspace, size_t workspace_bytes, dmx_stream_t stream);
 
+/* Teacher-forced scoring of known target ids (transformers' `VisionEncoderDecoderModel(pixel_values=..., labels=...)` over the
+ * model of app.ipynb:548): all B * T rows go through every layer at once (prefill), and the LM head keeps per (row, vocabulary
+ * tile) only the running (max, sum exp), the best (value, lowest index) and the label's logit, so the [B*T][V] logits exist in
+ * memory only when the caller asks for them.  1 <= B <= 64, 1 <= T <= max_position_embeddings, B * T <= 4096.
+ *   labels            int64 [B][T]; the decoder input at position 0 is start_token, at position t labels[t - 1] with
+ *                     ignore_index replaced by pad_token (transformers' shift_tokens_right).  Nullable with decoder_input_ids.
+ *   decoder_input_ids int64 [B][T] or null: the decoder inputs as they are (no shift)
+ *   token_logprob     fp32 [B][T]: logit[label] - log-sum-exp, 0 where the label is ignore_index (required with labels)
+ *   argmax            int32 [B][T], nullable: the teacher-forced arg-max (lowest index among equal maxima)
+ *   logits            fp32 [B*T][ld_logits], nullable */
+size_t dmx_trocr_dec_prefill_workspace_bytes(const dmx_trocr_dec* d, int B, int S, int T);     /* app.ipynb:845 */
+int dmx_trocr_dec_score(dmx_trocr_dec* d, const float* encoder_hidden_states, int B, int S, const long long* labels,
+                        const long long* decoder_input_ids, int T, int start_token, int pad_token, int ignore_index,
+                        float* token_logprob, int* argmax, float* logits, int ld_logits,
+                        void* workspace, size_t workspace_bytes, dmx_stream_t stream);          /* app.ipynb:845 */
+/* op entry points of the prefill kernels (tests; app.ipynb:845).  Embedding of a [B][T] block with the label shift:
+ * LN(embed_tokens[id] * scale + embed_positions[t + 2]) (no LayerNorm without gamma) -> xf fp32 and xb 16-bit, both [B*T][D] */
+int dmx_trocr_dec_prefill_embed(const long long* labels, const long long* decoder_input_ids, int B, int T, int start_token, int pad_token,
+                                int ignore_index, const void* embed_tokens, int V, const float* embed_positions, int num_positions,
+                                float scale, const float* gamma, const float* beta, int D, float* xf, void* xb, dmx_stream_t stream);
+/* causal self-attention, d = 64, Sq = Sk = T <= 512: row (b * T + t), head h at column h * 64 of q / k / v / out (16-bit
+ * elements, any column slices of one fused buffer); out = softmax(scale * q k^T, keys <= t) v */
+int dmx_trocr_dec_prefill_attn(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo,
+                               int B, int H, int T, float scale, dmx_stream_t stream);
+/* fused LM head + loss: x [M][K] and w [V][K] 16-bit (K % 128 == 0), labels int64 [M] or null -> token_logprob, argmax, logits
+ * as in dmx_trocr_dec_score */
+size_t dmx_trocr_dec_prefill_lm_loss_workspace_bytes(int M, int V);
+int dmx_trocr_dec_prefill_lm_loss(const void* x, int M, int K, const void* w, int V, const long long* labels, int ignore_index,
+                                  float* token_logprob, int* argmax, float* logits, int ld_logits,
+                                  void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+
 typedef struct dmx_vae_config {
   int in_channels, out_channels, latent_channels;
   int block_out_channels[4];
