@@ -132,6 +132,9 @@ _PROTOS = {
     "dmx_test_slice_cast": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P]),
     "dmx_test_mode_bwd": (c_int, [_P, c_int, _P, c_int, c_int, _P]),
     "dmx_test_bf16_to_f32_rows": (c_int, [_P, c_int, _P, c_int, c_int, _P]),
+    # ... and the weight-preparation kernels only the executors launch (tests/test_weight_pack_gpu.py)
+    "dmx_test_ln_fold": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
+    "dmx_test_cast_pad_rows": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, _P]),
     "dmx_conv_gemm_workspace_bytes": (c_size_t, [POINTER(GemmDesc)]),
     "dmx_conv_gemm": (c_int, [POINTER(GemmDesc), _P, c_size_t, _P]),
     "dmx_conv_gemm_rowstats_tiles": (c_int, [POINTER(GemmDesc)]),

@@ -274,6 +274,8 @@ __global__ __launch_bounds__(256) void dmx_pack_rows_kernel(const float* w, bf16
   }
 }
 int dmx_pack_rows_launch(const float* w, bf16* out, int rows, int cols, int ldo, int geglu, hipStream_t stream) {
+  // geglu_src_row is a permutation of the rows only over whole 64-row groups (32 value + 32 gate rows each)
+  DMX_REQUIRE(!geglu || rows % 64 == 0, "pack_linear_weight: geglu packing needs rows %% 64 == 0, got %d", rows);
   const size_t total = (size_t)rows * cols;
   int blocks = (int)((total + 255) / 256); if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(dmx_pack_rows_kernel, dim3(blocks), dim3(256), 0, stream, w, out, rows, cols, ldo, geglu);
@@ -284,6 +286,7 @@ __global__ void dmx_pack_geglu_bias_kernel(const float* b, float* out, int n) {
   if (i < n) out[i] = b[geglu_src_row(i, n)];
 }
 int dmx_pack_geglu_bias_launch(const float* b, float* out, int n, hipStream_t stream) {
+  DMX_REQUIRE(n > 0 && n % 64 == 0, "pack_geglu_bias: geglu packing needs n %% 64 == 0, got %d", n);
   hipLaunchKernelGGL(dmx_pack_geglu_bias_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, b, out, n);
   return dmx_check_launch("dmx_pack_geglu_bias_kernel");
 }

@@ -157,6 +157,7 @@ int model_master_import(const ModelBase* m, const char* who, void* masters, cons
     case PackRule::GEGLU_W: kind = 3; break;
     case PackRule::GEGLU_B: kind = 4; cols = 0; break;
   }
+  DMX_REQUIRE(kind < 3 || rows % 64 == 0, "%s_master_import: %s: geglu packing needs rows %% 64 == 0, got %d", who, name, rows);
   const size_t total = (kind == 1) ? (size_t)rows * cols * r.ks * r.ks : (size_t)rows * (cols > 0 ? cols : 1);
   int blocks = (int)((total + 255) / 256); if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(dmx_master_pack_kernel, dim3(blocks), dim3(256), 0, stream, src, g, kind, rows, cols, r.ks, r.ld, r.koff);

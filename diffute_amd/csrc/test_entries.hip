@@ -1,7 +1,8 @@
 // Test support (include/diffute_hip.h "test support"): extern "C" entries that reach the small training kernels which have no
 // operator-level entry of their own - train_small.hip's transposes, add, pointwise 1x1 and small-linear backward, norm.hip's row
-// softmax and vae_train.hip's casts.  Each entry checks its arguments and forwards to the *_launch function the training graphs
-// call (tests/test_train_small_gpu.py); none does arithmetic of its own.
+// softmax and vae_train.hip's casts (tests/test_train_small_gpu.py) - and the two weight-preparation kernels that only the model
+// executors launch: gemm.hip's folded-LayerNorm weights and elementwise.hip's padded context cast (tests/test_weight_pack_gpu.py).
+// Each entry checks its arguments and forwards to the *_launch function the graphs call; none does arithmetic of its own.
 #include "kernels.h"
 #include "../../include/diffute_hip.h"
 
@@ -79,4 +80,16 @@ extern "C" int dmx_test_mode_bwd(const void* dz, int lddz, float* dmom, int M, i
 extern "C" int dmx_test_bf16_to_f32_rows(const void* in, int ldin, float* out, int M, int C, dmx_stream_t stream) {
   DMX_REQUIRE(in && out && M > 0 && C > 0 && ldin >= C, "test_bf16_to_f32_rows: bad argument");
   return dmx_bf16_to_f32_rows_launch((const bf16*)in, ldin, out, M, C, ST(stream));
+}
+
+// W' (16) [N][K] = round16(w_raw * gamma), c1[n] = sum_k W'[n][k], c2[n] = sum_k beta[k] w_raw[n][k] (+ bias[n]); all dense, K a multiple of 8
+extern "C" int dmx_test_ln_fold(const void* w_raw, void* w_out, const float* gamma, const float* beta, const float* bias, float* c1, float* c2,
+                                int N, int K, dmx_stream_t stream) {
+  DMX_REQUIRE(w_raw && w_out && gamma && beta && c1 && c2 && N > 0 && K > 0, "test_ln_fold: bad argument");
+  return dmx_ln_fold_launch((const bf16*)w_raw, (bf16*)w_out, gamma, beta, bias, c1, c2, N, K, ST(stream));
+}
+// out (16) [B][Spad][C] = in (fp32, or 16-bit with in_is_16) [B][S][C], rows >= S zero
+extern "C" int dmx_test_cast_pad_rows(const void* in, int in_is_16, void* out, int B, int S, int Spad, int C, dmx_stream_t stream) {
+  DMX_REQUIRE(in && out && B > 0 && S > 0 && Spad >= S && C > 0, "test_cast_pad_rows: bad argument");
+  return dmx_cast_pad_rows_launch(in, in_is_16, (bf16*)out, B, S, Spad, C, ST(stream));
 }

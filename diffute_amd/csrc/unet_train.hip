@@ -524,6 +524,7 @@ int dmx_param_grad_export(const ParamTable& pt, const void* grads, const char* n
     case PackRule::GEGLU_W: kind = 3; break;
     case PackRule::GEGLU_B: kind = 4; cols = 0; break;
   }
+  DMX_REQUIRE(kind < 3 || rows % 64 == 0, "grad_export: %s: geglu packing needs rows %% 64 == 0, got %d", name, rows);
   const size_t total = (kind == 1) ? (size_t)rows * cols * r.ks * r.ks : (size_t)rows * (cols > 0 ? cols : 1);
   int blocks = (int)((total + 255) / 256); if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(dmx_grad_unpack_kernel, dim3(blocks), dim3(256), 0, stream, g, dst, kind, rows, cols, r.ks, r.ld, r.koff);

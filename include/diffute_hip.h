@@ -91,6 +91,12 @@ int dmx_test_linear_small_bwd(const float* x, int ldx, const float* dy, int lddy
 int dmx_test_slice_cast(const float* in, int ldin, void* out, int ldo, int M, int C, dmx_stream_t stream);
 int dmx_test_mode_bwd(const void* dz, int lddz, float* dmom, int M, int C, dmx_stream_t stream);
 int dmx_test_bf16_to_f32_rows(const void* in, int ldin, float* out, int M, int C, dmx_stream_t stream);
+/* the weight-preparation kernels only the model executors launch (tests/test_weight_pack_gpu.py).  Folded LayerNorm: w_out (16) [N][K] =
+ * round16(w_raw (16) [N][K] * gamma[k]), c1[n] = sum_k w_out[n][k], c2[n] = sum_k beta[k] * w_raw[n][k] (+ bias[n], bias may be NULL); K a
+ * multiple of 8.  Context cast: out (16) [B][Spad][C] = in [B][S][C] (fp32, or 16-bit when in_is_16), rows >= S zero. */
+int dmx_test_ln_fold(const void* w_raw, void* w_out, const float* gamma, const float* beta, const float* bias, float* c1, float* c2,
+                     int N, int K, dmx_stream_t stream);
+int dmx_test_cast_pad_rows(const void* in, int in_is_16, void* out, int B, int S, int Spad, int C, dmx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Operator level.  Used by the parity tests and by the executors.
