@@ -313,6 +313,8 @@ _PROTOS = {
 # the model lifecycle every handle shares (DMX_MODEL_ABI in include/diffute_hip.h); the UNet's finalize also takes the frequency table
 # words of the decoder's beam state block (include/diffute_hip.h DMX_TROCR_BEAM_*)
 BEAM_RUN_SCORE, BEAM_FIN_SCORE, BEAM_FIN_FLAG, BEAM_FIN_LEN, BEAM_IMPROVABLE, BEAM_PARENT, BEAM_STEPS, BEAM_WORDS = 0, 64, 128, 192, 256, 320, 580, 640
+# int32 state words at the start of the decoder's cache (include/diffute_hip.h DMX_TROCR_STATE_*)
+STATE_POS, STATE_DONE, STATE_STOP_LEN, STATE_TOKENS, STATE_FINISHED = 0, 1, 2, 16, 80
 
 for _kind, _cfg in (("unet", UNetConfig), ("vae", VAEConfig), ("vit", ViTConfig), ("trocr_dec", TrOCRDecConfig)):
     _PROTOS.update({

@@ -11,7 +11,8 @@
 //                 which also applies the epilogue: bias [+ act] | q-scale + K/V-cache write | + residual and, through a second
 //                 counter over the tiles, the row LayerNorm | logits + per-block (max, lowest index) and the greedy pick.
 //   dec_attn    - one query row per (b, head), d = 64, split over 64-key chunks; the last chunk block combines in chunk order.
-//   dec_embed   - token + position (+ scale) + layernorm_embedding, token and position read from device memory.
+//   dec_embed   - token + position (+ scale) + layernorm_embedding, token and position read from device memory (the row's
+//                 arithmetic, the wave reductions and the greedy order are in trocr_dec.h, shared with the prefill).
 // Per step: 1 + 8 per layer + 1 launches; the counters reset themselves, so one captured graph replays every step.
 // Beam search (rows = items x beams) runs the same step with an LM head that writes fp32 logits + log-sum-exp partials, one
 //   beam_select launch (top 2 x beams candidates per item, running / finished bookkeeping, loop condition) and an ancestry table through which
@@ -25,8 +26,9 @@
 namespace {
 enum { EPI_STORE = 0, EPI_QKV = 1, EPI_LN = 2, EPI_PICK = 3, EPI_BEAM = 4 };
 enum { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2 };
-// state words at the start of the cache (DMX_TROCR_STATE_* in the header)
-enum { ST_POS = 0, ST_DONE = 1, ST_STOP = 2, ST_TOK = 16, ST_FIN = 16 + 64, ST_INTS = 256 };
+// state words at the start of the cache: the public header's names, and the words reserved for them in front of the counters
+enum { ST_POS = DMX_TROCR_STATE_POS, ST_DONE = DMX_TROCR_STATE_DONE, ST_STOP = DMX_TROCR_STATE_STOP_LEN, ST_TOK = DMX_TROCR_STATE_TOKENS,
+       ST_FIN = DMX_TROCR_STATE_FINISHED, ST_INTS = 256 };
 // beam state block (DMX_TROCR_BEAM_* in the header): int32 / fp32 words, then the token history int32 [max_len][64], the
 // finished ids int32 [64][max_len] and the two ancestry tables uint8 [2][64][max_len]
 enum { BS_RUN = 0, BS_FSC = 64, BS_FFLAG = 128, BS_FLEN = 192, BS_IMPR = 256, BS_PARENT = 320, BS_FULL = 384, BS_HIT = 448,
@@ -53,20 +55,6 @@ struct DecLin {
   // EPI_BEAM: logits -> yf; per-block (max, sum exp(x - max)) -> pv, psum [M][gridDim.x]
   float* psum;
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
-  return v;
-}
-// greedy order: larger value first, equal values -> lower index (torch.argmax); NaN never wins
-__device__ __forceinline__ bool pick_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-__device__ __forceinline__ void pick_merge(float& bv, int& bi, float v, int i) { if (pick_better(v, i, bv, bi)) { bv = v; bi = i; } }
 
 // Cross-block hand-offs: the data another block of the same launch reads are stored WRITE-THROUGH (sc1 buffer stores) and read
 // with sc1 loads, so publishing needs no agent-scope release / acquire fence (buffer_wbl2 walks the whole L2, buffer_inv drops it:
@@ -492,36 +480,14 @@ __global__ __launch_bounds__(64) void dmx_dec_attn_kernel(DecAttn a) {
   a.o[(size_t)b * a.ldo + h * 64 + lane] = (bf16)(acc / den);
 }
 
-// x = LN(embed[tok] * scale + pos_table[pos + 2]) (LN skipped without gamma): one wave per row
+// x = LN(embed[tok] * scale + pos_table[pos + 2]) (LN skipped without gamma): one wave per row (dec_embed_row), token and
+// position read from the state words
 __global__ __launch_bounds__(64) void dmx_dec_embed_kernel(const int* state, const bf16* emb, int V, const float* posw, int npos, float scale,
                                                            const float* gamma, const float* beta, int D, float* yf, bf16* yb) {
-  const int lane = threadIdx.x, m = blockIdx.x, nper = D >> 6;
+  const int lane = threadIdx.x, m = blockIdx.x;
   int tok = state[ST_TOK + m]; tok = min(max(tok, 0), V - 1);
   const int prow = min(state[ST_POS] + 2, npos - 1);
-  float v[16];
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {                                // (clamped, unconditional loads: all in flight together)
-    const int n = min(j, nper - 1) * 64 + lane;
-    v[j] = (float)emb[(size_t)tok * D + n] * scale + posw[(size_t)prow * D + n];
-  }
-#pragma unroll
-  for (int j = 0; j < 16; ++j) if (j < nper) s += v[j];
-  if (gamma) {
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) if (j < nper) { const float d = v[j] - mean; q += d * d; }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + 1e-5f);
-#pragma unroll
-    for (int j = 0; j < 16; ++j) if (j < nper) { const int n = j * 64 + lane; v[j] = (v[j] - mean) * rstd * gamma[n] + beta[n]; }
-  }
-#pragma unroll
-  for (int j = 0; j < 16; ++j) if (j < nper) {
-    const int n = j * 64 + lane;
-    yf[(size_t)m * D + n] = v[j];
-    yb[(size_t)m * D + n] = (bf16)v[j];
-  }
+  dec_embed_row(tok, prow, lane, m, emb, posw, scale, gamma, beta, D, yf, yb);
 }
 
 // zero the counters / state, every row starts from `start`
@@ -529,9 +495,6 @@ __global__ __launch_bounds__(256) void dmx_dec_reset_kernel(int* words, size_t n
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += (size_t)gridDim.x * blockDim.x)
     words[i] = (i >= ST_TOK && i < (size_t)ST_TOK + B) ? start : 0;
   if (blockIdx.x == 0 && (int)threadIdx.x < B && ids) ids[(size_t)threadIdx.x * max_len] = start;
-}
-__global__ __launch_bounds__(256) void dmx_f32_to_bf16_kernel(const float* in, bf16* out, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = (bf16)in[i];
 }
 __global__ __launch_bounds__(256) void dmx_i64_to_i32_kernel(const long long* in, int* out, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -843,6 +806,17 @@ DecLayout dec_layout(const dmx_trocr_dec* d, int B, int S, int max_len) {
   return y;
 }
 
+// cross K/V of every layer, once per image: the encoder states as bf16 (encb), then one GEMM at B * S rows
+int cross_kv_launch(const dmx_trocr_dec* d, const float* enc, int B, int S, bf16* encb, char* gemm_ws, size_t gemm_ws_bytes, void* ckv_out,
+                    hipStream_t stream) {
+  const int rc = dmx_cast_f32_to_bf16_launch(enc, encb, (size_t)B * S * d->kdim, stream);
+  if (rc) return rc;
+  Exec ex = Exec::on(stream, gemm_ws, gemm_ws_bytes);
+  const int N = 2 * d->cfg.num_layers * d->cfg.d_model;
+  ex.gemm_raw(encb, d->kdim, B * S, d->at<bf16>(d->wckv), d->kdim, N, d->kdim, d->at<float>(d->bckv), ckv_out, N, 0);
+  return ex.rc;
+}
+
 int dec_attn_launch(const DecAttn& a0, int M, hipStream_t stream) {
   DecAttn a = a0; a.M = M;
   hipLaunchKernelGGL(dmx_dec_attn_kernel, dim3(a.nch, a.H, M), dim3(64), 0, stream, a);
@@ -912,6 +886,12 @@ int dec_step(dmx_trocr_dec* d, char* cache, int B, int S, int max_len, int eos, 
                      c.layernorm_embedding ? d->at<float>(d->leg) : nullptr, c.layernorm_embedding ? d->at<float>(d->leb) : nullptr, D, xf, xb);
   int rc = dmx_check_launch("dmx_dec_embed_kernel");
   const int act = c.activation == 1 ? ACT_RELU : ACT_GELU;
+  // x = LN(x + in w^T + bias): the residual stream xf / xb rewritten in place by the linear's LayerNorm epilogue
+  auto ln_linear = [&](const bf16* in, int K, size_t w, size_t bias, size_t gamma, size_t beta) {
+    DecLin a = lin_base(in, B, K, d->at<bf16>(w), D, d->at<float>(bias), EPI_LN, next_cnt(), part);
+    a.res = xf; a.pre = pre; a.gamma = d->at<float>(gamma); a.beta = d->at<float>(beta); a.yf = xf; a.yb = xb;
+    return dec_linear_launch(a, st);
+  };
   for (int l = 0; l < L && !rc; ++l) {
     const DecLayer& W = d->layers[l];
     bf16* kvl = kv + (size_t)l * B * max_len * 2 * D;
@@ -923,24 +903,18 @@ int dec_step(dmx_trocr_dec* d, char* cache, int B, int S, int max_len, int eos, 
     t.nch = y.nch_self; t.part = apart; t.cnt = next_cnt(); t.o = ab; t.ldo = D;
     if (bm) { t.src = beam_src_host(bstate, max_len); t.src_ld = max_len; }
     if ((rc = dec_attn_launch(t, B, st))) break;
-    a = lin_base(ab, B, D, d->at<bf16>(W.wo), D, d->at<float>(W.bo), EPI_LN, next_cnt(), part);
-    a.res = xf; a.pre = pre; a.gamma = d->at<float>(W.l1g); a.beta = d->at<float>(W.l1b); a.yf = xf; a.yb = xb;
-    if ((rc = dec_linear_launch(a, st))) break;
+    if ((rc = ln_linear(ab, D, W.wo, W.bo, W.l1g, W.l1b))) break;
     a = lin_base(xb, B, D, d->at<bf16>(W.wcq), D, d->at<float>(W.bcq), EPI_STORE, next_cnt(), part);
     a.oscale = qscale; a.yf = qf; a.ldyf = D;
     if ((rc = dec_linear_launch(a, st))) break;
     t.kv = ckv + (size_t)l * 2 * D; t.bstride = (long long)S * L * 2 * D; t.rstride = L * 2 * D; t.state = nullptr; t.L = S;
     t.nch = y.nch_cross; t.cnt = next_cnt(); t.src = nullptr; t.rpi = bm ? bm->nb : 0;
     if ((rc = dec_attn_launch(t, B, st))) break;
-    a = lin_base(ab, B, D, d->at<bf16>(W.wco), D, d->at<float>(W.bco), EPI_LN, next_cnt(), part);
-    a.res = xf; a.pre = pre; a.gamma = d->at<float>(W.l2g); a.beta = d->at<float>(W.l2b); a.yf = xf; a.yb = xb;
-    if ((rc = dec_linear_launch(a, st))) break;
+    if ((rc = ln_linear(ab, D, W.wco, W.bco, W.l2g, W.l2b))) break;
     a = lin_base(xb, B, D, d->at<bf16>(W.w1), F, d->at<float>(W.b1), EPI_STORE, next_cnt(), part);
     a.act = act; a.yb = hb; a.ldyb = F;
     if ((rc = dec_linear_launch(a, st))) break;
-    a = lin_base(hb, B, F, d->at<bf16>(W.w2), D, d->at<float>(W.b2), EPI_LN, next_cnt(), part);
-    a.res = xf; a.pre = pre; a.gamma = d->at<float>(W.l3g); a.beta = d->at<float>(W.l3b); a.yf = xf; a.yb = xb;
-    if ((rc = dec_linear_launch(a, st))) break;
+    if ((rc = ln_linear(hb, F, W.w2, W.b2, W.l3g, W.l3b))) break;
   }
   if (rc) return rc;
   if (bm) {
@@ -1020,16 +994,8 @@ extern "C" int dmx_trocr_dec_cross_kv(dmx_trocr_dec* d, const float* enc, int B,
               "trocr_dec_cross_kv: bad argument (B=%d S=%d max_len=%d)", B, S, max_len);
   const DecLayout y = dec_layout(d, B, S, max_len);
   DMX_REQUIRE(ws_bytes >= y.ws_total, "trocr_dec_cross_kv: workspace %zu < %zu bytes", ws_bytes, y.ws_total);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t n = (size_t)B * S * d->kdim;
-  bf16* eb = (bf16*)((char*)ws + y.encb);
-  hipLaunchKernelGGL(dmx_f32_to_bf16_kernel, dim3((unsigned)std::min<size_t>(8192, (n + 255) / 256)), dim3(256), 0, st, enc, eb, n);
-  int rc = dmx_check_launch("dmx_f32_to_bf16_kernel");
-  if (rc) return rc;
-  Exec ex = Exec::on(st, (char*)ws + y.gemm_ws, ws_bytes - y.gemm_ws);
-  const int N = 2 * d->cfg.num_layers * d->cfg.d_model;
-  ex.gemm_raw(eb, d->kdim, B * S, d->at<bf16>(d->wckv), d->kdim, N, d->kdim, d->at<float>(d->bckv), (char*)cache + y.ckv, N, 0);
-  return ex.rc;
+  return cross_kv_launch(d, enc, B, S, (bf16*)((char*)ws + y.encb), (char*)ws + y.gemm_ws, ws_bytes - y.gemm_ws, (char*)cache + y.ckv,
+                         (hipStream_t)stream);
 }
 extern "C" int dmx_trocr_dec_reset(dmx_trocr_dec* d, void* cache, int B, int S, int max_len, int start_token, long long* ids, dmx_stream_t stream) {
   DMX_REQUIRE(d && cache && B >= 1 && B <= 64, "trocr_dec_reset: bad argument");
@@ -1077,15 +1043,9 @@ extern "C" int dmx_trocr_dec_beam_begin(dmx_trocr_dec* d, const float* enc, int 
   DMX_REQUIRE(ws_bytes >= z.ws_total, "trocr_dec_beam_begin: workspace %zu < %zu bytes", ws_bytes, z.ws_total);
   hipStream_t st = (hipStream_t)stream;
   // cross K/V once per item: the GEMM runs at B * S rows
-  const size_t n = (size_t)B * S * d->kdim;
-  bf16* eb = (bf16*)((char*)ws + z.y.encb);
-  hipLaunchKernelGGL(dmx_f32_to_bf16_kernel, dim3((unsigned)std::min<size_t>(8192, (n + 255) / 256)), dim3(256), 0, st, enc, eb, n);
-  int rc = dmx_check_launch("dmx_f32_to_bf16_kernel");
+  const int rc = cross_kv_launch(d, enc, B, S, (bf16*)((char*)ws + z.y.encb), (char*)ws + z.y.gemm_ws, ws_bytes - z.y.gemm_ws,
+                                 (char*)cache + z.y.ckv, st);
   if (rc) return rc;
-  Exec ex = Exec::on(st, (char*)ws + z.y.gemm_ws, ws_bytes - z.y.gemm_ws);
-  const int N = 2 * d->cfg.num_layers * d->cfg.d_model;
-  ex.gemm_raw(eb, d->kdim, B * S, d->at<bf16>(d->wckv), d->kdim, N, d->kdim, d->at<float>(d->bckv), (char*)cache + z.y.ckv, N, 0);
-  if (ex.rc) return ex.rc;
   const size_t nwords = (z.y.kv - z.y.words) / 4, bwords = beam_state_bytes(max_len) / 4;
   hipLaunchKernelGGL(dmx_dec_beam_reset_kernel, dim3((unsigned)std::min<size_t>(1024, (std::max(nwords, bwords) + 255) / 256)), dim3(256), 0, st,
                      (int*)((char*)cache + z.y.words), nwords, B * nb, nb, start_token, (int*)((char*)cache + z.bstate), bwords, max_len);
@@ -1143,14 +1103,9 @@ extern "C" int dmx_trocr_dec_beam_select(const float* logits, int B, int nb, int
   q.eos = eos_token_id; q.early = early_stopping; q.lp = length_penalty; q.state = state; q.bs = (int*)beam_state; q.logp = logp;
   return beam_select_launch(q, st);
 }
-// decode attention with the beam indirections: table (nullable) uint8 [M][ld_table] - key j < L - 1 of row b from physical row
-// table[b][j], key L - 1 from row b -, rows_per_item > 0: row b reads the K/V of item b / rows_per_item
-extern "C" int dmx_trocr_dec_beam_attn(const float* q, int M, int H, const void* kv, long long bstride, int rstride, int L, const void* table,
-                                       int ld_table, int rows_per_item, void* out, void* ws, size_t ws_bytes, dmx_stream_t stream) {
-  DMX_REQUIRE(q && kv && out && ws && M >= 1 && M <= 64 && H >= 1 && L >= 1 && rstride >= 2 * H * 64 && rows_per_item >= 0, "trocr_dec_beam_attn: bad argument");
-  DMX_REQUIRE(!table || ld_table >= L - 1, "trocr_dec_beam_attn: ld_table %d < L - 1", ld_table);
-  DMX_REQUIRE(ws_bytes >= dmx_trocr_dec_attn_workspace_bytes(M, H, L), "trocr_dec_beam_attn: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
+// the body of both decode-attention op entries (arguments checked by the entry): counters zeroed, then one launch
+static int attn_op(const float* q, int M, int H, const void* kv, long long bstride, int rstride, int L, const void* table, int ld_table,
+                   int rows_per_item, void* out, void* ws, hipStream_t st) {
   int* cnt = (int*)ws;
   hipLaunchKernelGGL(dmx_dec_reset_kernel, dim3(1), dim3(256), 0, st, cnt, (size_t)M * H, 0, 0, (long long*)nullptr, 1);
   int rc = dmx_check_launch("dmx_dec_reset_kernel");
@@ -1160,6 +1115,15 @@ extern "C" int dmx_trocr_dec_beam_attn(const float* q, int M, int H, const void*
   t.nch = cdiv(L, 64); t.part = (float*)((char*)ws + align_up((size_t)M * H * 4, 256)); t.cnt = cnt; t.o = (bf16*)out; t.ldo = H * 64;
   t.src = (const unsigned char*)table; t.src_ld = ld_table; t.rpi = rows_per_item;
   return dec_attn_launch(t, M, st);
+}
+// decode attention with the beam indirections: table (nullable) uint8 [M][ld_table] - key j < L - 1 of row b from physical row
+// table[b][j], key L - 1 from row b -, rows_per_item > 0: row b reads the K/V of item b / rows_per_item
+extern "C" int dmx_trocr_dec_beam_attn(const float* q, int M, int H, const void* kv, long long bstride, int rstride, int L, const void* table,
+                                       int ld_table, int rows_per_item, void* out, void* ws, size_t ws_bytes, dmx_stream_t stream) {
+  DMX_REQUIRE(q && kv && out && ws && M >= 1 && M <= 64 && H >= 1 && L >= 1 && rstride >= 2 * H * 64 && rows_per_item >= 0, "trocr_dec_beam_attn: bad argument");
+  DMX_REQUIRE(!table || ld_table >= L - 1, "trocr_dec_beam_attn: ld_table %d < L - 1", ld_table);
+  DMX_REQUIRE(ws_bytes >= dmx_trocr_dec_attn_workspace_bytes(M, H, L), "trocr_dec_beam_attn: workspace too small");
+  return attn_op(q, M, H, kv, bstride, rstride, L, table, ld_table, rows_per_item, out, ws, (hipStream_t)stream);
 }
 
 // ---- op entry points (tests / benchmarks): one weight-streaming linear with a chosen epilogue, one decode attention
@@ -1202,13 +1166,5 @@ extern "C" int dmx_trocr_dec_attn(const float* q, int M, int H, const void* kv, 
                                   void* ws, size_t ws_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(q && kv && out && ws && M >= 1 && H >= 1 && L >= 1 && rstride >= 2 * H * 64, "trocr_dec_attn: bad argument");
   DMX_REQUIRE(ws_bytes >= dmx_trocr_dec_attn_workspace_bytes(M, H, L), "trocr_dec_attn: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  int* cnt = (int*)ws;
-  hipLaunchKernelGGL(dmx_dec_reset_kernel, dim3(1), dim3(256), 0, st, cnt, (size_t)M * H, 0, 0, (long long*)nullptr, 1);
-  int rc = dmx_check_launch("dmx_dec_reset_kernel");
-  if (rc) return rc;
-  DecAttn t{};
-  t.q = q; t.ldq = H * 64; t.kv = (const bf16*)kv; t.bstride = bstride; t.rstride = rstride; t.state = nullptr; t.L = L; t.H = H; t.D = H * 64;
-  t.nch = cdiv(L, 64); t.part = (float*)((char*)ws + align_up((size_t)M * H * 4, 256)); t.cnt = cnt; t.o = (bf16*)out; t.ldo = H * 64;
-  return dec_attn_launch(t, M, st);
+  return attn_op(q, M, H, kv, bstride, rstride, L, nullptr, 0, 0, out, ws, (hipStream_t)stream);
 }

@@ -9,7 +9,7 @@
 //   lm_tile       - x[M][K] W[V][K]^T on MFMA, 64 rows x 64 vocabulary entries per block; per (row, tile): (max, sum exp(x - max)),
 //                   (best value, lowest index), the label's logit where the label falls in the tile; fp32 logits only on request
 //   lm_combine    - one wave per row merges the tile partials in tile order: log-sum-exp, arg-max (ties -> lowest index, pick_better
-//                   of trocr_dec.hip), token_logprob = logit[label] - lse.  No counters, no float atomics: two plain launches.
+//                   of trocr_dec.h), token_logprob = logit[label] - lse.  No counters, no float atomics: two plain launches.
 // The layers (post-LN, tests/trocr_restatement._layers) are the GEMM / attention / cast kernels of the other models at fixed plans
 // (one tile instance, no K split: a row's arithmetic does not depend on how many rows run with it), with the residual stream in
 // fp32 as on the step path: x = LN(x + y) reads the GEMM's fp32 output and writes the fp32 stream and its 16-bit copy.
@@ -20,55 +20,18 @@
 namespace {
 constexpr int kMaxRows = 4096, kMaxItems = 64, kMaxT = 512;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
-  return v;
-}
-// larger value first, equal values -> lower index (torch.argmax); NaN never wins
-__device__ __forceinline__ bool pick_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-__device__ __forceinline__ void pick_merge(float& bv, int& bi, float v, int i) { if (pick_better(v, i, bv, bi)) { bv = v; bi = i; } }
-
-// ---- embedding of a [B][T] block: one wave per row; the arithmetic of dmx_dec_embed_kernel
+// ---- embedding of a [B][T] block: one wave per row (dec_embed_row), the token from the shifted labels, the position from the row
 __global__ __launch_bounds__(64) void dmx_prefill_embed_kernel(const long long* labels, const long long* dec_ids, int T, int start, int pad, int ignore,
                                                                const bf16* emb, int V, const float* posw, int npos, float scale,
                                                                const float* gamma, const float* beta, int D, float* yf, bf16* yb) {
-  const int lane = threadIdx.x, m = blockIdx.x, t = m % T, nper = D >> 6;
+  const int lane = threadIdx.x, m = blockIdx.x, t = m % T;
   long long id;
   if (dec_ids) id = dec_ids[m];
   else if (t == 0) id = start;
   else { id = labels[m - 1]; if (id == (long long)ignore) id = pad; }
   const int tok = id < 0 ? 0 : id >= V ? V - 1 : (int)id;
   const int prow = min(t + 2, npos - 1);
-  float v[16];
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const int n = min(j, nper - 1) * 64 + lane;
-    v[j] = (float)emb[(size_t)tok * D + n] * scale + posw[(size_t)prow * D + n];
-  }
-#pragma unroll
-  for (int j = 0; j < 16; ++j) if (j < nper) s += v[j];
-  if (gamma) {
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) if (j < nper) { const float d = v[j] - mean; q += d * d; }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + 1e-5f);
-#pragma unroll
-    for (int j = 0; j < 16; ++j) if (j < nper) { const int n = j * 64 + lane; v[j] = (v[j] - mean) * rstd * gamma[n] + beta[n]; }
-  }
-#pragma unroll
-  for (int j = 0; j < 16; ++j) if (j < nper) {
-    const int n = j * 64 + lane;
-    yf[(size_t)m * D + n] = v[j];
-    yb[(size_t)m * D + n] = (bf16)v[j];
-  }
+  dec_embed_row(tok, prow, lane, m, emb, posw, scale, gamma, beta, D, yf, yb);
 }
 
 // ---- x = LN(x + y) over rows of D = 64 nper values (D % 256 == 0, D <= 1024): one wave per row, lane -> columns lane * nper + e.
@@ -378,7 +341,7 @@ extern "C" int dmx_trocr_dec_score(dmx_trocr_dec* d, const float* enc, int B, in
   char* w = (char*)ws;
   bf16* encb = (bf16*)(w + y.encb); bf16* ckv = (bf16*)(w + y.ckv); float* xf = (float*)(w + y.xf); bf16* xb = (bf16*)(w + y.xb);
   float* yf = (float*)(w + y.y); bf16* qkv = (bf16*)(w + y.qkv); bf16* ab = (bf16*)(w + y.ab); bf16* qc = (bf16*)(w + y.qc); bf16* hb = (bf16*)(w + y.hb);
-  // cross K/V of every layer: one GEMM at B * S rows, as dmx_trocr_dec_cross_kv
+  // cross K/V of every layer: one GEMM at B * S rows, as the step path's cross_kv_launch but on the fixed plan
   int rc = dmx_cast_f32_to_bf16_launch(enc, encb, (size_t)B * S * d->kdim, st);
   if (rc) return rc;
   const int Nkv = 2 * L * D;

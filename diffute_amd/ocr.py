@@ -4,6 +4,8 @@ app.ipynb:547-548 builds two models from `trocr-large-printed`: `.encoder` (the 
 `VisionEncoderDecoderModel`, whose `generate(pixel_values)` reads an edited box back as token ids (app.ipynb:842-847; the
 tokenizer's `batch_decode` stays with the caller).  `from diffute_amd import VisionEncoderDecoderModel` serves both.
 Greedy generation follows transformers' `generate(num_beams=1, do_sample=False)`; every FLOP runs in the gfx950 library.
+The host side of the decoder is shared: `_cached_run` keys the buffers of a run, `_decode_loop` drives greedy and beam search alike
+(step graph, replay, the device's all-finished flag), `_check_enc_shape` checks encoder states for every entry.
 """
 import ctypes
 import json
@@ -33,7 +35,19 @@ _BEAM_ONLY = ("early_stopping", "length_penalty", "num_beam_groups")
 # the settings beam_search() implements itself (every other non-default entry of _GEN_UNSUPPORTED stays refused there too)
 _BEAM_SEARCH_OWN = ("num_beams", "length_penalty", "early_stopping", "num_return_sequences")
 
-POLL_EVERY = 4          # generate() reads the device's all-finished flag (copied asynchronously) every POLL_EVERY steps
+POLL_EVERY = 4          # a decode loop reads the device's all-finished flag (copied asynchronously) every POLL_EVERY steps
+
+
+def _eos_pad(eos_token_id, pad_token_id):
+    """the (eos, pad) ids a step takes: no eos = -1, pad defaults to eos, and to 0 without either"""
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    pad = eos if pad_token_id is None else int(pad_token_id)
+    return eos, max(pad, 0)
+
+
+def _state_words(r):
+    """int32 view of a run's state words (include/diffute_hip.h DMX_TROCR_STATE_*) up to the finished flags"""
+    return r["cache"][:4 * _cabi.STATE_FINISHED].view(torch.int32)
 
 
 class CausalLMOutput:
@@ -109,20 +123,24 @@ class TrOCRForCausalLM(_HipModel):
     def launches_per_step(self):
         return int(self._lib.dmx_trocr_dec_launches_per_step(self._h))
 
-    # ---- buffers of one (B, S, max_len): cache (state words, self / cross K/V), workspace, output ids, optional logits row
-    def _run(self, B, S, max_len):
-        key = (B, S, max_len)
+    def _cached_run(self, key, make):
+        """the buffers of one run, made once per key and set of weights"""
         if self._runs_epoch != self._epoch:      # runs (and their captured graphs) of earlier weights
             self._runs, self._runs_epoch = {}, self._epoch
         r = self._runs.get(key)
         if r is None:
-            lib, dev = self._lib, self.device
-            r = dict(cache=torch.empty(lib.dmx_trocr_dec_cache_bytes(self._h, B, S, max_len), dtype=torch.uint8, device=dev),
-                     ws=torch.empty(lib.dmx_trocr_dec_workspace_bytes(self._h, B, S, max_len), dtype=torch.uint8, device=dev),
-                     ids=torch.zeros(B, max_len, dtype=torch.int64, device=dev),
-                     logits=torch.empty(B, self.config.vocab_size, dtype=torch.float32, device=dev), graphs={})
-            self._runs[key] = r
+            r = self._runs[key] = make()
         return r
+
+    # ---- buffers of one (B, S, max_len): cache (state words, self / cross K/V), workspace, output ids, optional logits row
+    def _run(self, B, S, max_len):
+        def make():
+            lib, dev = self._lib, self.device
+            return dict(cache=torch.empty(lib.dmx_trocr_dec_cache_bytes(self._h, B, S, max_len), dtype=torch.uint8, device=dev),
+                        ws=torch.empty(lib.dmx_trocr_dec_workspace_bytes(self._h, B, S, max_len), dtype=torch.uint8, device=dev),
+                        ids=torch.zeros(B, max_len, dtype=torch.int64, device=dev),
+                        logits=torch.empty(B, self.config.vocab_size, dtype=torch.float32, device=dev), graphs={})
+        return self._cached_run((B, S, max_len), make)
 
     def _begin(self, r, enc, max_len, start):
         lib = self._lib
@@ -137,15 +155,22 @@ class TrOCRForCausalLM(_HipModel):
                                                  None if logits is None else ctypes.c_void_p(logits), ld, _cabi.ptr(r["ws"]),
                                                  r["ws"].numel(), _cabi.current_stream()), "trocr_dec_step")
 
+    def _check_enc_shape(self, enc_shape, rows_per_item=1):
+        """encoder states (a tensor or its shape) must be [B, S, kdim] with B * rows_per_item of the decoder's 64 rows"""
+        shape = tuple(getattr(enc_shape, "shape", enc_shape))
+        kdim = self.config.cross_attention_hidden_size or self.config.d_model
+        if len(shape) != 3 or shape[2] != kdim:
+            raise ValueError(f"encoder_hidden_states must be [B, S, {kdim}], got {shape}")
+        if not 1 <= shape[0] or shape[0] * rows_per_item > 64:
+            raise ValueError(f"TrOCRForCausalLM: 1 <= batch <= 64 rows, got {shape[0]}" if rows_per_item == 1 else
+                             f"beam_search: batch * num_beams = {shape[0]} * {rows_per_item} exceeds the decoder's 64 rows")
+        return shape
+
     def _check_inputs(self, enc):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError("diffute_amd: the OCR decoder is forward-only")
         _cabi.require_cuda(enc)
-        kdim = self.config.cross_attention_hidden_size or self.config.d_model
-        if enc.ndim != 3 or enc.shape[2] != kdim:
-            raise ValueError(f"encoder_hidden_states must be [B, S, {kdim}], got {tuple(enc.shape)}")
-        if not 1 <= enc.shape[0] <= 64:
-            raise ValueError(f"TrOCRForCausalLM: 1 <= batch <= 64 rows, got {enc.shape[0]}")
+        self._check_enc_shape(enc)
         self._ensure_packed()
         return enc.to(torch.float32).contiguous()
 
@@ -170,12 +195,7 @@ class TrOCRForCausalLM(_HipModel):
 
     def _check_score_args(self, enc_shape, labels, decoder_input_ids, ignore_index):
         """every shape / dtype / range check of score(), on the host side: nothing is launched before it passes"""
-        kdim = self.config.cross_attention_hidden_size or self.config.d_model
-        if len(enc_shape) != 3 or enc_shape[2] != kdim:
-            raise ValueError(f"encoder_hidden_states must be [B, S, {kdim}], got {tuple(enc_shape)}")
-        B = enc_shape[0]
-        if not 1 <= B <= 64:
-            raise ValueError(f"TrOCRForCausalLM: 1 <= batch <= 64 rows, got {B}")
+        B = self._check_enc_shape(enc_shape)[0]
         if enc_shape[1] < 1:
             raise ValueError("encoder_hidden_states has no rows")
         if labels is None and decoder_input_ids is None:
@@ -225,13 +245,8 @@ class TrOCRForCausalLM(_HipModel):
         dev, S, V = enc.device, enc.shape[1], self.config.vocab_size
         lab = None if labels is None else labels.to(dev).contiguous()
         dids = None if decoder_input_ids is None else decoder_input_ids.to(dev).contiguous()
-        key = ("score", B, S, T)
-        if self._runs_epoch != self._epoch:
-            self._runs, self._runs_epoch = {}, self._epoch
-        r = self._runs.get(key)
-        if r is None:
-            r = dict(ws=torch.empty(self._lib.dmx_trocr_dec_prefill_workspace_bytes(self._h, B, S, T), dtype=torch.uint8, device=dev))
-            self._runs[key] = r
+        r = self._cached_run(("score", B, S, T), lambda: dict(
+            ws=torch.empty(self._lib.dmx_trocr_dec_prefill_workspace_bytes(self._h, B, S, T), dtype=torch.uint8, device=dev)))
         logp = None if lab is None else torch.empty(B, T, dtype=torch.float32, device=dev)
         amax = torch.empty(B, T, dtype=torch.int32, device=dev)
         logits = torch.empty(B, T, V, dtype=torch.float32, device=dev) if return_logits else None
@@ -244,6 +259,47 @@ class TrOCRForCausalLM(_HipModel):
         seq = logp.sum(1)
         return ScoreOutput(logp, seq, n, amax.long(), -logp.sum() / n.sum(), logits)
 
+    def _decode_loop(self, r, gkey, step, n_steps, use_graph, after_step=None, finish=None):
+        """Enqueue up to n_steps calls of `step()` on the run r, as replays of one graph captured under r["graphs"][gkey] with
+        use_graph; after_step(i) follows step i = 1, 2, ... and finish() the last one.  Returns (steps enqueued, done, stop_len):
+        the device's all-finished flag and stop length, read once after everything enqueued has run."""
+        if use_graph and gkey not in r["graphs"]:
+            # one linear chain of kernels, captured on a side stream; the tokens, the position, the scores and the counters live in
+            # device memory, so the same graph replays every step
+            main, side = torch.cuda.current_stream(), torch.cuda.Stream(device=r["cache"].device)
+            side.wait_stream(main)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+                step()
+            main.wait_stream(side)
+            r["graphs"][gkey] = g
+        run = r["graphs"][gkey].replay if use_graph else step
+        flags = _state_words(r)[_cabi.STATE_DONE:_cabi.STATE_STOP_LEN + 1]
+        # every POLL_EVERY steps the all-finished flag is copied to pinned memory behind an event; before more steps are enqueued
+        # the host waits for the copy of POLL_EVERY steps back, so at most 2 * POLL_EVERY steps are in flight and a batch that
+        # has finished stops within that many steps instead of running to max_length
+        polls, steps = [], 0
+        while steps < n_steps:
+            run()
+            steps += 1
+            if after_step is not None:
+                after_step(steps)
+            if steps % POLL_EVERY == 0 and steps < n_steps:
+                f = torch.empty(2, dtype=torch.int32, pin_memory=True)
+                f.copy_(flags, non_blocking=True)
+                ev = torch.cuda.Event(); ev.record()
+                polls.append((ev, f))
+                if len(polls) > 1:
+                    ev0, f0 = polls.pop(0)
+                    ev0.synchronize()
+                    if int(f0[0]):
+                        break
+        if finish is not None:
+            finish()
+        flag = torch.empty(2, dtype=torch.int32)
+        flag.copy_(flags)                        # (the one synchronisation at the end)
+        return steps, int(flag[0]), int(flag[1])
+
     @torch.no_grad()
     def greedy(self, encoder_hidden_states, max_length, decoder_start_token_id, eos_token_id, pad_token_id, use_graph=True, keep_logits=False):
         """greedy ids [B, L] (L <= max_length, counting the start token), as transformers' greedy search; with keep_logits also the
@@ -252,58 +308,17 @@ class TrOCRForCausalLM(_HipModel):
         B, S = enc.shape[0], enc.shape[1]
         if not 1 <= max_length <= self.config.max_position_embeddings:
             raise ValueError(f"max_length={max_length}: the decoder has {self.config.max_position_embeddings} positions")
-        eos = -1 if eos_token_id is None else int(eos_token_id)
-        pad = eos if pad_token_id is None else int(pad_token_id)
-        if pad < 0:
-            pad = 0
+        eos, pad = _eos_pad(eos_token_id, pad_token_id)
         r = self._run(B, S, max_length)
         self._begin(r, enc, max_length, decoder_start_token_id)
-        n_steps = max_length - 1
-        if n_steps == 0:
+        if max_length == 1:
             return r["ids"][:, :1].clone(), None
-        V = self.config.vocab_size
         lg = r["logits"] if keep_logits else None
-        lg_ptr = None if lg is None else lg.data_ptr()
-        main = torch.cuda.current_stream()
-        if use_graph:
-            gkey = (eos, pad, keep_logits)
-            g = r["graphs"].get(gkey)
-            if g is None:
-                # one linear chain of kernels, captured on a side stream; the tokens, the position and the counters live in device
-                # memory, so the same graph replays every step
-                side = torch.cuda.Stream(device=enc.device)
-                side.wait_stream(main)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                    self._step(r, B, S, max_length, eos, pad, lg_ptr, V)
-                main.wait_stream(side)
-                r["graphs"][gkey] = g
-        state = r["cache"][:16].view(torch.int32)
-        # every POLL_EVERY steps the all-finished flag is copied to pinned memory behind an event; before more steps are enqueued
-        # the host waits for the copy of POLL_EVERY steps back, so at most 2 * POLL_EVERY steps are in flight and a batch that
-        # has finished stops within that many steps instead of running to max_length
-        polls, steps, kept = [], 0, []
-        while steps < n_steps:
-            if use_graph:
-                r["graphs"][gkey].replay()
-            else:
-                self._step(r, B, S, max_length, eos, pad, lg_ptr, V)
-            steps += 1
-            if keep_logits:
-                kept.append(lg.clone())
-            if steps % POLL_EVERY == 0 and steps < n_steps:
-                f = torch.empty(2, dtype=torch.int32, pin_memory=True)
-                f.copy_(state[1:3], non_blocking=True)
-                ev = torch.cuda.Event(); ev.record()
-                polls.append((ev, f))
-                if len(polls) > 1:
-                    ev0, f0 = polls.pop(0)
-                    ev0.synchronize()
-                    if int(f0[0]):
-                        break
-        flag = torch.empty(2, dtype=torch.int32)
-        flag.copy_(state[1:3])                   # (one synchronisation at the end: the stop length)
-        L = int(flag[1]) if int(flag[0]) else steps + 1
+        lg_ptr, kept = (None if lg is None else lg.data_ptr()), []
+        steps, done, stop_len = self._decode_loop(
+            r, (eos, pad, keep_logits), lambda: self._step(r, B, S, max_length, eos, pad, lg_ptr, self.config.vocab_size), max_length - 1,
+            use_graph, after_step=(lambda i: kept.append(lg.clone())) if keep_logits else None)
+        L = stop_len if done else steps + 1
         ids = r["ids"][:, :L].clone()
         return ids, (torch.stack(kept[:L - 1], 1) if keep_logits else None)
 
@@ -312,14 +327,10 @@ class TrOCRForCausalLM(_HipModel):
     def beam_launches_per_step(self):
         return int(self._lib.dmx_trocr_dec_beam_launches_per_step(self._h))
 
-    def _check_beam_args(self, enc, max_length, num_beams, length_penalty, early_stopping, num_return_sequences):
-        kdim = self.config.cross_attention_hidden_size or self.config.d_model
-        if enc.ndim != 3 or enc.shape[2] != kdim:
-            raise ValueError(f"encoder_hidden_states must be [B, S, {kdim}], got {tuple(enc.shape)}")
+    def _check_beam_args(self, enc_shape, max_length, num_beams, length_penalty, early_stopping, num_return_sequences):
         if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 2 <= num_beams <= 16:
             raise ValueError(f"beam_search: num_beams must be an integer in 2 ... 16, got {num_beams!r}")
-        if not 1 <= enc.shape[0] or enc.shape[0] * num_beams > 64:
-            raise ValueError(f"beam_search: batch * num_beams = {enc.shape[0]} * {num_beams} exceeds the decoder's 64 rows")
+        self._check_enc_shape(enc_shape, num_beams)
         if not 1 <= int(num_return_sequences) <= num_beams:
             raise ValueError(f"beam_search: num_return_sequences={num_return_sequences} must be in 1 ... num_beams")
         if self.config.vocab_size < 2 * num_beams:
@@ -331,11 +342,7 @@ class TrOCRForCausalLM(_HipModel):
         float(length_penalty)
 
     def _beam_run(self, B, nb, S, max_len):
-        key = ("beam", B, nb, S, max_len)
-        if self._runs_epoch != self._epoch:
-            self._runs, self._runs_epoch = {}, self._epoch
-        r = self._runs.get(key)
-        if r is None:
+        def make():
             lib, dev, h = self._lib, self.device, self._h
             nbytes = lib.dmx_trocr_dec_beam_cache_bytes(h, B, nb, S, max_len)
             if not nbytes:
@@ -344,13 +351,12 @@ class TrOCRForCausalLM(_HipModel):
             cache = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             bstate = cache[off:off + lib.dmx_trocr_dec_beam_state_bytes(max_len)]
             W = _cabi.BEAM_WORDS
-            r = dict(cache=cache, ws=torch.empty(lib.dmx_trocr_dec_beam_workspace_bytes(h, B, nb, S, max_len), dtype=torch.uint8, device=dev),
-                     words=bstate[:W * 4].view(torch.int32), fwords=bstate[:W * 4].view(torch.float32),
-                     hist=bstate[W * 4:(W + 64 * max_len) * 4].view(torch.int32).view(max_len, 64),
-                     table=bstate[(W + 128 * max_len) * 4:(W + 160 * max_len) * 4].view(2, 64, max_len),
-                     logp=torch.empty(B * nb, self.config.vocab_size, dtype=torch.float32, device=dev), graphs={})
-            self._runs[key] = r
-        return r
+            return dict(cache=cache, ws=torch.empty(lib.dmx_trocr_dec_beam_workspace_bytes(h, B, nb, S, max_len), dtype=torch.uint8, device=dev),
+                        words=bstate[:W * 4].view(torch.int32), fwords=bstate[:W * 4].view(torch.float32),
+                        hist=bstate[W * 4:(W + 64 * max_len) * 4].view(torch.int32).view(max_len, 64),
+                        table=bstate[(W + 128 * max_len) * 4:(W + 160 * max_len) * 4].view(2, 64, max_len),
+                        logp=torch.empty(B * nb, self.config.vocab_size, dtype=torch.float32, device=dev), graphs={})
+        return self._cached_run(("beam", B, nb, S, max_len), make)
 
     def _beam_step(self, r, B, nb, S, max_len, eos, lp, es, logp):
         _cabi.check(self._lib.dmx_trocr_dec_beam_step(self._h, _cabi.ptr(r["cache"]), B, nb, S, max_len, int(eos), float(lp), int(es),
@@ -367,10 +373,7 @@ class TrOCRForCausalLM(_HipModel):
         self._check_beam_args(encoder_hidden_states, max_length, num_beams, length_penalty, early_stopping, num_return_sequences)
         enc = self._check_inputs(encoder_hidden_states)
         B, S, nb, nret = enc.shape[0], enc.shape[1], num_beams, int(num_return_sequences)
-        eos = -1 if eos_token_id is None else int(eos_token_id)
-        pad = eos if pad_token_id is None else int(pad_token_id)
-        if pad < 0:
-            pad = 0
+        eos, pad = _eos_pad(eos_token_id, pad_token_id)
         if max_length == 1:
             return (torch.full((B * nret, 1), int(decoder_start_token_id), dtype=torch.int64, device=enc.device),
                     torch.full((B * nret,), -1.0e9, dtype=torch.float32, device=enc.device), [] if keep_trace else None)
@@ -380,73 +383,55 @@ class TrOCRForCausalLM(_HipModel):
         _cabi.check(lib.dmx_trocr_dec_beam_begin(self._h, _cabi.ptr(enc), B, nb, S, max_length, int(decoder_start_token_id), _cabi.ptr(r["cache"]),
                                                  _cabi.ptr(r["ws"]), r["ws"].numel(), _cabi.current_stream()), "trocr_dec_beam_begin")
         logp = r["logp"] if keep_trace else None
-        main = torch.cuda.current_stream()
-        gkey = (eos, float(length_penalty), es, keep_trace)
-        if use_graph and gkey not in r["graphs"]:
-            # one linear chain of kernels; tokens, position, scores, the ancestry table and the counters live in device memory
-            side = torch.cuda.Stream(device=enc.device)
-            side.wait_stream(main)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                self._beam_step(r, B, nb, S, max_length, eos, length_penalty, es, logp)
-            main.wait_stream(side)
-            r["graphs"][gkey] = g
-        state = r["cache"][:16].view(torch.int32)
-        words, fwords = r["words"], r["fwords"]
+        words, fwords, trace = r["words"], r["fwords"], []
+        tokens = _state_words(r)[_cabi.STATE_TOKENS:_cabi.STATE_TOKENS + M]
         RUN, PAR = _cabi.BEAM_RUN_SCORE, _cabi.BEAM_PARENT
-        n_steps, steps, polls, trace = max_length - 1, 0, [], []
-        while steps < n_steps:
-            if keep_trace:
-                before = dict(input_tokens=r["cache"][64:64 + 4 * M].view(torch.int32).clone(), running_scores=fwords[RUN:RUN + M].clone())
-            if use_graph:
-                r["graphs"][gkey].replay()
-            else:
-                self._beam_step(r, B, nb, S, max_length, eos, length_penalty, es, logp)
-            steps += 1
-            if keep_trace:
-                rows = torch.arange(M, device=enc.device)
-                tab = r["table"][steps & 1, :M, :steps].long()                       # physical row of positions 0 .. steps - 1
-                seq = torch.cat([r["hist"][torch.arange(steps, device=enc.device)[None, :], tab].long(), r["hist"][steps, :M].long()[:, None]], 1)
-                trace.append(dict(before, logp=logp.clone(), parent=words[PAR:PAR + M].clone() - (rows // nb * nb).int(),
-                                  token=r["cache"][64:64 + 4 * M].view(torch.int32).clone(), sequences=seq))
-            if steps % POLL_EVERY == 0 and steps < n_steps:
-                f = torch.empty(2, dtype=torch.int32, pin_memory=True)
-                f.copy_(state[1:3], non_blocking=True)
-                ev = torch.cuda.Event(); ev.record()
-                polls.append((ev, f))
-                if len(polls) > 1:
-                    ev0, f0 = polls.pop(0)
-                    ev0.synchronize()
-                    if int(f0[0]):
-                        break
+        # what a step starts from is what the step before left: the trace entry of step i takes its "before" values from here
+        before = dict(input_tokens=tokens.clone(), running_scores=fwords[RUN:RUN + M].clone()) if keep_trace else None
+
+        def record(steps):
+            rows = torch.arange(M, device=enc.device)
+            tab = r["table"][steps & 1, :M, :steps].long()                           # physical row of positions 0 .. steps - 1
+            seq = torch.cat([r["hist"][torch.arange(steps, device=enc.device)[None, :], tab].long(), r["hist"][steps, :M].long()[:, None]], 1)
+            trace.append(dict(before, logp=logp.clone(), parent=words[PAR:PAR + M].clone() - (rows // nb * nb).int(), token=tokens.clone(),
+                              sequences=seq))
+            before.update(input_tokens=trace[-1]["token"], running_scores=fwords[RUN:RUN + M].clone())
+
         seqs = torch.empty(B * nret, max_length, dtype=torch.int64, device=enc.device)
         scores = torch.empty(B * nret, dtype=torch.float32, device=enc.device)
         lens = torch.empty(B * nret, dtype=torch.int32, device=enc.device)
-        _cabi.check(lib.dmx_trocr_dec_beam_finalize(self._h, _cabi.ptr(r["cache"]), B, nb, S, max_length, nret, pad, _cabi.ptr(seqs), _cabi.ptr(scores),
-                                                    _cabi.ptr(lens), _cabi.current_stream()), "trocr_dec_beam_finalize")
-        flag = torch.empty(2, dtype=torch.int32)
-        flag.copy_(state[1:3])                   # (one synchronisation at the end)
+
+        def gather():
+            _cabi.check(lib.dmx_trocr_dec_beam_finalize(self._h, _cabi.ptr(r["cache"]), B, nb, S, max_length, nret, pad, _cabi.ptr(seqs), _cabi.ptr(scores),
+                                                        _cabi.ptr(lens), _cabi.current_stream()), "trocr_dec_beam_finalize")
+
+        steps, done, stop_len = self._decode_loop(
+            r, (eos, float(length_penalty), es, keep_trace), lambda: self._beam_step(r, B, nb, S, max_length, eos, length_penalty, es, logp),
+            max_length - 1, use_graph, after_step=record if keep_trace else None, finish=gather)
         L = 1 + int(lens.max())
         if keep_trace:
-            ran = int(flag[1]) - 1 if int(flag[0]) else steps    # steps the device executed before the loop condition ended it
-            trace = trace[:ran]
+            trace = trace[:stop_len - 1 if done else steps]      # steps the device executed before the loop condition ended it
         return seqs[:, :L].contiguous(), scores, (trace if keep_trace else None)
 
 
-def _check_generation(settings, explicit_beams):
+def _check_unsupported(who, settings, own, hint):
+    """refuse every non-default entry of _GEN_UNSUPPORTED but the settings in `own` (what the caller implements itself, or what
+    is inert in its search); hint(k) ends the message"""
     for k, want in _GEN_UNSUPPORTED.items():
         v = settings.get(k)
-        if v is None or v == want:
-            continue
-        if k == "num_beams" and explicit_beams:
+        if k in own or v is None or v == want:
             continue
         if k in ("temperature", "top_k", "top_p") and not settings.get("do_sample"):
-            continue                              # sampling knobs are inert under greedy search
-        if k in _BEAM_ONLY and (explicit_beams or int(settings.get("num_beams") or 1) == 1):
-            continue                              # beam-search knobs are inert under greedy search
-        hint = "; pass num_beams=1 to run greedy search anyway, or call beam_search()" if k in ("num_beams", *_BEAM_ONLY) else \
-            " (greedy search only: remove it from the call / generation_config)"
-        raise NotImplementedError(f"VisionEncoderDecoderModel.generate: {k}={v!r} is not implemented{hint}")
+            continue                              # sampling knobs are inert without sampling
+        raise NotImplementedError(f"VisionEncoderDecoderModel.{who}: {k}={v!r} is not implemented{hint(k)}")
+
+
+def _check_generation(settings, explicit_beams):
+    """generate(): greedy search only.  An explicit num_beams=1 overrides the configuration's; beam-search knobs are inert under it"""
+    greedy = explicit_beams or int(settings.get("num_beams") or 1) == 1
+    own = ("num_beams", *_BEAM_ONLY) if explicit_beams else _BEAM_ONLY if greedy else ()
+    _check_unsupported("generate", settings, own, lambda k: "; pass num_beams=1 to run greedy search anyway, or call beam_search()"
+                       if k in ("num_beams", *_BEAM_ONLY) else " (greedy search only: remove it from the call / generation_config)")
 
 
 class VisionEncoderDecoderModel(nn.Module):
@@ -517,10 +502,43 @@ class VisionEncoderDecoderModel(nn.Module):
         decoder.load_state_dict(dec_sd)
         return model
 
-    def _settings(self, kw):
+    def _call_args(self, who, check, pixel_values, encoder_hidden_states, max_new_tokens, max_length, kwargs, **named):
+        """what generate() / beam_search() were called with -> (settings g: the generation config overridden by the call, total
+        length L, the one eos id or None); check(g) refuses the settings `who` does not implement"""
+        unknown = set(kwargs) - set(_GEN_UNSUPPORTED) - {"decoder_start_token_id", "eos_token_id", "pad_token_id"}
+        if unknown:
+            raise TypeError(f"{who}() got unexpected keyword arguments {sorted(unknown)}")
         g = self.generation_config.to_dict()
-        g.update({k: v for k, v in kw.items() if v is not None})
-        return g
+        g.update({k: v for k, v in dict(kwargs, **named).items() if v is not None})
+        check(g)
+        if (pixel_values is None) == (encoder_hidden_states is None):
+            raise ValueError(f"{who}: pass exactly one of pixel_values / encoder_hidden_states")
+        if max_new_tokens is not None:
+            L = 1 + int(max_new_tokens)
+        elif max_length is not None:
+            L = int(max_length)
+        elif g.get("max_new_tokens") is not None:
+            L = 1 + int(g["max_new_tokens"])
+        else:
+            L = int(g.get("max_length") or 20)
+        if L > self.decoder.config.max_position_embeddings:
+            raise ValueError(f"{who}: max_length {L} exceeds the decoder's {self.decoder.config.max_position_embeddings} positions")
+        if L < 1:
+            raise ValueError(f"{who}: max_length must be >= 1")
+        eos = g.get("eos_token_id")
+        if isinstance(eos, (list, tuple)):
+            if len(eos) != 1:
+                raise NotImplementedError(f"{who}: several eos_token_id values are not implemented")
+            eos = eos[0]
+        return g, L, eos
+
+    def _enc_shape(self, pixel_values, encoder_hidden_states):
+        """the shape the decoder's argument checks take: the encoder states', or [B, 1, kdim] standing in for the encoder's output"""
+        if encoder_hidden_states is not None:
+            return tuple(encoder_hidden_states.shape)
+        if pixel_values.ndim != 4:
+            raise ValueError(f"pixel_values must be [B, C, H, W], got {tuple(pixel_values.shape)}")
+        return (pixel_values.shape[0], 1, self.decoder.config.cross_attention_hidden_size or self.decoder.config.d_model)
 
     def _score_inputs(self, who, pixel_values, encoder_hidden_states, labels, decoder_input_ids, ignore_index):
         """the argument checks of forward() / score(), all before the encoder runs"""
@@ -528,14 +546,7 @@ class VisionEncoderDecoderModel(nn.Module):
             raise ValueError(f"{who}: pass exactly one of pixel_values / encoder_hidden_states")
         if labels is None and decoder_input_ids is None:
             raise ValueError(f"{who}: pass labels or decoder_input_ids")
-        kdim = self.decoder.config.cross_attention_hidden_size or self.decoder.config.d_model
-        if encoder_hidden_states is not None:
-            shape = tuple(encoder_hidden_states.shape)
-        else:
-            if pixel_values.ndim != 4:
-                raise ValueError(f"pixel_values must be [B, C, H, W], got {tuple(pixel_values.shape)}")
-            shape = (pixel_values.shape[0], 1, kdim)
-        self.decoder._check_score_args(shape, labels, decoder_input_ids, ignore_index)
+        self.decoder._check_score_args(self._enc_shape(pixel_values, encoder_hidden_states), labels, decoder_input_ids, ignore_index)
 
     @torch.no_grad()
     def score(self, pixel_values=None, *, encoder_hidden_states=None, labels=None, decoder_input_ids=None, decoder_start_token_id=None,
@@ -574,30 +585,8 @@ class VisionEncoderDecoderModel(nn.Module):
         """greedy ids [B, L] (int64, on the device), L counting the decoder start token - transformers' `generate` with
         num_beams=1, do_sample=False.  Rows that emitted eos_token_id continue with pad_token_id; generation stops when every
         row has finished or at max_length (default 20) / 1 + max_new_tokens."""
-        unknown = set(kwargs) - set(_GEN_UNSUPPORTED) - {"decoder_start_token_id", "eos_token_id", "pad_token_id"}
-        if unknown:
-            raise TypeError(f"generate() got unexpected keyword arguments {sorted(unknown)}")
-        g = self._settings(dict(kwargs, num_beams=num_beams))
-        _check_generation(g, explicit_beams=num_beams == 1)
-        if (pixel_values is None) == (encoder_hidden_states is None):
-            raise ValueError("generate: pass exactly one of pixel_values / encoder_hidden_states")
-        if max_new_tokens is not None:
-            L = 1 + int(max_new_tokens)
-        elif max_length is not None:
-            L = int(max_length)
-        elif g.get("max_new_tokens") is not None:
-            L = 1 + int(g["max_new_tokens"])
-        else:
-            L = int(g.get("max_length") or 20)
-        if L > self.decoder.config.max_position_embeddings:
-            raise ValueError(f"generate: max_length {L} exceeds the decoder's {self.decoder.config.max_position_embeddings} positions")
-        if L < 1:
-            raise ValueError("generate: max_length must be >= 1")
-        eos = g.get("eos_token_id")
-        if isinstance(eos, (list, tuple)):
-            if len(eos) != 1:
-                raise NotImplementedError("generate: several eos_token_id values are not implemented")
-            eos = eos[0]
+        g, L, eos = self._call_args("generate", lambda g: _check_generation(g, explicit_beams=num_beams == 1), pixel_values,
+                                    encoder_hidden_states, max_new_tokens, max_length, kwargs, num_beams=num_beams)
         if encoder_hidden_states is None:
             encoder_hidden_states = self.encoder(pixel_values).last_hidden_state
         ids, _ = self.decoder.greedy(encoder_hidden_states, L, g["decoder_start_token_id"], eos, g.get("pad_token_id"),
@@ -610,50 +599,19 @@ class VisionEncoderDecoderModel(nn.Module):
         """beam-search ids [B * num_return_sequences, L] (int64, on the device) - transformers' `generate` with num_beams > 1,
         do_sample=False.  Settings not passed come from generation_config (what from_pretrained read; else length_penalty 1.0,
         early_stopping False, num_return_sequences 1, max_length 20).  With return_scores also `sequences_scores`."""
-        unknown = set(kwargs) - set(_GEN_UNSUPPORTED) - {"decoder_start_token_id", "eos_token_id", "pad_token_id"}
-        if unknown:
-            raise TypeError(f"beam_search() got unexpected keyword arguments {sorted(unknown)}")
-        g = self._settings(dict(kwargs, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping,
-                                num_return_sequences=num_return_sequences))
-        for k, want in _GEN_UNSUPPORTED.items():
-            v = g.get(k)
-            if k in _BEAM_SEARCH_OWN or v is None or v == want:
-                continue
-            if k in ("temperature", "top_k", "top_p") and not g.get("do_sample"):
-                continue
-            raise NotImplementedError(f"VisionEncoderDecoderModel.beam_search: {k}={v!r} is not implemented (remove it from the call / generation_config)")
-        nb = g.get("num_beams")
-        if isinstance(nb, bool) or not isinstance(nb, int) or not 2 <= nb <= 16:
-            raise ValueError(f"beam_search: num_beams must resolve to 2 ... 16, got {nb!r} (generate() runs greedy search)")
-        if (pixel_values is None) == (encoder_hidden_states is None):
-            raise ValueError("beam_search: pass exactly one of pixel_values / encoder_hidden_states")
-        if max_new_tokens is not None:
-            L = 1 + int(max_new_tokens)
-        elif max_length is not None:
-            L = int(max_length)
-        elif g.get("max_new_tokens") is not None:
-            L = 1 + int(g["max_new_tokens"])
-        else:
-            L = int(g.get("max_length") or 20)
-        if L > self.decoder.config.max_position_embeddings:
-            raise ValueError(f"beam_search: max_length {L} exceeds the decoder's {self.decoder.config.max_position_embeddings} positions")
-        if L < 1:
-            raise ValueError("beam_search: max_length must be >= 1")
-        eos = g.get("eos_token_id")
-        if isinstance(eos, (list, tuple)):
-            if len(eos) != 1:
-                raise NotImplementedError("beam_search: several eos_token_id values are not implemented")
-            eos = eos[0]
-        lp = g.get("length_penalty"); es = g.get("early_stopping"); nret = g.get("num_return_sequences")
+        def check(g):
+            _check_unsupported("beam_search", g, _BEAM_SEARCH_OWN, lambda k: " (remove it from the call / generation_config)")
+            nb = g.get("num_beams")
+            if isinstance(nb, bool) or not isinstance(nb, int) or not 2 <= nb <= 16:
+                raise ValueError(f"beam_search: num_beams must resolve to 2 ... 16, got {nb!r} (generate() runs greedy search)")
+
+        g, L, eos = self._call_args("beam_search", check, pixel_values, encoder_hidden_states, max_new_tokens, max_length, kwargs, num_beams=num_beams,
+                                    length_penalty=length_penalty, early_stopping=early_stopping, num_return_sequences=num_return_sequences)
+        nb, lp, es, nret = g["num_beams"], g.get("length_penalty"), g.get("early_stopping"), g.get("num_return_sequences")
         lp, es, nret = (1.0 if lp is None else float(lp)), (False if es is None else es), (1 if nret is None else int(nret))
-        probe = encoder_hidden_states if encoder_hidden_states is not None else None
-        if probe is not None:                        # every argument check before anything touches the device
-            self.decoder._check_beam_args(probe, L, nb, lp, es, nret)
-        else:
-            if pixel_values.ndim != 4:
-                raise ValueError(f"pixel_values must be [B, C, H, W], got {tuple(pixel_values.shape)}")
-            kdim = self.decoder.config.cross_attention_hidden_size or self.decoder.config.d_model
-            self.decoder._check_beam_args(torch.empty(pixel_values.shape[0], 1, kdim, device="meta"), L, nb, lp, es, nret)
+        # every argument check before anything touches the device
+        self.decoder._check_beam_args(self._enc_shape(pixel_values, encoder_hidden_states), L, nb, lp, es, nret)
+        if encoder_hidden_states is None:
             encoder_hidden_states = self.encoder(pixel_values).last_hidden_state
         ids, scores, _ = self.decoder.beam_search(encoder_hidden_states, L, g["decoder_start_token_id"], eos, g.get("pad_token_id"), num_beams=nb,
                                                   length_penalty=lp, early_stopping=es, num_return_sequences=nret, use_graph=use_graph)

@@ -275,3 +275,36 @@ def test_generate_stops_early_on_the_device():
     assert torch.equal(ids, ids_full[:, :stop])
     steps_run = int(m._runs[(1, enc.shape[1], 40)]["cache"][:4].view(torch.int32)[0])
     assert steps_run <= stop - 1 + 2 * ocr.POLL_EVERY, f"{steps_run} steps ran for a sequence that stopped at length {stop}"
+
+
+def test_decode_loop_graph_and_eager_agree_and_graphs_are_cached_per_key():
+    """what greedy and beam search share in the decode loop: the captured step graph and the uncaptured step give the same ids
+    (and beam scores) on a batch where one row finishes early and another never does, and a run keeps one graph per key - a
+    second eos id captures a second graph and leaves the first alone"""
+    cfg, meta, _ = _fixture("tied_gelu")
+    m = _tiny(cfg, meta)
+    B, S, L, start, pad = 3, 5, 12, meta["start"], meta["pad"]
+    enc = torch.randn(B, S, cfg["d_model"], generator=torch.Generator().manual_seed(3))
+    # the eos id comes from the CPU restatement's free-running greedy path on the same weights: the first token of row 0
+    free, free_lg = R.generate(_full_params(m), cfg, enc, L, start, None, pad)
+    eos, eos2 = int(free[0, 1]), int(free[1, 1])
+    early = (free[:, 1:-1] == eos).any(1)
+    assert bool(early.any()) and not bool((free[:, 1:] == eos).any(1).all()) and eos2 != eos, f"unfit inputs: {free.tolist()}"
+    # the GPU takes the same path: every pick on it is decided by more than four times the 2.3e-2 logit error measured above
+    assert float(R.margins(free_lg).min()) > 4 * 2.3e-2
+    enc = enc.to(DEV)
+    ids_g, _ = m.greedy(enc, L, start, eos, pad, use_graph=True)
+    ids_e, _ = m.greedy(enc, L, start, eos, pad, use_graph=False)
+    assert torch.equal(ids_g, ids_e), f"greedy: graph {ids_g.tolist()} vs uncaptured {ids_e.tolist()}"
+    hit = (ids_g[:, 1:-1] == eos).any(1).cpu()
+    assert ids_g.shape == (B, L) and bool(hit.any()) and not bool(hit.all()), f"one row should stop early, one not: {ids_g.tolist()}"
+    beam_g = m.beam_search(enc, L, start, eos, pad, num_beams=2, use_graph=True)
+    beam_e = m.beam_search(enc, L, start, eos, pad, num_beams=2, use_graph=False)
+    assert torch.equal(beam_g[0], beam_e[0]) and torch.equal(beam_g[1].view(torch.int32), beam_e[1].view(torch.int32)), "beam: graph vs uncaptured"
+    for key, again in (((B, S, L), lambda: m.greedy(enc, L, start, eos2, pad)),
+                       (("beam", B, 2, S, L), lambda: m.beam_search(enc, L, start, eos2, pad, num_beams=2))):
+        graphs = m._runs[key]["graphs"]
+        assert len(graphs) == 1, f"{key}: {list(graphs)}"
+        (k0, g0), = graphs.items()
+        again()
+        assert m._runs[key]["graphs"] is graphs and len(graphs) == 2 and graphs[k0] is g0, f"{key}: {list(graphs)}"
