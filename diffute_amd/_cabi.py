@@ -104,6 +104,13 @@ class EditItem(ctypes.Structure):
 
 
 EDIT_MAX_ITEMS = 64      # DMX_EDIT_MAX_ITEMS
+SELECT_MAX_CANDIDATES = 16      # DMX_SELECT_MAX_CANDIDATES
+
+
+class ReadbackPass(ctypes.Structure):
+    """dmx_readback_pass (include/diffute_hip.h): where the two resample tables of one box start inside `tables` (< 0: pass skipped) and
+    how long their coefficient rows are"""
+    _fields_ = [("h_off", c_int), ("h_taps", c_int), ("v_off", c_int), ("v_taps", c_int)]
 
 
 class VAEConfig(ctypes.Structure):
@@ -294,6 +301,8 @@ _PROTOS = {
     "dmx_edit_items_prepare": (c_int, [_P, c_int, c_int, c_int, c_int]),
     "dmx_preprocess_crop_batch": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
     "dmx_postprocess_paste_batch": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, _P, _P, c_int, _P]),
+    "dmx_readback_pixel_values": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, _P, c_int64, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "dmx_postprocess_paste_select": (c_int, [_P, c_int, _P, c_float, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, c_int, _P]),
     "dmx_glyph_max_taps": (c_int, []),
     "dmx_glyph_resize_normalize": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "dmx_gemm_plan_override": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),

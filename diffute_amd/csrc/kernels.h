@@ -417,3 +417,9 @@ int dmx_sched_dpmpp_launch(const float* x, const float* eps, const float* m1, co
 int dmx_add_noise_launch(const float* x0, const float* noise, const float* sa, const float* sb, float* out,
                          int B, size_t per, int velocity, hipStream_t stream);
 int dmx_gaussian_sample_launch(const float* moments, const float* noise, float* out, int B, int C, int HW, float scale, hipStream_t stream);
+
+// ------------------------------------------------------------------ prepost_batch.hip
+struct dmx_edit_item;                                  // include/diffute_hip.h
+// the host-side checks of an item table, shared by every entry that takes one (prepost_batch.hip, readback.hip): a bad item is reported by
+// index through the last-error string; `prepared` also compares the derived fields with what dmx_edit_items_prepare fills
+int dmx_check_edit_items(const char* what, const dmx_edit_item* items, int B, int H, int W, int S, bool prepared);

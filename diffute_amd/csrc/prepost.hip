@@ -8,6 +8,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "prepost_resize.h"
+#include "glyph_resample.h"
 #include "../../include/diffute_hip.h"
 #include <math.h>
 
@@ -92,61 +93,28 @@ extern "C" int dmx_postprocess_paste(const float* image_vae, int S, const unsign
 // normalisation as norm[3][256].  The kernel is integer MACs and table look-ups only, so its result does not depend on build flags.
 //   horizontal pass first: h = clip8((2^21 + sum pixel * k) >> 22) stored as a BYTE, the vertical pass runs on those bytes; a pass whose
 //   input and output size are equal is skipped (table offset < 0).
-// One thread per destination pixel, all three channels; the thread recomputes the horizontally-resampled bytes its vertical taps need.
+// One thread per destination pixel, all three channels; the per-pixel arithmetic is glyph_resample.h.
 namespace {
 struct GlyphArgs {
   const dmx_glyph_image* desc; const int* tab; const float* norm;
   int S_h, S_w; float* out; unsigned char* out_u8;
 };
-__device__ __forceinline__ int clip8(int v) { v >>= 22; return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
 __global__ __launch_bounds__(128) void dmx_glyph_resize_normalize_kernel(const GlyphArgs p) {
   const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y, b = blockIdx.z;
   if (ox >= p.S_w) return;
   const dmx_glyph_image d = p.desc[b];
   const unsigned char* src = (const unsigned char*)d.src;
-  // the tables come from device memory the entry cannot inspect: every bound is clamped to the image, so a bad table reads wrong pixels, never outside
-  int xmin = ox, xn = 1, ymin = oy, yn = 1;
-  const int *kh = nullptr, *kv = nullptr;
-  if (d.h_off >= 0) {
-    const int* t = p.tab + d.h_off;
-    xmin = min(max(t[2 * ox], 0), d.W - 1); xn = min(min(t[2 * ox + 1], d.h_taps), min(d.W - xmin, DMX_GLYPH_MAX_TAPS));
-    kh = t + 2 * p.S_w + (size_t)ox * d.h_taps;
-  } else xmin = min(xmin, d.W - 1);
-  if (d.v_off >= 0) {
-    const int* t = p.tab + d.v_off;
-    ymin = min(max(t[2 * oy], 0), d.H - 1); yn = min(min(t[2 * oy + 1], d.v_taps), min(d.H - ymin, DMX_GLYPH_MAX_TAPS));
-    kv = t + 2 * p.S_h + (size_t)oy * d.v_taps;
-  } else ymin = min(ymin, d.H - 1);
-  int acc[3] = {1 << 21, 1 << 21, 1 << 21}, h[3] = {0, 0, 0};
-  for (int j = 0; j < yn; ++j) {
-    const unsigned char* row = src + (long long)(ymin + j) * d.stride_y + (long long)xmin * d.stride_x;
-    if (kh) {
-      int s[3] = {1 << 21, 1 << 21, 1 << 21};
-      for (int i = 0; i < xn; ++i) {
-        const int k = kh[i];
-        const unsigned char* px = row + (long long)i * d.stride_x;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s[c] += (int)px[c * d.stride_c] * k;
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) h[c] = clip8(s[c]);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) h[c] = row[c * d.stride_c];
-    }
-    if (kv) {
-      const int k = kv[j];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) acc[c] += h[c] * k;
-    }
-  }
+  const dmx_glyph::Passes ps{d.h_off, d.h_taps, d.v_off, d.v_taps};
+  int v[3];
+  // the two-pass arithmetic and its clamps: glyph_resample.h, shared with the read-back kernel (readback.hip)
+  dmx_glyph::glyph_resample_pixel(
+      [&](int y, int x, int c) -> int { return src[(long long)y * d.stride_y + (long long)x * d.stride_x + (long long)c * d.stride_c]; }, d.H, d.W,
+      p.tab, ps, p.S_h, p.S_w, ox, oy, v);
   const size_t plane = (size_t)p.S_h * p.S_w, o = (size_t)b * 3 * plane + (size_t)oy * p.S_w + ox;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const int v = kv ? clip8(acc[c]) : h[c];
-    p.out[o + c * plane] = p.norm[c * 256 + v];
-    if (p.out_u8) p.out_u8[o + c * plane] = (unsigned char)v;
+    p.out[o + c * plane] = p.norm[c * 256 + v[c]];
+    if (p.out_u8) p.out_u8[o + c * plane] = (unsigned char)v[c];
   }
 }
 }  // namespace

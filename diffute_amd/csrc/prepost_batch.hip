@@ -13,17 +13,6 @@
 namespace {
 using namespace dmx_resize;
 
-// A table the entry could not inspect (the device copy) must never send a read outside the image: origin and extent are clamped to
-// it, and the exact-2x path is taken only when the clamped extent really is twice / half of S.
-__device__ __forceinline__ Geom item_geom(const dmx_edit_item& it, int H, int W, int S, bool pre) {
-  Geom g;
-  g.xs = min(max(it.x_s, 0), W - 1); g.ys = min(max(it.y_s, 0), H - 1);
-  g.cw = min(max(it.cw, 1), W - g.xs); g.ch = min(max(it.ch, 1), H - g.ys);
-  if (pre) { g.sx = it.pre_sx; g.sy = it.pre_sy; g.area2 = (it.pre_area2 && g.cw == 2 * S && g.ch == 2 * S) ? 1 : 0; }
-  else { g.sx = it.post_sx; g.sy = it.post_sy; g.area2 = (it.post_area2 && S == 2 * g.cw && S == 2 * g.ch) ? 1 : 0; }
-  return g;
-}
-
 struct PreBatchArgs {
   const unsigned char* img; int H, W;                                  // HWC uint8 image shared by all items
   const dmx_edit_item* items; int S;
@@ -56,39 +45,82 @@ struct PostBatchArgs {
 // B chained single pastes in index order leave, at every pixel, the value of the LAST item whose (half-open box) AND (resized crop
 // extent) covers it, computed from that item's decoder output alone, or the original where no item does: scan from the last item down
 // and stop at the first hit.  The integer half of the table is staged in LDS once per block (every pixel of the row scans all of it).
-__global__ __launch_bounds__(256) void dmx_postprocess_batch_kernel(const PostBatchArgs p) {
-  __shared__ int4 s_box[DMX_EDIT_MAX_ITEMS], s_crop[DMX_EDIT_MAX_ITEMS];
+__device__ __forceinline__ void stage_items(const PostBatchArgs& p, int4* s_box, int4* s_crop) {
   if ((int)threadIdx.x < p.B) {
     const dmx_edit_item& it = p.items[threadIdx.x];
     s_box[threadIdx.x] = make_int4(it.x1, it.y1, it.x2, it.y2);
     const int xs = min(max(it.x_s, 0), p.W - 1), ys = min(max(it.y_s, 0), p.H - 1);       // item_geom's clamps
     s_crop[threadIdx.x] = make_int4(xs, ys, min(max(it.cw, 1), p.W - xs), min(max(it.ch, 1), p.H - ys));
   }
-  __syncthreads();
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= p.W) return;
+}
+// One pixel of the page.  row(b) -> which [3][S][S] image of p.vae item b pastes, < 0 = the item is skipped (it still counts for the
+// union mask: the mask says where the boxes are, not what was pasted).
+template <class Row>
+__device__ __forceinline__ void paste_pixel(const PostBatchArgs& p, const int4* s_box, const int4* s_crop, Row row, int x, int y) {
   int hit = -1, any = 0;
   for (int b = p.B - 1; b >= 0; --b) {
     const int4 bx = s_box[b];
     any |= (x >= bx.x && x <= bx.z && y >= bx.y && y <= bx.w) ? 1 : 0;                    // union mask: PIL's inclusive rectangle
-    if (hit < 0 && x >= bx.x && x < bx.z && y >= bx.y && y < bx.w) {                       // the paste: inf_res[y1:y2, x1:x2]
+    if (hit < 0 && row(b) >= 0 && x >= bx.x && x < bx.z && y >= bx.y && y < bx.w) {        // the paste: inf_res[y1:y2, x1:x2]
       const int4 cr = s_crop[b];
       const int dx = x - cr.x, dy = y - cr.y;
       if (dx >= 0 && dx < cr.z && dy >= 0 && dy < cr.w) hit = b;
     }
-    if (hit >= 0) break;                                                                   // (a hit lies inside that item's inclusive box: `any` is set)
+    if (hit >= 0) break;                                                     // (a hit lies inside that item's inclusive box: `any` is set)
   }
   const size_t o = ((size_t)y * p.W + x) * 3;
   if (p.umask) p.umask[(size_t)y * p.W + x] = (unsigned char)any;
   if (hit < 0) { p.out[o] = p.ori[o]; p.out[o + 1] = p.ori[o + 1]; p.out[o + 2] = p.ori[o + 2]; return; }
   const Geom g = item_geom(p.items[hit], p.H, p.W, p.S, false);
-  const float* vae = p.vae + (size_t)hit * 3 * p.S * p.S;
+  const float* vae = p.vae + (size_t)row(hit) * 3 * p.S * p.S;
 #pragma unroll
   for (int c = 0; c < 3; ++c) p.out[o + c] = post_pixel(vae, p.S, g, c, x - g.xs, y - g.ys);
 }
 
+__global__ __launch_bounds__(256) void dmx_postprocess_batch_kernel(const PostBatchArgs p) {
+  __shared__ int4 s_box[DMX_EDIT_MAX_ITEMS], s_crop[DMX_EDIT_MAX_ITEMS];
+  stage_items(p, s_box, s_crop);
+  __syncthreads();
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x >= p.W) return;
+  paste_pixel(p, s_box, s_crop, [](int b) -> int { return b; }, x, y);
+}
+
+// Best of K candidates per item, chosen and pasted in ONE launch: p.vae is [B][K][3][S][S], scores [B][K] lives on the device, so the
+// host never waits for it.  Every block stages the score table in LDS and derives the same choices from it:
+//   choice[b] = arg-max over k of scores[b][k], the lowest k on a tie; a NaN never wins; 0 when every score is NaN;
+//   -1 (the item is skipped, its box keeps the original pixels) when the best score is below `threshold`.
+// Block (0, 0) alone writes `choice`, with plain vector stores.  The paste is paste_pixel, the rule of the kernel above.
+__global__ __launch_bounds__(256) void dmx_postprocess_select_kernel(const PostBatchArgs p, const float* scores, int K, float threshold, int* choice) {
+  __shared__ int4 s_box[DMX_EDIT_MAX_ITEMS], s_crop[DMX_EDIT_MAX_ITEMS];
+  __shared__ float s_score[DMX_EDIT_MAX_ITEMS * DMX_SELECT_MAX_CANDIDATES];
+  __shared__ int s_choice[DMX_EDIT_MAX_ITEMS];
+  stage_items(p, s_box, s_crop);
+  for (int i = threadIdx.x; i < p.B * K; i += blockDim.x) s_score[i] = scores[i];
+  __syncthreads();
+  if ((int)threadIdx.x < p.B) {
+    const float* sc = s_score + threadIdx.x * K;
+    int best = -1;
+    float bv = 0.f;
+    for (int k = 0; k < K; ++k) {
+      const float v = sc[k];
+      if (v != v) continue;                                                                // NaN
+      if (best < 0 || v > bv) { best = k; bv = v; }
+    }
+    const int ch = best < 0 ? 0 : (bv < threshold ? -1 : best);
+    s_choice[threadIdx.x] = ch;
+    if (blockIdx.x == 0 && blockIdx.y == 0) choice[threadIdx.x] = ch;
+  }
+  __syncthreads();
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x >= p.W) return;
+  paste_pixel(p, s_box, s_crop, [&](int b) -> int { const int k = s_choice[b]; return k < 0 ? -1 : b * K + k; }, x, y);
+}
+
+}  // namespace
+
 // the checks of the single-box entries, per item; `prepared` also compares the derived fields with what edit_items_prepare fills
-int check_items(const char* what, const dmx_edit_item* items, int B, int H, int W, int S, bool prepared) {
+int dmx_check_edit_items(const char* what, const dmx_edit_item* items, int B, int H, int W, int S, bool prepared) {
   DMX_REQUIRE(items, "%s: null item table", what);
   DMX_REQUIRE(B >= 1 && B <= DMX_EDIT_MAX_ITEMS, "%s: %d items, expected 1 .. %d", what, B, DMX_EDIT_MAX_ITEMS);
   DMX_REQUIRE(H > 0 && W > 0 && H <= 65535 && S > 0 && S <= 65535, "%s: bad sizes (image %dx%d, S %d)", what, W, H, S);
@@ -105,10 +137,9 @@ int check_items(const char* what, const dmx_edit_item* items, int B, int H, int 
   }
   return DMX_OK;
 }
-}  // namespace
 
 extern "C" int dmx_edit_items_prepare(dmx_edit_item* items, int B, int H, int W, int S) {
-  const int rc = check_items("edit_items_prepare", items, B, H, W, S, false);
+  const int rc = dmx_check_edit_items("edit_items_prepare", items, B, H, W, S, false);
   if (rc != DMX_OK) return rc;
   for (int b = 0; b < B; ++b) {
     dmx_edit_item& it = items[b];
@@ -124,7 +155,7 @@ extern "C" int dmx_preprocess_crop_batch(const unsigned char* image_hwc, int H, 
                                          dmx_stream_t stream) {
   DMX_REQUIRE(image_hwc && items_device && out_image && out_masked_image && out_mask, "preprocess_crop_batch: null argument");
   DMX_REQUIRE(S > 0 && S % 8 == 0, "preprocess_crop_batch: S = %d is no positive multiple of 8", S);
-  const int rc = check_items("preprocess_crop_batch", items_host, B, H, W, S, true);
+  const int rc = dmx_check_edit_items("preprocess_crop_batch", items_host, B, H, W, S, true);
   if (rc != DMX_OK) return rc;
   PreBatchArgs p{image_hwc, H, W, items_device, S, out_image, out_masked_image, out_mask, out_mask_latent};
   hipLaunchKernelGGL(dmx_preprocess_batch_kernel, dim3(cdiv(S, 256), S, B), dim3(256), 0, (hipStream_t)stream, p);
@@ -135,9 +166,22 @@ extern "C" int dmx_postprocess_paste_batch(const float* image_vae, int S, const 
                                            unsigned char* union_mask, int H, int W, const dmx_edit_item* items_host,
                                            const dmx_edit_item* items_device, int B, dmx_stream_t stream) {
   DMX_REQUIRE(image_vae && original_hwc && out_hwc && items_device, "postprocess_paste_batch: null argument");
-  const int rc = check_items("postprocess_paste_batch", items_host, B, H, W, S, true);
+  const int rc = dmx_check_edit_items("postprocess_paste_batch", items_host, B, H, W, S, true);
   if (rc != DMX_OK) return rc;
   PostBatchArgs p{image_vae, S, original_hwc, out_hwc, union_mask, H, W, items_device, B};
   hipLaunchKernelGGL(dmx_postprocess_batch_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, p);
   return dmx_check_launch("dmx_postprocess_batch_kernel");
+}
+
+extern "C" int dmx_postprocess_paste_select(const float* image_vae, int S, const float* scores, float threshold, const unsigned char* original_hwc,
+                                            unsigned char* out_hwc, unsigned char* union_mask, int* choice, int H, int W,
+                                            const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, dmx_stream_t stream) {
+  DMX_REQUIRE(image_vae && scores && original_hwc && out_hwc && choice && items_device, "postprocess_paste_select: null argument");
+  DMX_REQUIRE(K >= 1 && K <= DMX_SELECT_MAX_CANDIDATES, "postprocess_paste_select: %d candidates per box, expected 1 .. %d", K, DMX_SELECT_MAX_CANDIDATES);
+  DMX_REQUIRE(!(threshold != threshold), "postprocess_paste_select: the threshold is NaN (pass -inf for none)");
+  const int rc = dmx_check_edit_items("postprocess_paste_select", items_host, B, H, W, S, true);
+  if (rc != DMX_OK) return rc;
+  PostBatchArgs p{image_vae, S, original_hwc, out_hwc, union_mask, H, W, items_device, B};
+  hipLaunchKernelGGL(dmx_postprocess_select_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, p, scores, K, threshold, choice);
+  return dmx_check_launch("dmx_postprocess_select_kernel");
 }

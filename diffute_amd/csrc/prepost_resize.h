@@ -14,6 +14,7 @@
 #pragma once
 #include <math.h>
 #include <stddef.h>
+#include "../../include/diffute_hip.h"
 
 namespace dmx_resize {
 // What a resize needs besides the pixels: where the crop sits in the image, its extent clipped at the border (numpy slicing
@@ -137,6 +138,17 @@ __device__ __forceinline__ unsigned char post_pixel(const float* vae, int S, con
   v = rintf(v);
   v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
   return (unsigned char)v;
+}
+
+// A table the entry could not inspect (the device copy) must never send a read outside the image: origin and extent are clamped to
+// it, and the exact-2x path is taken only when the clamped extent really is twice / half of S.
+__device__ __forceinline__ Geom item_geom(const dmx_edit_item& it, int H, int W, int S, bool pre) {
+  Geom g;
+  g.xs = min(max(it.x_s, 0), W - 1); g.ys = min(max(it.y_s, 0), H - 1);
+  g.cw = min(max(it.cw, 1), W - g.xs); g.ch = min(max(it.ch, 1), H - g.ys);
+  if (pre) { g.sx = it.pre_sx; g.sy = it.pre_sy; g.area2 = (it.pre_area2 && g.cw == 2 * S && g.ch == 2 * S) ? 1 : 0; }
+  else { g.sx = it.post_sx; g.sy = it.post_sy; g.area2 = (it.post_area2 && S == 2 * g.cw && S == 2 * g.ch) ? 1 : 0; }
+  return g;
 }
 #endif  // __HIPCC__
 }  // namespace dmx_resize

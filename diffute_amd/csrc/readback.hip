@@ -1,0 +1,94 @@
+// OCR read-back of edited text boxes (reference: app.ipynb:842-846 - crop inf_res[y1:y2, x1:x2], run the processor, call generate):
+// from the decoder outputs of K candidates per box straight to the `pixel_values` the OCR encoder reads, in ONE launch.  Row (b, k) is,
+// bit for bit, what dmx_glyph_resize_normalize makes of the slice [y1:y2, x1:x2] of the page dmx_postprocess_paste writes for
+// image_vae[b][k] ALONE over the original image - but neither the page nor the slice exists: a source byte at page position (X, Y) is
+//   post_pixel(...) of that candidate   where (X, Y) lies inside item b's clipped crop extent (inside its box it does by construction),
+//   the original byte                   elsewhere (a box wider than its crop keeps original pixels there, as the slice would).
+// The per-pixel arithmetic is shared, not restated: prepost_resize.h (post_pixel, item_geom's clamps) for the paste and glyph_resample.h
+// (Pillow's integer two-pass resample) for the processor; the library is built with -ffp-contract=off, so the shared fp32 expressions
+// round alike in every kernel.  Pure byte work on a few thousand pixels per box: launch- and HBM-latency-bound, one thread per
+// destination pixel, coalesced plain vector stores, no uint8 intermediate in HBM.
+#include "common.h"
+#include "kernels.h"
+#include "prepost_resize.h"
+#include "glyph_resample.h"
+#include "../../include/diffute_hip.h"
+
+namespace {
+using namespace dmx_resize;
+
+struct ReadbackArgs {
+  const float* vae; int S;                                 // decoder outputs [B][K][3][S][S] in [-1, 1]
+  const unsigned char* ori; int H, W;                      // the original page, HWC uint8
+  const dmx_edit_item* items; const dmx_readback_pass* passes; int B, K;
+  const int* tab; const float* norm;
+  int S_h, S_w; float* out; unsigned char* out_u8;         // [B*K][3][S_h][S_w]
+};
+
+__global__ __launch_bounds__(128) void dmx_readback_pixel_values_kernel(const ReadbackArgs p) {
+  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y, r = blockIdx.z;       // r = b * K + k
+  if (ox >= p.S_w) return;
+  const int b = r / p.K;
+  const dmx_edit_item it = p.items[b];
+  const dmx_readback_pass ps = p.passes[b];
+  // everything that comes from the device table is clamped: the box to the image (at least one pixel), the crop by item_geom
+  const int x1 = min(max(it.x1, 0), p.W - 1), y1 = min(max(it.y1, 0), p.H - 1);
+  const int bw = min(max(it.x2 - x1, 1), p.W - x1), bh = min(max(it.y2 - y1, 1), p.H - y1);
+  const Geom g = item_geom(it, p.H, p.W, p.S, false);
+  const float* vae = p.vae + (size_t)r * 3 * p.S * p.S;
+  auto px = [&](int y, int x, int c) -> int {                                                  // byte (x, y) of the box slice of the pasted page
+    const int X = x1 + x, Y = y1 + y, dx = X - g.xs, dy = Y - g.ys;
+    if (dx >= 0 && dx < g.cw && dy >= 0 && dy < g.ch) return post_pixel(vae, p.S, g, c, dx, dy);
+    return p.ori[((size_t)Y * p.W + X) * 3 + c];
+  };
+  const dmx_glyph::Passes tp{ps.h_off, ps.h_taps, ps.v_off, ps.v_taps};
+  int v[3];
+  dmx_glyph::glyph_resample_pixel(px, bh, bw, p.tab, tp, p.S_h, p.S_w, ox, oy, v);
+  const size_t plane = (size_t)p.S_h * p.S_w, o = (size_t)r * 3 * plane + (size_t)oy * p.S_w + ox;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    p.out[o + c * plane] = p.norm[c * 256 + v[c]];
+    if (p.out_u8) p.out_u8[o + c * plane] = (unsigned char)v[c];
+  }
+}
+}  // namespace
+
+extern "C" int dmx_readback_pixel_values(const float* image_vae, int S, const unsigned char* original_hwc, int H, int W,
+                                         const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, const int* tables,
+                                         long long table_ints, const float* norm, const dmx_readback_pass* passes_host,
+                                         const dmx_readback_pass* passes_device, int max_taps, int S_h, int S_w, float* out_pixel_values,
+                                         unsigned char* out_resized, dmx_stream_t stream) {
+  DMX_REQUIRE(image_vae && original_hwc && items_device && tables && norm && passes_host && passes_device && out_pixel_values,
+              "readback_pixel_values: null argument");
+  DMX_REQUIRE(K >= 1 && K <= DMX_SELECT_MAX_CANDIDATES, "readback_pixel_values: %d candidates per box, expected 1 .. %d", K, DMX_SELECT_MAX_CANDIDATES);
+  DMX_REQUIRE(S_h > 0 && S_h <= 65535 && S_w > 0 && S_w <= 65535, "readback_pixel_values: bad output size %dx%d", S_w, S_h);
+  DMX_REQUIRE(max_taps >= 0 && max_taps <= DMX_GLYPH_MAX_TAPS,
+              "readback_pixel_values: %d taps per output pixel exceed the cap of %d (downscale ratio at most 31 for bilinear, 15 for bicubic)",
+              max_taps, DMX_GLYPH_MAX_TAPS);
+  DMX_REQUIRE(table_ints >= 0 && table_ints < (1ll << 31), "readback_pixel_values: bad table size %lld", table_ints);
+  const int rc = dmx_check_edit_items("readback_pixel_values", items_host, B, H, W, S, true);
+  if (rc != DMX_OK) return rc;
+  for (int b = 0; b < B; ++b) {
+    const dmx_edit_item& it = items_host[b];
+    DMX_REQUIRE(it.x2 > it.x1 && it.y2 > it.y1, "readback_pixel_values: item %d: empty box (%d, %d, %d, %d)", b, it.x1, it.y1, it.x2, it.y2);
+    DMX_REQUIRE(it.x1 >= 0 && it.y1 >= 0 && it.x2 <= W && it.y2 <= H, "readback_pixel_values: item %d: box (%d, %d, %d, %d) outside the %dx%d image",
+                b, it.x1, it.y1, it.x2, it.y2, W, H);
+    const dmx_readback_pass& ps = passes_host[b];
+    const struct { const char* name; int off, taps, n_in, n_out; } pass[2] = {{"horizontal", ps.h_off, ps.h_taps, it.x2 - it.x1, S_w},
+                                                                             {"vertical", ps.v_off, ps.v_taps, it.y2 - it.y1, S_h}};
+    for (const auto& q : pass) {
+      if (q.n_in == q.n_out) {                                                                 // equal sizes: Pillow skips the pass
+        DMX_REQUIRE(q.off < 0, "readback_pixel_values: item %d: the %s pass resizes %d -> %d and must be skipped (offset < 0)", b, q.name, q.n_in, q.n_out);
+        continue;
+      }
+      DMX_REQUIRE(q.off >= 0 && q.taps >= 1 && q.taps <= max_taps, "readback_pixel_values: item %d: %s pass: offset %d, %d taps (max_taps %d)", b,
+                  q.name, q.off, q.taps, max_taps);
+      DMX_REQUIRE((long long)q.off + 2ll * q.n_out + (long long)q.n_out * q.taps <= table_ints,
+                  "readback_pixel_values: item %d: the %s table (offset %d, %d x %d taps) ends past the %lld ints of `tables`", b, q.name, q.off,
+                  q.n_out, q.taps, table_ints);
+    }
+  }
+  ReadbackArgs p{image_vae, S, original_hwc, H, W, items_device, passes_device, B, K, tables, norm, S_h, S_w, out_pixel_values, out_resized};
+  hipLaunchKernelGGL(dmx_readback_pixel_values_kernel, dim3(cdiv(S_w, 128), S_h, B * K), dim3(128), 0, (hipStream_t)stream, p);
+  return dmx_check_launch("dmx_readback_pixel_values_kernel");
+}

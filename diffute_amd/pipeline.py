@@ -221,3 +221,136 @@ def edit_boxes(unet, vae, scheduler, instance_image, locations, encoder_hidden_s
     image_vae = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
     out = prepost.postprocess_batch(image_vae, instance_image, locations, origins, crop_scales)
     return (out, image_vae, pre) if return_intermediate else out
+
+
+class VerifiedEdit:
+    """what edit_boxes_verified(return_intermediate=True) returns: image uint8 [h][w][3]; choice int32 [N] (the pasted candidate of each
+    box, -1 = kept the original); scores fp32 [N,K] (mean log-probability per label token); image_vae fp32 [N,K,3,S,S]; pixel_values
+    fp32 [N*K,3,S_h,S_w] (what the OCR model read, box-major); pre (the preprocess_batch dict).  All on the device."""
+
+    def __init__(self, image, choice, scores, image_vae, pixel_values, pre):
+        self.image, self.choice, self.scores, self.image_vae, self.pixel_values, self.pre = image, choice, scores, image_vae, pixel_values, pre
+
+
+def _check_verified_args(ocr, processor, instance_image, locations, encoder_hidden_states, labels, candidates, seeds, min_score, batch_size,
+                         ocr_batch_size, origins, crop_scales, size):
+    """every argument check of edit_boxes_verified, on the host side: nothing touches the GPU before it passes.
+    Returns (N, K, seeds, h, w, image processor)."""
+    locations = list(locations)
+    N = len(locations)
+    if N < 1 or N > _cabi.EDIT_MAX_ITEMS:
+        raise ValueError(f"{N} boxes, expected 1 .. {_cabi.EDIT_MAX_ITEMS}")
+    if int(batch_size) < 1 or int(ocr_batch_size) < 1:
+        raise ValueError("batch_size and ocr_batch_size must be at least 1")
+    K = int(candidates)
+    if not 1 <= K <= _cabi.SELECT_MAX_CANDIDATES:
+        raise ValueError(f"candidates = {K}, expected 1 .. {_cabi.SELECT_MAX_CANDIDATES}")
+    seeds = list(range(K)) if seeds is None else [int(s) for s in seeds]
+    if len(seeds) != K:
+        raise ValueError(f"{K} candidates but {len(seeds)} seeds")
+    if min_score is not None and float(min_score) != float(min_score):
+        raise ValueError("min_score is NaN")
+    if not isinstance(instance_image, torch.Tensor) or instance_image.dim() != 3:
+        raise TypeError("instance_image: expected a contiguous uint8 CUDA tensor [h][w][3]")
+    h, w = int(instance_image.shape[0]), int(instance_image.shape[1])
+    for name, lst in (("origins", origins), ("crop_scales", crop_scales)):
+        if lst is not None and len(list(lst)) != N:
+            raise ValueError(f"{N} boxes, {len(list(lst))} {name}: the lengths must agree")
+    if encoder_hidden_states.shape[0] != N:
+        raise ValueError(f"{N} boxes but {encoder_hidden_states.shape[0]} glyph contexts")
+    if not torch.is_tensor(labels) or labels.dtype != torch.int64:
+        raise ValueError(f"labels must be an int64 tensor, got {getattr(labels, 'dtype', type(labels))}")
+    if labels.ndim != 2 or labels.shape[0] != N or labels.shape[1] < 1:
+        raise ValueError(f"labels must be [N, T] with N = {N} and T >= 1, got {tuple(labels.shape)}")
+    V, P = ocr.decoder.config.vocab_size, ocr.decoder.config.max_position_embeddings
+    if labels.shape[1] > P:
+        raise ValueError(f"labels have T = {labels.shape[1]} positions, the decoder {P}")
+    if not labels.is_cuda and bool((((labels < 0) | (labels >= V)) & (labels != -100)).any()):      # (labels on the device: ocr.score checks them)
+        raise ValueError(f"labels must lie in [0, {V}) or equal -100")
+    prepost.check_readback_boxes(locations, h, w)
+    ip =getattr(processor, "image_processor", processor)
+    if not getattr(ip, "do_resize", False):
+        raise ValueError("the processor must resize (do_resize=True)")
+    want = int(ocr.encoder.config.image_size)
+    if (ip.size["height"], ip.size["width"]) != (want, want):
+        raise ValueError(f"the processor resizes to {ip.size['width']}x{ip.size['height']}, ocr.encoder reads {want}x{want}")
+    if int(size) < 8 or int(size) % 8:
+        raise ValueError(f"size = {size} is no positive multiple of 8")
+    return N, K, seeds, h, w, ip
+
+
+@torch.no_grad()
+def _edit_candidates(unet, vae, scheduler, instance_image, locations, origins, crop_scales, ctx, num_inference_steps, seeds, bs, generator,
+                     enc_noise, variance_noise, S):
+    """the generating half of edit_boxes_verified: (preprocess dict, image_vae [N,K,3,S,S]).  Each box is preprocessed and VAE-encoded once;
+    the N*K rows (box-major, candidate k from seeds[k]) go through denoise + vae.decode in chunks of `bs`.  With one seed this is
+    edit_boxes' loop, chunk for chunk."""
+    N, K = len(locations), len(seeds)
+    pre = prepost.preprocess_batch(instance_image, locations, origins, crop_scales, size=S)
+    dev = instance_image.device
+    sf = vae.config.scaling_factor
+    f = 2 ** (len(vae.config.block_out_channels) - 1)
+    init = torch.cat([torch.randn((1, vae.config.latent_channels, S // f, S // f), generator=torch.manual_seed(s), dtype=torch.float32)
+                      for s in seeds], 0).to(dev)                                          # [K,4,h,w]; app.ipynb:796-801 for seed 0
+    mask_lat = mask_to_latent(pre["mask"], f)
+    mlat = [None] * N                        # box b's masked-image latents: encoded when the first chunk that holds one of its rows comes up
+    outs = []
+    for lo in range(0, N * K, bs):
+        hi = min(N * K, lo + bs)
+        b0, b1 = lo // K, (hi - 1) // K + 1
+        new = [b for b in range(b0, b1) if mlat[b] is None]
+        if new:                              # (consecutive boxes; with K = 1 exactly the chunk's boxes: edit_boxes' encode)
+            dist = vae.encode(pre["masked_image"][new[0]:new[-1] + 1]).latent_dist
+            z = (dist.sample(noise=enc_noise[new[0]:new[-1] + 1]) if enc_noise is not None else dist.sample(generator=generator)) * sf
+            for j, b in enumerate(new):
+                mlat[b] = z[j:j + 1]
+        rows = torch.arange(lo, hi)
+        box = (rows // K).tolist()
+        lat = denoise(unet, scheduler, init[(rows % K).to(dev)].contiguous(), mask_lat[box], torch.cat([mlat[b] for b in box], 0), ctx[box],
+                      num_inference_steps, variance_noise=None if variance_noise is None else variance_noise[:, lo:hi])
+        outs.append(vae.decode(lat / sf).sample)
+        for b in range(b0, b1):
+            if (b + 1) * K <= hi:
+                mlat[b] = False              # all K rows done: the latents are released (and never encoded again)
+    image_vae = (outs[0] if len(outs) == 1 else torch.cat(outs, 0)).reshape(N, K, 3, S, S)
+    return pre, image_vae
+
+
+@torch.no_grad()
+def edit_boxes_verified(unet, vae, scheduler, ocr, processor, instance_image, locations, encoder_hidden_states, labels, num_inference_steps, *,
+                        candidates=4, seeds=None, min_score=None, batch_size=4, ocr_batch_size=32, origins=None, crop_scales=None, rng=None,
+                        generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False):
+    """edit_boxes with a read-back: K = `candidates` edits per box from K starting noises, each read by the OCR model `ocr` (a
+    VisionEncoderDecoderModel) against the text the box should show, the best-reading one pasted (the reference sketches the read-back at
+    app.ipynb:842-846).  labels: int64 [N,T] token ids of the requested texts, -100 = padding (the tokenizer is out of scope).
+
+    Candidate k of every box starts from `torch.randn((1,4,h,w), generator=torch.manual_seed(seeds[k]))` on the CPU, seeds = range(K) by
+    default, so candidate 0 is edit_boxes' (the reference's) start.  The masked crop of a box is VAE-encoded and its posterior sampled
+    ONCE (enc_noise [N,4,h,w] injects the draw) and shared by the box's K candidates, as is its glyph context.  The N*K rows, box-major,
+    go through denoise + vae.decode in chunks of `batch_size` (variance_noise, if given, is [steps, N*K, 4, h, w] in that order), through
+    prepost.readback_pixel_values in one launch and through ocr.score in chunks of `ocr_batch_size`; a candidate's score is the mean
+    log-probability of its label tokens, sequence_logprobs / num_tokens.clamp(min=1).  prepost.postprocess_select_batch picks and pastes
+    on the device: no score is read on the host.  min_score: a box whose best candidate scores below it keeps the original pixels.
+
+    Returns the uint8 [h][w][3] page, or a VerifiedEdit with return_intermediate=True.  candidates=1 with min_score=None returns the
+    page of edit_boxes with the same arguments, bit for bit."""
+    N, K, seeds, h, w, ip = _check_verified_args(ocr, processor, instance_image, locations, encoder_hidden_states, labels, candidates, seeds, min_score,
+                                                 batch_size, ocr_batch_size, origins, crop_scales, size)
+    locations = list(locations)
+    if crop_scales is None:
+        crop_scales = [prepost.crop_scale_for(loc, h, w) for loc in locations]
+    crop_scales = list(crop_scales)
+    if origins is None:
+        origins = [prepost.crop_origin(loc, cs, w, rng if rng is not None else np.random) for loc, cs in zip(locations, crop_scales)]
+    pre, image_vae = _edit_candidates(unet, vae, scheduler, instance_image, locations, origins, crop_scales, encoder_hidden_states,
+                                      num_inference_steps, seeds, int(batch_size), generator, enc_noise, variance_noise, int(size))
+    dev = instance_image.device
+    pixel_values = prepost.readback_pixel_values(image_vae, instance_image, locations, origins, crop_scales, ip)
+    lab = labels.to(dev).repeat_interleave(K, 0)
+    seq, num = [], []
+    for lo in range(0, N * K, int(ocr_batch_size)):
+        r = ocr.score(pixel_values[lo:lo + int(ocr_batch_size)], labels=lab[lo:lo + int(ocr_batch_size)])
+        seq.append(r.sequence_logprobs); num.append(r.num_tokens)
+    scores = (torch.cat(seq) / torch.cat(num).clamp(min=1)).reshape(N, K)
+    out, choice = prepost.postprocess_select_batch(image_vae, scores, instance_image, locations, origins, crop_scales, threshold=min_score)
+    return VerifiedEdit(out, choice, scores, image_vae, pixel_values, pre) if return_intermediate else out

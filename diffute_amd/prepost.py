@@ -170,3 +170,146 @@ def postprocess_batch(image_vae, instance_image, locations, origins, crop_scales
         _cabi.check(_cabi.lib().dmx_postprocess_paste_batch(_cabi.ptr(v), S, _cabi.ptr(img), _cabi.ptr(out), _cabi.ptr(union), h, w, host,
                                                            _cabi.ptr(table), B, _cabi.current_stream()), "postprocess_paste_batch")
     return (out, union) if return_mask else out
+
+
+# ------------------------------------------------------------------------------------------------ K candidates per box: read-back and selection
+def _image_processor(processor):
+    """a ViTImageProcessor, or the one inside a TrOCRProcessor"""
+    return getattr(processor, "image_processor", processor)
+
+
+def _check_candidates(K):
+    if not 1 <= int(K) <= _cabi.SELECT_MAX_CANDIDATES:
+        raise ValueError(f"{K} candidates per box, expected 1 .. {_cabi.SELECT_MAX_CANDIDATES}")
+    return int(K)
+
+
+def check_readback_boxes(locations, h, w):
+    """what the read-back needs of the boxes beyond the batched paste's checks: the slice [y1:y2, x1:x2] is non-empty and inside the image"""
+    for b, loc in enumerate(locations):
+        x1, y1, x2, y2 = (int(v) for v in loc[:4])
+        if x2 <= x1 or y2 <= y1:
+            raise ValueError(f"box {b}: ({x1}, {y1}, {x2}, {y2}) is empty; the OCR read-back needs at least one pixel")
+        if x1 < 0 or y1 < 0 or x2 > w or y2 > h:
+            raise ValueError(f"box {b}: ({x1}, {y1}, {x2}, {y2}) lies outside the {w}x{h} image")
+
+
+def _readback_tables(locations, ip, cap):
+    """per box the two resample tables of (box width -> S_w) and (box height -> S_h), deduplicated: (passes [B][4] int32, the concatenated
+    int32 tables, max_taps).  A pass with equal sizes is skipped (offset -1), as Pillow does."""
+    from . import processing
+    S_h, S_w = ip.size["height"], ip.size["width"]
+    passes = np.zeros((len(locations), 4), dtype=np.int32)
+    tables, table_off, n_ints, max_taps = [], {}, 0, 0
+    for b, loc in enumerate(locations):
+        x1, y1, x2, y2 = (int(v) for v in loc[:4])
+        for col, (n_in, n_out) in ((0, (x2 - x1, S_w)), (2, (y2 - y1, S_h))):
+            if n_in == n_out:
+                passes[b, col], passes[b, col + 1] = -1, 0
+                continue
+            taps = processing._taps(n_in, n_out, ip.resample)
+            if taps > cap:
+                raise ValueError(f"box {b}: resizing {n_in} -> {n_out} needs {taps} taps per output pixel, more than the kernel's cap of {cap} "
+                                 "(downscale ratio at most 31 for bilinear, 15 for bicubic)")
+            k = (n_in, n_out, ip.resample)
+            if k not in table_off:
+                t = processing.resample_table(*k)
+                table_off[k] = n_ints; tables.append(t); n_ints += t.size
+            passes[b, col], passes[b, col + 1] = table_off[k], taps
+            max_taps = max(max_taps, taps)
+    return passes, (np.concatenate(tables) if tables else np.zeros(0, dtype=np.int32)), max_taps
+
+
+def readback_pixel_values(image_vae, instance_image, locations, origins, crop_scales, processor, return_resized=False, out=None, out_resized=None):
+    """The OCR model's input for K candidates of each of B boxes, in ONE launch: image_vae fp32 CUDA [B,K,3,S,S] decoder outputs ->
+    pixel_values fp32 [B*K,3,S_h,S_w], box-major.  Row (b, k) is bit for bit `processor(postprocess(image_vae[b, k], instance_image,
+    box b)[y1:y2, x1:x2])` - the reference's read-back (app.ipynb:842-846) - without the page, the slice or the processor call.
+    processor: a ViTImageProcessor or TrOCRProcessor with do_resize; its tables travel in one pinned staging buffer, one H2D copy.
+    return_resized=True also returns the uint8 [B*K,3,S_h,S_w] bytes before rescale / normalise.  out / out_resized (optional): contiguous
+    CUDA tensors of those shapes to write into."""
+    locations, origins, crop_scales = _check_items(locations, origins, crop_scales)
+    ip = _image_processor(processor)
+    if not ip.do_resize:
+        raise ValueError("readback_pixel_values: the processor must resize (do_resize=True): boxes have no common size")
+    img = _u8(instance_image, "instance_image")
+    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
+        raise TypeError("image_vae: expected a CUDA tensor")
+    h, w, _ = img.shape
+    B = len(locations)
+    if image_vae.dim() != 5 or image_vae.shape[0] != B or image_vae.shape[2] != 3 or image_vae.shape[3] != image_vae.shape[4]:
+        raise ValueError(f"image_vae must be [{B},K,3,S,S]: K square 3-channel candidates per box")
+    K = _check_candidates(image_vae.shape[1])
+    check_readback_boxes(locations, h, w)
+    lib = _cabi.lib()
+    passes, tables, max_taps = _readback_tables(locations, ip, int(lib.dmx_glyph_max_taps()))
+    v = image_vae.to(torch.float32).contiguous()
+    dev, S = img.device, int(v.shape[-1])
+    S_h, S_w = ip.size["height"], ip.size["width"]
+    # one staging buffer: items | passes | normalisation table | coefficient tables
+    n_items = B * ctypes.sizeof(_cabi.EditItem)
+    off_pass = n_items
+    off_norm = off_pass + passes.nbytes
+    off_tab = off_norm + ip._norm.nbytes
+    total = off_tab + tables.nbytes
+    stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+    st = stage.numpy()
+    host = (_cabi.EditItem * B).from_buffer(st[:n_items])
+    for it, loc, (x_s, y_s), crop_scale in zip(host, locations, origins, crop_scales):
+        it.x1, it.y1, it.x2, it.y2 = (int(t) for t in loc[:4])
+        it.x_s, it.y_s, it.crop_scale = int(x_s), int(y_s), int(crop_scale)
+    _cabi.check(lib.dmx_edit_items_prepare(host, B, h, w, S), "edit_items_prepare")
+    st[off_pass:off_norm] = passes.reshape(-1).view(np.uint8)
+    st[off_norm:off_tab] = ip._norm.reshape(-1).view(np.uint8)
+    st[off_tab:] = tables.view(np.uint8)
+    host_passes = (_cabi.ReadbackPass * B).from_buffer(st[off_pass:off_norm])
+    with torch.cuda.device(dev):
+        dbuf = torch.empty(total, dtype=torch.uint8, device=dev)
+        dbuf.copy_(stage, non_blocking=True)                          # the one H2D copy
+        base = dbuf.data_ptr()
+        for name, t, dt in (("out", out, torch.float32), ("out_resized", out_resized, torch.uint8)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dt and t.is_contiguous()
+                                      and tuple(t.shape) == (B * K, 3, S_h, S_w)):
+                raise ValueError(f"{name} must be a contiguous {dt} tensor [{B * K},3,{S_h},{S_w}] on {dev}")
+        if out is None:
+            out = torch.empty(B * K, 3, S_h, S_w, dtype=torch.float32, device=dev)
+        res = out_resized
+        if res is None and return_resized:
+            res = torch.empty(B * K, 3, S_h, S_w, dtype=torch.uint8, device=dev)
+        _cabi.check(lib.dmx_readback_pixel_values(_cabi.ptr(v), S, _cabi.ptr(img), h, w, host, base, B, K, base + off_tab, int(tables.size),
+                                                  base + off_norm, host_passes, base + off_pass, max_taps, S_h, S_w, _cabi.ptr(out),
+                                                  _cabi.ptr(res), _cabi.current_stream()), "readback_pixel_values", lib)
+    return (out, res) if (return_resized or out_resized is not None) else out
+
+
+def postprocess_select_batch(image_vae, scores, instance_image, locations, origins, crop_scales, threshold=None, return_mask=False):
+    """Choose and paste in ONE launch, without reading the scores on the host.  image_vae: fp32 CUDA [B,K,3,S,S]; scores: fp32 CUDA [B,K].
+    choice[b] = arg-max over k of scores[b] (lowest k on a tie; a NaN never wins; 0 when every score is NaN), or -1 when the best score
+    is below `threshold` (None: no threshold) - that box then keeps the original pixels.  Returns (out, choice): the uint8 [h][w][3] page
+    postprocess_batch gives for the chosen rows over the boxes that were kept, and choice int32 [B] on the device; with return_mask=True
+    also the union of ALL boxes as uint8 [h][w]."""
+    locations, origins, crop_scales = _check_items(locations, origins, crop_scales)
+    img = _u8(instance_image, "instance_image")
+    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda and isinstance(scores, torch.Tensor) and scores.is_cuda):
+        raise TypeError("image_vae, scores: expected CUDA tensors")
+    h, w, _ = img.shape
+    B = len(locations)
+    if image_vae.dim() != 5 or image_vae.shape[0] != B or image_vae.shape[2] != 3 or image_vae.shape[3] != image_vae.shape[4]:
+        raise ValueError(f"image_vae must be [{B},K,3,S,S]: K square 3-channel candidates per box")
+    K = _check_candidates(image_vae.shape[1])
+    if tuple(scores.shape) != (B, K):
+        raise ValueError(f"scores must be [{B},{K}], got {tuple(scores.shape)}")
+    thr = float("-inf") if threshold is None else float(threshold)
+    if thr != thr:
+        raise ValueError("threshold is NaN")
+    v = image_vae.to(torch.float32).contiguous()
+    sc = scores.to(torch.float32).contiguous()
+    dev, S = img.device, int(v.shape[-1])
+    host, stage, table = _upload_items(locations, origins, crop_scales, h, w, S, dev)
+    with torch.cuda.device(dev):
+        out = torch.empty_like(img)
+        choice = torch.empty(B, dtype=torch.int32, device=dev)
+        union = torch.empty(h, w, dtype=torch.uint8, device=dev) if return_mask else None
+        _cabi.check(_cabi.lib().dmx_postprocess_paste_select(_cabi.ptr(v), S, _cabi.ptr(sc), thr, _cabi.ptr(img), _cabi.ptr(out), _cabi.ptr(union),
+                                                            _cabi.ptr(choice), h, w, host, _cabi.ptr(table), B, K, _cabi.current_stream()),
+                    "postprocess_paste_select")
+    return (out, choice, union) if return_mask else (out, choice)

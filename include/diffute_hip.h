@@ -642,6 +642,37 @@ int dmx_glyph_max_taps(void);
 int dmx_glyph_resize_normalize(const dmx_glyph_image* images, int B, const int* tables, const float* norm, int max_taps, int S_h, int S_w,
                                float* out_pixel_values, unsigned char* out_resized, dmx_stream_t stream);
 
+/* Verified edits: K candidates per text box, read back by the OCR model, the best one pasted (reference sketch of the read-back:
+ * app.ipynb:842-846 - crop inf_res[y1:y2, x1:x2], run the processor, call generate).  Two launches, no page copy, no host sync.
+ *   readback_pixel_values: image_vae fp32 [B][K][3][S][S]; row (b, k) uses item b.  out_pixel_values fp32 [B*K][3][S_h][S_w]: row
+ *           (b, k) is, bit for bit, glyph_resize_normalize applied to the slice [y1:y2, x1:x2] of the page postprocess_paste writes
+ *           for image_vae[b][k] ALONE over original_hwc (one paste onto the ORIGINAL image, not chained with other boxes): a source
+ *           byte inside the item's clipped crop extent is the pasted byte of that candidate, any other the original byte (a box
+ *           wider than its crop keeps original pixels there).  Neither the page nor the slice is materialised.
+ *           tables / norm / max_taps / out_resized as for glyph_resize_normalize; table_ints = the length of `tables`.  passes: per
+ *           item the offsets and tap counts of its two pass tables (source size = the box, x2 - x1 by y2 - y1); a pass whose sizes
+ *           are equal must carry an offset < 0.  Host and device copies of items and passes, as for the batch entries above.
+ *           Refused (DMX_ERR_ARG, nothing launched): an empty box (x2 <= x1 or y2 <= y1), a box outside the image, K < 1 or
+ *           K > DMX_SELECT_MAX_CANDIDATES, max_taps > DMX_GLYPH_MAX_TAPS, a table that ends past table_ints.  The kernel clamps
+ *           whatever it reads from the device tables to the image.
+ *   postprocess_paste_select: image_vae as above, scores fp32 [B][K] ON THE DEVICE.  choice int32 [B] (device, out):
+ *           choice[b] = arg-max over k of scores[b][k], the lowest k on a tie; a NaN never wins; 0 if every score of the box is NaN;
+ *           -1 if the best score is below `threshold` (pass -INFINITY for none; NaN is refused) - that item is skipped and its box
+ *           keeps the original pixels.  out_hwc = postprocess_paste_batch of the chosen rows over the items that were not skipped
+ *           (a later item wins where boxes overlap); union_mask (may be NULL) covers the inclusive boxes of ALL items. */
+#define DMX_SELECT_MAX_CANDIDATES 16
+typedef struct dmx_readback_pass {
+  int h_off, h_taps, v_off, v_taps;
+} dmx_readback_pass;
+int dmx_readback_pixel_values(const float* image_vae, int S, const unsigned char* original_hwc, int H, int W,
+                              const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, const int* tables,
+                              long long table_ints, const float* norm, const dmx_readback_pass* passes_host,
+                              const dmx_readback_pass* passes_device, int max_taps, int S_h, int S_w, float* out_pixel_values,
+                              unsigned char* out_resized, dmx_stream_t stream);
+int dmx_postprocess_paste_select(const float* image_vae, int S, const float* scores, float threshold, const unsigned char* original_hwc,
+                                 unsigned char* out_hwc, unsigned char* union_mask, int* choice, int H, int W,
+                                 const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, dmx_stream_t stream);
+
 /* Fused AdamW + global-norm clipping over packed fp32 arenas (torch.optim.AdamW + clip_grad_norm_,
  * train_diffute_v1.py:721-727,927-930).  masters / exp_avg / exp_avg_sq / grads: dmx_unet_grad_bytes each.  The step also
  * rewrites the weights arena (bf16 weights, fp32 vectors) in place; afterwards call dmx_unet_refresh_derived (folded
