@@ -113,6 +113,13 @@ class ReadbackPass(ctypes.Structure):
     _fields_ = [("h_off", c_int), ("h_taps", c_int), ("v_off", c_int), ("v_taps", c_int)]
 
 
+class EditPage(ctypes.Structure):
+    """dmx_edit_page (include/diffute_hip.h): one page of the dmx_*_pages entries.  The caller sets the addresses, the size and the item
+    range, dmx_edit_pages_prepare fills block_lo / blocks."""
+    _fields_ = [("original", ctypes.c_uint64), ("out", ctypes.c_uint64), ("union_mask", ctypes.c_uint64), ("H", c_int), ("W", c_int),
+                ("item_lo", c_int), ("item_hi", c_int), ("block_lo", c_int), ("blocks", c_int)]
+
+
 class VAEConfig(ctypes.Structure):
     _fields_ = [("in_channels", c_int), ("out_channels", c_int), ("latent_channels", c_int),
                 ("block_out_channels", c_int * 4), ("layers_per_block", c_int), ("norm_num_groups", c_int)]
@@ -303,6 +310,11 @@ _PROTOS = {
     "dmx_postprocess_paste_batch": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, _P, _P, c_int, _P]),
     "dmx_readback_pixel_values": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, c_int, c_int, _P, c_int64, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "dmx_postprocess_paste_select": (c_int, [_P, c_int, _P, c_float, _P, _P, _P, _P, c_int, c_int, _P, _P, c_int, c_int, _P]),
+    "dmx_edit_pages_prepare": (c_int, [_P, c_int, _P, c_int, c_int]),
+    "dmx_preprocess_crop_pages": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+    "dmx_postprocess_paste_pages": (c_int, [_P, c_int, _P, _P, c_int, _P, _P, c_int, _P]),
+    "dmx_readback_pixel_values_pages": (c_int, [_P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, _P, c_int64, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "dmx_postprocess_paste_select_pages": (c_int, [_P, c_int, _P, c_float, _P, _P, _P, c_int, _P, _P, c_int, c_int, _P]),
     "dmx_glyph_max_taps": (c_int, []),
     "dmx_glyph_resize_normalize": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "dmx_gemm_plan_override": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),

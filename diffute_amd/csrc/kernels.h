@@ -420,6 +420,10 @@ int dmx_gaussian_sample_launch(const float* moments, const float* noise, float* 
 
 // ------------------------------------------------------------------ prepost_batch.hip
 struct dmx_edit_item;                                  // include/diffute_hip.h
+struct dmx_edit_page;
 // the host-side checks of an item table, shared by every entry that takes one (prepost_batch.hip, readback.hip): a bad item is reported by
-// index through the last-error string; `prepared` also compares the derived fields with what dmx_edit_items_prepare fills
-int dmx_check_edit_items(const char* what, const dmx_edit_item* items, int B, int H, int W, int S, bool prepared);
+// index through the last-error string; `prepared` also compares the derived fields with what dmx_edit_items_prepare fills.
+// dmx_check_edit_pages: the same for a page table and every page's slice of the item table (bad pages by page index, bad items by their
+// index in the whole table; dmx_edit_pages_prepare fills the derived fields)
+int dmx_check_edit_items(const char* what, const dmx_edit_item* items, int B, int H, int W, int S, bool prepared, int index0 = 0);
+int dmx_check_edit_pages(const char* what, const dmx_edit_page* pages, int P, const dmx_edit_item* items, int B, int S, bool prepared);

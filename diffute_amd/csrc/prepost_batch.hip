@@ -5,6 +5,8 @@
 // writes), so there is neither a mask buffer nor a rasterise launch.  The per-pixel arithmetic is prepost_resize.h, the same
 // functions the single-box kernels call: row b is bit for bit what the single-box entry gives for item b.
 // Pure HBM-bound byte work: one thread per destination pixel, coalesced plain vector stores.
+// The *_pages kernels further down do the same for boxes on SEVERAL pages (pipeline.edit_pages): a second device table, of dmx_edit_page,
+// says where each page lives and which items are its own, and the functions below are called on one-page views of it.
 #include "common.h"
 #include "kernels.h"
 #include "prepost_resize.h"
@@ -19,9 +21,8 @@ struct PreBatchArgs {
   float* out_img; float* out_masked; unsigned char* out_mask; float* out_mask_lat;   // [B][3][S][S], [B][3][S][S], [B][S][S], [B][S/8][S/8]
 };
 
-__global__ __launch_bounds__(256) void dmx_preprocess_batch_kernel(const PreBatchArgs p) {
-  const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y, b = blockIdx.z;
-  if (dx >= p.S) return;
+// Destination pixel (dx, dy) of row b: item b of p.items cropped from p.img.
+__device__ __forceinline__ void pre_item(const PreBatchArgs& p, int b, int dx, int dy) {
   const dmx_edit_item it = p.items[b];
   const Geom g = item_geom(it, p.H, p.W, p.S, true);
   int vi[3], vm[3], vk;
@@ -34,6 +35,34 @@ __global__ __launch_bounds__(256) void dmx_preprocess_batch_kernel(const PreBatc
   const size_t plane = (size_t)p.S * p.S, lat = (size_t)(p.S >> 3) * (p.S >> 3);
   pre_store(vi, vm, vk, p.S, dx, dy, p.out_img + (size_t)b * 3 * plane, p.out_masked + (size_t)b * 3 * plane, p.out_mask + (size_t)b * plane,
             p.out_mask_lat ? p.out_mask_lat + (size_t)b * lat : nullptr);
+}
+
+__global__ __launch_bounds__(256) void dmx_preprocess_batch_kernel(const PreBatchArgs p) {
+  const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y, b = blockIdx.z;
+  if (dx >= p.S) return;
+  pre_item(p, b, dx, dy);
+}
+
+// ---- B boxes on P pages per launch (pipeline.edit_pages): a device table of dmx_edit_page says where each page lives and which
+// contiguous range of the item table belongs to it.  Every kernel below hands the functions above a one-page VIEW of its arguments -
+// the page's pointers and size, its slice of the item table - so a row / a page is bit for bit what the one-page kernel gives.
+// Whatever comes from the device tables is clamped: a stale table reads wrong pixels, never outside a page (the pages' own addresses
+// and sizes are trusted, as the one-page kernels trust their arguments).
+__device__ __forceinline__ int page_of(const dmx_edit_item& it, int P) { return min(max(it.reserved, 0), P - 1); }
+
+struct PrePagesArgs {
+  const dmx_edit_page* pages; int P;
+  const dmx_edit_item* items; int S;
+  float* out_img; float* out_masked; unsigned char* out_mask; float* out_mask_lat;
+};
+
+// the grid runs over items, as above; the item's page supplies the image pointer, H and W
+__global__ __launch_bounds__(256) void dmx_preprocess_pages_kernel(const PrePagesArgs p) {
+  const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y, b = blockIdx.z;
+  if (dx >= p.S) return;
+  const dmx_edit_page pg = p.pages[page_of(p.items[b], p.P)];
+  const PreBatchArgs v{(const unsigned char*)pg.original, pg.H, pg.W, p.items, p.S, p.out_img, p.out_masked, p.out_mask, p.out_mask_lat};
+  pre_item(v, b, dx, dy);
 }
 
 struct PostBatchArgs {
@@ -86,19 +115,13 @@ __global__ __launch_bounds__(256) void dmx_postprocess_batch_kernel(const PostBa
   paste_pixel(p, s_box, s_crop, [](int b) -> int { return b; }, x, y);
 }
 
-// Best of K candidates per item, chosen and pasted in ONE launch: p.vae is [B][K][3][S][S], scores [B][K] lives on the device, so the
-// host never waits for it.  Every block stages the score table in LDS and derives the same choices from it:
-//   choice[b] = arg-max over k of scores[b][k], the lowest k on a tie; a NaN never wins; 0 when every score is NaN;
-//   -1 (the item is skipped, its box keeps the original pixels) when the best score is below `threshold`.
-// Block (0, 0) alone writes `choice`, with plain vector stores.  The paste is paste_pixel, the rule of the kernel above.
-__global__ __launch_bounds__(256) void dmx_postprocess_select_kernel(const PostBatchArgs p, const float* scores, int K, float threshold, int* choice) {
-  __shared__ int4 s_box[DMX_EDIT_MAX_ITEMS], s_crop[DMX_EDIT_MAX_ITEMS];
-  __shared__ float s_score[DMX_EDIT_MAX_ITEMS * DMX_SELECT_MAX_CANDIDATES];
-  __shared__ int s_choice[DMX_EDIT_MAX_ITEMS];
-  stage_items(p, s_box, s_crop);
-  for (int i = threadIdx.x; i < p.B * K; i += blockDim.x) s_score[i] = scores[i];
+// choice[b] for all B items from the score table [B][K]: staged in LDS, one thread per item; `writer` blocks also store it to HBM.
+// Ends with a barrier: s_choice is complete on return.
+__device__ __forceinline__ void select_choices(const float* scores, int B, int K, float threshold, float* s_score, int* s_choice, int* choice,
+                                               bool writer) {
+  for (int i = threadIdx.x; i < B * K; i += blockDim.x) s_score[i] = scores[i];
   __syncthreads();
-  if ((int)threadIdx.x < p.B) {
+  if ((int)threadIdx.x < B) {
     const float* sc = s_score + threadIdx.x * K;
     int best = -1;
     float bv = 0.f;
@@ -109,31 +132,100 @@ __global__ __launch_bounds__(256) void dmx_postprocess_select_kernel(const PostB
     }
     const int ch = best < 0 ? 0 : (bv < threshold ? -1 : best);
     s_choice[threadIdx.x] = ch;
-    if (blockIdx.x == 0 && blockIdx.y == 0) choice[threadIdx.x] = ch;
+    if (writer) choice[threadIdx.x] = ch;
   }
   __syncthreads();
+}
+
+// Best of K candidates per item, chosen and pasted in ONE launch: p.vae is [B][K][3][S][S], scores [B][K] lives on the device, so the
+// host never waits for it.  Every block stages the score table in LDS and derives the same choices from it:
+//   choice[b] = arg-max over k of scores[b][k], the lowest k on a tie; a NaN never wins; 0 when every score is NaN;
+//   -1 (the item is skipped, its box keeps the original pixels) when the best score is below `threshold`.
+// Block (0, 0) alone writes `choice`, with plain vector stores.  The paste is paste_pixel, the rule of the kernel above.
+__global__ __launch_bounds__(256) void dmx_postprocess_select_kernel(const PostBatchArgs p, const float* scores, int K, float threshold, int* choice) {
+  __shared__ int4 s_box[DMX_EDIT_MAX_ITEMS], s_crop[DMX_EDIT_MAX_ITEMS];
+  __shared__ float s_score[DMX_EDIT_MAX_ITEMS * DMX_SELECT_MAX_CANDIDATES];
+  __shared__ int s_choice[DMX_EDIT_MAX_ITEMS];
+  stage_items(p, s_box, s_crop);
+  select_choices(scores, p.B, K, threshold, s_score, s_choice, choice, blockIdx.x == 0 && blockIdx.y == 0);
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= p.W) return;
   paste_pixel(p, s_box, s_crop, [&](int b) -> int { const int k = s_choice[b]; return k < 0 ? -1 : b * K + k; }, x, y);
 }
 
+// The paste over P pages in ONE launch.  The rows of all pages do not fit in grid.y, so blocks enumerate (page, row, column tile) along
+// grid.x: page p owns the blocks [block_lo, block_lo + H * ceil(W / 256)).  A block finds its page by a uniform scan of the (at most
+// 64) block_lo values, then pastes one 256-pixel tile of one row through paste_pixel with the page's view: a pixel scans only its own
+// page's items, last to first.
+struct PostPagesArgs {
+  const float* vae; int S;
+  const dmx_edit_page* pages; int P;
+  const dmx_edit_item* items; int B;
+};
+struct PageTile { PostBatchArgs view; int lo, x, y; };
+
+// false: the block has no pixel to write (a stale table - with a good one every block lies inside its page).  Uniform per block.
+__device__ __forceinline__ bool page_tile(const PostPagesArgs& p, PageTile& t) {
+  int pi = 0;
+  for (int i = 1; i < p.P; ++i) pi = (int)blockIdx.x >= p.pages[i].block_lo ? i : pi;
+  const dmx_edit_page pg = p.pages[pi];
+  if (pg.H <= 0 || pg.W <= 0 || pg.W > DMX_EDIT_PAGE_MAX_W) return false;
+  const int tiles = (pg.W + 255) / 256, local = (int)blockIdx.x - pg.block_lo;
+  if (local < 0 || local / tiles >= pg.H) return false;
+  t.lo = min(max(pg.item_lo, 0), p.B - 1);
+  const int n = min(max(pg.item_hi - t.lo, 1), p.B - t.lo);
+  t.view = PostBatchArgs{p.vae, p.S, (const unsigned char*)pg.original, (unsigned char*)pg.out, (unsigned char*)pg.union_mask, pg.H, pg.W,
+                         p.items + t.lo, n};
+  t.y = local / tiles;
+  t.x = (local % tiles) * 256 + (int)threadIdx.x;
+  return true;
+}
+
+__global__ __launch_bounds__(256) void dmx_postprocess_pages_kernel(const PostPagesArgs p) {
+  __shared__ int4 s_box[DMX_EDIT_MAX_ITEMS], s_crop[DMX_EDIT_MAX_ITEMS];
+  PageTile t;
+  if (!page_tile(p, t)) return;
+  stage_items(t.view, s_box, s_crop);
+  __syncthreads();
+  if (t.x >= t.view.W) return;
+  const int lo = t.lo;
+  paste_pixel(t.view, s_box, s_crop, [lo](int b) -> int { return lo + b; }, t.x, t.y);
+}
+
+// choice is [B] over all items and every block derives all of it (one rule, one table); block 0 alone stores it
+__global__ __launch_bounds__(256) void dmx_postprocess_select_pages_kernel(const PostPagesArgs p, const float* scores, int K, float threshold,
+                                                                           int* choice) {
+  __shared__ int4 s_box[DMX_EDIT_MAX_ITEMS], s_crop[DMX_EDIT_MAX_ITEMS];
+  __shared__ float s_score[DMX_EDIT_MAX_ITEMS * DMX_SELECT_MAX_CANDIDATES];
+  __shared__ int s_choice[DMX_EDIT_MAX_ITEMS];
+  PageTile t;
+  const bool live = page_tile(p, t);
+  if (!live && blockIdx.x != 0) return;
+  if (live) stage_items(t.view, s_box, s_crop);
+  select_choices(scores, p.B, K, threshold, s_score, s_choice, choice, blockIdx.x == 0);
+  if (!live || t.x >= t.view.W) return;
+  const int lo = t.lo;
+  paste_pixel(t.view, s_box, s_crop, [&](int b) -> int { const int k = s_choice[lo + b]; return k < 0 ? -1 : (lo + b) * K + k; }, t.x, t.y);
+}
+
 }  // namespace
 
 // the checks of the single-box entries, per item; `prepared` also compares the derived fields with what edit_items_prepare fills
-int dmx_check_edit_items(const char* what, const dmx_edit_item* items, int B, int H, int W, int S, bool prepared) {
+// (index0: the table index of items[0], for the messages - the pages entries check one page's slice at a time)
+int dmx_check_edit_items(const char* what, const dmx_edit_item* items, int B, int H, int W, int S, bool prepared, int index0) {
   DMX_REQUIRE(items, "%s: null item table", what);
   DMX_REQUIRE(B >= 1 && B <= DMX_EDIT_MAX_ITEMS, "%s: %d items, expected 1 .. %d", what, B, DMX_EDIT_MAX_ITEMS);
   DMX_REQUIRE(H > 0 && W > 0 && H <= 65535 && S > 0 && S <= 65535, "%s: bad sizes (image %dx%d, S %d)", what, W, H, S);
   for (int b = 0; b < B; ++b) {
     const dmx_edit_item& it = items[b];
-    DMX_REQUIRE(it.crop_scale > 0, "%s: item %d: crop_scale %d", what, b, it.crop_scale);
-    DMX_REQUIRE(it.x_s >= 0 && it.y_s >= 0 && it.x_s < W && it.y_s < H, "%s: item %d: crop origin (%d, %d) outside the %dx%d image", what, b,
+    DMX_REQUIRE(it.crop_scale > 0, "%s: item %d: crop_scale %d", what, index0 + b, it.crop_scale);
+    DMX_REQUIRE(it.x_s >= 0 && it.y_s >= 0 && it.x_s < W && it.y_s < H, "%s: item %d: crop origin (%d, %d) outside the %dx%d image", what, index0 + b,
                 it.x_s, it.y_s, W, H);
     if (!prepared) continue;
     const Geom a = pre_geom(H, W, it.x_s, it.y_s, it.crop_scale, S), z = post_geom(H, W, it.x_s, it.y_s, it.crop_scale, S);
     DMX_REQUIRE(it.cw == a.cw && it.ch == a.ch && it.pre_area2 == a.area2 && it.post_area2 == z.area2 && it.pre_sx == a.sx && it.pre_sy == a.sy &&
                     it.post_sx == z.sx && it.post_sy == z.sy,
-                "%s: item %d: derived fields do not belong to a %dx%d image at S = %d (dmx_edit_items_prepare fills them)", what, b, W, H, S);
+                "%s: item %d: derived fields do not belong to a %dx%d image at S = %d (dmx_edit_items_prepare fills them)", what, index0 + b, W, H, S);
   }
   return DMX_OK;
 }
@@ -184,4 +276,105 @@ extern "C" int dmx_postprocess_paste_select(const float* image_vae, int S, const
   PostBatchArgs p{image_vae, S, original_hwc, out_hwc, union_mask, H, W, items_device, B};
   hipLaunchKernelGGL(dmx_postprocess_select_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, p, scores, K, threshold, choice);
   return dmx_check_launch("dmx_postprocess_select_kernel");
+}
+
+// ---- pages
+// the page table, then every page's slice of the item table against that page; `prepared` also compares the derived fields of both
+// tables with what edit_pages_prepare fills.  A bad page is named by page index, a bad item by its index in the whole table.
+int dmx_check_edit_pages(const char* what, const dmx_edit_page* pages, int P, const dmx_edit_item* items, int B, int S, bool prepared) {
+  DMX_REQUIRE(pages && items, "%s: null page or item table", what);
+  DMX_REQUIRE(P >= 1 && P <= DMX_EDIT_MAX_ITEMS, "%s: %d pages, expected 1 .. %d", what, P, DMX_EDIT_MAX_ITEMS);
+  DMX_REQUIRE(B >= 1 && B <= DMX_EDIT_MAX_ITEMS, "%s: %d items, expected 1 .. %d", what, B, DMX_EDIT_MAX_ITEMS);
+  long long blocks = 0;
+  for (int q = 0, next = 0; q < P; ++q) {
+    const dmx_edit_page& pg = pages[q];
+    // (W + 255 must not overflow an int, here or in the kernels' tile count)
+    DMX_REQUIRE(pg.H > 0 && pg.W > 0 && pg.H <= 65535 && pg.W <= DMX_EDIT_PAGE_MAX_W, "%s: page %d: bad size %dx%d (1 <= H <= 65535, 1 <= W <= %d)", what,
+                q, pg.W, pg.H, DMX_EDIT_PAGE_MAX_W);
+    DMX_REQUIRE(pg.item_hi > pg.item_lo, "%s: page %d: no items (range [%d, %d))", what, q, pg.item_lo, pg.item_hi);
+    DMX_REQUIRE(pg.item_lo == next && pg.item_hi <= B,
+                "%s: page %d: its items [%d, %d) must start at %d and end at or before %d (the ranges tile [0, B) in page order)", what, q, pg.item_lo,
+                pg.item_hi, next, B);
+    DMX_REQUIRE(q + 1 < P || pg.item_hi == B, "%s: page %d: the last page's items end at %d, the table holds %d", what, q, pg.item_hi, B);
+    next = pg.item_hi;
+    const long long mine = (long long)pg.H * cdiv(pg.W, 256);
+    DMX_REQUIRE(blocks + mine < (1ll << 31), "%s: page %d: the pages need more than 2^31 - 1 blocks of 256 pixels", what, q);
+    if (prepared)
+      DMX_REQUIRE(pg.block_lo == (int)blocks && pg.blocks == (int)mine,
+                  "%s: page %d: derived fields do not belong to this page table (dmx_edit_pages_prepare fills them)", what, q);
+    blocks += mine;
+    const int rc = dmx_check_edit_items(what, items + pg.item_lo, pg.item_hi - pg.item_lo, pg.H, pg.W, S, prepared, pg.item_lo);
+    if (rc != DMX_OK) return rc;
+    if (prepared)
+      for (int b = pg.item_lo; b < pg.item_hi; ++b)
+        DMX_REQUIRE(items[b].reserved == q, "%s: item %d: page index %d, the item lies in the range of page %d (dmx_edit_pages_prepare fills it)", what, b,
+                    items[b].reserved, q);
+  }
+  return DMX_OK;
+}
+
+static int check_page_addresses(const char* what, const dmx_edit_page* pages, int P, bool need_out) {
+  for (int q = 0; q < P; ++q) {
+    DMX_REQUIRE(pages[q].original, "%s: page %d: null original image", what, q);
+    DMX_REQUIRE(!need_out || (pages[q].out && pages[q].out != pages[q].original), "%s: page %d: the output image is null or the original itself", what, q);
+  }
+  return DMX_OK;
+}
+
+extern "C" int dmx_edit_pages_prepare(dmx_edit_page* pages, int P, dmx_edit_item* items, int B, int S) {
+  int rc = dmx_check_edit_pages("edit_pages_prepare", pages, P, items, B, S, false);
+  if (rc != DMX_OK) return rc;
+  int blocks = 0;
+  for (int q = 0; q < P; ++q) {
+    dmx_edit_page& pg = pages[q];
+    rc = dmx_edit_items_prepare(items + pg.item_lo, pg.item_hi - pg.item_lo, pg.H, pg.W, S);      // each item with its own page's size
+    if (rc != DMX_OK) return rc;
+    for (int b = pg.item_lo; b < pg.item_hi; ++b) items[b].reserved = q;
+    pg.block_lo = blocks; pg.blocks = pg.H * cdiv(pg.W, 256);
+    blocks += pg.blocks;
+  }
+  return DMX_OK;
+}
+
+extern "C" int dmx_preprocess_crop_pages(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_item* items_host,
+                                         const dmx_edit_item* items_device, int B, int S, float* out_image, float* out_masked_image,
+                                         unsigned char* out_mask, float* out_mask_latent, dmx_stream_t stream) {
+  DMX_REQUIRE(pages_device && items_device && out_image && out_masked_image && out_mask, "preprocess_crop_pages: null argument");
+  DMX_REQUIRE(S > 0 && S <= 65535 && S % 8 == 0, "preprocess_crop_pages: S = %d is no positive multiple of 8 (up to 65535)", S);
+  int rc = dmx_check_edit_pages("preprocess_crop_pages", pages_host, P, items_host, B, S, true);
+  if (rc == DMX_OK) rc = check_page_addresses("preprocess_crop_pages", pages_host, P, false);
+  if (rc != DMX_OK) return rc;
+  PrePagesArgs p{pages_device, P, items_device, S, out_image, out_masked_image, out_mask, out_mask_latent};
+  hipLaunchKernelGGL(dmx_preprocess_pages_kernel, dim3(cdiv(S, 256), S, B), dim3(256), 0, (hipStream_t)stream, p);
+  return dmx_check_launch("dmx_preprocess_pages_kernel");
+}
+
+extern "C" int dmx_postprocess_paste_pages(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                           const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, dmx_stream_t stream) {
+  DMX_REQUIRE(image_vae && pages_device && items_device, "postprocess_paste_pages: null argument");
+  DMX_REQUIRE(S > 0 && S <= 65535, "postprocess_paste_pages: bad S = %d", S);
+  int rc = dmx_check_edit_pages("postprocess_paste_pages", pages_host, P, items_host, B, S, true);
+  if (rc == DMX_OK) rc = check_page_addresses("postprocess_paste_pages", pages_host, P, true);
+  if (rc != DMX_OK) return rc;
+  PostPagesArgs p{image_vae, S, pages_device, P, items_device, B};
+  hipLaunchKernelGGL(dmx_postprocess_pages_kernel, dim3(pages_host[P - 1].block_lo + pages_host[P - 1].blocks), dim3(256), 0, (hipStream_t)stream, p);
+  return dmx_check_launch("dmx_postprocess_pages_kernel");
+}
+
+extern "C" int dmx_postprocess_paste_select_pages(const float* image_vae, int S, const float* scores, float threshold, int* choice,
+                                                  const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                                  const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K,
+                                                  dmx_stream_t stream) {
+  DMX_REQUIRE(image_vae && scores && choice && pages_device && items_device, "postprocess_paste_select_pages: null argument");
+  DMX_REQUIRE(S > 0 && S <= 65535, "postprocess_paste_select_pages: bad S = %d", S);
+  DMX_REQUIRE(K >= 1 && K <= DMX_SELECT_MAX_CANDIDATES, "postprocess_paste_select_pages: %d candidates per box, expected 1 .. %d", K,
+              DMX_SELECT_MAX_CANDIDATES);
+  DMX_REQUIRE(!(threshold != threshold), "postprocess_paste_select_pages: the threshold is NaN (pass -inf for none)");
+  int rc = dmx_check_edit_pages("postprocess_paste_select_pages", pages_host, P, items_host, B, S, true);
+  if (rc == DMX_OK) rc = check_page_addresses("postprocess_paste_select_pages", pages_host, P, true);
+  if (rc != DMX_OK) return rc;
+  PostPagesArgs p{image_vae, S, pages_device, P, items_device, B};
+  hipLaunchKernelGGL(dmx_postprocess_select_pages_kernel, dim3(pages_host[P - 1].block_lo + pages_host[P - 1].blocks), dim3(256), 0,
+                     (hipStream_t)stream, p, scores, K, threshold, choice);
+  return dmx_check_launch("dmx_postprocess_select_pages_kernel");
 }

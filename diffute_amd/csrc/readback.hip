@@ -25,9 +25,8 @@ struct ReadbackArgs {
   int S_h, S_w; float* out; unsigned char* out_u8;         // [B*K][3][S_h][S_w]
 };
 
-__global__ __launch_bounds__(128) void dmx_readback_pixel_values_kernel(const ReadbackArgs p) {
-  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y, r = blockIdx.z;       // r = b * K + k
-  if (ox >= p.S_w) return;
+// Output pixel (ox, oy) of row r = b * K + k: item b of p.items on the page p.ori.
+__device__ __forceinline__ void readback_row(const ReadbackArgs& p, int r, int ox, int oy) {
   const int b = r / p.K;
   const dmx_edit_item it = p.items[b];
   const dmx_readback_pass ps = p.passes[b];
@@ -51,6 +50,48 @@ __global__ __launch_bounds__(128) void dmx_readback_pixel_values_kernel(const Re
     if (p.out_u8) p.out_u8[o + c * plane] = (unsigned char)v[c];
   }
 }
+
+__global__ __launch_bounds__(128) void dmx_readback_pixel_values_kernel(const ReadbackArgs p) {
+  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y, r = blockIdx.z;       // r = b * K + k
+  if (ox >= p.S_w) return;
+  readback_row(p, r, ox, oy);
+}
+
+// Items on several pages (include/diffute_hip.h dmx_edit_page): p.ori / p.H / p.W are unset on entry, the item's page - its index
+// travels in the item, clamped here - supplies them, and the row is readback_row's on that one-page view.
+__global__ __launch_bounds__(128) void dmx_readback_pages_kernel(ReadbackArgs p, const dmx_edit_page* pages, int P) {
+  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y, r = blockIdx.z;
+  if (ox >= p.S_w) return;
+  const dmx_edit_page pg = pages[min(max(p.items[r / p.K].reserved, 0), P - 1)];
+  p.ori = (const unsigned char*)pg.original; p.H = pg.H; p.W = pg.W;
+  readback_row(p, r, ox, oy);
+}
+
+// what the read-back asks of the items [lo, hi) beyond dmx_check_edit_items: a non-empty box inside the H x W page, pass tables inside `tables`
+int check_readback_items(const char* what, const dmx_edit_item* items_host, const dmx_readback_pass* passes_host, int lo, int hi, int H, int W,
+                         int max_taps, long long table_ints, int S_h, int S_w) {
+  for (int b = lo; b < hi; ++b) {
+    const dmx_edit_item& it = items_host[b];
+    DMX_REQUIRE(it.x2 > it.x1 && it.y2 > it.y1, "%s: item %d: empty box (%d, %d, %d, %d)", what, b, it.x1, it.y1, it.x2, it.y2);
+    DMX_REQUIRE(it.x1 >= 0 && it.y1 >= 0 && it.x2 <= W && it.y2 <= H, "%s: item %d: box (%d, %d, %d, %d) outside the %dx%d image", what, b, it.x1,
+                it.y1, it.x2, it.y2, W, H);
+    const dmx_readback_pass& ps = passes_host[b];
+    const struct { const char* name; int off, taps, n_in, n_out; } pass[2] = {{"horizontal", ps.h_off, ps.h_taps, it.x2 - it.x1, S_w},
+                                                                             {"vertical", ps.v_off, ps.v_taps, it.y2 - it.y1, S_h}};
+    for (const auto& q : pass) {
+      if (q.n_in == q.n_out) {                                                                 // equal sizes: Pillow skips the pass
+        DMX_REQUIRE(q.off < 0, "%s: item %d: the %s pass resizes %d -> %d and must be skipped (offset < 0)", what, b, q.name, q.n_in, q.n_out);
+        continue;
+      }
+      DMX_REQUIRE(q.off >= 0 && q.taps >= 1 && q.taps <= max_taps, "%s: item %d: %s pass: offset %d, %d taps (max_taps %d)", what, b, q.name, q.off,
+                  q.taps, max_taps);
+      DMX_REQUIRE((long long)q.off + 2ll * q.n_out + (long long)q.n_out * q.taps <= table_ints,
+                  "%s: item %d: the %s table (offset %d, %d x %d taps) ends past the %lld ints of `tables`", what, b, q.name, q.off, q.n_out, q.taps,
+                  table_ints);
+    }
+  }
+  return DMX_OK;
+}
 }  // namespace
 
 extern "C" int dmx_readback_pixel_values(const float* image_vae, int S, const unsigned char* original_hwc, int H, int W,
@@ -68,27 +109,36 @@ extern "C" int dmx_readback_pixel_values(const float* image_vae, int S, const un
   DMX_REQUIRE(table_ints >= 0 && table_ints < (1ll << 31), "readback_pixel_values: bad table size %lld", table_ints);
   const int rc = dmx_check_edit_items("readback_pixel_values", items_host, B, H, W, S, true);
   if (rc != DMX_OK) return rc;
-  for (int b = 0; b < B; ++b) {
-    const dmx_edit_item& it = items_host[b];
-    DMX_REQUIRE(it.x2 > it.x1 && it.y2 > it.y1, "readback_pixel_values: item %d: empty box (%d, %d, %d, %d)", b, it.x1, it.y1, it.x2, it.y2);
-    DMX_REQUIRE(it.x1 >= 0 && it.y1 >= 0 && it.x2 <= W && it.y2 <= H, "readback_pixel_values: item %d: box (%d, %d, %d, %d) outside the %dx%d image",
-                b, it.x1, it.y1, it.x2, it.y2, W, H);
-    const dmx_readback_pass& ps = passes_host[b];
-    const struct { const char* name; int off, taps, n_in, n_out; } pass[2] = {{"horizontal", ps.h_off, ps.h_taps, it.x2 - it.x1, S_w},
-                                                                             {"vertical", ps.v_off, ps.v_taps, it.y2 - it.y1, S_h}};
-    for (const auto& q : pass) {
-      if (q.n_in == q.n_out) {                                                                 // equal sizes: Pillow skips the pass
-        DMX_REQUIRE(q.off < 0, "readback_pixel_values: item %d: the %s pass resizes %d -> %d and must be skipped (offset < 0)", b, q.name, q.n_in, q.n_out);
-        continue;
-      }
-      DMX_REQUIRE(q.off >= 0 && q.taps >= 1 && q.taps <= max_taps, "readback_pixel_values: item %d: %s pass: offset %d, %d taps (max_taps %d)", b,
-                  q.name, q.off, q.taps, max_taps);
-      DMX_REQUIRE((long long)q.off + 2ll * q.n_out + (long long)q.n_out * q.taps <= table_ints,
-                  "readback_pixel_values: item %d: the %s table (offset %d, %d x %d taps) ends past the %lld ints of `tables`", b, q.name, q.off,
-                  q.n_out, q.taps, table_ints);
-    }
-  }
+  const int rb = check_readback_items("readback_pixel_values", items_host, passes_host, 0, B, H, W, max_taps, table_ints, S_h, S_w);
+  if (rb != DMX_OK) return rb;
   ReadbackArgs p{image_vae, S, original_hwc, H, W, items_device, passes_device, B, K, tables, norm, S_h, S_w, out_pixel_values, out_resized};
   hipLaunchKernelGGL(dmx_readback_pixel_values_kernel, dim3(cdiv(S_w, 128), S_h, B * K), dim3(128), 0, (hipStream_t)stream, p);
   return dmx_check_launch("dmx_readback_pixel_values_kernel");
+}
+
+extern "C" int dmx_readback_pixel_values_pages(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                               const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, const int* tables,
+                                               long long table_ints, const float* norm, const dmx_readback_pass* passes_host,
+                                               const dmx_readback_pass* passes_device, int max_taps, int S_h, int S_w, float* out_pixel_values,
+                                               unsigned char* out_resized, dmx_stream_t stream) {
+  const char* what = "readback_pixel_values_pages";
+  DMX_REQUIRE(image_vae && pages_device && items_device && tables && norm && passes_host && passes_device && out_pixel_values, "%s: null argument", what);
+  DMX_REQUIRE(S > 0 && S <= 65535, "%s: bad S = %d", what, S);
+  DMX_REQUIRE(K >= 1 && K <= DMX_SELECT_MAX_CANDIDATES, "%s: %d candidates per box, expected 1 .. %d", what, K, DMX_SELECT_MAX_CANDIDATES);
+  DMX_REQUIRE(S_h > 0 && S_h <= 65535 && S_w > 0 && S_w <= 65535, "%s: bad output size %dx%d", what, S_w, S_h);
+  DMX_REQUIRE(max_taps >= 0 && max_taps <= DMX_GLYPH_MAX_TAPS,
+              "%s: %d taps per output pixel exceed the cap of %d (downscale ratio at most 31 for bilinear, 15 for bicubic)", what, max_taps,
+              DMX_GLYPH_MAX_TAPS);
+  DMX_REQUIRE(table_ints >= 0 && table_ints < (1ll << 31), "%s: bad table size %lld", what, table_ints);
+  int rc = dmx_check_edit_pages(what, pages_host, P, items_host, B, S, true);
+  if (rc != DMX_OK) return rc;
+  for (int q = 0; q < P; ++q) {
+    const dmx_edit_page& pg = pages_host[q];
+    DMX_REQUIRE(pg.original, "%s: page %d: null original image", what, q);
+    rc = check_readback_items(what, items_host, passes_host, pg.item_lo, pg.item_hi, pg.H, pg.W, max_taps, table_ints, S_h, S_w);
+    if (rc != DMX_OK) return rc;
+  }
+  ReadbackArgs p{image_vae, S, nullptr, 0, 0, items_device, passes_device, B, K, tables, norm, S_h, S_w, out_pixel_values, out_resized};
+  hipLaunchKernelGGL(dmx_readback_pages_kernel, dim3(cdiv(S_w, 128), S_h, B * K), dim3(128), 0, (hipStream_t)stream, p, pages_device, P);
+  return dmx_check_launch("dmx_readback_pages_kernel");
 }

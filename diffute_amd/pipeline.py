@@ -193,9 +193,27 @@ def edit_boxes(unet, vae, scheduler, instance_image, locations, encoder_hidden_s
     N = len(locations)
     if int(batch_size) < 1:
         raise ValueError("batch_size must be at least 1")
-    if not isinstance(instance_image, torch.Tensor) or instance_image.dim() != 3:
-        raise TypeError("instance_image: expected a contiguous uint8 CUDA tensor [h][w][3]")
-    h, w = int(instance_image.shape[0]), int(instance_image.shape[1])
+    h, w = _page_size(instance_image, "instance_image")
+    crop_scales, origins = _plan_boxes(locations, h, w, origins, crop_scales, rng)
+    _check_contexts(N, encoder_hidden_states)
+    pre = prepost.preprocess_batch(instance_image, locations, origins, crop_scales, size=size)
+    image_vae = _edit_rows(unet, vae, scheduler, pre, instance_image.device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
+                           enc_noise, variance_noise, int(size))
+    out = prepost.postprocess_batch(image_vae, instance_image, locations, origins, crop_scales)
+    return (out, image_vae, pre) if return_intermediate else out
+
+
+def _page_size(image, name):
+    """(h, w) of one page; only that it is a 3-d tensor is asked here - dtype, device and layout are prepost's to check"""
+    if not isinstance(image, torch.Tensor) or image.dim() != 3:
+        raise TypeError(f"{name}: expected a contiguous uint8 CUDA tensor [h][w][3]")
+    return int(image.shape[0]), int(image.shape[1])
+
+
+def _plan_boxes(locations, h, w, origins, crop_scales, rng):
+    """crop_scales / origins of the boxes of one h x w page where they are not given: the reference's ladder and origin rule, random
+    origins drawn from `rng` (default numpy's global state) in box order.  Returns (crop_scales, origins)."""
+    N = len(locations)
     if crop_scales is None:
         crop_scales = [prepost.crop_scale_for(loc, h, w) for loc in locations]
     crop_scales = list(crop_scales)
@@ -203,23 +221,76 @@ def edit_boxes(unet, vae, scheduler, instance_image, locations, encoder_hidden_s
         if len(crop_scales) != N:
             raise ValueError(f"{N} boxes, {len(crop_scales)} crop scales: the lengths must agree")
         origins = [prepost.crop_origin(loc, cs, w, rng if rng is not None else np.random) for loc, cs in zip(locations, crop_scales)]
+    return crop_scales, origins
+
+
+def _check_contexts(N, encoder_hidden_states):
     if encoder_hidden_states.shape[0] != N:
         raise ValueError(f"{N} boxes but {encoder_hidden_states.shape[0]} glyph contexts")
-    pre = prepost.preprocess_batch(instance_image, locations, origins, crop_scales, size=size)
+
+
+def _page_lists(images, locations, origins, crop_scales, rng):
+    """the list arguments of edit_pages / edit_pages_verified: P pages, P lists of boxes, origins / crop_scales None or P lists; what is
+    not given is planned page after page on one rng stream (prepost.plan_pages' draws).  Returns (images, locations, origins,
+    crop_scales, sizes, N) with P lists each."""
+    images, locations = list(images), [list(l) for l in locations]
+    origins = None if origins is None else [None if l is None else list(l) for l in origins]              # materialised once: a generator
+    crop_scales = None if crop_scales is None else [None if l is None else list(l) for l in crop_scales]  # would not survive the length checks
+    P = len(images)
+    if len(locations) != P:
+        raise ValueError(f"{P} pages, {len(locations)} lists of boxes: the lengths must agree")
+    for name, lst in (("origins", origins), ("crop_scales", crop_scales)):
+        if lst is not None and len(lst) != P:
+            raise ValueError(f"{P} pages, {len(lst)} lists of {name}: the lengths must agree")
+    sizes = [_page_size(img, f"images[{p}]") for p, img in enumerate(images)]
+    origins, crop_scales = [None] * P if origins is None else origins, [None] * P if crop_scales is None else crop_scales
+    for p, (h, w) in enumerate(sizes):
+        for name, lst in (("origins", origins[p]), ("crop_scales", crop_scales[p])):
+            if lst is not None and len(lst) != len(locations[p]):
+                raise ValueError(f"page {p}: {len(locations[p])} boxes, {len(lst)} {name}: the lengths must agree")
+        crop_scales[p], origins[p] = _plan_boxes(locations[p], h, w, origins[p], crop_scales[p], rng)
+    return images, locations, origins, crop_scales, sizes, sum(len(l) for l in locations)
+
+
+@torch.no_grad()
+def _edit_rows(unet, vae, scheduler, pre, dev, encoder_hidden_states, num_inference_steps, bs, generator, enc_noise, variance_noise, S):
+    """the model part of edit_boxes / edit_pages: the N rows of the preprocess dict `pre` through edit_latents in chunks of `bs` (the last
+    chunk may be smaller) -> image_vae [N,3,S,S].  A row's page plays no part here."""
+    N = pre["image"].shape[0]
     f = 2 ** (len(vae.config.block_out_channels) - 1)
-    S = int(size)
     # app.ipynb:796-801: ONE seed-0 draw of a single sample, shared by every box
-    init = torch.randn((1, vae.config.latent_channels, S // f, S // f), generator=torch.manual_seed(0), dtype=torch.float32).to(instance_image.device)
+    init = torch.randn((1, vae.config.latent_channels, S // f, S // f), generator=torch.manual_seed(0), dtype=torch.float32).to(dev)
     outs = []
-    for lo in range(0, N, int(batch_size)):
-        hi = min(N, lo + int(batch_size))
+    for lo in range(0, N, bs):
+        hi = min(N, lo + bs)
         outs.append(edit_latents(unet, vae, scheduler, pre["image"][lo:hi], pre["masked_image"][lo:hi], pre["mask"][lo:hi],
                                  encoder_hidden_states[lo:hi], num_inference_steps,
                                  init_latents=init.expand(hi - lo, -1, -1, -1).contiguous(), generator=generator,
                                  enc_noise=None if enc_noise is None else enc_noise[lo:hi],
                                  variance_noise=None if variance_noise is None else variance_noise[:, lo:hi]))
-    image_vae = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
-    out = prepost.postprocess_batch(image_vae, instance_image, locations, origins, crop_scales)
+    return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+
+@torch.no_grad()
+def edit_pages(unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, *, origins=None, crop_scales=None,
+               rng=None, batch_size=4, generator=None, enc_noise=None, variance_noise=None, return_intermediate=False, size=512):
+    """edit_boxes for boxes on SEVERAL pages as one batch - what a service holding requests for different images, or a training batch
+    of one box per image, needs.  images: a list of P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device; locations: P lists of
+    boxes (x1, y1, x2, y2); origins / crop_scales: None or P lists, as for edit_boxes per page (what is not given is planned page after
+    page, random origins drawn from `rng` in that order: prepost.plan_pages).  Rows are page-major - page 0's boxes in order, then
+    page 1's -, N in all: encoder_hidden_states [N,L,D], enc_noise [N,4,h,w], variance_noise [steps,N,4,h,w].
+
+    One preprocess_pages launch, the N rows through edit_latents in chunks of `batch_size` (chunks cross page boundaries; every box
+    starts from the seed-0 single-sample draw), one postprocess_pages launch.  Returns the list of P edited pages, with
+    return_intermediate=True also image_vae [N,3,S,S] and the preprocess dict.  With one page this is [edit_boxes(...)], bit for bit."""
+    if int(batch_size) < 1:
+        raise ValueError("batch_size must be at least 1")
+    images, locations, origins, crop_scales, _, N = _page_lists(images, locations, origins, crop_scales, rng)
+    _check_contexts(N, encoder_hidden_states)
+    pre = prepost.preprocess_pages(images, locations, origins, crop_scales, size=size)
+    image_vae = _edit_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
+                           enc_noise, variance_noise, int(size))
+    out = prepost.postprocess_pages(image_vae, images, locations, origins, crop_scales)
     return (out, image_vae, pre) if return_intermediate else out
 
 
@@ -232,12 +303,8 @@ class VerifiedEdit:
         self.image, self.choice, self.scores, self.image_vae, self.pixel_values, self.pre = image, choice, scores, image_vae, pixel_values, pre
 
 
-def _check_verified_args(ocr, processor, instance_image, locations, encoder_hidden_states, labels, candidates, seeds, min_score, batch_size,
-                         ocr_batch_size, origins, crop_scales, size):
-    """every argument check of edit_boxes_verified, on the host side: nothing touches the GPU before it passes.
-    Returns (N, K, seeds, h, w, image processor)."""
-    locations = list(locations)
-    N = len(locations)
+def _check_verified_counts(N, candidates, seeds, min_score, batch_size, ocr_batch_size):
+    """-> (K, seeds)"""
     if N < 1 or N > _cabi.EDIT_MAX_ITEMS:
         raise ValueError(f"{N} boxes, expected 1 .. {_cabi.EDIT_MAX_ITEMS}")
     if int(batch_size) < 1 or int(ocr_batch_size) < 1:
@@ -250,14 +317,11 @@ def _check_verified_args(ocr, processor, instance_image, locations, encoder_hidd
         raise ValueError(f"{K} candidates but {len(seeds)} seeds")
     if min_score is not None and float(min_score) != float(min_score):
         raise ValueError("min_score is NaN")
-    if not isinstance(instance_image, torch.Tensor) or instance_image.dim() != 3:
-        raise TypeError("instance_image: expected a contiguous uint8 CUDA tensor [h][w][3]")
-    h, w = int(instance_image.shape[0]), int(instance_image.shape[1])
-    for name, lst in (("origins", origins), ("crop_scales", crop_scales)):
-        if lst is not None and len(list(lst)) != N:
-            raise ValueError(f"{N} boxes, {len(list(lst))} {name}: the lengths must agree")
-    if encoder_hidden_states.shape[0] != N:
-        raise ValueError(f"{N} boxes but {encoder_hidden_states.shape[0]} glyph contexts")
+    return K, seeds
+
+
+def _check_verified_labels(ocr, N, encoder_hidden_states, labels):
+    _check_contexts(N, encoder_hidden_states)
     if not torch.is_tensor(labels) or labels.dtype != torch.int64:
         raise ValueError(f"labels must be an int64 tensor, got {getattr(labels, 'dtype', type(labels))}")
     if labels.ndim != 2 or labels.shape[0] != N or labels.shape[1] < 1:
@@ -267,7 +331,10 @@ def _check_verified_args(ocr, processor, instance_image, locations, encoder_hidd
         raise ValueError(f"labels have T = {labels.shape[1]} positions, the decoder {P}")
     if not labels.is_cuda and bool((((labels < 0) | (labels >= V)) & (labels != -100)).any()):      # (labels on the device: ocr.score checks them)
         raise ValueError(f"labels must lie in [0, {V}) or equal -100")
-    prepost.check_readback_boxes(locations, h, w)
+
+
+def _check_verified_processor(ocr, processor, size):
+    """-> the image processor"""
     ip =getattr(processor, "image_processor", processor)
     if not getattr(ip, "do_resize", False):
         raise ValueError("the processor must resize (do_resize=True)")
@@ -276,7 +343,23 @@ def _check_verified_args(ocr, processor, instance_image, locations, encoder_hidd
         raise ValueError(f"the processor resizes to {ip.size['width']}x{ip.size['height']}, ocr.encoder reads {want}x{want}")
     if int(size) < 8 or int(size) % 8:
         raise ValueError(f"size = {size} is no positive multiple of 8")
-    return N, K, seeds, h, w, ip
+    return ip
+
+
+def _check_verified_args(ocr, processor, instance_image, locations, encoder_hidden_states, labels, candidates, seeds, min_score, batch_size,
+                         ocr_batch_size, origins, crop_scales, size):
+    """every argument check of edit_boxes_verified, on the host side: nothing touches the GPU before it passes.
+    Returns (N, K, seeds, h, w, image processor)."""
+    locations = list(locations)
+    N = len(locations)
+    K, seeds = _check_verified_counts(N, candidates, seeds, min_score, batch_size, ocr_batch_size)
+    h, w = _page_size(instance_image, "instance_image")
+    for name, lst in (("origins", origins), ("crop_scales", crop_scales)):
+        if lst is not None and len(list(lst)) != N:
+            raise ValueError(f"{N} boxes, {len(list(lst))} {name}: the lengths must agree")
+    _check_verified_labels(ocr, N, encoder_hidden_states, labels)
+    prepost.check_readback_boxes(locations, h, w)
+    return N, K, seeds, h, w, _check_verified_processor(ocr, processor, size)
 
 
 @torch.no_grad()
@@ -285,9 +368,15 @@ def _edit_candidates(unet, vae, scheduler, instance_image, locations, origins, c
     """the generating half of edit_boxes_verified: (preprocess dict, image_vae [N,K,3,S,S]).  Each box is preprocessed and VAE-encoded once;
     the N*K rows (box-major, candidate k from seeds[k]) go through denoise + vae.decode in chunks of `bs`.  With one seed this is
     edit_boxes' loop, chunk for chunk."""
-    N, K = len(locations), len(seeds)
     pre = prepost.preprocess_batch(instance_image, locations, origins, crop_scales, size=S)
-    dev = instance_image.device
+    return pre, _candidate_rows(unet, vae, scheduler, pre, instance_image.device, ctx, num_inference_steps, seeds, bs, generator, enc_noise,
+                                variance_noise, S)
+
+
+@torch.no_grad()
+def _candidate_rows(unet, vae, scheduler, pre, dev, ctx, num_inference_steps, seeds, bs, generator, enc_noise, variance_noise, S):
+    """_edit_candidates' chunk loop over the N rows of a preprocess dict, whatever pages they come from -> image_vae [N,K,3,S,S]"""
+    N, K = pre["image"].shape[0], len(seeds)
     sf = vae.config.scaling_factor
     f = 2 ** (len(vae.config.block_out_channels) - 1)
     init = torch.cat([torch.randn((1, vae.config.latent_channels, S // f, S // f), generator=torch.manual_seed(s), dtype=torch.float32)
@@ -312,8 +401,7 @@ def _edit_candidates(unet, vae, scheduler, instance_image, locations, origins, c
         for b in range(b0, b1):
             if (b + 1) * K <= hi:
                 mlat[b] = False              # all K rows done: the latents are released (and never encoded again)
-    image_vae = (outs[0] if len(outs) == 1 else torch.cat(outs, 0)).reshape(N, K, 3, S, S)
-    return pre, image_vae
+    return (outs[0] if len(outs) == 1 else torch.cat(outs, 0)).reshape(N, K, 3, S, S)
 
 
 @torch.no_grad()
@@ -337,20 +425,45 @@ def edit_boxes_verified(unet, vae, scheduler, ocr, processor, instance_image, lo
     N, K, seeds, h, w, ip = _check_verified_args(ocr, processor, instance_image, locations, encoder_hidden_states, labels, candidates, seeds, min_score,
                                                  batch_size, ocr_batch_size, origins, crop_scales, size)
     locations = list(locations)
-    if crop_scales is None:
-        crop_scales = [prepost.crop_scale_for(loc, h, w) for loc in locations]
-    crop_scales = list(crop_scales)
-    if origins is None:
-        origins = [prepost.crop_origin(loc, cs, w, rng if rng is not None else np.random) for loc, cs in zip(locations, crop_scales)]
+    crop_scales, origins = _plan_boxes(locations, h, w, origins, crop_scales, rng)
     pre, image_vae = _edit_candidates(unet, vae, scheduler, instance_image, locations, origins, crop_scales, encoder_hidden_states,
                                       num_inference_steps, seeds, int(batch_size), generator, enc_noise, variance_noise, int(size))
-    dev = instance_image.device
     pixel_values = prepost.readback_pixel_values(image_vae, instance_image, locations, origins, crop_scales, ip)
-    lab = labels.to(dev).repeat_interleave(K, 0)
-    seq, num = [], []
-    for lo in range(0, N * K, int(ocr_batch_size)):
-        r = ocr.score(pixel_values[lo:lo + int(ocr_batch_size)], labels=lab[lo:lo + int(ocr_batch_size)])
-        seq.append(r.sequence_logprobs); num.append(r.num_tokens)
-    scores = (torch.cat(seq) / torch.cat(num).clamp(min=1)).reshape(N, K)
+    scores = _score_candidates(ocr, pixel_values, labels, N, K, int(ocr_batch_size))
     out, choice = prepost.postprocess_select_batch(image_vae, scores, instance_image, locations, origins, crop_scales, threshold=min_score)
+    return VerifiedEdit(out, choice, scores, image_vae, pixel_values, pre) if return_intermediate else out
+
+
+def _score_candidates(ocr, pixel_values, labels, N, K, ocr_bs):
+    """scores fp32 [N,K] on the device: ocr.score over the N*K read-back rows in chunks of `ocr_bs`, mean log-probability per label token"""
+    lab = labels.to(pixel_values.device).repeat_interleave(K, 0)
+    seq, num = [], []
+    for lo in range(0, N * K, ocr_bs):
+        r = ocr.score(pixel_values[lo:lo + ocr_bs], labels=lab[lo:lo + ocr_bs])
+        seq.append(r.sequence_logprobs); num.append(r.num_tokens)
+    return (torch.cat(seq) / torch.cat(num).clamp(min=1)).reshape(N, K)
+
+
+@torch.no_grad()
+def edit_pages_verified(unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps, *,
+                        candidates=4, seeds=None, min_score=None, batch_size=4, ocr_batch_size=32, origins=None, crop_scales=None, rng=None,
+                        generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False):
+    """edit_boxes_verified for boxes on several pages: images / locations / origins / crop_scales as for edit_pages, everything per box
+    (encoder_hidden_states [N,L,D], labels [N,T], enc_noise [N,4,h,w]) page-major.  The N*K rows go through edit_boxes_verified's chunk
+    loop, prepost.readback_pixel_values_pages, ocr.score and prepost.postprocess_select_pages - chunks cross page boundaries, no score is
+    read on the host.  Returns the list of P pages, or a VerifiedEdit whose `image` is that list with return_intermediate=True.
+    candidates=1 with min_score=None returns edit_pages' pages, bit for bit."""
+    locations = [list(l) for l in locations]
+    N = sum(len(l) for l in locations)
+    K, seeds = _check_verified_counts(N, candidates, seeds, min_score, batch_size, ocr_batch_size)
+    images, locations, origins, crop_scales, sizes, N = _page_lists(images, locations, origins, crop_scales, rng)
+    _check_verified_labels(ocr, N, encoder_hidden_states, labels)
+    prepost.check_readback_boxes_pages([loc for l in locations for loc in l], [len(l) for l in locations], sizes)
+    ip = _check_verified_processor(ocr, processor, size)
+    pre = prepost.preprocess_pages(images, locations, origins, crop_scales, size=int(size))
+    image_vae = _candidate_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, seeds, int(batch_size),
+                                generator, enc_noise, variance_noise, int(size))
+    pixel_values = prepost.readback_pixel_values_pages(image_vae, images, locations, origins, crop_scales, ip)
+    scores = _score_candidates(ocr, pixel_values, labels, N, K, int(ocr_batch_size))
+    out, choice = prepost.postprocess_select_pages(image_vae, scores, images, locations, origins, crop_scales, threshold=min_score)
     return VerifiedEdit(out, choice, scores, image_vae, pixel_values, pre) if return_intermediate else out

@@ -313,3 +313,235 @@ def postprocess_select_batch(image_vae, scores, instance_image, locations, origi
                                                             _cabi.ptr(choice), h, w, host, _cabi.ptr(table), B, K, _cabi.current_stream()),
                     "postprocess_paste_select")
     return (out, choice, union) if return_mask else (out, choice)
+
+
+# ------------------------------------------------------------------------------------------------ boxes on several pages per launch
+def plan_pages(locations, sizes, rng=np.random):
+    """plan_edits page after page on ONE rng stream: locations is a list of P lists of boxes, sizes the pages' (h, w).  Returns P lists
+    of (x_s, y_s, crop_scale); a seeded rng draws exactly what one text_editing() call per box, page after page, would draw."""
+    locations, sizes = list(locations), list(sizes)
+    if len(locations) != len(sizes):
+        raise ValueError(f"{len(locations)} lists of boxes, {len(sizes)} page sizes: the lengths must agree")
+    return [plan_edits(locs, int(h), int(w), rng) for locs, (h, w) in zip(locations, sizes)]
+
+
+def _check_pages(images, locations, origins, crop_scales):
+    """the list half of the *_pages functions' arguments, checked before anything touches a tensor.  Returns (images, the three lists
+    flattened page-major, the pages' box counts)."""
+    images, locations, origins, crop_scales = list(images), list(locations), list(origins), list(crop_scales)
+    P = len(images)
+    if P == 0:
+        raise ValueError("no pages: the paged pre/post-processing needs at least one")
+    if P > _cabi.EDIT_MAX_ITEMS:
+        raise ValueError(f"{P} pages in one launch, at most {_cabi.EDIT_MAX_ITEMS}")
+    if len(locations) != P or len(origins) != P or len(crop_scales) != P:
+        raise ValueError(f"{P} pages, {len(locations)} lists of boxes, {len(origins)} of origins, {len(crop_scales)} of crop scales: the lengths must agree")
+    flat, counts = ([], [], []), []
+    for p in range(P):
+        locs, orgs, crops = list(locations[p]), list(origins[p]), list(crop_scales[p])
+        if not locs:
+            raise ValueError(f"page {p}: no boxes; every page needs at least one")
+        if len(orgs) != len(locs) or len(crops) != len(locs):
+            raise ValueError(f"page {p}: {len(locs)} boxes, {len(orgs)} origins, {len(crops)} crop scales: the lengths must agree")
+        flat[0].extend(locs); flat[1].extend(orgs); flat[2].extend(crops)
+        counts.append(len(locs))
+    if len(flat[0]) > _cabi.EDIT_MAX_ITEMS:
+        raise ValueError(f"{len(flat[0])} boxes in one launch, at most {_cabi.EDIT_MAX_ITEMS}")
+    return (images,) + flat + (counts,)
+
+
+def _check_page_images(images):
+    """P contiguous uint8 CUDA [h][w][3] tensors on one device -> that device"""
+    for p, img in enumerate(images):
+        _u8(img, f"images[{p}]")
+        if img.dim() != 3 or img.shape[2] != 3:
+            raise ValueError(f"images[{p}] must be HWC with 3 channels")
+        if img.device != images[0].device:
+            raise ValueError(f"images[{p}] lives on {img.device}, images[0] on {images[0].device}: pages on several devices are not supported")
+    return images[0].device
+
+
+def _check_page_outputs(out, images):
+    """the optional `out` list of the paged pastes: P contiguous uint8 tensors of the pages' shapes on their device, sharing no memory with
+    the pages or with one another (one launch reads every page and writes every output)"""
+    out = list(out)
+    if len(out) != len(images):
+        raise ValueError(f"{len(images)} pages, {len(out)} output tensors: the lengths must agree")
+    spans = [(t.data_ptr(), t.data_ptr() + t.numel(), f"images[{p}]") for p, t in enumerate(images)]
+    for p, (o, img) in enumerate(zip(out, images)):
+        if not (isinstance(o, torch.Tensor) and o.is_cuda and o.dtype == torch.uint8 and o.is_contiguous() and o.device == img.device
+                and o.shape == img.shape):
+            raise ValueError(f"out[{p}] must be a contiguous uint8 tensor {tuple(img.shape)} on {img.device}")
+        lo, hi = o.data_ptr(), o.data_ptr() + o.numel()
+        for a, z, name in spans:
+            if lo < z and a < hi:
+                raise ValueError(f"out[{p}] shares memory with {name}")
+        spans.append((lo, hi, f"out[{p}]"))
+    return out
+
+
+def _upload_pages(images, locations, origins, crop_scales, counts, S, dev, out=None, union=None, extra=()):
+    """the tables of one paged launch - dmx_edit_item | dmx_edit_page | `extra` (numpy arrays) - filled and validated in ONE pinned staging
+    buffer, then ONE asynchronous copy on the current stream.  Returns (host items, host pages, the pinned storage, the device buffer,
+    the byte offsets of the pages and of every extra array in it): the entries read the host tables, the kernels the device copies.
+    The tests build real tables through this function (tests/test_prepost_pages_gpu.py): arguments and the returned tuple stay as they are."""
+    B, P = len(locations), len(images)
+    n_items, n_pages = B * ctypes.sizeof(_cabi.EditItem), P * ctypes.sizeof(_cabi.EditPage)
+    offs, total = [], n_items + n_pages
+    for a in extra:
+        offs.append(total); total += a.nbytes
+    stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+    st = stage.numpy()
+    host = (_cabi.EditItem * B).from_buffer(st[:n_items])
+    for it, loc, (x_s, y_s), crop_scale in zip(host, locations, origins, crop_scales):
+        it.x1, it.y1, it.x2, it.y2 = (int(v) for v in loc[:4])
+        it.x_s, it.y_s, it.crop_scale = int(x_s), int(y_s), int(crop_scale)
+    pages = (_cabi.EditPage * P).from_buffer(st[n_items:n_items + n_pages])
+    lo = 0
+    for p, (pg, img, n) in enumerate(zip(pages, images, counts)):
+        pg.original = img.data_ptr()
+        pg.out = out[p].data_ptr() if out is not None else 0
+        pg.union_mask = union[p].data_ptr() if union is not None else 0
+        pg.H, pg.W, pg.item_lo, pg.item_hi = int(img.shape[0]), int(img.shape[1]), lo, lo + n
+        lo += n
+    _cabi.check(_cabi.lib().dmx_edit_pages_prepare(pages, P, host, B, S), "edit_pages_prepare")
+    for a, o in zip(extra, offs):
+        st[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    with torch.cuda.device(dev):
+        dbuf = torch.empty(total, dtype=torch.uint8, device=dev)
+        dbuf.copy_(stage, non_blocking=True)                          # the one H2D copy
+    return host, pages, stage, dbuf, [n_items] + offs
+
+
+def preprocess_pages(images, locations, origins, crop_scales, size=512):
+    """preprocess_batch for boxes on SEVERAL pages, in one launch.  images: P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device;
+    locations / origins / crop_scales: P lists, one entry per box of that page (plan_pages gives the last two).  Returns the
+    preprocess_batch dict with N rows, N the total box count, page-major (page 0's boxes in order, then page 1's): row b equals
+    preprocess() of box b on its own page."""
+    images, locations, origins, crop_scales, counts = _check_pages(images, locations, origins, crop_scales)
+    dev, B, S = _check_page_images(images), len(locations), int(size)
+    host, pages, stage, dbuf, offs = _upload_pages(images, locations, origins, crop_scales, counts, S, dev)
+    base = dbuf.data_ptr()
+    with torch.cuda.device(dev):
+        image = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+        masked = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+        mask = torch.empty(B, 1, S, S, dtype=torch.uint8, device=dev)
+        mask_lat = torch.empty(B, 1, S // 8, S // 8, dtype=torch.float32, device=dev)
+        _cabi.check(_cabi.lib().dmx_preprocess_crop_pages(pages, base + offs[0], len(images), host, base, B, S, _cabi.ptr(image), _cabi.ptr(masked),
+                                                         _cabi.ptr(mask), _cabi.ptr(mask_lat), _cabi.current_stream()), "preprocess_crop_pages")
+    return dict(image=image, masked_image=masked, mask=mask, mask_latent=mask_lat)
+
+
+def _page_outputs(images, out, return_mask, dev):
+    with torch.cuda.device(dev):
+        out = [torch.empty_like(img) for img in images] if out is None else out
+        union = [torch.empty(img.shape[0], img.shape[1], dtype=torch.uint8, device=dev) for img in images] if return_mask else None
+    return out, union
+
+
+def postprocess_pages(image_vae, images, locations, origins, crop_scales, return_mask=False, out=None):
+    """postprocess_batch for boxes on several pages, in one launch.  image_vae: fp32 CUDA [N,3,S,S] decoder outputs, page-major; the
+    other arguments as for preprocess_pages.  Returns the list of P uint8 [h_p][w_p][3] pages - page p is postprocess_batch of its own
+    boxes (a later box wins where boxes overlap) -, with return_mask=True also the list of P union masks uint8 [h_p][w_p].  out
+    (optional): a list of P preallocated contiguous uint8 tensors of the pages' shapes, distinct from `images`, to write into."""
+    images, locations, origins, crop_scales, counts = _check_pages(images, locations, origins, crop_scales)
+    dev, B = _check_page_images(images), len(locations)
+    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
+        raise TypeError("image_vae: expected a CUDA tensor")
+    if image_vae.dim() != 4 or tuple(image_vae.shape[:2]) != (B, 3) or image_vae.shape[2] != image_vae.shape[3]:
+        raise ValueError(f"image_vae must be [{B},3,S,S]: one square 3-channel image per box")
+    if out is not None:
+        out = _check_page_outputs(out, images)
+    v = image_vae.to(torch.float32).contiguous()
+    S = int(v.shape[-1])
+    out, union = _page_outputs(images, out, return_mask, dev)
+    host, pages, stage, dbuf, offs = _upload_pages(images, locations, origins, crop_scales, counts, S, dev, out, union)
+    base = dbuf.data_ptr()
+    with torch.cuda.device(dev):
+        _cabi.check(_cabi.lib().dmx_postprocess_paste_pages(_cabi.ptr(v), S, pages, base + offs[0], len(images), host, base, B,
+                                                           _cabi.current_stream()), "postprocess_paste_pages")
+    return (out, union) if return_mask else out
+
+
+def readback_pixel_values_pages(image_vae, images, locations, origins, crop_scales, processor, return_resized=False, out=None, out_resized=None):
+    """readback_pixel_values for boxes on several pages, in one launch: image_vae fp32 CUDA [N,K,3,S,S], page-major -> pixel_values fp32
+    [N*K,3,S_h,S_w]; row (b, k) is the read-back of candidate k of box b on its own page.  The items, the pages and the processor's
+    tables travel in one pinned staging buffer, one H2D copy.  return_resized / out / out_resized as for readback_pixel_values."""
+    images, locations, origins, crop_scales, counts = _check_pages(images, locations, origins, crop_scales)
+    ip = _image_processor(processor)
+    if not ip.do_resize:
+        raise ValueError("readback_pixel_values_pages: the processor must resize (do_resize=True): boxes have no common size")
+    dev, B = _check_page_images(images), len(locations)
+    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
+        raise TypeError("image_vae: expected a CUDA tensor")
+    if image_vae.dim() != 5 or image_vae.shape[0] != B or image_vae.shape[2] != 3 or image_vae.shape[3] != image_vae.shape[4]:
+        raise ValueError(f"image_vae must be [{B},K,3,S,S]: K square 3-channel candidates per box")
+    K = _check_candidates(image_vae.shape[1])
+    check_readback_boxes_pages(locations, counts, [img.shape[:2] for img in images])
+    S_h, S_w = ip.size["height"], ip.size["width"]
+    for name, t, dt in (("out", out, torch.float32), ("out_resized", out_resized, torch.uint8)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dt and t.is_contiguous()
+                                  and tuple(t.shape) == (B * K, 3, S_h, S_w)):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor [{B * K},3,{S_h},{S_w}] on {dev}")
+    lib = _cabi.lib()
+    passes, tables, max_taps = _readback_tables(locations, ip, int(lib.dmx_glyph_max_taps()))
+    v = image_vae.to(torch.float32).contiguous()
+    S = int(v.shape[-1])
+    host, pages, stage, dbuf, offs = _upload_pages(images, locations, origins, crop_scales, counts, S, dev, extra=(passes, ip._norm, tables))
+    off_pages, off_pass, off_norm, off_tab = offs
+    host_passes = (_cabi.ReadbackPass * B).from_buffer(stage.numpy()[off_pass:off_norm])
+    base = dbuf.data_ptr()
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(B * K, 3, S_h, S_w, dtype=torch.float32, device=dev)
+        res = out_resized
+        if res is None and return_resized:
+            res = torch.empty(B * K, 3, S_h, S_w, dtype=torch.uint8, device=dev)
+        _cabi.check(lib.dmx_readback_pixel_values_pages(_cabi.ptr(v), S, pages, base + off_pages, len(images), host, base, B, K, base + off_tab,
+                                                        int(tables.size), base + off_norm, host_passes, base + off_pass, max_taps, S_h, S_w,
+                                                        _cabi.ptr(out), _cabi.ptr(res), _cabi.current_stream()), "readback_pixel_values_pages", lib)
+    return (out, res) if (return_resized or out_resized is not None) else out
+
+
+def check_readback_boxes_pages(locations, counts, sizes):
+    """check_readback_boxes page by page: locations flattened page-major, counts the pages' box counts, sizes their (h, w)"""
+    lo = 0
+    for p, (n, (h, w)) in enumerate(zip(counts, sizes)):
+        try:
+            check_readback_boxes(locations[lo:lo + n], int(h), int(w))
+        except ValueError as e:
+            raise ValueError(f"page {p}: {e}") from None
+        lo += n
+
+
+def postprocess_select_pages(image_vae, scores, images, locations, origins, crop_scales, threshold=None, return_mask=False, out=None):
+    """postprocess_select_batch for boxes on several pages, in one launch: image_vae fp32 CUDA [N,K,3,S,S], scores fp32 CUDA [N,K], both
+    page-major.  Returns (pages, choice): the list of P uint8 pages, page p being what postprocess_select_batch gives for its own boxes,
+    and choice int32 [N] on the device, by the same rule; with return_mask=True also the list of P union masks.  out as for
+    postprocess_pages."""
+    images, locations, origins, crop_scales, counts = _check_pages(images, locations, origins, crop_scales)
+    dev, B = _check_page_images(images), len(locations)
+    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda and isinstance(scores, torch.Tensor) and scores.is_cuda):
+        raise TypeError("image_vae, scores: expected CUDA tensors")
+    if image_vae.dim() != 5 or image_vae.shape[0] != B or image_vae.shape[2] != 3 or image_vae.shape[3] != image_vae.shape[4]:
+        raise ValueError(f"image_vae must be [{B},K,3,S,S]: K square 3-channel candidates per box")
+    K = _check_candidates(image_vae.shape[1])
+    if tuple(scores.shape) != (B, K):
+        raise ValueError(f"scores must be [{B},{K}], got {tuple(scores.shape)}")
+    thr = float("-inf") if threshold is None else float(threshold)
+    if thr != thr:
+        raise ValueError("threshold is NaN")
+    if out is not None:
+        out = _check_page_outputs(out, images)
+    v = image_vae.to(torch.float32).contiguous()
+    sc = scores.to(torch.float32).contiguous()
+    S = int(v.shape[-1])
+    out, union = _page_outputs(images, out, return_mask, dev)
+    host, pages, stage, dbuf, offs = _upload_pages(images, locations, origins, crop_scales, counts, S, dev, out, union)
+    base = dbuf.data_ptr()
+    with torch.cuda.device(dev):
+        choice = torch.empty(B, dtype=torch.int32, device=dev)
+        _cabi.check(_cabi.lib().dmx_postprocess_paste_select_pages(_cabi.ptr(v), S, _cabi.ptr(sc), thr, _cabi.ptr(choice), pages, base + offs[0],
+                                                                  len(images), host, base, B, K, _cabi.current_stream()),
+                    "postprocess_paste_select_pages")
+    return (out, choice, union) if return_mask else (out, choice)

@@ -673,6 +673,45 @@ int dmx_postprocess_paste_select(const float* image_vae, int S, const float* sco
                                  unsigned char* out_hwc, unsigned char* union_mask, int* choice, int H, int W,
                                  const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, dmx_stream_t stream);
 
+/* The four entries above for boxes on SEVERAL pages (images of different sizes) in one launch each: B items on P pages,
+ * 1 <= P <= DMX_EDIT_MAX_ITEMS, 1 <= B <= DMX_EDIT_MAX_ITEMS in all, every page with at least one item.  A table of dmx_edit_page
+ * travels like the item table, as a host copy the entry checks and a device copy the kernel reads.  The caller fills the addresses,
+ * H, W and the item range of every page - the ranges tile [0, B) in page order - and box, origin and crop_scale of every item, lets
+ * edit_pages_prepare validate both tables and fill the derived fields (every item with the arithmetic of edit_items_prepare at ITS
+ * page's size, the item's page index in `reserved`, every page's first block in the paste grid), and copies both to the device in
+ * stream order.  A bad page is reported by page index, a bad item by its index in the whole table; nothing is launched then.
+ *   preprocess_crop_pages / readback_pixel_values_pages: row b (rows (b, k)) is what the one-page entry writes for item b on its own
+ *           page.  They read `original` only.
+ *   postprocess_paste_pages / postprocess_paste_select_pages: page p's `out` (and `union_mask`, 0 = none) is what the one-page entry
+ *           writes for the items of page p alone; `out` must not be `original`.  choice is [B], scores [B][K], over all items.  One
+ *           launch covers the pixels of all pages, so H <= 65535 holds per page, not for the sum; W <= DMX_EDIT_PAGE_MAX_W, and the
+ *           pages together may take up to 2^31 - 1 blocks of 256 pixels.
+ * The kernels clamp what they read from the device tables (page index, item range, origins, extents, boxes) to the page; the
+ * pages' addresses and sizes are trusted. */
+#define DMX_EDIT_PAGE_MAX_W 0x7fffff00            /* 2^31 - 256: ceil(W / 256) is computed in int */
+typedef struct dmx_edit_page {
+  unsigned long long original;      /* device address of the page, uint8 [H][W][3] */
+  unsigned long long out;           /* device address of the pasted page (the paste entries) */
+  unsigned long long union_mask;    /* device address of uint8 [H][W], or 0 (the paste entries) */
+  int H, W;
+  int item_lo, item_hi;             /* the page's items: [item_lo, item_hi) of the item table */
+  int block_lo, blocks;             /* derived: the page's blocks in the paste grid, H * ceil(W / 256) of them */
+} dmx_edit_page;
+int dmx_edit_pages_prepare(dmx_edit_page* pages, int P, dmx_edit_item* items, int B, int S);
+int dmx_preprocess_crop_pages(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_item* items_host,
+                              const dmx_edit_item* items_device, int B, int S, float* out_image, float* out_masked_image,
+                              unsigned char* out_mask, float* out_mask_latent, dmx_stream_t stream);
+int dmx_postprocess_paste_pages(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, dmx_stream_t stream);
+int dmx_readback_pixel_values_pages(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                    const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, const int* tables,
+                                    long long table_ints, const float* norm, const dmx_readback_pass* passes_host,
+                                    const dmx_readback_pass* passes_device, int max_taps, int S_h, int S_w, float* out_pixel_values,
+                                    unsigned char* out_resized, dmx_stream_t stream);
+int dmx_postprocess_paste_select_pages(const float* image_vae, int S, const float* scores, float threshold, int* choice,
+                                       const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                       const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, dmx_stream_t stream);
+
 /* Fused AdamW + global-norm clipping over packed fp32 arenas (torch.optim.AdamW + clip_grad_norm_,
  * train_diffute_v1.py:721-727,927-930).  masters / exp_avg / exp_avg_sq / grads: dmx_unet_grad_bytes each.  The step also
  * rewrites the weights arena (bf16 weights, fp32 vectors) in place; afterwards call dmx_unet_refresh_derived (folded
