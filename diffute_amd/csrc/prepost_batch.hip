@@ -46,9 +46,8 @@ __global__ __launch_bounds__(256) void dmx_preprocess_batch_kernel(const PreBatc
 // ---- B boxes on P pages per launch (pipeline.edit_pages): a device table of dmx_edit_page says where each page lives and which
 // contiguous range of the item table belongs to it.  Every kernel below hands the functions above a one-page VIEW of its arguments -
 // the page's pointers and size, its slice of the item table - so a row / a page is bit for bit what the one-page kernel gives.
-// Whatever comes from the device tables is clamped: a stale table reads wrong pixels, never outside a page (the pages' own addresses
-// and sizes are trusted, as the one-page kernels trust their arguments).
-__device__ __forceinline__ int page_of(const dmx_edit_item& it, int P) { return min(max(it.reserved, 0), P - 1); }
+// Whatever comes from the device tables is clamped (page_of, item_geom: prepost_resize.h): a stale table reads wrong pixels, never
+// outside a page (the pages' own addresses and sizes are trusted, as the one-page kernels trust their arguments).
 
 struct PrePagesArgs {
   const dmx_edit_page* pages; int P;
@@ -265,13 +264,19 @@ extern "C" int dmx_postprocess_paste_batch(const float* image_vae, int S, const 
   return dmx_check_launch("dmx_postprocess_batch_kernel");
 }
 
+// what the two select entries ask of their scalars
+static int check_select_scalars(const char* what, int K, float threshold) {
+  DMX_REQUIRE(K >= 1 && K <= DMX_SELECT_MAX_CANDIDATES, "%s: %d candidates per box, expected 1 .. %d", what, K, DMX_SELECT_MAX_CANDIDATES);
+  DMX_REQUIRE(!(threshold != threshold), "%s: the threshold is NaN (pass -inf for none)", what);
+  return DMX_OK;
+}
+
 extern "C" int dmx_postprocess_paste_select(const float* image_vae, int S, const float* scores, float threshold, const unsigned char* original_hwc,
                                             unsigned char* out_hwc, unsigned char* union_mask, int* choice, int H, int W,
                                             const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, dmx_stream_t stream) {
   DMX_REQUIRE(image_vae && scores && original_hwc && out_hwc && choice && items_device, "postprocess_paste_select: null argument");
-  DMX_REQUIRE(K >= 1 && K <= DMX_SELECT_MAX_CANDIDATES, "postprocess_paste_select: %d candidates per box, expected 1 .. %d", K, DMX_SELECT_MAX_CANDIDATES);
-  DMX_REQUIRE(!(threshold != threshold), "postprocess_paste_select: the threshold is NaN (pass -inf for none)");
-  const int rc = dmx_check_edit_items("postprocess_paste_select", items_host, B, H, W, S, true);
+  int rc = check_select_scalars("postprocess_paste_select", K, threshold);
+  if (rc == DMX_OK) rc = dmx_check_edit_items("postprocess_paste_select", items_host, B, H, W, S, true);
   if (rc != DMX_OK) return rc;
   PostBatchArgs p{image_vae, S, original_hwc, out_hwc, union_mask, H, W, items_device, B};
   hipLaunchKernelGGL(dmx_postprocess_select_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, p, scores, K, threshold, choice);
@@ -367,10 +372,8 @@ extern "C" int dmx_postprocess_paste_select_pages(const float* image_vae, int S,
                                                   dmx_stream_t stream) {
   DMX_REQUIRE(image_vae && scores && choice && pages_device && items_device, "postprocess_paste_select_pages: null argument");
   DMX_REQUIRE(S > 0 && S <= 65535, "postprocess_paste_select_pages: bad S = %d", S);
-  DMX_REQUIRE(K >= 1 && K <= DMX_SELECT_MAX_CANDIDATES, "postprocess_paste_select_pages: %d candidates per box, expected 1 .. %d", K,
-              DMX_SELECT_MAX_CANDIDATES);
-  DMX_REQUIRE(!(threshold != threshold), "postprocess_paste_select_pages: the threshold is NaN (pass -inf for none)");
-  int rc = dmx_check_edit_pages("postprocess_paste_select_pages", pages_host, P, items_host, B, S, true);
+  int rc = check_select_scalars("postprocess_paste_select_pages", K, threshold);
+  if (rc == DMX_OK) rc = dmx_check_edit_pages("postprocess_paste_select_pages", pages_host, P, items_host, B, S, true);
   if (rc == DMX_OK) rc = check_page_addresses("postprocess_paste_select_pages", pages_host, P, true);
   if (rc != DMX_OK) return rc;
   PostPagesArgs p{image_vae, S, pages_device, P, items_device, B};

@@ -150,5 +150,9 @@ __device__ __forceinline__ Geom item_geom(const dmx_edit_item& it, int H, int W,
   else { g.sx = it.post_sx; g.sy = it.post_sy; g.area2 = (it.post_area2 && S == 2 * g.cw && S == 2 * g.ch) ? 1 : 0; }
   return g;
 }
+
+// The page of an item of a paged launch (include/diffute_hip.h dmx_edit_page): dmx_edit_pages_prepare writes its index into the item,
+// and like everything that comes from the device table it is clamped.
+__device__ __forceinline__ int page_of(const dmx_edit_item& it, int P) { return min(max(it.reserved, 0), P - 1); }
 #endif  // __HIPCC__
 }  // namespace dmx_resize

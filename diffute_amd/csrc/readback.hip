@@ -62,7 +62,7 @@ __global__ __launch_bounds__(128) void dmx_readback_pixel_values_kernel(const Re
 __global__ __launch_bounds__(128) void dmx_readback_pages_kernel(ReadbackArgs p, const dmx_edit_page* pages, int P) {
   const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y, r = blockIdx.z;
   if (ox >= p.S_w) return;
-  const dmx_edit_page pg = pages[min(max(p.items[r / p.K].reserved, 0), P - 1)];
+  const dmx_edit_page pg = pages[page_of(p.items[r / p.K], P)];
   p.ori = (const unsigned char*)pg.original; p.H = pg.H; p.W = pg.W;
   readback_row(p, r, ox, oy);
 }
@@ -92,6 +92,17 @@ int check_readback_items(const char* what, const dmx_edit_item* items_host, cons
   }
   return DMX_OK;
 }
+
+// the scalar arguments the one-page and the paged entry share
+int check_readback_scalars(const char* what, int K, int max_taps, long long table_ints, int S_h, int S_w) {
+  DMX_REQUIRE(K >= 1 && K <= DMX_SELECT_MAX_CANDIDATES, "%s: %d candidates per box, expected 1 .. %d", what, K, DMX_SELECT_MAX_CANDIDATES);
+  DMX_REQUIRE(S_h > 0 && S_h <= 65535 && S_w > 0 && S_w <= 65535, "%s: bad output size %dx%d", what, S_w, S_h);
+  DMX_REQUIRE(max_taps >= 0 && max_taps <= DMX_GLYPH_MAX_TAPS,
+              "%s: %d taps per output pixel exceed the cap of %d (downscale ratio at most 31 for bilinear, 15 for bicubic)", what, max_taps,
+              DMX_GLYPH_MAX_TAPS);
+  DMX_REQUIRE(table_ints >= 0 && table_ints < (1ll << 31), "%s: bad table size %lld", what, table_ints);
+  return DMX_OK;
+}
 }  // namespace
 
 extern "C" int dmx_readback_pixel_values(const float* image_vae, int S, const unsigned char* original_hwc, int H, int W,
@@ -99,18 +110,12 @@ extern "C" int dmx_readback_pixel_values(const float* image_vae, int S, const un
                                          long long table_ints, const float* norm, const dmx_readback_pass* passes_host,
                                          const dmx_readback_pass* passes_device, int max_taps, int S_h, int S_w, float* out_pixel_values,
                                          unsigned char* out_resized, dmx_stream_t stream) {
-  DMX_REQUIRE(image_vae && original_hwc && items_device && tables && norm && passes_host && passes_device && out_pixel_values,
-              "readback_pixel_values: null argument");
-  DMX_REQUIRE(K >= 1 && K <= DMX_SELECT_MAX_CANDIDATES, "readback_pixel_values: %d candidates per box, expected 1 .. %d", K, DMX_SELECT_MAX_CANDIDATES);
-  DMX_REQUIRE(S_h > 0 && S_h <= 65535 && S_w > 0 && S_w <= 65535, "readback_pixel_values: bad output size %dx%d", S_w, S_h);
-  DMX_REQUIRE(max_taps >= 0 && max_taps <= DMX_GLYPH_MAX_TAPS,
-              "readback_pixel_values: %d taps per output pixel exceed the cap of %d (downscale ratio at most 31 for bilinear, 15 for bicubic)",
-              max_taps, DMX_GLYPH_MAX_TAPS);
-  DMX_REQUIRE(table_ints >= 0 && table_ints < (1ll << 31), "readback_pixel_values: bad table size %lld", table_ints);
-  const int rc = dmx_check_edit_items("readback_pixel_values", items_host, B, H, W, S, true);
+  const char* what = "readback_pixel_values";
+  DMX_REQUIRE(image_vae && original_hwc && items_device && tables && norm && passes_host && passes_device && out_pixel_values, "%s: null argument", what);
+  int rc = check_readback_scalars(what, K, max_taps, table_ints, S_h, S_w);
+  if (rc == DMX_OK) rc = dmx_check_edit_items(what, items_host, B, H, W, S, true);
+  if (rc == DMX_OK) rc = check_readback_items(what, items_host, passes_host, 0, B, H, W, max_taps, table_ints, S_h, S_w);
   if (rc != DMX_OK) return rc;
-  const int rb = check_readback_items("readback_pixel_values", items_host, passes_host, 0, B, H, W, max_taps, table_ints, S_h, S_w);
-  if (rb != DMX_OK) return rb;
   ReadbackArgs p{image_vae, S, original_hwc, H, W, items_device, passes_device, B, K, tables, norm, S_h, S_w, out_pixel_values, out_resized};
   hipLaunchKernelGGL(dmx_readback_pixel_values_kernel, dim3(cdiv(S_w, 128), S_h, B * K), dim3(128), 0, (hipStream_t)stream, p);
   return dmx_check_launch("dmx_readback_pixel_values_kernel");
@@ -124,13 +129,8 @@ extern "C" int dmx_readback_pixel_values_pages(const float* image_vae, int S, co
   const char* what = "readback_pixel_values_pages";
   DMX_REQUIRE(image_vae && pages_device && items_device && tables && norm && passes_host && passes_device && out_pixel_values, "%s: null argument", what);
   DMX_REQUIRE(S > 0 && S <= 65535, "%s: bad S = %d", what, S);
-  DMX_REQUIRE(K >= 1 && K <= DMX_SELECT_MAX_CANDIDATES, "%s: %d candidates per box, expected 1 .. %d", what, K, DMX_SELECT_MAX_CANDIDATES);
-  DMX_REQUIRE(S_h > 0 && S_h <= 65535 && S_w > 0 && S_w <= 65535, "%s: bad output size %dx%d", what, S_w, S_h);
-  DMX_REQUIRE(max_taps >= 0 && max_taps <= DMX_GLYPH_MAX_TAPS,
-              "%s: %d taps per output pixel exceed the cap of %d (downscale ratio at most 31 for bilinear, 15 for bicubic)", what, max_taps,
-              DMX_GLYPH_MAX_TAPS);
-  DMX_REQUIRE(table_ints >= 0 && table_ints < (1ll << 31), "%s: bad table size %lld", what, table_ints);
-  int rc = dmx_check_edit_pages(what, pages_host, P, items_host, B, S, true);
+  int rc = check_readback_scalars(what, K, max_taps, table_ints, S_h, S_w);
+  if (rc == DMX_OK) rc = dmx_check_edit_pages(what, pages_host, P, items_host, B, S, true);
   if (rc != DMX_OK) return rc;
   for (int q = 0; q < P; ++q) {
     const dmx_edit_page& pg = pages_host[q];

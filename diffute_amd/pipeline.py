@@ -189,18 +189,44 @@ def edit_boxes(unet, vae, scheduler, instance_image, locations, encoder_hidden_s
 
     Difference from N sequential text_editing() calls: every crop is taken from the ORIGINAL image, so box k's context does not contain
     the edits of boxes < k.  The pastes are identical (a later box wins where boxes overlap)."""
-    locations = list(locations)
-    N = len(locations)
+    return _edit(False, unet, vae, scheduler, [instance_image], [locations], encoder_hidden_states, num_inference_steps, _one(origins),
+                 _one(crop_scales), rng, batch_size, generator, enc_noise, variance_noise, return_intermediate, size)
+
+
+@torch.no_grad()
+def edit_pages(unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, *, origins=None, crop_scales=None,
+               rng=None, batch_size=4, generator=None, enc_noise=None, variance_noise=None, return_intermediate=False, size=512):
+    """edit_boxes for boxes on SEVERAL pages as one batch - what a service holding requests for different images, or a training batch
+    of one box per image, needs.  images: a list of P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device; locations: P lists of
+    boxes (x1, y1, x2, y2); origins / crop_scales: None or P lists, as for edit_boxes per page (what is not given is planned page after
+    page, random origins drawn from `rng` in that order: prepost.plan_pages).  Rows are page-major - page 0's boxes in order, then
+    page 1's -, N in all: encoder_hidden_states [N,L,D], enc_noise [N,4,h,w], variance_noise [steps,N,4,h,w].
+
+    One preprocess_pages launch, the N rows through edit_latents in chunks of `batch_size` (chunks cross page boundaries; every box
+    starts from the seed-0 single-sample draw), one postprocess_pages launch.  Returns the list of P edited pages, with
+    return_intermediate=True also image_vae [N,3,S,S] and the preprocess dict.  With one page this is [edit_boxes(...)], bit for bit."""
+    return _edit(True, unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, origins, crop_scales, rng,
+                 batch_size, generator, enc_noise, variance_noise, return_intermediate, size)
+
+
+def _edit(paged, unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, origins, crop_scales, rng, batch_size,
+          generator, enc_noise, variance_noise, return_intermediate, size):
+    """edit_boxes (paged=False: one page, its lists wrapped into one-element lists) and edit_pages"""
     if int(batch_size) < 1:
         raise ValueError("batch_size must be at least 1")
-    h, w = _page_size(instance_image, "instance_image")
-    crop_scales, origins = _plan_boxes(locations, h, w, origins, crop_scales, rng)
+    images, locations, origins, crop_scales, sizes, N = _page_lists(paged, images, locations, origins, crop_scales)
     _check_contexts(N, encoder_hidden_states)
-    pre = prepost.preprocess_batch(instance_image, locations, origins, crop_scales, size=size)
-    image_vae = _edit_rows(unet, vae, scheduler, pre, instance_image.device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
+    where = _plan_pages(paged, images, locations, sizes, origins, crop_scales, rng)
+    pre = (prepost.preprocess_pages if paged else prepost.preprocess_batch)(*where, size=size)
+    image_vae = _edit_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
                            enc_noise, variance_noise, int(size))
-    out = prepost.postprocess_batch(image_vae, instance_image, locations, origins, crop_scales)
+    out = (prepost.postprocess_pages if paged else prepost.postprocess_batch)(image_vae, *where)
     return (out, image_vae, pre) if return_intermediate else out
+
+
+def _one(lst):
+    """a one-page function's optional list as the paged form's list of lists"""
+    return None if lst is None else [lst]
 
 
 def _page_size(image, name):
@@ -229,27 +255,34 @@ def _check_contexts(N, encoder_hidden_states):
         raise ValueError(f"{N} boxes but {encoder_hidden_states.shape[0]} glyph contexts")
 
 
-def _page_lists(images, locations, origins, crop_scales, rng):
-    """the list arguments of edit_pages / edit_pages_verified: P pages, P lists of boxes, origins / crop_scales None or P lists; what is
-    not given is planned page after page on one rng stream (prepost.plan_pages' draws).  Returns (images, locations, origins,
-    crop_scales, sizes, N) with P lists each."""
+def _page_lists(paged, images, locations, origins, crop_scales):
+    """the list arguments of the four edit functions, checked: P pages, P lists of boxes, origins / crop_scales None or P lists whose
+    entries are None or as long as the page's boxes.  Nothing is planned here, so nothing is drawn.  Returns (images, locations, origins,
+    crop_scales, sizes, N) with P lists each.  A one-page call (paged=False) is named by its own argument, not as page 0."""
     images, locations = list(images), [list(l) for l in locations]
-    origins = None if origins is None else [None if l is None else list(l) for l in origins]              # materialised once: a generator
-    crop_scales = None if crop_scales is None else [None if l is None else list(l) for l in crop_scales]  # would not survive the length checks
     P = len(images)
     if len(locations) != P:
         raise ValueError(f"{P} pages, {len(locations)} lists of boxes: the lengths must agree")
+    both = []
     for name, lst in (("origins", origins), ("crop_scales", crop_scales)):
-        if lst is not None and len(lst) != P:
+        lst = [None] * P if lst is None else [None if l is None else list(l) for l in lst]      # materialised once: a generator would not
+        if len(lst) != P:                                                                       # survive the length checks
             raise ValueError(f"{P} pages, {len(lst)} lists of {name}: the lengths must agree")
-    sizes = [_page_size(img, f"images[{p}]") for p, img in enumerate(images)]
-    origins, crop_scales = [None] * P if origins is None else origins, [None] * P if crop_scales is None else crop_scales
+        both.append(lst)
+    sizes = [_page_size(img, f"images[{p}]" if paged else "instance_image") for p, img in enumerate(images)]
+    for p, locs in enumerate(locations):
+        for name, lst in (("origins", both[0][p]), ("crop_scales", both[1][p])):
+            if lst is not None and len(lst) != len(locs):
+                raise ValueError((f"page {p}: " if paged else "") + f"{len(locs)} boxes, {len(lst)} {name}: the lengths must agree")
+    return images, locations, both[0], both[1], sizes, sum(len(l) for l in locations)
+
+
+def _plan_pages(paged, images, locations, sizes, origins, crop_scales, rng):
+    """the crops that _page_lists left open, planned page after page on one rng stream (prepost.plan_pages' draws) -> the leading
+    arguments of the prepost functions of the caller's form: (images, locations, origins, crop_scales), of the one page if not paged"""
     for p, (h, w) in enumerate(sizes):
-        for name, lst in (("origins", origins[p]), ("crop_scales", crop_scales[p])):
-            if lst is not None and len(lst) != len(locations[p]):
-                raise ValueError(f"page {p}: {len(locations[p])} boxes, {len(lst)} {name}: the lengths must agree")
         crop_scales[p], origins[p] = _plan_boxes(locations[p], h, w, origins[p], crop_scales[p], rng)
-    return images, locations, origins, crop_scales, sizes, sum(len(l) for l in locations)
+    return (images, locations, origins, crop_scales) if paged else (images[0], locations[0], origins[0], crop_scales[0])
 
 
 @torch.no_grad()
@@ -271,33 +304,11 @@ def _edit_rows(unet, vae, scheduler, pre, dev, encoder_hidden_states, num_infere
     return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
 
-@torch.no_grad()
-def edit_pages(unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, *, origins=None, crop_scales=None,
-               rng=None, batch_size=4, generator=None, enc_noise=None, variance_noise=None, return_intermediate=False, size=512):
-    """edit_boxes for boxes on SEVERAL pages as one batch - what a service holding requests for different images, or a training batch
-    of one box per image, needs.  images: a list of P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device; locations: P lists of
-    boxes (x1, y1, x2, y2); origins / crop_scales: None or P lists, as for edit_boxes per page (what is not given is planned page after
-    page, random origins drawn from `rng` in that order: prepost.plan_pages).  Rows are page-major - page 0's boxes in order, then
-    page 1's -, N in all: encoder_hidden_states [N,L,D], enc_noise [N,4,h,w], variance_noise [steps,N,4,h,w].
-
-    One preprocess_pages launch, the N rows through edit_latents in chunks of `batch_size` (chunks cross page boundaries; every box
-    starts from the seed-0 single-sample draw), one postprocess_pages launch.  Returns the list of P edited pages, with
-    return_intermediate=True also image_vae [N,3,S,S] and the preprocess dict.  With one page this is [edit_boxes(...)], bit for bit."""
-    if int(batch_size) < 1:
-        raise ValueError("batch_size must be at least 1")
-    images, locations, origins, crop_scales, _, N = _page_lists(images, locations, origins, crop_scales, rng)
-    _check_contexts(N, encoder_hidden_states)
-    pre = prepost.preprocess_pages(images, locations, origins, crop_scales, size=size)
-    image_vae = _edit_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
-                           enc_noise, variance_noise, int(size))
-    out = prepost.postprocess_pages(image_vae, images, locations, origins, crop_scales)
-    return (out, image_vae, pre) if return_intermediate else out
-
-
 class VerifiedEdit:
-    """what edit_boxes_verified(return_intermediate=True) returns: image uint8 [h][w][3]; choice int32 [N] (the pasted candidate of each
-    box, -1 = kept the original); scores fp32 [N,K] (mean log-probability per label token); image_vae fp32 [N,K,3,S,S]; pixel_values
-    fp32 [N*K,3,S_h,S_w] (what the OCR model read, box-major); pre (the preprocess_batch dict).  All on the device."""
+    """what edit_boxes_verified(return_intermediate=True) returns: image uint8 [h][w][3] (edit_pages_verified: the list of P pages); choice
+    int32 [N] (the pasted candidate of each box, -1 = kept the original); scores fp32 [N,K] (mean log-probability per label token);
+    image_vae fp32 [N,K,3,S,S]; pixel_values fp32 [N*K,3,S_h,S_w] (what the OCR model read, box-major); pre (the preprocess_batch dict).
+    All on the device."""
 
     def __init__(self, image, choice, scores, image_vae, pixel_values, pre):
         self.image, self.choice, self.scores, self.image_vae, self.pixel_values, self.pre = image, choice, scores, image_vae, pixel_values, pre
@@ -335,7 +346,7 @@ def _check_verified_labels(ocr, N, encoder_hidden_states, labels):
 
 def _check_verified_processor(ocr, processor, size):
     """-> the image processor"""
-    ip =getattr(processor, "image_processor", processor)
+    ip = getattr(processor, "image_processor", processor)
     if not getattr(ip, "do_resize", False):
         raise ValueError("the processor must resize (do_resize=True)")
     want = int(ocr.encoder.config.image_size)
@@ -346,36 +357,11 @@ def _check_verified_processor(ocr, processor, size):
     return ip
 
 
-def _check_verified_args(ocr, processor, instance_image, locations, encoder_hidden_states, labels, candidates, seeds, min_score, batch_size,
-                         ocr_batch_size, origins, crop_scales, size):
-    """every argument check of edit_boxes_verified, on the host side: nothing touches the GPU before it passes.
-    Returns (N, K, seeds, h, w, image processor)."""
-    locations = list(locations)
-    N = len(locations)
-    K, seeds = _check_verified_counts(N, candidates, seeds, min_score, batch_size, ocr_batch_size)
-    h, w = _page_size(instance_image, "instance_image")
-    for name, lst in (("origins", origins), ("crop_scales", crop_scales)):
-        if lst is not None and len(list(lst)) != N:
-            raise ValueError(f"{N} boxes, {len(list(lst))} {name}: the lengths must agree")
-    _check_verified_labels(ocr, N, encoder_hidden_states, labels)
-    prepost.check_readback_boxes(locations, h, w)
-    return N, K, seeds, h, w, _check_verified_processor(ocr, processor, size)
-
-
-@torch.no_grad()
-def _edit_candidates(unet, vae, scheduler, instance_image, locations, origins, crop_scales, ctx, num_inference_steps, seeds, bs, generator,
-                     enc_noise, variance_noise, S):
-    """the generating half of edit_boxes_verified: (preprocess dict, image_vae [N,K,3,S,S]).  Each box is preprocessed and VAE-encoded once;
-    the N*K rows (box-major, candidate k from seeds[k]) go through denoise + vae.decode in chunks of `bs`.  With one seed this is
-    edit_boxes' loop, chunk for chunk."""
-    pre = prepost.preprocess_batch(instance_image, locations, origins, crop_scales, size=S)
-    return pre, _candidate_rows(unet, vae, scheduler, pre, instance_image.device, ctx, num_inference_steps, seeds, bs, generator, enc_noise,
-                                variance_noise, S)
-
-
 @torch.no_grad()
 def _candidate_rows(unet, vae, scheduler, pre, dev, ctx, num_inference_steps, seeds, bs, generator, enc_noise, variance_noise, S):
-    """_edit_candidates' chunk loop over the N rows of a preprocess dict, whatever pages they come from -> image_vae [N,K,3,S,S]"""
+    """the generating half of the verified edits, after the preprocess: the N rows of the preprocess dict `pre`, whatever pages they come
+    from -> image_vae [N,K,3,S,S].  Each box is VAE-encoded once; the N*K rows (box-major, candidate k from seeds[k]) go through denoise +
+    vae.decode in chunks of `bs`.  With one seed this is _edit_rows' loop, chunk for chunk."""
     N, K = pre["image"].shape[0], len(seeds)
     sf = vae.config.scaling_factor
     f = 2 ** (len(vae.config.block_out_channels) - 1)
@@ -422,26 +408,9 @@ def edit_boxes_verified(unet, vae, scheduler, ocr, processor, instance_image, lo
 
     Returns the uint8 [h][w][3] page, or a VerifiedEdit with return_intermediate=True.  candidates=1 with min_score=None returns the
     page of edit_boxes with the same arguments, bit for bit."""
-    N, K, seeds, h, w, ip = _check_verified_args(ocr, processor, instance_image, locations, encoder_hidden_states, labels, candidates, seeds, min_score,
-                                                 batch_size, ocr_batch_size, origins, crop_scales, size)
-    locations = list(locations)
-    crop_scales, origins = _plan_boxes(locations, h, w, origins, crop_scales, rng)
-    pre, image_vae = _edit_candidates(unet, vae, scheduler, instance_image, locations, origins, crop_scales, encoder_hidden_states,
-                                      num_inference_steps, seeds, int(batch_size), generator, enc_noise, variance_noise, int(size))
-    pixel_values = prepost.readback_pixel_values(image_vae, instance_image, locations, origins, crop_scales, ip)
-    scores = _score_candidates(ocr, pixel_values, labels, N, K, int(ocr_batch_size))
-    out, choice = prepost.postprocess_select_batch(image_vae, scores, instance_image, locations, origins, crop_scales, threshold=min_score)
-    return VerifiedEdit(out, choice, scores, image_vae, pixel_values, pre) if return_intermediate else out
-
-
-def _score_candidates(ocr, pixel_values, labels, N, K, ocr_bs):
-    """scores fp32 [N,K] on the device: ocr.score over the N*K read-back rows in chunks of `ocr_bs`, mean log-probability per label token"""
-    lab = labels.to(pixel_values.device).repeat_interleave(K, 0)
-    seq, num = [], []
-    for lo in range(0, N * K, ocr_bs):
-        r = ocr.score(pixel_values[lo:lo + ocr_bs], labels=lab[lo:lo + ocr_bs])
-        seq.append(r.sequence_logprobs); num.append(r.num_tokens)
-    return (torch.cat(seq) / torch.cat(num).clamp(min=1)).reshape(N, K)
+    return _edit_verified(False, unet, vae, scheduler, ocr, processor, [instance_image], [locations], encoder_hidden_states, labels,
+                          num_inference_steps, candidates, seeds, min_score, batch_size, ocr_batch_size, _one(origins), _one(crop_scales), rng,
+                          generator, enc_noise, variance_noise, size, return_intermediate)
 
 
 @torch.no_grad()
@@ -453,17 +422,39 @@ def edit_pages_verified(unet, vae, scheduler, ocr, processor, images, locations,
     loop, prepost.readback_pixel_values_pages, ocr.score and prepost.postprocess_select_pages - chunks cross page boundaries, no score is
     read on the host.  Returns the list of P pages, or a VerifiedEdit whose `image` is that list with return_intermediate=True.
     candidates=1 with min_score=None returns edit_pages' pages, bit for bit."""
-    locations = [list(l) for l in locations]
-    N = sum(len(l) for l in locations)
+    return _edit_verified(True, unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps,
+                          candidates, seeds, min_score, batch_size, ocr_batch_size, origins, crop_scales, rng, generator, enc_noise,
+                          variance_noise, size, return_intermediate)
+
+
+def _edit_verified(paged, unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps, candidates,
+                   seeds, min_score, batch_size, ocr_batch_size, origins, crop_scales, rng, generator, enc_noise, variance_noise, size,
+                   return_intermediate):
+    """edit_boxes_verified (paged=False: one page, its lists wrapped into one-element lists) and edit_pages_verified.  Every argument is
+    checked on the host side first: nothing touches the GPU and no crop is planned - so nothing is drawn from rng - before all have passed."""
+    images, locations, origins, crop_scales, sizes, N = _page_lists(paged, images, locations, origins, crop_scales)
     K, seeds = _check_verified_counts(N, candidates, seeds, min_score, batch_size, ocr_batch_size)
-    images, locations, origins, crop_scales, sizes, N = _page_lists(images, locations, origins, crop_scales, rng)
     _check_verified_labels(ocr, N, encoder_hidden_states, labels)
-    prepost.check_readback_boxes_pages([loc for l in locations for loc in l], [len(l) for l in locations], sizes)
+    if paged:
+        prepost.check_readback_boxes_pages([loc for l in locations for loc in l], [len(l) for l in locations], sizes)
+    else:
+        prepost.check_readback_boxes(locations[0], *sizes[0])
     ip = _check_verified_processor(ocr, processor, size)
-    pre = prepost.preprocess_pages(images, locations, origins, crop_scales, size=int(size))
+    where = _plan_pages(paged, images, locations, sizes, origins, crop_scales, rng)
+    pre = (prepost.preprocess_pages if paged else prepost.preprocess_batch)(*where, size=int(size))
     image_vae = _candidate_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, seeds, int(batch_size),
                                 generator, enc_noise, variance_noise, int(size))
-    pixel_values = prepost.readback_pixel_values_pages(image_vae, images, locations, origins, crop_scales, ip)
+    pixel_values = (prepost.readback_pixel_values_pages if paged else prepost.readback_pixel_values)(image_vae, *where, ip)
     scores = _score_candidates(ocr, pixel_values, labels, N, K, int(ocr_batch_size))
-    out, choice = prepost.postprocess_select_pages(image_vae, scores, images, locations, origins, crop_scales, threshold=min_score)
+    out, choice = (prepost.postprocess_select_pages if paged else prepost.postprocess_select_batch)(image_vae, scores, *where, threshold=min_score)
     return VerifiedEdit(out, choice, scores, image_vae, pixel_values, pre) if return_intermediate else out
+
+
+def _score_candidates(ocr, pixel_values, labels, N, K, ocr_bs):
+    """scores fp32 [N,K] on the device: ocr.score over the N*K read-back rows in chunks of `ocr_bs`, mean log-probability per label token"""
+    lab = labels.to(pixel_values.device).repeat_interleave(K, 0)
+    seq, num = [], []
+    for lo in range(0, N * K, ocr_bs):
+        r = ocr.score(pixel_values[lo:lo + ocr_bs], labels=lab[lo:lo + ocr_bs])
+        seq.append(r.sequence_logprobs); num.append(r.num_tokens)
+    return (torch.cat(seq) / torch.cat(num).clamp(min=1)).reshape(N, K)

@@ -2,6 +2,7 @@
 functions (app.ipynb:370-383 mask, :674-720 crop ladder / origin, :722-745 resize + normalise, :776-779 latent mask,
 :825-846 paste-back) over the HIP kernels in csrc/prepost.hip.  The uint8 image is uploaded once; the three network inputs
 come out of one kernel and the result is pasted back by another - no PIL / cv2 / albumentations and no second PCIe hop."""
+import collections
 import ctypes
 
 import numpy as np
@@ -85,7 +86,7 @@ def postprocess(image_vae, instance_image, location, x_s, y_s, crop_scale):
     return out
 
 
-# ------------------------------------------------------------------------------------------------ several boxes of one image per launch
+# ------------------------------------------------------------------------------------------------ several boxes per launch, on one page or on several
 def plan_edits(locations, h, w, rng=np.random):
     """crop_scale_for + crop_origin for every box of one h x w image: [(x_s, y_s, crop_scale), ...].  Boxes that need a random origin draw
     from `rng` in box order, so a seeded rng gives what one text_editing() call per box would draw."""
@@ -95,6 +96,21 @@ def plan_edits(locations, h, w, rng=np.random):
         x_s, y_s = crop_origin(loc, crop_scale, w, rng)
         plans.append((x_s, y_s, crop_scale))
     return plans
+
+
+def plan_pages(locations, sizes, rng=np.random):
+    """plan_edits page after page on ONE rng stream: locations is a list of P lists of boxes, sizes the pages' (h, w).  Returns P lists
+    of (x_s, y_s, crop_scale); a seeded rng draws exactly what one text_editing() call per box, page after page, would draw."""
+    locations, sizes = list(locations), list(sizes)
+    if len(locations) != len(sizes):
+        raise ValueError(f"{len(locations)} lists of boxes, {len(sizes)} page sizes: the lengths must agree")
+    return [plan_edits(locs, int(h), int(w), rng) for locs, (h, w) in zip(locations, sizes)]
+
+
+# "the boxes of this call", whichever form the caller used: images - the page tensors, on the device dev; locations / origins /
+# crop_scales - one entry per box, flattened page-major; counts - the pages' box counts; paged - the caller passed lists of pages, so
+# the *_pages entries run and lists come back (a one-page call holds one image and runs the one-page entries).
+_Boxes = collections.namedtuple("_Boxes", "images dev locations origins crop_scales counts paged")
 
 
 def _check_items(locations, origins, crop_scales):
@@ -108,221 +124,6 @@ def _check_items(locations, origins, crop_scales):
     if len(origins) != B or len(crop_scales) != B:
         raise ValueError(f"{B} boxes, {len(origins)} origins, {len(crop_scales)} crop scales: the lengths must agree")
     return locations, origins, crop_scales
-
-
-def _upload_items(locations, origins, crop_scales, h, w, S, dev):
-    """the dmx_edit_item table of one launch: filled and validated in pinned memory, then ONE asynchronous copy on the current stream.
-    Returns (host table, its pinned storage, device table): the entry reads the host table, the kernel the device one."""
-    B = len(locations)
-    nbytes = B * ctypes.sizeof(_cabi.EditItem)
-    stage = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-    host = (_cabi.EditItem * B).from_buffer(stage.numpy())
-    for it, loc, (x_s, y_s), crop_scale in zip(host, locations, origins, crop_scales):
-        it.x1, it.y1, it.x2, it.y2 = (int(v) for v in loc[:4])
-        it.x_s, it.y_s, it.crop_scale = int(x_s), int(y_s), int(crop_scale)
-    _cabi.check(_cabi.lib().dmx_edit_items_prepare(host, B, h, w, S), "edit_items_prepare")
-    table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        table.copy_(stage, non_blocking=True)
-    return host, stage, table
-
-
-def preprocess_batch(instance_image, locations, origins, crop_scales, size=512):
-    """B boxes of one image in one launch.  instance_image: uint8 CUDA tensor [h][w][3]; locations: B boxes (x1, y1, x2, y2); origins: B
-    crop origins (x_s, y_s); crop_scales: B crop sides (plan_edits gives the last two).  Returns dict(image, masked_image: fp32
-    [B,3,S,S] in [-1,1]; mask: uint8 [B,1,S,S]; mask_latent: fp32 [B,1,S/8,S/8]); row b equals preprocess() of box b, whose mask holds
-    that box alone.  No [h][w] mask is built."""
-    locations, origins, crop_scales = _check_items(locations, origins, crop_scales)
-    img = _u8(instance_image, "instance_image")
-    h, w, c = img.shape
-    if c != 3:
-        raise ValueError("instance_image must be HWC with 3 channels")
-    dev, B, S = img.device, len(locations), int(size)
-    host, stage, table = _upload_items(locations, origins, crop_scales, h, w, S, dev)
-    with torch.cuda.device(dev):
-        image = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
-        masked = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
-        mask = torch.empty(B, 1, S, S, dtype=torch.uint8, device=dev)
-        mask_lat = torch.empty(B, 1, S // 8, S // 8, dtype=torch.float32, device=dev)
-        _cabi.check(_cabi.lib().dmx_preprocess_crop_batch(_cabi.ptr(img), h, w, host, _cabi.ptr(table), B, S, _cabi.ptr(image), _cabi.ptr(masked),
-                                                         _cabi.ptr(mask), _cabi.ptr(mask_lat), _cabi.current_stream()), "preprocess_crop_batch")
-    return dict(image=image, masked_image=masked, mask=mask, mask_latent=mask_lat)
-
-
-def postprocess_batch(image_vae, instance_image, locations, origins, crop_scales, return_mask=False):
-    """image_vae: fp32 CUDA [B,3,S,S] decoder outputs in [-1,1], one per box; returns the uint8 [h][w][3] image that B chained
-    postprocess() calls in box order leave (a later box wins where boxes overlap), in one launch.  return_mask=True also returns the
-    union of the boxes as uint8 [h][w] in {0, 1} (the app shows mask * 255)."""
-    locations, origins, crop_scales = _check_items(locations, origins, crop_scales)
-    img = _u8(instance_image, "instance_image")
-    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
-        raise TypeError("image_vae: expected a CUDA tensor")
-    h, w, _ = img.shape
-    B = len(locations)
-    if image_vae.dim() != 4 or tuple(image_vae.shape[:2]) != (B, 3) or image_vae.shape[2] != image_vae.shape[3]:
-        raise ValueError(f"image_vae must be [{B},3,S,S]: one square 3-channel image per box")
-    v = image_vae.to(torch.float32).contiguous()
-    dev, S = img.device, int(v.shape[-1])
-    host, stage, table = _upload_items(locations, origins, crop_scales, h, w, S, dev)
-    with torch.cuda.device(dev):
-        out = torch.empty_like(img)
-        union = torch.empty(h, w, dtype=torch.uint8, device=dev) if return_mask else None
-        _cabi.check(_cabi.lib().dmx_postprocess_paste_batch(_cabi.ptr(v), S, _cabi.ptr(img), _cabi.ptr(out), _cabi.ptr(union), h, w, host,
-                                                           _cabi.ptr(table), B, _cabi.current_stream()), "postprocess_paste_batch")
-    return (out, union) if return_mask else out
-
-
-# ------------------------------------------------------------------------------------------------ K candidates per box: read-back and selection
-def _image_processor(processor):
-    """a ViTImageProcessor, or the one inside a TrOCRProcessor"""
-    return getattr(processor, "image_processor", processor)
-
-
-def _check_candidates(K):
-    if not 1 <= int(K) <= _cabi.SELECT_MAX_CANDIDATES:
-        raise ValueError(f"{K} candidates per box, expected 1 .. {_cabi.SELECT_MAX_CANDIDATES}")
-    return int(K)
-
-
-def check_readback_boxes(locations, h, w):
-    """what the read-back needs of the boxes beyond the batched paste's checks: the slice [y1:y2, x1:x2] is non-empty and inside the image"""
-    for b, loc in enumerate(locations):
-        x1, y1, x2, y2 = (int(v) for v in loc[:4])
-        if x2 <= x1 or y2 <= y1:
-            raise ValueError(f"box {b}: ({x1}, {y1}, {x2}, {y2}) is empty; the OCR read-back needs at least one pixel")
-        if x1 < 0 or y1 < 0 or x2 > w or y2 > h:
-            raise ValueError(f"box {b}: ({x1}, {y1}, {x2}, {y2}) lies outside the {w}x{h} image")
-
-
-def _readback_tables(locations, ip, cap):
-    """per box the two resample tables of (box width -> S_w) and (box height -> S_h), deduplicated: (passes [B][4] int32, the concatenated
-    int32 tables, max_taps).  A pass with equal sizes is skipped (offset -1), as Pillow does."""
-    from . import processing
-    S_h, S_w = ip.size["height"], ip.size["width"]
-    passes = np.zeros((len(locations), 4), dtype=np.int32)
-    tables, table_off, n_ints, max_taps = [], {}, 0, 0
-    for b, loc in enumerate(locations):
-        x1, y1, x2, y2 = (int(v) for v in loc[:4])
-        for col, (n_in, n_out) in ((0, (x2 - x1, S_w)), (2, (y2 - y1, S_h))):
-            if n_in == n_out:
-                passes[b, col], passes[b, col + 1] = -1, 0
-                continue
-            taps = processing._taps(n_in, n_out, ip.resample)
-            if taps > cap:
-                raise ValueError(f"box {b}: resizing {n_in} -> {n_out} needs {taps} taps per output pixel, more than the kernel's cap of {cap} "
-                                 "(downscale ratio at most 31 for bilinear, 15 for bicubic)")
-            k = (n_in, n_out, ip.resample)
-            if k not in table_off:
-                t = processing.resample_table(*k)
-                table_off[k] = n_ints; tables.append(t); n_ints += t.size
-            passes[b, col], passes[b, col + 1] = table_off[k], taps
-            max_taps = max(max_taps, taps)
-    return passes, (np.concatenate(tables) if tables else np.zeros(0, dtype=np.int32)), max_taps
-
-
-def readback_pixel_values(image_vae, instance_image, locations, origins, crop_scales, processor, return_resized=False, out=None, out_resized=None):
-    """The OCR model's input for K candidates of each of B boxes, in ONE launch: image_vae fp32 CUDA [B,K,3,S,S] decoder outputs ->
-    pixel_values fp32 [B*K,3,S_h,S_w], box-major.  Row (b, k) is bit for bit `processor(postprocess(image_vae[b, k], instance_image,
-    box b)[y1:y2, x1:x2])` - the reference's read-back (app.ipynb:842-846) - without the page, the slice or the processor call.
-    processor: a ViTImageProcessor or TrOCRProcessor with do_resize; its tables travel in one pinned staging buffer, one H2D copy.
-    return_resized=True also returns the uint8 [B*K,3,S_h,S_w] bytes before rescale / normalise.  out / out_resized (optional): contiguous
-    CUDA tensors of those shapes to write into."""
-    locations, origins, crop_scales = _check_items(locations, origins, crop_scales)
-    ip = _image_processor(processor)
-    if not ip.do_resize:
-        raise ValueError("readback_pixel_values: the processor must resize (do_resize=True): boxes have no common size")
-    img = _u8(instance_image, "instance_image")
-    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
-        raise TypeError("image_vae: expected a CUDA tensor")
-    h, w, _ = img.shape
-    B = len(locations)
-    if image_vae.dim() != 5 or image_vae.shape[0] != B or image_vae.shape[2] != 3 or image_vae.shape[3] != image_vae.shape[4]:
-        raise ValueError(f"image_vae must be [{B},K,3,S,S]: K square 3-channel candidates per box")
-    K = _check_candidates(image_vae.shape[1])
-    check_readback_boxes(locations, h, w)
-    lib = _cabi.lib()
-    passes, tables, max_taps = _readback_tables(locations, ip, int(lib.dmx_glyph_max_taps()))
-    v = image_vae.to(torch.float32).contiguous()
-    dev, S = img.device, int(v.shape[-1])
-    S_h, S_w = ip.size["height"], ip.size["width"]
-    # one staging buffer: items | passes | normalisation table | coefficient tables
-    n_items = B * ctypes.sizeof(_cabi.EditItem)
-    off_pass = n_items
-    off_norm = off_pass + passes.nbytes
-    off_tab = off_norm + ip._norm.nbytes
-    total = off_tab + tables.nbytes
-    stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-    st = stage.numpy()
-    host = (_cabi.EditItem * B).from_buffer(st[:n_items])
-    for it, loc, (x_s, y_s), crop_scale in zip(host, locations, origins, crop_scales):
-        it.x1, it.y1, it.x2, it.y2 = (int(t) for t in loc[:4])
-        it.x_s, it.y_s, it.crop_scale = int(x_s), int(y_s), int(crop_scale)
-    _cabi.check(lib.dmx_edit_items_prepare(host, B, h, w, S), "edit_items_prepare")
-    st[off_pass:off_norm] = passes.reshape(-1).view(np.uint8)
-    st[off_norm:off_tab] = ip._norm.reshape(-1).view(np.uint8)
-    st[off_tab:] = tables.view(np.uint8)
-    host_passes = (_cabi.ReadbackPass * B).from_buffer(st[off_pass:off_norm])
-    with torch.cuda.device(dev):
-        dbuf = torch.empty(total, dtype=torch.uint8, device=dev)
-        dbuf.copy_(stage, non_blocking=True)                          # the one H2D copy
-        base = dbuf.data_ptr()
-        for name, t, dt in (("out", out, torch.float32), ("out_resized", out_resized, torch.uint8)):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dt and t.is_contiguous()
-                                      and tuple(t.shape) == (B * K, 3, S_h, S_w)):
-                raise ValueError(f"{name} must be a contiguous {dt} tensor [{B * K},3,{S_h},{S_w}] on {dev}")
-        if out is None:
-            out = torch.empty(B * K, 3, S_h, S_w, dtype=torch.float32, device=dev)
-        res = out_resized
-        if res is None and return_resized:
-            res = torch.empty(B * K, 3, S_h, S_w, dtype=torch.uint8, device=dev)
-        _cabi.check(lib.dmx_readback_pixel_values(_cabi.ptr(v), S, _cabi.ptr(img), h, w, host, base, B, K, base + off_tab, int(tables.size),
-                                                  base + off_norm, host_passes, base + off_pass, max_taps, S_h, S_w, _cabi.ptr(out),
-                                                  _cabi.ptr(res), _cabi.current_stream()), "readback_pixel_values", lib)
-    return (out, res) if (return_resized or out_resized is not None) else out
-
-
-def postprocess_select_batch(image_vae, scores, instance_image, locations, origins, crop_scales, threshold=None, return_mask=False):
-    """Choose and paste in ONE launch, without reading the scores on the host.  image_vae: fp32 CUDA [B,K,3,S,S]; scores: fp32 CUDA [B,K].
-    choice[b] = arg-max over k of scores[b] (lowest k on a tie; a NaN never wins; 0 when every score is NaN), or -1 when the best score
-    is below `threshold` (None: no threshold) - that box then keeps the original pixels.  Returns (out, choice): the uint8 [h][w][3] page
-    postprocess_batch gives for the chosen rows over the boxes that were kept, and choice int32 [B] on the device; with return_mask=True
-    also the union of ALL boxes as uint8 [h][w]."""
-    locations, origins, crop_scales = _check_items(locations, origins, crop_scales)
-    img = _u8(instance_image, "instance_image")
-    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda and isinstance(scores, torch.Tensor) and scores.is_cuda):
-        raise TypeError("image_vae, scores: expected CUDA tensors")
-    h, w, _ = img.shape
-    B = len(locations)
-    if image_vae.dim() != 5 or image_vae.shape[0] != B or image_vae.shape[2] != 3 or image_vae.shape[3] != image_vae.shape[4]:
-        raise ValueError(f"image_vae must be [{B},K,3,S,S]: K square 3-channel candidates per box")
-    K = _check_candidates(image_vae.shape[1])
-    if tuple(scores.shape) != (B, K):
-        raise ValueError(f"scores must be [{B},{K}], got {tuple(scores.shape)}")
-    thr = float("-inf") if threshold is None else float(threshold)
-    if thr != thr:
-        raise ValueError("threshold is NaN")
-    v = image_vae.to(torch.float32).contiguous()
-    sc = scores.to(torch.float32).contiguous()
-    dev, S = img.device, int(v.shape[-1])
-    host, stage, table = _upload_items(locations, origins, crop_scales, h, w, S, dev)
-    with torch.cuda.device(dev):
-        out = torch.empty_like(img)
-        choice = torch.empty(B, dtype=torch.int32, device=dev)
-        union = torch.empty(h, w, dtype=torch.uint8, device=dev) if return_mask else None
-        _cabi.check(_cabi.lib().dmx_postprocess_paste_select(_cabi.ptr(v), S, _cabi.ptr(sc), thr, _cabi.ptr(img), _cabi.ptr(out), _cabi.ptr(union),
-                                                            _cabi.ptr(choice), h, w, host, _cabi.ptr(table), B, K, _cabi.current_stream()),
-                    "postprocess_paste_select")
-    return (out, choice, union) if return_mask else (out, choice)
-
-
-# ------------------------------------------------------------------------------------------------ boxes on several pages per launch
-def plan_pages(locations, sizes, rng=np.random):
-    """plan_edits page after page on ONE rng stream: locations is a list of P lists of boxes, sizes the pages' (h, w).  Returns P lists
-    of (x_s, y_s, crop_scale); a seeded rng draws exactly what one text_editing() call per box, page after page, would draw."""
-    locations, sizes = list(locations), list(sizes)
-    if len(locations) != len(sizes):
-        raise ValueError(f"{len(locations)} lists of boxes, {len(sizes)} page sizes: the lengths must agree")
-    return [plan_edits(locs, int(h), int(w), rng) for locs, (h, w) in zip(locations, sizes)]
 
 
 def _check_pages(images, locations, origins, crop_scales):
@@ -361,6 +162,87 @@ def _check_page_images(images):
     return images[0].device
 
 
+def _resizing_processor(processor, what):
+    """the image processor of a read-back - a ViTImageProcessor, or the one inside a TrOCRProcessor -, refused unless it resizes; like the
+    lists it is checked before any tensor is looked at"""
+    ip = getattr(processor, "image_processor", processor)
+    if not ip.do_resize:
+        raise ValueError(f"{what}: the processor must resize (do_resize=True): boxes have no common size")
+    return ip
+
+
+def _one_page(instance_image, locations, origins, crop_scales):
+    """the boxes of a one-page call: the lists are checked before the tensor is looked at"""
+    locations, origins, crop_scales = _check_items(locations, origins, crop_scales)
+    img = _u8(instance_image, "instance_image")
+    if img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError("instance_image must be HWC with 3 channels")
+    return _Boxes([img], img.device, locations, origins, crop_scales, [len(locations)], False)
+
+
+def _paged(images, locations, origins, crop_scales):
+    """the boxes of a paged call: the lists are checked before any tensor is looked at"""
+    images, locations, origins, crop_scales, counts = _check_pages(images, locations, origins, crop_scales)
+    return _Boxes(images, _check_page_images(images), locations, origins, crop_scales, counts, True)
+
+
+def _upload(bx, S, out=None, union=None, extra=()):
+    """the tables of one launch - dmx_edit_item | dmx_edit_page (a paged call only; out / union: its pages' output tensors) | `extra`
+    (numpy arrays) - filled and validated in ONE pinned staging buffer, then ONE asynchronous copy on the current stream.  Returns (host
+    items, host pages or None, the pinned storage, the device buffer, the byte offsets of the pages and of every extra array in it):
+    the entries read the host tables, the kernels the device copies."""
+    B, P = len(bx.locations), len(bx.images) if bx.paged else 0
+    n_items, n_pages = B * ctypes.sizeof(_cabi.EditItem), P * ctypes.sizeof(_cabi.EditPage)
+    offs, total = [], n_items + n_pages
+    for a in extra:
+        offs.append(total); total += a.nbytes
+    stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+    st = stage.numpy()
+    host = (_cabi.EditItem * B).from_buffer(st[:n_items])
+    for it, loc, (x_s, y_s), crop_scale in zip(host, bx.locations, bx.origins, bx.crop_scales):
+        it.x1, it.y1, it.x2, it.y2 = (int(v) for v in loc[:4])
+        it.x_s, it.y_s, it.crop_scale = int(x_s), int(y_s), int(crop_scale)
+    if bx.paged:
+        pages = (_cabi.EditPage * P).from_buffer(st[n_items:n_items + n_pages])
+        lo = 0
+        for p, (pg, img, n) in enumerate(zip(pages, bx.images, bx.counts)):
+            pg.original = img.data_ptr()
+            pg.out = out[p].data_ptr() if out is not None else 0
+            pg.union_mask = union[p].data_ptr() if union is not None else 0
+            pg.H, pg.W, pg.item_lo, pg.item_hi = int(img.shape[0]), int(img.shape[1]), lo, lo + n
+            lo += n
+        _cabi.check(_cabi.lib().dmx_edit_pages_prepare(pages, P, host, B, S), "edit_pages_prepare")
+    else:
+        pages = None
+        _cabi.check(_cabi.lib().dmx_edit_items_prepare(host, B, int(bx.images[0].shape[0]), int(bx.images[0].shape[1]), S), "edit_items_prepare")
+    for a, o in zip(extra, offs):
+        st[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    with torch.cuda.device(bx.dev):
+        dbuf = torch.empty(total, dtype=torch.uint8, device=bx.dev)
+        dbuf.copy_(stage, non_blocking=True)                          # the one H2D copy
+    return host, pages, stage, dbuf, [n_items] + offs
+
+
+def _upload_pages(images, locations, origins, crop_scales, counts, S, dev, out=None, union=None, extra=()):
+    """_upload of a paged call from its parts.  The tests build real tables through this function (tests/test_prepost_pages_gpu.py):
+    arguments and the returned tuple stay as they are."""
+    return _upload(_Boxes(images, dev, locations, origins, crop_scales, counts, True), S, out, union, extra)
+
+
+def _check_vae(image_vae, B, candidates):
+    """the decoder outputs of B boxes - [B,3,S,S], or with `candidates` [B,K,3,S,S] - -> (S, K); nothing is converted or copied here"""
+    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
+        raise TypeError("image_vae: expected a CUDA tensor")
+    s = image_vae.shape
+    if image_vae.dim() != (5 if candidates else 4) or s[0] != B or s[-3] != 3 or s[-2] != s[-1]:
+        raise ValueError(f"image_vae must be [{B},K,3,S,S]: K square 3-channel candidates per box" if candidates else
+                         f"image_vae must be [{B},3,S,S]: one square 3-channel image per box")
+    K = int(s[1]) if candidates else 1
+    if not 1 <= K <= _cabi.SELECT_MAX_CANDIDATES:
+        raise ValueError(f"{K} candidates per box, expected 1 .. {_cabi.SELECT_MAX_CANDIDATES}")
+    return int(s[-1]), K
+
+
 def _check_page_outputs(out, images):
     """the optional `out` list of the paged pastes: P contiguous uint8 tensors of the pages' shapes on their device, sharing no memory with
     the pages or with one another (one launch reads every page and writes every output)"""
@@ -380,127 +262,60 @@ def _check_page_outputs(out, images):
     return out
 
 
-def _upload_pages(images, locations, origins, crop_scales, counts, S, dev, out=None, union=None, extra=()):
-    """the tables of one paged launch - dmx_edit_item | dmx_edit_page | `extra` (numpy arrays) - filled and validated in ONE pinned staging
-    buffer, then ONE asynchronous copy on the current stream.  Returns (host items, host pages, the pinned storage, the device buffer,
-    the byte offsets of the pages and of every extra array in it): the entries read the host tables, the kernels the device copies.
-    The tests build real tables through this function (tests/test_prepost_pages_gpu.py): arguments and the returned tuple stay as they are."""
-    B, P = len(locations), len(images)
-    n_items, n_pages = B * ctypes.sizeof(_cabi.EditItem), P * ctypes.sizeof(_cabi.EditPage)
-    offs, total = [], n_items + n_pages
-    for a in extra:
-        offs.append(total); total += a.nbytes
-    stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-    st = stage.numpy()
-    host = (_cabi.EditItem * B).from_buffer(st[:n_items])
-    for it, loc, (x_s, y_s), crop_scale in zip(host, locations, origins, crop_scales):
-        it.x1, it.y1, it.x2, it.y2 = (int(v) for v in loc[:4])
-        it.x_s, it.y_s, it.crop_scale = int(x_s), int(y_s), int(crop_scale)
-    pages = (_cabi.EditPage * P).from_buffer(st[n_items:n_items + n_pages])
-    lo = 0
-    for p, (pg, img, n) in enumerate(zip(pages, images, counts)):
-        pg.original = img.data_ptr()
-        pg.out = out[p].data_ptr() if out is not None else 0
-        pg.union_mask = union[p].data_ptr() if union is not None else 0
-        pg.H, pg.W, pg.item_lo, pg.item_hi = int(img.shape[0]), int(img.shape[1]), lo, lo + n
-        lo += n
-    _cabi.check(_cabi.lib().dmx_edit_pages_prepare(pages, P, host, B, S), "edit_pages_prepare")
-    for a, o in zip(extra, offs):
-        st[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
-    with torch.cuda.device(dev):
-        dbuf = torch.empty(total, dtype=torch.uint8, device=dev)
-        dbuf.copy_(stage, non_blocking=True)                          # the one H2D copy
-    return host, pages, stage, dbuf, [n_items] + offs
+def _paste_outputs(bx, out, return_mask):
+    """what the pastes write: (the output pages - `out` if given, checked -, the union masks or None); lists for a paged call, the one
+    page's tensors otherwise"""
+    if out is not None:
+        out = _check_page_outputs(out, bx.images)
+    with torch.cuda.device(bx.dev):
+        out = [torch.empty_like(img) for img in bx.images] if out is None else out
+        union = [torch.empty(img.shape[0], img.shape[1], dtype=torch.uint8, device=bx.dev) for img in bx.images] if return_mask else None
+    return (out, union) if bx.paged else (out[0], None if union is None else union[0])
 
 
-def preprocess_pages(images, locations, origins, crop_scales, size=512):
-    """preprocess_batch for boxes on SEVERAL pages, in one launch.  images: P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device;
-    locations / origins / crop_scales: P lists, one entry per box of that page (plan_pages gives the last two).  Returns the
-    preprocess_batch dict with N rows, N the total box count, page-major (page 0's boxes in order, then page 1's): row b equals
-    preprocess() of box b on its own page."""
-    images, locations, origins, crop_scales, counts = _check_pages(images, locations, origins, crop_scales)
-    dev, B, S = _check_page_images(images), len(locations), int(size)
-    host, pages, stage, dbuf, offs = _upload_pages(images, locations, origins, crop_scales, counts, S, dev)
+def _preprocess(bx, size):
+    B, S, img = len(bx.locations), int(size), bx.images[0]
+    host, pages, stage, dbuf, offs = _upload(bx, S)
     base = dbuf.data_ptr()
-    with torch.cuda.device(dev):
-        image = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
-        masked = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
-        mask = torch.empty(B, 1, S, S, dtype=torch.uint8, device=dev)
-        mask_lat = torch.empty(B, 1, S // 8, S // 8, dtype=torch.float32, device=dev)
-        _cabi.check(_cabi.lib().dmx_preprocess_crop_pages(pages, base + offs[0], len(images), host, base, B, S, _cabi.ptr(image), _cabi.ptr(masked),
-                                                         _cabi.ptr(mask), _cabi.ptr(mask_lat), _cabi.current_stream()), "preprocess_crop_pages")
+    with torch.cuda.device(bx.dev):
+        image = torch.empty(B, 3, S, S, dtype=torch.float32, device=bx.dev)
+        masked = torch.empty(B, 3, S, S, dtype=torch.float32, device=bx.dev)
+        mask = torch.empty(B, 1, S, S, dtype=torch.uint8, device=bx.dev)
+        mask_lat = torch.empty(B, 1, S // 8, S // 8, dtype=torch.float32, device=bx.dev)
+        outs = (_cabi.ptr(image), _cabi.ptr(masked), _cabi.ptr(mask), _cabi.ptr(mask_lat), _cabi.current_stream())
+        if bx.paged:
+            _cabi.check(_cabi.lib().dmx_preprocess_crop_pages(pages, base + offs[0], len(bx.images), host, base, B, S, *outs), "preprocess_crop_pages")
+        else:
+            _cabi.check(_cabi.lib().dmx_preprocess_crop_batch(_cabi.ptr(img), img.shape[0], img.shape[1], host, base, B, S, *outs),
+                        "preprocess_crop_batch")
     return dict(image=image, masked_image=masked, mask=mask, mask_latent=mask_lat)
 
 
-def _page_outputs(images, out, return_mask, dev):
-    with torch.cuda.device(dev):
-        out = [torch.empty_like(img) for img in images] if out is None else out
-        union = [torch.empty(img.shape[0], img.shape[1], dtype=torch.uint8, device=dev) for img in images] if return_mask else None
-    return out, union
-
-
-def postprocess_pages(image_vae, images, locations, origins, crop_scales, return_mask=False, out=None):
-    """postprocess_batch for boxes on several pages, in one launch.  image_vae: fp32 CUDA [N,3,S,S] decoder outputs, page-major; the
-    other arguments as for preprocess_pages.  Returns the list of P uint8 [h_p][w_p][3] pages - page p is postprocess_batch of its own
-    boxes (a later box wins where boxes overlap) -, with return_mask=True also the list of P union masks uint8 [h_p][w_p].  out
-    (optional): a list of P preallocated contiguous uint8 tensors of the pages' shapes, distinct from `images`, to write into."""
-    images, locations, origins, crop_scales, counts = _check_pages(images, locations, origins, crop_scales)
-    dev, B = _check_page_images(images), len(locations)
-    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
-        raise TypeError("image_vae: expected a CUDA tensor")
-    if image_vae.dim() != 4 or tuple(image_vae.shape[:2]) != (B, 3) or image_vae.shape[2] != image_vae.shape[3]:
-        raise ValueError(f"image_vae must be [{B},3,S,S]: one square 3-channel image per box")
-    if out is not None:
-        out = _check_page_outputs(out, images)
+def _paste(bx, image_vae, return_mask, out):
+    B, img = len(bx.locations), bx.images[0]
+    S, _ = _check_vae(image_vae, B, False)
+    out, union = _paste_outputs(bx, out, return_mask)
     v = image_vae.to(torch.float32).contiguous()
-    S = int(v.shape[-1])
-    out, union = _page_outputs(images, out, return_mask, dev)
-    host, pages, stage, dbuf, offs = _upload_pages(images, locations, origins, crop_scales, counts, S, dev, out, union)
+    host, pages, stage, dbuf, offs = _upload(bx, S, out, union) if bx.paged else _upload(bx, S)
     base = dbuf.data_ptr()
-    with torch.cuda.device(dev):
-        _cabi.check(_cabi.lib().dmx_postprocess_paste_pages(_cabi.ptr(v), S, pages, base + offs[0], len(images), host, base, B,
-                                                           _cabi.current_stream()), "postprocess_paste_pages")
+    with torch.cuda.device(bx.dev):
+        if bx.paged:
+            _cabi.check(_cabi.lib().dmx_postprocess_paste_pages(_cabi.ptr(v), S, pages, base + offs[0], len(bx.images), host, base, B,
+                                                               _cabi.current_stream()), "postprocess_paste_pages")
+        else:
+            _cabi.check(_cabi.lib().dmx_postprocess_paste_batch(_cabi.ptr(v), S, _cabi.ptr(img), _cabi.ptr(out), _cabi.ptr(union), img.shape[0],
+                                                               img.shape[1], host, base, B, _cabi.current_stream()), "postprocess_paste_batch")
     return (out, union) if return_mask else out
 
 
-def readback_pixel_values_pages(image_vae, images, locations, origins, crop_scales, processor, return_resized=False, out=None, out_resized=None):
-    """readback_pixel_values for boxes on several pages, in one launch: image_vae fp32 CUDA [N,K,3,S,S], page-major -> pixel_values fp32
-    [N*K,3,S_h,S_w]; row (b, k) is the read-back of candidate k of box b on its own page.  The items, the pages and the processor's
-    tables travel in one pinned staging buffer, one H2D copy.  return_resized / out / out_resized as for readback_pixel_values."""
-    images, locations, origins, crop_scales, counts = _check_pages(images, locations, origins, crop_scales)
-    ip = _image_processor(processor)
-    if not ip.do_resize:
-        raise ValueError("readback_pixel_values_pages: the processor must resize (do_resize=True): boxes have no common size")
-    dev, B = _check_page_images(images), len(locations)
-    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
-        raise TypeError("image_vae: expected a CUDA tensor")
-    if image_vae.dim() != 5 or image_vae.shape[0] != B or image_vae.shape[2] != 3 or image_vae.shape[3] != image_vae.shape[4]:
-        raise ValueError(f"image_vae must be [{B},K,3,S,S]: K square 3-channel candidates per box")
-    K = _check_candidates(image_vae.shape[1])
-    check_readback_boxes_pages(locations, counts, [img.shape[:2] for img in images])
-    S_h, S_w = ip.size["height"], ip.size["width"]
-    for name, t, dt in (("out", out, torch.float32), ("out_resized", out_resized, torch.uint8)):
-        if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dt and t.is_contiguous()
-                                  and tuple(t.shape) == (B * K, 3, S_h, S_w)):
-            raise ValueError(f"{name} must be a contiguous {dt} tensor [{B * K},3,{S_h},{S_w}] on {dev}")
-    lib = _cabi.lib()
-    passes, tables, max_taps = _readback_tables(locations, ip, int(lib.dmx_glyph_max_taps()))
-    v = image_vae.to(torch.float32).contiguous()
-    S = int(v.shape[-1])
-    host, pages, stage, dbuf, offs = _upload_pages(images, locations, origins, crop_scales, counts, S, dev, extra=(passes, ip._norm, tables))
-    off_pages, off_pass, off_norm, off_tab = offs
-    host_passes = (_cabi.ReadbackPass * B).from_buffer(stage.numpy()[off_pass:off_norm])
-    base = dbuf.data_ptr()
-    with torch.cuda.device(dev):
-        if out is None:
-            out = torch.empty(B * K, 3, S_h, S_w, dtype=torch.float32, device=dev)
-        res = out_resized
-        if res is None and return_resized:
-            res = torch.empty(B * K, 3, S_h, S_w, dtype=torch.uint8, device=dev)
-        _cabi.check(lib.dmx_readback_pixel_values_pages(_cabi.ptr(v), S, pages, base + off_pages, len(images), host, base, B, K, base + off_tab,
-                                                        int(tables.size), base + off_norm, host_passes, base + off_pass, max_taps, S_h, S_w,
-                                                        _cabi.ptr(out), _cabi.ptr(res), _cabi.current_stream()), "readback_pixel_values_pages", lib)
-    return (out, res) if (return_resized or out_resized is not None) else out
+def check_readback_boxes(locations, h, w):
+    """what the read-back needs of the boxes beyond the batched paste's checks: the slice [y1:y2, x1:x2] is non-empty and inside the image"""
+    for b, loc in enumerate(locations):
+        x1, y1, x2, y2 = (int(v) for v in loc[:4])
+        if x2 <= x1 or y2 <= y1:
+            raise ValueError(f"box {b}: ({x1}, {y1}, {x2}, {y2}) is empty; the OCR read-back needs at least one pixel")
+        if x1 < 0 or y1 < 0 or x2 > w or y2 > h:
+            raise ValueError(f"box {b}: ({x1}, {y1}, {x2}, {y2}) lies outside the {w}x{h} image")
 
 
 def check_readback_boxes_pages(locations, counts, sizes):
@@ -514,34 +329,157 @@ def check_readback_boxes_pages(locations, counts, sizes):
         lo += n
 
 
-def postprocess_select_pages(image_vae, scores, images, locations, origins, crop_scales, threshold=None, return_mask=False, out=None):
-    """postprocess_select_batch for boxes on several pages, in one launch: image_vae fp32 CUDA [N,K,3,S,S], scores fp32 CUDA [N,K], both
-    page-major.  Returns (pages, choice): the list of P uint8 pages, page p being what postprocess_select_batch gives for its own boxes,
-    and choice int32 [N] on the device, by the same rule; with return_mask=True also the list of P union masks.  out as for
-    postprocess_pages."""
-    images, locations, origins, crop_scales, counts = _check_pages(images, locations, origins, crop_scales)
-    dev, B = _check_page_images(images), len(locations)
-    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda and isinstance(scores, torch.Tensor) and scores.is_cuda):
-        raise TypeError("image_vae, scores: expected CUDA tensors")
-    if image_vae.dim() != 5 or image_vae.shape[0] != B or image_vae.shape[2] != 3 or image_vae.shape[3] != image_vae.shape[4]:
-        raise ValueError(f"image_vae must be [{B},K,3,S,S]: K square 3-channel candidates per box")
-    K = _check_candidates(image_vae.shape[1])
+def _readback_tables(locations, ip, cap):
+    """per box the two resample tables of (box width -> S_w) and (box height -> S_h), deduplicated: (passes [B][4] int32, the concatenated
+    int32 tables, max_taps).  A pass with equal sizes is skipped (offset -1), as Pillow does."""
+    from . import processing
+    S_h, S_w = ip.size["height"], ip.size["width"]
+    passes = np.zeros((len(locations), 4), dtype=np.int32)
+    tables, table_off, n_ints, max_taps = [], {}, 0, 0
+    for b, loc in enumerate(locations):
+        x1, y1, x2, y2 = (int(v) for v in loc[:4])
+        for col, (n_in, n_out) in ((0, (x2 - x1, S_w)), (2, (y2 - y1, S_h))):
+            if n_in == n_out:
+                passes[b, col], passes[b, col + 1] = -1, 0
+                continue
+            taps = processing._taps(n_in, n_out, ip.resample)
+            if taps > cap:
+                raise ValueError(f"box {b}: resizing {n_in} -> {n_out} needs {taps} taps per output pixel, more than the kernel's cap of {cap} "
+                                 "(downscale ratio at most 31 for bilinear, 15 for bicubic)")
+            k = (n_in, n_out, ip.resample)
+            if k not in table_off:
+                t = processing.resample_table(*k)
+                table_off[k] = n_ints; tables.append(t); n_ints += t.size
+            passes[b, col], passes[b, col + 1] = table_off[k], taps
+            max_taps = max(max_taps, taps)
+    return passes, (np.concatenate(tables) if tables else np.zeros(0, dtype=np.int32)), max_taps
+
+
+def _readback(bx, image_vae, ip, return_resized, out, out_resized):
+    B, img = len(bx.locations), bx.images[0]
+    S, K = _check_vae(image_vae, B, True)
+    if bx.paged:
+        check_readback_boxes_pages(bx.locations, bx.counts, [i.shape[:2] for i in bx.images])
+    else:
+        check_readback_boxes(bx.locations, img.shape[0], img.shape[1])
+    S_h, S_w = ip.size["height"], ip.size["width"]
+    for name, t, dt in (("out", out, torch.float32), ("out_resized", out_resized, torch.uint8)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.device == bx.dev and t.dtype == dt and t.is_contiguous()
+                                  and tuple(t.shape) == (B * K, 3, S_h, S_w)):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor [{B * K},3,{S_h},{S_w}] on {bx.dev}")
+    lib = _cabi.lib()
+    passes, tables, max_taps = _readback_tables(bx.locations, ip, int(lib.dmx_glyph_max_taps()))
+    v = image_vae.to(torch.float32).contiguous()
+    host, pages, stage, dbuf, (off_pages, off_pass, off_norm, off_tab) = _upload(bx, S, extra=(passes, ip._norm, tables))
+    host_passes = (_cabi.ReadbackPass * B).from_buffer(stage.numpy()[off_pass:off_norm])
+    base = dbuf.data_ptr()
+    with torch.cuda.device(bx.dev):
+        if out is None:
+            out = torch.empty(B * K, 3, S_h, S_w, dtype=torch.float32, device=bx.dev)
+        res = out_resized
+        if res is None and return_resized:
+            res = torch.empty(B * K, 3, S_h, S_w, dtype=torch.uint8, device=bx.dev)
+        rest = (host, base, B, K, base + off_tab, int(tables.size), base + off_norm, host_passes, base + off_pass, max_taps, S_h, S_w, _cabi.ptr(out),
+                _cabi.ptr(res), _cabi.current_stream())
+        if bx.paged:
+            _cabi.check(lib.dmx_readback_pixel_values_pages(_cabi.ptr(v), S, pages, base + off_pages, len(bx.images), *rest),
+                        "readback_pixel_values_pages", lib)
+        else:
+            _cabi.check(lib.dmx_readback_pixel_values(_cabi.ptr(v), S, _cabi.ptr(img), img.shape[0], img.shape[1], *rest), "readback_pixel_values", lib)
+    return (out, res) if (return_resized or out_resized is not None) else out
+
+
+def _select_paste(bx, image_vae, scores, threshold, return_mask, out):
+    B, img = len(bx.locations), bx.images[0]
+    if not (isinstance(scores, torch.Tensor) and scores.is_cuda):
+        raise TypeError("scores: expected a CUDA tensor")
+    S, K = _check_vae(image_vae, B, True)
     if tuple(scores.shape) != (B, K):
         raise ValueError(f"scores must be [{B},{K}], got {tuple(scores.shape)}")
     thr = float("-inf") if threshold is None else float(threshold)
     if thr != thr:
         raise ValueError("threshold is NaN")
-    if out is not None:
-        out = _check_page_outputs(out, images)
-    v = image_vae.to(torch.float32).contiguous()
-    sc = scores.to(torch.float32).contiguous()
-    S = int(v.shape[-1])
-    out, union = _page_outputs(images, out, return_mask, dev)
-    host, pages, stage, dbuf, offs = _upload_pages(images, locations, origins, crop_scales, counts, S, dev, out, union)
+    out, union = _paste_outputs(bx, out, return_mask)
+    v, sc = image_vae.to(torch.float32).contiguous(), scores.to(torch.float32).contiguous()
+    host, pages, stage, dbuf, offs = _upload(bx, S, out, union) if bx.paged else _upload(bx, S)
     base = dbuf.data_ptr()
-    with torch.cuda.device(dev):
-        choice = torch.empty(B, dtype=torch.int32, device=dev)
-        _cabi.check(_cabi.lib().dmx_postprocess_paste_select_pages(_cabi.ptr(v), S, _cabi.ptr(sc), thr, _cabi.ptr(choice), pages, base + offs[0],
-                                                                  len(images), host, base, B, K, _cabi.current_stream()),
-                    "postprocess_paste_select_pages")
+    with torch.cuda.device(bx.dev):
+        choice = torch.empty(B, dtype=torch.int32, device=bx.dev)
+        if bx.paged:
+            _cabi.check(_cabi.lib().dmx_postprocess_paste_select_pages(_cabi.ptr(v), S, _cabi.ptr(sc), thr, _cabi.ptr(choice), pages, base + offs[0],
+                                                                      len(bx.images), host, base, B, K, _cabi.current_stream()),
+                        "postprocess_paste_select_pages")
+        else:
+            _cabi.check(_cabi.lib().dmx_postprocess_paste_select(_cabi.ptr(v), S, _cabi.ptr(sc), thr, _cabi.ptr(img), _cabi.ptr(out), _cabi.ptr(union),
+                                                                _cabi.ptr(choice), img.shape[0], img.shape[1], host, base, B, K,
+                                                                _cabi.current_stream()), "postprocess_paste_select")
     return (out, choice, union) if return_mask else (out, choice)
+
+
+# ---- the public functions: each builds the description of its boxes and calls the body above; a one-page function runs the one-page
+# entry of the C-ABI and returns tensors, a paged one the *_pages entry and returns lists
+def preprocess_batch(instance_image, locations, origins, crop_scales, size=512):
+    """B boxes of one image in one launch.  instance_image: uint8 CUDA tensor [h][w][3]; locations: B boxes (x1, y1, x2, y2); origins: B
+    crop origins (x_s, y_s); crop_scales: B crop sides (plan_edits gives the last two).  Returns dict(image, masked_image: fp32
+    [B,3,S,S] in [-1,1]; mask: uint8 [B,1,S,S]; mask_latent: fp32 [B,1,S/8,S/8]); row b equals preprocess() of box b, whose mask holds
+    that box alone.  No [h][w] mask is built."""
+    return _preprocess(_one_page(instance_image, locations, origins, crop_scales), size)
+
+
+def preprocess_pages(images, locations, origins, crop_scales, size=512):
+    """preprocess_batch for boxes on SEVERAL pages, in one launch.  images: P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device;
+    locations / origins / crop_scales: P lists, one entry per box of that page (plan_pages gives the last two).  Returns the
+    preprocess_batch dict with N rows, N the total box count, page-major (page 0's boxes in order, then page 1's): row b equals
+    preprocess() of box b on its own page."""
+    return _preprocess(_paged(images, locations, origins, crop_scales), size)
+
+
+def postprocess_batch(image_vae, instance_image, locations, origins, crop_scales, return_mask=False):
+    """image_vae: fp32 CUDA [B,3,S,S] decoder outputs in [-1,1], one per box; returns the uint8 [h][w][3] image that B chained
+    postprocess() calls in box order leave (a later box wins where boxes overlap), in one launch.  return_mask=True also returns the
+    union of the boxes as uint8 [h][w] in {0, 1} (the app shows mask * 255)."""
+    return _paste(_one_page(instance_image, locations, origins, crop_scales), image_vae, return_mask, None)
+
+
+def postprocess_pages(image_vae, images, locations, origins, crop_scales, return_mask=False, out=None):
+    """postprocess_batch for boxes on several pages, in one launch.  image_vae: fp32 CUDA [N,3,S,S] decoder outputs, page-major; the
+    other arguments as for preprocess_pages.  Returns the list of P uint8 [h_p][w_p][3] pages - page p is postprocess_batch of its own
+    boxes (a later box wins where boxes overlap) -, with return_mask=True also the list of P union masks uint8 [h_p][w_p].  out
+    (optional): a list of P preallocated contiguous uint8 tensors of the pages' shapes, distinct from `images`, to write into."""
+    return _paste(_paged(images, locations, origins, crop_scales), image_vae, return_mask, out)
+
+
+def readback_pixel_values(image_vae, instance_image, locations, origins, crop_scales, processor, return_resized=False, out=None, out_resized=None):
+    """The OCR model's input for K candidates of each of B boxes, in ONE launch: image_vae fp32 CUDA [B,K,3,S,S] decoder outputs ->
+    pixel_values fp32 [B*K,3,S_h,S_w], box-major.  Row (b, k) is bit for bit `processor(postprocess(image_vae[b, k], instance_image,
+    box b)[y1:y2, x1:x2])` - the reference's read-back (app.ipynb:842-846) - without the page, the slice or the processor call.
+    processor: a ViTImageProcessor or TrOCRProcessor with do_resize; its tables travel in one pinned staging buffer, one H2D copy.
+    return_resized=True also returns the uint8 [B*K,3,S_h,S_w] bytes before rescale / normalise.  out / out_resized (optional): contiguous
+    CUDA tensors of those shapes to write into."""
+    ip = _resizing_processor(processor, "readback_pixel_values")
+    return _readback(_one_page(instance_image, locations, origins, crop_scales), image_vae, ip, return_resized, out, out_resized)
+
+
+def readback_pixel_values_pages(image_vae, images, locations, origins, crop_scales, processor, return_resized=False, out=None, out_resized=None):
+    """readback_pixel_values for boxes on several pages, in one launch: image_vae fp32 CUDA [N,K,3,S,S], page-major -> pixel_values fp32
+    [N*K,3,S_h,S_w]; row (b, k) is the read-back of candidate k of box b on its own page.  The items, the pages and the processor's
+    tables travel in one pinned staging buffer, one H2D copy.  return_resized / out / out_resized as for readback_pixel_values."""
+    ip = _resizing_processor(processor, "readback_pixel_values_pages")
+    return _readback(_paged(images, locations, origins, crop_scales), image_vae, ip, return_resized, out, out_resized)
+
+
+def postprocess_select_batch(image_vae, scores, instance_image, locations, origins, crop_scales, threshold=None, return_mask=False):
+    """Choose and paste in ONE launch, without reading the scores on the host.  image_vae: fp32 CUDA [B,K,3,S,S]; scores: fp32 CUDA [B,K].
+    choice[b] = arg-max over k of scores[b] (lowest k on a tie; a NaN never wins; 0 when every score is NaN), or -1 when the best score
+    is below `threshold` (None: no threshold) - that box then keeps the original pixels.  Returns (out, choice): the uint8 [h][w][3] page
+    postprocess_batch gives for the chosen rows over the boxes that were kept, and choice int32 [B] on the device; with return_mask=True
+    also the union of ALL boxes as uint8 [h][w]."""
+    return _select_paste(_one_page(instance_image, locations, origins, crop_scales), image_vae, scores, threshold, return_mask, None)
+
+
+def postprocess_select_pages(image_vae, scores, images, locations, origins, crop_scales, threshold=None, return_mask=False, out=None):
+    """postprocess_select_batch for boxes on several pages, in one launch: image_vae fp32 CUDA [N,K,3,S,S], scores fp32 CUDA [N,K], both
+    page-major.  Returns (pages, choice): the list of P uint8 pages, page p being what postprocess_select_batch gives for its own boxes,
+    and choice int32 [N] on the device, by the same rule; with return_mask=True also the list of P union masks.  out as for
+    postprocess_pages."""
+    return _select_paste(_paged(images, locations, origins, crop_scales), image_vae, scores, threshold, return_mask, out)

@@ -6,7 +6,7 @@ with its stages timed one by one and against the unfused chain built from the fu
 Full-size UNet / VAE / TrOCR (large, 384 x 384) with random weights, 512 px, the 1100 x 1300 page of scripts/bench_edit.py, N = 4 boxes,
 K = 1 / 2 / 4.  Prints one JSON line (and writes it to --out); per K, ms per call (wall clock around work that ends in a synchronise):
   total               edit_boxes_verified, everything
-  denoise_decode      preprocess + VAE encode + denoise + VAE decode of the N*K rows (pipeline._edit_candidates)
+  denoise_decode      preprocess + VAE encode + denoise + VAE decode of the N*K rows (prepost.preprocess_batch + pipeline._candidate_rows)
   readback            prepost.readback_pixel_values: ONE launch                      | chain_readback: N*K postprocess + slice, one processor call
   encoder / score     ocr.encoder on the N*K pixel_values / the decoder's teacher-forced scoring pass on its states
   select_paste        prepost.postprocess_select_batch: ONE launch, no host sync     | chain_select_paste: scores to the host, arg-max there,
@@ -72,8 +72,8 @@ def main():
                                               origins=origins, crop_scales=crops, enc_noise=noise, size=S, return_intermediate=True)
 
         def denoise_decode():
-            pipeline._edit_candidates(unet, vae, D.DDIMScheduler(), img, boxes, origins, crops, ctx, args.steps, list(range(K)), 4, None, noise,
-                                      None, S)
+            pre = prepost.preprocess_batch(img, boxes, origins, crops, size=S)
+            pipeline._candidate_rows(unet, vae, D.DDIMScheduler(), pre, dev, ctx, args.steps, list(range(K)), 4, None, noise, None, S)
 
         r = dict(total_ms=round(timed(total, args.iters, 1), 2), denoise_decode_ms=round(timed(denoise_decode, args.iters, 1), 2))
         v = kept["r"]

@@ -225,6 +225,79 @@ def test_select_pages(cuda, build, ref, threshold):
     assert torch.equal(choice2, choice) and all(torch.equal(a, b_) for a, b_ in zip(got2, got))
 
 
+class _Recorder:
+    """the library, noting the name of every dmx_* function called through it"""
+
+    def __init__(self, lib, names):
+        self._lib, self._names = lib, names
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("dmx_"):
+            return fn
+
+        def call(*args):
+            self._names.append(name)
+            return fn(*args)
+        return call
+
+
+def test_each_function_reaches_its_own_entry(cuda, build, ref, monkeypatch):
+    """a one-page function prepares an item table and runs the one-page entry (its kernel), a paged one a page table and the *_pages
+    entry: one prepare and one launch per call, nothing else"""
+    import diffute_amd as D
+    from diffute_amd import _cabi
+    P = D.prepost
+    names = []
+    rec = _Recorder(_cabi.lib(), names)
+    monkeypatch.setattr(_cabi, "lib", lambda elem=None: rec)
+    imgs = _dev_pages(ref, cuda)
+    boxes, origins, crops = _lists()
+    n0 = len(ITEMS[0])
+    vae = ref["vae"].to(cuda)
+    v0, scores = vae[:, 0].contiguous(), torch.tensor(SCORES, device=cuda)
+    ip = D.TrOCRProcessor(size=SIZE, resample=RB.BILINEAR)
+    one, pages = (imgs[0], boxes[0], origins[0], crops[0]), (imgs, boxes, origins, crops)
+    calls = [("dmx_preprocess_crop_batch", lambda: P.preprocess_batch(*one, size=S)),
+             ("dmx_postprocess_paste_batch", lambda: P.postprocess_batch(v0[:n0], *one)),
+             ("dmx_readback_pixel_values", lambda: P.readback_pixel_values(vae[:n0], *one, ip)),
+             ("dmx_postprocess_paste_select", lambda: P.postprocess_select_batch(vae[:n0], scores[:n0], *one)),
+             ("dmx_preprocess_crop_pages", lambda: P.preprocess_pages(*pages, size=S)),
+             ("dmx_postprocess_paste_pages", lambda: P.postprocess_pages(v0, *pages)),
+             ("dmx_readback_pixel_values_pages", lambda: P.readback_pixel_values_pages(vae, *pages, ip)),
+             ("dmx_postprocess_paste_select_pages", lambda: P.postprocess_select_pages(vae, scores, *pages))]
+    for entry, fn in calls:
+        del names[:]
+        fn()
+        got = [n for n in names if not ("readback" in entry and n == "dmx_glyph_max_taps")]
+        assert got == ["dmx_edit_pages_prepare" if entry.endswith("_pages") else "dmx_edit_items_prepare", entry], entry
+    D.synchronize()
+
+
+def test_one_page_in_the_paged_form_is_the_one_page_form(cuda, build, ref):
+    """page 0 alone, passed as a list of one page: every output equals the one-page function's, bit for bit"""
+    import diffute_amd as D
+    P = D.prepost
+    img = _dev_pages(ref, cuda)[0]
+    boxes, origins, crops = (l[0] for l in _lists())
+    n0 = len(ITEMS[0])
+    vae = ref["vae"][:n0].to(cuda)
+    v0, scores = vae[:, 0].contiguous(), torch.tensor(SCORES[:n0], device=cuda)
+    ip = D.TrOCRProcessor(size=SIZE, resample=RB.BILINEAR)
+    one, paged = (img, boxes, origins, crops), ([img], [boxes], [origins], [crops])
+    a, b = P.preprocess_batch(*one, size=S), P.preprocess_pages(*paged, size=S)
+    assert sorted(a) == sorted(b) and all(torch.equal(a[k], b[k]) for k in a)
+    (a, am), (b, bm) = P.postprocess_batch(v0, *one, return_mask=True), P.postprocess_pages(v0, *paged, return_mask=True)
+    assert len(b) == 1 and len(bm) == 1 and torch.equal(a, b[0]) and torch.equal(am, bm[0])
+    (a, au), (b, bu) = P.readback_pixel_values(vae, *one, ip, return_resized=True), P.readback_pixel_values_pages(vae, *paged, ip, return_resized=True)
+    assert torch.equal(a, b) and torch.equal(au, bu)
+    a, ac, am = P.postprocess_select_batch(vae, scores, *one, threshold=THRESHOLD, return_mask=True)
+    b, bc, bm = P.postprocess_select_pages(vae, scores, *paged, threshold=THRESHOLD, return_mask=True)
+    D.synchronize()
+    assert ac.tolist() == [0, 1, 0, -1, 1], "page 0's scores hold a tie, a NaN and a box below the threshold"
+    assert len(b) == 1 and len(bm) == 1 and torch.equal(a, b[0]) and torch.equal(ac, bc) and torch.equal(am, bm[0])
+
+
 def test_refusals_launch_nothing(cuda, ref):
     """a bad item, a bad output list and a host table spoiled after the prepare: an error, and the sentinel-filled slab stays as it was"""
     import diffute_amd as D

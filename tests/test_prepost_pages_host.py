@@ -247,6 +247,36 @@ def test_edit_pages_raises_its_argument_errors_without_a_gpu():
     run(TypeError)                                                          # every list is fine: the first thing that touches a tensor refuses the host pages
 
 
+def test_a_refused_verified_call_draws_nothing_from_rng():
+    """every argument check of edit_boxes_verified / edit_pages_verified runs before a crop is planned: after the ValueError the caller's
+    rng stands where it stood, so the next - corrected - call plans the crops the first one would have.  Origins and crop scales are
+    left out, and planning these pages does draw (the second page's origins)."""
+    from types import SimpleNamespace
+    import diffute_amd as D
+    from diffute_amd import prepost
+    ocr = SimpleNamespace(encoder=SimpleNamespace(config=SimpleNamespace(image_size=32)),
+                          decoder=SimpleNamespace(config=SimpleNamespace(vocab_size=300, max_position_embeddings=64)))
+    imgs = [torch.zeros(h, w, 3, dtype=torch.uint8) for h, w in SIZES]
+    N = sum(len(b) for b in BOXES)
+    ctx, labels, proc = torch.zeros(N, 77, 128), torch.full((N, 5), 7, dtype=torch.int64), D.TrOCRProcessor(size=32)
+    empty = [list(b) for b in BOXES]
+    empty[0][1] = (40, 40, 40, 60)
+    drawn, twin = np.random.RandomState(11), np.random.RandomState(11)
+    prepost.plan_pages(BOXES, SIZES, drawn)
+    assert drawn.randint(1 << 30) != twin.randint(1 << 30), "planning these pages draws nothing: the checks below would show nothing"
+    for n, images, boxes, call in ((N, imgs, BOXES, D.edit_pages_verified), (len(BOXES[0]), imgs[0], BOXES[0], D.edit_boxes_verified)):
+        one_page = call is D.edit_boxes_verified
+        for bad in (dict(labels=labels[:n - 1]),                                       # one row of labels too few
+                    dict(locations=empty[0] if one_page else empty),                   # an empty box: nothing to read back
+                    dict(processor=D.TrOCRProcessor(size=384))):                       # the encoder reads 32 x 32
+            a = dict(processor=proc, locations=boxes, labels=labels[:n])
+            a.update(bad)
+            mine, twin = np.random.RandomState(7), np.random.RandomState(7)
+            with pytest.raises(ValueError):
+                call(None, None, None, ocr, a["processor"], images, a["locations"], ctx[:n], a["labels"], 3, size=S, rng=mine)
+            assert mine.randint(1 << 30) == twin.randint(1 << 30), f"{call.__name__} refused {sorted(bad)} after drawing from rng"
+
+
 def test_public_names():
     import diffute_amd as D
     from diffute_amd import _cabi, edit_pages, edit_pages_verified, prepost
