@@ -8,13 +8,14 @@ from .models import (AutoencoderKL, UNet2DConditionModel, DiagonalGaussianDistri
                      SD2_INPAINT_UNET_CONFIG, SD_VAE_CONFIG, TROCR_LARGE_VIT_CONFIG)
 from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, SD2_SCHEDULER_CONFIG
 from .pipeline import denoise, edit_boxes, edit_boxes_verified, edit_latents, edit_pages, edit_pages_verified, mask_to_latent
+from .inflight import DenoiseEngine
 from .optim import FusedAdamW, GradScaler
 from .training_utils import EMAModel
 from .ocr import TrOCRForCausalLM, VisionEncoderDecoderModel, TROCR_LARGE_DECODER_CONFIG
 from .processing import TrOCRProcessor, ViTImageProcessor
 from ._cabi import set_exclusive_device, synchronize
 
-__all__ = ["AutoencoderKL", "UNet2DConditionModel", "DDPMScheduler", "DDIMScheduler", "DPMSolverMultistepScheduler", "denoise", "edit_latents", "edit_boxes", "edit_boxes_verified", "edit_pages", "edit_pages_verified",
+__all__ = ["AutoencoderKL", "UNet2DConditionModel", "DDPMScheduler", "DDIMScheduler", "DPMSolverMultistepScheduler", "DenoiseEngine", "denoise", "edit_latents", "edit_boxes", "edit_boxes_verified", "edit_pages", "edit_pages_verified",
            "mask_to_latent", "FusedAdamW", "GradScaler", "EMAModel", "TrOCREncoder", "TrOCRForCausalLM", "VisionEncoderDecoderModel", "TrOCRProcessor", "ViTImageProcessor", "TROCR_LARGE_DECODER_CONFIG", "TROCR_LARGE_VIT_CONFIG", "DiagonalGaussianDistribution", "SD2_INPAINT_UNET_CONFIG", "SD_VAE_CONFIG",
            "SD2_SCHEDULER_CONFIG", "set_exclusive_device", "synchronize"]
 __version__ = "0.1.0"

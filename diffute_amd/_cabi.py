@@ -73,6 +73,16 @@ class DpmCoefs(ctypes.Structure):
                 ("inv_r0", c_float), ("inv_r1", c_float), ("r0_over_r01", c_float), ("inv_r01", c_float)]
 
 
+class SchedRowRec(ctypes.Structure):
+    """dmx_sched_row_rec (include/diffute_hip.h): one step of a plan of the in-flight engine - the scheduler scalars (c: the five DDIM or DDPM
+    scalars in the order of the scalar entries' arguments; dpm / order: DPM-Solver++), use_noise, the three history-ring positions, the timestep"""
+    _fields_ = [("c", c_float * 5), ("dpm", DpmCoefs), ("order", c_int), ("use_noise", c_int),
+                ("ring_w", c_int), ("ring_m1", c_int), ("ring_m2", c_int), ("timestep", c_int64)]
+
+
+SCHED_DDIM, SCHED_DDPM, SCHED_DPMPP = 0, 1, 2      # DMX_SCHED_*
+
+
 class ViTConfig(ctypes.Structure):
     _fields_ = [("image_size", c_int), ("patch_size", c_int), ("num_channels", c_int), ("hidden_size", c_int), ("num_layers", c_int),
                 ("num_heads", c_int), ("intermediate_size", c_int), ("qkv_bias", c_int), ("layer_norm_eps", c_float)]
@@ -218,6 +228,9 @@ _PROTOS = {
     "dmx_sched_step_ddim": (c_int, [_P, _P, _P, _P, c_size_t, c_float, c_float, c_float, c_float, c_float, c_int, _P]),
     "dmx_sched_step_ddpm": (c_int, [_P, _P, _P, _P, c_size_t, c_float, c_float, c_float, c_float, c_float, c_int, _P]),
     "dmx_sched_step_dpmpp": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t, c_int, DpmCoefs, c_int, _P]),
+    "dmx_sched_step_rows": (c_int, [_P, _P, _P, _P, c_int, _P, _P, c_int, c_size_t, c_int, c_int, _P]),
+    "dmx_rows_admit": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "dmx_rows_advance": (c_int, [_P, _P, c_int, _P]),
     "dmx_sched_add_noise": (c_int, [_P, _P, _P, _P, _P, c_int, c_size_t, _P]),
     "dmx_sched_get_velocity": (c_int, [_P, _P, _P, _P, _P, c_int, c_size_t, _P]),
     "dmx_gaussian_sample": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, _P]),
@@ -259,6 +272,7 @@ _PROTOS = {
     "dmx_unet_context_bytes": (c_size_t, [_P, c_int, c_int]),
     "dmx_unet_workspace_bytes": (c_size_t, [_P, c_int, c_int, c_int, c_int]),
     "dmx_unet_set_context": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_size_t, _P, c_size_t, _P]),
+    "dmx_unet_set_context_rows": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P, c_size_t, _P]),
     "dmx_unet_forward": (c_int, [_P, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     "dmx_unet_forward_taps": (c_int, [_P, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_size_t,
                                       _P, c_size_t, _P, _P, _P]),
@@ -302,6 +316,7 @@ _PROTOS = {
     "dmx_unet_temb_table_workspace_bytes": (c_size_t, [_P, c_int]),
     "dmx_unet_temb_table": (c_int, [_P, _P, c_int, _P, _P, c_size_t, _P]),
     "dmx_unet_use_temb_table": (c_int, [_P, _P, _P]),
+    "dmx_unet_use_temb_table_rows": (c_int, [_P, _P, _P, _P]),
     "dmx_mask_rasterize": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "dmx_preprocess_crop": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "dmx_postprocess_paste": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),

@@ -387,6 +387,28 @@ extern "C" int dmx_sched_step_dpmpp(const float* sample, const float* model_outp
   DMX_REQUIRE(!dmx_overlap(x0_out, m1, n) && !dmx_overlap(x0_out, m2, n) && !dmx_overlap(x0_out, prev_sample, n), "sched_step_dpmpp: x0_out overlaps m1, m2 or prev_sample");
   return dmx_sched_dpmpp_launch(sample, model_output, m1, m2, x0_out, prev_sample, n, order, coefs, v_prediction, (hipStream_t)stream);
 }
+extern "C" int dmx_sched_step_rows(float* sample, const float* model_output, const float* noise, float* hist, int n_hist,
+                                   const dmx_sched_row_rec* plan, const int* row_index, int B, size_t per_sample, int kind, int v_prediction,
+                                   dmx_stream_t stream) {
+  DMX_REQUIRE(sample && model_output && plan && row_index, "sched_step_rows: null argument");
+  DMX_REQUIRE(B >= 1 && B <= 65535 && per_sample > 0, "sched_step_rows: B=%d rows of %zu elements", B, per_sample);
+  DMX_REQUIRE(kind == DMX_SCHED_DDIM || kind == DMX_SCHED_DDPM || kind == DMX_SCHED_DPMPP, "sched_step_rows: kind %d", kind);
+  if (kind == DMX_SCHED_DPMPP) {
+    DMX_REQUIRE(hist && n_hist >= 1 && n_hist <= 3, "sched_step_rows: DPM-Solver++ needs its history ring (n_hist 1..3)");
+    const size_t nb = (size_t)B * per_sample;
+    DMX_REQUIRE(hist + (size_t)n_hist * nb <= sample || sample + nb <= hist, "sched_step_rows: the history ring overlaps the sample");
+  }
+  return dmx_sched_rows_launch(sample, model_output, noise, kind == DMX_SCHED_DPMPP ? hist : nullptr, kind == DMX_SCHED_DPMPP ? n_hist : 0, plan,
+                               row_index, B, per_sample, kind, v_prediction, (hipStream_t)stream);
+}
+extern "C" int dmx_rows_admit(int* row_index, int* row_left, int b, int plan_base, int n_steps, dmx_stream_t stream) {
+  DMX_REQUIRE(row_index && row_left && b >= 0 && plan_base >= 0 && n_steps >= 0, "rows_admit: row %d, plan row %d, %d steps", b, plan_base, n_steps);
+  return dmx_rows_admit_launch(row_index, row_left, b, plan_base, n_steps, (hipStream_t)stream);
+}
+extern "C" int dmx_rows_advance(int* row_index, int* row_left, int B, dmx_stream_t stream) {
+  DMX_REQUIRE(row_index && row_left && B >= 1, "rows_advance: null argument");
+  return dmx_rows_advance_launch(row_index, row_left, B, (hipStream_t)stream);
+}
 extern "C" int dmx_sched_add_noise(const float* x0, const float* noise, const float* sa, const float* sb, float* out, int B, size_t per, dmx_stream_t stream) {
   DMX_REQUIRE(x0 && noise && sa && sb && out, "sched_add_noise: null argument");
   return dmx_add_noise_launch(x0, noise, sa, sb, out, B, per, 0, (hipStream_t)stream);

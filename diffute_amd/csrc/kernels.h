@@ -414,6 +414,11 @@ int dmx_sched_ddpm_launch(const float* x, const float* eps, const float* noise, 
 struct dmx_dpm_coefs;                                  // include/diffute_hip.h
 int dmx_sched_dpmpp_launch(const float* x, const float* eps, const float* m1, const float* m2, float* x0_out, float* out, size_t n,
                            int order, const dmx_dpm_coefs& c, int vpred, hipStream_t stream);
+struct dmx_sched_row_rec;
+int dmx_sched_rows_launch(float* x, const float* eps, const float* noise, float* hist, int n_hist, const dmx_sched_row_rec* plan,
+                          const int* row_index, int B, size_t per, int kind, int vpred, hipStream_t stream);
+int dmx_rows_admit_launch(int* row_index, int* row_left, int b, int plan_base, int n_steps, hipStream_t stream);
+int dmx_rows_advance_launch(int* row_index, int* row_left, int B, hipStream_t stream);
 int dmx_add_noise_launch(const float* x0, const float* noise, const float* sa, const float* sb, float* out,
                          int B, size_t per, int velocity, hipStream_t stream);
 int dmx_gaussian_sample_launch(const float* moments, const float* noise, float* out, int B, int C, int HW, float scale, hipStream_t stream);

@@ -8,22 +8,25 @@
 #include "../../include/diffute_hip.h"
 
 // DDIM: x0 = (x - sqrt(1-abar_t)*eps)/sqrt(abar_t); prev = sqrt(abar_p)*x0 + dir*eps (+ std*noise)
+// One element of the update; the scalar-timestep kernel and the per-row kernel (dmx_sched_rows_kernel) both call it, so a row is the same bits in either.
+__device__ __forceinline__ float ddim_elem(float xv, float ev, bool has_noise, float nz, float sqrt_bt, float sqrt_at, float sqrt_ap, float dir_coef,
+                                           float std, int vpred) {
+  float x0, pe;
+  if (!vpred) {
+    x0 = __fdiv_rn(__fsub_rn(xv, __fmul_rn(sqrt_bt, ev)), sqrt_at);
+    pe = ev;
+  } else {
+    x0 = __fsub_rn(__fmul_rn(sqrt_at, xv), __fmul_rn(sqrt_bt, ev));
+    pe = __fadd_rn(__fmul_rn(sqrt_at, ev), __fmul_rn(sqrt_bt, xv));
+  }
+  float prev = __fadd_rn(__fmul_rn(sqrt_ap, x0), __fmul_rn(dir_coef, pe));
+  if (has_noise) prev = __fadd_rn(prev, __fmul_rn(std, nz));
+  return prev;
+}
 __global__ __launch_bounds__(256) void dmx_sched_ddim_kernel(const float* x, const float* eps, const float* noise, float* out, size_t n,
                                                              float sqrt_bt, float sqrt_at, float sqrt_ap, float dir_coef, float std, int vpred) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float xv = x[i], ev = eps[i];
-    float x0, pe;
-    if (!vpred) {
-      x0 = __fdiv_rn(__fsub_rn(xv, __fmul_rn(sqrt_bt, ev)), sqrt_at);
-      pe = ev;
-    } else {
-      x0 = __fsub_rn(__fmul_rn(sqrt_at, xv), __fmul_rn(sqrt_bt, ev));
-      pe = __fadd_rn(__fmul_rn(sqrt_at, ev), __fmul_rn(sqrt_bt, xv));
-    }
-    float prev = __fadd_rn(__fmul_rn(sqrt_ap, x0), __fmul_rn(dir_coef, pe));
-    if (noise) prev = __fadd_rn(prev, __fmul_rn(std, noise[i]));
-    out[i] = prev;
-  }
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    out[i] = ddim_elem(x[i], eps[i], noise != nullptr, noise ? noise[i] : 0.f, sqrt_bt, sqrt_at, sqrt_ap, dir_coef, std, vpred);
 }
 int dmx_sched_ddim_launch(const float* x, const float* eps, const float* noise, float* out, size_t n,
                           float sqrt_bt, float sqrt_at, float sqrt_ap, float dir_coef, float std, int vpred, hipStream_t stream) {
@@ -33,17 +36,19 @@ int dmx_sched_ddim_launch(const float* x, const float* eps, const float* noise, 
 }
 
 // DDPM: prev = c0*x0 + c1*x (+ sigma*noise when t>0)
+__device__ __forceinline__ float ddpm_elem(float xv, float ev, bool has_noise, float nz, float sqrt_bt, float sqrt_at, float c0, float c1, float sigma,
+                                           int vpred) {
+  float x0;
+  if (!vpred) x0 = __fdiv_rn(__fsub_rn(xv, __fmul_rn(sqrt_bt, ev)), sqrt_at);
+  else x0 = __fsub_rn(__fmul_rn(sqrt_at, xv), __fmul_rn(sqrt_bt, ev));
+  float prev = __fadd_rn(__fmul_rn(c0, x0), __fmul_rn(c1, xv));
+  if (has_noise) prev = __fadd_rn(prev, __fmul_rn(sigma, nz));
+  return prev;
+}
 __global__ __launch_bounds__(256) void dmx_sched_ddpm_kernel(const float* x, const float* eps, const float* noise, float* out, size_t n,
                                                              float sqrt_bt, float sqrt_at, float c0, float c1, float sigma, int vpred) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float xv = x[i], ev = eps[i];
-    float x0;
-    if (!vpred) x0 = __fdiv_rn(__fsub_rn(xv, __fmul_rn(sqrt_bt, ev)), sqrt_at);
-    else x0 = __fsub_rn(__fmul_rn(sqrt_at, xv), __fmul_rn(sqrt_bt, ev));
-    float prev = __fadd_rn(__fmul_rn(c0, x0), __fmul_rn(c1, xv));
-    if (noise) prev = __fadd_rn(prev, __fmul_rn(sigma, noise[i]));
-    out[i] = prev;
-  }
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    out[i] = ddpm_elem(x[i], eps[i], noise != nullptr, noise ? noise[i] : 0.f, sqrt_bt, sqrt_at, c0, c1, sigma, vpred);
 }
 int dmx_sched_ddpm_launch(const float* x, const float* eps, const float* noise, float* out, size_t n,
                           float sqrt_bt, float sqrt_at, float c0, float c1, float sigma, int vpred, hipStream_t stream) {
@@ -159,4 +164,96 @@ int dmx_sched_dpmpp_launch(const float* x, const float* eps, const float* m1, co
   if (vec) hipLaunchKernelGGL(dmx_sched_dpmpp_kernel<true>, dim3(blocks), dim3(256), 0, stream, x, eps, m1, m2, x0_out, out, n, order, c, vpred);
   else hipLaunchKernelGGL(dmx_sched_dpmpp_kernel<false>, dim3(blocks), dim3(256), 0, stream, x, eps, m1, m2, x0_out, out, n, order, c, vpred);
   return dmx_check_launch("dmx_sched_dpmpp_kernel");
+}
+
+// ---- in-flight batching (diffute_amd/inflight.py): every row of the batch on its own schedule.  Row b runs plan record plan[row_index[b]]
+// (row_index[b] < 0: idle - the block returns before it reads or writes anything of the row).  Grid (chunks of a row, row): one record per block.
+// Per element the update is ddim_elem / ddpm_elem / dpm_elem above, so an active row equals the scalar entry run on that row alone, bit for bit.
+// hist [n_hist][B][per]: the DPM-Solver++ ring; the record names the slot it writes (ring_w) and the two it reads (ring_m1, ring_m2).
+// float4 where every slab of THIS row is 16-byte aligned (per need not be a multiple of 4, so rows differ), the per % 4 tail by scalar accesses.
+static_assert(sizeof(dmx_sched_row_rec) == 88, "dmx_sched_row_rec: the host packs 88-byte records (diffute_amd/_cabi.py SchedRowRec)");
+template <int KIND>
+__global__ __launch_bounds__(256) void dmx_sched_rows_kernel(float* x, const float* eps, const float* noise, float* hist, int n_hist,
+                                                             const dmx_sched_row_rec* plan, const int* row_index, int B, size_t per, int vpred) {
+  const int b = blockIdx.y;
+  const int idx = row_index[b];
+  if (idx < 0) return;
+  const dmx_sched_row_rec r = plan[idx];
+  float* xr = x + (size_t)b * per;
+  const float* er = eps + (size_t)b * per;
+  const bool has_noise = KIND != DMX_SCHED_DPMPP && noise != nullptr && r.use_noise != 0;
+  const float* nr = has_noise ? noise + (size_t)b * per : nullptr;
+  const int order = KIND == DMX_SCHED_DPMPP ? r.order : 0;
+  float* m0r = nullptr; const float* m1r = nullptr; const float* m2r = nullptr;
+  if (KIND == DMX_SCHED_DPMPP) {
+    if (order < 1 || order > n_hist || order > 3 || r.ring_w < 0 || r.ring_w >= n_hist) return;      // (a record the ring cannot serve: the row is left alone)
+    m0r = hist + ((size_t)r.ring_w * B + b) * per;
+    if (order >= 2) { if (r.ring_m1 < 0 || r.ring_m1 >= n_hist || r.ring_m1 == r.ring_w) return; m1r = hist + ((size_t)r.ring_m1 * B + b) * per; }
+    if (order >= 3) { if (r.ring_m2 < 0 || r.ring_m2 >= n_hist || r.ring_m2 == r.ring_w) return; m2r = hist + ((size_t)r.ring_m2 * B + b) * per; }
+  }
+  auto elem = [&](float xv, float ev, float nz, float a1, float a2, float& m0) -> float {
+    if (KIND == DMX_SCHED_DDIM) return ddim_elem(xv, ev, has_noise, nz, r.c[0], r.c[1], r.c[2], r.c[3], r.c[4], vpred);
+    if (KIND == DMX_SCHED_DDPM) return ddpm_elem(xv, ev, has_noise, nz, r.c[0], r.c[1], r.c[2], r.c[3], r.c[4], vpred);
+    return dpm_elem(xv, ev, a1, a2, m0, order, r.dpm, vpred);
+  };
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  const uintptr_t bits = (uintptr_t)xr | (uintptr_t)er | (uintptr_t)nr | (uintptr_t)m0r | (uintptr_t)m1r | (uintptr_t)m2r;
+  size_t done = 0;
+  if ((bits & 15) == 0) {
+    const size_t n4 = per / 4;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (size_t i = tid; i < n4; i += stride) {
+      const float4 xv = reinterpret_cast<const float4*>(xr)[i], ev = reinterpret_cast<const float4*>(er)[i];
+      const float4 nz = has_noise ? reinterpret_cast<const float4*>(nr)[i] : z4;
+      const float4 a = order >= 2 ? reinterpret_cast<const float4*>(m1r)[i] : z4;
+      const float4 c = order >= 3 ? reinterpret_cast<const float4*>(m2r)[i] : z4;
+      float4 m0 = z4, p;
+      p.x = elem(xv.x, ev.x, nz.x, a.x, c.x, m0.x);
+      p.y = elem(xv.y, ev.y, nz.y, a.y, c.y, m0.y);
+      p.z = elem(xv.z, ev.z, nz.z, a.z, c.z, m0.z);
+      p.w = elem(xv.w, ev.w, nz.w, a.w, c.w, m0.w);
+      if (KIND == DMX_SCHED_DPMPP) reinterpret_cast<float4*>(m0r)[i] = m0;
+      reinterpret_cast<float4*>(xr)[i] = p;
+    }
+    done = n4 * 4;
+  }
+  for (size_t i = done + tid; i < per; i += stride) {
+    float m0 = 0.f;
+    const float p = elem(xr[i], er[i], has_noise ? nr[i] : 0.f, order >= 2 ? m1r[i] : 0.f, order >= 3 ? m2r[i] : 0.f, m0);
+    if (KIND == DMX_SCHED_DPMPP) m0r[i] = m0;
+    xr[i] = p;
+  }
+}
+int dmx_sched_rows_launch(float* x, const float* eps, const float* noise, float* hist, int n_hist, const dmx_sched_row_rec* plan,
+                          const int* row_index, int B, size_t per, int kind, int vpred, hipStream_t stream) {
+  const size_t work = (per + 3) / 4;
+  int chunks = (int)((work + 255) / 256); if (chunks > 512) chunks = 512; if (chunks < 1) chunks = 1;
+  const dim3 grid(chunks, B);
+  if (kind == DMX_SCHED_DDIM) hipLaunchKernelGGL(dmx_sched_rows_kernel<DMX_SCHED_DDIM>, grid, dim3(256), 0, stream, x, eps, noise, hist, n_hist, plan, row_index, B, per, vpred);
+  else if (kind == DMX_SCHED_DDPM) hipLaunchKernelGGL(dmx_sched_rows_kernel<DMX_SCHED_DDPM>, grid, dim3(256), 0, stream, x, eps, noise, hist, n_hist, plan, row_index, B, per, vpred);
+  else hipLaunchKernelGGL(dmx_sched_rows_kernel<DMX_SCHED_DPMPP>, grid, dim3(256), 0, stream, x, eps, noise, hist, n_hist, plan, row_index, B, per, vpred);
+  return dmx_check_launch("dmx_sched_rows_kernel");
+}
+
+// the two device ints of a row: row_index[b] (a plan row, -1 = idle) and row_left[b] (steps still to run).  One block each; the values of an
+// admission travel as kernel arguments.
+__global__ void dmx_rows_admit_kernel(int* row_index, int* row_left, int b, int plan_base, int n_steps) {
+  if (threadIdx.x == 0) { row_index[b] = n_steps > 0 ? plan_base : -1; row_left[b] = n_steps > 0 ? n_steps : 0; }
+}
+__global__ void dmx_rows_advance_kernel(int* row_index, int* row_left, int B) {
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const int idx = row_index[b];
+    if (idx < 0) continue;
+    const int left = row_left[b] - 1;
+    row_left[b] = left;
+    row_index[b] = left > 0 ? idx + 1 : -1;
+  }
+}
+int dmx_rows_admit_launch(int* row_index, int* row_left, int b, int plan_base, int n_steps, hipStream_t stream) {
+  hipLaunchKernelGGL(dmx_rows_admit_kernel, dim3(1), dim3(64), 0, stream, row_index, row_left, b, plan_base, n_steps);
+  return dmx_check_launch("dmx_rows_admit_kernel");
+}
+int dmx_rows_advance_launch(int* row_index, int* row_left, int B, hipStream_t stream) {
+  hipLaunchKernelGGL(dmx_rows_advance_kernel, dim3(1), dim3(64), 0, stream, row_index, row_left, B);
+  return dmx_check_launch("dmx_rows_advance_kernel");
 }

@@ -222,6 +222,28 @@ extern "C" int dmx_unet_set_context(dmx_unet* u, const void* ctx, int ctx_is_bf1
   return ex.rc;
 }
 
+// the projection for n rows of a running batch: rows [row0, row0 + n) of every layer's [B*sp][2C] slab (row b is the contiguous
+// [sp][2C] block at b*sp).  The GEMM's M is n*sp and its output starts at row row0*sp: rows outside are not touched.
+extern "C" int dmx_unet_set_context_rows(dmx_unet* u, const void* ctx, int ctx_is_bf16, int row0, int n, int B, int ctx_len,
+                                         void* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
+  DMX_REQUIRE(u && u->finalized, "unet_set_context_rows: weights not finalized");
+  DMX_REQUIRE(B >= 1 && n >= 1 && row0 >= 0 && row0 <= B - n, "unet_set_context_rows: rows [%d, %d) of a cache of %d rows", row0, row0 + n, B);
+  DMX_REQUIRE(ctx_len >= 1, "unet_set_context_rows: ctx_len %d", ctx_len);
+  DMX_REQUIRE(ctx && cache && cache_bytes >= dmx_unet_context_bytes(u, B, ctx_len), "unet_set_context_rows: context cache too small");
+  Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes);
+  const int D = u->cfg.cross_attention_dim, sp = ctx_pad(ctx_len);
+  bf16* cp = (bf16*)ex.raw((size_t)n * sp * D * 2);
+  if (ex.rc) return ex.rc;
+  int rc = dmx_cast_pad_rows_launch(ctx, ctx_is_bf16, cp, n, ctx_len, sp, D, ex.stream);
+  if (rc) return rc;
+  for (const XfW* x : u->xf_all) {
+    const bf16* kv = ctx_slot_ptr(u, cache, B, ctx_len, x->ctx_slot) + (size_t)row0 * sp * 2 * x->C;
+    ex.gemm_raw(cp, D, n * sp, u->at<bf16>(x->wkv2), D, 2 * x->C, D, nullptr, (void*)kv, 2 * x->C, 0);
+    if (ex.rc) return ex.rc;
+  }
+  return ex.rc;
+}
+
 // ----------------------------------------------------------------------------- forward
 namespace {
 
@@ -352,6 +374,17 @@ __global__ __launch_bounds__(256) void dmx_temb_row_kernel(const float* table, c
   const float* src = table + (size_t)(*step) * n;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) out[i] = src[i];
 }
+// per-row form: image b fetches row max(row_index[b], 0) (an idle row reads row 0: finite, ignored); the first thread of each image's first
+// block also writes that plan row's timestep into the forward's timesteps buffer
+__global__ __launch_bounds__(256) void dmx_temb_rows_kernel(const float* table, const dmx_sched_row_rec* plan, const int* row_index, float* out,
+                                                            long long* timesteps, int n) {
+  const int b = blockIdx.y;
+  int idx = row_index[b]; if (idx < 0) idx = 0;
+  const float* src = table + (size_t)idx * n;
+  float* dst = out + (size_t)b * n;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) dst[i] = src[i];
+  if (blockIdx.x == 0 && threadIdx.x == 0) timesteps[b] = (long long)plan[idx].timestep;
+}
 
 }  // namespace
 
@@ -388,6 +421,12 @@ extern "C" int dmx_unet_use_temb_table(dmx_unet* u, const float* table, const in
   DMX_REQUIRE(u != nullptr, "unet_use_temb_table: null handle");
   DMX_REQUIRE((table == nullptr) == (step_index == nullptr), "unet_use_temb_table: table and step index go together");
   u->temb_table = table; u->temb_step = step_index;
+  return DMX_OK;
+}
+extern "C" int dmx_unet_use_temb_table_rows(dmx_unet* u, const float* table, const dmx_sched_row_rec* plan, const int* row_index) {
+  DMX_REQUIRE(u != nullptr, "unet_use_temb_table_rows: null handle");
+  DMX_REQUIRE((table == nullptr) == (row_index == nullptr) && (table == nullptr) == (plan == nullptr), "unet_use_temb_table_rows: table, plan and row index go together");
+  u->temb_rows_table = table; u->temb_rows_plan = plan; u->temb_rows_index = row_index;
   return DMX_OK;
 }
 
@@ -453,7 +492,12 @@ int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c) {
     ex.drop(x9);
   } else {
     if (!ex.dry && !ex.rc) {
-      if (u->temb_table && t_count == 1) {
+      if (u->temb_rows_table && t_count == B) {
+        // in-flight batching: every image on its own step - row row_index[b] of the plans' table, and timesteps[b] from the plan
+        hipLaunchKernelGGL(dmx_temb_rows_kernel, dim3(cdiv(u->tproj_total, 1024), B), dim3(256), 0, ex.stream, u->temb_rows_table, u->temb_rows_plan,
+                           u->temb_rows_index, tproj, const_cast<long long*>(c.timesteps), u->tproj_total);
+        ex.rc = dmx_check_launch("dmx_temb_rows_kernel");
+      } else if (u->temb_table && t_count == 1) {
         // the loop computed the projections of all its timesteps in one batched pass (dmx_unet_temb_table): fetch this step's row
         hipLaunchKernelGGL(dmx_temb_row_kernel, dim3(cdiv(u->tproj_total, 1024)), dim3(256), 0, ex.stream, u->temb_table, u->temb_step, tproj, u->tproj_total);
         ex.rc = dmx_check_launch("dmx_temb_row_kernel");

@@ -42,18 +42,21 @@ struct dmx_unet : ModelBase {
   // optional source of the time-embedding projections (dmx_unet_use_temb_table): row *temb_step of a table computed for all
   // timesteps of a denoise loop in one batched pass, instead of four small launches per step
   const float* temb_table = nullptr; const int* temb_step = nullptr;
+  // per-row form (dmx_unet_use_temb_table_rows): row row_index[b] of `temb_rows_table` for image b, timesteps[b] from the plan record
+  const float* temb_rows_table = nullptr; const dmx_sched_row_rec* temb_rows_plan = nullptr; const int* temb_rows_index = nullptr;
   // hipGraph cache: one captured UNet step per distinct call (pointers are baked into the nodes).  The key is everything the captured
-  // launches depend on: the call record, the workspace, the time-embedding table and dmx_plan_epoch() (every dmx_set_* switch changes
+  // launches depend on: the call record, the workspace, the time-embedding table (scalar or per-row form) and dmx_plan_epoch() (every dmx_set_* switch changes
   // the plans baked into the graph)
   struct GraphKey {
     const void *f0, *f1, *f2, *timesteps, *ctx, *out, *workspace; int c0, c1, c2, t_count, ctx_len, B, H, W;
-    const void *temb_table, *temb_step; int plan_epoch;
-    auto tie() const { return std::tie(f0, f1, f2, timesteps, ctx, out, workspace, c0, c1, c2, t_count, ctx_len, B, H, W, temb_table, temb_step, plan_epoch); }
+    const void *temb_table, *temb_step, *temb_rows_table, *temb_rows_plan, *temb_rows_index; int plan_epoch;
+    auto tie() const { return std::tie(f0, f1, f2, timesteps, ctx, out, workspace, c0, c1, c2, t_count, ctx_len, B, H, W, temb_table, temb_step, temb_rows_table, temb_rows_plan,
+                                       temb_rows_index, plan_epoch); }
     bool operator<(const GraphKey& o) const { return tie() < o.tie(); }
   };
   GraphKey graph_key(const UNetCall& c, const void* workspace) const {
     return GraphKey{c.f0, c.f1, c.f2, c.timesteps, c.ctx, c.out, workspace, c.c0, c.c1, c.c2, c.t_count, c.ctx_len, c.B, c.H, c.W,
-                    temb_table, temb_step, dmx_plan_epoch()};
+                    temb_table, temb_step, temb_rows_table, temb_rows_plan, temb_rows_index, dmx_plan_epoch()};
   }
   struct GraphEntry { hipGraphExec_t exec = nullptr; int seen = 0; };
   std::map<GraphKey, GraphEntry> graphs;

@@ -482,6 +482,44 @@ class UNet2DConditionModel(_HipModel):
         sl["ctx_key"] = (encoder_hidden_states, encoder_hidden_states._version, self._epoch)
         sl["ctx_shape"] = (B, S)
 
+    def reserve_context(self, B, ctx_len, slot=0):
+        """A zeroed K/V cache laid out for B rows of `ctx_len` context tokens on `slot`, to be filled row by row with set_context_rows()
+        (the in-flight engine: diffute_amd/inflight.py).  A zero row is a valid context (K = V = 0: finite attention output)."""
+        self._ensure_packed()
+        sl = self._slot(slot)
+        nb = self._lib.dmx_unet_context_bytes(self._h, int(B), int(ctx_len))
+        sl["ctx_cache"] = torch.zeros(nb, dtype=torch.uint8, device=self.device)
+        sl["ctx_key"] = (None, None, self._epoch)
+        sl["ctx_shape"] = (int(B), int(ctx_len))
+
+    def set_context_rows(self, encoder_hidden_states, row0, slot=0):
+        """set_context() for rows [row0, row0 + n) of the slot's cache (n = encoder_hidden_states.shape[0]) while the other rows keep their
+        K/V: the slot must hold a cache for at least row0 + n rows of the same context length (set_context / reserve_context).  With
+        row0 = 0 and n = the cache's rows this writes the bytes set_context writes."""
+        self._ensure_packed()
+        sl = self._slot(slot)
+        ctx = encoder_hidden_states
+        _cabi.require_cuda(ctx)
+        if ctx.dtype not in (torch.float32, self.compute_dtype):
+            ctx = ctx.to(torch.float32)
+        ctx = ctx.contiguous()
+        n, S, D = ctx.shape
+        if D != self.config.cross_attention_dim:
+            raise ValueError(f"encoder_hidden_states last dim {D} != cross_attention_dim {self.config.cross_attention_dim}")
+        if sl["ctx_key"] is None or sl["ctx_key"][2] != self._epoch:
+            raise RuntimeError("UNet2DConditionModel: set_context_rows() needs a cache made by set_context() / reserve_context() on this slot")
+        B, S0 = sl["ctx_shape"]
+        if S != S0:
+            raise ValueError(f"context length {S} != the cache's {S0}")
+        if n < 1 or row0 < 0 or row0 + n > B:
+            raise ValueError(f"rows [{row0}, {row0 + n}) of a cache of {B} rows")
+        lib = self._lib
+        ws = self._grown(sl, "ws", lib.dmx_unet_workspace_bytes(self._h, B, 8, 8, S))
+        _cabi.check(lib.dmx_unet_set_context_rows(self._h, _cabi.ptr(ctx), int(ctx.dtype == self.compute_dtype), int(row0), n, B, S,
+                                                  _cabi.ptr(sl["ctx_cache"]), sl["ctx_cache"].numel(),
+                                                  _cabi.ptr(ws), ws.numel(), _cabi.current_stream()), "unet_set_context_rows")
+        sl["ctx_key"] = (None, None, self._epoch)      # (no single tensor stands for the cache any more)
+
     def temb_table(self, timesteps_dev):
         """[T][sum of resnet widths] fp32: the time-embedding MLP + every resnet's time_emb_proj for ALL the (scalar) timesteps of a
         denoise loop in one batched pass (include/diffute_hip.h dmx_unet_temb_table); forward_parts(..., temb=(table, step_index))
@@ -500,7 +538,10 @@ class UNet2DConditionModel(_HipModel):
         (fuses the torch.cat of app.ipynb:811); timesteps_dev = int64 cuda tensor [1] or [B];
         context must have been set with set_context() on the same slot.  graph=True replays a captured hipGraph
         when the same buffers are passed again (needs a non-default current stream).  temb = (temb_table(...), int32 cuda
-        tensor [1] holding the step's row): the time-embedding projections come from the table (scalar timestep only)."""
+        tensor [1] holding the step's row): the time-embedding projections come from the table (scalar timestep only).
+        temb = (table, row_index, plan) is the per-row form of the in-flight engine: row_index int32 cuda [B] (-1 = idle row, served row 0),
+        plan the device array of dmx_sched_row_rec with the table's row numbering; timesteps_dev must be [B] and is WRITTEN with the
+        plan's timesteps by the forward."""
         lib = self._lib
         sl = self._slot(slot)
         x0 = parts[0]
@@ -515,7 +556,12 @@ class UNet2DConditionModel(_HipModel):
             sl["ws_need"] = (key, lib.dmx_unet_workspace_bytes(self._h, B, H, W, sl["ctx_shape"][1]))
         ws = self._grown(sl, "ws", sl["ws_need"][1])
         fwd = lib.dmx_unet_forward_graph if graph else lib.dmx_unet_forward
-        if temb is not None:
+        rows = temb is not None and len(temb) == 3
+        if rows:
+            if temb[1].numel() != B or timesteps_dev.numel() != B or temb[1].dtype != torch.int32:
+                raise ValueError(f"forward_parts: the per-row temb form needs an int32 row index and timesteps of {B} entries each")
+            _cabi.check(lib.dmx_unet_use_temb_table_rows(self._h, _cabi.ptr(temb[0]), _cabi.ptr(temb[2]), _cabi.ptr(temb[1])), "unet_use_temb_table_rows")
+        elif temb is not None:
             _cabi.check(lib.dmx_unet_use_temb_table(self._h, _cabi.ptr(temb[0]), _cabi.ptr(temb[1])), "unet_use_temb_table")
         try:
             _cabi.check(fwd(self._h, _cabi.ptr(ps[0][0]), ps[0][1], _cabi.ptr(ps[1][0]), ps[1][1],
@@ -523,7 +569,9 @@ class UNet2DConditionModel(_HipModel):
                             _cabi.ptr(sl["ctx_cache"]), sl["ctx_shape"][1], _cabi.ptr(out), B, H, W,
                             _cabi.ptr(ws), ws.numel(), _cabi.current_stream()), "unet_forward")
         finally:
-            if temb is not None:
+            if rows:
+                lib.dmx_unet_use_temb_table_rows(self._h, None, None, None)
+            elif temb is not None:
                 lib.dmx_unet_use_temb_table(self._h, None, None)
         return out
 

@@ -450,6 +450,35 @@ typedef struct dmx_dpm_coefs {
  * be `sample` (in-place update).  Bit-identical to the fp32 CPU evaluation of diffusers' expressions in their op order. */
 int dmx_sched_step_dpmpp(const float* sample, const float* model_output, const float* m1, const float* m2, float* x0_out,
                          float* prev_sample, size_t n, int order, dmx_dpm_coefs coefs, int v_prediction, dmx_stream_t stream);
+/* ---- in-flight batching (diffute_amd/inflight.py DenoiseEngine): every row of a denoise batch on its own schedule.
+ * A PLAN is built once per (scheduler kind, num_inference_steps): a device array of per-step records and a time-embedding table
+ * (dmx_unet_temb_table) with the same row numbering, so plan row p names the timestep, the table row and the scheduler scalars of
+ * one step at once.  Plans of several step counts are stored back to back in one array / one table.  Row b of the batch is two
+ * device ints at fixed addresses: row_index[b] (a plan row, -1 = idle) and row_left[b] (steps still to run).
+ * c[5]: DDIM (sqrt_beta_prod_t, sqrt_alpha_prod_t, sqrt_alpha_prod_prev, dir_coef, std_dev) or DDPM (sqrt_beta_prod_t,
+ * sqrt_alpha_prod_t, coef_x0, coef_xt, sigma) - the scalar arguments of the entries above in their order; dpm / order: the
+ * arguments of the DPM-Solver++ entry; ring_w / ring_m1 / ring_m2: the history slots step i of its request writes (i % k) and reads
+ * ((i-1) % k, (i-2) % k; k = solver_order); use_noise: add c[4] * noise (the entries above: noise != NULL). */
+typedef struct dmx_sched_row_rec {
+  float c[5];
+  dmx_dpm_coefs dpm;
+  int order, use_noise;
+  int ring_w, ring_m1, ring_m2;
+  int64_t timestep;
+} dmx_sched_row_rec;
+enum { DMX_SCHED_DDIM = 0, DMX_SCHED_DDPM = 1, DMX_SCHED_DPMPP = 2 };
+/* One launch for all B rows: row b with row_index[b] >= 0 is updated IN PLACE (sample [B][per_sample]) with record
+ * plan[row_index[b]]; per element bit-identical to the matching entry above run on that row alone.  A row with row_index[b] < 0
+ * is neither read nor written, nor is its slice of any history buffer.  model_output / noise [B][per_sample] (noise may be NULL:
+ * no row adds noise); hist [n_hist][B][per_sample] (DPM-Solver++ only, n_hist = solver_order; NULL, 0 otherwise).  per_sample
+ * need not be a multiple of 4. */
+int dmx_sched_step_rows(float* sample, const float* model_output, const float* noise, float* hist, int n_hist,
+                        const dmx_sched_row_rec* plan, const int* row_index, int B, size_t per_sample, int kind, int v_prediction,
+                        dmx_stream_t stream);
+/* row b starts at plan row plan_base with n_steps steps to run (the values travel as kernel arguments: no staging buffer) */
+int dmx_rows_admit(int* row_index, int* row_left, int b, int plan_base, int n_steps, dmx_stream_t stream);
+/* after the scheduler launch of a tick: every active row index++, left--, index = -1 at left == 0 */
+int dmx_rows_advance(int* row_index, int* row_left, int B, dmx_stream_t stream);
 /* scheduler.add_noise / get_velocity (train_diffute_v1.py:897,907): per-sample coefficients */
 int dmx_sched_add_noise(const float* x0, const float* noise, const float* sqrt_alpha_prod, const float* sqrt_one_minus,
                         float* out, int B, size_t per_sample, dmx_stream_t stream);
@@ -488,6 +517,12 @@ size_t dmx_unet_workspace_bytes(dmx_unet* u, int B, int H, int W, int ctx_len);
 int dmx_unet_set_context(dmx_unet* u, const void* ctx, int ctx_is_bf16, int B, int ctx_len,
                          void* context_cache, size_t context_bytes, void* workspace, size_t workspace_bytes,
                          dmx_stream_t stream);
+/* The same projection for `n` context rows (ctx [n][ctx_len][cross_attention_dim]) into rows [row0, row0 + n) of a cache laid out
+ * for B rows (dmx_unet_context_bytes(u, B, ctx_len)): one row of a running batch gets a new glyph context while the others are mid-loop.
+ * No byte of another row is written.  row0 = 0, n = B issues the GEMMs of dmx_unet_set_context (same M, ld, pointers): the same bytes. */
+int dmx_unet_set_context_rows(dmx_unet* u, const void* ctx, int ctx_is_bf16, int row0, int n, int B, int ctx_len,
+                              void* context_cache, size_t context_bytes, void* workspace, size_t workspace_bytes,
+                              dmx_stream_t stream);
 /* unet(sample, timestep, encoder_hidden_states).sample  (app.ipynb:814, train_diffute_v1.py:913).
  * The 9-channel sample is given as up to three NCHW fp32 tensors (c0+c1+c2 = in_channels):
  * pass the concatenated tensor as f0 with c0 = 9, or latents/mask/masked latents separately
@@ -507,6 +542,11 @@ size_t dmx_unet_temb_table_floats(dmx_unet* u, int T);
 size_t dmx_unet_temb_table_workspace_bytes(dmx_unet* u, int T);
 int dmx_unet_temb_table(dmx_unet* u, const int64_t* timesteps, int T, float* table, void* workspace, size_t workspace_bytes, dmx_stream_t stream);
 int dmx_unet_use_temb_table(dmx_unet* u, const float* table, const int* step_index);
+/* Per-row form (in-flight batching): with (table, plan, row_index) set, a forward with t_count == B fetches
+ * tproj[b] = table[max(row_index[b], 0)] with one launch, which also WRITES timesteps[b] = plan[max(row_index[b], 0)].timestep into the
+ * forward's `timesteps` argument (it stays truthful; the buffer must be writable).  `table` and `plan` share their row numbering;
+ * row_index is int [B] on the device.  All three NULL switches back.  Takes precedence over the scalar form when both are set. */
+int dmx_unet_use_temb_table_rows(dmx_unet* u, const float* table, const dmx_sched_row_rec* plan, const int* row_index);
 /* Same as dmx_unet_forward; the launch sequence is captured into a hipGraph the second time an identical argument
  * tuple is seen and replayed afterwards.  Requires a non-NULL stream (falls back to eager launches otherwise). */
 int dmx_unet_forward_graph(dmx_unet* u, const float* f0, int c0, const float* f1, int c1, const float* f2, int c2,
