@@ -364,19 +364,24 @@ extern "C" int dmx_nchw_f32_to_nhwc_bf16(const float* in, void* out, int ldo, in
   DMX_REQUIRE(in && out, "nchw_f32_to_nhwc_bf16: null argument");
   return dmx_nchw_f32_to_nhwc_bf16_launch(in, (bf16*)out, ldo, B, C, HW, (hipStream_t)stream);
 }
+// the record of a DDIM / DDPM scalar entry: its five scalars in argument order
+static dmx_sched_row_rec sched_rec5(float c0, float c1, float c2, float c3, float c4) {
+  dmx_sched_row_rec r{}; r.c[0] = c0; r.c[1] = c1; r.c[2] = c2; r.c[3] = c3; r.c[4] = c4;
+  return r;
+}
 extern "C" int dmx_sched_step_ddim(const float* sample, const float* model_output, const float* noise, float* prev_sample, size_t n,
                                    float sqrt_beta_prod_t, float sqrt_alpha_prod_t, float sqrt_alpha_prod_prev,
                                    float dir_coef, float std_dev, int v_prediction, dmx_stream_t stream) {
   DMX_REQUIRE(sample && model_output && prev_sample, "sched_step_ddim: null argument");
-  return dmx_sched_ddim_launch(sample, model_output, noise, prev_sample, n, sqrt_beta_prod_t, sqrt_alpha_prod_t, sqrt_alpha_prod_prev,
-                               dir_coef, std_dev, v_prediction, (hipStream_t)stream);
+  const dmx_sched_row_rec r = sched_rec5(sqrt_beta_prod_t, sqrt_alpha_prod_t, sqrt_alpha_prod_prev, dir_coef, std_dev);
+  return dmx_sched_step_launch(DMX_SCHED_DDIM, r, sample, model_output, noise, nullptr, nullptr, nullptr, prev_sample, n, v_prediction, (hipStream_t)stream);
 }
 extern "C" int dmx_sched_step_ddpm(const float* sample, const float* model_output, const float* noise, float* prev_sample, size_t n,
                                    float sqrt_beta_prod_t, float sqrt_alpha_prod_t, float coef_x0, float coef_xt,
                                    float sigma, int v_prediction, dmx_stream_t stream) {
   DMX_REQUIRE(sample && model_output && prev_sample, "sched_step_ddpm: null argument");
-  return dmx_sched_ddpm_launch(sample, model_output, noise, prev_sample, n, sqrt_beta_prod_t, sqrt_alpha_prod_t, coef_x0, coef_xt,
-                               sigma, v_prediction, (hipStream_t)stream);
+  const dmx_sched_row_rec r = sched_rec5(sqrt_beta_prod_t, sqrt_alpha_prod_t, coef_x0, coef_xt, sigma);
+  return dmx_sched_step_launch(DMX_SCHED_DDPM, r, sample, model_output, noise, nullptr, nullptr, nullptr, prev_sample, n, v_prediction, (hipStream_t)stream);
 }
 static bool dmx_overlap(const float* a, const float* b, size_t n) { return a && b && a < b + n && b < a + n; }
 extern "C" int dmx_sched_step_dpmpp(const float* sample, const float* model_output, const float* m1, const float* m2, float* x0_out,
@@ -385,7 +390,8 @@ extern "C" int dmx_sched_step_dpmpp(const float* sample, const float* model_outp
   DMX_REQUIRE(order >= 1 && order <= 3, "sched_step_dpmpp: order %d (1, 2 or 3)", order);
   DMX_REQUIRE((order < 2 || m1) && (order < 3 || m2), "sched_step_dpmpp: order %d needs the previous %d data prediction(s)", order, order - 1);
   DMX_REQUIRE(!dmx_overlap(x0_out, m1, n) && !dmx_overlap(x0_out, m2, n) && !dmx_overlap(x0_out, prev_sample, n), "sched_step_dpmpp: x0_out overlaps m1, m2 or prev_sample");
-  return dmx_sched_dpmpp_launch(sample, model_output, m1, m2, x0_out, prev_sample, n, order, coefs, v_prediction, (hipStream_t)stream);
+  dmx_sched_row_rec r{}; r.dpm = coefs; r.order = order;
+  return dmx_sched_step_launch(DMX_SCHED_DPMPP, r, sample, model_output, nullptr, m1, m2, x0_out, prev_sample, n, v_prediction, (hipStream_t)stream);
 }
 extern "C" int dmx_sched_step_rows(float* sample, const float* model_output, const float* noise, float* hist, int n_hist,
                                    const dmx_sched_row_rec* plan, const int* row_index, int B, size_t per_sample, int kind, int v_prediction,

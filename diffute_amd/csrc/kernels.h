@@ -407,14 +407,10 @@ int dmx_linear_small_launch(const float* x, int ldx, const bf16* w, int ldw, con
                             int B, int N, int K, int silu_in, hipStream_t stream);
 
 // ------------------------------------------------------------------ sched.hip
-int dmx_sched_ddim_launch(const float* x, const float* eps, const float* noise, float* out, size_t n,
-                          float sqrt_bt, float sqrt_at, float sqrt_ap, float dir_coef, float std, int vpred, hipStream_t stream);
-int dmx_sched_ddpm_launch(const float* x, const float* eps, const float* noise, float* out, size_t n,
-                          float sqrt_bt, float sqrt_at, float c0, float c1, float sigma, int vpred, hipStream_t stream);
-struct dmx_dpm_coefs;                                  // include/diffute_hip.h
-int dmx_sched_dpmpp_launch(const float* x, const float* eps, const float* m1, const float* m2, float* x0_out, float* out, size_t n,
-                           int order, const dmx_dpm_coefs& c, int vpred, hipStream_t stream);
-struct dmx_sched_row_rec;
+struct dmx_sched_row_rec;                              // include/diffute_hip.h: one step - the scheduler scalars, use_noise, ring slots, timestep
+// the scalar entries: one record by value over n elements; noise / m1 / m2 / x0_out as the entry of `kind` (DMX_SCHED_*) takes them, NULL otherwise
+int dmx_sched_step_launch(int kind, const dmx_sched_row_rec& rec, const float* x, const float* eps, const float* noise, const float* m1,
+                          const float* m2, float* x0_out, float* out, size_t n, int vpred, hipStream_t stream);
 int dmx_sched_rows_launch(float* x, const float* eps, const float* noise, float* hist, int n_hist, const dmx_sched_row_rec* plan,
                           const int* row_index, int B, size_t per, int kind, int vpred, hipStream_t stream);
 int dmx_rows_admit_launch(int* row_index, int* row_left, int b, int plan_base, int n_steps, hipStream_t stream);

@@ -203,27 +203,31 @@ static const bf16* ctx_slot_ptr(const dmx_unet* u, const void* cache, int B, int
   return (const bf16*)((const char*)cache + off);
 }
 
-extern "C" int dmx_unet_set_context(dmx_unet* u, const void* ctx, int ctx_is_bf16, int B, int ctx_len,
-                                    void* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
-  DMX_REQUIRE(u && u->finalized, "unet_set_context: weights not finalized");
-  DMX_REQUIRE(ctx && cache && cache_bytes >= dmx_unet_context_bytes(u, B, ctx_len), "unet_set_context: context cache too small");
-  Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes);
+// The K / V projection of n context rows (ctx [n][ctx_len][D]) into rows [row0, row0 + n) of a cache laid out for B rows: row b of every
+// layer's [B*sp][2C] slab is the contiguous [sp][2C] block at b*sp, so the GEMM's M is n*sp and its output starts at row row0*sp - rows
+// outside are not touched.  On a dry Exec (the workspace query) nothing is launched.
+static int project_context(const dmx_unet* u, Exec& ex, const void* ctx, int ctx_is_bf16, int row0, int n, int B, int ctx_len, void* cache) {
   const int D = u->cfg.cross_attention_dim, sp = ctx_pad(ctx_len);
-  bf16* cp = (bf16*)ex.raw((size_t)B * sp * D * 2);
+  bf16* cp = (bf16*)ex.raw((size_t)n * sp * D * 2);
   if (ex.rc) return ex.rc;
-  int rc = dmx_cast_pad_rows_launch(ctx, ctx_is_bf16, cp, B, ctx_len, sp, D, ex.stream);
-  if (rc) return rc;
+  if (!ex.dry) ex.rc = dmx_cast_pad_rows_launch(ctx, ctx_is_bf16, cp, n, ctx_len, sp, D, ex.stream);
+  if (ex.rc) return ex.rc;
   for (const XfW* x : u->xf_all) {
-    const bf16* kv = ctx_slot_ptr(u, cache, B, ctx_len, x->ctx_slot);
     // [K | V][b*sp + s][2C] = ctx [W_k ; W_v]^T   (padded context rows are zero -> finite K/V rows)
-    ex.gemm_raw(cp, D, B * sp, u->at<bf16>(x->wkv2), D, 2 * x->C, D, nullptr, (void*)kv, 2 * x->C, 0);
+    const bf16* kv = ex.dry ? nullptr : ctx_slot_ptr(u, cache, B, ctx_len, x->ctx_slot) + (size_t)row0 * sp * 2 * x->C;
+    ex.gemm_raw(cp, D, n * sp, ex.dry ? nullptr : u->at<bf16>(x->wkv2), D, 2 * x->C, D, nullptr, (void*)kv, 2 * x->C, 0);
     if (ex.rc) return ex.rc;
   }
   return ex.rc;
 }
 
-// the projection for n rows of a running batch: rows [row0, row0 + n) of every layer's [B*sp][2C] slab (row b is the contiguous
-// [sp][2C] block at b*sp).  The GEMM's M is n*sp and its output starts at row row0*sp: rows outside are not touched.
+extern "C" int dmx_unet_set_context(dmx_unet* u, const void* ctx, int ctx_is_bf16, int B, int ctx_len,
+                                    void* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
+  DMX_REQUIRE(u && u->finalized, "unet_set_context: weights not finalized");
+  DMX_REQUIRE(ctx && cache && cache_bytes >= dmx_unet_context_bytes(u, B, ctx_len), "unet_set_context: context cache too small");
+  Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes);
+  return project_context(u, ex, ctx, ctx_is_bf16, 0, B, B, ctx_len, cache);
+}
 extern "C" int dmx_unet_set_context_rows(dmx_unet* u, const void* ctx, int ctx_is_bf16, int row0, int n, int B, int ctx_len,
                                          void* cache, size_t cache_bytes, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(u && u->finalized, "unet_set_context_rows: weights not finalized");
@@ -231,17 +235,7 @@ extern "C" int dmx_unet_set_context_rows(dmx_unet* u, const void* ctx, int ctx_i
   DMX_REQUIRE(ctx_len >= 1, "unet_set_context_rows: ctx_len %d", ctx_len);
   DMX_REQUIRE(ctx && cache && cache_bytes >= dmx_unet_context_bytes(u, B, ctx_len), "unet_set_context_rows: context cache too small");
   Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes);
-  const int D = u->cfg.cross_attention_dim, sp = ctx_pad(ctx_len);
-  bf16* cp = (bf16*)ex.raw((size_t)n * sp * D * 2);
-  if (ex.rc) return ex.rc;
-  int rc = dmx_cast_pad_rows_launch(ctx, ctx_is_bf16, cp, n, ctx_len, sp, D, ex.stream);
-  if (rc) return rc;
-  for (const XfW* x : u->xf_all) {
-    const bf16* kv = ctx_slot_ptr(u, cache, B, ctx_len, x->ctx_slot) + (size_t)row0 * sp * 2 * x->C;
-    ex.gemm_raw(cp, D, n * sp, u->at<bf16>(x->wkv2), D, 2 * x->C, D, nullptr, (void*)kv, 2 * x->C, 0);
-    if (ex.rc) return ex.rc;
-  }
-  return ex.rc;
+  return project_context(u, ex, ctx, ctx_is_bf16, row0, n, B, ctx_len, cache);
 }
 
 // ----------------------------------------------------------------------------- forward
@@ -369,21 +363,18 @@ struct Fwd {
   }
 };
 
-// row *step of the precomputed time-embedding projection table -> the buffer every resnet's conv1 reads its row bias from
-__global__ __launch_bounds__(256) void dmx_temb_row_kernel(const float* table, const int* step, float* out, int n) {
-  const float* src = table + (size_t)(*step) * n;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) out[i] = src[i];
-}
-// per-row form: image b fetches row max(row_index[b], 0) (an idle row reads row 0: finite, ignored); the first thread of each image's first
-// block also writes that plan row's timestep into the forward's timesteps buffer
-__global__ __launch_bounds__(256) void dmx_temb_rows_kernel(const float* table, const dmx_sched_row_rec* plan, const int* row_index, float* out,
-                                                            long long* timesteps, int n) {
+// a row of the precomputed time-embedding projection table -> the buffer every resnet's conv1 reads its row bias from.  Grid (chunks, 1):
+// the scalar form, row index[0] into row 0 (every image reads it with row stride 0).  Grid (chunks, B) with a plan: image b fetches row
+// max(index[b], 0) (an idle row reads row 0: finite, ignored) and the first thread of each image's first block writes that plan row's
+// timestep into the forward's timesteps buffer.
+__global__ __launch_bounds__(256) void dmx_temb_fetch_kernel(const float* table, const int* index, const dmx_sched_row_rec* plan, float* out,
+                                                             long long* timesteps, int n) {
   const int b = blockIdx.y;
-  int idx = row_index[b]; if (idx < 0) idx = 0;
+  int idx = index[b]; if (plan && idx < 0) idx = 0;
   const float* src = table + (size_t)idx * n;
   float* dst = out + (size_t)b * n;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) dst[i] = src[i];
-  if (blockIdx.x == 0 && threadIdx.x == 0) timesteps[b] = (long long)plan[idx].timestep;
+  if (plan && blockIdx.x == 0 && threadIdx.x == 0) timesteps[b] = (long long)plan[idx].timestep;
 }
 
 }  // namespace
@@ -417,16 +408,17 @@ extern "C" int dmx_unet_temb_table(dmx_unet* u, const int64_t* timesteps, int T,
   Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes);
   return temb_table_run(u, ex, (const long long*)timesteps, T, table);
 }
+// each setter fills the one source; its all-NULL call clears it only while it holds that setter's own form
 extern "C" int dmx_unet_use_temb_table(dmx_unet* u, const float* table, const int* step_index) {
   DMX_REQUIRE(u != nullptr, "unet_use_temb_table: null handle");
   DMX_REQUIRE((table == nullptr) == (step_index == nullptr), "unet_use_temb_table: table and step index go together");
-  u->temb_table = table; u->temb_step = step_index;
+  if (table || !u->temb.plan) u->temb = {table, step_index, nullptr};
   return DMX_OK;
 }
 extern "C" int dmx_unet_use_temb_table_rows(dmx_unet* u, const float* table, const dmx_sched_row_rec* plan, const int* row_index) {
   DMX_REQUIRE(u != nullptr, "unet_use_temb_table_rows: null handle");
   DMX_REQUIRE((table == nullptr) == (row_index == nullptr) && (table == nullptr) == (plan == nullptr), "unet_use_temb_table_rows: table, plan and row index go together");
-  u->temb_rows_table = table; u->temb_rows_plan = plan; u->temb_rows_index = row_index;
+  if (table || u->temb.plan) u->temb = {table, row_index, plan};
   return DMX_OK;
 }
 
@@ -492,15 +484,13 @@ int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c) {
     ex.drop(x9);
   } else {
     if (!ex.dry && !ex.rc) {
-      if (u->temb_rows_table && t_count == B) {
-        // in-flight batching: every image on its own step - row row_index[b] of the plans' table, and timesteps[b] from the plan
-        hipLaunchKernelGGL(dmx_temb_rows_kernel, dim3(cdiv(u->tproj_total, 1024), B), dim3(256), 0, ex.stream, u->temb_rows_table, u->temb_rows_plan,
-                           u->temb_rows_index, tproj, const_cast<long long*>(c.timesteps), u->tproj_total);
-        ex.rc = dmx_check_launch("dmx_temb_rows_kernel");
-      } else if (u->temb_table && t_count == 1) {
-        // the loop computed the projections of all its timesteps in one batched pass (dmx_unet_temb_table): fetch this step's row
-        hipLaunchKernelGGL(dmx_temb_row_kernel, dim3(cdiv(u->tproj_total, 1024)), dim3(256), 0, ex.stream, u->temb_table, u->temb_step, tproj, u->tproj_total);
-        ex.rc = dmx_check_launch("dmx_temb_row_kernel");
+      // a table of the loop's timesteps (dmx_unet_temb_table): the per-row form serves per-image timesteps (in-flight batching: every image
+      // on its own step, timesteps[b] from the plan), the scalar form a scalar timestep; any other call computes its rows
+      const dmx_unet::TembSource& ts = u->temb;
+      if (ts.table && t_count == (ts.plan ? B : 1)) {
+        hipLaunchKernelGGL(dmx_temb_fetch_kernel, dim3(cdiv(u->tproj_total, 1024), ts.plan ? B : 1), dim3(256), 0, ex.stream, ts.table, ts.index,
+                           ts.plan, tproj, const_cast<long long*>(c.timesteps), u->tproj_total);
+        ex.rc = dmx_check_launch("dmx_temb_fetch_kernel");
       } else {
         temb_rows(u, ex, c.timesteps, t_count, Bt, te, tproj);
       }
@@ -618,10 +608,7 @@ extern "C" size_t dmx_unet_workspace_bytes(dmx_unet* u, int B, int H, int W, int
   size_t need = ex.ws.peak();
   // set_context needs the padded context + split-K scratch
   Exec e2 = Exec::dry_run();
-  const int D = u->cfg.cross_attention_dim, sp = ctx_pad(ctx_len);
-  void* cp = e2.raw((size_t)B * sp * D * 2);
-  for (const XfW* x : u->xf_all)
-    e2.gemm_raw((const bf16*)cp, D, B * sp, nullptr, D, 2 * x->C, D, nullptr, nullptr, 2 * x->C, 0);
+  project_context(u, e2, nullptr, 0, 0, B, B, ctx_len, nullptr);
   if (e2.ws.peak() > need) need = e2.ws.peak();
   return need + 4096;
 }

@@ -39,24 +39,22 @@ struct dmx_unet : ModelBase {
   std::vector<XfW*> xf_all;          // cross-attention layers in graph order (context cache slots)
   std::vector<TrJob> tr_cache;       // the transpose job table dmx_unet_train_prepare uploaded last (kernels.h TrBatch)
   std::shared_ptr<void> train_state;   // live training pass (unet_train.hip)
-  // optional source of the time-embedding projections (dmx_unet_use_temb_table): row *temb_step of a table computed for all
-  // timesteps of a denoise loop in one batched pass, instead of four small launches per step
-  const float* temb_table = nullptr; const int* temb_step = nullptr;
-  // per-row form (dmx_unet_use_temb_table_rows): row row_index[b] of `temb_rows_table` for image b, timesteps[b] from the plan record
-  const float* temb_rows_table = nullptr; const dmx_sched_row_rec* temb_rows_plan = nullptr; const int* temb_rows_index = nullptr;
+  // optional source of the time-embedding projections: rows of a table computed for all timesteps of a loop in one batched pass, instead of
+  // four small launches per step.  Scalar form (dmx_unet_use_temb_table; plan == nullptr): row index[0] for every image.  Per-row form
+  // (dmx_unet_use_temb_table_rows): row index[b] for image b, timesteps[b] from the plan record.
+  struct TembSource { const float* table = nullptr; const int* index = nullptr; const dmx_sched_row_rec* plan = nullptr; } temb;
   // hipGraph cache: one captured UNet step per distinct call (pointers are baked into the nodes).  The key is everything the captured
-  // launches depend on: the call record, the workspace, the time-embedding table (scalar or per-row form) and dmx_plan_epoch() (every dmx_set_* switch changes
-  // the plans baked into the graph)
+  // launches depend on: the call record, the workspace, the time-embedding source (its plan pointer tells the two forms apart) and
+  // dmx_plan_epoch() (every dmx_set_* switch changes the plans baked into the graph)
   struct GraphKey {
     const void *f0, *f1, *f2, *timesteps, *ctx, *out, *workspace; int c0, c1, c2, t_count, ctx_len, B, H, W;
-    const void *temb_table, *temb_step, *temb_rows_table, *temb_rows_plan, *temb_rows_index; int plan_epoch;
-    auto tie() const { return std::tie(f0, f1, f2, timesteps, ctx, out, workspace, c0, c1, c2, t_count, ctx_len, B, H, W, temb_table, temb_step, temb_rows_table, temb_rows_plan,
-                                       temb_rows_index, plan_epoch); }
+    const void *temb_table, *temb_index, *temb_plan; int plan_epoch;
+    auto tie() const { return std::tie(f0, f1, f2, timesteps, ctx, out, workspace, c0, c1, c2, t_count, ctx_len, B, H, W, temb_table, temb_index, temb_plan, plan_epoch); }
     bool operator<(const GraphKey& o) const { return tie() < o.tie(); }
   };
   GraphKey graph_key(const UNetCall& c, const void* workspace) const {
     return GraphKey{c.f0, c.f1, c.f2, c.timesteps, c.ctx, c.out, workspace, c.c0, c.c1, c.c2, c.t_count, c.ctx_len, c.B, c.H, c.W,
-                    temb_table, temb_step, temb_rows_table, temb_rows_plan, temb_rows_index, dmx_plan_epoch()};
+                    temb.table, temb.index, temb.plan, dmx_plan_epoch()};
   }
   struct GraphEntry { hipGraphExec_t exec = nullptr; int seen = 0; };
   std::map<GraphKey, GraphEntry> graphs;

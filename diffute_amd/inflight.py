@@ -4,19 +4,17 @@
 steps.  `DenoiseEngine` keeps a batch of `capacity` rows running: a request (one or several rows sharing a step count) takes free rows
 whenever they come up, runs ITS `num_inference_steps` ticks and leaves, while the other rows are mid-loop.  One tick is one UNet forward
 over all rows (`dmx_unet_forward` with per-row timesteps: each row fetches its own row of the time-embedding table), one per-row
-scheduler launch (`dmx_sched_step_rows`) and one `dmx_rows_advance`.  Which step a row is on lives in two device ints per row
-(`row_index`, `row_left`) at fixed addresses, so one captured graph serves every tick; the host mirrors that arithmetic (`Planner`) and
-never reads it back.
+scheduler launch (`dmx_sched_step_rows`, over the records of `scheduler.plan()` - the ones `denoise()` runs one at a time) and one
+`dmx_rows_advance`.  Which step a row is on lives in two device ints per row (`row_index`, `row_left`) at fixed addresses, so one captured
+graph serves every tick; the host mirrors that arithmetic (`Planner`) and never reads it back.
 
 `Planner`, `plan_records` and the queue are plain Python (no device calls): tests/test_inflight_host.py drives them without a GPU.
 """
-import ctypes
 from collections import deque
 
 import torch
 
 from . import _cabi
-from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
 
 
 # ----------------------------------------------------------------------------------------------------------------- host planner
@@ -110,41 +108,19 @@ class Planner:
 
 
 def scheduler_kind(scheduler):
-    if isinstance(scheduler, DPMSolverMultistepScheduler):
-        return _cabi.SCHED_DPMPP
-    if isinstance(scheduler, DDIMScheduler):
-        return _cabi.SCHED_DDIM
-    if isinstance(scheduler, DDPMScheduler):
-        return _cabi.SCHED_DDPM
-    raise TypeError(f"DenoiseEngine: no per-row step for {type(scheduler).__name__}")
+    kind = getattr(scheduler, "kind", None)
+    if kind is None:
+        raise TypeError(f"DenoiseEngine: no per-row step for {type(scheduler).__name__}")
+    return kind
 
 
 def plan_records(scheduler, num_inference_steps, eta=0.0):
-    """The plan of one step count: scheduler.set_timesteps(num_inference_steps) (pass a PRIVATE scheduler: it is mutated), then one
-    _cabi.SchedRowRec per step holding what denoise()'s loop reads for that step - step_coefficients(t[, eta]) for DDIM / DDPM, the
-    (order, dmx_dpm_coefs) of DPMSolverMultistepScheduler._plan - plus use_noise (DDIM: eta > 0, DDPM: t > 0), the history-ring
-    positions i % k, (i-1) % k, (i-2) % k (k = solver_order; 0 for the others) and the timestep.  -> (timesteps, records); DPM-Solver++
-    may return fewer steps than asked (its grid is deduplicated)."""
-    kind = scheduler_kind(scheduler)
+    """The plan of one step count: scheduler.set_timesteps(num_inference_steps) (pass a PRIVATE scheduler: it is mutated), then
+    scheduler.plan(eta) - the records denoise()'s loop reads, one per step.  -> (timesteps, records); DPM-Solver++ may return fewer steps
+    than asked (its grid is deduplicated)."""
+    scheduler_kind(scheduler)
     scheduler.set_timesteps(int(num_inference_steps))
-    ts = [int(t) for t in scheduler.timesteps]
-    recs = []
-    for i, t in enumerate(ts):
-        r = _cabi.SchedRowRec()
-        r.timestep = t
-        if kind == _cabi.SCHED_DPMPP:
-            order, c = scheduler._plan[i]
-            k = int(scheduler.config.solver_order)
-            r.order = int(order)
-            ctypes.memmove(ctypes.byref(r.dpm), ctypes.byref(c), ctypes.sizeof(_cabi.DpmCoefs))
-            r.ring_w, r.ring_m1, r.ring_m2 = i % k, (i - 1) % k, (i - 2) % k
-        else:
-            coefs = scheduler.step_coefficients(t, eta) if kind == _cabi.SCHED_DDIM else scheduler.step_coefficients(t)
-            for j, v in enumerate(coefs):
-                r.c[j] = v
-            r.use_noise = int(eta > 0) if kind == _cabi.SCHED_DDIM else int(t > 0)
-        recs.append(r)
-    return ts, recs
+    return [int(t) for t in scheduler.timesteps], scheduler.plan(eta)
 
 
 # ----------------------------------------------------------------------------------------------------------------- the engine

@@ -458,21 +458,26 @@ class UNet2DConditionModel(_HipModel):
         return sl
 
     # ---- glyph-context K/V cache (constant across denoise steps, app.ipynb:776,814)
-    def set_context(self, encoder_hidden_states, slot=0):
+    def _context_input(self, encoder_hidden_states, slot):
+        """the common preamble of set_context / set_context_rows -> (slot record, the context as the library takes it: fp32 or the compute
+        dtype, contiguous [n, S, cross_attention_dim], n, S)"""
         self._ensure_packed()
-        sl = self._slot(slot)
         ctx = encoder_hidden_states
         _cabi.require_cuda(ctx)
         if ctx.dtype not in (torch.float32, self.compute_dtype):
             ctx = ctx.to(torch.float32)
         ctx = ctx.contiguous()
-        B, S, D = ctx.shape
+        n, S, D = ctx.shape
         if D != self.config.cross_attention_dim:
             raise ValueError(f"encoder_hidden_states last dim {D} != cross_attention_dim {self.config.cross_attention_dim}")
-        lib = self._lib
-        nb = lib.dmx_unet_context_bytes(self._h, B, S)
+        return self._slot(slot), ctx, n, S
+
+    def set_context(self, encoder_hidden_states, slot=0):
+        sl, ctx, B, S = self._context_input(encoder_hidden_states, slot)
+        nb = self._lib.dmx_unet_context_bytes(self._h, B, S)
         if sl["ctx_cache"] is None or sl["ctx_cache"].numel() < nb or sl["ctx_cache"].device != ctx.device:
             sl["ctx_cache"] = torch.empty(nb, dtype=torch.uint8, device=ctx.device)
+        lib = self._lib
         ws = self._grown(sl, "ws", lib.dmx_unet_workspace_bytes(self._h, B, 8, 8, S))
         _cabi.check(lib.dmx_unet_set_context(self._h, _cabi.ptr(ctx), int(ctx.dtype == self.compute_dtype), B, S,
                                              _cabi.ptr(sl["ctx_cache"]), sl["ctx_cache"].numel(),
@@ -496,16 +501,7 @@ class UNet2DConditionModel(_HipModel):
         """set_context() for rows [row0, row0 + n) of the slot's cache (n = encoder_hidden_states.shape[0]) while the other rows keep their
         K/V: the slot must hold a cache for at least row0 + n rows of the same context length (set_context / reserve_context).  With
         row0 = 0 and n = the cache's rows this writes the bytes set_context writes."""
-        self._ensure_packed()
-        sl = self._slot(slot)
-        ctx = encoder_hidden_states
-        _cabi.require_cuda(ctx)
-        if ctx.dtype not in (torch.float32, self.compute_dtype):
-            ctx = ctx.to(torch.float32)
-        ctx = ctx.contiguous()
-        n, S, D = ctx.shape
-        if D != self.config.cross_attention_dim:
-            raise ValueError(f"encoder_hidden_states last dim {D} != cross_attention_dim {self.config.cross_attention_dim}")
+        sl, ctx, n, S = self._context_input(encoder_hidden_states, slot)
         if sl["ctx_key"] is None or sl["ctx_key"][2] != self._epoch:
             raise RuntimeError("UNet2DConditionModel: set_context_rows() needs a cache made by set_context() / reserve_context() on this slot")
         B, S0 = sl["ctx_shape"]
@@ -533,6 +529,17 @@ class UNet2DConditionModel(_HipModel):
                                             _cabi.current_stream()), "unet_temb_table")
         return table.view(T, -1)
 
+    def _use_temb(self, temb, on):
+        """point the handle's time-embedding source at `temb` - (table, step index) or, per row, (table, row index, plan) - or clear that form"""
+        lib = self._lib
+        ptr = _cabi.ptr if on else (lambda t: None)
+        if len(temb) == 3:
+            rc, what = lib.dmx_unet_use_temb_table_rows(self._h, ptr(temb[0]), ptr(temb[2]), ptr(temb[1])), "unet_use_temb_table_rows"
+        else:
+            rc, what = lib.dmx_unet_use_temb_table(self._h, ptr(temb[0]), ptr(temb[1])), "unet_use_temb_table"
+        if on:
+            _cabi.check(rc, what)
+
     def forward_parts(self, parts, timesteps_dev, out=None, graph=False, slot=0, temb=None):
         """Hot-loop entry: `parts` = list of (NCHW fp32 cuda tensor) whose channels sum to in_channels
         (fuses the torch.cat of app.ipynb:811); timesteps_dev = int64 cuda tensor [1] or [B];
@@ -556,23 +563,18 @@ class UNet2DConditionModel(_HipModel):
             sl["ws_need"] = (key, lib.dmx_unet_workspace_bytes(self._h, B, H, W, sl["ctx_shape"][1]))
         ws = self._grown(sl, "ws", sl["ws_need"][1])
         fwd = lib.dmx_unet_forward_graph if graph else lib.dmx_unet_forward
-        rows = temb is not None and len(temb) == 3
-        if rows:
-            if temb[1].numel() != B or timesteps_dev.numel() != B or temb[1].dtype != torch.int32:
-                raise ValueError(f"forward_parts: the per-row temb form needs an int32 row index and timesteps of {B} entries each")
-            _cabi.check(lib.dmx_unet_use_temb_table_rows(self._h, _cabi.ptr(temb[0]), _cabi.ptr(temb[2]), _cabi.ptr(temb[1])), "unet_use_temb_table_rows")
-        elif temb is not None:
-            _cabi.check(lib.dmx_unet_use_temb_table(self._h, _cabi.ptr(temb[0]), _cabi.ptr(temb[1])), "unet_use_temb_table")
+        if temb is not None and len(temb) == 3 and (temb[1].numel() != B or timesteps_dev.numel() != B or temb[1].dtype != torch.int32):
+            raise ValueError(f"forward_parts: the per-row temb form needs an int32 row index and timesteps of {B} entries each")
+        if temb is not None:
+            self._use_temb(temb, True)
         try:
             _cabi.check(fwd(self._h, _cabi.ptr(ps[0][0]), ps[0][1], _cabi.ptr(ps[1][0]), ps[1][1],
                             _cabi.ptr(ps[2][0]), ps[2][1], _cabi.ptr(timesteps_dev), timesteps_dev.numel(),
                             _cabi.ptr(sl["ctx_cache"]), sl["ctx_shape"][1], _cabi.ptr(out), B, H, W,
                             _cabi.ptr(ws), ws.numel(), _cabi.current_stream()), "unet_forward")
         finally:
-            if rows:
-                lib.dmx_unet_use_temb_table_rows(self._h, None, None, None)
-            elif temb is not None:
-                lib.dmx_unet_use_temb_table(self._h, None, None)
+            if temb is not None:
+                self._use_temb(temb, False)
         return out
 
     # ---- validation / debugging (tests only): per-block taps of the product path, and the fp32 instantiation of the graph

@@ -1,16 +1,19 @@
 """The reference's denoise loop (app.ipynb:796-816) driven through the C-ABI.
 
 `denoise()` is the hot path BASELINE.json names: per step one `dmx_unet_forward` (which fuses
-torch.cat([latents, mask, masked_image_latents], 1)) and one scheduler-step kernel (DDPM, DDIM or
-DPM-Solver++; the latter keeps its multistep history in fixed per-chain buffers).  The glyph
-context K/V are projected once per image, timesteps live on the device, nothing synchronises
-with the host inside the loop.
+torch.cat([latents, mask, masked_image_latents], 1)) and one scheduler-step kernel.  What a step is
+comes from the scheduler's plan (`scheduler.iter_plan(eta)`, the records of `plan(eta)` one at a time) -
+one record per step with the scalars, whether noise is added and,
+for DPM-Solver++, the slots of the per-chain history ring it writes and reads - and goes to the kernel
+through `schedulers.launch_step`; the loop knows nothing else about the scheduler.  The glyph context
+K/V are projected once per image, timesteps live on the device, nothing synchronises with the host
+inside the loop.
 """
 import numpy as np
 import torch
 
 from . import _cabi, prepost
-from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
+from .schedulers import launch_step
 
 
 _SIDE = {}
@@ -34,48 +37,36 @@ def mask_to_latent(mask, vae_scale_factor=8):
 class _Run:
     """One micro-batch of the denoise loop: its own stream, UNet execution slot and fixed-address buffers."""
 
-    def __init__(self, unet, scheduler, latents, mask, mlat, ctx, slot, stream, use_graph, temb_table=None, n_hist=0):
-        self.unet, self.sched, self.slot, self.stream, self.use_graph = unet, scheduler, slot, stream, use_graph
-        self.temb_table = temb_table
+    def __init__(self, unet, scheduler, latents, mask, mlat, ctx, slot, stream, use_graph, ts_dev, temb_table, table_rows):
+        self.unet, self.slot, self.stream, self.use_graph = unet, slot, stream, use_graph
+        self.kind, self.vpred = scheduler.kind, int(scheduler.config.prediction_type == "v_prediction")
+        self.ts_dev, self.temb_table, self.table_rows = ts_dev, temb_table, table_rows
         with torch.cuda.stream(stream):
             self.x = (latents.to(torch.float32) * scheduler.init_noise_sigma).contiguous()      # app.ipynb:800
             self.m = mask.to(torch.float32).contiguous()
             self.ml = mlat.to(torch.float32).contiguous()
             self.eps = torch.empty_like(self.x)
-            # DPM-Solver++: the data predictions of the last solver_order steps; step i writes hist[i % n], reads hist[(i-1) % n], hist[(i-2) % n]
+            # DPM-Solver++: the ring of the data predictions of the last solver_order steps; a step's record names the slots it writes and reads
+            n_hist = scheduler.config.solver_order if self.kind == _cabi.SCHED_DPMPP else 0
             self.hist = [torch.empty_like(self.x) for _ in range(n_hist)]
             self.t_cur = torch.empty(1, dtype=torch.int64, device=self.x.device)   # fixed address: the captured graph reads it
             self.step_idx = torch.zeros(1, dtype=torch.int32, device=self.x.device)   # likewise: the row of temb_table this step fetches
             unet.set_context(ctx, slot=slot)
 
-    def step(self, i, t, ts_dev, coefs, noise, is_ddim, vpred):
-        lib = _cabi.lib()
+    def step(self, i, rec, noise):
         x, eps = self.x, self.eps
         with torch.cuda.stream(self.stream):
-            st = _cabi.current_stream()
             if self.temb_table is not None:
-                self.step_idx.copy_(ts_dev[1][i:i + 1], non_blocking=True)
+                self.step_idx.copy_(self.table_rows[i:i + 1], non_blocking=True)
                 self.unet.forward_parts([x, self.m, self.ml], self.t_cur, out=eps, graph=self.use_graph, slot=self.slot,
                                         temb=(self.temb_table, self.step_idx))
             else:
-                self.t_cur.copy_(ts_dev[0][i:i + 1], non_blocking=True)
+                self.t_cur.copy_(self.ts_dev[i:i + 1], non_blocking=True)
                 self.unet.forward_parts([x, self.m, self.ml], self.t_cur, out=eps, graph=self.use_graph, slot=self.slot)
             # the update is elementwise, so prev_sample overwrites the sample in place (stable pointers for the graph)
-            if self.hist:
-                order, c = coefs
-                k = len(self.hist)
-                m1 = self.hist[(i - 1) % k] if order >= 2 else None
-                m2 = self.hist[(i - 2) % k] if order >= 3 else None
-                _cabi.check(lib.dmx_sched_step_dpmpp(_cabi.ptr(x), _cabi.ptr(eps), _cabi.ptr(m1), _cabi.ptr(m2), _cabi.ptr(self.hist[i % k]),
-                                                     _cabi.ptr(x), x.numel(), order, c, vpred, st), "sched_step_dpmpp")
-            elif is_ddim:
-                sbt, sat, sap, dirc, std = coefs
-                _cabi.check(lib.dmx_sched_step_ddim(_cabi.ptr(x), _cabi.ptr(eps), _cabi.ptr(noise), _cabi.ptr(x), x.numel(),
-                                                    sbt, sat, sap, dirc, std, vpred, st), "sched_step_ddim")
-            else:
-                sbt, sat, c0, c1, sigma = coefs
-                _cabi.check(lib.dmx_sched_step_ddpm(_cabi.ptr(x), _cabi.ptr(eps), _cabi.ptr(noise), _cabi.ptr(x), x.numel(),
-                                                    sbt, sat, c0, c1, sigma, vpred, st), "sched_step_ddpm")
+            launch_step(self.kind, rec, x, eps, noise, self.hist[rec.ring_m1] if rec.order >= 2 else None,
+                        self.hist[rec.ring_m2] if rec.order >= 3 else None, self.hist[rec.ring_w] if self.hist else None, x, self.vpred,
+                        _cabi.current_stream())
 
 
 @torch.no_grad()
@@ -89,68 +80,54 @@ def denoise(unet, scheduler, latents, mask, masked_image_latents, encoder_hidden
     with its own captured graph: one chain's kernels fill the CUs the other chain's small / draining kernels
     leave idle.  Results are identical to micro_batches=1 up to per-kernel tile-plan rounding."""
     _cabi.require_cuda(latents, mask, masked_image_latents, encoder_hidden_states)
-    if isinstance(scheduler, DPMSolverMultistepScheduler) and (variance_noise is not None or eta != 0):
+    if scheduler.kind == _cabi.SCHED_DPMPP and (variance_noise is not None or eta != 0):
         raise ValueError("DPMSolverMultistepScheduler is deterministic: no variance_noise, eta = 0")
     _cabi.poll_device_error()            # what a kernel of an EARLIER pass raised (no sync; include/diffute_hip.h dmx_device_error)
     unet._ensure_packed()
     scheduler.set_timesteps(int(num_inference_steps))
-    ts_host = [int(t) for t in scheduler.timesteps]
     dev = latents.device
     ts_dev = scheduler.timesteps.to(device=dev, dtype=torch.int64).contiguous()
-    is_ddim = isinstance(scheduler, DDIMScheduler)
-    vpred = int(scheduler.config.prediction_type == "v_prediction")
     B = latents.shape[0]
     n = max(1, min(int(micro_batches), B))
     bounds = [(B * j // n, B * (j + 1) // n) for j in range(n)]
     main = torch.cuda.current_stream(dev)
     # the time-embedding MLP + every resnet's time_emb_proj depend on the timestep only: all steps' rows in one batched pass up
     # front (bit-identical rows), each step then fetches its row with one tiny launch instead of recomputing four small layers
-    temb_table = unet.temb_table(ts_dev) if (ts_host and TEMB_TABLE) else None
-    ts_dev = (ts_dev, torch.arange(len(ts_host), dtype=torch.int32, device=dev))
-    streams = _side_streams(dev, n)             # the loop runs on side streams: graph capture needs a non-default stream
+    temb_table = unet.temb_table(ts_dev) if (len(ts_dev) and TEMB_TABLE) else None
+    table_rows = torch.arange(len(ts_dev), dtype=torch.int32, device=dev)
+    streams = _side_streams(dev, n)[:n]         # the loop runs on side streams: graph capture needs a non-default stream
     # several chains at once share the CUs: plans whose blocks wait for co-resident peers are off while they are enqueued (the plans are
     # chosen - and baked into the captured graphs, which are keyed on the setting - at enqueue time)
     lib_ = unet._lib
     old_exclusive = lib_.dmx_set_exclusive_device(0) if n > 1 else None
     try:
-        return _denoise_enqueue(unet, scheduler, bounds, streams, main, n, latents, mask, masked_image_latents, encoder_hidden_states,
-                                ts_host, ts_dev, temb_table, is_ddim, vpred, eta, variance_noise, callback, use_graph)
+        runs = []
+        for j, (lo, hi) in enumerate(bounds):
+            streams[j].wait_stream(main)
+            runs.append(_Run(unet, scheduler, latents[lo:hi], mask[lo:hi], masked_image_latents[lo:hi],
+                             encoder_hidden_states[lo:hi].contiguous(), j, streams[j], use_graph, ts_dev, temb_table, table_rows))
+        # the plan, one record per step, is all the loop knows about the scheduler; it is walked lazily, so that the host computes a step's
+        # scalars while the GPU works through the steps already enqueued
+        for i, rec in enumerate(scheduler.iter_plan(eta)):
+            for (lo, hi), run in zip(bounds, runs):
+                nz = None
+                if rec.use_noise:
+                    with torch.cuda.stream(run.stream):
+                        nz = (variance_noise[i][lo:hi] if variance_noise is not None else torch.randn_like(run.x)).to(torch.float32).contiguous()
+                run.step(i, rec, nz)
+            if callback is not None:
+                for s_ in streams:
+                    main.wait_stream(s_)
+                callback(i, int(rec.timestep), runs[0].x if n == 1 else torch.cat([r.x for r in runs], 0),
+                         runs[0].eps if n == 1 else torch.cat([r.eps for r in runs], 0))
+                for s_ in streams:
+                    s_.wait_stream(main)            # the callback's reads finish before the next step overwrites x / eps
+        for s_ in streams:
+            main.wait_stream(s_)
+        return runs[0].x if n == 1 else torch.cat([r.x for r in runs], 0)
     finally:
         if old_exclusive is not None:
             lib_.dmx_set_exclusive_device(old_exclusive)
-
-
-def _denoise_enqueue(unet, scheduler, bounds, streams, main, n, latents, mask, masked_image_latents, encoder_hidden_states,
-                     ts_host, ts_dev, temb_table, is_ddim, vpred, eta, variance_noise, callback, use_graph):
-    runs = []
-    dpm = scheduler._plan if isinstance(scheduler, DPMSolverMultistepScheduler) else None
-    n_hist = scheduler.config.solver_order if dpm is not None else 0
-    for j, (lo, hi) in enumerate(bounds):
-        streams[j].wait_stream(main)
-        runs.append(_Run(unet, scheduler, latents[lo:hi], mask[lo:hi], masked_image_latents[lo:hi],
-                         encoder_hidden_states[lo:hi].contiguous(), j, streams[j], use_graph, temb_table, n_hist))
-    for i, t in enumerate(ts_host):
-        if dpm is not None:
-            coefs, need_noise = dpm[i], False
-        else:
-            coefs = scheduler.step_coefficients(t, eta) if is_ddim else scheduler.step_coefficients(t)
-            need_noise = (eta > 0) if is_ddim else (t > 0)
-        for j, (lo, hi) in enumerate(bounds):
-            nz = None
-            if need_noise:
-                with torch.cuda.stream(streams[j]):
-                    nz = (variance_noise[i][lo:hi] if variance_noise is not None else torch.randn_like(runs[j].x)).to(torch.float32).contiguous()
-            runs[j].step(i, t, ts_dev, coefs, nz, is_ddim, vpred)
-        if callback is not None:
-            for s_ in streams[:n]:
-                main.wait_stream(s_)
-            callback(i, t, runs[0].x if n == 1 else torch.cat([r.x for r in runs], 0),
-                     runs[0].eps if n == 1 else torch.cat([r.eps for r in runs], 0))
-            for s_ in streams[:n]:
-                s_.wait_stream(main)            # the callback's reads finish before the next step overwrites x / eps
-    for s_ in streams[:n]:
-        main.wait_stream(s_)
-    return runs[0].x if n == 1 else torch.cat([r.x for r in runs], 0)
 
 
 @torch.no_grad()

@@ -9,6 +9,10 @@
 Host logic (tables, integer timestep grids, the scalar coefficients of a step) is Python/torch,
 written with the same tensor expressions as diffusers >=0.15 so it rounds identically on the same
 machine; the elementwise update over the latents is a gfx950 kernel behind the C-ABI.
+
+One step is one `_cabi.SchedRowRec` (`scheduler.plan(eta)`: the scalars, whether noise is added, the DPM-Solver++ history-ring
+slots, the timestep).  The three `step()` methods, `pipeline.denoise()` and the in-flight engine (`inflight.py`) all read that
+record; `launch_step` hands one to the scalar entry of its scheduler kind.
 """
 import json
 import os
@@ -29,6 +33,19 @@ class SchedulerOutput(SimpleNamespace):
     """`.prev_sample` (app.ipynb:816)."""
 
 
+def launch_step(kind, rec, x, eps, noise, m1, m2, x0_out, out, vpred, stream):
+    """One scalar scheduler step over fp32 CUDA tensors from its record: `kind` is the scheduler's (_cabi.SCHED_*), `out` may be `x`.
+    DDIM / DDPM read rec.c and add the noise term when `noise` is given; DPM-Solver++ reads rec.order / rec.dpm, the previous data
+    predictions m1 / m2 (None where the order does not read them) and writes this step's into x0_out."""
+    lib, P = _cabi.lib(), _cabi.ptr
+    if kind == _cabi.SCHED_DPMPP:
+        rc = lib.dmx_sched_step_dpmpp(P(x), P(eps), P(m1), P(m2), P(x0_out), P(out), x.numel(), rec.order, rec.dpm, vpred, stream)
+    else:
+        fn = lib.dmx_sched_step_ddim if kind == _cabi.SCHED_DDIM else lib.dmx_sched_step_ddpm
+        rc = fn(P(x), P(eps), P(noise), P(out), x.numel(), *rec.c, vpred, stream)
+    _cabi.check(rc, ("sched_step_ddim", "sched_step_ddpm", "sched_step_dpmpp")[kind])
+
+
 class _Config(SimpleNamespace):
     def __getitem__(self, k):
         return getattr(self, k)
@@ -36,6 +53,7 @@ class _Config(SimpleNamespace):
 
 class _SchedulerBase:
     order = 1
+    kind = None                                  # _cabi.SCHED_*: which step kernel runs this class's records
     _config_defaults = SD2_SCHEDULER_CONFIG      # the class's own defaults; their keys (+ "thresholding") are what from_pretrained / from_config keep
 
     def __init__(self, **config):
@@ -151,6 +169,34 @@ class _SchedulerBase:
     def _t_int(timestep):
         return int(timestep.item()) if torch.is_tensor(timestep) else int(timestep)
 
+    def plan(self, eta=0.0):
+        """One _cabi.SchedRowRec per step of the current grid (set_timesteps first): what the step kernels read for that step."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        return list(self.iter_plan(eta))
+
+    def iter_plan(self, eta=0.0):
+        """plan(eta) one record at a time, each built when it is asked for: a loop that enqueues step i before it asks for step i + 1 computes
+        the scalars (0-d torch expressions, about 0.1 ms of host time per step) behind the GPU work it has queued, not in front of it"""
+        for i, t in enumerate(self.timesteps.tolist()):
+            yield self._record(t, eta, i)
+
+    def _step(self, rec, model_output, sample, generator, variance_noise, return_dict):
+        """step() of DDIM / DDPM from the step's record"""
+        x = sample.to(torch.float32).contiguous(); eps = model_output.to(torch.float32).contiguous()
+        noise = None
+        if rec.use_noise:
+            if variance_noise is None:      # the reference passes no generator: device RNG (app.ipynb:816)
+                variance_noise = torch.randn(x.shape, generator=generator, device=x.device, dtype=torch.float32)
+            noise = variance_noise.to(torch.float32).contiguous()
+        out = torch.empty_like(x)
+        launch_step(self.kind, rec, x, eps, noise, None, None, None, out, self._vpred(), _cabi.current_stream())
+        out = out.to(sample.dtype)
+        return SchedulerOutput(prev_sample=out) if return_dict else (out,)
+
+    def _vpred(self):
+        return int(self.config.prediction_type == "v_prediction")
+
 
 class DDPMScheduler(_SchedulerBase):
     """The scheduler the reference instantiates (app.ipynb:545, train_diffute_v1.py:628).
@@ -160,6 +206,7 @@ class DDPMScheduler(_SchedulerBase):
     grid ends at timestep 0), while DDIMScheduler does.  Later diffusers releases apply the offset to DDPM as well.  The SD2
     `scheduler_config.json` carries `steps_offset: 1`; the key is kept in `.config` (round trip through save_pretrained) and a
     warning says once per process that the DDPM grid ignores it."""
+    kind = _cabi.SCHED_DDPM
     _warned_offset = False
 
     def __init__(self, **config):
@@ -197,26 +244,20 @@ class DDPMScheduler(_SchedulerBase):
             sigma = variance ** 0.5
         return (float(beta_prod_t ** 0.5), float(alpha_prod_t ** 0.5), float(c0), float(c1), float(sigma))
 
+    def _record(self, t, eta=0.0, i=None):
+        r = _cabi.SchedRowRec(timestep=t, use_noise=int(t > 0))
+        r.c[:] = self.step_coefficients(t)
+        return r
+
     def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True):
         _cabi.require_cuda(model_output, sample)
-        t = self._t_int(timestep)
-        sbt, sat, c0, c1, sigma = self.step_coefficients(t)
-        x = sample.to(torch.float32).contiguous(); eps = model_output.to(torch.float32).contiguous()
-        noise = None
-        if t > 0:
-            if variance_noise is None:      # the reference passes no generator: device RNG (app.ipynb:816)
-                variance_noise = torch.randn(x.shape, generator=generator, device=x.device, dtype=torch.float32)
-            noise = variance_noise.to(torch.float32).contiguous()
-        out = torch.empty_like(x)
-        _cabi.check(_cabi.lib().dmx_sched_step_ddpm(_cabi.ptr(x), _cabi.ptr(eps), _cabi.ptr(noise), _cabi.ptr(out), x.numel(),
-                                                    sbt, sat, c0, c1, sigma, int(self.config.prediction_type == "v_prediction"),
-                                                    _cabi.current_stream()), "sched_step_ddpm")
-        out = out.to(sample.dtype)
-        return SchedulerOutput(prev_sample=out) if return_dict else (out,)
+        rec = self._record(self._t_int(timestep))
+        return self._step(rec, model_output, sample, generator, variance_noise, return_dict)
 
 
 class DDIMScheduler(_SchedulerBase):
     """Named by BASELINE.json's north_star (deterministic eta=0 sampler); same surface as DDPM."""
+    kind = _cabi.SCHED_DDIM
 
     def __init__(self, **config):
         super().__init__(**config)
@@ -245,21 +286,15 @@ class DDIMScheduler(_SchedulerBase):
         return (float(beta_prod_t ** 0.5), float(alpha_prod_t ** 0.5), float(alpha_prod_t_prev ** 0.5),
                 float(dir_coef), float(std_dev_t))
 
+    def _record(self, t, eta=0.0, i=None):
+        r = _cabi.SchedRowRec(timestep=t, use_noise=int(eta > 0))
+        r.c[:] = self.step_coefficients(t, eta)
+        return r
+
     def step(self, model_output, timestep, sample, eta=0.0, generator=None, variance_noise=None, return_dict=True):
         _cabi.require_cuda(model_output, sample)
-        sbt, sat, sap, dirc, std = self.step_coefficients(timestep, eta)
-        x = sample.to(torch.float32).contiguous(); eps = model_output.to(torch.float32).contiguous()
-        noise = None
-        if eta > 0:
-            if variance_noise is None:
-                variance_noise = torch.randn(x.shape, generator=generator, device=x.device, dtype=torch.float32)
-            noise = variance_noise.to(torch.float32).contiguous()
-        out = torch.empty_like(x)
-        _cabi.check(_cabi.lib().dmx_sched_step_ddim(_cabi.ptr(x), _cabi.ptr(eps), _cabi.ptr(noise), _cabi.ptr(out), x.numel(),
-                                                    sbt, sat, sap, dirc, std, int(self.config.prediction_type == "v_prediction"),
-                                                    _cabi.current_stream()), "sched_step_ddim")
-        out = out.to(sample.dtype)
-        return SchedulerOutput(prev_sample=out) if return_dict else (out,)
+        rec = self._record(self._t_int(timestep), eta)
+        return self._step(rec, model_output, sample, generator, variance_noise, return_dict)
 
 
 DPM_SOLVER_CONFIG = dict(
@@ -274,13 +309,14 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
     prediction_type as SD2_SCHEDULER_CONFIG; the grid defaults to "linspace" (diffusers' default for this class).
 
     The scalars of every step (order plus the parenthesised 0-d fp32 expressions of diffusers' update) are computed on the host
-    once per set_timesteps (step_plan()); the elementwise update - data prediction m0, the multistep combination with the
-    previous m0's - is one kernel (dmx_sched_step_dpmpp).  step() keeps the m0 history itself, as diffusers does, so the
+    once per set_timesteps (plan() / step_plan()); the elementwise update - data prediction m0, the multistep combination with
+    the previous m0's - is one kernel (launch_step).  step() keeps the m0 history itself, as diffusers does, so the
     reference-shaped loop works unchanged; denoise() keeps its own fixed buffers instead.
 
     Refused (NotImplementedError): thresholding, algorithm_type other than "dpmsolver++", Karras / Lu sigmas, "trailing" spacing,
     clip_sample, euler_at_final=True and any final_sigmas_type but "sigma_min" (the last step lands on timestep 0 - diffusers'
     "zero" would land on sigma = 0).  The solver is deterministic: no noise, no eta."""
+    kind = _cabi.SCHED_DPMPP
     _config_defaults = DPM_SOLVER_CONFIG
 
     def __init__(self, **config):
@@ -388,6 +424,13 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
             plan.append((o, {k: float(v) for k, v in c.items()}))
         return plan
 
+    def _record(self, t, eta, i):
+        """step i of the grid: its order and coefficients, the history slots it writes (i % k) and reads ((i-1) % k, (i-2) % k); the solver is
+        deterministic, eta plays no part"""
+        k = int(self.config.solver_order)
+        order, c = self._plan[i]
+        return _cabi.SchedRowRec(dpm=c, order=order, ring_w=i % k, ring_m1=(i - 1) % k, ring_m2=(i - 2) % k, timestep=t)
+
     def step_plan(self):
         """[(order, {coefficient: float})] of every step of the current grid - what step() and denoise() hand to the kernel."""
         if self.num_inference_steps is None:
@@ -407,14 +450,12 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         if i >= len(self._ts) or int(self._ts[i]) != t:
             raise ValueError(f"step(): timestep {t} is not the next step of the grid (a multistep solver takes its steps in order; "
                              "call set_timesteps to start over)")
-        order, coefs = self._plan[i]
+        rec = self._record(t, 0.0, i)
         x = sample.to(torch.float32).contiguous(); e = model_output.to(torch.float32).contiguous()
-        m1 = self._history[-1] if order >= 2 else None
-        m2 = self._history[-2] if order >= 3 else None
+        m1 = self._history[-1] if rec.order >= 2 else None
+        m2 = self._history[-2] if rec.order >= 3 else None
         x0 = torch.empty_like(x); out = torch.empty_like(x)
-        _cabi.check(_cabi.lib().dmx_sched_step_dpmpp(_cabi.ptr(x), _cabi.ptr(e), _cabi.ptr(m1), _cabi.ptr(m2), _cabi.ptr(x0), _cabi.ptr(out),
-                                                     x.numel(), order, coefs, int(self.config.prediction_type == "v_prediction"),
-                                                     _cabi.current_stream()), "sched_step_dpmpp")
+        launch_step(self.kind, rec, x, e, None, m1, m2, x0, out, self._vpred(), _cabi.current_stream())
         k = self.config.solver_order
         self._history = (self._history + [x0])[1 - k:] if k > 1 else []
         self._step_index = i + 1

@@ -545,7 +545,8 @@ int dmx_unet_use_temb_table(dmx_unet* u, const float* table, const int* step_ind
 /* Per-row form (in-flight batching): with (table, plan, row_index) set, a forward with t_count == B fetches
  * tproj[b] = table[max(row_index[b], 0)] with one launch, which also WRITES timesteps[b] = plan[max(row_index[b], 0)].timestep into the
  * forward's `timesteps` argument (it stays truthful; the buffer must be writable).  `table` and `plan` share their row numbering;
- * row_index is int [B] on the device.  All three NULL switches back.  Takes precedence over the scalar form when both are set. */
+ * row_index is int [B] on the device.  All three NULL switches back.  A handle holds ONE table source: setting either form replaces
+ * the other, and the all-NULL call of a form clears the source only while it holds that form. */
 int dmx_unet_use_temb_table_rows(dmx_unet* u, const float* table, const dmx_sched_row_rec* plan, const int* row_index);
 /* Same as dmx_unet_forward; the launch sequence is captured into a hipGraph the second time an identical argument
  * tuple is seen and replayed afterwards.  Requires a non-NULL stream (falls back to eager launches otherwise). */

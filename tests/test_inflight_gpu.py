@@ -1,7 +1,10 @@
 """In-flight batching on the GPU (diffute_amd/inflight.py, include/diffute_hip.h "in-flight batching"): the per-row scheduler launch
 against the scalar entries, the admit / advance counters against the planner's mirror, the per-row time-embedding fetch, the row-wise
-context projection, and the engine against denoise() and the oracle goldens."""
+context projection, and the engine against denoise() and the oracle goldens.  The two loops share one step plan, one step kernel body, one
+context projection and one time-embedding fetch, so the shared pieces are pinned on their own as well (sections 9-12): the scalar step
+entries against the CPU restatement, denoise()'s C calls, the workspace query, and the scalar form of the time-embedding fetch."""
 import ctypes
+import functools
 import os
 
 import numpy as np
@@ -44,11 +47,11 @@ def _copy_rec(r):
 
 
 # ------------------------------------------------------------------------------------------------ 1. dmx_sched_step_rows
-def _guarded(n, offset, dev, gen):
-    """n floats of seeded data inside sentinel guard bands, `offset` floats past a 16-byte boundary -> (whole buffer, view)"""
+def _guarded(n, offset, dev, gen, data=None):
+    """n floats of seeded data (or of `data`) inside sentinel guard bands, `offset` floats past a 16-byte boundary -> (whole buffer, view)"""
     buf = torch.full((GUARD + offset + n + GUARD,), SENT, dtype=torch.int32, device=dev).view(torch.float32)
     view = buf[GUARD + offset:GUARD + offset + n]
-    view.copy_(torch.randn(n, generator=gen).to(dev))
+    view.copy_(torch.randn(n, generator=gen).to(dev) if data is None else data)
     return buf, view
 
 
@@ -394,3 +397,194 @@ def test_refusals_leave_the_engine_usable(cuda, tiny_unet_bf16):
     D.synchronize()
     assert torch.equal(out, ref)
     eng.close()
+
+
+# ------------------------------------------------------------------------------------------------ 9. the scalar step entries
+# dmx_sched_step_rows is compared with the scalar entries above, and both run one kernel body: here the scalar entries stand against the
+# numpy restatement (tests/inflight_restatement.row_update, which the host tests hold to oracle/schedulers.py and tests/dpm_restatement.py),
+# bit for bit.  The scalar launcher caps its grid at 2048 blocks of 256 threads; the last size is one full grid of float4s, four more blocks'
+# worth and a tail of three, so the grid-stride loop runs and ends in a partial float4.
+STEP_GRID_CAP = 2048 * 256
+STEP_SIZES = [3, 37, 1024, STEP_GRID_CAP * 4 + 1024 + 3]
+
+
+@functools.lru_cache(maxsize=1)
+def _step_reference(n):
+    """inputs (numpy, fp32) and, per case, the restatement's (prev_sample, m0): computed once per size, shared by both builds, only read"""
+    import diffute_amd as D
+    import inflight_restatement as IR
+    from diffute_amd import _cabi
+    from diffute_amd.inflight import plan_records
+    rng = np.random.default_rng(n)
+    data = {k: rng.standard_normal(n).astype(np.float32) for k in ("x", "e", "nz", "m1", "m2", "out", "x0")}
+    ddim = plan_records(D.DDIMScheduler(), 10, eta=0.5)[1][2]
+    ddpm = plan_records(D.DDPMScheduler(), 10)[1][3]
+    assert ddim.use_noise == 1 and ddpm.use_noise == 1 and all(float(v) != 0 for v in list(ddim.c) + list(ddpm.c))
+    dpm = plan_records(D.DPMSolverMultistepScheduler(solver_order=3), 10)[1]
+    heun = plan_records(D.DPMSolverMultistepScheduler(solver_order=2, solver_type="heun"), 5)[1][1]
+    assert [dpm[i].order for i in range(3)] == [1, 2, 3] and heun.order == 2
+    cases = []                          # (name, kind, record, noise given)
+    for noise in (True, False):
+        cases += [("ddim", _cabi.SCHED_DDIM, ddim, noise), ("ddpm", _cabi.SCHED_DDPM, ddpm, noise)]
+    cases += [(f"dpm{i + 1}", _cabi.SCHED_DPMPP, dpm[i], False) for i in range(3)] + [("dpm2heun", _cabi.SCHED_DPMPP, heun, False)]
+    want = {}
+    for name, kind, rec, noise in cases:
+        for vpred in (0, 1):
+            m1 = data["m1"] if rec.order >= 2 else None
+            m2 = data["m2"] if rec.order >= 3 else None
+            want[(name, noise, vpred)] = IR.row_update(kind, rec, data["x"], data["e"], data["nz"] if noise else None, m1, m2, bool(vpred))
+    for v in data.values():
+        v.setflags(write=False)
+    return data, cases, want
+
+
+@pytest.mark.parametrize("n,build", [(n, b) for n in STEP_SIZES for b in ("bf16", "fp16")])
+def test_scalar_step_entries_equal_the_restatement(cuda, n, build):
+    """Every case of every scalar entry, per size: all pointers aligned / all one float past a 16-byte boundary / exactly one operand
+    misaligned (the noise, else eps, for DDIM and DDPM; for DPM-Solver++ the oldest operand its order reads: x0_out, m1, m2); in place and
+    out of place; noise given and NULL; both prediction types; orders 1, 2, 3 (midpoint) and 2 (heun).  The whole of every buffer - guard
+    bands, inputs, operands an order does not read - is compared bit for bit."""
+    from diffute_amd import _cabi
+    lib = _cabi.lib(build)
+    st = _cabi.current_stream()
+    data, cases, want = _step_reference(n)
+    dev_data = {k: torch.from_numpy(v.copy()).to(cuda) for k, v in data.items()}
+    for name, kind, rec, noise in cases:
+        dpm = kind == _cabi.SCHED_DPMPP
+        odd = ("x0", "m1", "m2")[rec.order - 1] if dpm else ("nz" if noise else "e")
+        for vpred in (0, 1):
+            prev, m0 = want[(name, noise, vpred)]
+            prev_dev = torch.from_numpy(prev).to(cuda)
+            m0_dev = torch.from_numpy(m0).to(cuda) if dpm else None
+            for align in ("all0", "all1", "one"):
+                for inplace in (True, False):
+                    off = {k: (1 if align == "all1" or (align == "one" and k == odd) else 0) for k in dev_data}
+                    bufs = {k: _guarded(n, off[k], cuda, None, dev_data[k]) for k in dev_data}
+                    expect = {k: b.clone() for k, (b, _) in bufs.items()}
+                    view = {k: v for k, (_, v) in bufs.items()}
+                    out_key = "x" if inplace else "out"
+                    expect[out_key][GUARD + off[out_key]:GUARD + off[out_key] + n] = prev_dev
+                    if dpm:
+                        expect["x0"][GUARD + off["x0"]:GUARD + off["x0"] + n] = m0_dev
+                        rc = lib.dmx_sched_step_dpmpp(_cabi.ptr(view["x"]), _cabi.ptr(view["e"]), _cabi.ptr(view["m1"]) if rec.order >= 2 else None,
+                                                      _cabi.ptr(view["m2"]) if rec.order >= 3 else None, _cabi.ptr(view["x0"]), _cabi.ptr(view[out_key]),
+                                                      n, rec.order, rec.dpm, vpred, st)
+                    else:
+                        fn = lib.dmx_sched_step_ddim if kind == _cabi.SCHED_DDIM else lib.dmx_sched_step_ddpm
+                        rc = fn(_cabi.ptr(view["x"]), _cabi.ptr(view["e"]), _cabi.ptr(view["nz"]) if noise else None, _cabi.ptr(view[out_key]), n,
+                                *[float(v) for v in rec.c], vpred, st)
+                    _cabi.check(rc, name, lib)
+                    for k, (b, _) in bufs.items():
+                        bad = (_bits(b) != _bits(expect[k])).nonzero()
+                        assert bad.numel() == 0, (f"{name} n {n} vpred {vpred} noise {noise} {align} {'in place' if inplace else 'out of place'}: buffer {k!r} "
+                                                  f"differs at {bad.numel()} floats, first {int(bad[0]) - GUARD - off[k]} (guard excluded)")
+    _cabi.poll_device_error(lib)
+
+
+# ------------------------------------------------------------------------------------------------ 10. denoise() reaches the same entries
+# recorded on the commit before the denoise paths were unified (same recorder, same inputs, both builds alike): the table of the loop's
+# timesteps, the context, then per step one graph forward with its table set and unset around it and one scheduler entry
+DENOISE_CALLS = {
+    "ddim_eta0": [
+        "dmx_unet_temb_table_floats", "dmx_unet_temb_table_workspace_bytes", "dmx_unet_temb_table", "dmx_unet_context_bytes",
+        "dmx_unet_workspace_bytes", "dmx_unet_set_context", "dmx_plan_epoch", "dmx_unet_workspace_bytes", "dmx_unet_use_temb_table",
+        "dmx_unet_forward_graph", "dmx_unet_use_temb_table", "dmx_sched_step_ddim", "dmx_plan_epoch", "dmx_unet_use_temb_table",
+        "dmx_unet_forward_graph", "dmx_unet_use_temb_table", "dmx_sched_step_ddim", "dmx_plan_epoch", "dmx_unet_use_temb_table",
+        "dmx_unet_forward_graph", "dmx_unet_use_temb_table", "dmx_sched_step_ddim"
+    ],
+    "ddim_eta05": [
+        "dmx_unet_temb_table_floats", "dmx_unet_temb_table_workspace_bytes", "dmx_unet_temb_table", "dmx_unet_context_bytes",
+        "dmx_unet_workspace_bytes", "dmx_unet_set_context", "dmx_plan_epoch", "dmx_unet_workspace_bytes", "dmx_unet_use_temb_table",
+        "dmx_unet_forward_graph", "dmx_unet_use_temb_table", "dmx_sched_step_ddim", "dmx_plan_epoch", "dmx_unet_use_temb_table",
+        "dmx_unet_forward_graph", "dmx_unet_use_temb_table", "dmx_sched_step_ddim", "dmx_plan_epoch", "dmx_unet_use_temb_table",
+        "dmx_unet_forward_graph", "dmx_unet_use_temb_table", "dmx_sched_step_ddim"
+    ],
+    "ddpm": [
+        "dmx_unet_temb_table_floats", "dmx_unet_temb_table_workspace_bytes", "dmx_unet_temb_table", "dmx_unet_context_bytes",
+        "dmx_unet_workspace_bytes", "dmx_unet_set_context", "dmx_plan_epoch", "dmx_unet_workspace_bytes", "dmx_unet_use_temb_table",
+        "dmx_unet_forward_graph", "dmx_unet_use_temb_table", "dmx_sched_step_ddpm", "dmx_plan_epoch", "dmx_unet_use_temb_table",
+        "dmx_unet_forward_graph", "dmx_unet_use_temb_table", "dmx_sched_step_ddpm", "dmx_plan_epoch", "dmx_unet_use_temb_table",
+        "dmx_unet_forward_graph", "dmx_unet_use_temb_table", "dmx_sched_step_ddpm"
+    ],
+    "dpmpp2": [
+        "dmx_unet_temb_table_floats", "dmx_unet_temb_table_workspace_bytes", "dmx_unet_temb_table", "dmx_unet_context_bytes",
+        "dmx_unet_workspace_bytes", "dmx_unet_set_context", "dmx_plan_epoch", "dmx_unet_workspace_bytes", "dmx_unet_use_temb_table",
+        "dmx_unet_forward_graph", "dmx_unet_use_temb_table", "dmx_sched_step_dpmpp", "dmx_plan_epoch", "dmx_unet_use_temb_table",
+        "dmx_unet_forward_graph", "dmx_unet_use_temb_table", "dmx_sched_step_dpmpp", "dmx_plan_epoch", "dmx_unet_use_temb_table",
+        "dmx_unet_forward_graph", "dmx_unet_use_temb_table", "dmx_sched_step_dpmpp"
+    ],
+}
+
+
+@pytest.mark.parametrize("case", ["ddim_eta0", "ddim_eta05", "ddpm", "dpmpp2"])
+def test_denoise_makes_the_same_calls(cuda, tiny_unet, case, monkeypatch):
+    import diffute_amd as D
+    from diffute_amd import _cabi
+    from diffute_amd.synthetic import synth_inputs
+    from test_prepost_pages_gpu import _Recorder
+    lat, mask, mlat, ctx = synth_inputs(2, 16, 16, 77, 128, device=cuda)
+    sched, eta = {"ddim_eta0": (D.DDIMScheduler(), 0.0), "ddim_eta05": (D.DDIMScheduler(), 0.5), "ddpm": (D.DDPMScheduler(), 0.0),
+                  "dpmpp2": (D.DPMSolverMultistepScheduler(solver_order=2), 0.0)}[case]
+    tiny_unet._ensure_packed()
+    tiny_unet._slots.pop(0, None)                    # the loop's execution slot starts empty, whatever ran before
+    names, real = [], _cabi.lib
+    monkeypatch.setattr(_cabi, "lib", lambda elem="bf16": _Recorder(real(elem), names))      # (unet._lib is _cabi.lib(the model's build))
+    out = D.denoise(tiny_unet, sched, lat, mask, mlat, ctx, 3, eta=eta)
+    monkeypatch.undo()
+    D.synchronize()
+    assert torch.isfinite(out).all()
+    assert names == DENOISE_CALLS[case], f"{case}: {names}"
+
+
+# ------------------------------------------------------------------------------------------------ 11. the workspace query
+WORKSPACE_BYTES = [284672, 8722432]      # (B, H, W, ctx_len) = (1, 8, 8, 5), (3, 16, 16, 77), either build, recorded on that commit too
+
+
+def test_workspace_bytes_unchanged(cuda, tiny_unet):
+    """dmx_unet_workspace_bytes covers the forward and the context projection (whose dry walk is the projection's own function): the values
+    recorded before the two were unified"""
+    tiny_unet._ensure_packed()
+    got = [int(tiny_unet._lib.dmx_unet_workspace_bytes(tiny_unet._h, *shape)) for shape in ((1, 8, 8, 5), (3, 16, 16, 77))]
+    assert got == WORKSPACE_BYTES, got
+
+
+
+# ------------------------------------------------------------------------------------------------ 12. temb fetch, scalar form
+def test_temb_scalar_form_equals_explicit_timestep(cuda, tiny_unet):
+    """forward_parts(..., temb=(table, step index)) is forward_parts with that step's timestep, bit for bit: eager, and through the graph
+    path, whose third call is a replay (it reads a step index changed on the device in between).  A per-row call on the same slot and
+    buffers then runs its own walk: it writes the timesteps the scalar form never writes, and equals the explicit per-row timesteps."""
+    import diffute_amd as D
+    from diffute_amd.inflight import plan_records
+    from diffute_amd.synthetic import synth_inputs
+    ts, recs = plan_records(D.DDIMScheduler(), 4)
+    table = tiny_unet.temb_table(torch.tensor(ts, dtype=torch.int64, device=cuda))
+    plan = _upload_plan(recs, cuda)
+    for B in (3, 1):          # B = 1: the two forms take the same t_count, buffers and index tensor - only the plan tells their graph keys apart
+        lat, mask, mlat, ctx = synth_inputs(B, 16, 16, 77, 128, device=cuda)
+        parts = [lat, mask, mlat]
+        slot = f"t12_{B}"
+        tiny_unet.set_context(ctx, slot=slot)
+        explicit = {i: tiny_unet.forward_parts(parts, torch.tensor([ts[i]], dtype=torch.int64, device=cuda), slot=slot).clone() for i in (1, 2)}
+        tbuf = torch.full((B,), -7, dtype=torch.int64, device=cuda)
+        index = torch.full((B,), 2, dtype=torch.int32, device=cuda)
+        eager = tiny_unet.forward_parts(parts, tbuf[:1], slot=slot, temb=(table, index[:1])).clone()
+        assert torch.equal(eager, explicit[2])
+        side = torch.cuda.Stream(device=cuda)
+        side.wait_stream(torch.cuda.current_stream(cuda))
+        with torch.cuda.stream(side):
+            out = torch.empty_like(eager)
+            for call, i in enumerate((2, 2, 1)):                 # seen, captured, replayed
+                index.fill_(i)
+                tiny_unet.forward_parts(parts, tbuf[:1], out=out, graph=True, slot=slot, temb=(table, index[:1]))
+                assert torch.equal(out, explicit[i]), f"B {B} graph call {call}"
+            assert tbuf.tolist() == [-7] * B                     # the scalar form leaves the timesteps alone
+            rows = list(range(B))                                # row b on step b
+            index.copy_(torch.tensor(rows, dtype=torch.int32, device=cuda))
+            tiny_unet.forward_parts(parts, tbuf, out=out, graph=True, slot=slot, temb=(table, index, plan))
+            assert tbuf.tolist() == [ts[i] for i in rows], "the per-row call did not run its own walk (a replay of the scalar graph?)"
+            want = tiny_unet.forward_parts(parts, torch.tensor([ts[i] for i in rows], dtype=torch.int64, device=cuda), slot=slot)
+            assert torch.equal(out, want)
+        torch.cuda.current_stream(cuda).wait_stream(side)
+        D.synchronize()
+        tiny_unet._slots.pop(slot)

@@ -146,6 +146,54 @@ def test_plan_records_dpmpp(n, order):
         assert r.timestep == ts[i] and r.use_noise == 0
 
 
+def _rec_fields(r):
+    return (list(r.c), _dpm_fields(r.dpm), r.order, r.use_noise, r.ring_w, r.ring_m1, r.ring_m2, r.timestep)
+
+
+@pytest.mark.parametrize("n", [1, 3, 10])
+def test_scheduler_plan_equals_plan_records(n):
+    """scheduler.plan(eta) after set_timesteps(n) is plan_records(a fresh scheduler, n, eta), field by field, for the three classes"""
+    import diffute_amd as D
+    from diffute_amd.inflight import plan_records
+    cases = [(D.DDIMScheduler, {}, 0.0), (D.DDIMScheduler, {}, 0.5), (D.DDPMScheduler, {}, 0.0), (D.DPMSolverMultistepScheduler, {}, 0.0),
+             (D.DPMSolverMultistepScheduler, dict(solver_order=3, solver_type="heun"), 0.0)]
+    for cls, kw, eta in cases:
+        s = cls(**kw)
+        with pytest.raises(ValueError):
+            s.plan(eta)                                                  # no grid yet
+        s.set_timesteps(n)
+        ts, recs = plan_records(cls(**kw), n, eta)
+        got = s.plan(eta)
+        assert ts == s.timesteps.tolist() and len(got) == len(recs) == len(ts)
+        assert [_rec_fields(r) for r in got] == [_rec_fields(r) for r in recs]
+        assert [r.timestep for r in got] == ts
+        assert [_rec_fields(r) for r in s.iter_plan(eta)] == [_rec_fields(r) for r in got]      # the lazy walk denoise() takes
+
+
+def test_launch_step_is_the_only_caller_of_the_scalar_step_entries():
+    """in diffute_amd/*.py the three scalar entries are named in _cabi.py's signature table and inside schedulers.launch_step, nowhere else"""
+    import inspect
+    import re
+    import diffute_amd
+    from diffute_amd import schedulers
+    pat = re.compile(r"dmx_sched_step_(ddim|ddpm|dpmpp)\b")
+    pkg = os.path.dirname(os.path.abspath(diffute_amd.__file__))
+    body = inspect.getsource(schedulers.launch_step)
+    assert len(pat.findall(body)) == 3
+    for root, _, files in os.walk(pkg):
+        for f in files:
+            if not f.endswith(".py"):
+                continue
+            text = open(os.path.join(root, f)).read()
+            hits = len(pat.findall(text))
+            if f == "_cabi.py":
+                assert hits == 3, "_cabi.py: one signature each"
+            elif f == "schedulers.py":
+                assert text.count(body) == 1 and hits == 3, "schedulers.py names the entries outside launch_step"
+            else:
+                assert hits == 0, f"{f} names a scalar step entry: go through schedulers.launch_step"
+
+
 def test_record_layout():
     """the record is 88 bytes with the timestep last (the kernel's struct, which a static_assert holds to the same size)"""
     import ctypes
