@@ -81,6 +81,7 @@ class SchedRowRec(ctypes.Structure):
 
 
 SCHED_DDIM, SCHED_DDPM, SCHED_DPMPP = 0, 1, 2      # DMX_SCHED_*
+STEP_CACHE_FILL, STEP_CACHE_USE = 1, 2      # DMX_STEP_CACHE_*
 
 
 class ViTConfig(ctypes.Structure):
@@ -280,6 +281,12 @@ _PROTOS = {
     "dmx_unet_forward_f32": (c_int, [_P, _P, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_size_t,
                                      _P, c_size_t, _P, _P, _P]),
     "dmx_unet_forward_graph": (c_int, [_P, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "dmx_unet_step_cache_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
+    "dmx_unet_workspace_bytes_cached": (c_size_t, [_P, c_int, c_int, c_int, c_int]),
+    "dmx_unet_forward_cached": (c_int, [_P, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_size_t, c_int,
+                                        _P, c_size_t, _P]),
+    "dmx_unet_forward_cached_graph": (c_int, [_P, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P, c_size_t, c_int,
+                                              _P, c_size_t, _P]),
     "dmx_unet_train_workspace_bytes": (c_size_t, [_P, c_int, c_int, c_int, c_int]),
     "dmx_unet_train_wt_bytes": (c_size_t, [_P]),
     "dmx_unet_train_prepare": (c_int, [_P, _P, c_size_t, _P]),

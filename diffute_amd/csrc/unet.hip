@@ -377,7 +377,24 @@ __global__ __launch_bounds__(256) void dmx_temb_fetch_kernel(const float* table,
   if (plan && blockIdx.x == 0 && threadIdx.x == 0) timesteps[b] = (long long)plan[idx].timestep;
 }
 
+// Step cache hand-off (FILL): the tensor and, where it has them, its statistics records -> the caller's buffer, one launch behind the
+// producer (the statistics pool is zeroed per forward and the producers ADD into it, so the records are final only after it).  16-byte units.
+__global__ __launch_bounds__(256) void dmx_step_cache_store_kernel(const u32x4* t, u32x4* ct, size_t nt, const u32x4* st, u32x4* cs, size_t ns) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nt + ns; i += (size_t)gridDim.x * blockDim.x) {
+    if (i < nt) ct[i] = t[i];
+    else cs[i - nt] = st[i - nt];
+  }
+}
+
 }  // namespace
+
+// layout of a step cache: the tensor [B*H*W][C1] (H, W: the forward's latent grid, where up-block 3 runs), then its [B][C1][4] records
+static size_t step_cache_tensor_bytes(const dmx_unet* u, int B, int H, int W) { return (size_t)B * H * W * u->cfg.block_out_channels[1] * sizeof(bf16); }
+static size_t step_cache_stat_bytes(const dmx_unet* u, int B) { return (size_t)B * u->cfg.block_out_channels[1] * DMX_STAT_WORDS * sizeof(long long); }
+extern "C" size_t dmx_unet_step_cache_bytes(dmx_unet* u, int B, int H, int W) {
+  if (!u || B <= 0 || H <= 0 || W <= 0) return 0;
+  return align_up(step_cache_tensor_bytes(u, B, H, W), 256) + align_up(step_cache_stat_bytes(u, B), 256);
+}
 
 int temb_rows(const dmx_unet* u, Exec& ex, const long long* timesteps, int t_count, int rows, const TembBufs& b, float* tproj) {
   const int c0 = u->cfg.block_out_channels[0], temb = u->temb_dim;
@@ -432,8 +449,14 @@ int unet_check_call(const dmx_unet* u, const UNetCall& c, const void* workspace,
 
 namespace {
 
-int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c) {
+// One walk for the three forms of a step: sc.mode 0 / FILL run every layer (FILL also leaves the tensor that enters up-block 3 in the
+// step cache), USE runs what lies around that tensor - conv_in, down-block 0 (for its three skips; its stride-2 conv has no reader),
+// up-block 3 on the kept tensor, conv_norm_out, conv_out.
+int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c, StepCache& sc) {
   const int B = c.B, H = c.H, W = c.W, t_count = c.t_count;
+  const bool shallow = sc.mode == DMX_STEP_CACHE_USE;
+  bf16* const sc_t = (bf16*)sc.buf;
+  long long* const sc_st = sc.buf ? (long long*)((char*)sc.buf + align_up(step_cache_tensor_bytes(u, B, H, W), 256)) : nullptr;
   const dmx_unet_config& cfg = u->cfg;
   const int* boc = cfg.block_out_channels; const int L = cfg.layers_per_block; const int temb = u->temb_dim;
   // ---- time embedding (fp32, bf16 weights).  A scalar timestep (the denoise loop) is embedded once and every image reads
@@ -509,7 +532,7 @@ int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c) {
   ex.tap(h);                                           // "conv_in"
   ex.ensure_stats(h);
   std::vector<Tn> skips; skips.push_back(h);
-  for (int i = 0; i < 4; ++i) {
+  for (int i = 0; i < (shallow ? 1 : 4); ++i) {
     for (int j = 0; j < L; ++j) {
 #ifdef DMX_PROBES
       static const bool fine = getenv("DMX_TAPS_FINE") != nullptr;      // debugging aid: also tap every resnet / transformer output of the down path
@@ -522,7 +545,7 @@ int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c) {
       ex.ensure_stats(y);                             // (two GroupNorms read it: the next block's and the up path's concat)
       h = y; skips.push_back(h);                      // previous h stays alive as a skip
     }
-    if (i < 3) {
+    if (i < 3 && !shallow) {
       ConvOpts o; o.stride = 2; o.pad = 1; o.bias = f.W<float>(u->down_ds[i].b); o.stats = 1;
       h = ex.conv(h, nullptr, f.W<bf16>(u->down_ds[i].w), boc[i], o);
       ex.ensure_stats(h);
@@ -531,18 +554,25 @@ int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c) {
     ex.tap(h);                                         // "down{i}"
   }
   Tn mid_in;
-  { Tn y = f.resnet(u->mid_res[0], h, nullptr);          // h is also skips.back(): keep it
+  if (!shallow) {
+    Tn y = f.resnet(u->mid_res[0], h, nullptr);          // h is also skips.back(): keep it
     Tn z = f.xformer(u->mid_xf, y); ex.drop(y);
     ex.ensure_stats(z);
-    h = f.resnet(u->mid_res[1], z, nullptr); mid_in = z; }
-  ex.tap(h);                                           // "mid"
-  for (int i = 0; i < 4; ++i) {
+    h = f.resnet(u->mid_res[1], z, nullptr); mid_in = z;
+    ex.tap(h);                                         // "mid"
+  } else {
+    // the kept tensor in h's place: memory of the caller, not of the workspace (never dropped), complete (no pending reduce pass)
+    h = Tn(); h.p = sc_t; h.B = B; h.H = H; h.W = W; h.C = boc[1]; h.ld = boc[1];
+    h.cst = sc.has_stats ? (ex.dry ? (const long long*)8 : sc_st) : nullptr;      // (dry walk: no addresses - any non-null value asks the same question)
+  }
+  for (int i = shallow ? 3 : 0; i < 4; ++i) {
     for (int j = 0; j < L + 1; ++j) {
       Tn s = skips.back(); skips.pop_back();
       Tn y = f.resnet(u->up_res[i][j], h, &s);
       // (z is the residual of mid_res[1]'s conv2: where that conv left its split-K reduce to the GroupNorm that has just run, z had to live until here)
       if (i == 0 && j == 0) ex.drop(mid_in);
-      ex.drop(h); ex.drop(s);
+      if (!(shallow && j == 0)) ex.drop(h);
+      ex.drop(s);
       if (cfg.up_has_attn[i]) { Tn z = f.xformer(u->up_xf[i][j], y); ex.drop(y); y = z; }
       ex.ensure_stats(y);
       h = y;
@@ -554,6 +584,18 @@ int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c) {
       Tn y = ex.conv(h, nullptr, direct ? f.W<bf16>(u->up_us[i].w) : u->at<bf16>(u->up_us[i].wp), boc[3 - i], o);
       ex.ensure_stats(y);
       ex.drop(h); h = y;
+      if (i == 2 && sc.mode == DMX_STEP_CACHE_FILL) {
+        ex.flush(h);
+        sc.has_stats = h.cst != nullptr;
+        if (!ex.dry && !ex.rc) {
+          const size_t nt = step_cache_tensor_bytes(u, B, H, W) / 16, ns = sc.has_stats ? step_cache_stat_bytes(u, B) / 16 : 0;
+          ProfScope ps(PROF_OTHER, ex.stream, 0.0, 32.0 * (double)(nt + ns), "step cache store");
+          const size_t blocks = (nt + ns + 255) / 256;
+          hipLaunchKernelGGL(dmx_step_cache_store_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, ex.stream,
+                             (const u32x4*)h.p, (u32x4*)sc_t, nt, (const u32x4*)h.cst, (u32x4*)sc_st, ns);
+          ex.rc = dmx_check_launch("dmx_step_cache_store_kernel");
+        }
+      }
     }
     ex.tap(h);                                         // "up{i}"
   }
@@ -570,15 +612,16 @@ int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c) {
 
 // the product walk with the weight prefetch plan (Exec::note / peek): a dry walk of the same graph lists the weight ranges in launch
 // order, the real walk hands every launch the ranges of the launches that follow it
-int unet_run_planned(dmx_unet* u, Exec& ex, const UNetCall& c) {
+int unet_run_planned(dmx_unet* u, Exec& ex, const UNetCall& c, StepCache& sc) {
   Exec::PfPlan plan;
   {
     Exec dr = Exec::dry_run(); dr.plan = &plan; dr.plan_rec = true;
     UNetCall d = c; d.f0 = d.f1 = d.f2 = nullptr; d.timesteps = nullptr; d.out = nullptr;
-    unet_run(u, dr, d);
+    StepCache dsc = sc; dsc.buf = nullptr;
+    unet_run(u, dr, d, dsc);
   }
   ex.plan = &plan; ex.plan_rec = false; ex.plan_bad = false; ex.plan_i = 0;
-  int rc = unet_run(u, ex, c);
+  int rc = unet_run(u, ex, c, sc);
   if (!rc && (ex.plan_bad || ex.plan_i != (int)plan.w.size())) { dmx_set_error("unet: the prefetch plan of the dry walk (%d launches) does not match the real walk (%d)", (int)plan.w.size(), ex.plan_i); rc = DMX_ERR_ARG; }
   ex.plan = nullptr;
   return rc;
@@ -594,9 +637,33 @@ UNetCall dry_call(int t_count, int ctx_len, int B, int H, int W) {
                          const void* ctx, int ctx_len, float* out, int B, int H, int W
 #define UNET_CALL_RECORD UNetCall{f0, f1, f2, c0, c1, c2, (const long long*)timesteps, t_count, ctx, ctx_len, out, B, H, W}
 
-int forward_eager(dmx_unet* u, const UNetCall& c, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+int forward_eager(dmx_unet* u, const UNetCall& c, StepCache sc, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   Exec ex = Exec::on(stream, workspace, workspace_bytes);
-  return unet_run_planned(u, ex, c);
+  return unet_run_planned(u, ex, c, sc);
+}
+
+// whether the tensor a FILL walk of this shape keeps carries statistics records: asked of a dry FILL walk once per shape and plan epoch
+bool step_cache_has_stats(dmx_unet* u, const UNetCall& c) {
+  const auto key = std::make_tuple(c.B, c.H, c.W, dmx_plan_epoch());
+  auto it = u->step_cache_stats.find(key);
+  if (it != u->step_cache_stats.end()) return it->second;
+  Exec ex = Exec::dry_run();
+  StepCache sc; sc.mode = DMX_STEP_CACHE_FILL;
+  unet_run(u, ex, dry_call(c.t_count, c.ctx_len, c.B, c.H, c.W), sc);
+  if (u->step_cache_stats.size() > 256) u->step_cache_stats.clear();
+  return u->step_cache_stats[key] = sc.has_stats;
+}
+
+// the step-cache record of a cached forward, checked (house style: DMX_REQUIRE)
+int step_cache_record(dmx_unet* u, const UNetCall& c, void* cache, size_t cache_bytes, int mode, const char* who, StepCache* sc) {
+  DMX_REQUIRE(mode == DMX_STEP_CACHE_FILL || mode == DMX_STEP_CACHE_USE, "%s: unknown step cache mode %d", who, mode);
+  DMX_REQUIRE(cache != nullptr, "%s: null step cache", who);
+  DMX_REQUIRE(((size_t)cache & 15) == 0, "%s: the step cache must be 16-byte aligned", who);
+  DMX_REQUIRE(cache_bytes >= dmx_unet_step_cache_bytes(u, c.B, c.H, c.W), "%s: step cache too small (%zu bytes, needs %zu)", who, cache_bytes,
+              dmx_unet_step_cache_bytes(u, c.B, c.H, c.W));
+  sc->mode = mode; sc->buf = cache;
+  sc->has_stats = mode == DMX_STEP_CACHE_USE && step_cache_has_stats(u, c);
+  return DMX_OK;
 }
 
 }  // namespace
@@ -604,7 +671,8 @@ int forward_eager(dmx_unet* u, const UNetCall& c, void* workspace, size_t worksp
 extern "C" size_t dmx_unet_workspace_bytes(dmx_unet* u, int B, int H, int W, int ctx_len) {
   if (!u) return 0;
   Exec ex = Exec::dry_run();
-  unet_run(u, ex, dry_call(1, ctx_len, B, H, W));
+  StepCache off;
+  unet_run(u, ex, dry_call(1, ctx_len, B, H, W), off);
   size_t need = ex.ws.peak();
   // set_context needs the padded context + split-K scratch
   Exec e2 = Exec::dry_run();
@@ -616,7 +684,7 @@ extern "C" size_t dmx_unet_workspace_bytes(dmx_unet* u, int B, int H, int W, int
 extern "C" int dmx_unet_forward(dmx_unet* u, UNET_CALL_PARAMS, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   const UNetCall c = UNET_CALL_RECORD;
   if (const int rc = unet_check_call(u, c, workspace, "unet_forward")) return rc;
-  return forward_eager(u, c, workspace, workspace_bytes, (hipStream_t)stream);
+  return forward_eager(u, c, StepCache(), workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // dmx_unet_forward + debug taps: the block outputs conv_in, down0..3, mid, up0..3 (the oracle's tap points) are copied out as
@@ -628,7 +696,8 @@ extern "C" int dmx_unet_forward_taps(dmx_unet* u, UNET_CALL_PARAMS, void* worksp
   DMX_REQUIRE(taps && tap_shapes && n_taps, "unet_forward_taps: null argument");
   TapSink sink; sink.buf = taps; sink.cap = tap_floats;
   Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes); ex.taps = &sink;
-  const int rc = unet_run(u, ex, c);
+  StepCache off;
+  const int rc = unet_run(u, ex, c, off);
   write_taps(sink, tap_shapes, n_taps);
   return rc;
 }
@@ -640,7 +709,8 @@ extern "C" int dmx_unet_forward_taps(dmx_unet* u, UNET_CALL_PARAMS, void* worksp
 extern "C" size_t dmx_unet_workspace_bytes_f32(dmx_unet* u, int B, int H, int W, int ctx_len) {
   if (!u) return 0;
   Exec ex = Exec::dry_run(true);
-  unet_run(u, ex, dry_call(B, ctx_len, B, H, W));
+  StepCache off;
+  unet_run(u, ex, dry_call(B, ctx_len, B, H, W), off);
   return ex.ws.peak() + 4096;
 }
 extern "C" int dmx_unet_forward_f32(dmx_unet* u, const void* masters, const float* f0, int c0, const float* f1, int c1, const float* f2, int c2,
@@ -652,7 +722,8 @@ extern "C" int dmx_unet_forward_f32(dmx_unet* u, const void* masters, const floa
   TapSink sink; sink.buf = taps; sink.cap = tap_floats;
   Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes, true); ex.masters = (const char*)masters;
   if (taps) ex.taps = &sink;
-  const int rc = unet_run(u, ex, c);
+  StepCache off;
+  const int rc = unet_run(u, ex, c, off);
   write_taps(sink, tap_shapes, n_taps);
   return rc;
 }
@@ -662,20 +733,17 @@ extern "C" int dmx_unet_forward_f32(dmx_unet* u, const void* masters, const floa
 // non-default stream (the legacy NULL stream cannot be captured); falls back to eager launches otherwise or while
 // the profiler is recording.
 bool dmx_profile_active();
-extern "C" int dmx_unet_forward_graph(dmx_unet* u, UNET_CALL_PARAMS, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
-  const UNetCall c = UNET_CALL_RECORD;
-  if (const int rc = unet_check_call(u, c, workspace, "unet_forward_graph")) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if (s == nullptr || dmx_profile_active()) return forward_eager(u, c, workspace, workspace_bytes, s);
-  const dmx_unet::GraphKey key = u->graph_key(c, workspace);
+static int forward_graph(dmx_unet* u, const UNetCall& c, StepCache sc, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  if (s == nullptr || dmx_profile_active()) return forward_eager(u, c, sc, workspace, workspace_bytes, s);
+  const dmx_unet::GraphKey key = u->graph_key(c, workspace, sc);
   dmx_unet::GraphEntry& e = u->graphs[key];
   if (e.exec) { DMX_HIP(hipGraphLaunch(e.exec, s)); return dmx_poll_device_error(); }      // (what an earlier replay raised: common.h)
   if (e.seen++ == 0)        // first sight: eager (also runs every one-time hipFuncSetAttribute outside a capture)
-    return forward_eager(u, c, workspace, workspace_bytes, s);
+    return forward_eager(u, c, sc, workspace, workspace_bytes, s);
   if (u->graphs.size() > 64) { u->graphs.erase(key); u->drop_graphs(); }
   DMX_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   Exec ex = Exec::on(s, workspace, workspace_bytes);
-  const int rc = unet_run_planned(u, ex, c);
+  const int rc = unet_run_planned(u, ex, c, sc);
   hipGraph_t g = nullptr;
   const hipError_t ce = hipStreamEndCapture(s, &g);
   if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
@@ -687,4 +755,40 @@ extern "C" int dmx_unet_forward_graph(dmx_unet* u, UNET_CALL_PARAMS, void* works
   u->graphs[key].exec = exec;
   DMX_HIP(hipGraphLaunch(exec, s));
   return DMX_OK;
+}
+extern "C" int dmx_unet_forward_graph(dmx_unet* u, UNET_CALL_PARAMS, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
+  const UNetCall c = UNET_CALL_RECORD;
+  if (const int rc = unet_check_call(u, c, workspace, "unet_forward_graph")) return rc;
+  return forward_graph(u, c, StepCache(), workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------- step cache (DeepCache-style reuse of the deep features)
+// dmx_unet_forward / _graph with a step cache: FILL is the same forward (bit-equal `out`) that also leaves the tensor entering the last
+// up-block, with its statistics records, in `cache`; USE computes `out` from the cache and the layers around it only.
+extern "C" size_t dmx_unet_workspace_bytes_cached(dmx_unet* u, int B, int H, int W, int ctx_len) {
+  if (!u) return 0;
+  size_t need = dmx_unet_workspace_bytes(u, B, H, W, ctx_len);      // (the FILL walk allocates what the plain walk allocates)
+  // a first-fit peak is not monotone in the op list: the shallow walk is asked on its own
+  const UNetCall c = dry_call(1, ctx_len, B, H, W);
+  Exec ex = Exec::dry_run();
+  StepCache sc; sc.mode = DMX_STEP_CACHE_USE; sc.has_stats = step_cache_has_stats(u, c);
+  unet_run(u, ex, c, sc);
+  if (ex.ws.peak() + 4096 > need) need = ex.ws.peak() + 4096;
+  return need;
+}
+extern "C" int dmx_unet_forward_cached(dmx_unet* u, UNET_CALL_PARAMS, void* cache, size_t cache_bytes, int mode,
+                                       void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
+  const UNetCall c = UNET_CALL_RECORD;
+  if (const int rc = unet_check_call(u, c, workspace, "unet_forward_cached")) return rc;
+  StepCache sc;
+  if (const int rc = step_cache_record(u, c, cache, cache_bytes, mode, "unet_forward_cached", &sc)) return rc;
+  return forward_eager(u, c, sc, workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" int dmx_unet_forward_cached_graph(dmx_unet* u, UNET_CALL_PARAMS, void* cache, size_t cache_bytes, int mode,
+                                             void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
+  const UNetCall c = UNET_CALL_RECORD;
+  if (const int rc = unet_check_call(u, c, workspace, "unet_forward_cached_graph")) return rc;
+  StepCache sc;
+  if (const int rc = step_cache_record(u, c, cache, cache_bytes, mode, "unet_forward_cached_graph", &sc)) return rc;
+  return forward_graph(u, c, sc, workspace, workspace_bytes, (hipStream_t)stream);
 }

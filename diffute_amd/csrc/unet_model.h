@@ -27,6 +27,18 @@ struct UNetCall {
   float* out = nullptr; int B = 0, H = 0, W = 0;
 };
 
+// Step cache of a denoise loop (dmx_unet_forward_cached): the tensor that enters the last up-block - the output of up_us[2]'s phase
+// convolution, tap "up2", [B*H*W][block_out_channels[1]] in the compute element type - and its GroupNorm statistics records ([B][C][4]
+// DmxStat), in a caller-owned buffer outside the workspace.  FILL: the whole walk, which leaves both there; USE: only the layers
+// around them (conv_in, down-block 0, up-block 3, conv_norm_out, conv_out) run, on the kept tensor.
+struct StepCache {
+  int mode = 0;                     // 0 = off, DMX_STEP_CACHE_FILL, DMX_STEP_CACHE_USE
+  void* buf = nullptr;              // null in a dry walk
+  // whether the full walk's tensor carries statistics records (a property of the shape and the plan switches): FILL notes it, USE must be
+  // told (step_cache_has_stats) - with them the consumers run their apply-only forms, without them they compute their own
+  bool has_stats = false;
+};
+
 struct dmx_unet : ModelBase {
   dmx_unet_config cfg;
   int temb_dim = 0, tproj_total = 0;
@@ -49,13 +61,16 @@ struct dmx_unet : ModelBase {
   struct GraphKey {
     const void *f0, *f1, *f2, *timesteps, *ctx, *out, *workspace; int c0, c1, c2, t_count, ctx_len, B, H, W;
     const void *temb_table, *temb_index, *temb_plan; int plan_epoch;
-    auto tie() const { return std::tie(f0, f1, f2, timesteps, ctx, out, workspace, c0, c1, c2, t_count, ctx_len, B, H, W, temb_table, temb_index, temb_plan, plan_epoch); }
+    const void* step_cache; int step_mode;      // (a cached loop replays two graphs: its full step and its shallow step)
+    auto tie() const { return std::tie(f0, f1, f2, timesteps, ctx, out, workspace, c0, c1, c2, t_count, ctx_len, B, H, W, temb_table, temb_index, temb_plan, plan_epoch, step_cache, step_mode); }
     bool operator<(const GraphKey& o) const { return tie() < o.tie(); }
   };
-  GraphKey graph_key(const UNetCall& c, const void* workspace) const {
+  GraphKey graph_key(const UNetCall& c, const void* workspace, const StepCache& sc) const {
     return GraphKey{c.f0, c.f1, c.f2, c.timesteps, c.ctx, c.out, workspace, c.c0, c.c1, c.c2, c.t_count, c.ctx_len, c.B, c.H, c.W,
-                    temb.table, temb.index, temb.plan, dmx_plan_epoch()};
+                    temb.table, temb.index, temb.plan, dmx_plan_epoch(), sc.buf, sc.mode};
   }
+  // memo of StepCache::has_stats per (B, H, W, plan epoch), from a dry FILL walk (unet.hip step_cache_has_stats)
+  std::map<std::tuple<int, int, int, int>, bool> step_cache_stats;
   struct GraphEntry { hipGraphExec_t exec = nullptr; int seen = 0; };
   std::map<GraphKey, GraphEntry> graphs;
   void drop_graphs() { for (auto& kv : graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec); graphs.clear(); }

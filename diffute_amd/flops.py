@@ -2,8 +2,10 @@
 activations excluded, <0.1 %) - the figure roofline numbers are computed from."""
 
 
-def unet_flops(cfg, B, h, w, ctx_len=577, cached_ctx_kv=True, phase_upsample=False):
-    """phase_upsample: count the upsampler convs as executed by dmx_conv_ups2x (4 instead of 9 taps per output)."""
+def unet_flops(cfg, B, h, w, ctx_len=577, cached_ctx_kv=True, phase_upsample=False, shallow=False):
+    """phase_upsample: count the upsampler convs as executed by dmx_conv_ups2x (4 instead of 9 taps per output).
+    shallow: only the layers a shallow step of the step cache runs (denoise(cache_interval=n)): the time embedding, conv_in, down-block 0
+    without its downsampler, the last up-block, conv_out."""
     boc = tuple(cfg.block_out_channels); L = cfg.layers_per_block; ctxd = cfg.cross_attention_dim
     down_attn = [t.startswith("CrossAttn") for t in cfg.down_block_types]
     up_attn = [t.startswith("CrossAttn") for t in cfg.up_block_types]
@@ -28,13 +30,20 @@ def unet_flops(cfg, B, h, w, ctx_len=577, cached_ctx_kv=True, phase_upsample=Fal
     f += conv(hw, cfg.in_channels, boc[0])
     skips = [boc[0]]; cprev = boc[0]
     for i, c in enumerate(boc):
+        if shallow and i > 0:
+            break
         for _ in range(L):
             f += res(hw, cprev, c) + (xf(hw, c) if down_attn[i] else 0)
             cprev = c; skips.append(c)
-        if i < len(boc) - 1:
+        if i < len(boc) - 1 and not shallow:
             hw //= 4; f += conv(hw, c, c); skips.append(c)
-    f += 2 * res(hw, cprev, cprev) + xf(hw, cprev)
+    if shallow:
+        cprev = boc[1]                 # the kept tensor: the output of the last upsampler, block_out_channels[1] wide on the full grid
+    else:
+        f += 2 * res(hw, cprev, cprev) + xf(hw, cprev)
     for i, c in enumerate(reversed(boc)):
+        if shallow and i < len(boc) - 1:
+            continue
         for _ in range(L + 1):
             f += res(hw, cprev + skips.pop(), c) + (xf(hw, c) if up_attn[i] else 0)
             cprev = c

@@ -540,7 +540,14 @@ class UNet2DConditionModel(_HipModel):
         if on:
             _cabi.check(rc, what)
 
-    def forward_parts(self, parts, timesteps_dev, out=None, graph=False, slot=0, temb=None):
+    def step_cache(self, B, H, W):
+        """A step cache for forwards of B samples on an H x W latent grid: the uint8 CUDA buffer (dmx_unet_step_cache_bytes) that
+        forward_parts(..., step_cache=(buffer, "fill")) leaves the tensor entering the last up-block in, with its GroupNorm statistics,
+        and forward_parts(..., step_cache=(buffer, "use")) computes a shallow step from (pipeline.denoise(..., cache_interval=n))."""
+        self._ensure_packed()
+        return torch.empty(int(self._lib.dmx_unet_step_cache_bytes(self._h, int(B), int(H), int(W))), dtype=torch.uint8, device=self.device)
+
+    def forward_parts(self, parts, timesteps_dev, out=None, graph=False, slot=0, temb=None, step_cache=None):
         """Hot-loop entry: `parts` = list of (NCHW fp32 cuda tensor) whose channels sum to in_channels
         (fuses the torch.cat of app.ipynb:811); timesteps_dev = int64 cuda tensor [1] or [B];
         context must have been set with set_context() on the same slot.  graph=True replays a captured hipGraph
@@ -548,7 +555,9 @@ class UNet2DConditionModel(_HipModel):
         tensor [1] holding the step's row): the time-embedding projections come from the table (scalar timestep only).
         temb = (table, row_index, plan) is the per-row form of the in-flight engine: row_index int32 cuda [B] (-1 = idle row, served row 0),
         plan the device array of dmx_sched_row_rec with the table's row numbering; timesteps_dev must be [B] and is WRITTEN with the
-        plan's timesteps by the forward."""
+        plan's timesteps by the forward.  step_cache = (step_cache(B, H, W), "fill" | "use"): "fill" is the same forward (bit-equal
+        result) that also keeps the tensor entering the last up-block; "use" runs only conv_in, down-block 0, the last up-block on the
+        kept tensor, conv_norm_out and conv_out (include/diffute_hip.h dmx_unet_forward_cached)."""
         lib = self._lib
         sl = self._slot(slot)
         x0 = parts[0]
@@ -561,8 +570,21 @@ class UNet2DConditionModel(_HipModel):
         key = (B, H, W, sl["ctx_shape"][1], int(lib.dmx_plan_epoch()))      # (every plan switch changes the walk, hence the workspace it needs)
         if sl["ws_need"] is None or sl["ws_need"][0] != key:
             sl["ws_need"] = (key, lib.dmx_unet_workspace_bytes(self._h, B, H, W, sl["ctx_shape"][1]))
-        ws = self._grown(sl, "ws", sl["ws_need"][1])
-        fwd = lib.dmx_unet_forward_graph if graph else lib.dmx_unet_forward
+        sc_args = ()
+        if step_cache is None:
+            ws = self._grown(sl, "ws", sl["ws_need"][1])
+            fwd = lib.dmx_unet_forward_graph if graph else lib.dmx_unet_forward
+        else:
+            buf, mode = step_cache
+            if mode not in ("fill", "use"):
+                raise ValueError(f"forward_parts: step_cache mode {mode!r}, expected 'fill' or 'use'")
+            if not torch.is_tensor(buf) or buf.dtype != torch.uint8 or buf.device != x0.device or not buf.is_contiguous():
+                raise ValueError("forward_parts: the step cache must be the uint8 buffer of step_cache(B, H, W) on the inputs' device")
+            if sl.get("ws_need_cached") is None or sl["ws_need_cached"][0] != key:
+                sl["ws_need_cached"] = (key, lib.dmx_unet_workspace_bytes_cached(self._h, B, H, W, sl["ctx_shape"][1]))
+            ws = self._grown(sl, "ws", sl["ws_need_cached"][1])
+            fwd = lib.dmx_unet_forward_cached_graph if graph else lib.dmx_unet_forward_cached
+            sc_args = (_cabi.ptr(buf), buf.numel(), _cabi.STEP_CACHE_FILL if mode == "fill" else _cabi.STEP_CACHE_USE)
         if temb is not None and len(temb) == 3 and (temb[1].numel() != B or timesteps_dev.numel() != B or temb[1].dtype != torch.int32):
             raise ValueError(f"forward_parts: the per-row temb form needs an int32 row index and timesteps of {B} entries each")
         if temb is not None:
@@ -570,7 +592,7 @@ class UNet2DConditionModel(_HipModel):
         try:
             _cabi.check(fwd(self._h, _cabi.ptr(ps[0][0]), ps[0][1], _cabi.ptr(ps[1][0]), ps[1][1],
                             _cabi.ptr(ps[2][0]), ps[2][1], _cabi.ptr(timesteps_dev), timesteps_dev.numel(),
-                            _cabi.ptr(sl["ctx_cache"]), sl["ctx_shape"][1], _cabi.ptr(out), B, H, W,
+                            _cabi.ptr(sl["ctx_cache"]), sl["ctx_shape"][1], _cabi.ptr(out), B, H, W, *sc_args,
                             _cabi.ptr(ws), ws.numel(), _cabi.current_stream()), "unet_forward")
         finally:
             if temb is not None:

@@ -37,8 +37,9 @@ def mask_to_latent(mask, vae_scale_factor=8):
 class _Run:
     """One micro-batch of the denoise loop: its own stream, UNet execution slot and fixed-address buffers."""
 
-    def __init__(self, unet, scheduler, latents, mask, mlat, ctx, slot, stream, use_graph, ts_dev, temb_table, table_rows):
+    def __init__(self, unet, scheduler, latents, mask, mlat, ctx, slot, stream, use_graph, ts_dev, temb_table, table_rows, cache_interval=1):
         self.unet, self.slot, self.stream, self.use_graph = unet, slot, stream, use_graph
+        self.cache_interval, self.cache = cache_interval, None
         self.kind, self.vpred = scheduler.kind, int(scheduler.config.prediction_type == "v_prediction")
         self.ts_dev, self.temb_table, self.table_rows = ts_dev, temb_table, table_rows
         with torch.cuda.stream(stream):
@@ -52,33 +53,50 @@ class _Run:
             self.t_cur = torch.empty(1, dtype=torch.int64, device=self.x.device)   # fixed address: the captured graph reads it
             self.step_idx = torch.zeros(1, dtype=torch.int32, device=self.x.device)   # likewise: the row of temb_table this step fetches
             unet.set_context(ctx, slot=slot)
+            if cache_interval > 1:       # this chain's own step cache: step i is full (and refills it) iff i % cache_interval == 0
+                self.cache = unet.step_cache(*self.x.shape[:1], *self.x.shape[2:])
 
     def step(self, i, rec, noise):
         x, eps = self.x, self.eps
+        sc = {} if self.cache is None else dict(step_cache=(self.cache, "use" if i % self.cache_interval else "fill"))
         with torch.cuda.stream(self.stream):
             if self.temb_table is not None:
                 self.step_idx.copy_(self.table_rows[i:i + 1], non_blocking=True)
                 self.unet.forward_parts([x, self.m, self.ml], self.t_cur, out=eps, graph=self.use_graph, slot=self.slot,
-                                        temb=(self.temb_table, self.step_idx))
+                                        temb=(self.temb_table, self.step_idx), **sc)
             else:
                 self.t_cur.copy_(self.ts_dev[i:i + 1], non_blocking=True)
-                self.unet.forward_parts([x, self.m, self.ml], self.t_cur, out=eps, graph=self.use_graph, slot=self.slot)
+                self.unet.forward_parts([x, self.m, self.ml], self.t_cur, out=eps, graph=self.use_graph, slot=self.slot, **sc)
             # the update is elementwise, so prev_sample overwrites the sample in place (stable pointers for the graph)
             launch_step(self.kind, rec, x, eps, noise, self.hist[rec.ring_m1] if rec.order >= 2 else None,
                         self.hist[rec.ring_m2] if rec.order >= 3 else None, self.hist[rec.ring_w] if self.hist else None, x, self.vpred,
                         _cabi.current_stream())
 
 
+def _check_cache_interval(cache_interval):
+    """denoise's cache_interval, checked before anything touches the device -> the int"""
+    if isinstance(cache_interval, bool) or not isinstance(cache_interval, (int, np.integer)) or cache_interval < 1:
+        raise ValueError(f"cache_interval must be an int >= 1, got {cache_interval!r}")
+    return int(cache_interval)
+
+
 @torch.no_grad()
 def denoise(unet, scheduler, latents, mask, masked_image_latents, encoder_hidden_states,
-            num_inference_steps, variance_noise=None, eta=0.0, callback=None, use_graph=True, micro_batches=1):
+            num_inference_steps, variance_noise=None, eta=0.0, callback=None, use_graph=True, micro_batches=1, cache_interval=1):
     """latents/masked_image_latents [B,4,h,w], mask [B,1,h,w] (already at latent resolution), context
     [B,S,1024]; all on the GPU.  variance_noise: optional [steps,B,4,h,w] injected in place of the
     per-step device randn of DDPMScheduler.step (app.ipynb:816).  Returns the final latents (fp32).
 
     micro_batches=n splits the batch into n independent chains (images do not interact), each on its own stream
     with its own captured graph: one chain's kernels fill the CUs the other chain's small / draining kernels
-    leave idle.  Results are identical to micro_batches=1 up to per-kernel tile-plan rounding."""
+    leave idle.  Results are identical to micro_batches=1 up to per-kernel tile-plan rounding.
+
+    cache_interval=n > 1 reuses the deep UNet features across steps (DeepCache; Ma et al., CVPR 2024): step i of the plan runs the whole
+    UNet iff i % n == 0 and keeps the tensor entering the last up-block; the other steps run only conv_in, down-block 0, the last up-block
+    on the kept tensor and the output layers (UNet2DConditionModel.forward_parts(step_cache=)).  Every step still produces an eps, so the
+    schedulers - DPM-Solver++'s history ring included - see nothing of it.  The result differs from the plain loop's by design (how much
+    depends on the weights; not a rounding effect).  n = 1 is the plain loop: no cache, the plain entry points."""
+    cache_interval = _check_cache_interval(cache_interval)
     _cabi.require_cuda(latents, mask, masked_image_latents, encoder_hidden_states)
     if scheduler.kind == _cabi.SCHED_DPMPP and (variance_noise is not None or eta != 0):
         raise ValueError("DPMSolverMultistepScheduler is deterministic: no variance_noise, eta = 0")
@@ -105,7 +123,7 @@ def denoise(unet, scheduler, latents, mask, masked_image_latents, encoder_hidden
         for j, (lo, hi) in enumerate(bounds):
             streams[j].wait_stream(main)
             runs.append(_Run(unet, scheduler, latents[lo:hi], mask[lo:hi], masked_image_latents[lo:hi],
-                             encoder_hidden_states[lo:hi].contiguous(), j, streams[j], use_graph, ts_dev, temb_table, table_rows))
+                             encoder_hidden_states[lo:hi].contiguous(), j, streams[j], use_graph, ts_dev, temb_table, table_rows, cache_interval))
         # the plan, one record per step, is all the loop knows about the scheduler; it is walked lazily, so that the host computes a step's
         # scalars while the GPU works through the steps already enqueued
         for i, rec in enumerate(scheduler.iter_plan(eta)):
@@ -132,11 +150,12 @@ def denoise(unet, scheduler, latents, mask, masked_image_latents, encoder_hidden
 
 @torch.no_grad()
 def edit_latents(unet, vae, scheduler, image, masked_image, mask, encoder_hidden_states, num_inference_steps,
-                 init_latents=None, generator=None, enc_noise=None, variance_noise=None):
+                 init_latents=None, generator=None, enc_noise=None, variance_noise=None, cache_interval=1):
     """The model part of text_editing() (app.ipynb:779-819): VAE-encode the masked crop, downsample the
     mask, denoise from seeded noise, VAE-decode.  `image` is unused by the arithmetic (the reference's encode of it,
     app.ipynb:781, is dead code: its result is overwritten at :798); enc_noise / variance_noise inject the two device-RNG
-    draws (latent_dist.sample(), DDPMScheduler.step) for tests.  Crop / resize / paste: diffute_amd.prepost."""
+    draws (latent_dist.sample(), DDPMScheduler.step) for tests.  Crop / resize / paste: diffute_amd.prepost.  cache_interval: denoise's."""
+    cache_interval = _check_cache_interval(cache_interval)
     sf = vae.config.scaling_factor
     f = 2 ** (len(vae.config.block_out_channels) - 1)
     m = mask_to_latent(mask, f)
@@ -146,14 +165,15 @@ def edit_latents(unet, vae, scheduler, image, masked_image, mask, encoder_hidden
     if init_latents is None:
         init_latents = torch.randn((B, vae.config.latent_channels, H // f, W // f),
                                    generator=torch.manual_seed(0), dtype=torch.float32).to(masked_image.device)  # :798
-    lat = denoise(unet, scheduler, init_latents, m, mlat, encoder_hidden_states, num_inference_steps, variance_noise=variance_noise)
+    lat = denoise(unet, scheduler, init_latents, m, mlat, encoder_hidden_states, num_inference_steps, variance_noise=variance_noise,
+                  cache_interval=cache_interval)
     return vae.decode(lat / sf).sample                                                    # app.ipynb:818-819
 
 
 @torch.no_grad()
 def edit_boxes(unet, vae, scheduler, instance_image, locations, encoder_hidden_states, num_inference_steps, *, origins=None,
                crop_scales=None, rng=None, batch_size=4, generator=None, enc_noise=None, variance_noise=None,
-               return_intermediate=False, size=512):
+               return_intermediate=False, size=512, cache_interval=1):
     """text_editing() (app.ipynb:674-846) for several boxes of ONE image as one batch: instance_image uint8 CUDA [h][w][3], locations
     N boxes (x1, y1, x2, y2), encoder_hidden_states [N,L,D] the glyph context of each box.  One preprocess_batch launch, the boxes
     through edit_latents in chunks of `batch_size` (the last chunk may be smaller), one postprocess_batch launch; returns the uint8
@@ -165,14 +185,15 @@ def edit_boxes(unet, vae, scheduler, instance_image, locations, encoder_hidden_s
     single call starts it.  enc_noise [N,4,h,w] / variance_noise [steps,N,4,h,w] inject the device-RNG draws as in edit_latents.
 
     Difference from N sequential text_editing() calls: every crop is taken from the ORIGINAL image, so box k's context does not contain
-    the edits of boxes < k.  The pastes are identical (a later box wins where boxes overlap)."""
+    the edits of boxes < k.  The pastes are identical (a later box wins where boxes overlap).  cache_interval: denoise's."""
     return _edit(False, unet, vae, scheduler, [instance_image], [locations], encoder_hidden_states, num_inference_steps, _one(origins),
-                 _one(crop_scales), rng, batch_size, generator, enc_noise, variance_noise, return_intermediate, size)
+                 _one(crop_scales), rng, batch_size, generator, enc_noise, variance_noise, return_intermediate, size, cache_interval)
 
 
 @torch.no_grad()
 def edit_pages(unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, *, origins=None, crop_scales=None,
-               rng=None, batch_size=4, generator=None, enc_noise=None, variance_noise=None, return_intermediate=False, size=512):
+               rng=None, batch_size=4, generator=None, enc_noise=None, variance_noise=None, return_intermediate=False, size=512,
+               cache_interval=1):
     """edit_boxes for boxes on SEVERAL pages as one batch - what a service holding requests for different images, or a training batch
     of one box per image, needs.  images: a list of P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device; locations: P lists of
     boxes (x1, y1, x2, y2); origins / crop_scales: None or P lists, as for edit_boxes per page (what is not given is planned page after
@@ -183,20 +204,21 @@ def edit_pages(unet, vae, scheduler, images, locations, encoder_hidden_states, n
     starts from the seed-0 single-sample draw), one postprocess_pages launch.  Returns the list of P edited pages, with
     return_intermediate=True also image_vae [N,3,S,S] and the preprocess dict.  With one page this is [edit_boxes(...)], bit for bit."""
     return _edit(True, unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, origins, crop_scales, rng,
-                 batch_size, generator, enc_noise, variance_noise, return_intermediate, size)
+                 batch_size, generator, enc_noise, variance_noise, return_intermediate, size, cache_interval)
 
 
 def _edit(paged, unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, origins, crop_scales, rng, batch_size,
-          generator, enc_noise, variance_noise, return_intermediate, size):
+          generator, enc_noise, variance_noise, return_intermediate, size, cache_interval=1):
     """edit_boxes (paged=False: one page, its lists wrapped into one-element lists) and edit_pages"""
     if int(batch_size) < 1:
         raise ValueError("batch_size must be at least 1")
+    cache_interval = _check_cache_interval(cache_interval)
     images, locations, origins, crop_scales, sizes, N = _page_lists(paged, images, locations, origins, crop_scales)
     _check_contexts(N, encoder_hidden_states)
     where = _plan_pages(paged, images, locations, sizes, origins, crop_scales, rng)
     pre = (prepost.preprocess_pages if paged else prepost.preprocess_batch)(*where, size=size)
     image_vae = _edit_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
-                           enc_noise, variance_noise, int(size))
+                           enc_noise, variance_noise, int(size), cache_interval)
     out = (prepost.postprocess_pages if paged else prepost.postprocess_batch)(image_vae, *where)
     return (out, image_vae, pre) if return_intermediate else out
 
@@ -263,7 +285,8 @@ def _plan_pages(paged, images, locations, sizes, origins, crop_scales, rng):
 
 
 @torch.no_grad()
-def _edit_rows(unet, vae, scheduler, pre, dev, encoder_hidden_states, num_inference_steps, bs, generator, enc_noise, variance_noise, S):
+def _edit_rows(unet, vae, scheduler, pre, dev, encoder_hidden_states, num_inference_steps, bs, generator, enc_noise, variance_noise, S,
+               cache_interval=1):
     """the model part of edit_boxes / edit_pages: the N rows of the preprocess dict `pre` through edit_latents in chunks of `bs` (the last
     chunk may be smaller) -> image_vae [N,3,S,S].  A row's page plays no part here."""
     N = pre["image"].shape[0]
@@ -277,7 +300,7 @@ def _edit_rows(unet, vae, scheduler, pre, dev, encoder_hidden_states, num_infere
                                  encoder_hidden_states[lo:hi], num_inference_steps,
                                  init_latents=init.expand(hi - lo, -1, -1, -1).contiguous(), generator=generator,
                                  enc_noise=None if enc_noise is None else enc_noise[lo:hi],
-                                 variance_noise=None if variance_noise is None else variance_noise[:, lo:hi]))
+                                 variance_noise=None if variance_noise is None else variance_noise[:, lo:hi], cache_interval=cache_interval))
     return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
 
@@ -335,7 +358,8 @@ def _check_verified_processor(ocr, processor, size):
 
 
 @torch.no_grad()
-def _candidate_rows(unet, vae, scheduler, pre, dev, ctx, num_inference_steps, seeds, bs, generator, enc_noise, variance_noise, S):
+def _candidate_rows(unet, vae, scheduler, pre, dev, ctx, num_inference_steps, seeds, bs, generator, enc_noise, variance_noise, S,
+                    cache_interval=1):
     """the generating half of the verified edits, after the preprocess: the N rows of the preprocess dict `pre`, whatever pages they come
     from -> image_vae [N,K,3,S,S].  Each box is VAE-encoded once; the N*K rows (box-major, candidate k from seeds[k]) go through denoise +
     vae.decode in chunks of `bs`.  With one seed this is _edit_rows' loop, chunk for chunk."""
@@ -359,7 +383,8 @@ def _candidate_rows(unet, vae, scheduler, pre, dev, ctx, num_inference_steps, se
         rows = torch.arange(lo, hi)
         box = (rows // K).tolist()
         lat = denoise(unet, scheduler, init[(rows % K).to(dev)].contiguous(), mask_lat[box], torch.cat([mlat[b] for b in box], 0), ctx[box],
-                      num_inference_steps, variance_noise=None if variance_noise is None else variance_noise[:, lo:hi])
+                      num_inference_steps, variance_noise=None if variance_noise is None else variance_noise[:, lo:hi],
+                      cache_interval=cache_interval)
         outs.append(vae.decode(lat / sf).sample)
         for b in range(b0, b1):
             if (b + 1) * K <= hi:
@@ -370,7 +395,7 @@ def _candidate_rows(unet, vae, scheduler, pre, dev, ctx, num_inference_steps, se
 @torch.no_grad()
 def edit_boxes_verified(unet, vae, scheduler, ocr, processor, instance_image, locations, encoder_hidden_states, labels, num_inference_steps, *,
                         candidates=4, seeds=None, min_score=None, batch_size=4, ocr_batch_size=32, origins=None, crop_scales=None, rng=None,
-                        generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False):
+                        generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False, cache_interval=1):
     """edit_boxes with a read-back: K = `candidates` edits per box from K starting noises, each read by the OCR model `ocr` (a
     VisionEncoderDecoderModel) against the text the box should show, the best-reading one pasted (the reference sketches the read-back at
     app.ipynb:842-846).  labels: int64 [N,T] token ids of the requested texts, -100 = padding (the tokenizer is out of scope).
@@ -384,16 +409,16 @@ def edit_boxes_verified(unet, vae, scheduler, ocr, processor, instance_image, lo
     on the device: no score is read on the host.  min_score: a box whose best candidate scores below it keeps the original pixels.
 
     Returns the uint8 [h][w][3] page, or a VerifiedEdit with return_intermediate=True.  candidates=1 with min_score=None returns the
-    page of edit_boxes with the same arguments, bit for bit."""
+    page of edit_boxes with the same arguments, bit for bit.  cache_interval: denoise's, for every chunk of candidate rows."""
     return _edit_verified(False, unet, vae, scheduler, ocr, processor, [instance_image], [locations], encoder_hidden_states, labels,
                           num_inference_steps, candidates, seeds, min_score, batch_size, ocr_batch_size, _one(origins), _one(crop_scales), rng,
-                          generator, enc_noise, variance_noise, size, return_intermediate)
+                          generator, enc_noise, variance_noise, size, return_intermediate, cache_interval)
 
 
 @torch.no_grad()
 def edit_pages_verified(unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps, *,
                         candidates=4, seeds=None, min_score=None, batch_size=4, ocr_batch_size=32, origins=None, crop_scales=None, rng=None,
-                        generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False):
+                        generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False, cache_interval=1):
     """edit_boxes_verified for boxes on several pages: images / locations / origins / crop_scales as for edit_pages, everything per box
     (encoder_hidden_states [N,L,D], labels [N,T], enc_noise [N,4,h,w]) page-major.  The N*K rows go through edit_boxes_verified's chunk
     loop, prepost.readback_pixel_values_pages, ocr.score and prepost.postprocess_select_pages - chunks cross page boundaries, no score is
@@ -401,16 +426,17 @@ def edit_pages_verified(unet, vae, scheduler, ocr, processor, images, locations,
     candidates=1 with min_score=None returns edit_pages' pages, bit for bit."""
     return _edit_verified(True, unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps,
                           candidates, seeds, min_score, batch_size, ocr_batch_size, origins, crop_scales, rng, generator, enc_noise,
-                          variance_noise, size, return_intermediate)
+                          variance_noise, size, return_intermediate, cache_interval)
 
 
 def _edit_verified(paged, unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps, candidates,
                    seeds, min_score, batch_size, ocr_batch_size, origins, crop_scales, rng, generator, enc_noise, variance_noise, size,
-                   return_intermediate):
+                   return_intermediate, cache_interval=1):
     """edit_boxes_verified (paged=False: one page, its lists wrapped into one-element lists) and edit_pages_verified.  Every argument is
     checked on the host side first: nothing touches the GPU and no crop is planned - so nothing is drawn from rng - before all have passed."""
     images, locations, origins, crop_scales, sizes, N = _page_lists(paged, images, locations, origins, crop_scales)
     K, seeds = _check_verified_counts(N, candidates, seeds, min_score, batch_size, ocr_batch_size)
+    cache_interval = _check_cache_interval(cache_interval)
     _check_verified_labels(ocr, N, encoder_hidden_states, labels)
     if paged:
         prepost.check_readback_boxes_pages([loc for l in locations for loc in l], [len(l) for l in locations], sizes)
@@ -420,7 +446,7 @@ def _edit_verified(paged, unet, vae, scheduler, ocr, processor, images, location
     where = _plan_pages(paged, images, locations, sizes, origins, crop_scales, rng)
     pre = (prepost.preprocess_pages if paged else prepost.preprocess_batch)(*where, size=int(size))
     image_vae = _candidate_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, seeds, int(batch_size),
-                                generator, enc_noise, variance_noise, int(size))
+                                generator, enc_noise, variance_noise, int(size), cache_interval)
     pixel_values = (prepost.readback_pixel_values_pages if paged else prepost.readback_pixel_values)(image_vae, *where, ip)
     scores = _score_candidates(ocr, pixel_values, labels, N, K, int(ocr_batch_size))
     out, choice = (prepost.postprocess_select_pages if paged else prepost.postprocess_select_batch)(image_vae, scores, *where, threshold=min_score)

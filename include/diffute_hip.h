@@ -554,6 +554,28 @@ int dmx_unet_forward_graph(dmx_unet* u, const float* f0, int c0, const float* f1
                            const int64_t* timesteps, int t_count, const void* context_cache, int ctx_len,
                            float* out, int B, int H, int W, void* workspace, size_t workspace_bytes, dmx_stream_t stream);
 
+/* Step cache (DeepCache-style reuse of the deep features across denoise steps; Ma et al., CVPR 2024).  The output of the deep part of
+ * the UNet - levels 1..3, the mid block, up-blocks 0..2 - changes slowly from step to step, so a loop may run it on some steps only.
+ * A FILL forward is dmx_unet_forward (bit-equal `out`) that also leaves the tensor entering the last up-block
+ * ([B*H*W][block_out_channels[1]] in the compute element type) and its GroupNorm statistics records in `cache`, a caller-owned device
+ * buffer of dmx_unet_step_cache_bytes(u, B, H, W) bytes, 16-byte aligned.  A USE forward runs only conv_in, down-block 0, up-block 3 (fed
+ * the kept tensor), conv_norm_out and conv_out: with the inputs of the FILL that wrote the cache it returns that forward's bits, with
+ * other inputs the shallow step of the cached algorithm.  Both need dmx_unet_workspace_bytes_cached (the larger of the two walks); the
+ * _graph form captures one hipGraph per (call, cache, mode).  The time-embedding sources of dmx_unet_use_temb_table* apply as usual.
+ * A cache serves USE forwards of the shape (B, H, W) and under the dmx_set_* switches it was filled with; refill it after changing either. */
+#define DMX_STEP_CACHE_FILL 1
+#define DMX_STEP_CACHE_USE 2
+size_t dmx_unet_step_cache_bytes(dmx_unet* u, int B, int H, int W);
+size_t dmx_unet_workspace_bytes_cached(dmx_unet* u, int B, int H, int W, int ctx_len);
+int dmx_unet_forward_cached(dmx_unet* u, const float* f0, int c0, const float* f1, int c1, const float* f2, int c2,
+                            const int64_t* timesteps, int t_count, const void* context_cache, int ctx_len,
+                            float* out, int B, int H, int W, void* cache, size_t cache_bytes, int mode,
+                            void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+int dmx_unet_forward_cached_graph(dmx_unet* u, const float* f0, int c0, const float* f1, int c1, const float* f2, int c2,
+                                  const int64_t* timesteps, int t_count, const void* context_cache, int ctx_len,
+                                  float* out, int B, int H, int W, void* cache, size_t cache_bytes, int mode,
+                                  void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+
 /* Validation / debugging entry points (tests only; the product path never calls them).
  *   dmx_unet_forward_taps   dmx_unet_forward that also copies out the block outputs conv_in, down0..3, mid, up0..3 (the points the
  *                           oracle taps, oracle/unet.py) as NCHW fp32, back to back, into `taps`; tap_shapes[4*i..] = (B, C, H, W).
