@@ -160,6 +160,9 @@ _PROTOS = {
     # ... and the weight-preparation kernels only the executors launch (tests/test_weight_pack_gpu.py)
     "dmx_test_ln_fold": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     "dmx_test_cast_pad_rows": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, _P]),
+    "dmx_test_compose_linear": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
+    "dmx_test_folded_tail_gn_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "dmx_test_folded_tail_gn": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "dmx_conv_gemm_workspace_bytes": (c_size_t, [POINTER(GemmDesc)]),
     "dmx_conv_gemm": (c_int, [POINTER(GemmDesc), _P, c_size_t, _P]),
     "dmx_conv_gemm_rowstats_tiles": (c_int, [POINTER(GemmDesc)]),
@@ -188,6 +191,7 @@ _PROTOS = {
     "dmx_xf_chain_ok": (c_int, [c_int, c_int]),
     "dmx_xf_chain": (c_int, [POINTER(XfChainDesc), c_int, _P]),
     "dmx_set_xf_chain": (c_int, [c_int]),
+    "dmx_set_ff_fold": (c_int, [c_int]),
     "dmx_set_weight_prefetch": (c_int, [c_int]),
     "dmx_groupnorm_from_stats": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_float, c_int, _P, _P, _P, c_int, _P]),
     "dmx_conv_wgrad_workspace_bytes": (c_size_t, [POINTER(GemmDesc), c_int]),

@@ -151,6 +151,7 @@ class Exec {
   // fp32 VALIDATION mode (ref_f32.hip): activations are floats (Tn::p points to float data), weights come from the fp32
   // master arena (callers pass float pointers typed as bf16*), every op runs the plain fp32 kernel.  Tests only.
   bool f32 = false;
+  bool ff_fold = dmx_ff_fold_enabled();   // dmx_set_ff_fold as this walk sees it (the workspace query walks both settings)
   const char* masters = nullptr;   // f32 mode: the caller's fp32 master arena, where weights-arena byte o lives at byte 2*o (null in dry walks)
   struct Weights {                 // where the parameters of this walk come from: at<T>(offset in the weights arena)
     const char* base; size_t mul;

@@ -66,7 +66,7 @@ int dmx_check_launch(const char* what) {
 // hash of the values is part of the key of the captured hipGraphs (unet_model.h GraphKey) and of the host mirror's workspace-size cache, so toggling
 // a switch after the first forward can neither replay a graph captured under another setting nor run a walk in a workspace sized for another one -
 // and switching BACK finds the graphs of the old setting again (a counter would strand them).
-static int g_plan_sw[DMX_SW_COUNT] = {1, 1, 1, 1, 1, 1, 1, 0, 1, 1, 1};      // the defaults of the switches, in DmxPlanSwitch order
+static int g_plan_sw[DMX_SW_COUNT] = {1, 1, 1, 1, 1, 1, 1, 0, 1, 1, 1, 1};      // the defaults of the switches, in DmxPlanSwitch order
 void dmx_plan_switch(int slot, int value) { if (slot >= 0 && slot < DMX_SW_COUNT) g_plan_sw[slot] = value; }
 void dmx_plan_epoch_bump() { ++g_plan_sw[DMX_SW_OVERRIDES]; }
 extern "C" int dmx_plan_epoch(void) {
@@ -219,6 +219,12 @@ extern "C" int dmx_set_defer_reduce(int on) { const int old = g_defer_reduce; g_
 static int g_halo_conv = 1;
 extern "C" int dmx_set_halo_conv(int on) { const int old = g_halo_conv; g_halo_conv = on; dmx_plan_switch(DMX_SW_HALO, on); return old; }
 bool dmx_halo_conv_enabled() { return g_halo_conv != 0; }
+
+// 1 (default): the non-chain transformer blocks run ff.net.2 and proj_out as ONE GEMM over the composed weights (unet.hip Fwd::xformer, fold.hip);
+// 0: the two launches
+static int g_ff_fold = 1;
+extern "C" int dmx_set_ff_fold(int on) { const int old = g_ff_fold; g_ff_fold = on ? 1 : 0; dmx_plan_switch(DMX_SW_FF_FOLD, g_ff_fold); return old; }
+bool dmx_ff_fold_enabled() { return g_ff_fold != 0; }
 
 // The per-forward pools (statistics records, stream-K / halo flags) are zeroed by a KERNEL node (dmx_zero16_launch), never by
 // hipMemsetAsync: a memset node of a captured hipGraph is not safe to replay on this runtime (ROCm 7.2, gfx950).  Measured in round 5

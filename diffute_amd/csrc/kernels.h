@@ -10,7 +10,7 @@ enum ProfClass { PROF_GEMM128 = 0, PROF_GEMM64 = 1, PROF_SPLITK = 2, PROF_ATTN =
                  PROF_GEMM_CFG0 = 10 /* one class per GEMM tile config (template instance): 10 + plan id */, PROF_XFCHAIN = 26 /* xf_chain.hip */, PROF_HALO = 27 /* conv_halo.hip */, PROF_SKINNY = 28 /* skinny.hip */, PROF_NCLASS = 29 };
 int n_cus();                                           // compute units of the CURRENT device (conv_halo.hip)
 // exec.hip: the plan signature (key of captured graphs / cached workspace sizes): every plan-changing switch records its value
-enum DmxPlanSwitch { DMX_SW_EXCLUSIVE = 0, DMX_SW_GN_STATS, DMX_SW_DEFER, DMX_SW_HALO, DMX_SW_PREFETCH, DMX_SW_XF_CHAIN, DMX_SW_HALO_WS, DMX_SW_OVERRIDES, DMX_SW_SKINNY, DMX_SW_HALO_PEERS, DMX_SW_ATTN_BALANCED, DMX_SW_COUNT };
+enum DmxPlanSwitch { DMX_SW_EXCLUSIVE = 0, DMX_SW_GN_STATS, DMX_SW_DEFER, DMX_SW_HALO, DMX_SW_PREFETCH, DMX_SW_XF_CHAIN, DMX_SW_HALO_WS, DMX_SW_OVERRIDES, DMX_SW_SKINNY, DMX_SW_HALO_PEERS, DMX_SW_ATTN_BALANCED, DMX_SW_FF_FOLD, DMX_SW_COUNT };
 void dmx_plan_switch(int slot, int value);
 void dmx_plan_epoch_bump();                            // (dmx_gemm_plan_override: a counter)
 extern "C" int dmx_plan_epoch(void);
@@ -86,6 +86,10 @@ int dmx_gemm_tiles_n(const GemmArgs& a);       // n-tiles of the plan that dmx_g
 int dmx_ups_phase_weights_launch(const bf16* w3, int ldw3, bf16* wp, int N, int Cin, hipStream_t stream);
 int dmx_ln_fold_launch(const bf16* w_raw, bf16* w_out, const float* gamma, const float* beta, const float* bias,
                        float* c1, float* c2, int N, int K, hipStream_t stream);
+// fold.hip: two back-to-back linears as one matrix: w_out [C][K + C] = [ round16(wpo [C][C] . wf2 [C][K]) | wpo ], b_out = bpo + wpo . bf2
+// (fp32 sums in a fixed order); two launches, nothing else - legal inside a stream capture
+int dmx_compose_linear_launch(const bf16* wpo, const bf16* wf2, const float* bf2, const float* bpo, bf16* w_out, float* b_out, int C, int K, hipStream_t stream);
+bool dmx_ff_fold_enabled();                            // dmx_set_ff_fold (exec.hip)
 
 // ------------------------------------------------------------------ conv_halo.hip
 // 3x3 stride-1 pad-1 convolution with a HALO input tile staged once per 64-channel chunk in LDS (the nine taps are shifted LDS

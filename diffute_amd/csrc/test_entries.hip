@@ -1,9 +1,10 @@
 // Test support (include/diffute_hip.h "test support"): extern "C" entries that reach the small training kernels which have no
 // operator-level entry of their own - train_small.hip's transposes, add, pointwise 1x1 and small-linear backward, norm.hip's row
 // softmax and vae_train.hip's casts (tests/test_train_small_gpu.py) - and the two weight-preparation kernels that only the model
-// executors launch: gemm.hip's folded-LayerNorm weights and elementwise.hip's padded context cast (tests/test_weight_pack_gpu.py).
-// Each entry checks its arguments and forwards to the *_launch function the graphs call; none does arithmetic of its own.
-#include "kernels.h"
+// executors launch: gemm.hip's folded-LayerNorm weights and elementwise.hip's padded context cast (tests/test_weight_pack_gpu.py); fold.hip's
+// composition and the folded block tail on the executor (tests/test_ff_fold_gpu.py).
+// Each entry checks its arguments and forwards to the *_launch function / executor op the graphs call; none does arithmetic of its own.
+#include "exec.h"
 #include "../../include/diffute_hip.h"
 
 #define ST(s) ((hipStream_t)(s))
@@ -87,6 +88,44 @@ extern "C" int dmx_test_ln_fold(const void* w_raw, void* w_out, const float* gam
                                 int N, int K, dmx_stream_t stream) {
   DMX_REQUIRE(w_raw && w_out && gamma && beta && c1 && c2 && N > 0 && K > 0, "test_ln_fold: bad argument");
   return dmx_ln_fold_launch((const bf16*)w_raw, (bf16*)w_out, gamma, beta, bias, c1, c2, N, K, ST(stream));
+}
+// w_out (16) [C][K + C] = [ round16(wpo [C][C] . wf2 [C][K]) | wpo ], b_out [C] = bpo + wpo . bf2; all dense, any C and K
+extern "C" int dmx_test_compose_linear(const void* wpo, const void* wf2, const float* bf2, const float* bpo, void* w_out, float* b_out, int C, int K, dmx_stream_t stream) {
+  DMX_REQUIRE(wpo && wf2 && bf2 && bpo && w_out && b_out && C > 0 && K > 0, "test_compose_linear: bad argument");
+  return dmx_compose_linear_launch((const bf16*)wpo, (const bf16*)wf2, bf2, bpo, (bf16*)w_out, b_out, C, K, ST(stream));
+}
+// The folded tail of a transformer block as the UNet walk runs it (unet.hip Fwd::xformer + the GroupNorm behind the block), on the executor:
+//   y = [g | h3] wfpo^T + bfpo + x  (Exec::conv, two K segments; g [B*HW][4C], h3 / x [B*HW][C], wfpo [C][5C]),  t = GroupNorm(y; groups, eps 1e-5, no activation)
+// mode 0: the GEMM completes y itself;  1: ConvOpts.defer - a split-K plan leaves its reduce pass to the GroupNorm, x (the residual that pass
+// adds) is dropped after it;  2: the same, but x is dropped BEFORE the GroupNorm (Exec::drop completes y first).  y and t are copied out dense.
+static int folded_tail_gn(Exec& ex, const void* g, const void* h3, const void* x, const void* wfpo, const float* bfpo, const float* gamma, const float* beta,
+                          int B, int HW, int C, int groups, int mode, void* y_out, void* t_out) {
+  auto ext = [&](const void* p, int c) { Tn t; t.p = (bf16*)p; t.B = B; t.H = 1; t.W = HW; t.C = c; t.ld = c; return t; };      // (not workspace memory: drop only runs the pending-reduce rule)
+  const Tn tg = ext(g, 4 * C), th3 = ext(h3, C), tx = ext(x, C);
+  ConvOpts o; o.ksize = 1; o.pad = 0; o.bias = bfpo; o.res = &tx; o.defer = mode ? 2 : 0;
+  Tn y = ex.conv(tg, &th3, (const bf16*)wfpo, C, o);
+  if (mode == 2) ex.drop(tx);
+  Tn t = ex.groupnorm(y, nullptr, gamma, beta, groups, 1e-5f, false);
+  if (mode != 2) ex.drop(tx);
+  if (!ex.dry && !ex.rc) {
+    const size_t nb = (size_t)B * HW * C * sizeof(bf16);
+    DMX_HIP(hipMemcpyAsync(y_out, y.p, nb, hipMemcpyDeviceToDevice, ex.stream));
+    DMX_HIP(hipMemcpyAsync(t_out, t.p, nb, hipMemcpyDeviceToDevice, ex.stream));
+  }
+  ex.drop(t); ex.drop(y);
+  return ex.rc;
+}
+extern "C" size_t dmx_test_folded_tail_gn_workspace_bytes(int B, int HW, int C, int groups, int mode) {
+  Exec ex = Exec::dry_run();
+  folded_tail_gn(ex, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, HW, C, groups, mode, nullptr, nullptr);
+  return ex.ws.peak() + 4096;
+}
+extern "C" int dmx_test_folded_tail_gn(const void* g, const void* h3, const void* x, const void* wfpo, const float* bfpo, const float* gamma, const float* beta,
+                                       int B, int HW, int C, int groups, int mode, void* y_out, void* t_out, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
+  DMX_REQUIRE(g && h3 && x && wfpo && bfpo && gamma && beta && y_out && t_out && workspace, "test_folded_tail_gn: null argument");
+  DMX_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 64 == 0 && groups > 0 && C % groups == 0 && mode >= 0 && mode <= 2, "test_folded_tail_gn: bad shape or mode");
+  Exec ex = Exec::on(ST(stream), workspace, workspace_bytes);
+  return folded_tail_gn(ex, g, h3, x, wfpo, bfpo, gamma, beta, B, HW, C, groups, mode, y_out, t_out);
 }
 // out (16) [B][Spad][C] = in (fp32, or 16-bit with in_is_16) [B][S][C], rows >= S zero
 extern "C" int dmx_test_cast_pad_rows(const void* in, int in_is_16, void* out, int B, int S, int Spad, int C, dmx_stream_t stream) {

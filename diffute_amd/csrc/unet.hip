@@ -54,6 +54,7 @@ void build_xf(dmx_unet* u, XfW& x, const std::string& p, int C, int heads) {
     pt.add(t + "ff.net.0.proj.bias", {8 * C}, r); x.bf1 = r.dst; }
   x.wf2 = pt.linear(t + "ff.net.2.weight", C, 4 * C); x.bf2 = pt.f32(t + "ff.net.2.bias", C);
   x.wpo = pt.linear(p + "proj_out.weight", C, C); x.bpo = pt.f32(p + "proj_out.bias", C);
+  x.wfpo = pt.reserve((size_t)C * 5 * C * 2); x.bfpo = pt.reserve((size_t)C * 4);      // derived: [Wpo Wf2 | Wpo], bpo + Wpo bf2 (fold_ready)
 }
 
 }  // namespace
@@ -151,6 +152,7 @@ DMX_MODEL_ABI(dmx_unet, unet)
 // Recompute everything derived from the raw weights in the arena (folded shortcut biases, LayerNorm-folded GEMM
 // weights and their c1 / c2 vectors) after the raw weights changed in place (fused optimizer); asynchronous.
 static int refresh_derived(dmx_unet* u, hipStream_t s) {
+  u->fold_stale = true;                                // (the composed ff.net.2 / proj_out weights follow at the next inference entry: fold_ready)
   int rc = for_each_resnet(u, [&](const ResW& r) { return resnet_finalize(r, u->arena, s); });
   for (int i = 0; i < 3 && !rc; ++i)
     rc = dmx_ups_phase_weights_launch(u->at<bf16>(u->up_us[i].w), 9 * u->up_us[i].c, u->at<bf16>(u->up_us[i].wp), u->up_us[i].c, u->up_us[i].c, s);
@@ -165,6 +167,24 @@ static int refresh_derived(dmx_unet* u, hipStream_t s) {
                                      u->at<float>(x->c1_f1), u->at<float>(x->c2_f1), 8 * C, C, s);
   }
   return rc;
+}
+// The composed weights of dmx_set_ff_fold, once per weights change, at the entry of an inference call: on the call's stream, in front of its
+// launches and - every caller asks before its own hipStreamBeginCapture - outside the library's graph capture.  Where the CALLER is capturing
+// the stream, the two launches per block become nodes of the caller's graph and the weights stay marked stale: nothing has run yet.
+// Two things follow from composing lazily, both the caller's to order (include/diffute_hip.h dmx_set_ff_fold):
+//   - the mark is cleared when the launches are ENQUEUED on `s`: an inference call on another stream right afterwards is not ordered behind
+//     them (dmx_unet_refresh_derived's own launches have the same contract with the stream they were given);
+//   - a graph the CALLER captured around an inference call while the fold was fresh holds no composition: replayed after a weights change it
+//     reads composed weights that are stale until some inference entry of the library has run on the new weights (they are rebuilt in place).
+static int fold_ready(dmx_unet* u, hipStream_t s) {
+  if (!u->fold_stale || !dmx_ff_fold_enabled()) return DMX_OK;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (s != nullptr && hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+  for (const XfW* x : u->xf_all)
+    if (const int rc = dmx_compose_linear_launch(u->at<bf16>(x->wpo), u->at<bf16>(x->wf2), u->at<float>(x->bf2), u->at<float>(x->bpo),
+                                                 u->at<bf16>(x->wfpo), u->at<float>(x->bfpo), x->C, 4 * x->C, s)) return rc;
+  if (cs == hipStreamCaptureStatusNone) u->fold_stale = false;
+  return DMX_OK;
 }
 extern "C" int dmx_unet_refresh_derived(dmx_unet* u, dmx_stream_t stream) {
   DMX_REQUIRE(u && u->arena && u->finalized, "unet_refresh_derived: weights not finalized");
@@ -355,6 +375,15 @@ struct Fwd {
     Exec::LnIn ln3; ln3.stats = st3.buf; ln3.tiles = st3.tiles; ln3.c1 = u->at<float>(w.c1_f1); ln3.c2 = u->at<float>(w.c2_f1);
     Tn g = ex.linear(h3, u->at<bf16>(w.wf1), 8 * C, nullptr, nullptr, true, nullptr, &ln3);
     ex.drop(st3.buf);
+    if (ex.ff_fold) {
+      // ff.net.2 + residual and proj_out + block residual as ONE GEMM with two K segments: y = [g | h3] [Wpo Wf2 | Wpo]^T + (Wpo bf2 + bpo) + x.
+      // It is the block's last op and a GroupNorm reads y next, so a split-K plan leaves its reduce pass to that GroupNorm (defer = 2, like a
+      // resnet's conv2): the caller keeps x - the residual that pass adds - alive until then (Exec::drop of x would complete y first).
+      ConvOpts o; o.ksize = 1; o.pad = 0; o.bias = u->at<float>(w.bfpo); o.res = &x; o.stats = 1; o.defer = 2;
+      Tn y = ex.conv(g, &h3, u->at<bf16>(w.wfpo), C, o);
+      ex.drop(g); ex.drop(h3);
+      return y;
+    }
     Tn h4 = ex.linear(g, u->at<bf16>(w.wf2), C, u->at<float>(w.bf2), &h3, false);
     ex.drop(g); ex.drop(h3);
     Tn y = ex.linear(h4, u->at<bf16>(w.wpo), C, u->at<float>(w.bpo), &x, false, nullptr, nullptr, true);   // (+ GroupNorm statistics for the next block)
@@ -532,6 +561,16 @@ int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c, StepCache& sc) {
   ex.tap(h);                                           // "conv_in"
   ex.ensure_stats(h);
   std::vector<Tn> skips; skips.push_back(h);
+  // The input of a transformer block whose folded last GEMM (dmx_set_ff_fold) left its split-K reduce pass to the GroupNorm that reads the block's
+  // output next: it is the residual that pass adds, so it lives until the op after the block has run (like mid_in below).  Dropping it then is
+  // right whatever that op was: one that is no GroupNorm has completed the output itself (Exec::flush), and Exec::drop completes it otherwise.
+  Tn held;
+  auto xf = [&](const XfW& w, Tn& y) {
+    Tn z = f.xformer(w, y);
+    if (z.pend >= 0) held = y; else ex.drop(y);
+    y = z;
+  };
+  auto drop_held = [&]() { if (held.p) { ex.drop(held); held = Tn(); } };
   for (int i = 0; i < (shallow ? 1 : 4); ++i) {
     for (int j = 0; j < L; ++j) {
 #ifdef DMX_PROBES
@@ -540,25 +579,30 @@ int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c, StepCache& sc) {
       constexpr bool fine = false;
 #endif
       Tn y = f.resnet(u->down_res[i][j], h, nullptr);
+      drop_held();
       if (fine) ex.tap(y);
-      if (cfg.down_has_attn[i]) { Tn z = f.xformer(u->down_xf[i][j], y); ex.drop(y); y = z; if (fine) ex.tap(y); }
+      if (cfg.down_has_attn[i]) { xf(u->down_xf[i][j], y); if (fine) ex.tap(y); }
       ex.ensure_stats(y);                             // (two GroupNorms read it: the next block's and the up path's concat)
       h = y; skips.push_back(h);                      // previous h stays alive as a skip
     }
     if (i < 3 && !shallow) {
       ConvOpts o; o.stride = 2; o.pad = 1; o.bias = f.W<float>(u->down_ds[i].b); o.stats = 1;
       h = ex.conv(h, nullptr, f.W<bf16>(u->down_ds[i].w), boc[i], o);
+      drop_held();
       ex.ensure_stats(h);
       skips.push_back(h);
     }
     ex.tap(h);                                         // "down{i}"
   }
+  if (shallow) drop_held();                              // (a shallow walk leaves the down path here)
   Tn mid_in;
   if (!shallow) {
-    Tn y = f.resnet(u->mid_res[0], h, nullptr);          // h is also skips.back(): keep it
-    Tn z = f.xformer(u->mid_xf, y); ex.drop(y);
+    Tn z = f.resnet(u->mid_res[0], h, nullptr);          // h is also skips.back(): keep it
+    drop_held();
+    xf(u->mid_xf, z);
     ex.ensure_stats(z);
     h = f.resnet(u->mid_res[1], z, nullptr); mid_in = z;
+    drop_held();
     ex.tap(h);                                         // "mid"
   } else {
     // the kept tensor in h's place: memory of the caller, not of the workspace (never dropped), complete (no pending reduce pass)
@@ -569,11 +613,12 @@ int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c, StepCache& sc) {
     for (int j = 0; j < L + 1; ++j) {
       Tn s = skips.back(); skips.pop_back();
       Tn y = f.resnet(u->up_res[i][j], h, &s);
+      drop_held();
       // (z is the residual of mid_res[1]'s conv2: where that conv left its split-K reduce to the GroupNorm that has just run, z had to live until here)
       if (i == 0 && j == 0) ex.drop(mid_in);
       if (!(shallow && j == 0)) ex.drop(h);
       ex.drop(s);
-      if (cfg.up_has_attn[i]) { Tn z = f.xformer(u->up_xf[i][j], y); ex.drop(y); y = z; }
+      if (cfg.up_has_attn[i]) xf(u->up_xf[i][j], y);
       ex.ensure_stats(y);
       h = y;
     }
@@ -582,6 +627,7 @@ int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c, StepCache& sc) {
       const bool direct = ex.f32;                                          // (the phase weights are derived data of the bf16 path)
       ConvOpts o; o.ups = 1; o.ups2 = direct ? 0 : 1; o.bias = f.W<float>(u->up_us[i].b); o.stats = 1;
       Tn y = ex.conv(h, nullptr, direct ? f.W<bf16>(u->up_us[i].w) : u->at<bf16>(u->up_us[i].wp), boc[3 - i], o);
+      drop_held();
       ex.ensure_stats(y);
       ex.drop(h); h = y;
       if (i == 2 && sc.mode == DMX_STEP_CACHE_FILL) {
@@ -600,6 +646,7 @@ int unet_run(dmx_unet* u, Exec& ex, const UNetCall& c, StepCache& sc) {
     ex.tap(h);                                         // "up{i}"
   }
   Tn t = ex.groupnorm(h, nullptr, f.W<float>(u->cno_g), f.W<float>(u->cno_b), cfg.norm_num_groups, 1e-5f, true);
+  drop_held();
   ex.drop(h);
   float* eps_nhwc = (float*)ex.raw((size_t)B * H * W * cfg.out_channels * 4);
   ConvOpts oo; oo.bias = f.W<float>(u->co_b); oo.out_f32 = 1;
@@ -638,6 +685,7 @@ UNetCall dry_call(int t_count, int ctx_len, int B, int H, int W) {
 #define UNET_CALL_RECORD UNetCall{f0, f1, f2, c0, c1, c2, (const long long*)timesteps, t_count, ctx, ctx_len, out, B, H, W}
 
 int forward_eager(dmx_unet* u, const UNetCall& c, StepCache sc, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (const int rc = fold_ready(u, stream)) return rc;
   Exec ex = Exec::on(stream, workspace, workspace_bytes);
   return unet_run_planned(u, ex, c, sc);
 }
@@ -668,12 +716,23 @@ int step_cache_record(dmx_unet* u, const UNetCall& c, void* cache, size_t cache_
 
 }  // namespace
 
+// peak of a dry walk under BOTH settings of dmx_set_ff_fold (a first-fit peak is not monotone in the op list: either may be the larger), so that
+// a workspace sized once serves the walk whichever way the switch stands and is never smaller than what the two-launch walk asked for
+static size_t walk_peak(dmx_unet* u, const UNetCall& c, const StepCache& sc) {
+  size_t need = 0;
+  for (int k = 0; k < 2; ++k) {
+    Exec ex = Exec::dry_run();
+    if (k) ex.ff_fold = !ex.ff_fold;
+    StepCache s = sc;
+    unet_run(u, ex, c, s);
+    if (ex.ws.peak() > need) need = ex.ws.peak();
+  }
+  return need;
+}
+
 extern "C" size_t dmx_unet_workspace_bytes(dmx_unet* u, int B, int H, int W, int ctx_len) {
   if (!u) return 0;
-  Exec ex = Exec::dry_run();
-  StepCache off;
-  unet_run(u, ex, dry_call(1, ctx_len, B, H, W), off);
-  size_t need = ex.ws.peak();
+  size_t need = walk_peak(u, dry_call(1, ctx_len, B, H, W), StepCache());
   // set_context needs the padded context + split-K scratch
   Exec e2 = Exec::dry_run();
   project_context(u, e2, nullptr, 0, 0, B, B, ctx_len, nullptr);
@@ -694,6 +753,7 @@ extern "C" int dmx_unet_forward_taps(dmx_unet* u, UNET_CALL_PARAMS, void* worksp
   const UNetCall c = UNET_CALL_RECORD;
   if (const int rc = unet_check_call(u, c, workspace, "unet_forward_taps")) return rc;
   DMX_REQUIRE(taps && tap_shapes && n_taps, "unet_forward_taps: null argument");
+  if (const int rc = fold_ready(u, (hipStream_t)stream)) return rc;
   TapSink sink; sink.buf = taps; sink.cap = tap_floats;
   Exec ex = Exec::on((hipStream_t)stream, workspace, workspace_bytes); ex.taps = &sink;
   StepCache off;
@@ -735,6 +795,7 @@ extern "C" int dmx_unet_forward_f32(dmx_unet* u, const void* masters, const floa
 bool dmx_profile_active();
 static int forward_graph(dmx_unet* u, const UNetCall& c, StepCache sc, void* workspace, size_t workspace_bytes, hipStream_t s) {
   if (s == nullptr || dmx_profile_active()) return forward_eager(u, c, sc, workspace, workspace_bytes, s);
+  if (const int rc = fold_ready(u, s)) return rc;      // (in front of a replay as well as of the capture below: never inside it)
   const dmx_unet::GraphKey key = u->graph_key(c, workspace, sc);
   dmx_unet::GraphEntry& e = u->graphs[key];
   if (e.exec) { DMX_HIP(hipGraphLaunch(e.exec, s)); return dmx_poll_device_error(); }      // (what an earlier replay raised: common.h)
@@ -770,10 +831,9 @@ extern "C" size_t dmx_unet_workspace_bytes_cached(dmx_unet* u, int B, int H, int
   size_t need = dmx_unet_workspace_bytes(u, B, H, W, ctx_len);      // (the FILL walk allocates what the plain walk allocates)
   // a first-fit peak is not monotone in the op list: the shallow walk is asked on its own
   const UNetCall c = dry_call(1, ctx_len, B, H, W);
-  Exec ex = Exec::dry_run();
   StepCache sc; sc.mode = DMX_STEP_CACHE_USE; sc.has_stats = step_cache_has_stats(u, c);
-  unet_run(u, ex, c, sc);
-  if (ex.ws.peak() + 4096 > need) need = ex.ws.peak() + 4096;
+  const size_t shallow = walk_peak(u, c, sc);
+  if (shallow + 4096 > need) need = shallow + 4096;
   return need;
 }
 extern "C" int dmx_unet_forward_cached(dmx_unet* u, UNET_CALL_PARAMS, void* cache, size_t cache_bytes, int mode,

@@ -14,6 +14,8 @@ struct XfW {
   size_t wqkv, wo1, bo1, wq2, wkv2, wo2, bo2, wf1, bf1, wf2, bf2, wpo, bpo;
   // folded LayerNorm: raw (as loaded) copies of the three LN-consuming weights + the derived c1 / c2 vectors
   size_t wqkv_raw, wq2_raw, wf1_raw, c1_qkv, c2_qkv, c1_q2, c2_q2, c1_f1, c2_f1;
+  // ff.net.2 and proj_out composed into one linear over [g | h3] (fold.hip): wfpo [C][5C] = [Wpo Wf2 | Wpo], bfpo [C] = bpo + Wpo bf2
+  size_t wfpo, bfpo;
 };
 struct ConvW { size_t w, b; int c; size_t wp = 0; /* upsamplers: derived [4][c][4c] phase weights */ };
 
@@ -73,6 +75,9 @@ struct dmx_unet : ModelBase {
   std::map<std::tuple<int, int, int, int>, bool> step_cache_stats;
   struct GraphEntry { hipGraphExec_t exec = nullptr; int seen = 0; };
   std::map<GraphKey, GraphEntry> graphs;
+  // the composed ff.net.2 / proj_out weights (XfW::wfpo / bfpo) lag the raw weights: derive() and dmx_unet_refresh_derived only set this, the
+  // next inference entry composes (unet.hip fold_ready) - a training step launches nothing for them
+  bool fold_stale = true;
   void drop_graphs() { for (auto& kv : graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec); graphs.clear(); }
   ~dmx_unet() override { drop_graphs(); }
   void rebound() override { drop_graphs(); }

@@ -97,6 +97,15 @@ int dmx_test_bf16_to_f32_rows(const void* in, int ldin, float* out, int M, int C
 int dmx_test_ln_fold(const void* w_raw, void* w_out, const float* gamma, const float* beta, const float* bias, float* c1, float* c2,
                      int N, int K, dmx_stream_t stream);
 int dmx_test_cast_pad_rows(const void* in, int in_is_16, void* out, int B, int S, int Spad, int C, dmx_stream_t stream);
+/* the composition behind dmx_set_ff_fold (tests/test_ff_fold_gpu.py): w_out (16) [C][K + C], row n = [ round16(sum_j wpo[n][j] * wf2[j][k]), k < K |
+ * wpo[n][0..C) ], from wpo (16) [C][C] and wf2 (16) [C][K]; b_out[n] = bpo[n] + sum_j wpo[n][j] * bf2[j].  fp32 sums in a fixed order; any C, K. */
+int dmx_test_compose_linear(const void* wpo, const void* wf2, const float* bf2, const float* bpo, void* w_out, float* b_out, int C, int K, dmx_stream_t stream);
+/* the folded block tail as the UNet walk runs it, on the executor: y (16) [B*HW][C] = [g (16) [B*HW][4C] | h3 (16) [B*HW][C]] wfpo^T + bfpo + x, then
+ * t (16) = GroupNorm(y; groups, eps 1e-5, no activation).  mode 0: the GEMM completes y itself; 1: a split-K plan leaves its reduce pass (with bfpo and x)
+ * to the GroupNorm; 2: as 1, but x is released before the GroupNorm, which completes y first.  The three give the same bits.  C a multiple of 64. */
+size_t dmx_test_folded_tail_gn_workspace_bytes(int B, int HW, int C, int groups, int mode);
+int dmx_test_folded_tail_gn(const void* g, const void* h3, const void* x, const void* wfpo, const float* bfpo, const float* gamma, const float* beta,
+                            int B, int HW, int C, int groups, int mode, void* y_out, void* t_out, void* workspace, size_t workspace_bytes, dmx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Operator level.  Used by the parity tests and by the executors.
@@ -321,6 +330,16 @@ typedef struct {
 int dmx_xf_chain_ok(int M, int C);
 int dmx_xf_chain(const dmx_xf_chain_desc* d, int mode, dmx_stream_t stream);
 int dmx_set_xf_chain(int on);
+/* ff.net.2 + proj_out of the transformer blocks that run as separate GEMMs (the levels the chains do not take) as ONE GEMM over
+ * [g | h3] with the composed weights [Wpo Wf2 | Wpo] and bias Wpo bf2 + bpo: 1 (default) on, 0 the two launches; returns the old setting.
+ * The composed weights are derived data: the first dmx_unet_forward* call after the weights changed (finalize, dmx_unet_refresh_derived)
+ * composes them on its stream, before its own launches and outside its own graph capture; dmx_unet_refresh_derived itself only marks them stale.
+ * What the caller orders: (a) that composition is enqueued on the stream of the call that finds the weights stale - an inference call on ANOTHER
+ * stream must be ordered behind that call (event / synchronise), as behind dmx_unet_refresh_derived; (b) a graph the caller itself captured around
+ * dmx_unet_forward* while the composed weights were fresh contains no composition: after a weights change, make one dmx_unet_forward* call outside
+ * that graph (it recomposes in place, same addresses) before replaying it - every other derived weight is rebuilt by dmx_unet_refresh_derived
+ * itself, the composed ones are not.  A graph captured while they were stale contains the composition and recomposes at every replay. */
+int dmx_set_ff_fold(int on);
 int dmx_set_weight_prefetch(int on); /* tuning aid: 0 = the launches of dmx_unet_forward* do not touch the weights of the launches that follow them
                                       * (default 1: every GEMM / attention / halo-conv / chain launch prefetches up to 4 MB of them into the memory-side
                                       * cache - the plan comes from a dry walk of the same graph); returns the old setting */
