@@ -1,6 +1,5 @@
 // extern "C" operator-level entry points declared in include/diffute_hip.h.
 #include "kernels.h"
-#include "../../include/diffute_hip.h"
 
 const char* dmx_get_error();
 

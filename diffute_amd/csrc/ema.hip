@@ -9,7 +9,7 @@
 // The 16-bit types are named explicitly (__bf16 / _Float16), not through common.h's build-dependent element type: the
 // bf16 and the fp16 builds of the library run the same arithmetic here.
 #include "common.h"
-#include "../../include/diffute_hip.h"
+#include "kernels.h"
 
 namespace {
 

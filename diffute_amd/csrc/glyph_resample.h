@@ -5,7 +5,7 @@
 //   input and output size are equal is skipped (table offset < 0).
 // The thread recomputes the horizontally-resampled bytes its vertical taps need.
 #pragma once
-#include "../../include/diffute_hip.h"
+#include "kernels.h"
 
 namespace dmx_glyph {
 #ifdef __HIPCC__

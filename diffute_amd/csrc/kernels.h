@@ -2,6 +2,7 @@
 #pragma once
 #include <vector>
 #include "common.h"
+#include "../../include/diffute_hip.h"          // the public C ABI: every extern "C" definition is compiled against its declaration
 
 // ------------------------------------------------------------------ profiler (exec.hip)
 // Optional per-kernel-class timing with hipEvents on the launch stream (bench.py roofline leg).
@@ -13,7 +14,6 @@ int n_cus();                                           // compute units of the C
 enum DmxPlanSwitch { DMX_SW_EXCLUSIVE = 0, DMX_SW_GN_STATS, DMX_SW_DEFER, DMX_SW_HALO, DMX_SW_PREFETCH, DMX_SW_XF_CHAIN, DMX_SW_HALO_WS, DMX_SW_OVERRIDES, DMX_SW_SKINNY, DMX_SW_HALO_PEERS, DMX_SW_ATTN_BALANCED, DMX_SW_FF_FOLD, DMX_SW_COUNT };
 void dmx_plan_switch(int slot, int value);
 void dmx_plan_epoch_bump();                            // (dmx_gemm_plan_override: a counter)
-extern "C" int dmx_plan_epoch(void);
 int dmx_exclusive_device();                            // dmx_set_exclusive_device (conv_halo.hip): 0 = plans that need co-resident blocks are off
 void dmx_profile_note_symbol(const char* sym);         // kernel symbol of the launch inside the innermost open ProfScope (exec.hip)
 struct ProfScope {
@@ -411,7 +411,6 @@ int dmx_linear_small_launch(const float* x, int ldx, const bf16* w, int ldw, con
                             int B, int N, int K, int silu_in, hipStream_t stream);
 
 // ------------------------------------------------------------------ sched.hip
-struct dmx_sched_row_rec;                              // include/diffute_hip.h: one step - the scheduler scalars, use_noise, ring slots, timestep
 // the scalar entries: one record by value over n elements; noise / m1 / m2 / x0_out as the entry of `kind` (DMX_SCHED_*) takes them, NULL otherwise
 int dmx_sched_step_launch(int kind, const dmx_sched_row_rec& rec, const float* x, const float* eps, const float* noise, const float* m1,
                           const float* m2, float* x0_out, float* out, size_t n, int vpred, hipStream_t stream);
@@ -424,8 +423,6 @@ int dmx_add_noise_launch(const float* x0, const float* noise, const float* sa, c
 int dmx_gaussian_sample_launch(const float* moments, const float* noise, float* out, int B, int C, int HW, float scale, hipStream_t stream);
 
 // ------------------------------------------------------------------ prepost_batch.hip
-struct dmx_edit_item;                                  // include/diffute_hip.h
-struct dmx_edit_page;
 // the host-side checks of an item table, shared by every entry that takes one (prepost_batch.hip, readback.hip): a bad item is reported by
 // index through the last-error string; `prepared` also compares the derived fields with what dmx_edit_items_prepare fills.
 // dmx_check_edit_pages: the same for a page table and every page's slice of the item table (bad pages by page index, bad items by their

@@ -9,7 +9,6 @@
 #include "kernels.h"
 #include "prepost_resize.h"
 #include "glyph_resample.h"
-#include "../../include/diffute_hip.h"
 #include <math.h>
 
 namespace {

@@ -10,7 +10,6 @@
 #include "common.h"
 #include "kernels.h"
 #include "prepost_resize.h"
-#include "../../include/diffute_hip.h"
 
 namespace {
 using namespace dmx_resize;

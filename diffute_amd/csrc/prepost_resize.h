@@ -14,7 +14,7 @@
 #pragma once
 #include <math.h>
 #include <stddef.h>
-#include "../../include/diffute_hip.h"
+#include "kernels.h"
 
 namespace dmx_resize {
 // What a resize needs besides the pixels: where the crop sits in the image, its extent clipped at the border (numpy slicing

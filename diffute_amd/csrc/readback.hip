@@ -12,7 +12,6 @@
 #include "kernels.h"
 #include "prepost_resize.h"
 #include "glyph_resample.h"
-#include "../../include/diffute_hip.h"
 
 namespace {
 using namespace dmx_resize;

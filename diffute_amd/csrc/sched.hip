@@ -7,7 +7,6 @@
 // sched_span is the one loop around them, so a row is the same bits through either entry.
 #include "common.h"
 #include "kernels.h"
-#include "../../include/diffute_hip.h"
 
 // DDIM: x0 = (x - sqrt(1-abar_t)*eps)/sqrt(abar_t); prev = sqrt(abar_p)*x0 + dir*eps (+ std*noise)
 __device__ __forceinline__ float ddim_elem(float xv, float ev, bool has_noise, float nz, float sqrt_bt, float sqrt_at, float sqrt_ap, float dir_coef,

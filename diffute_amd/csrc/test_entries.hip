@@ -5,7 +5,6 @@
 // composition and the folded block tail on the executor (tests/test_ff_fold_gpu.py).
 // Each entry checks its arguments and forwards to the *_launch function / executor op the graphs call; none does arithmetic of its own.
 #include "exec.h"
-#include "../../include/diffute_hip.h"
 
 #define ST(s) ((hipStream_t)(s))
 

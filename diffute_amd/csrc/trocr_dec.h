@@ -3,7 +3,6 @@
 #pragma once
 #include <vector>
 #include "exec.h"
-#include "../../include/diffute_hip.h"
 
 // byte offsets of one layer's parameters in the weights arena
 struct DecLayer { size_t wqkv, bqkv, wo, bo, l1g, l1b, wcq, bcq, wco, bco, l2g, l2b, w1, b1, w2, b2, l3g, l3b; };

@@ -6,7 +6,6 @@
 #include <tuple>
 #include <vector>
 #include "exec.h"
-#include "../../include/diffute_hip.h"
 
 struct XfW {
   int C = 0, heads = 0, ctx_slot = -1;

@@ -10,7 +10,6 @@
 #include <string>
 #include <vector>
 #include "exec.h"
-#include "../../include/diffute_hip.h"
 
 namespace {
 struct VitLayer { size_t l1g, l1b, wqkv, bqkv, wo, bo, l2g, l2b, w1, b1, w2, b2; };

@@ -20,10 +20,7 @@ BILINEAR, BICUBIC = 2, 3                     # PIL.Image.Resampling values, as s
 _PRECISION_BITS = 32 - 8 - 2                 # Resample.c
 _CONFIG_NAME = "preprocessor_config.json"
 
-# include/diffute_hip.h dmx_glyph_image
-_DESC = np.dtype([("src", "<u8"), ("stride_y", "<i8"), ("stride_x", "<i8"), ("stride_c", "<i8"), ("H", "<i4"), ("W", "<i4"),
-                  ("h_off", "<i4"), ("h_taps", "<i4"), ("v_off", "<i4"), ("v_taps", "<i4")])
-assert _DESC.itemsize == 56
+_DESC = np.dtype(_cabi.GlyphImage)           # include/diffute_hip.h dmx_glyph_image
 
 
 def _filter_weights(x, resample):

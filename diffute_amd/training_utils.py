@@ -27,11 +27,10 @@ import torch
 
 from . import _cabi
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}          # DMX_DT_* (include/diffute_hip.h)
-_EMA, _COPY = 0, 1                                                      # DMX_MULTI_*
+_DT = {torch.float32: _cabi.DT_F32, torch.bfloat16: _cabi.DT_BF16, torch.float16: _cabi.DT_F16}
+_EMA, _COPY = _cabi.MULTI_EMA, _cabi.MULTI_COPY
 _CHUNK = 65536                                                          # elements per table entry (a multiple of 4: aligned tensors give aligned chunks)
-_ENTRY = np.dtype([("dst", "<u8"), ("src", "<u8"), ("count", "<u4"), ("dst_dtype", "u1"), ("src_dtype", "u1"),
-                   ("mode", "u1"), ("reserved", "u1")])                 # dmx_multi_chunk, 24 bytes
+_ENTRY = np.dtype(_cabi.MultiChunk)                                     # include/diffute_hip.h dmx_multi_chunk
 
 
 def _runs_to_table(runs):
