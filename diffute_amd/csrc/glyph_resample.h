@@ -14,6 +14,13 @@ __device__ __forceinline__ int clip8(int v) { v >>= 22; return v < 0 ? 0 : (v > 
 // One pass table set of one source image: offsets (in ints) into `tab`, < 0 = pass skipped; taps = coefficient row length.
 struct Passes { int h_off, h_taps, v_off, v_taps; };
 
+// The source span [lo, lo + n) that output index o of one pass (table at `off`, not skipped) reads, clamped to the `src` source pixels.
+// glyph_resample_pixel reads its bounds through this; a kernel that stages source pixels first (glyph_text.hip) asks it what to stage.
+__device__ __forceinline__ void pass_span(const int* tab, int off, int taps, int o, int src, int& lo, int& n) {
+  const int* t = tab + off;
+  lo = min(max(t[2 * o], 0), src - 1); n = min(min(t[2 * o + 1], taps), min(src - lo, DMX_GLYPH_MAX_TAPS));
+}
+
 // Destination pixel (ox, oy) of an S_h x S_w output from a src_h x src_w source; px(y, x, c) -> the source byte.  The tables come
 // from device memory the entry cannot inspect: every bound is clamped to the source, so a bad table reads wrong pixels, never outside.
 template <class Px>
@@ -22,14 +29,12 @@ __device__ __forceinline__ void glyph_resample_pixel(Px px, int src_h, int src_w
   int xmin = ox, xn = 1, ymin = oy, yn = 1;
   const int *kh = nullptr, *kv = nullptr;
   if (d.h_off >= 0) {
-    const int* t = tab + d.h_off;
-    xmin = min(max(t[2 * ox], 0), src_w - 1); xn = min(min(t[2 * ox + 1], d.h_taps), min(src_w - xmin, DMX_GLYPH_MAX_TAPS));
-    kh = t + 2 * S_w + (size_t)ox * d.h_taps;
+    pass_span(tab, d.h_off, d.h_taps, ox, src_w, xmin, xn);
+    kh = tab + d.h_off + 2 * S_w + (size_t)ox * d.h_taps;
   } else xmin = min(xmin, src_w - 1);
   if (d.v_off >= 0) {
-    const int* t = tab + d.v_off;
-    ymin = min(max(t[2 * oy], 0), src_h - 1); yn = min(min(t[2 * oy + 1], d.v_taps), min(src_h - ymin, DMX_GLYPH_MAX_TAPS));
-    kv = t + 2 * S_h + (size_t)oy * d.v_taps;
+    pass_span(tab, d.v_off, d.v_taps, oy, src_h, ymin, yn);
+    kv = tab + d.v_off + 2 * S_h + (size_t)oy * d.v_taps;
   } else ymin = min(ymin, src_h - 1);
   int acc[3] = {1 << 21, 1 << 21, 1 << 21}, h[3] = {0, 0, 0};
   for (int j = 0; j < yn; ++j) {

@@ -12,7 +12,7 @@ inside the loop.
 import numpy as np
 import torch
 
-from . import _cabi, prepost
+from . import _cabi, glyphs, prepost
 from .schedulers import launch_step
 
 
@@ -173,7 +173,7 @@ def edit_latents(unet, vae, scheduler, image, masked_image, mask, encoder_hidden
 @torch.no_grad()
 def edit_boxes(unet, vae, scheduler, instance_image, locations, encoder_hidden_states, num_inference_steps, *, origins=None,
                crop_scales=None, rng=None, batch_size=4, generator=None, enc_noise=None, variance_noise=None,
-               return_intermediate=False, size=512, cache_interval=1):
+               return_intermediate=False, size=512, cache_interval=1, texts=None, glyph=None):
     """text_editing() (app.ipynb:674-846) for several boxes of ONE image as one batch: instance_image uint8 CUDA [h][w][3], locations
     N boxes (x1, y1, x2, y2), encoder_hidden_states [N,L,D] the glyph context of each box.  One preprocess_batch launch, the boxes
     through edit_latents in chunks of `batch_size` (the last chunk may be smaller), one postprocess_batch launch; returns the uint8
@@ -185,15 +185,19 @@ def edit_boxes(unet, vae, scheduler, instance_image, locations, encoder_hidden_s
     single call starts it.  enc_noise [N,4,h,w] / variance_noise [steps,N,4,h,w] inject the device-RNG draws as in edit_latents.
 
     Difference from N sequential text_editing() calls: every crop is taken from the ORIGINAL image, so box k's context does not contain
-    the edits of boxes < k.  The pastes are identical (a later box wins where boxes overlap).  cache_interval: denoise's."""
+    the edits of boxes < k.  The pastes are identical (a later box wins where boxes overlap).  cache_interval: denoise's.
+
+    texts / glyph: instead of encoder_hidden_states (pass None there), the N strings the boxes should show and
+    glyph = (renderer, processor, encoder) - a GlyphRenderer, a TrOCRProcessor and a TrOCREncoder; the contexts are then
+    glyph_contexts(texts, *glyph), rendered on the device.  Exactly one of encoder_hidden_states and texts must be given."""
     return _edit(False, unet, vae, scheduler, [instance_image], [locations], encoder_hidden_states, num_inference_steps, _one(origins),
-                 _one(crop_scales), rng, batch_size, generator, enc_noise, variance_noise, return_intermediate, size, cache_interval)
+                 _one(crop_scales), rng, batch_size, generator, enc_noise, variance_noise, return_intermediate, size, cache_interval, texts, glyph)
 
 
 @torch.no_grad()
 def edit_pages(unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, *, origins=None, crop_scales=None,
                rng=None, batch_size=4, generator=None, enc_noise=None, variance_noise=None, return_intermediate=False, size=512,
-               cache_interval=1):
+               cache_interval=1, texts=None, glyph=None):
     """edit_boxes for boxes on SEVERAL pages as one batch - what a service holding requests for different images, or a training batch
     of one box per image, needs.  images: a list of P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device; locations: P lists of
     boxes (x1, y1, x2, y2); origins / crop_scales: None or P lists, as for edit_boxes per page (what is not given is planned page after
@@ -202,20 +206,22 @@ def edit_pages(unet, vae, scheduler, images, locations, encoder_hidden_states, n
 
     One preprocess_pages launch, the N rows through edit_latents in chunks of `batch_size` (chunks cross page boundaries; every box
     starts from the seed-0 single-sample draw), one postprocess_pages launch.  Returns the list of P edited pages, with
-    return_intermediate=True also image_vae [N,3,S,S] and the preprocess dict.  With one page this is [edit_boxes(...)], bit for bit."""
+    return_intermediate=True also image_vae [N,3,S,S] and the preprocess dict.  With one page this is [edit_boxes(...)], bit for bit.
+    texts / glyph: as for edit_boxes, N strings page-major."""
     return _edit(True, unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, origins, crop_scales, rng,
-                 batch_size, generator, enc_noise, variance_noise, return_intermediate, size, cache_interval)
+                 batch_size, generator, enc_noise, variance_noise, return_intermediate, size, cache_interval, texts, glyph)
 
 
 def _edit(paged, unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, origins, crop_scales, rng, batch_size,
-          generator, enc_noise, variance_noise, return_intermediate, size, cache_interval=1):
+          generator, enc_noise, variance_noise, return_intermediate, size, cache_interval=1, texts=None, glyph=None):
     """edit_boxes (paged=False: one page, its lists wrapped into one-element lists) and edit_pages"""
     if int(batch_size) < 1:
         raise ValueError("batch_size must be at least 1")
     cache_interval = _check_cache_interval(cache_interval)
     images, locations, origins, crop_scales, sizes, N = _page_lists(paged, images, locations, origins, crop_scales)
-    _check_contexts(N, encoder_hidden_states)
+    _check_contexts(N, encoder_hidden_states, texts, glyph)
     where = _plan_pages(paged, images, locations, sizes, origins, crop_scales, rng)
+    encoder_hidden_states = _contexts(encoder_hidden_states, texts, glyph)
     pre = (prepost.preprocess_pages if paged else prepost.preprocess_batch)(*where, size=size)
     image_vae = _edit_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
                            enc_noise, variance_noise, int(size), cache_interval)
@@ -249,9 +255,27 @@ def _plan_boxes(locations, h, w, origins, crop_scales, rng):
     return crop_scales, origins
 
 
-def _check_contexts(N, encoder_hidden_states):
-    if encoder_hidden_states.shape[0] != N:
-        raise ValueError(f"{N} boxes but {encoder_hidden_states.shape[0]} glyph contexts")
+def _check_contexts(N, encoder_hidden_states, texts=None, glyph=None):
+    """the context arguments of the four edit functions: exactly one of encoder_hidden_states [N,L,D] and texts (N strings, which need
+    glyph = (renderer, processor, encoder)).  Host work only - a text the atlas cannot lay out raises here, before anything is launched."""
+    if (encoder_hidden_states is None) == (texts is None):
+        raise ValueError("exactly one of encoder_hidden_states and texts must be given")
+    if texts is None:
+        if encoder_hidden_states.shape[0] != N:
+            raise ValueError(f"{N} boxes but {encoder_hidden_states.shape[0]} glyph contexts")
+        return
+    if glyph is None:
+        raise ValueError("texts needs glyph=(renderer, processor, encoder)")
+    if not isinstance(glyph, (tuple, list)) or len(glyph) != 3 or not isinstance(getattr(glyph[0], "atlas", None), glyphs.GlyphAtlas):
+        raise ValueError("glyph must be a (renderer, processor, encoder) triple: a GlyphRenderer, a TrOCRProcessor, a TrOCREncoder")
+    if isinstance(texts, str) or len(texts) != N:
+        raise ValueError(f"{N} boxes but " + ("one str, not a list of texts" if isinstance(texts, str) else f"{len(texts)} texts"))
+    glyphs.layout(glyph[0].atlas, texts)
+
+
+def _contexts(encoder_hidden_states, texts, glyph):
+    """what _check_contexts passed -> the contexts [N,L,D]"""
+    return encoder_hidden_states if texts is None else glyphs.glyph_contexts(list(texts), *glyph)
 
 
 def _page_lists(paged, images, locations, origins, crop_scales):
@@ -331,8 +355,8 @@ def _check_verified_counts(N, candidates, seeds, min_score, batch_size, ocr_batc
     return K, seeds
 
 
-def _check_verified_labels(ocr, N, encoder_hidden_states, labels):
-    _check_contexts(N, encoder_hidden_states)
+def _check_verified_labels(ocr, N, encoder_hidden_states, labels, texts=None, glyph=None):
+    _check_contexts(N, encoder_hidden_states, texts, glyph)
     if not torch.is_tensor(labels) or labels.dtype != torch.int64:
         raise ValueError(f"labels must be an int64 tensor, got {getattr(labels, 'dtype', type(labels))}")
     if labels.ndim != 2 or labels.shape[0] != N or labels.shape[1] < 1:
@@ -395,7 +419,8 @@ def _candidate_rows(unet, vae, scheduler, pre, dev, ctx, num_inference_steps, se
 @torch.no_grad()
 def edit_boxes_verified(unet, vae, scheduler, ocr, processor, instance_image, locations, encoder_hidden_states, labels, num_inference_steps, *,
                         candidates=4, seeds=None, min_score=None, batch_size=4, ocr_batch_size=32, origins=None, crop_scales=None, rng=None,
-                        generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False, cache_interval=1):
+                        generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False, cache_interval=1, texts=None,
+                        glyph=None):
     """edit_boxes with a read-back: K = `candidates` edits per box from K starting noises, each read by the OCR model `ocr` (a
     VisionEncoderDecoderModel) against the text the box should show, the best-reading one pasted (the reference sketches the read-back at
     app.ipynb:842-846).  labels: int64 [N,T] token ids of the requested texts, -100 = padding (the tokenizer is out of scope).
@@ -409,41 +434,44 @@ def edit_boxes_verified(unet, vae, scheduler, ocr, processor, instance_image, lo
     on the device: no score is read on the host.  min_score: a box whose best candidate scores below it keeps the original pixels.
 
     Returns the uint8 [h][w][3] page, or a VerifiedEdit with return_intermediate=True.  candidates=1 with min_score=None returns the
-    page of edit_boxes with the same arguments, bit for bit.  cache_interval: denoise's, for every chunk of candidate rows."""
+    page of edit_boxes with the same arguments, bit for bit.  cache_interval: denoise's, for every chunk of candidate rows.
+    texts / glyph: as for edit_boxes, in place of encoder_hidden_states (labels stay token ids: the tokenizer is out of scope)."""
     return _edit_verified(False, unet, vae, scheduler, ocr, processor, [instance_image], [locations], encoder_hidden_states, labels,
                           num_inference_steps, candidates, seeds, min_score, batch_size, ocr_batch_size, _one(origins), _one(crop_scales), rng,
-                          generator, enc_noise, variance_noise, size, return_intermediate, cache_interval)
+                          generator, enc_noise, variance_noise, size, return_intermediate, cache_interval, texts, glyph)
 
 
 @torch.no_grad()
 def edit_pages_verified(unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps, *,
                         candidates=4, seeds=None, min_score=None, batch_size=4, ocr_batch_size=32, origins=None, crop_scales=None, rng=None,
-                        generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False, cache_interval=1):
+                        generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False, cache_interval=1, texts=None,
+                        glyph=None):
     """edit_boxes_verified for boxes on several pages: images / locations / origins / crop_scales as for edit_pages, everything per box
     (encoder_hidden_states [N,L,D], labels [N,T], enc_noise [N,4,h,w]) page-major.  The N*K rows go through edit_boxes_verified's chunk
     loop, prepost.readback_pixel_values_pages, ocr.score and prepost.postprocess_select_pages - chunks cross page boundaries, no score is
     read on the host.  Returns the list of P pages, or a VerifiedEdit whose `image` is that list with return_intermediate=True.
-    candidates=1 with min_score=None returns edit_pages' pages, bit for bit."""
+    candidates=1 with min_score=None returns edit_pages' pages, bit for bit.  texts / glyph: as for edit_boxes, page-major."""
     return _edit_verified(True, unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps,
                           candidates, seeds, min_score, batch_size, ocr_batch_size, origins, crop_scales, rng, generator, enc_noise,
-                          variance_noise, size, return_intermediate, cache_interval)
+                          variance_noise, size, return_intermediate, cache_interval, texts, glyph)
 
 
 def _edit_verified(paged, unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps, candidates,
                    seeds, min_score, batch_size, ocr_batch_size, origins, crop_scales, rng, generator, enc_noise, variance_noise, size,
-                   return_intermediate, cache_interval=1):
+                   return_intermediate, cache_interval=1, texts=None, glyph=None):
     """edit_boxes_verified (paged=False: one page, its lists wrapped into one-element lists) and edit_pages_verified.  Every argument is
     checked on the host side first: nothing touches the GPU and no crop is planned - so nothing is drawn from rng - before all have passed."""
     images, locations, origins, crop_scales, sizes, N = _page_lists(paged, images, locations, origins, crop_scales)
     K, seeds = _check_verified_counts(N, candidates, seeds, min_score, batch_size, ocr_batch_size)
     cache_interval = _check_cache_interval(cache_interval)
-    _check_verified_labels(ocr, N, encoder_hidden_states, labels)
+    _check_verified_labels(ocr, N, encoder_hidden_states, labels, texts, glyph)
     if paged:
         prepost.check_readback_boxes_pages([loc for l in locations for loc in l], [len(l) for l in locations], sizes)
     else:
         prepost.check_readback_boxes(locations[0], *sizes[0])
     ip = _check_verified_processor(ocr, processor, size)
     where = _plan_pages(paged, images, locations, sizes, origins, crop_scales, rng)
+    encoder_hidden_states = _contexts(encoder_hidden_states, texts, glyph)
     pre = (prepost.preprocess_pages if paged else prepost.preprocess_batch)(*where, size=int(size))
     image_vae = _candidate_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, seeds, int(batch_size),
                                 generator, enc_noise, variance_noise, int(size), cache_interval)

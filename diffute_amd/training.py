@@ -38,7 +38,8 @@ def training_target(scheduler, latents, noise, timesteps):
 def train_step(unet, vae, scheduler, optimizer, batch, *, noise=None, timesteps=None, enc_noise=None, enc_noise_masked=None,
                max_grad_norm=1.0, generator=None, scaler=None):
     """One optimizer step.  batch: dict with pixel_values [B,3,H,W], masked_images [B,3,H,W], masks [B,1,H,W] and
-    ocr_embeddings [B,S,1024] (the frozen TrOCR encoder's output, train_diffute_v1.py:868-871).  The random draws can be
+    ocr_embeddings [B,S,1024] (the frozen TrOCR encoder's output, train_diffute_v1.py:868-871; from the batch's strings it is
+    `diffute_amd.glyph_contexts(batch_texts, renderer, processor, encoder)`, rendered on the device).  The random draws can be
     injected (tests); otherwise they come from torch's device RNG like the reference.  Returns loss / grad_norm tensors.
     scaler: a diffute_amd.GradScaler (or torch.amp.GradScaler with a torch optimizer) - `--mixed_precision fp16` (train_diffute_v1.py:267,583):
     backward on the scaled loss, unscale before clipping, the step skipped and the scale halved when the gradient overflowed."""

@@ -724,6 +724,64 @@ int dmx_glyph_max_taps(void);
 int dmx_glyph_resize_normalize(const dmx_glyph_image* images, int B, const int* tables, const float* norm, int max_taps, int S_h, int S_w,
                                float* out_pixel_values, unsigned char* out_resized, dmx_stream_t stream);
 
+/* Glyph images from text (the reference's draw_text, app.ipynb:347-363, train_diffute_v1.py:352-368: a white canvas, black text) on the
+ * device.  The caller rasterises a font ONCE into an atlas - per glyph a coverage bitmap (uint8, row-major, w x h bytes at `off` of
+ * the pool) with its offset (left, top) - and lays text out on the host into placements: (glyph, x, y) = where the bitmap's top-left
+ * pixel lands on the canvas.  A canvas byte is 255 - m in all three channels, m the coverage composed over the item's placements IN
+ * ORDER, m = s + round(m * (255 - s) / 255) with s the glyph's byte at that pixel (0 outside its bitmap); what leaves the canvas on
+ * any side is clipped.  This is, bit for bit, Pillow's ImageDraw.text under the BASIC layout.  Integer arithmetic only.
+ *   atlas   pool / glyphs_device on the device, glyphs_host the same records on the host.  Refused: a record whose bitmap is not
+ *           inside the pool.
+ *   items   B of them, a host copy the entry checks and a device copy the kernel reads: the item's placements are
+ *           [first, first + count) of the placement table (count may be 0: a white canvas), its canvas is H x W.
+ *           glyph_render writes byte (y, x, c) to dst + y * stride_y + x * stride_x + c * stride_c (bytes; trusted, like
+ *           dmx_glyph_image); the h_* / v_* fields are the canvas's pass tables for glyph_text_pixel_values, as in dmx_glyph_image.
+ *   placements  n_placements of them, host and device copies (both may be NULL when n_placements is 0).  Refused: a range that
+ *           ends past the table, a glyph index outside the atlas, a coordinate beyond +-2^24.
+ *   glyph_render: one launch, one thread per canvas pixel of the ragged batch.
+ *   glyph_text_pixel_values: from the placements straight to out_pixel_values fp32 [B][3][S_h][S_w] (and out_resized, optional), bit
+ *           for bit glyph_resize_normalize over the canvases glyph_render writes - without a canvas in memory: a block of
+ *           DMX_GLYPH_TEXT_BLOCK output pixels of one row renders the source rows and columns its taps touch as grey bytes into LDS
+ *           and resamples from there.  tables / table_ints / norm / max_taps as for readback_pixel_values.  The strip of a block is
+ *           at most min(v_taps, H) rows (1 if the vertical pass is skipped) of min(W, (BLOCK - 1) * W / S_w + h_taps + 2) columns
+ *           (min(W, BLOCK) if the horizontal pass is skipped); if that exceeds DMX_GLYPH_TEXT_LDS_BYTES for any item the entry
+ *           returns DMX_ERR_UNSUPPORTED and launches nothing (glyph_render + glyph_resize_normalize serve every shape).
+ * The kernels clamp what they read from the device copies - placement range, glyph index, bitmap offset - to the tables and the
+ * pool, and the strip reads to the strip: a device table that differs from its host copy gives wrong pixels, no access outside. */
+#define DMX_GLYPH_TEXT_BLOCK 128
+#define DMX_GLYPH_TEXT_LDS_BYTES 32768
+#define DMX_GLYPH_TEXT_MAX_COORD 16777216
+typedef struct dmx_glyph_rec {
+  int off, w, h;                    /* bitmap: w * h bytes at pool + off */
+  int left, top;                    /* offset of the bitmap from the pen position (host layout only) */
+  int advance;                      /* in 1/64 px (host layout only) */
+} dmx_glyph_rec;
+typedef struct dmx_glyph_atlas {
+  const unsigned char* pool;
+  long long pool_bytes;
+  const dmx_glyph_rec* glyphs_host;
+  const dmx_glyph_rec* glyphs_device;
+  int n_glyphs;
+} dmx_glyph_atlas;
+typedef struct dmx_glyph_placement {
+  int glyph, x, y;
+} dmx_glyph_placement;
+typedef struct dmx_glyph_text_item {
+  unsigned long long dst;
+  long long stride_y, stride_x, stride_c;
+  int first, count;
+  int H, W;
+  int h_off, h_taps, v_off, v_taps;
+} dmx_glyph_text_item;
+int dmx_glyph_render(const dmx_glyph_atlas* atlas, const dmx_glyph_text_item* items_host, const dmx_glyph_text_item* items_device,
+                     const dmx_glyph_placement* placements_host, const dmx_glyph_placement* placements_device, int n_placements, int B,
+                     dmx_stream_t stream);
+int dmx_glyph_text_pixel_values(const dmx_glyph_atlas* atlas, const dmx_glyph_text_item* items_host,
+                                const dmx_glyph_text_item* items_device, const dmx_glyph_placement* placements_host,
+                                const dmx_glyph_placement* placements_device, int n_placements, int B, const int* tables,
+                                long long table_ints, const float* norm, int max_taps, int S_h, int S_w, float* out_pixel_values,
+                                unsigned char* out_resized, dmx_stream_t stream);
+
 /* Verified edits: K candidates per text box, read back by the OCR model, the best one pasted (reference sketch of the read-back:
  * app.ipynb:842-846 - crop inf_res[y1:y2, x1:x2], run the processor, call generate).  Two launches, no page copy, no host sync.
  *   readback_pixel_values: image_vae fp32 [B][K][3][S][S]; row (b, k) uses item b.  out_pixel_values fp32 [B*K][3][S_h][S_w]: row
