@@ -21,3 +21,4 @@ __all__ = ["AutoencoderKL", "UNet2DConditionModel", "DDPMScheduler", "DDIMSchedu
            "SD2_SCHEDULER_CONFIG", "set_exclusive_device", "synchronize"]
 __version__ = "0.1.0"
 from . import prepost  # noqa: E402,F401  (on-device pre/post-processing)
+from . import metrics  # noqa: E402,F401  (per-box MSE / PSNR / SSIM and the outside-the-boxes diff of two versions of a page)

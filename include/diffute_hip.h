@@ -852,6 +852,52 @@ int dmx_postprocess_paste_select_pages(const float* image_vae, int S, const floa
                                        const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
                                        const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, dmx_stream_t stream);
 
+/* Comparing two versions of a set of pages (metrics.hip): what the scene-text-editing literature reports on the edited box - MSE,
+ * PSNR, SSIM - and what changed OUTSIDE all boxes.  P pairs of pages a / b, uint8 [H][W][3] contiguous, both of a pair H x W; B boxes
+ * (page, x1, y1, x2, y2), each the slice [y1:y2, x1:x2] of its page: exclusive upper corner, non-empty, inside the page (the read-back's
+ * convention).  B is not capped at DMX_EDIT_MAX_ITEMS; P >= 1; a page may have no box.  The boxes of page q are [box_lo, box_hi) of the
+ * box table and the ranges tile [0, B) in page order.  The caller fills addresses, sizes and ranges of the pages and page and corners of
+ * the boxes, lets metric_tables_prepare validate both tables and fill the derived fields, and copies both to the device in stream order.
+ * The entries take the host tables and their device copies, as the page entries above: a bad page is reported by page index, a bad box
+ * by its index in the whole table, and nothing is launched.  The kernels clamp what they read from the device tables (page index, box
+ * corners, ranges) to the tables and the page; the pages' addresses and sizes are trusted.
+ *   box_metrics_pages: per box and channel, sse [B][3] = the exact integer sum of (a - b)^2 over the box, and ssim [B][3] = the mean SSIM
+ *           of Wang et al. 2004 with an 11-tap Gaussian window (sigma 1.5, radius 5, weights computed in double and rounded to fp32:
+ *           box_metrics_weights returns them), population covariance, data range 255, K1 = 0.01, K2 = 0.03, over the (h - 10) (w - 10)
+ *           window centres whose whole window lies inside the box (scikit-image's structural_similarity with gaussian_weights=True,
+ *           use_sample_covariance=False on the slice).  Pixels outside the box never enter.  A box with min(h, w) < 11 gets NaN in all
+ *           three channels; its sse is still written.  Blocks enumerate (box, tile): a tile is DMX_METRIC_TILE x DMX_METRIC_TILE window
+ *           centres counted from the BOX's corner; the moments of a tile are taken about an integer pivot, the rounded mean of `a` over its pixels
+ *           (a variance is a small difference of large numbers on a flat bright page otherwise), per window in fp32; a tile's sums and
+ *           the sums over a box's tiles are fp64 in a fixed order, a second small launch combines them.  So a box's outputs are
+ *           bit-equal from run to run, alone or anywhere in a batch, and in both builds of the library; overlapping boxes are independent.
+ *           workspace: box_metrics_workspace_bytes of the PREPARED box table; too small is DMX_ERR_WORKSPACE.
+ *   page_outside_diff: out [P][2] = per page (changed_outside, sse_outside): the number of pixels covered by NO box of that page
+ *           whose three bytes are not all equal in a and b, and the exact sum of (a - b)^2 over those pixels and the three channels.
+ *           A page without boxes counts all its pixels.  One launch over blocks of 256 pixels, a page's blocks taken from the table
+ *           (up to 2^31 - 1 blocks in all); integer sums, so the result does not depend on any order. */
+#define DMX_METRIC_TILE 16
+#define DMX_METRIC_WINDOW 11
+typedef struct dmx_metric_page {
+  unsigned long long a, b;          /* device addresses of the two versions of the page, uint8 [H][W][3] */
+  int H, W;
+  int box_lo, box_hi;               /* the page's boxes: [box_lo, box_hi) of the box table; may be empty */
+  int block_lo, blocks;             /* derived: the page's blocks in the outside-diff grid, H * ceil(W / 256) of them */
+} dmx_metric_page;
+typedef struct dmx_metric_box {
+  int page, x1, y1, x2, y2;
+  int tiles_x, tiles_y;             /* derived: max(1, ceil((w - 10) / TILE)), likewise in y */
+  int tile_lo;                      /* derived: the box's first block in the box-metrics grid (and first record in the workspace) */
+} dmx_metric_box;
+int dmx_metric_tables_prepare(dmx_metric_page* pages, int P, dmx_metric_box* boxes, int B);
+int dmx_box_metrics_weights(float* h_weights);
+size_t dmx_box_metrics_workspace_bytes(const dmx_metric_box* boxes_host, int B);
+int dmx_box_metrics_pages(const dmx_metric_page* pages_host, const dmx_metric_page* pages_device, int P, const dmx_metric_box* boxes_host,
+                          const dmx_metric_box* boxes_device, int B, unsigned long long* sse, float* ssim, void* workspace,
+                          size_t workspace_bytes, dmx_stream_t stream);
+int dmx_page_outside_diff(const dmx_metric_page* pages_host, const dmx_metric_page* pages_device, int P, const dmx_metric_box* boxes_host,
+                          const dmx_metric_box* boxes_device, int B, unsigned long long* out, dmx_stream_t stream);
+
 /* Fused AdamW + global-norm clipping over packed fp32 arenas (torch.optim.AdamW + clip_grad_norm_,
  * train_diffute_v1.py:721-727,927-930).  masters / exp_avg / exp_avg_sq / grads: dmx_unet_grad_bytes each.  The step also
  * rewrites the weights arena (bf16 weights, fp32 vectors) in place; afterwards call dmx_unet_refresh_derived (folded
