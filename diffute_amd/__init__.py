@@ -14,10 +14,11 @@ from .training_utils import EMAModel
 from .ocr import TrOCRForCausalLM, VisionEncoderDecoderModel, TROCR_LARGE_DECODER_CONFIG
 from .processing import TrOCRProcessor, ViTImageProcessor
 from .glyphs import GlyphAtlas, GlyphRenderer, glyph_contexts
+from .data import SyntheticDocuments, sample_boxes, training_batch
 from ._cabi import set_exclusive_device, synchronize
 
 __all__ = ["AutoencoderKL", "UNet2DConditionModel", "DDPMScheduler", "DDIMScheduler", "DPMSolverMultistepScheduler", "DenoiseEngine", "denoise", "edit_latents", "edit_boxes", "edit_boxes_verified", "edit_pages", "edit_pages_verified",
-           "mask_to_latent", "FusedAdamW", "GradScaler", "EMAModel", "TrOCREncoder", "TrOCRForCausalLM", "VisionEncoderDecoderModel", "TrOCRProcessor", "ViTImageProcessor", "GlyphAtlas", "GlyphRenderer", "glyph_contexts", "TROCR_LARGE_DECODER_CONFIG", "TROCR_LARGE_VIT_CONFIG", "DiagonalGaussianDistribution", "SD2_INPAINT_UNET_CONFIG", "SD_VAE_CONFIG",
+           "mask_to_latent", "FusedAdamW", "GradScaler", "EMAModel", "TrOCREncoder", "TrOCRForCausalLM", "VisionEncoderDecoderModel", "TrOCRProcessor", "ViTImageProcessor", "GlyphAtlas", "GlyphRenderer", "glyph_contexts", "SyntheticDocuments", "sample_boxes", "training_batch", "TROCR_LARGE_DECODER_CONFIG", "TROCR_LARGE_VIT_CONFIG", "DiagonalGaussianDistribution", "SD2_INPAINT_UNET_CONFIG", "SD_VAE_CONFIG",
            "SD2_SCHEDULER_CONFIG", "set_exclusive_device", "synchronize"]
 __version__ = "0.1.0"
 from . import prepost  # noqa: E402,F401  (on-device pre/post-processing)

@@ -2,7 +2,8 @@
 // canvas, ImageDraw.text in black).  The font is rasterised once on the host into an atlas of coverage bitmaps, text is laid out on the
 // host into placements (glyph, x, y) - include/diffute_hip.h dmx_glyph_render - and composed here:
 //   coverage m over the item's placements IN ORDER: m = s + round(m * (255 - s) / 255), canvas byte = 255 - m, three equal channels.
-// That is Pillow's BASIC-layout ImageDraw.text bit for bit (taking the maximum, or adding, is wrong where neighbours overlap).
+// That is Pillow's BASIC-layout ImageDraw.text bit for bit (taking the maximum, or adding, is wrong where neighbours overlap).  The
+// coverage of a pixel and the checks of atlas and placements live in glyph_coverage.h, shared with the page composer (page_compose.hip).
 //   dmx_glyph_render             the uint8 canvases of a ragged batch, one thread per canvas pixel.
 //   dmx_glyph_text_pixel_values  placements -> the processor's fp32 batch in one launch: a block of 128 output pixels of one output row
 //                                renders the few source rows x columns its taps touch as grey bytes into LDS, then every thread runs
@@ -14,42 +15,23 @@
 #include "common.h"
 #include "kernels.h"
 #include "glyph_resample.h"
+#include "glyph_coverage.h"
 #include <limits.h>
 
 namespace {
 constexpr int kBlock = DMX_GLYPH_TEXT_BLOCK;
 
-struct TextArgs {
-  const unsigned char* pool; long long pool_bytes;
-  const dmx_glyph_rec* glyphs; int n_glyphs;
-  const dmx_glyph_text_item* items;
-  const dmx_glyph_placement* places; int n_places;
-};
+using dmx_glyph::Tables;
+using dmx_glyph::text_coverage;                 // glyph_coverage.h: shared with the page composer
 
-// Pillow's MULDIV255: round(a * b / 255) for bytes a, b
-__device__ __forceinline__ int muldiv255(int a, int b) { const int t = a * b + 128; return ((t >> 8) + t) >> 8; }
+struct TextArgs {
+  Tables g;
+  const dmx_glyph_text_item* items;
+};
 
 // the item's placement range, clamped to the table
 __device__ __forceinline__ void text_range(const TextArgs& a, const dmx_glyph_text_item& it, int& first, int& count) {
-  first = min(max(it.first, 0), a.n_places);
-  count = min(max(it.count, 0), a.n_places - first);
-}
-
-// Coverage of canvas pixel (x, y) under placements [first, first + count).  [bx0, bx1) x [by0, by1) holds every pixel the BLOCK asks for:
-// a glyph that misses it is skipped on a block-uniform branch, so a pixel only looks into the few bitmaps near it.
-__device__ __forceinline__ int text_coverage(const TextArgs& a, int first, int count, int bx0, int bx1, int by0, int by1, int x, int y) {
-  int m = 0;
-  for (int i = 0; i < count; ++i) {
-    const dmx_glyph_placement p = a.places[first + i];
-    const dmx_glyph_rec g = a.glyphs[min(max(p.glyph, 0), a.n_glyphs - 1)];
-    if ((long long)p.x + g.w <= bx0 || p.x >= bx1 || (long long)p.y + g.h <= by0 || p.y >= by1) continue;
-    const long long lx = (long long)x - p.x, ly = (long long)y - p.y;
-    if (lx < 0 || lx >= g.w || ly < 0 || ly >= g.h) continue;
-    const long long o = min(max((long long)g.off + ly * g.w + lx, 0ll), a.pool_bytes - 1);
-    const int s = a.pool[o];
-    m = s + muldiv255(m, 255 - s);
-  }
-  return m;
+  dmx_glyph::text_range(a.g, it.first, it.count, first, count);
 }
 
 __global__ __launch_bounds__(kBlock) void dmx_glyph_render_kernel(const TextArgs a) {
@@ -58,7 +40,7 @@ __global__ __launch_bounds__(kBlock) void dmx_glyph_render_kernel(const TextArgs
   if (x >= it.W || y >= it.H) return;
   int first, count;
   text_range(a, it, first, count);
-  const unsigned char v = (unsigned char)(255 - text_coverage(a, first, count, bx0, bx0 + kBlock, y, y + 1, x, y));
+  const unsigned char v = (unsigned char)(255 - text_coverage(a.g, first, count, bx0, bx0 + kBlock, y, y + 1, x, y));
   unsigned char* dst = (unsigned char*)it.dst + (long long)y * it.stride_y + (long long)x * it.stride_x;
   dst[0] = v; dst[it.stride_c] = v; dst[2 * it.stride_c] = v;
 }
@@ -110,7 +92,7 @@ __global__ __launch_bounds__(kBlock) void dmx_glyph_text_pixel_values_kernel(con
   text_range(p.t, it, first, count);
   for (int i = tid; i < rows * cols; i += kBlock) {
     const int r = i / cols, c = i - r * cols;
-    strip[i] = (unsigned char)(255 - text_coverage(p.t, first, count, x_lo, x_lo + cols, y_lo, y_lo + rows, x_lo + c, y_lo + r));
+    strip[i] = (unsigned char)(255 - text_coverage(p.t.g, first, count, x_lo, x_lo + cols, y_lo, y_lo + rows, x_lo + c, y_lo + r));
   }
   __syncthreads();
   if (ox >= p.S_w) return;
@@ -130,29 +112,16 @@ __global__ __launch_bounds__(kBlock) void dmx_glyph_text_pixel_values_kernel(con
 int check_text(const char* what, const dmx_glyph_atlas* atlas, const dmx_glyph_text_item* items_host, const dmx_glyph_text_item* items_device,
                const dmx_glyph_placement* places_host, const dmx_glyph_placement* places_device, int n_places, int B, TextArgs& a) {
   DMX_REQUIRE(atlas && items_host && items_device, "%s: null argument", what);
-  DMX_REQUIRE(atlas->pool && atlas->glyphs_host && atlas->glyphs_device, "%s: null atlas table", what);
-  DMX_REQUIRE(atlas->n_glyphs >= 1 && atlas->pool_bytes >= 1 && atlas->pool_bytes < (1ll << 31), "%s: bad atlas (%d glyphs, %lld pool bytes)", what,
-              atlas->n_glyphs, atlas->pool_bytes);
   DMX_REQUIRE(B >= 1 && B <= 65535, "%s: B = %d, expected 1 .. 65535", what, B);
-  DMX_REQUIRE(n_places >= 0 && (n_places == 0 || (places_host && places_device)), "%s: %d placements but no placement table", what, n_places);
-  for (int g = 0; g < atlas->n_glyphs; ++g) {
-    const dmx_glyph_rec& r = atlas->glyphs_host[g];
-    DMX_REQUIRE(r.off >= 0 && r.w >= 0 && r.h >= 0 && r.w <= 65535 && r.h <= 65535 && (long long)r.off + (long long)r.w * r.h <= atlas->pool_bytes,
-                "%s: glyph %d: bitmap %dx%d at %d lies outside the pool of %lld bytes", what, g, r.w, r.h, r.off, atlas->pool_bytes);
-  }
+  const int rc = dmx_glyph::check_tables(what, atlas, places_host, places_device, n_places, a.g);
+  if (rc != DMX_OK) return rc;
   for (int b = 0; b < B; ++b) {
     const dmx_glyph_text_item& it = items_host[b];
     DMX_REQUIRE(it.H >= 1 && it.H <= 65535 && it.W >= 1 && it.W <= DMX_GLYPH_TEXT_MAX_COORD, "%s: item %d: bad canvas %dx%d", what, b, it.W, it.H);
     DMX_REQUIRE(it.first >= 0 && it.count >= 0 && (long long)it.first + it.count <= n_places,
                 "%s: item %d: placements [%d, %d + %d) end past the table of %d", what, b, it.first, it.first, it.count, n_places);
   }
-  for (int i = 0; i < n_places; ++i) {
-    const dmx_glyph_placement& p = places_host[i];
-    DMX_REQUIRE(p.glyph >= 0 && p.glyph < atlas->n_glyphs, "%s: placement %d: glyph %d outside the atlas of %d", what, i, p.glyph, atlas->n_glyphs);
-    DMX_REQUIRE(p.x >= -DMX_GLYPH_TEXT_MAX_COORD && p.x <= DMX_GLYPH_TEXT_MAX_COORD && p.y >= -DMX_GLYPH_TEXT_MAX_COORD && p.y <= DMX_GLYPH_TEXT_MAX_COORD,
-                "%s: placement %d: position (%d, %d) beyond +-%d", what, i, p.x, p.y, DMX_GLYPH_TEXT_MAX_COORD);
-  }
-  a = TextArgs{atlas->pool, atlas->pool_bytes, atlas->glyphs_device, atlas->n_glyphs, items_device, places_device, n_places};
+  a.items = items_device;
   return DMX_OK;
 }
 }  // namespace

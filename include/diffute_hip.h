@@ -782,6 +782,52 @@ int dmx_glyph_text_pixel_values(const dmx_glyph_atlas* atlas, const dmx_glyph_te
                                 long long table_ints, const float* norm, int max_taps, int S_h, int S_w, float* out_pixel_values,
                                 unsigned char* out_resized, dmx_stream_t stream);
 
+/* Synthetic document pages (page_compose.hip): P ragged pages of coloured text lines on a textured background in ONE launch - training
+ * pages whose strings and boxes are known.  Atlas and placements as for glyph_render, placements in PAGE coordinates.  Per page pixel
+ * (y, x) and channel c, integer arithmetic only:
+ *   background  v = clip8(bg[c] + off), off = (int)(h % (2 * tex_amp + 1)) - tex_amp (0 when tex_amp is 0) with the 32-bit hash, all
+ *           arithmetic modulo 2^32,
+ *               h = tex_seed + 0x9E3779B1 * y + 0x85EBCA77 * x + 0xC2B2AE3D * c
+ *               h ^= h >> 16;  h *= 0x7FEB352D;  h ^= h >> 15;  h *= 0x846CA68B;  h ^= h >> 16
+ *   lines   for the page's lines [first_line, first_line + n_lines) of the line table IN TABLE ORDER: m = the coverage of the line's
+ *           placements [first, first + count) composed in order as in glyph_render, m = s + round(m * (255 - s) / 255); then
+ *               v = round((v * (255 - m) + rgb[c] * m) / 255),   round(t / 255) = ((u >> 8) + u) >> 8 with u = t + 128
+ *           - one rounding of the sum: Pillow's masked fill (ImageDraw.text(xy, text, font=font, fill=rgb) on an RGB image, BASIC
+ *           layout), bit for bit.  A later line is drawn over an earlier one; the maximum over lines, or one coverage for all of
+ *           them, differs where lines overlap.
+ *   store   byte (y, x, c) of page p goes to dst + y * stride_y + x * stride_x + c * stride_c (bytes; trusted, as in glyph_render):
+ *           HWC and planar destinations both work.
+ *   pages   P of them, 1 <= P <= 65535, host copy and device copy; 1 <= H <= 65535, 1 <= W <= DMX_GLYPH_TEXT_MAX_COORD, bg in 0 .. 255,
+ *           0 <= tex_amp <= 255.  n_lines may be 0.
+ *   lines   n_lines_total of them, host and device copies (both may be NULL when there is none).  [x0, x1) x [y0, y1) is a box that
+ *           holds every bitmap of the line; it is used for rejection only: a block of DMX_GLYPH_TEXT_BLOCK pixels of one row skips a
+ *           line whose box misses it, then a glyph whose bitmap misses it.  rgb in 0 .. 255.
+ * Refused (DMX_ERR_ARG, nothing launched): a null table or destination, P out of range, a line range past the line table, a placement
+ * range past the placement table, a bitmap of a line outside the line's box, a value out of the ranges above, and what glyph_render
+ * refuses of the atlas and the placements.  The kernel clamps what it reads from the device copies (line range, placement range, glyph
+ * index, bitmap offset, colours, tex_amp): a device table that differs from its host copy gives wrong pixels, no access outside the
+ * tables and the pool. */
+typedef struct dmx_page_rec {
+  unsigned long long dst;
+  long long stride_y, stride_x, stride_c;
+  int H, W;
+  int first_line, n_lines;
+  unsigned int tex_seed;
+  int tex_amp;
+  int bg[3];
+  int reserved;
+} dmx_page_rec;
+typedef struct dmx_page_line {
+  int first, count;                 /* the line's placements */
+  int x0, y0, x1, y1;               /* box of the line's bitmaps, upper corner exclusive */
+  int rgb[3];
+  int reserved;
+} dmx_page_line;
+int dmx_page_compose(const dmx_glyph_atlas* atlas, const dmx_page_rec* pages_host, const dmx_page_rec* pages_device, int P,
+                     const dmx_page_line* lines_host, const dmx_page_line* lines_device, int n_lines_total,
+                     const dmx_glyph_placement* placements_host, const dmx_glyph_placement* placements_device, int n_placements,
+                     dmx_stream_t stream);
+
 /* Verified edits: K candidates per text box, read back by the OCR model, the best one pasted (reference sketch of the read-back:
  * app.ipynb:842-846 - crop inf_res[y1:y2, x1:x2], run the processor, call generate).  Two launches, no page copy, no host sync.
  *   readback_pixel_values: image_vae fp32 [B][K][3][S][S]; row (b, k) uses item b.  out_pixel_values fp32 [B*K][3][S_h][S_w]: row
