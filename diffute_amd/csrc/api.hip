@@ -1,5 +1,6 @@
 // extern "C" operator-level entry points declared in include/diffute_hip.h.
 #include "kernels.h"
+#include <cmath>
 
 const char* dmx_get_error();
 
@@ -405,6 +406,30 @@ extern "C" int dmx_sched_step_rows(float* sample, const float* model_output, con
   }
   return dmx_sched_rows_launch(sample, model_output, noise, kind == DMX_SCHED_DPMPP ? hist : nullptr, kind == DMX_SCHED_DPMPP ? n_hist : 0, plan,
                                row_index, B, per_sample, kind, v_prediction, (hipStream_t)stream);
+}
+extern "C" int dmx_sched_step_guided(float* sample, const float* model_output, const float* noise, float* hist, int n_hist, dmx_sched_row_rec rec,
+                                     int kind, int v_prediction, float guidance_scale, float rescale, float one_minus_rescale, float* ratio_out,
+                                     int B, size_t per_sample, dmx_stream_t stream) {
+  DMX_REQUIRE(sample && model_output, "sched_step_guided: null argument");
+  DMX_REQUIRE(B >= 1 && B <= 32767 && per_sample > 0, "sched_step_guided: B=%d samples of %zu elements", B, per_sample);
+  DMX_REQUIRE(kind == DMX_SCHED_DDIM || kind == DMX_SCHED_DDPM || kind == DMX_SCHED_DPMPP, "sched_step_guided: kind %d", kind);
+  DMX_REQUIRE(std::isfinite(guidance_scale) && std::isfinite(rescale) && std::isfinite(one_minus_rescale),
+              "sched_step_guided: guidance_scale, rescale and one_minus_rescale must be finite");
+  DMX_REQUIRE(rescale >= 0.f && rescale <= 1.f, "sched_step_guided: rescale %g outside [0, 1]", (double)rescale);
+  DMX_REQUIRE(rescale == 0.f || per_sample >= 2, "sched_step_guided: the rescale needs samples of at least 2 elements (unbiased deviation)");
+  if (kind == DMX_SCHED_DPMPP) {
+    DMX_REQUIRE(noise == nullptr, "sched_step_guided: DPM-Solver++ is deterministic (noise must be NULL)");
+    DMX_REQUIRE(hist && n_hist >= 1 && n_hist <= 3, "sched_step_guided: DPM-Solver++ needs its history ring (n_hist 1..3)");
+    const int o = rec.order;
+    DMX_REQUIRE(o >= 1 && o <= n_hist && rec.ring_w >= 0 && rec.ring_w < n_hist &&
+                (o < 2 || (rec.ring_m1 >= 0 && rec.ring_m1 < n_hist && rec.ring_m1 != rec.ring_w)) &&
+                (o < 3 || (rec.ring_m2 >= 0 && rec.ring_m2 < n_hist && rec.ring_m2 != rec.ring_w)),
+                "sched_step_guided: order %d with slots (%d, %d, %d) cannot be served from a ring of %d", o, rec.ring_w, rec.ring_m1, rec.ring_m2, n_hist);
+    const size_t nb = (size_t)B * per_sample;
+    DMX_REQUIRE(hist + (size_t)n_hist * nb <= sample || sample + 2 * nb <= hist, "sched_step_guided: the history ring overlaps the sample");
+  }
+  return dmx_sched_guided_launch(kind, rec, sample, model_output, noise, kind == DMX_SCHED_DPMPP ? hist : nullptr, guidance_scale, rescale,
+                                 one_minus_rescale, ratio_out, B, per_sample, v_prediction, (hipStream_t)stream);
 }
 extern "C" int dmx_rows_admit(int* row_index, int* row_left, int b, int plan_base, int n_steps, dmx_stream_t stream) {
   DMX_REQUIRE(row_index && row_left && b >= 0 && plan_base >= 0 && n_steps >= 0, "rows_admit: row %d, plan row %d, %d steps", b, plan_base, n_steps);

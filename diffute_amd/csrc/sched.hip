@@ -4,7 +4,8 @@
 // fp32 CPU evaluation of the same formulas (scalar coefficients are computed on the host).
 // DPMSolverMultistepScheduler.step likewise.  One step is one dmx_sched_row_rec (diffute_amd/schedulers.py plan()): the scalar entries receive it
 // by value, the per-row entry of the in-flight engine reads it from the plan array; ddim_elem / ddpm_elem / dpm_elem are the arithmetic and
-// sched_span is the one loop around them, so a row is the same bits through either entry.
+// sched_span is the one loop around them, so a row is the same bits through either entry.  The guided entry (dmx_sched_step_guided: classifier-free
+// guidance, the optional guidance rescale and the update in one launch) runs the same loop on the combined model output (sched_span_g).
 #include "common.h"
 #include "kernels.h"
 
@@ -117,9 +118,22 @@ __host__ __device__ __forceinline__ bool sched_span_aligned(bool dpm, int order,
                          (dpm && order >= 2 ? (uintptr_t)m1 : 0) | (dpm && order >= 3 ? (uintptr_t)m2 : 0);
   return (bits & 15) == 0;
 }
-template <int KIND>
-__device__ __forceinline__ void sched_span(const dmx_sched_row_rec& r, const float* x, const float* eps, const float* nz, const float* m1,
-                                           const float* m2, float* m0, float* out, size_t n, int vpred) {
+// GUIDED (dmx_sched_step_guided): `eps` is the conditional model output and G.eu the unconditional one; the update runs on their
+// classifier-free combination (guided_eps) and the result is stored twice, to out and to G.out2.  Not GUIDED: G is never read.
+struct sched_guide {
+  const float* eu; float* out2;                // the unconditional model output of the span; the second copy of prev_sample
+  float scale, rescale, one_minus_rescale, k;  // k: the span's std(ec) / std(g) (guided_ratio), read only when rescale != 0
+};
+// g = eu + scale * (ec - eu); rescale != 0 (Lin et al. 2023, diffusers' rescale_noise_cfg): rescale * (g * k) + (1 - rescale) * g
+__device__ __forceinline__ float guided_mix(float ec, float eu, float scale) { return __fadd_rn(eu, __fmul_rn(scale, __fsub_rn(ec, eu))); }
+__device__ __forceinline__ float guided_eps(float ec, float eu, const sched_guide& G) {
+  const float g = guided_mix(ec, eu, G.scale);
+  if (G.rescale == 0.f) return g;
+  return __fadd_rn(__fmul_rn(G.rescale, __fmul_rn(g, G.k)), __fmul_rn(G.one_minus_rescale, g));
+}
+template <int KIND, bool GUIDED>
+__device__ __forceinline__ void sched_span_g(const dmx_sched_row_rec& r, const float* x, const float* eps, const float* nz, const float* m1,
+                                             const float* m2, float* m0, float* out, size_t n, int vpred, const sched_guide& G) {
   constexpr bool DPM = KIND == DMX_SCHED_DPMPP;
   const int order = DPM ? r.order : 0;
   const bool has_noise = !DPM && nz != nullptr;
@@ -130,11 +144,16 @@ __device__ __forceinline__ void sched_span(const dmx_sched_row_rec& r, const flo
   };
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
   size_t done = 0;
-  if (sched_span_aligned(DPM, order, x, eps, nz, m1, m2, m0, out)) {
+  if (sched_span_aligned(DPM, order, x, eps, nz, m1, m2, m0, out) && (!GUIDED || (((uintptr_t)G.eu | (uintptr_t)G.out2) & 15) == 0)) {
     const size_t n4 = n / 4;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     for (size_t i = tid; i < n4; i += stride) {
-      const float4 xv = reinterpret_cast<const float4*>(x)[i], ev = reinterpret_cast<const float4*>(eps)[i];
+      const float4 xv = reinterpret_cast<const float4*>(x)[i];
+      float4 ev = reinterpret_cast<const float4*>(eps)[i];
+      if (GUIDED) {
+        const float4 uv = reinterpret_cast<const float4*>(G.eu)[i];
+        ev.x = guided_eps(ev.x, uv.x, G); ev.y = guided_eps(ev.y, uv.y, G); ev.z = guided_eps(ev.z, uv.z, G); ev.w = guided_eps(ev.w, uv.w, G);
+      }
       const float4 nv = has_noise ? reinterpret_cast<const float4*>(nz)[i] : z4;
       const float4 a = order >= 2 ? reinterpret_cast<const float4*>(m1)[i] : z4;
       const float4 c = order >= 3 ? reinterpret_cast<const float4*>(m2)[i] : z4;
@@ -145,15 +164,24 @@ __device__ __forceinline__ void sched_span(const dmx_sched_row_rec& r, const flo
       p.w = elem(xv.w, ev.w, nv.w, a.w, c.w, d0.w);
       if (DPM) reinterpret_cast<float4*>(m0)[i] = d0;
       reinterpret_cast<float4*>(out)[i] = p;
+      if (GUIDED) reinterpret_cast<float4*>(G.out2)[i] = p;
     }
     done = n4 * 4;
   }
   for (size_t i = done + tid; i < n; i += stride) {
     float d0 = 0.f;
-    const float p = elem(x[i], eps[i], has_noise ? nz[i] : 0.f, order >= 2 ? m1[i] : 0.f, order >= 3 ? m2[i] : 0.f, d0);
+    const float xv = x[i], ec = eps[i];
+    const float ev = GUIDED ? guided_eps(ec, G.eu[i], G) : ec;
+    const float p = elem(xv, ev, has_noise ? nz[i] : 0.f, order >= 2 ? m1[i] : 0.f, order >= 3 ? m2[i] : 0.f, d0);
     if (DPM) m0[i] = d0;
     out[i] = p;
+    if (GUIDED) G.out2[i] = p;
   }
+}
+template <int KIND>
+__device__ __forceinline__ void sched_span(const dmx_sched_row_rec& r, const float* x, const float* eps, const float* nz, const float* m1,
+                                           const float* m2, float* m0, float* out, size_t n, int vpred) {
+  sched_span_g<KIND, false>(r, x, eps, nz, m1, m2, m0, out, n, vpred, sched_guide{});
 }
 // one of three instantiations by the runtime kind
 #define DMX_SCHED_LAUNCH(kind, kernel, grid, ...)                                                                                   \
@@ -210,6 +238,90 @@ int dmx_sched_rows_launch(float* x, const float* eps, const float* noise, float*
   return dmx_check_launch("dmx_sched_rows_kernel");
 }
 #undef DMX_SCHED_LAUNCH
+
+// ---- the guided step (dmx_sched_step_guided): classifier-free guidance, the optional guidance rescale and the scheduler update of B samples
+// in one launch.  eps [2B][per]: rows [0,B) conditional, [B,2B) unconditional; x [2B][per]: sample b is read from row b only and prev_sample
+// is stored to row b AND row B + b (the next 2B-row forward needs no copy; an element is read before it is written, by the same thread);
+// noise / hist [.][B][per].  The record travels by value; the host entry has refused a ring it cannot be served from.
+// One block row per sample (blockIdx.y).  rescale == 0: grid (chunks, B) of 256 threads, the span of the per-row kernel.  rescale != 0: grid
+// (1, B) of 1024 threads; the block first reduces the sample's two standard deviations (guided_ratio), then runs the same span.
+//
+// guided_ratio: k = std(ec) / std(g), both UNBIASED over the sample's n elements, g = guided_mix recomputed from (ec, eu) exactly as the span
+// recomputes it.  Two passes - the means, then the centred squares (never E[x^2] - E[x]^2) - each in fp32 and in a FIXED order, so the result
+// is the same bits on every run: a thread sums its elements in index order (float4 i = tid, tid + T, ..: lanes x, y, z, w in turn; then the
+// n % 4 tail - or everything, unaligned - as scalars i = tid, tid + T, ..), a wave combines its 64 partials by an xor butterfly (32, 16, .. 1:
+// fp32 addition is commutative, so every lane holds the same bits), and every thread adds the waves' partials from LDS in wave order.  No
+// atomics.  std(g) == 0 gives k = inf (or NaN for 0 / 0) and propagates, as in diffusers.
+__device__ __forceinline__ float2 guided_block_sum2(float a, float b, float2* sh) {
+  for (int o = 32; o > 0; o >>= 1) { a = __fadd_rn(a, __shfl_xor(a, o)); b = __fadd_rn(b, __shfl_xor(b, o)); }
+  __syncthreads();                                        // (the previous round's reads of sh are done)
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = make_float2(a, b);
+  __syncthreads();
+  float2 s = make_float2(0.f, 0.f);
+  for (int w = 0; w < (int)(blockDim.x >> 6); w++) { s.x = __fadd_rn(s.x, sh[w].x); s.y = __fadd_rn(s.y, sh[w].y); }
+  return s;
+}
+// sum over the row of f(ec, g) -> (x, y) contributions, the calling block's threads in the order above
+template <class F>
+__device__ __forceinline__ float2 guided_row_sum2(const float* ec, const float* eu, size_t n, float scale, float2* sh, F f) {
+  float a = 0.f, b = 0.f;
+  auto add = [&](float c, float u) { const float2 v = f(c, guided_mix(c, u, scale)); a = __fadd_rn(a, v.x); b = __fadd_rn(b, v.y); };
+  size_t done = 0;
+  if ((((uintptr_t)ec | (uintptr_t)eu) & 15) == 0) {
+    const size_t n4 = n / 4;
+    for (size_t i = threadIdx.x; i < n4; i += blockDim.x) {
+      const float4 c = reinterpret_cast<const float4*>(ec)[i], u = reinterpret_cast<const float4*>(eu)[i];
+      add(c.x, u.x); add(c.y, u.y); add(c.z, u.z); add(c.w, u.w);
+    }
+    done = n4 * 4;
+  }
+  for (size_t i = done + threadIdx.x; i < n; i += blockDim.x) add(ec[i], eu[i]);
+  return guided_block_sum2(a, b, sh);
+}
+__device__ __forceinline__ float guided_ratio(const float* ec, const float* eu, size_t n, float scale, float2* sh) {
+  const float2 s = guided_row_sum2(ec, eu, n, scale, sh, [](float c, float g) { return make_float2(c, g); });
+  const float mc = __fdiv_rn(s.x, (float)n), mg = __fdiv_rn(s.y, (float)n);
+  const float2 q = guided_row_sum2(ec, eu, n, scale, sh, [=](float c, float g) {
+    const float dc = __fsub_rn(c, mc), dg = __fsub_rn(g, mg);
+    return make_float2(__fmul_rn(dc, dc), __fmul_rn(dg, dg));
+  });
+  const float nm1 = (float)(n - 1);
+  return __fdiv_rn(__fsqrt_rn(__fdiv_rn(q.x, nm1)), __fsqrt_rn(__fdiv_rn(q.y, nm1)));
+}
+template <int KIND>
+__global__ __launch_bounds__(1024) void dmx_sched_guided_kernel(dmx_sched_row_rec r, float* x, const float* eps, const float* noise, float* hist,
+                                                                float scale, float rescale, float one_minus_rescale, float* ratio_out, int B,
+                                                                size_t per, int vpred) {
+  __shared__ float2 sh[16];
+  const int b = blockIdx.y;
+  float* m0 = nullptr; const float* m1 = nullptr; const float* m2 = nullptr;
+  if (KIND == DMX_SCHED_DPMPP) {
+    m0 = hist + ((size_t)r.ring_w * B + b) * per;
+    if (r.order >= 2) m1 = hist + ((size_t)r.ring_m1 * B + b) * per;
+    if (r.order >= 3) m2 = hist + ((size_t)r.ring_m2 * B + b) * per;
+  }
+  const float* ec = eps + (size_t)b * per;
+  sched_guide G{eps + ((size_t)B + b) * per, x + ((size_t)B + b) * per, scale, rescale, one_minus_rescale, 1.f};
+  if (rescale != 0.f) {                                   // (uniform over the launch: the grid is (1, B) then)
+    G.k = guided_ratio(ec, G.eu, per, scale, sh);
+    if (ratio_out != nullptr && threadIdx.x == 0) ratio_out[b] = G.k;
+  }
+  float* xr = x + (size_t)b * per;
+  sched_span_g<KIND, true>(r, xr, ec, noise != nullptr ? noise + (size_t)b * per : nullptr, m1, m2, m0, xr, per, vpred, G);
+}
+int dmx_sched_guided_launch(int kind, const dmx_sched_row_rec& r, float* x, const float* eps, const float* noise, float* hist, float scale,
+                            float rescale, float one_minus_rescale, float* ratio_out, int B, size_t per, int vpred, hipStream_t stream) {
+  const size_t work = (per + 3) / 4;
+  int chunks = (int)((work + 255) / 256); if (chunks > 512) chunks = 512; if (chunks < 1) chunks = 1;
+  const dim3 grid(rescale != 0.f ? 1 : chunks, B), block(rescale != 0.f ? 1024 : 256);
+  if (kind == DMX_SCHED_DDIM)
+    hipLaunchKernelGGL(dmx_sched_guided_kernel<DMX_SCHED_DDIM>, grid, block, 0, stream, r, x, eps, noise, hist, scale, rescale, one_minus_rescale, ratio_out, B, per, vpred);
+  else if (kind == DMX_SCHED_DDPM)
+    hipLaunchKernelGGL(dmx_sched_guided_kernel<DMX_SCHED_DDPM>, grid, block, 0, stream, r, x, eps, noise, hist, scale, rescale, one_minus_rescale, ratio_out, B, per, vpred);
+  else
+    hipLaunchKernelGGL(dmx_sched_guided_kernel<DMX_SCHED_DPMPP>, grid, block, 0, stream, r, x, eps, noise, hist, scale, rescale, one_minus_rescale, ratio_out, B, per, vpred);
+  return dmx_check_launch("dmx_sched_guided_kernel");
+}
 
 // the two device ints of a row: row_index[b] (a plan row, -1 = idle) and row_left[b] (steps still to run).  One block each; the values of an
 // admission travel as kernel arguments.

@@ -154,13 +154,32 @@ def sample_boxes(records, rng, crop_scale=256):
     return locations, origins, texts
 
 
-def training_batch(pages, locations, origins, texts, glyph, size=512, crop_scale=256):
+def _check_dropout(context_dropout):
+    p = float(context_dropout)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"context_dropout = {context_dropout!r}: a probability in [0, 1]")
+    return p
+
+
+def training_batch(pages, locations, origins, texts, glyph, size=512, crop_scale=256, context_dropout=0.0, drop_rng=None):
     """The dict train_step takes - pixel_values, masked_images fp32 [B,3,size,size], masks uint8 [B,1,size,size], ocr_embeddings [B,L,D] -
     for one box on each of B device pages: prepost.preprocess_pages (the crop of `crop_scale` resized to `size`, the reference's training
-    transform) and glyph_contexts(texts, *glyph), glyph = (renderer, processor, encoder); nothing else."""
+    transform) and glyph_contexts(texts, *glyph), glyph = (renderer, processor, encoder); nothing else.
+
+    context_dropout = p > 0: the training half of classifier-free guidance - with probability p a row's ocr_embeddings are replaced by
+    zeros, the default unconditional context of Guidance.  One uniform draw per row from `drop_rng` (a numpy Generator, required then), in
+    row order; row b is dropped where its draw is below p.  With the default 0.0 nothing is drawn and the batch is what it always was."""
+    p = _check_dropout(context_dropout)
+    if p > 0.0 and drop_rng is None:
+        raise ValueError("context_dropout > 0 needs drop_rng (a numpy Generator)")
     pre = prepost.preprocess_pages(pages, locations, origins, [[int(crop_scale)]] * len(pages), size)
-    return dict(pixel_values=pre["image"], masked_images=pre["masked_image"], masks=pre["mask"],
-                ocr_embeddings=glyphs.glyph_contexts(texts, *glyph))
+    ctx = glyphs.glyph_contexts(texts, *glyph)
+    if p > 0.0:
+        drop = drop_rng.random(ctx.shape[0]) < p
+        if drop.any():
+            ctx = ctx.clone()
+            ctx[torch.from_numpy(drop).to(ctx.device)] = 0
+    return dict(pixel_values=pre["image"], masked_images=pre["masked_image"], masks=pre["mask"], ocr_embeddings=ctx)
 
 
 _LETTERS = "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789"
@@ -261,9 +280,12 @@ class SyntheticDocuments:
         """the records' pages as uint8 CUDA [H][W][3] tensors (views of one buffer; `out`: that buffer), one dmx_page_compose launch"""
         return compose_pages(self._need_renderer(), records, out=out)
 
-    def batches(self, B, rng, glyph=None, size=512, crop_scale=256, start=0):
+    def batches(self, B, rng, glyph=None, size=512, crop_scale=256, start=0, context_dropout=0.0):
         """an endless iterator of train_step batches of B pages each, pages start, start + 1, ...: compose, sample_boxes, training_batch.
-        glyph = (renderer, processor, encoder), default self.glyph; rng draws the boxes and origins."""
+        glyph = (renderer, processor, encoder), default self.glyph; rng draws the boxes and origins.  context_dropout: training_batch's;
+        the rows dropped from the batch that starts at page i come from np.random.default_rng([seed, i, 1]) - a function of the
+        dataset's seed and the batch's first page alone, never of `rng`."""
+        context_dropout = _check_dropout(context_dropout)
         glyph = self.glyph if glyph is None else glyph
         if glyph is None:
             raise ValueError("batches needs (renderer, processor, encoder) for the glyph contexts: pass glyph= or set ds.glyph")
@@ -273,4 +295,5 @@ class SyntheticDocuments:
             i += B
             pages = self.compose(records)
             locations, origins, texts = sample_boxes(records, rng, crop_scale)
-            yield training_batch(pages, locations, origins, texts, glyph, size, crop_scale)
+            drop_rng = np.random.default_rng([self.seed, i - B, 1]) if context_dropout > 0.0 else None
+            yield training_batch(pages, locations, origins, texts, glyph, size, crop_scale, context_dropout, drop_rng)

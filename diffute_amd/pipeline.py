@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _cabi, glyphs, prepost
-from .schedulers import launch_step
+from .schedulers import Guidance, launch_step, launch_step_guided
 
 
 _SIDE = {}
@@ -37,8 +37,10 @@ def mask_to_latent(mask, vae_scale_factor=8):
 class _Run:
     """One micro-batch of the denoise loop: its own stream, UNet execution slot and fixed-address buffers."""
 
-    def __init__(self, unet, scheduler, latents, mask, mlat, ctx, slot, stream, use_graph, ts_dev, temb_table, table_rows, cache_interval=1):
+    def __init__(self, unet, scheduler, latents, mask, mlat, ctx, slot, stream, use_graph, ts_dev, temb_table, table_rows, cache_interval=1,
+                 guidance=None):
         self.unet, self.slot, self.stream, self.use_graph = unet, slot, stream, use_graph
+        self.guidance, self.B = guidance, latents.shape[0]
         self.cache_interval, self.cache = cache_interval, None
         self.kind, self.vpred = scheduler.kind, int(scheduler.config.prediction_type == "v_prediction")
         self.ts_dev, self.temb_table, self.table_rows = ts_dev, temb_table, table_rows
@@ -46,10 +48,18 @@ class _Run:
             self.x = (latents.to(torch.float32) * scheduler.init_noise_sigma).contiguous()      # app.ipynb:800
             self.m = mask.to(torch.float32).contiguous()
             self.ml = mlat.to(torch.float32).contiguous()
+            if guidance is not None:
+                # guided: rows [0,B) run on the glyph context and rows [B,2B) on the unconditional one.  The second half of x / mask / masked
+                # latents is a duplicate made once, here; the guided step writes both halves of x.  The ring and the noise stay [B].
+                self.x, self.m, self.ml = (torch.cat([t, t], 0) for t in (self.x, self.m, self.ml))
+                ctx = torch.cat([ctx, guidance.uncond_for(ctx)], 0)
             self.eps = torch.empty_like(self.x)
             # DPM-Solver++: the ring of the data predictions of the last solver_order steps; a step's record names the slots it writes and reads
             n_hist = scheduler.config.solver_order if self.kind == _cabi.SCHED_DPMPP else 0
-            self.hist = [torch.empty_like(self.x) for _ in range(n_hist)]
+            if guidance is None:
+                self.hist = [torch.empty_like(self.x) for _ in range(n_hist)]
+            else:                        # one tensor [n_hist][B][...]: the guided step takes the ring whole and finds the slots from the record
+                self.hist = torch.empty((n_hist, self.B) + tuple(self.x.shape[1:]), dtype=torch.float32, device=self.x.device) if n_hist else None
             self.t_cur = torch.empty(1, dtype=torch.int64, device=self.x.device)   # fixed address: the captured graph reads it
             self.step_idx = torch.zeros(1, dtype=torch.int32, device=self.x.device)   # likewise: the row of temb_table this step fetches
             unet.set_context(ctx, slot=slot)
@@ -68,9 +78,36 @@ class _Run:
                 self.t_cur.copy_(self.ts_dev[i:i + 1], non_blocking=True)
                 self.unet.forward_parts([x, self.m, self.ml], self.t_cur, out=eps, graph=self.use_graph, slot=self.slot, **sc)
             # the update is elementwise, so prev_sample overwrites the sample in place (stable pointers for the graph)
+            if self.guidance is not None:
+                launch_step_guided(self.kind, rec, x, eps, noise, self.hist, self.vpred, self.guidance.scale, self.guidance.rescale,
+                                   _cabi.current_stream())
+                return
             launch_step(self.kind, rec, x, eps, noise, self.hist[rec.ring_m1] if rec.order >= 2 else None,
                         self.hist[rec.ring_m2] if rec.order >= 3 else None, self.hist[rec.ring_w] if self.hist else None, x, self.vpred,
                         _cabi.current_stream())
+
+
+def _rows(runs, name):
+    """the chains' x (the [B] latents) or eps (the raw model output: [B], guided [2B] with the conditional rows first) as one tensor"""
+    if runs[0].guidance is None:
+        return getattr(runs[0], name) if len(runs) == 1 else torch.cat([getattr(r, name) for r in runs], 0)
+    if name == "x":
+        return runs[0].x[:runs[0].B] if len(runs) == 1 else torch.cat([r.x[:r.B] for r in runs], 0)
+    return runs[0].eps if len(runs) == 1 else torch.cat([r.eps[:r.B] for r in runs] + [r.eps[r.B:] for r in runs], 0)
+
+
+def _check_guidance(guidance, encoder_hidden_states=None, N=None):
+    """the guidance= argument of denoise and the edit functions, checked on the host -> the Guidance to run, None for the plain loop.
+    encoder_hidden_states: the conditional contexts where they are known already (a per-row uncond must fit them), N their number."""
+    if guidance is None:
+        return None
+    if not isinstance(guidance, Guidance):
+        raise TypeError(f"guidance must be a diffute_amd.Guidance or None, got {type(guidance).__name__}")
+    if encoder_hidden_states is not None:
+        guidance.check_context(encoder_hidden_states, N)
+    elif guidance.uncond is not None and N is not None and guidance.uncond.shape[0] not in (1, N):
+        raise ValueError(f"Guidance: uncond {tuple(guidance.uncond.shape)} does not fit {N} boxes")
+    return guidance if guidance.active else None
 
 
 def _check_cache_interval(cache_interval):
@@ -82,7 +119,8 @@ def _check_cache_interval(cache_interval):
 
 @torch.no_grad()
 def denoise(unet, scheduler, latents, mask, masked_image_latents, encoder_hidden_states,
-            num_inference_steps, variance_noise=None, eta=0.0, callback=None, use_graph=True, micro_batches=1, cache_interval=1):
+            num_inference_steps, variance_noise=None, eta=0.0, callback=None, use_graph=True, micro_batches=1, cache_interval=1,
+            guidance=None):
     """latents/masked_image_latents [B,4,h,w], mask [B,1,h,w] (already at latent resolution), context
     [B,S,1024]; all on the GPU.  variance_noise: optional [steps,B,4,h,w] injected in place of the
     per-step device randn of DDPMScheduler.step (app.ipynb:816).  Returns the final latents (fp32).
@@ -95,8 +133,15 @@ def denoise(unet, scheduler, latents, mask, masked_image_latents, encoder_hidden
     UNet iff i % n == 0 and keeps the tensor entering the last up-block; the other steps run only conv_in, down-block 0, the last up-block
     on the kept tensor and the output layers (UNet2DConditionModel.forward_parts(step_cache=)).  Every step still produces an eps, so the
     schedulers - DPM-Solver++'s history ring included - see nothing of it.  The result differs from the plain loop's by design (how much
-    depends on the weights; not a rounding effect).  n = 1 is the plain loop: no cache, the plain entry points."""
+    depends on the weights; not a rounding effect).  n = 1 is the plain loop: no cache, the plain entry points.
+
+    guidance: a Guidance - classifier-free guidance.  Each chain then holds 2b rows (its b rows on the glyph context, then the same b rows
+    on the unconditional context), runs one 2b-row forward per step and one guided step (schedulers.launch_step_guided: the combination,
+    the optional rescale and the scheduler update in one launch, which also writes the new latents into both halves), so a guided pass at
+    B launches what a plain pass at 2B launches.  The result is rows [0,B); `callback` gets those and the raw [2B] model output
+    (conditional rows first).  None, or a Guidance with scale 1.0 and rescale 0, is the plain loop, bit for bit."""
     cache_interval = _check_cache_interval(cache_interval)
+    guidance = _check_guidance(guidance, encoder_hidden_states)
     _cabi.require_cuda(latents, mask, masked_image_latents, encoder_hidden_states)
     if scheduler.kind == _cabi.SCHED_DPMPP and (variance_noise is not None or eta != 0):
         raise ValueError("DPMSolverMultistepScheduler is deterministic: no variance_noise, eta = 0")
@@ -123,7 +168,8 @@ def denoise(unet, scheduler, latents, mask, masked_image_latents, encoder_hidden
         for j, (lo, hi) in enumerate(bounds):
             streams[j].wait_stream(main)
             runs.append(_Run(unet, scheduler, latents[lo:hi], mask[lo:hi], masked_image_latents[lo:hi],
-                             encoder_hidden_states[lo:hi].contiguous(), j, streams[j], use_graph, ts_dev, temb_table, table_rows, cache_interval))
+                             encoder_hidden_states[lo:hi].contiguous(), j, streams[j], use_graph, ts_dev, temb_table, table_rows, cache_interval,
+                             None if guidance is None else guidance.rows(slice(lo, hi))))
         # the plan, one record per step, is all the loop knows about the scheduler; it is walked lazily, so that the host computes a step's
         # scalars while the GPU works through the steps already enqueued
         for i, rec in enumerate(scheduler.iter_plan(eta)):
@@ -131,18 +177,17 @@ def denoise(unet, scheduler, latents, mask, masked_image_latents, encoder_hidden
                 nz = None
                 if rec.use_noise:
                     with torch.cuda.stream(run.stream):
-                        nz = (variance_noise[i][lo:hi] if variance_noise is not None else torch.randn_like(run.x)).to(torch.float32).contiguous()
+                        nz = (variance_noise[i][lo:hi] if variance_noise is not None else torch.randn_like(run.x[:run.B])).to(torch.float32).contiguous()
                 run.step(i, rec, nz)
             if callback is not None:
                 for s_ in streams:
                     main.wait_stream(s_)
-                callback(i, int(rec.timestep), runs[0].x if n == 1 else torch.cat([r.x for r in runs], 0),
-                         runs[0].eps if n == 1 else torch.cat([r.eps for r in runs], 0))
+                callback(i, int(rec.timestep), _rows(runs, "x"), _rows(runs, "eps"))
                 for s_ in streams:
                     s_.wait_stream(main)            # the callback's reads finish before the next step overwrites x / eps
         for s_ in streams:
             main.wait_stream(s_)
-        return runs[0].x if n == 1 else torch.cat([r.x for r in runs], 0)
+        return _rows(runs, "x")
     finally:
         if old_exclusive is not None:
             lib_.dmx_set_exclusive_device(old_exclusive)
@@ -150,12 +195,13 @@ def denoise(unet, scheduler, latents, mask, masked_image_latents, encoder_hidden
 
 @torch.no_grad()
 def edit_latents(unet, vae, scheduler, image, masked_image, mask, encoder_hidden_states, num_inference_steps,
-                 init_latents=None, generator=None, enc_noise=None, variance_noise=None, cache_interval=1):
+                 init_latents=None, generator=None, enc_noise=None, variance_noise=None, cache_interval=1, *, guidance=None):
     """The model part of text_editing() (app.ipynb:779-819): VAE-encode the masked crop, downsample the
     mask, denoise from seeded noise, VAE-decode.  `image` is unused by the arithmetic (the reference's encode of it,
     app.ipynb:781, is dead code: its result is overwritten at :798); enc_noise / variance_noise inject the two device-RNG
-    draws (latent_dist.sample(), DDPMScheduler.step) for tests.  Crop / resize / paste: diffute_amd.prepost.  cache_interval: denoise's."""
+    draws (latent_dist.sample(), DDPMScheduler.step) for tests.  Crop / resize / paste: diffute_amd.prepost.  cache_interval, guidance: denoise's."""
     cache_interval = _check_cache_interval(cache_interval)
+    _check_guidance(guidance, encoder_hidden_states)
     sf = vae.config.scaling_factor
     f = 2 ** (len(vae.config.block_out_channels) - 1)
     m = mask_to_latent(mask, f)
@@ -166,14 +212,14 @@ def edit_latents(unet, vae, scheduler, image, masked_image, mask, encoder_hidden
         init_latents = torch.randn((B, vae.config.latent_channels, H // f, W // f),
                                    generator=torch.manual_seed(0), dtype=torch.float32).to(masked_image.device)  # :798
     lat = denoise(unet, scheduler, init_latents, m, mlat, encoder_hidden_states, num_inference_steps, variance_noise=variance_noise,
-                  cache_interval=cache_interval)
+                  cache_interval=cache_interval, guidance=guidance)
     return vae.decode(lat / sf).sample                                                    # app.ipynb:818-819
 
 
 @torch.no_grad()
 def edit_boxes(unet, vae, scheduler, instance_image, locations, encoder_hidden_states, num_inference_steps, *, origins=None,
                crop_scales=None, rng=None, batch_size=4, generator=None, enc_noise=None, variance_noise=None,
-               return_intermediate=False, size=512, cache_interval=1, texts=None, glyph=None):
+               return_intermediate=False, size=512, cache_interval=1, texts=None, glyph=None, guidance=None):
     """text_editing() (app.ipynb:674-846) for several boxes of ONE image as one batch: instance_image uint8 CUDA [h][w][3], locations
     N boxes (x1, y1, x2, y2), encoder_hidden_states [N,L,D] the glyph context of each box.  One preprocess_batch launch, the boxes
     through edit_latents in chunks of `batch_size` (the last chunk may be smaller), one postprocess_batch launch; returns the uint8
@@ -189,15 +235,19 @@ def edit_boxes(unet, vae, scheduler, instance_image, locations, encoder_hidden_s
 
     texts / glyph: instead of encoder_hidden_states (pass None there), the N strings the boxes should show and
     glyph = (renderer, processor, encoder) - a GlyphRenderer, a TrOCRProcessor and a TrOCREncoder; the contexts are then
-    glyph_contexts(texts, *glyph), rendered on the device.  Exactly one of encoder_hidden_states and texts must be given."""
+    glyph_contexts(texts, *glyph), rendered on the device.  Exactly one of encoder_hidden_states and texts must be given.
+
+    guidance: a Guidance, denoise's classifier-free guidance for every chunk; an uncond of [N,S,D] is one unconditional context per box
+    and is chunked like encoder_hidden_states."""
     return _edit(False, unet, vae, scheduler, [instance_image], [locations], encoder_hidden_states, num_inference_steps, _one(origins),
-                 _one(crop_scales), rng, batch_size, generator, enc_noise, variance_noise, return_intermediate, size, cache_interval, texts, glyph)
+                 _one(crop_scales), rng, batch_size, generator, enc_noise, variance_noise, return_intermediate, size, cache_interval, texts, glyph,
+                 guidance)
 
 
 @torch.no_grad()
 def edit_pages(unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, *, origins=None, crop_scales=None,
                rng=None, batch_size=4, generator=None, enc_noise=None, variance_noise=None, return_intermediate=False, size=512,
-               cache_interval=1, texts=None, glyph=None):
+               cache_interval=1, texts=None, glyph=None, guidance=None):
     """edit_boxes for boxes on SEVERAL pages as one batch - what a service holding requests for different images, or a training batch
     of one box per image, needs.  images: a list of P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device; locations: P lists of
     boxes (x1, y1, x2, y2); origins / crop_scales: None or P lists, as for edit_boxes per page (what is not given is planned page after
@@ -207,24 +257,25 @@ def edit_pages(unet, vae, scheduler, images, locations, encoder_hidden_states, n
     One preprocess_pages launch, the N rows through edit_latents in chunks of `batch_size` (chunks cross page boundaries; every box
     starts from the seed-0 single-sample draw), one postprocess_pages launch.  Returns the list of P edited pages, with
     return_intermediate=True also image_vae [N,3,S,S] and the preprocess dict.  With one page this is [edit_boxes(...)], bit for bit.
-    texts / glyph: as for edit_boxes, N strings page-major."""
+    texts / glyph: as for edit_boxes, N strings page-major.  guidance: as for edit_boxes, a per-box uncond [N,S,D] page-major."""
     return _edit(True, unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, origins, crop_scales, rng,
-                 batch_size, generator, enc_noise, variance_noise, return_intermediate, size, cache_interval, texts, glyph)
+                 batch_size, generator, enc_noise, variance_noise, return_intermediate, size, cache_interval, texts, glyph, guidance)
 
 
 def _edit(paged, unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, origins, crop_scales, rng, batch_size,
-          generator, enc_noise, variance_noise, return_intermediate, size, cache_interval=1, texts=None, glyph=None):
+          generator, enc_noise, variance_noise, return_intermediate, size, cache_interval=1, texts=None, glyph=None, guidance=None):
     """edit_boxes (paged=False: one page, its lists wrapped into one-element lists) and edit_pages"""
     if int(batch_size) < 1:
         raise ValueError("batch_size must be at least 1")
     cache_interval = _check_cache_interval(cache_interval)
     images, locations, origins, crop_scales, sizes, N = _page_lists(paged, images, locations, origins, crop_scales)
     _check_contexts(N, encoder_hidden_states, texts, glyph)
+    guidance = _check_guidance(guidance, encoder_hidden_states, N)
     where = _plan_pages(paged, images, locations, sizes, origins, crop_scales, rng)
     encoder_hidden_states = _contexts(encoder_hidden_states, texts, glyph)
     pre = (prepost.preprocess_pages if paged else prepost.preprocess_batch)(*where, size=size)
     image_vae = _edit_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
-                           enc_noise, variance_noise, int(size), cache_interval)
+                           enc_noise, variance_noise, int(size), cache_interval, guidance)
     out = (prepost.postprocess_pages if paged else prepost.postprocess_batch)(image_vae, *where)
     return (out, image_vae, pre) if return_intermediate else out
 
@@ -310,7 +361,7 @@ def _plan_pages(paged, images, locations, sizes, origins, crop_scales, rng):
 
 @torch.no_grad()
 def _edit_rows(unet, vae, scheduler, pre, dev, encoder_hidden_states, num_inference_steps, bs, generator, enc_noise, variance_noise, S,
-               cache_interval=1):
+               cache_interval=1, guidance=None):
     """the model part of edit_boxes / edit_pages: the N rows of the preprocess dict `pre` through edit_latents in chunks of `bs` (the last
     chunk may be smaller) -> image_vae [N,3,S,S].  A row's page plays no part here."""
     N = pre["image"].shape[0]
@@ -324,7 +375,8 @@ def _edit_rows(unet, vae, scheduler, pre, dev, encoder_hidden_states, num_infere
                                  encoder_hidden_states[lo:hi], num_inference_steps,
                                  init_latents=init.expand(hi - lo, -1, -1, -1).contiguous(), generator=generator,
                                  enc_noise=None if enc_noise is None else enc_noise[lo:hi],
-                                 variance_noise=None if variance_noise is None else variance_noise[:, lo:hi], cache_interval=cache_interval))
+                                 variance_noise=None if variance_noise is None else variance_noise[:, lo:hi], cache_interval=cache_interval,
+                                 guidance=None if guidance is None else guidance.rows(slice(lo, hi))))
     return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
 
@@ -383,7 +435,7 @@ def _check_verified_processor(ocr, processor, size):
 
 @torch.no_grad()
 def _candidate_rows(unet, vae, scheduler, pre, dev, ctx, num_inference_steps, seeds, bs, generator, enc_noise, variance_noise, S,
-                    cache_interval=1):
+                    cache_interval=1, guidance=None):
     """the generating half of the verified edits, after the preprocess: the N rows of the preprocess dict `pre`, whatever pages they come
     from -> image_vae [N,K,3,S,S].  Each box is VAE-encoded once; the N*K rows (box-major, candidate k from seeds[k]) go through denoise +
     vae.decode in chunks of `bs`.  With one seed this is _edit_rows' loop, chunk for chunk."""
@@ -408,7 +460,7 @@ def _candidate_rows(unet, vae, scheduler, pre, dev, ctx, num_inference_steps, se
         box = (rows // K).tolist()
         lat = denoise(unet, scheduler, init[(rows % K).to(dev)].contiguous(), mask_lat[box], torch.cat([mlat[b] for b in box], 0), ctx[box],
                       num_inference_steps, variance_noise=None if variance_noise is None else variance_noise[:, lo:hi],
-                      cache_interval=cache_interval)
+                      cache_interval=cache_interval, guidance=None if guidance is None else guidance.rows(box))
         outs.append(vae.decode(lat / sf).sample)
         for b in range(b0, b1):
             if (b + 1) * K <= hi:
@@ -420,7 +472,7 @@ def _candidate_rows(unet, vae, scheduler, pre, dev, ctx, num_inference_steps, se
 def edit_boxes_verified(unet, vae, scheduler, ocr, processor, instance_image, locations, encoder_hidden_states, labels, num_inference_steps, *,
                         candidates=4, seeds=None, min_score=None, batch_size=4, ocr_batch_size=32, origins=None, crop_scales=None, rng=None,
                         generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False, cache_interval=1, texts=None,
-                        glyph=None):
+                        glyph=None, guidance=None):
     """edit_boxes with a read-back: K = `candidates` edits per box from K starting noises, each read by the OCR model `ocr` (a
     VisionEncoderDecoderModel) against the text the box should show, the best-reading one pasted (the reference sketches the read-back at
     app.ipynb:842-846).  labels: int64 [N,T] token ids of the requested texts, -100 = padding (the tokenizer is out of scope).
@@ -435,36 +487,38 @@ def edit_boxes_verified(unet, vae, scheduler, ocr, processor, instance_image, lo
 
     Returns the uint8 [h][w][3] page, or a VerifiedEdit with return_intermediate=True.  candidates=1 with min_score=None returns the
     page of edit_boxes with the same arguments, bit for bit.  cache_interval: denoise's, for every chunk of candidate rows.
-    texts / glyph: as for edit_boxes, in place of encoder_hidden_states (labels stay token ids: the tokenizer is out of scope)."""
+    texts / glyph: as for edit_boxes, in place of encoder_hidden_states (labels stay token ids: the tokenizer is out of scope).
+    guidance: as for edit_boxes; a per-box uncond [N,S,D] is shared by the box's K candidates, like its glyph context."""
     return _edit_verified(False, unet, vae, scheduler, ocr, processor, [instance_image], [locations], encoder_hidden_states, labels,
                           num_inference_steps, candidates, seeds, min_score, batch_size, ocr_batch_size, _one(origins), _one(crop_scales), rng,
-                          generator, enc_noise, variance_noise, size, return_intermediate, cache_interval, texts, glyph)
+                          generator, enc_noise, variance_noise, size, return_intermediate, cache_interval, texts, glyph, guidance)
 
 
 @torch.no_grad()
 def edit_pages_verified(unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps, *,
                         candidates=4, seeds=None, min_score=None, batch_size=4, ocr_batch_size=32, origins=None, crop_scales=None, rng=None,
                         generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False, cache_interval=1, texts=None,
-                        glyph=None):
+                        glyph=None, guidance=None):
     """edit_boxes_verified for boxes on several pages: images / locations / origins / crop_scales as for edit_pages, everything per box
     (encoder_hidden_states [N,L,D], labels [N,T], enc_noise [N,4,h,w]) page-major.  The N*K rows go through edit_boxes_verified's chunk
     loop, prepost.readback_pixel_values_pages, ocr.score and prepost.postprocess_select_pages - chunks cross page boundaries, no score is
     read on the host.  Returns the list of P pages, or a VerifiedEdit whose `image` is that list with return_intermediate=True.
-    candidates=1 with min_score=None returns edit_pages' pages, bit for bit.  texts / glyph: as for edit_boxes, page-major."""
+    candidates=1 with min_score=None returns edit_pages' pages, bit for bit.  texts / glyph, guidance: as for edit_boxes, page-major."""
     return _edit_verified(True, unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps,
                           candidates, seeds, min_score, batch_size, ocr_batch_size, origins, crop_scales, rng, generator, enc_noise,
-                          variance_noise, size, return_intermediate, cache_interval, texts, glyph)
+                          variance_noise, size, return_intermediate, cache_interval, texts, glyph, guidance)
 
 
 def _edit_verified(paged, unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps, candidates,
                    seeds, min_score, batch_size, ocr_batch_size, origins, crop_scales, rng, generator, enc_noise, variance_noise, size,
-                   return_intermediate, cache_interval=1, texts=None, glyph=None):
+                   return_intermediate, cache_interval=1, texts=None, glyph=None, guidance=None):
     """edit_boxes_verified (paged=False: one page, its lists wrapped into one-element lists) and edit_pages_verified.  Every argument is
     checked on the host side first: nothing touches the GPU and no crop is planned - so nothing is drawn from rng - before all have passed."""
     images, locations, origins, crop_scales, sizes, N = _page_lists(paged, images, locations, origins, crop_scales)
     K, seeds = _check_verified_counts(N, candidates, seeds, min_score, batch_size, ocr_batch_size)
     cache_interval = _check_cache_interval(cache_interval)
     _check_verified_labels(ocr, N, encoder_hidden_states, labels, texts, glyph)
+    guidance = _check_guidance(guidance, encoder_hidden_states, N)
     if paged:
         prepost.check_readback_boxes_pages([loc for l in locations for loc in l], [len(l) for l in locations], sizes)
     else:
@@ -474,7 +528,7 @@ def _edit_verified(paged, unet, vae, scheduler, ocr, processor, images, location
     encoder_hidden_states = _contexts(encoder_hidden_states, texts, glyph)
     pre = (prepost.preprocess_pages if paged else prepost.preprocess_batch)(*where, size=int(size))
     image_vae = _candidate_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, seeds, int(batch_size),
-                                generator, enc_noise, variance_noise, int(size), cache_interval)
+                                generator, enc_noise, variance_noise, int(size), cache_interval, guidance)
     pixel_values = (prepost.readback_pixel_values_pages if paged else prepost.readback_pixel_values)(image_vae, *where, ip)
     scores = _score_candidates(ocr, pixel_values, labels, N, K, int(ocr_batch_size))
     out, choice = (prepost.postprocess_select_pages if paged else prepost.postprocess_select_batch)(image_vae, scores, *where, threshold=min_score)

@@ -46,6 +46,72 @@ def launch_step(kind, rec, x, eps, noise, m1, m2, x0_out, out, vpred, stream):
     _cabi.check(rc, ("sched_step_ddim", "sched_step_ddpm", "sched_step_dpmpp")[kind])
 
 
+def launch_step_guided(kind, rec, x, eps, noise, hist, vpred, scale, rescale, stream, ratio_out=None):
+    """One guided scheduler step in one launch (include/diffute_hip.h dmx_sched_step_guided): x / eps fp32 CUDA [2B, ...], rows [0,B) the
+    conditional half and [B,2B) the unconditional one.  The classifier-free combination eu + scale * (ec - eu), with rescale != 0 the
+    guidance rescale (per-sample std(ec) / std(g), Lin et al. 2023), then the update of `kind` from the record; prev_sample is written in
+    place to row b AND row B + b of x.  noise [B, ...] or None; hist [n_hist, B, ...], the DPM-Solver++ ring (None otherwise);
+    ratio_out fp32 [B] or None receives the per-sample ratios."""
+    B2 = x.shape[0]
+    if B2 < 2 or B2 % 2 or eps.shape != x.shape:
+        raise ValueError(f"launch_step_guided: x {tuple(x.shape)} / eps {tuple(eps.shape)} must be [2B, ...] and agree")
+    B = B2 // 2
+    rc = _cabi.lib().dmx_sched_step_guided(_cabi.ptr(x), _cabi.ptr(eps), _cabi.ptr(noise), _cabi.ptr(hist), 0 if hist is None else hist.shape[0],
+                                           rec, kind, vpred, float(scale), float(rescale), float(1 - rescale), _cabi.ptr(ratio_out), B,
+                                           x.numel() // B2, stream)
+    _cabi.check(rc, "sched_step_guided")
+
+
+class Guidance:
+    """Classifier-free guidance for denoise() and the edit functions: the model runs on the glyph context and on an unconditional one and
+    the scheduler steps on eu + scale * (ec - eu).  rescale in [0, 1] is the guidance rescale of Lin et al. 2023 (diffusers'
+    rescale_noise_cfg): the guided output scaled back towards the per-sample standard deviation of the conditional one.  uncond: the
+    unconditional context - None is the all-zero context (what training_batch(context_dropout=) trains), a tensor [1,S,D] is shared by all
+    rows, [N,S,D] is one per row.  scale == 1 with rescale == 0 is the plain loop (`active` is False): no unconditional rows are run.
+    Everything is checked here or, against the conditional context, in check_context - on the host, before anything touches the device."""
+
+    def __init__(self, scale, rescale=0.0, uncond=None):
+        scale, rescale = float(scale), float(rescale)
+        if not np.isfinite(scale):
+            raise ValueError(f"Guidance: scale = {scale} is not finite")
+        if not 0.0 <= rescale <= 1.0:                      # (NaN fails both comparisons)
+            raise ValueError(f"Guidance: rescale = {rescale} outside [0, 1]")
+        if uncond is not None:
+            if not torch.is_tensor(uncond) or uncond.dim() != 3 or uncond.shape[0] < 1:
+                raise ValueError("Guidance: uncond must be a tensor [1,S,D] or [N,S,D]")
+            if not uncond.is_floating_point():
+                raise ValueError(f"Guidance: uncond has dtype {uncond.dtype}, expected a floating-point context")
+        self.scale, self.rescale, self.uncond = scale, rescale, uncond
+
+    @property
+    def active(self):
+        return not (self.scale == 1.0 and self.rescale == 0.0)
+
+    def check_context(self, ctx, N=None):
+        """uncond against the conditional context [N,S,D] (N: the number of rows where ctx is not given whole)"""
+        u = self.uncond
+        if u is None:
+            return
+        N = ctx.shape[0] if N is None else N
+        if tuple(u.shape[1:]) != tuple(ctx.shape[1:]) or u.shape[0] not in (1, N):
+            raise ValueError(f"Guidance: uncond {tuple(u.shape)} does not fit {N} contexts of {tuple(ctx.shape[1:])}: expected "
+                             f"[1,{ctx.shape[1]},{ctx.shape[2]}] or [{N},{ctx.shape[1]},{ctx.shape[2]}]")
+        if u.dtype != ctx.dtype or u.device != ctx.device:
+            raise ValueError(f"Guidance: uncond is {u.dtype} on {u.device}, the context {ctx.dtype} on {ctx.device}")
+
+    def rows(self, index):
+        """the guidance of the rows `index` (a slice or a list of row numbers) of a batch: a per-row uncond follows its rows"""
+        if self.uncond is None or self.uncond.shape[0] == 1:
+            return self
+        return Guidance(self.scale, self.rescale, self.uncond[index])
+
+    def uncond_for(self, ctx):
+        """the unconditional context of the rows of `ctx` [B,S,D]"""
+        if self.uncond is None:
+            return torch.zeros_like(ctx)
+        return self.uncond.expand(ctx.shape[0], -1, -1) if self.uncond.shape[0] == 1 else self.uncond
+
+
 class _Config(SimpleNamespace):
     def __getitem__(self, k):
         return getattr(self, k)

@@ -494,6 +494,24 @@ enum { DMX_SCHED_DDIM = 0, DMX_SCHED_DDPM = 1, DMX_SCHED_DPMPP = 2 };
 int dmx_sched_step_rows(float* sample, const float* model_output, const float* noise, float* hist, int n_hist,
                         const dmx_sched_row_rec* plan, const int* row_index, int B, size_t per_sample, int kind, int v_prediction,
                         dmx_stream_t stream);
+/* Classifier-free guidance (Ho & Salimans 2022), the optional guidance rescale (Lin et al. 2023, diffusers' rescale_noise_cfg) and the
+ * scheduler step of B samples in ONE launch.  model_output [2B][per_sample]: rows [0,B) from the conditional context, rows [B,2B) from
+ * the unconditional one.  sample [2B][per_sample]: sample b is READ from row b only; prev_sample is written to row b AND row B + b, so
+ * the next 2B-row forward reads it with no copy (rows [B,2B) are write-only).  noise [B][per_sample] or NULL (added when given; must be
+ * NULL for DPM-Solver++); hist [n_hist][B][per_sample], the DPM-Solver++ ring (NULL, 0 otherwise): rec names the slot it writes
+ * (ring_w, this step's m0) and the two it reads, as for the per-row entry.  rec: the step's record, by value.  Per element, ec / eu the
+ * conditional / unconditional model output, every op fp32 round-to-nearest in this order:
+ *   g = eu + guidance_scale * (ec - eu);   rescale == 0: e = g;   else e = rescale * (g * k_b) + one_minus_rescale * g
+ * with k_b = std_b(ec) / std_b(g), the UNBIASED standard deviations over the per_sample elements of sample b (fp32, mean first, then
+ * the centred squares, in a fixed order: the same bits on every run).  std_b(g) == 0 gives k_b = inf or NaN, which propagates into the
+ * sample as it does in diffusers.  Then the update of `kind` on (sample, e): bit-identical to the matching scalar entry above run on e.
+ * ratio_out [B] or NULL receives k_b (written only when rescale != 0).  per_sample need not be a multiple of 4.
+ * DMX_ERR_ARG, nothing written: B < 1, per_sample == 0, NULL sample / model_output, kind outside the enum, DPM-Solver++ with noise or
+ * with a record its ring cannot serve (order 1..n_hist, slots inside the ring, a read slot equal to the written one), rescale outside
+ * [0, 1], rescale != 0 with per_sample < 2, a non-finite guidance_scale / rescale / one_minus_rescale. */
+int dmx_sched_step_guided(float* sample, const float* model_output, const float* noise, float* hist, int n_hist, dmx_sched_row_rec rec,
+                          int kind, int v_prediction, float guidance_scale, float rescale, float one_minus_rescale, float* ratio_out,
+                          int B, size_t per_sample, dmx_stream_t stream);
 /* row b starts at plan row plan_base with n_steps steps to run (the values travel as kernel arguments: no staging buffer) */
 int dmx_rows_admit(int* row_index, int* row_left, int b, int plan_base, int n_steps, dmx_stream_t stream);
 /* after the scheduler launch of a tick: every active row index++, left--, index = -1 at left == 0 */

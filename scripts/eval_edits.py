@@ -1,6 +1,6 @@
 """What a change to the denoise loop does to the PAGE a user gets back, measured on the edited boxes with diffute_amd.metrics:
 
-    python scripts/eval_edits.py [--weights DIR] [--ocr DIR --labels FILE.json] [--steps 50] [--out FILE]
+    python scripts/eval_edits.py [--weights DIR] [--ocr DIR --labels FILE.json] [--steps 50] [--guidance] [--out FILE]
 
 A synthetic 1100 x 1300 page (white, dark strokes), N = 4 boxes (scripts/bench_edit.py's), 512 px.  The base is the plain DDIM-50 loop;
 the variants are cache_interval 2 / 3 / 5, DPM-Solver++ 20 / 25 and, where the library is built, the fp16 build.  Per variant, against
@@ -11,6 +11,8 @@ the ORIGINAL page, which must be 0 for every variant (the script exits 1 otherwi
 pixel-space distances between runs of a random network - better than the rel-L2 of latents they replace, no statement about quality.
 --ocr DIR (a TrOCR VisionEncoderDecoder directory) with --labels FILE.json (N lists of token ids, the text each box should show): also the
 share of boxes whose teacher-forced arg-max equals the labels (ocr.score), per variant.
+--guidance: also the guided variants - classifier-free guidance (diffute_amd.Guidance, the zero context as the unconditional one) at
+scale 3 and 7.5, and 7.5 with rescale 0.7 - on the base's loop.  Without the flag the line is what it always was.
 
 It also times box_metrics_pages at N = 4 / 16 / 64 boxes of 40 x 200 px against the same numbers from a chain of torch ops on the device
 (per box one conv2d over x, y, x^2, y^2, xy with the 11 x 11 window): median of 7, one process.  Prints one JSON line
@@ -77,6 +79,7 @@ def main():
     ap.add_argument("--ocr", default=None, help="TrOCR VisionEncoderDecoder directory: report the share of boxes that read as their labels")
     ap.add_argument("--labels", default=None, help="JSON file: N lists of token ids (needed with --ocr)")
     ap.add_argument("--steps", type=int, default=50, help="DDIM steps of the base")
+    ap.add_argument("--guidance", action="store_true", help="add the classifier-free-guidance variants (scale 3, 7.5, 7.5 with rescale 0.7)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if (args.ocr is None) != (args.labels is None):
@@ -119,6 +122,9 @@ def main():
 
     variants = [(f"ddim{args.steps}_interval{n}", lambda n=n: edit(D.DDIMScheduler(), args.steps, cache_interval=n)) for n in (2, 3, 5)]
     variants += [(f"dpmpp2m_{s}", lambda s=s: edit(D.DPMSolverMultistepScheduler(), s)) for s in (20, 25)]
+    if args.guidance:
+        variants += [(f"ddim{args.steps}_guidance{sc:g}" + (f"_rescale{rs:g}" if rs else ""),
+                      lambda sc=sc, rs=rs: edit(D.DDIMScheduler(), args.steps, guidance=D.Guidance(sc, rs))) for sc, rs in ((3.0, 0.0), (7.5, 0.0), (7.5, 0.7))]
     base = edit(D.DDIMScheduler(), args.steps)
     ok = bool(torch.equal(base, edit(D.DDIMScheduler(), args.steps)))            # the base itself repeats bit for bit
     base_out = metrics.outside_diff(page, base, boxes)

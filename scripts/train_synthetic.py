@@ -1,6 +1,7 @@
 """Does the training loop learn on rendered text, and does the glyph context carry anything the UNet can use?
 
-    python scripts/train_synthetic.py [--steps 300] [--batch 4] [--lr 2e-4] [--size 128] [--eval-pages 8] [--out profiles/train_synthetic_line.json]
+    python scripts/train_synthetic.py [--steps 300] [--batch 4] [--lr 2e-4] [--size 128] [--eval-pages 8] [--context_dropout 0]
+                                      [--out profiles/train_synthetic_line.json]
 
 The tiny UNet / VAE / glyph encoder of the tests (random initialisation; VAE and encoder frozen, as in the reference) are trained with
 train_step + FusedAdamW on SyntheticDocuments.batches: pages composed on the device, one confident line per page, the reference's
@@ -9,7 +10,11 @@ reaches) are evaluated at fixed timesteps and fixed noise in two ways: with each
 by one row (row b gets the text of row b + 1).  If the UNet uses the context, the own-context loss falls below the rotated one.
 
 Prints one JSON line (and writes it to --out): the mean loss of the first and of the last tenth of the steps, and the two held-out losses
-before and after training.  The numbers are reported, not asserted: nobody has measured whether a random frozen VAE leaves a visible gap."""
+before and after training.  The numbers are reported, not asserted: nobody has measured whether a random frozen VAE leaves a visible gap.
+
+--context_dropout P (the training half of classifier-free guidance, diffute_amd.Guidance): with probability P a training row's glyph
+context is replaced by zeros (SyntheticDocuments.batches(context_dropout=P)).  The line then also carries the held-out loss under the NULL
+(all-zero) context before and after training, next to the own / rotated figures.  With the default 0 the line is what it always was."""
 import argparse
 import json
 import os
@@ -57,6 +62,7 @@ def main():
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--eval-pages", type=int, default=8)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--context_dropout", type=float, default=0.0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_synthetic_line.json"))
     args = ap.parse_args()
     import diffute_amd as D
@@ -82,11 +88,13 @@ def main():
     own, rotated = held["ocr_embeddings"], torch.roll(held["ocr_embeddings"], -1, 0)
 
     def evaluate():
-        return held_out_loss(unet, vae, sched, held, own, fixed), held_out_loss(unet, vae, sched, held, rotated, fixed)
+        r = held_out_loss(unet, vae, sched, held, own, fixed), held_out_loss(unet, vae, sched, held, rotated, fixed)
+        return r + (held_out_loss(unet, vae, sched, held, torch.zeros_like(own), fixed),) if args.context_dropout > 0 else r
 
     before = evaluate()
     losses, t0 = [], time.perf_counter()
-    batches = ds.batches(args.batch, np.random.default_rng(args.seed + 3), size=S)
+    drop = dict(context_dropout=args.context_dropout) if args.context_dropout > 0 else {}
+    batches = ds.batches(args.batch, np.random.default_rng(args.seed + 3), size=S, **drop)
     for _ in range(args.steps):
         out = train_step(unet, vae, sched, opt, next(batches), generator=gen)
         losses.append(out["loss"])
@@ -102,6 +110,9 @@ def main():
                held_out_own_after=round(after[0], 6), held_out_rotated_after=round(after[1], 6),
                gap_before=round(before[1] - before[0], 6), gap_after=round(after[1] - after[0], 6),
                ms_per_step_with_data=round(seconds / args.steps * 1e3, 2))
+    if args.context_dropout > 0:
+        res.update(context_dropout=args.context_dropout, held_out_null_before=round(before[2], 6), held_out_null_after=round(after[2], 6),
+                   null_gap_before=round(before[2] - before[0], 6), null_gap_after=round(after[2] - after[0], 6))
     line = json.dumps(res)
     print(line)
     if args.out:
