@@ -431,6 +431,29 @@ extern "C" int dmx_sched_step_guided(float* sample, const float* model_output, c
   return dmx_sched_guided_launch(kind, rec, sample, model_output, noise, kind == DMX_SCHED_DPMPP ? hist : nullptr, guidance_scale, rescale,
                                  one_minus_rescale, ratio_out, B, per_sample, v_prediction, (hipStream_t)stream);
 }
+extern "C" int dmx_sched_step_rows_guided(float* sample, const float* model_output, const float* noise, float* hist, int n_hist,
+                                          const dmx_sched_row_rec* plan, const int* row_index, const dmx_guide_row* guide, float* ratio_out, int B,
+                                          size_t per_sample, int kind, int v_prediction, dmx_stream_t stream) {
+  DMX_REQUIRE(sample && model_output && plan && row_index && guide, "sched_step_rows_guided: null argument");
+  DMX_REQUIRE(B >= 1 && B <= 65535 && per_sample >= 2, "sched_step_rows_guided: B=%d rows of %zu elements (a rescaled row needs at least 2)", B, per_sample);
+  DMX_REQUIRE(kind == DMX_SCHED_DDIM || kind == DMX_SCHED_DDPM || kind == DMX_SCHED_DPMPP, "sched_step_rows_guided: kind %d", kind);
+  if (kind == DMX_SCHED_DPMPP) {
+    DMX_REQUIRE(noise == nullptr, "sched_step_rows_guided: DPM-Solver++ is deterministic (noise must be NULL)");
+    DMX_REQUIRE(hist && n_hist >= 1 && n_hist <= 3, "sched_step_rows_guided: DPM-Solver++ needs its history ring (n_hist 1..3)");
+    const size_t nb = (size_t)B * per_sample;
+    DMX_REQUIRE(hist + (size_t)n_hist * nb <= sample || sample + nb <= hist, "sched_step_rows_guided: the history ring overlaps the sample");
+  }
+  return dmx_sched_rows_guided_launch(sample, model_output, noise, kind == DMX_SCHED_DPMPP ? hist : nullptr, kind == DMX_SCHED_DPMPP ? n_hist : 0,
+                                      plan, row_index, guide, ratio_out, B, per_sample, kind, v_prediction, (hipStream_t)stream);
+}
+extern "C" int dmx_rows_guide(dmx_guide_row* guide, int b0, int n, int guided, float scale, float rescale, float one_minus_rescale,
+                              dmx_stream_t stream) {
+  DMX_REQUIRE(guide && b0 >= 0 && n >= 1 && (guided == 0 || guided == 1), "rows_guide: rows from %d, %d of them, guided %d", b0, n, guided);
+  DMX_REQUIRE(std::isfinite(scale) && std::isfinite(rescale) && std::isfinite(one_minus_rescale),
+              "rows_guide: scale, rescale and one_minus_rescale must be finite");
+  DMX_REQUIRE(rescale >= 0.f && rescale <= 1.f, "rows_guide: rescale %g outside [0, 1]", (double)rescale);
+  return dmx_rows_guide_launch(guide, b0, n, guided, scale, rescale, one_minus_rescale, (hipStream_t)stream);
+}
 extern "C" int dmx_rows_admit(int* row_index, int* row_left, int b, int plan_base, int n_steps, dmx_stream_t stream) {
   DMX_REQUIRE(row_index && row_left && b >= 0 && plan_base >= 0 && n_steps >= 0, "rows_admit: row %d, plan row %d, %d steps", b, plan_base, n_steps);
   return dmx_rows_admit_launch(row_index, row_left, b, plan_base, n_steps, (hipStream_t)stream);

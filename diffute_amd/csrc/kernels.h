@@ -419,6 +419,11 @@ int dmx_sched_rows_launch(float* x, const float* eps, const float* noise, float*
 // the guided step: x / eps [2B][per] (conditional rows, then unconditional), noise / hist [.][B][per]; the record's ring slots are the caller's to check
 int dmx_sched_guided_launch(int kind, const dmx_sched_row_rec& rec, float* x, const float* eps, const float* noise, float* hist, float scale,
                             float rescale, float one_minus_rescale, float* ratio_out, int B, size_t per, int vpred, hipStream_t stream);
+// the per-row guided step: the per-row form with a role per row (guide [B]); always grid (1, B) of 1024 threads
+int dmx_sched_rows_guided_launch(float* x, const float* eps, const float* noise, float* hist, int n_hist, const dmx_sched_row_rec* plan,
+                                 const int* row_index, const dmx_guide_row* guide, float* ratio_out, int B, size_t per, int kind, int vpred,
+                                 hipStream_t stream);
+int dmx_rows_guide_launch(dmx_guide_row* guide, int b0, int n, int guided, float scale, float rescale, float one_minus_rescale, hipStream_t stream);
 int dmx_rows_admit_launch(int* row_index, int* row_left, int b, int plan_base, int n_steps, hipStream_t stream);
 int dmx_rows_advance_launch(int* row_index, int* row_left, int B, hipStream_t stream);
 int dmx_add_noise_launch(const float* x0, const float* noise, const float* sa, const float* sb, float* out,

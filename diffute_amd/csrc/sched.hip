@@ -212,6 +212,19 @@ int dmx_sched_step_launch(int kind, const dmx_sched_row_rec& r, const float* x, 
 // (row_index[b] < 0: idle - the block returns before it reads or writes anything of the row), with the noise term only where the record asks
 // for it.  hist [n_hist][B][per]: the DPM-Solver++ ring; the record names the slot it writes (ring_w) and the two it reads (ring_m1, ring_m2).
 // The span is the scalar entries', so an active row equals the scalar entry run on that row alone, bit for bit.
+// the history slices of row b under record r -> false: a record the ring cannot serve (the row is left alone).  Not DPM-Solver++: no slices.
+template <int KIND>
+__device__ __forceinline__ bool sched_row_ring(const dmx_sched_row_rec& r, float* hist, int n_hist, int B, int b, size_t per, float*& m0,
+                                               const float*& m1, const float*& m2) {
+  m0 = nullptr; m1 = nullptr; m2 = nullptr;
+  if (KIND != DMX_SCHED_DPMPP) return true;
+  const int order = r.order;
+  if (order < 1 || order > n_hist || order > 3 || r.ring_w < 0 || r.ring_w >= n_hist) return false;
+  m0 = hist + ((size_t)r.ring_w * B + b) * per;
+  if (order >= 2) { if (r.ring_m1 < 0 || r.ring_m1 >= n_hist || r.ring_m1 == r.ring_w) return false; m1 = hist + ((size_t)r.ring_m1 * B + b) * per; }
+  if (order >= 3) { if (r.ring_m2 < 0 || r.ring_m2 >= n_hist || r.ring_m2 == r.ring_w) return false; m2 = hist + ((size_t)r.ring_m2 * B + b) * per; }
+  return true;
+}
 template <int KIND>
 __global__ __launch_bounds__(256) void dmx_sched_rows_kernel(float* x, const float* eps, const float* noise, float* hist, int n_hist,
                                                              const dmx_sched_row_rec* plan, const int* row_index, int B, size_t per, int vpred) {
@@ -219,14 +232,8 @@ __global__ __launch_bounds__(256) void dmx_sched_rows_kernel(float* x, const flo
   const int idx = row_index[b];
   if (idx < 0) return;
   const dmx_sched_row_rec r = plan[idx];
-  float* m0 = nullptr; const float* m1 = nullptr; const float* m2 = nullptr;
-  if (KIND == DMX_SCHED_DPMPP) {
-    const int order = r.order;
-    if (order < 1 || order > n_hist || order > 3 || r.ring_w < 0 || r.ring_w >= n_hist) return;      // (a record the ring cannot serve: the row is left alone)
-    m0 = hist + ((size_t)r.ring_w * B + b) * per;
-    if (order >= 2) { if (r.ring_m1 < 0 || r.ring_m1 >= n_hist || r.ring_m1 == r.ring_w) return; m1 = hist + ((size_t)r.ring_m1 * B + b) * per; }
-    if (order >= 3) { if (r.ring_m2 < 0 || r.ring_m2 >= n_hist || r.ring_m2 == r.ring_w) return; m2 = hist + ((size_t)r.ring_m2 * B + b) * per; }
-  }
+  float* m0; const float* m1; const float* m2;
+  if (!sched_row_ring<KIND>(r, hist, n_hist, B, b, per, m0, m1, m2)) return;
   float* xr = x + (size_t)b * per;
   sched_span<KIND>(r, xr, eps + (size_t)b * per, noise != nullptr && r.use_noise != 0 ? noise + (size_t)b * per : nullptr, m1, m2, m0, xr, per, vpred);
 }
@@ -321,6 +328,83 @@ int dmx_sched_guided_launch(int kind, const dmx_sched_row_rec& r, float* x, cons
   else
     hipLaunchKernelGGL(dmx_sched_guided_kernel<DMX_SCHED_DPMPP>, grid, block, 0, stream, r, x, eps, noise, hist, scale, rescale, one_minus_rescale, ratio_out, B, per, vpred);
   return dmx_check_launch("dmx_sched_guided_kernel");
+}
+
+// ---- the per-row guided step (dmx_sched_step_rows_guided): the per-row form for an engine whose rows are plain or halves of a guided pair.
+// guide [B]: row b's role.  One block row per engine row; every early return below depends on b alone, so a block leaves whole (before any
+// barrier):
+//   idle (row_index[b] < 0)  returns first, whatever guide[b] says: nothing of the row is read or written;
+//   PLAIN                    sched_span on plan[row_index[b]], the body of dmx_sched_rows_kernel: the same bits;
+//   UNCOND                   returns: its sample slab is written by its partner's block and never read, its noise / history slices are nobody's;
+//   COND, partner p          the body of dmx_sched_guided_kernel on (ec = eps[b], eu = eps[p]) with the row's OWN record, scale and rescale,
+//                            noise[b] where the record asks for it, the history slices hist[.][b]; prev_sample goes to x[b] and x[p];
+//   anything else            (a role outside the enum; a partner outside [0, B), equal to b, on another plan row, not UNCOND, or not pointing
+//                            back at b; a record the ring cannot serve) the row is left alone, the per-row kernel's rule for a bad ring.
+// Whether a row reduces (its rescale != 0) is per row here, and guided_ratio's summation order depends on the block size: so EVERY launch of
+// this entry is grid (1, B) of 1024 threads, the shape dmx_sched_guided_kernel reduces with - k is that entry's bits.  One block per row is
+// enough: a row is 16384 floats at 512 px, 4 float4 trips per thread, and the launch is bounded by its latency, not by one block's bandwidth
+// (the rescale path); the per-element results do not depend on the grid, so PLAIN and rescale-free rows lose no bit by it.
+template <int KIND>
+__global__ __launch_bounds__(1024) void dmx_sched_rows_guided_kernel(float* x, const float* eps, const float* noise, float* hist, int n_hist,
+                                                                     const dmx_sched_row_rec* plan, const int* row_index, const dmx_guide_row* guide,
+                                                                     float* ratio_out, int B, size_t per, int vpred) {
+  __shared__ float2 sh[16];
+  const int b = blockIdx.y;
+  const int idx = row_index[b];
+  if (idx < 0) return;
+  const dmx_guide_row g = guide[b];
+  if (g.role != DMX_GUIDE_PLAIN && g.role != DMX_GUIDE_COND) return;
+  const int p = g.partner;
+  if (g.role == DMX_GUIDE_COND) {
+    if (p < 0 || p >= B || p == b || row_index[p] != idx) return;
+    const dmx_guide_row gp = guide[p];
+    if (gp.role != DMX_GUIDE_UNCOND || gp.partner != b) return;
+  }
+  const dmx_sched_row_rec r = plan[idx];
+  float* m0; const float* m1; const float* m2;
+  if (!sched_row_ring<KIND>(r, hist, n_hist, B, b, per, m0, m1, m2)) return;
+  float* xr = x + (size_t)b * per;
+  const float* ec = eps + (size_t)b * per;
+  const float* nz = noise != nullptr && r.use_noise != 0 ? noise + (size_t)b * per : nullptr;
+  if (g.role == DMX_GUIDE_PLAIN) {
+    sched_span<KIND>(r, xr, ec, nz, m1, m2, m0, xr, per, vpred);
+    return;
+  }
+  sched_guide G{eps + (size_t)p * per, x + (size_t)p * per, g.scale, g.rescale, g.one_minus_rescale, 1.f};
+  if (g.rescale != 0.f) {                                 // (uniform over the block)
+    G.k = guided_ratio(ec, G.eu, per, g.scale, sh);
+    if (ratio_out != nullptr && threadIdx.x == 0) ratio_out[b] = G.k;
+  }
+  sched_span_g<KIND, true>(r, xr, ec, nz, m1, m2, m0, xr, per, vpred, G);
+}
+int dmx_sched_rows_guided_launch(float* x, const float* eps, const float* noise, float* hist, int n_hist, const dmx_sched_row_rec* plan,
+                                 const int* row_index, const dmx_guide_row* guide, float* ratio_out, int B, size_t per, int kind, int vpred,
+                                 hipStream_t stream) {
+  const dim3 grid(1, B), block(1024);
+  if (kind == DMX_SCHED_DDIM)
+    hipLaunchKernelGGL(dmx_sched_rows_guided_kernel<DMX_SCHED_DDIM>, grid, block, 0, stream, x, eps, noise, hist, n_hist, plan, row_index, guide, ratio_out, B, per, vpred);
+  else if (kind == DMX_SCHED_DDPM)
+    hipLaunchKernelGGL(dmx_sched_rows_guided_kernel<DMX_SCHED_DDPM>, grid, block, 0, stream, x, eps, noise, hist, n_hist, plan, row_index, guide, ratio_out, B, per, vpred);
+  else
+    hipLaunchKernelGGL(dmx_sched_rows_guided_kernel<DMX_SCHED_DPMPP>, grid, block, 0, stream, x, eps, noise, hist, n_hist, plan, row_index, guide, ratio_out, B, per, vpred);
+  return dmx_check_launch("dmx_sched_rows_guided_kernel");
+}
+// the guide entries of one request, from kernel arguments (no staging buffer).  guided: rows [b0, b0 + n) COND with partner b + n, rows
+// [b0 + n, b0 + 2n) UNCOND with partner b - n, all with the request's scalars; not guided: rows [b0, b0 + n) PLAIN (all-zero entries).
+__global__ void dmx_rows_guide_kernel(dmx_guide_row* guide, int b0, int n, int guided, float scale, float rescale, float one_minus_rescale) {
+  for (int i = threadIdx.x; i < (guided ? 2 * n : n); i += blockDim.x) {
+    dmx_guide_row g{};                                    // PLAIN is the all-zero entry: a zeroed table is a table of PLAIN rows
+    if (guided) {
+      g.role = i < n ? DMX_GUIDE_COND : DMX_GUIDE_UNCOND;
+      g.partner = i < n ? b0 + i + n : b0 + i - n;
+      g.scale = scale; g.rescale = rescale; g.one_minus_rescale = one_minus_rescale;
+    }
+    guide[b0 + i] = g;
+  }
+}
+int dmx_rows_guide_launch(dmx_guide_row* guide, int b0, int n, int guided, float scale, float rescale, float one_minus_rescale, hipStream_t stream) {
+  hipLaunchKernelGGL(dmx_rows_guide_kernel, dim3(1), dim3(64), 0, stream, guide, b0, n, guided, scale, rescale, one_minus_rescale);
+  return dmx_check_launch("dmx_rows_guide_kernel");
 }
 
 // the two device ints of a row: row_index[b] (a plan row, -1 = idle) and row_left[b] (steps still to run).  One block each; the values of an

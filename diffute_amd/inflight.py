@@ -8,13 +8,22 @@ scheduler launch (`dmx_sched_step_rows`, over the records of `scheduler.plan()` 
 `dmx_rows_advance`.  Which step a row is on lives in two device ints per row (`row_index`, `row_left`) at fixed addresses, so one captured
 graph serves every tick; the host mirrors that arithmetic (`Planner`) and never reads it back.
 
+A request with classifier-free guidance (`submit(..., guidance=Guidance(...))`) is a request of 2n rows to the planner: rows [s0, s0+n) run
+on the glyph context, rows [s0+n, s0+2n) on the unconditional one - the layout `denoise(guidance=)` gives its 2B rows -, both halves with
+the same (plan_base, T), so they advance and retire together.  Which half a row is, its partner and the pair's own scale and rescale live
+in a per-row device table (`dmx_rows_guide` writes a request's entries at admission and returns them to PLAIN when it leaves); while a
+guided request is running the tick's scheduler launch is `dmx_sched_step_rows_guided` (schedulers.launch_step_rows_guided), which does a
+plain row's update, a pair's guided update (into both of its rows) and nothing for idle rows in the same single launch.
+
 `Planner`, `plan_records` and the queue are plain Python (no device calls): tests/test_inflight_host.py drives them without a GPU.
 """
+import ctypes
 from collections import deque
 
 import torch
 
 from . import _cabi
+from .schedulers import Guidance, launch_step_rows_guided
 
 
 # ----------------------------------------------------------------------------------------------------------------- host planner
@@ -125,13 +134,13 @@ def plan_records(scheduler, num_inference_steps, eta=0.0):
 
 # ----------------------------------------------------------------------------------------------------------------- the engine
 class _Request:
-    def __init__(self, lat, mask, mlat, ctx, variance_noise):
-        self.lat, self.mask, self.mlat, self.ctx, self.variance_noise = lat, mask, mlat, ctx, variance_noise
+    def __init__(self, lat, mask, mlat, ctx, variance_noise, guidance=None):
+        self.lat, self.mask, self.mlat, self.ctx, self.variance_noise, self.guidance = lat, mask, mlat, ctx, variance_noise, guidance
 
 
 class DenoiseEngine:
     """eng = DenoiseEngine(unet, scheduler, capacity=4, latent_shape=(4, 64, 64), ctx_len=577)
-    ticket = eng.submit(latents, mask, masked_image_latents, encoder_hidden_states, num_inference_steps)
+    ticket = eng.submit(latents, mask, masked_image_latents, encoder_hidden_states, num_inference_steps, guidance=None)
     finished = eng.tick()            # one UNet forward + one scheduler launch + one advance for all rows -> the tickets that finished
     latents = eng.result(ticket)     # fp32 [n,4,h,w]: a copy taken on the engine's stream at the finishing tick, before the rows are reused
     eng.run_until_idle()
@@ -141,6 +150,12 @@ class DenoiseEngine:
     engine and starts alone computes denoise()'s result bit for bit.  DDIM (with `eta`), DDPM (device randn per tick, or the request's
     `variance_noise` [T,n,4,h,w]) and DPM-Solver++ are served; what denoise() refuses is refused with the same exception.  The
     caller's scheduler object is never mutated: plans come from a private `type(scheduler).from_config(scheduler.config)`.
+
+    guidance: a Guidance, denoise()'s classifier-free guidance, per request: its own scale, rescale and unconditional context.  The
+    request then holds 2n consecutive rows (n on the glyph context, then the same n on the unconditional one), so 2n must fit the capacity;
+    its result is still [n,4,h,w] and variance_noise still [T,n,4,h,w].  Guided and plain requests share the engine, and a tick is one
+    forward, one scheduler launch and one advance either way; a guided request that fills the engine and starts alone computes
+    denoise(guidance=)'s result bit for bit.  None, or a Guidance with scale 1.0 and rescale 0, is the plain request (n rows).
 
     All buffers (x, mask, masked latents, eps, the DPM history ring, noise, row_index, row_left, timesteps) keep their addresses for the
     life of the engine and the loop runs on the engine's own stream, so one captured graph serves every tick.  Plans are cached per
@@ -183,6 +198,7 @@ class DenoiseEngine:
             self.noise = torch.zeros_like(self.x) if self.kind != _cabi.SCHED_DPMPP else None
             self.row_index = torch.full((B,), -1, dtype=torch.int32, device=dev)
             self.row_left = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.guide = torch.zeros(B * ctypes.sizeof(_cabi.GuideRow), dtype=torch.uint8, device=dev)     # [B] dmx_guide_row, all PLAIN
             self.timesteps = torch.zeros(B, dtype=torch.int64, device=dev)
             unet.reserve_context(B, self.ctx_len, slot=self.slot)
         self.table = None                  # [rows of all plans][tproj] fp32
@@ -191,6 +207,7 @@ class DenoiseEngine:
         self._plans = {}                   # num_inference_steps -> (plan_base, T)
         self._pending = {}                 # ticket -> _Request (queued: all tensors; running: variance_noise only)
         self._results = {}
+        self._guided = {}                  # ticket -> n: the guided requests, queued or running, and their samples (they hold 2n rows)
 
     # ---- plans
     def _plan(self, steps):
@@ -218,7 +235,9 @@ class DenoiseEngine:
         return base, T
 
     # ---- requests
-    def submit(self, latents, mask, masked_image_latents, encoder_hidden_states, num_inference_steps, variance_noise=None):
+    def submit(self, latents, mask, masked_image_latents, encoder_hidden_states, num_inference_steps, variance_noise=None, guidance=None):
+        if guidance is not None and not isinstance(guidance, Guidance):
+            raise TypeError(f"guidance must be a diffute_amd.Guidance or None, got {type(guidance).__name__}")
         _cabi.require_cuda(latents, mask, masked_image_latents, encoder_hidden_states, variance_noise)
         if self.kind == _cabi.SCHED_DPMPP and variance_noise is not None:
             raise ValueError("DPMSolverMultistepScheduler is deterministic: no variance_noise, eta = 0")
@@ -235,39 +254,54 @@ class DenoiseEngine:
         if tuple(encoder_hidden_states.shape) != (n, self.ctx_len, D):
             raise ValueError(f"encoder_hidden_states {tuple(encoder_hidden_states.shape)}: expected [{n}, {self.ctx_len}, {D}] (the engine's "
                              "context length is fixed)")
+        if guidance is not None:
+            guidance.check_context(encoder_hidden_states)
+            guidance = guidance if guidance.active else None
+        if guidance is not None and 2 * n > self.capacity:
+            raise ValueError(f"a guided request of {n} samples holds {2 * n} rows and does not fit an engine of capacity {self.capacity}")
         base, T = self._plan(num_inference_steps)
         if variance_noise is not None and (variance_noise.dim() != 5 or variance_noise.shape[0] < T or tuple(variance_noise.shape[1:]) != (n, C, h, w)):
             raise ValueError(f"variance_noise {tuple(variance_noise.shape)}: expected [{T}, {n}, {C}, {h}, {w}]")
-        ticket = self.planner.submit(n, T, base)
+        ticket = self.planner.submit(n if guidance is None else 2 * n, T, base)
         self.stream.wait_stream(torch.cuda.current_stream(self.device))      # the inputs were produced on the caller's stream
-        for t in (latents, mask, masked_image_latents, encoder_hidden_states, variance_noise):
+        for t in (latents, mask, masked_image_latents, encoder_hidden_states, variance_noise, None if guidance is None else guidance.uncond):
             if t is not None:
                 t.record_stream(self.stream)
-        self._pending[ticket] = _Request(latents, mask, masked_image_latents, encoder_hidden_states, variance_noise)
+        self._pending[ticket] = _Request(latents, mask, masked_image_latents, encoder_hidden_states, variance_noise, guidance)
+        if guidance is not None:
+            self._guided[ticket] = n
         self._admit()
         return ticket
 
     def _admit(self):
         lib = self.unet._lib
-        for ticket, s0, n, T, base in self.planner.admit():
+        for ticket, s0, rows, T, base in self.planner.admit():
             rq = self._pending[ticket]
+            g = rq.guidance
+            n = rows if g is None else rows // 2
             with torch.cuda.stream(self.stream):
                 st = _cabi.current_stream()
-                self.x[s0:s0 + n].copy_(rq.lat.to(torch.float32) * self._sched.init_noise_sigma)      # app.ipynb:800
-                self.mask[s0:s0 + n].copy_(rq.mask)
-                self.mlat[s0:s0 + n].copy_(rq.mlat)
-                self.unet.set_context_rows(rq.ctx, s0, slot=self.slot)
-                for b in range(s0, s0 + n):
+                lat = rq.lat.to(torch.float32) * self._sched.init_noise_sigma      # app.ipynb:800
+                for lo in range(s0, s0 + rows, n):                                  # guided: the second half is a duplicate of the first
+                    self.x[lo:lo + n].copy_(lat)
+                    self.mask[lo:lo + n].copy_(rq.mask)
+                    self.mlat[lo:lo + n].copy_(rq.mlat)
+                self.unet.set_context_rows(rq.ctx if g is None else torch.cat([rq.ctx, g.uncond_for(rq.ctx)], 0), s0, slot=self.slot)
+                for b in range(s0, s0 + rows):
                     _cabi.check(lib.dmx_rows_admit(_cabi.ptr(self.row_index), _cabi.ptr(self.row_left), b, base, T, st), "rows_admit", lib)
-            rq.lat = rq.mask = rq.mlat = rq.ctx = None
+                if g is not None:
+                    _cabi.check(lib.dmx_rows_guide(_cabi.ptr(self.guide), s0, n, 1, g.scale, g.rescale, float(1 - g.rescale), st), "rows_guide", lib)
+            rq.lat = rq.mask = rq.mlat = rq.ctx = rq.guidance = None
             if rq.variance_noise is None:
                 del self._pending[ticket]
 
     def _fill_noise(self):
-        """the noise rows of this tick: a request's injected variance_noise[step], device randn for the rest (drawn for the whole buffer)"""
+        """the noise rows of this tick: a request's injected variance_noise[step], device randn for the rest (drawn for the whole buffer).
+        A guided request's noise goes to its conditional rows; the step never reads the noise of the unconditional ones."""
         pl = self.planner
         inject, draw = [], False
         for ticket, (s0, n, _, _) in pl.running.items():
+            n = self._guided.get(ticket, n)
             if not self.plan_host[pl.row_index[s0]].use_noise:
                 continue
             rq = self._pending.get(ticket)
@@ -295,12 +329,19 @@ class DenoiseEngine:
                                     temb=(self.table, self.row_index, self.plan_dev))
             if self.noise is not None:
                 self._fill_noise()
-            _cabi.check(lib.dmx_sched_step_rows(_cabi.ptr(self.x), _cabi.ptr(self.eps), _cabi.ptr(self.noise), _cabi.ptr(self.hist), self.n_hist,
-                                                _cabi.ptr(self.plan_dev), _cabi.ptr(self.row_index), self.capacity, self.per, self.kind,
-                                                self.vpred, st), "sched_step_rows", lib)
+            if any(t in pl.running for t in self._guided):       # a guided request is running (the mirror knows: no readback)
+                launch_step_rows_guided(self.kind, self.x, self.eps, self.noise, self.hist, self.plan_dev, self.row_index, self.guide, self.vpred,
+                                        st, lib=lib)
+            else:
+                _cabi.check(lib.dmx_sched_step_rows(_cabi.ptr(self.x), _cabi.ptr(self.eps), _cabi.ptr(self.noise), _cabi.ptr(self.hist), self.n_hist,
+                                                    _cabi.ptr(self.plan_dev), _cabi.ptr(self.row_index), self.capacity, self.per, self.kind,
+                                                    self.vpred, st), "sched_step_rows", lib)
             for ticket, s0, n in pl.finishing():
-                self._results[ticket] = self.x[s0:s0 + n].clone()
+                samples = self._guided.pop(ticket, None)         # guided: n = 2 * samples rows, the result is the conditional half
+                self._results[ticket] = self.x[s0:s0 + (n if samples is None else samples)].clone()
                 self.x[s0:s0 + n].zero_(); self.mask[s0:s0 + n].zero_(); self.mlat[s0:s0 + n].zero_()
+                if samples is not None:
+                    _cabi.check(lib.dmx_rows_guide(_cabi.ptr(self.guide), s0, n, 0, 1.0, 0.0, 1.0, st), "rows_guide", lib)
                 self._pending.pop(ticket, None)
             _cabi.check(lib.dmx_rows_advance(_cabi.ptr(self.row_index), _cabi.ptr(self.row_left), self.capacity, st), "rows_advance", lib)
         return pl.advance()

@@ -62,6 +62,20 @@ def launch_step_guided(kind, rec, x, eps, noise, hist, vpred, scale, rescale, st
     _cabi.check(rc, "sched_step_guided")
 
 
+def launch_step_rows_guided(kind, x, eps, noise, hist, plan, row_index, guide, vpred, stream, ratio_out=None, lib=None):
+    """The per-row guided scheduler step in one launch (include/diffute_hip.h dmx_sched_step_rows_guided): the in-flight engine's per-row
+    step with a role per row.  x / eps fp32 CUDA [B, ...]; `plan` the device records and `row_index` int32 [B] as for the per-row entry;
+    `guide` the device table of B _cabi.GuideRow (dmx_rows_guide writes it).  A PLAIN row is the per-row entry's update, a COND row the
+    guided update of its pair - prev_sample into its own row and its UNCOND partner's -, idle and UNCOND rows are left alone.  noise
+    [B, ...] or None; hist [n_hist, B, ...], the DPM-Solver++ ring (None otherwise); ratio_out fp32 [B] or None."""
+    l = _cabi.lib() if lib is None else lib
+    B = x.shape[0]
+    rc = l.dmx_sched_step_rows_guided(_cabi.ptr(x), _cabi.ptr(eps), _cabi.ptr(noise), _cabi.ptr(hist), 0 if hist is None else hist.shape[0],
+                                      _cabi.ptr(plan), _cabi.ptr(row_index), _cabi.ptr(guide), _cabi.ptr(ratio_out), B, x.numel() // B, kind,
+                                      vpred, stream)
+    _cabi.check(rc, "sched_step_rows_guided", l)
+
+
 class Guidance:
     """Classifier-free guidance for denoise() and the edit functions: the model runs on the glyph context and on an unconditional one and
     the scheduler steps on eu + scale * (ec - eu).  rescale in [0, 1] is the guidance rescale of Lin et al. 2023 (diffusers'

@@ -512,6 +512,38 @@ int dmx_sched_step_rows(float* sample, const float* model_output, const float* n
 int dmx_sched_step_guided(float* sample, const float* model_output, const float* noise, float* hist, int n_hist, dmx_sched_row_rec rec,
                           int kind, int v_prediction, float guidance_scale, float rescale, float one_minus_rescale, float* ratio_out,
                           int B, size_t per_sample, dmx_stream_t stream);
+/* ---- the per-row guided step: in-flight batching WITH classifier-free guidance.  A guided request of n samples holds 2n consecutive
+ * engine rows, [s0, s0+n) on the glyph context and [s0+n, s0+2n) on the unconditional one - the layout dmx_sched_step_guided gives its 2B
+ * rows; both halves are admitted with the same (plan_base, n_steps), so they advance and retire together.  The GUIDE TABLE, one entry per
+ * engine row at a fixed address, says which half a row is: role (PLAIN: a row of a request without guidance; COND / UNCOND: the two halves
+ * of a pair), partner (the other row of the pair; unused for PLAIN) and the pair's own scale, rescale and one_minus_rescale (read from
+ * the COND entry). */
+typedef struct dmx_guide_row { int role, partner; float scale, rescale, one_minus_rescale; } dmx_guide_row;
+enum { DMX_GUIDE_PLAIN = 0, DMX_GUIDE_COND = 1, DMX_GUIDE_UNCOND = 2 };
+/* One launch for all B rows, dmx_sched_step_rows with the guide table.  Per row b:
+ *   row_index[b] < 0           idle: nothing of the row is read or written, whatever guide[b] says;
+ *   PLAIN                      dmx_sched_step_rows' update of the row, bit for bit;
+ *   UNCOND                     nothing is done for the row itself: its sample slab is written by its partner's update and never read, its
+ *                              noise and history slices are neither read nor written;
+ *   COND with partner p        dmx_sched_step_guided run on the pair alone (B = 1), bit for bit: ec = model_output[b], eu = model_output[p],
+ *                              the record plan[row_index[b]], guide[b]'s scale / rescale / one_minus_rescale, noise[b] where the record
+ *                              asks for it (use_noise), the history slices hist[.][b]; prev_sample is written to sample[b] AND sample[p],
+ *                              and with rescale != 0 the ratio k to ratio_out[b] (ratio_out [B] or NULL).
+ * A row that cannot be served is left alone (sample, noise and history slices unchanged), the rest of the launch is not affected: a role
+ * outside the enum; a COND row whose partner is outside [0, B), is b itself, has another row_index, is not UNCOND or does not name b as ITS
+ * partner; for DPM-Solver++ a record its ring cannot serve (as for dmx_sched_step_rows).  The launch is always B blocks of 1024 threads, the
+ * shape dmx_sched_step_guided reduces the ratio with: the sums of k are taken in that entry's order.
+ * DMX_ERR_ARG, nothing written: B < 1, per_sample < 2 (a rescaled row divides by per_sample - 1), NULL sample / model_output / plan /
+ * row_index / guide, kind outside the enum, DPM-Solver++ with noise, with hist == NULL or n_hist outside 1..3. */
+int dmx_sched_step_rows_guided(float* sample, const float* model_output, const float* noise, float* hist, int n_hist,
+                               const dmx_sched_row_rec* plan, const int* row_index, const dmx_guide_row* guide, float* ratio_out, int B,
+                               size_t per_sample, int kind, int v_prediction, dmx_stream_t stream);
+/* the guide entries of one request, one tiny launch (the values travel as kernel arguments: no staging buffer).  guided = 1: rows
+ * [b0, b0+n) become COND with partner b + n and rows [b0+n, b0+2n) UNCOND with partner b - n, all carrying the three scalars;
+ * guided = 0: rows [b0, b0+n) become PLAIN, the all-zero entry (a zeroed table is a table of PLAIN rows; the scalars are checked but not
+ * stored).  The caller keeps [b0, b0+2n) / [b0, b0+n) inside its table.
+ * DMX_ERR_ARG, nothing written: NULL guide, b0 < 0, n < 1, guided outside {0, 1}, a non-finite scalar, rescale outside [0, 1]. */
+int dmx_rows_guide(dmx_guide_row* guide, int b0, int n, int guided, float scale, float rescale, float one_minus_rescale, dmx_stream_t stream);
 /* row b starts at plan row plan_base with n_steps steps to run (the values travel as kernel arguments: no staging buffer) */
 int dmx_rows_admit(int* row_index, int* row_left, int b, int plan_base, int n_steps, dmx_stream_t stream);
 /* after the scheduler launch of a tick: every active row index++, left--, index = -1 at left == 0 */
