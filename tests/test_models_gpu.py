@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import assert_close, rel_l2
+from util import assert_close, rel_l2, oracle_unet_train_grads as _oracle_train_grads
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -397,18 +397,6 @@ def test_full_size_properties(cuda):
 
 
 # ------------------------------------------------------------------------------------------------ training (P5 / P6)
-def _oracle_train_grads(model, cfg_oracle, x, t, ctx, target, emulate_bf16=False):
-    """loss and parameter gradients of the oracle (torch autograd on the CPU restatement; with emulate_bf16 the forward
-    rounds where the HIP path materialises bf16, the backward stays fp32 - casts are straight-through)"""
-    from oracle import unet as OU
-    P = {k: v.detach().cpu().float().clone().requires_grad_(True) for k, v in model.state_dict().items()}
-    with torch.enable_grad():
-        pred = OU.unet_forward.__wrapped__(P, cfg_oracle, x.cpu(), t.cpu(), ctx.cpu(), emulate_bf16=emulate_bf16)
-        loss = torch.mean((pred.float() - target.cpu().float()) ** 2)
-        loss.backward()
-    return float(loss.detach()), pred.detach(), {k: p.grad for k, p in P.items()}
-
-
 def test_tiny_unet_train_step(cuda):
     """P5/P6: one training step of the tiny UNet through the product classes (HIP forward that keeps activations, HIP
     MSE loss, hand-written HIP backward) vs torch autograd on the oracle.  Tolerances (bf16 activations AND bf16

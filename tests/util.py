@@ -27,6 +27,37 @@ def seeded(shape, seed, scale=1.0):
     return torch.randn(shape, generator=g) * scale
 
 
+# ---------------------------------------------------------------------------- training gradients against the oracle
+def oracle_unet_train_grads(model, cfg_oracle, x, t, ctx, target, emulate_bf16=False):
+    """loss and parameter gradients of the oracle (torch autograd on the CPU restatement; with emulate_bf16 the forward
+    rounds where the HIP path materialises bf16, the backward stays fp32 - casts are straight-through).  `model` is a model or its
+    state_dict."""
+    from oracle import unet as OU
+    sd = model.state_dict() if hasattr(model, "state_dict") else model
+    P = {k: v.detach().cpu().float().clone().requires_grad_(True) for k, v in sd.items()}
+    with torch.enable_grad():
+        pred = OU.unet_forward.__wrapped__(P, cfg_oracle, x.cpu(), t.cpu(), ctx.cpu(), emulate_bf16=emulate_bf16)
+        loss = torch.mean((pred.float() - target.cpu().float()) ** 2)
+        loss.backward()
+    return float(loss.detach()), pred.detach(), {k: p.grad for k, p in P.items()}
+
+
+def grad_errors(grads, ref, not_ranked=lambda k: False):
+    """{name: gradient} against the oracle's -> (rel-L2 of the whole gradient vector, [(rel-L2, name)] worst first); parameters for which
+    `not_ranked(name)` holds count in the whole vector but are left out of the ranking"""
+    errs = []
+    num = den = 0.0
+    for k, gh in grads.items():
+        assert gh is not None, f"no gradient for {k}"
+        gh = gh.detach().float().cpu(); gr = ref[k]
+        assert torch.isfinite(gh).all(), f"{k}: non-finite gradient"
+        num += float((gh - gr).pow(2).sum()); den += float(gr.pow(2).sum())
+        if not not_ranked(k):
+            errs.append((rel_l2(gh, gr), k))
+    errs.sort(reverse=True)
+    return (num / den) ** 0.5, errs
+
+
 # ---------------------------------------------------------------------------- local (per-slice) parity
 def _slice_norms(hip, ref, dim):
     h = hip.detach().double().cpu(); r = ref.detach().double().cpu()
