@@ -8,7 +8,7 @@ extern "C" int dmx_version(void) { return 100; }
 extern "C" const char* dmx_last_error(void) { return dmx_get_error(); }
 extern "C" const char* dmx_element_type(void) { return DMX_ELEM_NAME; }
 
-static GemmArgs to_args(const dmx_gemm_desc* d) {
+GemmArgs dmx_gemm_args(const dmx_gemm_desc* d) {
   GemmArgs a{};
   a.x0 = (const bf16*)d->x0; a.x1 = d->x1 ? (const bf16*)d->x1 : (const bf16*)d->x0;
   a.ldx0 = d->ldx0; a.ldx1 = d->x1 ? d->ldx1 : d->ldx0; a.cx0 = d->cx0; a.direct = d->direct;
@@ -25,17 +25,17 @@ static GemmArgs to_args(const dmx_gemm_desc* d) {
   a.colstats = d->colstats; a.cs_rows = d->cs_rows;
   return a;
 }
-extern "C" int dmx_conv_gemm_colstats_ok(const dmx_gemm_desc* d) { return d && dmx_gemm_colstats_ok(to_args(d)) ? 1 : 0; }
+extern "C" int dmx_conv_gemm_colstats_ok(const dmx_gemm_desc* d) { return d && dmx_gemm_plan(dmx_gemm_args(d)).colstats_ok ? 1 : 0; }
 extern "C" int dmx_conv_gemm_rowstats_tiles(const dmx_gemm_desc* d) {
   if (!d) return 0;
-  GemmArgs a = to_args(d);
+  GemmArgs a = dmx_gemm_args(d);
   if (!a.rowstats_out) a.rowstats_out = (float*)8;      // the plan depends on whether statistics are emitted
-  return dmx_gemm_tiles_n(a);
+  return dmx_gemm_plan(a).tiles_n;
 }
-extern "C" size_t dmx_conv_gemm_workspace_bytes(const dmx_gemm_desc* d) { return d ? dmx_gemm_workspace_bytes(to_args(d)) : 0; }
+extern "C" size_t dmx_conv_gemm_workspace_bytes(const dmx_gemm_desc* d) { return d ? dmx_gemm_plan(dmx_gemm_args(d)).workspace_bytes : 0; }
 extern "C" int dmx_conv_gemm(const dmx_gemm_desc* d, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(d && d->x0 && d->w && d->out, "conv_gemm: null argument");
-  return dmx_gemm_launch(to_args(d), workspace, workspace_bytes, (hipStream_t)stream);
+  return dmx_gemm_launch(dmx_gemm_args(d), workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // nearest x2 upsample + conv3x3 as four 2x2 phase convolutions (GemmArgs.ups2)
@@ -51,7 +51,7 @@ static GemmArgs ups2x_args(const void* x, int ldx, int B, int IH, int IW, int Ci
   return a;
 }
 extern "C" size_t dmx_conv_ups2x_workspace_bytes(int B, int IH, int IW, int Cin, int N, int force_tn, int force_splitk) {
-  return dmx_gemm_workspace_bytes(ups2x_args(nullptr, Cin, B, IH, IW, Cin, nullptr, N, nullptr, nullptr, N, force_tn, force_splitk));
+  return dmx_gemm_plan(ups2x_args(nullptr, Cin, B, IH, IW, Cin, nullptr, N, nullptr, nullptr, N, force_tn, force_splitk)).workspace_bytes;
 }
 extern "C" int dmx_conv_ups2x(const void* x, int ldx, int B, int IH, int IW, int Cin, const void* phase_weights, int N, const float* bias,
                               void* out, int ldo, int force_tn, int force_splitk, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {

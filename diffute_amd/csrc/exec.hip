@@ -285,7 +285,7 @@ long long* Exec::stat_slice(int B, int C) {
 void Exec::want_stats(GemmArgs& a, Tn& y, int rows_per_sample, int B) {
   if (rc || f32 || !g_gn_producer_stats) return;
   a.cs_rows = rows_per_sample;
-  if (!dmx_gemm_colstats_ok(a)) { a.cs_rows = 0; return; }
+  if (!dmx_gemm_plan(a).colstats_ok) { a.cs_rows = 0; return; }
   a.colstats = stat_slice(B, a.N);
   if (!a.colstats) { a.cs_rows = 0; return; }                 // pool exhausted: the consumer computes its own statistics
   y.cst = a.colstats;
@@ -326,7 +326,8 @@ void Exec::run_gemm(GemmArgs& a, Tn* defer_to) {
   if (rc) return;
   note(a.w, (long)a.N * a.ldw * 2 * (a.ups2 ? 4 : 1));
   peek(a.pf, a.pf_bytes, 2);
-  if (const int pg = dmx_gemm_persist_blocks(a)) {
+  const GemmPlan plan = dmx_gemm_plan(a);              // once: the flags, the workspace and the deferred reduce all follow from it
+  if (const int pg = plan.persist_blocks) {
     constexpr size_t POOL = 64 * 1024;                 // ints: 256 launches of 256 blocks
     if (!flag_pool) {
       flag_pool = (int*)raw(POOL * sizeof(int)); flag_cap = POOL; flag_used = 0;
@@ -335,15 +336,13 @@ void Exec::run_gemm(GemmArgs& a, Tn* defer_to) {
     const size_t n = align_up((size_t)pg, 64);
     if (flag_used + n <= flag_cap) { a.flags = flag_pool + flag_used; flag_used += n; }   // else: the launcher zeroes a slice of its own workspace
   }
-  const size_t wsb = dmx_gemm_workspace_bytes(a);
+  const size_t wsb = plan.workspace_bytes;
   void* w = wsb ? raw(wsb) : nullptr;
-  int c = 0, sk = 1, ktps = 0;
-  if (defer_to) dmx_gemm_plan(a, &c, &sk, &ktps);
-  const bool defer = defer_to && sk > 1 && !dmx_gemm_persist_blocks(a) && !a.out_f32 && wsb > 0;      // (no pointer values in this decision: the dry walk has none)
+  const bool defer = defer_to && plan.splitk > 1 && !plan.persist_blocks && !a.out_f32 && wsb > 0;      // (no pointer values in this decision: the dry walk has none)
   if (defer) a.defer_reduce = 1;
   if (!dry && !rc) rc = dmx_gemm_launch(a, w, wsb, stream);
   if (defer) {                                         // the partial planes stay in the workspace until the GroupNorm (or a flush) has read them
-    PendRed P; P.a = a; P.a.partial = (float*)w; P.a.splitk = sk; P.a.kt_per_split = ktps; P.wsp = w;
+    PendRed P; P.a = a; P.a.partial = (float*)w; P.a.splitk = plan.splitk; P.a.kt_per_split = plan.kt_per_split; P.wsp = w;
     defer_to->pend = (int)pend_.size();
     pend_.push_back(P);
   } else if (w) ws.release(w);
@@ -551,7 +550,7 @@ Tn Exec::linear(const Tn& x, const bf16* w, int N, const float* bias, const Tn* 
   if (ln) { a.ln_stats = ln->stats; a.ln_tiles = ln->tiles; a.ln_c1 = ln->c1; a.ln_c2 = ln->c2; a.ln_C = x.C; a.ln_eps = ln->eps; }
   if (rowstats) {
     a.rowstats_out = (float*)8;                      // non-null marker so the plan is the one the launch will use
-    rowstats->tiles = dmx_gemm_tiles_n(a);
+    rowstats->tiles = dmx_gemm_plan(a).tiles_n;
     rowstats->buf = (float*)raw((size_t)rowstats->tiles * a.M * 2 * sizeof(float));
     a.rowstats_out = rowstats->buf;
   }

@@ -20,11 +20,12 @@
 // 16-byte k-chunk XOR-swizzled on the SOURCE side (glds writes lane-linear), which makes the ds_read_b128 fragment
 // reads bank-conflict free.  An NSTAGE-deep LDS ring keeps NSTAGE-1 K-tiles of DMA in flight behind a counted
 // `s_waitcnt vmcnt(N)` + raw s_barrier; the queue is never drained inside the loop.  The instances and what each is for
-// are listed at kCfg below; DESIGN.md section 4 has the measurements behind them.
+// are listed in gemm_tile.h, which also derives the tile shape and the LDS layout (GemmTile) for the kernel, its launcher and the
+// planner (gemm_plan.hip); DESIGN.md section 4 has the measurements behind them.
 #include "common.h"
 #include "kernels.h"
+#include "gemm_tile.h"
 #include <stdio.h>
-#include <vector>
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -35,21 +36,6 @@ struct RowSrc {          // per-thread state for one staged activation row
   int valid;             // m < M
 };
 
-// Tile configurations (plan id -> instance), see kCfg:
-//   0 <2,2,32,4>      128x128x32, 4 waves, 64 KB ring -> 2 blocks/CU   (mid-size GEMMs, split-K convolutions)
-//   1 <2,1,32,4>      128x 64x32, 4 waves, 48 KB                        (N <= 64)
-//   2 <4,2,64,3>      256x128x64, 8 waves, 144 KB -> 1 block/CU         (large GEMMs: 128-byte DMA rows, 85 FLOP/B)
-//   6 <2,2,64,3,4,4>  warp-specialised 256x128x64: waves 0-3 MFMA (128x64 sub-tiles, software-pipelined fragment reads),
-//                     waves 4-7 issue the LDS-DMA refills                (large K)
-//   7..9 <4,1,64,3,1> / <4,2,32,4,1> / <4,2,64,3,1>  128x64 / 128x128 tiles with EIGHT waves (32x32 / 32x64 sub-tiles): small
-//                     grids are bound by the per-CU LDS-DMA fill rate, which doubles with 8 issuing waves
-//   10 <4,5,64,2,1,0,1> 128x160x64: FOUR waves in one column (NWN = 1), 32x160 sub-tiles, 2-buffer ring (72 KB -> 2 blocks/CU).
-//                     160 divides every channel count of the UNet (320 k): no wasted tile columns where N = 320 / 640 / 960;
-//                     its own coalesced epilogue (20 octets per row do not divide the block); bias / row bias / residual only
-//   11 <4,5,64,2,1,0,2> 128x320x64: eight waves (4 x 2) of 32x160 sub-tiles, 2-buffer ring (112 KB, 1 block/CU); five whole packed
-//                     GEGLU groups per tile, same epilogue as 10 plus folded LayerNorm + GEGLU: the FF1 GEMM of the 16x16 level
-//                     (1024 x 10240 x 1280) becomes 256 tiles = one full round instead of 640 tiles on 512 slots
-//   3, 4, 5           retired (two-stage 128x64, deep-ring 128x128x64, 256x256x32: measured, not adopted - EXPERIMENTS.md)
 // measurement aid: 100 MHz wall ticks, or (dbg bit 2) shader-clock cycles - their ratio is the effective clock
 __device__ __forceinline__ long long dmx_now(int dbg) {
   return (dbg & 4) ? (long long)__builtin_amdgcn_s_memtime() : (long long)__builtin_amdgcn_s_memrealtime();
@@ -57,16 +43,17 @@ __device__ __forceinline__ long long dmx_now(int dbg) {
 // CS: this instance also emits the GroupNorm column statistics of its output (GemmArgs.colstats) - a separate instantiation so
 // that the 16 registers the partials cost do not touch the occupancy of the plain instances
 template <int WM, int TN, int BKT, int NSTAGE, int TM = 2, int NP = 0, int NWN = 2, bool PS = false, int MF = 32, bool CS = false>
-__global__ __launch_bounds__(64 * (NWN * WM + NP), (TN == 5 && NWN == 2) ? 1 : ((WM == 4 && TM == 1 && TN <= 2 && NP == 0 && NWN == 2) ? 4 : 2)) void dmx_gemm_kernel(const GemmArgs p) {
+__global__ __launch_bounds__((GemmTile<WM, TN, BKT, NSTAGE, TM, NP, NWN, PS, MF>::NT), (GemmTile<WM, TN, BKT, NSTAGE, TM, NP, NWN, PS, MF>::MIN_WAVES)) void dmx_gemm_kernel(const GemmArgs p) {
+  typedef GemmTile<WM, TN, BKT, NSTAGE, TM, NP, NWN, PS, MF> L;       // tile shape, block size and LDS layout: one definition with the launcher
   static_assert(NWN == 1 || NWN == 2, "one or two waves along n");
   // MF = MFMA fragment size: 32 -> v_mfma_f32_32x32x16 (wave tile 32 TM x 32 TN), 16 -> v_mfma_f32_16x16x32 (16 TM x 16 TN: the
   // 64 x 80 wave tiles of the 256x160 persistent instance - 25 % fewer LDS fragment bytes per FLOP than 32 x 160 wave tiles)
-  static_assert(MF == 32 || (MF == 16 && TN == 5 && PS && NP == 0 && BKT == 64), "16x16 fragments: 160-column persistent instance only");
+  static_assert(MF == 32 || (MF == 16 && L::COL160 && PS && NP == 0 && BKT == 64), "16x16 fragments: 160-column persistent instance only");
   constexpr int NGRP = MF == 32 ? 4 : 1;               // float4 groups per accumulator fragment and lane
   typedef float accv __attribute__((ext_vector_type(4 * NGRP)));
-  constexpr int BM = MF * TM * WM, BN = MF * TN * NWN;
-  constexpr int NC = NWN * WM;                         // consumer (MFMA) waves: WM along m x NWN along n
-  constexpr int NT = 64 * (NC + NP);                   // block threads
+  constexpr int BM = L::BM, BN = L::BN;
+  constexpr int NC = L::NC;                            // consumer (MFMA) waves: WM along m x NWN along n
+  constexpr int NT = L::NT;                            // block threads
   constexpr int NL = NP ? 64 * NP : NT;                // threads that stage tiles (all of them unless warp-specialised)
   constexpr int CPR = BKT / 8;                         // 16-byte chunks per LDS row
   constexpr int ROWB = BKT * 2;                        // LDS row bytes
@@ -77,7 +64,8 @@ __global__ __launch_bounds__(64 * (NWN * WM + NP), (TN == 5 && NWN == 2) ? 1 : (
                                                        // waves' loads (same bytes to the same LDS address) so every thread issues NLOADS
   static_assert(BM * CPR % NL == 0 && (WREM & (WREM - 1)) == 0 && WREM % 64 == 0, "staging rounds");
   constexpr int NLOADS = XL + WL;
-  constexpr int X_BYTES = BM * ROWB, W_BYTES = BN * ROWB, STAGE = X_BYTES + W_BYTES;
+  constexpr int X_BYTES = BM * ROWB, W_BYTES = BN * ROWB, STAGE = L::STAGE;
+  static_assert(STAGE == X_BYTES + W_BYTES, "ring stage");
   constexpr int KSTEPS = BKT / (MF == 32 ? 16 : 32);   // MFMA k-steps per K-tile
   constexpr int CPS = 64 / MF;                         // 16-byte k-chunks per k-step and fragment row (2 lane halves / 4 lane quarters)
   static_assert(XL >= 1 && WL >= 1, "tile too small for the block");
@@ -402,10 +390,7 @@ __global__ __launch_bounds__(64 * (NWN * WM + NP), (TN == 5 && NWN == 2) ? 1 : (
 
   // ---- folded LayerNorm (consumer side): the GEMM runs on the RAW rows x with W' = W*diag(gamma); the epilogue
   // applies y = rstd*(acc - mean*c1[n]) + c2[n].  Row mean / rstd come from the producer's per-n-tile partial sums.
-  constexpr int EPI_BYTES = BM * (BN + 4) * 4;                                  // whole-tile fp32 staging (epilogue)
-  constexpr int EPI_PASS = TN == 5 ? EPI_BYTES / 2 : (EPI_BYTES <= 152 * 1024) ? EPI_BYTES : EPI_BYTES / WM;  // or one slab of rows per pass
-  constexpr int LN_OFF = (NSTAGE * STAGE > EPI_PASS) ? NSTAGE * STAGE : EPI_PASS;
-  float* lnst = (float*)(smem + LN_OFF);               // [BM][2] = (mean, rstd); only allocated when ln_stats != null
+  float* lnst = (float*)(smem + L::LN_OFF);            // [BM][2] = (mean, rstd); only allocated when ln_stats != null (or with the column vectors)
   if (p.ln_stats) {
     for (int r = t; r < BM; r += NT) {
       int m = m0 + r; if (m >= p.M) m = p.M - 1;
@@ -421,7 +406,7 @@ __global__ __launch_bounds__(64 * (NWN * WM + NP), (TN == 5 && NWN == 2) ? 1 : (
   }
 
   // ---- NSTAGE-deep LDS ring, NSTAGE-1 K-tiles of DMA in flight, counted vmcnt (never drained to 0 in the loop)
-  if constexpr (NP > 0) {
+  if constexpr (L::WARP_SPEC) {
     // warp-specialised: loader waves and MFMA waves run separate loops that meet at one s_barrier per K-tile
     // (separate loops keep the loaders' pointer state and the consumers' accumulators out of each other's live ranges)
     if (is_loader) {
@@ -504,7 +489,7 @@ __global__ __launch_bounds__(64 * (NWN * WM + NP), (TN == 5 && NWN == 2) ? 1 : (
 #undef DMX_CSUB
 #undef DMX_SB
     }
-  } else if constexpr (PS && BM >= 256) {
+  } else if constexpr (L::PINGPONG) {
     // ---- two-group ping-pong (persistent big-tile instances).  Waves w and w + NC/2 share a SIMD; group A = waves [0, NC/2), group B the
     // rest.  Per K-tile every wave runs a DMA phase (its share of tile j+1 -> stage (j+1) % NSTAGE), a barrier, an MFMA phase
     // (tile j), a barrier.  Both groups run the SAME instruction stream, but B takes one extra barrier up front (and A one at the
@@ -685,20 +670,20 @@ __global__ __launch_bounds__(64 * (NWN * WM + NP), (TN == 5 && NWN == 2) ? 1 : (
           }
         }
       }
-  } else if (TN == 5 && !p.out_f32 && (p.N & 7) == 0 && (p.ldo & 7) == 0 && (p.res == nullptr || (p.ldres & 7) == 0)) {
+  } else if (L::COL160 && !p.out_f32 && (p.N & 7) == 0 && (p.ldo & 7) == 0 && (p.res == nullptr || (p.ldres & 7) == 0)) {
     // ---- coalesced epilogue of the 160 / 320-column tiles (BN / 8 = 20 or 40 octets per row do not divide the block, so
     // the (row, octet) of an item varies per thread and the column vectors are fetched per item): two passes of BM/2 rows
     // staged in LDS as fp32; bias or the folded-LayerNorm affine, time-embedding row bias, residual, GEGLU (320-column
     // tile: 5 whole packed 64-column groups), bf16 out.  Row statistics / GELU stay on the power-of-two tiles (plan).
-    if constexpr (TN == 5) {
-      constexpr int LDT = BN + 4, EP = 2, RPP = BM / EP;
+    if constexpr (L::COL160) {
+      constexpr int LDT = BN + 4, EP = L::EPI_PASSES, RPP = BM / EP;
       static_assert(WM % EP == 0, "160-column epilogue: whole waves per pass");
       float* tile = (float*)smem;
       const bool geglu = NWN == 2 && p.geglu != 0;
       const float* bsrc = p.ln_stats ? p.ln_c2 : p.bias;
       // the tile's column vectors (bias | c2, c1, time-embedding row bias) go to LDS once: fetched per item from global memory
       // (three dependent L2 round trips inside the item loop) they made this epilogue 4-5 us per tile
-      float* colv = lnst + 2 * BM;                       // [3][BN]
+      float* colv = (float*)(smem + L::COLV_OFF);        // [3][BN]
       const bool rb_one = p.rowbias && (m0 / p.rows_per_group == (min(m0 + BM, Mlim) - 1) / p.rows_per_group);   // whole tile inside one row-bias group
       for (int c = t; c < BN; c += NT) {
         const int n = min(n0 + c, p.N - 1);
@@ -857,16 +842,16 @@ __global__ __launch_bounds__(64 * (NWN * WM + NP), (TN == 5 && NWN == 2) ? 1 : (
         }
       }
     }
-  } else if (TN != 5 && !p.out_f32 && (p.N & 7) == 0 && (p.ldo & 7) == 0 && (p.res == nullptr || (p.ldres & 7) == 0)) {
+  } else if (!L::COL160 && !p.out_f32 && (p.N & 7) == 0 && (p.ldo & 7) == 0 && (p.res == nullptr || (p.ldres & 7) == 0)) {
     // ---- coalesced epilogue: accumulators (+ time-embedding row bias) -> LDS as fp32 (the ring is free now) ->
     // each thread finishes 8 consecutive channels of one pixel: + bias + residual (or GEGLU a*gelu(b)), one
     // rounding to bf16, one 16-byte store; a wave writes whole 128/256-byte row segments.  Raw s_barrier +
     // lgkmcnt only: __syncthreads() would also wait for the global stores (vmcnt counts stores on gfx950), and
     // every global load is issued before the first store for the same reason.
-    if constexpr (TN != 5) {
+    if constexpr (!L::COL160) {
     constexpr int LDT = BN + 4;                        // padded row stride (floats): conflict-free b128 writes
     constexpr int OC = BN / 8;                         // output octets per tile row (NT % OC == 0: o fixed per thread)
-    constexpr int EP = (EPI_BYTES <= 152 * 1024) ? 1 : WM;   // passes: the 256x256 tile stages 64 rows (one wm) at a time
+    constexpr int EP = L::EPI_PASSES;                  // passes: the 256x256 tile stages 64 rows (one wm) at a time
     constexpr int RPP = BM / EP;                       // tile rows per pass
     constexpr int OCT = RPP * OC / NT;                 // (row, octet) items per thread per pass
     float* tile = (float*)smem;
@@ -1047,7 +1032,7 @@ __global__ __launch_bounds__(64 * (NWN * WM + NP), (TN == 5 && NWN == 2) ? 1 : (
       }
     }
     if (CS && p.colstats && !geglu) publish_colstats(cs_s, cs_q, o, t / OC, NT / OC, true, tile);
-    }   // if constexpr (TN != 5)
+    }   // if constexpr (!L::COL160)
   } else {
     // ---- generic epilogue (fp32 output, channel counts that are not multiples of 8): per-lane 4-channel groups
     const bool vec_ok = ((p.N & 3) == 0) && ((p.ldo & 3) == 0);
@@ -1139,285 +1124,56 @@ int dmx_zero_page(const bf16** out) {
   return DMX_OK;
 }
 
-// Tile / split-K plan.  Config ids: 0 = 128x128x32 (2 blocks/CU), 1 = 128x64x32, 2 = 256x128x64 (1 block/CU).
-// The UNet's GEMMs are small next to 256 CUs (M = 256..16384 rows), so the plan trades tile efficiency against
-// filling the CUs, with split-K (fp32 partials + a reduce pass) when tiles alone leave CUs idle.  Costs are in
-// units of one 128x128x32 K-tile step of one block; constants fitted on scripts/tune_gemm.py measurements.
-struct TileCfg { int bm, bn, bk, slots; double per_ktile, fixed; };
-static const TileCfg kCfg[16] = {            // measured (scripts/attic/gemm_timeline.py): 0.45 / 0.35 / 1.05 us per K-tile,
-    {128, 128, 32, 512, 1.00, 9.0},         // ~4 us of prologue + epilogue per block
-    {128, 64, 32, 512, 0.78, 6.0},
-    {256, 128, 64, 256, 2.35, 10.0},        // 4x the FLOPs of config 0 per K-tile at ~1.7x its rate
-    {128, 64, 64, 768, 0.55, 5.0},          // 128x64x64, eight waves, TWO-stage ring (49 KB): three blocks per CU so one block's prologue / epilogue
-                                            // overlaps the others' K loops (the K = C linears are 70 % prologue + epilogue); force_tn = 4 / tuned table
-    {128, 128, 64, 256, 1.00, 7.0},         // deep ring (4 x 32 KB, 1 block/CU)
-    {256, 256, 32, 256, 2.40, 16.0},        // 128 FLOP/B (experimental, force_tn = 6 only)
-    {256, 128, 64, 256, 1.90, 11.0},        // warp-specialised 256x128x64: 4 MFMA waves + 4 DMA waves (~0.85 us per K-tile)
-    {128, 64, 64, 512, 0.55, 5.0},          // 128x64x64 with EIGHT waves (32x32 each): small grids are bound by the per-CU LDS-DMA fill
-                                            // rate, which doubles with 8 issuing waves (~95 vs ~50 GB/s); force_tn = 8 / tuned table
-    {128, 128, 32, 512, 1.00, 8.0},         // 128x128x32 with eight waves (32x64 each), 4-stage ring; force_tn = 9 / tuned table
-    {128, 128, 64, 256, 1.00, 8.0},         // 128x128x64 with eight waves, 3-stage ring (96 KB); force_tn = 10 / tuned table
-    {128, 160, 64, 512, 1.10, 8.0},         // 128x160x64, four waves with 32x160 sub-tiles (one wave column): 160 divides every channel
-                                            // count of this UNet (320 k), so no column of a tile is wasted; force_tn = 11 / tuned table
-    {128, 320, 64, 256, 2.00, 10.0},        // 128x320x64, eight waves (4 x 2), 32x160 sub-tiles, 2-buffer ring (112 KB, 1 block/CU): five whole
-                                            // GEGLU groups per tile - the feed-forward GEMMs (N = 8C) tile without a partial round; force_tn = 12
-    // 12..14: PERSISTENT stream-K instances (one block per CU walks (tile, K-range) items, fix-up in the kernel, no reduce pass;
-    //         two-group ping-pong K loop over a 3+ stage ring):
-    {256, 160, 64, 256, 1.6, 8.0},          // 12: 256x160x64, eight waves in one column (32x160 sub-tiles), 3-stage ring (156 KB); force_tn = 13
-    {256, 256, 32, 256, 1.2, 9.0},          // 13: 256x256x32, eight waves (4 x 2) of 64x128 sub-tiles, 4-stage ring (128 KB); force_tn = 14
-    {256, 128, 64, 256, 1.3, 7.0},          // 14: 256x128x64, eight waves in one column (32x128 sub-tiles), 3-stage ring (144 KB); force_tn = 15
-    {256, 160, 64, 256, 1.4, 8.0},          // 15: 256x160x64 with 16x16x32 MFMAs: eight waves (4 x 2) of 64x80 sub-tiles, 3-stage ring; force_tn = 16
-};
-
-static bool cfg_persistent(int c) { return c >= 12; }
-
-// number of blocks of a persistent launch: one per CU, fewer when the iteration space is small (>= 4 K-tiles per block),
-// a multiple of 8 so the XCD-contiguous remap applies
-static int persist_grid(const GemmArgs& a, int c) {
-  const int n_cu = n_cus();                            // of the current device (conv_halo.hip)
-  const TileCfg& T = kCfg[c];
-  const long tiles = (long)(a.ups2 ? 4 * cdiv(a.M4, T.bm) : cdiv(a.M, T.bm)) * cdiv(a.N, T.bn);
-  const long total = tiles * (a.K / T.bk);
-  long g = total / 4; if (g > n_cu) g = n_cu; if (g < 1) g = 1;
-  if (g >= 8) g &= ~7L;
-  return (int)g;
-}
-
-// what an instance can run: K-tile alignment of every K segment, and what its epilogue covers
-static bool cfg_applicable(const GemmArgs& a, int c) {
-  const TileCfg& T = kCfg[c];
-  if (c == 3 || c == 4 || c == 5 || c == 13) return false;   // retired / unused instances (13: the 256x256 tile spills - 128 accumulators + the ping-pong loop) (EXPERIMENTS.md); ids kept so the tuned table's numbering is stable
-  if (a.K % T.bk != 0 || a.Cin % T.bk != 0 || a.cx0 % T.bk != 0 || a.Ktaps % T.bk != 0 || (a.Ktaps < a.K && a.cs0 % T.bk != 0)) return false;
-  const bool col160 = (c == 10 || c == 11 || c == 12 || c == 15);   // the 160 / 320-column epilogue: bias | folded LayerNorm, row bias, residual (+ GEGLU on 320)
-  if (col160 && (a.rowstats_out || a.act || a.out_f32 || (a.N & 7) || (c != 11 && a.geglu))) return false;
-  if (cfg_persistent(c) && ((a.N & 7) || a.out_f32)) return false;   // stream-K owners finish through the coalesced bf16 epilogue
-  return true;
-}
-
-static double plan_cost(const GemmArgs& a, int c, int sk) {
-  const TileCfg& T = kCfg[c];
-  const int nkt = a.K / T.bk;
-  const long tiles = (long)cdiv(a.M, T.bm) * cdiv(a.N, T.bn);
-  if (cfg_persistent(c)) {                                     // every block gets total / grid K-tiles; ~2 tile boundaries per block
-    const int g = persist_grid(a, c);
-    return (double)cdiv((int)(tiles * nkt), g) * T.per_ktile + T.fixed * (1.0 + (double)tiles / g);
-  }
-  const long nb = tiles * sk;
-  const double t_block = cdiv(nkt, sk) * T.per_ktile + T.fixed;
-  const int per_round = 256;                                   // CUs
-  double rounds = (double)((nb + per_round - 1) / per_round);
-  if (T.slots == 512) {                                        // two co-resident blocks overlap each other's stalls
-    if (nb <= 256) rounds = 1.2; 
-  }
-  double t = rounds * t_block;
-  if (sk > 1) t += 12.0 + ((double)a.M * a.N * 4.0 * (sk + 1) / 5.0e12) / 0.45e-6;   // reduce pass: ~5 us + traffic
-  return t;
-}
-
-#include "gemm_tuned.h"
-
-// Tuning aid (scripts/tune_in_situ.py): plan overrides set at run time take precedence over the compiled table, so a
-// candidate plan can be timed inside the real UNet pass - with the shape's real epilogue, neighbours and cache state.
-static std::vector<TunedPlan> g_plan_overrides;
-void dmx_gemm_plan_override_set(int M, int N, int K, int st, int ups, int cfg, int sk) {
-  dmx_plan_epoch_bump();
-  if (cfg < 0) { g_plan_overrides.clear(); return; }
-  for (TunedPlan& tp : g_plan_overrides)
-    if (tp.M == M && tp.N == N && tp.K == K && tp.st == st && tp.ups == ups) { tp.cfg = cfg; tp.sk = sk; return; }
-  g_plan_overrides.push_back(TunedPlan{M, N, K, 0, st, ups, cfg, sk});
-}
-
-// force_tn -> plan id: 1 -> 1 (128x64), 2 -> 0 (128x128), n >= 3 -> n - 1
-static int force_to_cfg(int force_tn) { return force_tn == 1 ? 1 : force_tn == 2 ? 0 : force_tn - 1; }
-
-void dmx_gemm_plan(const GemmArgs& a, int* cfg_out, int* splitk_out, int* ktps_out) {
-  const bool no_split = a.rowstats_out || a.ln_stats || a.geglu || a.act || (a.N % 4) != 0;   // those epilogues live in the GEMM kernel
-  auto take = [&](int c, int sk) -> bool {
-    if (c < 0 || c >= 16 || !cfg_applicable(a, c)) return false;
-    const int nkt = a.K / kCfg[c].bk;
-    if (cfg_persistent(c)) { *cfg_out = c; *splitk_out = 1; *ktps_out = nkt; return true; }
-    if (sk < 1 || (sk > 1 && (no_split || nkt / sk < 4))) return false;
-    const int ktps = cdiv(nkt, sk);
-    *cfg_out = c; *splitk_out = cdiv(nkt, ktps); *ktps_out = ktps;
-    return true;
-  };
-  if (!a.force_tn && !a.force_splitk && (a.N % 4) == 0) {
-    for (const TunedPlan& tp : g_plan_overrides)
-      if (tp.M == a.M && tp.N == a.N && tp.K == a.K && tp.st == a.stride && tp.ups == (a.ups2 ? 2 : a.ups)) {
-        if (take(tp.cfg, tp.sk)) return;
-        break;                                                 // not applicable: normal plan
-      }
-    for (const TunedPlan& tp : kTuned)      // keyed on the GEMM view (M, N, K) + gather flavour; tap structure does not matter
-      if (tp.M == a.M && tp.N == a.N && tp.K == a.K && tp.st == a.stride && tp.ups == (a.ups2 ? 2 : a.ups) && take(tp.cfg, tp.sk)) return;
-  }
-  int best_c = 0, best_sk = 1; double best = 1e300;
-  for (int c = 0; c < 16; ++c) {
-    const TileCfg& T = kCfg[c];
-    if (!cfg_applicable(a, c)) continue;
-    if (a.force_tn) { if (c != force_to_cfg(a.force_tn)) continue; }
-    else {
-      if (c >= 7) continue;                               // eight-wave / 160-column / persistent instances: tuned table or force_tn only
-      if (c != 1 && a.N <= 64) continue;
-      if ((c == 2 || c == 6) && ((long)a.M * a.N < 256L * 128 * 96)) continue;     // big tiles only for big outputs
-      // 3x3 convolutions over <= 128 input channels (the 512^2 / 256^2 levels of the autoencoder, K = 1152): the weight operand is
-      // as large as the activation operand per tile, so the 256-row tile's reuse buys nothing and its longer prologue / epilogue
-      // shows - measured at batch 32 (scripts/attic/vae_conv_probe.py): 128->128 3.54 vs 3.79 ms, 128->256 1.61 vs 1.76 ms
-      if (c == 2 && a.ksize == 3 && !a.direct && a.Cin <= 128 && a.Ktaps == a.K) continue;
-    }
-    const int nkt = a.K / T.bk;
-    const int max_sk = (no_split || cfg_persistent(c)) ? 1 : 16;
-    for (int sk = 1; sk <= max_sk; ++sk) {
-      if (a.force_splitk && sk != a.force_splitk && !cfg_persistent(c)) continue;
-      if (sk > 1 && nkt / sk < (T.bk == 64 ? 4 : 8)) break;
-      if (c == 6 && !a.force_tn && nkt / sk < 40) break;      // the warp-specialised loop pays off from ~2.5k of K per block
-      const double cst = plan_cost(a, c, sk);
-      if (cst < best) { best = cst; best_c = c; best_sk = sk; }
-    }
-  }
-  const int nkt = a.K / kCfg[best_c].bk;
-  int ktps = cdiv(nkt, best_sk);
-  best_sk = cdiv(nkt, ktps);
-  *cfg_out = best_c; *splitk_out = best_sk; *ktps_out = ktps;
-}
-
-bool dmx_gemm_colstats_ok(const GemmArgs& a) {
-  if (a.out_f32 || a.geglu || (a.N & 7) || (a.ldo & 7) || (a.res && (a.ldres & 7)) || a.cs_rows <= 0) return false;
-  int c, sk, ktps;
-  dmx_gemm_plan(a, &c, &sk, &ktps);
-  if (sk > 1 || c == 6) return false;                        // the reduce pass finishes those tiles; the warp-specialised instance has no twin
-  if (c == 12 || c == 15) return false;                      // persistent 160-column instances: the statistics cost the producer +5 us per launch
-                                                             // (measured in situ: 53.8 -> 59.1 us), as much as the consumer saves
-  const int rows = a.ups2 ? a.M4 : a.M;
-  return a.cs_rows % kCfg[c].bm == 0 && rows % a.cs_rows == 0;
-}
-
-int dmx_gemm_persist_blocks(const GemmArgs& a) {
-  int c, sk, ktps;
-  dmx_gemm_plan(a, &c, &sk, &ktps);
-  return cfg_persistent(c) ? persist_grid(a, c) : 0;
-}
-
-int dmx_gemm_tiles_n(const GemmArgs& a) {
-  int c, sk, ktps;
-  dmx_gemm_plan(a, &c, &sk, &ktps);
-  return cdiv(a.N, kCfg[c].bn);
-}
-
-// split-K: sk fp32 planes of the output.  Persistent stream-K: 256 bytes of flags per 64 blocks, then one accumulator slab per block.
-static size_t persist_flag_bytes(int grid) { return align_up((size_t)grid * sizeof(int), 256); }
-size_t dmx_gemm_workspace_bytes(const GemmArgs& a) {
-  int c, sk, ktps;
-  dmx_gemm_plan(a, &c, &sk, &ktps);
-  if (cfg_persistent(c)) {
-    const int g = persist_grid(a, c);
-    return persist_flag_bytes(g) + (size_t)g * kCfg[c].bm * kCfg[c].bn * sizeof(float);
-  }
-  return sk > 1 ? (size_t)sk * a.M * a.N * sizeof(float) : 0;
-}
-
+// One launcher per instance; the statistics-emitting twin of an instance (CS) is used exactly when GemmArgs.colstats is set.
+// `s` is dmx_gemm_launch_shape of the plan: the LDS layout is GemmTile's, for the kernel and for the size asked here.
 template <int WM, int TN, int BKT, int NST, int TM = 2, int NP = 0, int NWN = 2, bool PS = false, int MF = 32, bool CS = false>
-static void launch_cfg_(const GemmArgs& a, dim3 grid, hipStream_t stream) {
-  constexpr int BM = MF * TM * WM, BN = MF * TN * NWN;
-  size_t lds = (size_t)NST * (BM + BN) * BKT * 2;
-  size_t lds_epi = (size_t)BM * (BN + 4) * sizeof(float);             // fp32 staging tile of the coalesced epilogue
-  if (TN == 5) lds_epi /= 2;                                           // the 160 / 320-column tiles stage half their rows per pass
-  else if (lds_epi > 152 * 1024) lds_epi /= WM;                        // the 256x256 tiles stage one 64-row slab (one wave row) per pass
-  if (lds_epi > lds) lds = lds_epi;
-  if (a.ln_stats || TN == 5) lds += (size_t)BM * 2 * sizeof(float);    // (mean, rstd) per row of the folded LayerNorm
-  if (TN == 5) lds += (size_t)3 * BN * sizeof(float);                  // the tile's column vectors (160 / 320-column epilogue)
-  {
-    char sym[112];
-    snprintf(sym, sizeof(sym), "void dmx_gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %s, %d, %s>(GemmArgs)", WM, TN, BKT, NST, TM, NP, NWN, PS ? "true" : "false", MF, CS ? "true" : "false");
-    dmx_profile_note_symbol(sym);
-  }
-  GemmArgs ap = a;                                                     // (the prefetch dump slot: 1 KB behind everything else, where it fits)
-  ap.pf_dump_off = 0;
-  if (a.pf_bytes[0] > 0 && lds + 1024 <= 163840 && (PS ? false : true)) { ap.pf_dump_off = (int)align_up(lds, 16); lds = (size_t)ap.pf_dump_off + 1024; }
-  static bool attr[64] = {};                          // the dynamic-LDS opt-in is per device
-  int dev = 0; (void)hipGetDevice(&dev);
-  if (dev < 64 && !attr[dev]) { (void)hipFuncSetAttribute((const void*)dmx_gemm_kernel<WM, TN, BKT, NST, TM, NP, NWN, PS, MF, CS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + 1040 + BM * 2 * sizeof(float) + 3 * BN * sizeof(float) > 163840 ? 163840 : lds + 1040 + BM * 2 * sizeof(float) + 3 * BN * sizeof(float))); attr[dev] = true; }
-  hipLaunchKernelGGL((dmx_gemm_kernel<WM, TN, BKT, NST, TM, NP, NWN, PS, MF, CS>), grid, dim3(64 * (NWN * WM + NP)), lds, stream, ap);
+static int launch_cfg(const GemmArgs& a, const GemmLaunchShape& s, hipStream_t stream) {
+  typedef GemmTile<WM, TN, BKT, NST, TM, NP, NWN, PS, MF> L;
+  if constexpr (!CS && L::CS_TWIN) { if (a.colstats) return launch_cfg<WM, TN, BKT, NST, TM, NP, NWN, PS, MF, true>(a, s, stream); }
+  char sym[112];
+  snprintf(sym, sizeof(sym), "void dmx_gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %s, %d, %s>(GemmArgs)", WM, TN, BKT, NST, TM, NP, NWN, PS ? "true" : "false", MF, CS ? "true" : "false");
+  dmx_profile_note_symbol(sym);
+  DMX_LDS_OPT_IN((dmx_gemm_kernel<WM, TN, BKT, NST, TM, NP, NWN, PS, MF, CS>), L::LDS_OPT_IN);
+  hipLaunchKernelGGL((dmx_gemm_kernel<WM, TN, BKT, NST, TM, NP, NWN, PS, MF, CS>), dim3(s.grid_x, s.grid_y, 1), dim3(L::NT), s.lds_bytes, stream, a);
+  return DMX_OK;
 }
-
-// the statistics-emitting twin of an instance is used exactly when GemmArgs.colstats is set (the warp-specialised instance has none)
-template <int WM, int TN, int BKT, int NST, int TM = 2, int NP = 0, int NWN = 2, bool PS = false, int MF = 32>
-static void launch_cfg(const GemmArgs& a, dim3 grid, hipStream_t stream) {
-  if constexpr (NP == 0 && !(PS && TN == 5)) { if (a.colstats) { launch_cfg_<WM, TN, BKT, NST, TM, NP, NWN, PS, MF, true>(a, grid, stream); return; } }
-  launch_cfg_<WM, TN, BKT, NST, TM, NP, NWN, PS, MF, false>(a, grid, stream);
-}
+// the launcher column of gemm_tile.h's instance table
+typedef int (*GemmLauncher)(const GemmArgs&, const GemmLaunchShape&, hipStream_t);
+#define DMX_LIVE_(id, name, slots, pk, fx, geglu160, search, what, ...) &launch_cfg<__VA_ARGS__>,
+#define DMX_GONE_(id, name, announced, why) nullptr,
+static const GemmLauncher kLaunch[DMX_GEMM_NCFG] = {DMX_GEMM_INSTANCES(DMX_LIVE_, DMX_GONE_)};
 
 int dmx_gemm_launch(GemmArgs a, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  DMX_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
-  DMX_REQUIRE(a.K % 32 == 0, "gemm: K=%d must be a multiple of 32", a.K);
-  DMX_REQUIRE(a.ldw % 8 == 0 && a.ldx0 % 8 == 0, "gemm: leading dimensions must be multiples of 8 (ldw=%d ldx0=%d)", a.ldw, a.ldx0);
-  DMX_REQUIRE(a.cx0 % 32 == 0 && a.Cin % 32 == 0, "gemm: channel splits must be multiples of 32 (Cin=%d cx0=%d)", a.Cin, a.cx0);
-  DMX_REQUIRE(a.Ktaps % 32 == 0 && a.Ktaps <= a.K, "gemm: bad Ktaps=%d K=%d", a.Ktaps, a.K);
-  if (a.Ktaps < a.K) DMX_REQUIRE(a.s0 != nullptr && a.cs0 % 32 == 0, "gemm: shortcut segment needs s0 and aligned cs0");
-  if (a.ln_stats) DMX_REQUIRE(a.ln_c1 && a.ln_c2 && a.ln_tiles > 0 && a.ln_C > 0 && !a.out_f32 && a.N % 8 == 0 && a.ldo % 8 == 0, "gemm: folded LayerNorm needs c1/c2, bf16 output and N %% 8 == 0");
-  if (a.rowstats_out) DMX_REQUIRE(!a.out_f32 && a.N % 8 == 0 && a.ldo % 8 == 0 && !a.geglu, "gemm: row statistics need the bf16 coalesced epilogue");
-  if (a.act) DMX_REQUIRE(a.act == 1 && !a.out_f32 && !a.geglu && a.N % 8 == 0 && a.ldo % 8 == 0 && (a.res == nullptr || a.ldres % 8 == 0), "gemm: the GELU epilogue needs the bf16 coalesced path (N %% 8 == 0)");
-  if (a.geglu) DMX_REQUIRE((a.bias || a.ln_stats) && a.N % 128 == 0 && !a.out_f32 && !a.res && !a.rowbias && a.ldo % 8 == 0, "gemm: GEGLU needs bias, N%%128==0, bf16 out");
-  if (a.ups2) {
-    DMX_REQUIRE(a.ksize == 2 && !a.direct && !a.ups && a.stride == 1 && a.OH == a.IH && a.OW == a.IW && a.M4 > 0 && a.M == 4 * a.M4 &&
-                a.Ktaps == a.K && a.K == 4 * a.Cin && a.w_phase_stride > 0, "gemm: inconsistent phase-decomposed upsample conv arguments");
-    DMX_REQUIRE(!a.res && !a.rowbias && !a.geglu && !a.act && !a.ln_stats && !a.rowstats_out, "gemm: the phase-decomposed upsample conv takes a bias only");
+  GemmPlan P;
+  if (const int rc = dmx_gemm_check_and_plan(a, n_cus(), &P)) return rc;
+  if (const int rc = dmx_zero_page(&a.zeros)) return rc;
+  const int c = P.cfg, sk = P.splitk;
+  const GemmLaunchShape shape = dmx_gemm_launch_shape(a, P);
+  a.pf_dump_off = shape.pf_dump_off;                           // (0: no room for the prefetch dump slot behind this instance's LDS, no prefetch)
+  a.splitk = sk; a.kt_per_split = P.kt_per_split; a.persist = 0;
+  if (P.workspace_bytes && (workspace == nullptr || workspace_bytes < P.workspace_bytes)) {
+    dmx_set_error(P.persist_blocks ? "gemm: the persistent stream-K plan needs %zu bytes of workspace, got %zu" : "gemm: split-K needs %zu bytes of workspace, got %zu", P.workspace_bytes, workspace_bytes);
+    return DMX_ERR_WORKSPACE;
   }
-  DMX_REQUIRE(a.force_tn < 4 || a.force_tn > 6, "gemm: tile instance %d was retired", a.force_tn);
-  if (a.colstats) DMX_REQUIRE(dmx_gemm_colstats_ok(a), "gemm: this plan cannot emit column statistics (split-K, fp32 / GEGLU output or tiles straddling samples)");
-  if (a.force_tn) DMX_REQUIRE(a.force_tn <= 16 && cfg_applicable(a, force_to_cfg(a.force_tn)), "gemm: tile instance %d cannot run this problem (K-tile alignment / epilogue)", a.force_tn);
-  int rc = dmx_zero_page(&a.zeros);
-  if (rc) return rc;
-  int c, sk, ktps;
-  dmx_gemm_plan(a, &c, &sk, &ktps);
-  a.splitk = sk; a.kt_per_split = ktps; a.persist = 0;
-  const TileCfg& T = kCfg[c];
-  dim3 grid((a.ups2 ? 4 * cdiv(a.M4, T.bm) : cdiv(a.M, T.bm)) * cdiv(a.N, T.bn), sk, 1);
-  if (cfg_persistent(c)) {
-    const int g = persist_grid(a, c);
-    const size_t fb = persist_flag_bytes(g), need = fb + (size_t)g * T.bm * T.bn * sizeof(float);
-    if (workspace == nullptr || workspace_bytes < need) {
-      dmx_set_error("gemm: the persistent stream-K plan needs %zu bytes of workspace, got %zu", need, workspace_bytes);
-      return DMX_ERR_WORKSPACE;
-    }
-    a.persist = 1; a.partial = (float*)((char*)workspace + fb); a.err = dmx_dev_err_words();
+  if (P.persist_blocks) {
+    a.persist = 1; a.partial = (float*)((char*)workspace + P.flag_bytes); a.err = dmx_dev_err_words();
     if (!a.flags) {                                            // standalone call: the executors hand out slices of a pool they zero once per forward
       a.flags = (int*)workspace;
-      if (const int zr = dmx_zero16_launch(a.flags, fb, stream)) return zr;      // a kernel node, not a memset node: exec.hip Exec::zero_pool
+      if (const int zr = dmx_zero16_launch(a.flags, P.flag_bytes, stream)) return zr;      // a kernel node, not a memset node: exec.hip Exec::zero_pool
     }
-    grid = dim3(g, 1, 1);
-  } else if (sk > 1) {
-    const size_t need = (size_t)sk * a.M * a.N * sizeof(float);
-    if (workspace == nullptr || workspace_bytes < need) {
-      dmx_set_error("gemm: split-K needs %zu bytes of workspace, got %zu", need, workspace_bytes);
-      return DMX_ERR_WORKSPACE;
-    }
-    a.partial = (float*)workspace;
-  }
+  } else if (sk > 1) a.partial = (float*)workspace;
   // algorithmic work of this launch: 2*M*N*K flops; bytes = activations read once + weights + output
   const double flops = 2.0 * a.M * (double)a.N * a.K;
   const double bytes = 2.0 * ((double)(a.ups2 ? a.M4 : a.M) * (a.K / (a.direct ? 1 : (a.ksize * a.ksize))) + (double)a.N * a.K * (a.ups2 ? 4 : 1) + (double)a.M * (a.geglu ? a.N / 2 : a.N));
   char tag[96];
-  snprintf(tag, sizeof(tag), "M=%d N=%d K=%d ks=%d st=%d ups=%d tn=%d sk=%d", a.M, a.N, a.K, a.direct ? 1 : a.ksize, a.stride, a.ups2 ? 2 : a.ups, c == 0 ? 2 : (c == 1 ? 1 : c + 1), sk);
+  snprintf(tag, sizeof(tag), "M=%d N=%d K=%d ks=%d st=%d ups=%d tn=%d sk=%d", a.M, a.N, a.K, a.direct ? 1 : a.ksize, a.stride, a.ups2 ? 2 : a.ups, dmx_gemm_force_of_cfg(c), sk);
   {
     ProfScope ps((ProfClass)(PROF_GEMM_CFG0 + c), stream, flops, bytes, tag);
-    if (c == 0) launch_cfg<2, 2, 32, 4>(a, grid, stream);
-    else if (c == 1) launch_cfg<2, 1, 32, 4>(a, grid, stream);
-    else if (c == 2) launch_cfg<4, 2, 64, 3>(a, grid, stream);
-    else if (c == 6) launch_cfg<2, 2, 64, 3, 4, 4>(a, grid, stream);
-    else if (c == 7) launch_cfg<4, 1, 64, 3, 1>(a, grid, stream);
-    else if (c == 8) launch_cfg<4, 2, 32, 4, 1>(a, grid, stream);
-    else if (c == 9) launch_cfg<4, 2, 64, 3, 1>(a, grid, stream);
-    else if (c == 10) launch_cfg<4, 5, 64, 2, 1, 0, 1>(a, grid, stream);
-    else if (c == 11) launch_cfg<4, 5, 64, 2, 1, 0, 2>(a, grid, stream);
-    else if (c == 12) launch_cfg<8, 5, 64, 3, 1, 0, 1, true>(a, grid, stream);
-    else if (c == 14) launch_cfg<8, 4, 64, 3, 1, 0, 1, true>(a, grid, stream);
-    else if (c == 15) launch_cfg<4, 5, 64, 3, 4, 0, 2, true, 16>(a, grid, stream);
-    else { dmx_set_error("gemm: plan id %d has no instance", c); return DMX_ERR_ARG; }
+    if (!kLaunch[c]) { dmx_set_error("gemm: plan id %d has no instance", c); return DMX_ERR_ARG; }
+    if (const int rc = kLaunch[c](a, shape, stream)) return rc;
   }
-  rc = dmx_check_launch("dmx_gemm_kernel");
-  if (rc) return rc;
-  if (sk > 1 && !a.defer_reduce) rc = dmx_splitk_reduce_launch(a, stream);
-  return rc;
+  if (const int rc = dmx_check_launch("dmx_gemm_kernel")) return rc;
+  return (sk > 1 && !a.defer_reduce) ? dmx_splitk_reduce_launch(a, stream) : DMX_OK;
 }
 
 // the reduce pass of a split-K GEMM on its own (a: the arguments dmx_gemm_launch ran with, partial / splitk filled in)

@@ -69,18 +69,30 @@ struct GemmArgs {
   // GroupNorm statistics of the output for its consumer (norm.hip dmx_groupnorm_sums_launch, conv_halo.hip): per (sample, channel) a
   // DmxStat record (common.h; 4 x int64 fixed point) of the rounded outputs, ADDED into colstats[(sample*N + n)*4 ..] (zero before the launch);
   // cs_rows = rows per sample (a tile must not straddle samples: cs_rows % tile rows == 0).  Plans without a reduce pass only
-  // (dmx_gemm_colstats_ok); bf16 coalesced epilogues.
+  // (GemmPlan.colstats_ok); bf16 coalesced epilogues.
   long long* colstats; int cs_rows;
   const bf16* zeros;                           // filled by the launcher
 };
 int dmx_gemm_launch(GemmArgs a, void* workspace, size_t workspace_bytes, hipStream_t stream);
-size_t dmx_gemm_workspace_bytes(const GemmArgs& a);
-void dmx_gemm_plan(const GemmArgs& a, int* tn, int* splitk, int* ktps);
 int dmx_zero_page(const bf16** out);
+// gemm_plan.hip: what dmx_gemm_launch will do with a problem on a device of n_cu compute units.  Host arithmetic only (no HIP call).
+struct GemmPlan {
+  int cfg;                               // plan id: the instance of gemm_tile.h
+  int splitk, kt_per_split;              // > 1: fp32 partial planes of the output + a reduce pass; K-tiles per split
+  int tiles_n;                           // n-tiles (rowstats_out sizing)
+  int persist_blocks;                    // grid of a persistent stream-K plan, 0 for a classic plan
+  size_t flag_bytes, workspace_bytes;    // persistent: the flags in front of the accumulator slabs; all of the workspace the launch needs
+  bool colstats_ok;                      // this plan can emit GemmArgs.colstats (a.cs_rows set)
+};
+GemmPlan dmx_gemm_plan(const GemmArgs& a, int n_cu);
+inline GemmPlan dmx_gemm_plan(const GemmArgs& a) { return dmx_gemm_plan(a, n_cus()); }
+struct GemmLaunchShape { int grid_x, grid_y, threads, lds_bytes, pf_dump_off; };
+GemmLaunchShape dmx_gemm_launch_shape(const GemmArgs& a, const GemmPlan& p);
+int dmx_gemm_check_and_plan(const GemmArgs& a, int n_cu, GemmPlan* plan);   // dmx_gemm_launch's argument checks, then the plan (DMX_ERR_ARG + message for a problem it refuses)
+int dmx_gemm_cfg_of_force(int force_tn);         // GemmArgs.force_tn <-> plan id
+int dmx_gemm_force_of_cfg(int cfg);
 void dmx_gemm_plan_override_set(int M, int N, int K, int st, int ups, int cfg, int sk);   // tuning aid; cfg < 0 clears all
-bool dmx_gemm_colstats_ok(const GemmArgs& a);    // the plan this problem runs on can emit GemmArgs.colstats (a.cs_rows set)
-int dmx_gemm_persist_blocks(const GemmArgs& a);   // grid of the persistent stream-K plan this problem will run on, 0 for a classic plan
-int dmx_gemm_tiles_n(const GemmArgs& a);       // n-tiles of the plan that dmx_gemm_launch will pick (rowstats_out sizing)
+GemmArgs dmx_gemm_args(const dmx_gemm_desc* d);  // api.hip: the C ABI's descriptor as launch arguments
 // W' = bf16(W*gamma) and the c1 / c2 vectors of the folded LayerNorm, from the raw bf16 weights (rows may be GEGLU-packed)
 // [4][N][4*Cin] phase weights of GemmArgs.ups2 from taps-major 3x3 weights [N][ldw3]
 int dmx_ups_phase_weights_launch(const bf16* w3, int ldw3, bf16* wp, int N, int Cin, hipStream_t stream);

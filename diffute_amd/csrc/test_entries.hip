@@ -2,7 +2,7 @@
 // operator-level entry of their own - train_small.hip's transposes, add, pointwise 1x1 and small-linear backward, norm.hip's row
 // softmax and vae_train.hip's casts (tests/test_train_small_gpu.py) - and the two weight-preparation kernels that only the model
 // executors launch: gemm.hip's folded-LayerNorm weights and elementwise.hip's padded context cast (tests/test_weight_pack_gpu.py); fold.hip's
-// composition and the folded block tail on the executor (tests/test_ff_fold_gpu.py).
+// composition and the folded block tail on the executor (tests/test_ff_fold_gpu.py); gemm_plan.hip's planner (tests/test_gemm_plan_host.py).
 // Each entry checks its arguments and forwards to the *_launch function / executor op the graphs call; none does arithmetic of its own.
 #include "exec.h"
 
@@ -80,6 +80,21 @@ extern "C" int dmx_test_mode_bwd(const void* dz, int lddz, float* dmom, int M, i
 extern "C" int dmx_test_bf16_to_f32_rows(const void* in, int ldin, float* out, int M, int C, dmx_stream_t stream) {
   DMX_REQUIRE(in && out && M > 0 && C > 0 && ldin >= C, "test_bf16_to_f32_rows: bad argument");
   return dmx_bf16_to_f32_rows_launch((const bf16*)in, ldin, out, M, C, ST(stream));
+}
+
+// The GEMM planner without a device (tests/test_gemm_plan_host.py): what dmx_conv_gemm(d) would check, plan and launch on n_cus compute units
+extern "C" int dmx_test_gemm_plan(const dmx_gemm_desc* d, int n_cus, long long* out) {
+  DMX_REQUIRE(d && out && n_cus > 0, "test_gemm_plan: bad argument");
+  for (int i = 0; i < 12; ++i) out[i] = 0;
+  GemmArgs a = dmx_gemm_args(d);
+  if (d->ups == 2) { a.ups = 0; a.ups2 = 1; a.M4 = a.M / 4; a.w_phase_stride = (long long)a.N * a.K; }   // the phase-decomposed upsample conv of dmx_conv_ups2x
+  GemmPlan P;
+  if (const int rc = dmx_gemm_check_and_plan(a, n_cus, &P)) return rc;
+  a.pf_bytes[0] = 0;    const GemmLaunchShape s = dmx_gemm_launch_shape(a, P);        // without / with weight-prefetch ranges (Exec::peek)
+  a.pf_bytes[0] = 4096; const GemmLaunchShape spf = dmx_gemm_launch_shape(a, P);
+  const long long v[12] = {P.cfg, P.splitk, P.kt_per_split, P.tiles_n, P.persist_blocks, (long long)P.workspace_bytes, s.grid_x, s.grid_y, s.threads, s.lds_bytes, spf.lds_bytes, P.colstats_ok ? 1 : 0};
+  for (int i = 0; i < 12; ++i) out[i] = v[i];
+  return DMX_OK;
 }
 
 // W' (16) [N][K] = round16(w_raw * gamma), c1[n] = sum_k W'[n][k], c2[n] = sum_k beta[k] w_raw[n][k] (+ bias[n]); all dense, K a multiple of 8

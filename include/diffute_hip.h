@@ -133,7 +133,7 @@ typedef struct dmx_gemm_desc {
   const void* res; int ldres;       /* bf16 residual or NULL                                 */
   void* out; int ldo; int out_f32;  /* bf16 (default) or fp32 output                         */
   int geglu;                        /* 1: weights/bias GEGLU-packed, out[m][j] = a*gelu(b)   */
-  int force_tn, force_splitk;       /* 0 = automatic plan; tuning / tests may pin the tile (1|2) and split */
+  int force_tn, force_splitk;       /* 0 = automatic plan; tuning / tests may pin the tile instance (1..16) and split */
   int group_m;                      /* m-tiles per L2 super-tile of the block rasterisation (0 = default) */
   long long* timing;                /* optional device buffer [blocks][4]: per-block start / prologue / loop / end
                                        timestamps in 10 ns ticks (measurement aid), normally NULL */
@@ -162,6 +162,12 @@ int dmx_set_gn_producer_stats(int on);                      /* tuning aid: 0 mak
 int dmx_conv_gemm_colstats_ok(const dmx_gemm_desc* d);      /* 1 when dmx_conv_gemm(d) can fill d->colstats (d->cs_rows set)      */
 int dmx_conv_gemm_rowstats_tiles(const dmx_gemm_desc* d);   /* partials per row that dmx_conv_gemm(d) will write to rowstats_out */
 int dmx_conv_gemm(const dmx_gemm_desc* d, void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+/* Test support (tests/test_gemm_plan_host.py; declared here because it takes the descriptor): what dmx_conv_gemm(d) would do on a device of
+ * n_cus compute units, without a device call and without reading through any pointer of d.  Returns what dmx_conv_gemm returns for the
+ * arguments (DMX_ERR_ARG for a problem it refuses, out zeroed) and writes out[12] = {plan id, split-K factor, K-tiles per split, n-tiles,
+ * blocks of a persistent plan (0: classic), workspace bytes, grid x, grid y, block threads, dynamic LDS bytes without and with weight-prefetch
+ * ranges, dmx_conv_gemm_colstats_ok(d)}.  d->ups = 2 stands for the problem dmx_conv_ups2x builds (ksize 2, K = 4 Cin, M = 4 rows per source pixel). */
+int dmx_test_gemm_plan(const dmx_gemm_desc* d, int n_cus, long long* out);
 
 /* K10 (Upsample2D: F.interpolate(scale 2, nearest) + conv3x3, the diffusers call inside pipeline_diffute.py's unet(...),
  * SURVEY.md 8a) as four 2x2 convolutions on the SOURCE grid, one per output pixel parity, with the 3x3 taps that land on
@@ -175,7 +181,8 @@ int dmx_conv_ups2x(const void* x, int ldx, int B, int IH, int IW, int Cin, const
                    void* out, int ldo, int force_tn, int force_splitk, void* workspace, size_t workspace_bytes, dmx_stream_t stream);
 
 /* Tuning aid (scripts/tune_in_situ.py): override the tile plan of every GEMM with this (M, N, K, stride, ups) signature
- * (ups: 0, 1, or 2 for the phase-decomposed upsample conv) by template instance `cfg` (0..11: gemm.hip tiles; 12..14: the persistent linear kernel of lin.hip) and split-K factor; cfg < 0
+ * (ups: 0, 1, or 2 for the phase-decomposed upsample conv) by tile instance `cfg`
+ * (plan id 0..15, the rows of csrc/gemm_tile.h: 0..11 classic tiles, 12..15 persistent stream-K; force_tn = 1 for id 1, 2 for id 0, id + 1 otherwise) and split-K factor; cfg < 0
  * clears all overrides.  Not thread-safe; captured hipGraphs keep the plan they were captured with. */
 int dmx_gemm_plan_override(int M, int N, int K, int stride, int ups, int cfg, int splitk);
 

@@ -150,7 +150,7 @@ def lnf_eval(case, elem, fault=None):
 
 
 # ---------------------------------------------------------------------------------------------- GEMM / implicit conv
-# force_tn -> (rows, columns, K-tile, persistent stream-K, 160 / 320-column epilogue)   (gemm.hip kCfg / cfg_applicable)
+# force_tn -> (rows, columns, K-tile, persistent stream-K, 160 / 320-column epilogue)   (csrc/gemm_tile.h DMX_GEMM_INSTANCES / gemm_plan.hip cfg_applicable)
 GEMM_TN = {1: (128, 64, 32, 0, 0), 2: (128, 128, 32, 0, 0), 3: (256, 128, 64, 0, 0), 7: (256, 128, 64, 0, 0), 8: (128, 64, 64, 0, 0),
            9: (128, 128, 32, 0, 0), 10: (128, 128, 64, 0, 0), 11: (128, 160, 64, 0, 1), 12: (128, 320, 64, 0, 1), 13: (256, 160, 64, 1, 1),
            15: (256, 128, 64, 1, 0), 16: (256, 160, 64, 1, 1)}
@@ -159,7 +159,7 @@ GEMM_FAMILIES = ("base", "shortcut", "f32_N4", "f32_N3", "geglu", "act1", "rowst
 
 
 def gemm_cannot_run(tn, fam):
-    """the reason (instance tn, family) cannot run - gemm.hip's cfg_applicable - or None.  The GPU test asserts the library agrees both ways."""
+    """the reason (instance tn, family) cannot run - gemm_plan.hip's cfg_applicable - or None.  The GPU test asserts the library agrees both ways."""
     bm, bn, bk, persist, col160 = GEMM_TN[tn]
     if fam in ("f32_N4", "f32_N3"):
         if col160: return "the 160 / 320-column epilogue has no fp32 output"
