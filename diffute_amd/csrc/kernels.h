@@ -400,6 +400,12 @@ int dmx_add_bf16_launch(const bf16* a, int lda, const bf16* b, int ldb, bf16* o,
 size_t dmx_mse_workspace_bytes();
 int dmx_mse_loss_launch(const float* pred, const float* target, size_t n, float* loss, float* dpred, float grad_scale,
                         void* workspace, size_t workspace_bytes, hipStream_t stream);
+// the weighted objective of the denoiser (loss.hip; arithmetic, records and reduction shape: include/diffute_hip.h)
+size_t dmx_diffusion_loss_ws_bytes(int B, int C, int hw);
+int dmx_diffusion_loss_launch(const float* pred, const float* latents, const float* noise, const float* mask, const int64_t* timesteps,
+                              const float* sa, const float* sb, const float* wt, int B, int C, int hw, int T, int v_prediction,
+                              float mask_weight, float grad_scale, float* loss, float* records, float* dpred,
+                              void* workspace, size_t workspace_bytes, hipStream_t stream);
 // 1x1 convs between <= 8 channels (VAE quant / post_quant), softmax backward over rows (VAE mid attention)
 int dmx_pointwise_small_fwd_launch(const bf16* x, int ldx, const bf16* w, int ldw, const float* bias, void* y, int ldy, int M, int Cin, int Cout,
                                    int out_f32, hipStream_t stream);

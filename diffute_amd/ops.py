@@ -170,6 +170,38 @@ def mse_loss(pred, target, grad_scale=1.0, dpred=True, loss=None):
     return loss, dpred
 
 
+def diffusion_loss(pred, latents, noise, timesteps, sa, sb, wt, *, mask=None, v_prediction=False, mask_weight=0.0, grad_scale=1.0,
+                   dpred=True, loss=None, records=None):
+    """-> (loss fp32 [1], records fp32 [B, LOSS_ROW_FLOATS], dpred): dmx_diffusion_loss (include/diffute_hip.h has the arithmetic).
+    pred / latents / noise fp32 [B,C,h,w]; mask fp32 [B,1,h,w] or None; timesteps int64 [B]; sa / sb / wt fp32 [T] tables.
+    dpred: True = a fresh tensor, a tensor = write there, None / False = loss and records only."""
+    B, C = pred.shape[0], pred.shape[1]
+    hw = pred.numel() // (B * C)
+    for t in (pred, latents, noise):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == pred.shape
+    assert timesteps.dtype == torch.int64 and timesteps.is_contiguous() and timesteps.numel() == B
+    T = sa.numel()
+    for t in (sa, sb, wt):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == T
+    if mask is not None:
+        assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.numel() == B * hw
+    loss = _out(loss, (1,), torch.float32, pred.device)
+    records = _out(records, (B, _cabi.LOSS_ROW_FLOATS), torch.float32, pred.device)
+    assert records.is_contiguous()
+    if dpred is True:
+        dpred = torch.empty_like(pred)
+    elif dpred is False:
+        dpred = None
+    if dpred is not None:
+        assert dpred.is_contiguous() and dpred.numel() == pred.numel() and dpred.dtype == torch.float32
+    wsb = lib().dmx_diffusion_loss_workspace_bytes(B, C, hw)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=pred.device)
+    check(lib().dmx_diffusion_loss(ptr(pred), ptr(latents), ptr(noise), ptr(mask), ptr(timesteps), ptr(sa), ptr(sb), ptr(wt), B, C, hw, T,
+                                   int(bool(v_prediction)), float(mask_weight), float(grad_scale), ptr(loss), ptr(records), ptr(dpred),
+                                   ptr(ws), wsb, current_stream()), "diffusion_loss")
+    return loss, records, dpred
+
+
 def pack_geglu_bias(b):
     b = b.to(torch.float32).contiguous()
     out = torch.empty_like(b)

@@ -15,6 +15,7 @@ slots, the timestep).  The three `step()` methods, `pipeline.denoise()` and the 
 record; `launch_step` hands one to the scalar entry of its scheduler kind.
 """
 import json
+import math
 import os
 from types import SimpleNamespace
 
@@ -221,6 +222,38 @@ class _SchedulerBase:
             sa = (self.alphas_cumprod ** 0.5).to(device)
             sb = ((1 - self.alphas_cumprod) ** 0.5).to(device)
             self._dev_tables[key] = (sa, sb)
+        return self._dev_tables[key]
+
+    def loss_weights(self, snr_gamma=None):
+        """The per-timestep sample weight of the training loss, float64 [num_train_timesteps], computed in float64 from alphas_cumprod.
+        None: 1 everywhere.  Otherwise Min-SNR-gamma (Hang et al., ICCV 2023; diffusers' --snr_gamma) with snr = abar / (1 - abar):
+        min(snr, gamma) / snr for an epsilon model, min(snr, gamma) / (snr + 1) for a v model."""
+        abar = self.alphas_cumprod.to(torch.float64)
+        g = self._check_snr_gamma(snr_gamma)
+        if g is None:
+            return torch.ones_like(abar)
+        snr = abar / (1 - abar)
+        clipped = torch.minimum(snr, torch.full_like(snr, g))
+        if self.config.prediction_type == "epsilon":
+            return clipped / snr
+        if self.config.prediction_type == "v_prediction":
+            return clipped / (snr + 1)
+        raise ValueError(f"Unknown prediction type {self.config.prediction_type}")
+
+    @staticmethod
+    def _check_snr_gamma(snr_gamma):
+        if snr_gamma is None:
+            return None
+        g = float(snr_gamma)
+        if not (math.isfinite(g) and g > 0):
+            raise ValueError(f"snr_gamma must be finite and greater than 0, got {snr_gamma!r}")
+        return g
+
+    def _loss_weight_table(self, device, snr_gamma=None):
+        """loss_weights(snr_gamma) as fp32 on `device`, cached per (device, snr_gamma, prediction_type) like _coef_tables"""
+        key = (str(device), self._check_snr_gamma(snr_gamma), self.config.prediction_type)
+        if key not in self._dev_tables:
+            self._dev_tables[key] = self.loss_weights(snr_gamma).to(torch.float32).to(device)
         return self._dev_tables[key]
 
     def _mix(self, a, b, timesteps, velocity):

@@ -676,6 +676,7 @@ int dmx_unet_forward_f32(dmx_unet* u, const void* masters, const float* f0, int 
  *                            bucket i is final, so the gradient exchange (RCCL) can overlap the rest of the backward
  *   dmx_unet_grad_export     one parameter's gradient in its torch layout
  *   dmx_mse_loss             loss = mean((pred - target)^2) and dpred = 2 (pred - target) / n * grad_scale
+ *   dmx_diffusion_loss       the Min-SNR / text-box weighted objective with its target, gradient and per-sample sums (declared below)
  * ---------------------------------------------------------------------------------- */
 size_t dmx_unet_train_workspace_bytes(dmx_unet* u, int B, int H, int W, int ctx_len);
 size_t dmx_unet_train_wt_bytes(const dmx_unet* u);
@@ -1056,6 +1057,43 @@ int dmx_copy_multi(const void* table, int nchunks, dmx_stream_t stream);
 size_t dmx_mse_loss_workspace_bytes(void);
 int dmx_mse_loss(const float* pred, const float* target, size_t n, float* loss, float* dpred, float grad_scale,
                  void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+/* The weighted objective of the denoiser in one entry (csrc/loss.hip): Min-SNR-gamma sample weights (Hang et al., ICCV 2023; diffusers'
+ * --snr_gamma), an emphasis on the text box, the epsilon / v target, dLoss/dpred and per-sample sums, from what the training step holds.
+ * No target and no weight tensor is materialised.  pred, latents (x0), noise, dpred: fp32 [B][C][hw]; mask: fp32 [B][1][hw] at latent
+ * resolution (1 inside the box) or NULL; timesteps: int64 [B]; sa = sqrt(abar), sb = sqrt(1 - abar), wt = the per-timestep sample weight:
+ * T floats each.  For sample b with t = timesteps[b], every line one rounded fp32 operation, in this order:
+ *     tau   = noise                                     (v_prediction 0)
+ *     tau   = fsub(fmul(sa[t], noise), fmul(sb[t], x0)) (v_prediction 1: the bits dmx_sched_get_velocity writes)
+ *     d     = fsub(pred, tau)          q = fmul(d, d)
+ *     m     = fadd(1, fmul(mask_weight, M))             (M = mask[b][0][pixel], the same for every channel; M = 0 when mask is NULL)
+ *     e     = fmul(wt[t], m)
+ *     dpred = fmul(fmul(d, e), gs)                      gs = (float)(2 * grad_scale / N) in double on the host, N = B*C*hw
+ * records: fp32 [B][DMX_LOSS_ROW_FLOATS], the sums of sample b over its C*hw elements (mask_sum: over its hw pixels) and its weight:
+ *     SQ_ALL = sum q     SQ_MASK = sum fmul(M, q)     SQ_WEIGHTED = sum fmul(m, q)     MASK_SUM = sum M     WEIGHT = wt[t]
+ * loss (fp32 [1]): acc = 0; for b = 0 .. B-1: acc = fadd(acc, fmul(WEIGHT[b], SQ_WEIGHTED[b])); loss = fmul(acc, (float)(1.0 / N)).
+ * That is (1/N) sum_b w_b sum m (pred - tau)^2: diffusers' Min-SNR loss at mask_weight 0, the plain MSE when wt is all ones as well.  The
+ * emphasis is NOT renormalised by sum m: mask_weight changes the scale of the loss.
+ * Two launches (per-block partial sums; one block that folds them), no float atomics, no block waits for another.  A sample is cut into
+ * chunks of DMX_LOSS_CHUNK elements, one block each, so which block and which thread adds an element depends on C*hw alone, never on B or
+ * on b: a sample's record and dpred row are the same bits alone or as any row of any batch, and from run to run.  16-byte accesses where a
+ * sample's first element is 16-byte aligned in every tensor (scalar otherwise and for the last, partial quad; the order of the additions
+ * is the same either way).  Reduction shape: 8 serial adds per thread, an 8-level tree over the 256 threads of a block, then the
+ * ceil(C*hw / DMX_LOSS_CHUNK) chunk sums serially: a term passes through at most k = 16 + ceil(C*hw / DMX_LOSS_CHUNK) additions.
+ * A timestep outside [0, T) reads the tables at the clamped index and gives that sample WEIGHT = NaN, hence NaN dpred rows and a NaN
+ * loss; the other samples' records and dpred rows are what they are in a clean batch.  dpred == NULL: loss and records only.
+ * mask_weight must be finite and >= 0.  Everything is fp32: both builds of the library compute the same bits. */
+#define DMX_LOSS_ROW_FLOATS 5
+#define DMX_LOSS_SQ_ALL 0
+#define DMX_LOSS_SQ_MASK 1
+#define DMX_LOSS_SQ_WEIGHTED 2
+#define DMX_LOSS_MASK_SUM 3
+#define DMX_LOSS_WEIGHT 4
+#define DMX_LOSS_CHUNK 2048
+size_t dmx_diffusion_loss_workspace_bytes(int B, int C, int hw);
+int dmx_diffusion_loss(const float* pred, const float* latents, const float* noise, const float* mask, const int64_t* timesteps,
+                       const float* sa, const float* sb, const float* wt, int B, int C, int hw, int T, int v_prediction,
+                       float mask_weight, float grad_scale, float* loss, float* records, float* dpred,
+                       void* workspace, size_t workspace_bytes, dmx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Glyph encoder: the ViT encoder of TrOCR, `trocr_model(pixel_values).last_hidden_state`

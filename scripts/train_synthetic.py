@@ -1,7 +1,7 @@
 """Does the training loop learn on rendered text, and does the glyph context carry anything the UNet can use?
 
     python scripts/train_synthetic.py [--steps 300] [--batch 4] [--lr 2e-4] [--size 128] [--eval-pages 8] [--context_dropout 0]
-                                      [--out profiles/train_synthetic_line.json]
+                                      [--snr_gamma G] [--mask_weight L] [--out profiles/train_synthetic_line.json]
 
 The tiny UNet / VAE / glyph encoder of the tests (random initialisation; VAE and encoder frozen, as in the reference) are trained with
 train_step + FusedAdamW on SyntheticDocuments.batches: pages composed on the device, one confident line per page, the reference's
@@ -14,7 +14,14 @@ before and after training.  The numbers are reported, not asserted: nobody has m
 
 --context_dropout P (the training half of classifier-free guidance, diffute_amd.Guidance): with probability P a training row's glyph
 context is replaced by zeros (SyntheticDocuments.batches(context_dropout=P)).  The line then also carries the held-out loss under the NULL
-(all-zero) context before and after training, next to the own / rotated figures.  With the default 0 the line is what it always was."""
+(all-zero) context before and after training, next to the own / rotated figures.  With the default 0 the line is what it always was.
+
+--snr_gamma G / --mask_weight L: train on the weighted objective (train_step(snr_gamma=G, mask_weight=L): Min-SNR-gamma sample weights and / or
+1 + L times the loss inside the text box, diffute_amd.training.diffusion_loss).  With neither, training and every figure above are what they
+always were.  The held-out evaluation is an UNWEIGHTED statistic whatever the training objective, and the line always carries it split at the
+text box as well (the `masked` / `unmasked` entries: the mean over rows and EVAL_TIMESTEPS of diffusion_loss(...).masked_mse / .unmasked_mse at
+snr_gamma=None, mask_weight=0, no gradient asked of the kernel) for the own, rotated and - with --context_dropout - null contexts, before and
+after training, with the own-versus-rotated gap inside the box."""
 import argparse
 import json
 import os
@@ -36,22 +43,25 @@ HELD_OUT = 1 << 20              # first held-out page index
 
 @torch.no_grad()
 def held_out_loss(unet, vae, scheduler, batch, contexts, fixed):
-    """mean over EVAL_TIMESTEPS of the training loss on `batch` with `contexts`, every random draw taken from `fixed`"""
+    """mean over EVAL_TIMESTEPS of the (unweighted) training loss on `batch` with `contexts`, every random draw taken from `fixed`
+    -> (loss, the same inside the text box, outside it)"""
     import diffute_amd as D
     from diffute_amd.models import mse_loss
-    from diffute_amd.training import encode_latents, training_target
+    from diffute_amd.training import diffusion_loss, encode_latents, training_target
     pv = batch["pixel_values"]
     B = pv.shape[0]
     both = encode_latents(vae, torch.cat([pv, batch["masked_images"]], 0), fixed["enc_noise"], None)
     latents, masked = both[:B].contiguous(), both[B:].contiguous()
     mask = D.mask_to_latent(batch["masks"], 2 ** (len(vae.config.block_out_channels) - 1)).to(latents.dtype)
-    losses = []
+    losses, inside, outside = [], [], []
     for t in EVAL_TIMESTEPS:
         ts = torch.full((B,), t, device=pv.device, dtype=torch.long)
         noisy = scheduler.add_noise(latents, fixed["noise"], ts)
         pred = unet(torch.cat([noisy, mask, masked], 1), ts, contexts).sample
         losses.append(float(mse_loss(pred.float(), training_target(scheduler, latents, fixed["noise"], ts).float())))
-    return sum(losses) / len(losses)
+        split = diffusion_loss(pred.float(), latents, fixed["noise"], ts, scheduler, mask=mask)
+        inside.append(split.masked_mse); outside.append(split.unmasked_mse)
+    return sum(losses) / len(losses), float(torch.nanmean(torch.stack(inside))), float(torch.nanmean(torch.stack(outside)))
 
 
 def main():
@@ -63,6 +73,8 @@ def main():
     ap.add_argument("--eval-pages", type=int, default=8)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--context_dropout", type=float, default=0.0)
+    ap.add_argument("--snr_gamma", type=float, default=None)
+    ap.add_argument("--mask_weight", type=float, default=0.0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_synthetic_line.json"))
     args = ap.parse_args()
     import diffute_amd as D
@@ -94,9 +106,11 @@ def main():
     before = evaluate()
     losses, t0 = [], time.perf_counter()
     drop = dict(context_dropout=args.context_dropout) if args.context_dropout > 0 else {}
+    weighted = args.snr_gamma is not None or args.mask_weight != 0
+    objective = dict(snr_gamma=args.snr_gamma, mask_weight=args.mask_weight) if weighted else {}
     batches = ds.batches(args.batch, np.random.default_rng(args.seed + 3), size=S, **drop)
     for _ in range(args.steps):
-        out = train_step(unet, vae, sched, opt, next(batches), generator=gen)
+        out = train_step(unet, vae, sched, opt, next(batches), generator=gen, **objective)
         losses.append(out["loss"])
     losses = [float(l) for l in torch.stack(losses).cpu()]
     D.synchronize()
@@ -106,13 +120,19 @@ def main():
     res = dict(bench="train_synthetic", steps=args.steps, batch=args.batch, lr=args.lr, size=S, eval_pages=E, eval_timesteps=list(EVAL_TIMESTEPS),
                finite=bool(np.isfinite(losses).all()),
                loss_first_tenth=round(float(np.mean(losses[:tenth])), 6), loss_last_tenth=round(float(np.mean(losses[-tenth:])), 6),
-               held_out_own_before=round(before[0], 6), held_out_rotated_before=round(before[1], 6),
-               held_out_own_after=round(after[0], 6), held_out_rotated_after=round(after[1], 6),
-               gap_before=round(before[1] - before[0], 6), gap_after=round(after[1] - after[0], 6),
+               held_out_own_before=round(before[0][0], 6), held_out_rotated_before=round(before[1][0], 6),
+               held_out_own_after=round(after[0][0], 6), held_out_rotated_after=round(after[1][0], 6),
+               gap_before=round(before[1][0] - before[0][0], 6), gap_after=round(after[1][0] - after[0][0], 6),
                ms_per_step_with_data=round(seconds / args.steps * 1e3, 2))
     if args.context_dropout > 0:
-        res.update(context_dropout=args.context_dropout, held_out_null_before=round(before[2], 6), held_out_null_after=round(after[2], 6),
-                   null_gap_before=round(before[2] - before[0], 6), null_gap_after=round(after[2] - after[0], 6))
+        res.update(context_dropout=args.context_dropout, held_out_null_before=round(before[2][0], 6), held_out_null_after=round(after[2][0], 6),
+                   null_gap_before=round(before[2][0] - before[0][0], 6), null_gap_after=round(after[2][0] - after[0][0], 6))
+    if weighted:
+        res.update(snr_gamma=args.snr_gamma, mask_weight=args.mask_weight)
+    for when, r in (("before", before), ("after", after)):
+        for i, ctx in enumerate(("own", "rotated", "null")[:len(r)]):
+            res[f"masked_{ctx}_{when}"], res[f"unmasked_{ctx}_{when}"] = round(r[i][1], 6), round(r[i][2], 6)
+        res[f"masked_gap_{when}"] = round(r[1][1] - r[0][1], 6)
     line = json.dumps(res)
     print(line)
     if args.out:
