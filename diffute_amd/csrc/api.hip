@@ -121,7 +121,7 @@ extern "C" int dmx_groupnorm_from_stats(const void* x0, int ldx0, const void* x1
   a.st0 = st0; a.st1 = x1 ? st1 : st0;
   return dmx_groupnorm_sums_launch(a, (hipStream_t)stream);
 }
-static HaloConvArgs halo_args(const dmx_halo_conv_desc* d) {
+HaloConvArgs dmx_halo_args(const dmx_halo_conv_desc* d) {
   HaloConvArgs a{};
   a.x0 = (const bf16*)d->x0; a.x1 = (const bf16*)d->x1; a.ldx0 = d->ldx0; a.ldx1 = d->ldx1; a.cx0 = d->x1 ? d->cx0 : d->Cin; a.Cin = d->Cin;
   a.B = d->B; a.H = d->H; a.W = d->W; a.gn = d->gn; a.silu = d->silu; a.groups = d->groups; a.eps = d->eps;
@@ -132,11 +132,13 @@ static HaloConvArgs halo_args(const dmx_halo_conv_desc* d) {
   a.force_split = d->force_split; a.force_bn = d->force_bn; a.force_waves = d->force_waves; a.dbg = d->dbg; a.timing = d->timing;
   return a;
 }
-extern "C" int dmx_conv3x3_gn_supported(const dmx_halo_conv_desc* d) { return d && dmx_conv_halo_supported(halo_args(d)) ? 1 : 0; }
-extern "C" size_t dmx_conv3x3_gn_workspace_bytes(const dmx_halo_conv_desc* d) { return d ? dmx_conv_halo_workspace_bytes(halo_args(d)) : 0; }
+// (each entry plans once: dmx_conv_halo_plan is host arithmetic)
+extern "C" int dmx_conv3x3_gn_supported(const dmx_halo_conv_desc* d) { return d && dmx_conv_halo_plan(dmx_halo_args(d), dmx_halo_env()).ok ? 1 : 0; }
+extern "C" size_t dmx_conv3x3_gn_workspace_bytes(const dmx_halo_conv_desc* d) { return d ? dmx_conv_halo_plan(dmx_halo_args(d), dmx_halo_env()).workspace_bytes : 0; }
 extern "C" int dmx_conv3x3_gn(const dmx_halo_conv_desc* d, void* workspace, size_t workspace_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(d && d->x0 && d->w && d->out, "conv3x3_gn: null argument");
-  return dmx_conv_halo_launch(halo_args(d), workspace, workspace_bytes, (hipStream_t)stream);
+  const HaloConvArgs a = dmx_halo_args(d);
+  return dmx_conv_halo_launch(a, dmx_conv_halo_plan(a, dmx_halo_env()), workspace, workspace_bytes, (hipStream_t)stream);
 }
 static SkinnyArgs skinny_args(const dmx_skinny_desc* d) {
   SkinnyArgs a{};

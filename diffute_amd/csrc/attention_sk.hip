@@ -286,7 +286,7 @@ extern "C" int dmx_set_attn_balanced(int mode) { const int old = g_attn_balanced
 int dmx_attention_balanced_slots(const AttnArgs& a) {
   if (!g_attn_balanced || !a.v || a.lse || a.Sq % 128 || a.B <= 0) return 0;
   const long long nqb = (long long)a.B * a.H * (a.Sq / 128), nt = (a.Skv + 63) / 64, T = nqb * nt;
-  const int ns = 3 * n_cus();                          // of the current device (conv_halo.hip)
+  const int ns = 3 * n_cus();                          // of the current device (exec.hip)
   if (T < ns) return 0;
   if (g_attn_balanced >= 2) return ns;
   // (with other streams sharing the CUs - dmx_set_exclusive_device(0): micro-batches, a collective next to the step - the slots of a launch are not all

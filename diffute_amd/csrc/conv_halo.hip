@@ -28,79 +28,22 @@
 //     next GroupNorm.
 #include "common.h"
 #include "kernels.h"
+#include "halo_tile.h"
 #include <stdio.h>
 #include <type_traits>
+#include <utility>
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
-int n_cus() {                                          // of the CURRENT device (the K-split plans need a tile's blocks co-resident on it)
-  static int n_cu[64] = {};
-  int dev = 0; (void)hipGetDevice(&dev);
-  int& n = n_cu[dev & 63];
-  if (!n) { (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); if (n <= 0) n = 256; }
-  return n;
-}
-
-// dmx_set_exclusive_device(0): other streams / other kernels may hold CUs while a launch of the library runs (micro-batches on several streams,
-// a collective on a side stream).  The in-kernel K-split exchange needs the S blocks of a tile co-resident - symmetric peers wait for each
-// other - so without the device to itself the planner takes no split: shapes that need one fall back to GroupNorm + the implicit GEMM.
-// (The stream-K GEMMs are not affected: an owner only ever waits for blocks dispatched AFTER it, which start as soon as any block retires.)
-int g_exclusive_device = 1;
-extern "C" int dmx_set_exclusive_device(int on) { const int old = g_exclusive_device; g_exclusive_device = on ? 1 : 0; dmx_plan_switch(DMX_SW_EXCLUSIVE, g_exclusive_device); return old; }
-int dmx_exclusive_device() { return g_exclusive_device; }
-extern "C" int dmx_get_exclusive_device(void) { return g_exclusive_device; }
-
 namespace {
 
-// x / d for x < 2^20, 2 <= d < 2^12 with magic = 2^32 / d + 1; d = 1: magic 0 (host: halo_magic)
+// x / d for x < 2^20, 2 <= d < 2^12 with magic = 2^32 / d + 1; d = 1: magic 0 (host: halo_magic of conv_halo_plan.hip)
 __device__ __forceinline__ int hb_div(int x, unsigned magic) { return magic ? (int)(((unsigned long long)(unsigned)x * magic) >> 32) : x; }
-static unsigned halo_magic(int d) { return d <= 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d + 1); }
 
-constexpr int HB_PATCH = 44032;            // patch buffer: 2752 pieces of 16 B (340 rows of 128 B, rounded up to whole 1-KB DMA instructions)
-
-// WMW = waves along the pixel axis: 4 -> 4 x 2 waves of 64-pixel x 16 NF-channel tiles (BN = 32 NF = 160 / 128 columns),
-//                                   8 -> 8 x 1 waves of 32-pixel x 16 NF-channel tiles (BN = 16 NF = 80 / 64 columns: twice the tiles - levels
-//                                        where the wider tile would need a K split, i.e. an exchange of fp32 slabs through memory)
-//   WNW = waves along the channel axis (1 or 2).  WMW x WNW = 8 waves: two-group ping-pong K loop; 16 waves (8 x 2, 32 x 16 NF wave tiles,
-//   <= 128 registers per lane, four waves per SIMD): lock step, one barrier per tap - what bounds the 8-wave loop is every wave's SERIAL
-//   non-MFMA work per tap (DMA issue, normalisation, addressing), and twice the waves halve it per wave at 1.55 x the LDS fragment bytes
-//   WS (warp-specialised; 4 x 1 compute waves of 64-pixel x 160 / 128-column tiles + four LOADER waves): the compute waves only read
-//   fragments and issue MFMAs, the loaders issue every LDS-DMA instruction and normalise the patches - one barrier per tap.  What bounds a
-//   ping-pong step is the DMA phase of a group (each LDS-DMA instruction holds its wave ~100 cycles; 6-7 per wave and tap plus the
-//   normalisation is longer than the partner's 640 cycles of MFMAs), and the 64 x 80 wave tiles read 144 KB of fragments per tap (88 % of
-//   the LDS bandwidth under the MFMAs); here the loaders have the whole tap for the same DMA work and the fragment reads are 112 KB
-template <int NF, int WMW, int WNW, bool WS_ = false> struct HaloLds {
-  static constexpr bool WS = WS_;
-  static constexpr int NCW = WMW * WNW;               // compute waves
-  static constexpr int NT = 64 * NCW + (WS ? 256 : 0);   // threads (WS: + four loader waves)
-  static constexpr int DNT = WS ? 256 : NT;           // threads that issue DMA / normalise (WS: the last 256 threads of the block)
-  static constexpr bool PP = !WS && (NCW == 8);       // two-group ping-pong (8 waves)
-  static constexpr int BN = WNW * 16 * NF;
-  static constexpr int MFR = 16 / WMW;                // 16-pixel fragments per wave
-  // TPS = taps per pipeline step: the narrow tiles have the LDS for TWO weight tiles per ring stage (2 x 10 KB = one stage of the
-  // 160-column tile): per step the same DMA / MFMA work as the wide tile with half the barriers, DMA-phase overheads and
-  // normalisation slots per FLOP - and twice the tiles, i.e. no K split (no fp32 slab exchange) at the 64 x 64 level
-  static constexpr int TPS = (WMW == 8 && WNW == 1) ? 2 : 1;
-  static constexpr int WTILE = BN * 128;              // one tap's [BN][64] weight tile
-  static constexpr int WSTAGE = TPS * WTILE;
-  // weight ring: 3 stages = prefetch distance 1 under the two-group ping-pong (stage (s - 1) % 3 is the partner's, s % 3 this wave's next).
-  // A 4-stage ring / distance 2 with a counted vmcnt was built for the tiles that have the LDS for it and measured SLOWER (64x64x320,
-  // 80 columns: 72 vs 62 us): what bounds a step is each wave's serial non-MFMA work, not the landing time of the tile (EXPERIMENTS.md)
-  static constexpr int NSTG = 3;
-  static constexpr int PATCH0 = NSTG * WSTAGE, PATCH1 = PATCH0 + HB_PATCH;
-  static constexpr int GB = PATCH1 + HB_PATCH;        // gamma | beta of a chunk, two 1-KB slots (lanes 32..63 of the DMA land in the second half)
-  static constexpr int COEF = GB + 2048;              // (a, s) of the 64 channels of a chunk, 512 B
-  static constexpr int GST = COEF + 512;              // (mean, rstd) of the 32 groups, 256 B (+ 256 spare)
-  static constexpr int DUMP = GST + 512;              // 1 KB the weight prefetch for the NEXT launches lands in (HaloConvArgs.pf)
-  static constexpr int TOTAL = DUMP + 1024;
-  // epilogue: fp32 staging of 128 rows + the statistics fold
-  static constexpr int LDT = BN + 4;
-  static constexpr int EPI_FOLD = 128 * LDT * 4;
-  static constexpr int OCP = BN / 8, RL = NT / OCP;
-  static constexpr int EPI_TOTAL = EPI_FOLD + RL * BN * 8;
-  static_assert(EPI_TOTAL <= TOTAL && TOTAL <= 163840, "LDS budget");
-};
+// f(integral_constant<int, 0>{}), ..., f(integral_constant<int, N - 1>{}) in order: the steps of a chunk's static schedule
+template <int N, class F, int... I> __device__ __forceinline__ void hb_static_for_(F& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F> __device__ __forceinline__ void hb_static_for(F& f) { hb_static_for_<N>(f, std::make_integer_sequence<int, N>{}); }
 
 // lgkmcnt of the wait in front of MFMA group g of the hand-scheduled stream of TAPS taps (see mma_stream): reads issued so far minus the
 // position of the last read the group needs.  Group g = (tap t, k-step kk, weight fragment j), gl = g % (2 NF).  Issue order:
@@ -128,8 +71,8 @@ constexpr int hb_wait(int NF, int MFR, int TAPS, int g, bool PF = false) {
 }
 
 template <int NF, int WMW, int WNW, bool WS = false>
-__global__ __launch_bounds__((HaloLds<NF, WMW, WNW, WS>::NT), ((HaloLds<NF, WMW, WNW, WS>::NT + 255) / 256)) void dmx_conv_halo_kernel(const HaloConvArgs p) {
-  typedef HaloLds<NF, WMW, WNW, WS> L;
+__global__ __launch_bounds__((HaloTile<NF, WMW, WNW, WS>::NT), ((HaloTile<NF, WMW, WNW, WS>::NT + 255) / 256)) void dmx_conv_halo_kernel(const HaloConvArgs p) {
+  typedef HaloTile<NF, WMW, WNW, WS> L;
   constexpr int BN = L::BN, WSTAGE = L::WSTAGE, WTILE = L::WTILE, TPS = L::TPS, MFR = L::MFR, NSTG = L::NSTG, HB_NT = L::NT, DNT = L::DNT, NCW = L::NCW;
   constexpr bool PP = L::PP;
   constexpr int PD = PP ? 1 : 2;                       // prefetch distance of the weight tiles (taps): the ping-pong keeps one stage for the partner group
@@ -380,7 +323,7 @@ __global__ __launch_bounds__((HaloLds<NF, WMW, WNW, WS>::NT), ((HaloLds<NF, WMW,
     }
     __builtin_amdgcn_s_setprio(0);
   };
-  auto mma_post = [&](const unsigned* xa, unsigned wbase, auto&&) { mma_stream(std::integral_constant<int, 1>{}, xa, &wbase, std::false_type{}); };
+  auto mma_post = [&](const unsigned* xa, unsigned wbase) { mma_stream(std::integral_constant<int, 1>{}, xa, &wbase, std::false_type{}); };
   auto xa_main = [&](int pb, int tapoff, unsigned* xa) {
     int pr = xrow0;
     asm volatile("" : "+v"(pr));                       // (the tap addresses are loop-invariant: hoisted they would live across the whole K loop)
@@ -618,8 +561,7 @@ __global__ __launch_bounds__((HaloLds<NF, WMW, WNW, WS>::NT), ((HaloLds<NF, WMW,
       HB_STAMP(pa_wy)
       ++rs;
     };
-    step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{}); step(std::integral_constant<int, 2>{});
-    step(std::integral_constant<int, 3>{}); step(std::integral_constant<int, 4>{});
+    hb_static_for<5>(step);
     gstep += 9; ++seq;
     cur = next;
   }
@@ -661,8 +603,7 @@ __global__ __launch_bounds__((HaloLds<NF, WMW, WNW, WS>::NT), ((HaloLds<NF, WMW,
         if constexpr (s == 2) { issue_piece(dn, pbn, 3); issue_piece(dn, pbn, 4); issue_piece(dn, pbn, 5); }
         static_assert(!PP || NPP == 6, "ping-pong schedule: six patch pieces per thread");
       }
-      int nw = 0;                                        // (patch pieces first, the weight tile last: the counted wait below leaves only IT in flight)
-      if (!(DBG & 2)) { const long kn = koff_of(g + PD); if (kn >= 0) nw = issue_w(kn, ((g + PD) % NSTG) * WSTAGE); }
+      if (!(DBG & 2)) { const long kn = koff_of(g + PD); if (kn >= 0) issue_w(kn, ((g + PD) % NSTG) * WSTAGE); }      // (patch pieces first, the weight tile last)
       if constexpr (s == 2) { if (dn.mode == 1) coef_table(next); }
       if constexpr (s >= 3) { if (dn.mode == 1 && !(DBG & 4)) norm_piece(pbn, s - 3); }
       unsigned xa[MFR];
@@ -674,16 +615,14 @@ __global__ __launch_bounds__((HaloLds<NF, WMW, WNW, WS>::NT), ((HaloLds<NF, WMW,
       HB_STAMP(pa_wx)
       // ---- MFMA phase.  (The normalisation arithmetic as per-group slices in here - loads in the DMA phase, one element after each
       // MFMA group - was built and measured slower, 65 vs 60 us: one wave per SIMD is in this phase, so VALU between its MFMAs delays them)
-      if (active && !(DBG & 1)) mma_post(xa, lds0 + (g % NSTG) * WSTAGE, [&](auto, const int) {});
+      if (active && !(DBG & 1)) mma_post(xa, lds0 + (g % NSTG) * WSTAGE);
       // this wave's pieces of the NEXT tap's weight tile (requested a DMA + an MFMA phase ago) and everything older have landed
-      wait_vm(0); (void)nw;
+      wait_vm(0);
       HB_STAMP(pa_mma)
       if (!(DBG & 16)) __builtin_amdgcn_s_barrier();
       HB_STAMP(pa_wy)
     };
-    step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{}); step(std::integral_constant<int, 2>{});
-    step(std::integral_constant<int, 3>{}); step(std::integral_constant<int, 4>{}); step(std::integral_constant<int, 5>{});
-    step(std::integral_constant<int, 6>{}); step(std::integral_constant<int, 7>{}); step(std::integral_constant<int, 8>{});
+    hb_static_for<9>(step);
     gstep += 9; ++seq;
     cur = next;
   }
@@ -694,14 +633,13 @@ __global__ __launch_bounds__((HaloLds<NF, WMW, WNW, WS>::NT), ((HaloLds<NF, WMW,
     const int pb = (seq & 1) ? L::PATCH1 : L::PATCH0, pbn = (seq & 1) ? L::PATCH0 : L::PATCH1;
     const PDesc dn = pdesc(next);
     issue_piece(dn, pbn, 0); issue_piece(dn, pbn, 1); issue_piece(dn, pbn, 2); issue_piece(dn, pbn, 3);
-    int nw = 0;
-    { const long kn = koff_of(gstep + PD); if (kn >= 0) nw = issue_w(kn, ((gstep + PD) % NSTG) * WSTAGE); }
+    { const long kn = koff_of(gstep + PD); if (kn >= 0) issue_w(kn, ((gstep + PD) % NSTG) * WSTAGE); }
     unsigned xa[MFR];
     xa_sc(pb, xa);
     mma_pre(xa);
     __builtin_amdgcn_s_barrier();
-    mma_post(xa, lds0 + (gstep % NSTG) * WSTAGE, [&](auto, const int) {});
-    wait_vm(0); (void)nw;                              // (the next shortcut patch and weight tile have landed)
+    mma_post(xa, lds0 + (gstep % NSTG) * WSTAGE);
+    wait_vm(0);                                        // (the next shortcut patch and weight tile have landed)
     __builtin_amdgcn_s_barrier();
     gstep += 1; ++seq;
     cur = next;                                        // (-1 ends the loop)
@@ -745,9 +683,7 @@ __global__ __launch_bounds__((HaloLds<NF, WMW, WNW, WS>::NT), ((HaloLds<NF, WMW,
         wait_vm(n);                                      // everything requested before this step has landed
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       };
-      step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{}); step(std::integral_constant<int, 2>{});
-      step(std::integral_constant<int, 3>{}); step(std::integral_constant<int, 4>{}); step(std::integral_constant<int, 5>{});
-      step(std::integral_constant<int, 6>{}); step(std::integral_constant<int, 7>{}); step(std::integral_constant<int, 8>{});
+      hb_static_for<9>(step);
       gstep += 9; ++seq;
       cur = next;
     }
@@ -788,9 +724,7 @@ __global__ __launch_bounds__((HaloLds<NF, WMW, WNW, WS>::NT), ((HaloLds<NF, WMW,
           mma_stream(std::integral_constant<int, 1>{}, xa, &wb1, std::integral_constant<bool, (s < 8)>{});
         }
       };
-      step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{}); step(std::integral_constant<int, 2>{});
-      step(std::integral_constant<int, 3>{}); step(std::integral_constant<int, 4>{}); step(std::integral_constant<int, 5>{});
-      step(std::integral_constant<int, 6>{}); step(std::integral_constant<int, 7>{}); step(std::integral_constant<int, 8>{});
+      hb_static_for<9>(step);
       gstep += 9; ++seq;
       cur = next;
     }
@@ -1061,174 +995,43 @@ __global__ __launch_bounds__(512) void dmx_colstats_kernel(const bf16* x, int ld
 }
 
 
-// Plan: tile geometry, column width BN (160 / 128: 4 x 2 waves; 80 / 64: 8 x 1 waves) and K split.  A K split costs an exchange of fp32
-// slabs through memory ((S - 1) / S x 256 x BN x 4 bytes per block, written and read back) and the co-residency of a tile's blocks, so the
-// plan takes the narrow tiles where they make the split unnecessary or smaller; with tiles to spare the wide tile wins (twice the work per
-// weight byte and per barrier).  Costs in us, fitted on scripts/attic/halo_probe.py.
-int g_halo_peers = 1;
-int g_halo_ws = 1;                                     // dmx_set_halo_ws: 0 = the planner never takes the warp-specialised instances (A/B aid)
-struct HaloPlan { int TH, TW, nf, wmw, bn, splits, waves; };
-HaloPlan halo_plan(const HaloConvArgs& a) {
-  HaloPlan P{0, 0, 0, 0, 0, 0, 8};
-  if (a.W % 32 == 0 && a.H % 8 == 0) { P.TW = 32; P.TH = 8; }
-  else if (a.W % 16 == 0 && a.H % 16 == 0) { P.TW = 16; P.TH = 16; }
-  else return P;
-  const long tiles_m = (long)a.B * (a.H / P.TH) * (a.W / P.TW);
-  const int T = 9 * (a.Cin / 64) + a.Csc / 64;
-  double best = 1e300;
-  const int cand[4][3] = {{5, 4, 160}, {4, 4, 128}, {5, 8, 80}, {4, 8, 64}};
-  for (int c = 0; c < 4; ++c) {
-    const int bn = cand[c][2];
-    if (a.N % bn) continue;
-    if (a.force_bn && a.force_bn != bn) continue;
-    const long tiles = tiles_m * (a.N / bn);
-    for (int s = 1; s <= 8; s *= 2) {
-      if (a.force_split && s != a.force_split) continue;
-      if (s > 1 && (!g_exclusive_device || tiles * s > n_cus() || T / s < 3)) continue;
-      const double rounds = (double)((tiles * s + n_cus() - 1) / n_cus());
-      const double step = bn >= 128 ? 1.45 : 0.96;                         // us per tap and block (measured, B = 4 64x64x320: K = 2880 / 5760 / 8640)
-      double cost = rounds * ((double)((T + s - 1) / s) * step + 13.0);    // + prologue / epilogue of a block
-      if (s > 1) cost += 3.5 + 2.0 * (double)(s - 1) * bn / 160.0;         // publish + wait + the peers' slabs
-      if (cost < best) { best = cost; P.nf = cand[c][0]; P.wmw = cand[c][1]; P.bn = bn; P.splits = s; }
-    }
-  }
-  // waves: 8 = two-group ping-pong, 4 = warp-specialised (4 compute + 4 loader waves; the wide tiles only).  (16-wave lock-step instances
-  // of the wide tiles were built in round 4 and measured slower than the ping-pong - 68 / 95 / 130 vs 60 / 87 / 118 us - and removed.)
-  // Measured (B = 4, stand-alone incl. GroupNorm, us; ping-pong / 4 + 4 / 8 + 4): 64x64x320 K = 2880 / 5760 / 8640 (two-way splits): 62.2 /
-  // 85.3 / 113.1 - 61.0 / 81.7 / 107.0 - 62.6 / 84.2 / 111.1; 32x32x640 K = 5760 (four-way): 59.5 - 64.3 - 66.9; 16x16x1280 K = 11520
-  // (eight-way): 58.8 - 70.0 - 77.6: the warp-specialised K loop is ~10 % faster per tap (1.02 vs 1.13 us), its epilogue with four / eight
-  // slabs per row in flight has fewer registers to hide them in -> 4 + 4 up to two-way splits, the ping-pong beyond
-  P.waves = 8;
-#ifndef DMX_F16
-  // (bf16 build only: in the fp16 build the compiler spills an accumulator of the 160-column instance INSIDE the tap loop, which the
-  // asm MFMAs make a correctness bug - non-deterministic results at 768 px, EXPERIMENTS.md round 4 item 1b; tests/test_build_cpu.py
-  // checks the ISA of both builds)
-  if (P.bn >= 128 && P.splits <= 2 && g_halo_ws) P.waves = 4;
-  if (P.bn >= 128 && (a.force_waves == 4 || a.force_waves == 12 || a.force_waves == 8)) P.waves = a.force_waves;
-#else
-  if (a.force_waves == 8) P.waves = 8;
-#endif
-  if (a.force_waves && a.force_waves != P.waves) P.splits = 0;
-  return P;
+template <int NF, int WMW, int WNW, bool WS> int halo_launch_(const HaloConvArgs& a, const HaloPlan& P, const char* symbol, hipStream_t stream) {
+  DMX_LDS_OPT_IN((dmx_conv_halo_kernel<NF, WMW, WNW, WS>), (HaloTile<NF, WMW, WNW, WS>::TOTAL));
+  dmx_profile_note_symbol(symbol);
+  hipLaunchKernelGGL((dmx_conv_halo_kernel<NF, WMW, WNW, WS>), dim3(P.blocks), dim3(P.threads), P.lds_bytes, stream, a);      // (the instance's NT and TOTAL)
+  return dmx_check_launch("dmx_conv_halo_kernel");
 }
 
 }  // namespace
 
-// what the model executors ask: the fused launch is at least as fast IN SITU as GroupNorm + the implicit-GEMM conv (+ its split-K reduce).
-// Measured per shape inside the 50-step pass (B = 4; halo incl. GroupNorm vs conv + reduce + GroupNorm): 64x64 level 61 vs 69, 87 vs 105,
-// 119 vs 129 us; 32x32 level 63 vs 66, 89 vs 98, 124 vs 125; 16x16 level 64 vs 61, 85 vs 77, 48 vs 44 - the blocks of the deep levels
-// are 8-way K splits whose fp32 slab exchange costs what the fusion saves.
-// dmx_set_halo_peers: 0 = round-5 dealing and write-through slabs everywhere (A/B and the tests' second opinion); 1 = a tile's K-split peers on one XCD
-extern "C" int dmx_set_halo_peers(int on) { const int old = g_halo_peers; g_halo_peers = on ? 1 : 0; dmx_plan_switch(DMX_SW_HALO_PEERS, g_halo_peers); return old; }
-extern "C" int dmx_set_halo_ws(int on) { const int old = g_halo_ws; g_halo_ws = on; dmx_plan_switch(DMX_SW_HALO_WS, on); return old; }
-// ONE place for "could a fused GroupNorm -> conv launch consume statistics records of an H x W tensor": the tile geometries of halo_plan and the
-// level rule of dmx_conv_halo_pays.  The executors ask this before they spend a statistics pass / a statistics epilogue on a tensor
-// (Exec::ensure_stats, Exec::chain_stats); `everywhere` = dmx_set_halo_conv(2): wherever the kernel takes the problem.
-bool dmx_conv_halo_wants_stats(int H, int W, bool everywhere) {
-  const bool geometry = (W % 32 == 0 && H % 8 == 0) || (W % 16 == 0 && H % 16 == 0);
-  return geometry && (everywhere || (long)H * W >= 1024);
-}
-bool dmx_conv_halo_pays(const HaloConvArgs& a) {
-  if (!dmx_conv_halo_supported(a)) return false;
-  return dmx_conv_halo_wants_stats(a.H, a.W, false);
-}
-
-static long halo_blocks(const HaloConvArgs& a, const HaloPlan& P);
-// the block decode divides by multiplication (hb_div: magic = 2^32 / d + 1), exact only while x * d < 2^32 for every dividend x
-// (block index, channel, patch row) and divisor d of the decode
-static bool halo_decode_ok(const HaloConvArgs& a, const HaloPlan& P) {
-  const long tiles_x = a.W / P.TW, tiles_img = tiles_x * (a.H / P.TH), tiles_m = (long)a.B * tiles_img, ncombo = (long)(a.N / P.bn) * P.splits;
-  long dmax = tiles_m; for (long d : {ncombo, tiles_img, tiles_x, (long)P.TW + 2, (long)(a.gn ? a.Cin / a.groups : 1)}) if (d > dmax) dmax = d;
-  long xmax = halo_blocks(a, P); for (long x : {(long)a.Cin, (long)(P.TH + 2) * (P.TW + 2) * 8}) if (x > xmax) xmax = x;
-  return xmax < (1l << 31) && dmax < (1l << 31) && (unsigned long long)xmax * (unsigned long long)dmax < (1ull << 32);
-}
-
-bool dmx_conv_halo_supported(const HaloConvArgs& a) {
-  if (a.Cin <= 0 || a.Cin % 64 || a.cx0 % 64 || a.cx0 > a.Cin || a.Csc % 64 || (a.Csc && a.cs0 % 64) || a.N % 8 || a.ldo % 8) return false;
-  if (a.ldx0 % 8 || (a.x1 && a.ldx1 % 8) || a.ldw % 8 || (a.res && a.ldres % 8)) return false;
-  if (a.gn && (a.groups != 32 || a.Cin % a.groups)) return false;
-  if (a.force_split && (a.force_split & (a.force_split - 1) || a.force_split > 8)) return false;
-  const HaloPlan P = halo_plan(a);
-  return P.splits > 0 && halo_decode_ok(a, P);         // (larger problems: GroupNorm + the implicit GEMM, whose decode is 64-bit)
-}
-
-static long halo_blocks(const HaloConvArgs& a, const HaloPlan& P) {
-  return (long)a.B * (a.H / P.TH) * (a.W / P.TW) * (a.N / P.bn) * P.splits;
-}
-
-// one completion flag per block + one XCC-id word per block (peers_local)
-int dmx_conv_halo_flag_count(const HaloConvArgs& a) {
-  const HaloPlan P = halo_plan(a);
-  return P.splits > 1 ? 2 * (int)halo_blocks(a, P) : 0;
-}
-
-static size_t halo_flag_bytes(int n) { return align_up((size_t)2 * n * sizeof(int), 256); }
-
-size_t dmx_conv_halo_workspace_bytes(const HaloConvArgs& a) {
-  const HaloPlan P = halo_plan(a);
-  if (P.splits <= 1) return 0;
-  const long n = halo_blocks(a, P);
-  return halo_flag_bytes((int)n) + (size_t)n * 256 * P.bn * sizeof(float);
-}
-
-template <int NF, int WMW, int WNW, bool WS = false> static int halo_launch_(const HaloConvArgs& a, int blocks, hipStream_t stream) {
-  DMX_LDS_OPT_IN((dmx_conv_halo_kernel<NF, WMW, WNW, WS>), (HaloLds<NF, WMW, WNW, WS>::TOTAL));
-  {
-    char sym[112];
-    snprintf(sym, sizeof(sym), "void (anonymous namespace)::dmx_conv_halo_kernel<%d, %d, %d, %s>(HaloConvArgs)", NF, WMW, WNW, WS ? "true" : "false");
-    dmx_profile_note_symbol(sym);
-  }
-  hipLaunchKernelGGL((dmx_conv_halo_kernel<NF, WMW, WNW, WS>), dim3(blocks), dim3(HaloLds<NF, WMW, WNW, WS>::NT), (HaloLds<NF, WMW, WNW, WS>::TOTAL), stream, a);
-  return dmx_check_launch("dmx_conv_halo_kernel");
-}
-
-int dmx_conv_halo_launch(HaloConvArgs a, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  DMX_REQUIRE(a.x0 && a.w && a.out, "conv_halo: null argument");
-  DMX_REQUIRE(dmx_conv_halo_supported(a), "conv_halo: unsupported problem (H=%d W=%d Cin=%d cx0=%d Csc=%d N=%d split=%d bn=%d)", a.H, a.W, a.Cin, a.cx0, a.Csc, a.N, a.force_split, a.force_bn);
-  if (a.gn) DMX_REQUIRE(a.st0 && a.gamma && a.beta && (a.cx0 == a.Cin || a.st1), "conv_halo: the fused GroupNorm needs statistics records, gamma and beta");
-  if (a.Csc) DMX_REQUIRE(a.s0 && (a.cs0 == a.Csc || a.s1), "conv_halo: the shortcut segment needs its source tensor(s)");
-  DMX_REQUIRE(a.ldw >= 9 * a.Cin + a.Csc, "conv_halo: weight rows shorter than K");
+// P = dmx_conv_halo_plan(a, dmx_halo_env()): the caller plans once, sizes flags and workspace from the plan and hands it over
+int dmx_conv_halo_launch(HaloConvArgs a, const HaloPlan& P, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (const int rc = dmx_conv_halo_check(a, P)) return rc;
   if (!a.x1) { a.x1 = a.x0; a.ldx1 = a.ldx0; }
   if (!a.s1) { a.s1 = a.s0; a.lds1 = a.lds0; }
-  int rc = dmx_zero_page(&a.zeros);
-  if (rc) return rc;
+  if (const int rc = dmx_zero_page(&a.zeros)) return rc;
   a.err = dmx_dev_err_words();
-  const HaloPlan P = halo_plan(a);
-  a.TH = P.TH; a.TW = P.TW; a.splits = P.splits;
-  const int blocks = (int)halo_blocks(a, P);
-  a.tiles_x = a.W / P.TW; a.tiles_img = a.tiles_x * (a.H / P.TH); a.tiles_m = a.B * a.tiles_img; a.ncombo = (a.N / P.bn) * P.splits;
-  a.cpg = a.gn ? a.Cin / a.groups : 1;
-  DMX_REQUIRE(halo_decode_ok(a, P), "conv_halo: problem too large for the block decode (%d blocks, %d pixel tiles)", blocks, a.tiles_m);
-  a.mg_tiles_x = halo_magic(a.tiles_x); a.mg_tiles_img = halo_magic(a.tiles_img); a.mg_tiles_m = halo_magic(a.tiles_m);
-  a.mg_ncombo = halo_magic(a.ncombo); a.mg_pw = halo_magic(P.TW + 2); a.mg_cpg = halo_magic(a.cpg);
-  // block -> XCD dealing: weights-major when the weight slab is the larger stream of an XCD, pixel-tile-major otherwise
-  {
-    const double wbytes = 2.0 * a.N * (9.0 * a.Cin + a.Csc), abytes = 2.0 * a.B * a.H * a.W * (double)(a.Cin + a.Csc) * 1.33;
-    const int combos = (a.N / P.bn) * P.splits;
-    // weights-major: every XCD reads its combos' weights once, the activations combos / 8 .. combos times; tile-major: the reverse
-    a.xcd_tile_major = (abytes * (combos >= 8 ? combos / 8.0 : 1.0) + wbytes > abytes + wbytes * 8.0) ? 1 : 0;
-  }
-  // the S blocks of a tile on one XCD: r is the fastest index of the decode and an XCD's share of the grid (blocks / 8 consecutive Lb) holds whole tiles
-  a.peers_local = (g_halo_peers && a.splits > 1 && blocks % 8 == 0 && (blocks / 8) % a.splits == 0) ? 1 : 0;
-  if (a.splits > 1) {
-    const size_t fb = halo_flag_bytes(blocks), need = fb + (size_t)blocks * 256 * P.bn * sizeof(float);
-    if (!workspace || workspace_bytes < need) { dmx_set_error("conv_halo: the K split needs %zu bytes of workspace, got %zu", need, workspace_bytes); return DMX_ERR_WORKSPACE; }
-    a.slabs = (float*)((char*)workspace + fb);
-    if (!a.flags) { a.flags = (int*)workspace; if (const int zr = dmx_zero16_launch(a.flags, fb, stream)) return zr; }      // a kernel node, not a memset node: exec.hip Exec::zero_pool
+  a.TH = P.TH; a.TW = P.TW; a.splits = P.splits; a.xcd_tile_major = P.xcd_tile_major; a.peers_local = P.peers_local;
+  a.tiles_x = P.tiles_x; a.tiles_img = P.tiles_img; a.tiles_m = P.tiles_m; a.ncombo = P.ncombo; a.cpg = P.cpg;
+  a.mg_tiles_x = P.mg_tiles_x; a.mg_tiles_img = P.mg_tiles_img; a.mg_tiles_m = P.mg_tiles_m; a.mg_ncombo = P.mg_ncombo; a.mg_pw = P.mg_pw; a.mg_cpg = P.mg_cpg;
+  if (P.splits > 1) {
+    if (!workspace || workspace_bytes < P.workspace_bytes) { dmx_set_error("conv_halo: the K split needs %zu bytes of workspace, got %zu", P.workspace_bytes, workspace_bytes); return DMX_ERR_WORKSPACE; }
+    a.slabs = (float*)((char*)workspace + P.flag_bytes);
+    if (!a.flags) { a.flags = (int*)workspace; if (const int zr = dmx_zero16_launch(a.flags, P.flag_bytes, stream)) return zr; }      // a kernel node, not a memset node: exec.hip Exec::zero_pool
   }
   const double flops = 2.0 * a.B * a.H * a.W * (double)a.N * (9.0 * a.Cin + a.Csc);
   const double bytes = 2.0 * ((double)a.B * a.H * a.W * (a.Cin + a.Csc + a.N) + (double)a.N * (9.0 * a.Cin + a.Csc));
   char tag[96];
   snprintf(tag, sizeof(tag), "M=%d N=%d K=%d halo gn=%d bn=%d sk=%d", a.B * a.H * a.W, a.N, 9 * a.Cin + a.Csc, a.gn, P.bn, a.splits);
   ProfScope ps(PROF_HALO, stream, flops, bytes, tag);
-#ifndef DMX_F16
-  if (P.waves == 4) return P.nf == 5 ? halo_launch_<10, 4, 1, true>(a, blocks, stream) : halo_launch_<8, 4, 1, true>(a, blocks, stream);
-  if (P.waves == 12) return P.nf == 5 ? halo_launch_<5, 4, 2, true>(a, blocks, stream) : halo_launch_<4, 4, 2, true>(a, blocks, stream);
-#endif
-  if (P.nf == 5 && P.wmw == 4) return halo_launch_<5, 4, 2>(a, blocks, stream);
-  if (P.nf == 4 && P.wmw == 4) return halo_launch_<4, 4, 2>(a, blocks, stream);
-  if (P.nf == 5 && P.wmw == 8) return halo_launch_<5, 8, 1>(a, blocks, stream);
-  return halo_launch_<4, 8, 1>(a, blocks, stream);
+  switch (P.inst) {                                    // the instances this build has (halo_tile.h)
+#define DMX_HALO_CASE_(id, bn, waves, NF, WMW, WNW, WS, builds, what) \
+    DMX_HALO_IN_BUILD_##builds(case id: return halo_launch_<NF, WMW, WNW, WS>(a, P, "void (anonymous namespace)::dmx_conv_halo_kernel<" #NF ", " #WMW ", " #WNW ", " #WS ">(HaloConvArgs)", stream);)
+    DMX_HALO_INSTANCES(DMX_HALO_CASE_)
+#undef DMX_HALO_CASE_
+  }
+  dmx_set_error("conv_halo: plan names instance %d, which this build does not have", P.inst);
+  return DMX_ERR_ARG;
 }
 
 int dmx_colstats_launch(const bf16* x, int ldx, int B, int HW, int C, long long* st, hipStream_t stream) {

@@ -75,6 +75,24 @@ extern "C" int dmx_plan_epoch(void) {
   return (int)(h & 0x7fffffffu);
 }
 
+// --------------------------------------------------------------------------- the device as the planners see it
+int n_cus() {                                          // of the CURRENT device (the K-split plans need a tile's blocks co-resident on it)
+  static int n_cu[64] = {};
+  int dev = 0; (void)hipGetDevice(&dev);
+  int& n = n_cu[dev & 63];
+  if (!n) { (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); if (n <= 0) n = 256; }
+  return n;
+}
+
+// dmx_set_exclusive_device(0): other streams / other kernels may hold CUs while a launch of the library runs (micro-batches on several streams,
+// a collective on a side stream).  The in-kernel K-split exchange of the halo conv needs the S blocks of a tile co-resident - symmetric peers wait
+// for each other - so without the device to itself its planner takes no split: shapes that need one fall back to GroupNorm + the implicit GEMM.
+// (The stream-K GEMMs are not affected: an owner only ever waits for blocks dispatched AFTER it, which start as soon as any block retires.)
+static int g_exclusive_device = 1;
+extern "C" int dmx_set_exclusive_device(int on) { const int old = g_exclusive_device; g_exclusive_device = on ? 1 : 0; dmx_plan_switch(DMX_SW_EXCLUSIVE, g_exclusive_device); return old; }
+int dmx_exclusive_device() { return g_exclusive_device; }
+extern "C" int dmx_get_exclusive_device(void) { return g_exclusive_device; }
+
 // --------------------------------------------------------------------------- profiler
 namespace {
 struct ProfRec { hipEvent_t a, b; int cls; double flops, bytes; char tag[96]; char sym[112]; };
@@ -480,6 +498,7 @@ void Exec::ensure_stats(Tn& t) {
 
 Tn Exec::conv_gn(const Tn& x0, const Tn* x1, const float* gamma, const float* beta, int groups, float eps, const bf16* w, int Cout, const ConvOpts& o) {
   HaloConvArgs a{};
+  HaloPlan P{};
   bool fused = !f32 && dmx_halo_conv_enabled() && o.ksize == 3 && o.stride == 1 && o.pad == 1 && !o.ups && !o.out_f32 && x0.cst && (!x1 || x1->cst);
   if (fused) {
     a.x0 = x0.p; a.ldx0 = x0.ld; a.cx0 = x0.C; a.Cin = x0.C + (x1 ? x1->C : 0);
@@ -494,7 +513,8 @@ Tn Exec::conv_gn(const Tn& x0, const Tn* x1, const float* gamma, const float* be
     a.bias = o.bias; a.rowbias = o.rowbias; a.ldrb = o.ldrb;
     if (o.res) { a.res = o.res->p; a.ldres = o.res->ld; }
     a.ldo = Cout;
-    fused = g_halo_conv > 1 ? dmx_conv_halo_supported(a) : dmx_conv_halo_pays(a);      // (dmx_set_halo_conv(2): wherever the kernel runs - tests, A/B)
+    P = dmx_conv_halo_plan(a, dmx_halo_env());           // the ONE plan of this conv (dry runs too): supported, flags, workspace, launch
+    fused = P.ok && (g_halo_conv > 1 || dmx_conv_halo_wants_stats(a.H, a.W, false));     // (dmx_set_halo_conv(2): wherever the kernel runs - tests, A/B; else where it pays)
   }
   if (!fused) {
     Tn t = groupnorm(x0, x1, gamma, beta, groups, eps, true);
@@ -506,21 +526,19 @@ Tn Exec::conv_gn(const Tn& x0, const Tn* x1, const float* gamma, const float* be
   Tn y = make(x0.B, x0.H, x0.W, Cout);
   a.out = y.p;
   if (o.stats && g_gn_producer_stats) { a.colstats = stat_slice(x0.B, Cout); y.cst = a.colstats; }
-  const int nflags = dmx_conv_halo_flag_count(a);
-  if (nflags) {                                        // one zeroed int per block from the pool the stream-K GEMMs use (zeroed once per forward)
+  if (P.flag_count) {                                  // one zeroed int per block from the pool the stream-K GEMMs use (zeroed once per forward)
     constexpr size_t POOL = 64 * 1024;
     if (!flag_pool) {
       flag_pool = (int*)raw(POOL * sizeof(int)); flag_cap = POOL; flag_used = 0;
       if (!zero_pool(flag_pool, POOL * sizeof(int), 2)) return y;
     }
-    const size_t n = align_up((size_t)nflags, 64);
+    const size_t n = align_up((size_t)P.flag_count, 64);
     if (flag_used + n <= flag_cap) { a.flags = flag_pool + flag_used; flag_used += n; }   // else: the launcher zeroes a slice of its own workspace
   }
-  const size_t wsb = dmx_conv_halo_workspace_bytes(a);
-  void* wsp = wsb ? raw(wsb) : nullptr;
+  void* wsp = P.workspace_bytes ? raw(P.workspace_bytes) : nullptr;
   note(a.w, (long)a.N * a.ldw * 2);
   peek(a.pf, a.pf_bytes, 2);
-  if (!dry && !rc) rc = dmx_conv_halo_launch(a, wsp, wsb, stream);
+  if (!dry && !rc) rc = dmx_conv_halo_launch(a, P, wsp, P.workspace_bytes, stream);
   if (wsp) ws.release(wsp);
   return y;
 }

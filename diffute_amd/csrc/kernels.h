@@ -9,12 +9,12 @@
 enum ProfClass { PROF_GEMM128 = 0, PROF_GEMM64 = 1, PROF_SPLITK = 2, PROF_ATTN = 3, PROF_GNORM = 4, PROF_LNORM = 5,
                  PROF_OTHER = 6, PROF_GEMM256 = 7, PROF_WGRAD = 8, PROF_GEMM256WS = 9,
                  PROF_GEMM_CFG0 = 10 /* one class per GEMM tile config (template instance): 10 + plan id */, PROF_XFCHAIN = 26 /* xf_chain.hip */, PROF_HALO = 27 /* conv_halo.hip */, PROF_SKINNY = 28 /* skinny.hip */, PROF_NCLASS = 29 };
-int n_cus();                                           // compute units of the CURRENT device (conv_halo.hip)
+int n_cus();                                           // compute units of the CURRENT device (exec.hip)
 // exec.hip: the plan signature (key of captured graphs / cached workspace sizes): every plan-changing switch records its value
 enum DmxPlanSwitch { DMX_SW_EXCLUSIVE = 0, DMX_SW_GN_STATS, DMX_SW_DEFER, DMX_SW_HALO, DMX_SW_PREFETCH, DMX_SW_XF_CHAIN, DMX_SW_HALO_WS, DMX_SW_OVERRIDES, DMX_SW_SKINNY, DMX_SW_HALO_PEERS, DMX_SW_ATTN_BALANCED, DMX_SW_FF_FOLD, DMX_SW_COUNT };
 void dmx_plan_switch(int slot, int value);
 void dmx_plan_epoch_bump();                            // (dmx_gemm_plan_override: a counter)
-int dmx_exclusive_device();                            // dmx_set_exclusive_device (conv_halo.hip): 0 = plans that need co-resident blocks are off
+int dmx_exclusive_device();                            // dmx_set_exclusive_device (exec.hip): 0 = plans that need co-resident blocks are off
 void dmx_profile_note_symbol(const char* sym);         // kernel symbol of the launch inside the innermost open ProfScope (exec.hip)
 struct ProfScope {
   ProfScope(ProfClass c, hipStream_t s, double flops, double bytes, const char* tag = nullptr);
@@ -103,7 +103,7 @@ int dmx_ln_fold_launch(const bf16* w_raw, bf16* w_out, const float* gamma, const
 int dmx_compose_linear_launch(const bf16* wpo, const bf16* wf2, const float* bf2, const float* bpo, bf16* w_out, float* b_out, int C, int K, hipStream_t stream);
 bool dmx_ff_fold_enabled();                            // dmx_set_ff_fold (exec.hip)
 
-// ------------------------------------------------------------------ conv_halo.hip
+// ------------------------------------------------------------------ conv_halo.hip, conv_halo_plan.hip
 // 3x3 stride-1 pad-1 convolution with a HALO input tile staged once per 64-channel chunk in LDS (the nine taps are shifted LDS
 // fragment reads; only the weight tiles stream) and the preceding GroupNorm(+SiLU) applied to the staged tile in place, from the
 // per-(sample, channel) statistics its producer(s) emitted (DmxStat below).  ResnetBlock2D = [GN -> SiLU -> conv3x3] x 2 becomes two launches.
@@ -126,20 +126,36 @@ struct HaloConvArgs {
   int force_waves;                                   // 0 = automatic; 8 = two-group ping-pong; 4 / 12 = warp-specialised, 4 compute + 4 / 8 loader waves (160 / 128-column tiles, bf16 build)
   int dbg; long long* timing;                        // measurement aids (0 / null in the product path)
   const void* pf[2]; int pf_bytes[2];                // optional: byte ranges (the next launches' weights) the blocks touch at their start (Exec::peek)
-  // filled by the launcher
+  // filled by the launcher: the plan's fields (HaloPlan below), the workspace pointers, the zero page and the error words
   int TH, TW, splits, xcd_tile_major; float* slabs; int* flags; const bf16* zeros; int* err;      // err: dmx_dev_err_words() (set by the launcher)
-  int peers_local;          // launcher: 1 = the S blocks of a tile are dealt to ONE XCD (r fastest in the block decode) and may exchange their slabs through that
+  int peers_local;          // plan: 1 = the S blocks of a tile are dealt to ONE XCD (r fastest in the block decode) and may exchange their slabs through that
                             // XCD's L2 (plain stores) once every peer has confirmed its XCC id (words flags[blocks ..)); 0 = round-5 dealing, write-through always
   // (the block decode of the kernel without integer divisions: x / d = (x * magic) >> 32 for the dividends that occur, all < 2^20)
   int tiles_x, tiles_img, tiles_m, ncombo, cpg;
   unsigned mg_tiles_x, mg_tiles_img, mg_tiles_m, mg_ncombo, mg_pw, mg_cpg;
 };
-bool dmx_conv_halo_supported(const HaloConvArgs& a);
-bool dmx_conv_halo_pays(const HaloConvArgs& a);        // supported AND at least as fast in situ as GroupNorm + implicit-GEMM conv (what the executors ask)
-size_t dmx_conv_halo_workspace_bytes(const HaloConvArgs& a);
-bool dmx_conv_halo_wants_stats(int H, int W, bool everywhere);   // geometry + level rule shared by the planner and the executors
-int dmx_conv_halo_flag_count(const HaloConvArgs& a);   // ints of zeroed flags the launch needs (0: none)
-int dmx_conv_halo_launch(HaloConvArgs a, void* workspace, size_t workspace_bytes, hipStream_t stream);
+// conv_halo_plan.hip: what dmx_conv_halo_launch will do with a problem.  Host arithmetic only (no HIP call): what the plan reads from the
+// process - the device's CU count and three switches - enters as a HaloEnv (tests/test_halo_plan_host.py runs without a GPU).
+struct HaloEnv { int n_cu, exclusive, peers, ws; };    // n_cus(), dmx_set_exclusive_device, dmx_set_halo_peers, dmx_set_halo_ws
+HaloEnv dmx_halo_env();                                // of the current device and the live switches
+struct HaloPlan {
+  bool ok;                                             // false: the kernel does not take the problem (everything else zero)
+  int inst;                                            // instance id: the row of halo_tile.h
+  int TH, TW, bn, splits, waves;                       // pixel tile, column tile, blocks per tile along K, the instance's force_waves value
+  int blocks, threads, lds_bytes;                      // launch shape
+  int flag_count;                                      // zeroed ints the launch needs (0: none): one completion flag + one XCC-id word per block
+  size_t flag_bytes, workspace_bytes;                  // K splits: the flags in front of the fp32 slabs; all of the workspace the launch needs
+  int tiles_x, tiles_img, tiles_m, ncombo, cpg;        // the kernel's block decode (HaloConvArgs fields of the same names)
+  unsigned mg_tiles_x, mg_tiles_img, mg_tiles_m, mg_ncombo, mg_pw, mg_cpg;
+  int xcd_tile_major, peers_local;
+};
+HaloPlan dmx_conv_halo_plan(const HaloConvArgs& a, const HaloEnv& env);
+int dmx_conv_halo_check(const HaloConvArgs& a, const HaloPlan& p);      // the launch's argument checks (DMX_ERR_ARG + message for a problem the plan refuses)
+int dmx_conv_halo_check_and_plan(const HaloConvArgs& a, const HaloEnv& env, HaloPlan* plan);   // the plan, then those checks
+// could a fused GroupNorm -> conv launch consume statistics records of an H x W tensor: the geometry and the level rule (what the executors ask)
+bool dmx_conv_halo_wants_stats(int H, int W, bool everywhere);
+int dmx_conv_halo_launch(HaloConvArgs a, const HaloPlan& p, void* workspace, size_t workspace_bytes, hipStream_t stream);
+HaloConvArgs dmx_halo_args(const dmx_halo_conv_desc* d);   // api.hip: the C ABI's descriptor as launch arguments
 // statistics of a tensor nobody emitted them for: one streaming pass, DmxStat records [B][C][4] (zero before the launch)
 int dmx_colstats_launch(const bf16* x, int ldx, int B, int HW, int C, long long* st, hipStream_t stream);
 

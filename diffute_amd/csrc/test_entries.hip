@@ -2,7 +2,8 @@
 // operator-level entry of their own - train_small.hip's transposes, add, pointwise 1x1 and small-linear backward, norm.hip's row
 // softmax and vae_train.hip's casts (tests/test_train_small_gpu.py) - and the two weight-preparation kernels that only the model
 // executors launch: gemm.hip's folded-LayerNorm weights and elementwise.hip's padded context cast (tests/test_weight_pack_gpu.py); fold.hip's
-// composition and the folded block tail on the executor (tests/test_ff_fold_gpu.py); gemm_plan.hip's planner (tests/test_gemm_plan_host.py).
+// composition and the folded block tail on the executor (tests/test_ff_fold_gpu.py); gemm_plan.hip's and conv_halo_plan.hip's planners
+// (tests/test_gemm_plan_host.py, tests/test_halo_plan_host.py).
 // Each entry checks its arguments and forwards to the *_launch function / executor op the graphs call; none does arithmetic of its own.
 #include "exec.h"
 
@@ -94,6 +95,19 @@ extern "C" int dmx_test_gemm_plan(const dmx_gemm_desc* d, int n_cus, long long* 
   a.pf_bytes[0] = 4096; const GemmLaunchShape spf = dmx_gemm_launch_shape(a, P);
   const long long v[12] = {P.cfg, P.splitk, P.kt_per_split, P.tiles_n, P.persist_blocks, (long long)P.workspace_bytes, s.grid_x, s.grid_y, s.threads, s.lds_bytes, spf.lds_bytes, P.colstats_ok ? 1 : 0};
   for (int i = 0; i < 12; ++i) out[i] = v[i];
+  return DMX_OK;
+}
+
+// The halo-conv planner without a device (tests/test_halo_plan_host.py): what dmx_conv3x3_gn(d) would check and plan on n_cus compute units under
+// the given settings of dmx_set_exclusive_device / dmx_set_halo_peers / dmx_set_halo_ws
+extern "C" int dmx_test_halo_plan(const dmx_halo_conv_desc* d, int n_cus, int exclusive, int peers, int ws, long long* out) {
+  DMX_REQUIRE(d && out && n_cus > 0, "test_halo_plan: bad argument");
+  for (int i = 0; i < 23; ++i) out[i] = 0;
+  HaloPlan P;
+  if (const int rc = dmx_conv_halo_check_and_plan(dmx_halo_args(d), HaloEnv{n_cus, exclusive, peers, ws}, &P)) return rc;
+  const long long v[23] = {P.TH, P.TW, P.bn, P.waves, P.splits, P.blocks, P.threads, P.lds_bytes, P.flag_count, (long long)P.workspace_bytes, P.xcd_tile_major, P.peers_local,
+                           P.tiles_x, P.tiles_img, P.tiles_m, P.ncombo, P.cpg, P.mg_tiles_x, P.mg_tiles_img, P.mg_tiles_m, P.mg_ncombo, P.mg_pw, P.mg_cpg};
+  for (int i = 0; i < 23; ++i) out[i] = v[i];
   return DMX_OK;
 }
 

@@ -244,6 +244,13 @@ typedef struct dmx_halo_conv_desc {
 int dmx_conv3x3_gn_supported(const dmx_halo_conv_desc* d);
 size_t dmx_conv3x3_gn_workspace_bytes(const dmx_halo_conv_desc* d);
 int dmx_conv3x3_gn(const dmx_halo_conv_desc* d, void* workspace, size_t workspace_bytes, dmx_stream_t stream);
+/* Test support (tests/test_halo_plan_host.py; declared here because it takes the descriptor): what dmx_conv3x3_gn(d) would do on a device of n_cus
+ * compute units with dmx_set_exclusive_device(exclusive), dmx_set_halo_peers(peers) and dmx_set_halo_ws(ws), without a device call and without reading
+ * through any pointer of d.  Returns what dmx_conv3x3_gn returns for the arguments (DMX_ERR_ARG for a problem it refuses, out zeroed) and writes
+ * out[23] = {tile rows, tile columns, output columns per block, the instance's force_waves value, K split, blocks, block threads, dynamic LDS bytes,
+ * zeroed flag words, workspace bytes, pixel-tile-major dealing, peers on one XCD, the five counts of the kernel's block decode (tiles per row, per
+ * image, pixel tiles, (column tile, slice) combos, channels per group) and its six division constants}. */
+int dmx_test_halo_plan(const dmx_halo_conv_desc* d, int n_cus, int exclusive, int peers, int ws, long long* out);
 int dmx_colstats(const void* x, int ldx, int B, int HW, int C, long long* st, dmx_stream_t stream);
 int dmx_set_halo_conv(int on);      /* tuning aid: 0 makes the model executors use GroupNorm + dmx_conv_gemm everywhere; returns the old setting */
 int dmx_set_exclusive_device(int on); /* 1 (default): the library's launches have the GPU to themselves, one stream at a time.  0: other streams or other kernels (micro-batches on
