@@ -280,6 +280,44 @@ def _edit(paged, unet, vae, scheduler, images, locations, encoder_hidden_states,
     return (out, image_vae, pre) if return_intermediate else out
 
 
+@torch.no_grad()
+def edit_quads(unet, vae, scheduler, images, quads, encoder_hidden_states, num_inference_steps, *, frames=None, batch_size=4, generator=None,
+               enc_noise=None, variance_noise=None, return_intermediate=False, size=512, cache_interval=1, texts=None, glyph=None, guidance=None):
+    """edit_pages for skewed and rotated text: every region is a QUAD - the four corners of the line as an OCR record gives them (top-left,
+    top-right, bottom-right, bottom-left as read) - instead of a rectangle.  images: a list of P contiguous uint8 CUDA [h_p][w_p][3] tensors
+    on one device; quads: P lists of quads; frames: None or P lists of oriented crops (cx2, cy2, crop_scale, ux, uy), planned by
+    prepost.plan_quads where not given (deterministic: nothing is drawn).  The mask is the quad itself, so the lines above and below a
+    tilted line stay out of it; the crop is turned to the line's baseline, so the network sees the text upright, as its glyph image shows
+    it; the paste maps page pixels back through the inverse of that frame and touches no pixel outside the quads.
+
+    One preprocess_quads launch, the N rows (page-major) through edit_latents in chunks of `batch_size` exactly as edit_pages sends them
+    (chunks cross page boundaries; every row starts from the seed-0 single-sample draw), one postprocess_quads launch.  Returns the list of
+    P edited pages, with return_intermediate=True also image_vae [N,3,S,S] and the preprocess dict.  encoder_hidden_states / texts / glyph /
+    enc_noise / variance_noise / cache_interval / guidance: as for edit_pages."""
+    if int(batch_size) < 1:
+        raise ValueError("batch_size must be at least 1")
+    cache_interval = _check_cache_interval(cache_interval)
+    images, quads = list(images), [list(q) for q in quads]
+    if len(quads) != len(images):
+        raise ValueError(f"{len(images)} pages, {len(quads)} lists of quads: the lengths must agree")
+    sizes = [_page_size(img, f"images[{p}]") for p, img in enumerate(images)]
+    if frames is not None:
+        frames = [list(f) for f in frames]
+        if len(frames) != len(images) or any(len(f) != len(q) for f, q in zip(frames, quads)):
+            raise ValueError(f"frames must be {len(images)} lists, one frame per quad: the lengths must agree")
+    N = sum(len(q) for q in quads)
+    _check_contexts(N, encoder_hidden_states, texts, glyph)
+    guidance = _check_guidance(guidance, encoder_hidden_states, N)
+    if frames is None:
+        frames = prepost.plan_quads(quads, sizes)
+    encoder_hidden_states = _contexts(encoder_hidden_states, texts, glyph)
+    pre = prepost.preprocess_quads(images, quads, frames, size=size)
+    image_vae = _edit_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
+                           enc_noise, variance_noise, int(size), cache_interval, guidance)
+    out = prepost.postprocess_quads(image_vae, images, quads, frames)
+    return (out, image_vae, pre) if return_intermediate else out
+
+
 def _one(lst):
     """a one-page function's optional list as the paged form's list of lists"""
     return None if lst is None else [lst]

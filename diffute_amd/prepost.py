@@ -483,3 +483,183 @@ def postprocess_select_pages(image_vae, scores, images, locations, origins, crop
     and choice int32 [N] on the device, by the same rule; with return_mask=True also the list of P union masks.  out as for
     postprocess_pages."""
     return _select_paste(_paged(images, locations, origins, crop_scales), image_vae, scores, threshold, return_mask, out)
+
+
+# ------------------------------------------------------------------------------------------------ quadrilateral regions, oriented crops
+# (csrc/prepost_quad.hip; the arithmetic is stated in csrc/prepost_quad.h).  A quad is four corners (x, y) - top-left, top-right,
+# bottom-right, bottom-left of the text as read, clockwise with y down -, a frame is (cx2, cy2, crop_scale, ux, uy): the crop's centre in
+# half-pixels of pixel-index space, its side in page pixels and the direction of its x axis.
+def _corners(quad):
+    """a quad as given - 4 x (x, y) or 8 numbers - -> [[x, y]] * 4 of ints"""
+    c = np.asarray(quad).reshape(-1)
+    if c.size != 8:
+        raise ValueError(f"a quad is four corners (x, y): TL, TR, BR, BL; got {c.size} numbers")
+    return [[int(c[2 * k]), int(c[2 * k + 1])] for k in range(4)]
+
+
+def _rn(v):
+    return int(np.rint(v))                                             # round half to even, as the C side's rint
+
+
+def quad_baseline(quad):
+    """u = (TR - TL) + (BR - BL): the direction of the text, top and bottom edge averaged (twice their mean)"""
+    (x0, y0), (x1, y1), (x2, y2), (x3, y3) = _corners(quad)
+    return (x1 - x0) + (x2 - x3), (y1 - y0) + (y2 - y3)
+
+
+def frame_for(quad, h, w):
+    """The oriented crop of one quad on an h x w page -> (cx2, cy2, crop_scale, ux, uy), integers, no rng.  (ux, uy) is the quad's
+    baseline u.  crop_scale is the ladder crop_scale_for applied to the quad's OWN length and height (rn of the mean length of its top and
+    bottom edge / of its left and right edge), as if the line lay upright.  The centre is the quad's centre (rn of the corner sum / 2, in
+    half-pixels), moved along each page axis by the smallest translation that brings the frame's bounding box - half-extent
+    crop_scale * (|ux| + |uy|) / (2 |u|) on both axes - inside the page; where the box is larger than the page along an axis the frame
+    is centred on the page along that axis."""
+    c = _corners(quad)
+    ux, uy = quad_baseline(c)
+    if ux == 0 and uy == 0:
+        raise ValueError("the quad has no baseline: (TR - TL) + (BR - BL) is (0, 0)")
+    dist = lambda a, b: float(np.sqrt(float((c[a][0] - c[b][0]) ** 2 + (c[a][1] - c[b][1]) ** 2)))
+    length, height = _rn((dist(1, 0) + dist(2, 3)) / 2.0), _rn((dist(3, 0) + dist(2, 1)) / 2.0)
+    crop_scale = max(1, int(crop_scale_for((0, 0, length, height), h, w)))
+    ext2 = int(np.ceil(crop_scale * (abs(ux) + abs(uy)) / float(np.sqrt(float(ux * ux + uy * uy)))))       # the box's side, = 2 half-extents in half-pixels
+    centre = []
+    for axis, n in ((0, w), (1, h)):
+        c2 = _rn(sum(p[axis] for p in c) / 2.0)
+        lo, hi = ext2 - 1, 2 * n - 1 - ext2                            # the box [c2/2 - ext/2, c2/2 + ext/2] inside [-1/2, n - 1/2]
+        centre.append(min(max(c2, lo), hi) if lo <= hi else n - 1)
+    return centre[0], centre[1], crop_scale, ux, uy
+
+
+def plan_quads(quads_per_page, sizes):
+    """frame_for for every quad of every page: quads_per_page is a list of P lists of quads, sizes the pages' (h, w).  Returns P lists of
+    frames.  Deterministic: nothing is drawn."""
+    quads_per_page, sizes = list(quads_per_page), list(sizes)
+    if len(quads_per_page) != len(sizes):
+        raise ValueError(f"{len(quads_per_page)} lists of quads, {len(sizes)} page sizes: the lengths must agree")
+    return [[frame_for(q, int(h), int(w)) for q in quads] for quads, (h, w) in zip(quads_per_page, sizes)]
+
+
+_Quads = collections.namedtuple("_Quads", "images dev quads frames counts")
+
+
+def _check_quads(images, quads, frames):
+    """the list half of the quad functions' arguments, checked before any tensor is looked at; frames None (rectify_quads): placeholders"""
+    images, quads = list(images), [list(q) for q in quads]
+    P = len(images)
+    if P == 0:
+        raise ValueError("no pages: the quad pre/post-processing needs at least one")
+    if P > _cabi.EDIT_MAX_ITEMS:
+        raise ValueError(f"{P} pages in one launch, at most {_cabi.EDIT_MAX_ITEMS}")
+    if len(quads) != P:
+        raise ValueError(f"{P} pages, {len(quads)} lists of quads: the lengths must agree")
+    if frames is not None:
+        frames = [list(f) for f in frames]
+        if len(frames) != P:
+            raise ValueError(f"{P} pages, {len(frames)} lists of frames: the lengths must agree")
+    flat_q, flat_f, counts = [], [], []
+    for p in range(P):
+        if not quads[p]:
+            raise ValueError(f"page {p}: no quads; every page needs at least one")
+        if frames is not None and len(frames[p]) != len(quads[p]):
+            raise ValueError(f"page {p}: {len(quads[p])} quads, {len(frames[p])} frames: the lengths must agree")
+        flat_q.extend(_corners(q) for q in quads[p])
+        if frames is not None:
+            for f in frames[p]:
+                if len(f) != 5:
+                    raise ValueError(f"page {p}: a frame is (cx2, cy2, crop_scale, ux, uy)")
+                flat_f.append(tuple(int(v) for v in f))
+        counts.append(len(quads[p]))
+    if len(flat_q) > _cabi.EDIT_MAX_ITEMS:
+        raise ValueError(f"{len(flat_q)} quads in one launch, at most {_cabi.EDIT_MAX_ITEMS}")
+    dev = _check_page_images(images)
+    if frames is None:                                                 # the strips read no frame: any valid one, on the quad's first corner
+        flat_f = [(2 * q[0][0], 2 * q[0][1], 1, 1, 0) for q in flat_q]
+    return _Quads(images, dev, flat_q, flat_f, counts)
+
+
+def _upload_quads(qx, S, out=None, union=None):
+    """the tables of one quad launch - dmx_edit_quad | dmx_edit_page - filled and validated (dmx_edit_quads_prepare) in ONE pinned staging
+    buffer, then ONE asynchronous copy on the current stream.  Returns (host quads, host pages, the pinned storage, the device buffer, the
+    byte offset of the page table in it)."""
+    B, P = len(qx.quads), len(qx.images)
+    n_quads, n_pages = B * ctypes.sizeof(_cabi.EditQuad), P * ctypes.sizeof(_cabi.EditPage)
+    stage = torch.empty(n_quads + n_pages, dtype=torch.uint8, pin_memory=True)
+    st = stage.numpy()
+    st[:] = 0
+    host = (_cabi.EditQuad * B).from_buffer(st[:n_quads])
+    pages = (_cabi.EditPage * P).from_buffer(st[n_quads:])
+    lo = 0
+    for p, (pg, img, n) in enumerate(zip(pages, qx.images, qx.counts)):
+        pg.original = img.data_ptr()
+        pg.out = out[p].data_ptr() if out is not None else 0
+        pg.union_mask = union[p].data_ptr() if union is not None else 0
+        pg.H, pg.W, pg.item_lo, pg.item_hi = int(img.shape[0]), int(img.shape[1]), lo, lo + n
+        for it, c, f in zip(host[lo:lo + n], qx.quads[lo:lo + n], qx.frames[lo:lo + n]):
+            for k in range(4):
+                it.x[k], it.y[k] = c[k]
+            it.cx2, it.cy2, it.crop_scale, it.ux, it.uy = f
+            it.page = p
+        lo += n
+    _cabi.check(_cabi.lib().dmx_edit_quads_prepare(pages, P, host, B, S), "edit_quads_prepare")
+    with torch.cuda.device(qx.dev):
+        dbuf = torch.empty(n_quads + n_pages, dtype=torch.uint8, device=qx.dev)
+        dbuf.copy_(stage, non_blocking=True)                          # the one H2D copy
+    return host, pages, stage, dbuf, n_quads
+
+
+def preprocess_quads(images, quads, frames, size=512):
+    """preprocess_pages for quadrilateral regions, in one launch.  images: P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device;
+    quads: P lists of quads (four corners TL, TR, BR, BL); frames: P lists of (cx2, cy2, crop_scale, ux, uy) (plan_quads gives them).
+    Returns the dict preprocess_pages returns, N rows page-major: row b is quad b's oriented crop - the text's baseline horizontal -,
+    masked_image with the quad itself blacked out before resampling, mask the quad as seen in the crop."""
+    qx = _check_quads(images, quads, frames)
+    B, S = len(qx.quads), int(size)
+    host, pages, stage, dbuf, off = _upload_quads(qx, S)
+    base = dbuf.data_ptr()
+    with torch.cuda.device(qx.dev):
+        image = torch.empty(B, 3, S, S, dtype=torch.float32, device=qx.dev)
+        masked = torch.empty(B, 3, S, S, dtype=torch.float32, device=qx.dev)
+        mask = torch.empty(B, 1, S, S, dtype=torch.uint8, device=qx.dev)
+        mask_lat = torch.empty(B, 1, S // 8, S // 8, dtype=torch.float32, device=qx.dev)
+        _cabi.check(_cabi.lib().dmx_preprocess_quads(pages, base + off, len(qx.images), host, base, B, S, _cabi.ptr(image), _cabi.ptr(masked),
+                                                    _cabi.ptr(mask), _cabi.ptr(mask_lat), _cabi.current_stream()), "preprocess_quads")
+    return dict(image=image, masked_image=masked, mask=mask, mask_latent=mask_lat)
+
+
+def postprocess_quads(image_vae, images, quads, frames, return_mask=False, out=None):
+    """postprocess_pages for quadrilateral regions, in one launch.  image_vae: fp32 CUDA [N,3,S,S] decoder outputs, page-major; the other
+    arguments as for preprocess_quads.  Returns the list of P uint8 [h_p][w_p][3] pages: a pixel inside a quad (edges included) and on
+    that quad's crop comes from the decoder output through the inverse of the frame - where quads overlap the later one decides -, every
+    other pixel is the original's; with return_mask=True also the list of P union masks uint8 [h_p][w_p] (1 inside any quad).  out: as
+    for postprocess_pages."""
+    qx = _check_quads(images, quads, frames)
+    B = len(qx.quads)
+    S, _ = _check_vae(image_vae, B, False)
+    if out is not None:
+        out = _check_page_outputs(out, qx.images)
+    with torch.cuda.device(qx.dev):
+        out = [torch.empty_like(img) for img in qx.images] if out is None else out
+        union = [torch.empty(img.shape[0], img.shape[1], dtype=torch.uint8, device=qx.dev) for img in qx.images] if return_mask else None
+    v = image_vae.to(torch.float32).contiguous()
+    host, pages, stage, dbuf, off = _upload_quads(qx, S, out, union)
+    base = dbuf.data_ptr()
+    with torch.cuda.device(qx.dev):
+        _cabi.check(_cabi.lib().dmx_postprocess_paste_quads(_cabi.ptr(v), S, pages, base + off, len(qx.images), host, base, B,
+                                                           _cabi.current_stream()), "postprocess_paste_quads")
+    return (out, union) if return_mask else out
+
+
+def rectify_quads(images, quads):
+    """Every quad as an upright strip, in one launch: a list of N uint8 CUDA [h_b][w_b][3] tensors, page-major, views of ONE buffer -
+    what TrOCRProcessor(images=...) accepts on the device, so the OCR model can read a skewed line.  The strip runs along the quad's
+    baseline at scale 1 (w_b, h_b: rn of half the summed opposite edges, plus 1); an axis-aligned quad gives page[y1:y2+1, x1:x2+1]."""
+    qx = _check_quads(images, quads, None)
+    B = len(qx.quads)
+    host, pages, stage, dbuf, off = _upload_quads(qx, 8)               # (the strips depend neither on the frames nor on S)
+    total = int(host[B - 1].rect_off) + int(host[B - 1].rw) * int(host[B - 1].rh) * 3
+    base = dbuf.data_ptr()
+    with torch.cuda.device(qx.dev):
+        buf = torch.empty(total, dtype=torch.uint8, device=qx.dev)
+        _cabi.check(_cabi.lib().dmx_rectify_quads(pages, base + off, len(qx.images), host, base, B, _cabi.ptr(buf), total, _cabi.current_stream()),
+                    "rectify_quads")
+    return [buf[int(q.rect_off):int(q.rect_off) + int(q.rw) * int(q.rh) * 3].view(int(q.rh), int(q.rw), 3) for q in host]

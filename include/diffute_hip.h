@@ -963,6 +963,51 @@ int dmx_postprocess_paste_select_pages(const float* image_vae, int S, const floa
                                        const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
                                        const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, dmx_stream_t stream);
 
+/* Skewed and rotated text: QUADRILATERAL regions with ORIENTED crops (prepost_quad.hip; the arithmetic is stated in csrc/prepost_quad.h).
+ * An item is a dmx_edit_quad: the four corners of a text line as an OCR record gives them (top-left, top-right, bottom-right,
+ * bottom-left as read; clockwise with y down) and a frame - a square crop of side crop_scale, centred at (cx2 / 2, cy2 / 2) in
+ * pixel-index space, whose x axis runs along (ux, uy).  The mask is the quad itself (edges included), the network sees the crop with
+ * the baseline horizontal, and the paste maps every page pixel inside the quad back through the inverse of the frame.  The same
+ * predicate decides mask and paste (the reference pastes the half-open slice of the box; a quad has none).  Paged form only: the pages
+ * travel as a dmx_edit_page table exactly as for the *_pages entries (one page is P = 1), here with W <= 65535 as well.  The caller
+ * fills the pages' addresses, sizes and item ranges and every quad's corners, frame and page index, lets edit_quads_prepare validate
+ * both tables and fill the derived fields (host-only: callable without a GPU), and copies both to the device in stream order.
+ *   edit_quads_prepare refuses, by page or item index: a quad that is not convex, not clockwise or has no area; a corner outside
+ *           its page; (ux, uy) = (0, 0) or a component beyond +-131070; a centre outside the page; crop_scale outside 1 .. 65535; a page
+ *           index that is not the page whose range holds the item; B or P outside 1 .. DMX_EDIT_MAX_ITEMS; item ranges that do not tile
+ *           [0, B); S outside 1 .. 65535.
+ *   preprocess_quads: the four outputs of preprocess_crop_pages, row b from quad b's frame (S a multiple of 8).
+ *   postprocess_paste_quads: page p's `out` (and `union_mask`, 0 = none; 1 where any quad of the page covers the pixel) from image_vae
+ *           fp32 [B][3][S][S]; where quads overlap the later item decides; every other pixel is copied; `out` must not be `original`.
+ *   rectify_quads: quad b as an upright strip uint8 [rh][rw][3] at out + rect_off of its table entry (the strips are packed in item
+ *           order; out_bytes >= the last strip's end).  It reads neither the frames nor S.
+ * Each entry is one launch; each checks the host tables again (a bad page or item is named by index and nothing is launched), the kernels
+ * read the device copies and clamp what comes from them: taps to the page, page index and item range to the tables, strip writes to
+ * out_bytes. */
+typedef struct dmx_edit_quad {
+  int x[4], y[4];                   /* corners: TL, TR, BR, BL */
+  int cx2, cy2;                     /* frame centre in half-pixels of pixel-index space */
+  int crop_scale;                   /* frame side in page pixels */
+  int ux, uy;                       /* baseline direction */
+  int page;                         /* index of the quad's page */
+  int fwd[4], inv[4];               /* derived: a b c d (crop -> page) and ia ib ic id (page -> crop), Q15 */
+  int ex[4], ey[4];                 /* derived: edge k runs from corner k to corner k + 1 */
+  int bx1, by1, bx2, by2;           /* derived: bounding box, both corners included */
+  int rect[4];                      /* derived: ra rb rc rd, Q15, scale 1 along u */
+  int sx4, sy4;                     /* derived: corner sums = the centre in quarter-pixels */
+  int rw, rh;                       /* derived: size of the rectified strip */
+  int rect_block_lo, rect_blocks;   /* derived: the strip's blocks in the rectify grid, rh * ceil(rw / 256) of them */
+  long long rect_off;               /* derived: byte offset of the strip in the rectify output */
+} dmx_edit_quad;
+int dmx_edit_quads_prepare(dmx_edit_page* pages, int P, dmx_edit_quad* quads, int B, int S);
+int dmx_preprocess_quads(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_host,
+                         const dmx_edit_quad* quads_device, int B, int S, float* out_image, float* out_masked_image, unsigned char* out_mask,
+                         float* out_mask_latent, dmx_stream_t stream);
+int dmx_postprocess_paste_quads(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device, int B, dmx_stream_t stream);
+int dmx_rectify_quads(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_host,
+                      const dmx_edit_quad* quads_device, int B, unsigned char* out, long long out_bytes, dmx_stream_t stream);
+
 /* Comparing two versions of a set of pages (metrics.hip): what the scene-text-editing literature reports on the edited box - MSE,
  * PSNR, SSIM - and what changed OUTSIDE all boxes.  P pairs of pages a / b, uint8 [H][W][3] contiguous, both of a pair H x W; B boxes
  * (page, x1, y1, x2, y2), each the slice [y1:y2, x1:x2] of its page: exclusive upper corner, non-empty, inside the page (the read-back's
