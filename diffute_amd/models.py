@@ -20,6 +20,7 @@ from torch import nn
 
 from . import _cabi
 from .init import init_param
+from .lora import LoraMixin
 
 SD2_INPAINT_UNET_CONFIG = dict(
     in_channels=9, out_channels=4, block_out_channels=(320, 640, 1280, 1280), layers_per_block=2,
@@ -369,7 +370,7 @@ class _HipModel(nn.Module):
         os.makedirs(save_directory, exist_ok=True)
         with open(os.path.join(save_directory, "config.json"), "w") as f:
             json.dump(dict(self.config.to_dict(), _class_name=type(self).__name__), f, indent=2)
-        save_file({k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()},
+        save_file({k: v.detach().cpu().contiguous() for k, v in self.state_dict().items() if not k.startswith("lora_adapters.")},     # (adapters: save_lora_weights)
                   os.path.join(save_directory, "diffusion_pytorch_model.safetensors"))
 
     @classmethod
@@ -409,7 +410,7 @@ class _HipModel(nn.Module):
         return out
 
 
-class UNet2DConditionModel(_HipModel):
+class UNet2DConditionModel(LoraMixin, _HipModel):
     """SD2-inpainting UNet (reference: train_diffute_v1.py:633-635, app.ipynb:551-553)."""
     _kind = "unet"
     _master_bytes = "dmx_unet_grad_bytes"
@@ -439,7 +440,27 @@ class UNet2DConditionModel(_HipModel):
             c.down_has_attn[i] = int(cfg["down_block_types"][i].startswith("CrossAttn"))
             c.up_has_attn[i] = int(cfg["up_block_types"][i].startswith("CrossAttn"))
         self._cstruct = c
+        self._lora_init()
         self._setup(self._create_handle("bf16"), seed, device)
+
+    # ---- LoRA (lora.py): the base signature leaves the adapter Parameters out; the arena follows them through a second signature
+    def _signature(self):
+        if not self._lora_ids:
+            return super()._signature()
+        return tuple((p.data_ptr(), p._version) for p in self.parameters() if id(p) not in self._lora_ids)
+
+    def _ensure_packed(self, reimport_masters=True):
+        if not self._lora_ever:
+            return super()._ensure_packed(reimport_masters)
+        repack = self._arena is None or self._packed_sig != self._signature()
+        super()._ensure_packed(reimport_masters)           # the base Parameters changed: the full re-pack, the adapters go on top
+        if self._lora_sync_arena(repack):
+            self._weights_changed()
+
+    def _train_params(self):
+        """the Parameters the training function takes as inputs (and returns gradients for): every base Parameter, or - once the model
+        has adapters, until the last one is deleted or fused - A and B of the active ones"""
+        return self._lora_train_params() if self._lora else self._param_list()
 
     def _finalize(self, st):
         half = self.config.block_out_channels[0] // 2
@@ -749,6 +770,8 @@ class UNet2DConditionModel(_HipModel):
 
     def _train_backward(self, dpred):
         """-> list of parameter gradients (torch layouts, fp32) in self._keys order"""
+        if self._lora:
+            return self._lora_train_backward(dpred)
         lib = self._lib
         tb = self._tb
         sync = self._sync
@@ -825,12 +848,12 @@ class UNet2DConditionModel(_HipModel):
     def forward(self, sample, timestep, encoder_hidden_states, return_dict=True, **unused):
         """unet(sample[B,9,h,w], timestep (int / 0-d / [B] tensor), encoder_hidden_states[B,S,1024])."""
         _cabi.require_cuda(sample, encoder_hidden_states)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in (self._train_params() if self._lora else self.parameters())):
             t = self._timesteps(timestep, sample.shape[0], sample.device)
             # (the fp16 build trains too - `--mixed_precision fp16`, train_diffute_v1.py:267,583,790: activation gradients are stored in
             # fp16 there, so run the backward under a loss scale: diffute_amd.GradScaler / torch.amp.GradScaler, training.train_step(scaler=))
             ctx = encoder_hidden_states if encoder_hidden_states.dtype in (torch.float32, self.compute_dtype) else encoder_hidden_states.float()
-            out = _UNetTrainFn.apply(self, sample.detach().to(torch.float32).contiguous(), t, ctx.detach().contiguous(), *self._param_list())
+            out = _UNetTrainFn.apply(self, sample.detach().to(torch.float32).contiguous(), t, ctx.detach().contiguous(), *self._train_params())
             if self._dtype != torch.float32 and sample.dtype != torch.float32:
                 out = out.to(sample.dtype)
             return UNet2DConditionOutput(sample=out) if return_dict else (out,)

@@ -26,6 +26,9 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def __init__(self, unet, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=1.0,
                  ema_decay=None, ema_min_decay=0.0, ema_update_after_step=0, ema_use_warmup=False, ema_inv_gamma=1.0, ema_power=2.0 / 3.0):
+        if getattr(unet, "_lora", None):
+            raise RuntimeError("FusedAdamW owns the fp32 masters of every weight of the model and cannot train a model with LoRA adapters: "
+                               "use torch.optim.AdamW(unet.lora_parameters()), or fuse_lora() / delete_adapter() first")
         unet._ensure_packed()
         super().__init__(unet._param_list(), dict(lr=float(lr), betas=tuple(betas), eps=float(eps), weight_decay=float(weight_decay)))
         self.unet = unet

@@ -1080,6 +1080,42 @@ int dmx_unet_adamw_step_scaled(dmx_unet* u, const void* table_dev, int nchunks, 
                                dmx_stream_t stream);
 int dmx_unet_refresh_derived(dmx_unet* u, dmx_stream_t stream);
 
+/* LoRA: low-rank adapters on the UNet's linear weights, MERGED into the weights arena (diffute_amd/lora.py; peft / diffusers
+ * `unet.add_adapter`).  The arena holds W' = W0 + sum_j s_j B_j A_j, so every forward and backward graph runs unchanged, and the adapter
+ * gradients are linear images of the dW the backward leaves in the gradient arena: dA_j = s_j B_j^T dW, dB_j = s_j dW A_j^T.
+ * One dmx_lora_rec per (target linear, active adapter); all matrices fp32, row-major, dense: A [r][K] and B [N][r] (peft's lora_A.weight /
+ * lora_B.weight), s = weight * alpha / r.  The calls take the records on the HOST and upload them into `table`, the caller's device buffer
+ * of at least n_records * sizeof(dmx_lora_rec) bytes, on `stream`; at most 65535 records per call.
+ *   dmx_lora_merge  W = the target's base weight W0 [N][K] (torch layout), dst = where W' [N][K] goes.  The records of one target are
+ *                   contiguous and are summed in table order; the first carries count = their number, the others count = 0, and all repeat
+ *                   N, K, W and dst.  W'[n][k] = fma(s_J, dot_J, ... fma(s_1, dot_1, W0[n][k])), dot_j = the fma chain over p = 0 .. r-1 from 0:
+ *                   one thread per element, so the bits depend on nothing but the target's own records.  One launch.
+ *   dmx_lora_grads  W = dW [N][K] (torch layout, e.g. from dmx_unet_grad_export), dst = dA [r][K], dst2 = dB [N][r]; count is ignored.
+ *                   dA[p][k] = s * (((q0 + q1) + q2) + q3), q_i the fma chain over the i-th quarter (ceil(N / 4) rows) of n ascending;
+ *                   dB[n][p] = s * the sum over k: per lane l of 64 the fma chain over k = l, l + 64, ..., then a fixed halving tree.  Plain
+ *                   IEEE arithmetic: an inf / NaN in dW comes through in every dA column and dB row it takes part in.  One launch.
+ *   dmx_unet_lora_apply  merges, packs every target's merged weight into the weights arena by the pack path of dmx_unet_load_param (a
+ *                   target with nrec = 0 is packed from its base weight w0: the adapter is removed) and calls dmx_unet_refresh_derived.
+ *                   Targets are linear weights (parameter names as in dmx_unet_param_info), in the order of their records. */
+typedef struct dmx_lora_rec {
+  const float* A; const float* B;
+  const float* W;
+  float* dst; float* dst2;
+  int N, K, r;
+  float s;
+  int count;
+  int reserved;
+} dmx_lora_rec;
+typedef struct dmx_lora_target {
+  const char* name;
+  const float* w0;
+  int rec0, nrec;
+} dmx_lora_target;
+int dmx_lora_merge(const dmx_lora_rec* h_recs, int n_records, void* table, size_t table_bytes, dmx_stream_t stream);
+int dmx_lora_grads(const dmx_lora_rec* h_recs, int n_records, void* table, size_t table_bytes, dmx_stream_t stream);
+int dmx_unet_lora_apply(dmx_unet* u, const dmx_lora_target* h_targets, int n_targets, const dmx_lora_rec* h_recs, int n_records,
+                        void* table, size_t table_bytes, dmx_stream_t stream);
+
 /* Multi-tensor EMA update / cast-copy (diffusers EMAModel as the reference drives it: `ema_unet.step(unet.parameters())`,
  * train_diffute_v1.py:934-935; copy_to / store / restore; diffute_amd.EMAModel).  One launch per call whatever the number of
  * tensors: `table` is a DEVICE array of `nchunks` entries, each a contiguous run of `count` elements; the host splits large
