@@ -76,6 +76,10 @@ inline void fill_derived(dmx_edit_quad& q, int S, long long rect_off, int rect_b
   q.rect_off = rect_off;
 }
 
+// The host-side checks of a page table and a quad table (prepost_quad.hip), shared with the projective entries of prepost_persp.hip
+int check_quads(const char* what, const dmx_edit_page* pages, int P, const dmx_edit_quad* quads, int B, int S, bool frames, bool prepared);
+int check_quad_pages(const char* what, const dmx_edit_page* pages, int P, bool need_out);
+
 #ifdef __HIPCC__
 // what the paste scans per item, staged in LDS
 struct QuadEdges { int x[4], y[4], ex[4], ey[4]; int bx1, by1, bx2, by2; };

@@ -131,6 +131,9 @@ __global__ __launch_bounds__(256) void dmx_rectify_quads_kernel(const RectQuadAr
   for (int c = 0; c < 3; ++c) p.out[o + c] = (unsigned char)page_sample((const unsigned char*)pg.original, pg.W, tx, ty, c);
 }
 
+}  // namespace
+
+namespace dmx_quad {
 // The host-side checks of a page table and a quad table.  frames: the frame fields are looked at (the rectify entry reads none of
 // them).  prepared: the derived fields of both tables are compared with what dmx_edit_quads_prepare fills.  A bad page is named by page
 // index, a bad quad by its index in the whole table.
@@ -207,7 +210,7 @@ int check_quad_pages(const char* what, const dmx_edit_page* pages, int P, bool n
   }
   return DMX_OK;
 }
-}  // namespace
+}  // namespace dmx_quad
 
 extern "C" int dmx_edit_quads_prepare(dmx_edit_page* pages, int P, dmx_edit_quad* quads, int B, int S) {
   const int rc = check_quads("edit_quads_prepare", pages, P, quads, B, S, true, false);

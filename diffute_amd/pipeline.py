@@ -282,7 +282,8 @@ def _edit(paged, unet, vae, scheduler, images, locations, encoder_hidden_states,
 
 @torch.no_grad()
 def edit_quads(unet, vae, scheduler, images, quads, encoder_hidden_states, num_inference_steps, *, frames=None, batch_size=4, generator=None,
-               enc_noise=None, variance_noise=None, return_intermediate=False, size=512, cache_interval=1, texts=None, glyph=None, guidance=None):
+               enc_noise=None, variance_noise=None, return_intermediate=False, size=512, cache_interval=1, texts=None, glyph=None, guidance=None,
+               perspective=False):
     """edit_pages for skewed and rotated text: every region is a QUAD - the four corners of the line as an OCR record gives them (top-left,
     top-right, bottom-right, bottom-left as read) - instead of a rectangle.  images: a list of P contiguous uint8 CUDA [h_p][w_p][3] tensors
     on one device; quads: P lists of quads; frames: None or P lists of oriented crops (cx2, cy2, crop_scale, ux, uy), planned by
@@ -293,7 +294,14 @@ def edit_quads(unet, vae, scheduler, images, quads, encoder_hidden_states, num_i
     One preprocess_quads launch, the N rows (page-major) through edit_latents in chunks of `batch_size` exactly as edit_pages sends them
     (chunks cross page boundaries; every row starts from the seed-0 single-sample draw), one postprocess_quads launch.  Returns the list of
     P edited pages, with return_intermediate=True also image_vae [N,3,S,S] and the preprocess dict.  encoder_hidden_states / texts / glyph /
-    enc_noise / variance_noise / cache_interval / guidance: as for edit_pages."""
+    enc_noise / variance_noise / cache_interval / guidance: as for edit_pages.
+
+    perspective=True - for phone photos, signs and scene text, where a line is a trapezoid: frames are PROJECTIVE, (ci2, cj2, crop_scale),
+    planned by prepost.plan_quads(..., perspective=True) where not given.  The crop is taken through the homography that makes the quad an
+    upright rectangle, so the network sees the text without keystone, and the paste goes back through its inverse; everything between the
+    two launches is the same.  Limits: the window is not moved to stay on the page (the border is replicated), a window over which the
+    homography's denominator changes by more than 4x is refused, curved text is out."""
+    perspective = bool(perspective)
     if int(batch_size) < 1:
         raise ValueError("batch_size must be at least 1")
     cache_interval = _check_cache_interval(cache_interval)
@@ -309,12 +317,12 @@ def edit_quads(unet, vae, scheduler, images, quads, encoder_hidden_states, num_i
     _check_contexts(N, encoder_hidden_states, texts, glyph)
     guidance = _check_guidance(guidance, encoder_hidden_states, N)
     if frames is None:
-        frames = prepost.plan_quads(quads, sizes)
+        frames = prepost.plan_quads(quads, sizes, perspective, int(size))
     encoder_hidden_states = _contexts(encoder_hidden_states, texts, glyph)
-    pre = prepost.preprocess_quads(images, quads, frames, size=size)
+    pre = prepost.preprocess_quads(images, quads, frames, size=size, perspective=perspective)
     image_vae = _edit_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
                            enc_noise, variance_noise, int(size), cache_interval, guidance)
-    out = prepost.postprocess_quads(image_vae, images, quads, frames)
+    out = prepost.postprocess_quads(image_vae, images, quads, frames, perspective=perspective)
     return (out, image_vae, pre) if return_intermediate else out
 
 

@@ -530,20 +530,71 @@ def frame_for(quad, h, w):
     return centre[0], centre[1], crop_scale, ux, uy
 
 
-def plan_quads(quads_per_page, sizes):
+def persp_frame_accepted(quad, h, w, frame, size=512):
+    """None if the C side (host-only: dmx_edit_quads_prepare, dmx_edit_quads_persp_prepare) accepts the projective frame (ci2, cj2,
+    crop_scale) of `quad` on an h x w page at crop size `size`, else its message"""
+    c = _corners(quad)
+    pages, host, persp = (_cabi.EditPage * 1)(), (_cabi.EditQuad * 1)(), (_cabi.QuadPersp * 1)()
+    pages[0].original, pages[0].H, pages[0].W, pages[0].item_lo, pages[0].item_hi = 64, int(h), int(w), 0, 1
+    for k in range(4):
+        host[0].x[k], host[0].y[k] = c[k]
+    host[0].cx2, host[0].cy2, host[0].crop_scale, host[0].ux, host[0].uy = 2 * c[0][0], 2 * c[0][1], 1, 1, 0
+    persp[0].ci2, persp[0].cj2, persp[0].crop_scale = (int(v) for v in frame)
+    lib = _cabi.lib()
+    if lib.dmx_edit_quads_prepare(pages, 1, host, 1, int(size)) != 0 or lib.dmx_edit_quads_persp_prepare(pages, 1, host, persp, 1, int(size)) != 0:
+        return lib.dmx_last_error().decode()
+    return None
+
+
+def strip_size(quad):
+    """(rw, rh) of the quad's upright strip: rn of half the summed opposite edges, plus 1 (csrc/prepost_quad.h, the rectify section)"""
+    c = _corners(quad)
+    ux, uy = quad_baseline(c)
+    vx, vy = (c[3][0] - c[0][0]) + (c[2][0] - c[1][0]), (c[3][1] - c[0][1]) + (c[2][1] - c[1][1])
+    return _rn(np.sqrt(float(ux * ux + uy * uy)) / 2.0) + 1, _rn(np.sqrt(float(vx * vx + vy * vy)) / 2.0) + 1
+
+
+_LADDER = (128, 256, 384, 512, 640, 784, 1000)
+
+
+def persp_frame_for(quad, h, w, size=512):
+    """The projective frame of one quad on an h x w page -> (ci2, cj2, crop_scale), integers, no rng (csrc/prepost_persp.h): the window
+    the network sees is a square of side crop_scale in the pixels of the quad's upright rw x rh STRIP, carried to the page by the
+    homography that takes the strip to the quad.  The centre is the strip's centre, (rw - 1, rh - 1) half-pixels.  crop_scale is the
+    ladder crop_scale_for applied to (rw, rh) as frame_for applies it to length and height; where the C side refuses that window - the
+    homography's denominator changes by more than 4x over it, or its horizon crosses it - it is stepped down: the ladder's rungs below
+    it that are still longer than the strip, then the strip's own length rw.  ValueError, naming the quad, if that is refused too.
+    Limit: the centre is NOT moved to keep the window on the page; where the window overhangs, clamped taps replicate the border."""
+    c = _corners(quad)
+    rw, rh = strip_size(c)
+    first = max(1, int(crop_scale_for((0, 0, rw, rh), h, w)))
+    tries = [first] + [b for b in reversed(_LADDER) if rw < b < first] + ([rw] if rw < first else [])
+    why = None
+    for crop_scale in tries:
+        why = persp_frame_accepted(c, h, w, (rw - 1, rh - 1, crop_scale), size)
+        if why is None:
+            return rw - 1, rh - 1, crop_scale
+    raise ValueError(f"no projective frame for the quad {c} on a {w}x{h} page: windows of {tries} strip pixels are all refused; the last: {why}")
+
+
+def plan_quads(quads_per_page, sizes, perspective=False, size=512):
     """frame_for for every quad of every page: quads_per_page is a list of P lists of quads, sizes the pages' (h, w).  Returns P lists of
-    frames.  Deterministic: nothing is drawn."""
+    frames.  Deterministic: nothing is drawn.  perspective=True: persp_frame_for instead - projective frames (ci2, cj2, crop_scale), for
+    crops of `size`."""
     quads_per_page, sizes = list(quads_per_page), list(sizes)
     if len(quads_per_page) != len(sizes):
         raise ValueError(f"{len(quads_per_page)} lists of quads, {len(sizes)} page sizes: the lengths must agree")
+    if perspective:
+        return [[persp_frame_for(q, int(h), int(w), size) for q in quads] for quads, (h, w) in zip(quads_per_page, sizes)]
     return [[frame_for(q, int(h), int(w)) for q in quads] for quads, (h, w) in zip(quads_per_page, sizes)]
 
 
-_Quads = collections.namedtuple("_Quads", "images dev quads frames counts")
+_Quads = collections.namedtuple("_Quads", "images dev quads frames counts persp", defaults=(None,))
 
 
-def _check_quads(images, quads, frames):
-    """the list half of the quad functions' arguments, checked before any tensor is looked at; frames None (rectify_quads): placeholders"""
+def _check_quads(images, quads, frames, perspective=False):
+    """the list half of the quad functions' arguments, checked before any tensor is looked at; frames None (rectify_quads): placeholders.
+    perspective: the frames are projective, (ci2, cj2, crop_scale) - they go to `persp`, and `frames` holds the placeholders"""
     images, quads = list(images), [list(q) for q in quads]
     P = len(images)
     if P == 0:
@@ -564,30 +615,35 @@ def _check_quads(images, quads, frames):
             raise ValueError(f"page {p}: {len(quads[p])} quads, {len(frames[p])} frames: the lengths must agree")
         flat_q.extend(_corners(q) for q in quads[p])
         if frames is not None:
-            for f in frames[p]:
-                if len(f) != 5:
+            for j, f in enumerate(frames[p]):
+                if perspective and (f is None or len(f) != 3):
+                    raise ValueError(f"page {p}: quad {j}: a projective frame is (ci2, cj2, crop_scale)")
+                if not perspective and len(f) != 5:
                     raise ValueError(f"page {p}: a frame is (cx2, cy2, crop_scale, ux, uy)")
                 flat_f.append(tuple(int(v) for v in f))
         counts.append(len(quads[p]))
     if len(flat_q) > _cabi.EDIT_MAX_ITEMS:
         raise ValueError(f"{len(flat_q)} quads in one launch, at most {_cabi.EDIT_MAX_ITEMS}")
     dev = _check_page_images(images)
+    persp = None
+    if perspective:                                                    # (frames None: the strips alone, which read no frame)
+        persp, frames = (flat_f if frames is not None else []), None
     if frames is None:                                                 # the strips read no frame: any valid one, on the quad's first corner
         flat_f = [(2 * q[0][0], 2 * q[0][1], 1, 1, 0) for q in flat_q]
-    return _Quads(images, dev, flat_q, flat_f, counts)
+    return _Quads(images, dev, flat_q, flat_f, counts, persp)
 
 
-def _upload_quads(qx, S, out=None, union=None):
-    """the tables of one quad launch - dmx_edit_quad | dmx_edit_page - filled and validated (dmx_edit_quads_prepare) in ONE pinned staging
-    buffer, then ONE asynchronous copy on the current stream.  Returns (host quads, host pages, the pinned storage, the device buffer, the
-    byte offset of the page table in it)."""
+def _stage_quads(qx, S, out=None, union=None, n_persp=0):
+    """dmx_edit_quad | dmx_edit_page | n_persp bytes in ONE pinned staging buffer, the first two tables filled and validated
+    (dmx_edit_quads_prepare).  Returns (host quads, host pages, the pinned storage, its numpy view, the page table's byte offset, the
+    offset of the rest)"""
     B, P = len(qx.quads), len(qx.images)
     n_quads, n_pages = B * ctypes.sizeof(_cabi.EditQuad), P * ctypes.sizeof(_cabi.EditPage)
-    stage = torch.empty(n_quads + n_pages, dtype=torch.uint8, pin_memory=True)
+    stage = torch.empty(n_quads + n_pages + n_persp, dtype=torch.uint8, pin_memory=True)
     st = stage.numpy()
     st[:] = 0
     host = (_cabi.EditQuad * B).from_buffer(st[:n_quads])
-    pages = (_cabi.EditPage * P).from_buffer(st[n_quads:])
+    pages = (_cabi.EditPage * P).from_buffer(st[n_quads:n_quads + n_pages])
     lo = 0
     for p, (pg, img, n) in enumerate(zip(pages, qx.images, qx.counts)):
         pg.original = img.data_ptr()
@@ -601,38 +657,80 @@ def _upload_quads(qx, S, out=None, union=None):
             it.page = p
         lo += n
     _cabi.check(_cabi.lib().dmx_edit_quads_prepare(pages, P, host, B, S), "edit_quads_prepare")
+    return host, pages, stage, st, n_quads, n_quads + n_pages
+
+
+def _to_device(qx, stage):
     with torch.cuda.device(qx.dev):
-        dbuf = torch.empty(n_quads + n_pages, dtype=torch.uint8, device=qx.dev)
+        dbuf = torch.empty(stage.numel(), dtype=torch.uint8, device=qx.dev)
         dbuf.copy_(stage, non_blocking=True)                          # the one H2D copy
-    return host, pages, stage, dbuf, n_quads
+    return dbuf
 
 
-def preprocess_quads(images, quads, frames, size=512):
+def _upload_quads(qx, S, out=None, union=None):
+    """the tables of one quad launch - dmx_edit_quad | dmx_edit_page - filled and validated (dmx_edit_quads_prepare) in ONE pinned staging
+    buffer, then ONE asynchronous copy on the current stream.  Returns (host quads, host pages, the pinned storage, the device buffer, the
+    byte offset of the page table in it)."""
+    host, pages, stage, st, off, _ = _stage_quads(qx, S, out, union)
+    return host, pages, stage, _to_device(qx, stage), off
+
+
+def _upload_quads_persp(qx, S, out=None, union=None):
+    """_upload_quads with the projective table behind the other two - dmx_edit_quad | dmx_edit_page | dmx_quad_persp -, filled from
+    qx.persp and prepared by dmx_edit_quads_persp_prepare (S = 0: the strip maps alone; the frames are not read).  Returns (host quads,
+    host pages, host projective table, the pinned storage, the device buffer, the page table's byte offset, the projective table's)."""
+    B = len(qx.quads)
+    host, pages, stage, st, off, xoff = _stage_quads(qx, max(S, 8), out, union, B * ctypes.sizeof(_cabi.QuadPersp))
+    persp = (_cabi.QuadPersp * B).from_buffer(st[xoff:])
+    for e, f in zip(persp, qx.persp):
+        e.ci2, e.cj2, e.crop_scale = f
+    _cabi.check(_cabi.lib().dmx_edit_quads_persp_prepare(pages, len(qx.images), host, persp, B, S), "edit_quads_persp_prepare")
+    return host, pages, persp, stage, _to_device(qx, stage), off, xoff
+
+
+def preprocess_quads(images, quads, frames, size=512, perspective=False):
     """preprocess_pages for quadrilateral regions, in one launch.  images: P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device;
     quads: P lists of quads (four corners TL, TR, BR, BL); frames: P lists of (cx2, cy2, crop_scale, ux, uy) (plan_quads gives them).
     Returns the dict preprocess_pages returns, N rows page-major: row b is quad b's oriented crop - the text's baseline horizontal -,
-    masked_image with the quad itself blacked out before resampling, mask the quad as seen in the crop."""
-    qx = _check_quads(images, quads, frames)
-    B, S = len(qx.quads), int(size)
-    host, pages, stage, dbuf, off = _upload_quads(qx, S)
+    masked_image with the quad itself blacked out before resampling, mask the quad as seen in the crop.
+    perspective=True: frames are projective, (ci2, cj2, crop_scale) (plan_quads(..., perspective=True); None plans them here) - the crop
+    is taken through the homography that makes the quad an upright rectangle (csrc/prepost_persp.h), so a trapezoid's text is seen
+    without keystone; the same outputs."""
+    S = int(size)
+    if perspective and frames is None:
+        frames = plan_quads([list(q) for q in quads], [(int(i.shape[0]), int(i.shape[1])) for i in images], True, S)
+    qx = _check_quads(images, quads, frames, perspective)
+    B = len(qx.quads)
+    if perspective:
+        host, pages, persp, stage, dbuf, off, xoff = _upload_quads_persp(qx, S)
+    else:
+        host, pages, stage, dbuf, off = _upload_quads(qx, S)
     base = dbuf.data_ptr()
     with torch.cuda.device(qx.dev):
         image = torch.empty(B, 3, S, S, dtype=torch.float32, device=qx.dev)
         masked = torch.empty(B, 3, S, S, dtype=torch.float32, device=qx.dev)
         mask = torch.empty(B, 1, S, S, dtype=torch.uint8, device=qx.dev)
         mask_lat = torch.empty(B, 1, S // 8, S // 8, dtype=torch.float32, device=qx.dev)
+        if perspective:
+            _cabi.check(_cabi.lib().dmx_preprocess_quads_persp(pages, base + off, len(qx.images), host, base, persp, base + xoff, B, S, _cabi.ptr(image),
+                                                              _cabi.ptr(masked), _cabi.ptr(mask), _cabi.ptr(mask_lat), _cabi.current_stream()),
+                        "preprocess_quads_persp")
+            return dict(image=image, masked_image=masked, mask=mask, mask_latent=mask_lat)
         _cabi.check(_cabi.lib().dmx_preprocess_quads(pages, base + off, len(qx.images), host, base, B, S, _cabi.ptr(image), _cabi.ptr(masked),
                                                     _cabi.ptr(mask), _cabi.ptr(mask_lat), _cabi.current_stream()), "preprocess_quads")
     return dict(image=image, masked_image=masked, mask=mask, mask_latent=mask_lat)
 
 
-def postprocess_quads(image_vae, images, quads, frames, return_mask=False, out=None):
+def postprocess_quads(image_vae, images, quads, frames, return_mask=False, out=None, perspective=False):
     """postprocess_pages for quadrilateral regions, in one launch.  image_vae: fp32 CUDA [N,3,S,S] decoder outputs, page-major; the other
     arguments as for preprocess_quads.  Returns the list of P uint8 [h_p][w_p][3] pages: a pixel inside a quad (edges included) and on
     that quad's crop comes from the decoder output through the inverse of the frame - where quads overlap the later one decides -, every
     other pixel is the original's; with return_mask=True also the list of P union masks uint8 [h_p][w_p] (1 inside any quad).  out: as
-    for postprocess_pages."""
-    qx = _check_quads(images, quads, frames)
+    for postprocess_pages.  perspective=True: frames are projective (None plans them), and a page pixel finds its crop coordinates
+    through the inverse homography; which pixels are pasted, and the union masks, follow the same rule."""
+    if perspective and frames is None:
+        frames = plan_quads([list(q) for q in quads], [(int(i.shape[0]), int(i.shape[1])) for i in images], True, int(image_vae.shape[-1]))
+    qx = _check_quads(images, quads, frames, perspective)
     B = len(qx.quads)
     S, _ = _check_vae(image_vae, B, False)
     if out is not None:
@@ -641,6 +739,13 @@ def postprocess_quads(image_vae, images, quads, frames, return_mask=False, out=N
         out = [torch.empty_like(img) for img in qx.images] if out is None else out
         union = [torch.empty(img.shape[0], img.shape[1], dtype=torch.uint8, device=qx.dev) for img in qx.images] if return_mask else None
     v = image_vae.to(torch.float32).contiguous()
+    if perspective:
+        host, pages, persp, stage, dbuf, off, xoff = _upload_quads_persp(qx, S, out, union)
+        base = dbuf.data_ptr()
+        with torch.cuda.device(qx.dev):
+            _cabi.check(_cabi.lib().dmx_postprocess_paste_quads_persp(_cabi.ptr(v), S, pages, base + off, len(qx.images), host, base, persp, base + xoff, B,
+                                                                     _cabi.current_stream()), "postprocess_paste_quads_persp")
+        return (out, union) if return_mask else out
     host, pages, stage, dbuf, off = _upload_quads(qx, S, out, union)
     base = dbuf.data_ptr()
     with torch.cuda.device(qx.dev):
@@ -649,17 +754,26 @@ def postprocess_quads(image_vae, images, quads, frames, return_mask=False, out=N
     return (out, union) if return_mask else out
 
 
-def rectify_quads(images, quads):
+def rectify_quads(images, quads, perspective=False):
     """Every quad as an upright strip, in one launch: a list of N uint8 CUDA [h_b][w_b][3] tensors, page-major, views of ONE buffer -
     what TrOCRProcessor(images=...) accepts on the device, so the OCR model can read a skewed line.  The strip runs along the quad's
-    baseline at scale 1 (w_b, h_b: rn of half the summed opposite edges, plus 1); an axis-aligned quad gives page[y1:y2+1, x1:x2+1]."""
-    qx = _check_quads(images, quads, None)
+    baseline at scale 1 (w_b, h_b: rn of half the summed opposite edges, plus 1); an axis-aligned quad gives page[y1:y2+1, x1:x2+1].
+    perspective=True: strips of the same sizes through the homography that takes the quad's corners to the strip's corners - a
+    trapezoid comes out upright and without keystone (no frame is needed: the strip is the quad itself)."""
+    qx = _check_quads(images, quads, None, perspective)
     B = len(qx.quads)
-    host, pages, stage, dbuf, off = _upload_quads(qx, 8)               # (the strips depend neither on the frames nor on S)
+    if perspective:
+        host, pages, persp, stage, dbuf, off, xoff = _upload_quads_persp(qx, 0)
+    else:
+        host, pages, stage, dbuf, off = _upload_quads(qx, 8)           # (the strips depend neither on the frames nor on S)
     total = int(host[B - 1].rect_off) + int(host[B - 1].rw) * int(host[B - 1].rh) * 3
     base = dbuf.data_ptr()
     with torch.cuda.device(qx.dev):
         buf = torch.empty(total, dtype=torch.uint8, device=qx.dev)
+        if perspective:
+            _cabi.check(_cabi.lib().dmx_rectify_quads_persp(pages, base + off, len(qx.images), host, base, persp, base + xoff, B, _cabi.ptr(buf), total,
+                                                           _cabi.current_stream()), "rectify_quads_persp")
+            return [buf[int(q.rect_off):int(q.rect_off) + int(q.rw) * int(q.rh) * 3].view(int(q.rh), int(q.rw), 3) for q in host]
         _cabi.check(_cabi.lib().dmx_rectify_quads(pages, base + off, len(qx.images), host, base, B, _cabi.ptr(buf), total, _cabi.current_stream()),
                     "rectify_quads")
     return [buf[int(q.rect_off):int(q.rect_off) + int(q.rw) * int(q.rh) * 3].view(int(q.rh), int(q.rw), 3) for q in host]

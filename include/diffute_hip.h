@@ -1008,6 +1008,49 @@ int dmx_postprocess_paste_quads(const float* image_vae, int S, const dmx_edit_pa
 int dmx_rectify_quads(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_host,
                       const dmx_edit_quad* quads_device, int B, unsigned char* out, long long out_bytes, dmx_stream_t stream);
 
+/* Text in PERSPECTIVE: a projective frame beside the similarity frame of the quad entries (prepost_persp.hip; the arithmetic is stated in
+ * csrc/prepost_persp.h).  A trapezoid - a line on a phone photo, a sign - is no rotated rectangle: through one rotation and one scale the
+ * network sees keystoned text.  Here the homography that takes the quad to its upright rw x rh strip drives the crop (a square window
+ * of side crop_scale STRIP pixels, centred at (ci2 / 2, cj2 / 2) in the strip's pixel-index space, extrapolated by the homography), the
+ * paste (through its inverse) and the rectified strip.  A table of dmx_quad_persp runs parallel to the dmx_edit_quad table, index for
+ * index; dmx_edit_quad keeps its layout, and its similarity frame is not read (any frame edit_quads_prepare accepts will do).  The
+ * caller prepares pages and quads with edit_quads_prepare, fills ci2, cj2, crop_scale of every item and lets edit_quads_persp_prepare
+ * (host-only) fill the three integer maps; S = 0 fills the strip maps alone, which is all rectify_quads_persp reads.
+ *   edit_quads_persp_prepare refuses, by item index, on top of what edit_quads_prepare refuses about pages and quads (tables it did not
+ *           prepare included): rw or rh below 2; an item without a frame (crop_scale 0) or with crop_scale beyond 65535 or a centre beyond
+ *           +-2^20; a crop window or a strip on which the homography's denominator D is not positive at all four corners (the horizon
+ *           crosses it) or on which max D > 4 * min D (the stated cap); a page -> crop denominator that is not positive at the quad's
+ *           corners; any map whose numerators or denominators leave the 64-bit budget of csrc/prepost_persp.h, or whose exact host
+ *           arithmetic leaves 126 bits.
+ *   preprocess_quads_persp / postprocess_paste_quads_persp / rectify_quads_persp: what the quad entries of the same name write, with
+ *           the projective coordinates; mask, blacking-out, taps, rounding and the paste rule are theirs.  The window's centre is not
+ *           moved to keep the window on the page: clamped taps replicate the border.
+ * Each entry is one launch; each checks the host tables again (a bad page or item is named by index and nothing is launched); the
+ * kernels clamp what they read from the device tables exactly as the quad entries do, and paste nothing where a denominator read
+ * from the device table is not positive. */
+typedef struct dmx_persp_map {
+  long long c16[2];                 /* the Q16 image of the grid's centre */
+  long long t[9];                   /* numerators' (t0..t5) and denominator's (t6..t8, t8 = 2^43) coefficients about that centre */
+} dmx_persp_map;
+typedef struct dmx_quad_persp {
+  int ci2, cj2;                     /* the window's centre in half-pixels of the strip's pixel-index space */
+  int crop_scale;                   /* the window's side in strip pixels */
+  int cx2, cy2;                     /* derived: the page-side centre in half-pixels, the origin of the paste map's grid */
+  int reserved;
+  dmx_persp_map crop, paste, strip; /* derived: crop grid -> page, page -> crop, strip grid -> page */
+} dmx_quad_persp;
+int dmx_edit_quads_persp_prepare(const dmx_edit_page* pages, int P, const dmx_edit_quad* quads, dmx_quad_persp* persp, int B, int S);
+int dmx_preprocess_quads_persp(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_host,
+                               const dmx_edit_quad* quads_device, const dmx_quad_persp* persp_host, const dmx_quad_persp* persp_device, int B,
+                               int S, float* out_image, float* out_masked_image, unsigned char* out_mask, float* out_mask_latent,
+                               dmx_stream_t stream);
+int dmx_postprocess_paste_quads_persp(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                      const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device, const dmx_quad_persp* persp_host,
+                                      const dmx_quad_persp* persp_device, int B, dmx_stream_t stream);
+int dmx_rectify_quads_persp(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_host,
+                            const dmx_edit_quad* quads_device, const dmx_quad_persp* persp_host, const dmx_quad_persp* persp_device, int B,
+                            unsigned char* out, long long out_bytes, dmx_stream_t stream);
+
 /* Comparing two versions of a set of pages (metrics.hip): what the scene-text-editing literature reports on the edited box - MSE,
  * PSNR, SSIM - and what changed OUTSIDE all boxes.  P pairs of pages a / b, uint8 [H][W][3] contiguous, both of a pair H x W; B boxes
  * (page, x1, y1, x2, y2), each the slice [y1:y2, x1:x2] of its page: exclusive upper corner, non-empty, inside the page (the read-back's
