@@ -64,31 +64,34 @@ def train_forward(Pu, ucfg, Pv, vcfg, pixel_values, masked_images, masks, ctx, t
     return torch.mean((pred.float() - target.float()) ** 2), pred
 
 
-def unet_train_grads(P, cfg, inp, timesteps, ctx, target, emulate_bf16=False):
+def unet_train_grads(P, cfg, inp, timesteps, ctx, target, emulate_bf16=False, *, grad_scale=1.0, train_points=False, tap=None, dtype=torch.float32):
     """Loss and parameter gradients of one denoiser training step (train_diffute_v1.py:913-925:
     `model_pred = unet(...).sample; loss = F.mse_loss(model_pred.float(), target.float()); accelerator.backward(loss)`),
-    by torch autograd over the restatement.  With emulate_bf16 the forward rounds where the HIP path materialises bf16
-    (the casts are straight-through), the backward arithmetic stays fp32.  Returns (loss, pred, {name: grad})."""
-    Pg = {k: v.detach().clone().to(torch.float32).requires_grad_(True) for k, v in P.items()}
+    by torch autograd over the restatement.  With emulate_bf16 ("bf16" / True, or "fp16") every tensor the HIP path
+    materialises in 16 bits is rounded by a cast; autograd differentiates the cast, so the gradient that flows back through
+    such a point is rounded to the same element: the backward is restated with its rounding points too (fp32 arithmetic in
+    between).  grad_scale: the loss scale of a GradScaler - the backward runs on grad_scale * loss and the returned gradients
+    are divided by it again.  train_points / tap / dtype: see unet.unet_forward.  Returns (loss, pred, {name: grad})."""
+    Pg = {k: v.detach().clone().to(dtype).requires_grad_(True) for k, v in P.items()}
     with torch.enable_grad():
-        pred = unet_forward.__wrapped__(Pg, cfg, inp, timesteps, ctx, emulate_bf16=emulate_bf16)
-        loss = torch.mean((pred.float() - target.float()) ** 2)
-        loss.backward()
-    return float(loss.detach()), pred.detach(), {k: p.grad for k, p in Pg.items()}
+        pred = unet_forward.__wrapped__(Pg, cfg, inp, timesteps, ctx, emulate_bf16=emulate_bf16, train_points=train_points, tap=tap, dtype=dtype)
+        loss = torch.mean((pred.to(dtype) - target.to(dtype)) ** 2)
+        (loss if grad_scale == 1.0 else loss * grad_scale).backward()
+    return float(loss.detach()), pred.detach(), {k: (p.grad if grad_scale == 1.0 else p.grad / grad_scale) for k, p in Pg.items()}
 
 
-def vae_train_grads(P, cfg, x, target, emulate_bf16=False):
+def vae_train_grads(P, cfg, x, target, emulate_bf16=False, *, grad_scale=1.0, train_points=False, dtype=torch.float32):
     """Loss and parameter gradients of one autoencoder training step (train_vae.py:716-736: `pred = vae(x)["sample"]` =
     decode(encode(x).latent_dist.mode()); `loss = F.mse_loss(pred.float(), target.float())`; backward), by torch autograd
-    over the restatement.  Returns (loss, recon, {name: grad})."""
+    over the restatement (grad_scale / train_points as in unet_train_grads).  Returns (loss, recon, {name: grad})."""
     from .vae import gaussian_mode, vae_decode, vae_encode_moments
-    Pg = {k: v.detach().clone().to(torch.float32).requires_grad_(True) for k, v in P.items()}
+    Pg = {k: v.detach().clone().to(dtype).requires_grad_(True) for k, v in P.items()}
     with torch.enable_grad():
-        z = gaussian_mode(vae_encode_moments.__wrapped__(Pg, cfg, x, emulate_bf16=emulate_bf16))
-        recon = vae_decode.__wrapped__(Pg, cfg, z, emulate_bf16=emulate_bf16)
-        loss = torch.mean((recon.float() - target.float()) ** 2)
-        loss.backward()
-    return float(loss.detach()), recon.detach(), {k: p.grad for k, p in Pg.items()}
+        z = gaussian_mode(vae_encode_moments.__wrapped__(Pg, cfg, x, emulate_bf16=emulate_bf16, train_points=train_points, dtype=dtype))
+        recon = vae_decode.__wrapped__(Pg, cfg, z, emulate_bf16=emulate_bf16, train_points=train_points, dtype=dtype)
+        loss = torch.mean((recon.to(dtype) - target.to(dtype)) ** 2)
+        (loss if grad_scale == 1.0 else loss * grad_scale).backward()
+    return float(loss.detach()), recon.detach(), {k: (p.grad if grad_scale == 1.0 else p.grad / grad_scale) for k, p in Pg.items()}
 
 
 def initial_latents(shape, seed=0):

@@ -135,7 +135,33 @@ def _q(x, on):
     train_diffute_v1.py:789-797, BASELINE configs[4])."""
     if not on:
         return x
-    return x.to(torch.float16 if on == "fp16" else torch.bfloat16).to(torch.float32)
+    return x.to(torch.float16 if on == "fp16" else torch.bfloat16).to(x.dtype if x.dtype == torch.float64 else torch.float32)
+
+
+class _RoundGrad(torch.autograd.Function):
+    """identity whose backward rounds the gradient to the 16-bit element: a tensor the training walk materialises in 16 bits
+    only on the way back (dL/dpred, the shortcut-path gradient of a resnet)"""
+
+    @staticmethod
+    def forward(ctx, x, dt):
+        ctx.dt = dt
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(ctx.dt).to(g.dtype), None
+
+
+def _qg(x, on):
+    """Forward: x unchanged.  Backward: the gradient rounded as `_q` would round it."""
+    if not on or not torch.is_grad_enabled():
+        return x
+    return _RoundGrad.apply(x, torch.float16 if on == "fp16" else torch.bfloat16)
+
+
+def _tap(tap, name, x):
+    """`tap(name, tensor) -> tensor` lets a test rewire one named edge of the graph (fault injection); None: no-op."""
+    return x if tap is None else tap(name, x)
 
 
 def timestep_embedding(t, dim):
@@ -157,18 +183,22 @@ def _conv(x, P, p, em, stride=1, padding=1):
     return F.conv2d(x, _q(P[p + "weight"], em), P[p + "bias"], stride=stride, padding=padding)
 
 
-def resnet(x, emb_act, P, p, groups, eps, em):
-    """ResnetBlock2D (Appendix A.1). emb_act = SiLU(emb) or None (VAE)."""
+def resnet(x, emb_act, P, p, groups, eps, em, *, train_points=False, tap=None):
+    """ResnetBlock2D (Appendix A.1). emb_act = SiLU(emb) or None (VAE).
+    train_points: also round where only the TRAINING walk materialises a 16-bit tensor - here the gradient that the shortcut
+    conv sends to x, stored before the norm1 backward adds it (train_common.h res_bwd `dxs`).  Edges a `tap` can rewire:
+    `<p>emb_act` (the time embedding as this block reads it) and `<p>shortcut_in` (x as the shortcut conv reads it)."""
     h = _gn(x, P, p + "norm1.", groups, eps, True, em)
     h = _conv(h, P, p + "conv1.", em)
     if emb_act is not None:
-        tp = F.linear(emb_act, _q(P[p + "time_emb_proj.weight"], em), P[p + "time_emb_proj.bias"])
+        tp = F.linear(_tap(tap, p + "emb_act", emb_act), _q(P[p + "time_emb_proj.weight"], em), P[p + "time_emb_proj.bias"])
         h = h + tp[:, :, None, None]
     h = _q(h, em)
     h = _gn(h, P, p + "norm2.", groups, eps, True, em)
     h = _conv(h, P, p + "conv2.", em)
     if (p + "conv_shortcut.weight") in P:
-        x = F.conv2d(x, _q(P[p + "conv_shortcut.weight"], em), P[p + "conv_shortcut.bias"])
+        xs = _tap(tap, p + "shortcut_in", _qg(x, em) if train_points else x)
+        x = F.conv2d(xs, _q(P[p + "conv_shortcut.weight"], em), P[p + "conv_shortcut.bias"])
     return _q(x + h, em)
 
 
@@ -187,10 +217,12 @@ def _attention(xq, src, P, p, heads, em):
     return F.linear(a, _q(P[p + "to_out.0.weight"], em), P[p + "to_out.0.bias"])
 
 
-def transformer2d(x, ctx, P, p, heads, groups, em):
-    """Transformer2DModel, use_linear_projection=True, one BasicTransformerBlock."""
+def transformer2d(x, ctx, P, p, heads, groups, em, *, train_points=False, tap=None):
+    """Transformer2DModel, use_linear_projection=True, one BasicTransformerBlock.
+    train_points: the training walk stores the FF1 output (`ffh`, both GEGLU halves) in 16 bits before the elementwise GEGLU;
+    inference fuses the GEGLU into the GEMM and never materialises it.  Edge a `tap` can rewire: `<p>residual`."""
     B, C, H, W = x.shape
-    r = x
+    r = _tap(tap, p + "residual", x)
     h = _gn(x, P, p + "norm.", groups, 1e-6, False, em)
     h = h.permute(0, 2, 3, 1).reshape(B, H * W, C)
     h = _q(F.linear(h, _q(P[p + "proj_in.weight"], em), P[p + "proj_in.bias"]), em)
@@ -201,6 +233,8 @@ def transformer2d(x, ctx, P, p, heads, groups, em):
     h = _q(h + _attention(n, ctx, P, t + "attn2.", heads, em), em)
     n = _q(F.layer_norm(h, (C,), P[t + "norm3.weight"], P[t + "norm3.bias"], 1e-5), em)
     g = F.linear(n, _q(P[t + "ff.net.0.proj.weight"], em), P[t + "ff.net.0.proj.bias"])
+    if train_points:
+        g = _q(g, em)
     a, b = g.chunk(2, dim=-1)
     g = _q(a * F.gelu(b), em)                      # exact (erf) GELU
     h = _q(h + F.linear(g, _q(P[t + "ff.net.2.weight"], em), P[t + "ff.net.2.bias"]), em)
@@ -210,18 +244,23 @@ def transformer2d(x, ctx, P, p, heads, groups, em):
 
 
 @torch.no_grad()
-def unet_forward(P, cfg, sample, timestep, ctx, emulate_bf16=False, taps=None):
-    """eps = unet(sample[B,9,h,w], timestep (0-d or [B] int), ctx[B,577,1024]).  NCHW fp32."""
+def unet_forward(P, cfg, sample, timestep, ctx, emulate_bf16=False, taps=None, *, train_points=False, tap=None, dtype=torch.float32):
+    """eps = unet(sample[B,9,h,w], timestep (0-d or [B] int), ctx[B,577,1024]).  NCHW fp32.
+    train_points / tap (used under autograd by pipeline.unet_train_grads): the extra 16-bit materialisation points of the
+    training walk, and a hook that rewires named edges (see resnet / transformer2d); both default to the inference graph.
+    dtype=torch.float64 (with float64 parameters): the arithmetic between the rounding points in double, which makes a
+    16-bit restatement independent of the host's float32 summation order."""
     em = emulate_bf16
+    kw = dict(train_points=train_points, tap=tap)
     boc = cfg["block_out_channels"]; L = cfg["layers_per_block"]
     heads = cfg["attention_head_dim"]; G = cfg["norm_num_groups"]
     B = sample.shape[0]
     t = torch.as_tensor(timestep, dtype=torch.int64).reshape(-1)
     if t.numel() == 1:
         t = t.expand(B)
-    sample = _q(sample.to(torch.float32), em)
-    ctx = _q(ctx.to(torch.float32), em)
-    temb = timestep_embedding(t, boc[0])
+    sample = _q(sample.to(dtype), em)
+    ctx = _q(ctx.to(dtype), em)
+    temb = timestep_embedding(t, boc[0]).to(dtype)
     emb = F.linear(temb, _q(P["time_embedding.linear_1.weight"], em), P["time_embedding.linear_1.bias"])
     emb = F.linear(F.silu(emb), _q(P["time_embedding.linear_2.weight"], em), P["time_embedding.linear_2.bias"])
     emb_act = F.silu(emb)
@@ -230,31 +269,32 @@ def unet_forward(P, cfg, sample, timestep, ctx, emulate_bf16=False, taps=None):
     skips = [h]
     for i, c in enumerate(boc):
         for j in range(L):
-            h = resnet(h, emb_act, P, f"down_blocks.{i}.resnets.{j}.", G, 1e-5, em)
+            h = resnet(h, emb_act, P, f"down_blocks.{i}.resnets.{j}.", G, 1e-5, em, **kw)
             if cfg["down_has_attn"][i]:
-                h = transformer2d(h, ctx, P, f"down_blocks.{i}.attentions.{j}.", heads[i], G, em)
+                h = transformer2d(h, ctx, P, f"down_blocks.{i}.attentions.{j}.", heads[i], G, em, **kw)
             skips.append(h)
         if i < len(boc) - 1:
             h = _q(_conv(h, P, f"down_blocks.{i}.downsamplers.0.conv.", em, stride=2, padding=1), em)
             skips.append(h)
         if taps is not None: taps[f"down{i}"] = h
-    h = resnet(h, emb_act, P, "mid_block.resnets.0.", G, 1e-5, em)
-    h = transformer2d(h, ctx, P, "mid_block.attentions.0.", heads[-1], G, em)
-    h = resnet(h, emb_act, P, "mid_block.resnets.1.", G, 1e-5, em)
+    h = resnet(h, emb_act, P, "mid_block.resnets.0.", G, 1e-5, em, **kw)
+    h = transformer2d(h, ctx, P, "mid_block.attentions.0.", heads[-1], G, em, **kw)
+    h = resnet(h, emb_act, P, "mid_block.resnets.1.", G, 1e-5, em, **kw)
     if taps is not None: taps["mid"] = h
     rheads = list(reversed(heads))
     for i, c in enumerate(reversed(boc)):
         for j in range(L + 1):
             h = torch.cat([h, skips.pop()], dim=1)
-            h = resnet(h, emb_act, P, f"up_blocks.{i}.resnets.{j}.", G, 1e-5, em)
+            h = resnet(h, emb_act, P, f"up_blocks.{i}.resnets.{j}.", G, 1e-5, em, **kw)
             if cfg["up_has_attn"][i]:
-                h = transformer2d(h, ctx, P, f"up_blocks.{i}.attentions.{j}.", rheads[i], G, em)
+                h = transformer2d(h, ctx, P, f"up_blocks.{i}.attentions.{j}.", rheads[i], G, em, **kw)
         if i < len(boc) - 1:
             h = F.interpolate(h, scale_factor=2.0, mode="nearest")
             h = _q(_conv(h, P, f"up_blocks.{i}.upsamplers.0.conv.", em), em)
         if taps is not None: taps[f"up{i}"] = h
     h = _gn(h, P, "conv_norm_out.", G, 1e-5, True, em)
-    return _conv(h, P, "conv_out.", em)        # fp32 eps (kept fp32 by the HIP path too)
+    h = _conv(h, P, "conv_out.", em)           # fp32 eps (kept fp32 by the HIP path too)
+    return _qg(h, em) if train_points else h   # ... but the backward reads dL/deps as a 16-bit GEMM operand
 
 
 def unet_flops(cfg, B, h, w, ctx_len=577, cached_ctx_kv=False):

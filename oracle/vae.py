@@ -10,7 +10,7 @@ from collections import OrderedDict
 import torch
 import torch.nn.functional as F
 
-from .unet import _resnet_spec, _q, _gn, _conv, resnet
+from .unet import _resnet_spec, _q, _qg, _gn, _conv, resnet
 
 SD_VAE = dict(in_channels=3, out_channels=3, latent_channels=4,
               block_out_channels=(128, 256, 512, 512), layers_per_block=2,
@@ -63,8 +63,9 @@ def vae_param_spec(cfg):
     return spec
 
 
-def _mid_attn(x, P, p, groups, em):
-    """Single-head attention over H*W tokens, d=C, with bias on q/k/v/out (Appendix A.2)."""
+def _mid_attn(x, P, p, groups, em, *, train_points=False):
+    """Single-head attention over H*W tokens, d=C, with bias on q/k/v/out (Appendix A.2).
+    train_points: the training walk keeps the softmax P as a 16-bit [S][S] matrix per image (vae_train.hip attn_fwd)."""
     B, C, H, W = x.shape
     r = x
     h = _gn(x, P, p + "group_norm.", groups, 1e-6, False, em)
@@ -73,28 +74,33 @@ def _mid_attn(x, P, p, groups, em):
     k = _q(F.linear(h, _q(P[p + "to_k.weight"], em), P[p + "to_k.bias"]), em)
     v = _q(F.linear(h, _q(P[p + "to_v.weight"], em), P[p + "to_v.bias"]), em)
     s = torch.matmul(q, k.transpose(-1, -2)) * (C ** -0.5)
-    a = _q(torch.matmul(torch.softmax(s, dim=-1), v), em)
+    pr = torch.softmax(s, dim=-1)
+    if train_points:
+        pr = _q(pr, em)
+    a = _q(torch.matmul(pr, v), em)
     a = F.linear(a, _q(P[p + "to_out.0.weight"], em), P[p + "to_out.0.bias"])
     a = a.reshape(B, H, W, C).permute(0, 3, 1, 2)
     return _q(a + r, em)
 
 
 @torch.no_grad()
-def vae_encode_moments(P, cfg, x, emulate_bf16=False):
-    """x [B,3,H,W] -> moments [B,8,H/8,W/8] (mean | logvar), fp32."""
+def vae_encode_moments(P, cfg, x, emulate_bf16=False, *, train_points=False, dtype=torch.float32):
+    """x [B,3,H,W] -> moments [B,8,H/8,W/8] (mean | logvar), fp32.  train_points: see unet.resnet / _mid_attn; dtype: see
+    unet.unet_forward."""
     em = emulate_bf16
+    kw = dict(train_points=train_points)
     boc = cfg["block_out_channels"]; L = cfg["layers_per_block"]; G = cfg["norm_num_groups"]
     e = "encoder."
-    h = _q(_conv(_q(x.to(torch.float32), em), P, e + "conv_in.", em), em)
+    h = _q(_conv(_q(x.to(dtype), em), P, e + "conv_in.", em), em)
     for i, c in enumerate(boc):
         for j in range(L):
-            h = resnet(h, None, P, e + f"down_blocks.{i}.resnets.{j}.", G, 1e-6, em)
+            h = resnet(h, None, P, e + f"down_blocks.{i}.resnets.{j}.", G, 1e-6, em, **kw)
         if i < len(boc) - 1:
             h = F.pad(h, (0, 1, 0, 1))                       # asymmetric pad, then s2 p0
             h = _q(_conv(h, P, e + f"down_blocks.{i}.downsamplers.0.conv.", em, stride=2, padding=0), em)
-    h = resnet(h, None, P, e + "mid_block.resnets.0.", G, 1e-6, em)
-    h = _mid_attn(h, P, e + "mid_block.attentions.0.", G, em)
-    h = resnet(h, None, P, e + "mid_block.resnets.1.", G, 1e-6, em)
+    h = resnet(h, None, P, e + "mid_block.resnets.0.", G, 1e-6, em, **kw)
+    h = _mid_attn(h, P, e + "mid_block.attentions.0.", G, em, **kw)
+    h = resnet(h, None, P, e + "mid_block.resnets.1.", G, 1e-6, em, **kw)
     h = _gn(h, P, e + "conv_norm_out.", G, 1e-6, True, em)
     h = _q(_conv(h, P, e + "conv_out.", em), em)
     return F.conv2d(h, _q(P["quant_conv.weight"], em), P["quant_conv.bias"])
@@ -113,24 +119,27 @@ def gaussian_mode(moments):
 
 
 @torch.no_grad()
-def vae_decode(P, cfg, z, emulate_bf16=False):
-    """z [B,4,h,w] -> image [B,3,8h,8w], fp32."""
+def vae_decode(P, cfg, z, emulate_bf16=False, *, train_points=False, dtype=torch.float32):
+    """z [B,4,h,w] -> image [B,3,8h,8w], fp32.  train_points: see unet.resnet / _mid_attn; dL/dimage is read in 16 bits.
+    dtype: see unet.unet_forward."""
     em = emulate_bf16
+    kw = dict(train_points=train_points)
     boc = cfg["block_out_channels"]; L = cfg["layers_per_block"]; G = cfg["norm_num_groups"]
     d = "decoder."
-    z = _q(F.conv2d(_q(z.to(torch.float32), em), _q(P["post_quant_conv.weight"], em), P["post_quant_conv.bias"]), em)
+    z = _q(F.conv2d(_q(z.to(dtype), em), _q(P["post_quant_conv.weight"], em), P["post_quant_conv.bias"]), em)
     h = _q(_conv(z, P, d + "conv_in.", em), em)
-    h = resnet(h, None, P, d + "mid_block.resnets.0.", G, 1e-6, em)
-    h = _mid_attn(h, P, d + "mid_block.attentions.0.", G, em)
-    h = resnet(h, None, P, d + "mid_block.resnets.1.", G, 1e-6, em)
+    h = resnet(h, None, P, d + "mid_block.resnets.0.", G, 1e-6, em, **kw)
+    h = _mid_attn(h, P, d + "mid_block.attentions.0.", G, em, **kw)
+    h = resnet(h, None, P, d + "mid_block.resnets.1.", G, 1e-6, em, **kw)
     for i, c in enumerate(reversed(boc)):
         for j in range(L + 1):
-            h = resnet(h, None, P, d + f"up_blocks.{i}.resnets.{j}.", G, 1e-6, em)
+            h = resnet(h, None, P, d + f"up_blocks.{i}.resnets.{j}.", G, 1e-6, em, **kw)
         if i < len(boc) - 1:
             h = F.interpolate(h, scale_factor=2.0, mode="nearest")
             h = _q(_conv(h, P, d + f"up_blocks.{i}.upsamplers.0.conv.", em), em)
     h = _gn(h, P, d + "conv_norm_out.", G, 1e-6, True, em)
-    return _conv(h, P, d + "conv_out.", em)
+    h = _conv(h, P, d + "conv_out.", em)
+    return _qg(h, em) if train_points else h
 
 
 def vae_flops(cfg, B, H, W):
