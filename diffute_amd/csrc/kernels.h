@@ -471,3 +471,6 @@ int dmx_gaussian_sample_launch(const float* moments, const float* noise, float* 
 // index in the whole table; dmx_edit_pages_prepare fills the derived fields)
 int dmx_check_edit_items(const char* what, const dmx_edit_item* items, int B, int H, int W, int S, bool prepared, int index0 = 0);
 int dmx_check_edit_pages(const char* what, const dmx_edit_page* pages, int P, const dmx_edit_item* items, int B, int S, bool prepared);
+// what the paged entries ask of the pages' addresses, and the select entries of their scalars (also asked by prepost_blend.hip)
+int dmx_check_page_addresses(const char* what, const dmx_edit_page* pages, int P, bool need_out);
+int dmx_check_select_scalars(const char* what, int K, float threshold);

@@ -9,10 +9,12 @@
 // says where each page lives and which items are its own, and the functions below are called on one-page views of it.
 #include "common.h"
 #include "kernels.h"
+#include "prepost_paste.h"
 #include "prepost_resize.h"
 
 namespace {
 using namespace dmx_resize;
+using namespace dmx_paste;      // PostBatchArgs, select_choices, PostPagesArgs, PageTile, page_tile: shared with prepost_blend.hip
 
 struct PreBatchArgs {
   const unsigned char* img; int H, W;                                  // HWC uint8 image shared by all items
@@ -63,12 +65,6 @@ __global__ __launch_bounds__(256) void dmx_preprocess_pages_kernel(const PrePage
   pre_item(v, b, dx, dy);
 }
 
-struct PostBatchArgs {
-  const float* vae; int S;                     // decoder outputs [B][3][S][S] in [-1, 1]
-  const unsigned char* ori; unsigned char* out; unsigned char* umask; int H, W;
-  const dmx_edit_item* items; int B;
-};
-
 // B chained single pastes in index order leave, at every pixel, the value of the LAST item whose (half-open box) AND (resized crop
 // extent) covers it, computed from that item's decoder output alone, or the original where no item does: scan from the last item down
 // and stop at the first hit.  The integer half of the table is staged in LDS once per block (every pixel of the row scans all of it).
@@ -113,28 +109,6 @@ __global__ __launch_bounds__(256) void dmx_postprocess_batch_kernel(const PostBa
   paste_pixel(p, s_box, s_crop, [](int b) -> int { return b; }, x, y);
 }
 
-// choice[b] for all B items from the score table [B][K]: staged in LDS, one thread per item; `writer` blocks also store it to HBM.
-// Ends with a barrier: s_choice is complete on return.
-__device__ __forceinline__ void select_choices(const float* scores, int B, int K, float threshold, float* s_score, int* s_choice, int* choice,
-                                               bool writer) {
-  for (int i = threadIdx.x; i < B * K; i += blockDim.x) s_score[i] = scores[i];
-  __syncthreads();
-  if ((int)threadIdx.x < B) {
-    const float* sc = s_score + threadIdx.x * K;
-    int best = -1;
-    float bv = 0.f;
-    for (int k = 0; k < K; ++k) {
-      const float v = sc[k];
-      if (v != v) continue;                                                                // NaN
-      if (best < 0 || v > bv) { best = k; bv = v; }
-    }
-    const int ch = best < 0 ? 0 : (bv < threshold ? -1 : best);
-    s_choice[threadIdx.x] = ch;
-    if (writer) choice[threadIdx.x] = ch;
-  }
-  __syncthreads();
-}
-
 // Best of K candidates per item, chosen and pasted in ONE launch: p.vae is [B][K][3][S][S], scores [B][K] lives on the device, so the
 // host never waits for it.  Every block stages the score table in LDS and derives the same choices from it:
 //   choice[b] = arg-max over k of scores[b][k], the lowest k on a tie; a NaN never wins; 0 when every score is NaN;
@@ -155,30 +129,7 @@ __global__ __launch_bounds__(256) void dmx_postprocess_select_kernel(const PostB
 // grid.x: page p owns the blocks [block_lo, block_lo + H * ceil(W / 256)).  A block finds its page by a uniform scan of the (at most
 // 64) block_lo values, then pastes one 256-pixel tile of one row through paste_pixel with the page's view: a pixel scans only its own
 // page's items, last to first.
-struct PostPagesArgs {
-  const float* vae; int S;
-  const dmx_edit_page* pages; int P;
-  const dmx_edit_item* items; int B;
-};
-struct PageTile { PostBatchArgs view; int lo, x, y; };
-
-// false: the block has no pixel to write (a stale table - with a good one every block lies inside its page).  Uniform per block.
-__device__ __forceinline__ bool page_tile(const PostPagesArgs& p, PageTile& t) {
-  int pi = 0;
-  for (int i = 1; i < p.P; ++i) pi = (int)blockIdx.x >= p.pages[i].block_lo ? i : pi;
-  const dmx_edit_page pg = p.pages[pi];
-  if (pg.H <= 0 || pg.W <= 0 || pg.W > DMX_EDIT_PAGE_MAX_W) return false;
-  const int tiles = (pg.W + 255) / 256, local = (int)blockIdx.x - pg.block_lo;
-  if (local < 0 || local / tiles >= pg.H) return false;
-  t.lo = min(max(pg.item_lo, 0), p.B - 1);
-  const int n = min(max(pg.item_hi - t.lo, 1), p.B - t.lo);
-  t.view = PostBatchArgs{p.vae, p.S, (const unsigned char*)pg.original, (unsigned char*)pg.out, (unsigned char*)pg.union_mask, pg.H, pg.W,
-                         p.items + t.lo, n};
-  t.y = local / tiles;
-  t.x = (local % tiles) * 256 + (int)threadIdx.x;
-  return true;
-}
-
+// (PostPagesArgs, PageTile, page_tile: prepost_paste.h)
 __global__ __launch_bounds__(256) void dmx_postprocess_pages_kernel(const PostPagesArgs p) {
   __shared__ int4 s_box[DMX_EDIT_MAX_ITEMS], s_crop[DMX_EDIT_MAX_ITEMS];
   PageTile t;
@@ -264,7 +215,7 @@ extern "C" int dmx_postprocess_paste_batch(const float* image_vae, int S, const 
 }
 
 // what the two select entries ask of their scalars
-static int check_select_scalars(const char* what, int K, float threshold) {
+int dmx_check_select_scalars(const char* what, int K, float threshold) {
   DMX_REQUIRE(K >= 1 && K <= DMX_SELECT_MAX_CANDIDATES, "%s: %d candidates per box, expected 1 .. %d", what, K, DMX_SELECT_MAX_CANDIDATES);
   DMX_REQUIRE(!(threshold != threshold), "%s: the threshold is NaN (pass -inf for none)", what);
   return DMX_OK;
@@ -274,7 +225,7 @@ extern "C" int dmx_postprocess_paste_select(const float* image_vae, int S, const
                                             unsigned char* out_hwc, unsigned char* union_mask, int* choice, int H, int W,
                                             const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, dmx_stream_t stream) {
   DMX_REQUIRE(image_vae && scores && original_hwc && out_hwc && choice && items_device, "postprocess_paste_select: null argument");
-  int rc = check_select_scalars("postprocess_paste_select", K, threshold);
+  int rc = dmx_check_select_scalars("postprocess_paste_select", K, threshold);
   if (rc == DMX_OK) rc = dmx_check_edit_items("postprocess_paste_select", items_host, B, H, W, S, true);
   if (rc != DMX_OK) return rc;
   PostBatchArgs p{image_vae, S, original_hwc, out_hwc, union_mask, H, W, items_device, B};
@@ -317,7 +268,7 @@ int dmx_check_edit_pages(const char* what, const dmx_edit_page* pages, int P, co
   return DMX_OK;
 }
 
-static int check_page_addresses(const char* what, const dmx_edit_page* pages, int P, bool need_out) {
+int dmx_check_page_addresses(const char* what, const dmx_edit_page* pages, int P, bool need_out) {
   for (int q = 0; q < P; ++q) {
     DMX_REQUIRE(pages[q].original, "%s: page %d: null original image", what, q);
     DMX_REQUIRE(!need_out || (pages[q].out && pages[q].out != pages[q].original), "%s: page %d: the output image is null or the original itself", what, q);
@@ -346,7 +297,7 @@ extern "C" int dmx_preprocess_crop_pages(const dmx_edit_page* pages_host, const 
   DMX_REQUIRE(pages_device && items_device && out_image && out_masked_image && out_mask, "preprocess_crop_pages: null argument");
   DMX_REQUIRE(S > 0 && S <= 65535 && S % 8 == 0, "preprocess_crop_pages: S = %d is no positive multiple of 8 (up to 65535)", S);
   int rc = dmx_check_edit_pages("preprocess_crop_pages", pages_host, P, items_host, B, S, true);
-  if (rc == DMX_OK) rc = check_page_addresses("preprocess_crop_pages", pages_host, P, false);
+  if (rc == DMX_OK) rc = dmx_check_page_addresses("preprocess_crop_pages", pages_host, P, false);
   if (rc != DMX_OK) return rc;
   PrePagesArgs p{pages_device, P, items_device, S, out_image, out_masked_image, out_mask, out_mask_latent};
   hipLaunchKernelGGL(dmx_preprocess_pages_kernel, dim3(cdiv(S, 256), S, B), dim3(256), 0, (hipStream_t)stream, p);
@@ -358,7 +309,7 @@ extern "C" int dmx_postprocess_paste_pages(const float* image_vae, int S, const 
   DMX_REQUIRE(image_vae && pages_device && items_device, "postprocess_paste_pages: null argument");
   DMX_REQUIRE(S > 0 && S <= 65535, "postprocess_paste_pages: bad S = %d", S);
   int rc = dmx_check_edit_pages("postprocess_paste_pages", pages_host, P, items_host, B, S, true);
-  if (rc == DMX_OK) rc = check_page_addresses("postprocess_paste_pages", pages_host, P, true);
+  if (rc == DMX_OK) rc = dmx_check_page_addresses("postprocess_paste_pages", pages_host, P, true);
   if (rc != DMX_OK) return rc;
   PostPagesArgs p{image_vae, S, pages_device, P, items_device, B};
   hipLaunchKernelGGL(dmx_postprocess_pages_kernel, dim3(pages_host[P - 1].block_lo + pages_host[P - 1].blocks), dim3(256), 0, (hipStream_t)stream, p);
@@ -371,9 +322,9 @@ extern "C" int dmx_postprocess_paste_select_pages(const float* image_vae, int S,
                                                   dmx_stream_t stream) {
   DMX_REQUIRE(image_vae && scores && choice && pages_device && items_device, "postprocess_paste_select_pages: null argument");
   DMX_REQUIRE(S > 0 && S <= 65535, "postprocess_paste_select_pages: bad S = %d", S);
-  int rc = check_select_scalars("postprocess_paste_select_pages", K, threshold);
+  int rc = dmx_check_select_scalars("postprocess_paste_select_pages", K, threshold);
   if (rc == DMX_OK) rc = dmx_check_edit_pages("postprocess_paste_select_pages", pages_host, P, items_host, B, S, true);
-  if (rc == DMX_OK) rc = check_page_addresses("postprocess_paste_select_pages", pages_host, P, true);
+  if (rc == DMX_OK) rc = dmx_check_page_addresses("postprocess_paste_select_pages", pages_host, P, true);
   if (rc != DMX_OK) return rc;
   PostPagesArgs p{image_vae, S, pages_device, P, items_device, B};
   hipLaunchKernelGGL(dmx_postprocess_select_pages_kernel, dim3(pages_host[P - 1].block_lo + pages_host[P - 1].blocks), dim3(256), 0,

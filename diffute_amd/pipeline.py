@@ -219,7 +219,7 @@ def edit_latents(unet, vae, scheduler, image, masked_image, mask, encoder_hidden
 @torch.no_grad()
 def edit_boxes(unet, vae, scheduler, instance_image, locations, encoder_hidden_states, num_inference_steps, *, origins=None,
                crop_scales=None, rng=None, batch_size=4, generator=None, enc_noise=None, variance_noise=None,
-               return_intermediate=False, size=512, cache_interval=1, texts=None, glyph=None, guidance=None):
+               return_intermediate=False, size=512, cache_interval=1, texts=None, glyph=None, guidance=None, blend=None):
     """text_editing() (app.ipynb:674-846) for several boxes of ONE image as one batch: instance_image uint8 CUDA [h][w][3], locations
     N boxes (x1, y1, x2, y2), encoder_hidden_states [N,L,D] the glyph context of each box.  One preprocess_batch launch, the boxes
     through edit_latents in chunks of `batch_size` (the last chunk may be smaller), one postprocess_batch launch; returns the uint8
@@ -238,16 +238,19 @@ def edit_boxes(unet, vae, scheduler, instance_image, locations, encoder_hidden_s
     glyph_contexts(texts, *glyph), rendered on the device.  Exactly one of encoder_hidden_states and texts must be given.
 
     guidance: a Guidance, denoise's classifier-free guidance for every chunk; an uncond of [N,S,D] is one unconditional context per box
-    and is chunked like encoder_hidden_states."""
+    and is chunked like encoder_hidden_states.
+
+    blend: None - the reference's hard paste -, or a PasteBlend: the paste gets a feathered edge and / or a colour match of every patch
+    against the page around it (prepost.postprocess_batch), so the edited box does not show as a rectangle."""
     return _edit(False, unet, vae, scheduler, [instance_image], [locations], encoder_hidden_states, num_inference_steps, _one(origins),
                  _one(crop_scales), rng, batch_size, generator, enc_noise, variance_noise, return_intermediate, size, cache_interval, texts, glyph,
-                 guidance)
+                 guidance, blend)
 
 
 @torch.no_grad()
 def edit_pages(unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, *, origins=None, crop_scales=None,
                rng=None, batch_size=4, generator=None, enc_noise=None, variance_noise=None, return_intermediate=False, size=512,
-               cache_interval=1, texts=None, glyph=None, guidance=None):
+               cache_interval=1, texts=None, glyph=None, guidance=None, blend=None):
     """edit_boxes for boxes on SEVERAL pages as one batch - what a service holding requests for different images, or a training batch
     of one box per image, needs.  images: a list of P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device; locations: P lists of
     boxes (x1, y1, x2, y2); origins / crop_scales: None or P lists, as for edit_boxes per page (what is not given is planned page after
@@ -257,16 +260,18 @@ def edit_pages(unet, vae, scheduler, images, locations, encoder_hidden_states, n
     One preprocess_pages launch, the N rows through edit_latents in chunks of `batch_size` (chunks cross page boundaries; every box
     starts from the seed-0 single-sample draw), one postprocess_pages launch.  Returns the list of P edited pages, with
     return_intermediate=True also image_vae [N,3,S,S] and the preprocess dict.  With one page this is [edit_boxes(...)], bit for bit.
-    texts / glyph: as for edit_boxes, N strings page-major.  guidance: as for edit_boxes, a per-box uncond [N,S,D] page-major."""
+    texts / glyph: as for edit_boxes, N strings page-major.  guidance: as for edit_boxes, a per-box uncond [N,S,D] page-major.
+    blend: as for edit_boxes."""
     return _edit(True, unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, origins, crop_scales, rng,
-                 batch_size, generator, enc_noise, variance_noise, return_intermediate, size, cache_interval, texts, glyph, guidance)
+                 batch_size, generator, enc_noise, variance_noise, return_intermediate, size, cache_interval, texts, glyph, guidance, blend)
 
 
 def _edit(paged, unet, vae, scheduler, images, locations, encoder_hidden_states, num_inference_steps, origins, crop_scales, rng, batch_size,
-          generator, enc_noise, variance_noise, return_intermediate, size, cache_interval=1, texts=None, glyph=None, guidance=None):
+          generator, enc_noise, variance_noise, return_intermediate, size, cache_interval=1, texts=None, glyph=None, guidance=None, blend=None):
     """edit_boxes (paged=False: one page, its lists wrapped into one-element lists) and edit_pages"""
     if int(batch_size) < 1:
         raise ValueError("batch_size must be at least 1")
+    _check_blend(blend)
     cache_interval = _check_cache_interval(cache_interval)
     images, locations, origins, crop_scales, sizes, N = _page_lists(paged, images, locations, origins, crop_scales)
     _check_contexts(N, encoder_hidden_states, texts, glyph)
@@ -276,14 +281,14 @@ def _edit(paged, unet, vae, scheduler, images, locations, encoder_hidden_states,
     pre = (prepost.preprocess_pages if paged else prepost.preprocess_batch)(*where, size=size)
     image_vae = _edit_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
                            enc_noise, variance_noise, int(size), cache_interval, guidance)
-    out = (prepost.postprocess_pages if paged else prepost.postprocess_batch)(image_vae, *where)
+    out = (prepost.postprocess_pages if paged else prepost.postprocess_batch)(image_vae, *where, blend=blend)
     return (out, image_vae, pre) if return_intermediate else out
 
 
 @torch.no_grad()
 def edit_quads(unet, vae, scheduler, images, quads, encoder_hidden_states, num_inference_steps, *, frames=None, batch_size=4, generator=None,
                enc_noise=None, variance_noise=None, return_intermediate=False, size=512, cache_interval=1, texts=None, glyph=None, guidance=None,
-               perspective=False):
+               perspective=False, blend=None):
     """edit_pages for skewed and rotated text: every region is a QUAD - the four corners of the line as an OCR record gives them (top-left,
     top-right, bottom-right, bottom-left as read) - instead of a rectangle.  images: a list of P contiguous uint8 CUDA [h_p][w_p][3] tensors
     on one device; quads: P lists of quads; frames: None or P lists of oriented crops (cx2, cy2, crop_scale, ux, uy), planned by
@@ -300,7 +305,12 @@ def edit_quads(unet, vae, scheduler, images, quads, encoder_hidden_states, num_i
     planned by prepost.plan_quads(..., perspective=True) where not given.  The crop is taken through the homography that makes the quad an
     upright rectangle, so the network sees the text without keystone, and the paste goes back through its inverse; everything between the
     two launches is the same.  Limits: the window is not moved to stay on the page (the border is replicated), a window over which the
-    homography's denominator changes by more than 4x is refused, curved text is out."""
+    homography's denominator changes by more than 4x is refused, curved text is out.
+
+    blend: must be None.  The feathered, colour-matched paste of edit_boxes is not built for quads: the ramp would have to be measured in
+    the strip's coordinates, not the page's."""
+    if blend is not None:
+        raise NotImplementedError("edit_quads: blend is not supported for quads (the ramp would have to be measured in strip coordinates); pass None")
     perspective = bool(perspective)
     if int(batch_size) < 1:
         raise ValueError("batch_size must be at least 1")
@@ -324,6 +334,11 @@ def edit_quads(unet, vae, scheduler, images, quads, encoder_hidden_states, num_i
                            enc_noise, variance_noise, int(size), cache_interval, guidance)
     out = prepost.postprocess_quads(image_vae, images, quads, frames, perspective=perspective)
     return (out, image_vae, pre) if return_intermediate else out
+
+
+def _check_blend(blend):
+    if blend is not None and not isinstance(blend, prepost.PasteBlend):
+        raise TypeError(f"blend: expected a PasteBlend or None, got {type(blend).__name__}")
 
 
 def _one(lst):
@@ -518,7 +533,7 @@ def _candidate_rows(unet, vae, scheduler, pre, dev, ctx, num_inference_steps, se
 def edit_boxes_verified(unet, vae, scheduler, ocr, processor, instance_image, locations, encoder_hidden_states, labels, num_inference_steps, *,
                         candidates=4, seeds=None, min_score=None, batch_size=4, ocr_batch_size=32, origins=None, crop_scales=None, rng=None,
                         generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False, cache_interval=1, texts=None,
-                        glyph=None, guidance=None):
+                        glyph=None, guidance=None, blend=None):
     """edit_boxes with a read-back: K = `candidates` edits per box from K starting noises, each read by the OCR model `ocr` (a
     VisionEncoderDecoderModel) against the text the box should show, the best-reading one pasted (the reference sketches the read-back at
     app.ipynb:842-846).  labels: int64 [N,T] token ids of the requested texts, -100 = padding (the tokenizer is out of scope).
@@ -534,34 +549,38 @@ def edit_boxes_verified(unet, vae, scheduler, ocr, processor, instance_image, lo
     Returns the uint8 [h][w][3] page, or a VerifiedEdit with return_intermediate=True.  candidates=1 with min_score=None returns the
     page of edit_boxes with the same arguments, bit for bit.  cache_interval: denoise's, for every chunk of candidate rows.
     texts / glyph: as for edit_boxes, in place of encoder_hidden_states (labels stay token ids: the tokenizer is out of scope).
-    guidance: as for edit_boxes; a per-box uncond [N,S,D] is shared by the box's K candidates, like its glyph context."""
+    guidance: as for edit_boxes; a per-box uncond [N,S,D] is shared by the box's K candidates, like its glyph context.
+    blend: as for edit_boxes, applied to the chosen candidates (choose -> [stats ->] paste on the device, still no score read on the host).
+    The read-back scores the candidates as the hard paste would show them."""
     return _edit_verified(False, unet, vae, scheduler, ocr, processor, [instance_image], [locations], encoder_hidden_states, labels,
                           num_inference_steps, candidates, seeds, min_score, batch_size, ocr_batch_size, _one(origins), _one(crop_scales), rng,
-                          generator, enc_noise, variance_noise, size, return_intermediate, cache_interval, texts, glyph, guidance)
+                          generator, enc_noise, variance_noise, size, return_intermediate, cache_interval, texts, glyph, guidance, blend)
 
 
 @torch.no_grad()
 def edit_pages_verified(unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps, *,
                         candidates=4, seeds=None, min_score=None, batch_size=4, ocr_batch_size=32, origins=None, crop_scales=None, rng=None,
                         generator=None, enc_noise=None, variance_noise=None, size=512, return_intermediate=False, cache_interval=1, texts=None,
-                        glyph=None, guidance=None):
+                        glyph=None, guidance=None, blend=None):
     """edit_boxes_verified for boxes on several pages: images / locations / origins / crop_scales as for edit_pages, everything per box
     (encoder_hidden_states [N,L,D], labels [N,T], enc_noise [N,4,h,w]) page-major.  The N*K rows go through edit_boxes_verified's chunk
     loop, prepost.readback_pixel_values_pages, ocr.score and prepost.postprocess_select_pages - chunks cross page boundaries, no score is
     read on the host.  Returns the list of P pages, or a VerifiedEdit whose `image` is that list with return_intermediate=True.
-    candidates=1 with min_score=None returns edit_pages' pages, bit for bit.  texts / glyph, guidance: as for edit_boxes, page-major."""
+    candidates=1 with min_score=None returns edit_pages' pages, bit for bit.  texts / glyph, guidance: as for edit_boxes, page-major.
+    blend: as for edit_boxes_verified."""
     return _edit_verified(True, unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps,
                           candidates, seeds, min_score, batch_size, ocr_batch_size, origins, crop_scales, rng, generator, enc_noise,
-                          variance_noise, size, return_intermediate, cache_interval, texts, glyph, guidance)
+                          variance_noise, size, return_intermediate, cache_interval, texts, glyph, guidance, blend)
 
 
 def _edit_verified(paged, unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps, candidates,
                    seeds, min_score, batch_size, ocr_batch_size, origins, crop_scales, rng, generator, enc_noise, variance_noise, size,
-                   return_intermediate, cache_interval=1, texts=None, glyph=None, guidance=None):
+                   return_intermediate, cache_interval=1, texts=None, glyph=None, guidance=None, blend=None):
     """edit_boxes_verified (paged=False: one page, its lists wrapped into one-element lists) and edit_pages_verified.  Every argument is
     checked on the host side first: nothing touches the GPU and no crop is planned - so nothing is drawn from rng - before all have passed."""
     images, locations, origins, crop_scales, sizes, N = _page_lists(paged, images, locations, origins, crop_scales)
     K, seeds = _check_verified_counts(N, candidates, seeds, min_score, batch_size, ocr_batch_size)
+    _check_blend(blend)
     cache_interval = _check_cache_interval(cache_interval)
     _check_verified_labels(ocr, N, encoder_hidden_states, labels, texts, glyph)
     guidance = _check_guidance(guidance, encoder_hidden_states, N)
@@ -577,7 +596,7 @@ def _edit_verified(paged, unet, vae, scheduler, ocr, processor, images, location
                                 generator, enc_noise, variance_noise, int(size), cache_interval, guidance)
     pixel_values = (prepost.readback_pixel_values_pages if paged else prepost.readback_pixel_values)(image_vae, *where, ip)
     scores = _score_candidates(ocr, pixel_values, labels, N, K, int(ocr_batch_size))
-    out, choice = (prepost.postprocess_select_pages if paged else prepost.postprocess_select_batch)(image_vae, scores, *where, threshold=min_score)
+    out, choice = (prepost.postprocess_select_pages if paged else prepost.postprocess_select_batch)(image_vae, scores, *where, threshold=min_score, blend=blend)
     return VerifiedEdit(out, choice, scores, image_vae, pixel_values, pre) if return_intermediate else out
 
 

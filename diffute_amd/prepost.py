@@ -291,6 +291,127 @@ def _preprocess(bx, size):
     return dict(image=image, masked_image=masked, mask=mask, mask_latent=mask_lat)
 
 
+class PasteBlend:
+    """How the batched pastes put a generated patch onto the page (include/diffute_hip.h dmx_paste_blend; integers throughout):
+    feather - the width f of the linear ramp at the edge of the paste rectangle: the weight of the patch is min(d + 1, f + 1) / (f + 1)
+              at distance d from the rectangle's edge (0 on the edge), so f = 0 is a hard edge;
+    grow - the paste rectangle is the box grown by g pixels on every side (clipped to the crop).  With grow >= feather the whole box is
+              fully generated and the ramp lies around it - the setting for tight OCR boxes; with grow = 0 the ramp lies INSIDE the box;
+    match_color - shift every channel of the patch by the mean difference between the original page and the patch over a ring of
+              `ring` pixels around the paste rectangle, at most `max_shift` levels (a mean shift of bytes: no gain, no gamma).
+    PasteBlend() - all off - pastes what blend=None pastes, bit for bit.  Quads are out of scope (edit_quads refuses a blend)."""
+    __slots__ = ("feather", "grow", "match_color", "ring", "max_shift")
+
+    def __init__(self, feather=0, grow=0, match_color=False, ring=8, max_shift=32):
+        cap = _cabi.PASTE_BLEND_MAX
+        for name, v, lo, hi in (("feather", feather, 0, cap), ("grow", grow, 0, cap), ("ring", ring, 1, cap), ("max_shift", max_shift, 0, 255)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"PasteBlend: {name} must be an integer, got {v!r}")
+            if not lo <= v <= hi:
+                raise ValueError(f"PasteBlend: {name} = {v}, expected {lo} .. {hi}")
+        if not isinstance(match_color, (bool, np.bool_)):
+            raise TypeError(f"PasteBlend: match_color must be a bool, got {match_color!r}")
+        self.feather, self.grow, self.match_color, self.ring, self.max_shift = int(feather), int(grow), bool(match_color), int(ring), int(max_shift)
+
+    def __repr__(self):
+        return (f"PasteBlend(feather={self.feather}, grow={self.grow}, match_color={self.match_color}, ring={self.ring}, "
+                f"max_shift={self.max_shift})")
+
+    def grown(self, locations, h=None, w=None):
+        """the boxes grown by `grow` - every paste rectangle lies inside its grown box - as [(x1, y1, x2, y2)], clipped to an h x w page if
+        the size is given: what metrics.outside_diff takes to show that nothing outside the paste rectangles changed"""
+        g, out = self.grow, []
+        for loc in locations:
+            x1, y1, x2, y2 = (int(v) for v in loc[:4])
+            x1, y1, x2, y2 = x1 - g, y1 - g, x2 + g, y2 + g
+            if w is not None:
+                x1, x2 = max(x1, 0), min(x2, int(w))
+            if h is not None:
+                y1, y2 = max(y1, 0), min(y2, int(h))
+            out.append((x1, y1, x2, y2))
+        return out
+
+    def _struct(self):
+        return _cabi.PasteBlend(self.feather, self.grow, self.ring, self.max_shift, int(self.match_color))
+
+
+def _check_blend(blend):
+    if not isinstance(blend, PasteBlend):
+        raise TypeError(f"blend: expected a PasteBlend or None, got {type(blend).__name__}")
+    return blend
+
+
+def _check_scores(scores, B, K, threshold):
+    if not (isinstance(scores, torch.Tensor) and scores.is_cuda):
+        raise TypeError("scores: expected a CUDA tensor")
+    if tuple(scores.shape) != (B, K):
+        raise ValueError(f"scores must be [{B},{K}], got {tuple(scores.shape)}")
+    thr = float("-inf") if threshold is None else float(threshold)
+    if thr != thr:
+        raise ValueError("threshold is NaN")
+    return thr
+
+
+def _choose(lib, scores, B, K, thr, dev):
+    """choice int32 [B] on the device from scores [B,K], by the rule of the select pastes (dmx_select_choices: a launch of its own)"""
+    sc = scores.to(torch.float32).contiguous()
+    choice = torch.empty(B, dtype=torch.int32, device=dev)
+    _cabi.check(lib.dmx_select_choices(_cabi.ptr(sc), B, K, thr, _cabi.ptr(choice), _cabi.current_stream()), "select_choices", lib)
+    return choice
+
+
+def _color_stats(lib, bx, v, S, K, choice, bs, host, pages, base, off_pages):
+    """stats int64 [B,4] on the device: one launch, one block per item"""
+    B, img = len(bx.locations), bx.images[0]
+    stats = torch.empty(B, 4, dtype=torch.int64, device=bx.dev)
+    if bx.paged:
+        _cabi.check(lib.dmx_paste_color_stats_pages(_cabi.ptr(v), S, pages, base + off_pages, len(bx.images), host, base, B, ctypes.byref(bs),
+                                                    _cabi.ptr(choice), K, _cabi.ptr(stats), _cabi.current_stream()), "paste_color_stats_pages", lib)
+    else:
+        _cabi.check(lib.dmx_paste_color_stats(_cabi.ptr(v), S, _cabi.ptr(img), img.shape[0], img.shape[1], host, base, B, ctypes.byref(bs),
+                                              _cabi.ptr(choice), K, _cabi.ptr(stats), _cabi.current_stream()), "paste_color_stats", lib)
+    return stats
+
+
+def _blend_paste(bx, image_vae, blend, return_mask, out, scores=None, threshold=None):
+    """the blended pastes: [choose ->] [stats ->] paste, every launch on the current stream, nothing read on the host.  scores given:
+    image_vae is [B,K,3,S,S] and (out, choice[, union]) comes back, as from the select pastes"""
+    blend = _check_blend(blend)
+    B, img, select = len(bx.locations), bx.images[0], scores is not None
+    S, K = _check_vae(image_vae, B, select)
+    thr = _check_scores(scores, B, K, threshold) if select else None
+    out, union = _paste_outputs(bx, out, return_mask)
+    v = image_vae.to(torch.float32).contiguous()
+    host, pages, stage, dbuf, offs = _upload(bx, S, out, union) if bx.paged else _upload(bx, S)
+    base, bs, lib = dbuf.data_ptr(), blend._struct(), _cabi.lib()
+    with torch.cuda.device(bx.dev):
+        choice = _choose(lib, scores, B, K, thr, bx.dev) if select else None
+        stats = _color_stats(lib, bx, v, S, K, choice, bs, host, pages, base, offs[0]) if blend.match_color else None
+        rest = (ctypes.byref(bs), _cabi.ptr(stats), _cabi.ptr(choice), K, _cabi.current_stream())
+        if bx.paged:
+            _cabi.check(lib.dmx_postprocess_paste_blend_pages(_cabi.ptr(v), S, pages, base + offs[0], len(bx.images), host, base, B, *rest),
+                        "postprocess_paste_blend_pages", lib)
+        else:
+            _cabi.check(lib.dmx_postprocess_paste_blend(_cabi.ptr(v), S, _cabi.ptr(img), _cabi.ptr(out), _cabi.ptr(union), img.shape[0], img.shape[1],
+                                                        host, base, B, *rest), "postprocess_paste_blend", lib)
+    if select:
+        return (out, choice, union) if return_mask else (out, choice)
+    return (out, union) if return_mask else out
+
+
+def _stats_only(bx, image_vae, blend, choice):
+    blend = _check_blend(blend)
+    B = len(bx.locations)
+    S, K = _check_vae(image_vae, B, choice is not None)
+    if choice is not None and not (isinstance(choice, torch.Tensor) and choice.is_cuda and choice.dtype == torch.int32 and choice.is_contiguous()
+                                   and tuple(choice.shape) == (B,)):
+        raise ValueError(f"choice must be a contiguous int32 CUDA tensor [{B}]")
+    v = image_vae.to(torch.float32).contiguous()
+    host, pages, stage, dbuf, offs = _upload(bx, S)
+    with torch.cuda.device(bx.dev):
+        return _color_stats(_cabi.lib(), bx, v, S, K, choice, blend._struct(), host, pages, dbuf.data_ptr(), offs[0])
+
+
 def _paste(bx, image_vae, return_mask, out):
     B, img = len(bx.locations), bx.images[0]
     S, _ = _check_vae(image_vae, B, False)
@@ -434,19 +555,38 @@ def preprocess_pages(images, locations, origins, crop_scales, size=512):
     return _preprocess(_paged(images, locations, origins, crop_scales), size)
 
 
-def postprocess_batch(image_vae, instance_image, locations, origins, crop_scales, return_mask=False):
+def postprocess_batch(image_vae, instance_image, locations, origins, crop_scales, return_mask=False, blend=None):
     """image_vae: fp32 CUDA [B,3,S,S] decoder outputs in [-1,1], one per box; returns the uint8 [h][w][3] image that B chained
     postprocess() calls in box order leave (a later box wins where boxes overlap), in one launch.  return_mask=True also returns the
-    union of the boxes as uint8 [h][w] in {0, 1} (the app shows mask * 255)."""
-    return _paste(_one_page(instance_image, locations, origins, crop_scales), image_vae, return_mask, None)
+    union of the boxes as uint8 [h][w] in {0, 1} (the app shows mask * 255).
+    blend: None - the hard paste above -, or a PasteBlend: feathered edge and / or colour match ([stats ->] blended paste, one launch
+    each; the chain of single blended pastes in box order).  The mask is then the union of the PASTE RECTANGLES (half-open, the boxes
+    grown by blend.grow and clipped to their crops): the result equals the original wherever it is 0."""
+    bx = _one_page(instance_image, locations, origins, crop_scales)
+    return _paste(bx, image_vae, return_mask, None) if blend is None else _blend_paste(bx, image_vae, blend, return_mask, None)
 
 
-def postprocess_pages(image_vae, images, locations, origins, crop_scales, return_mask=False, out=None):
+def postprocess_pages(image_vae, images, locations, origins, crop_scales, return_mask=False, out=None, blend=None):
     """postprocess_batch for boxes on several pages, in one launch.  image_vae: fp32 CUDA [N,3,S,S] decoder outputs, page-major; the
     other arguments as for preprocess_pages.  Returns the list of P uint8 [h_p][w_p][3] pages - page p is postprocess_batch of its own
     boxes (a later box wins where boxes overlap) -, with return_mask=True also the list of P union masks uint8 [h_p][w_p].  out
-    (optional): a list of P preallocated contiguous uint8 tensors of the pages' shapes, distinct from `images`, to write into."""
-    return _paste(_paged(images, locations, origins, crop_scales), image_vae, return_mask, out)
+    (optional): a list of P preallocated contiguous uint8 tensors of the pages' shapes, distinct from `images`, to write into.
+    blend: as for postprocess_batch."""
+    bx = _paged(images, locations, origins, crop_scales)
+    return _paste(bx, image_vae, return_mask, out) if blend is None else _blend_paste(bx, image_vae, blend, return_mask, out)
+
+
+def paste_color_stats(image_vae, instance_image, locations, origins, crop_scales, blend, choice=None):
+    """The colour statistics a blended paste with blend.match_color uses, int64 CUDA [B,4]: per box n - the pixels of the ring of
+    blend.ring pixels around its paste rectangle, inside its crop - and D_r, D_g, D_b - the sums over the ring of (original - generated
+    byte), clamped to +- blend.max_shift * n.  Read from the ORIGINAL page and the box's own decoder output: a box's numbers do not depend
+    on the other boxes.  image_vae: [B,3,S,S], or with choice (int32 CUDA [B], -1 = skipped: zeros) [B,K,3,S,S]."""
+    return _stats_only(_one_page(instance_image, locations, origins, crop_scales), image_vae, blend, choice)
+
+
+def paste_color_stats_pages(image_vae, images, locations, origins, crop_scales, blend, choice=None):
+    """paste_color_stats for boxes on several pages: int64 CUDA [N,4], page-major, every box against its own page"""
+    return _stats_only(_paged(images, locations, origins, crop_scales), image_vae, blend, choice)
 
 
 def readback_pixel_values(image_vae, instance_image, locations, origins, crop_scales, processor, return_resized=False, out=None, out_resized=None):
@@ -468,21 +608,29 @@ def readback_pixel_values_pages(image_vae, images, locations, origins, crop_scal
     return _readback(_paged(images, locations, origins, crop_scales), image_vae, ip, return_resized, out, out_resized)
 
 
-def postprocess_select_batch(image_vae, scores, instance_image, locations, origins, crop_scales, threshold=None, return_mask=False):
+def postprocess_select_batch(image_vae, scores, instance_image, locations, origins, crop_scales, threshold=None, return_mask=False, blend=None):
     """Choose and paste in ONE launch, without reading the scores on the host.  image_vae: fp32 CUDA [B,K,3,S,S]; scores: fp32 CUDA [B,K].
     choice[b] = arg-max over k of scores[b] (lowest k on a tie; a NaN never wins; 0 when every score is NaN), or -1 when the best score
     is below `threshold` (None: no threshold) - that box then keeps the original pixels.  Returns (out, choice): the uint8 [h][w][3] page
     postprocess_batch gives for the chosen rows over the boxes that were kept, and choice int32 [B] on the device; with return_mask=True
-    also the union of ALL boxes as uint8 [h][w]."""
-    return _select_paste(_one_page(instance_image, locations, origins, crop_scales), image_vae, scores, threshold, return_mask, None)
+    also the union of ALL boxes as uint8 [h][w].
+    blend: None, or a PasteBlend: choose -> [stats ->] blended paste of the chosen rows, one launch each and still no score read on the
+    host; the mask is then the union of the paste rectangles of all boxes (postprocess_batch)."""
+    bx = _one_page(instance_image, locations, origins, crop_scales)
+    if blend is None:
+        return _select_paste(bx, image_vae, scores, threshold, return_mask, None)
+    return _blend_paste(bx, image_vae, blend, return_mask, None, scores, threshold)
 
 
-def postprocess_select_pages(image_vae, scores, images, locations, origins, crop_scales, threshold=None, return_mask=False, out=None):
+def postprocess_select_pages(image_vae, scores, images, locations, origins, crop_scales, threshold=None, return_mask=False, out=None, blend=None):
     """postprocess_select_batch for boxes on several pages, in one launch: image_vae fp32 CUDA [N,K,3,S,S], scores fp32 CUDA [N,K], both
     page-major.  Returns (pages, choice): the list of P uint8 pages, page p being what postprocess_select_batch gives for its own boxes,
     and choice int32 [N] on the device, by the same rule; with return_mask=True also the list of P union masks.  out as for
-    postprocess_pages."""
-    return _select_paste(_paged(images, locations, origins, crop_scales), image_vae, scores, threshold, return_mask, out)
+    postprocess_pages.  blend: as for postprocess_select_batch."""
+    bx = _paged(images, locations, origins, crop_scales)
+    if blend is None:
+        return _select_paste(bx, image_vae, scores, threshold, return_mask, out)
+    return _blend_paste(bx, image_vae, blend, return_mask, out, scores, threshold)
 
 
 # ------------------------------------------------------------------------------------------------ quadrilateral regions, oriented crops

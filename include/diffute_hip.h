@@ -963,6 +963,50 @@ int dmx_postprocess_paste_select_pages(const float* image_vae, int S, const floa
                                        const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
                                        const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, dmx_stream_t stream);
 
+/* Seam-free paste (prepost_blend.hip): the pastes above with a feathered edge and a colour match of the generated patch against its
+ * surroundings, in integers throughout.  For item b with box (x1, y1, x2, y2) and clipped crop extent E = [xs, xs+cw) x [ys, ys+ch),
+ * G(x, y, c) is the byte the plain paste would write at page pixel (x, y) - defined on all of E, not only inside the box.
+ *   paste rectangle  R = [x1-grow, x2+grow) x [y1-grow, y2+grow) intersected with E; an empty R pastes nothing.
+ *   colour statistics (match_color): over the ring Q = ([x1-grow-ring, x2+grow+ring) x [y1-grow-ring, y2+grow+ring) in E) \ R of the
+ *           ORIGINAL page and the item's own decoder row, never of another item's paste: n = |Q| and per channel
+ *           D_c = sum over Q of (original - G), clamped to [-max_shift * n, max_shift * n].  Integer sums: any order is exact.
+ *   corrected byte   g1 = clamp(floor((2 (G n + D_c) + n) / (2 n)), 0, 255) when match_color and n > 0, else G (floor division; this is
+ *           G + floor((2 D_c + n) / (2 n)), one constant per item and channel: a mean shift, no gain).
+ *   weight           F = feather + 1, d = the pixel's distance to the nearest edge of R (0 on the edge), a = min(d + 1, F).
+ *   blend            cur' = floor((2 (a g1 + (F - a) cur) + F) / (2 F)).
+ * A page pixel starts as the original byte and is updated by every item whose R covers it, in ascending index order; an item with
+ * choice[b] < 0 updates nothing.  feather = grow = 0 without match_color is the plain paste, bit for bit.  With grow >= feather the whole
+ * box is fully generated and the ramp lies in the ring around it; with grow = 0 the ramp lies inside the box.
+ *   paste_color_stats[_pages]: image_vae fp32 [B*K][3][S][S]; choice int32 [B] on the device or NULL (then K must be 1): item b reads
+ *           row b * K + choice[b], choice[b] < 0 = skipped.  stats (device, out) [B][4] = n, D_r, D_g, D_b, clamped; a skipped item
+ *           writes zeros.  One block per item: an item's numbers do not depend on the rest of the table.
+ *   postprocess_paste_blend[_pages]: the arguments of postprocess_paste_batch / _pages, then blend, stats (what paste_color_stats wrote;
+ *           NULL without match_color), choice and K as above.  union_mask: 1 where the R of any item (skipped ones included) covers
+ *           the pixel, and out == original wherever it is 0.
+ *   select_choices: choice[b] by the rule of postprocess_paste_select from scores fp32 [B][K] on the device, as a launch of its own
+ *           (one block), so choose -> stats -> paste runs without the host reading a score.
+ * Refused (DMX_ERR_ARG, nothing launched): feather, grow < 0 or > DMX_PASTE_BLEND_MAX, ring < 1 or > DMX_PASTE_BLEND_MAX, max_shift
+ * outside 0 .. 255, match_color without stats, K outside 1 .. DMX_SELECT_MAX_CANDIDATES, K > 1 without choice, and whatever the plain
+ * entries refuse.  The kernels clamp what they read from the device tables exactly as the plain pastes do; a stale choice or stats
+ * table changes bytes inside the paste rectangles, never an address. */
+#define DMX_PASTE_BLEND_MAX 1048576
+typedef struct dmx_paste_blend {
+  int feather, grow, ring, max_shift, match_color;
+} dmx_paste_blend;
+int dmx_paste_color_stats(const float* image_vae, int S, const unsigned char* original_hwc, int H, int W, const dmx_edit_item* items_host,
+                          const dmx_edit_item* items_device, int B, const dmx_paste_blend* blend, const int* choice, int K, long long* stats,
+                          dmx_stream_t stream);
+int dmx_paste_color_stats_pages(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, const dmx_paste_blend* blend,
+                                const int* choice, int K, long long* stats, dmx_stream_t stream);
+int dmx_postprocess_paste_blend(const float* image_vae, int S, const unsigned char* original_hwc, unsigned char* out_hwc,
+                                unsigned char* union_mask, int H, int W, const dmx_edit_item* items_host, const dmx_edit_item* items_device,
+                                int B, const dmx_paste_blend* blend, const long long* stats, const int* choice, int K, dmx_stream_t stream);
+int dmx_postprocess_paste_blend_pages(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                      const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, const dmx_paste_blend* blend,
+                                      const long long* stats, const int* choice, int K, dmx_stream_t stream);
+int dmx_select_choices(const float* scores, int B, int K, float threshold, int* choice, dmx_stream_t stream);
+
 /* Skewed and rotated text: QUADRILATERAL regions with ORIENTED crops (prepost_quad.hip; the arithmetic is stated in csrc/prepost_quad.h).
  * An item is a dmx_edit_quad: the four corners of a text line as an OCR record gives them (top-left, top-right, bottom-right,
  * bottom-left as read; clockwise with y down) and a frame - a square crop of side crop_scale, centred at (cx2 / 2, cy2 / 2) in
