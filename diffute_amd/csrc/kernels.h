@@ -471,6 +471,10 @@ int dmx_gaussian_sample_launch(const float* moments, const float* noise, float* 
 // index in the whole table; dmx_edit_pages_prepare fills the derived fields)
 int dmx_check_edit_items(const char* what, const dmx_edit_item* items, int B, int H, int W, int S, bool prepared, int index0 = 0);
 int dmx_check_edit_pages(const char* what, const dmx_edit_page* pages, int P, const dmx_edit_item* items, int B, int S, bool prepared);
+// the page table alone, whatever its B items are (boxes here, quads in prepost_quad.hip; the caller has checked 1 <= P, B <=
+// DMX_EDIT_MAX_ITEMS): sizes up to 65535 x max_w, item ranges that tile [0, B) in page order, fewer than 2^31 blocks of 256 pixels;
+// `prepared` also compares block_lo / blocks with what the entry named `prepare` fills
+int dmx_check_page_table(const char* what, const dmx_edit_page* pages, int P, int B, int max_w, const char* prepare, bool prepared);
 // what the paged entries ask of the pages' addresses, and the select entries of their scalars (also asked by prepost_blend.hip)
 int dmx_check_page_addresses(const char* what, const dmx_edit_page* pages, int P, bool need_out);
 int dmx_check_select_scalars(const char* what, int K, float threshold);

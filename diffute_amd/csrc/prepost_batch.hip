@@ -234,18 +234,14 @@ extern "C" int dmx_postprocess_paste_select(const float* image_vae, int S, const
 }
 
 // ---- pages
-// the page table, then every page's slice of the item table against that page; `prepared` also compares the derived fields of both
-// tables with what edit_pages_prepare fills.  A bad page is named by page index, a bad item by its index in the whole table.
-int dmx_check_edit_pages(const char* what, const dmx_edit_page* pages, int P, const dmx_edit_item* items, int B, int S, bool prepared) {
-  DMX_REQUIRE(pages && items, "%s: null page or item table", what);
-  DMX_REQUIRE(P >= 1 && P <= DMX_EDIT_MAX_ITEMS, "%s: %d pages, expected 1 .. %d", what, P, DMX_EDIT_MAX_ITEMS);
-  DMX_REQUIRE(B >= 1 && B <= DMX_EDIT_MAX_ITEMS, "%s: %d items, expected 1 .. %d", what, B, DMX_EDIT_MAX_ITEMS);
+// the page table of 1 .. DMX_EDIT_MAX_ITEMS pages and B items of any kind (kernels.h); a bad page is named by page index
+int dmx_check_page_table(const char* what, const dmx_edit_page* pages, int P, int B, int max_w, const char* prepare, bool prepared) {
   long long blocks = 0;
   for (int q = 0, next = 0; q < P; ++q) {
     const dmx_edit_page& pg = pages[q];
     // (W + 255 must not overflow an int, here or in the kernels' tile count)
-    DMX_REQUIRE(pg.H > 0 && pg.W > 0 && pg.H <= 65535 && pg.W <= DMX_EDIT_PAGE_MAX_W, "%s: page %d: bad size %dx%d (1 <= H <= 65535, 1 <= W <= %d)", what,
-                q, pg.W, pg.H, DMX_EDIT_PAGE_MAX_W);
+    DMX_REQUIRE(pg.H > 0 && pg.W > 0 && pg.H <= 65535 && pg.W <= max_w, "%s: page %d: bad size %dx%d (1 <= H <= 65535, 1 <= W <= %d)", what, q, pg.W,
+                pg.H, max_w);
     DMX_REQUIRE(pg.item_hi > pg.item_lo, "%s: page %d: no items (range [%d, %d))", what, q, pg.item_lo, pg.item_hi);
     DMX_REQUIRE(pg.item_lo == next && pg.item_hi <= B,
                 "%s: page %d: its items [%d, %d) must start at %d and end at or before %d (the ranges tile [0, B) in page order)", what, q, pg.item_lo,
@@ -255,17 +251,29 @@ int dmx_check_edit_pages(const char* what, const dmx_edit_page* pages, int P, co
     const long long mine = (long long)pg.H * cdiv(pg.W, 256);
     DMX_REQUIRE(blocks + mine < (1ll << 31), "%s: page %d: the pages need more than 2^31 - 1 blocks of 256 pixels", what, q);
     if (prepared)
-      DMX_REQUIRE(pg.block_lo == (int)blocks && pg.blocks == (int)mine,
-                  "%s: page %d: derived fields do not belong to this page table (dmx_edit_pages_prepare fills them)", what, q);
+      DMX_REQUIRE(pg.block_lo == (int)blocks && pg.blocks == (int)mine, "%s: page %d: derived fields do not belong to this page table (%s fills them)",
+                  what, q, prepare);
     blocks += mine;
-    const int rc = dmx_check_edit_items(what, items + pg.item_lo, pg.item_hi - pg.item_lo, pg.H, pg.W, S, prepared, pg.item_lo);
-    if (rc != DMX_OK) return rc;
-    if (prepared)
-      for (int b = pg.item_lo; b < pg.item_hi; ++b)
-        DMX_REQUIRE(items[b].reserved == q, "%s: item %d: page index %d, the item lies in the range of page %d (dmx_edit_pages_prepare fills it)", what, b,
-                    items[b].reserved, q);
   }
   return DMX_OK;
+}
+
+// the page table, then every page's slice of the item table against that page; `prepared` also compares the derived fields of both
+// tables with what edit_pages_prepare fills.  A bad page is named by page index, a bad item by its index in the whole table.
+int dmx_check_edit_pages(const char* what, const dmx_edit_page* pages, int P, const dmx_edit_item* items, int B, int S, bool prepared) {
+  DMX_REQUIRE(pages && items, "%s: null page or item table", what);
+  DMX_REQUIRE(P >= 1 && P <= DMX_EDIT_MAX_ITEMS, "%s: %d pages, expected 1 .. %d", what, P, DMX_EDIT_MAX_ITEMS);
+  DMX_REQUIRE(B >= 1 && B <= DMX_EDIT_MAX_ITEMS, "%s: %d items, expected 1 .. %d", what, B, DMX_EDIT_MAX_ITEMS);
+  int rc = dmx_check_page_table(what, pages, P, B, DMX_EDIT_PAGE_MAX_W, "dmx_edit_pages_prepare", prepared);
+  for (int q = 0; q < P && rc == DMX_OK; ++q) {                        // the ranges tile [0, B): every item has its page
+    const dmx_edit_page& pg = pages[q];
+    rc = dmx_check_edit_items(what, items + pg.item_lo, pg.item_hi - pg.item_lo, pg.H, pg.W, S, prepared, pg.item_lo);
+    if (rc != DMX_OK || !prepared) continue;
+    for (int b = pg.item_lo; b < pg.item_hi; ++b)
+      DMX_REQUIRE(items[b].reserved == q, "%s: item %d: page index %d, the item lies in the range of page %d (dmx_edit_pages_prepare fills it)", what, b,
+                  items[b].reserved, q);
+  }
+  return rc;
 }
 
 int dmx_check_page_addresses(const char* what, const dmx_edit_page* pages, int P, bool need_out) {

@@ -1,6 +1,7 @@
 // What the paste kernels of prepost_batch.hip (the plain paste) and prepost_blend.hip (the feathered, colour-matched paste) share: the
-// arguments of a one-page paste and of a paged one, the block -> (page, row, column tile) map of the paged grid, and the choice rule of
-// the verified edits.  Device code only; everything here is called on a block of 256 threads.
+// arguments of a one-page paste and of a paged one, the block -> (page, row, column tile) map of the paged grid - which the quad pastes
+// of prepost_quad.hip use too -, and the choice rule of the verified edits.  Device code only; everything here is called on a block of
+// 256 threads.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -39,6 +40,25 @@ __device__ __forceinline__ void select_choices(const float* scores, int B, int K
 // The paste over P pages in ONE launch.  The rows of all pages do not fit in grid.y, so blocks enumerate (page, row, column tile) along
 // grid.x: page p owns the blocks [block_lo, block_lo + H * ceil(W / 256)).  A block finds its page by a uniform scan of the (at most
 // 64) block_lo values, then pastes one 256-pixel tile of one row with the page's view: a pixel scans only its own page's items.
+// The quad pastes (prepost_quad.hip) enumerate their blocks the same way: page_block is the map, whatever the items are.
+struct PageBlock { dmx_edit_page pg; int lo, n, x, y; };         // the page, its items [lo, lo + n) of the table, this thread's pixel
+
+// false: the block has no pixel to write (a stale table - with a good one every block lies inside its page, no wider than max_w, and
+// its items inside the table of B).  Uniform per block.
+__device__ __forceinline__ bool page_block(const dmx_edit_page* pages, int P, int B, int max_w, PageBlock& t) {
+  int pi = 0;
+  for (int i = 1; i < P; ++i) pi = (int)blockIdx.x >= pages[i].block_lo ? i : pi;
+  t.pg = pages[pi];
+  if (t.pg.H <= 0 || t.pg.W <= 0 || t.pg.W > max_w) return false;
+  const int tiles = (t.pg.W + 255) / 256, local = (int)blockIdx.x - t.pg.block_lo;
+  if (local < 0 || local / tiles >= t.pg.H) return false;
+  t.lo = min(max(t.pg.item_lo, 0), B - 1);
+  t.n = min(max(t.pg.item_hi - t.lo, 1), B - t.lo);
+  t.y = local / tiles;
+  t.x = (local % tiles) * 256 + (int)threadIdx.x;
+  return true;
+}
+
 struct PostPagesArgs {
   const float* vae; int S;
   const dmx_edit_page* pages; int P;
@@ -46,20 +66,13 @@ struct PostPagesArgs {
 };
 struct PageTile { PostBatchArgs view; int lo, x, y; };
 
-// false: the block has no pixel to write (a stale table - with a good one every block lies inside its page).  Uniform per block.
+// page_block with the page as the view the one-page box pastes take
 __device__ __forceinline__ bool page_tile(const PostPagesArgs& p, PageTile& t) {
-  int pi = 0;
-  for (int i = 1; i < p.P; ++i) pi = (int)blockIdx.x >= p.pages[i].block_lo ? i : pi;
-  const dmx_edit_page pg = p.pages[pi];
-  if (pg.H <= 0 || pg.W <= 0 || pg.W > DMX_EDIT_PAGE_MAX_W) return false;
-  const int tiles = (pg.W + 255) / 256, local = (int)blockIdx.x - pg.block_lo;
-  if (local < 0 || local / tiles >= pg.H) return false;
-  t.lo = min(max(pg.item_lo, 0), p.B - 1);
-  const int n = min(max(pg.item_hi - t.lo, 1), p.B - t.lo);
-  t.view = PostBatchArgs{p.vae, p.S, (const unsigned char*)pg.original, (unsigned char*)pg.out, (unsigned char*)pg.union_mask, pg.H, pg.W,
-                         p.items + t.lo, n};
-  t.y = local / tiles;
-  t.x = (local % tiles) * 256 + (int)threadIdx.x;
+  PageBlock k;
+  if (!page_block(p.pages, p.P, p.B, DMX_EDIT_PAGE_MAX_W, k)) return false;
+  t.view = PostBatchArgs{p.vae, p.S, (const unsigned char*)k.pg.original, (unsigned char*)k.pg.out, (unsigned char*)k.pg.union_mask, k.pg.H,
+                         k.pg.W, p.items + k.lo, k.n};
+  t.lo = k.lo; t.x = k.x; t.y = k.y;
   return true;
 }
 

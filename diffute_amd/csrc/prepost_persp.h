@@ -1,7 +1,7 @@
 // Quadrilateral text regions seen in PERSPECTIVE, stated once: the projective frame beside prepost_quad.h's similarity frame.  The host
 // half is what dmx_edit_quads_persp_prepare fills into a dmx_quad_persp, the device half the coordinates of the three kernels of
-// prepost_persp.hip.  tests/persp_restatement.py restates this comment in Python ints and numpy int64 and the GPU tests compare bit for
-// bit.  Only WHERE THE COORDINATES COME FROM is new: taps, the single rounding, the predicate, blacking out before resampling and the
+// prepost_quad.hip in their projective frame.  tests/persp_restatement.py restates this comment in Python ints and numpy int64 and
+// the GPU tests compare bit for bit.  Only WHERE THE COORDINATES COME FROM is new: taps, the single rounding, the predicate, blacking out before resampling and the
 // paste rule are dmx_quad::tap16, pre_pixel, page_sample, post_pixel and inside of prepost_quad.h, called, not restated.
 //
 // Strip space.  rw x rh of prepost_quad.h's rectify section; in the strip's pixel-index space TL <-> (0, 0), TR <-> (rw - 1, 0),

@@ -1,6 +1,7 @@
 // The geometry of quadrilateral text regions with oriented crops, stated once: the host half (what dmx_edit_quads_prepare fills into a
-// dmx_edit_quad) and the per-pixel arithmetic of the three kernels of prepost_quad.hip.  tests/quad_restatement.py restates this comment
-// in numpy and the GPU tests compare bit for bit.  Everything a kernel reads from the table is an integer.
+// dmx_edit_quad) and the per-pixel arithmetic of the three kernels of prepost_quad.hip in their similarity frame (the projective frame's
+// coordinates are prepost_persp.h).  tests/quad_restatement.py restates this comment in numpy and the GPU tests compare bit for bit.
+// Everything a kernel reads from the table is an integer.
 //
 // Quad.  Corners k = 0..3 with integer page coordinates (x_k, y_k) in the OCR record's order - top-left, top-right, bottom-right,
 //   bottom-left of the text as read -, clockwise with y down.  Pixel (X, Y) is inside iff all four edge functions
@@ -75,10 +76,6 @@ inline void fill_derived(dmx_edit_quad& q, int S, long long rect_off, int rect_b
   q.rect_block_lo = rect_block_lo; q.rect_blocks = q.rh * ((q.rw + 255) / 256);
   q.rect_off = rect_off;
 }
-
-// The host-side checks of a page table and a quad table (prepost_quad.hip), shared with the projective entries of prepost_persp.hip
-int check_quads(const char* what, const dmx_edit_page* pages, int P, const dmx_edit_quad* quads, int B, int S, bool frames, bool prepared);
-int check_quad_pages(const char* what, const dmx_edit_page* pages, int P, bool need_out);
 
 #ifdef __HIPCC__
 // what the paste scans per item, staged in LDS

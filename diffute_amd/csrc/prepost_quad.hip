@@ -1,24 +1,76 @@
-// Quadrilateral text regions with oriented crops: the two ends of the editing path for skewed and rotated lines (pipeline.edit_quads),
-// beside prepost_batch.hip's axis-aligned boxes.  Items are dmx_edit_quad, pages the dmx_edit_page table of the *_pages entries.  Three
-// kernels, one launch each: the crop (mask = the quad itself, frame turned to the baseline), the paste (every page pixel mapped back
-// through the inverse frame; the last quad that covers a pixel decides) and the rectify (a quad as an upright strip, for the OCR model).
-// The per-pixel arithmetic is prepost_quad.h.  Pure HBM-bound byte work: one thread per destination pixel, coalesced plain vector
-// stores, the integer tables staged in LDS once per block, no atomics.
+// Quadrilateral text regions: the two ends of the editing path for skewed, rotated and keystoned lines (pipeline.edit_quads), beside
+// prepost_batch.hip's axis-aligned boxes.  Items are dmx_edit_quad, pages the dmx_edit_page table of the *_pages entries.  Three
+// kernels, one launch each: the crop (mask = the quad itself, seen through the frame), the paste (every page pixel mapped back through
+// the inverse frame; the last quad that covers a pixel decides) and the rectify (a quad as an upright strip, for the OCR model).
+// Each kernel is written ONCE, over a frame that says where the sample coordinates come from:
+//   SimilarityFrame   one rotation and one scale, the Q15 matrices of dmx_edit_quad (prepost_quad.h): the dmx_*_quads entries;
+//   ProjectiveFrame   the homography that takes the quad to its upright strip, from a parallel, index-aligned table of dmx_quad_persp
+//                     (prepost_persp.h) - phone photos, signs and scene text, where a line is a trapezoid and the similarity frame leaves
+//                     the text keystoned: the dmx_*_quads_persp entries.  Per pixel two 64-bit numerators, one denominator and four
+//                     64-bit divisions more.
+// Everything after the coordinates (taps, rounding, predicate, paste rule, stores) is prepost_quad.h's.  Pure HBM-bound byte work: one
+// thread per destination pixel, coalesced plain vector stores, the integer tables staged in LDS once per block, no atomics.
 #include "common.h"
 #include "kernels.h"
-#include "prepost_quad.h"
+#include "prepost_paste.h"
+#include "prepost_persp.h"
 
 namespace {
 using namespace dmx_quad;
 
 constexpr int kQuadInts = (int)(sizeof(dmx_edit_quad) / sizeof(int));
-static_assert(sizeof(dmx_edit_quad) % sizeof(int) == 0 && kQuadInts <= 256, "a block stages one quad with one int per thread");
+constexpr int kPerspInts = (int)(sizeof(dmx_quad_persp) / sizeof(int));
+static_assert(sizeof(dmx_edit_quad) % sizeof(int) == 0 && sizeof(dmx_quad_persp) % sizeof(int) == 0 && kQuadInts + kPerspInts <= 256,
+              "a block stages one quad and its projective frame with one int per thread");
 
-// one table entry into LDS, one int per thread; ends with a barrier
-__device__ __forceinline__ void stage_quad(dmx_edit_quad* s_q, const dmx_edit_quad* src) {
-  if ((int)threadIdx.x < kQuadInts) ((int*)s_q)[threadIdx.x] = ((const int*)src)[threadIdx.x];
-  __syncthreads();
-}
+// A frame travels to the kernels by value, beside their arguments.  Item: what a block of the crop and of the rectify stages of item b
+// in LDS - stage() fills it with one int per thread and ends with ONE barrier.  crop / strip: the page coordinates (Q16) of the grid
+// point (p, q) of the staged item's crop / strip.  paste: the crop coordinates of page pixel (x, y) for item b, read from global memory
+// (the paste stages edges, not frames); false where the map is not defined.
+struct SimilarityFrame {
+  struct Item { dmx_edit_quad q; };
+  __device__ __forceinline__ void stage(Item& s, const dmx_edit_quad* quads, int b) const {
+    if ((int)threadIdx.x < kQuadInts) ((int*)&s.q)[threadIdx.x] = ((const int*)(quads + b))[threadIdx.x];
+    __syncthreads();
+  }
+  __device__ __forceinline__ void crop(const Item& s, long long p, long long q, long long& X16, long long& Y16) const {
+    X16 = ((long long)s.q.cx2 << 15) + s.q.fwd[0] * p + s.q.fwd[1] * q;
+    Y16 = ((long long)s.q.cy2 << 15) + s.q.fwd[2] * p + s.q.fwd[3] * q;
+  }
+  __device__ __forceinline__ void strip(const Item& s, long long p, long long q, long long& X16, long long& Y16) const {
+    X16 = ((long long)s.q.sx4 << 14) + s.q.rect[0] * p + s.q.rect[1] * q;
+    Y16 = ((long long)s.q.sy4 << 14) + s.q.rect[2] * p + s.q.rect[3] * q;
+  }
+  __device__ __forceinline__ bool paste(const dmx_edit_quad* quads, int b, int S, int x, int y, long long& U16, long long& V16) const {
+    const dmx_edit_quad& q = quads[b];
+    const long long qx = 2ll * x - q.cx2, qy = 2ll * y - q.cy2, base = (long long)(S - 1) << 15;
+    U16 = base + q.inv[0] * qx + q.inv[1] * qy;
+    V16 = base + q.inv[2] * qx + q.inv[3] * qy;
+    return true;
+  }
+};
+
+struct ProjectiveFrame {
+  const dmx_quad_persp* table;
+  struct Item { dmx_edit_quad q; dmx_quad_persp x; };
+  __device__ __forceinline__ void stage(Item& s, const dmx_edit_quad* quads, int b) const {
+    const int t = threadIdx.x;
+    if (t < kQuadInts) ((int*)&s.q)[t] = ((const int*)(quads + b))[t];
+    else if (t < kQuadInts + kPerspInts) ((int*)&s.x)[t - kQuadInts] = ((const int*)(table + b))[t - kQuadInts];
+    __syncthreads();
+  }
+  // (a stale table: coords writes nothing, the sample is the page's corner; tap16 clamps anyway)
+  __device__ __forceinline__ void crop(const Item& s, long long p, long long q, long long& X16, long long& Y16) const {
+    dmx_persp::coords(s.x.crop, p, q, X16, Y16);
+  }
+  __device__ __forceinline__ void strip(const Item& s, long long p, long long q, long long& X16, long long& Y16) const {
+    dmx_persp::coords(s.x.strip, p, q, X16, Y16);
+  }
+  __device__ __forceinline__ bool paste(const dmx_edit_quad*, int b, int, int x, int y, long long& U16, long long& V16) const {
+    const dmx_quad_persp& f = table[b];
+    return dmx_persp::coords(f.paste, 2ll * x - f.cx2, 2ll * y - f.cy2, U16, V16);
+  }
+};
 
 struct PreQuadArgs {
   const dmx_edit_page* pages; int P;
@@ -27,19 +79,19 @@ struct PreQuadArgs {
 };
 
 // grid (ceil(S / 256), S, B): block z handles row y of quad z's crop
-__global__ __launch_bounds__(256) void dmx_preprocess_quads_kernel(const PreQuadArgs p) {
-  __shared__ dmx_edit_quad s_q;
+template <class Frame>
+__global__ __launch_bounds__(256) void dmx_preprocess_quads_kernel(const PreQuadArgs p, const Frame frame) {
+  __shared__ typename Frame::Item s;
   const int b = blockIdx.z;
-  stage_quad(&s_q, p.quads + b);
+  frame.stage(s, p.quads, b);
   const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y;
   if (dx >= p.S) return;
-  const dmx_edit_page pg = p.pages[min(max(s_q.page, 0), p.P - 1)];
+  const dmx_edit_page pg = p.pages[min(max(s.q.page, 0), p.P - 1)];
   if (pg.H <= 0 || pg.W <= 0) return;
-  const long long px = 2 * dx + 1 - p.S, py = 2 * dy + 1 - p.S;
-  const long long X16 = ((long long)s_q.cx2 << 15) + s_q.fwd[0] * px + s_q.fwd[1] * py;
-  const long long Y16 = ((long long)s_q.cy2 << 15) + s_q.fwd[2] * px + s_q.fwd[3] * py;
+  long long X16 = 0, Y16 = 0;
+  frame.crop(s, 2 * dx + 1 - p.S, 2 * dy + 1 - p.S, X16, Y16);
   int vi[3], vm[3], vk;
-  pre_pixel((const unsigned char*)pg.original, pg.H, pg.W, X16, Y16, [&](int X, int Y) -> int { return inside(s_q, X, Y); }, vi, vm, vk);
+  pre_pixel((const unsigned char*)pg.original, pg.H, pg.W, X16, Y16, [&](int X, int Y) -> int { return inside(s.q, X, Y); }, vi, vm, vk);
   const size_t plane = (size_t)p.S * p.S, lat = (size_t)(p.S >> 3) * (p.S >> 3);
   dmx_resize::pre_store(vi, vm, vk, p.S, dx, dy, p.out_img + (size_t)b * 3 * plane, p.out_masked + (size_t)b * 3 * plane,
                         p.out_mask + (size_t)b * plane, p.out_mask_lat ? p.out_mask_lat + (size_t)b * lat : nullptr);
@@ -51,18 +103,16 @@ struct PostQuadArgs {
   const dmx_edit_quad* quads; int B;
 };
 
-// The paste over P pages: blocks enumerate (page, row, 256-column tile) along grid.x as in dmx_postprocess_pages_kernel; a block finds
-// its page by a uniform scan of the block_lo values and stages the page's quads - corners, edges, bounding box - in LDS.  A pixel scans
-// them last to first and stops at the first quad that covers it.
-__global__ __launch_bounds__(256) void dmx_postprocess_quads_kernel(const PostQuadArgs p) {
+// The paste over P pages: blocks enumerate (page, row, 256-column tile) along grid.x as in dmx_postprocess_pages_kernel
+// (dmx_paste::page_block); a block stages its page's quads - corners, edges, bounding box - in LDS.  A pixel scans them last to first,
+// stops at the first quad that covers it and maps itself through THAT item's frame.
+template <class Frame>
+__global__ __launch_bounds__(256) void dmx_postprocess_quads_kernel(const PostQuadArgs p, const Frame frame) {
   __shared__ QuadEdges s_e[DMX_EDIT_MAX_ITEMS];
-  int pi = 0;
-  for (int i = 1; i < p.P; ++i) pi = (int)blockIdx.x >= p.pages[i].block_lo ? i : pi;
-  const dmx_edit_page pg = p.pages[pi];
-  if (pg.H <= 0 || pg.W <= 0 || pg.W > 65535) return;                          // (uniform per block: a stale table)
-  const int tiles = (pg.W + 255) / 256, local = (int)blockIdx.x - pg.block_lo;
-  if (local < 0 || local / tiles >= pg.H) return;
-  const int lo = min(max(pg.item_lo, 0), p.B - 1), n = min(max(pg.item_hi - lo, 1), p.B - lo);
+  dmx_paste::PageBlock t;
+  if (!dmx_paste::page_block(p.pages, p.P, p.B, 65535, t)) return;             // (uniform per block: a stale table)
+  const dmx_edit_page& pg = t.pg;
+  const int lo = t.lo, n = t.n, x = t.x, y = t.y;
   if ((int)threadIdx.x < n) {
     const dmx_edit_quad& q = p.quads[lo + threadIdx.x];
     QuadEdges e;
@@ -72,7 +122,6 @@ __global__ __launch_bounds__(256) void dmx_postprocess_quads_kernel(const PostQu
     s_e[threadIdx.x] = e;
   }
   __syncthreads();
-  const int y = local / tiles, x = (local % tiles) * 256 + (int)threadIdx.x;
   if (x >= pg.W) return;
   int hit = -1;
   for (int b = n - 1; b >= 0; --b) {
@@ -86,11 +135,8 @@ __global__ __launch_bounds__(256) void dmx_postprocess_quads_kernel(const PostQu
   bool paste = false;
   long long U16 = 0, V16 = 0;
   if (hit >= 0) {
-    const dmx_edit_quad& q = p.quads[lo + hit];
-    const long long qx = 2ll * x - q.cx2, qy = 2ll * y - q.cy2, base = (long long)(p.S - 1) << 15, top = ((long long)p.S << 16) - 32768;
-    U16 = base + q.inv[0] * qx + q.inv[1] * qy;
-    V16 = base + q.inv[2] * qx + q.inv[3] * qy;
-    paste = U16 >= -32768 && U16 < top && V16 >= -32768 && V16 < top;
+    const long long top = ((long long)p.S << 16) - 32768;
+    paste = frame.paste(p.quads, lo + hit, p.S, x, y, U16, V16) && U16 >= -32768 && U16 < top && V16 >= -32768 && V16 < top;
   }
   if (!paste) { out[o] = ori[o]; out[o + 1] = ori[o + 1]; out[o + 2] = ori[o + 2]; return; }
   const float* vae = p.vae + (size_t)(lo + hit) * 3 * p.S * p.S;
@@ -105,59 +151,43 @@ struct RectQuadArgs {
 };
 
 // The strips of all quads: blocks enumerate (quad, row, 256-column tile) along grid.x; a block finds its quad by a uniform scan of the
-// rect_block_lo values (staged in LDS), stages that quad and writes one tile of one strip row.  No byte is written at or past out_bytes.
-__global__ __launch_bounds__(256) void dmx_rectify_quads_kernel(const RectQuadArgs p) {
+// rect_block_lo values (staged in LDS), stages that item and writes one tile of one strip row.  No byte is written at or past out_bytes.
+template <class Frame>
+__global__ __launch_bounds__(256) void dmx_rectify_quads_kernel(const RectQuadArgs p, const Frame frame) {
   __shared__ int s_lo[DMX_EDIT_MAX_ITEMS];
-  __shared__ dmx_edit_quad s_q;
+  __shared__ typename Frame::Item s;
   if ((int)threadIdx.x < p.B) s_lo[threadIdx.x] = p.quads[threadIdx.x].rect_block_lo;
   __syncthreads();
   int b = 0;
   for (int i = 1; i < p.B; ++i) b = (int)blockIdx.x >= s_lo[i] ? i : b;
-  stage_quad(&s_q, p.quads + b);
-  const dmx_edit_page pg = p.pages[min(max(s_q.page, 0), p.P - 1)];
-  const int rw = s_q.rw, rh = s_q.rh;
-  if (pg.H <= 0 || pg.W <= 0 || rw <= 0 || rh <= 0 || rw > (1 << 20) || s_q.rect_off < 0) return;
-  const int tiles = (rw + 255) / 256, local = (int)blockIdx.x - s_q.rect_block_lo;
+  frame.stage(s, p.quads, b);
+  const dmx_edit_page pg = p.pages[min(max(s.q.page, 0), p.P - 1)];
+  const int rw = s.q.rw, rh = s.q.rh;
+  if (pg.H <= 0 || pg.W <= 0 || rw <= 0 || rh <= 0 || rw > (1 << 20) || s.q.rect_off < 0) return;
+  const int tiles = (rw + 255) / 256, local = (int)blockIdx.x - s.q.rect_block_lo;
   if (local < 0 || local / tiles >= rh) return;
   const int j = local / tiles, i = (local % tiles) * 256 + (int)threadIdx.x;
   if (i >= rw) return;
-  const long long o = s_q.rect_off + ((long long)j * rw + i) * 3;
+  const long long o = s.q.rect_off + ((long long)j * rw + i) * 3;
   if (o + 3 > p.out_bytes) return;
-  const long long px = 2 * i + 1 - rw, py = 2 * j + 1 - rh;
-  const long long X16 = ((long long)s_q.sx4 << 14) + s_q.rect[0] * px + s_q.rect[1] * py;
-  const long long Y16 = ((long long)s_q.sy4 << 14) + s_q.rect[2] * px + s_q.rect[3] * py;
+  long long X16 = 0, Y16 = 0;
+  frame.strip(s, 2 * i + 1 - rw, 2 * j + 1 - rh, X16, Y16);
   const Tap16 tx = tap16(X16, pg.W), ty = tap16(Y16, pg.H);
 #pragma unroll
   for (int c = 0; c < 3; ++c) p.out[o + c] = (unsigned char)page_sample((const unsigned char*)pg.original, pg.W, tx, ty, c);
 }
 
-}  // namespace
-
-namespace dmx_quad {
-// The host-side checks of a page table and a quad table.  frames: the frame fields are looked at (the rectify entry reads none of
-// them).  prepared: the derived fields of both tables are compared with what dmx_edit_quads_prepare fills.  A bad page is named by page
-// index, a bad quad by its index in the whole table.
+// The host-side checks of a page table and a quad table.  frames: the frame fields are looked at (the rectify entry and the projective
+// entries read none of them).  prepared: the derived fields of both tables are compared with what dmx_edit_quads_prepare fills.  A bad
+// page is named by page index, a bad quad by its index in the whole table.
 int check_quads(const char* what, const dmx_edit_page* pages, int P, const dmx_edit_quad* quads, int B, int S, bool frames, bool prepared) {
   DMX_REQUIRE(pages && quads, "%s: null page or quad table", what);
   DMX_REQUIRE(P >= 1 && P <= DMX_EDIT_MAX_ITEMS, "%s: %d pages, expected 1 .. %d", what, P, DMX_EDIT_MAX_ITEMS);
   DMX_REQUIRE(B >= 1 && B <= DMX_EDIT_MAX_ITEMS, "%s: %d items, expected 1 .. %d", what, B, DMX_EDIT_MAX_ITEMS);
   DMX_REQUIRE(!frames || (S >= 1 && S <= 65535), "%s: bad S = %d (1 .. 65535)", what, S);
-  long long blocks = 0, rect_off = 0, rect_blocks = 0;
-  for (int q = 0, next = 0; q < P; ++q) {
-    const dmx_edit_page& pg = pages[q];
-    DMX_REQUIRE(pg.H > 0 && pg.W > 0 && pg.H <= 65535 && pg.W <= 65535, "%s: page %d: bad size %dx%d (1 <= H, W <= 65535)", what, q, pg.W, pg.H);
-    DMX_REQUIRE(pg.item_hi > pg.item_lo, "%s: page %d: no items (range [%d, %d))", what, q, pg.item_lo, pg.item_hi);
-    DMX_REQUIRE(pg.item_lo == next && pg.item_hi <= B,
-                "%s: page %d: its items [%d, %d) must start at %d and end at or before %d (the ranges tile [0, B) in page order)", what, q, pg.item_lo,
-                pg.item_hi, next, B);
-    DMX_REQUIRE(q + 1 < P || pg.item_hi == B, "%s: page %d: the last page's items end at %d, the table holds %d", what, q, pg.item_hi, B);
-    next = pg.item_hi;
-    const long long mine = (long long)pg.H * cdiv(pg.W, 256);
-    if (prepared)
-      DMX_REQUIRE(pg.block_lo == (int)blocks && pg.blocks == (int)mine,
-                  "%s: page %d: derived fields do not belong to this page table (dmx_edit_quads_prepare fills them)", what, q);
-    blocks += mine;                                                    // (at most 64 * 65535 * 256 < 2^31)
-  }
+  const int rc = dmx_check_page_table(what, pages, P, B, 65535, "dmx_edit_quads_prepare", prepared);
+  if (rc != DMX_OK) return rc;
+  long long rect_off = 0, rect_blocks = 0;
   for (int q = 0; q < P; ++q) {                                        // the ranges tile [0, B): every item has its page
     const dmx_edit_page& pg = pages[q];
     for (int b = pg.item_lo; b < pg.item_hi; ++b) {
@@ -203,14 +233,66 @@ int check_quads(const char* what, const dmx_edit_page* pages, int P, const dmx_e
   return DMX_OK;
 }
 
-int check_quad_pages(const char* what, const dmx_edit_page* pages, int P, bool need_out) {
-  for (int q = 0; q < P; ++q) {
-    DMX_REQUIRE(pages[q].original, "%s: page %d: null original image", what, q);
-    DMX_REQUIRE(!need_out || (pages[q].out && pages[q].out != pages[q].original), "%s: page %d: the output image is null or the original itself", what, q);
+// The host-side check of the projective table beside checked, PREPARED page and quad tables.  S >= 1: frames and all three maps; S == 0:
+// the strip maps alone (the rectify entry reads nothing else).  fill == null: the derived fields are compared with what the prepare
+// entry fills; otherwise they are written there.  A bad item is named by its index in the whole table.
+int check_persp(const char* what, const dmx_edit_quad* quads, const dmx_quad_persp* persp, dmx_quad_persp* fill, int B, int S) {
+  const bool prepared = fill == nullptr;
+  DMX_REQUIRE(persp, "%s: null projective table", what);
+  for (int b = 0; b < B; ++b) {
+    dmx_quad_persp t = persp[b];
+    const char *where = "", *wrong = nullptr;
+    if (S >= 1) {
+      wrong = dmx_persp::fill_derived(quads[b], t, S, &where);
+    } else {
+      where = "the strip";
+      wrong = dmx_persp::fill_strip(quads[b], t);
+    }
+    DMX_REQUIRE(!wrong, "%s: item %d: %s: %s", what, b, where, wrong);
+    if (!prepared) { fill[b] = t; continue; }
+    const bool same = S >= 1 ? memcmp(&t, &persp[b], sizeof t) == 0 : memcmp(&t.strip, &persp[b].strip, sizeof t.strip) == 0;
+    DMX_REQUIRE(same, "%s: item %d: derived fields do not belong to this quad, projective frame and S (dmx_edit_quads_persp_prepare fills them)", what, b);
   }
   return DMX_OK;
 }
-}  // namespace dmx_quad
+
+// what every launch entry asks of its host tables: prepared page and quad tables (check_quads) and the pages' addresses
+int check_tables(const char* what, const dmx_edit_page* pages, int P, const dmx_edit_quad* quads, int B, int S, bool frames, bool need_out) {
+  const int rc = check_quads(what, pages, P, quads, B, S, frames, true);
+  return rc != DMX_OK ? rc : dmx_check_page_addresses(what, pages, P, need_out);
+}
+
+// The launches, one per stage; the tables are checked.  `kernel` names the launch in the last-error string.
+template <class Frame>
+int launch_pre(const char* kernel, const Frame& frame, const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_device, int B, int S,
+               float* out_image, float* out_masked_image, unsigned char* out_mask, float* out_mask_latent, dmx_stream_t stream) {
+  PreQuadArgs p{pages_device, P, quads_device, S, out_image, out_masked_image, out_mask, out_mask_latent};
+  hipLaunchKernelGGL(dmx_preprocess_quads_kernel<Frame>, dim3(cdiv(S, 256), S, B), dim3(256), 0, (hipStream_t)stream, p, frame);
+  return dmx_check_launch(kernel);
+}
+
+template <class Frame>
+int launch_post(const char* kernel, const Frame& frame, const float* image_vae, int S, const dmx_edit_page* pages_host,
+                const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_device, int B, dmx_stream_t stream) {
+  PostQuadArgs p{image_vae, S, pages_device, P, quads_device, B};
+  hipLaunchKernelGGL(dmx_postprocess_quads_kernel<Frame>, dim3(pages_host[P - 1].block_lo + pages_host[P - 1].blocks), dim3(256), 0,
+                     (hipStream_t)stream, p, frame);
+  return dmx_check_launch(kernel);
+}
+
+template <class Frame>
+int launch_rectify(const char* what, const char* kernel, const Frame& frame, const dmx_edit_page* pages_device, int P,
+                   const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device, int B, unsigned char* out, long long out_bytes,
+                   dmx_stream_t stream) {
+  const dmx_edit_quad& last = quads_host[B - 1];
+  DMX_REQUIRE(out_bytes >= last.rect_off + (long long)last.rw * last.rh * 3, "%s: the strips take %lld bytes, the output holds %lld", what,
+              last.rect_off + (long long)last.rw * last.rh * 3, out_bytes);
+  RectQuadArgs p{pages_device, P, quads_device, B, out, out_bytes};
+  hipLaunchKernelGGL(dmx_rectify_quads_kernel<Frame>, dim3(last.rect_block_lo + last.rect_blocks), dim3(256), 0, (hipStream_t)stream, p, frame);
+  return dmx_check_launch(kernel);
+}
+
+}  // namespace
 
 extern "C" int dmx_edit_quads_prepare(dmx_edit_page* pages, int P, dmx_edit_quad* quads, int B, int S) {
   const int rc = check_quads("edit_quads_prepare", pages, P, quads, B, S, true, false);
@@ -230,40 +312,74 @@ extern "C" int dmx_edit_quads_prepare(dmx_edit_page* pages, int P, dmx_edit_quad
   return DMX_OK;
 }
 
+extern "C" int dmx_edit_quads_persp_prepare(const dmx_edit_page* pages, int P, const dmx_edit_quad* quads, dmx_quad_persp* persp, int B, int S) {
+  DMX_REQUIRE(S >= 0 && S <= 65535, "edit_quads_persp_prepare: bad S = %d (0 = strips only, 1 .. 65535)", S);
+  const int rc = check_quads("edit_quads_persp_prepare", pages, P, quads, B, 0, false, true);
+  return rc != DMX_OK ? rc : check_persp("edit_quads_persp_prepare", quads, persp, persp, B, S);
+}
+
+// ---- the similarity frame
 extern "C" int dmx_preprocess_quads(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_host,
                                     const dmx_edit_quad* quads_device, int B, int S, float* out_image, float* out_masked_image,
                                     unsigned char* out_mask, float* out_mask_latent, dmx_stream_t stream) {
   DMX_REQUIRE(pages_device && quads_device && out_image && out_masked_image && out_mask, "preprocess_quads: null argument");
   DMX_REQUIRE(S > 0 && S <= 65535 && S % 8 == 0, "preprocess_quads: S = %d is no positive multiple of 8 (up to 65535)", S);
-  int rc = check_quads("preprocess_quads", pages_host, P, quads_host, B, S, true, true);
-  if (rc == DMX_OK) rc = check_quad_pages("preprocess_quads", pages_host, P, false);
+  const int rc = check_tables("preprocess_quads", pages_host, P, quads_host, B, S, true, false);
   if (rc != DMX_OK) return rc;
-  PreQuadArgs p{pages_device, P, quads_device, S, out_image, out_masked_image, out_mask, out_mask_latent};
-  hipLaunchKernelGGL(dmx_preprocess_quads_kernel, dim3(cdiv(S, 256), S, B), dim3(256), 0, (hipStream_t)stream, p);
-  return dmx_check_launch("dmx_preprocess_quads_kernel");
+  return launch_pre("dmx_preprocess_quads_kernel", SimilarityFrame{}, pages_device, P, quads_device, B, S, out_image, out_masked_image, out_mask,
+                    out_mask_latent, stream);
 }
 
 extern "C" int dmx_postprocess_paste_quads(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
                                            const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device, int B, dmx_stream_t stream) {
   DMX_REQUIRE(image_vae && pages_device && quads_device, "postprocess_paste_quads: null argument");
-  int rc = check_quads("postprocess_paste_quads", pages_host, P, quads_host, B, S, true, true);
-  if (rc == DMX_OK) rc = check_quad_pages("postprocess_paste_quads", pages_host, P, true);
+  const int rc = check_tables("postprocess_paste_quads", pages_host, P, quads_host, B, S, true, true);
   if (rc != DMX_OK) return rc;
-  PostQuadArgs p{image_vae, S, pages_device, P, quads_device, B};
-  hipLaunchKernelGGL(dmx_postprocess_quads_kernel, dim3(pages_host[P - 1].block_lo + pages_host[P - 1].blocks), dim3(256), 0, (hipStream_t)stream, p);
-  return dmx_check_launch("dmx_postprocess_quads_kernel");
+  return launch_post("dmx_postprocess_quads_kernel", SimilarityFrame{}, image_vae, S, pages_host, pages_device, P, quads_device, B, stream);
 }
 
 extern "C" int dmx_rectify_quads(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_host,
                                  const dmx_edit_quad* quads_device, int B, unsigned char* out, long long out_bytes, dmx_stream_t stream) {
   DMX_REQUIRE(pages_device && quads_device && out, "rectify_quads: null argument");
-  int rc = check_quads("rectify_quads", pages_host, P, quads_host, B, 0, false, true);
-  if (rc == DMX_OK) rc = check_quad_pages("rectify_quads", pages_host, P, false);
+  const int rc = check_tables("rectify_quads", pages_host, P, quads_host, B, 0, false, false);
   if (rc != DMX_OK) return rc;
-  const dmx_edit_quad& last = quads_host[B - 1];
-  DMX_REQUIRE(out_bytes >= last.rect_off + (long long)last.rw * last.rh * 3, "rectify_quads: the strips take %lld bytes, the output holds %lld",
-              last.rect_off + (long long)last.rw * last.rh * 3, out_bytes);
-  RectQuadArgs p{pages_device, P, quads_device, B, out, out_bytes};
-  hipLaunchKernelGGL(dmx_rectify_quads_kernel, dim3(last.rect_block_lo + last.rect_blocks), dim3(256), 0, (hipStream_t)stream, p);
-  return dmx_check_launch("dmx_rectify_quads_kernel");
+  return launch_rectify("rectify_quads", "dmx_rectify_quads_kernel", SimilarityFrame{}, pages_device, P, quads_host, quads_device, B, out, out_bytes,
+                        stream);
+}
+
+// ---- the projective frame: the quad table's own frames are placeholders, not looked at
+extern "C" int dmx_preprocess_quads_persp(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_host,
+                                          const dmx_edit_quad* quads_device, const dmx_quad_persp* persp_host, const dmx_quad_persp* persp_device,
+                                          int B, int S, float* out_image, float* out_masked_image, unsigned char* out_mask,
+                                          float* out_mask_latent, dmx_stream_t stream) {
+  DMX_REQUIRE(pages_device && quads_device && persp_device && out_image && out_masked_image && out_mask, "preprocess_quads_persp: null argument");
+  DMX_REQUIRE(S > 0 && S <= 65535 && S % 8 == 0, "preprocess_quads_persp: S = %d is no positive multiple of 8 (up to 65535)", S);
+  int rc = check_tables("preprocess_quads_persp", pages_host, P, quads_host, B, 0, false, false);
+  if (rc == DMX_OK) rc = check_persp("preprocess_quads_persp", quads_host, persp_host, nullptr, B, S);
+  if (rc != DMX_OK) return rc;
+  return launch_pre("dmx_preprocess_quads_persp_kernel", ProjectiveFrame{persp_device}, pages_device, P, quads_device, B, S, out_image,
+                    out_masked_image, out_mask, out_mask_latent, stream);
+}
+
+extern "C" int dmx_postprocess_paste_quads_persp(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device,
+                                                 int P, const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device,
+                                                 const dmx_quad_persp* persp_host, const dmx_quad_persp* persp_device, int B, dmx_stream_t stream) {
+  DMX_REQUIRE(image_vae && pages_device && quads_device && persp_device, "postprocess_paste_quads_persp: null argument");
+  DMX_REQUIRE(S > 0 && S <= 65535, "postprocess_paste_quads_persp: bad S = %d (1 .. 65535)", S);
+  int rc = check_tables("postprocess_paste_quads_persp", pages_host, P, quads_host, B, 0, false, true);
+  if (rc == DMX_OK) rc = check_persp("postprocess_paste_quads_persp", quads_host, persp_host, nullptr, B, S);
+  if (rc != DMX_OK) return rc;
+  return launch_post("dmx_postprocess_quads_persp_kernel", ProjectiveFrame{persp_device}, image_vae, S, pages_host, pages_device, P, quads_device, B,
+                     stream);
+}
+
+extern "C" int dmx_rectify_quads_persp(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_host,
+                                       const dmx_edit_quad* quads_device, const dmx_quad_persp* persp_host, const dmx_quad_persp* persp_device, int B,
+                                       unsigned char* out, long long out_bytes, dmx_stream_t stream) {
+  DMX_REQUIRE(pages_device && quads_device && persp_device && out, "rectify_quads_persp: null argument");
+  int rc = check_tables("rectify_quads_persp", pages_host, P, quads_host, B, 0, false, false);
+  if (rc == DMX_OK) rc = check_persp("rectify_quads_persp", quads_host, persp_host, nullptr, B, 0);
+  if (rc != DMX_OK) return rc;
+  return launch_rectify("rectify_quads_persp", "dmx_rectify_quads_persp_kernel", ProjectiveFrame{persp_device}, pages_device, P, quads_host,
+                        quads_device, B, out, out_bytes, stream);
 }

@@ -781,17 +781,23 @@ def _check_quads(images, quads, frames, perspective=False):
     return _Quads(images, dev, flat_q, flat_f, counts, persp)
 
 
-def _stage_quads(qx, S, out=None, union=None, n_persp=0):
-    """dmx_edit_quad | dmx_edit_page | n_persp bytes in ONE pinned staging buffer, the first two tables filled and validated
-    (dmx_edit_quads_prepare).  Returns (host quads, host pages, the pinned storage, its numpy view, the page table's byte offset, the
-    offset of the rest)"""
+_QuadTables = collections.namedtuple("_QuadTables", "host pages persp stage dbuf off xoff")
+
+
+def _upload_quads(qx, S, out=None, union=None):
+    """the tables of one quad launch - dmx_edit_quad | dmx_edit_page, and with projective frames (qx.persp) | dmx_quad_persp - in ONE
+    pinned staging buffer, filled and validated (dmx_edit_quads_prepare, then dmx_edit_quads_persp_prepare), then ONE asynchronous copy on
+    the current stream.  S = 0 (rectify_quads): the strips alone, which depend neither on the frames nor on S.  Returns a _QuadTables:
+    the host tables (persp None for the similarity frame), the pinned storage, the device buffer, the byte offsets of the page table and
+    of the projective table in it."""
     B, P = len(qx.quads), len(qx.images)
     n_quads, n_pages = B * ctypes.sizeof(_cabi.EditQuad), P * ctypes.sizeof(_cabi.EditPage)
-    stage = torch.empty(n_quads + n_pages + n_persp, dtype=torch.uint8, pin_memory=True)
+    off, xoff = n_quads, n_quads + n_pages
+    stage = torch.empty(xoff + (B * ctypes.sizeof(_cabi.QuadPersp) if qx.persp is not None else 0), dtype=torch.uint8, pin_memory=True)
     st = stage.numpy()
     st[:] = 0
-    host = (_cabi.EditQuad * B).from_buffer(st[:n_quads])
-    pages = (_cabi.EditPage * P).from_buffer(st[n_quads:n_quads + n_pages])
+    host = (_cabi.EditQuad * B).from_buffer(st[:off])
+    pages = (_cabi.EditPage * P).from_buffer(st[off:xoff])
     lo = 0
     for p, (pg, img, n) in enumerate(zip(pages, qx.images, qx.counts)):
         pg.original = img.data_ptr()
@@ -804,36 +810,28 @@ def _stage_quads(qx, S, out=None, union=None, n_persp=0):
             it.cx2, it.cy2, it.crop_scale, it.ux, it.uy = f
             it.page = p
         lo += n
-    _cabi.check(_cabi.lib().dmx_edit_quads_prepare(pages, P, host, B, S), "edit_quads_prepare")
-    return host, pages, stage, st, n_quads, n_quads + n_pages
-
-
-def _to_device(qx, stage):
+    # (the placeholder frames of the strips and of the projective entries are prepared at any valid S)
+    _cabi.check(_cabi.lib().dmx_edit_quads_prepare(pages, P, host, B, max(S, 8) if qx.persp is not None or S == 0 else S), "edit_quads_prepare")
+    persp = None
+    if qx.persp is not None:
+        persp = (_cabi.QuadPersp * B).from_buffer(st[xoff:])
+        for e, f in zip(persp, qx.persp):
+            e.ci2, e.cj2, e.crop_scale = f
+        _cabi.check(_cabi.lib().dmx_edit_quads_persp_prepare(pages, P, host, persp, B, S), "edit_quads_persp_prepare")
     with torch.cuda.device(qx.dev):
         dbuf = torch.empty(stage.numel(), dtype=torch.uint8, device=qx.dev)
         dbuf.copy_(stage, non_blocking=True)                          # the one H2D copy
-    return dbuf
+    return _QuadTables(host, pages, persp, stage, dbuf, off, xoff)
 
 
-def _upload_quads(qx, S, out=None, union=None):
-    """the tables of one quad launch - dmx_edit_quad | dmx_edit_page - filled and validated (dmx_edit_quads_prepare) in ONE pinned staging
-    buffer, then ONE asynchronous copy on the current stream.  Returns (host quads, host pages, the pinned storage, the device buffer, the
-    byte offset of the page table in it)."""
-    host, pages, stage, st, off, _ = _stage_quads(qx, S, out, union)
-    return host, pages, stage, _to_device(qx, stage), off
-
-
-def _upload_quads_persp(qx, S, out=None, union=None):
-    """_upload_quads with the projective table behind the other two - dmx_edit_quad | dmx_edit_page | dmx_quad_persp -, filled from
-    qx.persp and prepared by dmx_edit_quads_persp_prepare (S = 0: the strip maps alone; the frames are not read).  Returns (host quads,
-    host pages, host projective table, the pinned storage, the device buffer, the page table's byte offset, the projective table's)."""
-    B = len(qx.quads)
-    host, pages, stage, st, off, xoff = _stage_quads(qx, max(S, 8), out, union, B * ctypes.sizeof(_cabi.QuadPersp))
-    persp = (_cabi.QuadPersp * B).from_buffer(st[xoff:])
-    for e, f in zip(persp, qx.persp):
-        e.ci2, e.cj2, e.crop_scale = f
-    _cabi.check(_cabi.lib().dmx_edit_quads_persp_prepare(pages, len(qx.images), host, persp, B, S), "edit_quads_persp_prepare")
-    return host, pages, persp, stage, _to_device(qx, stage), off, xoff
+def _call_quads(name, t, head, *tail):
+    """dmx_<name>(*head, the tables of t - host and device, pages then quads -, B, *tail, stream) on the current stream; with projective
+    frames dmx_<name>_persp, their table (host, device) spliced in behind the quads, where the C signature has it"""
+    base = t.dbuf.data_ptr()
+    tables = (t.pages, base + t.off, len(t.pages), t.host, base)
+    if t.persp is not None:
+        name, tables = name + "_persp", tables + (t.persp, base + t.xoff)
+    _cabi.check(getattr(_cabi.lib(), "dmx_" + name)(*head, *tables, len(t.host), *tail, _cabi.current_stream()), name)
 
 
 def preprocess_quads(images, quads, frames, size=512, perspective=False):
@@ -849,23 +847,13 @@ def preprocess_quads(images, quads, frames, size=512, perspective=False):
         frames = plan_quads([list(q) for q in quads], [(int(i.shape[0]), int(i.shape[1])) for i in images], True, S)
     qx = _check_quads(images, quads, frames, perspective)
     B = len(qx.quads)
-    if perspective:
-        host, pages, persp, stage, dbuf, off, xoff = _upload_quads_persp(qx, S)
-    else:
-        host, pages, stage, dbuf, off = _upload_quads(qx, S)
-    base = dbuf.data_ptr()
+    t = _upload_quads(qx, S)
     with torch.cuda.device(qx.dev):
         image = torch.empty(B, 3, S, S, dtype=torch.float32, device=qx.dev)
         masked = torch.empty(B, 3, S, S, dtype=torch.float32, device=qx.dev)
         mask = torch.empty(B, 1, S, S, dtype=torch.uint8, device=qx.dev)
         mask_lat = torch.empty(B, 1, S // 8, S // 8, dtype=torch.float32, device=qx.dev)
-        if perspective:
-            _cabi.check(_cabi.lib().dmx_preprocess_quads_persp(pages, base + off, len(qx.images), host, base, persp, base + xoff, B, S, _cabi.ptr(image),
-                                                              _cabi.ptr(masked), _cabi.ptr(mask), _cabi.ptr(mask_lat), _cabi.current_stream()),
-                        "preprocess_quads_persp")
-            return dict(image=image, masked_image=masked, mask=mask, mask_latent=mask_lat)
-        _cabi.check(_cabi.lib().dmx_preprocess_quads(pages, base + off, len(qx.images), host, base, B, S, _cabi.ptr(image), _cabi.ptr(masked),
-                                                    _cabi.ptr(mask), _cabi.ptr(mask_lat), _cabi.current_stream()), "preprocess_quads")
+        _call_quads("preprocess_quads", t, (), S, _cabi.ptr(image), _cabi.ptr(masked), _cabi.ptr(mask), _cabi.ptr(mask_lat))
     return dict(image=image, masked_image=masked, mask=mask, mask_latent=mask_lat)
 
 
@@ -887,18 +875,9 @@ def postprocess_quads(image_vae, images, quads, frames, return_mask=False, out=N
         out = [torch.empty_like(img) for img in qx.images] if out is None else out
         union = [torch.empty(img.shape[0], img.shape[1], dtype=torch.uint8, device=qx.dev) for img in qx.images] if return_mask else None
     v = image_vae.to(torch.float32).contiguous()
-    if perspective:
-        host, pages, persp, stage, dbuf, off, xoff = _upload_quads_persp(qx, S, out, union)
-        base = dbuf.data_ptr()
-        with torch.cuda.device(qx.dev):
-            _cabi.check(_cabi.lib().dmx_postprocess_paste_quads_persp(_cabi.ptr(v), S, pages, base + off, len(qx.images), host, base, persp, base + xoff, B,
-                                                                     _cabi.current_stream()), "postprocess_paste_quads_persp")
-        return (out, union) if return_mask else out
-    host, pages, stage, dbuf, off = _upload_quads(qx, S, out, union)
-    base = dbuf.data_ptr()
+    t = _upload_quads(qx, S, out, union)
     with torch.cuda.device(qx.dev):
-        _cabi.check(_cabi.lib().dmx_postprocess_paste_quads(_cabi.ptr(v), S, pages, base + off, len(qx.images), host, base, B,
-                                                           _cabi.current_stream()), "postprocess_paste_quads")
+        _call_quads("postprocess_paste_quads", t, (_cabi.ptr(v), S))
     return (out, union) if return_mask else out
 
 
@@ -909,19 +888,10 @@ def rectify_quads(images, quads, perspective=False):
     perspective=True: strips of the same sizes through the homography that takes the quad's corners to the strip's corners - a
     trapezoid comes out upright and without keystone (no frame is needed: the strip is the quad itself)."""
     qx = _check_quads(images, quads, None, perspective)
-    B = len(qx.quads)
-    if perspective:
-        host, pages, persp, stage, dbuf, off, xoff = _upload_quads_persp(qx, 0)
-    else:
-        host, pages, stage, dbuf, off = _upload_quads(qx, 8)           # (the strips depend neither on the frames nor on S)
-    total = int(host[B - 1].rect_off) + int(host[B - 1].rw) * int(host[B - 1].rh) * 3
-    base = dbuf.data_ptr()
+    t = _upload_quads(qx, 0)                                           # (the strips depend neither on the frames nor on S)
+    last = t.host[len(t.host) - 1]
+    total = int(last.rect_off) + int(last.rw) * int(last.rh) * 3
     with torch.cuda.device(qx.dev):
         buf = torch.empty(total, dtype=torch.uint8, device=qx.dev)
-        if perspective:
-            _cabi.check(_cabi.lib().dmx_rectify_quads_persp(pages, base + off, len(qx.images), host, base, persp, base + xoff, B, _cabi.ptr(buf), total,
-                                                           _cabi.current_stream()), "rectify_quads_persp")
-            return [buf[int(q.rect_off):int(q.rect_off) + int(q.rw) * int(q.rh) * 3].view(int(q.rh), int(q.rw), 3) for q in host]
-        _cabi.check(_cabi.lib().dmx_rectify_quads(pages, base + off, len(qx.images), host, base, B, _cabi.ptr(buf), total, _cabi.current_stream()),
-                    "rectify_quads")
-    return [buf[int(q.rect_off):int(q.rect_off) + int(q.rw) * int(q.rh) * 3].view(int(q.rh), int(q.rw), 3) for q in host]
+        _call_quads("rectify_quads", t, (), _cabi.ptr(buf), total)
+    return [buf[int(q.rect_off):int(q.rect_off) + int(q.rw) * int(q.rh) * 3].view(int(q.rh), int(q.rw), 3) for q in t.host]

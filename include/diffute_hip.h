@@ -1052,7 +1052,7 @@ int dmx_postprocess_paste_quads(const float* image_vae, int S, const dmx_edit_pa
 int dmx_rectify_quads(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_host,
                       const dmx_edit_quad* quads_device, int B, unsigned char* out, long long out_bytes, dmx_stream_t stream);
 
-/* Text in PERSPECTIVE: a projective frame beside the similarity frame of the quad entries (prepost_persp.hip; the arithmetic is stated in
+/* Text in PERSPECTIVE: a projective frame beside the similarity frame of the quad entries (prepost_quad.hip; the arithmetic is stated in
  * csrc/prepost_persp.h).  A trapezoid - a line on a phone photo, a sign - is no rotated rectangle: through one rotation and one scale the
  * network sees keystoned text.  Here the homography that takes the quad to its upright rw x rh strip drives the crop (a square window
  * of side crop_scale STRIP pixels, centred at (ci2 / 2, cj2 / 2) in the strip's pixel-index space, extrapolated by the homography), the

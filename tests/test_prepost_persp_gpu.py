@@ -1,4 +1,4 @@
-"""Quadrilateral regions in perspective on the GPU (csrc/prepost_persp.hip through prepost.preprocess_quads / postprocess_quads /
+"""Quadrilateral regions in perspective on the GPU (csrc/prepost_quad.hip through prepost.preprocess_quads / postprocess_quads /
 rectify_quads with perspective=True, and pipeline.edit_quads(perspective=True)) against the numpy restatement of csrc/prepost_persp.h
 (tests/persp_restatement.py, fed with the integers the prepare entries filled) - bit exact, on both builds.  The cases are
 tests/persp_cases.py: nine quads on three pages in one launch at S = 64 - trapezoids narrowing to the right and upwards, a general quad
@@ -254,7 +254,7 @@ def test_refusals_launch_nothing(cuda, ref):
     pre_out = [torch.full((N * 3 * S * S,), 3.0, device=cuda), torch.full((N * 3 * S * S,), 3.0, device=cuda),
                torch.full((N * S * S,), 0x5A, dtype=torch.uint8, device=cuda), torch.full((N * 64,), 3.0, device=cuda)]
     for spoil in ("map", "quad", "page"):
-        host, pages, persp, stage, dbuf, off, xoff = prepost._upload_quads_persp(qx, S, views, None)
+        host, pages, persp, stage, dbuf, off, xoff = prepost._upload_quads(qx, S, views, None)
         if spoil == "map":
             persp[6].strip.t[0] += 1
             persp[6].crop.t[6] += 1

@@ -294,7 +294,7 @@ def test_refusals_launch_nothing(cuda, ref):
     pre_out = [torch.full((N * 3 * S * S,), 3.0, device=cuda), torch.full((N * 3 * S * S,), 3.0, device=cuda),
                torch.full((N * S * S,), 0x5A, dtype=torch.uint8, device=cuda), torch.full((N * 64,), 3.0, device=cuda)]
     for spoil in ("item", "page"):
-        host, pages, stage, dbuf, off = prepost._upload_quads(qx, S, views, None)
+        host, pages, _, stage, dbuf, off, _ = prepost._upload_quads(qx, S, views, None)
         if spoil == "item":
             host[6].x[0] = 260                                 # the first column right of page 2
         else:
