@@ -478,3 +478,9 @@ int dmx_check_page_table(const char* what, const dmx_edit_page* pages, int P, in
 // what the paged entries ask of the pages' addresses, and the select entries of their scalars (also asked by prepost_blend.hip)
 int dmx_check_page_addresses(const char* what, const dmx_edit_page* pages, int P, bool need_out);
 int dmx_check_select_scalars(const char* what, int K, float threshold);
+// ------------------------------------------------------------------ readback.hip
+// what every read-back entry asks of its scalars, and of the pass tables of item b whose source is src_w x src_h - a box's slice in
+// readback.hip, a quad's strip in prepost_quad.hip: inside `tables`, at most max_taps taps, skipped (offset < 0) where the sizes are equal
+int dmx_check_readback_scalars(const char* what, int K, int max_taps, long long table_ints, int S_h, int S_w);
+int dmx_check_readback_item(const char* what, int b, const dmx_readback_pass& ps, int src_w, int src_h, int max_taps, long long table_ints, int S_h,
+                            int S_w);

@@ -117,11 +117,16 @@ __device__ __forceinline__ void pre_pixel(const unsigned char* img, int H, int W
   }
   vk = round32(w00 * m00 + w01 * m01 + w10 * m10 + w11 * m11);
 }
+// The single-rounding bilinear of four taps: at(kx, ky) -> the byte at tap (kx ? tx.i1 : tx.i0, ky ? ty.i1 : ty.i0).  Integers: exact
+// whatever the order of the sum.
+template <class At>
+__device__ __forceinline__ int sample4(const Tap16& tx, const Tap16& ty, At at) {
+  return round32(ty.w0 * tx.w0 * at(0, 0) + ty.w0 * tx.w1 * at(1, 0) + ty.w1 * tx.w0 * at(0, 1) + ty.w1 * tx.w1 * at(1, 1));
+}
 // one channel of the page itself at (X16, Y16): the rectified strip
 __device__ __forceinline__ int page_sample(const unsigned char* img, int W, const Tap16& tx, const Tap16& ty, int c) {
   const unsigned char *r0 = img + (size_t)ty.i0 * W * 3, *r1 = img + (size_t)ty.i1 * W * 3;
-  return round32(ty.w0 * tx.w0 * r0[tx.i0 * 3 + c] + ty.w0 * tx.w1 * r0[tx.i1 * 3 + c] + ty.w1 * tx.w0 * r1[tx.i0 * 3 + c] +
-                 ty.w1 * tx.w1 * r1[tx.i1 * 3 + c]);
+  return sample4(tx, ty, [&](int kx, int ky) -> long long { return (ky ? r1 : r0)[(kx ? tx.i1 : tx.i0) * 3 + c]; });
 }
 
 // Channel c of the decoder output vae [3][S][S] at the crop coordinates (U16, V16), as the byte that is pasted

@@ -1,7 +1,10 @@
 // Quadrilateral text regions: the two ends of the editing path for skewed, rotated and keystoned lines (pipeline.edit_quads), beside
 // prepost_batch.hip's axis-aligned boxes.  Items are dmx_edit_quad, pages the dmx_edit_page table of the *_pages entries.  Three
 // kernels, one launch each: the crop (mask = the quad itself, seen through the frame), the paste (every page pixel mapped back through
-// the inverse frame; the last quad that covers a pixel decides) and the rectify (a quad as an upright strip, for the OCR model).
+// the inverse frame; the last quad that covers a pixel decides) and the rectify (a quad as an upright strip, for the OCR model).  Two
+// more for verified edits, beside readback.hip's for boxes: the read-back (K candidates per quad -> the OCR model's pixel_values: paste,
+// rectify and Pillow resample of one candidate in one pass, no page and no strip in memory) and the select-paste (the paste of the
+// best-scoring candidate per quad, chosen on the device).
 // Each kernel is written ONCE, over a frame that says where the sample coordinates come from:
 //   SimilarityFrame   one rotation and one scale, the Q15 matrices of dmx_edit_quad (prepost_quad.h): the dmx_*_quads entries;
 //   ProjectiveFrame   the homography that takes the quad to its upright strip, from a parallel, index-aligned table of dmx_quad_persp
@@ -14,6 +17,7 @@
 #include "kernels.h"
 #include "prepost_paste.h"
 #include "prepost_persp.h"
+#include "glyph_resample.h"
 
 namespace {
 using namespace dmx_quad;
@@ -103,45 +107,154 @@ struct PostQuadArgs {
   const dmx_edit_quad* quads; int B;
 };
 
-// The paste over P pages: blocks enumerate (page, row, 256-column tile) along grid.x as in dmx_postprocess_pages_kernel
-// (dmx_paste::page_block); a block stages its page's quads - corners, edges, bounding box - in LDS.  A pixel scans them last to first,
-// stops at the first quad that covers it and maps itself through THAT item's frame.
+// Item b's crop coordinates of page pixel (x, y), and whether the pixel lies on that crop with the frame's map defined there: what decides
+// between the decoder's byte and the original one, in the paste and in the read-back alike.
 template <class Frame>
-__global__ __launch_bounds__(256) void dmx_postprocess_quads_kernel(const PostQuadArgs p, const Frame frame) {
-  __shared__ QuadEdges s_e[DMX_EDIT_MAX_ITEMS];
-  dmx_paste::PageBlock t;
-  if (!dmx_paste::page_block(p.pages, p.P, p.B, 65535, t)) return;             // (uniform per block: a stale table)
-  const dmx_edit_page& pg = t.pg;
-  const int lo = t.lo, n = t.n, x = t.x, y = t.y;
-  if ((int)threadIdx.x < n) {
-    const dmx_edit_quad& q = p.quads[lo + threadIdx.x];
+__device__ __forceinline__ bool on_crop(const Frame& frame, const dmx_edit_quad* quads, int b, int S, int x, int y, long long& U16, long long& V16) {
+  const long long top = ((long long)S << 16) - 32768;
+  return frame.paste(quads, b, S, x, y, U16, V16) && U16 >= -32768 && U16 < top && V16 >= -32768 && V16 < top;
+}
+
+// The paste over P pages: blocks enumerate (page, row, 256-column tile) along grid.x as in dmx_postprocess_pages_kernel
+// (dmx_paste::page_block); a block stages its page's quads - corners, edges, bounding box - in LDS (stage_edges; the caller's barrier
+// follows).  A pixel scans them last to first, stops at the first quad that covers it and is not skipped, and maps itself through THAT
+// item's frame (paste_quads_pixel).  row(b) -> item lo + b's row of p.vae, or < 0: the item is skipped - transparent, an earlier quad
+// under it still shows -, as paste_pixel of prepost_batch.hip has it; the union mask counts skipped items too.
+__device__ __forceinline__ void stage_edges(const PostQuadArgs& p, const dmx_paste::PageBlock& t, QuadEdges* s_e) {
+  if ((int)threadIdx.x < t.n) {
+    const dmx_edit_quad& q = p.quads[t.lo + threadIdx.x];
     QuadEdges e;
 #pragma unroll
     for (int k = 0; k < 4; ++k) { e.x[k] = q.x[k]; e.y[k] = q.y[k]; e.ex[k] = q.ex[k]; e.ey[k] = q.ey[k]; }
     e.bx1 = q.bx1; e.by1 = q.by1; e.bx2 = q.bx2; e.by2 = q.by2;
     s_e[threadIdx.x] = e;
   }
-  __syncthreads();
-  if (x >= pg.W) return;
-  int hit = -1;
-  for (int b = n - 1; b >= 0; --b) {
+}
+
+template <class Frame, class Row>
+__device__ __forceinline__ void paste_quads_pixel(const PostQuadArgs& p, const Frame& frame, const dmx_paste::PageBlock& t, const QuadEdges* s_e,
+                                                  Row row) {
+  const dmx_edit_page& pg = t.pg;
+  const int lo = t.lo, x = t.x, y = t.y;
+  int hit = -1, any = 0;
+  for (int b = t.n - 1; b >= 0; --b) {
     const QuadEdges& e = s_e[b];
-    if (x >= e.bx1 && x <= e.bx2 && y >= e.by1 && y <= e.by2 && inside(e, x, y)) { hit = b; break; }
+    if (x >= e.bx1 && x <= e.bx2 && y >= e.by1 && y <= e.by2 && inside(e, x, y)) {
+      any = 1;
+      if (row(b) >= 0) { hit = b; break; }
+    }
   }
   const unsigned char* ori = (const unsigned char*)pg.original;
   unsigned char *out = (unsigned char*)pg.out, *umask = (unsigned char*)pg.union_mask;
   const size_t o = ((size_t)y * pg.W + x) * 3;
-  if (umask) umask[(size_t)y * pg.W + x] = (unsigned char)(hit >= 0 ? 1 : 0);
-  bool paste = false;
+  if (umask) umask[(size_t)y * pg.W + x] = (unsigned char)any;
   long long U16 = 0, V16 = 0;
-  if (hit >= 0) {
-    const long long top = ((long long)p.S << 16) - 32768;
-    paste = frame.paste(p.quads, lo + hit, p.S, x, y, U16, V16) && U16 >= -32768 && U16 < top && V16 >= -32768 && V16 < top;
-  }
+  const bool paste = hit >= 0 && on_crop(frame, p.quads, lo + hit, p.S, x, y, U16, V16);
   if (!paste) { out[o] = ori[o]; out[o + 1] = ori[o + 1]; out[o + 2] = ori[o + 2]; return; }
-  const float* vae = p.vae + (size_t)(lo + hit) * 3 * p.S * p.S;
+  const float* vae = p.vae + (size_t)row(hit) * 3 * p.S * p.S;
 #pragma unroll
   for (int c = 0; c < 3; ++c) out[o + c] = post_pixel(vae, p.S, c, U16, V16);
+}
+
+template <class Frame>
+__global__ __launch_bounds__(256) void dmx_postprocess_quads_kernel(const PostQuadArgs p, const Frame frame) {
+  __shared__ QuadEdges s_e[DMX_EDIT_MAX_ITEMS];
+  dmx_paste::PageBlock t;
+  if (!dmx_paste::page_block(p.pages, p.P, p.B, 65535, t)) return;             // (uniform per block: a stale table)
+  stage_edges(p, t, s_e);
+  __syncthreads();
+  if (t.x >= t.pg.W) return;
+  const int lo = t.lo;
+  paste_quads_pixel(p, frame, t, s_e, [lo](int b) -> int { return lo + b; });
+}
+
+// Best of K candidates per quad, chosen and pasted in ONE launch: p.vae is [B][K][3][S][S], scores [B][K] lives on the device.  choice is
+// [B] over all items and every block derives all of it by the rule of the box pastes (dmx_paste::select_choices, which ends with a
+// barrier); block 0 alone stores it, with plain vector stores.  The block then stages ONE int per item of its page beside the edges -
+// the item's row of p.vae, or -1 for a skipped item - so that a pixel's scan reads s_row[b] as it reads s_e[b].
+template <class Frame>
+__global__ __launch_bounds__(256) void dmx_postprocess_select_quads_kernel(const PostQuadArgs p, const Frame frame, const float* scores, int K,
+                                                                           float threshold, int* choice) {
+  __shared__ QuadEdges s_e[DMX_EDIT_MAX_ITEMS];
+  __shared__ float s_score[DMX_EDIT_MAX_ITEMS * DMX_SELECT_MAX_CANDIDATES];
+  __shared__ int s_choice[DMX_EDIT_MAX_ITEMS], s_row[DMX_EDIT_MAX_ITEMS];
+  dmx_paste::PageBlock t;
+  const bool live = dmx_paste::page_block(p.pages, p.P, p.B, 65535, t);
+  if (!live && blockIdx.x != 0) return;
+  if (live) stage_edges(p, t, s_e);
+  dmx_paste::select_choices(scores, p.B, K, threshold, s_score, s_choice, choice, blockIdx.x == 0);
+  if (!live) return;                                                           // (uniform per block)
+  if ((int)threadIdx.x < t.n) {
+    const int b = t.lo + (int)threadIdx.x, k = min(s_choice[b], K - 1);
+    s_row[threadIdx.x] = k < 0 ? -1 : b * K + k;
+  }
+  __syncthreads();
+  if (t.x >= t.pg.W) return;
+  paste_quads_pixel(p, frame, t, s_e, [&](int b) -> int { return s_row[b]; });
+}
+
+struct ReadQuadArgs {
+  const float* vae; int S;                                 // decoder outputs [B][K][3][S][S] in [-1, 1]
+  const dmx_edit_page* pages; int P;
+  const dmx_edit_quad* quads; const dmx_readback_pass* passes; int K;
+  const int* tab; const float* norm;
+  int S_h, S_w; float* out; unsigned char* out_u8;         // [B*K][3][S_h][S_w]
+};
+
+// OCR read-back of K candidates per quad: from the decoder outputs straight to the OCR model's pixel_values, grid (ceil(S_w / 256), S_h,
+// B * K), block z = row r = b * K + k.  The row is the Pillow resample (glyph_resample.h) of quad b's upright strip of the page that the
+// paste above would write for candidate r ALONE over the original page - a one-quad table -, but neither that page nor the strip exists:
+// strip byte (i, j) is the rectify kernel's sample4 of four page taps, and a tap (after its clamp to the page) is the candidate's
+// post_pixel where the paste would have pasted it - inside quad b and on its crop (on_crop) -, the original byte elsewhere.  A thread
+// keeps the three channels of the strip pixel it computed last: the resample asks for them one after the other.
+template <class Frame>
+__global__ __launch_bounds__(256) void dmx_readback_quads_kernel(const ReadQuadArgs p, const Frame frame) {
+  __shared__ typename Frame::Item s;
+  const int r = blockIdx.z, b = r / p.K;                                       // (the grid is B * K rows deep: b lies inside the tables)
+  frame.stage(s, p.quads, b);
+  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y;
+  if (ox >= p.S_w) return;
+  const dmx_edit_page pg = p.pages[min(max(s.q.page, 0), p.P - 1)];
+  if (pg.H <= 0 || pg.W <= 0) return;
+  const dmx_readback_pass ps = p.passes[b];
+  const int rw = max(s.q.rw, 1), rh = max(s.q.rh, 1);
+  const unsigned char* ori = (const unsigned char*)pg.original;
+  const float* vae = p.vae + (size_t)r * 3 * p.S * p.S;
+  int ly = -1, lx = -1, lv[3] = {0, 0, 0};
+  auto px = [&](int y, int x, int c) -> int {                                  // byte (x, y) of the strip of the pasted page
+    if (y != ly || x != lx) {
+      ly = y; lx = x;
+      long long X16 = 0, Y16 = 0;
+      frame.strip(s, 2ll * x + 1 - rw, 2ll * y + 1 - rh, X16, Y16);
+      const Tap16 tx = tap16(X16, pg.W), ty = tap16(Y16, pg.H);
+      bool gen[2][2];
+      long long U16[2][2], V16[2][2];
+#pragma unroll
+      for (int ky = 0; ky < 2; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 2; ++kx) {
+          const int X = kx ? tx.i1 : tx.i0, Y = ky ? ty.i1 : ty.i0;
+          U16[ky][kx] = V16[ky][kx] = 0;
+          gen[ky][kx] = inside(s.q, X, Y) && on_crop(frame, p.quads, b, p.S, X, Y, U16[ky][kx], V16[ky][kx]);
+        }
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch)
+        lv[ch] = sample4(tx, ty, [&](int kx, int ky) -> long long {
+          if (gen[ky][kx]) return post_pixel(vae, p.S, ch, U16[ky][kx], V16[ky][kx]);
+          return ori[((size_t)(ky ? ty.i1 : ty.i0) * pg.W + (kx ? tx.i1 : tx.i0)) * 3 + ch];
+        });
+    }
+    return lv[c];
+  };
+  const dmx_glyph::Passes tp{ps.h_off, ps.h_taps, ps.v_off, ps.v_taps};
+  int v[3];
+  dmx_glyph::glyph_resample_pixel(px, rh, rw, p.tab, tp, p.S_h, p.S_w, ox, oy, v);
+  const size_t plane = (size_t)p.S_h * p.S_w, o = (size_t)r * 3 * plane + (size_t)oy * p.S_w + ox;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    p.out[o + c * plane] = p.norm[c * 256 + v[c]];
+    if (p.out_u8) p.out_u8[o + c * plane] = (unsigned char)v[c];
+  }
 }
 
 struct RectQuadArgs {
@@ -281,6 +394,35 @@ int launch_post(const char* kernel, const Frame& frame, const float* image_vae, 
 }
 
 template <class Frame>
+int launch_select(const char* kernel, const Frame& frame, const float* image_vae, int S, const float* scores, float threshold, int* choice,
+                  const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_device, int B, int K,
+                  dmx_stream_t stream) {
+  PostQuadArgs p{image_vae, S, pages_device, P, quads_device, B};
+  hipLaunchKernelGGL(dmx_postprocess_select_quads_kernel<Frame>, dim3(pages_host[P - 1].block_lo + pages_host[P - 1].blocks), dim3(256), 0,
+                     (hipStream_t)stream, p, frame, scores, K, threshold, choice);
+  return dmx_check_launch(kernel);
+}
+
+// what the read-back asks of checked, prepared quads beyond their tables: the pass tables of every strip (source size rw x rh)
+int check_readback_quads(const char* what, const dmx_edit_quad* quads_host, const dmx_readback_pass* passes_host, int B, int max_taps,
+                         long long table_ints, int S_h, int S_w) {
+  for (int b = 0; b < B; ++b) {
+    const int rc = dmx_check_readback_item(what, b, passes_host[b], quads_host[b].rw, quads_host[b].rh, max_taps, table_ints, S_h, S_w);
+    if (rc != DMX_OK) return rc;
+  }
+  return DMX_OK;
+}
+
+template <class Frame>
+int launch_readback(const char* kernel, const Frame& frame, const float* image_vae, int S, const dmx_edit_page* pages_device, int P,
+                    const dmx_edit_quad* quads_device, int B, int K, const int* tables, const float* norm, const dmx_readback_pass* passes_device,
+                    int S_h, int S_w, float* out_pixel_values, unsigned char* out_resized, dmx_stream_t stream) {
+  ReadQuadArgs p{image_vae, S, pages_device, P, quads_device, passes_device, K, tables, norm, S_h, S_w, out_pixel_values, out_resized};
+  hipLaunchKernelGGL(dmx_readback_quads_kernel<Frame>, dim3(cdiv(S_w, 256), S_h, B * K), dim3(256), 0, (hipStream_t)stream, p, frame);
+  return dmx_check_launch(kernel);
+}
+
+template <class Frame>
 int launch_rectify(const char* what, const char* kernel, const Frame& frame, const dmx_edit_page* pages_device, int P,
                    const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device, int B, unsigned char* out, long long out_bytes,
                    dmx_stream_t stream) {
@@ -347,6 +489,34 @@ extern "C" int dmx_rectify_quads(const dmx_edit_page* pages_host, const dmx_edit
                         stream);
 }
 
+extern "C" int dmx_readback_pixel_values_quads(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                               const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device, int B, int K, const int* tables,
+                                               long long table_ints, const float* norm, const dmx_readback_pass* passes_host,
+                                               const dmx_readback_pass* passes_device, int max_taps, int S_h, int S_w, float* out_pixel_values,
+                                               unsigned char* out_resized, dmx_stream_t stream) {
+  const char* what = "readback_pixel_values_quads";
+  DMX_REQUIRE(image_vae && pages_device && quads_device && tables && norm && passes_host && passes_device && out_pixel_values, "%s: null argument", what);
+  int rc = dmx_check_readback_scalars(what, K, max_taps, table_ints, S_h, S_w);
+  if (rc == DMX_OK) rc = check_tables(what, pages_host, P, quads_host, B, S, true, false);
+  if (rc == DMX_OK) rc = check_readback_quads(what, quads_host, passes_host, B, max_taps, table_ints, S_h, S_w);
+  if (rc != DMX_OK) return rc;
+  return launch_readback("dmx_readback_quads_kernel", SimilarityFrame{}, image_vae, S, pages_device, P, quads_device, B, K, tables, norm,
+                         passes_device, S_h, S_w, out_pixel_values, out_resized, stream);
+}
+
+extern "C" int dmx_postprocess_paste_select_quads(const float* image_vae, int S, const float* scores, float threshold, int* choice,
+                                                  const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                                  const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device, int B, int K,
+                                                  dmx_stream_t stream) {
+  const char* what = "postprocess_paste_select_quads";
+  DMX_REQUIRE(image_vae && scores && choice && pages_device && quads_device, "%s: null argument", what);
+  int rc = dmx_check_select_scalars(what, K, threshold);
+  if (rc == DMX_OK) rc = check_tables(what, pages_host, P, quads_host, B, S, true, true);
+  if (rc != DMX_OK) return rc;
+  return launch_select("dmx_postprocess_select_quads_kernel", SimilarityFrame{}, image_vae, S, scores, threshold, choice, pages_host, pages_device, P,
+                       quads_device, B, K, stream);
+}
+
 // ---- the projective frame: the quad table's own frames are placeholders, not looked at
 extern "C" int dmx_preprocess_quads_persp(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_quad* quads_host,
                                           const dmx_edit_quad* quads_device, const dmx_quad_persp* persp_host, const dmx_quad_persp* persp_device,
@@ -382,4 +552,39 @@ extern "C" int dmx_rectify_quads_persp(const dmx_edit_page* pages_host, const dm
   if (rc != DMX_OK) return rc;
   return launch_rectify("rectify_quads_persp", "dmx_rectify_quads_persp_kernel", ProjectiveFrame{persp_device}, pages_device, P, quads_host,
                         quads_device, B, out, out_bytes, stream);
+}
+
+extern "C" int dmx_readback_pixel_values_quads_persp(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device,
+                                                     int P, const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device,
+                                                     const dmx_quad_persp* persp_host, const dmx_quad_persp* persp_device, int B, int K,
+                                                     const int* tables, long long table_ints, const float* norm,
+                                                     const dmx_readback_pass* passes_host, const dmx_readback_pass* passes_device, int max_taps,
+                                                     int S_h, int S_w, float* out_pixel_values, unsigned char* out_resized, dmx_stream_t stream) {
+  const char* what = "readback_pixel_values_quads_persp";
+  DMX_REQUIRE(image_vae && pages_device && quads_device && persp_device && tables && norm && passes_host && passes_device && out_pixel_values,
+              "%s: null argument", what);
+  DMX_REQUIRE(S > 0 && S <= 65535, "%s: bad S = %d (1 .. 65535)", what, S);
+  int rc = dmx_check_readback_scalars(what, K, max_taps, table_ints, S_h, S_w);
+  if (rc == DMX_OK) rc = check_tables(what, pages_host, P, quads_host, B, 0, false, false);
+  if (rc == DMX_OK) rc = check_persp(what, quads_host, persp_host, nullptr, B, S);
+  if (rc == DMX_OK) rc = check_readback_quads(what, quads_host, passes_host, B, max_taps, table_ints, S_h, S_w);
+  if (rc != DMX_OK) return rc;
+  return launch_readback("dmx_readback_quads_persp_kernel", ProjectiveFrame{persp_device}, image_vae, S, pages_device, P, quads_device, B, K, tables,
+                         norm, passes_device, S_h, S_w, out_pixel_values, out_resized, stream);
+}
+
+extern "C" int dmx_postprocess_paste_select_quads_persp(const float* image_vae, int S, const float* scores, float threshold, int* choice,
+                                                        const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                                        const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device,
+                                                        const dmx_quad_persp* persp_host, const dmx_quad_persp* persp_device, int B, int K,
+                                                        dmx_stream_t stream) {
+  const char* what = "postprocess_paste_select_quads_persp";
+  DMX_REQUIRE(image_vae && scores && choice && pages_device && quads_device && persp_device, "%s: null argument", what);
+  DMX_REQUIRE(S > 0 && S <= 65535, "%s: bad S = %d (1 .. 65535)", what, S);
+  int rc = dmx_check_select_scalars(what, K, threshold);
+  if (rc == DMX_OK) rc = check_tables(what, pages_host, P, quads_host, B, 0, false, true);
+  if (rc == DMX_OK) rc = check_persp(what, quads_host, persp_host, nullptr, B, S);
+  if (rc != DMX_OK) return rc;
+  return launch_select("dmx_postprocess_select_quads_persp_kernel", ProjectiveFrame{persp_device}, image_vae, S, scores, threshold, choice, pages_host,
+                       pages_device, P, quads_device, B, K, stream);
 }

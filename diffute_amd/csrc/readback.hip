@@ -66,34 +66,44 @@ __global__ __launch_bounds__(128) void dmx_readback_pages_kernel(ReadbackArgs p,
   readback_row(p, r, ox, oy);
 }
 
-// what the read-back asks of the items [lo, hi) beyond dmx_check_edit_items: a non-empty box inside the H x W page, pass tables inside `tables`
-int check_readback_items(const char* what, const dmx_edit_item* items_host, const dmx_readback_pass* passes_host, int lo, int hi, int H, int W,
+// what the read-back asks of the boxes [lo, hi) beyond dmx_check_edit_items: a non-empty box inside the H x W page, and of each one's passes
+// what dmx_check_readback_item asks at the box's size
+int check_readback_boxes(const char* what, const dmx_edit_item* items_host, const dmx_readback_pass* passes_host, int lo, int hi, int H, int W,
                          int max_taps, long long table_ints, int S_h, int S_w) {
   for (int b = lo; b < hi; ++b) {
     const dmx_edit_item& it = items_host[b];
     DMX_REQUIRE(it.x2 > it.x1 && it.y2 > it.y1, "%s: item %d: empty box (%d, %d, %d, %d)", what, b, it.x1, it.y1, it.x2, it.y2);
     DMX_REQUIRE(it.x1 >= 0 && it.y1 >= 0 && it.x2 <= W && it.y2 <= H, "%s: item %d: box (%d, %d, %d, %d) outside the %dx%d image", what, b, it.x1,
                 it.y1, it.x2, it.y2, W, H);
-    const dmx_readback_pass& ps = passes_host[b];
-    const struct { const char* name; int off, taps, n_in, n_out; } pass[2] = {{"horizontal", ps.h_off, ps.h_taps, it.x2 - it.x1, S_w},
-                                                                             {"vertical", ps.v_off, ps.v_taps, it.y2 - it.y1, S_h}};
-    for (const auto& q : pass) {
-      if (q.n_in == q.n_out) {                                                                 // equal sizes: Pillow skips the pass
-        DMX_REQUIRE(q.off < 0, "%s: item %d: the %s pass resizes %d -> %d and must be skipped (offset < 0)", what, b, q.name, q.n_in, q.n_out);
-        continue;
-      }
-      DMX_REQUIRE(q.off >= 0 && q.taps >= 1 && q.taps <= max_taps, "%s: item %d: %s pass: offset %d, %d taps (max_taps %d)", what, b, q.name, q.off,
-                  q.taps, max_taps);
-      DMX_REQUIRE((long long)q.off + 2ll * q.n_out + (long long)q.n_out * q.taps <= table_ints,
-                  "%s: item %d: the %s table (offset %d, %d x %d taps) ends past the %lld ints of `tables`", what, b, q.name, q.off, q.n_out, q.taps,
-                  table_ints);
+    const int rc = dmx_check_readback_item(what, b, passes_host[b], it.x2 - it.x1, it.y2 - it.y1, max_taps, table_ints, S_h, S_w);
+    if (rc != DMX_OK) return rc;
+  }
+  return DMX_OK;
+}
+}  // namespace
+
+// The pass tables of item b, whose source - a box's slice, a quad's strip - is src_w x src_h: inside `tables`, and skipped where the sizes
+// are equal
+int dmx_check_readback_item(const char* what, int b, const dmx_readback_pass& ps, int src_w, int src_h, int max_taps, long long table_ints, int S_h,
+                            int S_w) {
+  const struct { const char* name; int off, taps, n_in, n_out; } pass[2] = {{"horizontal", ps.h_off, ps.h_taps, src_w, S_w},
+                                                                           {"vertical", ps.v_off, ps.v_taps, src_h, S_h}};
+  for (const auto& q : pass) {
+    if (q.n_in == q.n_out) {                                                                   // equal sizes: Pillow skips the pass
+      DMX_REQUIRE(q.off < 0, "%s: item %d: the %s pass resizes %d -> %d and must be skipped (offset < 0)", what, b, q.name, q.n_in, q.n_out);
+      continue;
     }
+    DMX_REQUIRE(q.off >= 0 && q.taps >= 1 && q.taps <= max_taps, "%s: item %d: %s pass: offset %d, %d taps (max_taps %d)", what, b, q.name, q.off,
+                q.taps, max_taps);
+    DMX_REQUIRE((long long)q.off + 2ll * q.n_out + (long long)q.n_out * q.taps <= table_ints,
+                "%s: item %d: the %s table (offset %d, %d x %d taps) ends past the %lld ints of `tables`", what, b, q.name, q.off, q.n_out, q.taps,
+                table_ints);
   }
   return DMX_OK;
 }
 
-// the scalar arguments the one-page and the paged entry share
-int check_readback_scalars(const char* what, int K, int max_taps, long long table_ints, int S_h, int S_w) {
+// the scalar arguments every read-back entry shares (boxes here, quads in prepost_quad.hip)
+int dmx_check_readback_scalars(const char* what, int K, int max_taps, long long table_ints, int S_h, int S_w) {
   DMX_REQUIRE(K >= 1 && K <= DMX_SELECT_MAX_CANDIDATES, "%s: %d candidates per box, expected 1 .. %d", what, K, DMX_SELECT_MAX_CANDIDATES);
   DMX_REQUIRE(S_h > 0 && S_h <= 65535 && S_w > 0 && S_w <= 65535, "%s: bad output size %dx%d", what, S_w, S_h);
   DMX_REQUIRE(max_taps >= 0 && max_taps <= DMX_GLYPH_MAX_TAPS,
@@ -102,7 +112,6 @@ int check_readback_scalars(const char* what, int K, int max_taps, long long tabl
   DMX_REQUIRE(table_ints >= 0 && table_ints < (1ll << 31), "%s: bad table size %lld", what, table_ints);
   return DMX_OK;
 }
-}  // namespace
 
 extern "C" int dmx_readback_pixel_values(const float* image_vae, int S, const unsigned char* original_hwc, int H, int W,
                                          const dmx_edit_item* items_host, const dmx_edit_item* items_device, int B, int K, const int* tables,
@@ -111,9 +120,9 @@ extern "C" int dmx_readback_pixel_values(const float* image_vae, int S, const un
                                          unsigned char* out_resized, dmx_stream_t stream) {
   const char* what = "readback_pixel_values";
   DMX_REQUIRE(image_vae && original_hwc && items_device && tables && norm && passes_host && passes_device && out_pixel_values, "%s: null argument", what);
-  int rc = check_readback_scalars(what, K, max_taps, table_ints, S_h, S_w);
+  int rc = dmx_check_readback_scalars(what, K, max_taps, table_ints, S_h, S_w);
   if (rc == DMX_OK) rc = dmx_check_edit_items(what, items_host, B, H, W, S, true);
-  if (rc == DMX_OK) rc = check_readback_items(what, items_host, passes_host, 0, B, H, W, max_taps, table_ints, S_h, S_w);
+  if (rc == DMX_OK) rc = check_readback_boxes(what, items_host, passes_host, 0, B, H, W, max_taps, table_ints, S_h, S_w);
   if (rc != DMX_OK) return rc;
   ReadbackArgs p{image_vae, S, original_hwc, H, W, items_device, passes_device, B, K, tables, norm, S_h, S_w, out_pixel_values, out_resized};
   hipLaunchKernelGGL(dmx_readback_pixel_values_kernel, dim3(cdiv(S_w, 128), S_h, B * K), dim3(128), 0, (hipStream_t)stream, p);
@@ -128,13 +137,13 @@ extern "C" int dmx_readback_pixel_values_pages(const float* image_vae, int S, co
   const char* what = "readback_pixel_values_pages";
   DMX_REQUIRE(image_vae && pages_device && items_device && tables && norm && passes_host && passes_device && out_pixel_values, "%s: null argument", what);
   DMX_REQUIRE(S > 0 && S <= 65535, "%s: bad S = %d", what, S);
-  int rc = check_readback_scalars(what, K, max_taps, table_ints, S_h, S_w);
+  int rc = dmx_check_readback_scalars(what, K, max_taps, table_ints, S_h, S_w);
   if (rc == DMX_OK) rc = dmx_check_edit_pages(what, pages_host, P, items_host, B, S, true);
   if (rc != DMX_OK) return rc;
   for (int q = 0; q < P; ++q) {
     const dmx_edit_page& pg = pages_host[q];
     DMX_REQUIRE(pg.original, "%s: page %d: null original image", what, q);
-    rc = check_readback_items(what, items_host, passes_host, pg.item_lo, pg.item_hi, pg.H, pg.W, max_taps, table_ints, S_h, S_w);
+    rc = check_readback_boxes(what, items_host, passes_host, pg.item_lo, pg.item_hi, pg.H, pg.W, max_taps, table_ints, S_h, S_w);
     if (rc != DMX_OK) return rc;
   }
   ReadbackArgs p{image_vae, S, nullptr, 0, 0, items_device, passes_device, B, K, tables, norm, S_h, S_w, out_pixel_values, out_resized};

@@ -309,21 +309,12 @@ def edit_quads(unet, vae, scheduler, images, quads, encoder_hidden_states, num_i
 
     blend: must be None.  The feathered, colour-matched paste of edit_boxes is not built for quads: the ramp would have to be measured in
     the strip's coordinates, not the page's."""
-    if blend is not None:
-        raise NotImplementedError("edit_quads: blend is not supported for quads (the ramp would have to be measured in strip coordinates); pass None")
+    _no_quad_blend(blend, "edit_quads")
     perspective = bool(perspective)
     if int(batch_size) < 1:
         raise ValueError("batch_size must be at least 1")
     cache_interval = _check_cache_interval(cache_interval)
-    images, quads = list(images), [list(q) for q in quads]
-    if len(quads) != len(images):
-        raise ValueError(f"{len(images)} pages, {len(quads)} lists of quads: the lengths must agree")
-    sizes = [_page_size(img, f"images[{p}]") for p, img in enumerate(images)]
-    if frames is not None:
-        frames = [list(f) for f in frames]
-        if len(frames) != len(images) or any(len(f) != len(q) for f, q in zip(frames, quads)):
-            raise ValueError(f"frames must be {len(images)} lists, one frame per quad: the lengths must agree")
-    N = sum(len(q) for q in quads)
+    images, quads, frames, sizes, N = _quad_lists(images, quads, frames)
     _check_contexts(N, encoder_hidden_states, texts, glyph)
     guidance = _check_guidance(guidance, encoder_hidden_states, N)
     if frames is None:
@@ -334,6 +325,25 @@ def edit_quads(unet, vae, scheduler, images, quads, encoder_hidden_states, num_i
                            enc_noise, variance_noise, int(size), cache_interval, guidance)
     out = prepost.postprocess_quads(image_vae, images, quads, frames, perspective=perspective)
     return (out, image_vae, pre) if return_intermediate else out
+
+
+def _no_quad_blend(blend, who):
+    if blend is not None:
+        raise NotImplementedError(f"{who}: blend is not supported for quads (the ramp would have to be measured in strip coordinates); pass None")
+
+
+def _quad_lists(images, quads, frames):
+    """the list arguments of the quad edit functions, checked: P pages, P lists of quads, frames None or P lists of one frame per quad.
+    Returns (images, quads, frames, sizes, N)."""
+    images, quads = list(images), [list(q) for q in quads]
+    if len(quads) != len(images):
+        raise ValueError(f"{len(images)} pages, {len(quads)} lists of quads: the lengths must agree")
+    sizes = [_page_size(img, f"images[{p}]") for p, img in enumerate(images)]
+    if frames is not None:
+        frames = [list(f) for f in frames]
+        if len(frames) != len(images) or any(len(f) != len(q) for f, q in zip(frames, quads)):
+            raise ValueError(f"frames must be {len(images)} lists, one frame per quad: the lengths must agree")
+    return images, quads, frames, sizes, sum(len(q) for q in quads)
 
 
 def _check_blend(blend):
@@ -552,8 +562,8 @@ def edit_boxes_verified(unet, vae, scheduler, ocr, processor, instance_image, lo
     guidance: as for edit_boxes; a per-box uncond [N,S,D] is shared by the box's K candidates, like its glyph context.
     blend: as for edit_boxes, applied to the chosen candidates (choose -> [stats ->] paste on the device, still no score read on the host).
     The read-back scores the candidates as the hard paste would show them."""
-    return _edit_verified(False, unet, vae, scheduler, ocr, processor, [instance_image], [locations], encoder_hidden_states, labels,
-                          num_inference_steps, candidates, seeds, min_score, batch_size, ocr_batch_size, _one(origins), _one(crop_scales), rng,
+    return _edit_verified(_BoxRegions(False, [instance_image], [locations], _one(origins), _one(crop_scales), rng), unet, vae, scheduler, ocr,
+                          processor, encoder_hidden_states, labels, num_inference_steps, candidates, seeds, min_score, batch_size, ocr_batch_size,
                           generator, enc_noise, variance_noise, size, return_intermediate, cache_interval, texts, glyph, guidance, blend)
 
 
@@ -568,36 +578,116 @@ def edit_pages_verified(unet, vae, scheduler, ocr, processor, images, locations,
     read on the host.  Returns the list of P pages, or a VerifiedEdit whose `image` is that list with return_intermediate=True.
     candidates=1 with min_score=None returns edit_pages' pages, bit for bit.  texts / glyph, guidance: as for edit_boxes, page-major.
     blend: as for edit_boxes_verified."""
-    return _edit_verified(True, unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps,
-                          candidates, seeds, min_score, batch_size, ocr_batch_size, origins, crop_scales, rng, generator, enc_noise,
-                          variance_noise, size, return_intermediate, cache_interval, texts, glyph, guidance, blend)
+    return _edit_verified(_BoxRegions(True, images, locations, origins, crop_scales, rng), unet, vae, scheduler, ocr, processor,
+                          encoder_hidden_states, labels, num_inference_steps, candidates, seeds, min_score, batch_size, ocr_batch_size, generator,
+                          enc_noise, variance_noise, size, return_intermediate, cache_interval, texts, glyph, guidance, blend)
 
 
-def _edit_verified(paged, unet, vae, scheduler, ocr, processor, images, locations, encoder_hidden_states, labels, num_inference_steps, candidates,
-                   seeds, min_score, batch_size, ocr_batch_size, origins, crop_scales, rng, generator, enc_noise, variance_noise, size,
-                   return_intermediate, cache_interval=1, texts=None, glyph=None, guidance=None, blend=None):
-    """edit_boxes_verified (paged=False: one page, its lists wrapped into one-element lists) and edit_pages_verified.  Every argument is
-    checked on the host side first: nothing touches the GPU and no crop is planned - so nothing is drawn from rng - before all have passed."""
-    images, locations, origins, crop_scales, sizes, N = _page_lists(paged, images, locations, origins, crop_scales)
+class _BoxRegions:
+    """the regions of edit_boxes_verified (paged=False: one page, its lists wrapped into one-element lists) and edit_pages_verified, as
+    _edit_verified sees them: lists checked at construction, N, then the stages in the order it calls them"""
+
+    def __init__(self, paged, images, locations, origins, crop_scales, rng):
+        self.paged, self.rng = paged, rng
+        self.images, self.locations, self.origins, self.crop_scales, self.sizes, self.N = _page_lists(paged, images, locations, origins, crop_scales)
+
+    def check_blend(self, blend):
+        _check_blend(blend)
+
+    def check_readback(self):
+        if self.paged:
+            prepost.check_readback_boxes_pages([loc for l in self.locations for loc in l], [len(l) for l in self.locations], self.sizes)
+        else:
+            prepost.check_readback_boxes(self.locations[0], *self.sizes[0])
+
+    def plan(self, size):
+        self.where = _plan_pages(self.paged, self.images, self.locations, self.sizes, self.origins, self.crop_scales, self.rng)
+
+    def preprocess(self, size):
+        return (prepost.preprocess_pages if self.paged else prepost.preprocess_batch)(*self.where, size=size)
+
+    def readback(self, image_vae, ip):
+        return (prepost.readback_pixel_values_pages if self.paged else prepost.readback_pixel_values)(image_vae, *self.where, ip)
+
+    def select_paste(self, image_vae, scores, min_score, blend):
+        return (prepost.postprocess_select_pages if self.paged else prepost.postprocess_select_batch)(image_vae, scores, *self.where,
+                                                                                                       threshold=min_score, blend=blend)
+
+
+class _QuadRegions:
+    """the regions of edit_quads_verified: quads on several pages, frames given or planned (deterministic: nothing is drawn)"""
+
+    def __init__(self, images, quads, frames, perspective):
+        self.images, self.quads, self.frames, self.sizes, self.N = _quad_lists(images, quads, frames)
+        self.perspective = bool(perspective)
+
+    def check_blend(self, blend):
+        _no_quad_blend(blend, "edit_quads_verified")
+
+    def check_readback(self):
+        pass                                                           # (a prepared quad has a strip of at least one pixel)
+
+    def plan(self, size):
+        if self.frames is None:
+            self.frames = prepost.plan_quads(self.quads, self.sizes, self.perspective, size)
+
+    def preprocess(self, size):
+        return prepost.preprocess_quads(self.images, self.quads, self.frames, size=size, perspective=self.perspective)
+
+    def readback(self, image_vae, ip):
+        return prepost.readback_pixel_values_quads(image_vae, self.images, self.quads, self.frames, ip, perspective=self.perspective)
+
+    def select_paste(self, image_vae, scores, min_score, blend):
+        return prepost.postprocess_select_quads(image_vae, scores, self.images, self.quads, self.frames, threshold=min_score,
+                                                perspective=self.perspective)
+
+
+def _edit_verified(regions, unet, vae, scheduler, ocr, processor, encoder_hidden_states, labels, num_inference_steps, candidates, seeds, min_score,
+                   batch_size, ocr_batch_size, generator, enc_noise, variance_noise, size, return_intermediate, cache_interval=1, texts=None,
+                   glyph=None, guidance=None, blend=None):
+    """the verified edits of every region kind - `regions` is a _BoxRegions or a _QuadRegions, whose construction has checked the list
+    arguments.  Every argument is checked on the host side first: nothing touches the GPU and no crop is planned - so nothing is drawn from
+    rng - before all have passed."""
+    N = regions.N
     K, seeds = _check_verified_counts(N, candidates, seeds, min_score, batch_size, ocr_batch_size)
-    _check_blend(blend)
+    regions.check_blend(blend)
     cache_interval = _check_cache_interval(cache_interval)
     _check_verified_labels(ocr, N, encoder_hidden_states, labels, texts, glyph)
     guidance = _check_guidance(guidance, encoder_hidden_states, N)
-    if paged:
-        prepost.check_readback_boxes_pages([loc for l in locations for loc in l], [len(l) for l in locations], sizes)
-    else:
-        prepost.check_readback_boxes(locations[0], *sizes[0])
+    regions.check_readback()
     ip = _check_verified_processor(ocr, processor, size)
-    where = _plan_pages(paged, images, locations, sizes, origins, crop_scales, rng)
+    regions.plan(int(size))
     encoder_hidden_states = _contexts(encoder_hidden_states, texts, glyph)
-    pre = (prepost.preprocess_pages if paged else prepost.preprocess_batch)(*where, size=int(size))
-    image_vae = _candidate_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, seeds, int(batch_size),
-                                generator, enc_noise, variance_noise, int(size), cache_interval, guidance)
-    pixel_values = (prepost.readback_pixel_values_pages if paged else prepost.readback_pixel_values)(image_vae, *where, ip)
+    pre = regions.preprocess(int(size))
+    image_vae = _candidate_rows(unet, vae, scheduler, pre, regions.images[0].device, encoder_hidden_states, num_inference_steps, seeds,
+                                int(batch_size), generator, enc_noise, variance_noise, int(size), cache_interval, guidance)
+    pixel_values = regions.readback(image_vae, ip)
     scores = _score_candidates(ocr, pixel_values, labels, N, K, int(ocr_batch_size))
-    out, choice = (prepost.postprocess_select_pages if paged else prepost.postprocess_select_batch)(image_vae, scores, *where, threshold=min_score, blend=blend)
+    out, choice = regions.select_paste(image_vae, scores, min_score, blend)
     return VerifiedEdit(out, choice, scores, image_vae, pixel_values, pre) if return_intermediate else out
+
+
+@torch.no_grad()
+def edit_quads_verified(unet, vae, scheduler, ocr, processor, images, quads, encoder_hidden_states, labels, num_inference_steps, *, frames=None,
+                        candidates=4, seeds=None, min_score=None, batch_size=4, ocr_batch_size=32, generator=None, enc_noise=None,
+                        variance_noise=None, size=512, return_intermediate=False, cache_interval=1, texts=None, glyph=None, guidance=None,
+                        perspective=False, blend=None):
+    """edit_quads with edit_pages_verified's read-back - for skewed lines, scene text and phone photos, where a single sample most often
+    reads wrong: K = `candidates` edits per quad, each read by the OCR model as its upright strip, the best-reading one pasted through the
+    quad's frame.  images / quads / frames / perspective: as for edit_quads; everything per quad (encoder_hidden_states [N,L,D], labels
+    [N,T], enc_noise [N,4,h,w]) page-major; candidates / seeds / min_score / batch_size / ocr_batch_size and the chunking of the N*K rows:
+    as for edit_boxes_verified.
+
+    One preprocess_quads launch, the N*K rows through edit_boxes_verified's chunk loop, prepost.readback_pixel_values_quads in one launch -
+    row (b, k) is what the processor makes of rectify_quads of the page with candidate k of quad b ALONE pasted on it -, ocr.score, and
+    prepost.postprocess_select_quads: no score is read on the host.  A quad whose best candidate scores below min_score keeps the original
+    pixels and is transparent: an earlier chosen quad under it still shows.
+
+    Returns the list of P pages, or a VerifiedEdit whose `image` is that list with return_intermediate=True.  candidates=1 with
+    min_score=None returns edit_quads' pages, bit for bit.  blend: must be None, as for edit_quads."""
+    return _edit_verified(_QuadRegions(images, quads, frames, perspective), unet, vae, scheduler, ocr, processor, encoder_hidden_states, labels,
+                          num_inference_steps, candidates, seeds, min_score, batch_size, ocr_batch_size, generator, enc_noise, variance_noise, size,
+                          return_intermediate, cache_interval, texts, glyph, guidance, blend)
 
 
 def _score_candidates(ocr, pixel_values, labels, N, K, ocr_bs):

@@ -450,9 +450,10 @@ def check_readback_boxes_pages(locations, counts, sizes):
         lo += n
 
 
-def _readback_tables(locations, ip, cap):
+def _readback_tables(locations, ip, cap, what="box"):
     """per box the two resample tables of (box width -> S_w) and (box height -> S_h), deduplicated: (passes [B][4] int32, the concatenated
-    int32 tables, max_taps).  A pass with equal sizes is skipped (offset -1), as Pillow does."""
+    int32 tables, max_taps).  A pass with equal sizes is skipped (offset -1), as Pillow does.  what: how the error names a region (the
+    quad read-back passes the pseudo-boxes (0, 0, rw, rh) of its strips)."""
     from . import processing
     S_h, S_w = ip.size["height"], ip.size["width"]
     passes = np.zeros((len(locations), 4), dtype=np.int32)
@@ -465,7 +466,7 @@ def _readback_tables(locations, ip, cap):
                 continue
             taps = processing._taps(n_in, n_out, ip.resample)
             if taps > cap:
-                raise ValueError(f"box {b}: resizing {n_in} -> {n_out} needs {taps} taps per output pixel, more than the kernel's cap of {cap} "
+                raise ValueError(f"{what} {b}: resizing {n_in} -> {n_out} needs {taps} taps per output pixel, more than the kernel's cap of {cap} "
                                  "(downscale ratio at most 31 for bilinear, 15 for bicubic)")
             k = (n_in, n_out, ip.resample)
             if k not in table_off:
@@ -790,14 +791,28 @@ def _upload_quads(qx, S, out=None, union=None):
     the current stream.  S = 0 (rectify_quads): the strips alone, which depend neither on the frames nor on S.  Returns a _QuadTables:
     the host tables (persp None for the similarity frame), the pinned storage, the device buffer, the byte offsets of the page table and
     of the projective table in it."""
+    return _upload_quads_extra(qx, S, out, union, None)[0]
+
+
+def _upload_quads_extra(qx, S, out, union, extra):
+    """_upload_quads with more tables behind the quad tables, in the same pinned buffer and the same copy, in the spirit of `extra` of
+    _upload.  extra: None, or a function of the PREPARED host quad table that returns numpy arrays - tables that depend on derived fields,
+    as the read-back's resample tables depend on the strips' sizes.  The arrays size the buffer, so with `extra` the tables are prepared
+    in plain host memory first and copied into the pinned buffer; without it they are filled in the pinned buffer directly.  Returns
+    (the _QuadTables, the byte offsets of the extra arrays)."""
     B, P = len(qx.quads), len(qx.images)
     n_quads, n_pages = B * ctypes.sizeof(_cabi.EditQuad), P * ctypes.sizeof(_cabi.EditPage)
     off, xoff = n_quads, n_quads + n_pages
-    stage = torch.empty(xoff + (B * ctypes.sizeof(_cabi.QuadPersp) if qx.persp is not None else 0), dtype=torch.uint8, pin_memory=True)
-    st = stage.numpy()
-    st[:] = 0
-    host = (_cabi.EditQuad * B).from_buffer(st[:off])
-    pages = (_cabi.EditPage * P).from_buffer(st[off:xoff])
+    n_tables = xoff + (B * ctypes.sizeof(_cabi.QuadPersp) if qx.persp is not None else 0)
+
+    def views(st):
+        return ((_cabi.EditQuad * B).from_buffer(st[:off]), (_cabi.EditPage * P).from_buffer(st[off:xoff]),
+                (_cabi.QuadPersp * B).from_buffer(st[xoff:n_tables]) if qx.persp is not None else None)
+
+    stage = torch.empty(n_tables, dtype=torch.uint8, pin_memory=True) if extra is None else None
+    tab = stage.numpy() if extra is None else np.empty(n_tables, dtype=np.uint8)
+    tab[:] = 0
+    host, pages, persp = views(tab)
     lo = 0
     for p, (pg, img, n) in enumerate(zip(pages, qx.images, qx.counts)):
         pg.original = img.data_ptr()
@@ -812,16 +827,26 @@ def _upload_quads(qx, S, out=None, union=None):
         lo += n
     # (the placeholder frames of the strips and of the projective entries are prepared at any valid S)
     _cabi.check(_cabi.lib().dmx_edit_quads_prepare(pages, P, host, B, max(S, 8) if qx.persp is not None or S == 0 else S), "edit_quads_prepare")
-    persp = None
-    if qx.persp is not None:
-        persp = (_cabi.QuadPersp * B).from_buffer(st[xoff:])
+    if persp is not None:
         for e, f in zip(persp, qx.persp):
             e.ci2, e.cj2, e.crop_scale = f
         _cabi.check(_cabi.lib().dmx_edit_quads_persp_prepare(pages, P, host, persp, B, S), "edit_quads_persp_prepare")
+    eoffs = []
+    if extra is not None:
+        arrays, total = [np.ascontiguousarray(a) for a in extra(host)], n_tables
+        for a in arrays:
+            total = (total + 15) // 16 * 16                            # (every array 16-byte aligned, whatever lies before it)
+            eoffs.append(total); total += a.nbytes
+        stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        st = stage.numpy()
+        st[:n_tables] = tab
+        for a, o in zip(arrays, eoffs):
+            st[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+        host, pages, persp = views(st)                                 # the entries read the host tables where the copy reads them
     with torch.cuda.device(qx.dev):
         dbuf = torch.empty(stage.numel(), dtype=torch.uint8, device=qx.dev)
         dbuf.copy_(stage, non_blocking=True)                          # the one H2D copy
-    return _QuadTables(host, pages, persp, stage, dbuf, off, xoff)
+    return _QuadTables(host, pages, persp, stage, dbuf, off, xoff), eoffs
 
 
 def _call_quads(name, t, head, *tail):
@@ -895,3 +920,84 @@ def rectify_quads(images, quads, perspective=False):
         buf = torch.empty(total, dtype=torch.uint8, device=qx.dev)
         _call_quads("rectify_quads", t, (), _cabi.ptr(buf), total)
     return [buf[int(q.rect_off):int(q.rect_off) + int(q.rw) * int(q.rh) * 3].view(int(q.rh), int(q.rw), 3) for q in t.host]
+
+
+def _plan_persp(images, quads, frames, perspective, size):
+    """the projective frames where a perspective call left them open, as the other quad functions plan them"""
+    if perspective and frames is None:
+        return plan_quads([list(q) for q in quads], [(int(i.shape[0]), int(i.shape[1])) for i in images], True, int(size))
+    return frames
+
+
+def readback_pixel_values_quads(image_vae, images, quads, frames, processor, perspective=False, return_resized=False, out=None, out_resized=None):
+    """readback_pixel_values_pages for quadrilateral regions, in ONE launch: image_vae fp32 CUDA [N,K,3,S,S] (or [N*K,3,S,S]) decoder
+    outputs, page-major -> pixel_values fp32 [N*K,3,S_h,S_w].  Row (b, k) is bit for bit `processor(rectify_quads(postprocess_quads(
+    image_vae[b, k], quad b ALONE)))` - candidate k pasted over the original page through quad b's frame, the quad taken as an upright strip,
+    the strip resized and normalised - without the pasted page, the strip or the processor call; other quads of the page play no part.
+    images / quads / frames / perspective: as for postprocess_quads (perspective=True with frames=None plans them).  processor: a
+    ViTImageProcessor or TrOCRProcessor with do_resize.  The quads, the pages, the projective frames, the passes and the processor's
+    tables travel in one pinned staging buffer, one H2D copy.  return_resized / out / out_resized as for readback_pixel_values."""
+    ip = _resizing_processor(processor, "readback_pixel_values_quads")
+    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
+        raise TypeError("image_vae: expected a CUDA tensor")
+    frames = _plan_persp(images, quads, frames, perspective, image_vae.shape[-1])
+    qx = _check_quads(images, quads, frames, perspective)
+    B = len(qx.quads)
+    if image_vae.dim() == 4:                                           # [N*K,3,S,S]: the rows of _candidate_rows before their reshape
+        if image_vae.shape[0] % B:
+            raise ValueError(f"image_vae must be [{B},K,3,S,S] or [{B}*K,3,S,S]: {image_vae.shape[0]} rows are no multiple of {B} quads")
+        image_vae = image_vae.reshape(B, image_vae.shape[0] // B, *image_vae.shape[1:])
+    S, K = _check_vae(image_vae, B, True)
+    S_h, S_w = ip.size["height"], ip.size["width"]
+    for name, t, dt in (("out", out, torch.float32), ("out_resized", out_resized, torch.uint8)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.device == qx.dev and t.dtype == dt and t.is_contiguous()
+                                  and tuple(t.shape) == (B * K, 3, S_h, S_w)):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor [{B * K},3,{S_h},{S_w}] on {qx.dev}")
+    lib = _cabi.lib()
+    cap, made = int(lib.dmx_glyph_max_taps()), {}
+
+    def tables_of(host):                                               # the strips' sizes are derived fields: (0, 0, rw, rh) stands for a box
+        made["passes"], made["tables"], made["max_taps"] = _readback_tables([(0, 0, int(q.rw), int(q.rh)) for q in host], ip, cap, "quad")
+        return made["passes"], ip._norm, made["tables"]
+
+    v = image_vae.to(torch.float32).contiguous()
+    t, (off_pass, off_norm, off_tab) = _upload_quads_extra(qx, S, None, None, tables_of)
+    host_passes = (_cabi.ReadbackPass * B).from_buffer(t.stage.numpy()[off_pass:off_pass + made["passes"].nbytes])
+    base = t.dbuf.data_ptr()
+    with torch.cuda.device(qx.dev):
+        if out is None:
+            out = torch.empty(B * K, 3, S_h, S_w, dtype=torch.float32, device=qx.dev)
+        res = out_resized
+        if res is None and return_resized:
+            res = torch.empty(B * K, 3, S_h, S_w, dtype=torch.uint8, device=qx.dev)
+        _call_quads("readback_pixel_values_quads", t, (_cabi.ptr(v), S), K, base + off_tab, int(made["tables"].size), base + off_norm, host_passes,
+                    base + off_pass, made["max_taps"], S_h, S_w, _cabi.ptr(out), _cabi.ptr(res))
+    return (out, res) if (return_resized or out_resized is not None) else out
+
+
+def postprocess_select_quads(image_vae, scores, images, quads, frames, threshold=None, return_mask=False, out=None, perspective=False):
+    """postprocess_select_pages for quadrilateral regions: choose and paste in ONE launch, without reading the scores on the host.
+    image_vae fp32 CUDA [N,K,3,S,S], scores fp32 CUDA [N,K], both page-major; the other arguments as for postprocess_quads.  Returns
+    (pages, choice): choice int32 [N] on the device by the rule of postprocess_select_batch, and the list of P pages postprocess_quads
+    gives for the chosen rows.  A quad whose best score is below `threshold` (choice -1) is TRANSPARENT: it pastes nothing, and an earlier
+    chosen quad under it still shows.  With return_mask=True also the list of P union masks, 1 inside ANY quad, skipped ones included."""
+    if not (isinstance(scores, torch.Tensor) and scores.is_cuda):
+        raise TypeError("scores: expected a CUDA tensor")
+    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
+        raise TypeError("image_vae: expected a CUDA tensor")
+    frames = _plan_persp(images, quads, frames, perspective, image_vae.shape[-1])
+    qx = _check_quads(images, quads, frames, perspective)
+    B = len(qx.quads)
+    S, K = _check_vae(image_vae, B, True)
+    thr = _check_scores(scores, B, K, threshold)
+    if out is not None:
+        out = _check_page_outputs(out, qx.images)
+    with torch.cuda.device(qx.dev):
+        out = [torch.empty_like(img) for img in qx.images] if out is None else out
+        union = [torch.empty(img.shape[0], img.shape[1], dtype=torch.uint8, device=qx.dev) for img in qx.images] if return_mask else None
+        choice = torch.empty(B, dtype=torch.int32, device=qx.dev)
+    v, sc = image_vae.to(torch.float32).contiguous(), scores.to(torch.float32).contiguous()
+    t = _upload_quads(qx, S, out, union)
+    with torch.cuda.device(qx.dev):
+        _call_quads("postprocess_paste_select_quads", t, (_cabi.ptr(v), S, _cabi.ptr(sc), thr, _cabi.ptr(choice)), K)
+    return (out, choice, union) if return_mask else (out, choice)

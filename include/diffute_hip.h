@@ -1095,6 +1095,49 @@ int dmx_rectify_quads_persp(const dmx_edit_page* pages_host, const dmx_edit_page
                             const dmx_edit_quad* quads_device, const dmx_quad_persp* persp_host, const dmx_quad_persp* persp_device, int B,
                             unsigned char* out, long long out_bytes, dmx_stream_t stream);
 
+/* Verified edits for quads (prepost_quad.hip): the read-back and the select-paste of the box entries above, through a quad's frame; each
+ * is written once and instantiated for the similarity and the projective frame (the _persp entries take the projective table as the
+ * quad entries of that name do).  Two launches, no page copy, no strip in memory, no host sync.
+ *   readback_pixel_values_quads[_persp]: image_vae fp32 [B][K][3][S][S]; out_pixel_values fp32 [B*K][3][S_h][S_w] (and out_resized uint8,
+ *           optional).  Row (b, k) is, bit for bit, the end of this chain: postprocess_paste_quads[_persp] pastes image_vae[b][k] ALONE over
+ *           the original page - a one-quad table that holds quad b and its frame, so other quads of the page play no part -,
+ *           rectify_quads[_persp] takes quad b's strip from that page, glyph_resize_normalize resamples the strip.  Per pixel: source byte
+ *           (i, j, c) of the rw x rh strip is the rectify's single-rounding bilinear of four page taps at the frame's strip coordinates of
+ *           (2i + 1 - rw, 2j + 1 - rh); a tap at page pixel (X, Y), taken after the clamp to the page, is the paste's byte of the
+ *           candidate's row at the crop coordinates (U16, V16) of (X, Y) when (X, Y) is inside quad b (edges included), the frame's paste
+ *           map is defined there and -2^15 <= U16, V16 < (S << 16) - 2^15; otherwise it is the original page byte.  tables / table_ints /
+ *           norm / passes / max_taps as for readback_pixel_values_pages, the source size of item b being (rw, rh) of the prepared quad.
+ *   postprocess_paste_select_quads[_persp]: scores fp32 [B][K] ON THE DEVICE, choice int32 [B] (device, out) by the rule of
+ *           postprocess_paste_select.  The paste is postprocess_paste_quads[_persp] with item b reading row b * K + choice[b]; an item with
+ *           choice[b] < 0 is TRANSPARENT: the last-to-first scan of the page's quads passes over it, so an earlier chosen quad under it
+ *           still shows, and where no chosen quad covers the pixel the original byte stays.  The union mask is 1 where any quad covers
+ *           the pixel, skipped ones included.  With K = 1 and threshold = -INFINITY pages and union masks equal
+ *           postprocess_paste_quads[_persp] bit for bit.
+ * Refused (DMX_ERR_ARG, nothing launched, a bad page or item named by index): what the quad entries refuse of their tables (the _persp
+ * entries re-check the prepared projective table), K outside 1 .. DMX_SELECT_MAX_CANDIDATES, a NaN threshold, null arguments, and for the
+ * read-back what readback_pixel_values_pages refuses of its scalars and pass tables.  The kernels trust the pages' addresses and sizes
+ * and clamp everything else they read from the device tables (page index, rw / rh to at least 1, pass spans, taps): a stale table reads
+ * wrong pixels, never outside a buffer; output addresses depend on the grid alone. */
+int dmx_readback_pixel_values_quads(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                    const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device, int B, int K, const int* tables,
+                                    long long table_ints, const float* norm, const dmx_readback_pass* passes_host,
+                                    const dmx_readback_pass* passes_device, int max_taps, int S_h, int S_w, float* out_pixel_values,
+                                    unsigned char* out_resized, dmx_stream_t stream);
+int dmx_readback_pixel_values_quads_persp(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                          const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device, const dmx_quad_persp* persp_host,
+                                          const dmx_quad_persp* persp_device, int B, int K, const int* tables, long long table_ints,
+                                          const float* norm, const dmx_readback_pass* passes_host, const dmx_readback_pass* passes_device,
+                                          int max_taps, int S_h, int S_w, float* out_pixel_values, unsigned char* out_resized,
+                                          dmx_stream_t stream);
+int dmx_postprocess_paste_select_quads(const float* image_vae, int S, const float* scores, float threshold, int* choice,
+                                       const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                       const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device, int B, int K, dmx_stream_t stream);
+int dmx_postprocess_paste_select_quads_persp(const float* image_vae, int S, const float* scores, float threshold, int* choice,
+                                             const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                             const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device,
+                                             const dmx_quad_persp* persp_host, const dmx_quad_persp* persp_device, int B, int K,
+                                             dmx_stream_t stream);
+
 /* Comparing two versions of a set of pages (metrics.hip): what the scene-text-editing literature reports on the edited box - MSE,
  * PSNR, SSIM - and what changed OUTSIDE all boxes.  P pairs of pages a / b, uint8 [H][W][3] contiguous, both of a pair H x W; B boxes
  * (page, x1, y1, x2, y2), each the slice [y1:y2, x1:x2] of its page: exclusive upper corner, non-empty, inside the page (the read-back's
