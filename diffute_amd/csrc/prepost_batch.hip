@@ -1,12 +1,17 @@
-// Several text boxes of ONE image per launch: the batched ends of the editing path (pipeline.edit_boxes).  prepost.hip turns one box
-// into the [1,3,S,S] network inputs and pastes one decoder output back, with the geometry as kernel arguments and a full-size [H][W]
-// mask rasterised by a launch of its own; here B boxes share the uint8 image in HBM, item b's geometry comes from a device table of
-// dmx_edit_item, and the mask is the predicate "inside item b's inclusive box" (PIL's rectangle rule, what dmx_mask_rasterize_kernel
+// Several text boxes per launch: the batched ends of the editing path (pipeline.edit_boxes, pipeline.edit_pages).  prepost.hip turns
+// one box into the [1,3,S,S] network inputs and pastes one decoder output back, with the geometry as kernel arguments and a full-size
+// [H][W] mask rasterised by a launch of its own; here B boxes share the uint8 pages in HBM, item b's geometry comes from a device table
+// of dmx_edit_item, and the mask is the predicate "inside item b's inclusive box" (PIL's rectangle rule, what dmx_mask_rasterize_kernel
 // writes), so there is neither a mask buffer nor a rasterise launch.  The per-pixel arithmetic is prepost_resize.h, the same
 // functions the single-box kernels call: row b is bit for bit what the single-box entry gives for item b.
 // Pure HBM-bound byte work: one thread per destination pixel, coalesced plain vector stores.
-// The *_pages kernels further down do the same for boxes on SEVERAL pages (pipeline.edit_pages): a second device table, of dmx_edit_page,
-// says where each page lives and which items are its own, and the functions below are called on one-page views of it.
+// Three kernel bodies - crop, paste, select-paste -, each written ONCE over a page source (prepost_paste.h) and instantiated twice:
+//   OnePage     the boxes of ONE image, given by kernel arguments: the dmx_*_batch entries and dmx_postprocess_paste_select;
+//   PageTable   boxes on SEVERAL pages: a second device table, of dmx_edit_page, says where each page lives and which contiguous range
+//               of the item table belongs to it: the dmx_*_pages entries.  A page is bit for bit what the one-page kernel gives for its
+//               items alone.  Whatever comes from the device tables is clamped (page_of, item_geom: prepost_resize.h; page_block):
+//               a stale table reads wrong pixels, never outside a page (the pages' own addresses and sizes are trusted, as the
+//               one-page kernels trust their arguments).
 #include "common.h"
 #include "kernels.h"
 #include "prepost_paste.h"
@@ -14,74 +19,56 @@
 
 namespace {
 using namespace dmx_resize;
-using namespace dmx_paste;      // PostBatchArgs, select_choices, PostPagesArgs, PageTile, page_tile: shared with prepost_blend.hip
+using namespace dmx_paste;      // PasteArgs, OnePage, PageTable, PageBlock, select_choices: shared with prepost_blend.hip
 
-struct PreBatchArgs {
-  const unsigned char* img; int H, W;                                  // HWC uint8 image shared by all items
+struct PreArgs {
   const dmx_edit_item* items; int S;
   float* out_img; float* out_masked; unsigned char* out_mask; float* out_mask_lat;   // [B][3][S][S], [B][3][S][S], [B][S][S], [B][S/8][S/8]
 };
 
-// Destination pixel (dx, dy) of row b: item b of p.items cropped from p.img.
-__device__ __forceinline__ void pre_item(const PreBatchArgs& p, int b, int dx, int dy) {
-  const dmx_edit_item it = p.items[b];
-  const Geom g = item_geom(it, p.H, p.W, p.S, true);
+// Destination pixel (dx, dy) of row b: item `it` cropped from its page pg (HWC uint8).
+__device__ __forceinline__ void pre_item(const PreArgs& p, const dmx_edit_page& pg, const dmx_edit_item& it, int b, int dx, int dy) {
+  const Geom g = item_geom(it, pg.H, pg.W, p.S, true);
   int vi[3], vm[3], vk;
   // generate_mask (app.ipynb:370-378) as a predicate on image coordinates: item b's box alone, both corners included
   auto mk = [&](int y, int x) -> int {
     const int X = g.xs + x, Y = g.ys + y;
     return (X >= it.x1 && X <= it.x2 && Y >= it.y1 && Y <= it.y2) ? 1 : 0;
   };
-  pre_pixel(p.img, p.W, g, mk, dx, dy, vi, vm, vk);
+  pre_pixel((const unsigned char*)pg.original, pg.W, g, mk, dx, dy, vi, vm, vk);
   const size_t plane = (size_t)p.S * p.S, lat = (size_t)(p.S >> 3) * (p.S >> 3);
   pre_store(vi, vm, vk, p.S, dx, dy, p.out_img + (size_t)b * 3 * plane, p.out_masked + (size_t)b * 3 * plane, p.out_mask + (size_t)b * plane,
             p.out_mask_lat ? p.out_mask_lat + (size_t)b * lat : nullptr);
 }
 
-__global__ __launch_bounds__(256) void dmx_preprocess_batch_kernel(const PreBatchArgs p) {
+// grid (ceil(S / 256), S, B): the grid runs over items; the item's page supplies the image pointer, H and W
+template <class Pages>
+__global__ __launch_bounds__(256) void dmx_preprocess_boxes_kernel(const PreArgs p, const Pages pages) {
   const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y, b = blockIdx.z;
   if (dx >= p.S) return;
-  pre_item(p, b, dx, dy);
-}
-
-// ---- B boxes on P pages per launch (pipeline.edit_pages): a device table of dmx_edit_page says where each page lives and which
-// contiguous range of the item table belongs to it.  Every kernel below hands the functions above a one-page VIEW of its arguments -
-// the page's pointers and size, its slice of the item table - so a row / a page is bit for bit what the one-page kernel gives.
-// Whatever comes from the device tables is clamped (page_of, item_geom: prepost_resize.h): a stale table reads wrong pixels, never
-// outside a page (the pages' own addresses and sizes are trusted, as the one-page kernels trust their arguments).
-
-struct PrePagesArgs {
-  const dmx_edit_page* pages; int P;
-  const dmx_edit_item* items; int S;
-  float* out_img; float* out_masked; unsigned char* out_mask; float* out_mask_lat;
-};
-
-// the grid runs over items, as above; the item's page supplies the image pointer, H and W
-__global__ __launch_bounds__(256) void dmx_preprocess_pages_kernel(const PrePagesArgs p) {
-  const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y, b = blockIdx.z;
-  if (dx >= p.S) return;
-  const dmx_edit_page pg = p.pages[page_of(p.items[b], p.P)];
-  const PreBatchArgs v{(const unsigned char*)pg.original, pg.H, pg.W, p.items, p.S, p.out_img, p.out_masked, p.out_mask, p.out_mask_lat};
-  pre_item(v, b, dx, dy);
+  const dmx_edit_item it = p.items[b];
+  pre_item(p, pages.of(it), it, b, dx, dy);
 }
 
 // B chained single pastes in index order leave, at every pixel, the value of the LAST item whose (half-open box) AND (resized crop
 // extent) covers it, computed from that item's decoder output alone, or the original where no item does: scan from the last item down
-// and stop at the first hit.  The integer half of the table is staged in LDS once per block (every pixel of the row scans all of it).
-__device__ __forceinline__ void stage_items(const PostBatchArgs& p, int4* s_box, int4* s_crop) {
-  if ((int)threadIdx.x < p.B) {
-    const dmx_edit_item& it = p.items[threadIdx.x];
+// and stop at the first hit.  The integer half of the page's items (t: its page and its slice of the table) is staged in LDS once per
+// block (every pixel of the row scans all of it).
+__device__ __forceinline__ void stage_items(const PasteArgs& p, const PageBlock& t, int4* s_box, int4* s_crop) {
+  if ((int)threadIdx.x < t.n) {
+    const dmx_edit_item& it = p.items[t.lo + threadIdx.x];
     s_box[threadIdx.x] = make_int4(it.x1, it.y1, it.x2, it.y2);
-    const int xs = min(max(it.x_s, 0), p.W - 1), ys = min(max(it.y_s, 0), p.H - 1);       // item_geom's clamps
-    s_crop[threadIdx.x] = make_int4(xs, ys, min(max(it.cw, 1), p.W - xs), min(max(it.ch, 1), p.H - ys));
+    const int xs = min(max(it.x_s, 0), t.pg.W - 1), ys = min(max(it.y_s, 0), t.pg.H - 1);       // item_geom's clamps
+    s_crop[threadIdx.x] = make_int4(xs, ys, min(max(it.cw, 1), t.pg.W - xs), min(max(it.ch, 1), t.pg.H - ys));
   }
 }
-// One pixel of the page.  row(b) -> which [3][S][S] image of p.vae item b pastes, < 0 = the item is skipped (it still counts for the
-// union mask: the mask says where the boxes are, not what was pasted).
+// Pixel (t.x, t.y) of the page.  row(b) -> which [3][S][S] image of p.vae the page's item b pastes, < 0 = the item is skipped (it still
+// counts for the union mask: the mask says where the boxes are, not what was pasted).
 template <class Row>
-__device__ __forceinline__ void paste_pixel(const PostBatchArgs& p, const int4* s_box, const int4* s_crop, Row row, int x, int y) {
+__device__ __forceinline__ void paste_pixel(const PasteArgs& p, const PageBlock& t, const int4* s_box, const int4* s_crop, Row row) {
+  const int x = t.x, y = t.y, W = t.pg.W;
   int hit = -1, any = 0;
-  for (int b = p.B - 1; b >= 0; --b) {
+  for (int b = t.n - 1; b >= 0; --b) {
     const int4 bx = s_box[b];
     any |= (x >= bx.x && x <= bx.z && y >= bx.y && y <= bx.w) ? 1 : 0;                    // union mask: PIL's inclusive rectangle
     if (hit < 0 && row(b) >= 0 && x >= bx.x && x < bx.z && y >= bx.y && y < bx.w) {        // the paste: inf_res[y1:y2, x1:x2]
@@ -91,70 +78,77 @@ __device__ __forceinline__ void paste_pixel(const PostBatchArgs& p, const int4* 
     }
     if (hit >= 0) break;                                                     // (a hit lies inside that item's inclusive box: `any` is set)
   }
-  const size_t o = ((size_t)y * p.W + x) * 3;
-  if (p.umask) p.umask[(size_t)y * p.W + x] = (unsigned char)any;
-  if (hit < 0) { p.out[o] = p.ori[o]; p.out[o + 1] = p.ori[o + 1]; p.out[o + 2] = p.ori[o + 2]; return; }
-  const Geom g = item_geom(p.items[hit], p.H, p.W, p.S, false);
+  const unsigned char* ori = (const unsigned char*)t.pg.original;
+  unsigned char *out = (unsigned char*)t.pg.out, *umask = (unsigned char*)t.pg.union_mask;
+  const size_t o = ((size_t)y * W + x) * 3;
+  if (umask) umask[(size_t)y * W + x] = (unsigned char)any;
+  if (hit < 0) { out[o] = ori[o]; out[o + 1] = ori[o + 1]; out[o + 2] = ori[o + 2]; return; }
+  const Geom g = item_geom(p.items[t.lo + hit], t.pg.H, W, p.S, false);
   const float* vae = p.vae + (size_t)row(hit) * 3 * p.S * p.S;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) p.out[o + c] = post_pixel(vae, p.S, g, c, x - g.xs, y - g.ys);
+  for (int c = 0; c < 3; ++c) out[o + c] = post_pixel(vae, p.S, g, c, x - g.xs, y - g.ys);
 }
 
-__global__ __launch_bounds__(256) void dmx_postprocess_batch_kernel(const PostBatchArgs p) {
+// One 256-pixel tile of one page row per block: grid (ceil(W / 256), H) for one page; for a page table the blocks enumerate (page, row,
+// column tile) along grid.x (dmx_paste::page_block), and a pixel scans only its own page's items, last to first.
+template <class Pages>
+__global__ __launch_bounds__(256) void dmx_postprocess_boxes_kernel(const PasteArgs p, const Pages pages) {
   __shared__ int4 s_box[DMX_EDIT_MAX_ITEMS], s_crop[DMX_EDIT_MAX_ITEMS];
-  stage_items(p, s_box, s_crop);
+  PageBlock t;
+  if (!pages.tile(p.B, t)) return;                                             // (uniform per block: a stale table)
+  stage_items(p, t, s_box, s_crop);
   __syncthreads();
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= p.W) return;
-  paste_pixel(p, s_box, s_crop, [](int b) -> int { return b; }, x, y);
+  if (t.x >= t.pg.W) return;
+  const int lo = t.lo;
+  paste_pixel(p, t, s_box, s_crop, [lo](int b) -> int { return lo + b; });
 }
 
 // Best of K candidates per item, chosen and pasted in ONE launch: p.vae is [B][K][3][S][S], scores [B][K] lives on the device, so the
-// host never waits for it.  Every block stages the score table in LDS and derives the same choices from it:
+// host never waits for it.  choice is [B] over all items; every live block stages the score table in LDS and derives all of it (one
+// rule, one table: select_choices, which contains barriers - a block enters it with all its threads or not at all):
 //   choice[b] = arg-max over k of scores[b][k], the lowest k on a tie; a NaN never wins; 0 when every score is NaN;
 //   -1 (the item is skipped, its box keeps the original pixels) when the best score is below `threshold`.
-// Block (0, 0) alone writes `choice`, with plain vector stores.  The paste is paste_pixel, the rule of the kernel above.
-__global__ __launch_bounds__(256) void dmx_postprocess_select_kernel(const PostBatchArgs p, const float* scores, int K, float threshold, int* choice) {
+// The source's one `chooser` block stores `choice`, with plain vector stores - also where a stale page table leaves it no pixel; any
+// other block without a pixel returns at once.  The paste is paste_pixel, the rule of the kernel above.
+template <class Pages>
+__global__ __launch_bounds__(256) void dmx_postprocess_select_boxes_kernel(const PasteArgs p, const Pages pages, const float* scores, int K,
+                                                                           float threshold, int* choice) {
   __shared__ int4 s_box[DMX_EDIT_MAX_ITEMS], s_crop[DMX_EDIT_MAX_ITEMS];
   __shared__ float s_score[DMX_EDIT_MAX_ITEMS * DMX_SELECT_MAX_CANDIDATES];
   __shared__ int s_choice[DMX_EDIT_MAX_ITEMS];
-  stage_items(p, s_box, s_crop);
-  select_choices(scores, p.B, K, threshold, s_score, s_choice, choice, blockIdx.x == 0 && blockIdx.y == 0);
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= p.W) return;
-  paste_pixel(p, s_box, s_crop, [&](int b) -> int { const int k = s_choice[b]; return k < 0 ? -1 : b * K + k; }, x, y);
+  PageBlock t;
+  const bool live = pages.tile(p.B, t), chooser = pages.chooser();
+  if (!live && !chooser) return;
+  if (live) stage_items(p, t, s_box, s_crop);
+  select_choices(scores, p.B, K, threshold, s_score, s_choice, choice, chooser);
+  if (!live || t.x >= t.pg.W) return;
+  const int lo = t.lo;
+  paste_pixel(p, t, s_box, s_crop, [&](int b) -> int { const int k = s_choice[lo + b]; return k < 0 ? -1 : (lo + b) * K + k; });
 }
 
-// The paste over P pages in ONE launch.  The rows of all pages do not fit in grid.y, so blocks enumerate (page, row, column tile) along
-// grid.x: page p owns the blocks [block_lo, block_lo + H * ceil(W / 256)).  A block finds its page by a uniform scan of the (at most
-// 64) block_lo values, then pastes one 256-pixel tile of one row through paste_pixel with the page's view: a pixel scans only its own
-// page's items, last to first.
-// (PostPagesArgs, PageTile, page_tile: prepost_paste.h)
-__global__ __launch_bounds__(256) void dmx_postprocess_pages_kernel(const PostPagesArgs p) {
-  __shared__ int4 s_box[DMX_EDIT_MAX_ITEMS], s_crop[DMX_EDIT_MAX_ITEMS];
-  PageTile t;
-  if (!page_tile(p, t)) return;
-  stage_items(t.view, s_box, s_crop);
-  __syncthreads();
-  if (t.x >= t.view.W) return;
-  const int lo = t.lo;
-  paste_pixel(t.view, s_box, s_crop, [lo](int b) -> int { return lo + b; }, t.x, t.y);
+// The launches, one per stage; the tables are checked.  `kernel` names the launch in the last-error string.
+template <class Pages>
+int launch_pre(const char* kernel, const Pages& pages, const dmx_edit_item* items_device, int B, int S, float* out_image, float* out_masked_image,
+               unsigned char* out_mask, float* out_mask_latent, dmx_stream_t stream) {
+  PreArgs p{items_device, S, out_image, out_masked_image, out_mask, out_mask_latent};
+  hipLaunchKernelGGL(dmx_preprocess_boxes_kernel<Pages>, dim3(cdiv(S, 256), S, B), dim3(256), 0, (hipStream_t)stream, p, pages);
+  return dmx_check_launch(kernel);
 }
 
-// choice is [B] over all items and every block derives all of it (one rule, one table); block 0 alone stores it
-__global__ __launch_bounds__(256) void dmx_postprocess_select_pages_kernel(const PostPagesArgs p, const float* scores, int K, float threshold,
-                                                                           int* choice) {
-  __shared__ int4 s_box[DMX_EDIT_MAX_ITEMS], s_crop[DMX_EDIT_MAX_ITEMS];
-  __shared__ float s_score[DMX_EDIT_MAX_ITEMS * DMX_SELECT_MAX_CANDIDATES];
-  __shared__ int s_choice[DMX_EDIT_MAX_ITEMS];
-  PageTile t;
-  const bool live = page_tile(p, t);
-  if (!live && blockIdx.x != 0) return;
-  if (live) stage_items(t.view, s_box, s_crop);
-  select_choices(scores, p.B, K, threshold, s_score, s_choice, choice, blockIdx.x == 0);
-  if (!live || t.x >= t.view.W) return;
-  const int lo = t.lo;
-  paste_pixel(t.view, s_box, s_crop, [&](int b) -> int { const int k = s_choice[lo + b]; return k < 0 ? -1 : (lo + b) * K + k; }, t.x, t.y);
+template <class Pages>
+int launch_post(const char* kernel, const Pages& pages, dim3 grid, const float* image_vae, int S, const dmx_edit_item* items_device, int B,
+                dmx_stream_t stream) {
+  PasteArgs p{image_vae, S, items_device, B};
+  hipLaunchKernelGGL(dmx_postprocess_boxes_kernel<Pages>, grid, dim3(256), 0, (hipStream_t)stream, p, pages);
+  return dmx_check_launch(kernel);
+}
+
+template <class Pages>
+int launch_select(const char* kernel, const Pages& pages, dim3 grid, const float* image_vae, int S, const float* scores, float threshold, int* choice,
+                  const dmx_edit_item* items_device, int B, int K, dmx_stream_t stream) {
+  PasteArgs p{image_vae, S, items_device, B};
+  hipLaunchKernelGGL(dmx_postprocess_select_boxes_kernel<Pages>, grid, dim3(256), 0, (hipStream_t)stream, p, pages, scores, K, threshold, choice);
+  return dmx_check_launch(kernel);
 }
 
 }  // namespace
@@ -198,9 +192,8 @@ extern "C" int dmx_preprocess_crop_batch(const unsigned char* image_hwc, int H, 
   DMX_REQUIRE(S > 0 && S % 8 == 0, "preprocess_crop_batch: S = %d is no positive multiple of 8", S);
   const int rc = dmx_check_edit_items("preprocess_crop_batch", items_host, B, H, W, S, true);
   if (rc != DMX_OK) return rc;
-  PreBatchArgs p{image_hwc, H, W, items_device, S, out_image, out_masked_image, out_mask, out_mask_latent};
-  hipLaunchKernelGGL(dmx_preprocess_batch_kernel, dim3(cdiv(S, 256), S, B), dim3(256), 0, (hipStream_t)stream, p);
-  return dmx_check_launch("dmx_preprocess_batch_kernel");
+  return launch_pre("dmx_preprocess_batch_kernel", OnePage{image_hwc, nullptr, nullptr, H, W}, items_device, B, S, out_image, out_masked_image, out_mask,
+                    out_mask_latent, stream);
 }
 
 extern "C" int dmx_postprocess_paste_batch(const float* image_vae, int S, const unsigned char* original_hwc, unsigned char* out_hwc,
@@ -209,9 +202,8 @@ extern "C" int dmx_postprocess_paste_batch(const float* image_vae, int S, const 
   DMX_REQUIRE(image_vae && original_hwc && out_hwc && items_device, "postprocess_paste_batch: null argument");
   const int rc = dmx_check_edit_items("postprocess_paste_batch", items_host, B, H, W, S, true);
   if (rc != DMX_OK) return rc;
-  PostBatchArgs p{image_vae, S, original_hwc, out_hwc, union_mask, H, W, items_device, B};
-  hipLaunchKernelGGL(dmx_postprocess_batch_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, p);
-  return dmx_check_launch("dmx_postprocess_batch_kernel");
+  return launch_post("dmx_postprocess_batch_kernel", OnePage{original_hwc, out_hwc, union_mask, H, W}, dim3(cdiv(W, 256), H), image_vae, S, items_device,
+                     B, stream);
 }
 
 // what the two select entries ask of their scalars
@@ -228,9 +220,8 @@ extern "C" int dmx_postprocess_paste_select(const float* image_vae, int S, const
   int rc = dmx_check_select_scalars("postprocess_paste_select", K, threshold);
   if (rc == DMX_OK) rc = dmx_check_edit_items("postprocess_paste_select", items_host, B, H, W, S, true);
   if (rc != DMX_OK) return rc;
-  PostBatchArgs p{image_vae, S, original_hwc, out_hwc, union_mask, H, W, items_device, B};
-  hipLaunchKernelGGL(dmx_postprocess_select_kernel, dim3(cdiv(W, 256), H), dim3(256), 0, (hipStream_t)stream, p, scores, K, threshold, choice);
-  return dmx_check_launch("dmx_postprocess_select_kernel");
+  return launch_select("dmx_postprocess_select_kernel", OnePage{original_hwc, out_hwc, union_mask, H, W}, dim3(cdiv(W, 256), H), image_vae, S, scores,
+                       threshold, choice, items_device, B, K, stream);
 }
 
 // ---- pages
@@ -307,9 +298,8 @@ extern "C" int dmx_preprocess_crop_pages(const dmx_edit_page* pages_host, const 
   int rc = dmx_check_edit_pages("preprocess_crop_pages", pages_host, P, items_host, B, S, true);
   if (rc == DMX_OK) rc = dmx_check_page_addresses("preprocess_crop_pages", pages_host, P, false);
   if (rc != DMX_OK) return rc;
-  PrePagesArgs p{pages_device, P, items_device, S, out_image, out_masked_image, out_mask, out_mask_latent};
-  hipLaunchKernelGGL(dmx_preprocess_pages_kernel, dim3(cdiv(S, 256), S, B), dim3(256), 0, (hipStream_t)stream, p);
-  return dmx_check_launch("dmx_preprocess_pages_kernel");
+  return launch_pre("dmx_preprocess_pages_kernel", PageTable{pages_device, P}, items_device, B, S, out_image, out_masked_image, out_mask,
+                    out_mask_latent, stream);
 }
 
 extern "C" int dmx_postprocess_paste_pages(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
@@ -319,9 +309,7 @@ extern "C" int dmx_postprocess_paste_pages(const float* image_vae, int S, const 
   int rc = dmx_check_edit_pages("postprocess_paste_pages", pages_host, P, items_host, B, S, true);
   if (rc == DMX_OK) rc = dmx_check_page_addresses("postprocess_paste_pages", pages_host, P, true);
   if (rc != DMX_OK) return rc;
-  PostPagesArgs p{image_vae, S, pages_device, P, items_device, B};
-  hipLaunchKernelGGL(dmx_postprocess_pages_kernel, dim3(pages_host[P - 1].block_lo + pages_host[P - 1].blocks), dim3(256), 0, (hipStream_t)stream, p);
-  return dmx_check_launch("dmx_postprocess_pages_kernel");
+  return launch_post("dmx_postprocess_pages_kernel", PageTable{pages_device, P}, paged_grid(pages_host, P), image_vae, S, items_device, B, stream);
 }
 
 extern "C" int dmx_postprocess_paste_select_pages(const float* image_vae, int S, const float* scores, float threshold, int* choice,
@@ -334,8 +322,6 @@ extern "C" int dmx_postprocess_paste_select_pages(const float* image_vae, int S,
   if (rc == DMX_OK) rc = dmx_check_edit_pages("postprocess_paste_select_pages", pages_host, P, items_host, B, S, true);
   if (rc == DMX_OK) rc = dmx_check_page_addresses("postprocess_paste_select_pages", pages_host, P, true);
   if (rc != DMX_OK) return rc;
-  PostPagesArgs p{image_vae, S, pages_device, P, items_device, B};
-  hipLaunchKernelGGL(dmx_postprocess_select_pages_kernel, dim3(pages_host[P - 1].block_lo + pages_host[P - 1].blocks), dim3(256), 0,
-                     (hipStream_t)stream, p, scores, K, threshold, choice);
-  return dmx_check_launch("dmx_postprocess_select_pages_kernel");
+  return launch_select("dmx_postprocess_select_pages_kernel", PageTable{pages_device, P}, paged_grid(pages_host, P), image_vae, S, scores, threshold,
+                       choice, items_device, B, K, stream);
 }

@@ -1,7 +1,7 @@
-// What the paste kernels of prepost_batch.hip (the plain paste) and prepost_blend.hip (the feathered, colour-matched paste) share: the
-// arguments of a one-page paste and of a paged one, the block -> (page, row, column tile) map of the paged grid - which the quad pastes
-// of prepost_quad.hip use too -, and the choice rule of the verified edits.  Device code only; everything here is called on a block of
-// 256 threads.
+// What the box kernels of prepost_batch.hip (crop, paste, select-paste), prepost_blend.hip (colour statistics, feathered paste) and
+// readback.hip share: the page SOURCE each of them is written over - one page given by kernel arguments, or a device table of pages -,
+// the block -> (page, row, column tile) map of the paged grid - which the quad pastes of prepost_quad.hip use too -, and the choice rule
+// of the verified edits.  Device code only; the pastes are called on a block of 256 threads.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -9,9 +9,8 @@
 
 namespace dmx_paste {
 
-struct PostBatchArgs {
+struct PasteArgs {
   const float* vae; int S;                     // decoder outputs [B][3][S][S] in [-1, 1]
-  const unsigned char* ori; unsigned char* out; unsigned char* umask; int H, W;
   const dmx_edit_item* items; int B;
 };
 
@@ -59,21 +58,34 @@ __device__ __forceinline__ bool page_block(const dmx_edit_page* pages, int P, in
   return true;
 }
 
-struct PostPagesArgs {
-  const float* vae; int S;
-  const dmx_edit_page* pages; int P;
-  const dmx_edit_item* items; int B;
+// A page source travels to the kernels by value, beside their arguments, and answers, uniformly per block:
+//   tile     (the paste-shaped grids) this thread's pixel, the page and the page's slice of the item table, as a PageBlock; false: the
+//            block has no pixel to write;
+//   of       (the item-shaped grids: crop, statistics, read-back) the page of an item - `original`, H and W of it are read;
+//   chooser  (the select-paste) whether this block stores `choice`.
+// A page is a dmx_edit_page to every kernel body; OnePage's holds its arguments and no item range or block numbers.
+struct OnePage {                               // the dmx_*_batch and unsuffixed entries: grid (ceil(W / 256), H), every block has pixels
+  const unsigned char* ori; unsigned char* out; unsigned char* umask; int H, W;
+  __device__ __forceinline__ dmx_edit_page page() const {
+    return dmx_edit_page{(unsigned long long)ori, (unsigned long long)out, (unsigned long long)umask, H, W, 0, 0, 0, 0};
+  }
+  __device__ __forceinline__ bool tile(int B, PageBlock& t) const {
+    t.pg = page(); t.lo = 0; t.n = B;
+    t.x = blockIdx.x * 256 + threadIdx.x; t.y = blockIdx.y;
+    return true;
+  }
+  __device__ __forceinline__ dmx_edit_page of(const dmx_edit_item&) const { return page(); }
+  __device__ __forceinline__ bool chooser() const { return blockIdx.x == 0 && blockIdx.y == 0; }
 };
-struct PageTile { PostBatchArgs view; int lo, x, y; };
 
-// page_block with the page as the view the one-page box pastes take
-__device__ __forceinline__ bool page_tile(const PostPagesArgs& p, PageTile& t) {
-  PageBlock k;
-  if (!page_block(p.pages, p.P, p.B, DMX_EDIT_PAGE_MAX_W, k)) return false;
-  t.view = PostBatchArgs{p.vae, p.S, (const unsigned char*)k.pg.original, (unsigned char*)k.pg.out, (unsigned char*)k.pg.union_mask, k.pg.H,
-                         k.pg.W, p.items + k.lo, k.n};
-  t.lo = k.lo; t.x = k.x; t.y = k.y;
-  return true;
-}
+struct PageTable {                             // the dmx_*_pages entries: the 1-D grid of page_block, clamps included
+  const dmx_edit_page* pages; int P;
+  __device__ __forceinline__ bool tile(int B, PageBlock& t) const { return page_block(pages, P, B, DMX_EDIT_PAGE_MAX_W, t); }
+  __device__ __forceinline__ dmx_edit_page of(const dmx_edit_item& it) const { return pages[dmx_resize::page_of(it, P)]; }
+  __device__ __forceinline__ bool chooser() const { return blockIdx.x == 0; }
+};
+
+// the 1-D grid of a checked, prepared host page table
+inline dim3 paged_grid(const dmx_edit_page* pages_host, int P) { return dim3(pages_host[P - 1].block_lo + pages_host[P - 1].blocks); }
 
 }  // namespace dmx_paste

@@ -115,7 +115,7 @@ __device__ __forceinline__ bool on_crop(const Frame& frame, const dmx_edit_quad*
   return frame.paste(quads, b, S, x, y, U16, V16) && U16 >= -32768 && U16 < top && V16 >= -32768 && V16 < top;
 }
 
-// The paste over P pages: blocks enumerate (page, row, 256-column tile) along grid.x as in dmx_postprocess_pages_kernel
+// The paste over P pages: blocks enumerate (page, row, 256-column tile) along grid.x as in the paged box pastes
 // (dmx_paste::page_block); a block stages its page's quads - corners, edges, bounding box - in LDS (stage_edges; the caller's barrier
 // follows).  A pixel scans them last to first, stops at the first quad that covers it and is not skipped, and maps itself through THAT
 // item's frame (paste_quads_pixel).  row(b) -> item lo + b's row of p.vae, or < 0: the item is skipped - transparent, an earlier quad

@@ -8,36 +8,40 @@
 // (Pillow's integer two-pass resample) for the processor; the library is built with -ffp-contract=off, so the shared fp32 expressions
 // round alike in every kernel.  Pure byte work on a few thousand pixels per box: launch- and HBM-latency-bound, one thread per
 // destination pixel, coalesced plain vector stores, no uint8 intermediate in HBM.
+// ONE kernel body over a page source (prepost_paste.h), instantiated for the boxes of one image (OnePage) and for boxes on several pages
+// (PageTable: the item's page - its index travels in the item, clamped - supplies the image pointer, H and W).
 #include "common.h"
 #include "kernels.h"
+#include "prepost_paste.h"
 #include "prepost_resize.h"
 #include "glyph_resample.h"
 
 namespace {
 using namespace dmx_resize;
+using dmx_paste::OnePage;
+using dmx_paste::PageTable;
 
 struct ReadbackArgs {
   const float* vae; int S;                                 // decoder outputs [B][K][3][S][S] in [-1, 1]
-  const unsigned char* ori; int H, W;                      // the original page, HWC uint8
   const dmx_edit_item* items; const dmx_readback_pass* passes; int B, K;
   const int* tab; const float* norm;
   int S_h, S_w; float* out; unsigned char* out_u8;         // [B*K][3][S_h][S_w]
 };
 
-// Output pixel (ox, oy) of row r = b * K + k: item b of p.items on the page p.ori.
-__device__ __forceinline__ void readback_row(const ReadbackArgs& p, int r, int ox, int oy) {
-  const int b = r / p.K;
-  const dmx_edit_item it = p.items[b];
+// Output pixel (ox, oy) of row r = b * K + k: item `it` = p.items[b] on its page pg (the original, HWC uint8).
+__device__ __forceinline__ void readback_row(const ReadbackArgs& p, const dmx_edit_page& pg, const dmx_edit_item& it, int r, int ox, int oy) {
+  const int b = r / p.K, H = pg.H, W = pg.W;
+  const unsigned char* ori = (const unsigned char*)pg.original;
   const dmx_readback_pass ps = p.passes[b];
   // everything that comes from the device table is clamped: the box to the image (at least one pixel), the crop by item_geom
-  const int x1 = min(max(it.x1, 0), p.W - 1), y1 = min(max(it.y1, 0), p.H - 1);
-  const int bw = min(max(it.x2 - x1, 1), p.W - x1), bh = min(max(it.y2 - y1, 1), p.H - y1);
-  const Geom g = item_geom(it, p.H, p.W, p.S, false);
+  const int x1 = min(max(it.x1, 0), W - 1), y1 = min(max(it.y1, 0), H - 1);
+  const int bw = min(max(it.x2 - x1, 1), W - x1), bh = min(max(it.y2 - y1, 1), H - y1);
+  const Geom g = item_geom(it, H, W, p.S, false);
   const float* vae = p.vae + (size_t)r * 3 * p.S * p.S;
   auto px = [&](int y, int x, int c) -> int {                                                  // byte (x, y) of the box slice of the pasted page
     const int X = x1 + x, Y = y1 + y, dx = X - g.xs, dy = Y - g.ys;
     if (dx >= 0 && dx < g.cw && dy >= 0 && dy < g.ch) return post_pixel(vae, p.S, g, c, dx, dy);
-    return p.ori[((size_t)Y * p.W + X) * 3 + c];
+    return ori[((size_t)Y * W + X) * 3 + c];
   };
   const dmx_glyph::Passes tp{ps.h_off, ps.h_taps, ps.v_off, ps.v_taps};
   int v[3];
@@ -50,20 +54,23 @@ __device__ __forceinline__ void readback_row(const ReadbackArgs& p, int r, int o
   }
 }
 
-__global__ __launch_bounds__(128) void dmx_readback_pixel_values_kernel(const ReadbackArgs p) {
+// grid (ceil(S_w / 128), S_h, B * K)
+template <class Pages>
+__global__ __launch_bounds__(128) void dmx_readback_boxes_kernel(const ReadbackArgs p, const Pages pages) {
   const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y, r = blockIdx.z;       // r = b * K + k
   if (ox >= p.S_w) return;
-  readback_row(p, r, ox, oy);
+  const dmx_edit_item it = p.items[r / p.K];
+  readback_row(p, pages.of(it), it, r, ox, oy);
 }
 
-// Items on several pages (include/diffute_hip.h dmx_edit_page): p.ori / p.H / p.W are unset on entry, the item's page - its index
-// travels in the item, clamped here - supplies them, and the row is readback_row's on that one-page view.
-__global__ __launch_bounds__(128) void dmx_readback_pages_kernel(ReadbackArgs p, const dmx_edit_page* pages, int P) {
-  const int ox = blockIdx.x * blockDim.x + threadIdx.x, oy = blockIdx.y, r = blockIdx.z;
-  if (ox >= p.S_w) return;
-  const dmx_edit_page pg = pages[page_of(p.items[r / p.K], P)];
-  p.ori = (const unsigned char*)pg.original; p.H = pg.H; p.W = pg.W;
-  readback_row(p, r, ox, oy);
+// The launch; the tables are checked.  `kernel` names it in the last-error string.
+template <class Pages>
+int launch_readback(const char* kernel, const Pages& pages, const float* image_vae, int S, const dmx_edit_item* items_device, int B, int K,
+                    const int* tables, const float* norm, const dmx_readback_pass* passes_device, int S_h, int S_w, float* out_pixel_values,
+                    unsigned char* out_resized, dmx_stream_t stream) {
+  ReadbackArgs p{image_vae, S, items_device, passes_device, B, K, tables, norm, S_h, S_w, out_pixel_values, out_resized};
+  hipLaunchKernelGGL(dmx_readback_boxes_kernel<Pages>, dim3(cdiv(S_w, 128), S_h, B * K), dim3(128), 0, (hipStream_t)stream, p, pages);
+  return dmx_check_launch(kernel);
 }
 
 // what the read-back asks of the boxes [lo, hi) beyond dmx_check_edit_items: a non-empty box inside the H x W page, and of each one's passes
@@ -124,9 +131,8 @@ extern "C" int dmx_readback_pixel_values(const float* image_vae, int S, const un
   if (rc == DMX_OK) rc = dmx_check_edit_items(what, items_host, B, H, W, S, true);
   if (rc == DMX_OK) rc = check_readback_boxes(what, items_host, passes_host, 0, B, H, W, max_taps, table_ints, S_h, S_w);
   if (rc != DMX_OK) return rc;
-  ReadbackArgs p{image_vae, S, original_hwc, H, W, items_device, passes_device, B, K, tables, norm, S_h, S_w, out_pixel_values, out_resized};
-  hipLaunchKernelGGL(dmx_readback_pixel_values_kernel, dim3(cdiv(S_w, 128), S_h, B * K), dim3(128), 0, (hipStream_t)stream, p);
-  return dmx_check_launch("dmx_readback_pixel_values_kernel");
+  return launch_readback("dmx_readback_pixel_values_kernel", OnePage{original_hwc, nullptr, nullptr, H, W}, image_vae, S, items_device, B, K, tables, norm,
+                         passes_device, S_h, S_w, out_pixel_values, out_resized, stream);
 }
 
 extern "C" int dmx_readback_pixel_values_pages(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
@@ -146,7 +152,6 @@ extern "C" int dmx_readback_pixel_values_pages(const float* image_vae, int S, co
     rc = check_readback_boxes(what, items_host, passes_host, pg.item_lo, pg.item_hi, pg.H, pg.W, max_taps, table_ints, S_h, S_w);
     if (rc != DMX_OK) return rc;
   }
-  ReadbackArgs p{image_vae, S, nullptr, 0, 0, items_device, passes_device, B, K, tables, norm, S_h, S_w, out_pixel_values, out_resized};
-  hipLaunchKernelGGL(dmx_readback_pages_kernel, dim3(cdiv(S_w, 128), S_h, B * K), dim3(128), 0, (hipStream_t)stream, p, pages_device, P);
-  return dmx_check_launch("dmx_readback_pages_kernel");
+  return launch_readback("dmx_readback_pages_kernel", PageTable{pages_device, P}, image_vae, S, items_device, B, K, tables, norm, passes_device, S_h, S_w,
+                         out_pixel_values, out_resized, stream);
 }

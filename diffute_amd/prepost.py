@@ -262,33 +262,57 @@ def _check_page_outputs(out, images):
     return out
 
 
-def _paste_outputs(bx, out, return_mask):
-    """what the pastes write: (the output pages - `out` if given, checked -, the union masks or None); lists for a paged call, the one
-    page's tensors otherwise"""
+def _page_outputs(images, dev, out, return_mask):
+    """what a paste over `images` writes, as lists: (the output pages - `out` if given, checked -, the union masks or None)"""
     if out is not None:
-        out = _check_page_outputs(out, bx.images)
-    with torch.cuda.device(bx.dev):
-        out = [torch.empty_like(img) for img in bx.images] if out is None else out
-        union = [torch.empty(img.shape[0], img.shape[1], dtype=torch.uint8, device=bx.dev) for img in bx.images] if return_mask else None
+        out = _check_page_outputs(out, images)
+    with torch.cuda.device(dev):
+        out = [torch.empty_like(img) for img in images] if out is None else out
+        union = [torch.empty(img.shape[0], img.shape[1], dtype=torch.uint8, device=dev) for img in images] if return_mask else None
+    return out, union
+
+
+def _paste_outputs(bx, out, return_mask):
+    """_page_outputs of the boxes' pages: lists for a paged call, the one page's tensors otherwise"""
+    out, union = _page_outputs(bx.images, bx.dev, out, return_mask)
     return (out, union) if bx.paged else (out[0], None if union is None else union[0])
 
 
+def _crop_outputs(B, S, dev):
+    """what a crop of B regions writes, in the order the C entries take it (call it on the device)"""
+    return dict(image=torch.empty(B, 3, S, S, dtype=torch.float32, device=dev), masked_image=torch.empty(B, 3, S, S, dtype=torch.float32, device=dev),
+                mask=torch.empty(B, 1, S, S, dtype=torch.uint8, device=dev), mask_latent=torch.empty(B, 1, S // 8, S // 8, dtype=torch.float32, device=dev))
+
+
+def _check_readback_outputs(out, out_resized, rows, S_h, S_w, dev):
+    """the optional preallocated outputs of a read-back: contiguous [rows,3,S_h,S_w] on dev, fp32 and uint8"""
+    for name, t, dt in (("out", out, torch.float32), ("out_resized", out_resized, torch.uint8)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dt and t.is_contiguous()
+                                  and tuple(t.shape) == (rows, 3, S_h, S_w)):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor [{rows},3,{S_h},{S_w}] on {dev}")
+
+
+def _call_boxes(name, bx, tables, head, *tail, outs=(), choice=()):
+    """dmx_<name>(*head, the page part, the item table - host and device -, B, *tail, stream) on the current stream, `tables` being what
+    _upload returned.  The page part of a one-page call is `img, *outs, *choice, H, W` - outs: the (out, union) a paste writes; choice: the
+    select paste's, which the C signature has there.  A paged call runs dmx_<name>_pages (for dmx_<name>_batch) and its page part is
+    `*choice, pages_host, pages_device, P`: the outputs travel in the page table."""
+    host, pages, _, dbuf, offs = tables
+    base, img, lib = dbuf.data_ptr(), bx.images[0], _cabi.lib()
+    if bx.paged:
+        name, page = name.removesuffix("_batch") + "_pages", (*choice, pages, base + offs[0], len(bx.images))
+    else:
+        page = (_cabi.ptr(img), *map(_cabi.ptr, outs), *choice, img.shape[0], img.shape[1])
+    _cabi.check(getattr(lib, "dmx_" + name)(*head, *page, host, base, len(host), *tail, _cabi.current_stream()), name, lib)
+
+
 def _preprocess(bx, size):
-    B, S, img = len(bx.locations), int(size), bx.images[0]
-    host, pages, stage, dbuf, offs = _upload(bx, S)
-    base = dbuf.data_ptr()
+    B, S = len(bx.locations), int(size)
+    tables = _upload(bx, S)
     with torch.cuda.device(bx.dev):
-        image = torch.empty(B, 3, S, S, dtype=torch.float32, device=bx.dev)
-        masked = torch.empty(B, 3, S, S, dtype=torch.float32, device=bx.dev)
-        mask = torch.empty(B, 1, S, S, dtype=torch.uint8, device=bx.dev)
-        mask_lat = torch.empty(B, 1, S // 8, S // 8, dtype=torch.float32, device=bx.dev)
-        outs = (_cabi.ptr(image), _cabi.ptr(masked), _cabi.ptr(mask), _cabi.ptr(mask_lat), _cabi.current_stream())
-        if bx.paged:
-            _cabi.check(_cabi.lib().dmx_preprocess_crop_pages(pages, base + offs[0], len(bx.images), host, base, B, S, *outs), "preprocess_crop_pages")
-        else:
-            _cabi.check(_cabi.lib().dmx_preprocess_crop_batch(_cabi.ptr(img), img.shape[0], img.shape[1], host, base, B, S, *outs),
-                        "preprocess_crop_batch")
-    return dict(image=image, masked_image=masked, mask=mask, mask_latent=mask_lat)
+        pre = _crop_outputs(B, S, bx.dev)
+        _call_boxes("preprocess_crop_batch", bx, tables, (), S, *map(_cabi.ptr, pre.values()))
+    return pre
 
 
 class PasteBlend:
@@ -341,9 +365,14 @@ def _check_blend(blend):
     return blend
 
 
-def _check_scores(scores, B, K, threshold):
+def _check_scores_tensor(scores):
     if not (isinstance(scores, torch.Tensor) and scores.is_cuda):
         raise TypeError("scores: expected a CUDA tensor")
+
+
+def _check_scores(scores, B, K, threshold):
+    """scores [B,K] on the device and the threshold -> the threshold as the C entries take it (None: -inf)"""
+    _check_scores_tensor(scores)
     if tuple(scores.shape) != (B, K):
         raise ValueError(f"scores must be [{B},{K}], got {tuple(scores.shape)}")
     thr = float("-inf") if threshold is None else float(threshold)
@@ -360,16 +389,10 @@ def _choose(lib, scores, B, K, thr, dev):
     return choice
 
 
-def _color_stats(lib, bx, v, S, K, choice, bs, host, pages, base, off_pages):
+def _color_stats(bx, tables, v, S, K, choice, bs):
     """stats int64 [B,4] on the device: one launch, one block per item"""
-    B, img = len(bx.locations), bx.images[0]
-    stats = torch.empty(B, 4, dtype=torch.int64, device=bx.dev)
-    if bx.paged:
-        _cabi.check(lib.dmx_paste_color_stats_pages(_cabi.ptr(v), S, pages, base + off_pages, len(bx.images), host, base, B, ctypes.byref(bs),
-                                                    _cabi.ptr(choice), K, _cabi.ptr(stats), _cabi.current_stream()), "paste_color_stats_pages", lib)
-    else:
-        _cabi.check(lib.dmx_paste_color_stats(_cabi.ptr(v), S, _cabi.ptr(img), img.shape[0], img.shape[1], host, base, B, ctypes.byref(bs),
-                                              _cabi.ptr(choice), K, _cabi.ptr(stats), _cabi.current_stream()), "paste_color_stats", lib)
+    stats = torch.empty(len(bx.locations), 4, dtype=torch.int64, device=bx.dev)
+    _call_boxes("paste_color_stats", bx, tables, (_cabi.ptr(v), S), ctypes.byref(bs), _cabi.ptr(choice), K, _cabi.ptr(stats))
     return stats
 
 
@@ -377,23 +400,16 @@ def _blend_paste(bx, image_vae, blend, return_mask, out, scores=None, threshold=
     """the blended pastes: [choose ->] [stats ->] paste, every launch on the current stream, nothing read on the host.  scores given:
     image_vae is [B,K,3,S,S] and (out, choice[, union]) comes back, as from the select pastes"""
     blend = _check_blend(blend)
-    B, img, select = len(bx.locations), bx.images[0], scores is not None
+    B, select = len(bx.locations), scores is not None
     S, K = _check_vae(image_vae, B, select)
     thr = _check_scores(scores, B, K, threshold) if select else None
     out, union = _paste_outputs(bx, out, return_mask)
     v = image_vae.to(torch.float32).contiguous()
-    host, pages, stage, dbuf, offs = _upload(bx, S, out, union) if bx.paged else _upload(bx, S)
-    base, bs, lib = dbuf.data_ptr(), blend._struct(), _cabi.lib()
+    tables, bs = _upload(bx, S, out, union), blend._struct()
     with torch.cuda.device(bx.dev):
-        choice = _choose(lib, scores, B, K, thr, bx.dev) if select else None
-        stats = _color_stats(lib, bx, v, S, K, choice, bs, host, pages, base, offs[0]) if blend.match_color else None
-        rest = (ctypes.byref(bs), _cabi.ptr(stats), _cabi.ptr(choice), K, _cabi.current_stream())
-        if bx.paged:
-            _cabi.check(lib.dmx_postprocess_paste_blend_pages(_cabi.ptr(v), S, pages, base + offs[0], len(bx.images), host, base, B, *rest),
-                        "postprocess_paste_blend_pages", lib)
-        else:
-            _cabi.check(lib.dmx_postprocess_paste_blend(_cabi.ptr(v), S, _cabi.ptr(img), _cabi.ptr(out), _cabi.ptr(union), img.shape[0], img.shape[1],
-                                                        host, base, B, *rest), "postprocess_paste_blend", lib)
+        choice = _choose(_cabi.lib(), scores, B, K, thr, bx.dev) if select else None
+        stats = _color_stats(bx, tables, v, S, K, choice, bs) if blend.match_color else None
+        _call_boxes("postprocess_paste_blend", bx, tables, (_cabi.ptr(v), S), ctypes.byref(bs), _cabi.ptr(stats), _cabi.ptr(choice), K, outs=(out, union))
     if select:
         return (out, choice, union) if return_mask else (out, choice)
     return (out, union) if return_mask else out
@@ -407,25 +423,18 @@ def _stats_only(bx, image_vae, blend, choice):
                                    and tuple(choice.shape) == (B,)):
         raise ValueError(f"choice must be a contiguous int32 CUDA tensor [{B}]")
     v = image_vae.to(torch.float32).contiguous()
-    host, pages, stage, dbuf, offs = _upload(bx, S)
+    tables = _upload(bx, S)
     with torch.cuda.device(bx.dev):
-        return _color_stats(_cabi.lib(), bx, v, S, K, choice, blend._struct(), host, pages, dbuf.data_ptr(), offs[0])
+        return _color_stats(bx, tables, v, S, K, choice, blend._struct())
 
 
 def _paste(bx, image_vae, return_mask, out):
-    B, img = len(bx.locations), bx.images[0]
-    S, _ = _check_vae(image_vae, B, False)
+    S, _ = _check_vae(image_vae, len(bx.locations), False)
     out, union = _paste_outputs(bx, out, return_mask)
     v = image_vae.to(torch.float32).contiguous()
-    host, pages, stage, dbuf, offs = _upload(bx, S, out, union) if bx.paged else _upload(bx, S)
-    base = dbuf.data_ptr()
+    tables = _upload(bx, S, out, union)
     with torch.cuda.device(bx.dev):
-        if bx.paged:
-            _cabi.check(_cabi.lib().dmx_postprocess_paste_pages(_cabi.ptr(v), S, pages, base + offs[0], len(bx.images), host, base, B,
-                                                               _cabi.current_stream()), "postprocess_paste_pages")
-        else:
-            _cabi.check(_cabi.lib().dmx_postprocess_paste_batch(_cabi.ptr(v), S, _cabi.ptr(img), _cabi.ptr(out), _cabi.ptr(union), img.shape[0],
-                                                               img.shape[1], host, base, B, _cabi.current_stream()), "postprocess_paste_batch")
+        _call_boxes("postprocess_paste_batch", bx, tables, (_cabi.ptr(v), S), outs=(out, union))
     return (out, union) if return_mask else out
 
 
@@ -485,14 +494,11 @@ def _readback(bx, image_vae, ip, return_resized, out, out_resized):
     else:
         check_readback_boxes(bx.locations, img.shape[0], img.shape[1])
     S_h, S_w = ip.size["height"], ip.size["width"]
-    for name, t, dt in (("out", out, torch.float32), ("out_resized", out_resized, torch.uint8)):
-        if t is not None and not (isinstance(t, torch.Tensor) and t.device == bx.dev and t.dtype == dt and t.is_contiguous()
-                                  and tuple(t.shape) == (B * K, 3, S_h, S_w)):
-            raise ValueError(f"{name} must be a contiguous {dt} tensor [{B * K},3,{S_h},{S_w}] on {bx.dev}")
-    lib = _cabi.lib()
-    passes, tables, max_taps = _readback_tables(bx.locations, ip, int(lib.dmx_glyph_max_taps()))
+    _check_readback_outputs(out, out_resized, B * K, S_h, S_w, bx.dev)
+    passes, tables, max_taps = _readback_tables(bx.locations, ip, int(_cabi.lib().dmx_glyph_max_taps()))
     v = image_vae.to(torch.float32).contiguous()
-    host, pages, stage, dbuf, (off_pages, off_pass, off_norm, off_tab) = _upload(bx, S, extra=(passes, ip._norm, tables))
+    up = _upload(bx, S, extra=(passes, ip._norm, tables))
+    _, _, stage, dbuf, (_, off_pass, off_norm, off_tab) = up
     host_passes = (_cabi.ReadbackPass * B).from_buffer(stage.numpy()[off_pass:off_norm])
     base = dbuf.data_ptr()
     with torch.cuda.device(bx.dev):
@@ -501,40 +507,22 @@ def _readback(bx, image_vae, ip, return_resized, out, out_resized):
         res = out_resized
         if res is None and return_resized:
             res = torch.empty(B * K, 3, S_h, S_w, dtype=torch.uint8, device=bx.dev)
-        rest = (host, base, B, K, base + off_tab, int(tables.size), base + off_norm, host_passes, base + off_pass, max_taps, S_h, S_w, _cabi.ptr(out),
-                _cabi.ptr(res), _cabi.current_stream())
-        if bx.paged:
-            _cabi.check(lib.dmx_readback_pixel_values_pages(_cabi.ptr(v), S, pages, base + off_pages, len(bx.images), *rest),
-                        "readback_pixel_values_pages", lib)
-        else:
-            _cabi.check(lib.dmx_readback_pixel_values(_cabi.ptr(v), S, _cabi.ptr(img), img.shape[0], img.shape[1], *rest), "readback_pixel_values", lib)
+        _call_boxes("readback_pixel_values", bx, up, (_cabi.ptr(v), S), K, base + off_tab, int(tables.size), base + off_norm, host_passes,
+                    base + off_pass, max_taps, S_h, S_w, _cabi.ptr(out), _cabi.ptr(res))
     return (out, res) if (return_resized or out_resized is not None) else out
 
 
 def _select_paste(bx, image_vae, scores, threshold, return_mask, out):
-    B, img = len(bx.locations), bx.images[0]
-    if not (isinstance(scores, torch.Tensor) and scores.is_cuda):
-        raise TypeError("scores: expected a CUDA tensor")
+    B = len(bx.locations)
+    _check_scores_tensor(scores)                                       # (before image_vae is looked at, the rest after)
     S, K = _check_vae(image_vae, B, True)
-    if tuple(scores.shape) != (B, K):
-        raise ValueError(f"scores must be [{B},{K}], got {tuple(scores.shape)}")
-    thr = float("-inf") if threshold is None else float(threshold)
-    if thr != thr:
-        raise ValueError("threshold is NaN")
+    thr = _check_scores(scores, B, K, threshold)
     out, union = _paste_outputs(bx, out, return_mask)
     v, sc = image_vae.to(torch.float32).contiguous(), scores.to(torch.float32).contiguous()
-    host, pages, stage, dbuf, offs = _upload(bx, S, out, union) if bx.paged else _upload(bx, S)
-    base = dbuf.data_ptr()
+    tables = _upload(bx, S, out, union)
     with torch.cuda.device(bx.dev):
         choice = torch.empty(B, dtype=torch.int32, device=bx.dev)
-        if bx.paged:
-            _cabi.check(_cabi.lib().dmx_postprocess_paste_select_pages(_cabi.ptr(v), S, _cabi.ptr(sc), thr, _cabi.ptr(choice), pages, base + offs[0],
-                                                                      len(bx.images), host, base, B, K, _cabi.current_stream()),
-                        "postprocess_paste_select_pages")
-        else:
-            _cabi.check(_cabi.lib().dmx_postprocess_paste_select(_cabi.ptr(v), S, _cabi.ptr(sc), thr, _cabi.ptr(img), _cabi.ptr(out), _cabi.ptr(union),
-                                                                _cabi.ptr(choice), img.shape[0], img.shape[1], host, base, B, K,
-                                                                _cabi.current_stream()), "postprocess_paste_select")
+        _call_boxes("postprocess_paste_select", bx, tables, (_cabi.ptr(v), S, _cabi.ptr(sc), thr), K, outs=(out, union), choice=(_cabi.ptr(choice),))
     return (out, choice, union) if return_mask else (out, choice)
 
 
@@ -859,6 +847,15 @@ def _call_quads(name, t, head, *tail):
     _cabi.check(getattr(_cabi.lib(), "dmx_" + name)(*head, *tables, len(t.host), *tail, _cabi.current_stream()), name)
 
 
+def _plan_persp(images, quads, frames, perspective, size):
+    """the projective frames where a perspective call left them open (frames None), planned here; size: the crop size, or the decoder
+    outputs whose last dimension it is"""
+    if perspective and frames is None:
+        S = size if isinstance(size, (int, np.integer)) else size.shape[-1]
+        return plan_quads([list(q) for q in quads], [(int(i.shape[0]), int(i.shape[1])) for i in images], True, int(S))
+    return frames
+
+
 def preprocess_quads(images, quads, frames, size=512, perspective=False):
     """preprocess_pages for quadrilateral regions, in one launch.  images: P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device;
     quads: P lists of quads (four corners TL, TR, BR, BL); frames: P lists of (cx2, cy2, crop_scale, ux, uy) (plan_quads gives them).
@@ -868,18 +865,12 @@ def preprocess_quads(images, quads, frames, size=512, perspective=False):
     is taken through the homography that makes the quad an upright rectangle (csrc/prepost_persp.h), so a trapezoid's text is seen
     without keystone; the same outputs."""
     S = int(size)
-    if perspective and frames is None:
-        frames = plan_quads([list(q) for q in quads], [(int(i.shape[0]), int(i.shape[1])) for i in images], True, S)
-    qx = _check_quads(images, quads, frames, perspective)
-    B = len(qx.quads)
+    qx = _check_quads(images, quads, _plan_persp(images, quads, frames, perspective, S), perspective)
     t = _upload_quads(qx, S)
     with torch.cuda.device(qx.dev):
-        image = torch.empty(B, 3, S, S, dtype=torch.float32, device=qx.dev)
-        masked = torch.empty(B, 3, S, S, dtype=torch.float32, device=qx.dev)
-        mask = torch.empty(B, 1, S, S, dtype=torch.uint8, device=qx.dev)
-        mask_lat = torch.empty(B, 1, S // 8, S // 8, dtype=torch.float32, device=qx.dev)
-        _call_quads("preprocess_quads", t, (), S, _cabi.ptr(image), _cabi.ptr(masked), _cabi.ptr(mask), _cabi.ptr(mask_lat))
-    return dict(image=image, masked_image=masked, mask=mask, mask_latent=mask_lat)
+        pre = _crop_outputs(len(qx.quads), S, qx.dev)
+        _call_quads("preprocess_quads", t, (), S, *map(_cabi.ptr, pre.values()))
+    return pre
 
 
 def postprocess_quads(image_vae, images, quads, frames, return_mask=False, out=None, perspective=False):
@@ -889,16 +880,9 @@ def postprocess_quads(image_vae, images, quads, frames, return_mask=False, out=N
     other pixel is the original's; with return_mask=True also the list of P union masks uint8 [h_p][w_p] (1 inside any quad).  out: as
     for postprocess_pages.  perspective=True: frames are projective (None plans them), and a page pixel finds its crop coordinates
     through the inverse homography; which pixels are pasted, and the union masks, follow the same rule."""
-    if perspective and frames is None:
-        frames = plan_quads([list(q) for q in quads], [(int(i.shape[0]), int(i.shape[1])) for i in images], True, int(image_vae.shape[-1]))
-    qx = _check_quads(images, quads, frames, perspective)
-    B = len(qx.quads)
-    S, _ = _check_vae(image_vae, B, False)
-    if out is not None:
-        out = _check_page_outputs(out, qx.images)
-    with torch.cuda.device(qx.dev):
-        out = [torch.empty_like(img) for img in qx.images] if out is None else out
-        union = [torch.empty(img.shape[0], img.shape[1], dtype=torch.uint8, device=qx.dev) for img in qx.images] if return_mask else None
+    qx = _check_quads(images, quads, _plan_persp(images, quads, frames, perspective, image_vae), perspective)
+    S, _ = _check_vae(image_vae, len(qx.quads), False)
+    out, union = _page_outputs(qx.images, qx.dev, out, return_mask)
     v = image_vae.to(torch.float32).contiguous()
     t = _upload_quads(qx, S, out, union)
     with torch.cuda.device(qx.dev):
@@ -922,13 +906,6 @@ def rectify_quads(images, quads, perspective=False):
     return [buf[int(q.rect_off):int(q.rect_off) + int(q.rw) * int(q.rh) * 3].view(int(q.rh), int(q.rw), 3) for q in t.host]
 
 
-def _plan_persp(images, quads, frames, perspective, size):
-    """the projective frames where a perspective call left them open, as the other quad functions plan them"""
-    if perspective and frames is None:
-        return plan_quads([list(q) for q in quads], [(int(i.shape[0]), int(i.shape[1])) for i in images], True, int(size))
-    return frames
-
-
 def readback_pixel_values_quads(image_vae, images, quads, frames, processor, perspective=False, return_resized=False, out=None, out_resized=None):
     """readback_pixel_values_pages for quadrilateral regions, in ONE launch: image_vae fp32 CUDA [N,K,3,S,S] (or [N*K,3,S,S]) decoder
     outputs, page-major -> pixel_values fp32 [N*K,3,S_h,S_w].  Row (b, k) is bit for bit `processor(rectify_quads(postprocess_quads(
@@ -949,10 +926,7 @@ def readback_pixel_values_quads(image_vae, images, quads, frames, processor, per
         image_vae = image_vae.reshape(B, image_vae.shape[0] // B, *image_vae.shape[1:])
     S, K = _check_vae(image_vae, B, True)
     S_h, S_w = ip.size["height"], ip.size["width"]
-    for name, t, dt in (("out", out, torch.float32), ("out_resized", out_resized, torch.uint8)):
-        if t is not None and not (isinstance(t, torch.Tensor) and t.device == qx.dev and t.dtype == dt and t.is_contiguous()
-                                  and tuple(t.shape) == (B * K, 3, S_h, S_w)):
-            raise ValueError(f"{name} must be a contiguous {dt} tensor [{B * K},3,{S_h},{S_w}] on {qx.dev}")
+    _check_readback_outputs(out, out_resized, B * K, S_h, S_w, qx.dev)
     lib = _cabi.lib()
     cap, made = int(lib.dmx_glyph_max_taps()), {}
 
@@ -981,8 +955,7 @@ def postprocess_select_quads(image_vae, scores, images, quads, frames, threshold
     (pages, choice): choice int32 [N] on the device by the rule of postprocess_select_batch, and the list of P pages postprocess_quads
     gives for the chosen rows.  A quad whose best score is below `threshold` (choice -1) is TRANSPARENT: it pastes nothing, and an earlier
     chosen quad under it still shows.  With return_mask=True also the list of P union masks, 1 inside ANY quad, skipped ones included."""
-    if not (isinstance(scores, torch.Tensor) and scores.is_cuda):
-        raise TypeError("scores: expected a CUDA tensor")
+    _check_scores_tensor(scores)
     if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
         raise TypeError("image_vae: expected a CUDA tensor")
     frames = _plan_persp(images, quads, frames, perspective, image_vae.shape[-1])
@@ -990,11 +963,8 @@ def postprocess_select_quads(image_vae, scores, images, quads, frames, threshold
     B = len(qx.quads)
     S, K = _check_vae(image_vae, B, True)
     thr = _check_scores(scores, B, K, threshold)
-    if out is not None:
-        out = _check_page_outputs(out, qx.images)
+    out, union = _page_outputs(qx.images, qx.dev, out, return_mask)
     with torch.cuda.device(qx.dev):
-        out = [torch.empty_like(img) for img in qx.images] if out is None else out
-        union = [torch.empty(img.shape[0], img.shape[1], dtype=torch.uint8, device=qx.dev) for img in qx.images] if return_mask else None
         choice = torch.empty(B, dtype=torch.int32, device=qx.dev)
     v, sc = image_vae.to(torch.float32).contiguous(), scores.to(torch.float32).contiguous()
     t = _upload_quads(qx, S, out, union)
