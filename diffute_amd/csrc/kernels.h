@@ -484,3 +484,8 @@ int dmx_check_select_scalars(const char* what, int K, float threshold);
 int dmx_check_readback_scalars(const char* what, int K, int max_taps, long long table_ints, int S_h, int S_w);
 int dmx_check_readback_item(const char* what, int b, const dmx_readback_pass& ps, int src_w, int src_h, int max_taps, long long table_ints, int S_h,
                             int S_w);
+// ------------------------------------------------------------------ prepost_quad.hip
+// what every quad launch entry asks of its host tables (also asked by prepost_quad_blend.hip): prepared page and quad tables - `frames`:
+// the similarity frames are looked at - and the pages' addresses; and of the prepared projective table beside them (S >= 1: all three maps)
+int dmx_check_quad_tables(const char* what, const dmx_edit_page* pages, int P, const dmx_edit_quad* quads, int B, int S, bool frames, bool need_out);
+int dmx_check_quad_persp(const char* what, const dmx_edit_quad* quads, const dmx_quad_persp* persp, int B, int S);

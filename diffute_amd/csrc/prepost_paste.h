@@ -88,4 +88,27 @@ struct PageTable {                             // the dmx_*_pages entries: the 1
 // the 1-D grid of a checked, prepared host page table
 inline dim3 paged_grid(const dmx_edit_page* pages_host, int P) { return dim3(pages_host[P - 1].block_lo + pages_host[P - 1].blocks); }
 
+// What the blended pastes share (prepost_blend.hip for boxes, prepost_quad_blend.hip for quads).
+// the decoder row of item b (its index in the whole table): b itself, or with a choice table row b * K + choice[b]; < 0 = skipped
+__device__ __forceinline__ int row_of(const int* choice, int K, int b) {
+  if (!choice) return b;
+  const int k = choice[b];
+  return k < 0 ? -1 : b * K + min(k, K - 1);
+}
+
+__device__ __forceinline__ long long floor_div(long long a, long long b) {           // b > 0
+  const long long q = a / b;
+  return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+
+// dmx_paste_blend as the kernels take it: F = feather + 1
+struct Blend { int F, grow, ring, max_shift, match; };
+
+// the colour shift of one channel from an item's statistics (n > 0): floor((2 D + n) / (2 n)); |D| <= 255 n, the clamp is for stale tables
+__device__ __forceinline__ int color_shift(long long D, long long n) { return (int)min(max(floor_div(2 * D + n, 2 * n), -255ll), 255ll); }
+
 }  // namespace dmx_paste
+
+// the blend parameters and the choice table, as every blended entry checks them (prepost_blend.hip); cap: DMX_PASTE_BLEND_MAX for boxes,
+// DMX_QUAD_BLEND_MAX for quads
+int dmx_check_paste_blend(const char* what, const dmx_paste_blend* blend, int cap, const int* choice, int K, dmx_paste::Blend& bl);

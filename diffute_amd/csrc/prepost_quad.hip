@@ -11,70 +11,17 @@
 //                     (prepost_persp.h) - phone photos, signs and scene text, where a line is a trapezoid and the similarity frame leaves
 //                     the text keystoned: the dmx_*_quads_persp entries.  Per pixel two 64-bit numerators, one denominator and four
 //                     64-bit divisions more.
+// The frames themselves live in prepost_quad_frame.h (the blended pastes of prepost_quad_blend.hip are written over them too).
 // Everything after the coordinates (taps, rounding, predicate, paste rule, stores) is prepost_quad.h's.  Pure HBM-bound byte work: one
 // thread per destination pixel, coalesced plain vector stores, the integer tables staged in LDS once per block, no atomics.
 #include "common.h"
 #include "kernels.h"
 #include "prepost_paste.h"
-#include "prepost_persp.h"
+#include "prepost_quad_frame.h"
 #include "glyph_resample.h"
 
 namespace {
 using namespace dmx_quad;
-
-constexpr int kQuadInts = (int)(sizeof(dmx_edit_quad) / sizeof(int));
-constexpr int kPerspInts = (int)(sizeof(dmx_quad_persp) / sizeof(int));
-static_assert(sizeof(dmx_edit_quad) % sizeof(int) == 0 && sizeof(dmx_quad_persp) % sizeof(int) == 0 && kQuadInts + kPerspInts <= 256,
-              "a block stages one quad and its projective frame with one int per thread");
-
-// A frame travels to the kernels by value, beside their arguments.  Item: what a block of the crop and of the rectify stages of item b
-// in LDS - stage() fills it with one int per thread and ends with ONE barrier.  crop / strip: the page coordinates (Q16) of the grid
-// point (p, q) of the staged item's crop / strip.  paste: the crop coordinates of page pixel (x, y) for item b, read from global memory
-// (the paste stages edges, not frames); false where the map is not defined.
-struct SimilarityFrame {
-  struct Item { dmx_edit_quad q; };
-  __device__ __forceinline__ void stage(Item& s, const dmx_edit_quad* quads, int b) const {
-    if ((int)threadIdx.x < kQuadInts) ((int*)&s.q)[threadIdx.x] = ((const int*)(quads + b))[threadIdx.x];
-    __syncthreads();
-  }
-  __device__ __forceinline__ void crop(const Item& s, long long p, long long q, long long& X16, long long& Y16) const {
-    X16 = ((long long)s.q.cx2 << 15) + s.q.fwd[0] * p + s.q.fwd[1] * q;
-    Y16 = ((long long)s.q.cy2 << 15) + s.q.fwd[2] * p + s.q.fwd[3] * q;
-  }
-  __device__ __forceinline__ void strip(const Item& s, long long p, long long q, long long& X16, long long& Y16) const {
-    X16 = ((long long)s.q.sx4 << 14) + s.q.rect[0] * p + s.q.rect[1] * q;
-    Y16 = ((long long)s.q.sy4 << 14) + s.q.rect[2] * p + s.q.rect[3] * q;
-  }
-  __device__ __forceinline__ bool paste(const dmx_edit_quad* quads, int b, int S, int x, int y, long long& U16, long long& V16) const {
-    const dmx_edit_quad& q = quads[b];
-    const long long qx = 2ll * x - q.cx2, qy = 2ll * y - q.cy2, base = (long long)(S - 1) << 15;
-    U16 = base + q.inv[0] * qx + q.inv[1] * qy;
-    V16 = base + q.inv[2] * qx + q.inv[3] * qy;
-    return true;
-  }
-};
-
-struct ProjectiveFrame {
-  const dmx_quad_persp* table;
-  struct Item { dmx_edit_quad q; dmx_quad_persp x; };
-  __device__ __forceinline__ void stage(Item& s, const dmx_edit_quad* quads, int b) const {
-    const int t = threadIdx.x;
-    if (t < kQuadInts) ((int*)&s.q)[t] = ((const int*)(quads + b))[t];
-    else if (t < kQuadInts + kPerspInts) ((int*)&s.x)[t - kQuadInts] = ((const int*)(table + b))[t - kQuadInts];
-    __syncthreads();
-  }
-  // (a stale table: coords writes nothing, the sample is the page's corner; tap16 clamps anyway)
-  __device__ __forceinline__ void crop(const Item& s, long long p, long long q, long long& X16, long long& Y16) const {
-    dmx_persp::coords(s.x.crop, p, q, X16, Y16);
-  }
-  __device__ __forceinline__ void strip(const Item& s, long long p, long long q, long long& X16, long long& Y16) const {
-    dmx_persp::coords(s.x.strip, p, q, X16, Y16);
-  }
-  __device__ __forceinline__ bool paste(const dmx_edit_quad*, int b, int, int x, int y, long long& U16, long long& V16) const {
-    const dmx_quad_persp& f = table[b];
-    return dmx_persp::coords(f.paste, 2ll * x - f.cx2, 2ll * y - f.cy2, U16, V16);
-  }
-};
 
 struct PreQuadArgs {
   const dmx_edit_page* pages; int P;
@@ -106,14 +53,6 @@ struct PostQuadArgs {
   const dmx_edit_page* pages; int P;
   const dmx_edit_quad* quads; int B;
 };
-
-// Item b's crop coordinates of page pixel (x, y), and whether the pixel lies on that crop with the frame's map defined there: what decides
-// between the decoder's byte and the original one, in the paste and in the read-back alike.
-template <class Frame>
-__device__ __forceinline__ bool on_crop(const Frame& frame, const dmx_edit_quad* quads, int b, int S, int x, int y, long long& U16, long long& V16) {
-  const long long top = ((long long)S << 16) - 32768;
-  return frame.paste(quads, b, S, x, y, U16, V16) && U16 >= -32768 && U16 < top && V16 >= -32768 && V16 < top;
-}
 
 // The paste over P pages: blocks enumerate (page, row, 256-column tile) along grid.x as in the paged box pastes
 // (dmx_paste::page_block); a block stages its page's quads - corners, edges, bounding box - in LDS (stage_edges; the caller's barrier
@@ -435,6 +374,13 @@ int launch_rectify(const char* what, const char* kernel, const Frame& frame, con
 }
 
 }  // namespace
+
+int dmx_check_quad_tables(const char* what, const dmx_edit_page* pages, int P, const dmx_edit_quad* quads, int B, int S, bool frames, bool need_out) {
+  return check_tables(what, pages, P, quads, B, S, frames, need_out);
+}
+int dmx_check_quad_persp(const char* what, const dmx_edit_quad* quads, const dmx_quad_persp* persp, int B, int S) {
+  return check_persp(what, quads, persp, nullptr, B, S);
+}
 
 extern "C" int dmx_edit_quads_prepare(dmx_edit_page* pages, int P, dmx_edit_quad* quads, int B, int S) {
   const int rc = check_quads("edit_quads_prepare", pages, P, quads, B, S, true, false);

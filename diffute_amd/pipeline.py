@@ -307,9 +307,12 @@ def edit_quads(unet, vae, scheduler, images, quads, encoder_hidden_states, num_i
     two launches is the same.  Limits: the window is not moved to stay on the page (the border is replicated), a window over which the
     homography's denominator changes by more than 4x is refused, curved text is out.
 
-    blend: must be None.  The feathered, colour-matched paste of edit_boxes is not built for quads: the ramp would have to be measured in
-    the strip's coordinates, not the page's."""
-    _no_quad_blend(blend, "edit_quads")
+    blend: None - the hard paste of the quad -, or a prepost.QuadBlend: the paste gets a feathered edge and / or a colour match of every
+    patch against the page around it ([stats ->] blended paste on the device, prepost.postprocess_quads(blend=...)).  The ramp is measured
+    perpendicular to the quad's edges in whole pixel steps, so it follows a tilted line or a trapezoid and survives a quarter turn of the
+    page; with grow > 0 pixels outside the quad change, but none outside blend.grown(quads).  A PasteBlend - the box blend, whose ramp runs
+    along the page's axes - raises NotImplementedError; anything else TypeError."""
+    _check_quad_blend(blend, "edit_quads")
     perspective = bool(perspective)
     if int(batch_size) < 1:
         raise ValueError("batch_size must be at least 1")
@@ -323,13 +326,16 @@ def edit_quads(unet, vae, scheduler, images, quads, encoder_hidden_states, num_i
     pre = prepost.preprocess_quads(images, quads, frames, size=size, perspective=perspective)
     image_vae = _edit_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
                            enc_noise, variance_noise, int(size), cache_interval, guidance)
-    out = prepost.postprocess_quads(image_vae, images, quads, frames, perspective=perspective)
+    out = prepost.postprocess_quads(image_vae, images, quads, frames, perspective=perspective, blend=blend)
     return (out, image_vae, pre) if return_intermediate else out
 
 
-def _no_quad_blend(blend, who):
-    if blend is not None:
-        raise NotImplementedError(f"{who}: blend is not supported for quads (the ramp would have to be measured in strip coordinates); pass None")
+def _check_quad_blend(blend, who):
+    """the blend rule of the quad edits: None or a QuadBlend; a PasteBlend is the box blend"""
+    if isinstance(blend, prepost.PasteBlend):
+        raise NotImplementedError(f"{who}: a PasteBlend is not supported for quads (its ramp is measured along the page's axes); pass a QuadBlend or None")
+    if blend is not None and not isinstance(blend, prepost.QuadBlend):
+        raise TypeError(f"{who}: blend: expected a QuadBlend or None, got {type(blend).__name__}")
 
 
 def _quad_lists(images, quads, frames):
@@ -622,7 +628,7 @@ class _QuadRegions:
         self.perspective = bool(perspective)
 
     def check_blend(self, blend):
-        _no_quad_blend(blend, "edit_quads_verified")
+        _check_quad_blend(blend, "edit_quads_verified")
 
     def check_readback(self):
         pass                                                           # (a prepared quad has a strip of at least one pixel)
@@ -639,7 +645,7 @@ class _QuadRegions:
 
     def select_paste(self, image_vae, scores, min_score, blend):
         return prepost.postprocess_select_quads(image_vae, scores, self.images, self.quads, self.frames, threshold=min_score,
-                                                perspective=self.perspective)
+                                                perspective=self.perspective, blend=blend)
 
 
 def _edit_verified(regions, unet, vae, scheduler, ocr, processor, encoder_hidden_states, labels, num_inference_steps, candidates, seeds, min_score,
@@ -684,7 +690,10 @@ def edit_quads_verified(unet, vae, scheduler, ocr, processor, images, quads, enc
     pixels and is transparent: an earlier chosen quad under it still shows.
 
     Returns the list of P pages, or a VerifiedEdit whose `image` is that list with return_intermediate=True.  candidates=1 with
-    min_score=None returns edit_quads' pages, bit for bit.  blend: must be None, as for edit_quads."""
+    min_score=None returns edit_quads' pages, bit for bit.  blend: as for edit_quads, applied to the chosen candidates (choose -> [stats ->]
+    blended paste on the device, still no score read on the host).  The read-back keeps scoring every candidate as the HARD paste shows
+    it - candidate k of quad b pasted alone, without feather, grow or colour match -: the blend changes how the chosen candidate is put on
+    the page, not which one is chosen."""
     return _edit_verified(_QuadRegions(images, quads, frames, perspective), unet, vae, scheduler, ocr, processor, encoder_hidden_states, labels,
                           num_inference_steps, candidates, seeds, min_score, batch_size, ocr_batch_size, generator, enc_noise, variance_noise, size,
                           return_intermediate, cache_interval, texts, glyph, guidance, blend)

@@ -323,7 +323,8 @@ class PasteBlend:
               fully generated and the ramp lies around it - the setting for tight OCR boxes; with grow = 0 the ramp lies INSIDE the box;
     match_color - shift every channel of the patch by the mean difference between the original page and the patch over a ring of
               `ring` pixels around the paste rectangle, at most `max_shift` levels (a mean shift of bytes: no gain, no gamma).
-    PasteBlend() - all off - pastes what blend=None pastes, bit for bit.  Quads are out of scope (edit_quads refuses a blend)."""
+    PasteBlend() - all off - pastes what blend=None pastes, bit for bit.  For boxes only: quads take a QuadBlend, whose ramp is measured
+    perpendicular to the quad's edges (edit_quads refuses a PasteBlend)."""
     __slots__ = ("feather", "grow", "match_color", "ring", "max_shift")
 
     def __init__(self, feather=0, grow=0, match_color=False, ring=8, max_shift=32):
@@ -419,9 +420,7 @@ def _stats_only(bx, image_vae, blend, choice):
     blend = _check_blend(blend)
     B = len(bx.locations)
     S, K = _check_vae(image_vae, B, choice is not None)
-    if choice is not None and not (isinstance(choice, torch.Tensor) and choice.is_cuda and choice.dtype == torch.int32 and choice.is_contiguous()
-                                   and tuple(choice.shape) == (B,)):
-        raise ValueError(f"choice must be a contiguous int32 CUDA tensor [{B}]")
+    _check_choice(choice, B)
     v = image_vae.to(torch.float32).contiguous()
     tables = _upload(bx, S)
     with torch.cuda.device(bx.dev):
@@ -873,14 +872,129 @@ def preprocess_quads(images, quads, frames, size=512, perspective=False):
     return pre
 
 
-def postprocess_quads(image_vae, images, quads, frames, return_mask=False, out=None, perspective=False):
+class QuadBlend:
+    """How the quad pastes put a generated patch onto the page (include/diffute_hip.h above dmx_paste_color_stats_quads; integers
+    throughout).  A pixel's depth m is the smallest of its whole pixel steps inside the quad's four edges, measured PERPENDICULAR to each
+    edge (floor(E_k / |e_k|), exactly), and inside the quad's bounding box; m >= 0 is the quad itself.
+    feather - the width f of the linear ramp: the weight of the patch is min(m + grow + 1, f + 1) / (f + 1), so f = 0 is a hard edge;
+    grow - the paste region is the quad with every edge moved out by g pixels, its mitres cut by the bounding box grown by g, and cut
+              where it leaves the quad's crop (a hard edge there).  With grow >= feather the whole quad is fully generated and the ramp
+              lies around it; with grow = 0 the ramp lies INSIDE the quad;
+    match_color - shift every channel of the patch by the mean difference between the original page and the patch over the ring of
+              `ring` pixels around the paste region, at most `max_shift` levels (a mean shift of bytes: no gain, no gamma).
+    feather, grow <= QUAD_BLEND_MAX = 1024, 1 <= ring <= 1024.  A type of its own, not a PasteBlend: the ramp and the caps differ.
+    QuadBlend() - all off - pastes what blend=None pastes, bit for bit, when every pixel of every quad lies on that quad's crop: here an
+    item whose pixel is off its crop updates nothing and an earlier quad shows through, where the plain paste lets the last covering
+    quad decide and leaves the original byte."""
+    __slots__ = ("feather", "grow", "match_color", "ring", "max_shift")
+
+    def __init__(self, feather=0, grow=0, match_color=False, ring=8, max_shift=32):
+        cap = _cabi.QUAD_BLEND_MAX
+        for name, v, lo, hi in (("feather", feather, 0, cap), ("grow", grow, 0, cap), ("ring", ring, 1, cap), ("max_shift", max_shift, 0, 255)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"QuadBlend: {name} must be an integer, got {v!r}")
+            if not lo <= v <= hi:
+                raise ValueError(f"QuadBlend: {name} = {v}, expected {lo} .. {hi}")
+        if not isinstance(match_color, (bool, np.bool_)):
+            raise TypeError(f"QuadBlend: match_color must be a bool, got {match_color!r}")
+        self.feather, self.grow, self.match_color, self.ring, self.max_shift = int(feather), int(grow), bool(match_color), int(ring), int(max_shift)
+
+    def __repr__(self):
+        return (f"QuadBlend(feather={self.feather}, grow={self.grow}, match_color={self.match_color}, ring={self.ring}, "
+                f"max_shift={self.max_shift})")
+
+    def grown(self, quads, h=None, w=None):
+        """the quads' bounding boxes grown by `grow` - every paste region lies inside its grown bounding box - as half-open
+        [(x1, y1, x2, y2)], clipped to an h x w page if the size is given: what metrics.outside_diff takes to show that nothing outside
+        them changed"""
+        g, out = self.grow, []
+        for quad in quads:
+            c = _corners(quad)
+            x1, y1 = min(x for x, _ in c) - g, min(y for _, y in c) - g
+            x2, y2 = max(x for x, _ in c) + g + 1, max(y for _, y in c) + g + 1
+            if w is not None:
+                x1, x2 = max(x1, 0), min(x2, int(w))
+            if h is not None:
+                y1, y2 = max(y1, 0), min(y2, int(h))
+            out.append((x1, y1, x2, y2))
+        return out
+
+    def _struct(self):
+        return _cabi.PasteBlend(self.feather, self.grow, self.ring, self.max_shift, int(self.match_color))
+
+
+def _check_quad_blend(blend):
+    if isinstance(blend, PasteBlend):
+        raise NotImplementedError("blend: a PasteBlend is not supported for quads (its ramp is measured along the page's axes); pass a QuadBlend")
+    if not isinstance(blend, QuadBlend):
+        raise TypeError(f"blend: expected a QuadBlend or None, got {type(blend).__name__}")
+    return blend
+
+
+def _check_choice(choice, B):
+    if choice is not None and not (isinstance(choice, torch.Tensor) and choice.is_cuda and choice.dtype == torch.int32 and choice.is_contiguous()
+                                   and tuple(choice.shape) == (B,)):
+        raise ValueError(f"choice must be a contiguous int32 CUDA tensor [{B}]")
+
+
+def _blend_paste_quads(qx, image_vae, blend, return_mask, out, scores=None, threshold=None):
+    """the blended quad pastes: [choose ->] [stats ->] paste, every launch on the current stream, ONE table upload, nothing read on the
+    host.  scores given: image_vae is [B,K,3,S,S] and (out, choice[, union]) comes back, as from postprocess_select_quads"""
+    B, select = len(qx.quads), scores is not None
+    S, K = _check_vae(image_vae, B, select)
+    thr = _check_scores(scores, B, K, threshold) if select else None
+    out, union = _page_outputs(qx.images, qx.dev, out, return_mask)
+    v = image_vae.to(torch.float32).contiguous()
+    t, bs = _upload_quads(qx, S, out, union), blend._struct()
+    with torch.cuda.device(qx.dev):
+        choice = _choose(_cabi.lib(), scores, B, K, thr, qx.dev) if select else None
+        stats = None
+        if blend.match_color:
+            stats = torch.empty(B, 4, dtype=torch.int64, device=qx.dev)
+            _call_quads("paste_color_stats_quads", t, (_cabi.ptr(v), S), ctypes.byref(bs), _cabi.ptr(choice), K, _cabi.ptr(stats))
+        _call_quads("postprocess_paste_blend_quads", t, (_cabi.ptr(v), S), ctypes.byref(bs), _cabi.ptr(stats), _cabi.ptr(choice), K)
+    if select:
+        return (out, choice, union) if return_mask else (out, choice)
+    return (out, union) if return_mask else out
+
+
+def paste_color_stats_quads(image_vae, images, quads, frames, blend, choice=None, perspective=False):
+    """The colour statistics the blended quad paste would use, int64 CUDA [N,4] = (n, D_r, D_g, D_b) per quad, D already clamped to
+    +- max_shift * n: over the ring of blend.ring pixels around the quad's paste region (on its crop), of the ORIGINAL page against the
+    quad's own decoder row.  One launch, one block per quad: a quad's numbers are the same alone or in any batch.  images / quads /
+    frames / perspective: as for postprocess_quads.  choice: None - image_vae is [N,3,S,S] -, or int32 CUDA [N] - image_vae is
+    [N,K,3,S,S], quad b reads candidate choice[b], a quad with choice[b] < 0 writes zeros."""
+    blend = _check_quad_blend(blend)
+    if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
+        raise TypeError("image_vae: expected a CUDA tensor")
+    qx = _check_quads(images, quads, _plan_persp(images, quads, frames, perspective, image_vae), perspective)
+    B = len(qx.quads)
+    S, K = _check_vae(image_vae, B, choice is not None)
+    _check_choice(choice, B)
+    v = image_vae.to(torch.float32).contiguous()
+    t, bs = _upload_quads(qx, S), blend._struct()
+    with torch.cuda.device(qx.dev):
+        stats = torch.empty(B, 4, dtype=torch.int64, device=qx.dev)
+        _call_quads("paste_color_stats_quads", t, (_cabi.ptr(v), S), ctypes.byref(bs), _cabi.ptr(choice), K, _cabi.ptr(stats))
+    return stats
+
+
+def postprocess_quads(image_vae, images, quads, frames, return_mask=False, out=None, perspective=False, blend=None):
     """postprocess_pages for quadrilateral regions, in one launch.  image_vae: fp32 CUDA [N,3,S,S] decoder outputs, page-major; the other
     arguments as for preprocess_quads.  Returns the list of P uint8 [h_p][w_p][3] pages: a pixel inside a quad (edges included) and on
     that quad's crop comes from the decoder output through the inverse of the frame - where quads overlap the later one decides -, every
     other pixel is the original's; with return_mask=True also the list of P union masks uint8 [h_p][w_p] (1 inside any quad).  out: as
     for postprocess_pages.  perspective=True: frames are projective (None plans them), and a page pixel finds its crop coordinates
-    through the inverse homography; which pixels are pasted, and the union masks, follow the same rule."""
+    through the inverse homography; which pixels are pasted, and the union masks, follow the same rule.
+    blend: None - the hard paste above, exactly today's code path -, or a QuadBlend: feathered edge and / or colour match ([stats ->]
+    blended paste, one launch each, one table upload).  Every quad is blended over what the quads before it left, in table order; a pixel
+    off a quad's crop is left to the earlier quads; the union masks are then 1 inside any quad GROWN by blend.grow, and the page equals
+    the original wherever the mask is 0."""
+    if blend is not None:
+        blend = _check_quad_blend(blend)
     qx = _check_quads(images, quads, _plan_persp(images, quads, frames, perspective, image_vae), perspective)
+    if blend is not None:
+        return _blend_paste_quads(qx, image_vae, blend, return_mask, out)
     S, _ = _check_vae(image_vae, len(qx.quads), False)
     out, union = _page_outputs(qx.images, qx.dev, out, return_mask)
     v = image_vae.to(torch.float32).contiguous()
@@ -949,17 +1063,24 @@ def readback_pixel_values_quads(image_vae, images, quads, frames, processor, per
     return (out, res) if (return_resized or out_resized is not None) else out
 
 
-def postprocess_select_quads(image_vae, scores, images, quads, frames, threshold=None, return_mask=False, out=None, perspective=False):
+def postprocess_select_quads(image_vae, scores, images, quads, frames, threshold=None, return_mask=False, out=None, perspective=False, blend=None):
     """postprocess_select_pages for quadrilateral regions: choose and paste in ONE launch, without reading the scores on the host.
     image_vae fp32 CUDA [N,K,3,S,S], scores fp32 CUDA [N,K], both page-major; the other arguments as for postprocess_quads.  Returns
     (pages, choice): choice int32 [N] on the device by the rule of postprocess_select_batch, and the list of P pages postprocess_quads
     gives for the chosen rows.  A quad whose best score is below `threshold` (choice -1) is TRANSPARENT: it pastes nothing, and an earlier
-    chosen quad under it still shows.  With return_mask=True also the list of P union masks, 1 inside ANY quad, skipped ones included."""
+    chosen quad under it still shows.  With return_mask=True also the list of P union masks, 1 inside ANY quad, skipped ones included.
+    blend: None - exactly today's code path -, or a QuadBlend: choose (dmx_select_choices) -> [stats ->] blended paste of the chosen rows,
+    one launch each, one table upload and still no score read on the host; pages and masks as postprocess_quads(blend=...) gives them
+    for the chosen rows, a skipped quad updating nothing."""
+    if blend is not None:
+        blend = _check_quad_blend(blend)
     _check_scores_tensor(scores)
     if not (isinstance(image_vae, torch.Tensor) and image_vae.is_cuda):
         raise TypeError("image_vae: expected a CUDA tensor")
     frames = _plan_persp(images, quads, frames, perspective, image_vae.shape[-1])
     qx = _check_quads(images, quads, frames, perspective)
+    if blend is not None:
+        return _blend_paste_quads(qx, image_vae, blend, return_mask, out, scores, threshold)
     B = len(qx.quads)
     S, K = _check_vae(image_vae, B, True)
     thr = _check_scores(scores, B, K, threshold)

@@ -103,6 +103,14 @@ int dmx_test_compose_linear(const void* wpo, const void* wf2, const float* bf2, 
 /* the folded block tail as the UNet walk runs it, on the executor: y (16) [B*HW][C] = [g (16) [B*HW][4C] | h3 (16) [B*HW][C]] wfpo^T + bfpo + x, then
  * t (16) = GroupNorm(y; groups, eps 1e-5, no activation).  mode 0: the GEMM completes y itself; 1: a split-K plan leaves its reduce pass (with bfpo and x)
  * to the GroupNorm; 2: as 1, but x is released before the GroupNorm, which completes y first.  The three give the same bits.  C a multiple of 64. */
+/* the exact integer arithmetic of the quad blend (csrc/prepost_quad_blend.h, stated above dmx_paste_color_stats_quads), host-only, no GPU:
+ * the edge steps s = floor(E / sqrt(ex^2 + ey^2)) of an edge (ex, ey) at edge function E, saturated to [-M, M] - M for an edge of
+ * length 0, which takes part in nothing -, and the threshold of s >= j: the least E with s(E) >= j, by which the kernels know a pixel to
+ * be outside or at full weight.  |ex|, |ey| <= 65535, |E| <= 2^33, 1 <= M <= 2 DMX_QUAD_BLEND_MAX + 2, |j| <= 2 DMX_QUAD_BLEND_MAX + 2, an
+ * edge with length for the threshold; anything else returns LLONG_MIN.  tests/test_quad_blend_host.py compares both with Python ints at
+ * magnitudes no small page reaches. */
+long long dmx_test_quad_edge_steps(int ex, int ey, long long E, int M);
+long long dmx_test_quad_edge_threshold(int ex, int ey, int j);
 size_t dmx_test_folded_tail_gn_workspace_bytes(int B, int HW, int C, int groups, int mode);
 int dmx_test_folded_tail_gn(const void* g, const void* h3, const void* x, const void* wfpo, const float* bfpo, const float* gamma, const float* beta,
                             int B, int HW, int C, int groups, int mode, void* y_out, void* t_out, void* workspace, size_t workspace_bytes, dmx_stream_t stream);
@@ -1137,6 +1145,68 @@ int dmx_postprocess_paste_select_quads_persp(const float* image_vae, int S, cons
                                              const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device,
                                              const dmx_quad_persp* persp_host, const dmx_quad_persp* persp_device, int B, int K,
                                              dmx_stream_t stream);
+
+/* Seam-free paste for quads (prepost_quad_blend.hip): the feathered, colour-matched paste of the box entries above, through a quad's
+ * frame.  The ramp is measured PERPENDICULAR to the quad's edges, in whole steps of one pixel, in integers throughout: no floating-point
+ * value decides a weight, a membership or a sum (a float estimate is corrected by exact integer comparisons).  dmx_paste_blend is
+ * reused; dmx_edit_quad keeps its layout.  Item b is a quad with corners (x_k, y_k), edges (ex_k, ey_k), inclusive bounding box
+ * (bx1, by1, bx2, by2) and L2_k = ex_k^2 + ey_k^2 (64 bits, computed by the kernels).  Per page pixel (X, Y):
+ *   edge function    E_k of csrc/prepost_quad.h, 64 bits.
+ *   edge steps       s_k = floor(E_k / sqrt(L2_k)), exactly: for E_k >= 0 the largest j >= 0 with j^2 L2_k <= E_k^2, for E_k < 0 minus the
+ *           smallest j with j^2 L2_k >= E_k^2; saturated to [-M, M], M = 2 DMX_QUAD_BLEND_MAX + 2.  An edge of length 0 (a degenerate
+ *           corner is accepted, its E is 0) takes part in nothing.
+ *   box steps        t = min(X - bx1, bx2 - X, Y - by1, by2 - Y): negative outside the bounding box.
+ *   depth            m = min(min_k s_k, t).  The plain coverage of the quad pastes is m >= 0; for an axis-aligned quad m is the box
+ *           blend's distance d on the rectangle (x1, y1, x2 + 1, y2 + 1).
+ *   grown coverage   C_b(g) = the page pixels with m >= -g: the quad with every edge moved out by g pixels, its mitres cut by the
+ *           bounding box grown by g - a bounded region, which a block can walk.
+ *   paste region     R_b = C_b(grow) intersected with on_crop_b, the predicate of the plain quad paste (the frame's paste map defined,
+ *           -2^15 <= U16, V16 < (S << 16) - 2^15).  G(X, Y, c) is the byte the plain paste forms at the item's (U16, V16): defined on
+ *           all of on_crop_b.
+ *   colour statistics (match_color): over the ring Q_b = (C_b(grow + ring) \ C_b(grow)) intersected with on_crop_b, of the ORIGINAL
+ *           page and the item's own decoder row: n = |Q_b|, D_c = sum over Q_b of (original - G) in 64-bit integers, clamped to
+ *           [-max_shift n, max_shift n].
+ *   corrected byte   g1 = clamp(G + floor((2 D_c + n) / (2 n)), 0, 255) when match_color and n > 0, else G (floor division).
+ *   weight           F = feather + 1, d = m + grow, a = min(d + 1, F).
+ *   blend            cur' = floor((2 (a g1 + (F - a) cur) + F) / (2 F)).
+ * A page pixel starts as the original byte; the items of its page are scanned in ASCENDING order and every item that is not skipped
+ * (choice[b] >= 0, or no choice table) and has the pixel in its R_b updates cur.  The union mask is 1 where any C_b(grow) covers the
+ * pixel - skipped items and off-crop pixels count -, and out == original wherever it is 0.
+ * A DEVIATION from the plain quad paste: there the LAST covering quad decides, and a pixel off THAT quad's crop is the original byte;
+ * here an item whose pixel is off its crop updates nothing and an earlier item shows through.  So feather = grow = 0 without
+ * match_color equals postprocess_paste_quads[_persp] bit for bit exactly when every pixel of every quad lies on that quad's crop.
+ * Quarter turn: E_k, L2_k, t, U16 and V16 are unchanged when page, quads and frames are turned by 90 degrees, so statistics, pages and
+ * masks of the turned input are the turned outputs, bit for bit.
+ * Integer budget: H, W <= 65535, so |E_k| < 2^33 and L2_k < 2^33; M^2 < 2^23 and M^2 L2_k < 2^56; |E_k| >= 2^31 lies beyond
+ * M sqrt(L2_k) < 2^28 and saturates by its sign alone; below that E_k^2 < 2^62.  Nothing needs 128 bits, and no pixel a 64-bit division:
+ * a float estimate of s_k is corrected by exact comparisons, and only where the pixel is neither known to be outside (E_k below the
+ * exact threshold of s_k >= -grow) nor known to be at full weight (E_k at or above that of s_k >= feather - grow); the thresholds are
+ * exact integer square roots, taken once per staged item and edge.
+ *   paste_color_stats_quads[_persp]: the arguments of postprocess_paste_quads[_persp], then blend, choice, K, stats as for
+ *           paste_color_stats_pages: stats (device, out) [B][4] = n, D_r, D_g, D_b; a skipped item writes four zeros.  One block per
+ *           item: an item's numbers are the same alone or in any batch.
+ *   postprocess_paste_blend_quads[_persp]: the arguments of postprocess_paste_quads[_persp], then blend, stats (NULL without
+ *           match_color), choice and K as for postprocess_paste_blend_pages.  select_choices serves unchanged.
+ * Refused (DMX_ERR_ARG, nothing launched): feather or grow outside 0 .. DMX_QUAD_BLEND_MAX, ring outside 1 .. DMX_QUAD_BLEND_MAX,
+ * max_shift outside 0 .. 255, match_color without stats, K outside 1 .. DMX_SELECT_MAX_CANDIDATES, K > 1 without choice, and whatever
+ * the plain quad entries refuse (a bad page or item named by index).  The kernels clamp what they read from the device tables as the
+ * plain pastes do; a stale table changes bytes inside grown bounding boxes, never an address. */
+#define DMX_QUAD_BLEND_MAX 1024
+int dmx_paste_color_stats_quads(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device, int B, const dmx_paste_blend* blend,
+                                const int* choice, int K, long long* stats, dmx_stream_t stream);
+int dmx_paste_color_stats_quads_persp(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                      const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device, const dmx_quad_persp* persp_host,
+                                      const dmx_quad_persp* persp_device, int B, const dmx_paste_blend* blend, const int* choice, int K,
+                                      long long* stats, dmx_stream_t stream);
+int dmx_postprocess_paste_blend_quads(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                      const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device, int B, const dmx_paste_blend* blend,
+                                      const long long* stats, const int* choice, int K, dmx_stream_t stream);
+int dmx_postprocess_paste_blend_quads_persp(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device,
+                                            int P, const dmx_edit_quad* quads_host, const dmx_edit_quad* quads_device,
+                                            const dmx_quad_persp* persp_host, const dmx_quad_persp* persp_device, int B,
+                                            const dmx_paste_blend* blend, const long long* stats, const int* choice, int K,
+                                            dmx_stream_t stream);
 
 /* Comparing two versions of a set of pages (metrics.hip): what the scene-text-editing literature reports on the edited box - MSE,
  * PSNR, SSIM - and what changed OUTSIDE all boxes.  P pairs of pages a / b, uint8 [H][W][3] contiguous, both of a pair H x W; B boxes
