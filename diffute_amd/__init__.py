@@ -7,7 +7,7 @@ switch with `from diffute_amd import ...`.
 from .models import (AutoencoderKL, UNet2DConditionModel, DiagonalGaussianDistribution, TrOCREncoder,
                      SD2_INPAINT_UNET_CONFIG, SD_VAE_CONFIG, TROCR_LARGE_VIT_CONFIG)
 from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, Guidance, SD2_SCHEDULER_CONFIG
-from .pipeline import denoise, edit_boxes, edit_boxes_verified, edit_latents, edit_pages, edit_pages_verified, edit_quads, edit_quads_verified, mask_to_latent
+from .pipeline import denoise, edit_boxes, edit_boxes_verified, edit_latents, edit_pages, edit_curved, edit_pages_verified, edit_quads, edit_quads_verified, mask_to_latent
 from .inflight import DenoiseEngine
 from .optim import FusedAdamW, GradScaler
 from .training_utils import EMAModel
@@ -19,7 +19,7 @@ from .data import SyntheticDocuments, sample_boxes, training_batch
 from ._cabi import set_exclusive_device, synchronize
 from .prepost import PasteBlend, QuadBlend
 
-__all__ = ["AutoencoderKL", "UNet2DConditionModel", "DDPMScheduler", "DDIMScheduler", "DPMSolverMultistepScheduler", "DenoiseEngine", "Guidance", "denoise", "edit_latents", "edit_boxes", "edit_boxes_verified", "edit_pages", "edit_pages_verified", "edit_quads", "edit_quads_verified",
+__all__ = ["AutoencoderKL", "UNet2DConditionModel", "DDPMScheduler", "DDIMScheduler", "DPMSolverMultistepScheduler", "DenoiseEngine", "Guidance", "denoise", "edit_latents", "edit_boxes", "edit_boxes_verified", "edit_pages", "edit_pages_verified", "edit_quads", "edit_quads_verified", "edit_curved",
            "mask_to_latent", "FusedAdamW", "GradScaler", "EMAModel", "TrOCREncoder", "TrOCRForCausalLM", "VisionEncoderDecoderModel", "TrOCRProcessor", "ViTImageProcessor", "GlyphAtlas", "GlyphRenderer", "glyph_contexts", "SyntheticDocuments", "sample_boxes", "training_batch", "TROCR_LARGE_DECODER_CONFIG", "TROCR_LARGE_VIT_CONFIG", "DiagonalGaussianDistribution", "SD2_INPAINT_UNET_CONFIG", "SD_VAE_CONFIG",
            "SD2_SCHEDULER_CONFIG", "set_exclusive_device", "synchronize", "LoraConfig", "PasteBlend", "QuadBlend"]
 __version__ = "0.1.0"

@@ -54,7 +54,7 @@
 //                                                           final rdiv X16 is within 0.6251 of the exact coordinate * 2^16.
 //   For a 700-pixel line on a 1100 x 1300 page at S = 512: A < 2^53, min D > 2^41.
 //   Limits: the window's centre is NOT moved to keep the window on the page (clamped taps replicate the border); a window beyond the
-//   cap is refused; curved text is out.
+//   cap is refused; a line on an arc is no quad: curved text is prepost_curved.h's, whose affine pieces are maps of this kind.
 #pragma once
 #include "prepost_quad.h"
 

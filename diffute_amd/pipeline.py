@@ -305,7 +305,7 @@ def edit_quads(unet, vae, scheduler, images, quads, encoder_hidden_states, num_i
     planned by prepost.plan_quads(..., perspective=True) where not given.  The crop is taken through the homography that makes the quad an
     upright rectangle, so the network sees the text without keystone, and the paste goes back through its inverse; everything between the
     two launches is the same.  Limits: the window is not moved to stay on the page (the border is replicated), a window over which the
-    homography's denominator changes by more than 4x is refused, curved text is out.
+    homography's denominator changes by more than 4x is refused; a line on an arc is edit_curved's.
 
     blend: None - the hard paste of the quad -, or a prepost.QuadBlend: the paste gets a feathered edge and / or a colour match of every
     patch against the page around it ([stats ->] blended paste on the device, prepost.postprocess_quads(blend=...)).  The ramp is measured
@@ -327,6 +327,46 @@ def edit_quads(unet, vae, scheduler, images, quads, encoder_hidden_states, num_i
     image_vae = _edit_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
                            enc_noise, variance_noise, int(size), cache_interval, guidance)
     out = prepost.postprocess_quads(image_vae, images, quads, frames, perspective=perspective, blend=blend)
+    return (out, image_vae, pre) if return_intermediate else out
+
+
+@torch.no_grad()
+def edit_curved(unet, vae, scheduler, images, polygons, encoder_hidden_states, num_inference_steps, *, frames=None, batch_size=4, generator=None,
+                enc_noise=None, variance_noise=None, return_intermediate=False, size=512, cache_interval=1, texts=None, glyph=None, guidance=None,
+                blend=None):
+    """edit_quads for CURVED text - signs, logos, seals, stamps, labels, arched shop fronts: every region is a polygon of 2n points,
+    2 <= n <= 17, as scene-text OCR gives a curved line (the n top points left to right as read, then the n bottom points right to left).
+    images: a list of P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device; polygons: P lists of polygons; frames: None or P lists
+    of (ci2, cj2, crop_scale) - a square window in the pixels of the polygon's straightened strip -, planned by prepost.plan_curved where
+    not given (deterministic: nothing is drawn).  The polygon is cut into n - 1 quad cells and every cell into two triangles; each
+    triangle goes to the strip by its own affine map, and neighbouring maps agree on the line they share.  So the mask is the polygon
+    itself - what lies inside the arc's chord stays out of it -, the network sees the line STRAIGHT beside its upright glyph image, and
+    the paste puts the result back BENT, without a tear, touching no pixel outside the polygons.
+
+    One preprocess_curved launch, the N rows (page-major) through edit_latents in chunks of `batch_size` exactly as edit_pages sends them
+    (chunks cross page boundaries; every row starts from the seed-0 single-sample draw), one postprocess_curved launch.  Returns the list
+    of P edited pages, with return_intermediate=True also image_vae [N,3,S,S] and the preprocess dict.  encoder_hidden_states / texts /
+    glyph / enc_noise / variance_noise / cache_interval / guidance: as for edit_pages.
+
+    Limits: blend must be None (no blend for curved regions yet: anything else raises NotImplementedError); there is no
+    edit_curved_verified (no fused read-back and select-paste; prepost.rectify_curved gives the straightened strips for an OCR pass of
+    one's own); no fan cells - a point repeated on one side is refused -, and top and bottom carry the same number of points; the window
+    is not moved to stay on the page (the border is replicated)."""
+    if blend is not None:
+        raise NotImplementedError("edit_curved: no blend for curved regions yet (blend must be None)")
+    if int(batch_size) < 1:
+        raise ValueError("batch_size must be at least 1")
+    cache_interval = _check_cache_interval(cache_interval)
+    images, polygons, frames, sizes, N = _quad_lists(images, polygons, frames)
+    _check_contexts(N, encoder_hidden_states, texts, glyph)
+    guidance = _check_guidance(guidance, encoder_hidden_states, N)
+    if frames is None:
+        frames = prepost.plan_curved(polygons, sizes, int(size))
+    encoder_hidden_states = _contexts(encoder_hidden_states, texts, glyph)
+    pre = prepost.preprocess_curved(images, polygons, frames, size=size)
+    image_vae = _edit_rows(unet, vae, scheduler, pre, images[0].device, encoder_hidden_states, num_inference_steps, int(batch_size), generator,
+                           enc_noise, variance_noise, int(size), cache_interval, guidance)
+    out = prepost.postprocess_curved(image_vae, images, polygons, frames)
     return (out, image_vae, pre) if return_intermediate else out
 
 

@@ -1092,3 +1092,219 @@ def postprocess_select_quads(image_vae, scores, images, quads, frames, threshold
     with torch.cuda.device(qx.dev):
         _call_quads("postprocess_paste_select_quads", t, (_cabi.ptr(v), S, _cabi.ptr(sc), thr, _cabi.ptr(choice)), K)
     return (out, choice, union) if return_mask else (out, choice)
+
+
+# ------------------------------------------------------------------------------------------------ curved regions, piecewise-affine maps
+# (csrc/prepost_curved.hip; the arithmetic is stated in csrc/prepost_curved.h).  A curved region is a polygon of 2n points (x, y),
+# 2 <= n <= 17, as scene-text OCR gives a curved line: the n top points left to right as read, then the n bottom points right to left,
+# clockwise with y down.  A frame is the projective quads': (ci2, cj2, crop_scale), the window's centre in half-pixels of the
+# straightened strip's pixel-index space and its side in strip pixels.
+def _polygon(polygon):
+    """a polygon as given - 2n x (x, y) or 4n numbers - -> [[x, y]] * 2n of ints"""
+    c = np.asarray(polygon).reshape(-1)
+    if c.size % 2 != 0 or (c.size // 2) % 2 != 0:
+        raise ValueError(f"a curved region is 2n points (x, y) - n on top as read, then n on the bottom backwards; got {c.size} numbers: an odd point count")
+    n = c.size // 4
+    if not 2 <= n <= _cabi.CURVED_MAX_PAIRS:
+        raise ValueError(f"a curved region has 2 .. {_cabi.CURVED_MAX_PAIRS} point pairs, got {n}")
+    return [[int(c[2 * k]), int(c[2 * k + 1])] for k in range(2 * n)]
+
+
+def strip_size_curved(polygon):
+    """(rw, rh) of the polygon's straightened strip (csrc/prepost_curved.h): cell k is w_k = max(1, rn(|u_k| / 2)) columns long,
+    u_k = (T_k+1 - T_k) + (B_k+1 - B_k), and rw = sum of w_k, plus 1; rh = rn(the mean length of the n segments T_k B_k) + 1.  For a
+    parallelogram given as four points this is strip_size(quad)."""
+    p = _polygon(polygon)
+    n = len(p) // 2
+    rw, total = 1, np.float64(0.0)
+    for k in range(n):
+        dx, dy = p[2 * n - 1 - k][0] - p[k][0], p[2 * n - 1 - k][1] - p[k][1]
+        total = total + np.sqrt(np.float64(dx * dx + dy * dy))
+        if k < n - 1:
+            ux = (p[k + 1][0] - p[k][0]) + (p[2 * n - 2 - k][0] - p[2 * n - 1 - k][0])
+            uy = (p[k + 1][1] - p[k][1]) + (p[2 * n - 2 - k][1] - p[2 * n - 1 - k][1])
+            rw += max(1, _rn(np.sqrt(np.float64(ux * ux + uy * uy)) / 2.0))
+    return rw, _rn(total / np.float64(n)) + 1
+
+
+def curved_frame_accepted(polygon, h, w, frame, size=512):
+    """None if the C side (host-only: dmx_edit_curved_prepare) accepts the frame (ci2, cj2, crop_scale) of `polygon` on an h x w page at
+    crop size `size`, else its message"""
+    p = _polygon(polygon)
+    M = len(p) // 2 - 1
+    pages, host, pieces = (_cabi.EditPage * 1)(), (_cabi.EditCurved * 1)(), (_cabi.CurvedPiece * (2 * M))()
+    pages[0].original, pages[0].H, pages[0].W, pages[0].item_lo, pages[0].item_hi = 64, int(h), int(w), 0, 1
+    for k, (x, y) in enumerate(p):
+        host[0].x[k], host[0].y[k] = x, y
+    host[0].count = len(p)
+    host[0].ci2, host[0].cj2, host[0].crop_scale = (int(v) for v in frame)
+    lib = _cabi.lib()
+    if lib.dmx_edit_curved_prepare(pages, 1, host, pieces, 1, int(size)) != 0:
+        return lib.dmx_last_error().decode()
+    return None
+
+
+def curved_frame_for(polygon, h, w, size=512):
+    """The frame of one curved region on an h x w page -> (ci2, cj2, crop_scale), integers, no rng: the window the network sees is a
+    square of side crop_scale in the pixels of the polygon's straightened rw x rh strip, centred on the strip - (rw - 1, rh - 1)
+    half-pixels -, with crop_scale the ladder crop_scale_for applied to (rw, rh) as persp_frame_for applies it.  ValueError, naming the
+    polygon and with the C side's reason, where dmx_edit_curved_prepare refuses the polygon or that window.
+    Limit: the centre is NOT moved to keep the window on the page; where the window overhangs, clamped taps replicate the border."""
+    p = _polygon(polygon)
+    rw, rh = strip_size_curved(p)
+    frame = (rw - 1, rh - 1, max(1, int(crop_scale_for((0, 0, rw, rh), h, w))))
+    why = curved_frame_accepted(p, h, w, frame, size)
+    if why is not None:
+        raise ValueError(f"no frame for the curved region {p} on a {w}x{h} page: {why}")
+    return frame
+
+
+def plan_curved(polygons_per_page, sizes, size=512):
+    """curved_frame_for for every polygon of every page: polygons_per_page is a list of P lists of polygons, sizes the pages' (h, w).
+    Returns P lists of frames (ci2, cj2, crop_scale), for crops of `size`.  Deterministic: nothing is drawn."""
+    polygons_per_page, sizes = list(polygons_per_page), list(sizes)
+    if len(polygons_per_page) != len(sizes):
+        raise ValueError(f"{len(polygons_per_page)} lists of polygons, {len(sizes)} page sizes: the lengths must agree")
+    return [[curved_frame_for(q, int(h), int(w), size) for q in polys] for polys, (h, w) in zip(polygons_per_page, sizes)]
+
+
+_Curved = collections.namedtuple("_Curved", "images dev polygons frames counts")
+
+
+def _check_curved(images, polygons, frames):
+    """the list half of the curved functions' arguments, checked before any tensor is looked at; frames None (rectify_curved): no frames"""
+    images, polygons = list(images), [list(q) for q in polygons]
+    P = len(images)
+    if P == 0:
+        raise ValueError("no pages: the curved pre/post-processing needs at least one")
+    if P > _cabi.EDIT_MAX_ITEMS:
+        raise ValueError(f"{P} pages in one launch, at most {_cabi.EDIT_MAX_ITEMS}")
+    if len(polygons) != P:
+        raise ValueError(f"{P} pages, {len(polygons)} lists of polygons: the lengths must agree")
+    if frames is not None:
+        frames = [list(f) for f in frames]
+        if len(frames) != P:
+            raise ValueError(f"{P} pages, {len(frames)} lists of frames: the lengths must agree")
+    flat_q, flat_f, counts = [], [], []
+    for p in range(P):
+        if not polygons[p]:
+            raise ValueError(f"page {p}: no polygons; every page needs at least one")
+        if frames is not None and len(frames[p]) != len(polygons[p]):
+            raise ValueError(f"page {p}: {len(polygons[p])} polygons, {len(frames[p])} frames: the lengths must agree")
+        flat_q.extend(_polygon(q) for q in polygons[p])
+        for j, f in enumerate(frames[p] if frames is not None else [(0, 0, 0)] * len(polygons[p])):
+            if f is None or len(f) != 3:
+                raise ValueError(f"page {p}: polygon {j}: a frame is (ci2, cj2, crop_scale)")
+            flat_f.append(tuple(int(v) for v in f))
+        counts.append(len(polygons[p]))
+    if len(flat_q) > _cabi.EDIT_MAX_ITEMS:
+        raise ValueError(f"{len(flat_q)} polygons in one launch, at most {_cabi.EDIT_MAX_ITEMS}")
+    cells = sum(len(q) // 2 - 1 for q in flat_q)
+    if cells > _cabi.CURVED_MAX_CELLS:
+        raise ValueError(f"{cells} cells in one launch, at most {_cabi.CURVED_MAX_CELLS}")
+    return _Curved(images, _check_page_images(images), flat_q, flat_f, counts)
+
+
+_CurvedTables = collections.namedtuple("_CurvedTables", "host pages pieces stage dbuf off xoff")
+
+
+def _upload_curved(cx, S, out=None, union=None):
+    """the tables of one curved launch - dmx_edit_curved | dmx_edit_page | dmx_curved_piece - in ONE pinned staging buffer, filled and
+    validated (dmx_edit_curved_prepare), then ONE asynchronous copy on the current stream.  S = 0 (rectify_curved): the strips alone,
+    which depend neither on the frames nor on S.  Returns a _CurvedTables: the host tables, the pinned storage, the device buffer, the
+    byte offsets of the page table and of the piece table in it."""
+    B, P = len(cx.polygons), len(cx.images)
+    NP = sum(len(q) - 2 for q in cx.polygons)
+    off = B * ctypes.sizeof(_cabi.EditCurved)
+    xoff = off + P * ctypes.sizeof(_cabi.EditPage)
+    total = xoff + NP * ctypes.sizeof(_cabi.CurvedPiece)
+    stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+    st = stage.numpy()
+    st[:] = 0
+    host, pages = (_cabi.EditCurved * B).from_buffer(st[:off]), (_cabi.EditPage * P).from_buffer(st[off:xoff])
+    pieces = (_cabi.CurvedPiece * NP).from_buffer(st[xoff:total])
+    lo = 0
+    for p, (pg, img, n) in enumerate(zip(pages, cx.images, cx.counts)):
+        pg.original = img.data_ptr()
+        pg.out = out[p].data_ptr() if out is not None else 0
+        pg.union_mask = union[p].data_ptr() if union is not None else 0
+        pg.H, pg.W, pg.item_lo, pg.item_hi = int(img.shape[0]), int(img.shape[1]), lo, lo + n
+        for it, c, f in zip(host[lo:lo + n], cx.polygons[lo:lo + n], cx.frames[lo:lo + n]):
+            for k, (x, y) in enumerate(c):
+                it.x[k], it.y[k] = x, y
+            it.count, it.page = len(c), p
+            it.ci2, it.cj2, it.crop_scale = f
+        lo += n
+    _cabi.check(_cabi.lib().dmx_edit_curved_prepare(pages, P, host, pieces, B, S), "edit_curved_prepare")
+    with torch.cuda.device(cx.dev):
+        dbuf = torch.empty(total, dtype=torch.uint8, device=cx.dev)
+        dbuf.copy_(stage, non_blocking=True)                          # the one H2D copy
+    return _CurvedTables(host, pages, pieces, stage, dbuf, off, xoff)
+
+
+def _call_curved(name, t, head, *tail):
+    """dmx_<name>(*head, the tables of t - host and device: pages, items, pieces -, B, *tail, stream) on the current stream"""
+    base = t.dbuf.data_ptr()
+    _cabi.check(getattr(_cabi.lib(), "dmx_" + name)(*head, t.pages, base + t.off, len(t.pages), t.host, base, t.pieces, base + t.xoff, len(t.host),
+                                                    *tail, _cabi.current_stream()), name)
+
+
+def _plan_curved(images, polygons, frames, size):
+    """the frames where a call left them open (frames None), planned here; size: the crop size, or the decoder outputs whose last
+    dimension it is"""
+    if frames is not None:
+        return frames
+    S = size if isinstance(size, (int, np.integer)) else size.shape[-1]
+    return plan_curved([list(q) for q in polygons], [(int(i.shape[0]), int(i.shape[1])) for i in images], int(S))
+
+
+def _no_curved_blend(blend, who):
+    if blend is not None:
+        raise NotImplementedError(f"{who}: no blend for curved regions yet (blend must be None); the hard paste of the polygon is what there is")
+
+
+def preprocess_curved(images, polygons, frames, size=512):
+    """preprocess_quads for curved regions, in one launch.  images: P contiguous uint8 CUDA [h_p][w_p][3] tensors on one device; polygons:
+    P lists of polygons (2n points: top as read, then bottom backwards); frames: P lists of (ci2, cj2, crop_scale) (plan_curved gives
+    them; None plans them here).  Returns the dict preprocess_quads returns, N rows page-major: row b is polygon b's window with the line
+    STRAIGHT - every crop pixel goes to the page through the affine piece of its column band of the strip -, masked_image with the
+    polygon (the union of its cells) blacked out before resampling, mask the polygon as seen in the crop."""
+    S = int(size)
+    cx = _check_curved(images, polygons, _plan_curved(images, polygons, frames, S))
+    t = _upload_curved(cx, S)
+    with torch.cuda.device(cx.dev):
+        pre = _crop_outputs(len(cx.polygons), S, cx.dev)
+        _call_curved("preprocess_curved", t, (), S, *map(_cabi.ptr, pre.values()))
+    return pre
+
+
+def postprocess_curved(image_vae, images, polygons, frames, return_mask=False, out=None, blend=None):
+    """postprocess_quads for curved regions, in one launch.  image_vae: fp32 CUDA [N,3,S,S] decoder outputs, page-major; the other
+    arguments as for preprocess_curved.  Returns the list of P uint8 [h_p][w_p][3] pages: a pixel inside a polygon (some cell covers it,
+    edges included) and on that polygon's crop comes from the decoder output through the inverse of the piece it lies in - the result is
+    put back BENT; where polygons overlap the later one decides -, every other pixel is the original's; with return_mask=True also the
+    list of P union masks uint8 [h_p][w_p] (1 inside any polygon).  out: as for postprocess_pages.
+    blend: must be None - there is no blend for curved regions yet; anything else raises NotImplementedError."""
+    _no_curved_blend(blend, "postprocess_curved")
+    cx = _check_curved(images, polygons, _plan_curved(images, polygons, frames, image_vae))
+    S, _ = _check_vae(image_vae, len(cx.polygons), False)
+    out, union = _page_outputs(cx.images, cx.dev, out, return_mask)
+    v = image_vae.to(torch.float32).contiguous()
+    t = _upload_curved(cx, S, out, union)
+    with torch.cuda.device(cx.dev):
+        _call_curved("postprocess_paste_curved", t, (_cabi.ptr(v), S))
+    return (out, union) if return_mask else out
+
+
+def rectify_curved(images, polygons):
+    """Every curved region as an upright, STRAIGHT strip, in one launch: a list of N uint8 CUDA [h_b][w_b][3] tensors, page-major, views
+    of ONE buffer - what TrOCRProcessor(images=...) accepts on the device, so the OCR model can read a line on an arc.  (w_b, h_b) is
+    strip_size_curved(polygon); an axis-aligned rectangle given as four points gives page[y1:y2+1, x1:x2+1].  No frame is needed."""
+    cx = _check_curved(images, polygons, None)
+    t = _upload_curved(cx, 0)                                          # (the strips depend neither on the frames nor on S)
+    last = t.host[len(t.host) - 1]
+    total = int(last.rect_off) + int(last.rw) * int(last.rh) * 3
+    with torch.cuda.device(cx.dev):
+        buf = torch.empty(total, dtype=torch.uint8, device=cx.dev)
+        _call_curved("rectify_curved", t, (), _cabi.ptr(buf), total)
+    return [buf[int(q.rect_off):int(q.rect_off) + int(q.rw) * int(q.rh) * 3].view(int(q.rh), int(q.rw), 3) for q in t.host]

@@ -1208,6 +1208,67 @@ int dmx_postprocess_paste_blend_quads_persp(const float* image_vae, int S, const
                                             const dmx_paste_blend* blend, const long long* stats, const int* choice, int K,
                                             dmx_stream_t stream);
 
+/* CURVED text: polygon regions straightened by piecewise-affine maps (prepost_curved.hip; the arithmetic is stated in
+ * csrc/prepost_curved.h).  An item is a dmx_edit_curved: a polygon of 2n points, 2 <= n <= DMX_CURVED_MAX_PAIRS, in the order scene-text
+ * OCR gives a curved line - the n top points left to right as read, then the n bottom points right to left; clockwise with y down.
+ * Point pair k is T_k = p[k], B_k = p[2n - 1 - k]; CELL k = 0 .. M - 1, M = n - 1, is the quad T_k, T_k+1, B_k+1, B_k, and the region is the
+ * union of its cells: a pixel is inside iff the quad predicate (csrc/prepost_quad.h, edges included) holds for some cell.  The same
+ * predicate decides mask and paste.  The straightened strip is rw x rh with pair k at column c_k (T_k at (c_k, 0), B_k at (c_k, rh - 1));
+ * every cell is cut by the diagonal T_k+1 - B_k into PIECES 2k = (T_k, T_k+1, B_k) and 2k + 1 = (T_k+1, B_k+1, B_k), and a piece is the
+ * affine map that takes its strip triangle to its page triangle - continuous across every shared line, so the paste does not tear.  The
+ * frame is the projective entries': a square window of side crop_scale STRIP pixels centred at (ci2 / 2, cj2 / 2) in the strip's
+ * pixel-index space.  A piece holds the three maps of a dmx_quad_persp as dmx_persp_map, with t6 = t7 = 0; the table of dmx_curved_piece is
+ * ordered by item, then piece: item b owns [piece_lo, piece_lo + pieces), pieces = 2M.  For n = 2 on a parallelogram every piece holds
+ * the maps dmx_edit_quads_persp_prepare fills for the same quad and frame.
+ *   edit_curved_prepare (host-only): validates pages, items and frames, fills the derived fields of all three tables.  S = 0 fills the
+ *           strip maps alone (the frames are not looked at), which is all rectify_curved reads.  Refuses, by page or item index, naming
+ *           the cell: an odd point count, or n outside 2 .. DMX_CURVED_MAX_PAIRS; a cell that
+ *           is not convex, not clockwise or has no area; a point outside the page; rh < 2, rw or rh beyond 2^20; a frame without
+ *           crop_scale (0) or with crop_scale beyond 65535 or a centre beyond +-2^20; a piece whose maps leave the budget of
+ *           csrc/prepost_persp.h over the crop window, the strip or its cell; B or P outside 1 .. DMX_EDIT_MAX_ITEMS; more than
+ *           DMX_CURVED_MAX_CELLS cells in the launch; what edit_quads_prepare refuses about the page table.
+ *   preprocess_curved: the four outputs of preprocess_quads, row b from item b's window: a crop pixel takes the piece of its column band
+ *           and its side of the diagonal; a page tap is blacked out (and counts in the mask) iff some cell of the item covers it.
+ *   postprocess_paste_curved: the outputs of postprocess_paste_quads.  The items of a page are scanned last to first - the later item
+ *           decides -, within an item the first covering cell is taken, then the piece by the sign of the diagonal's edge function
+ *           (>= 0: piece 2k); the pixel is pasted iff it lies on the crop under that piece's paste map; every other pixel is copied.
+ *   rectify_curved: item b's strip uint8 [rh][rw][3] at out + rect_off, packed in item order; out_bytes >= the last strip's end.
+ * Each entry is one launch; each checks the host tables again (stale derived fields are refused, a bad page or item is named by index,
+ * nothing is launched); the kernels clamp what they read from the device tables: taps to the page, n, page index, item, cell and piece
+ * ranges to the tables, strip writes to out_bytes, and paste nothing where a map is not defined.
+ * Limits: no fused read-back / select-paste and no blend for curved regions; no fan cells (a repeated point gives a piece without area: refused);
+ * top and bottom carry the same number of points. */
+#define DMX_CURVED_MAX_PAIRS 17
+#define DMX_CURVED_MAX_CELLS 512
+typedef struct dmx_edit_curved {
+  int x[34], y[34];                 /* the polygon: n top points as read, then n bottom points backwards; the rest is 0 */
+  int count;                        /* the number of points, 2n */
+  int page;                         /* index of the item's page */
+  int ci2, cj2;                     /* the window's centre in half-pixels of the strip's pixel-index space */
+  int crop_scale;                   /* the window's side in strip pixels */
+  int rw, rh;                       /* derived: size of the straightened strip */
+  int c[17];                        /* derived: column of pair k in the strip, c[0] = 0, c[n - 1] = rw - 1; the rest is 0 */
+  int bx1, by1, bx2, by2;           /* derived: bounding box of the polygon, both corners included */
+  int piece_lo, pieces;             /* derived: the item's pieces in the piece table, 2 (n - 1) of them; its cells are piece_lo / 2 .. */
+  int rect_block_lo, rect_blocks;   /* derived: the strip's blocks in the rectify grid, rh * ceil(rw / 256) of them */
+  long long rect_off;               /* derived: byte offset of the strip in the rectify output */
+} dmx_edit_curved;
+typedef struct dmx_curved_piece {
+  int cx2, cy2;                     /* derived: the page-side centre in half-pixels, the origin of the paste map's grid */
+  dmx_persp_map crop, paste, strip; /* derived: crop grid -> page, page -> crop, strip grid -> page */
+} dmx_curved_piece;
+int dmx_edit_curved_prepare(dmx_edit_page* pages, int P, dmx_edit_curved* items, dmx_curved_piece* pieces, int B, int S);
+int dmx_preprocess_curved(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_curved* items_host,
+                          const dmx_edit_curved* items_device, const dmx_curved_piece* pieces_host, const dmx_curved_piece* pieces_device, int B,
+                          int S, float* out_image, float* out_masked_image, unsigned char* out_mask, float* out_mask_latent,
+                          dmx_stream_t stream);
+int dmx_postprocess_paste_curved(const float* image_vae, int S, const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P,
+                                 const dmx_edit_curved* items_host, const dmx_edit_curved* items_device, const dmx_curved_piece* pieces_host,
+                                 const dmx_curved_piece* pieces_device, int B, dmx_stream_t stream);
+int dmx_rectify_curved(const dmx_edit_page* pages_host, const dmx_edit_page* pages_device, int P, const dmx_edit_curved* items_host,
+                       const dmx_edit_curved* items_device, const dmx_curved_piece* pieces_host, const dmx_curved_piece* pieces_device, int B,
+                       unsigned char* out, long long out_bytes, dmx_stream_t stream);
+
 /* Comparing two versions of a set of pages (metrics.hip): what the scene-text-editing literature reports on the edited box - MSE,
  * PSNR, SSIM - and what changed OUTSIDE all boxes.  P pairs of pages a / b, uint8 [H][W][3] contiguous, both of a pair H x W; B boxes
  * (page, x1, y1, x2, y2), each the slice [y1:y2, x1:x2] of its page: exclusive upper corner, non-empty, inside the page (the read-back's
